@@ -21,6 +21,12 @@ frame k+1): `ms_per_displayed_frame` = loop time / frames handed over, with the 
 `single_frame_launches` repeats the strict per-frame figure under one name whatever the timed mode is, so the 1/2/4/8 curve can
 be read from one key; `n_ranks_seen` is the size of the communicator the collectives ran on (RCCL's for backend nccl).
 
+A plain run sets up, warms up, times the K frames and prints the line.  Everything measured after the timed region — the other
+schedules, the displayed-frame loop, the isolated single-stream frames behind the per-kernel figures and the CPU baseline — runs
+only with `--full` (their keys are null or absent without it).  `--dump-outputs DIR` writes the buffers of the last timed frame
+(accum and frame, float32, DIR/<name>.npy; rank 0's when N>1) right after the timed region, a fixed pixel sample of them when
+they would exceed DUMP_BUDGET_BYTES together.
+
 `python3 bench.py --gpus N` without a launcher starts its own N ranks: N child processes of this script with
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, spawned BEFORE this process imports torch or loads the
 HIP library (a process that has touched the GPU is never re-executed); rank 0's JSON line is relayed, the exit status is the
@@ -69,6 +75,7 @@ BYTES_PER_PIXEL_FRAME = 84           # 16 B accum read + (16*4 + 4) B written pe
 BYTES_PER_RADIANCE_RAY_TRACE = 48    # traversal stage alone: read ray 32 B + write hit 16 B
 BYTES_PER_SHADOW_RAY_TRACE = 36      # read ray 32 B + write 4 B
 FLOPS_PER_HIT = 700                  # 2 x BSDFEval + 2 x BSDFPdf + BSDFSample + hit setup
+DUMP_BUDGET_BYTES = 60_000_000       # --dump-outputs: .npy data of one run, all files together
 
 
 def _strip_comments(text):
@@ -109,12 +116,33 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes every (H, W, C) array of `arrays` as out_dir/<name>.npy in float32.  When they would take more than `budget` bytes
+    together, every array is cut to the same fixed, seeded sample of pixels — shape (k, C), pixel order — so that two runs with the
+    same arguments write comparable files.  Returns (pixels written, pixels of the image)."""
+    arrays = {name: np.ascontiguousarray(a, np.float32) for name, a in arrays.items()}
+    h, w = next(iter(arrays.values())).shape[:2]
+    n_px = h * w
+    px_bytes = sum(a.nbytes // n_px for a in arrays.values())
+    k = n_px
+    if n_px * px_bytes > budget:
+        k = (budget - 4096) // px_bytes  # (a .npy header is 128 bytes)
+        idx = np.sort(np.random.default_rng(0).choice(n_px, k, replace=False))
+        arrays = {name: a.reshape(n_px, -1)[idx] for name, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return k, n_px
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c3_terrain1M_1080p_4spp_d8", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure the other schedules, the displayed-frame loop (N>1), the isolated per-kernel frames and the CPU baseline (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the accum and frame buffers of the last timed frame as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--depth", type=int, default=0, help="experiments only: override the workload's depth limit (the metric's is 8); the line then says so in config.max_depth")
     ap.add_argument("--no-isolated", action="store_true", help="skip the extra single-stream frames that give per-kernel (non-overlapped) durations")
@@ -135,6 +163,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true", help="ranks only join the process group, all-reduce their rank, gather one record per rank and print {n_ranks_seen, ranks}: tests the self-launcher without a GPU")
     ap.add_argument("--launch-render", action="store_true", help="with --launch-check (implied by --backend nccl): every rank also creates a renderer on its device, renders its share of C1 (Cornell box, 256x256, 1 spp, depth 4) and the checksums of the shares are gathered and compared with rank 0's render of the whole frame — first contact with N devices in seconds")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # nothing GPU-related has been imported yet
@@ -284,12 +314,16 @@ def main():
     if not per_frame_stats:  # per-launch-chain figures of the LAST chain only, scaled to the loop (the frames differ only by their random numbers)
         agg = {key: st[key] * n_chains for key in keys}
     next_sub = warm + args.steps
+    if args.dump_outputs and rank == 0:  # before anything else renders into the buffers
+        frame = r.downloadPixels()
+        k_px, n_px = dump_outputs(args.dump_outputs, {"accum": r.download(R.PT_BUF_ACCUM), "frame": frame.view(np.uint8).reshape(frame.shape + (4,))})
+        print(f"[bench] outputs of the last timed frame: {k_px} of {n_px} pixels in {args.dump_outputs}", file=sys.stderr)
 
     # Other schedules of the same frames, for the record (after the timed region, never part of `value`; same images bit for bit):
     # three whole frames in flight, and — on a partitioned frame — wavefront batches of as many subframes as there are shares
     # (a 1/N share x N subframes per launch chain carries the rays of one whole frame)
     extra = {}
-    if not args.no_extra_schedules and not sv4 and not args.kernel_timing:
+    if args.full and not args.no_extra_schedules and not sv4 and not args.kernel_timing:
         n_x = max(6, min(args.steps, 30))
         if not pipelined:
             r.setOptions(**dict(opts, frames_in_flight=3))
@@ -352,7 +386,7 @@ def main():
     # scatter into the display buffer — with the exchange of chain k overlapping the rendering of chain k+1 (multigpu.HandOff over
     # pt_pack_async / pt_unpack_display; whole frames in flight, so the context's own stream is free for the hand-off)
     gather_ms = ms_displayed = None
-    if dist is not None:
+    if dist is not None and args.full:
         from optixpathtracer_amd import multigpu
 
         packer = multigpu.DevicePacker(r)
@@ -403,7 +437,7 @@ def main():
     # HIP-event sums include time spent sharing the machine.  A few extra frames with ONE chunk stream give durations that
     # add up to the frame (rank 0, N=1 only; not part of `value`).
     iso = None
-    if world == 1 and not args.no_isolated and not sv4 and args.streams == 0:
+    if args.full and world == 1 and not args.no_isolated and not sv4 and args.streams == 0:
         r.setOptions(**dict(opts, streams=1, kernel_timing=1, frames_in_flight=0))
         n_iso = 3
         render_frame(0)
@@ -544,7 +578,7 @@ def main():
                 "shade": shade, "valu": valu, "valu_replayed_from": replayed if valu is not None else None, "src_hash": shash,
             },
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(model, probe, cam, w, h, spp, depth, r.exportBVH())
         print(json.dumps(out), flush=True)
     if dist is not None:

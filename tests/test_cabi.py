@@ -118,6 +118,35 @@ def test_bench_source_hash_ignores_comments_only():
             pytest.skip(f"{os.path.relpath(path, ROOT)} was measured on other kernel sources (re-run tools/r4_final.sh to quote its numbers)")
 
 
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: the buffers as float32 .npy files, whole while they fit the budget; above it every file holds the
+    same seeded sample of pixels (in pixel order, the same from call to call) and all files together stay within the budget."""
+    import bench
+
+    rng = np.random.default_rng(5)
+    accum = rng.random((90, 160, 4), dtype=np.float32)
+    frame = rng.integers(0, 256, (90, 160, 4)).astype(np.uint8)
+    arrays = {"accum": accum, "frame": frame}
+    assert bench.dump_outputs(str(tmp_path / "whole"), arrays) == (90 * 160, 90 * 160)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    budget = 100_000
+    runs = []
+    for d in ("s1", "s2"):
+        k, n = bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+        assert n == 90 * 160 and 0 < k < n
+        assert sum(os.path.getsize(tmp_path / d / f"{name}.npy") for name in arrays) <= budget
+        runs.append({name: np.load(tmp_path / d / f"{name}.npy") for name in arrays})
+    for name in arrays:
+        assert runs[0][name].dtype == np.float32 and runs[0][name].shape == (k, 4) and np.array_equal(runs[0][name], runs[1][name])
+    # the rows are pixels of the image, in pixel order, and both files sample the same pixels
+    flat = accum.reshape(-1, 4)
+    idx = np.array([int(np.flatnonzero((flat == row).all(1))[0]) for row in runs[0]["accum"]])
+    assert (np.diff(idx) > 0).all()
+    assert np.array_equal(runs[0]["frame"], frame.reshape(-1, 4)[idx].astype(np.float32))
+
+
 def test_reference_main_cpp_statements_compile_against_the_facade(tmp_path):
     """What the reference's application does with its renderer (HelloPathtracing_original/main.cpp:131-144 initLaunchParams, :211-218
     construction / setCamera / resize / setProbe, :245 output_buffer.setStream(sample.stream), :259 and :286 subframe_index, :262 resize,

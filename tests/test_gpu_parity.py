@@ -1597,8 +1597,8 @@ def test_async_shadow_schedule_matches_oracle(ptlib, orc_det, small_probe):
 
 
 def test_bench_line_contract(ptlib):
-    """bench.py as the driver runs it (one process, default workload, few steps): ONE JSON line with the contract's keys, the
-    metric's configuration, a roofline and a CPU-baseline object, and figures that are consistent with each other."""
+    """bench.py --full (one process, default workload, few steps): ONE JSON line with the contract's keys, the metric's
+    configuration, a roofline and a CPU-baseline object, and figures that are consistent with each other."""
     import json
     import os
     import subprocess
@@ -1606,7 +1606,7 @@ def test_bench_line_contract(ptlib):
 
     from conftest import ROOT
 
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2"], capture_output=True, text=True, timeout=400)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full"], capture_output=True, text=True, timeout=400)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -1635,6 +1635,57 @@ def test_bench_line_contract(ptlib):
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "Mrays/s" and cb["cores"] >= 1 and cb["value"] > 0 and isinstance(cb["sample"], str)
     assert cb["single_thread"]["cores"] == 1 and 0 < cb["single_thread"]["value"] <= cb["value"] * 1.05
+
+
+def test_bench_plain_line_and_dumped_outputs(ptlib, tmp_path):
+    """bench.py without --full (C1, few steps): the contract's keys, none of the figures that take runs of their own, and with
+    --dump-outputs the accum and frame buffers of the last timed frame — equal, bit for bit, to the same subframes rendered here, and
+    the same from a second run with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+    from optixpathtracer_amd import renderer as R
+
+    steps = 3
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--workload", "c1_cornell_256_1spp_d4",
+                              "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [l for l in res.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, res.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        # value = rays / time of the timed frames.  A C1 step takes a fraction of a millisecond, so the line's ms_per_step (rounded to
+        # 0.001 ms) carries a relative rounding error of up to 0.0005 / ms_per_step; fps (0.01 frames/s) pins the same ratio more finely
+        assert abs(d["value"] - d["rays_per_frame"] * d["fps"] / 1e6) / d["value"] < 1e-3
+        assert abs(d["value"] - d["rays_per_frame"] / d["ms_per_step"] / 1e3) / d["value"] < 1e-3 + 0.0005 / d["ms_per_step"]
+        assert abs(d["ms_per_step"] - 1e3 / d["fps"]) <= 0.0005 + 1e-3 * d["ms_per_step"]
+        assert "cpu_baseline" not in d and d["mrays_per_s_pipelined"] is None and d["kernel_ms_per_frame_isolated"] is None
+        dumps.append((d["schedule"]["warmup_frames"], np.load(out / "accum.npy"), np.load(out / "frame.npy")))
+    for warm, accum, frame in dumps:
+        assert accum.dtype == np.float32 and accum.shape == (256, 256, 4) and frame.dtype == np.float32 and frame.shape == (256, 256, 4)
+    assert dumps[0][0] == dumps[1][0]
+    assert_bits_equal(dumps[0][1], dumps[1][1], "accum of two runs")
+    assert np.array_equal(dumps[0][2], dumps[1][2])
+    # the progressive loop up to the last timed subframe, rendered here with the workload's settings
+    w = h = 256
+    r = R.SampleRenderer(scenes.cornell_box())
+    r.setProbe(scenes.sky_probe(2048, 1024).BuildCDF())
+    r.setOptions(max_depth=4)
+    r.resize((w, h))
+    r.setCamera(R.make_camera(scenes.CORNELL_CAMERA, w / h))
+    r.launchParams.samples_per_launch = 1
+    for sf in range(dumps[0][0] + steps):
+        r.launchParams.frame.subframe_index = sf
+        r.render()
+    assert_bits_equal(dumps[0][1], r.download(R.PT_BUF_ACCUM), "dumped accum vs the same subframes")
+    assert np.array_equal(dumps[0][2], r.downloadPixels().view(np.uint8).reshape(h, w, 4).astype(np.float32))
+    r.close()
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])

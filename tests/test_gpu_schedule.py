@@ -193,7 +193,7 @@ def test_bench_multi_gpu_code_path_runs_over_rccl_with_one_rank():
     from conftest import ROOT
 
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-isolated",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-isolated",
                           "--workload", "c2_cornell_1080p_4spp_d8"], capture_output=True, text=True, timeout=400, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.strip()][-1])
@@ -214,7 +214,7 @@ def test_bench_starts_its_own_ranks():
     from conftest import ROOT
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--steps", "4", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--full", "--steps", "4", "--warmup", "1",
                           "--workload", "c2_cornell_1080p_4spp_d8"], capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]

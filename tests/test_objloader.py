@@ -4,7 +4,8 @@ stb_image it vendors, into oracle/_ref/libptref.so — makes of the same files. 
 
   * test_*_golden: the committed inputs (tests/golden/obj_fixture/, written by tests/golden/make_model_golden.py) against the
     reference's stored outputs (tests/golden/ref_model.npz) — runs anywhere;
-  * test_*_live: freshly generated random OBJ / MTL / PNG sets against libptref.so directly — runs where the library was built.
+  * test_*_live: seeded random OBJ / MTL / PNG sets against libptref.so directly where the library was built, and against the digests
+    of its outputs for the same files (tests/golden/ref_live.json, tests/golden/make_live_golden.py) everywhere else.
 
 Two implementations are held to the reference: the native parser behind the C ABI (pt_load_obj, csrc/pt_objload.cpp — the product's
 route, `native=True`, the default) and the line-cited Python restatement it was written from (`native=False`)."""
@@ -172,13 +173,35 @@ def test_native_loader_speed(tmp_path):
 # ----------------------------------------------------------------------------------------------------------------- live
 
 
+def _live_golden():
+    import importlib.util
+    import json
+
+    spec = importlib.util.spec_from_file_location("make_live_golden", os.path.join(HERE, "golden", "make_live_golden.py"))
+    LG = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(LG)
+    return LG, json.load(open(LG.OUT))
+
+
 def _ref():
+    """(orc, libptref.so) where the library with the Model.cpp shims is built, else (None, (make_live_golden module, stored digests))."""
     from oracle import orc
 
     R = orc.load_ref()
     if R is None or not hasattr(R, "refm_load_obj"):
-        pytest.skip("oracle/_ref/libptref.so with the Model.cpp shims is not built here")
+        return None, _live_golden()
     return orc, R
+
+
+def _check_live(orc, R, model, ref_out, digest_of, what):
+    """model against the reference's ([meshes], [textures]): ref_out() from the library, or without it the stored digest digest_of(stored)."""
+    if orc is None:
+        LG, stored = R
+        assert LG.model_digest(*LG.model_fields(model)) == digest_of(stored), what
+    else:
+        out = ref_out()
+        assert out is not None, what
+        _check_model(model, out[0], out[1], what)
 
 
 def _num(rng, v):
@@ -253,39 +276,47 @@ def _random_set(rng, d):
 def test_load_obj_live_fixture(native):
     orc, R = _ref()
     for name in ("basic", "concave", "numbers", "quirks"):
-        out = orc.ref_load_obj(R, os.path.join(FIX, name + ".obj"))
-        _check_model(objloader.load_obj(os.path.join(FIX, name + ".obj"), native=native), out[0], out[1], name)
-    out = orc.ref_load_obj(R, os.path.join(FIX, "images.obj"))  # TGA live (the JPEG, texture 3, is compared with a tolerance in the golden test)
+        path = os.path.join(FIX, name + ".obj")
+        _check_live(orc, R, objloader.load_obj(path, native=native), lambda: orc.ref_load_obj(R, path), lambda G: G["obj_fixture"][name], name)
+    # TGA live (the JPEG, texture 3, is compared with a tolerance in the golden test)
     m = objloader.load_obj(os.path.join(FIX, "images.obj"), native=native)
-    _check_model(scenes.Model(meshes=m.meshes, textures=m.textures[:3]), out[0], out[1][:3], "images")
+    _check_live(orc, R, scenes.Model(meshes=m.meshes, textures=m.textures[:3]), lambda: (lambda o: (o[0], o[1][:3]))(orc.ref_load_obj(R, os.path.join(FIX, "images.obj"))),
+                lambda G: G["obj_fixture"]["images"], "images")
+
+
+def random_sets(d):
+    """The 150 random OBJ / MTL / PNG sets of test_load_obj_live_random, written under d (seeded): the OBJ paths."""
+    rng = np.random.default_rng(2024)
+    for it in range(150):
+        s = os.path.join(d, f"s{it}")
+        os.mkdir(s)
+        yield _random_set(rng, s)
 
 
 def test_load_obj_live_random(tmp_path):
     """150 random OBJ / MTL / PNG sets through the reference's loadOBJ and through objloader.load_obj."""
     orc, R = _ref()
-    rng = np.random.default_rng(2024)
     total_tris = 0
-    for it in range(150):
-        d = tmp_path / f"s{it}"
-        d.mkdir()
-        path = _random_set(rng, str(d))
-        out = orc.ref_load_obj(R, path)
-        assert out is not None
-        _check_model(objloader.load_obj(path, native=True), out[0], out[1], f"random set {it} (native)")
-        _check_model(objloader.load_obj(path, native=False), out[0], out[1], f"random set {it} (python)")
-        total_tris += sum(len(m["index"]) for m in out[0])
+    for it, path in enumerate(random_sets(str(tmp_path))):
+        native = objloader.load_obj(path, native=True)
+        _check_live(orc, R, native, lambda: orc.ref_load_obj(R, path), lambda G: G["obj_random"][it], f"random set {it} (native)")
+        _check_live(orc, R, objloader.load_obj(path, native=False), lambda: orc.ref_load_obj(R, path), lambda G: G["obj_random"][it], f"random set {it} (python)")
+        total_tris += sum(len(m.index) for m in native.meshes)  # (the reference's count: the check above holds the index arrays equal)
     assert total_tris > 1500
+
+
+def live_boxes():
+    rng = np.random.default_rng(5)
+    return [(scenes.Material(color=rng.random(3), roughness=rng.random()), rng.standard_normal(3) * 10, rng.random(3) * 5) for _ in range(50)]
 
 
 def test_add_box_live():
     orc, R = _ref()
-    rng = np.random.default_rng(5)
-    boxes = [(scenes.Material(color=rng.random(3), roughness=rng.random()), rng.standard_normal(3) * 10, rng.random(3) * 5) for _ in range(50)]
-    ref = orc.ref_add_boxes(R, boxes)
+    boxes = live_boxes()
     model = scenes.Model()
     for mat, pos, ext in boxes:
         scenes.add_box(model, mat, pos, ext)
-    _check_model(model, ref, [], "addBox live")
+    _check_live(orc, R, model, lambda: (orc.ref_add_boxes(R, boxes), []), lambda G: G["add_box"], "addBox live")
 
 
 def test_batched_quad_triangulation_equals_scalar_ear_clipping():
@@ -328,21 +359,30 @@ def test_batched_quad_triangulation_equals_scalar_ear_clipping():
         assert a.meshes[0].vertex.tobytes() == b.meshes[0].vertex.tobytes() == c.meshes[0].vertex.tobytes()
 
 
-def test_load_obj_live_many_quads(tmp_path):
-    """A file with thousands of random 4-gons (the batched triangulation path of objloader) against the reference's loadOBJ."""
-    orc, R = _ref()
+MANY_QUADS = 3000
+
+
+def many_quads_file(d):
+    """The OBJ (+ MTL) of test_load_obj_live_many_quads, written under d (seeded): its path."""
     rng = np.random.default_rng(12)
-    n = 3000
+    n = MANY_QUADS
     V = (rng.standard_normal((4 * n, 3)) * np.exp(rng.uniform(-2, 2, (4 * n, 1)))).astype(np.float32)
     V[: 4 * 400, 1] = -1.5
     V[4 * 400: 4 * 600] = np.round(V[4 * 400: 4 * 600])
-    open(tmp_path / "q.mtl", "w").write("newmtl a\nKd 0.5 0.25 0.125\n")
+    open(os.path.join(d, "q.mtl"), "w").write("newmtl a\nKd 0.5 0.25 0.125\n")
     lines = ["mtllib q.mtl", "usemtl a"] + ["v %.9g %.9g %.9g" % tuple(p) for p in V] + ["f %d %d %d %d" % tuple(q) for q in np.arange(1, 4 * n + 1).reshape(n, 4)]
-    open(tmp_path / "q.obj", "w").write("\n".join(lines) + "\n")
-    out = orc.ref_load_obj(R, str(tmp_path / "q.obj"))
-    _check_model(objloader.load_obj(str(tmp_path / "q.obj"), native=True), out[0], out[1], "many quads (native)")
-    _check_model(objloader.load_obj(str(tmp_path / "q.obj"), native=False), out[0], out[1], "many quads (python)")
-    assert len(out[0][0]["index"]) > 1.5 * n
+    open(os.path.join(d, "q.obj"), "w").write("\n".join(lines) + "\n")
+    return os.path.join(d, "q.obj")
+
+
+def test_load_obj_live_many_quads(tmp_path):
+    """A file with thousands of random 4-gons (the batched triangulation path of objloader) against the reference's loadOBJ."""
+    orc, R = _ref()
+    path = many_quads_file(str(tmp_path))
+    native = objloader.load_obj(path, native=True)
+    _check_live(orc, R, native, lambda: orc.ref_load_obj(R, path), lambda G: G["many_quads"], "many quads (native)")
+    _check_live(orc, R, objloader.load_obj(path, native=False), lambda: orc.ref_load_obj(R, path), lambda G: G["many_quads"], "many quads (python)")
+    assert len(native.meshes[0].index) > 1.5 * MANY_QUADS
 
 
 def test_native_loader_refuses_a_directory_without_throwing():

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/kdur_$$; rm -rf $OUT; mkdir -p $OUT
 [ -n "$1" ] && export PT_LIB=$1
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline $KDUR_ARGS > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline $KDUR_ARGS > $OUT/log 2>&1
 python3 - $OUT <<'PY'
 import csv,glob,sys
 f=glob.glob(sys.argv[1]+'/**/*kernel_trace.csv',recursive=True)[0]
