@@ -431,6 +431,37 @@ int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit, float* t_o
  * record: k_shade reads these very triangles through the leaf index a closest-hit record holds), 1 unused. */
 int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes, uint32_t* num_nodes, uint32_t* num_tris);
 
+/* In-place vertex updates (no reference counterpart: the reference builds its GAS once with OPTIX_BUILD_OPERATION_BUILD,
+ * SimplePathtracer.cpp:529; the OptiX analogue is OPTIX_BUILD_FLAG_ALLOW_UPDATE + OPTIX_BUILD_OPERATION_UPDATE).
+ * Contract:
+ *   - only vertex positions change: index buffers, texcoords, materials and the mesh count stay as created;
+ *   - one call updates `n` >= 1 meshes with ONE refit or ONE rebuild and is atomic: on any error (mesh index out of range, a mesh named
+ *     twice, num_vertices different from the mesh's, a non-finite coordinate, out of memory, a rebuilt tree deeper than the traversal
+ *     stack) the context is exactly as before — vertices, tree and side arrays — and PT_ERR_INVALID / PT_ERR_HIP / PT_ERR_UNSUPPORTED
+ *     is returned.  The vertices are validated on the host and staged in a scratch buffer first;
+ *   - it waits for the frames in flight (pt_sync) and is complete when it returns (STREAM CONTRACT): frames enqueued before the call see
+ *     the old geometry, frames after it the new.  accum_buffer is left alone: restart the accumulation at subframe 0, as after a camera move;
+ *   - PT_UPDATE_REFIT keeps the tree's topology and recomputes its boxes on the GPU (leaf triangles, then one launch per level, deepest
+ *     first).  Images are those of a fresh pt_create over the new vertices, bit for bit (a hit does not depend on the tree); the traversal
+ *     cost grows as the vertices drift from where the tree was built — rebuild when frames get slower.  The calibration cost is kept,
+ *     the on-line chain/fused schedule trial starts over.  Builds with PT8_NODE64 return PT_ERR_UNSUPPORTED (that node's origin grid is
+ *     fixed to the scene bounds of the build);
+ *   - PT_UPDATE_REBUILD runs the whole build of pt_create over the new vertices (calibration, stack-depth check, pt_stats.bvh_build_ms)
+ *     into a new tree, then swaps it in;
+ *   - kernel_ms (may be NULL): device time of the update (hipEvents around its kernels; the host-to-device copy is not included). */
+typedef struct pt_mesh_update {
+    uint32_t mesh;          /* index into the pt_scene_desc.meshes the context was created from */
+    const float* vertex;    /* num_vertices * 3, host memory */
+    uint32_t num_vertices;  /* must equal that mesh's num_vertices */
+} pt_mesh_update;
+
+enum pt_update_mode { PT_UPDATE_REFIT = 0, PT_UPDATE_REBUILD = 1 };
+
+int pt_update_meshes(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms /* may be NULL */);
+/* every rank of a pt_multi (all ranks drained first, like pt_multi_resize); validation and staging happen on every rank before any rank
+ * changes, so a failure leaves all ranks as they were.  kernel_ms: the slowest rank's */
+int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms /* may be NULL: the slowest rank */);
+
 /* Scene ingestion, host only (no GPU needed): loadOBJ (HelloPathtracing_original/Model.cpp:137-212 — tinyobjloader 2.0.0's LoadObj with
  * triangulation, then one TriangleMesh per (shape, material id)) as native code.  The arrays are the reference's bit for bit
  * (tests/test_objloader.py: the reference's own Model.cpp, compiled from where it lies, on committed fixtures and random files):

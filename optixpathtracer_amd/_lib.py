@@ -22,7 +22,14 @@ EXPORTS = [
     "pt_pack_async", "pt_pack_wait", "pt_unpack_display", "pt_display_sync", "pt_display_buffer", "pt_download_display", "pt_multi_flush",
     "pt_render_device", "pt_stream", "pt_wait_event", "pt_get_stats_n", "pt_stats_size",
     "pt_load_obj", "pt_obj_free", "pt_obj_num_meshes", "pt_obj_get_mesh", "pt_obj_num_textures", "pt_obj_texture_path", "pt_obj_last_error",
+    "pt_update_meshes", "pt_multi_update_meshes",
 ]
+
+PT_UPDATE_REFIT, PT_UPDATE_REBUILD = 0, 1  # pt_update_mode
+
+
+class MeshUpdate(C.Structure):  # pt_mesh_update
+    _fields_ = [("mesh", C.c_uint32), ("vertex", C.POINTER(C.c_float)), ("num_vertices", C.c_uint32)]
 
 
 class DenoiseParams(C.Structure):  # pt_denoise_params
@@ -194,6 +201,8 @@ def load_library() -> C.CDLL:
     L.pt_trace.argtypes = [vp, vp, u32, i, vp, vp, i, C.POINTER(C.c_double)]
     L.pt_eval_table.argtypes = [vp, i, vp, i, vp, u32, vp]
     L.pt_export_bvh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]
+    L.pt_update_meshes.argtypes = [vp, C.POINTER(MeshUpdate), u32, i, C.POINTER(C.c_double)]
+    L.pt_multi_update_meshes.argtypes = [vp, C.POINTER(MeshUpdate), u32, i, C.POINTER(C.c_double)]
     L.pt_version.restype = C.c_char_p
     f3p = C.POINTER(f * 3)
     L.pt_create_multi.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), i, C.POINTER(vp)]

@@ -191,6 +191,25 @@ class SampleRenderer {
         ck(pt_set_options(ctx, &o));
     }
     void sync() { ck(pt_sync(ctx)); }
+    // Moved vertices (no reference counterpart; OptiX: OPTIX_BUILD_OPERATION_UPDATE): after changing model->meshes[m]->vertex in place for
+    // every m in `meshes` (same vertex count, same indices), the context takes the new positions — the tree refitted on the GPU, or rebuilt
+    // with rebuild = true (pt_update_meshes).  Restart the accumulation at subframe 0 afterwards.  Returns the device time in ms.
+    double updateMeshes(const Model* model, const std::vector<uint32_t>& meshes, bool rebuild = false) {
+        double ms = 0;
+        const std::vector<pt_mesh_update> u = mesh_updates(model, meshes);
+        ck(pt_update_meshes(ctx, u.data(), (uint32_t)u.size(), rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
+        return ms;
+    }
+    static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
+        static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
+        std::vector<pt_mesh_update> u;
+        for (uint32_t m : meshes) {
+            if (m >= model->meshes.size()) throw std::runtime_error("updateMeshes: mesh index out of range");
+            const TriangleMesh* tm = model->meshes[m];
+            u.push_back(pt_mesh_update{m, tm->vertex.empty() ? nullptr : &tm->vertex[0].x, (uint32_t)tm->vertex.size()});
+        }
+        return u;
+    }
     bool denoiserOn = true;  // SimplePathtracer.h:63 (default true there too); nothing reads it in the reference (OptixDenoiser.cpp:15-42 is empty)
     LaunchParams launchParams;   // SimplePathtracer.h:137
     stream_t stream = nullptr;   // SimplePathtracer.h:107: the context's stream (pt_stream), e.g. for output_buffer.setStream(sample.stream), main.cpp:245
@@ -258,6 +277,12 @@ class MultiSampleRenderer {
         ck(pt_multi_set_options(multi, &o));
     }
     void flush(uint32_t* h_pixels = nullptr) { ck(pt_multi_flush(multi, h_pixels)); }
+    double updateMeshes(const Model* model, const std::vector<uint32_t>& meshes, bool rebuild = false) { // SampleRenderer::updateMeshes on every rank
+        double ms = 0;
+        const std::vector<pt_mesh_update> u = SampleRenderer::mesh_updates(model, meshes);
+        ck(pt_multi_update_meshes(multi, u.data(), (uint32_t)u.size(), rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
+        return ms;
+    }
     void downloadDisplayedPixels(uint32_t h_pixels[]) { // the frame on display (rank 0's display buffer) in the frames-in-flight mode
         if (pt_download_display(pt_multi_ctx(multi, 0), PT_BUF_FRAME, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * launchParams.frame.size.y) != PT_OK)
             throw std::runtime_error(pt_last_error(pt_multi_ctx(multi, 0)));

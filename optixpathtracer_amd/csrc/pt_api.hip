@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <chrono>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -90,6 +91,8 @@ struct pt_ctx {
     pt_options opt{};
     // scene
     uint32_t ntri = 0, nmesh = 0;
+    size_t nvert = 0;
+    std::vector<uint32_t> mesh_vbase, mesh_nv; // per mesh: first vertex in the global vertex space, vertex count (pt_update_meshes)
     float* d_verts = nullptr;
     uint32_t* d_idx = nullptr;
     uint32_t* d_tri_mesh = nullptr;
@@ -332,10 +335,11 @@ static int stack_capacity8(const pt_ctx* ctx) { return (PT8_LDS_DEPTH - ctx->lds
 
 // The traversal stack is finite (k_trace8: one pushed group per level of the wide tree).  A tree deeper than the stack is refused
 // here, loudly, instead of being traversed with dropped entries.
-static int check_tree_depth(pt_ctx* ctx, char* msg, size_t msg_len) {
+static int check_tree_depth(pt_ctx* ctx, char* msg, size_t msg_len, const PtBvh* bvh = nullptr) {
     if (!ctx->stack_check) return PT_OK;
-    if (ctx->bvh.levels8 > stack_capacity8(ctx)) {
-        snprintf(msg, msg_len, "acceleration structure has %d levels, the traversal stack holds %d", ctx->bvh.levels8, stack_capacity8(ctx));
+    const int levels = (bvh ? bvh : &ctx->bvh)->levels8;
+    if (levels > stack_capacity8(ctx)) {
+        snprintf(msg, msg_len, "acceleration structure has %d levels, the traversal stack holds %d", levels, stack_capacity8(ctx));
         return PT_ERR_UNSUPPORTED;
     }
     return PT_OK;
@@ -456,6 +460,11 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
     struct JoinWarm { std::thread& t; ~JoinWarm() { if (t.joinable()) t.join(); } } join_warm{warm_thread};
     ctx->ntri = (uint32_t)nt;
     ctx->nmesh = scene->num_meshes;
+    ctx->nvert = nv;
+    for (uint32_t m = 0, vb = 0; m < scene->num_meshes; vb += scene->meshes[m].num_vertices, ++m) {
+        ctx->mesh_vbase.push_back(vb);
+        ctx->mesh_nv.push_back(scene->meshes[m].num_vertices);
+    }
     CKC(dalloc(&ctx->d_verts, 3 * nv));
     CKC(dalloc(&ctx->d_idx, 3 * nt));
     CKC(dalloc(&ctx->d_tri_mesh, nt));
@@ -2321,6 +2330,139 @@ extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void*
     return PT_OK;
 }
 
+// ------------------------------------------------------------------ in-place vertex updates (pt_update_meshes, include/pt_amd.h)
+// Two phases, so that an update is atomic on one context and on all ranks of a pt_multi: update_stage validates, drains the frames in
+// flight and prepares everything that can fail — the new vertex array in a scratch buffer, the refit's side arrays, or the whole rebuilt tree
+// with its side arrays — without touching the context; update_commit then refits in place or swaps the new tree in, and only a failing HIP
+// runtime can stop it half way.
+struct MeshUpdate {
+    float* d_new = nullptr; // the whole vertex array with the updated meshes
+    PtBvh nb;               // PT_UPDATE_REBUILD: the new tree and its side arrays
+    float4* nrm = nullptr;
+    TexTri* textris = nullptr;
+    double build_ms = 0;
+    void discard() { dfree(d_new); pt_bvh_free(&nb); dfree(nrm); dfree(textris); }
+};
+
+// host-side checks, shared by every rank (they share the scene's mesh table)
+static int update_validate(const pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, std::string& err) {
+    if (!up || n == 0) { err = "pt_update_meshes: no updates"; return PT_ERR_INVALID; }
+    if (mode != PT_UPDATE_REFIT && mode != PT_UPDATE_REBUILD) { err = "pt_update_meshes: mode must be PT_UPDATE_REFIT or PT_UPDATE_REBUILD"; return PT_ERR_INVALID; }
+    std::vector<char> seen(ctx->nmesh, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const pt_mesh_update& u = up[k];
+        if (u.mesh >= ctx->nmesh) { err = "pt_update_meshes: mesh index " + std::to_string(u.mesh) + " out of range"; return PT_ERR_INVALID; }
+        if (seen[u.mesh]) { err = "pt_update_meshes: mesh " + std::to_string(u.mesh) + " named twice"; return PT_ERR_INVALID; }
+        seen[u.mesh] = 1;
+        if (!u.vertex) { err = "pt_update_meshes: null vertex pointer"; return PT_ERR_INVALID; }
+        if (u.num_vertices != ctx->mesh_nv[u.mesh]) {
+            err = "pt_update_meshes: mesh " + std::to_string(u.mesh) + " has " + std::to_string(ctx->mesh_nv[u.mesh]) + " vertices, the update " + std::to_string(u.num_vertices);
+            return PT_ERR_INVALID;
+        }
+        for (size_t i = 0; i < 3 * (size_t)u.num_vertices; ++i)
+            if (!std::isfinite(u.vertex[i])) { err = "pt_update_meshes: non-finite coordinate in mesh " + std::to_string(u.mesh); return PT_ERR_INVALID; }
+    }
+    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = "pt_update_meshes: refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
+    return PT_OK;
+}
+
+static int update_stage(pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, MeshUpdate& U) {
+    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames enqueued before the call render the old geometry
+    CK(hipSetDevice(ctx->device));
+    CK(dalloc(&U.d_new, 3 * ctx->nvert));
+    CK(hipMemcpyAsync(U.d_new, ctx->d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
+    for (uint32_t k = 0; k < n; ++k)
+        CK(hipMemcpyAsync(U.d_new + 3 * (size_t)ctx->mesh_vbase[up[k].mesh], up[k].vertex, sizeof(float) * 3 * up[k].num_vertices, hipMemcpyHostToDevice, ctx->stream));
+    if (mode == PT_UPDATE_REFIT) {
+        CK(pt_bvh_refit_alloc(&ctx->bvh));
+        CK(hipStreamSynchronize(ctx->stream));
+        return PT_OK;
+    }
+    // rebuild: pt_create's build and side arrays over the new vertices, into a tree of its own
+    DevScope tmp;
+    hipEvent_t e0, e1;
+    CK(tmp.event(&e0));
+    CK(tmp.event(&e1));
+    CK(hipEventRecord(e0, ctx->stream));
+    CK(pt_bvh_build(U.d_new, ctx->d_idx, ctx->d_tri_mesh, ctx->ntri, ctx->stream, &U.nb));
+    const uint32_t nt8 = U.nb.num_tris8;
+    CK(dalloc(&U.nrm, (size_t)nt8));
+    hipLaunchKernelGGL(k_shade_normals, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.nb.tris8, nt8, U.nrm);
+    if (ctx->d_textris) { // the texcoords per primitive, from the old tree's records, then the records in the new leaf order
+        PrimUV* uvs = nullptr;
+        CK(tmp.alloc(&uvs, (size_t)ctx->ntri));
+        CK(dalloc(&U.textris, (size_t)nt8));
+        hipLaunchKernelGGL(k_textris_to_uvs, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->d_textris, ctx->bvh.num_tris8, uvs);
+        hipLaunchKernelGGL(k_emit_textris, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.nb.tris8, uvs, nt8, U.textris);
+    }
+    CK(hipGetLastError());
+    CK(hipEventRecord(e1, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    U.build_ms = ms;
+    char msg[160];
+    if (check_tree_depth(ctx, msg, sizeof(msg), &U.nb) != PT_OK) {
+        ctx->err = std::string("pt_update_meshes: ") + msg;
+        return PT_ERR_UNSUPPORTED;
+    }
+    return PT_OK;
+}
+
+static int update_commit(pt_ctx* ctx, int mode, MeshUpdate& U, double* kernel_ms) {
+    CK(hipSetDevice(ctx->device));
+    double ms = U.build_ms;
+    if (mode == PT_UPDATE_REFIT) {
+        DevScope tmp;
+        hipEvent_t e0, e1;
+        CK(tmp.event(&e0));
+        CK(tmp.event(&e1));
+        CK(hipEventRecord(e0, ctx->stream));
+        CK(pt_bvh_refit_begin(&ctx->bvh, U.d_new, ctx->d_idx, ctx->ntri, ctx->stream));
+        const uint32_t nt8 = ctx->bvh.num_tris8;
+        hipLaunchKernelGGL(k_refit_leaves, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.d_new, ctx->d_idx, nt8, const_cast<LeafTri*>(ctx->bvh.tris8),
+                           ctx->d_tri_nrm, ctx->d_textris);
+        CK(hipGetLastError());
+        CK(pt_bvh_refit_nodes(&ctx->bvh, ctx->stream));
+        CK(hipEventRecord(e1, ctx->stream));
+        CK(pt_bvh_refit_end(&ctx->bvh, ctx->stream)); // waits; the new bounds and padding
+        float fms = 0;
+        CK(hipEventElapsedTime(&fms, e0, e1));
+        ms = fms;
+    } else {
+        pt_bvh_free(&ctx->bvh);
+        ctx->bvh = std::move(U.nb);
+        U.nb = PtBvh{};
+        dfree(ctx->d_tri_nrm);
+        ctx->d_tri_nrm = U.nrm;
+        U.nrm = nullptr;
+        if (U.textris) {
+            dfree(ctx->d_textris);
+            ctx->d_textris = U.textris;
+            U.textris = nullptr;
+        }
+        ctx->bvh_build_ms = U.build_ms;
+    }
+    dfree(ctx->d_verts);
+    ctx->d_verts = U.d_new;
+    U.d_new = nullptr;
+    ctx->sched = pt_ctx::Sched{}; // the tree's traversal cost changed: the chain/fused trial starts over
+    if (kernel_ms) *kernel_ms = ms;
+    return PT_OK;
+}
+
+extern "C" int pt_update_meshes(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_update_meshes: null context");
+    std::string err;
+    int rc = update_validate(ctx, updates, n, mode, err);
+    if (rc != PT_OK) return fail(ctx, rc, err.c_str());
+    MeshUpdate U;
+    rc = update_stage(ctx, updates, n, mode, U);
+    if (rc == PT_OK) rc = update_commit(ctx, mode, U, kernel_ms);
+    U.discard();
+    return rc;
+}
+
 extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material, int bsdf_mode, const float* in, uint32_t n, float* out) {
     if (!ctx || !in || !out) return PT_ERR_INVALID;
     if (n == 0) return PT_OK;
@@ -3031,4 +3173,24 @@ extern "C" int pt_multi_get_stats(const pt_multi* m, pt_multi_stats* out) {
     out->threads = (int32_t)m->workers.size();
     out->frames_handed_over = m->handed;
     return PT_OK;
+}
+
+extern "C" int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
+    if (!m) return PT_ERR_INVALID;
+    const int world = (int)m->ctx.size();
+    std::string err;
+    int rc = update_validate(m->ctx[0], updates, n, mode, err);
+    if (rc != PT_OK) return mfail(m, rc, err);
+    std::vector<MeshUpdate> U(world);
+    auto discard = [&] { for (auto& u : U) u.discard(); };
+    for (int r = 0; r < world && rc == PT_OK; ++r) rc = mctx(m, r, update_stage(m->ctx[r], updates, n, mode, U[r]), "pt_multi_update_meshes");
+    double slow = 0;
+    for (int r = 0; r < world && rc == PT_OK; ++r) {
+        double ms = 0;
+        rc = mctx(m, r, update_commit(m->ctx[r], mode, U[r], &ms), "pt_multi_update_meshes");
+        slow = std::max(slow, ms);
+    }
+    discard();
+    if (rc == PT_OK && kernel_ms) *kernel_ms = slow;
+    return rc;
 }

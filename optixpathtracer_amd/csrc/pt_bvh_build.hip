@@ -22,6 +22,21 @@
 
 namespace {
 
+// scene bounds from k_bounds' ordered uints, and the padding of every box: 2^-16 of the largest |coordinate| (the refit derives it on the
+// device from the same words, so both sides must compute it alike)
+__host__ __device__ inline float bounds_pad(const uint32_t ob[6], float bounds[6]) {
+    float maxabs = 0.f;
+    for (int a = 0; a < 6; ++a) {
+        const uint32_t u = ob[a];
+        const uint32_t bits = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+        float f;
+        memcpy(&f, &bits, 4);
+        bounds[a] = f;
+        maxabs = fmaxf(maxabs, fabsf(f));
+    }
+    return maxabs * (1.0f / 65536.0f);
+}
+
 __device__ __forceinline__ uint32_t f2ord(float f) {
     uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -365,6 +380,42 @@ __global__ void k_collapse_cost_level(const int* __restrict__ order, int count, 
     collapse_cost_node(order[t], n, left, right, cnt_of, box, pad, cp, cost, dec, true);
 }
 
+// ---- quantisation of a wide node, shared by the collapse (k_collapse8) and the refit (k_refit_nodes): a refit over unchanged vertices
+// reproduces every node byte for byte.  The node box is the union of the children's boxes, each padded by `pad`.
+__device__ __forceinline__ void node_box_add(float lo[3], float hi[3], const float* b, float pad) {
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = fminf(lo[a], b[a] - pad);
+        hi[a] = fmaxf(hi[a], b[3 + a] + pad);
+    }
+}
+// grid step per axis: ext/255 rounded UP to a float with an 8-bit significand (the 16 bits the node stores), so the
+// 255 steps cover the extent with < 1 % slack (a power-of-two step wasted up to 2x of the 8-bit resolution)
+__device__ __forceinline__ void node_steps80(const float lo[3], const float hi[3], uint32_t eb[3] /* upper 16 bits of the step */, float step[3]) {
+    for (int a = 0; a < 3; ++a) {
+        const float ext = hi[a] - lo[a];
+        float st = ext * (1.0f / 255.0f) * 1.015625f;
+        if (!(st >= 2.3509887e-38f)) st = 2.3509887e-38f; // 2^-125
+        if (st > 1.0e38f) st = 1.0e38f;
+        eb[a] = (__float_as_uint(st) + 0xffffu) >> 16;
+        step[a] = __uint_as_float(eb[a] << 16);
+    }
+}
+// the quantised planes of the child box b (unpadded) in slot s, rounded outward
+__device__ __forceinline__ void child_planes(const float* b, float pad, const float lo[3], const float step[3], int s, uint32_t q[6][2]) {
+    for (int a = 0; a < 3; ++a) {
+        float ql = floorf(((b[a] - pad) - lo[a]) / step[a]);
+        float qh = ceilf(((b[3 + a] + pad) - lo[a]) / step[a]);
+        ql = fminf(fmaxf(ql, 0.f), 255.f);
+        qh = fminf(fmaxf(qh, 0.f), 255.f);
+        // the division by a non-power-of-two step rounds: make sure the grid planes still enclose the padded box
+        while (ql > 0.f && lo[a] + ql * step[a] > b[a] - pad) ql -= 1.f;
+        while (qh < 255.f && lo[a] + qh * step[a] < b[3 + a] + pad) qh += 1.f;
+        const int w = s >> 2, k = s & 3;
+        q[a][w] = (q[a][w] & ~(0xffu << (8 * k))) | ((uint32_t)ql << (8 * k));
+        q[3 + a][w] = (q[3 + a][w] & ~(0xffu << (8 * k))) | ((uint32_t)qh << (8 * k));
+    }
+}
+
 __global__ void k_collapse8(const Task8* __restrict__ tin, uint32_t nin, Task8* __restrict__ tout, uint32_t* __restrict__ counters /*0 next tasks,1 nodes,2 tris*/,
                             int n, const int* __restrict__ left, const int* __restrict__ right, const int* __restrict__ cnt_of,
                             const float* __restrict__ box, float pad, const uint8_t* __restrict__ dec /* null: greedy by area */,
@@ -418,11 +469,7 @@ __global__ void k_collapse8(const Task8* __restrict__ tin, uint32_t nin, Task8* 
     }
     // node box (padded)
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int j = 0; j < nch; ++j)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fminf(lo[a], box[(size_t)ch[j] * 6 + a] - pad);
-            hi[a] = fmaxf(hi[a], box[(size_t)ch[j] * 6 + 3 + a] + pad);
-        }
+    for (int j = 0; j < nch; ++j) node_box_add(lo, hi, &box[(size_t)ch[j] * 6], pad);
     // greedy octant slot assignment: cost(child j, slot s) = dot(centroid_j - centre, signs(s))
     float cen[3] = {0.5f * (lo[0] + hi[0]), 0.5f * (lo[1] + hi[1]), 0.5f * (lo[2] + hi[2])};
     int slot_of[8], child_in[8];
@@ -487,18 +534,9 @@ __global__ void k_collapse8(const Task8* __restrict__ tin, uint32_t nin, Task8* 
         step[a] = __uint_as_float((grid.ebase + e) << 23);
     }
 #else
-    // grid step per axis: ext/255 rounded UP to a float with an 8-bit significand (the 16 bits the node stores), so the
-    // 255 steps cover the extent with < 1 % slack (a power-of-two step wasted up to 2x of the 8-bit resolution)
     uint32_t eb[3]; // upper 16 bits of the step
     float step[3];
-    for (int a = 0; a < 3; ++a) {
-        const float ext = hi[a] - lo[a];
-        float st = ext * (1.0f / 255.0f) * 1.015625f;
-        if (!(st >= 2.3509887e-38f)) st = 2.3509887e-38f; // 2^-125
-        if (st > 1.0e38f) st = 1.0e38f;
-        eb[a] = (__float_as_uint(st) + 0xffffu) >> 16;
-        step[a] = __uint_as_float(eb[a] << 16);
-    }
+    node_steps80(lo, hi, eb, step);
 #endif
     uint32_t q[6][2] = {{0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}, {0u, 0u}, {0u, 0u}, {0u, 0u}};
     uint32_t leafbits = 0u;
@@ -507,19 +545,7 @@ __global__ void k_collapse8(const Task8* __restrict__ tin, uint32_t nin, Task8* 
         const int j = child_in[s];
         if (j < 0) continue; // empty slot keeps the inverted box
         const int c = ch[j];
-        const float* b = &box[(size_t)c * 6];
-        for (int a = 0; a < 3; ++a) {
-            float ql = floorf(((b[a] - pad) - lo[a]) / step[a]);
-            float qh = ceilf(((b[3 + a] + pad) - lo[a]) / step[a]);
-            ql = fminf(fmaxf(ql, 0.f), 255.f);
-            qh = fminf(fmaxf(qh, 0.f), 255.f);
-            // the division by a non-power-of-two step rounds: make sure the grid planes still enclose the padded box
-            while (ql > 0.f && lo[a] + ql * step[a] > b[a] - pad) ql -= 1.f;
-            while (qh < 255.f && lo[a] + qh * step[a] < b[3 + a] + pad) qh += 1.f;
-            const int w = s >> 2, k = s & 3;
-            q[a][w] = (q[a][w] & ~(0xffu << (8 * k))) | ((uint32_t)ql << (8 * k));
-            q[3 + a][w] = (q[3 + a][w] & ~(0xffu << (8 * k))) | ((uint32_t)qh << (8 * k));
-        }
+        child_planes(&box[(size_t)c * 6], pad, lo, step, s, q);
         if (imask & (1u << s)) {
             tout[task_base + irank] = Task8{c, child_base + irank};
             ++irank;
@@ -730,8 +756,7 @@ __global__ void __launch_bounds__(1024) k_ploc_tail(const int* __restrict__ cl_i
 }
 
 // scenes with <= PT8_LEAF_MAX triangles: one node, one leaf child
-__global__ void k_single_node8(int n, const float* __restrict__ bounds6, float pad, Node8* __restrict__ nodes, Grid8 grid) {
-    if (threadIdx.x || blockIdx.x) return;
+__device__ void single_node8(int n, const float* bounds6, float pad, Node8* __restrict__ nodes, Grid8 grid) {
     float lo[3], hi[3];
 #if PT8_NODE64
     uint32_t e5[3];
@@ -770,6 +795,10 @@ __global__ void k_single_node8(int n, const float* __restrict__ bounds6, float p
     nd.n4 = make_float4(__uint_as_float(qhi), __uint_as_float(0u), __uint_as_float(qhi), __uint_as_float(0u));
     nodes[0] = nd;
 #endif
+}
+__global__ void k_single_node8(int n, const float* __restrict__ bounds6, float pad, Node8* __restrict__ nodes, Grid8 grid) {
+    if (threadIdx.x || blockIdx.x) return;
+    single_node8(n, bounds6, pad, nodes, grid);
 }
 
 // ---- choosing between two hierarchies by measurement (pt_bvh_build, PT_BVH_BUILDER unset).  The SAH cost of the collapsed tree
@@ -1084,12 +1113,14 @@ static hipError_t build_bvh8(int n, int root, const int* left, const int* right,
     HIPCHK(hipMemcpyAsync(ta, &root_task, sizeof(root_task), hipMemcpyHostToDevice, stream));
     uint32_t nin = 1;
     int levels = 0;
+    std::vector<uint32_t> level_off(1, 0u); // round r emits the nodes [level_off[r], level_off[r + 1]): the tasks it was handed
     while (nin) {
         hipLaunchKernelGGL(k_collapse8, dim3((nin + 63) / 64), dim3(64), 0, stream, ta, nin, tb, counters, n, left, right, cnt, box, pad, dec,
                            tris_sorted, nodes, tris8, out->grid);
         HIPCHK(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         nin = hc[0];
+        level_off.push_back(hc[1] - nin); // counters[1] is never reset: the nodes handed out so far minus the next round's
         const uint32_t zero = 0;
         HIPCHK(hipMemcpyAsync(counters, &zero, 4, hipMemcpyHostToDevice, stream));
         Task8* t = ta; ta = tb; tb = t;
@@ -1145,6 +1176,7 @@ static hipError_t build_bvh8(int n, int root, const int* left, const int* right,
     out->num_nodes8 = hc[1];
     out->num_tris8 = hc[2];
     out->levels8 = levels;
+    out->level_off = std::move(level_off);
     tfree(ta); tfree(tb); tfree(counters);
     if (dec) tfree(dec);
     return hipSuccess;
@@ -1913,16 +1945,7 @@ hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint3
     uint32_t hb[6];
     HIPCHK(hipMemcpyAsync(hb, bounds, sizeof(hb), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    float maxabs = 0.f;
-    for (int a = 0; a < 6; ++a) {
-        uint32_t u = hb[a];
-        uint32_t bits = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-        float f;
-        memcpy(&f, &bits, 4);
-        out->bounds[a] = f;
-        maxabs = fmaxf(maxabs, fabsf(f));
-    }
-    const float pad = maxabs * (1.0f / 65536.0f);
+    const float pad = bounds_pad(hb, out->bounds);
     out->pad = pad;
 #if PT8_NODE64
     {
@@ -1961,6 +1984,7 @@ hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint3
         HIPCHK(hipMemcpyAsync(tris8, tris, sizeof(LeafTri) * (size_t)n, hipMemcpyDeviceToDevice, stream));
         hipLaunchKernelGGL(k_single_node8, dim3(1), dim3(64), 0, stream, n, dbounds, pad, nodes8, out->grid);
         out->nodes8 = nodes8; out->tris8 = tris8; out->num_nodes8 = 1; out->num_tris8 = (uint32_t)n; out->levels8 = 1;
+        out->level_off = {0u, 1u};
         HIPCHK(hipStreamSynchronize(stream));
         tfree(dbounds);
         tfree(tris);
@@ -2063,6 +2087,7 @@ hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint3
                 if (cost_alt < cost_cur) {
                     hipFree((void*)out->nodes8); hipFree((void*)out->tris8);
                     out->nodes8 = alt.nodes8; out->tris8 = alt.tris8; out->num_nodes8 = alt.num_nodes8; out->num_tris8 = alt.num_tris8; out->levels8 = alt.levels8;
+                    out->level_off = std::move(alt.level_off);
                     out->builder = kind;
                 } else {
                     hipFree((void*)alt.nodes8); hipFree((void*)alt.tris8);
@@ -2101,6 +2126,131 @@ void pt_bvh_warm(hipStream_t stream) {
 void pt_bvh_free(PtBvh* b) {
     if (b->nodes8) hipFree((void*)b->nodes8);
     if (b->tris8) hipFree((void*)b->tris8);
+    if (b->d_exact) hipFree(b->d_exact);
+    if (b->d_refit) hipFree(b->d_refit);
     b->nodes8 = nullptr;
     b->tris8 = nullptr;
+    b->d_exact = nullptr;
+    b->d_refit = nullptr;
+}
+
+// ------------------------------------------------------------------ refit (pt_update_meshes, PT_UPDATE_REFIT)
+// The topology stays: slots, imask, child_base, tri_base and leafbits.  The leaf triangles were rewritten by the caller (k_refit_leaves);
+// one launch per wide level, deepest first, then recomputes every node's origin, steps and planes from its children's exact boxes — an
+// internal child's from d_exact (written by the level below), a leaf child's as the union of its triangles — with the collapse's own
+// quantisation, and stores the node's exact box for its parent.  Min and max are exact, so the boxes are those the build derived from the
+// binary hierarchy and a refit over unchanged vertices gives the tree back byte for byte.  PT_BVH_CHECK builds compare every index taken
+// from a node word with its array before the access (fault bit 0: child node, bit 1: leaf triangles).
+namespace {
+#if PT_BVH_CHECK
+#define REFIT_OK(cond, bit, fault) ((cond) ? true : (atomicOr((fault), 1u << (bit)), false))
+#else
+#define REFIT_OK(cond, bit, fault) (true)
+#endif
+__device__ __forceinline__ void tri_box_add(float b[6], const LeafTri& t) {
+    const float v[9] = {t.t0.x, t.t0.y, t.t0.z, t.t0.w, t.t1.x, t.t1.y, t.t1.z, t.t1.w, t.t2.x};
+    for (int k = 0; k < 3; ++k)
+        for (int a = 0; a < 3; ++a) {
+            b[a] = fminf(b[a], v[3 * k + a]);
+            b[3 + a] = fmaxf(b[3 + a], v[3 * k + a]);
+        }
+}
+__global__ void k_refit_nodes(uint32_t first, uint32_t count, Node8* __restrict__ nodes, const LeafTri* __restrict__ tris, float* __restrict__ exact,
+                              uint32_t num_nodes, uint32_t num_tris, uint32_t* __restrict__ refit /* [0..5] ordered bounds, [6] fault */) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const uint32_t i = first + t;
+#if !PT8_NODE64
+    float sb[6];
+    const float pad = bounds_pad(refit, sb);
+    Node8 nd = nodes[i];
+    const uint32_t child_base = __float_as_uint(nd.n1.x), tri_base = __float_as_uint(nd.n1.y), leafbits = __float_as_uint(nd.n1.z);
+    const uint32_t imask = __float_as_uint(nd.n1.w) >> 16;
+    float cb[8][6];
+    uint32_t occupied = 0u, irank = 0u, toff = 0u;
+    for (int s = 0; s < 8; ++s) {
+        float* b = cb[s];
+        for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[3 + a] = -INFINITY; }
+        if (imask & (1u << s)) {
+            const uint32_t c = child_base + irank++;
+            if (!REFIT_OK(c < num_nodes, 0, &refit[6])) continue;
+            for (int a = 0; a < 6; ++a) b[a] = exact[(size_t)c * 6 + a];
+            occupied |= 1u << s;
+        } else if (const uint32_t cnt = (leafbits >> (3 * s)) & 7u) {
+            const uint32_t k0 = tri_base + toff, nk = (uint32_t)__popc(cnt);
+            toff += nk;
+            if (!REFIT_OK(k0 + nk <= num_tris, 1, &refit[6])) continue;
+            for (uint32_t k = 0; k < nk; ++k) tri_box_add(b, tris[k0 + k]);
+            occupied |= 1u << s;
+        }
+    }
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    float ex[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int s = 0; s < 8; ++s)
+        if (occupied & (1u << s)) {
+            node_box_add(lo, hi, cb[s], pad);
+            node_box_add(ex, ex + 3, cb[s], 0.f);
+        }
+    uint32_t eb[3];
+    float step[3];
+    node_steps80(lo, hi, eb, step);
+    uint32_t q[6][2] = {{0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}, {0u, 0u}, {0u, 0u}, {0u, 0u}};
+    for (int s = 0; s < 8; ++s)
+        if (occupied & (1u << s)) child_planes(cb[s], pad, lo, step, s, q);
+    nd.n0 = make_float4(lo[0], lo[1], lo[2], __uint_as_float(eb[0] | (eb[1] << 16)));
+    nd.n1.w = __uint_as_float(eb[2] | (imask << 16));
+    nd.n2 = make_float4(__uint_as_float(q[0][0]), __uint_as_float(q[0][1]), __uint_as_float(q[1][0]), __uint_as_float(q[1][1]));
+    nd.n3 = make_float4(__uint_as_float(q[2][0]), __uint_as_float(q[2][1]), __uint_as_float(q[3][0]), __uint_as_float(q[3][1]));
+    nd.n4 = make_float4(__uint_as_float(q[4][0]), __uint_as_float(q[4][1]), __uint_as_float(q[5][0]), __uint_as_float(q[5][1]));
+    nodes[i] = nd;
+    for (int a = 0; a < 6; ++a) exact[(size_t)i * 6 + a] = ex[a];
+#endif
+}
+// scenes of at most PT8_LEAF_MAX triangles: the build's single node (k_single_node8) over the new scene bounds
+__global__ void k_refit_single(int n, Node8* __restrict__ nodes, const uint32_t* __restrict__ refit, Grid8 grid) {
+    if (threadIdx.x || blockIdx.x) return;
+    float sb[6];
+    const float pad = bounds_pad(refit, sb);
+    single_node8(n, sb, pad, nodes, grid);
+}
+} // namespace
+
+hipError_t pt_bvh_refit_alloc(PtBvh* b) {
+    if (PT8_NODE64) return hipErrorNotSupported; // the one-line nodes' origin grid is fixed to the scene bounds of the build
+    if (b->level_off.size() < 2 || b->level_off.back() != b->num_nodes8) return hipErrorInvalidValue;
+    if (!b->d_refit) HIPCHK(hipMalloc(&b->d_refit, sizeof(uint32_t) * 8));
+    if (!b->d_exact) HIPCHK(hipMalloc(&b->d_exact, sizeof(float) * 6 * (size_t)b->num_nodes8));
+    return hipSuccess;
+}
+hipError_t pt_bvh_refit_begin(PtBvh* b, const float* d_verts, const uint32_t* d_idx, uint32_t ntri, hipStream_t stream) {
+    HIPCHK(pt_bvh_refit_alloc(b));
+    const uint32_t init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
+    HIPCHK(hipMemcpyAsync(b->d_refit, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    const int B = 256;
+    hipLaunchKernelGGL(k_bounds, dim3(min((int)((ntri + B - 1) / B), 2048)), dim3(B), 0, stream, d_verts, d_idx, ntri, b->d_refit);
+    return hipGetLastError();
+}
+hipError_t pt_bvh_refit_nodes(PtBvh* b, hipStream_t stream) {
+    if (b->num_tris8 <= PT8_LEAF_MAX && b->num_nodes8 == 1) {
+        hipLaunchKernelGGL(k_refit_single, dim3(1), dim3(64), 0, stream, (int)b->num_tris8, const_cast<Node8*>(b->nodes8), b->d_refit, b->grid);
+        return hipGetLastError();
+    }
+    for (int d = (int)b->level_off.size() - 2; d >= 0; --d) { // ~8 small launches: the kernel boundary is the only ordering needed
+        const uint32_t first = b->level_off[d], count = b->level_off[d + 1] - first;
+        if (!count) continue;
+        hipLaunchKernelGGL(k_refit_nodes, dim3((count + 63) / 64), dim3(64), 0, stream, first, count, const_cast<Node8*>(b->nodes8), b->tris8, b->d_exact,
+                           b->num_nodes8, b->num_tris8, b->d_refit);
+    }
+    return hipGetLastError();
+}
+hipError_t pt_bvh_refit_end(PtBvh* b, hipStream_t stream) {
+    uint32_t h[8];
+    HIPCHK(hipMemcpyAsync(h, b->d_refit, sizeof(h), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (h[6]) {
+        fprintf(stderr, "[pt_bvh] refit bounds check failed: fault bits 0x%x (1 child node, 2 leaf triangles)\n", h[6]);
+        return hipErrorIllegalAddress;
+    }
+    b->pad = bounds_pad(h, b->bounds);
+    return hipSuccess;
 }

@@ -924,13 +924,38 @@ __global__ void k_accum_stats(const uint32_t* __restrict__ counters, int nq, int
 }
 
 // per leaf triangle: the geometric normal of __closesthit__radiance (:491) and the mesh, for k_shade
+PT_DEV float4 shade_normal(const LeafTri& tri) {
+    const v3 v0 = mk3(tri.t0.x, tri.t0.y, tri.t0.z), v1 = mk3(tri.t0.w, tri.t1.x, tri.t1.y), v2 = mk3(tri.t1.z, tri.t1.w, tri.t2.x);
+    const v3 N = normalize3(cross3(sub3(v1, v0), sub3(v2, v0)));
+    return make_float4(N.x, N.y, N.z, tri.t2.z);
+}
 __global__ void k_shade_normals(const LeafTri* __restrict__ tris, uint32_t n, float4* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const LeafTri tri = tris[i];
-    const v3 v0 = mk3(tri.t0.x, tri.t0.y, tri.t0.z), v1 = mk3(tri.t0.w, tri.t1.x, tri.t1.y), v2 = mk3(tri.t1.z, tri.t1.w, tri.t2.x);
-    const v3 N = normalize3(cross3(sub3(v1, v0), sub3(v2, v0)));
-    out[i] = make_float4(N.x, N.y, N.z, tri.t2.z);
+    out[i] = shade_normal(tris[i]);
+}
+// refit (pt_update_meshes): the vertex words of every leaf triangle from the moved vertices (primitive and mesh stay), and the side
+// arrays in leaf order with them — the shade normal, and for textured scenes the vertex words of the 64-byte record (its texcoords stay)
+__global__ void k_refit_leaves(const float* __restrict__ verts, const uint32_t* __restrict__ idx, uint32_t n, LeafTri* __restrict__ tris,
+                               float4* __restrict__ nrm, TexTri* __restrict__ textris /* null: untextured */) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    LeafTri t = tris[i];
+    const uint32_t p = (uint32_t)__float_as_int(t.t2.y);
+    const float* v0 = &verts[3 * (size_t)idx[3 * (size_t)p + 0]];
+    const float* v1 = &verts[3 * (size_t)idx[3 * (size_t)p + 1]];
+    const float* v2 = &verts[3 * (size_t)idx[3 * (size_t)p + 2]];
+    t.t0 = make_float4(v0[0], v0[1], v0[2], v1[0]);
+    t.t1 = make_float4(v1[1], v1[2], v2[0], v2[1]);
+    t.t2.x = v2[2];
+    tris[i] = t;
+    nrm[i] = shade_normal(t);
+    if (textris) {
+        TexTri& o = textris[i];
+        o.a = t.t0;
+        o.b = t.t1;
+        o.c.x = t.t2.x;
+    }
 }
 // pt_trace (the query entry point): closest-hit records hold leaf-triangle indices, the caller is given primitive indices
 __global__ void k_hits_to_prims(float2* __restrict__ hit, const LeafTri* __restrict__ tris, uint32_t n) {
@@ -1156,6 +1181,18 @@ __global__ void k_emit_textris(const LeafTri* __restrict__ tris, const PrimUV* _
     o.c = make_float4(t.t2.x, u.c0.x, u.c0.y, u.c1.x);
     o.d = make_float4(u.c1.y, u.c2.x, u.c2.y, 0.f);
     out[i] = o;
+}
+// rebuild (pt_update_meshes, PT_UPDATE_REBUILD) of a textured scene: the per-primitive texcoords back from the leaf-ordered records of the
+// old tree, for k_emit_textris over the new one (pt_create frees the PrimUV array once the records exist)
+__global__ void k_textris_to_uvs(const LeafTri* __restrict__ tris, const TexTri* __restrict__ textris, uint32_t n, PrimUV* __restrict__ uvs) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const TexTri o = textris[i];
+    PrimUV u;
+    u.c0 = make_float2(o.c.y, o.c.z);
+    u.c1 = make_float2(o.c.w, o.d.x);
+    u.c2 = make_float2(o.d.y, o.d.z);
+    uvs[__float_as_int(tris[i].t2.y)] = u;
 }
 __global__ void k_table_rng(const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

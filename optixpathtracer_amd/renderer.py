@@ -85,6 +85,19 @@ def _scene_desc(model: Model):
     return SceneDesc(meshes, len(model.meshes), tdesc, len(textures)), keep
 
 
+def _mesh_updates(vertices: dict):
+    """pt_mesh_update[] for {mesh_index: (num_vertices, 3) float32 array} plus the arrays it points into (keep them alive for the call)."""
+    ups = (_lib.MeshUpdate * max(1, len(vertices)))()
+    keep = []
+    for k, (mesh, v) in enumerate(vertices.items()):
+        v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+        keep.append(v)
+        ups[k].mesh = int(mesh)
+        ups[k].vertex = v.ctypes.data_as(C.POINTER(C.c_float))
+        ups[k].num_vertices = len(v)
+    return ups, len(vertices), keep
+
+
 class SampleRenderer:
     def __init__(self, model: Model, device: int = 0):
         self._L = L = _lib.load_library()
@@ -320,6 +333,15 @@ class SampleRenderer:
         self._ck(self._L.pt_export_bvh(self._ctx, nodes.ctypes.data, nodes.nbytes, tris.ctypes.data, tris.nbytes, None, None), "pt_export_bvh")
         return nodes, tris
 
+    def updateMeshes(self, vertices: dict, rebuild: bool = False) -> float:
+        """New vertex positions for some meshes ({mesh_index: (num_vertices, 3) array}, pt_update_meshes): the tree is refitted on the GPU,
+        or rebuilt with rebuild=True.  Waits for frames in flight; restart the accumulation at subframe 0 afterwards.  Returns kernel ms."""
+        ups, n, keep = _mesh_updates(vertices)
+        ms = C.c_double()
+        self._ck(self._L.pt_update_meshes(self._ctx, ups if n else None, n, _lib.PT_UPDATE_REBUILD if rebuild else _lib.PT_UPDATE_REFIT, C.byref(ms)), "pt_update_meshes")
+        del keep
+        return ms.value
+
     def trace(self, rays: np.ndarray, any_hit=False, iters=1):
         """optixTrace as a batch query: rays (n,8) = o.xyz,tmin,d.xyz,tmax → (t, prim) or occluded flags; + kernel ms."""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
@@ -423,6 +445,14 @@ class MultiRenderer:
         U, V, W = camera.UVWFrame()
         f3 = C.c_float * 3
         self._ck(self._L.pt_multi_set_camera(self._m, C.byref(f3(*[float(x) for x in camera.eye])), C.byref(f3(*[float(x) for x in U])), C.byref(f3(*[float(x) for x in V])), C.byref(f3(*[float(x) for x in W]))), "pt_multi_set_camera")
+
+    def updateMeshes(self, vertices: dict, rebuild: bool = False) -> float:
+        """SampleRenderer.updateMeshes on every rank (pt_multi_update_meshes); returns the slowest rank's kernel ms."""
+        ups, n, keep = _mesh_updates(vertices)
+        ms = C.c_double()
+        self._ck(self._L.pt_multi_update_meshes(self._m, ups if n else None, n, _lib.PT_UPDATE_REBUILD if rebuild else _lib.PT_UPDATE_REFIT, C.byref(ms)), "pt_multi_update_meshes")
+        del keep
+        return ms.value
 
     def render(self, out: np.ndarray | None = None):
         ptr = out.ctypes.data if out is not None else None
