@@ -137,7 +137,6 @@ struct pt_ctx {
     // set runs on its own pair of streams, so one chunk's kernel tails overlap with the other chunks' bulk work
     struct BatchSet {
         hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr;
-        hipStream_t shade_stream = nullptr; // PT_SHADE_CUS experiment: k_shade runs here (every CU) while `stream` is confined to the other CUs
         PathState st{}; // the arrays indexed by path slot; the stream pointers are filled per launch (stream_view)
         // what a path carries from bounce to bounce, in queue order (pt_kernels.h PathState): X[0] travels with queueA, X[1] with queueB
         // (the generate kernels write X[1]); the shadow records travel with squeue
@@ -173,20 +172,16 @@ struct pt_ctx {
     uint32_t* ovf = nullptr; // spill stacks for pt_trace queries
     unsigned long long* dbg = nullptr; // PT_DEBUG_COUNTS: traversal step counters of the last frame
     int trace_grid = 0;
-    int num_cus = 0;
     bool cam_packets = true; // camera rays as packets (PT_CAM_PACKETS=0 turns it off)
     uint64_t cam_min_paths = 1u << 19; // ... for launches of at least this many camera rays (PT_CAM_MIN_PATHS): a packet is one wave's work from start to end,
                                        // so a launch of a few thousand packets is as long as its longest packet (chunks of a 1/8 share of C3, 345 k rays: 1.93 against 1.84 ms per frame; 1/4 share, 690 k: 2.88 against 2.92)
-    int shade_cus = 0;       // PT_SHADE_CUS (experiment): CUs the chunk chains' streams may NOT use; k_shade launches go to unmasked streams
-    std::vector<hipStream_t> masked_streams; // [set]: the set's stream when shade_cus > 0 (set_streams[set] then carries its k_shade launches)
     int cam_grid = 0;        // PT_CAM_GRID (tuning hook): waves of a packet launch, 0 = the policy of launch_closest
     // the bounce loop of a small frame as ONE persistent kernel (pt_fused.h): PT_FUSED=0 never / 1 (default) synchronous frames of at most
     // fused_max_paths paths (PT_FUSED_MAX_PATHS), as one pass / 2 every pass the kernel covers, chunked as usual (tests); fused_cap: window entries per wave (PT_FUSED_CAP, a multiple of 64; default: 128 or 64 by frame size)
     int fused = 1;
     uint64_t fused_max_paths = 2500000;
     uint32_t fused_cap = 0; // 0: by frame size (enqueue_chunk)
-    float fused_max_cost = 22.f; // PT_FUSED_MAX_COST: fused_one_pass only for trees whose calibration rays cost at most this many steps (see render_enqueue)
-    bool fused_frame = false; // the frame being enqueued is one fused pass (render_enqueue)
+    float fused_max_cost = 22.f; // PT_FUSED_MAX_COST: fused_one_pass only for trees whose calibration rays cost at most this many steps (see sched_choose)
     // Which of the two schedules a synchronous frame takes is MEASURED (round 6): both leave the same bits, so for every frame configuration
     // (pixels owned x samples, depth limit, BSDF mode, size, partition) the context renders the first frames alternately as a launch chain and as
     // one fused pass — the first frame of each is warm-up, then `sched_trials` timed frames each (device time between the frame's begin and end
@@ -219,7 +214,6 @@ struct pt_ctx {
     uint32_t sched_flags = 0;      // pt_stats.schedule of the last synchronous frame
     int fused_grid = 0; // PT_FUSED_GRID: waves of the fused kernel (0: the traversal grid)
     int enqueue_threads = 1; // PT_ENQUEUE_THREADS: 0 one enqueue thread, 1 one thread per pixel chunk for small synchronous frames (default), 2 at every size
-    bool adapt_grid = false; // set around the enqueue of a whole frame (frames_in_flight = 3)
     int trace_grid_min = 2048, grid_chunks = 6; // PT_GRID_MIN / PT_GRID_CHUNKS (tuning hooks): smallest persistent grid, chunks of 64 paths per wave aimed at
     int lds_skip = 0; // PT_STACK_LDS_SKIP (test hook, pt_bvh8.h)
     int ovf_depth = 0; // spill levels of the traversal stack (PT8_OVF_DEPTH; test hook PT_STACK_CAP lowers the total capacity)
@@ -241,6 +235,7 @@ struct pt_ctx {
         hipEvent_t ev_begin = nullptr, ev_end = nullptr;
         uint64_t paths = 0, seq = 0;
         uint32_t subframes = 1; // subframes the slot's launch chain completes (pt_render_batch)
+        int nsets = 0;          // batch sets the frame used: render_finish sums their totals
         LaunchCounts lc;
     };
     Inflight fr[3];
@@ -536,8 +531,6 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
         if (const char* e = getenv("PT_CAM_PACKETS")) ctx->cam_packets = atoi(e) != 0;
         if (const char* e = getenv("PT_CAM_MIN_PATHS")) ctx->cam_min_paths = (uint64_t)atoll(e);
         if (const char* e = getenv("PT_CAM_GRID")) ctx->cam_grid = atoi(e);
-        if (const char* e = getenv("PT_SHADE_CUS")) ctx->shade_cus = std::max(0, std::min(prop.multiProcessorCount - 8, atoi(e)));
-        ctx->num_cus = prop.multiProcessorCount;
         if (const char* e = getenv("PT_ENQUEUE_THREADS")) ctx->enqueue_threads = atoi(e);
         if (const char* e = getenv("PT_FUSED")) ctx->fused = atoi(e);
         if (const char* e = getenv("PT_FUSED_MAX_PATHS")) ctx->fused_max_paths = strtoull(e, nullptr, 10);
@@ -613,7 +606,6 @@ extern "C" int pt_destroy(pt_ctx* ctx) {
     free_path_state(ctx);
     for (hipStream_t st : ctx->set_streams) if (st) hipStreamDestroy(st);
     for (hipStream_t st : ctx->side_streams) if (st) hipStreamDestroy(st);
-    for (hipStream_t st : ctx->masked_streams) if (st) hipStreamDestroy(st);
     free_frame(ctx);
     dfree(ctx->d_verts); dfree(ctx->d_idx); dfree(ctx->d_tri_mesh); dfree(ctx->d_mats);
     dfree(ctx->d_mesh_tex); dfree(ctx->d_uvs); dfree(ctx->d_textris); dfree(ctx->d_textures);
@@ -981,20 +973,8 @@ static int assign_streams(pt_ctx* ctx, int nsets) {
         if (!ctx->set_streams[i]) CK(stream_create(&ctx->set_streams[i]));
         if (!ctx->side_streams[2 * i]) CK(stream_create(&ctx->side_streams[2 * i]));
         if (async && !ctx->side_streams[2 * i + 1]) CK(stream_create(&ctx->side_streams[2 * i + 1]));
-        if (ctx->shade_cus > 0) { // experiment: the chain's stream is a queue of its own with a CU mask, the probed stream carries k_shade
-            if ((int)ctx->masked_streams.size() <= i) ctx->masked_streams.resize(i + 1, nullptr);
-            if (!ctx->masked_streams[i]) {
-                std::vector<uint32_t> mask((size_t)(ctx->num_cus + 31) / 32, 0u);
-                for (int c = 0; c < ctx->num_cus - ctx->shade_cus; ++c) mask[c / 32] |= 1u << (c % 32);
-                CK(hipExtStreamCreateWithCUMask(&ctx->masked_streams[i], (uint32_t)mask.size(), mask.data()));
-            }
-        }
         if (i < (int)ctx->sets.size()) {
             ctx->sets[i].stream = ctx->set_streams[i];
-            if (ctx->shade_cus > 0) {
-                ctx->sets[i].stream = ctx->masked_streams[i];
-                ctx->sets[i].shade_stream = ctx->set_streams[i];
-            }
             ctx->sets[i].stream2 = ctx->side_streams[2 * i];
             ctx->sets[i].stream3 = ctx->side_streams[2 * i + 1];
         }
@@ -1113,24 +1093,12 @@ static PathState stream_view(const pt_ctx::BatchSet& bs, int k) {
     return s;
 }
 template <int MODE>
-static void launch_shade(pt_ctx* ctx, pt_ctx::BatchSet& bs, const PathState& st, const ShadeParams& sp) {
+static void launch_shade(const pt_ctx* ctx, hipStream_t s, const PathState& st, const ShadeParams& sp) {
     const unsigned lds = (unsigned)shade_lds_bytes(sp.probe);
-    hipStream_t s = bs.stream;
-    if (bs.shade_stream) { // PT_SHADE_CUS experiment: behind the chain's last launch, on the stream that may use every CU
-        hipEvent_t e = next_event(ctx);
-        hipEventRecord(e, bs.stream);
-        s = bs.shade_stream;
-        hipStreamWaitEvent(s, e, 0);
-    }
     if (ctx->has_catcher)
         hipLaunchKernelGGL((k_shade<MODE, true>), dim3(GRID), dim3(256), lds, s, st, sp);
     else
         hipLaunchKernelGGL((k_shade<MODE, false>), dim3(GRID), dim3(256), lds, s, st, sp);
-    if (bs.shade_stream) {
-        hipEvent_t e = next_event(ctx);
-        hipEventRecord(e, s);
-        hipStreamWaitEvent(bs.stream, e, 0);
-    }
 }
 
 // Closest-hit launch of a bounce chain.  The identity queue of bounce 0 holds camera rays in pixel-block order: they are traversed as
@@ -1165,17 +1133,110 @@ struct RegionJob { // non-null: one launch-index range of a foveated launch inst
     VariantParams var;
     uint32_t l0, nl;
 };
+// what the frame decided for all of its chunks (render_enqueue)
+struct ChunkMode {
+    bool fused_frame = false; // the frame is one fused pass
+    bool adapt_grid = false;  // whole frames in flight (frames_in_flight = 3): traversal grids sized by the pass
+};
+
+// When the chunks of a frame may be enqueued by worker threads (PT_ENQUEUE_THREADS): only when the branches of enqueue_chunk they take
+// record no events and touch no ctx state other than the locked launch error.  Span timing records events around every launch group, the
+// split and asynchronous shadow placements record events for their stream hand-offs, a resolve that waits for earlier frames reads the
+// frame's event list, and two chunks on one batch set would share its streams and counters.
+static bool chunks_threadable(const pt_ctx* ctx, uint32_t nchunks, int nsets, bool waits_before_resolve) {
+    return !ctx->span_timing() && ctx->opt.split_shadow == 0 && !waits_before_resolve && nchunks <= (uint32_t)nsets;
+}
+
+// the fused bounce loop of one pass (pt_fused.h)
+static void launch_path_loop(const pt_ctx* ctx, hipStream_t s, unsigned grid, const PathLoopArgs& pa) {
+    if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_path_loop<PT_BSDF_LAMBERT>), dim3(grid), dim3(64), 0, s, pa);
+    else hipLaunchKernelGGL((k_path_loop<PT_BSDF_DISNEY>), dim3(grid), dim3(64), 0, s, pa);
+}
+
+// One sample pass of a chunk's bounce chain: what all its launches share, built once per pass; the builders take what varies per launch.
+// X[sin] holds the state of the queue being traced / shaded (qcur), X[sin ^ 1] receives the next queue's; rotate() moves on one bounce.
+// Traversal launches of bounce b use work counter b (closest hit) and nq + b (shadow).
+struct ChainPass {
+    pt_ctx* ctx;
+    pt_ctx::BatchSet& bs;
+    Bvh8Dev bvh8;
+    int cull;
+    float tmin;
+    unsigned tgrid;
+    uint64_t pass_paths;
+    uint32_t* cntA; // radiance queue counters, per bounce
+    uint32_t* cntS; // shadow queue counters, per bounce
+    uint32_t* work; // work counters of the persistent traversal
+    int nq;
+    LaunchCounts& lc;
+    QView qcur;
+    uint32_t* qnext_base;
+    int sin;
+
+    Trace8Args trace_args(int k, QView q, QView q2, int wslot, uint32_t* ovf, unsigned long long* dbg, int bounce) const {
+        Trace8Args ta{stream_view(bs, k), bvh8, q, q2, work + (size_t)wslot * PT_WSTRIDE, ovf, cull, dbg, bounce, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
+        return ta;
+    }
+    // (the hit records index the leaf triangles of the structure that was traversed)
+    ShadeParams shade_params(QView q, QView next, QView shadow, const pt_ctx::BatchSet::StreamBuf* out, int aov, int first) const {
+        ShadeParams sp{ctx->bvh.tris8, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin, q, next, shadow,
+                       out ? out->rayO : nullptr, out ? out->rayD : nullptr, out ? out->thr : nullptr, out ? out->rf : nullptr, aov, first};
+        return sp;
+    }
+    void closest(int k, QView q, int b, unsigned long long* dbg) {
+        SpanGuard g(ctx, CLS_TRACE, bs.stream);
+        launch_closest(ctx, bs.stream, trace_args(k, q, QView{}, b, bs.ovf, dbg, 0), tgrid, pass_paths);
+        ++lc.trace;
+    }
+    void shade(QView next, QView shadow, int aov, int first) {
+        const ShadeParams sp = shade_params(qcur, next, shadow, &bs.X[sin ^ 1], aov, first);
+        SpanGuard g(ctx, CLS_SHADE, bs.stream);
+        if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) launch_shade<PT_BSDF_LAMBERT>(ctx, bs.stream, stream_view(bs, sin), sp);
+        else launch_shade<PT_BSDF_DISNEY>(ctx, bs.stream, stream_view(bs, sin), sp);
+        ++lc.shade;
+    }
+    void shadow(hipStream_t s, QView q, int b, uint32_t* ovf, unsigned long long* dbg, int bounce) {
+        SpanGuard g(ctx, CLS_SHADOW, s);
+        launch_trace8<TR_SHADOW_APPLY>(s, tgrid, trace_args(sin, q, QView{}, nq + b, ovf, dbg, bounce));
+        ++lc.shadow;
+    }
+    // shadow rays on a side stream, behind the k_shade that wrote them; returns the event behind them
+    hipEvent_t side_shadow(hipStream_t s, QView q, int b, uint32_t* ovf, int bounce) {
+        hipEvent_t ev_shaded = next_event(ctx);
+        hipEventRecord(ev_shaded, bs.stream);
+        hipStreamWaitEvent(s, ev_shaded, 0);
+        shadow(s, q, b, ovf, nullptr, bounce);
+        hipEvent_t done = next_event(ctx);
+        hipEventRecord(done, s);
+        return done;
+    }
+    void rotate(QView next) {
+        qcur = next;
+        qnext_base = (qnext_base == bs.queueA) ? bs.queueB : bs.queueA;
+        sin ^= 1;
+    }
+};
 
 // spp: samples of the whole chunk = samples_per_launch x subframes of the batch (pt_render_batch; a foveated launch: its own spp),
 // S: samples per pass
-static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& fp, uint32_t pix0, uint32_t npix, uint32_t spp, uint32_t S,
+static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& fp, uint32_t pix0, uint32_t npix, uint32_t spp, uint32_t S, ChunkMode mode,
                           LaunchCounts& lc, const RegionJob* job = nullptr, const std::vector<hipEvent_t>* before_resolve = nullptr) {
     const int nq = ctx->nq;
-    const float tmin_rad = job ? job->var.radiance_tmin : 0.001f;
-    const int cull = job ? job->var.cull_back_occlusion : 0;
-    const Bvh8Dev bvh8 = bvh_dev(ctx);
-    const LeafTri* shade_tris = ctx->bvh.tris8; // the hit records index the leaf triangles of the structure that was traversed
     const size_t CS = (size_t)PT_NSUB * PT_CSTRIDE;
+    const size_t qsize = (size_t)PT_NSUB * ctx->sub_cap;
+    const bool fused = !job && ctx->opt.split_shadow == 0 && !ctx->cap_async && !ctx->has_catcher && (ctx->fused == 2 || mode.fused_frame);
+    // Where the shadow rays of bounce b are traced.  Unified (default): in the traversal launch of bounce b+1's closest-hit rays (per-lane
+    // ray type), so the long-ray tail of one kind is filled with rays of the other and a frame has max_depth+1 traversal launches instead of
+    // 2*max_depth.  Split (split_shadow = 1): on the set's second stream, concurrently with the next bounce's closest-hit traversal (both only
+    // read the ray arrays); the next shade waits for both.  Async (split_shadow = 2): from their own records on one of two side streams as
+    // soon as k_shade(b) has written them, and nothing waits for them before k_resolve.
+    enum { UNIFIED, SPLIT, ASYNC } const placement = ctx->cap_async ? ASYNC : ctx->opt.split_shadow == 0 ? UNIFIED : SPLIT;
+    // depth d = 0..max_depth traces in the reference (the trace at depth == max_depth can only matter
+    // through a shadow-catcher pass-through or alpha; without catcher materials it is provably dead and skipped)
+    // (a foveated launch of the sv / sv2 variants starts its paths at depth 1: that many fewer bounces are live)
+    const int depth0 = job ? job->var.initial_depth : 0;
+    const int last_bounce = (ctx->has_catcher ? ctx->opt.max_depth : ctx->opt.max_depth - 1) - depth0;
+    const int aov = job ? (job->var.write_aov && job->var.initial_depth == 0 ? 1 : 0) : 1;
     for (uint32_t s0 = 0; s0 < spp; s0 += S) {
         const uint32_t Sc = std::min(S, spp - s0);
         // Persistent traversal waves of this pass's launches.  A synchronous frame wants the full grid (5 waves per SIMD): its latency is what
@@ -1184,33 +1245,14 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
         // ≈ 6 chunks of 64 of the pass's paths per wave
         const uint64_t pass_paths = job ? (uint64_t)job->nl * spp : (uint64_t)npix * Sc;
         // (never above trace_grid: the spill stacks are sized for trace_grid waves and the kernels are compiled for that occupancy)
-        const unsigned tgrid = !ctx->adapt_grid ? (unsigned)ctx->trace_grid
+        const unsigned tgrid = !mode.adapt_grid ? (unsigned)ctx->trace_grid
             : (unsigned)std::min<uint64_t>((uint64_t)ctx->trace_grid, std::max<uint64_t>((uint64_t)ctx->trace_grid_min, pass_paths / (64ull * (uint64_t)ctx->grid_chunks)));
         BatchParams bp{ctx->d_pixels + pix0, npix, s0, Sc, ctx->has_catcher ? 1 : 0, bs.pixResult, bs.pixAlpha, bs.pixNormal, bs.pixAlbedo};
         hipMemsetAsync(bs.counters, 0, sizeof(uint32_t) * counter_words(nq), bs.stream);
-        uint32_t* cntA = bs.counters;                       // radiance queue counters, per bounce
-        uint32_t* cntS = bs.counters + (size_t)nq * CS;     // shadow queue counters, per bounce
-        uint32_t* work = bs.counters + (size_t)2 * nq * CS; // work counters of the persistent traversal
-        QView qcur{nullptr, cntA, ctx->sub_cap};            // identity for bounce 0 (k_generate wrote the count)
-        if (job) qcur.base = bs.queueB;                     // foveated launch: only the paths inside the annulus are queued
-        const bool fused = !job && ctx->opt.split_shadow == 0 && !ctx->cap_async && !ctx->has_catcher && (ctx->fused == 2 || ctx->fused_frame);
-        if (!fused) {
-            SpanGuard g(ctx, CLS_OTHER, bs.stream);
-            if (job)
-                hipLaunchKernelGGL(k_generate_region, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, tmin_rad, (uint32_t)job->var.initial_depth, job->l0, job->nl, qcur);
-            else
-                hipLaunchKernelGGL(k_generate, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0);
-        }
-        uint32_t* qnext_base = bs.queueA;
-        int sin = 1; // X[sin] holds the state of the queue being traced / shaded, X[sin ^ 1] receives the next queue's
-        // depth d = 0..max_depth traces in the reference (the trace at depth == max_depth can only matter
-        // through a shadow-catcher pass-through or alpha; without catcher materials it is provably dead and skipped)
-        // (a foveated launch of the sv / sv2 variants starts its paths at depth 1: that many fewer bounces are live)
-        const int depth0 = job ? job->var.initial_depth : 0;
-        const int last_bounce = (ctx->has_catcher ? ctx->opt.max_depth : ctx->opt.max_depth - 1) - depth0;
-        hipEvent_t ev_shadow_done = nullptr;
-        const bool unified = ctx->opt.split_shadow == 0;
-        const bool async = ctx->cap_async;
+        ChainPass P{ctx, bs, bvh_dev(ctx), job ? job->var.cull_back_occlusion : 0, job ? job->var.radiance_tmin : 0.001f, tgrid, pass_paths,
+                    bs.counters, bs.counters + (size_t)nq * CS, bs.counters + (size_t)2 * nq * CS, nq, lc,
+                    // identity for bounce 0 (k_generate wrote the count); a foveated launch: only the paths inside the annulus are queued
+                    QView{job ? bs.queueB : nullptr, bs.counters, ctx->sub_cap}, bs.queueA, 1};
         if (fused) {
             // one persistent kernel instead of the chain below: every wave runs generate -> trace -> shade rounds on a private window of the
             // queue arrays (pt_fused.h); the windows of all waves fit the arrays (grid x cap <= the pass's paths, rounded up to whole waves)
@@ -1223,137 +1265,54 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
             const uint32_t cap = std::min<uint32_t>(ctx->fused_cap ? ctx->fused_cap : cap_auto, ((uint32_t)pass_paths + 63u) & ~63u);
             const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ctx->fused_grid > 0 ? std::min<unsigned>(tgrid, (unsigned)ctx->fused_grid) : tgrid, pass_paths / cap));
             PathLoopArgs pa{};
-            pa.ta = Trace8Args{stream_view(bs, 0), bvh8, QView{bs.queueA, nullptr, 0u}, QView{bs.squeue, nullptr, 0u}, work, bs.ovf, cull, ctx->dbg, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
+            pa.ta = P.trace_args(0, QView{bs.queueA, nullptr, 0u}, QView{bs.squeue, nullptr, 0u}, 0, bs.ovf, ctx->dbg, 0);
             pa.rayO1 = bs.X[1].rayO; pa.rayD1 = bs.X[1].rayD; pa.thr1 = bs.X[1].thr; pa.hit1 = bs.X[1].hit; pa.rf1 = bs.X[1].rf;
             pa.qbase1 = bs.queueB;
-            pa.sp = ShadeParams{shade_tris, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin_rad, QView{}, QView{}, QView{}, nullptr, nullptr, nullptr, nullptr, 1, 0};
+            pa.sp = P.shade_params(QView{}, QView{}, QView{}, nullptr, 1, 0);
             pa.fp = fp;
             pa.bp = bp;
-            pa.pool = work; // the first traversal launch's chunk counter, unused here (zeroed with the pass's counters)
+            pa.pool = P.work; // the first traversal launch's chunk counter, unused here (zeroed with the pass's counters)
             pa.cap = cap;
             pa.totals = bs.totals;
-            if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_path_loop<PT_BSDF_LAMBERT>), dim3(grid), dim3(64), 0, bs.stream, pa);
-            else hipLaunchKernelGGL((k_path_loop<PT_BSDF_DISNEY>), dim3(grid), dim3(64), 0, bs.stream, pa);
+            launch_path_loop(ctx, bs.stream, grid, pa);
             ++lc.trace;
             ++lc.fused;
-        } else if (async) {
-            // The bounce chain holds closest-hit launches only; the shadow rays of bounce b are traced from their own records
-            // on one of two side streams as soon as k_shade(b) has written them, and nothing waits for them before k_resolve.
-            const size_t qsize = (size_t)PT_NSUB * ctx->sub_cap;
-            std::vector<hipEvent_t> shadow_done;
+        } else {
             {
-                SpanGuard g(ctx, CLS_TRACE, bs.stream);
-                Trace8Args ta{stream_view(bs, sin), bvh8, qcur, QView{}, work, bs.ovf, cull, ctx->dbg, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                launch_closest(ctx, bs.stream, ta, tgrid, pass_paths);
-                ++lc.trace;
+                SpanGuard g(ctx, CLS_OTHER, bs.stream);
+                if (job)
+                    hipLaunchKernelGGL(k_generate_region, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, P.tmin, (uint32_t)job->var.initial_depth, job->l0, job->nl, P.qcur);
+                else
+                    hipLaunchKernelGGL(k_generate, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0);
             }
+            hipEvent_t ev_shadow_done = nullptr; // split: behind the previous bounce's shadow rays
+            std::vector<hipEvent_t> shadow_done; // async: behind every bounce's shadow rays
+            if (placement != SPLIT) P.closest(P.sin, P.qcur, 0, ctx->dbg);
             for (int b = 0; b <= last_bounce; ++b) {
-                QView qnext{qnext_base, cntA + (size_t)(b + 1) * CS, ctx->sub_cap};
-                QView qshadow{bs.squeueB + (size_t)b * qsize, cntS + (size_t)b * CS, ctx->sub_cap};
-                ShadeParams sp{shade_tris, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin_rad, qcur, qnext, qshadow, bs.X[sin ^ 1].rayO, bs.X[sin ^ 1].rayD, bs.X[sin ^ 1].thr, bs.X[sin ^ 1].rf, job ? (job->var.write_aov && job->var.initial_depth == 0 ? 1 : 0) : 1, (b == 0) ? 1 : 0};
-                {
-                    SpanGuard g(ctx, CLS_SHADE, bs.stream);
-                    if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) launch_shade<PT_BSDF_LAMBERT>(ctx, bs, stream_view(bs, sin), sp);
-                    else launch_shade<PT_BSDF_DISNEY>(ctx, bs, stream_view(bs, sin), sp);
-                    ++lc.shade;
+                const QView qnext{P.qnext_base, P.cntA + (size_t)(b + 1) * CS, ctx->sub_cap};
+                const QView qshadow{placement == ASYNC ? bs.squeueB + (size_t)b * qsize : bs.squeue, P.cntS + (size_t)b * CS, ctx->sub_cap};
+                if (placement == SPLIT) {
+                    P.closest(P.sin, P.qcur, b, nullptr);
+                    if (ev_shadow_done) hipStreamWaitEvent(bs.stream, ev_shadow_done, 0); // shade overwrites what shadow(b-1) reads
                 }
-                {
-                    hipEvent_t ev_shaded = next_event(ctx);
-                    hipEventRecord(ev_shaded, bs.stream);
-                    hipStream_t ss = (b & 1) ? bs.stream3 : bs.stream2;
-                    hipStreamWaitEvent(ss, ev_shaded, 0);
-                    {
-                        SpanGuard g(ctx, CLS_SHADOW, ss);
-                        Trace8Args ta{stream_view(bs, sin), bvh8, qshadow, QView{}, work + (size_t)(nq + b) * PT_WSTRIDE, (b & 1) ? bs.ovf3 : bs.ovf2, cull, nullptr, b, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                        hipLaunchKernelGGL((k_trace8<TR_SHADOW_APPLY>), dim3(tgrid), dim3(64), 0, ss, ta);
-                        ++lc.shadow;
-                    }
-                    hipEvent_t ev = next_event(ctx);
-                    hipEventRecord(ev, ss);
-                    shadow_done.push_back(ev);
-                }
-                if (b < last_bounce) {
+                P.shade(qnext, qshadow, aov, (b == 0) ? 1 : 0);
+                if (placement == SPLIT) {
+                    ev_shadow_done = P.side_shadow(bs.stream2, qshadow, b, bs.ovf2, 0);
+                } else if (placement == ASYNC) {
+                    shadow_done.push_back(P.side_shadow((b & 1) ? bs.stream3 : bs.stream2, qshadow, b, (b & 1) ? bs.ovf3 : bs.ovf2, b));
+                    if (b < last_bounce) P.closest(P.sin ^ 1, qnext, b + 1, ctx->dbg);
+                } else if (b < last_bounce) {
                     SpanGuard g(ctx, CLS_TRACE, bs.stream);
-                    Trace8Args ta{stream_view(bs, sin ^ 1), bvh8, qnext, QView{}, work + (size_t)(b + 1) * PT_WSTRIDE, bs.ovf, cull, ctx->dbg, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                    launch_closest(ctx, bs.stream, ta, tgrid, pass_paths);
-                    ++lc.trace;
-                }
-                qcur = qnext;
-                qnext_base = (qnext_base == bs.queueA) ? bs.queueB : bs.queueA;
-                sin ^= 1;
-            }
-            for (hipEvent_t e : shadow_done) hipStreamWaitEvent(bs.stream, e, 0);
-        } else if (unified) {
-            // One traversal launch per bounce: the closest-hit rays of bounce b+1 and the shadow rays of bounce b share
-            // a persistent kernel (per-lane ray type), so the long-ray tail of one kind is filled with rays of the other
-            // and a frame has max_depth+1 traversal launches instead of 2*max_depth.
-            {
-                SpanGuard g(ctx, CLS_TRACE, bs.stream);
-                Trace8Args ta{stream_view(bs, sin), bvh8, qcur, QView{}, work, bs.ovf, cull, ctx->dbg, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                launch_closest(ctx, bs.stream, ta, tgrid, pass_paths);
-                ++lc.trace;
-            }
-            for (int b = 0; b <= last_bounce; ++b) {
-                QView qnext{qnext_base, cntA + (size_t)(b + 1) * CS, ctx->sub_cap};
-                QView qshadow{bs.squeue, cntS + (size_t)b * CS, ctx->sub_cap};
-                ShadeParams sp{shade_tris, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin_rad, qcur, qnext, qshadow, bs.X[sin ^ 1].rayO, bs.X[sin ^ 1].rayD, bs.X[sin ^ 1].thr, bs.X[sin ^ 1].rf, job ? (job->var.write_aov && job->var.initial_depth == 0 ? 1 : 0) : 1, (b == 0) ? 1 : 0};
-                {
-                    SpanGuard g(ctx, CLS_SHADE, bs.stream);
-                    if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) launch_shade<PT_BSDF_LAMBERT>(ctx, bs, stream_view(bs, sin), sp);
-                    else launch_shade<PT_BSDF_DISNEY>(ctx, bs, stream_view(bs, sin), sp);
-                    ++lc.shade;
-                }
-                if (b < last_bounce) {
-                    SpanGuard g(ctx, CLS_TRACE, bs.stream);
-                    Trace8Args ta{stream_view(bs, sin ^ 1), bvh8, qnext, qshadow, work + (size_t)(b + 1) * PT_WSTRIDE, bs.ovf, cull, ctx->dbg, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                    launch_trace8<TR_UNIFIED>(bs.stream, tgrid, ta);
+                    launch_trace8<TR_UNIFIED>(bs.stream, tgrid, P.trace_args(P.sin ^ 1, qnext, qshadow, b + 1, bs.ovf, ctx->dbg, 0));
                     ++lc.trace;
                 } else {
-                    SpanGuard g(ctx, CLS_SHADOW, bs.stream);
-                    Trace8Args ta{stream_view(bs, sin), bvh8, qshadow, QView{}, work + (size_t)(nq + b) * PT_WSTRIDE, bs.ovf, cull, ctx->dbg, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                    launch_trace8<TR_SHADOW_APPLY>(bs.stream, tgrid, ta);
-                    ++lc.shadow;
+                    P.shadow(bs.stream, qshadow, b, bs.ovf, ctx->dbg, 0);
                 }
-                qcur = qnext;
-                qnext_base = (qnext_base == bs.queueA) ? bs.queueB : bs.queueA;
-                sin ^= 1;
+                P.rotate(qnext);
             }
-        } else
-        for (int b = 0; b <= last_bounce; ++b) {
-            QView qnext{qnext_base, cntA + (size_t)(b + 1) * CS, ctx->sub_cap};
-            QView qshadow{bs.squeue, cntS + (size_t)b * CS, ctx->sub_cap};
-            {
-                SpanGuard g(ctx, CLS_TRACE, bs.stream);
-                Trace8Args ta{stream_view(bs, sin), bvh8, qcur, QView{}, work + (size_t)b * PT_WSTRIDE, bs.ovf, cull, nullptr, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                launch_closest(ctx, bs.stream, ta, tgrid, pass_paths);
-                ++lc.trace;
-            }
-            ShadeParams sp{shade_tris, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin_rad, qcur, qnext, qshadow, bs.X[sin ^ 1].rayO, bs.X[sin ^ 1].rayD, bs.X[sin ^ 1].thr, bs.X[sin ^ 1].rf, job ? (job->var.write_aov && job->var.initial_depth == 0 ? 1 : 0) : 1, (b == 0) ? 1 : 0};
-            if (ev_shadow_done) hipStreamWaitEvent(bs.stream, ev_shadow_done, 0); // shade overwrites what shadow(b-1) reads
-            {
-                SpanGuard g(ctx, CLS_SHADE, bs.stream);
-                if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) launch_shade<PT_BSDF_LAMBERT>(ctx, bs, stream_view(bs, sin), sp);
-                else launch_shade<PT_BSDF_DISNEY>(ctx, bs, stream_view(bs, sin), sp);
-                ++lc.shade;
-            }
-            {
-                // shadow rays of this bounce run on the set's second stream, concurrently with the next bounce's
-                // closest-hit traversal (both only read the ray arrays); the next shade waits for both
-                hipEvent_t ev_shaded = next_event(ctx);
-                hipEventRecord(ev_shaded, bs.stream);
-                hipStreamWaitEvent(bs.stream2, ev_shaded, 0);
-                SpanGuard g(ctx, CLS_SHADOW, bs.stream2);
-                Trace8Args ta{stream_view(bs, sin), bvh8, qshadow, QView{}, work + (size_t)(nq + b) * PT_WSTRIDE, bs.ovf2, cull, nullptr, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                hipLaunchKernelGGL((k_trace8<TR_SHADOW_APPLY>), dim3(tgrid), dim3(64), 0, bs.stream2, ta);
-                ++lc.shadow;
-            }
-            ev_shadow_done = next_event(ctx);
-            hipEventRecord(ev_shadow_done, bs.stream2);
-            qcur = qnext;
-            qnext_base = (qnext_base == bs.queueA) ? bs.queueB : bs.queueA;
-                sin ^= 1;
+            if (ev_shadow_done) hipStreamWaitEvent(bs.stream, ev_shadow_done, 0);
+            for (hipEvent_t e : shadow_done) hipStreamWaitEvent(bs.stream, e, 0);
         }
-        if (ev_shadow_done) hipStreamWaitEvent(bs.stream, ev_shadow_done, 0);
         if (ctx->has_catcher) {
             // A secondary hit on a shadow-catcher surface passes through WITHOUT consuming depth (--prd->depth, deviceProgram.cu:503-508),
             // so a path with k pass-throughs is traced max_depth+1+k times by the reference's raygen loop (:411-443).  The chain
@@ -1363,41 +1322,23 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
             int cur = e0;
             for (int guard = 0; guard < 4096; ++guard) {
                 uint32_t hc[PT_NSUB * PT_CSTRIDE];
-                if (hipMemcpyAsync(hc, cntA + (size_t)cur * CS, sizeof(hc), hipMemcpyDeviceToHost, bs.stream) != hipSuccess) break;
+                if (hipMemcpyAsync(hc, P.cntA + (size_t)cur * CS, sizeof(hc), hipMemcpyDeviceToHost, bs.stream) != hipSuccess) break;
                 if (hipStreamSynchronize(bs.stream) != hipSuccess) break;
                 unsigned long long left = 0;
                 for (int q = 0; q < PT_NSUB; ++q) left += hc[q * PT_CSTRIDE];
                 if (left == 0) break;
                 const int nxt = (cur == e0 + 1) ? e0 + 2 : e0 + 1;
-                hipMemsetAsync(cntA + (size_t)nxt * CS, 0, sizeof(uint32_t) * CS, bs.stream);
-                hipMemsetAsync(cntS + (size_t)cur * CS, 0, sizeof(uint32_t) * CS, bs.stream);
-                hipMemsetAsync(work + (size_t)cur * PT_WSTRIDE, 0, sizeof(uint32_t) * PT_WSTRIDE, bs.stream);
-                hipMemsetAsync(work + (size_t)(nq + cur) * PT_WSTRIDE, 0, sizeof(uint32_t) * PT_WSTRIDE, bs.stream);
-                QView qnext{qnext_base, cntA + (size_t)nxt * CS, ctx->sub_cap};
-                QView qshadow{bs.squeue, cntS + (size_t)cur * CS, ctx->sub_cap};
-                {
-                    SpanGuard g(ctx, CLS_TRACE, bs.stream);
-                    Trace8Args ta{stream_view(bs, sin), bvh8, qcur, QView{}, work + (size_t)cur * PT_WSTRIDE, bs.ovf, cull, nullptr, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                    launch_closest(ctx, bs.stream, ta, tgrid, pass_paths);
-                    ++lc.trace;
-                }
-                ShadeParams sp{shade_tris, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin_rad, qcur, qnext, qshadow, bs.X[sin ^ 1].rayO, bs.X[sin ^ 1].rayD, bs.X[sin ^ 1].thr, bs.X[sin ^ 1].rf, 1, 0};
-                {
-                    SpanGuard g(ctx, CLS_SHADE, bs.stream);
-                    if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) launch_shade<PT_BSDF_LAMBERT>(ctx, bs, stream_view(bs, sin), sp);
-                    else launch_shade<PT_BSDF_DISNEY>(ctx, bs, stream_view(bs, sin), sp);
-                    ++lc.shade;
-                }
-                {
-                    SpanGuard g(ctx, CLS_SHADOW, bs.stream);
-                    Trace8Args ta{stream_view(bs, sin), bvh8, qshadow, QView{}, work + (size_t)(nq + cur) * PT_WSTRIDE, bs.ovf, cull, nullptr, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(bs), ctx->bvh.num_nodes8};
-                    hipLaunchKernelGGL((k_trace8<TR_SHADOW_APPLY>), dim3(tgrid), dim3(64), 0, bs.stream, ta);
-                    ++lc.shadow;
-                }
+                hipMemsetAsync(P.cntA + (size_t)nxt * CS, 0, sizeof(uint32_t) * CS, bs.stream);
+                hipMemsetAsync(P.cntS + (size_t)cur * CS, 0, sizeof(uint32_t) * CS, bs.stream);
+                hipMemsetAsync(P.work + (size_t)cur * PT_WSTRIDE, 0, sizeof(uint32_t) * PT_WSTRIDE, bs.stream);
+                hipMemsetAsync(P.work + (size_t)(nq + cur) * PT_WSTRIDE, 0, sizeof(uint32_t) * PT_WSTRIDE, bs.stream);
+                const QView qnext{P.qnext_base, P.cntA + (size_t)nxt * CS, ctx->sub_cap};
+                const QView qshadow{bs.squeue, P.cntS + (size_t)cur * CS, ctx->sub_cap};
+                P.closest(P.sin, P.qcur, cur, nullptr);
+                P.shade(qnext, qshadow, 1, 0);
+                P.shadow(bs.stream, qshadow, cur, bs.ovf, nullptr, 0);
                 hipLaunchKernelGGL(k_accum_stats, dim3(1), dim3(64), 0, bs.stream, bs.counters + (size_t)cur * CS, nq, 1, 0, bs.totals);
-                qcur = qnext;
-                qnext_base = (qnext_base == bs.queueA) ? bs.queueB : bs.queueA;
-                sin ^= 1;
+                P.rotate(qnext);
                 cur = nxt;
             }
         }
@@ -1428,33 +1369,79 @@ static void begin_slot(pt_ctx* ctx, int slot) {
     for (size_t i = 0; i < ctx->sets.size(); ++i) ctx->sets[i].totals = totals_of(ctx, slot, (int)i);
 }
 
-// mode 0: synchronous frame (pixel chunks on all streams); 2: the same chunks without a frame-wide start; 3: the whole frame on one stream
-// count > 1 (pt_render_batch): the launch chain carries the rays of `count` consecutive subframes — generate / trace / shade launches are
-// count times as large, the resolve blends the subframes in order — and leaves the buffers `count` frames would have left.
-static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, int slot = 0, int mode = 0, uint32_t count = 1) {
-    const bool pipelined = mode != 0, whole = mode == 3;
+// The start of every frame's enqueue (render_enqueue, regions_enqueue): a synchronous frame waits for the frames in flight, the slot is
+// emptied, then the checks — bad_args is the caller's own argument check.  PT_OK with ctx->width == 0: not resized yet, nothing to render
+// (SimplePathtracer.cpp:77).
+static int frame_open(pt_ctx* ctx, int slot, bool pipelined, const char* what, const char* bad_args) {
     if (!pipelined) {
         int rc = drain(ctx);
         if (rc) return rc;
     }
     ctx->fr[slot].active = 0;
-    if (ctx->width == 0) return PT_OK; // not resized yet (SimplePathtracer.cpp:77)
-    if (spp == 0 || spp > 4096) return fail(ctx, PT_ERR_INVALID, "pt_render: samples_per_launch must be in [1,4096]");
-    if (count == 0 || count > 4096 || (uint64_t)subframe_index + count > 0xffffffffull) return fail(ctx, PT_ERR_INVALID, "pt_render_batch: count must be in [1,4096] and the subframe indices must fit 32 bits");
-    const uint32_t vspp = spp * count; // samples of a pixel over the whole batch
-    if (!ctx->probe.data) return fail(ctx, PT_ERR_INVALID, "pt_render: no probe set (setProbe)");
+    if (ctx->width == 0) return PT_OK;
+    if (bad_args) return fail(ctx, PT_ERR_INVALID, bad_args);
+    if (!ctx->probe.data) return fail(ctx, PT_ERR_INVALID, (std::string(what) + ": no probe set (setProbe)").c_str());
     CK(hipSetDevice(ctx->device));
-    const uint32_t owned = ctx->owned;
-    // Chunking.  All samples of a pixel stay in one pixel chunk.  The frame is cut into (at least) `streams` pixel
-    // chunks that run concurrently on separate stream pairs; a chunk holds at most max_paths/streams paths, so
-    // samples are split when spp*pixels exceed that; shadow-catcher scenes run one sample per pass so that the
-    // per-pixel normal/albedo sums keep the reference order.  None of this changes a bit of the result.
-    // PT_FUSED=1: a frame small enough for the fused bounce loop (pt_fused.h) is ONE pass on one stream — the persistent waves of one fused
-    // kernel fill the chip, so three chunk kernels would only run one after the other
-    // (pt_options.streams set by the caller is respected: the chain on that many chunk streams).  Scenes whose rays are expensive and heavy-tailed keep
-    // the chain: every round of every fused wave ends with its own slowest ray, and on the stadium (27 steps per calibration ray; terrain 14) a
-    // 1/8 share runs 7-13 % slower fused while the terrain, the textured terrain and the Cornell box run 3-11 % faster (profiles/r5_14_fused_bounce_loop.md).
-    // One scene family on either side of the threshold: a rule of thumb, PT_FUSED_MAX_COST moves it.
+    return PT_OK;
+}
+// The frame's start in its slot: the totals of its `nsets` sets are cleared and ev_begin is recorded.  A synchronous frame does both on the
+// context's stream and its sets wait for it; a frame in flight has no frame-wide start: every set clears its own counters behind its own
+// previous chunk and goes on; a whole frame (frames_in_flight = 3) does both on its one stream `whole`.
+static int frame_begin(pt_ctx* ctx, int slot, bool pipelined, int nsets, hipStream_t whole, hipEvent_t* ev_begin) {
+    begin_slot(ctx, slot);
+    *ev_begin = next_event(ctx);
+    if (!pipelined || whole) {
+        hipStream_t s = whole ? whole : ctx->stream;
+        CK(hipMemsetAsync(totals_of(ctx, slot, 0), 0, sizeof(unsigned long long) * PT_MAX_SETS * 4, s));
+        CK(hipEventRecord(*ev_begin, s));
+        if (!whole)
+            for (int i = 0; i < nsets; ++i) hipStreamWaitEvent(ctx->sets[i].stream, *ev_begin, 0); // (the context may hold more sets than this frame uses)
+    } else {
+        for (int i = 0; i < nsets; ++i) CK(hipMemsetAsync(ctx->sets[i].totals, 0, sizeof(unsigned long long) * 4, ctx->sets[i].stream));
+        CK(hipEventRecord(*ev_begin, nsets ? ctx->sets[0].stream : ctx->stream));
+    }
+    return PT_OK;
+}
+// The frame's end: the streams of its sets fan in to the context's stream (a whole frame stays on `whole`: the context's own stream keeps
+// out of the way, one hardware queue fewer), the totals are copied out and ev_end recorded behind them, and the slot is filled in for
+// render_finish, which sums the totals of the frame's `nsets` sets.  resolved_kind >= 0: later frames order their resolves behind ev_end.
+static int frame_close(pt_ctx* ctx, int slot, hipEvent_t ev_begin, int nsets, hipStream_t whole, int resolved_kind, uint64_t paths, uint32_t subframes,
+                       const LaunchCounts& lc) {
+    hipStream_t end_stream = whole ? whole : ctx->stream;
+    if (!whole)
+        for (int i = 0; i < nsets; ++i) {
+            hipEvent_t e = next_event(ctx);
+            hipEventRecord(e, ctx->sets[i].stream);
+            hipStreamWaitEvent(ctx->stream, e, 0);
+        }
+    CK(hipMemcpyAsync(ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4, totals_of(ctx, slot, 0), sizeof(unsigned long long) * PT_MAX_SETS * 4, hipMemcpyDeviceToHost, end_stream));
+    hipEvent_t ev_end = next_event(ctx);
+    CK(hipEventRecord(ev_end, end_stream));
+    if (resolved_kind >= 0) {
+        ctx->ev_resolved = ev_end;
+        ctx->resolved_kind = resolved_kind;
+    }
+    pt_ctx::Inflight& fr = ctx->fr[slot];
+    fr.ev_begin = ev_begin;
+    fr.ev_end = ev_end;
+    fr.active = 1;
+    fr.nsets = nsets;
+    fr.paths = paths;
+    fr.subframes = subframes;
+    fr.lc = lc;
+    fr.seq = ++ctx->frame_seq;
+    return PT_OK;
+}
+
+// Whether a frame of `owned` pixels x `vspp` samples runs as ONE fused pass (pt_fused.h) instead of the launch chain.
+// PT_FUSED=1: a frame small enough for the fused bounce loop is ONE pass on one stream — the persistent waves of one fused
+// kernel fill the chip, so three chunk kernels would only run one after the other
+// (pt_options.streams set by the caller is respected: the chain on that many chunk streams).  Scenes whose rays are expensive and heavy-tailed keep
+// the chain: every round of every fused wave ends with its own slowest ray, and on the stadium (27 steps per calibration ray; terrain 14) a
+// 1/8 share runs 7-13 % slower fused while the terrain, the textured terrain and the Cornell box run 3-11 % faster (profiles/r5_14_fused_bounce_loop.md).
+// One scene family on either side of the threshold: a rule of thumb, PT_FUSED_MAX_COST moves it.  Synchronous frames that can take either
+// schedule take part in the measured trial (pt_ctx::sched); sched_record collects their times.
+static bool sched_choose(pt_ctx* ctx, bool pipelined, uint32_t owned, uint32_t vspp) {
     const uint64_t frame_paths = (uint64_t)owned * vspp;
     // what the fused pass needs at all: the default schedule of a scene without shadow-catcher materials, the whole frame in one batch set
     const bool fused_ok = ctx->fused == 1 && !pipelined && owned > 0 && ctx->opt.streams <= 0 && !ctx->has_catcher && ctx->opt.split_shadow == 0 && frame_paths <= ctx->opt.max_paths;
@@ -1479,72 +1466,101 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
         ctx->sched_pending.probe = probe;
     }
     if (!pipelined) ctx->sched_flags = (fused_one_pass ? 1u : 0u) | ((ctx->sched_pending.valid && ctx->sched.choice < 0) ? 0x100u : 0u);
-    ctx->fused_frame = fused_one_pass;
-    const int nsets = fused_one_pass ? 1 : std::max(1, std::min(PT_MAX_SETS, ctx->opt.streams > 0 ? ctx->opt.streams : 3));
+    return fused_one_pass;
+}
+// the device time of a frame that took part in the chain-against-fused measurement (sched_choose)
+static void sched_record(pt_ctx* ctx, int slot, float ms) {
+    if (!ctx->sched_pending.valid || slot != 0) return;
+    ctx->sched_pending.valid = false;
+    pt_ctx::Sched& sc = ctx->sched;
+    const int w = ctx->sched_pending.which;
+    const double t = ctx->sched_fake[0] > 0 ? ctx->sched_fake[w] : (double)ms;
+    if (sc.choice < 0) {
+        if (sc.n[w] > 0) sc.best[w] = sc.best[w] > 0 ? std::min(sc.best[w], t) : t; // (the first frame of each schedule is warm-up: code objects, cold caches, first-touch of the path state)
+        ++sc.n[w];
+        if (sc.n[0] > ctx->sched_trials && sc.n[1] > ctx->sched_trials) {
+            sc.choice = sc.best[1] < sc.best[0] ? 1 : 0;
+            sc.since = 0;
+            sc.mean = sc.best[sc.choice];
+        }
+    } else if (ctx->sched_pending.probe) {
+        ++sc.since;
+        if (t < 0.95 * sc.mean) { // the loser is clearly ahead now: time both again (they are warm: no warm-up frame)
+            sc.choice = -1;
+            sc.n[0] = sc.n[1] = 1;
+            sc.best[0] = sc.best[1] = 0;
+        }
+    } else {
+        ++sc.since;
+        sc.mean = 0.9 * sc.mean + 0.1 * t;
+    }
+}
+
+// mode 0: synchronous frame (pixel chunks on all streams); 2: the same chunks without a frame-wide start; 3: the whole frame on one stream
+// count > 1 (pt_render_batch): the launch chain carries the rays of `count` consecutive subframes — generate / trace / shade launches are
+// count times as large, the resolve blends the subframes in order — and leaves the buffers `count` frames would have left.
+static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, int slot = 0, int mode = 0, uint32_t count = 1) {
+    const bool pipelined = mode != 0, whole = mode == 3;
+    const char* bad_args = (spp == 0 || spp > 4096) ? "pt_render: samples_per_launch must be in [1,4096]"
+        : (count == 0 || count > 4096 || (uint64_t)subframe_index + count > 0xffffffffull) ? "pt_render_batch: count must be in [1,4096] and the subframe indices must fit 32 bits"
+        : nullptr;
+    int rc = frame_open(ctx, slot, pipelined, "pt_render", bad_args);
+    if (rc || ctx->width == 0) return rc;
+    const uint32_t vspp = spp * count; // samples of a pixel over the whole batch
+    const uint32_t owned = ctx->owned;
+    // Chunking.  All samples of a pixel stay in one pixel chunk.  The frame is cut into (at least) `streams` pixel
+    // chunks that run concurrently on separate stream pairs; a chunk holds at most max_paths/streams paths, so
+    // samples are split when spp*pixels exceed that; shadow-catcher scenes run one sample per pass so that the
+    // per-pixel normal/albedo sums keep the reference order.  None of this changes a bit of the result.
+    const ChunkMode cm{sched_choose(ctx, pipelined, owned, vspp), whole};
+    const int nsets = cm.fused_frame ? 1 : std::max(1, std::min(PT_MAX_SETS, ctx->opt.streams > 0 ? ctx->opt.streams : 3));
     const uint32_t max_paths = std::max<uint32_t>(ctx->opt.max_paths, 64u);
     const uint32_t cap = std::max<uint32_t>(64u, whole ? max_paths : max_paths / nsets);
     uint32_t Np = whole ? owned : (owned + nsets - 1) / nsets; // pixels per chunk ...
     Np = std::min(cap, std::max(64u, (Np + 63u) & ~63u)); // ... whole 8x8 blocks, within the set capacity
     const uint32_t S = ctx->has_catcher ? 1u : std::max(1u, std::min(vspp, cap / Np));
     if (owned) {
-        int rc = ensure_path_state(ctx, nsets, Np * S, Np); // waits for the frames in flight before it re-allocates
+        rc = ensure_path_state(ctx, nsets, Np * S, Np); // waits for the frames in flight before it re-allocates
         if (rc) return rc;
     }
     if (getenv("PT_DEBUG_COUNTS")) {
         if (!ctx->dbg) CK(dalloc(&ctx->dbg, 64 + (size_t)8 * PT_WAVELOG_CAP)); // 64 counters + the per-wave log of PT_DEBUG_STATS builds
         CK(dclear(ctx->stream, ctx->dbg, 512));
     }
-    begin_slot(ctx, slot);
-    hipEvent_t ev_begin = next_event(ctx);
-    if (!pipelined) {
-        CK(hipMemsetAsync(totals_of(ctx, slot, 0), 0, sizeof(unsigned long long) * PT_MAX_SETS * 4, ctx->stream));
-        CK(hipEventRecord(ev_begin, ctx->stream));
-    }
+    // a whole frame's chunks (one, unless spp x pixels exceed max_paths) all go to the stream of this frame's set
+    pt_ctx::BatchSet* whole_set = (owned && whole) ? &ctx->sets[ctx->frame_seq % (uint64_t)nsets] : nullptr;
+    hipStream_t whole_stream = whole_set ? whole_set->stream : nullptr;
+    const int used = owned ? nsets : 0;
+    hipEvent_t ev_begin;
+    rc = frame_begin(ctx, slot, pipelined, used, whole_stream, &ev_begin);
+    if (rc) return rc;
     FrameParams fp{ctx->accum, ctx->frame, ctx->color, ctx->normal, ctx->albedo, ctx->width, ctx->height, subframe_index,
                    ctx->eye, ctx->U, ctx->V, ctx->W, spp, ctx->probe};
     LaunchCounts lc;
-    hipStream_t end_stream = ctx->stream; // where the frame's counters are copied out and its end event is recorded
-    if (owned && whole) {
-        // the frame's chunks (one, unless spp x pixels exceed max_paths) all go to the stream of this frame; its resolve blends into
-        // accum_buffer after the previous frame's
-        pt_ctx::BatchSet& bs = ctx->sets[ctx->frame_seq % (uint64_t)nsets];
-        CK(hipMemsetAsync(totals_of(ctx, slot, 0), 0, sizeof(unsigned long long) * PT_MAX_SETS * 4, bs.stream));
-        CK(hipEventRecord(ev_begin, bs.stream));
-        std::vector<hipEvent_t> before;
-        if (ctx->ev_resolved) before.push_back(ctx->ev_resolved);
-        if (ctx->ev_pack_guard) before.push_back(ctx->ev_pack_guard); // the hand-off of the previous frame reads the buffers this frame's resolve overwrites
-        ctx->adapt_grid = true;
+    // What the resolves of a frame in flight wait for.  Chunk c of consecutive pt_render frames runs on the same stream, which orders their
+    // resolves; a foveated frame (pt_render_regions) deals its launches to the streams differently, so after one of those every resolve waits
+    // for that frame's end; a whole frame's resolve blends into accum_buffer after the previous frame's.  The hand-off of the previous frame
+    // reads the buffers this frame's resolve overwrites (a synchronous frame starts behind the context's stream, which carries the pack).
+    std::vector<hipEvent_t> before;
+    if (pipelined && ctx->ev_resolved && (whole || ctx->resolved_kind != 0)) before.push_back(ctx->ev_resolved);
+    if (pipelined && ctx->ev_pack_guard) before.push_back(ctx->ev_pack_guard);
+    if (whole_set) {
         for (uint32_t pix0 = 0; pix0 < owned; pix0 += Np)
-            enqueue_chunk(ctx, bs, fp, pix0, std::min(Np, owned - pix0), vspp, S, lc, nullptr, before.empty() ? nullptr : &before);
-        ctx->adapt_grid = false;
+            enqueue_chunk(ctx, *whole_set, fp, pix0, std::min(Np, owned - pix0), vspp, S, cm, lc, nullptr, before.empty() ? nullptr : &before);
         hipEvent_t e = next_event(ctx);
-        hipEventRecord(e, bs.stream);
+        hipEventRecord(e, whole_set->stream);
         ctx->ev_resolved = e;
         ctx->resolved_kind = 1;
-        end_stream = bs.stream; // the whole frame is on this stream: the context's own stream stays out of the way (one hardware queue fewer)
     } else if (owned) {
-        if (!pipelined) {
-            for (int i = 0; i < nsets; ++i) hipStreamWaitEvent(ctx->sets[i].stream, ev_begin, 0); // (the context may hold more sets than this frame uses)
-        } else {
-            // no frame-wide start: every set clears its own counters behind its own previous chunk and goes on
-            for (int i = 0; i < nsets; ++i) CK(hipMemsetAsync(ctx->sets[i].totals, 0, sizeof(unsigned long long) * 4, ctx->sets[i].stream));
-            CK(hipEventRecord(ev_begin, ctx->sets[0].stream));
-        }
-        // Chunk c of consecutive pt_render frames runs on the same stream, which orders their resolves; a foveated frame (pt_render_regions)
-        // deals its launches to the streams differently, so after one of those every resolve waits for that frame's end
-        std::vector<hipEvent_t> before;
-        if (pipelined && ctx->ev_resolved && ctx->resolved_kind != 0) before.push_back(ctx->ev_resolved);
-        if (pipelined && ctx->ev_pack_guard) before.push_back(ctx->ev_pack_guard); // (a synchronous frame starts behind the context's stream, which carries the pack)
         // A SMALL synchronous frame in the default schedule (a share of a partitioned image): chunk c's chain is enqueued by thread c, so that
         // all chains start together instead of one third / two thirds of the enqueue time apart.  Measured: a 1/8 share of C3 1.84 -> 1.78 ms;
         // 1/4 and 1/2 shares unchanged; the full frame 8.03 -> 8.16 ms (its chains are long, and the staggered start is what makes one chunk's
-        // shade launches overlap another's traversal) — hence the size limit.  Each chunk runs on its own batch set and stream; nothing the
-        // threads touch is shared but the error string (locked).  PT_ENQUEUE_THREADS=0 keeps one thread, =2 uses threads at every size.
+        // shade launches overlap another's traversal) — hence the size limit.  Each chunk runs on its own batch set and stream (chunks_threadable).
+        // PT_ENQUEUE_THREADS=0 keeps one thread, =2 uses threads at every size.
         const uint32_t nchunks = (owned + Np - 1) / Np;
-        const int threads_env = ctx->enqueue_threads;
         const bool small_frame = (uint64_t)owned * vspp <= (3u << 19); // 1.5 M paths
-        const bool parallel = ctx->shade_cus == 0 && threads_env != 0 && (small_frame || threads_env == 2) && !pipelined && nchunks > 1 && nchunks <= (uint32_t)nsets && !ctx->span_timing() &&
-                              ctx->opt.split_shadow == 0 && before.empty();
+        const bool parallel = ctx->enqueue_threads != 0 && (small_frame || ctx->enqueue_threads == 2) && !pipelined && nchunks > 1 &&
+                              chunks_threadable(ctx, nchunks, nsets, !before.empty());
         if (parallel) {
             while (ctx->chunk_workers.size() + 1 < nchunks) {
                 ctx->chunk_workers.emplace_back(new EnqueueWorker());
@@ -1555,11 +1571,11 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
             for (uint32_t c = 1; c < nchunks; ++c) {
                 const uint32_t pix0 = c * Np;
                 enqueue_worker_post(ctx->chunk_workers[c - 1].get(), [&, c, pix0]() {
-                    enqueue_chunk(ctx, ctx->sets[c], fp, pix0, std::min(Np, owned - pix0), vspp, S, lcs[c]);
+                    enqueue_chunk(ctx, ctx->sets[c], fp, pix0, std::min(Np, owned - pix0), vspp, S, cm, lcs[c]);
                     return 0;
                 });
             }
-            enqueue_chunk(ctx, ctx->sets[0], fp, 0, std::min(Np, owned), vspp, S, lcs[0]);
+            enqueue_chunk(ctx, ctx->sets[0], fp, 0, std::min(Np, owned), vspp, S, cm, lcs[0]);
             int wrc = 0;
             for (uint32_t c = 1; c < nchunks; ++c) wrc |= enqueue_worker_wait(ctx->chunk_workers[c - 1].get());
             if (wrc != 0) return fail(ctx, PT_ERR_HIP, "pt_render: a chunk's enqueue thread failed");
@@ -1567,58 +1583,15 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
         } else {
             uint32_t k = 0;
             for (uint32_t pix0 = 0; pix0 < owned; pix0 += Np, ++k)
-                enqueue_chunk(ctx, ctx->sets[k % nsets], fp, pix0, std::min(Np, owned - pix0), vspp, S, lc, nullptr, before.empty() ? nullptr : &before);
+                enqueue_chunk(ctx, ctx->sets[k % nsets], fp, pix0, std::min(Np, owned - pix0), vspp, S, cm, lc, nullptr, before.empty() ? nullptr : &before);
         }
-        for (int i = 0; i < nsets; ++i) {
-            hipEvent_t e = next_event(ctx);
-            hipEventRecord(e, ctx->sets[i].stream);
-            hipStreamWaitEvent(ctx->stream, e, 0);
-        }
-    } else if (pipelined) {
-        CK(hipEventRecord(ev_begin, ctx->stream));
     }
-    CK(hipMemcpyAsync(ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4, totals_of(ctx, slot, 0), sizeof(unsigned long long) * PT_MAX_SETS * 4, hipMemcpyDeviceToHost, end_stream));
-    hipEvent_t ev_end = next_event(ctx);
-    CK(hipEventRecord(ev_end, end_stream));
-    if (pipelined && !whole) { // a later foveated frame (or a whole frame) orders its resolves behind this frame's end
-        ctx->ev_resolved = ev_end;
-        ctx->resolved_kind = 0;
-    }
-    pt_ctx::Inflight& fr = ctx->fr[slot];
-    fr.ev_begin = ev_begin;
-    fr.ev_end = ev_end;
-    fr.active = 1;
-    fr.paths = (uint64_t)owned * vspp;
-    fr.subframes = count;
-    fr.lc = lc;
-    fr.seq = ++ctx->frame_seq;
-    return PT_OK;
+    // a later foveated frame (or a whole frame) orders its resolves behind the end of a frame of pixel chunks in flight
+    return frame_close(ctx, slot, ev_begin, used, whole_stream, (pipelined && !whole) ? 0 : -1, (uint64_t)owned * vspp, count, lc);
 }
 
-static int render_finish(pt_ctx* ctx, int slot = 0) {
-    pt_ctx::Inflight& fr = ctx->fr[slot];
-    if (!fr.active) return PT_OK;
-    fr.active = 0;
-    CK(hipSetDevice(ctx->device));
-    const uint32_t owned = ctx->owned;
-    const LaunchCounts lc = fr.lc;
-    hipEvent_t ev_begin = fr.ev_begin, ev_end = fr.ev_end;
-    CK(hipEventSynchronize(ev_end)); // SimplePathtracer.cpp:96 CUDA_SYNC_CHECK (the frame's last event on the context's stream)
-    if (!ctx->launch_err.empty()) {
-        ctx->err = ctx->launch_err;
-        ctx->launch_err.clear();
-        return PT_ERR_HIP;
-    }
-    CK(hipGetLastError());
-    const unsigned long long* per_set = ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4; // copied behind the frame's last kernel, before ev_end
-    unsigned long long totals[4] = {0, 0, 0, 0};
-    for (int i = 0; i < PT_MAX_SETS; ++i) {
-        totals[0] += per_set[i * 4 + 0];
-        totals[1] += per_set[i * 4 + 1];
-        totals[2] |= per_set[i * 4 + 2];
-        totals[3] += per_set[i * 4 + 3];
-    }
-    if (totals[2] & 1ull) return fail(ctx, PT_ERR_UNSUPPORTED, "traversal stack overflow: the acceleration structure is deeper than the traversal stack; the frame is invalid");
+// PT_DEBUG_COUNTS: the traversal counters of the frame just waited for, and the per-bounce queue sizes of the last chunk of set 0
+static int debug_report(pt_ctx* ctx) {
     if (ctx->dbg) {
         unsigned long long h[64];
         CK(hipMemcpy(h, ctx->dbg, 512, hipMemcpyDeviceToHost));
@@ -1646,7 +1619,7 @@ static int render_finish(pt_ctx* ctx, int slot = 0) {
             fprintf(stderr, "[pt_render] camera packets %llu: node steps %.1f per packet (%.1f lanes hit something), triangle tests %.1f per packet (%.1f lanes inside the leaf's box)\n",
                     h[48], (double)h[49] / h[48], h[49] ? (double)h[52] / h[49] : 0.0, (double)h[50] / h[48], h[50] ? (double)h[51] / h[50] : 0.0);
     }
-    if (getenv("PT_DEBUG_COUNTS") && owned) { // per-bounce queue sizes of the last chunk of set 0
+    if (getenv("PT_DEBUG_COUNTS") && ctx->owned) {
         const size_t CS = (size_t)PT_NSUB * PT_CSTRIDE;
         std::vector<uint32_t> hc((size_t)2 * ctx->nq * CS);
         CK(hipMemcpy(hc.data(), ctx->sets[0].counters, sizeof(uint32_t) * hc.size(), hipMemcpyDeviceToHost));
@@ -1661,6 +1634,36 @@ static int render_finish(pt_ctx* ctx, int slot = 0) {
         }
         fprintf(stderr, "\n");
     }
+    return PT_OK;
+}
+
+static int render_finish(pt_ctx* ctx, int slot = 0) {
+    pt_ctx::Inflight& fr = ctx->fr[slot];
+    if (!fr.active) return PT_OK;
+    fr.active = 0;
+    CK(hipSetDevice(ctx->device));
+    const LaunchCounts lc = fr.lc;
+    hipEvent_t ev_begin = fr.ev_begin, ev_end = fr.ev_end;
+    CK(hipEventSynchronize(ev_end)); // SimplePathtracer.cpp:96 CUDA_SYNC_CHECK (the frame's last event on the context's stream)
+    if (!ctx->launch_err.empty()) {
+        ctx->err = ctx->launch_err;
+        ctx->launch_err.clear();
+        return PT_ERR_HIP;
+    }
+    CK(hipGetLastError());
+    const unsigned long long* per_set = ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4; // copied behind the frame's last kernel, before ev_end
+    unsigned long long totals[4] = {0, 0, 0, 0};
+    for (int i = 0; i < fr.nsets; ++i) { // the frame's sets only: a frame in flight clears only theirs, the others may hold an older frame's counts
+        totals[0] += per_set[i * 4 + 0];
+        totals[1] += per_set[i * 4 + 1];
+        totals[2] |= per_set[i * 4 + 2];
+        totals[3] += per_set[i * 4 + 3];
+    }
+    if (totals[2] & 1ull) return fail(ctx, PT_ERR_UNSUPPORTED, "traversal stack overflow: the acceleration structure is deeper than the traversal stack; the frame is invalid");
+    {
+        int rc = debug_report(ctx);
+        if (rc) return rc;
+    }
     pt_stats& st = ctx->stats;
     st.radiance_rays = totals[0];
     st.shadow_rays = totals[1];
@@ -1672,31 +1675,7 @@ static int render_finish(pt_ctx* ctx, int slot = 0) {
     float ms = 0;
     hipEventElapsedTime(&ms, ev_begin, ev_end);
     st.render_ms = ms;
-    if (ctx->sched_pending.valid && slot == 0) { // the frame took part in the chain-against-fused measurement (render_enqueue)
-        ctx->sched_pending.valid = false;
-        pt_ctx::Sched& sc = ctx->sched;
-        const int w = ctx->sched_pending.which;
-        const double t = ctx->sched_fake[0] > 0 ? ctx->sched_fake[w] : (double)ms;
-        if (sc.choice < 0) {
-            if (sc.n[w] > 0) sc.best[w] = sc.best[w] > 0 ? std::min(sc.best[w], t) : t; // (the first frame of each schedule is warm-up: code objects, cold caches, first-touch of the path state)
-            ++sc.n[w];
-            if (sc.n[0] > ctx->sched_trials && sc.n[1] > ctx->sched_trials) {
-                sc.choice = sc.best[1] < sc.best[0] ? 1 : 0;
-                sc.since = 0;
-                sc.mean = sc.best[sc.choice];
-            }
-        } else if (ctx->sched_pending.probe) {
-            ++sc.since;
-            if (t < 0.95 * sc.mean) { // the loser is clearly ahead now: time both again (they are warm: no warm-up frame)
-                sc.choice = -1;
-                sc.n[0] = sc.n[1] = 1;
-                sc.best[0] = sc.best[1] = 0;
-            }
-        } else {
-            ++sc.since;
-            sc.mean = 0.9 * sc.mean + 0.1 * t;
-        }
-    }
+    sched_record(ctx, slot, ms);
     st.schedule = ctx->sched_flags;
     st.sched_chain_ms = ctx->sched.best[0];
     st.sched_fused_ms = ctx->sched.best[1];
@@ -1746,11 +1725,12 @@ extern "C" int pt_sync(pt_ctx* ctx) { return ctx ? drain(ctx) : PT_ERR_INVALID; 
 static int frames_mode(pt_ctx* ctx) {
     return (ctx->opt.frames_in_flight >= 2 && !ctx->span_timing() && !getenv("PT_DEBUG_COUNTS")) ? std::min(ctx->opt.frames_in_flight, PT_MAX_FRAMES) : 1;
 }
-// frame k goes into the slot the oldest finished frame has left ...
-static int pipelined_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, int F, uint32_t count = 1) {
+// frame k goes into the slot the oldest finished frame has left (enqueue(slot): render_enqueue or regions_enqueue) ...
+template <typename Enqueue>
+static int enqueue_next_slot(pt_ctx* ctx, int F, Enqueue&& enqueue) {
     const int slot = (ctx->last_slot + 1) % F;
     int rc = render_finish(ctx, slot);
-    if (rc == PT_OK) rc = render_enqueue(ctx, spp, subframe_index, slot, F, count);
+    if (rc == PT_OK) rc = enqueue(slot);
     if (rc == PT_OK) ctx->last_slot = slot;
     return rc;
 }
@@ -1781,7 +1761,7 @@ extern "C" int pt_render_batch(pt_ctx* ctx, uint32_t spp, uint32_t first_subfram
         if (rc == PT_OK) rc = render_enqueue(ctx, spp, subframe_index, 0, 0, count);
         if (rc == PT_OK) rc = render_finish(ctx);
     } else {
-        rc = pipelined_enqueue(ctx, spp, subframe_index, F, count);
+        rc = enqueue_next_slot(ctx, F, [&](int slot) { return render_enqueue(ctx, spp, subframe_index, slot, F, count); });
         const int rw = pipelined_wait(ctx, F);
         if (rc == PT_OK) rc = rw;
     }
@@ -1836,15 +1816,9 @@ extern "C" int pt_wait_event(pt_ctx* ctx, void* hip_event) {
 // passes of the frame's launches go to the batch sets in turn, every stream carries on behind its own previous work, and the first
 // resolve of the frame waits for the end of the previous frame (later frames overwrite earlier ones)
 static int regions_enqueue(pt_ctx* ctx, const pt_region* regions, uint32_t n, const pt_variant* variant, int slot = 0, bool pipelined = false) {
-    if (!pipelined) {
-        int rc = drain(ctx);
-        if (rc) return rc;
-    }
-    ctx->fr[slot].active = 0;
-    if (ctx->width == 0) return PT_OK;
-    if (!ctx->probe.data) return fail(ctx, PT_ERR_INVALID, "pt_render_regions: no probe set (setProbe)");
+    int rc = frame_open(ctx, slot, pipelined, "pt_render_regions", nullptr);
+    if (rc || ctx->width == 0) return rc;
     if (ctx->has_catcher) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_render_regions: shadow-catcher materials are not supported in foveated launches");
-    CK(hipSetDevice(ctx->device));
     VariantParams var{0.001f, 0, 0, 1.0f, 1.0f, 0, 0};
     if (variant) var = VariantParams{variant->radiance_tmin, variant->cull_back_occlusion, variant->tonemap, variant->exposure, variant->white, variant->initial_depth, variant->write_aov};
     if (var.initial_depth < 0 || (var.initial_depth > 0 && var.initial_depth >= ctx->opt.max_depth)) return fail(ctx, PT_ERR_INVALID, "pt_render_regions: initial_depth must be 0 or below max_depth");
@@ -1864,20 +1838,11 @@ static int regions_enqueue(pt_ctx* ctx, const pt_region* regions, uint32_t n, co
         const unsigned long long total = (unsigned long long)g.launch_w * g.launch_h * g.spp;
         need = (uint32_t)std::max<unsigned long long>(need, std::min<unsigned long long>(total, cap));
     }
-    {
-        int rc = ensure_path_state(ctx, nsets, need, 64);
-        if (rc) return rc;
-    }
-    begin_slot(ctx, slot);
-    hipEvent_t ev_begin = next_event(ctx);
-    if (!pipelined) {
-        CK(hipMemsetAsync(totals_of(ctx, slot, 0), 0, sizeof(unsigned long long) * PT_MAX_SETS * 4, ctx->stream));
-        CK(hipEventRecord(ev_begin, ctx->stream));
-        for (int i = 0; i < nsets; ++i) hipStreamWaitEvent(ctx->sets[i].stream, ev_begin, 0);
-    } else {
-        for (int i = 0; i < nsets; ++i) CK(hipMemsetAsync(ctx->sets[i].totals, 0, sizeof(unsigned long long) * 4, ctx->sets[i].stream));
-        CK(hipEventRecord(ev_begin, ctx->sets[0].stream));
-    }
+    rc = ensure_path_state(ctx, nsets, need, 64);
+    if (rc) return rc;
+    hipEvent_t ev_begin;
+    rc = frame_begin(ctx, slot, pipelined, nsets, nullptr, &ev_begin);
+    if (rc) return rc;
     LaunchCounts lc;
     uint64_t paths = 0;
     uint32_t next_set = 0;
@@ -1898,7 +1863,7 @@ static int regions_enqueue(pt_ctx* ctx, const pt_region* regions, uint32_t n, co
             job.l0 = l0;
             job.nl = std::min(per, nlaunch - l0);
             const uint32_t si = next_set++ % (uint32_t)nsets;
-            enqueue_chunk(ctx, ctx->sets[si], fp, 0, 0, g.spp, g.spp, lc, &job, prev_done.empty() ? nullptr : &prev_done);
+            enqueue_chunk(ctx, ctx->sets[si], fp, 0, 0, g.spp, g.spp, ChunkMode{}, lc, &job, prev_done.empty() ? nullptr : &prev_done);
             used[si] = true;
         }
         cur_done.clear();
@@ -1911,27 +1876,7 @@ static int regions_enqueue(pt_ctx* ctx, const pt_region* regions, uint32_t n, co
         prev_done = cur_done; // these resolves waited for the older launches themselves: the order is transitive
         paths += (uint64_t)nlaunch * g.spp;
     }
-    for (int i = 0; i < nsets; ++i) {
-        hipEvent_t e = next_event(ctx);
-        hipEventRecord(e, ctx->sets[i].stream);
-        hipStreamWaitEvent(ctx->stream, e, 0);
-    }
-    CK(hipMemcpyAsync(ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4, totals_of(ctx, slot, 0), sizeof(unsigned long long) * PT_MAX_SETS * 4, hipMemcpyDeviceToHost, ctx->stream));
-    hipEvent_t ev_end = next_event(ctx);
-    CK(hipEventRecord(ev_end, ctx->stream));
-    if (pipelined) { // behind every resolve of this frame
-        ctx->ev_resolved = ev_end;
-        ctx->resolved_kind = 2;
-    }
-    pt_ctx::Inflight& fr = ctx->fr[slot];
-    fr.subframes = 1;
-    fr.ev_begin = ev_begin;
-    fr.ev_end = ev_end;
-    fr.active = 1;
-    fr.paths = paths;
-    fr.lc = lc;
-    fr.seq = ++ctx->frame_seq;
-    return PT_OK;
+    return frame_close(ctx, slot, ev_begin, nsets, nullptr, pipelined ? 2 : -1, paths, 1, lc); // (frames in flight: ev_end is behind every resolve of this frame)
 }
 
 extern "C" int pt_render_regions(pt_ctx* ctx, const pt_region* regions, uint32_t n, const pt_variant* variant, uint32_t* host_rgba8) {
@@ -1942,10 +1887,7 @@ extern "C" int pt_render_regions(pt_ctx* ctx, const pt_region* regions, uint32_t
         rc = regions_enqueue(ctx, regions, n, variant);
         if (rc == PT_OK) rc = render_finish(ctx);
     } else {
-        const int slot = (ctx->last_slot + 1) % F;
-        rc = render_finish(ctx, slot);
-        if (rc == PT_OK) rc = regions_enqueue(ctx, regions, n, variant, slot, true);
-        if (rc == PT_OK) ctx->last_slot = slot;
+        rc = enqueue_next_slot(ctx, F, [&](int slot) { return regions_enqueue(ctx, regions, n, variant, slot, true); });
         const int rw = pipelined_wait(ctx, F);
         if (rc == PT_OK) rc = rw;
     }
@@ -3069,14 +3011,7 @@ static int multi_render_common(pt_multi* m, uint32_t spp, uint32_t subframe_inde
         pt_ctx* c = m->ctx[r];
         return regions ? regions_enqueue(c, regions, nreg, variant, slot, mode != 0) : render_enqueue(c, spp, subframe_index, slot, mode, count);
     };
-    auto enqueue_pipelined = [&](int r) {
-        pt_ctx* c = m->ctx[r];
-        const int slot = (c->last_slot + 1) % F;
-        int rc = render_finish(c, slot);
-        if (rc == PT_OK) rc = enqueue(r, slot, F);
-        if (rc == PT_OK) c->last_slot = slot;
-        return rc;
-    };
+    auto enqueue_pipelined = [&](int r) { return enqueue_next_slot(m->ctx[r], F, [&](int slot) { return enqueue(r, slot, F); }); };
     if (F > 1 && gather_mask == 0) {
         // pure throughput (nothing is handed over after this frame): pt_options.frames_in_flight applies on every device
         int rc = multi_present_pending(m, true); // a frame of an earlier call that was waiting for its hand-over

@@ -601,6 +601,34 @@ def test_pipelined_frames_are_bit_identical(ptlib, small_probe, opts):
         assert pipe["st2"]["total_radiance_rays"] == sync["st2"]["total_radiance_rays"]
 
 
+def test_pipelined_frames_count_only_their_own_sets(ptlib, small_probe):
+    """A frame in flight clears the ray counters of the batch sets it uses, not those of every set the context holds.  After
+    pt_options.streams goes 2 -> 3 -> 2 under frames_in_flight = 2 (the path state only grows: no re-allocation clears the counters on
+    the way back), both frame slots hold the counts of a 3-set frame in set 2's slice; the 2-set frames after that must report what a
+    fresh 2-stream context reports for the same frame."""
+    m = scenes.voxel_terrain(n=96, target_tris=70000)
+    w, h = 160, 96
+
+    def last_frame(r, subframes):
+        for sf in subframes:
+            r.launchParams.frame.subframe_index = sf
+            r.render()
+        r.sync()
+        st = r.stats()
+        return st["radiance_rays"], st["shadow_rays"], st["shaded_hits"]
+
+    r = _renderer(m, small_probe, scenes.TERRAIN_CAMERA, w, h, max_depth=4, streams=2, frames_in_flight=2)
+    r.launchParams.samples_per_launch = 2
+    last_frame(r, [0])
+    r.setOptions(max_depth=4, streams=3, frames_in_flight=2)
+    last_frame(r, [1, 2, 3])  # both slots: a 3-set frame
+    r.setOptions(max_depth=4, streams=2, frames_in_flight=2)
+    reused = last_frame(r, [4, 5, 6])
+    fresh = _renderer(m, small_probe, scenes.TERRAIN_CAMERA, w, h, max_depth=4, streams=2, frames_in_flight=2)
+    fresh.launchParams.samples_per_launch = 2
+    assert reused == last_frame(fresh, [4, 5, 6])
+
+
 @pytest.mark.parametrize("fif", [2, 3])
 def test_pipelined_frames_report_errors_late_but_loudly(ptlib, small_probe, monkeypatch, fif):
     """A traversal-stack overflow in frame k is reported by the call that waits for frame k (the next pt_render or pt_sync)."""
