@@ -317,6 +317,26 @@ def load_ref():
     return R
 
 
+REF_DISNEY_FLAVOURS = {"libm": "libptref_disney.so", "det": "libptref_disney_det.so"}
+
+
+def load_ref_disney(flavour: str = "det"):
+    """oracle/_ref/libptref_disney{,_det}.so (the reference's own Disney.cuh BSDF and Probe.h BuildCDF, built by
+    oracle/ref_build/ref_disney.cpp with glibc ('libm') or include/pt_detmath.h ('det') transcendentals) or None when it
+    was not built."""
+    path = os.path.join(HERE, "_ref", REF_DISNEY_FLAVOURS[flavour])
+    if not os.path.exists(path):
+        return None
+    R = C.CDLL(path)
+    R.ref_bsdf_pdf.restype = C.c_float
+    R.ref_bsdf_pdf.argtypes = [C.c_void_p, C.c_float, C.c_float, f32p, f32p, f32p]
+    R.ref_bsdf_eval.argtypes = [C.c_void_p, f32p, C.c_float, C.c_float, f32p, f32p, f32p, f32p]
+    R.ref_bsdf_sample.argtypes = [C.c_void_p, C.c_float, C.c_float, f32p, f32p, C.c_uint32, f32p, C.POINTER(C.c_float), u32p]
+    R.ref_build_cdf.argtypes = [f32p, C.c_int, C.c_int, f32p, f32p, f32p, f32p]
+    R.path = path
+    return R
+
+
 def ref_loadf(R, path):
     """stbi_loadf(path, ..., 4) of the reference's vendored stb_image (main.cpp:146-156 loadProbe): (h, w, 4) float32 or None."""
     res = np.zeros(2, np.int32)

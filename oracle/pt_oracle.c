@@ -27,10 +27,14 @@
  * PINNING STATUS.  RNG, samplers, probe lookup/sampling, make_color, Material
  * defaults/IOR and UVWFrame are pinned against the reference's own headers
  * compiled from where they lie (oracle/ref_build -> oracle/_ref, tests/golden).
- * Disney.cuh, Probe.h and deviceProgram.cu need optix.h / optix_device.h, which
- * the image lacks, and the reference has no tests or golden images: for the
- * BSDF, BuildCDF and the raygen/closest-hit orchestration PARITY IS UNPINNED —
- * they are restated from reading the source, line by line.
+ * So are the Disney BSDF (BSDFPdf/Sample/Eval) and BuildCDF: Disney.cuh and
+ * Probe.h need optix.h, and oracle/ref_build/stub/ supplies stand-ins that only
+ * declare OptixTraversableHandle, no-op the CUDA/OptiX check macros and redirect
+ * "Maths.h" as Windows' case-insensitive lookup does; no pinned function reaches
+ * them (ref_build/ref_disney.cpp, tests/golden/ref_disney.npz).  deviceProgram.cu
+ * needs optixTrace and the payload calls, which a stand-in would define rather
+ * than pin: for the raygen/closest-hit orchestration PARITY IS UNPINNED — it is
+ * restated from reading the source, line by line.
  *
  * Math modes: built twice.  Default uses glibc sinf/cosf/acosf/atan2f/logf/powf
  * (independent of the product).  With -DORC_DETMATH it uses include/pt_detmath.h

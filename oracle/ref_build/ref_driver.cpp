@@ -4,11 +4,12 @@
 // oracle/pt_oracle.c function by function and (b) generate tests/golden/*.npz via
 // tests/golden/make_golden.py.  /root/reference does not exist on the GPU box.
 //
-// Only headers that compile with what the image already holds are used (CUDA's
-// host-side vector_types.h etc. ship inside the Triton wheel).  Disney.cuh,
-// LaunchParams.h, Probe.h, CUDABuffer.h and deviceProgram.cu include <optix.h> /
-// <optix_device.h>, which the image lacks; no stand-ins are written for them, so
-// those parts of the reference are NOT in this library ("oracle").
+// Only headers that compile with what the image already holds are used here (CUDA's
+// host-side vector_types.h etc. ship inside the Triton wheel), with no stand-in header.
+// Disney.cuh and Probe.h (BuildCDF) include <optix.h>: they are built by a TU of their
+// own, ref_disney.cpp, with the stand-ins of ref_build/stub/, so that this TU's include
+// resolution (and tests/golden/ref_tables.npz) stays as it is.  deviceProgram.cu
+// (optixTrace, payloads) is built nowhere ("oracle").
 #include <cfloat>
 #include <cmath>
 #include <algorithm>
