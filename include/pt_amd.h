@@ -292,6 +292,67 @@ typedef struct pt_variant {
  * Writes accum_buffer and frame_buffer (plus the three AOV buffers with pt_variant.write_aov).  variant may be NULL (canonical settings). */
 int pt_render_regions(pt_ctx* ctx, const pt_region* regions, uint32_t n, const pt_variant* variant, uint32_t* host_rgba8);
 
+/* BLOCK MASKS AND ADAPTIVE STOPPING (no reference counterpart): render only chosen 8x8 blocks of the image.
+ * A block is one 8x8 tile of the image grid: bx = x / 8, by = y / 8, nbx = (width + 7) / 8, nby = (height + 7) / 8, block id by * nbx + bx
+ * (edge blocks hold fewer than 64 pixels).  On a partitioned context (pt_set_partition) only the blocks the rank owns count; tile sizes are
+ * multiples of 8, so a block never straddles ranks.  A pixel's result depends on nothing but (x, y, subframe_index, spp) and its own previous
+ * accum value, so the pixels of a rendered block get the bits a full frame gives them.
+ *
+ * pt_render_mask: one byte per block (nbx * nby, host memory), non-zero = render this block.  Pixels of rendered blocks end up exactly as
+ * pt_render(spp, subframe_index) leaves them, in all five buffers; pixels of other blocks are not touched in any buffer.  A compaction kernel
+ * builds the list of active pixels on the device in the order of the rank's own list (whole blocks, block order kept); its count comes back
+ * with one 4-byte copy and the frame then runs through the code of pt_render.  Synchronous whatever pt_options.frames_in_flight says: frames
+ * in flight are waited for first and the call is complete when it returns.  The on-line schedule trial (pt_stats.schedule) neither sees nor
+ * is reset by a masked frame: it takes the launch chain or the fused pass by the static rule on its own path count (both leave the same
+ * bits; PT_FUSED=0/1 still forces it), and it never asks for more path state than the rank's full frame of the same samples does: after a full
+ * frame it allocates nothing (pt_stats.path_state_allocs), before one it may grow the state up to that shape.  pt_stats of the call describe the active pixels only.  Zero active
+ * pixels: no kernel launch, PT_OK.  Refused with PT_ERR_INVALID (text in pt_last_error): null context or mask, no pt_resize yet, spp
+ * outside [1,4096]. */
+int pt_render_mask(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, const uint8_t* block_mask,
+                   uint32_t* host_rgba8 /* may be NULL; else the whole frame buffer */, uint32_t* active_pixels /* may be NULL */);
+
+/* The policy on top of it: a progressive loop in which every block stops being rendered once its pixels have converged.
+ *
+ * Moments.  For every pixel a pt_render_adaptive call renders, the resolve records the value c that enters the blend (the subframe's own
+ * colour, clamped to [0,10] when subframe_index > 0, unclamped at subframe 0): x = 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z evaluated
+ * left to right, then n += 1, s1 += x, s2 += x * x.  pt_render and pt_render_mask never touch this state.
+ *
+ * Stopping rule, evaluated on the device after the resolve for the blocks the call rendered; float32 throughout, one rounding per
+ * operation (no fused multiply-add), in exactly this order.  n = the block's subframe count, N = its pixel count as a float:
+ *   per pixel p:  m_p = s1_p / n;   v_p = max(0, s2_p / n - m_p * m_p)
+ *   V = sum v_p, M = sum m_p: each a butterfly over 64 slots, slot l = the pixel (8 bx + (l & 7), 8 by + (l >> 3)), slots outside the image
+ *       hold 0; for off = 32, 16, 8, 4, 2, 1: every slot l becomes slot[l] + slot[l ^ off] (all slots end up equal)
+ *   B = M + dark_floor * N;   lhs = V * N;   rhs = (((threshold * threshold) * (n - 1)) * B) * B
+ *   the block stops when (n >= min_subframes and lhs <= rhs) or (max_subframes > 0 and n >= max_subframes)
+ * i.e. the RMS standard error of a pixel's mean, relative to the block's mean luminance (plus dark_floor), is at most `threshold`.  A
+ * stopped block stays stopped until the next pt_adaptive_begin.  Non-finite moments: the colour of subframe 0 enters unclamped, so an inf or
+ * NaN sample there makes s1 or s2 of its pixel non-finite for good; lhs <= rhs is then false (a comparison with NaN, or inf <= inf * 0 -> NaN)
+ * and the block is never stopped by the rule, only by max_subframes.  A loop that waits for active_blocks == 0 should therefore set
+ * max_subframes (or bound its own iteration count). */
+typedef struct pt_adaptive_params {
+    float    threshold;     /* >= 0; see the rule above */
+    float    dark_floor;    /* >= 0, added to the block's mean luminance (so that near-black blocks can stop) */
+    uint32_t min_subframes; /* >= 2: a block is never stopped by the rule with fewer subframes behind it */
+    uint32_t max_subframes; /* 0 = no limit; a block stops once it has this many */
+} pt_adaptive_params;
+typedef struct pt_adaptive_stats {
+    uint32_t blocks, active_blocks;     /* owned blocks; still active after the last call */
+    uint64_t active_pixels;             /* rendered by the last call */
+    uint64_t pixel_subframes;           /* sum over owned pixels of subframes rendered since pt_adaptive_begin */
+    double   decide_ms;                 /* device time of the compaction + decision kernels of the last call (events) */
+} pt_adaptive_stats;
+/* (re)allocates and clears the state, all owned blocks active; call it after a camera move, where one restarts at subframe 0.
+ * Refused: null context or params, no pt_resize yet, min_subframes < 2, negative or non-finite threshold / dark_floor. */
+int pt_adaptive_begin(pt_ctx* ctx, const pt_adaptive_params* params);
+/* pt_render_mask with the blocks that are still active, recording the moments; then the decision for those blocks and the compaction for
+ * the next call, both behind the frame on the device (their count returns with the frame's own final synchronisation: no host round trip
+ * in front of a frame).  Synchronous.  With no block left it launches nothing.  Refused without pt_adaptive_begin. */
+int pt_render_adaptive(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, uint32_t* host_rgba8 /* may be NULL */, pt_adaptive_stats* out /* may be NULL */);
+/* frees the state; pt_resize, pt_set_partition and pt_destroy imply it */
+int pt_adaptive_end(pt_ctx* ctx);
+enum pt_adaptive_array { PT_ADAPT_MOMENTS = 0 /* width*height x {n, s1, s2, 0} f32 */, PT_ADAPT_ACTIVE = 1 /* nbx*nby u8 (0 for blocks of other ranks) */ };
+int pt_download_adaptive(pt_ctx* ctx, int which /* pt_adaptive_array */, void* host, size_t bytes);
+
 /* SampleRenderer::downloadPixels (SimplePathtracer.cpp:149-153), generalised to all five buffers.
  * bytes must equal width*height*(16 or 4). */
 int pt_download(pt_ctx* ctx, int which /* pt_buffer */, void* host, size_t bytes);

@@ -23,9 +23,25 @@ EXPORTS = [
     "pt_render_device", "pt_stream", "pt_wait_event", "pt_get_stats_n", "pt_stats_size",
     "pt_load_obj", "pt_obj_free", "pt_obj_num_meshes", "pt_obj_get_mesh", "pt_obj_num_textures", "pt_obj_texture_path", "pt_obj_last_error",
     "pt_update_meshes", "pt_multi_update_meshes",
+    "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
 ]
 
 PT_UPDATE_REFIT, PT_UPDATE_REBUILD = 0, 1  # pt_update_mode
+
+
+PT_ADAPT_MOMENTS, PT_ADAPT_ACTIVE = 0, 1  # pt_adaptive_array
+
+
+class AdaptiveParams(C.Structure):  # pt_adaptive_params
+    _fields_ = [("threshold", C.c_float), ("dark_floor", C.c_float), ("min_subframes", C.c_uint32), ("max_subframes", C.c_uint32)]
+
+
+class AdaptiveStats(C.Structure):  # pt_adaptive_stats
+    _fields_ = [("blocks", C.c_uint32), ("active_blocks", C.c_uint32), ("active_pixels", C.c_uint64), ("pixel_subframes", C.c_uint64),
+                ("decide_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class MeshUpdate(C.Structure):  # pt_mesh_update
@@ -203,6 +219,11 @@ def load_library() -> C.CDLL:
     L.pt_export_bvh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]
     L.pt_update_meshes.argtypes = [vp, C.POINTER(MeshUpdate), u32, i, C.POINTER(C.c_double)]
     L.pt_multi_update_meshes.argtypes = [vp, C.POINTER(MeshUpdate), u32, i, C.POINTER(C.c_double)]
+    L.pt_render_mask.argtypes = [vp, u32, u32, vp, vp, C.POINTER(u32)]
+    L.pt_adaptive_begin.argtypes = [vp, C.POINTER(AdaptiveParams)]
+    L.pt_render_adaptive.argtypes = [vp, u32, u32, vp, C.POINTER(AdaptiveStats)]
+    L.pt_adaptive_end.argtypes = [vp]
+    L.pt_download_adaptive.argtypes = [vp, i, vp, C.c_size_t]
     L.pt_version.restype = C.c_char_p
     f3p = C.POINTER(f * 3)
     L.pt_create_multi.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), i, C.POINTER(vp)]

@@ -191,6 +191,25 @@ class SampleRenderer {
         ck(pt_set_options(ctx, &o));
     }
     void sync() { ck(pt_sync(ctx)); }
+    // Beyond the reference: render() for chosen 8x8 blocks only (pt_render_mask; one byte per block, (size.x + 7) / 8 per row, non-zero =
+    // render).  Those pixels end up as render() leaves them, the others are untouched.  Returns the number of pixels rendered.
+    uint32_t renderMask(const std::vector<uint8_t>& block_mask, uint32_t* h_pixels = nullptr) {
+        const size_t need = (size_t)((launchParams.frame.size.x + 7) / 8) * (size_t)((launchParams.frame.size.y + 7) / 8);
+        if (block_mask.size() != need) throw std::runtime_error("renderMask: the mask needs one byte per 8x8 block");
+        uint32_t active = 0;
+        ck(pt_render_mask(ctx, launchParams.samples_per_launch, launchParams.frame.subframe_index, block_mask.data(), h_pixels, &active));
+        return active;
+    }
+    // ... and the progressive loop that stops rendering a block once it has converged (pt_adaptive_begin / pt_render_adaptive): call
+    // adaptiveBegin after a camera move, where the accumulation restarts at subframe 0, then renderAdaptive() + subframe_index++ until
+    // active_blocks is 0.
+    void adaptiveBegin(const pt_adaptive_params& params) { ck(pt_adaptive_begin(ctx, &params)); }
+    pt_adaptive_stats renderAdaptive(uint32_t* h_pixels = nullptr) {
+        pt_adaptive_stats st{};
+        ck(pt_render_adaptive(ctx, launchParams.samples_per_launch, launchParams.frame.subframe_index, h_pixels, &st));
+        return st;
+    }
+    void adaptiveEnd() { ck(pt_adaptive_end(ctx)); }
     // Moved vertices (no reference counterpart; OptiX: OPTIX_BUILD_OPERATION_UPDATE): after changing model->meshes[m]->vertex in place for
     // every m in `meshes` (same vertex count, same indices), the context takes the new positions — the tree refitted on the GPU, or rebuilt
     // with rebuild = true (pt_update_meshes).  Restart the accumulation at subframe 0 afterwards.  Returns the device time in ms.

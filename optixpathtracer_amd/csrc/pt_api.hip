@@ -133,6 +133,32 @@ struct pt_ctx {
     uint32_t owned = 0, padded = 0;
     uint32_t* d_pixels = nullptr;     // this rank's pixel list
     uint32_t* d_all_pixels = nullptr; // world * padded, rank-major (0xffffffff = pad)
+    // Block masks (pt_render_mask, pt_render_adaptive): where each 8x8 block's pixels sit in d_pixels, and what the compaction kernels work
+    // on.  Built by the first call that needs them at the current size and partition, freed with the frame buffers.
+    struct Blocks {
+        uint32_t nbx = 0, nby = 0, nblk = 0, owned_blocks = 0;
+        BlockSpan* d_spans = nullptr;  // [nblk] (size 0: another rank's block)
+        uint8_t* d_flags = nullptr;    // [nblk] the caller's mask of the pt_render_mask call under way
+        uint32_t* d_offsets = nullptr; // [nblk] scratch of the compaction: a block's offset inside its group of 256 blocks
+        uint32_t* d_parts = nullptr;   // [2][nparts] per group of 256 blocks: active pixels (then their prefix sums), active blocks
+        uint32_t nparts = 0;
+        uint32_t* d_list = nullptr;    // [owned] the compacted pixel list of pt_render_mask
+        uint32_t* d_counts = nullptr;  // {active pixels, active blocks} of the last compaction
+        uint32_t* h_counts = nullptr;  // pinned host copy
+        std::vector<uint8_t> owned_flags; // [nblk] 1 = the rank owns the block: the active set pt_adaptive_begin starts from
+    } blk;
+    // pt_adaptive_begin .. pt_adaptive_end.  `list` / `count` are what the NEXT pt_render_adaptive renders: the compaction that follows a
+    // call's decision is enqueued behind that call's frame and its count comes back with the frame's own final synchronisation.
+    struct Adaptive {
+        bool on = false;
+        pt_adaptive_params prm{};
+        float4* d_moments = nullptr; // [width * height] {n, s1, s2, 0}
+        uint8_t* d_active = nullptr; // [nblk]
+        uint32_t* d_list = nullptr;  // [owned]
+        uint32_t count = 0, active_blocks = 0;
+        uint64_t pixel_subframes = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the decision + compaction kernels of a call
+    } ad;
     // path state: NSETS independent batch sets; pixel chunks of one frame are dealt round-robin to the sets and each
     // set runs on its own pair of streams, so one chunk's kernel tails overlap with the other chunks' bulk work
     struct BatchSet {
@@ -585,7 +611,22 @@ static void free_path_state(pt_ctx* ctx) {
     ctx->sets.clear();
     ctx->set_cap = ctx->set_pix_cap = 0;
 }
+static void free_adaptive(pt_ctx* ctx) {
+    pt_ctx::Adaptive& ad = ctx->ad;
+    dfree(ad.d_moments); dfree(ad.d_active); dfree(ad.d_list);
+    if (ad.ev0) hipEventDestroy(ad.ev0);
+    if (ad.ev1) hipEventDestroy(ad.ev1);
+    ad = pt_ctx::Adaptive{};
+}
+static void free_blocks(pt_ctx* ctx) {
+    free_adaptive(ctx);
+    pt_ctx::Blocks& b = ctx->blk;
+    dfree(b.d_spans); dfree(b.d_flags); dfree(b.d_offsets); dfree(b.d_parts); dfree(b.d_list); dfree(b.d_counts);
+    if (b.h_counts) hipHostFree(b.h_counts);
+    b = pt_ctx::Blocks{};
+}
 static void free_frame(pt_ctx* ctx) {
+    free_blocks(ctx);
     for (void*& d : ctx->display) {
         if (d) hipFree(d);
         d = nullptr;
@@ -1137,6 +1178,16 @@ struct RegionJob { // non-null: one launch-index range of a foveated launch inst
 struct ChunkMode {
     bool fused_frame = false; // the frame is one fused pass
     bool adapt_grid = false;  // whole frames in flight (frames_in_flight = 3): traversal grids sized by the pass
+    const uint32_t* pixels = nullptr; // the frame's pixel list (null: the rank's whole list, ctx->d_pixels)
+    float4* moments = nullptr;        // pt_render_adaptive: the resolve records the per-pixel moments
+};
+// A frame over a subset of the rank's pixels (pt_render_mask, pt_render_adaptive): a compacted list in the order of d_pixels, and what runs
+// on the context's stream between the frame's last kernel and its end event.
+struct PixelSubset {
+    const uint32_t* pixels;
+    uint32_t count;
+    float4* moments;
+    std::function<int(hipStream_t)> tail;
 };
 
 // When the chunks of a frame may be enqueued by worker threads (PT_ENQUEUE_THREADS): only when the branches of enqueue_chunk they take
@@ -1247,7 +1298,7 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
         // (never above trace_grid: the spill stacks are sized for trace_grid waves and the kernels are compiled for that occupancy)
         const unsigned tgrid = !mode.adapt_grid ? (unsigned)ctx->trace_grid
             : (unsigned)std::min<uint64_t>((uint64_t)ctx->trace_grid, std::max<uint64_t>((uint64_t)ctx->trace_grid_min, pass_paths / (64ull * (uint64_t)ctx->grid_chunks)));
-        BatchParams bp{ctx->d_pixels + pix0, npix, s0, Sc, ctx->has_catcher ? 1 : 0, bs.pixResult, bs.pixAlpha, bs.pixNormal, bs.pixAlbedo};
+        BatchParams bp{(mode.pixels ? mode.pixels : ctx->d_pixels) + pix0, npix, s0, Sc, ctx->has_catcher ? 1 : 0, bs.pixResult, bs.pixAlpha, bs.pixNormal, bs.pixAlbedo};
         hipMemsetAsync(bs.counters, 0, sizeof(uint32_t) * counter_words(nq), bs.stream);
         ChainPass P{ctx, bs, bvh_dev(ctx), job ? job->var.cull_back_occlusion : 0, job ? job->var.radiance_tmin : 0.001f, tgrid, pass_paths,
                     bs.counters, bs.counters + (size_t)nq * CS, bs.counters + (size_t)2 * nq * CS, nq, lc,
@@ -1353,6 +1404,8 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
             if (!fused) hipLaunchKernelGGL(k_accum_stats, dim3(1), dim3(64), 0, bs.stream, bs.counters, nq, last_bounce + 1, 1, bs.totals);
             if (job)
                 hipLaunchKernelGGL(k_resolve_region, dim3((job->nl + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, job->var, job->l0, job->nl);
+            else if (mode.moments)
+                hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp, mode.moments);
             else
                 hipLaunchKernelGGL(k_resolve, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp);
         }
@@ -1405,8 +1458,9 @@ static int frame_begin(pt_ctx* ctx, int slot, bool pipelined, int nsets, hipStre
 // The frame's end: the streams of its sets fan in to the context's stream (a whole frame stays on `whole`: the context's own stream keeps
 // out of the way, one hardware queue fewer), the totals are copied out and ev_end recorded behind them, and the slot is filled in for
 // render_finish, which sums the totals of the frame's `nsets` sets.  resolved_kind >= 0: later frames order their resolves behind ev_end.
+// tail: what a frame over a pixel subset enqueues behind its last kernel, inside the frame's begin / end events.
 static int frame_close(pt_ctx* ctx, int slot, hipEvent_t ev_begin, int nsets, hipStream_t whole, int resolved_kind, uint64_t paths, uint32_t subframes,
-                       const LaunchCounts& lc) {
+                       const LaunchCounts& lc, const std::function<int(hipStream_t)>* tail = nullptr) {
     hipStream_t end_stream = whole ? whole : ctx->stream;
     if (!whole)
         for (int i = 0; i < nsets; ++i) {
@@ -1414,6 +1468,10 @@ static int frame_close(pt_ctx* ctx, int slot, hipEvent_t ev_begin, int nsets, hi
             hipEventRecord(e, ctx->sets[i].stream);
             hipStreamWaitEvent(ctx->stream, e, 0);
         }
+    if (tail && *tail) {
+        int rc = (*tail)(end_stream);
+        if (rc) return rc;
+    }
     CK(hipMemcpyAsync(ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4, totals_of(ctx, slot, 0), sizeof(unsigned long long) * PT_MAX_SETS * 4, hipMemcpyDeviceToHost, end_stream));
     hipEvent_t ev_end = next_event(ctx);
     CK(hipEventRecord(ev_end, end_stream));
@@ -1441,14 +1499,21 @@ static int frame_close(pt_ctx* ctx, int slot, hipEvent_t ev_begin, int nsets, hi
 // 1/8 share runs 7-13 % slower fused while the terrain, the textured terrain and the Cornell box run 3-11 % faster (profiles/r5_14_fused_bounce_loop.md).
 // One scene family on either side of the threshold: a rule of thumb, PT_FUSED_MAX_COST moves it.  Synchronous frames that can take either
 // schedule take part in the measured trial (pt_ctx::sched); sched_record collects their times.
-static bool sched_choose(pt_ctx* ctx, bool pipelined, uint32_t owned, uint32_t vspp) {
+// The static rule; *fused_ok_out: whether the frame could be a fused pass at all.
+static bool sched_static(const pt_ctx* ctx, bool pipelined, uint32_t owned, uint32_t vspp, bool* fused_ok_out = nullptr) {
     const uint64_t frame_paths = (uint64_t)owned * vspp;
     // what the fused pass needs at all: the default schedule of a scene without shadow-catcher materials, the whole frame in one batch set
     const bool fused_ok = ctx->fused == 1 && !pipelined && owned > 0 && ctx->opt.streams <= 0 && !ctx->has_catcher && ctx->opt.split_shadow == 0 && frame_paths <= ctx->opt.max_paths;
     // round 5's rule of thumb, now the first guess: small frames of scenes whose calibration rays are cheap; a tree that was never calibrated
     // (builder forced or imported, challenger not built) keeps the chain unless the scene is tiny
     const bool cost_ok = ctx->bvh.calib_cost > 0.f ? ctx->bvh.calib_cost <= ctx->fused_max_cost : ctx->ntri < 4096u;
-    const bool guess = fused_ok && cost_ok && frame_paths <= ctx->fused_max_paths;
+    if (fused_ok_out) *fused_ok_out = fused_ok;
+    return fused_ok && cost_ok && frame_paths <= ctx->fused_max_paths;
+}
+static bool sched_choose(pt_ctx* ctx, bool pipelined, uint32_t owned, uint32_t vspp) {
+    const uint64_t frame_paths = (uint64_t)owned * vspp;
+    bool fused_ok;
+    const bool guess = sched_static(ctx, pipelined, owned, vspp, &fused_ok);
     bool fused_one_pass = guess;
     ctx->sched_pending.valid = false;
     if (fused_ok && ctx->sched_trials > 0 && frame_paths <= ctx->sched_max_paths && !ctx->span_timing()) {
@@ -1499,7 +1564,9 @@ static void sched_record(pt_ctx* ctx, int slot, float ms) {
 // mode 0: synchronous frame (pixel chunks on all streams); 2: the same chunks without a frame-wide start; 3: the whole frame on one stream
 // count > 1 (pt_render_batch): the launch chain carries the rays of `count` consecutive subframes — generate / trace / shade launches are
 // count times as large, the resolve blends the subframes in order — and leaves the buffers `count` frames would have left.
-static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, int slot = 0, int mode = 0, uint32_t count = 1) {
+// sub: the frame covers a subset of the rank's pixels (synchronous frames only).  It takes the static schedule rule on its own path count and stays
+// out of the measured trial, which is keyed by the full frame; and it keeps within the path state a full frame needs (below).
+static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, int slot = 0, int mode = 0, uint32_t count = 1, const PixelSubset* sub = nullptr) {
     const bool pipelined = mode != 0, whole = mode == 3;
     const char* bad_args = (spp == 0 || spp > 4096) ? "pt_render: samples_per_launch must be in [1,4096]"
         : (count == 0 || count > 4096 || (uint64_t)subframe_index + count > 0xffffffffull) ? "pt_render_batch: count must be in [1,4096] and the subframe indices must fit 32 bits"
@@ -1507,18 +1574,47 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
     int rc = frame_open(ctx, slot, pipelined, "pt_render", bad_args);
     if (rc || ctx->width == 0) return rc;
     const uint32_t vspp = spp * count; // samples of a pixel over the whole batch
-    const uint32_t owned = ctx->owned;
+    const uint32_t owned = sub ? sub->count : ctx->owned;
     // Chunking.  All samples of a pixel stay in one pixel chunk.  The frame is cut into (at least) `streams` pixel
     // chunks that run concurrently on separate stream pairs; a chunk holds at most max_paths/streams paths, so
     // samples are split when spp*pixels exceed that; shadow-catcher scenes run one sample per pass so that the
     // per-pixel normal/albedo sums keep the reference order.  None of this changes a bit of the result.
-    const ChunkMode cm{sched_choose(ctx, pipelined, owned, vspp), whole};
-    const int nsets = cm.fused_frame ? 1 : std::max(1, std::min(PT_MAX_SETS, ctx->opt.streams > 0 ? ctx->opt.streams : 3));
+    ChunkMode cm{false, whole};
+    if (sub) {
+        cm.fused_frame = sched_static(ctx, pipelined, owned, vspp);
+        cm.pixels = sub->pixels;
+        cm.moments = sub->moments;
+        ctx->sched_pending.valid = false;
+        ctx->sched_flags = cm.fused_frame ? 1u : 0u;
+    } else {
+        cm.fused_frame = sched_choose(ctx, pipelined, owned, vspp);
+    }
     const uint32_t max_paths = std::max<uint32_t>(ctx->opt.max_paths, 64u);
-    const uint32_t cap = std::max<uint32_t>(64u, whole ? max_paths : max_paths / nsets);
-    uint32_t Np = whole ? owned : (owned + nsets - 1) / nsets; // pixels per chunk ...
-    Np = std::min(cap, std::max(64u, (Np + 63u) & ~63u)); // ... whole 8x8 blocks, within the set capacity
-    const uint32_t S = ctx->has_catcher ? 1u : std::max(1u, std::min(vspp, cap / Np));
+    // sets, paths per set, pixels per chunk and samples per pass of a frame of `px` pixels, each bounded by lim_* (a subset frame's envelope)
+    struct Shape { int nsets; uint32_t cap, Np, S; };
+    auto shape = [&](uint32_t px, bool fused_frame, int lim_sets, uint32_t lim_cap, uint32_t lim_pix) {
+        Shape sh;
+        sh.nsets = std::min(lim_sets, fused_frame ? 1 : std::max(1, std::min(PT_MAX_SETS, ctx->opt.streams > 0 ? ctx->opt.streams : 3)));
+        sh.cap = std::min(lim_cap, std::max<uint32_t>(64u, whole ? max_paths : max_paths / sh.nsets));
+        sh.Np = whole ? px : (px + sh.nsets - 1) / sh.nsets; // pixels per chunk ...
+        sh.Np = std::min(std::min(sh.cap, lim_pix), std::max(64u, (sh.Np + 63u) & ~63u)); // ... whole 8x8 blocks, within the set capacity
+        sh.S = ctx->has_catcher ? 1u : std::max(1u, std::min(vspp, sh.cap / sh.Np));
+        return sh;
+    };
+    // A subset frame asks for what its own size needs, but never for more than the larger of what is allocated and what the rank's FULL frame
+    // of these samples would ask for: after a full frame it allocates nothing, and a context that began with a small mask (or with foveated
+    // launches) grows once to the full frame's shape instead of cutting every later frame into chunks of its first one.
+    int lim_sets = PT_MAX_SETS;
+    uint32_t lim_cap = 0xffffffffu, lim_pix = 0xffffffc0u;
+    if (sub) {
+        const Shape full = shape(ctx->owned, sched_static(ctx, pipelined, ctx->owned, vspp), lim_sets, lim_cap, lim_pix);
+        lim_sets = std::max((int)ctx->sets.size(), full.nsets);
+        lim_cap = std::max(ctx->set_cap, full.Np * full.S);
+        lim_pix = std::max(ctx->set_pix_cap & ~63u, full.Np);
+    }
+    const Shape sh = shape(owned, cm.fused_frame, lim_sets, lim_cap, lim_pix);
+    const int nsets = sh.nsets;
+    const uint32_t Np = sh.Np, S = sh.S;
     if (owned) {
         rc = ensure_path_state(ctx, nsets, Np * S, Np); // waits for the frames in flight before it re-allocates
         if (rc) return rc;
@@ -1587,7 +1683,7 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
         }
     }
     // a later foveated frame (or a whole frame) orders its resolves behind the end of a frame of pixel chunks in flight
-    return frame_close(ctx, slot, ev_begin, used, whole_stream, (pipelined && !whole) ? 0 : -1, (uint64_t)owned * vspp, count, lc);
+    return frame_close(ctx, slot, ev_begin, used, whole_stream, (pipelined && !whole) ? 0 : -1, (uint64_t)owned * vspp, count, lc, sub ? &sub->tail : nullptr);
 }
 
 // PT_DEBUG_COUNTS: the traversal counters of the frame just waited for, and the per-bounce queue sizes of the last chunk of set 0
@@ -1893,6 +1989,187 @@ extern "C" int pt_render_regions(pt_ctx* ctx, const pt_region* regions, uint32_t
     }
     if (rc != PT_OK) return rc;
     if (host_rgba8 && ctx->width) return pt_download(ctx, PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)ctx->width * ctx->height);
+    return PT_OK;
+}
+
+// ------------------------------------------------------------------ block masks and adaptive stopping
+// the block table of the current size and partition: block b's pixels are d_pixels[start, start + size) (build_pixel_lists walks the same order)
+static int build_blocks(pt_ctx* ctx) {
+    pt_ctx::Blocks& B = ctx->blk;
+    const int w = ctx->width, h = ctx->height;
+    B.nbx = (uint32_t)(w + 7) / 8u;
+    B.nby = (uint32_t)(h + 7) / 8u;
+    B.nblk = B.nbx * B.nby;
+    std::vector<BlockSpan> spans(B.nblk);
+    uint32_t at = 0;
+    B.owned_blocks = 0;
+    for (uint32_t by = 0; by < B.nby; ++by)
+        for (uint32_t bx = 0; bx < B.nbx; ++bx) {
+            const int owner = (int)(((bx * 8u) / (uint32_t)ctx->tile_w + (by * 8u) / (uint32_t)ctx->tile_h) % (uint32_t)ctx->world);
+            const uint32_t size = owner == ctx->rank ? (uint32_t)(std::min(8, w - (int)bx * 8) * std::min(8, h - (int)by * 8)) : 0u;
+            spans[by * B.nbx + bx] = BlockSpan{at, size};
+            B.owned_flags.push_back(size ? 1 : 0);
+            at += size;
+            B.owned_blocks += size ? 1u : 0u;
+        }
+    if (at != ctx->owned) return fail(ctx, PT_ERR_INVALID, "block table does not match the pixel list");
+    CK(dalloc(&B.d_spans, (size_t)B.nblk));
+    CK(dalloc(&B.d_flags, (size_t)B.nblk));
+    CK(dalloc(&B.d_offsets, (size_t)B.nblk));
+    B.nparts = (B.nblk + 255u) / 256u;
+    CK(dalloc(&B.d_parts, (size_t)2 * B.nparts));
+    CK(dalloc(&B.d_list, (size_t)ctx->owned));
+    CK(dalloc(&B.d_counts, (size_t)2));
+    CK(hipHostMalloc((void**)&B.h_counts, sizeof(uint32_t) * 2));
+    CK(hipMemcpy(B.d_spans, spans.data(), sizeof(BlockSpan) * B.nblk, hipMemcpyHostToDevice));
+    return PT_OK;
+}
+static int ensure_blocks(pt_ctx* ctx) {
+    if (ctx->blk.d_spans) return PT_OK;
+    const int rc = build_blocks(ctx);
+    if (rc) free_blocks(ctx); // all of it or nothing: the next call starts over
+    return rc;
+}
+// flags -> compacted list + counts, then the copy of `words` counts (1: pixels; 2: and blocks) to the pinned host words; all on stream s
+static int compact_enqueue(pt_ctx* ctx, hipStream_t s, const uint8_t* d_flags, uint32_t* d_list, int words) {
+    pt_ctx::Blocks& B = ctx->blk;
+    uint32_t *part_pix = B.d_parts, *part_blk = B.d_parts + B.nparts;
+    hipLaunchKernelGGL(k_mask_partials, dim3(B.nparts), dim3(256), 0, s, d_flags, B.d_spans, B.nblk, B.d_offsets, part_pix, part_blk);
+    hipLaunchKernelGGL(k_mask_scan_parts, dim3(1), dim3(1024), 0, s, part_pix, part_blk, B.nparts, B.d_counts);
+    hipLaunchKernelGGL(k_mask_compact, dim3((B.nblk + 3u) / 4u), dim3(256), 0, s, d_flags, B.d_spans, B.nblk, B.d_offsets, part_pix, ctx->d_pixels, d_list);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(B.h_counts, B.d_counts, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s));
+    return PT_OK;
+}
+// what pt_render_mask and the adaptive entry points refuse alike; leaves the context drained and its device current
+static int subset_open(pt_ctx* ctx, const char* what, bool check_spp, uint32_t spp) {
+    int rc = drain(ctx); // synchronous: frames in flight (pt_options.frames_in_flight) finish first
+    if (rc) return rc;
+    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, (std::string(what) + ": no frame size yet (pt_resize)").c_str());
+    if (check_spp && (spp == 0 || spp > 4096)) return fail(ctx, PT_ERR_INVALID, (std::string(what) + ": samples_per_launch must be in [1,4096]").c_str());
+    CK(hipSetDevice(ctx->device));
+    return ensure_blocks(ctx);
+}
+static int subset_render(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, const PixelSubset& sub, uint32_t* host_rgba8) {
+    int rc = render_enqueue(ctx, spp, subframe_index, 0, 0, 1, &sub);
+    if (rc == PT_OK) rc = render_finish(ctx);
+    if (rc != PT_OK) return rc;
+    if (host_rgba8) return pt_download(ctx, PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)ctx->width * ctx->height);
+    return PT_OK;
+}
+
+extern "C" int pt_render_mask(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, const uint8_t* block_mask, uint32_t* host_rgba8, uint32_t* active_pixels) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_render_mask: null context");
+    if (!block_mask) return fail(ctx, PT_ERR_INVALID, "pt_render_mask: null block mask");
+    int rc = subset_open(ctx, "pt_render_mask", true, spp);
+    if (rc) return rc;
+    pt_ctx::Blocks& B = ctx->blk;
+    CK(hipMemcpyAsync(B.d_flags, block_mask, B.nblk, hipMemcpyHostToDevice, ctx->stream));
+    rc = compact_enqueue(ctx, ctx->stream, B.d_flags, B.d_list, 1);
+    if (rc) return rc;
+    CK(hipStreamSynchronize(ctx->stream)); // the chunking is decided on the host: it needs the count
+    const PixelSubset sub{B.d_list, B.h_counts[0], nullptr, nullptr};
+    if (active_pixels) *active_pixels = sub.count;
+    return subset_render(ctx, spp, subframe_index, sub, host_rgba8);
+}
+
+extern "C" int pt_adaptive_begin(pt_ctx* ctx, const pt_adaptive_params* prm) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_adaptive_begin: null context");
+    if (!prm) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: null parameters");
+    if (!(prm->threshold >= 0.f) || !std::isfinite(prm->threshold)) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: threshold must be finite and >= 0");
+    if (!(prm->dark_floor >= 0.f) || !std::isfinite(prm->dark_floor)) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: dark_floor must be finite and >= 0");
+    if (prm->min_subframes < 2) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: min_subframes must be at least 2");
+    int rc = subset_open(ctx, "pt_adaptive_begin", false, 0);
+    if (rc) return rc;
+    free_adaptive(ctx);
+    pt_ctx::Blocks& B = ctx->blk;
+    pt_ctx::Adaptive& A = ctx->ad;
+    const size_t n = (size_t)ctx->width * ctx->height;
+    CK(dalloc(&A.d_moments, n));
+    CK(dalloc(&A.d_active, (size_t)B.nblk));
+    CK(dalloc(&A.d_list, (size_t)ctx->owned));
+    CK(hipEventCreate(&A.ev0));
+    CK(hipEventCreate(&A.ev1));
+    CK(hipMemsetAsync(A.d_moments, 0, sizeof(float4) * n, ctx->stream));
+    CK(hipMemcpyAsync(A.d_active, B.owned_flags.data(), B.nblk, hipMemcpyHostToDevice, ctx->stream)); // (blocks of other ranks are never active)
+    rc = compact_enqueue(ctx, ctx->stream, A.d_active, A.d_list, 2);
+    if (rc) return rc;
+    CK(hipStreamSynchronize(ctx->stream));
+    A.count = B.h_counts[0];
+    A.active_blocks = B.h_counts[1];
+    A.prm = *prm;
+    A.pixel_subframes = 0;
+    A.on = true;
+    return PT_OK;
+}
+
+extern "C" int pt_render_adaptive(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, uint32_t* host_rgba8, pt_adaptive_stats* out) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_render_adaptive: null context");
+    if (!ctx->ad.on) return fail(ctx, PT_ERR_INVALID, "pt_render_adaptive: call pt_adaptive_begin first");
+    int rc = subset_open(ctx, "pt_render_adaptive", true, spp);
+    if (rc) return rc;
+    pt_ctx::Blocks& B = ctx->blk;
+    pt_ctx::Adaptive& A = ctx->ad;
+    const uint32_t rendered = A.count;
+    PixelSubset sub{A.d_list, rendered, A.d_moments, nullptr};
+    if (rendered) // behind the frame's last kernel: decide for the blocks just rendered, then compact for the next call (in place: every reader of the list has finished)
+        sub.tail = [ctx](hipStream_t s) -> int {
+            pt_ctx::Blocks& B = ctx->blk;
+            pt_ctx::Adaptive& A = ctx->ad;
+            const AdaptParams ap{A.prm.threshold, A.prm.dark_floor, (float)A.prm.min_subframes, (float)A.prm.max_subframes};
+            CK(hipEventRecord(A.ev0, s));
+            hipLaunchKernelGGL(k_adapt_decide, dim3((B.nblk + 3u) / 4u), dim3(256), 0, s, A.d_moments, A.d_active, B.d_spans, B.nblk, B.nbx, ctx->width, ctx->height, ap);
+            int rc = compact_enqueue(ctx, s, A.d_active, A.d_list, 2);
+            if (rc) return rc;
+            CK(hipEventRecord(A.ev1, s));
+            return PT_OK;
+        };
+    rc = subset_render(ctx, spp, subframe_index, sub, host_rgba8);
+    if (rc) return rc;
+    float ms = 0.f;
+    if (rendered) {
+        A.count = B.h_counts[0];
+        A.active_blocks = B.h_counts[1];
+        A.pixel_subframes += rendered;
+        CK(hipEventElapsedTime(&ms, A.ev0, A.ev1));
+    }
+    if (out) {
+        out->blocks = B.owned_blocks;
+        out->active_blocks = A.active_blocks;
+        out->active_pixels = rendered;
+        out->pixel_subframes = A.pixel_subframes;
+        out->decide_ms = ms;
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_adaptive_end(pt_ctx* ctx) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_adaptive_end: null context");
+    int rc = drain(ctx);
+    if (rc) return rc;
+    if (ctx->ad.on) {
+        CK(hipSetDevice(ctx->device));
+        CK(hipStreamSynchronize(ctx->stream));
+    }
+    free_adaptive(ctx);
+    return PT_OK;
+}
+
+extern "C" int pt_download_adaptive(pt_ctx* ctx, int which, void* host, size_t bytes) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_download_adaptive: null context");
+    if (!host) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: null destination");
+    if (!ctx->ad.on) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: call pt_adaptive_begin first");
+    const pt_ctx::Blocks& B = ctx->blk;
+    CK(hipSetDevice(ctx->device));
+    if (which == PT_ADAPT_MOMENTS) {
+        if (bytes != sizeof(float4) * (size_t)ctx->width * ctx->height) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: byte count does not match the frame size");
+        CK(hipMemcpy(host, ctx->ad.d_moments, bytes, hipMemcpyDeviceToHost));
+    } else if (which == PT_ADAPT_ACTIVE) {
+        if (bytes != (size_t)B.nblk) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: byte count does not match the block grid");
+        CK(hipMemcpy(host, ctx->ad.d_active, bytes, hipMemcpyDeviceToHost));
+    } else {
+        return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: unknown array");
+    }
     return PT_OK;
 }
 

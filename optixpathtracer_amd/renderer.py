@@ -244,6 +244,57 @@ class SampleRenderer:
         self.renderRegions(regs, variant or self.SV4_VARIANT, out)
         self.launchParams.frame.subframe_index += 1
 
+    # -- block masks and adaptive stopping (pt_render_mask, pt_render_adaptive; include/pt_amd.h)
+    def blockGrid(self):
+        """(nby, nbx): the 8x8 blocks of the current frame size."""
+        w, h = self.launchParams.frame.size
+        return (h + 7) // 8, (w + 7) // 8
+
+    def renderMask(self, mask: np.ndarray, out: np.ndarray | None = None) -> int:
+        """render() for the 8x8 blocks whose byte in `mask` (nby x nbx, or flat) is non-zero: those pixels end up as render() leaves them,
+        all others are untouched.  Synchronous.  Like render(), it leaves launchParams.frame.subframe_index to the application.
+        Returns the number of pixels rendered."""
+        nby, nbx = self.blockGrid()
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if m.size != nby * nbx:
+            raise ValueError(f"renderMask: the mask needs {nby} x {nbx} entries, got {m.size}")
+        ptr = None
+        if out is not None:
+            assert out.dtype == np.uint32 and out.flags["C_CONTIGUOUS"]
+            ptr = out.ctypes.data
+        n = C.c_uint32()
+        self._ck(self._L.pt_render_mask(self._ctx, int(self.launchParams.samples_per_launch), int(self.launchParams.frame.subframe_index), m.ctypes.data, ptr, C.byref(n)), "pt_render_mask")
+        return n.value
+
+    def adaptiveBegin(self, threshold=0.02, dark_floor=0.01, min_subframes=8, max_subframes=0):
+        """Starts (or restarts, after a camera move) an adaptive accumulation: all blocks active, moments cleared."""
+        prm = _lib.AdaptiveParams(float(threshold), float(dark_floor), int(min_subframes), int(max_subframes))
+        self._ck(self._L.pt_adaptive_begin(self._ctx, C.byref(prm)), "pt_adaptive_begin")
+
+    def renderAdaptive(self, out: np.ndarray | None = None) -> dict:
+        """render() for the blocks that have not converged yet, then the stopping rule for them on the GPU.  Returns pt_adaptive_stats as a
+        dict; a progressive loop ends when its active_blocks is 0.  Advancing subframe_index stays the caller's job."""
+        ptr = None
+        if out is not None:
+            assert out.dtype == np.uint32 and out.flags["C_CONTIGUOUS"]
+            ptr = out.ctypes.data
+        st = _lib.AdaptiveStats()
+        self._ck(self._L.pt_render_adaptive(self._ctx, int(self.launchParams.samples_per_launch), int(self.launchParams.frame.subframe_index), ptr, C.byref(st)), "pt_render_adaptive")
+        return st.as_dict()
+
+    def adaptiveArrays(self):
+        """(moments float32[h, w, 4] = {n, s1, s2, 0} per pixel, active uint8[nby, nbx])"""
+        w, h = self.launchParams.frame.size
+        nby, nbx = self.blockGrid()
+        moments = np.empty((h, w, 4), np.float32)
+        active = np.empty((nby, nbx), np.uint8)
+        self._ck(self._L.pt_download_adaptive(self._ctx, _lib.PT_ADAPT_MOMENTS, moments.ctypes.data, moments.nbytes), "pt_download_adaptive")
+        self._ck(self._L.pt_download_adaptive(self._ctx, _lib.PT_ADAPT_ACTIVE, active.ctypes.data, active.nbytes), "pt_download_adaptive")
+        return moments, active
+
+    def adaptiveEnd(self):
+        self._ck(self._L.pt_adaptive_end(self._ctx), "pt_adaptive_end")
+
     # -- beyond the reference (runtime versions of its compile-time constants, multi-GPU, stats)
     def setOptions(self, max_depth=8, bsdf_mode=PT_BSDF_DISNEY, max_paths=0, bvh_kind=0, trace_kernel=0, streams=0, split_shadow=0, kernel_timing=0, frames_in_flight=0):
         o = Options(max_depth, bsdf_mode, max_paths, kernel_timing, bvh_kind, trace_kernel, streams, split_shadow, frames_in_flight)
