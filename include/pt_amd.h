@@ -523,6 +523,59 @@ int pt_update_meshes(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int
  * changes, so a failure leaves all ranks as they were.  kernel_ms: the slowest rank's */
 int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms /* may be NULL: the slowest rank */);
 
+/* Updates fed from GPU memory: the same update, with the staging and the validation on the device.
+ * pt_update_meshes_device is pt_update_meshes with pt_mesh_update.vertex a DEVICE pointer on the context's device (a simulation or
+ * skinning step that leaves its vertices in GPU memory); pt_transform_meshes gives a 3x4 matrix per mesh instead of vertices (the OptiX
+ * analogue is an instance transform).  One kernel stages all named meshes of a call into the scratch vertex array; everything behind that
+ * array — refit, rebuild, commit — is pt_update_meshes' code.
+ * Same contract as pt_update_meshes, item by item:
+ *   - only vertex positions change;
+ *   - one call does ONE refit or ONE rebuild and is atomic: on any error the context is exactly as before;
+ *   - it waits for the frames in flight and is complete when it returns; accum_buffer is left alone;
+ *   - the on-line chain/fused schedule trial starts over; PT_UPDATE_REFIT on a PT8_NODE64 build returns PT_ERR_UNSUPPORTED;
+ *   - kernel_ms (may be NULL) covers the staging kernel as well as the refit or the build.
+ * Device pointers:
+ *   - the library reads them on pt_stream(ctx), under the STREAM CONTRACT: an array produced on another stream must be complete, or ordered
+ *     with pt_wait_event, before the call;
+ *   - before any device work each pointer is checked with hipPointerGetAttributes (as pt_render_device checks its buffer): a null pointer, a
+ *     pointer HIP does not know, host memory (pinned or managed included), memory of another device, a pointer that is not 4-byte aligned, or
+ *     an array that does not fit into what is left of its allocation returns PT_ERR_INVALID.  No wider alignment than 4 bytes is assumed.
+ * Validation on the device:
+ *   - the staging kernel tests the exponent bits of every coordinate it writes (no compiler mode can remove the test) and records the lowest
+ *     position in the call of a mesh with a non-finite coordinate; the host reads that word at the synchronisation the staging makes anyway
+ *     (PT_UPDATE_REBUILD waits once more, before the build: the builder never sees a non-finite vertex);
+ *   - on a bad mesh the call returns PT_ERR_INVALID, pt_last_error names the mesh index, and nothing of the context has changed.
+ * Transform arithmetic:
+ *   - float32, one rounding per operation, no fused multiply-add, in exactly this order:
+ *       x' = ((m[0]*x + m[1]*y) + m[2]*z) + m[3],  y' likewise with m[4..7],  z' with m[8..11];
+ *     float32 NumPy evaluating that expression reproduces the vertices bit for bit.  The identity matrix therefore maps -0.0f to +0.0f;
+ *   - a matrix entry that is not finite is refused on the host, a result that is not finite (an overflow) by the device check.
+ * Rest positions:
+ *   - a mesh's rest positions are the ones last given explicitly: by pt_create, pt_update_meshes or pt_update_meshes_device;
+ *   - the first pt_transform_meshes of a context (either source) allocates the rest array as a copy of the current vertices: 12 bytes per
+ *     vertex, only for contexts that use transforms; if that allocation fails the call returns PT_ERR_HIP and nothing has changed.  From then
+ *     on explicit updates write both arrays at commit;
+ *   - PT_FROM_REST transforms the rest positions (repeated calls do not drift), PT_FROM_CURRENT what is there now; meshes not named in a
+ *     call keep their current positions;
+ *   - pt_download_vertices(rest = 1) before any transform returns the current positions.
+ * PT_ERR_INVALID also for: null arguments, n == 0, a mesh out of range, a mesh named twice, a wrong num_vertices, an unknown source or mode. */
+int pt_update_meshes_device(pt_ctx* ctx, const pt_mesh_update* updates /* .vertex: device memory */, uint32_t n, int mode, double* kernel_ms /* may be NULL */);
+
+typedef struct pt_mesh_transform {
+    uint32_t mesh; /* index into the pt_scene_desc.meshes the context was created from */
+    float m[12];   /* row-major 3x4; p' = M[:, :3] p + M[:, 3] */
+} pt_mesh_transform;
+
+enum pt_transform_source { PT_FROM_REST = 0, PT_FROM_CURRENT = 1 };
+
+int pt_transform_meshes(pt_ctx* ctx, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms /* may be NULL */);
+/* the transforms are host data and go to every rank; every rank stages before any rank commits, like pt_multi_update_meshes.  (There is no
+ * multi-rank variant of the device-pointer call: the pointer lives on one device; with one process per GPU call the rank's own context.) */
+int pt_multi_transform_meshes(pt_multi* m, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms /* may be NULL: the slowest rank */);
+
+/* current (rest = 0) or rest (rest = 1) positions of one mesh, to host memory.  bytes must equal num_vertices * 12. */
+int pt_download_vertices(pt_ctx* ctx, uint32_t mesh, int rest, float* host, size_t bytes);
+
 /* Scene ingestion, host only (no GPU needed): loadOBJ (HelloPathtracing_original/Model.cpp:137-212 — tinyobjloader 2.0.0's LoadObj with
  * triangulation, then one TriangleMesh per (shape, material id)) as native code.  The arrays are the reference's bit for bit
  * (tests/test_objloader.py: the reference's own Model.cpp, compiled from where it lies, on committed fixtures and random files):

@@ -23,10 +23,12 @@ EXPORTS = [
     "pt_render_device", "pt_stream", "pt_wait_event", "pt_get_stats_n", "pt_stats_size",
     "pt_load_obj", "pt_obj_free", "pt_obj_num_meshes", "pt_obj_get_mesh", "pt_obj_num_textures", "pt_obj_texture_path", "pt_obj_last_error",
     "pt_update_meshes", "pt_multi_update_meshes",
+    "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
 ]
 
 PT_UPDATE_REFIT, PT_UPDATE_REBUILD = 0, 1  # pt_update_mode
+PT_FROM_REST, PT_FROM_CURRENT = 0, 1  # pt_transform_source
 
 
 PT_ADAPT_MOMENTS, PT_ADAPT_ACTIVE = 0, 1  # pt_adaptive_array
@@ -46,6 +48,10 @@ class AdaptiveStats(C.Structure):  # pt_adaptive_stats
 
 class MeshUpdate(C.Structure):  # pt_mesh_update
     _fields_ = [("mesh", C.c_uint32), ("vertex", C.POINTER(C.c_float)), ("num_vertices", C.c_uint32)]
+
+
+class MeshTransform(C.Structure):  # pt_mesh_transform
+    _fields_ = [("mesh", C.c_uint32), ("m", C.c_float * 12)]
 
 
 class DenoiseParams(C.Structure):  # pt_denoise_params
@@ -219,6 +225,10 @@ def load_library() -> C.CDLL:
     L.pt_export_bvh.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]
     L.pt_update_meshes.argtypes = [vp, C.POINTER(MeshUpdate), u32, i, C.POINTER(C.c_double)]
     L.pt_multi_update_meshes.argtypes = [vp, C.POINTER(MeshUpdate), u32, i, C.POINTER(C.c_double)]
+    L.pt_update_meshes_device.argtypes = [vp, C.POINTER(MeshUpdate), u32, i, C.POINTER(C.c_double)]
+    L.pt_transform_meshes.argtypes = [vp, C.POINTER(MeshTransform), u32, i, i, C.POINTER(C.c_double)]
+    L.pt_multi_transform_meshes.argtypes = [vp, C.POINTER(MeshTransform), u32, i, i, C.POINTER(C.c_double)]
+    L.pt_download_vertices.argtypes = [vp, u32, i, vp, C.c_size_t]
     L.pt_render_mask.argtypes = [vp, u32, u32, vp, vp, C.POINTER(u32)]
     L.pt_adaptive_begin.argtypes = [vp, C.POINTER(AdaptiveParams)]
     L.pt_render_adaptive.argtypes = [vp, u32, u32, vp, C.POINTER(AdaptiveStats)]

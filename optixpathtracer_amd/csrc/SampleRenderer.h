@@ -219,6 +219,22 @@ class SampleRenderer {
         ck(pt_update_meshes(ctx, u.data(), (uint32_t)u.size(), rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
         return ms;
     }
+    // ... with the new positions in DEVICE memory (pt_update_meshes_device): `updates` name a mesh, a device pointer on the context's device to
+    // num_vertices * 3 floats (4-byte aligned) and that count; the arrays must be complete, or ordered with pt_wait_event.  The vertices are
+    // validated on the GPU; Model is not touched.
+    double updateMeshesDevice(const std::vector<pt_mesh_update>& updates, bool rebuild = false) {
+        double ms = 0;
+        ck(pt_update_meshes_device(ctx, updates.data(), (uint32_t)updates.size(), rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
+        return ms;
+    }
+    // ... or a 3x4 matrix per mesh (pt_transform_meshes; the OptiX analogue is an instance transform): applied on the GPU to the mesh's rest
+    // positions — the ones last given explicitly — or with from_current = true to what is there now.
+    double transformMeshes(const std::vector<pt_mesh_transform>& transforms, bool from_current = false, bool rebuild = false) {
+        double ms = 0;
+        ck(pt_transform_meshes(ctx, transforms.data(), (uint32_t)transforms.size(), from_current ? PT_FROM_CURRENT : PT_FROM_REST,
+                               rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
+        return ms;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;
@@ -300,6 +316,12 @@ class MultiSampleRenderer {
         double ms = 0;
         const std::vector<pt_mesh_update> u = SampleRenderer::mesh_updates(model, meshes);
         ck(pt_multi_update_meshes(multi, u.data(), (uint32_t)u.size(), rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
+        return ms;
+    }
+    double transformMeshes(const std::vector<pt_mesh_transform>& transforms, bool from_current = false, bool rebuild = false) { // on every rank
+        double ms = 0;
+        ck(pt_multi_transform_meshes(multi, transforms.data(), (uint32_t)transforms.size(), from_current ? PT_FROM_CURRENT : PT_FROM_REST,
+                                     rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
         return ms;
     }
     void downloadDisplayedPixels(uint32_t h_pixels[]) { // the frame on display (rank 0's display buffer) in the frames-in-flight mode

@@ -23,6 +23,7 @@
 #include "pt_kernels.h"
 #include "pt_bvh8.h"
 #include "pt_fused.h"
+#include "pt_stage.h"
 
 static thread_local std::string g_create_error;
 
@@ -94,6 +95,10 @@ struct pt_ctx {
     size_t nvert = 0;
     std::vector<uint32_t> mesh_vbase, mesh_nv; // per mesh: first vertex in the global vertex space, vertex count (pt_update_meshes)
     float* d_verts = nullptr;
+    float* d_rest = nullptr;         // rest positions (pt_transform_meshes), allocated by the first transform: until then d_verts stands for them
+    uint8_t* d_stage = nullptr;      // k_stage_vertices: the non-finite report word, then the call's segment table (grown on demand)
+    size_t stage_cap = 0;
+    uint32_t* h_stage_bad = nullptr; // pinned: the report word, read after the synchronisation update_stage makes anyway
     uint32_t* d_idx = nullptr;
     uint32_t* d_tri_mesh = nullptr;
     pt_material* d_mats = nullptr;
@@ -649,6 +654,8 @@ extern "C" int pt_destroy(pt_ctx* ctx) {
     for (hipStream_t st : ctx->side_streams) if (st) hipStreamDestroy(st);
     free_frame(ctx);
     dfree(ctx->d_verts); dfree(ctx->d_idx); dfree(ctx->d_tri_mesh); dfree(ctx->d_mats);
+    dfree(ctx->d_rest); dfree(ctx->d_stage);
+    if (ctx->h_stage_bad) hipHostFree(ctx->h_stage_bad);
     dfree(ctx->d_mesh_tex); dfree(ctx->d_uvs); dfree(ctx->d_textris); dfree(ctx->d_textures);
     for (uint32_t*& px : ctx->d_tex_pixels) dfree(px);
     pt_bvh_free(&ctx->bvh);
@@ -2560,45 +2567,196 @@ struct MeshUpdate {
     float4* nrm = nullptr;
     TexTri* textris = nullptr;
     double build_ms = 0;
-    void discard() { dfree(d_new); pt_bvh_free(&nb); dfree(nrm); dfree(textris); }
+    float* rest = nullptr;  // the first transform of a context: the rest array, a copy of the vertices before the call
+    std::vector<std::pair<size_t, size_t>> explicit_ranges; // (first float, floats) of the meshes given explicitly: they become rest positions too
+    double stage_ms = 0;    // k_stage_vertices
+    std::vector<uint8_t> table; // its report word and segment table on the host: alive until the stream has been waited for
+    void discard() { dfree(d_new); pt_bvh_free(&nb); dfree(nrm); dfree(textris); dfree(rest); }
+};
+
+// What update_stage writes into the named meshes: host arrays (copied), device arrays or transforms (k_stage_vertices).
+struct UpdateSource {
+    const char* fn;                             // the entry point, for messages
+    const pt_mesh_update* host = nullptr;       // pt_update_meshes
+    const pt_mesh_update* dev = nullptr;        // pt_update_meshes_device
+    const pt_mesh_transform* xform = nullptr;   // pt_transform_meshes
+    int from = PT_FROM_REST;
+    uint32_t n = 0;
 };
 
 // host-side checks, shared by every rank (they share the scene's mesh table)
-static int update_validate(const pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, std::string& err) {
-    if (!up || n == 0) { err = "pt_update_meshes: no updates"; return PT_ERR_INVALID; }
-    if (mode != PT_UPDATE_REFIT && mode != PT_UPDATE_REBUILD) { err = "pt_update_meshes: mode must be PT_UPDATE_REFIT or PT_UPDATE_REBUILD"; return PT_ERR_INVALID; }
+static int update_validate(const pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, std::string& err, const char* fn = "pt_update_meshes",
+                           bool host_vertices = true) {
+    const std::string f = std::string(fn) + ": ";
+    if (!up || n == 0) { err = f + "no updates"; return PT_ERR_INVALID; }
+    if (mode != PT_UPDATE_REFIT && mode != PT_UPDATE_REBUILD) { err = f + "mode must be PT_UPDATE_REFIT or PT_UPDATE_REBUILD"; return PT_ERR_INVALID; }
     std::vector<char> seen(ctx->nmesh, 0);
     for (uint32_t k = 0; k < n; ++k) {
         const pt_mesh_update& u = up[k];
-        if (u.mesh >= ctx->nmesh) { err = "pt_update_meshes: mesh index " + std::to_string(u.mesh) + " out of range"; return PT_ERR_INVALID; }
-        if (seen[u.mesh]) { err = "pt_update_meshes: mesh " + std::to_string(u.mesh) + " named twice"; return PT_ERR_INVALID; }
+        if (u.mesh >= ctx->nmesh) { err = f + "mesh index " + std::to_string(u.mesh) + " out of range"; return PT_ERR_INVALID; }
+        if (seen[u.mesh]) { err = f + "mesh " + std::to_string(u.mesh) + " named twice"; return PT_ERR_INVALID; }
         seen[u.mesh] = 1;
-        if (!u.vertex) { err = "pt_update_meshes: null vertex pointer"; return PT_ERR_INVALID; }
+        if (!u.vertex) { err = f + "null vertex pointer"; return PT_ERR_INVALID; }
         if (u.num_vertices != ctx->mesh_nv[u.mesh]) {
-            err = "pt_update_meshes: mesh " + std::to_string(u.mesh) + " has " + std::to_string(ctx->mesh_nv[u.mesh]) + " vertices, the update " + std::to_string(u.num_vertices);
+            err = f + "mesh " + std::to_string(u.mesh) + " has " + std::to_string(ctx->mesh_nv[u.mesh]) + " vertices, the update " + std::to_string(u.num_vertices);
             return PT_ERR_INVALID;
         }
-        for (size_t i = 0; i < 3 * (size_t)u.num_vertices; ++i)
-            if (!std::isfinite(u.vertex[i])) { err = "pt_update_meshes: non-finite coordinate in mesh " + std::to_string(u.mesh); return PT_ERR_INVALID; }
+        if (host_vertices) {
+            for (size_t i = 0; i < 3 * (size_t)u.num_vertices; ++i)
+                if (!std::isfinite(u.vertex[i])) { err = f + "non-finite coordinate in mesh " + std::to_string(u.mesh); return PT_ERR_INVALID; }
+        } else if ((uintptr_t)u.vertex & 3u) {
+            err = f + "the vertex pointer of mesh " + std::to_string(u.mesh) + " is not 4-byte aligned";
+            return PT_ERR_INVALID;
+        }
     }
-    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = "pt_update_meshes: refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
+    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = f + "refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
     return PT_OK;
 }
 
-static int update_stage(pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, MeshUpdate& U) {
+static int transform_validate(const pt_ctx* ctx, const pt_mesh_transform* t, uint32_t n, int source, int mode, std::string& err, const char* fn) {
+    const std::string f = std::string(fn) + ": ";
+    if (!t || n == 0) { err = f + "no transforms"; return PT_ERR_INVALID; }
+    if (source != PT_FROM_REST && source != PT_FROM_CURRENT) { err = f + "source must be PT_FROM_REST or PT_FROM_CURRENT"; return PT_ERR_INVALID; }
+    if (mode != PT_UPDATE_REFIT && mode != PT_UPDATE_REBUILD) { err = f + "mode must be PT_UPDATE_REFIT or PT_UPDATE_REBUILD"; return PT_ERR_INVALID; }
+    std::vector<char> seen(ctx->nmesh, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        if (t[k].mesh >= ctx->nmesh) { err = f + "mesh index " + std::to_string(t[k].mesh) + " out of range"; return PT_ERR_INVALID; }
+        if (seen[t[k].mesh]) { err = f + "mesh " + std::to_string(t[k].mesh) + " named twice"; return PT_ERR_INVALID; }
+        seen[t[k].mesh] = 1;
+        for (int i = 0; i < 12; ++i)
+            if (!std::isfinite(t[k].m[i])) { err = f + "non-finite matrix entry for mesh " + std::to_string(t[k].mesh); return PT_ERR_INVALID; }
+    }
+    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = f + "refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
+    return PT_OK;
+}
+
+// pt_update_meshes_device: every pointer must be memory of the context's device that HIP knows, checked before any device work (as
+// pt_render_device checks its buffer) — a host pointer handed to a kernel is a fault, not an error code.  Where HIP tells the extent of
+// the allocation, the array has to lie inside it.
+static int device_pointers_validate(pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, std::string& err) {
+    CK(hipSetDevice(ctx->device));
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string who = "pt_update_meshes_device: the vertex pointer of mesh " + std::to_string(up[k].mesh);
+        hipPointerAttribute_t at;
+        const hipError_t pe = hipPointerGetAttributes(&at, up[k].vertex);
+        if (pe != hipSuccess || at.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError(); // an unknown pointer leaves hipErrorInvalidValue behind
+            err = who + " is not device memory (for host arrays use pt_update_meshes)";
+            return PT_ERR_INVALID;
+        }
+        if (at.device != ctx->device) { err = who + " is memory of device " + std::to_string(at.device) + ", the context is on device " + std::to_string(ctx->device); return PT_ERR_INVALID; }
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)up[k].vertex) != hipSuccess) { (void)hipGetLastError(); continue; }
+        const size_t off = (size_t)((const char*)up[k].vertex - (const char*)base), bytes = sizeof(float) * 3 * (size_t)up[k].num_vertices;
+        if (off > size || bytes > size - off) { err = who + " has fewer than num_vertices * 12 bytes left in its allocation"; return PT_ERR_INVALID; }
+    }
+    return PT_OK;
+}
+
+// Enqueues k_stage_vertices for a device or transform source into U.d_new (which already holds the current vertices), its report word's
+// copy to pinned memory, and the events around the kernel.  Nothing of the context changes: the table and the word are scratch.
+static int stage_on_device(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hipEvent_t e0, hipEvent_t e1) {
+    const float* from = ctx->d_verts;
+    if (S.xform) {
+        if (!ctx->d_rest) { // the first transform of the context: its rest positions are the vertices as they are now
+            CK(dalloc(&U.rest, 3 * ctx->nvert));
+            CK(hipMemcpyAsync(U.rest, ctx->d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
+        } else if (S.from == PT_FROM_REST) {
+            from = ctx->d_rest;
+        }
+    }
+    const size_t bytes = 16 + sizeof(StageSeg) * (size_t)S.n; // the report word (in a 16-byte line of its own), then the table
+    std::vector<uint8_t>& host = U.table;
+    host.assign(bytes, 0);
+    *reinterpret_cast<uint32_t*>(host.data()) = PT_STAGE_NONE;
+    StageSeg* segs = reinterpret_cast<StageSeg*>(host.data() + 16);
+    uint64_t waves = 0;
+    for (uint32_t k = 0; k < S.n; ++k) {
+        const uint32_t mesh = S.xform ? S.xform[k].mesh : S.dev[k].mesh;
+        const size_t first = 3 * (size_t)ctx->mesh_vbase[mesh];
+        StageSeg& g = segs[k];
+        g.dst = U.d_new + first;
+        g.first_wave = (uint32_t)waves;
+        g.order = k;
+        if (S.xform) {
+            g.src = from + first;
+            g.count = ctx->mesh_nv[mesh];
+            g.xform = 1;
+            memcpy(g.m, S.xform[k].m, sizeof(g.m));
+        } else {
+            g.src = S.dev[k].vertex;
+            g.count = 3 * (uint64_t)ctx->mesh_nv[mesh];
+            U.explicit_ranges.emplace_back(first, (size_t)g.count);
+        }
+        waves += (g.count + PT_STAGE_CHUNK - 1) / PT_STAGE_CHUNK;
+    }
+    if (waves > 0xfffffffcull) { ctx->err = std::string(S.fn) + ": too many vertices for one call"; return PT_ERR_UNSUPPORTED; }
+    if (!ctx->h_stage_bad) CK(hipHostMalloc((void**)&ctx->h_stage_bad, sizeof(uint32_t)));
+    if (ctx->stage_cap < bytes) {
+        uint8_t* grown = nullptr;
+        CK(dalloc(&grown, bytes));
+        dfree(ctx->d_stage);
+        ctx->d_stage = grown;
+        ctx->stage_cap = bytes;
+    }
+    *ctx->h_stage_bad = PT_STAGE_NONE;
+    CK(hipMemcpyAsync(ctx->d_stage, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream)); 
+    CK(hipEventRecord(e0, ctx->stream));
+    if (waves) {
+        hipLaunchKernelGGL(k_stage_vertices, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, ctx->stream, reinterpret_cast<const StageSeg*>(ctx->d_stage + 16), S.n,
+                           (uint32_t)waves, reinterpret_cast<uint32_t*>(ctx->d_stage));
+        CK(hipGetLastError());
+    }
+    CK(hipEventRecord(e1, ctx->stream));
+    CK(hipMemcpyAsync(ctx->h_stage_bad, ctx->d_stage, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return PT_OK;
+}
+
+// after a synchronisation of the stream: did k_stage_vertices write a non-finite coordinate?
+static int stage_verdict(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hipEvent_t e0, hipEvent_t e1) {
+    const uint32_t bad = *ctx->h_stage_bad;
+    if (bad != PT_STAGE_NONE) {
+        const uint32_t mesh = bad < S.n ? (S.xform ? S.xform[bad].mesh : S.dev[bad].mesh) : bad;
+        ctx->err = std::string(S.fn) + ": non-finite coordinate in mesh " + std::to_string(mesh) + (S.xform ? " after the transform" : "");
+        return PT_ERR_INVALID;
+    }
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    U.stage_ms = ms;
+    return PT_OK;
+}
+
+static int update_stage(pt_ctx* ctx, const UpdateSource& S, int mode, MeshUpdate& U) {
     { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames enqueued before the call render the old geometry
     CK(hipSetDevice(ctx->device));
     CK(dalloc(&U.d_new, 3 * ctx->nvert));
     CK(hipMemcpyAsync(U.d_new, ctx->d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
-    for (uint32_t k = 0; k < n; ++k)
-        CK(hipMemcpyAsync(U.d_new + 3 * (size_t)ctx->mesh_vbase[up[k].mesh], up[k].vertex, sizeof(float) * 3 * up[k].num_vertices, hipMemcpyHostToDevice, ctx->stream));
+    DevScope tmp;
+    hipEvent_t s0 = nullptr, s1 = nullptr;
+    if (S.host) {
+        for (uint32_t k = 0; k < S.n; ++k) {
+            const size_t first = 3 * (size_t)ctx->mesh_vbase[S.host[k].mesh], floats = 3 * (size_t)S.host[k].num_vertices;
+            CK(hipMemcpyAsync(U.d_new + first, S.host[k].vertex, sizeof(float) * floats, hipMemcpyHostToDevice, ctx->stream));
+            U.explicit_ranges.emplace_back(first, floats);
+        }
+    } else {
+        CK(tmp.event(&s0));
+        CK(tmp.event(&s1));
+        const int rc = stage_on_device(ctx, S, U, s0, s1);
+        if (rc != PT_OK) return rc;
+    }
     if (mode == PT_UPDATE_REFIT) {
         CK(pt_bvh_refit_alloc(&ctx->bvh));
         CK(hipStreamSynchronize(ctx->stream));
-        return PT_OK;
+        return S.host ? PT_OK : stage_verdict(ctx, S, U, s0, s1);
+    }
+    if (!S.host) { // the builder must never see a non-finite vertex: the verdict comes before the build, at the price of one wait
+        CK(hipStreamSynchronize(ctx->stream));
+        const int rc = stage_verdict(ctx, S, U, s0, s1);
+        if (rc != PT_OK) return rc;
     }
     // rebuild: pt_create's build and side arrays over the new vertices, into a tree of its own
-    DevScope tmp;
     hipEvent_t e0, e1;
     CK(tmp.event(&e0));
     CK(tmp.event(&e1));
@@ -2622,15 +2780,27 @@ static int update_stage(pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int m
     U.build_ms = ms;
     char msg[160];
     if (check_tree_depth(ctx, msg, sizeof(msg), &U.nb) != PT_OK) {
-        ctx->err = std::string("pt_update_meshes: ") + msg;
+        ctx->err = std::string(S.fn) + ": " + msg;
         return PT_ERR_UNSUPPORTED;
     }
     return PT_OK;
 }
 
+static int update_stage(pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, MeshUpdate& U) {
+    UpdateSource S{"pt_update_meshes"};
+    S.host = up;
+    S.n = n;
+    return update_stage(ctx, S, mode, U);
+}
+
 static int update_commit(pt_ctx* ctx, int mode, MeshUpdate& U, double* kernel_ms) {
     CK(hipSetDevice(ctx->device));
     double ms = U.build_ms;
+    if (ctx->d_rest && !U.explicit_ranges.empty()) { // positions given explicitly are rest positions from now on
+        for (const auto& r : U.explicit_ranges)
+            CK(hipMemcpyAsync(ctx->d_rest + r.first, U.d_new + r.first, sizeof(float) * r.second, hipMemcpyDeviceToDevice, ctx->stream));
+        if (mode != PT_UPDATE_REFIT) CK(hipStreamSynchronize(ctx->stream)); // (the refit below waits)
+    }
     if (mode == PT_UPDATE_REFIT) {
         DevScope tmp;
         hipEvent_t e0, e1;
@@ -2665,8 +2835,12 @@ static int update_commit(pt_ctx* ctx, int mode, MeshUpdate& U, double* kernel_ms
     dfree(ctx->d_verts);
     ctx->d_verts = U.d_new;
     U.d_new = nullptr;
+    if (U.rest) {
+        ctx->d_rest = U.rest;
+        U.rest = nullptr;
+    }
     ctx->sched = pt_ctx::Sched{}; // the tree's traversal cost changed: the chain/fused trial starts over
-    if (kernel_ms) *kernel_ms = ms;
+    if (kernel_ms) *kernel_ms = ms + U.stage_ms;
     return PT_OK;
 }
 
@@ -2680,6 +2854,51 @@ extern "C" int pt_update_meshes(pt_ctx* ctx, const pt_mesh_update* updates, uint
     if (rc == PT_OK) rc = update_commit(ctx, mode, U, kernel_ms);
     U.discard();
     return rc;
+}
+
+extern "C" int pt_update_meshes_device(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_update_meshes_device: null context");
+    std::string err;
+    int rc = update_validate(ctx, updates, n, mode, err, "pt_update_meshes_device", /*host_vertices=*/false);
+    if (rc == PT_OK) rc = device_pointers_validate(ctx, updates, n, err);
+    if (rc != PT_OK) return err.empty() ? rc : fail(ctx, rc, err.c_str());
+    UpdateSource S{"pt_update_meshes_device"};
+    S.dev = updates;
+    S.n = n;
+    MeshUpdate U;
+    rc = update_stage(ctx, S, mode, U);
+    if (rc == PT_OK) rc = update_commit(ctx, mode, U, kernel_ms);
+    U.discard();
+    return rc;
+}
+
+extern "C" int pt_transform_meshes(pt_ctx* ctx, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_transform_meshes: null context");
+    std::string err;
+    int rc = transform_validate(ctx, t, n, source, mode, err, "pt_transform_meshes");
+    if (rc != PT_OK) return fail(ctx, rc, err.c_str());
+    UpdateSource S{"pt_transform_meshes"};
+    S.xform = t;
+    S.from = source;
+    S.n = n;
+    MeshUpdate U;
+    rc = update_stage(ctx, S, mode, U);
+    if (rc == PT_OK) rc = update_commit(ctx, mode, U, kernel_ms);
+    U.discard();
+    return rc;
+}
+
+extern "C" int pt_download_vertices(pt_ctx* ctx, uint32_t mesh, int rest, float* host, size_t bytes) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_download_vertices: null context");
+    if (!host) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: null buffer");
+    if (mesh >= ctx->nmesh) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: mesh index out of range");
+    if (rest != 0 && rest != 1) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: rest must be 0 or 1");
+    if (bytes != sizeof(float) * 3 * (size_t)ctx->mesh_nv[mesh]) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: bytes must equal num_vertices * 12");
+    if (bytes == 0) return PT_OK;
+    CK(hipSetDevice(ctx->device));
+    const float* from = rest && ctx->d_rest ? ctx->d_rest : ctx->d_verts; // before the first transform the vertices are their own rest positions
+    CK(hipMemcpy(host, from + 3 * (size_t)ctx->mesh_vbase[mesh], bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material, int bsdf_mode, const float* in, uint32_t n, float* out) {
@@ -3403,6 +3622,29 @@ extern "C" int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates
         slow = std::max(slow, ms);
     }
     discard();
+    if (rc == PT_OK && kernel_ms) *kernel_ms = slow;
+    return rc;
+}
+
+extern "C" int pt_multi_transform_meshes(pt_multi* m, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms) {
+    if (!m) { (void)fail(nullptr, PT_ERR_INVALID, "pt_multi_transform_meshes: null pt_multi"); return mfail(nullptr, PT_ERR_INVALID, "pt_multi_transform_meshes: null pt_multi"); }
+    const int world = (int)m->ctx.size();
+    std::string err;
+    int rc = transform_validate(m->ctx[0], t, n, source, mode, err, "pt_multi_transform_meshes");
+    if (rc != PT_OK) return mfail(m, rc, err);
+    UpdateSource S{"pt_multi_transform_meshes"};
+    S.xform = t;
+    S.from = source;
+    S.n = n;
+    std::vector<MeshUpdate> U(world);
+    for (int r = 0; r < world && rc == PT_OK; ++r) rc = mctx(m, r, update_stage(m->ctx[r], S, mode, U[r]), "pt_multi_transform_meshes");
+    double slow = 0;
+    for (int r = 0; r < world && rc == PT_OK; ++r) {
+        double ms = 0;
+        rc = mctx(m, r, update_commit(m->ctx[r], mode, U[r], &ms), "pt_multi_transform_meshes");
+        slow = std::max(slow, ms);
+    }
+    for (auto& u : U) u.discard();
     if (rc == PT_OK && kernel_ms) *kernel_ms = slow;
     return rc;
 }

@@ -98,8 +98,54 @@ def _mesh_updates(vertices: dict):
     return ups, len(vertices), keep
 
 
+def _pairs(d):
+    """{mesh: value} or [(mesh, value), ...] (the list form can name a mesh twice: the library refuses that)."""
+    return list(d.items()) if hasattr(d, "items") else list(d)
+
+
+def _device_updates(vertices, device: int):
+    """pt_mesh_update[] over DEVICE memory: a value is a CUDA float32 contiguous (nv, 3) torch tensor on `device`, or (pointer, nv)."""
+    pairs = _pairs(vertices)
+    ups = (_lib.MeshUpdate * max(1, len(pairs)))()
+    keep = []
+    for k, (mesh, v) in enumerate(pairs):
+        if isinstance(v, tuple):
+            ptr, nv = int(v[0]), int(v[1])
+        else:
+            import torch
+
+            if not isinstance(v, torch.Tensor):
+                raise TypeError(f"updateMeshesDevice: mesh {mesh}: a torch tensor or (device pointer, num_vertices) is expected (host arrays: updateMeshes)")
+            if not v.is_cuda or (v.device.index or 0) != device:
+                raise ValueError(f"updateMeshesDevice: mesh {mesh}: the tensor is on {v.device}, the context on GPU {device}")
+            if v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3 or not v.is_contiguous():
+                raise ValueError(f"updateMeshesDevice: mesh {mesh}: a contiguous float32 (num_vertices, 3) tensor is expected")
+            torch.cuda.current_stream(v.device).synchronize()  # the library reads on its own stream: what torch enqueued must be complete
+            keep.append(v)
+            ptr, nv = v.data_ptr(), v.shape[0]
+        ups[k].mesh = int(mesh)
+        ups[k].vertex = C.cast(C.c_void_p(ptr), C.POINTER(C.c_float))
+        ups[k].num_vertices = nv
+    return ups, len(pairs), keep
+
+
+def _mesh_transforms(transforms):
+    """pt_mesh_transform[] for {mesh_index: 3x4 or 4x4 array} (the last row of a 4x4 is dropped)."""
+    pairs = _pairs(transforms)
+    arr = (_lib.MeshTransform * max(1, len(pairs)))()
+    for k, (mesh, m) in enumerate(pairs):
+        m = np.asarray(m, np.float32)
+        if m.shape not in ((3, 4), (4, 4)):
+            raise ValueError(f"transformMeshes: mesh {mesh}: a 3x4 or 4x4 matrix is expected, got {m.shape}")
+        arr[k].mesh = int(mesh)
+        arr[k].m[:] = [float(x) for x in m[:3].reshape(-1)]
+    return arr, len(pairs)
+
+
 class SampleRenderer:
     def __init__(self, model: Model, device: int = 0):
+        self._device = int(device)
+        self._nv = [len(m.vertex) for m in model.meshes]
         self._L = L = _lib.load_library()
         self._ctx = C.c_void_p()
         self.launchParams = LaunchParams()
@@ -393,6 +439,35 @@ class SampleRenderer:
         del keep
         return ms.value
 
+    def updateMeshesDevice(self, vertices, rebuild: bool = False) -> float:
+        """updateMeshes with the vertices in GPU memory (pt_update_meshes_device): {mesh_index: tensor} with CUDA float32 contiguous
+        (num_vertices, 3) torch tensors on the context's device, or {mesh_index: (device pointer, num_vertices)}.  A tensor's current
+        torch stream is synchronised first; a raw pointer's producer must be complete.  Non-finite coordinates are found on the GPU."""
+        ups, n, keep = _device_updates(vertices, getattr(self, "_device", 0))
+        ms = C.c_double()
+        self._ck(self._L.pt_update_meshes_device(self._ctx, ups if n else None, n, _lib.PT_UPDATE_REBUILD if rebuild else _lib.PT_UPDATE_REFIT, C.byref(ms)),
+                 "pt_update_meshes_device")
+        del keep
+        return ms.value
+
+    def transformMeshes(self, transforms, from_current: bool = False, rebuild: bool = False) -> float:
+        """A 3x4 (or 4x4) matrix per mesh ({mesh_index: array}, pt_transform_meshes): p' = M[:, :3] p + M[:, 3] in float32, applied to the
+        mesh's rest positions — the ones last given explicitly — or with from_current=True to what is there now.  Returns kernel ms."""
+        arr, n = _mesh_transforms(transforms)
+        ms = C.c_double()
+        self._ck(self._L.pt_transform_meshes(self._ctx, arr if n else None, n, _lib.PT_FROM_CURRENT if from_current else _lib.PT_FROM_REST,
+                                             _lib.PT_UPDATE_REBUILD if rebuild else _lib.PT_UPDATE_REFIT, C.byref(ms)), "pt_transform_meshes")
+        return ms.value
+
+    def downloadVertices(self, mesh: int, rest: bool = False) -> np.ndarray:
+        """The current (or rest) positions of one mesh as the context holds them: float32 (num_vertices, 3) (pt_download_vertices)."""
+        if not 0 <= int(mesh) < len(self._nv):
+            raise IndexError(f"downloadVertices: mesh {mesh} out of range")
+        nv = self._nv[int(mesh)]
+        out = np.empty((nv, 3), np.float32)
+        self._ck(self._L.pt_download_vertices(self._ctx, int(mesh), int(bool(rest)), out.ctypes.data, out.nbytes), "pt_download_vertices")
+        return out
+
     def trace(self, rays: np.ndarray, any_hit=False, iters=1):
         """optixTrace as a batch query: rays (n,8) = o.xyz,tmin,d.xyz,tmax → (t, prim) or occluded flags; + kernel ms."""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
@@ -420,8 +495,8 @@ class _RankView(SampleRenderer):
     """A rank's context of a MultiRenderer seen through the single-context facade (download, stats, deviceBuffer ...).
     It does not own the context."""
 
-    def __init__(self, L, ctx, launchParams):
-        self._L, self._ctx, self.launchParams = L, ctx, launchParams
+    def __init__(self, L, ctx, launchParams, nv=(), device=0):
+        self._L, self._ctx, self.launchParams, self._nv, self._device = L, ctx, launchParams, list(nv), device
 
     def close(self):
         self._ctx = C.c_void_p()
@@ -441,6 +516,7 @@ class MultiRenderer:
         self._m = C.c_void_p()
         self.launchParams = LaunchParams()
         self.devices = [int(d) for d in devices]
+        self._nv = [len(m.vertex) for m in model.meshes]
         sd, keep = _scene_desc(model)
         dv = (C.c_int * len(self.devices))(*self.devices)
         rc = L.pt_create_multi(C.byref(sd), dv, len(self.devices), C.byref(self._m))
@@ -473,7 +549,7 @@ class MultiRenderer:
         ctx = self._L.pt_multi_ctx(self._m, int(r))
         if not ctx:
             raise IndexError(r)
-        return _RankView(self._L, C.c_void_p(ctx), self.launchParams)
+        return _RankView(self._L, C.c_void_p(ctx), self.launchParams, self._nv, self.devices[int(r)])
 
     def setOptions(self, max_depth=8, bsdf_mode=PT_BSDF_DISNEY, max_paths=0, bvh_kind=0, trace_kernel=0, streams=0, split_shadow=0, kernel_timing=0, frames_in_flight=0):
         o = Options(max_depth, bsdf_mode, max_paths, kernel_timing, bvh_kind, trace_kernel, streams, split_shadow, frames_in_flight)
@@ -503,6 +579,14 @@ class MultiRenderer:
         ms = C.c_double()
         self._ck(self._L.pt_multi_update_meshes(self._m, ups if n else None, n, _lib.PT_UPDATE_REBUILD if rebuild else _lib.PT_UPDATE_REFIT, C.byref(ms)), "pt_multi_update_meshes")
         del keep
+        return ms.value
+
+    def transformMeshes(self, transforms, from_current: bool = False, rebuild: bool = False) -> float:
+        """SampleRenderer.transformMeshes on every rank (pt_multi_transform_meshes); returns the slowest rank's kernel ms."""
+        arr, n = _mesh_transforms(transforms)
+        ms = C.c_double()
+        self._ck(self._L.pt_multi_transform_meshes(self._m, arr if n else None, n, _lib.PT_FROM_CURRENT if from_current else _lib.PT_FROM_REST,
+                                                   _lib.PT_UPDATE_REBUILD if rebuild else _lib.PT_UPDATE_REFIT, C.byref(ms)), "pt_multi_transform_meshes")
         return ms.value
 
     def render(self, out: np.ndarray | None = None):
