@@ -18,7 +18,7 @@
  * hipStreamNonBlocking: they do NOT synchronise with the null stream or with any stream of the
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
- * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer — read and write them on
+ * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -478,6 +478,66 @@ int pt_multi_get_stats(const pt_multi* m, pt_multi_stats* out);
  * iters>1 repeats the kernel for timing; kernel_ms (may be NULL) receives the mean kernel time. */
 int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit, float* t_out, int32_t* prim_out, int iters,
              double* kernel_ms);
+
+/* Ray queries from and to GPU memory (what optixTrace is to an application's own buffers): pt_trace with the rays and the results in DEVICE
+ * memory, hit attributes, no per-call allocation and, with PT_QUERY_ASYNC, no host wait.  A simulation, picking, lidar, baking or collision
+ * step that keeps its rays in a tensor asks its question without a host copy; together with pt_update_meshes_device / pt_transform_meshes a
+ * whole interactive loop stays on the GPU.
+ * Pointers and streams:
+ *   - dev_rays (n x 8 floats: o.xyz, tmin, d.xyz, tmax) and dev_out (PT_QUERY_CLOSEST: n x pt_hit; PT_QUERY_ANY: n x int32) live on the
+ *     context's device and are read and written on pt_stream(ctx), under the STREAM CONTRACT: rays produced on another stream must be
+ *     complete, or ordered with pt_wait_event, before the call;
+ *   - before any device work each pointer is checked with hipPointerGetAttributes, exactly as pt_update_meshes_device checks its arrays: a
+ *     null pointer, a pointer HIP does not know, host memory (pinned or managed included), memory of another device, a pointer that is not
+ *     4-byte aligned, an array that does not fit into what is left of its allocation, input and output ranges that overlap, unknown flag
+ *     bits or more than 2^31 rays return PT_ERR_INVALID, and nothing is enqueued.  No wider alignment than 4 bytes is assumed (a tensor
+ *     slice is routinely offset by one float); arrays that happen to be 16-byte aligned are moved with 16-byte loads and stores;
+ *   - n == 0 returns PT_OK and launches nothing.
+ * Validity of a ray, decided on the device by the staging kernel with tests on the exponent bits:
+ *   - a ray is valid when its eight words are finite and s = (dx*dx + dy*dy) + dz*dz and 1.0f / s are both finite and non-zero (float32, one
+ *     rounding per operation: what the traversal divides by);
+ *   - an invalid ray never enters the traversal with its own values: it is staged as the neutral ray o = (0,0,0), tmin = 1, d = (0,0,1),
+ *     tmax = -1 and remembered in a bit mask of its own (one bit per ray), so a caller's own ray (0,0,0,1, 0,0,1,-1) is still an ordinary miss;
+ *   - it is reported as prim = -2 (closest hit) or -2 (any hit) and counted in invalid_rays; the call still returns PT_OK;
+ *   - a valid ray with tmax <= tmin is an ordinary miss.
+ * Results:
+ *   - t and prim are pt_trace's, bit for bit (and so the CPU checker's); mesh is the leaf triangle's mesh word; ng is the geometric normal
+ *     k_shade uses, normalize(cross(v1 - v0, v2 - v0)), not flipped towards the ray;
+ *   - u, v are optixGetTriangleBarycentrics — the weights of vertex 1 and vertex 2 — from the triangle's vertices and the ray as given, by the
+ *     expression the shade kernel uses for textured hits; float32, one rounding per operation, no fused multiply-add, dot = (x + y) + z:
+ *       A = v0 - o, B = v1 - o, C = v2 - o;  Uw = dot(d, cross(C, B)), Vw = dot(d, cross(A, C)), Ww = dot(d, cross(B, A));
+ *       det = (Uw + Vw) + Ww;  u = Vw / det;  v = Ww / det
+ *     (float32 NumPy evaluating this reproduces them bit for bit);
+ *   - any-hit output: 1 occluded, 0 not occluded, -2 invalid.
+ * Ordering and completion:
+ *   - the call first waits for the frames in flight, like pt_trace (queries already queued keep running);
+ *   - without PT_QUERY_ASYNC it is complete when it returns and *stats describes what pt_query_wait would: the queries since the last wait
+ *     (this one alone unless asynchronous ones were pending);
+ *   - with PT_QUERY_ASYNC it returns after enqueueing on pt_stream(ctx) — no allocation after the first query of that size, no host copy, no
+ *     synchronisation — and does not touch stats.  Results are complete after pt_query_wait or pt_sync; a consumer on another stream may
+ *     instead wait for an event recorded on pt_stream(ctx).  Several asynchronous queries may be queued: they run in stream order;
+ *   - pt_query_wait waits for the queued queries and reports the sums over the queries since the last pt_query_wait (or synchronous query).
+ *     The traversal's stack-overflow bit is read there and gives PT_ERR_UNSUPPORTED, as in pt_trace;
+ *   - every entry point that waits for the frames in flight (pt_update_meshes*, pt_resize, pt_get_stats, pt_destroy, ...) completes the queued
+ *     queries first; what they counted stays for the next pt_query_wait.  A query enqueued after a mesh update sees the new geometry.
+ * State: the staged rays, the hit records, the marks and a small counter block live in the context, are allocated by the first query, grow
+ * when a query has more rays than any before it (never shrink) and are freed by pt_destroy; state_bytes reports their size.  If growing
+ * fails the call returns PT_ERR_HIP and the context is unchanged. */
+enum pt_query_flags { PT_QUERY_CLOSEST = 0, PT_QUERY_ANY = 1, PT_QUERY_ASYNC = 2 /* or-able with either */ };
+typedef struct pt_hit {       /* 32 bytes, one per ray, closest-hit queries */
+    float   t;                /* hit distance; the ray's own tmax on a miss; 0 for an invalid ray */
+    float   u, v;             /* barycentric weights of vertex 1 and vertex 2; 0 when there is no hit */
+    int32_t prim;             /* global triangle index in mesh order (pt_trace's); -1 miss; -2 invalid ray */
+    int32_t mesh;             /* index into pt_scene_desc.meshes (= material record); -1 when there is no hit */
+    float   ng[3];            /* geometric normal, not flipped towards the ray; 0 when there is no hit */
+} pt_hit;
+typedef struct pt_query_stats {
+    uint64_t rays, hits, invalid_rays;      /* hits: closest hits found / rays found occluded */
+    double stage_ms, trace_ms, attrib_ms;   /* device time of the three kernels (hipEvents) */
+    uint64_t state_bytes;                   /* device memory the query state currently holds */
+} pt_query_stats;
+int pt_trace_device(pt_ctx* ctx, const float* dev_rays, uint32_t n, uint32_t flags /* pt_query_flags */, void* dev_out, pt_query_stats* stats /* may be NULL */);
+int pt_query_wait(pt_ctx* ctx, pt_query_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

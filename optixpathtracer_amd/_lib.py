@@ -25,6 +25,7 @@ EXPORTS = [
     "pt_update_meshes", "pt_multi_update_meshes",
     "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
+    "pt_trace_device", "pt_query_wait",
 ]
 
 PT_UPDATE_REFIT, PT_UPDATE_REBUILD = 0, 1  # pt_update_mode
@@ -32,6 +33,23 @@ PT_FROM_REST, PT_FROM_CURRENT = 0, 1  # pt_transform_source
 
 
 PT_ADAPT_MOMENTS, PT_ADAPT_ACTIVE = 0, 1  # pt_adaptive_array
+PT_QUERY_CLOSEST, PT_QUERY_ANY, PT_QUERY_ASYNC = 0, 1, 2  # pt_query_flags
+
+
+class Hit(C.Structure):  # pt_hit
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_int32), ("mesh", C.c_int32), ("ng", C.c_float * 3)]
+
+
+# pt_hit as a NumPy record: the same 32 bytes
+HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("mesh", "<i4"), ("ng", "<f4", (3,))])
+
+
+class QueryStats(C.Structure):  # pt_query_stats
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("invalid_rays", C.c_uint64), ("stage_ms", C.c_double), ("trace_ms", C.c_double),
+                ("attrib_ms", C.c_double), ("state_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
@@ -134,6 +152,7 @@ class MultiStats(C.Structure):  # pt_multi_stats
 
 
 assert C.sizeof(Material) == 104
+assert C.sizeof(Hit) == 32 == HIT_DTYPE.itemsize
 
 _lib = None
 
@@ -234,6 +253,8 @@ def load_library() -> C.CDLL:
     L.pt_render_adaptive.argtypes = [vp, u32, u32, vp, C.POINTER(AdaptiveStats)]
     L.pt_adaptive_end.argtypes = [vp]
     L.pt_download_adaptive.argtypes = [vp, i, vp, C.c_size_t]
+    L.pt_trace_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(QueryStats)]
+    L.pt_query_wait.argtypes = [vp, C.POINTER(QueryStats)]
     L.pt_version.restype = C.c_char_p
     f3p = C.POINTER(f * 3)
     L.pt_create_multi.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), i, C.POINTER(vp)]

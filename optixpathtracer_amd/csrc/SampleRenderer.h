@@ -235,6 +235,19 @@ class SampleRenderer {
                                rebuild ? PT_UPDATE_REBUILD : PT_UPDATE_REFIT, &ms));
         return ms;
     }
+    // optixTrace from the application's own DEVICE buffers (pt_trace_device): d_rays = n x 8 floats (o.xyz, tmin, d.xyz, tmax), d_out = n x
+    // pt_hit (closest hit) or n x int32 (any_hit), both on this context's device, read and written on stream().  wait = false enqueues and
+    // returns: the results are complete after queryWait(), or for a consumer that waits on an event recorded on stream().
+    pt_query_stats traceDevice(const float* d_rays, uint32_t n, void* d_out, bool any_hit = false, bool wait = true) {
+        pt_query_stats s{};
+        ck(pt_trace_device(ctx, d_rays, n, (any_hit ? PT_QUERY_ANY : PT_QUERY_CLOSEST) | (wait ? 0u : (uint32_t)PT_QUERY_ASYNC), d_out, wait ? &s : nullptr));
+        return s;
+    }
+    pt_query_stats queryWait() { // waits for the queued queries; the sums over the queries since the last wait
+        pt_query_stats s{};
+        ck(pt_query_wait(ctx, &s));
+        return s;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;

@@ -201,6 +201,21 @@ struct pt_ctx {
     unsigned long long* d_totals = nullptr;
     unsigned long long* h_totals = nullptr; // pinned host copy, same shape: filled by an asynchronous copy behind each frame (a blocking hipMemcpy would wait for the NEXT frame too)
     uint32_t* ovf = nullptr; // spill stacks for pt_trace queries
+    // pt_trace_device: the query state.  Allocated by the first query, grown when a query has more rays than any before it, freed by
+    // pt_destroy: a query of the same or a smaller size allocates nothing (pt_query_stats.state_bytes).
+    struct Query {
+        float4 *rayO = nullptr, *rayD = nullptr; // the rays as staged by k_stage_rays: what the traversal reads
+        float2* hit = nullptr;                   // its (t, leaf) records
+        unsigned long long* mark = nullptr;      // [ceil(cap / 64)] one bit per ray: invalid, staged as the neutral ray
+        uint8_t* block = nullptr;                // QueryCounters, then 64 bytes each for the identity queue's count word and the traversal's chunk counter
+        QueryCounters* h_counters = nullptr;     // pinned: the counters of the queries since the last wait
+        uint32_t cap = 0;                        // rays the arrays hold
+        uint64_t bytes = 0;                      // device memory of the state
+        std::vector<hipEvent_t> events;          // four per queued query: before the staging, between the three kernels, behind the last
+        uint32_t pending = 0;                    // queries enqueued and not waited for
+        uint64_t pending_rays = 0;
+        pt_query_stats acc{};                    // completed queries nobody has asked about yet (pt_query_wait reads and clears it)
+    } q;
     unsigned long long* dbg = nullptr; // PT_DEBUG_COUNTS: traversal step counters of the last frame
     int trace_grid = 0;
     bool cam_packets = true; // camera rays as packets (PT_CAM_PACKETS=0 turns it off)
@@ -666,6 +681,9 @@ extern "C" int pt_destroy(pt_ctx* ctx) {
     if (ctx->h_totals) hipHostFree(ctx->h_totals);
     dfree(ctx->ovf);
     dfree(ctx->dbg);
+    dfree(ctx->q.rayO); dfree(ctx->q.rayD); dfree(ctx->q.hit); dfree(ctx->q.mark); dfree(ctx->q.block);
+    if (ctx->q.h_counters) hipHostFree(ctx->q.h_counters);
+    for (hipEvent_t e : ctx->q.events) hipEventDestroy(e);
     for (auto& pool : ctx->ev_pools)
         for (hipEvent_t e : pool) hipEventDestroy(e);
     for (hipEvent_t e : {ctx->ev_packed[0], ctx->ev_packed[1], ctx->ev_displayed})
@@ -1807,7 +1825,7 @@ static int oldest_active(pt_ctx* ctx) {
 }
 
 // waits for every frame in flight, oldest first
-static int drain(pt_ctx* ctx) {
+static int drain_frames(pt_ctx* ctx) {
     int rc = PT_OK;
     for (int o; (o = oldest_active(ctx)) >= 0;) {
         const int r = render_finish(ctx, o);
@@ -1820,6 +1838,13 @@ static int drain(pt_ctx* ctx) {
         else (void)hipGetLastError(); // "not ready" is an answer, not an error to be found by the next hipGetLastError
     }
     return rc;
+}
+static int query_complete(pt_ctx* ctx);
+// ... and for the queued queries of pt_trace_device: every entry point that reads or changes device state goes through here
+static int drain(pt_ctx* ctx) {
+    int rc = drain_frames(ctx);
+    const int rq = query_complete(ctx);
+    return rc != PT_OK ? rc : rq;
 }
 
 extern "C" int pt_sync(pt_ctx* ctx) { return ctx ? drain(ctx) : PT_ERR_INVALID; }
@@ -2525,6 +2550,171 @@ extern "C" int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit,
         }
     }
     return PT_OK;
+}
+
+// ------------------------------------------------------------------ pt_trace_device: queries from and to the caller's device arrays
+// One array of the call: memory of the context's device that HIP knows, 4-byte aligned, inside its allocation (pt_update_meshes_device's checks).
+static int query_pointer_validate(pt_ctx* ctx, const void* p, size_t bytes, const char* who, std::string& err) {
+    const std::string name = std::string("pt_trace_device: ") + who;
+    if (!p) { err = name + " is null"; return PT_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(p) & 3u) { err = name + " is not 4-byte aligned"; return PT_ERR_INVALID; }
+    hipPointerAttribute_t at;
+    const hipError_t pe = hipPointerGetAttributes(&at, p);
+    if (pe != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError(); // an unknown pointer leaves hipErrorInvalidValue behind
+        err = name + " is not device memory (for host arrays use pt_trace)";
+        return PT_ERR_INVALID;
+    }
+    if (at.device != ctx->device) { err = name + " is memory of device " + std::to_string(at.device) + ", the context is on device " + std::to_string(ctx->device); return PT_ERR_INVALID; }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return PT_OK; }
+    const size_t off = (size_t)((const char*)p - (const char*)base);
+    if (off > size || bytes > size - off) { err = name + " has fewer than " + std::to_string(bytes) + " bytes left in its allocation"; return PT_ERR_INVALID; }
+    return PT_OK;
+}
+
+// Waits for the queued queries and adds what they counted to q.acc; reports the traversal's fault bit.  The host's only wait of a query.
+static int query_complete(pt_ctx* ctx) {
+    pt_ctx::Query& q = ctx->q;
+    if (q.pending == 0) return PT_OK;
+    const uint32_t pending = q.pending;
+    const uint64_t rays = q.pending_rays;
+    q.pending = 0; // whatever happens below, these queries are not waited for twice
+    q.pending_rays = 0;
+    CK(hipSetDevice(ctx->device));
+    CK(hipMemcpyAsync(q.h_counters, q.block, sizeof(QueryCounters), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    CK(hipGetLastError());
+    for (uint32_t k = 0; k < pending; ++k) {
+        float a = 0, b = 0, c = 0;
+        const hipEvent_t* e = &q.events[4 * (size_t)k];
+        CK(hipEventElapsedTime(&a, e[0], e[1]));
+        CK(hipEventElapsedTime(&b, e[1], e[2]));
+        CK(hipEventElapsedTime(&c, e[2], e[3]));
+        q.acc.stage_ms += a;
+        q.acc.trace_ms += b;
+        q.acc.attrib_ms += c;
+    }
+    q.acc.rays += rays;
+    for (const QuerySlot& sl : q.h_counters->slot) {
+        q.acc.hits += sl.hits;
+        q.acc.invalid_rays += sl.invalid;
+    }
+    if (q.h_counters->fault & 1u) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_trace_device: traversal stack overflow: the acceleration structure is deeper than the traversal stack");
+    return PT_OK;
+}
+
+static const size_t PT_QUERY_BLOCK = sizeof(QueryCounters) + 128; // the counters, the count word, the chunk counter
+// room for n rays and for one more queued query's events; on failure nothing of the context has changed
+static int query_reserve(pt_ctx* ctx, uint32_t n) {
+    pt_ctx::Query& q = ctx->q;
+    if (!q.block) {
+        uint8_t* block = nullptr;
+        QueryCounters* h = nullptr;
+        CK(dalloc(&block, PT_QUERY_BLOCK));
+        if (hipHostMalloc((void**)&h, sizeof(QueryCounters)) != hipSuccess) {
+            (void)hipGetLastError();
+            dfree(block);
+            return fail(ctx, PT_ERR_HIP, "pt_trace_device: out of pinned host memory for the counters");
+        }
+        q.block = block;
+        q.h_counters = h;
+        q.bytes += PT_QUERY_BLOCK;
+    }
+    if (n > q.cap) {
+        // queued queries still use the old arrays: they finish first (only a query larger than every one before it comes here)
+        { int rc_ = query_complete(ctx); if (rc_ != PT_OK) return rc_; }
+        float4 *o = nullptr, *d = nullptr;
+        float2* h = nullptr;
+        unsigned long long* m = nullptr;
+        const size_t words = ((size_t)n + 63) / 64;
+        if (dalloc(&o, n) != hipSuccess || dalloc(&d, n) != hipSuccess || dalloc(&h, n) != hipSuccess || dalloc(&m, words) != hipSuccess) {
+            (void)hipGetLastError();
+            dfree(o); dfree(d); dfree(h); dfree(m);
+            return fail(ctx, PT_ERR_HIP, "pt_trace_device: out of device memory for the query state");
+        }
+        dfree(q.rayO); dfree(q.rayD); dfree(q.hit); dfree(q.mark);
+        q.rayO = o; q.rayD = d; q.hit = h; q.mark = m;
+        q.cap = n;
+        q.bytes = PT_QUERY_BLOCK + (size_t)n * (2 * sizeof(float4) + sizeof(float2)) + words * sizeof(unsigned long long);
+    }
+    while (q.events.size() < 4 * ((size_t)q.pending + 1)) {
+        hipEvent_t e;
+        CK(hipEventCreate(&e));
+        q.events.push_back(e);
+    }
+    return PT_OK;
+}
+
+static void query_report(pt_ctx* ctx, pt_query_stats* stats) {
+    if (stats) {
+        *stats = ctx->q.acc;
+        stats->state_bytes = ctx->q.bytes;
+    }
+    ctx->q.acc = pt_query_stats{};
+}
+
+extern "C" int pt_query_wait(pt_ctx* ctx, pt_query_stats* stats) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_query_wait: null context");
+    const int rc = query_complete(ctx);
+    query_report(ctx, stats);
+    return rc;
+}
+
+extern "C" int pt_trace_device(pt_ctx* ctx, const float* dev_rays, uint32_t n, uint32_t flags, void* dev_out, pt_query_stats* stats) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_trace_device: null context");
+    if (flags & ~(uint32_t)(PT_QUERY_ANY | PT_QUERY_ASYNC)) return fail(ctx, PT_ERR_INVALID, "pt_trace_device: unknown flag bits");
+    const bool any_hit = (flags & PT_QUERY_ANY) != 0, async = (flags & PT_QUERY_ASYNC) != 0;
+    if (n > 0x80000000u) return fail(ctx, PT_ERR_INVALID, "pt_trace_device: more than 2^31 rays in one call");
+    if (n != 0) {
+        CK(hipSetDevice(ctx->device));
+        const size_t in_bytes = (size_t)n * 32, out_bytes = (size_t)n * (any_hit ? sizeof(int32_t) : sizeof(pt_hit));
+        std::string err;
+        int rc = query_pointer_validate(ctx, dev_rays, in_bytes, "dev_rays", err);
+        if (rc == PT_OK) rc = query_pointer_validate(ctx, dev_out, out_bytes, "dev_out", err);
+        if (rc == PT_OK) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(dev_rays), b = reinterpret_cast<uintptr_t>(dev_out);
+            if (a < b + out_bytes && b < a + in_bytes) { err = "pt_trace_device: dev_rays and dev_out overlap"; rc = PT_ERR_INVALID; }
+        }
+        if (rc != PT_OK) return fail(ctx, rc, err.c_str());
+    }
+    { int rc_ = drain_frames(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight finish first, like pt_trace; queued queries keep running
+    if (n != 0) {
+        { int rc_ = query_reserve(ctx, n); if (rc_ != PT_OK) return rc_; }
+        pt_ctx::Query& q = ctx->q;
+        QueryCounters* counters = reinterpret_cast<QueryCounters*>(q.block);
+        uint32_t* count = reinterpret_cast<uint32_t*>(q.block + sizeof(QueryCounters));
+        uint32_t* work = reinterpret_cast<uint32_t*>(q.block + sizeof(QueryCounters) + 64);
+        const hipEvent_t* e = &q.events[4 * (size_t)q.pending];
+        if (q.pending == 0) CK(hipMemsetAsync(counters, 0, sizeof(QueryCounters), ctx->stream)); // the counters sum over the queries up to the next wait
+        // The staged rays, the hit records, the marks, the count word and the chunk counter are reused by every query.  That is safe with
+        // several queries queued because all of a query's kernels run on pt_stream(ctx), in order: query k+1's staging kernel starts after
+        // query k's attribute kernel has read the last of them.
+        const unsigned sgrid = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 2048); // grid-stride above 2048 workgroups
+        CK(hipEventRecord(e[0], ctx->stream));
+        hipLaunchKernelGGL(k_stage_rays, dim3(sgrid), dim3(256), 0, ctx->stream, dev_rays, n, (int)((reinterpret_cast<uintptr_t>(dev_rays) & 15u) == 0), q.rayO, q.rayD,
+                           q.mark, count, work, counters);
+        CK(hipEventRecord(e[1], ctx->stream));
+        PathState st{};
+        st.rayO = q.rayO;
+        st.rayD = q.rayD;
+        st.hit = q.hit;
+        Trace8Args ta{st, bvh_dev(ctx), QView{nullptr, count, 0}, QView{}, work, ctx->ovf, 0, nullptr, 0, ctx->lds_skip, ctx->ovf_depth, &counters->fault, ctx->bvh.num_nodes8};
+        if (any_hit) hipLaunchKernelGGL((k_trace8<TR_ANY_QUERY>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
+        else hipLaunchKernelGGL((k_trace8<TR_CLOSEST>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
+        CK(hipEventRecord(e[2], ctx->stream));
+        hipLaunchKernelGGL(k_hit_attributes, dim3(sgrid), dim3(256), 0, ctx->stream, q.hit, q.rayO, q.rayD, q.mark, ctx->bvh.tris8, ctx->d_tri_nrm, n, (int)any_hit,
+                           (int)((reinterpret_cast<uintptr_t>(dev_out) & 15u) == 0), dev_out, counters);
+        CK(hipEventRecord(e[3], ctx->stream));
+        CK(hipGetLastError());
+        ++q.pending;
+        q.pending_rays += n;
+    }
+    if (async) return PT_OK;
+    const int rc = query_complete(ctx);
+    query_report(ctx, stats);
+    return rc;
 }
 
 extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes, uint32_t* num_nodes, uint32_t* num_tris) {

@@ -1112,6 +1112,135 @@ __global__ void k_hits_to_prims(float2* __restrict__ hit, const LeafTri* __restr
     if (leaf >= 0) hit[i].y = tris[leaf].t2.y;
 }
 
+// ------------------------------------------------------------------ pt_trace_device: ray queries from and to the caller's device arrays
+// The two kernels around the traversal launch.  Both walk the rays wave by wave — wave w of the grid takes rays [64 w, 64 w + 64), then the
+// same 64 further on by the grid's lanes — so that a wave's ballot describes 64 consecutive rays: bit l of mark[i >> 6] says that ray
+// (i & ~63) + l was invalid.  That word, not the staged values, is how k_hit_attributes recognises an invalid ray: a caller's own ray
+// (0,0,0,1, 0,0,1,-1) has the neutral ray's bits and a clear mark, and is reported as the miss it is.
+// What the two kernels count, one atomic per wave.  Thousands of atomics on ONE address serialise in the L2 (about 10 ns each: with a single
+// counter k_hit_attributes took 0.11 ms for 2 M rays, 0.09 of them this queue), so wave w adds into slot w % 64, the slots 64 bytes apart,
+// and the host sums the slots at the wait.  Cleared by the first query after a wait.
+#define PT_QUERY_SLOTS 64
+struct QuerySlot {
+    unsigned long long invalid, hits;
+    unsigned long long pad_[6];
+};
+struct QueryCounters {
+    QuerySlot slot[PT_QUERY_SLOTS];
+    uint32_t fault; // the traversal's stack-overflow bit (Trace8Args::fault)
+    uint32_t pad_[15];
+};
+static_assert(sizeof(QuerySlot) == 64 && sizeof(QueryCounters) == 64 * PT_QUERY_SLOTS + 64, "QueryCounters is copied as bytes");
+PT_DEV QuerySlot* query_slot(QueryCounters* c) { return &c->slot[(blockIdx.x * 4u + (threadIdx.x >> 6)) & (PT_QUERY_SLOTS - 1u)]; }
+
+PT_DEV bool query_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; } // exponent bits: no compiler mode can fold it away
+PT_DEV bool query_nonzero(float v) { return (__float_as_uint(v) & 0x7fffffffu) != 0u; }
+
+// n x 8 floats of the caller (o.xyz, tmin, d.xyz, tmax; 4-byte aligned, 16 only when `aligned16` says so) -> rayO, rayD; the identity
+// queue's count word and the traversal's chunk counter; the marks; the number of invalid rays (one atomic per wave).
+__global__ __launch_bounds__(256) void k_stage_rays(const float* __restrict__ rays, uint32_t n, int aligned16, float4* __restrict__ rayO, float4* __restrict__ rayD,
+                                                    unsigned long long* __restrict__ mark, uint32_t* __restrict__ count, uint32_t* __restrict__ work,
+                                                    QueryCounters* __restrict__ counters) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t stride = gridDim.x * 256u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *count = n; // QView{nullptr, count}: the identity queue [0, n), as pt_trace sets it
+        *work = 0;
+    }
+    uint32_t bad = 0; // lane 0: invalid rays this wave has met
+    for (uint32_t base = blockIdx.x * 256u + (threadIdx.x & ~63u); base < n; base += stride) { // wave-uniform: every lane reaches the ballot
+        const uint32_t i = base + lane;
+        bool invalid = false;
+        if (i < n) {
+            float4 o, d;
+            if (aligned16) { // uniform for the launch: one 16-byte load pair per ray
+                o = reinterpret_cast<const float4*>(rays)[2 * (size_t)i];
+                d = reinterpret_cast<const float4*>(rays)[2 * (size_t)i + 1];
+            } else {
+                const float* r = rays + 8 * (size_t)i;
+                o = make_float4(r[0], r[1], r[2], r[3]);
+                d = make_float4(r[4], r[5], r[6], r[7]);
+            }
+            // what ray_setup divides by (pt_bvh.h): dot3(d, d), left to right, and its reciprocal
+            const float s = __fadd_rn(__fadd_rn(__fmul_rn(d.x, d.x), __fmul_rn(d.y, d.y)), __fmul_rn(d.z, d.z));
+            const float inv = __fdiv_rn(1.0f, s);
+            const bool ok = query_finite(o.x) && query_finite(o.y) && query_finite(o.z) && query_finite(o.w) && query_finite(d.x) && query_finite(d.y) &&
+                            query_finite(d.z) && query_finite(d.w) && query_finite(s) && query_nonzero(s) && query_finite(inv) && query_nonzero(inv);
+            invalid = !ok;
+            if (invalid) { // never traversed with its own values: the neutral ray of the packet kernel's idle lanes
+                o = make_float4(0.f, 0.f, 0.f, 1.f);
+                d = make_float4(0.f, 0.f, 1.f, -1.f);
+            }
+            rayO[i] = o;
+            rayD[i] = d;
+        }
+        const unsigned long long m = __ballot(invalid);
+        if (lane == 0) {
+            mark[base >> 6] = m;
+            bad += (uint32_t)__popcll(m);
+        }
+    }
+    if (lane == 0 && bad) atomicAdd(&query_slot(counters)->invalid, (unsigned long long)bad);
+}
+
+// closest-hit queries: one 32-byte pt_hit per ray (include/pt_amd.h) from the traversal's (t, leaf) record, the leaf triangle, its shade
+// normal and the ray as staged; any-hit queries: the int32 flag.  Hits are counted with one atomic per wave.
+__global__ __launch_bounds__(256) void k_hit_attributes(const float2* __restrict__ hit, const float4* __restrict__ rayO, const float4* __restrict__ rayD,
+                                                        const unsigned long long* __restrict__ mark, const LeafTri* __restrict__ tris, const float4* __restrict__ tri_nrm,
+                                                        uint32_t n, int any_hit, int aligned16, void* __restrict__ out, QueryCounters* __restrict__ counters) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t stride = gridDim.x * 256u;
+    uint32_t nhit = 0;
+    for (uint32_t base = blockIdx.x * 256u + (threadIdx.x & ~63u); base < n; base += stride) {
+        const uint32_t i = base + lane;
+        bool is_hit = false;
+        if (i < n) {
+            const bool invalid = ((mark[base >> 6] >> lane) & 1ull) != 0ull;
+            const float2 h = hit[i];
+            const int32_t rec = __float_as_int(h.y); // closest: leaf triangle or -1; any: 1 occluded / 0
+            if (any_hit) {
+                is_hit = !invalid && rec != 0;
+                reinterpret_cast<int32_t*>(out)[i] = invalid ? -2 : rec;
+            } else {
+                float4 a = make_float4(h.x, 0.f, 0.f, __int_as_float(-1)); // t, u, v, prim
+                float4 b = make_float4(__int_as_float(-1), 0.f, 0.f, 0.f); // mesh, ng.xyz
+                if (invalid) {
+                    a.x = 0.f;
+                    a.w = __int_as_float(-2);
+                } else if (rec >= 0) {
+                    is_hit = true;
+                    const LeafTri tri = tris[rec];
+                    const float4 tn = tri_nrm[rec];
+                    const float4 o4 = rayO[i], d4 = rayD[i];
+                    const v3 ray_o = mk3(o4.x, o4.y, o4.z), ray_dir = mk3(d4.x, d4.y, d4.z);
+                    const v3 v0 = mk3(tri.t0.x, tri.t0.y, tri.t0.z), v1 = mk3(tri.t0.w, tri.t1.x, tri.t1.y), v2 = mk3(tri.t1.z, tri.t1.w, tri.t2.x);
+                    // optixGetTriangleBarycentrics, restated from shade_path's textured branch rather than shared with it: a common helper
+                    // would have changed the shade kernels' code, which this feature leaves as it is
+                    const v3 A = sub3(v0, ray_o), B = sub3(v1, ray_o), C = sub3(v2, ray_o);
+                    const v3 CxB = cross3(C, B), AxC = cross3(A, C), BxA = cross3(B, A);
+                    const float Uw = dot3(ray_dir, CxB), Vw = dot3(ray_dir, AxC), Ww = dot3(ray_dir, BxA);
+                    const float det = Uw + Vw + Ww;
+                    a.y = Vw / det;
+                    a.z = Ww / det;
+                    a.w = tri.t2.y; // the primitive's bits
+                    b = make_float4(tri.t2.z /* the mesh's bits */, tn.x, tn.y, tn.z);
+                }
+                if (aligned16) {
+                    reinterpret_cast<float4*>(out)[2 * (size_t)i] = a;
+                    reinterpret_cast<float4*>(out)[2 * (size_t)i + 1] = b;
+                } else {
+                    float* w = reinterpret_cast<float*>(out) + 8 * (size_t)i;
+                    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+                    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+                }
+            }
+        }
+        const unsigned long long m = __ballot(is_hit);
+        if (lane == 0) nhit += (uint32_t)__popcll(m);
+    }
+    if (lane == 0 && nhit) atomicAdd(&query_slot(counters)->hits, (unsigned long long)nhit);
+}
+
 // ------------------------------------------------------------------ probe CDF on the GPU (Probe.h:29-77)
 // BuildCDF (Probe.h:29-77) on the GPU with the reference's sequential float accumulation order, so the arrays equal the host
 // loop bit for bit (a parallel scan would reassociate the sums).  One wave per row: 64 pixels are loaded coalesced and their

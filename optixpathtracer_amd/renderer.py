@@ -129,6 +129,18 @@ def _device_updates(vertices, device: int):
     return ups, len(pairs), keep
 
 
+def _check_query_tensor(name, t, device: int, dtype, tail: tuple):
+    """traceDevice: a CUDA tensor of `dtype` on GPU `device`, shape (n,) + tail, rows dense (any storage offset) — checked before the library is called."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"traceDevice: {name}: a torch tensor or a device pointer is expected (host arrays: trace)")
+    if not t.is_cuda or (t.device.index or 0) != device:
+        raise ValueError(f"traceDevice: {name}: the tensor is on {t.device}, the context on GPU {device}")
+    if t.dtype != dtype or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tuple(tail) or not t.is_contiguous():
+        raise ValueError(f"traceDevice: {name}: a contiguous {dtype} tensor of shape (n{''.join(f', {k}' for k in tail)}) is expected, got {t.dtype} {tuple(t.shape)}")
+
+
 def _mesh_transforms(transforms):
     """pt_mesh_transform[] for {mesh_index: 3x4 or 4x4 array} (the last row of a 4x4 is dropped)."""
     pairs = _pairs(transforms)
@@ -477,6 +489,69 @@ class SampleRenderer:
         ms = C.c_double()
         self._ck(self._L.pt_trace(self._ctx, rays.ctypes.data, n, int(any_hit), t.ctypes.data, prim.ctypes.data, iters, C.byref(ms)), "pt_trace")
         return (prim.astype(np.uint8) if any_hit else (t, prim)), ms.value
+
+    def traceDevice(self, rays, any_hit=False, out=None, wait=True):
+        """optixTrace from the application's own GPU buffers (pt_trace_device): nothing touches the host.
+
+        rays: a CUDA float32 (n, 8) torch tensor on the context's device — o.xyz, tmin, d.xyz, tmax per row, rows 32 bytes apart, any
+        4-byte-aligned storage offset — or a (device pointer, n) tuple.  out: where the results go — a float32 (n, 8) tensor (closest hit:
+        one 32-byte pt_hit per ray) or an int32 (n,) tensor (any_hit: 1 occluded, 0 not, -2 invalid ray), or a raw device pointer; allocated
+        with torch when None.
+        Returns, for a closest-hit query, a dict of typed views of `out`, no copies: t, u, v (float32 (n,)), prim, mesh (int32 (n,)), ng
+        (float32 (n, 3)) and "record", the (n, 8) tensor itself; prim is -1 for a miss (t = the ray's tmax) and -2 for an invalid ray (a
+        non-finite word, a direction of length zero).  For an any-hit query the int32 tensor.  None when `out` was a raw pointer.
+        Ordering is on the device: for a tensor, the library's stream waits for an event recorded on torch's current stream (no host
+        synchronise); a raw pointer's producer must be complete.  wait=True returns when the results are complete, wait=False after
+        enqueueing (several queries may be queued): torch's current stream is then made to wait for the query, so torch work enqueued
+        afterwards on that stream sees the results; queryWait() waits on the host and returns the statistics (after a wait=True call
+        they are in self.queryStats)."""
+        torch, dev = None, getattr(self, "_device", 0)
+        if isinstance(rays, tuple):
+            ptr, n = int(rays[0]), int(rays[1])
+        else:
+            import torch
+
+            _check_query_tensor("rays", rays, dev, torch.float32, (8,))
+            ptr, n = rays.data_ptr(), rays.shape[0]
+        if out is None:
+            import torch
+
+            out = torch.empty((n,) if any_hit else (n, 8), dtype=torch.int32 if any_hit else torch.float32, device=f"cuda:{dev}")
+        if isinstance(out, int):
+            optr = out
+        else:
+            import torch
+
+            _check_query_tensor("out", out, dev, torch.int32 if any_hit else torch.float32, () if any_hit else (8,))
+            if out.shape[0] != n:
+                raise ValueError(f"traceDevice: out has {out.shape[0]} rows for {n} rays")
+            optr = out.data_ptr()
+        if torch is not None:  # what torch enqueued so far — the rays' producer, earlier users of `out` — comes first, on the device
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self.waitEvent(ev.cuda_event)
+        flags = (_lib.PT_QUERY_ANY if any_hit else _lib.PT_QUERY_CLOSEST) | (0 if wait else _lib.PT_QUERY_ASYNC)
+        stats = _lib.QueryStats()
+        self._ck(self._L.pt_trace_device(self._ctx, ptr, n, flags, optr, C.byref(stats) if wait else None), "pt_trace_device")
+        if wait:
+            self.queryStats = stats.as_dict()  # of the query just completed (and of asynchronous ones that were still queued)
+        if torch is not None and not wait:
+            done = torch.cuda.Event()
+            done.record(torch.cuda.ExternalStream(self.stream, device=dev))
+            torch.cuda.current_stream(dev).wait_event(done)
+        if isinstance(out, int):
+            return None
+        if any_hit:
+            return out
+        words = out.view(torch.int32)
+        return dict(t=out[:, 0], u=out[:, 1], v=out[:, 2], prim=words[:, 3], mesh=words[:, 4], ng=out[:, 5:8], record=out)
+
+    def queryWait(self) -> dict:
+        """Waits for the queued traceDevice(wait=False) queries (pt_query_wait).  Returns pt_query_stats summed over the queries since the
+        last wait: rays, hits, invalid_rays, stage_ms / trace_ms / attrib_ms (device time of the three kernels), state_bytes."""
+        s = _lib.QueryStats()
+        self._ck(self._L.pt_query_wait(self._ctx, C.byref(s)), "pt_query_wait")
+        return s.as_dict()
 
     def evalTable(self, which, inp: np.ndarray, out_width: int, material=None, bsdf_mode=PT_BSDF_DISNEY) -> np.ndarray:
         inp = np.ascontiguousarray(inp, np.float32)
