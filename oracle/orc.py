@@ -99,6 +99,8 @@ class Oracle:
         L.orc_hit_census.restype = None
         L.orc_trace_closest.argtypes = [C.c_void_p, f32p, C.c_int, f32p, i32p]
         L.orc_trace_any.argtypes = [C.c_void_p, f32p, C.c_int, u8p]
+        L.orc_trace_any_cull.argtypes = [C.c_void_p, f32p, C.c_int, u8p]
+        L.orc_hit_barycentrics.argtypes = [C.c_void_p, f32p, C.c_uint32, f32p]
         L.orc_bsdf_eval.argtypes = [C.c_int, C.c_void_p, f32p, C.c_float, C.c_float, f32p, f32p, f32p, f32p]
         L.orc_bsdf_pdf.restype = C.c_float
         L.orc_bsdf_pdf.argtypes = [C.c_int, C.c_void_p, C.c_float, C.c_float, f32p, f32p, f32p]
@@ -381,3 +383,108 @@ def ref_add_boxes(R, boxes):
         m = np.array(mat)
         R.refm_add_box(h, m.ctypes.data, np.array(pos, np.float32), np.array(ext, np.float32))
     return ref_model_arrays(R, h)[0]
+
+
+REF_DEVICE_VARIANTS = ("original", "sv", "sv2", "sv3", "sv4_vmv23")
+REF_DEVICE_COUNTERS = ("primary_miss", "secondary_miss", "shadow_occluded", "shadow_unoccluded", "catcher_pass_through", "bsdf_pdf_le_0",
+                       "transmission", "depth_cutoff", "emission_primary", "textured_hit", "clamp_active")
+
+
+class RefFrame(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("subframe_index", C.c_uint32), ("samples_per_launch", C.c_uint32),
+        ("eye", C.c_float * 3), ("U", C.c_float * 3), ("V", C.c_float * 3), ("W", C.c_float * 3),
+        ("launch_w", C.c_uint32), ("launch_h", C.c_uint32), ("factor_x", C.c_uint32), ("factor_y", C.c_uint32), ("fill_size", C.c_int32),
+        ("cx", C.c_uint32), ("cy", C.c_uint32), ("r_inner", C.c_float), ("r_outer", C.c_float),
+        ("offset_x", C.c_uint32), ("offset_y", C.c_uint32), ("redraw", C.c_uint32),
+    ]
+
+
+class RefProbe(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("data", C.c_void_p), ("pdfX", C.c_void_p), ("cdfX", C.c_void_p), ("pdfY", C.c_void_p), ("cdfY", C.c_void_p)]
+
+
+class RefDevice:
+    """oracle/_ref/libptref_device_<variant>{,_det}.so: the reference's own device programs (<variant>/deviceProgram.cu) run on the
+    host by oracle/ref_build/ref_device.cpp.  The ray search, the barycentrics and the texture filter are the checker's (the
+    addresses of O's C functions are handed over once); everything else is the reference's code."""
+
+    def __init__(self, lib, O: Oracle, path: str):
+        self.lib, self.O, self.path = lib, O, path
+        lib.ref_device_compiler.restype = C.c_char_p
+        lib.ref_device_variant.restype = C.c_char_p
+        lib.ref_scene_create.restype = C.c_void_p
+        lib.ref_scene_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ref_scene_destroy.argtypes = [C.c_void_p]
+        lib.ref_render.argtypes = [C.c_void_p, C.POINTER(RefProbe), C.POINTER(RefFrame), f32p, u32p, f32p, f32p, f32p, np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")]
+        lib.ref_set_search.argtypes = [C.c_void_p] * 5
+        L = O.lib
+        lib.ref_set_search(*[C.cast(fn, C.c_void_p) for fn in (L.orc_trace_closest, L.orc_trace_any, L.orc_trace_any_cull, L.orc_hit_barycentrics, L.orc_tex2d)])
+        assert lib.ref_device_num_counters() == len(REF_DEVICE_COUNTERS)
+        self.compiler = lib.ref_device_compiler().decode()
+        self.variant = lib.ref_device_variant().decode()
+        self.detmath = bool(lib.ref_device_detmath())
+        self.foveated = bool(lib.ref_device_foveated())
+
+    def make_scene(self, model, use_bvh=None):
+        """The checker's scene (for the search) and the SBT records of the reference's TriangleMeshSBTData over the same flattened arrays."""
+        osc = self.O.make_scene(model, use_bvh)
+        verts, idx, tri_mesh, mats = model.flatten()
+        keep = [np.ascontiguousarray(verts, np.float32), np.ascontiguousarray(idx, np.uint32), np.ascontiguousarray(tri_mesh, np.uint32), np.ascontiguousarray(mats)]
+        tc = mesh_tex = has_uv = None
+        pix = []
+        if (getattr(model, "textures", []) or []) or any(m.diffuseTextureID >= 0 for m in model.meshes):
+            tc, mesh_tex, has_uv = model.flatten_textures()
+            tc = None if tc is None else np.ascontiguousarray(tc, np.float32)
+            mesh_tex = np.ascontiguousarray(mesh_tex, np.int32)
+            has_uv = np.ascontiguousarray(has_uv, np.uint8)
+            pix = [np.ascontiguousarray(t.pixel, np.uint32) for t in model.textures]
+        ptrs = (C.c_void_p * max(1, len(pix)))(*[p.ctypes.data for p in pix])
+        ws = np.array([p.shape[1] for p in pix] or [0], np.int32)
+        hs = np.array([p.shape[0] for p in pix] or [0], np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        h = self.lib.ref_scene_create(osc.h, keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, len(keep[3]),
+                                      ptr(tc), ptr(mesh_tex), ptr(has_uv), len(pix), ptrs, ws.ctypes.data, hs.ctypes.data)
+        return RefDeviceScene(self, h, [osc, keep, tc, mesh_tex, has_uv, pix, ptrs, ws, hs])
+
+    def launch(self, scene, probe, cam_uvw, eye, width, height, spp, subframe, buffers, region=None, counters=None):
+        """One optixLaunch, in place on buffers = dict(accum, frame, normal, color, albedo); probe: Oracle.make_probe's struct;
+        region: a pt_region dict (the foveated variants' frame fields and launch size) or None for a width x height launch.
+        Adds the branch counts to counters (uint64[len(REF_DEVICE_COUNTERS)]) and returns it."""
+        f = RefFrame()
+        f.width, f.height, f.subframe_index, f.samples_per_launch = width, height, subframe, spp
+        for dst, src in ((f.eye, eye), (f.U, cam_uvw[0]), (f.V, cam_uvw[1]), (f.W, cam_uvw[2])):
+            for k in range(3):
+                dst[k] = float(src[k])
+        f.launch_w, f.launch_h, f.factor_x, f.factor_y, f.fill_size = width, height, 1, 1, 1
+        if region is not None:
+            assert self.foveated
+            f.samples_per_launch, f.subframe_index = region["spp"], region["subframe_index"]
+            for k in ("launch_w", "launch_h", "factor_x", "factor_y", "fill_size", "cx", "cy", "r_inner", "r_outer", "offset_x", "offset_y", "redraw"):
+                setattr(f, k, region[k])
+        p = RefProbe(probe.width, probe.height, probe.data, probe.pdfX, probe.cdfX, probe.pdfY, probe.cdfY)
+        counters = np.zeros(len(REF_DEVICE_COUNTERS), np.uint64) if counters is None else counters
+        b = buffers
+        self.lib.ref_render(scene.h, C.byref(p), C.byref(f), b["accum"].reshape(-1), b["frame"].reshape(-1), b["normal"].reshape(-1),
+                            b["color"].reshape(-1), b["albedo"].reshape(-1), counters)
+        return counters
+
+
+class RefDeviceScene:
+    def __init__(self, dev, h, keep):
+        self.dev, self.h, self._keep = dev, h, keep
+
+    def __del__(self):
+        try:
+            self.dev.lib.ref_scene_destroy(self.h)
+        except Exception:
+            pass
+
+
+def load_ref_device(variant: str, O: Oracle):
+    """The reference's device programs of `variant` in O's math flavour, or None when oracle/_ref does not hold the library."""
+    path = os.path.join(HERE, "_ref", f"libptref_device_{variant}{'_det' if O.mode == 'det' else ''}.so")
+    if not os.path.exists(path):
+        return None
+    return RefDevice(C.CDLL(path), O, path)

@@ -1104,6 +1104,31 @@ void orc_trace_any(const orc_scene* s, const float* rays, int n, uint8_t* occ_ou
     }
 }
 
+/* optixGetTriangleBarycentrics: (weight of vertex 1, weight of vertex 2) — from the hit test's own weights (wtri2's U, V, W) */
+static inline void hit_barycentrics(f3 ray_o, f3 ray_dir, f3 v0, f3 v1, f3 v2, float* bu, float* bv) {
+    wray r;
+    wray_init(&r, ray_o, ray_dir);
+    const f3 A = sub3(v0, r.o), B = sub3(v1, r.o), C = sub3(v2, r.o);
+    const f3 CxB = cross3(C, B), AxC = cross3(A, C), BxA = cross3(B, A);
+    const float Uw = dot3(r.d, CxB), Vw = dot3(r.d, AxC), Ww = dot3(r.d, BxA);
+    const float det = Uw + Vw + Ww;
+    *bu = Vw / det;
+    *bv = Ww / det;
+}
+/* the same for a (ray, primitive) pair of a batch query: ray = (o.xyz, tmin, d.xyz, tmax) as in orc_trace_closest */
+void orc_hit_barycentrics(const orc_scene* s, const float* ray, uint32_t prim, float uv[2]) {
+    const float *p0, *p1, *p2;
+    tri_verts(s, prim, &p0, &p1, &p2);
+    hit_barycentrics(mk3(ray[0], ray[1], ray[2]), mk3(ray[4], ray[5], ray[6]), mk3(p0[0], p0[1], p0[2]), mk3(p1[0], p1[1], p1[2]), mk3(p2[0], p2[1], p2[2]), &uv[0], &uv[1]);
+}
+/* orc_trace_any with OPTIX_RAY_FLAG_CULL_BACK_FACING_TRIANGLES (any_hit_c's cull_back: the sv3/sv4 occlusion ray) */
+void orc_trace_any_cull(const orc_scene* s, const float* rays, int n, uint8_t* occ_out) {
+    for (int i = 0; i < n; ++i) {
+        const float* r = &rays[8 * (size_t)i];
+        occ_out[i] = (uint8_t)any_hit_c(s, mk3(r[0], r[1], r[2]), mk3(r[4], r[5], r[6]), r[3], r[7], 1);
+    }
+}
+
 /* ---------------------------------------------------------------- table entry points (function-level tests) */
 void orc_bsdf_eval(int mode, const orc_material* mat, const float albedo[3], float etaI, float etaO, const float N[3],
                    const float V[3], const float L[3], float out[3]) {
@@ -1244,14 +1269,8 @@ static void closest_hit_program(const orc_scene* s, const orc_probe* probe, int 
     {   /* deviceProgram.cu:512-523: hasTexture && texcoord → albedo REPLACED by tex2D at the interpolated texcoord */
         const uint32_t mesh = s->tri_mesh[prim];
         if (s->mesh_tex && s->mesh_tex[mesh] >= 0 && s->mesh_has_uv[mesh] && s->texcoord) {
-            /* optixGetTriangleBarycentrics: (weight of vertex 1, weight of vertex 2) — from the hit test's own weights */
-            wray r;
-            wray_init(&r, ray_o, ray_dir);
-            const f3 A = sub3(v0, r.o), B = sub3(v1, r.o), C = sub3(v2, r.o);
-            const f3 CxB = cross3(C, B), AxC = cross3(A, C), BxA = cross3(B, A);
-            const float Uw = dot3(r.d, CxB), Vw = dot3(r.d, AxC), Ww = dot3(r.d, BxA);
-            const float det = Uw + Vw + Ww;
-            const float bu = Vw / det, bv = Ww / det;
+            float bu, bv;
+            hit_barycentrics(ray_o, ray_dir, v0, v1, v2, &bu, &bv);
             const uint32_t* ix = &s->idx[3 * (size_t)prim];
             const float *c0 = &s->texcoord[2 * (size_t)ix[0]], *c1 = &s->texcoord[2 * (size_t)ix[1]], *c2 = &s->texcoord[2 * (size_t)ix[2]];
             const float w0 = 1.f - bu - bv;

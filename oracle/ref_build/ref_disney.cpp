@@ -7,8 +7,8 @@
 // Disney.cuh and Probe.h include <optix.h> (through LaunchParams.h and CUDABuffer.h), which the image lacks.
 // ref_build/stub/ holds stand-ins of our own: a type declaration (OptixTraversableHandle), three no-op
 // CUDA/OptiX check macros, an empty optix_stubs.h and the Windows case-insensitive lookup of "Maths.h".
-// None of the functions pinned here reaches them.  deviceProgram.cu (optixTrace, payloads) is NOT built:
-// a stand-in there would define OptiX's behaviour, not pin the reference's.
+// None of the functions pinned here reaches them.  deviceProgram.cu is built by a TU of its own, ref_device.cpp,
+// over a dispatch-only stand-in for <optix_device.h> and the checker's ray search.
 //
 // Kept apart from ref_driver.cpp so that that TU's include resolution (and tests/golden/ref_tables.npz) is unchanged.
 #include <cfloat>

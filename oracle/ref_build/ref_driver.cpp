@@ -9,7 +9,7 @@
 // Disney.cuh and Probe.h (BuildCDF) include <optix.h>: they are built by a TU of their
 // own, ref_disney.cpp, with the stand-ins of ref_build/stub/, so that this TU's include
 // resolution (and tests/golden/ref_tables.npz) stays as it is.  deviceProgram.cu
-// (optixTrace, payloads) is built nowhere ("oracle").
+// (optixTrace, payloads) is built by ref_device.cpp ("oracle").
 #include <cfloat>
 #include <cmath>
 #include <algorithm>

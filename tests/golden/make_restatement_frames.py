@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Generates tests/golden/restatement_frames.npz: small whole frames rendered by the CPU restatement built with the
 deterministic math header (oracle 'det': only IEEE + - * / sqrt, so the bits do not depend on the machine or libm).
-These are NOT reference outputs (the reference's device program cannot be built here): they freeze the
-restatement's semantics so that a later edit of oracle/ or include/pt_detmath.h that changes a single bit of a frame is
-noticed (tests/test_oracle_golden.py::test_restatement_frames_frozen).  Run:  python tests/golden/make_restatement_frames.py"""
+These are NOT reference outputs: they freeze the restatement's semantics so that a later edit of oracle/ or
+include/pt_detmath.h that changes a single bit of a frame is noticed (tests/test_oracle_golden.py::test_restatement_frames_frozen).
+Frames computed by the reference's own device programs are in tests/golden/ref_frames.npz (make_ref_frames.py); the
+Lambert case here is a project extension that the reference has no program for.  Run:  python tests/golden/make_restatement_frames.py"""
 import os
 import sys
 
