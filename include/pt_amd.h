@@ -353,6 +353,55 @@ int pt_adaptive_end(pt_ctx* ctx);
 enum pt_adaptive_array { PT_ADAPT_MOMENTS = 0 /* width*height x {n, s1, s2, 0} f32 */, PT_ADAPT_ACTIVE = 1 /* nbx*nby u8 (0 for blocks of other ranks) */ };
 int pt_download_adaptive(pt_ctx* ctx, int which /* pt_adaptive_array */, void* host, size_t bytes);
 
+/* VIEWPORTS (no reference counterpart): several cameras rendered into rectangles of ONE frame, in one wavefront batch, over one copy of the
+ * scene and its acceleration structure — a stereo pair for a head-mounted display, a camera array for synthetic data.
+ *
+ * What a view pixel holds.  Frame pixel (X, Y) inside view v has local coordinates x = X - v.x, y = Y - v.y and is rendered exactly as
+ * pixel (x, y) of a v.width x v.height frame with camera v: seed tea4(y * v.width + x, subframe), jitter 2 * ((x + jx) / v.width) - 1 (and
+ * likewise with y, jy, v.height), direction normalize(dx*U + dy*V + W) with v's vectors, origin v.eye; the backplate in the resolve comes from
+ * the same ray.  Its five buffers at (X, Y) get the bits pt_render(spp, subframe_index) would leave at (x, y) of such a context, given the
+ * same previous accum value.  A pixel in no view is not touched in any buffer by any render call.  pt_set_camera is remembered but unused
+ * while views are set; it is in force again after pt_set_views(n = 0).
+ *
+ * pt_set_views is refused with PT_ERR_INVALID (text in pt_last_error, nothing changed) for: a null context; null `views` with n > 0; no
+ * pt_resize yet; n > PT_MAX_VIEWS; x or y negative or not a multiple of 8; width or height < 1; a rectangle leaving the frame; two
+ * rectangles sharing a pixel.  With origins on the 8x8 block grid and no shared pixels a block touches at most one view; the device code
+ * looks the view up by block.
+ *
+ * Ordering.  pt_set_views and both camera setters wait for the frames in flight first (pt_options.frames_in_flight), as pt_resize does, and
+ * are complete when they return.  A loop that moves its cameras every frame therefore runs one frame at a time; camera updates that do not
+ * wait for the frames in flight are not part of this interface.
+ *
+ * pt_set_view_cameras / pt_set_view_cameras_device: n x 12 floats (eye, U, V, W per view, in the order of pt_set_views); n must equal the
+ * current view count, else PT_ERR_INVALID.  They change cameras only — the rectangles and the pixel list stay as they are — so this is the
+ * per-frame call.  Values are taken as given, as pt_set_camera takes them.  The device variant checks its pointer as pt_trace_device checks
+ * its arrays (known to HIP, device memory of the context's device, 4-byte aligned, fitting its allocation; otherwise PT_ERR_INVALID), reads
+ * the values on pt_stream(ctx) under the STREAM CONTRACT and returns when the copy is complete.
+ *
+ * State changes.  pt_resize and pt_set_partition drop the views: the order of calls is partition, resize, views.  pt_set_views implies
+ * pt_adaptive_end.
+ *
+ * Honoured by pt_render, pt_render_batch and pt_render_device (launch chain and fused pass, frames_in_flight 0-3), by pt_render_mask (it
+ * renders the view pixels of the blocks the mask names, and active_pixels counts those), on a partitioned context (the view pixels of the
+ * blocks the rank owns; ownership stays a function of frame coordinates) and by pt_multi_render / pt_multi_render_batch.  Refused with
+ * PT_ERR_UNSUPPORTED while views are set, state unchanged: pt_render_regions and pt_multi_render_regions (the foveated launches have their
+ * own index mapping) and pt_adaptive_begin.  pt_denoise, pack / unpack and the downloads work on the whole buffers as before; the a-trous
+ * filter does not know about view borders (its taps cross them).
+ *
+ * pt_stats.paths and the ray counts describe the pixels rendered.  The on-line chain/fused trial (pt_stats.schedule) treats a change of
+ * the views' pixel count as any other change of the frame's path count, and a frame with views never asks for more path state than the
+ * rank's full frame at the same samples. */
+#define PT_MAX_VIEWS 4096
+typedef struct pt_view {            /* 64 bytes */
+    int32_t x, y;                   /* top-left pixel of the rectangle in the frame; multiples of 8 */
+    int32_t width, height;          /* >= 1; the rectangle lies inside the frame */
+    float eye[3], U[3], V[3], W[3]; /* what pt_set_camera takes */
+} pt_view;
+int pt_set_views(pt_ctx* ctx, const pt_view* views, uint32_t n); /* n == 0 (views may be NULL): back to the single camera */
+int pt_get_views(const pt_ctx* ctx, pt_view* out /* may be NULL */, uint32_t cap, uint32_t* n /* may be NULL: the view count */); /* copies min(cap, count) views */
+int pt_set_view_cameras(pt_ctx* ctx, const float* cams /* n x 12: eye,U,V,W */, uint32_t n);            /* host memory */
+int pt_set_view_cameras_device(pt_ctx* ctx, const float* dev_cams /* n x 12 */, uint32_t n);            /* device memory */
+
 /* SampleRenderer::downloadPixels (SimplePathtracer.cpp:149-153), generalised to all five buffers.
  * bytes must equal width*height*(16 or 4). */
 int pt_download(pt_ctx* ctx, int which /* pt_buffer */, void* host, size_t bytes);
@@ -455,6 +504,9 @@ int pt_multi_set_probe(pt_multi* m, const float* data_rgba, const float* pdfX, c
 int pt_multi_set_probe_image(pt_multi* m, const float* data_rgba, int width, int height);
 int pt_multi_resize(pt_multi* m, int width, int height, int tile_w, int tile_h); /* tile sizes: multiples of 8; 0 = 64 x 16 */
 int pt_multi_set_camera(pt_multi* m, const float eye[3], const float U[3], const float V[3], const float W[3]);
+/* VIEWPORTS on every rank (after pt_multi_resize): each rank renders the view pixels of the blocks it owns; the gathers are unchanged */
+int pt_multi_set_views(pt_multi* m, const pt_view* views, uint32_t n);
+int pt_multi_set_view_cameras(pt_multi* m, const float* cams /* n x 12, host memory */, uint32_t n);
 /* gather_mask: bit (1 << pt_buffer) for every buffer to assemble on all ranks after the frame (0 = none: pure throughput);
  * host_rgba8 (may be NULL) receives rank 0's frame buffer and implies gathering PT_BUF_FRAME.
  * Every rank's launches are enqueued by a host thread of its own (pt_multi_stats.enqueue_ms, .threads), so the host time of a frame does

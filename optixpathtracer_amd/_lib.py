@@ -26,6 +26,7 @@ EXPORTS = [
     "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
     "pt_trace_device", "pt_query_wait",
+    "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
 PT_UPDATE_REFIT, PT_UPDATE_REBUILD = 0, 1  # pt_update_mode
@@ -34,6 +35,15 @@ PT_FROM_REST, PT_FROM_CURRENT = 0, 1  # pt_transform_source
 
 PT_ADAPT_MOMENTS, PT_ADAPT_ACTIVE = 0, 1  # pt_adaptive_array
 PT_QUERY_CLOSEST, PT_QUERY_ANY, PT_QUERY_ASYNC = 0, 1, 2  # pt_query_flags
+PT_MAX_VIEWS = 4096
+
+
+class View(C.Structure):  # pt_view
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("eye", C.c_float * 3), ("U", C.c_float * 3), ("V", C.c_float * 3), ("W", C.c_float * 3)]
+
+
+assert C.sizeof(View) == 64
 
 
 class Hit(C.Structure):  # pt_hit
@@ -255,6 +265,12 @@ def load_library() -> C.CDLL:
     L.pt_download_adaptive.argtypes = [vp, i, vp, C.c_size_t]
     L.pt_trace_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(QueryStats)]
     L.pt_query_wait.argtypes = [vp, C.POINTER(QueryStats)]
+    L.pt_set_views.argtypes = [vp, C.POINTER(View), u32]
+    L.pt_get_views.argtypes = [vp, C.POINTER(View), u32, C.POINTER(u32)]
+    L.pt_set_view_cameras.argtypes = [vp, vp, u32]
+    L.pt_set_view_cameras_device.argtypes = [vp, vp, u32]
+    L.pt_multi_set_views.argtypes = [vp, C.POINTER(View), u32]
+    L.pt_multi_set_view_cameras.argtypes = [vp, vp, u32]
     L.pt_version.restype = C.c_char_p
     f3p = C.POINTER(f * 3)
     L.pt_create_multi.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), i, C.POINTER(vp)]

@@ -94,6 +94,23 @@ struct Camera {
     void UVWFrame(float3& U, float3& V, float3& W) const { pt_uvw_frame(&eye.x, &lookat.x, &up.x, fovY, aspectRatio, &U.x, &V.x, &W.x); }
 };
 
+// Beyond the reference: one rectangle of the frame with a camera of its own (pt_view, include/pt_amd.h "VIEWPORTS"); x and y are
+// multiples of 8, and the camera's aspectRatio is the view's own width / height
+struct View {
+    int x = 0, y = 0, width = 0, height = 0;
+    Camera camera;
+};
+inline std::vector<pt_view> toViews(const std::vector<View>& views) {
+    std::vector<pt_view> out(views.size());
+    for (size_t i = 0; i < views.size(); ++i) {
+        const View& v = views[i];
+        float3 U, V, W;
+        v.camera.UVWFrame(U, V, W);
+        out[i] = pt_view{v.x, v.y, v.width, v.height, {v.camera.eye.x, v.camera.eye.y, v.camera.eye.z}, {U.x, U.y, U.z}, {V.x, V.y, V.z}, {W.x, W.y, W.z}};
+    }
+    return out;
+}
+
 // LaunchParams.h:32-38 — set by initLaunchParams (main.cpp:138-143), never read by the device code
 struct ParallelogramLight {
     float3 corner{0, 0, 0};
@@ -170,6 +187,22 @@ class SampleRenderer {
         camera.UVWFrame(U, V, W);
         launchParams.camera.eye = camera.eye; launchParams.camera.U = U; launchParams.camera.V = V; launchParams.camera.W = W;
         ck(pt_set_camera(ctx, &camera.eye.x, &U.x, &V.x, &W.x));
+    }
+    // Beyond the reference: several cameras in rectangles of this one frame (pt_set_views): a stereo pair, a camera array.  Every render call
+    // then fills each rectangle as a frame of its size with its camera would be filled; pixels in no view are left alone; an empty vector
+    // returns to setCamera's camera.  setViewCameras moves the cameras of the current views (the per-frame call).
+    void setViews(const std::vector<View>& views) {
+        const std::vector<pt_view> v = toViews(views);
+        ck(pt_set_views(ctx, v.data(), (uint32_t)v.size()));
+    }
+    void setViewCameras(const std::vector<Camera>& cameras) {
+        std::vector<float> rows;
+        for (const Camera& c : cameras) {
+            float3 U, V, W;
+            c.UVWFrame(U, V, W);
+            for (const float3& f : {c.eye, U, V, W}) rows.insert(rows.end(), {f.x, f.y, f.z});
+        }
+        ck(pt_set_view_cameras(ctx, rows.data(), (uint32_t)cameras.size()));
     }
     void setProbe(const ProbeData& probe) {
         if (!probe.valid) throw std::runtime_error("Probe Data is not valid"); // Probe.h:104-105
@@ -310,6 +343,10 @@ class MultiSampleRenderer {
         float3 U, V, W;
         camera.UVWFrame(U, V, W);
         ck(pt_multi_set_camera(multi, &camera.eye.x, &U.x, &V.x, &W.x));
+    }
+    void setViews(const std::vector<View>& views) { // SampleRenderer::setViews on every rank, after resize()
+        const std::vector<pt_view> v = toViews(views);
+        ck(pt_multi_set_views(multi, v.data(), (uint32_t)v.size()));
     }
     void setProbe(const ProbeData& probe) {
         if (!probe.valid) throw std::runtime_error("Probe Data is not valid");

@@ -152,6 +152,19 @@ struct pt_ctx {
         uint32_t* h_counts = nullptr;  // pinned host copy
         std::vector<uint8_t> owned_flags; // [nblk] 1 = the rank owns the block: the active set pt_adaptive_begin starts from
     } blk;
+    // Viewports (pt_set_views): n > 0 while views are set.  A frame then runs over d_pixels / owned below instead of the rank's whole list: the
+    // view pixels of the blocks the rank owns, in the order of build_pixel_lists.  Freed with the frame buffers.
+    struct Views {
+        uint32_t n = 0;
+        std::vector<pt_view> host;    // what pt_get_views returns (the device camera feed copies its values back)
+        std::vector<uint16_t> vblock; // [nbx * nby] the view of each 8x8 block, 0xffff: none
+        pt_view* d_views = nullptr;
+        uint16_t* d_vblock = nullptr;
+        uint32_t* d_pixels = nullptr;
+        uint32_t owned = 0;
+    } vw;
+    const uint32_t* frame_pixels() const { return vw.n ? vw.d_pixels : d_pixels; } // the pixel list of a whole frame
+    uint32_t frame_owned() const { return vw.n ? vw.owned : owned; }
     // pt_adaptive_begin .. pt_adaptive_end.  `list` / `count` are what the NEXT pt_render_adaptive renders: the compaction that follows a
     // call's decision is enqueued behind that call's frame and its count comes back with the frame's own final synchronisation.
     struct Adaptive {
@@ -645,8 +658,14 @@ static void free_blocks(pt_ctx* ctx) {
     if (b.h_counts) hipHostFree(b.h_counts);
     b = pt_ctx::Blocks{};
 }
+static void free_views(pt_ctx* ctx) {
+    pt_ctx::Views& v = ctx->vw;
+    dfree(v.d_views); dfree(v.d_vblock); dfree(v.d_pixels);
+    v = pt_ctx::Views{};
+}
 static void free_frame(pt_ctx* ctx) {
     free_blocks(ctx);
+    free_views(ctx);
     for (void*& d : ctx->display) {
         if (d) hipFree(d);
         d = nullptr;
@@ -1205,6 +1224,7 @@ struct ChunkMode {
     bool adapt_grid = false;  // whole frames in flight (frames_in_flight = 3): traversal grids sized by the pass
     const uint32_t* pixels = nullptr; // the frame's pixel list (null: the rank's whole list, ctx->d_pixels)
     float4* moments = nullptr;        // pt_render_adaptive: the resolve records the per-pixel moments
+    ViewParams vp{};                  // viewports (pt_set_views): the *_views kernels generate and resolve (null: the frame's single camera)
 };
 // A frame over a subset of the rank's pixels (pt_render_mask, pt_render_adaptive): a compacted list in the order of d_pixels, and what runs
 // on the context's stream between the frame's last kernel and its end event.
@@ -1224,7 +1244,12 @@ static bool chunks_threadable(const pt_ctx* ctx, uint32_t nchunks, int nsets, bo
 }
 
 // the fused bounce loop of one pass (pt_fused.h)
-static void launch_path_loop(const pt_ctx* ctx, hipStream_t s, unsigned grid, const PathLoopArgs& pa) {
+static void launch_path_loop(const pt_ctx* ctx, hipStream_t s, unsigned grid, const PathLoopArgs& pa, const ViewParams& vp) {
+    if (vp.views) { // a frame with viewports
+        if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_path_loop_views<PT_BSDF_LAMBERT>), dim3(grid), dim3(64), 0, s, pa, vp);
+        else hipLaunchKernelGGL((k_path_loop_views<PT_BSDF_DISNEY>), dim3(grid), dim3(64), 0, s, pa, vp);
+        return;
+    }
     if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_path_loop<PT_BSDF_LAMBERT>), dim3(grid), dim3(64), 0, s, pa);
     else hipLaunchKernelGGL((k_path_loop<PT_BSDF_DISNEY>), dim3(grid), dim3(64), 0, s, pa);
 }
@@ -1350,7 +1375,7 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
             pa.pool = P.work; // the first traversal launch's chunk counter, unused here (zeroed with the pass's counters)
             pa.cap = cap;
             pa.totals = bs.totals;
-            launch_path_loop(ctx, bs.stream, grid, pa);
+            launch_path_loop(ctx, bs.stream, grid, pa, mode.vp);
             ++lc.trace;
             ++lc.fused;
         } else {
@@ -1358,6 +1383,8 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
                 SpanGuard g(ctx, CLS_OTHER, bs.stream);
                 if (job)
                     hipLaunchKernelGGL(k_generate_region, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, P.tmin, (uint32_t)job->var.initial_depth, job->l0, job->nl, P.qcur);
+                else if (mode.vp.views)
+                    hipLaunchKernelGGL(k_generate_views, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0, mode.vp);
                 else
                     hipLaunchKernelGGL(k_generate, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0);
             }
@@ -1431,6 +1458,8 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
                 hipLaunchKernelGGL(k_resolve_region, dim3((job->nl + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, job->var, job->l0, job->nl);
             else if (mode.moments)
                 hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp, mode.moments);
+            else if (mode.vp.views)
+                hipLaunchKernelGGL(k_resolve_views, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp, mode.vp);
             else
                 hipLaunchKernelGGL(k_resolve, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp);
         }
@@ -1599,7 +1628,8 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
     int rc = frame_open(ctx, slot, pipelined, "pt_render", bad_args);
     if (rc || ctx->width == 0) return rc;
     const uint32_t vspp = spp * count; // samples of a pixel over the whole batch
-    const uint32_t owned = sub ? sub->count : ctx->owned;
+    const bool views = ctx->vw.n != 0;
+    const uint32_t owned = sub ? sub->count : ctx->frame_owned();
     // Chunking.  All samples of a pixel stay in one pixel chunk.  The frame is cut into (at least) `streams` pixel
     // chunks that run concurrently on separate stream pairs; a chunk holds at most max_paths/streams paths, so
     // samples are split when spp*pixels exceed that; shadow-catcher scenes run one sample per pass so that the
@@ -1612,8 +1642,10 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
         ctx->sched_pending.valid = false;
         ctx->sched_flags = cm.fused_frame ? 1u : 0u;
     } else {
-        cm.fused_frame = sched_choose(ctx, pipelined, owned, vspp);
+        cm.fused_frame = sched_choose(ctx, pipelined, owned, vspp); // (viewports: keyed by the views' pixel count like any other path count)
+        if (views) cm.pixels = ctx->vw.d_pixels;
     }
+    if (views) cm.vp = ViewParams{ctx->vw.d_vblock, ctx->vw.d_views, (uint32_t)(ctx->width + 7) / 8u}; // (a masked frame's list holds view pixels only, too)
     const uint32_t max_paths = std::max<uint32_t>(ctx->opt.max_paths, 64u);
     // sets, paths per set, pixels per chunk and samples per pass of a frame of `px` pixels, each bounded by lim_* (a subset frame's envelope)
     struct Shape { int nsets; uint32_t cap, Np, S; };
@@ -1631,7 +1663,7 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
     // launches) grows once to the full frame's shape instead of cutting every later frame into chunks of its first one.
     int lim_sets = PT_MAX_SETS;
     uint32_t lim_cap = 0xffffffffu, lim_pix = 0xffffffc0u;
-    if (sub) {
+    if (sub || views) { // (a frame with viewports is a subset of the rank's pixels too)
         const Shape full = shape(ctx->owned, sched_static(ctx, pipelined, ctx->owned, vspp), lim_sets, lim_cap, lim_pix);
         lim_sets = std::max((int)ctx->sets.size(), full.nsets);
         lim_cap = std::max(ctx->set_cap, full.Np * full.S);
@@ -1944,6 +1976,7 @@ extern "C" int pt_wait_event(pt_ctx* ctx, void* hip_event) {
 // passes of the frame's launches go to the batch sets in turn, every stream carries on behind its own previous work, and the first
 // resolve of the frame waits for the end of the previous frame (later frames overwrite earlier ones)
 static int regions_enqueue(pt_ctx* ctx, const pt_region* regions, uint32_t n, const pt_variant* variant, int slot = 0, bool pipelined = false) {
+    if (ctx->vw.n) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_render_regions: not with viewports set (pt_set_views): the foveated launches have their own index mapping");
     int rc = frame_open(ctx, slot, pipelined, "pt_render_regions", nullptr);
     if (rc || ctx->width == 0) return rc;
     if (ctx->has_catcher) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_render_regions: shadow-catcher materials are not supported in foveated launches");
@@ -2009,6 +2042,7 @@ static int regions_enqueue(pt_ctx* ctx, const pt_region* regions, uint32_t n, co
 
 extern "C" int pt_render_regions(pt_ctx* ctx, const pt_region* regions, uint32_t n, const pt_variant* variant, uint32_t* host_rgba8) {
     if (!ctx || (!regions && n)) return PT_ERR_INVALID;
+    if (ctx->vw.n) return regions_enqueue(ctx, regions, n, variant); // refused before any frame slot is touched
     const int F = frames_mode(ctx);
     int rc;
     if (F < 2) {
@@ -2038,13 +2072,22 @@ static int build_blocks(pt_ctx* ctx) {
     for (uint32_t by = 0; by < B.nby; ++by)
         for (uint32_t bx = 0; bx < B.nbx; ++bx) {
             const int owner = (int)(((bx * 8u) / (uint32_t)ctx->tile_w + (by * 8u) / (uint32_t)ctx->tile_h) % (uint32_t)ctx->world);
-            const uint32_t size = owner == ctx->rank ? (uint32_t)(std::min(8, w - (int)bx * 8) * std::min(8, h - (int)by * 8)) : 0u;
+            uint32_t size = owner == ctx->rank ? (uint32_t)(std::min(8, w - (int)bx * 8) * std::min(8, h - (int)by * 8)) : 0u;
+            if (size && ctx->vw.n) { // viewports: the block's pixels inside its view (the order of the view pixel list, pt_set_views)
+                const uint16_t vi = ctx->vw.vblock[by * B.nbx + bx];
+                if (vi == 0xffffu) {
+                    size = 0u;
+                } else {
+                    const pt_view& v = ctx->vw.host[vi];
+                    size = (uint32_t)(std::min(8, v.x + v.width - (int)bx * 8) * std::min(8, v.y + v.height - (int)by * 8));
+                }
+            }
             spans[by * B.nbx + bx] = BlockSpan{at, size};
             B.owned_flags.push_back(size ? 1 : 0);
             at += size;
             B.owned_blocks += size ? 1u : 0u;
         }
-    if (at != ctx->owned) return fail(ctx, PT_ERR_INVALID, "block table does not match the pixel list");
+    if (at != ctx->frame_owned()) return fail(ctx, PT_ERR_INVALID, "block table does not match the pixel list");
     CK(dalloc(&B.d_spans, (size_t)B.nblk));
     CK(dalloc(&B.d_flags, (size_t)B.nblk));
     CK(dalloc(&B.d_offsets, (size_t)B.nblk));
@@ -2068,7 +2111,7 @@ static int compact_enqueue(pt_ctx* ctx, hipStream_t s, const uint8_t* d_flags, u
     uint32_t *part_pix = B.d_parts, *part_blk = B.d_parts + B.nparts;
     hipLaunchKernelGGL(k_mask_partials, dim3(B.nparts), dim3(256), 0, s, d_flags, B.d_spans, B.nblk, B.d_offsets, part_pix, part_blk);
     hipLaunchKernelGGL(k_mask_scan_parts, dim3(1), dim3(1024), 0, s, part_pix, part_blk, B.nparts, B.d_counts);
-    hipLaunchKernelGGL(k_mask_compact, dim3((B.nblk + 3u) / 4u), dim3(256), 0, s, d_flags, B.d_spans, B.nblk, B.d_offsets, part_pix, ctx->d_pixels, d_list);
+    hipLaunchKernelGGL(k_mask_compact, dim3((B.nblk + 3u) / 4u), dim3(256), 0, s, d_flags, B.d_spans, B.nblk, B.d_offsets, part_pix, ctx->frame_pixels(), d_list);
     CK(hipGetLastError());
     CK(hipMemcpyAsync(B.h_counts, B.d_counts, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s));
     return PT_OK;
@@ -2111,6 +2154,7 @@ extern "C" int pt_adaptive_begin(pt_ctx* ctx, const pt_adaptive_params* prm) {
     if (!(prm->threshold >= 0.f) || !std::isfinite(prm->threshold)) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: threshold must be finite and >= 0");
     if (!(prm->dark_floor >= 0.f) || !std::isfinite(prm->dark_floor)) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: dark_floor must be finite and >= 0");
     if (prm->min_subframes < 2) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: min_subframes must be at least 2");
+    if (ctx->vw.n) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_adaptive_begin: not with viewports set (pt_set_views)");
     int rc = subset_open(ctx, "pt_adaptive_begin", false, 0);
     if (rc) return rc;
     free_adaptive(ctx);
@@ -2554,15 +2598,15 @@ extern "C" int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit,
 
 // ------------------------------------------------------------------ pt_trace_device: queries from and to the caller's device arrays
 // One array of the call: memory of the context's device that HIP knows, 4-byte aligned, inside its allocation (pt_update_meshes_device's checks).
-static int query_pointer_validate(pt_ctx* ctx, const void* p, size_t bytes, const char* who, std::string& err) {
-    const std::string name = std::string("pt_trace_device: ") + who;
+static int query_pointer_validate(pt_ctx* ctx, const void* p, size_t bytes, const char* who, std::string& err, const char* fn = "pt_trace_device", const char* host_fn = "pt_trace") {
+    const std::string name = std::string(fn) + ": " + who;
     if (!p) { err = name + " is null"; return PT_ERR_INVALID; }
     if (reinterpret_cast<uintptr_t>(p) & 3u) { err = name + " is not 4-byte aligned"; return PT_ERR_INVALID; }
     hipPointerAttribute_t at;
     const hipError_t pe = hipPointerGetAttributes(&at, p);
     if (pe != hipSuccess || at.type != hipMemoryTypeDevice) {
         (void)hipGetLastError(); // an unknown pointer leaves hipErrorInvalidValue behind
-        err = name + " is not device memory (for host arrays use pt_trace)";
+        err = name + " is not device memory (for host arrays use " + std::string(host_fn) + ")";
         return PT_ERR_INVALID;
     }
     if (at.device != ctx->device) { err = name + " is memory of device " + std::to_string(at.device) + ", the context is on device " + std::to_string(ctx->device); return PT_ERR_INVALID; }
@@ -2715,6 +2759,113 @@ extern "C" int pt_trace_device(pt_ctx* ctx, const float* dev_rays, uint32_t n, u
     const int rc = query_complete(ctx);
     query_report(ctx, stats);
     return rc;
+}
+
+// ------------------------------------------------------------------ viewports: several cameras in rectangles of one frame
+static int upload_views(pt_ctx* ctx) {
+    CK(hipMemcpy(ctx->vw.d_views, ctx->vw.host.data(), sizeof(pt_view) * ctx->vw.n, hipMemcpyHostToDevice));
+    return PT_OK;
+}
+extern "C" int pt_set_views(pt_ctx* ctx, const pt_view* views, uint32_t n) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_set_views: null context");
+    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
+    if (n && !views) return fail(ctx, PT_ERR_INVALID, "pt_set_views: null views");
+    if (n && ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_set_views: no frame size yet (pt_resize)");
+    if (n > PT_MAX_VIEWS) return fail(ctx, PT_ERR_INVALID, "pt_set_views: more than PT_MAX_VIEWS views");
+    const int w = ctx->width, h = ctx->height;
+    const uint32_t nbx = (uint32_t)(w + 7) / 8u, nby = (uint32_t)(h + 7) / 8u;
+    std::vector<uint16_t> vblock((size_t)nbx * nby, (uint16_t)0xffffu);
+    for (uint32_t i = 0; i < n; ++i) {
+        const pt_view& v = views[i];
+        const std::string who = "pt_set_views: view " + std::to_string(i);
+        if (v.x < 0 || v.y < 0 || (v.x & 7) || (v.y & 7)) return fail(ctx, PT_ERR_INVALID, (who + ": x and y must be non-negative multiples of 8").c_str());
+        if (v.width < 1 || v.height < 1) return fail(ctx, PT_ERR_INVALID, (who + ": width and height must be at least 1").c_str());
+        if (v.x >= w || v.y >= h || v.width > w - v.x || v.height > h - v.y) return fail(ctx, PT_ERR_INVALID, (who + ": the rectangle leaves the frame").c_str());
+        // origins sit on the block grid, so two views that touch the same block both hold its first pixel
+        for (uint32_t by = (uint32_t)v.y / 8u; by <= (uint32_t)(v.y + v.height - 1) / 8u; ++by)
+            for (uint32_t bx = (uint32_t)v.x / 8u; bx <= (uint32_t)(v.x + v.width - 1) / 8u; ++bx) {
+                uint16_t& b = vblock[(size_t)by * nbx + bx];
+                if (b != 0xffffu) return fail(ctx, PT_ERR_INVALID, (who + " shares pixels with view " + std::to_string(b)).c_str());
+                b = (uint16_t)i;
+            }
+    }
+    CK(hipSetDevice(ctx->device));
+    CK(hipStreamSynchronize(ctx->stream));
+    free_blocks(ctx); // the block spans follow the frame's pixel list; implies pt_adaptive_end
+    free_views(ctx);
+    ctx->sched_pending.valid = false;
+    if (n == 0) return PT_OK;
+    // the view pixel list in the order of build_pixel_lists: whole blocks, block order kept, only pixels inside their view, only owned blocks
+    std::vector<uint32_t> list;
+    for (uint32_t by = 0; by < nby; ++by)
+        for (uint32_t bx = 0; bx < nbx; ++bx) {
+            const uint16_t vi = vblock[(size_t)by * nbx + bx];
+            const int owner = (int)(((bx * 8u) / (uint32_t)ctx->tile_w + (by * 8u) / (uint32_t)ctx->tile_h) % (uint32_t)ctx->world);
+            if (vi == 0xffffu || owner != ctx->rank) continue;
+            const pt_view& v = views[vi];
+            for (int iy = 0; iy < 8; ++iy)
+                for (int ix = 0; ix < 8; ++ix) {
+                    const int x = (int)bx * 8 + ix, y = (int)by * 8 + iy;
+                    if (x < v.x + v.width && y < v.y + v.height) list.push_back((uint32_t)x | ((uint32_t)y << 16));
+                }
+        }
+    pt_ctx::Views& V = ctx->vw;
+    V.host.assign(views, views + n);
+    V.vblock = vblock;
+    V.owned = (uint32_t)list.size();
+    int rc = PT_OK;
+    hipError_t e = dalloc(&V.d_views, (size_t)n);
+    if (e == hipSuccess) e = dalloc(&V.d_vblock, vblock.size());
+    if (e == hipSuccess) e = dalloc(&V.d_pixels, list.size());
+    if (e == hipSuccess) e = hipMemcpy(V.d_views, V.host.data(), sizeof(pt_view) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(V.d_vblock, vblock.data(), sizeof(uint16_t) * vblock.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !list.empty()) e = hipMemcpy(V.d_pixels, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        ctx->err = std::string("pt_set_views: ") + hipGetErrorString(e);
+        free_views(ctx); // all of it or nothing
+        rc = PT_ERR_HIP;
+    } else {
+        V.n = n;
+    }
+    return rc;
+}
+
+extern "C" int pt_get_views(const pt_ctx* ctx, pt_view* out, uint32_t cap, uint32_t* n) {
+    if (!ctx) return PT_ERR_INVALID;
+    if (n) *n = ctx->vw.n;
+    if (out)
+        for (uint32_t i = 0; i < std::min(cap, ctx->vw.n); ++i) out[i] = ctx->vw.host[i];
+    return PT_OK;
+}
+
+static int view_cameras_open(pt_ctx* ctx, const char* fn, uint32_t n) {
+    int rc = drain(ctx); // frames in flight read the view records
+    if (rc) return rc;
+    if (n != ctx->vw.n) return fail(ctx, PT_ERR_INVALID, (std::string(fn) + ": n must equal the current view count (pt_set_views)").c_str());
+    CK(hipSetDevice(ctx->device));
+    return PT_OK;
+}
+extern "C" int pt_set_view_cameras(pt_ctx* ctx, const float* cams, uint32_t n) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_set_view_cameras: null context");
+    int rc = view_cameras_open(ctx, "pt_set_view_cameras", n);
+    if (rc || n == 0) return rc;
+    if (!cams) return fail(ctx, PT_ERR_INVALID, "pt_set_view_cameras: null cameras");
+    for (uint32_t i = 0; i < n; ++i) memcpy(ctx->vw.host[i].eye, cams + (size_t)i * 12, sizeof(float) * 12);
+    return upload_views(ctx);
+}
+extern "C" int pt_set_view_cameras_device(pt_ctx* ctx, const float* dev_cams, uint32_t n) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_set_view_cameras_device: null context");
+    int rc = view_cameras_open(ctx, "pt_set_view_cameras_device", n);
+    if (rc || n == 0) return rc;
+    std::string err;
+    rc = query_pointer_validate(ctx, dev_cams, sizeof(float) * 12 * (size_t)n, "dev_cams", err, "pt_set_view_cameras_device", "pt_set_view_cameras");
+    if (rc) return fail(ctx, rc, err.c_str());
+    pt_ctx::Views& V = ctx->vw;
+    hipLaunchKernelGGL(k_view_cameras, dim3((n * 12u + 255u) / 256u), dim3(256), 0, ctx->stream, dev_cams, n, V.d_views);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(V.host.data(), V.d_views, sizeof(pt_view) * n, hipMemcpyDeviceToHost, ctx->stream)); // what pt_get_views reports
+    CK(hipStreamSynchronize(ctx->stream));
+    return PT_OK;
 }
 
 extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes, uint32_t* num_nodes, uint32_t* num_tris) {
@@ -3438,6 +3589,23 @@ extern "C" int pt_multi_set_camera(pt_multi* m, const float eye[3], const float 
     return PT_OK;
 }
 
+extern "C" int pt_multi_set_views(pt_multi* m, const pt_view* views, uint32_t n) {
+    if (!m) return PT_ERR_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        int rc = mctx(m, (int)r, pt_set_views(m->ctx[r], views, n), "pt_multi_set_views");
+        if (rc) return rc;
+    }
+    return PT_OK;
+}
+extern "C" int pt_multi_set_view_cameras(pt_multi* m, const float* cams, uint32_t n) {
+    if (!m) return PT_ERR_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        int rc = mctx(m, (int)r, pt_set_view_cameras(m->ctx[r], cams, n), "pt_multi_set_view_cameras");
+        if (rc) return rc;
+    }
+    return PT_OK;
+}
+
 extern "C" int pt_multi_resize(pt_multi* m, int width, int height, int tile_w, int tile_h) {
     if (!m) return PT_ERR_INVALID;
     if (width == 0 || height == 0) return PT_OK;
@@ -3744,6 +3912,7 @@ extern "C" int pt_multi_render_batch(pt_multi* m, uint32_t spp, uint32_t subfram
 
 extern "C" int pt_multi_render_regions(pt_multi* m, const pt_region* regions, uint32_t n, const pt_variant* variant, uint32_t gather_mask, uint32_t* host_rgba8) {
     if (!m || (!regions && n)) return PT_ERR_INVALID;
+    if (!m->ctx.empty() && m->ctx[0]->vw.n) return mfail(m, PT_ERR_UNSUPPORTED, "pt_multi_render_regions: not with viewports set (pt_multi_set_views)");
     return multi_render_common(m, 0, 0, 1, regions, n, variant, gather_mask, host_rgba8, "pt_multi_render_regions");
 }
 

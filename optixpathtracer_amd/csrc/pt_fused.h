@@ -39,9 +39,9 @@ struct PathLoopArgs {
 #ifndef PT_FUSED_WAVES
 #define PT_FUSED_WAVES PT8_WAVES_PER_EU
 #endif
-template <int MODE>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_FUSED_WAVES, PT_FUSED_WAVES)))
-k_path_loop(PathLoopArgs A) {
+// VIEWS: the pool's paths take the camera of their pixel's view (generate_path<true>); k_path_loop itself stays the code it was
+template <int MODE, bool VIEWS>
+PT_DEV void path_loop(const PathLoopArgs A, const ViewParams vp) {
     __shared__ uint32_t s_q[4]; // [0] entries of the next window, [1] shaded hits that continue (incl. those past the depth cutoff), [2] shadow entries
     __shared__ float s_u8[256];
     const uint32_t lane = threadIdx.x;
@@ -76,7 +76,7 @@ k_path_loop(PathLoopArgs A) {
             }
             for (uint32_t k = lane; k < avail; k += 64u) {
                 const uint32_t i = first + k, pos = woff + n_cur + k;
-                generate_path(t.st, A.fp, A.bp, i, pos);
+                generate_path<VIEWS>(t.st, A.fp, A.bp, i, pos, vp);
                 t.st.thr[pos] = make_float4(1.f, 1.f, 1.f, 1.f); // pathThroughput = 1, rayEta = 1 (deviceProgram.cu:379-380): k_shade's `first` launch does not read it
                 t.queue.base[pos] = i;
             }
@@ -135,4 +135,15 @@ k_path_loop(PathLoopArgs A) {
         atomicAdd(&A.totals[1], c_s);
         atomicAdd(&A.totals[3], c_h);
     }
+}
+template <int MODE>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_FUSED_WAVES, PT_FUSED_WAVES)))
+k_path_loop(PathLoopArgs A) {
+    path_loop<MODE, false>(A, ViewParams{});
+}
+// frames with viewports (pt_set_views)
+template <int MODE>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_FUSED_WAVES, PT_FUSED_WAVES)))
+k_path_loop_views(PathLoopArgs A, ViewParams vp) {
+    path_loop<MODE, true>(A, vp);
 }

@@ -63,6 +63,32 @@ struct FrameParams { // LaunchParams (LaunchParams.h:51-79) minus the OptiX hand
     uint32_t spp; // samples_per_launch
     DevProbe probe;
 };
+// viewports (pt_set_views): the view of each 8x8 block of the frame (0xffff: none) and the view records.  An argument of the *_views
+// kernels only; the kernels of a frame without views do not know it.
+struct ViewParams {
+    const uint16_t* vblock;
+    const pt_view* views;
+    uint32_t nbx; // blocks per row of the frame
+};
+
+// What the raygen prologue and the backplate of the epilogue need of frame pixel (x, y): its coordinates in its camera's image, that image's
+// size and the camera.  VIEWS = false: the frame's single camera (the code k_generate / k_resolve always had).  VIEWS = true: the view of
+// the pixel's block — pt_set_views put origins on the block grid and refused shared pixels, so a block touches at most one view, and the
+// pixel lists of a frame with views hold view pixels only.
+struct PixelCamera {
+    uint32_t x, y;
+    int width, height;
+    v3 eye, U, V, W;
+};
+template <bool VIEWS>
+PT_DEV PixelCamera pixel_camera(const FrameParams& fp, const ViewParams& vp, uint32_t x, uint32_t y) {
+    if (VIEWS) {
+        const pt_view v = vp.views[vp.vblock[(y >> 3) * vp.nbx + (x >> 3)]];
+        return PixelCamera{x - (uint32_t)v.x, y - (uint32_t)v.y, v.width, v.height, mk3(v.eye[0], v.eye[1], v.eye[2]), mk3(v.U[0], v.U[1], v.U[2]),
+                           mk3(v.V[0], v.V[1], v.V[2]), mk3(v.W[0], v.W[1], v.W[2])};
+    }
+    return PixelCamera{x, y, fp.width, fp.height, fp.eye, fp.U, fp.V, fp.W};
+}
 
 struct BatchParams {
     const uint32_t* pixels; // x | y << 16 for the pixels of this chunk
@@ -162,20 +188,22 @@ PT_DEV uint32_t qreader_get(const QView& q, const uint32_t* s_prefix, uint32_t i
 // ------------------------------------------------------------------ generate
 // raygen prologue of path i (sample-major over the chunk's pixel list): the camera ray and random state go to position `pos` of the
 // queue-order arrays (k_generate: pos = i, the identity queue), what is summed per path to slot i
-PT_DEV void generate_path(const PathState& st, const FrameParams& fp, const BatchParams& bp, uint32_t i, uint32_t pos) {
+template <bool VIEWS = false>
+PT_DEV void generate_path(const PathState& st, const FrameParams& fp, const BatchParams& bp, uint32_t i, uint32_t pos, const ViewParams& vp = ViewParams{}) {
     const uint32_t vl = i / bp.npix, pix = i - vl * bp.npix;
     const uint32_t xy = bp.pixels[pix];
-    const uint32_t x = xy & 0xffffu, y = xy >> 16;
+    const PixelCamera cam = pixel_camera<VIEWS>(fp, vp, xy & 0xffffu, xy >> 16);
+    const uint32_t x = cam.x, y = cam.y;
     const uint32_t v = bp.s0 + vl, sub = v / fp.spp, sl = v - sub * fp.spp; // sample sl of subframe subframe_index + sub
-    uint32_t seed = tea4(y * (uint32_t)fp.width + x, fp.subframe_index + sub);
+    uint32_t seed = tea4(y * (uint32_t)cam.width + x, fp.subframe_index + sub);
     for (uint32_t k = 0; k < 2u * sl; ++k) lcg(seed); // earlier samples drew 2 rnd() each (:388)
     Rng r;
     r.init(seed); // prd.rand = Random(seed) BEFORE the jitter draws (:375-376)
     const float jx = rnd(seed), jy = rnd(seed);
-    const float dx = 2.0f * (((float)x + jx) / (float)fp.width) - 1.0f;
-    const float dy = 2.0f * (((float)y + jy) / (float)fp.height) - 1.0f;
-    const v3 dir = normalize3(add3(add3(scl3(fp.U, dx), scl3(fp.V, dy)), fp.W));
-    st.rayO[pos] = make_float4(fp.eye.x, fp.eye.y, fp.eye.z, 0.001f);
+    const float dx = 2.0f * (((float)x + jx) / (float)cam.width) - 1.0f;
+    const float dy = 2.0f * (((float)y + jy) / (float)cam.height) - 1.0f;
+    const v3 dir = normalize3(add3(add3(scl3(cam.U, dx), scl3(cam.V, dy)), cam.W));
+    st.rayO[pos] = make_float4(cam.eye.x, cam.eye.y, cam.eye.z, 0.001f);
     st.rayD[pos] = make_float4(dir.x, dir.y, dir.z, 1e16f);
     st.rf[pos] = make_uint4(r.seed1, r.seed2, 0u, 0u);
     st.pflags[i] = 0u;
@@ -195,6 +223,12 @@ __global__ void __launch_bounds__(256) k_generate(PathState st, FrameParams fp, 
     const uint32_t total = bp.npix * bp.S;
     if (blockIdx.x == 0 && threadIdx.x == 0) *qcount0 = total;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) generate_path(st, fp, bp, i, i);
+}
+// the same for a frame with viewports (pt_set_views): every path takes the camera of its pixel's view
+__global__ void __launch_bounds__(256) k_generate_views(PathState st, FrameParams fp, BatchParams bp, uint32_t* qcount0, ViewParams vp) {
+    const uint32_t total = bp.npix * bp.S;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *qcount0 = total;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) generate_path<true>(st, fp, bp, i, i, vp);
 }
 
 // ------------------------------------------------------------------ shade
@@ -587,8 +621,9 @@ PT_DEV void record_moments(float4* __restrict__ moments, size_t image_index, v3 
 // completed at least one subframe (all five, with the values of the last completed one).
 // MOMENTS (k_resolve_moments, pt_render_adaptive only): per pixel {n, s1, s2, 0} of the luminance of the value that enters the blend.  The
 // flag is a template parameter so that k_resolve itself stays the code it was.
-template <bool MOMENTS>
-PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const BatchParams& bp, float4* __restrict__ moments) {
+// VIEWS (k_resolve_views, frames with viewports): the backplate's ray is the one of the pixel's view; the buffers are indexed by frame pixel.
+template <bool MOMENTS, bool VIEWS = false>
+PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const BatchParams& bp, float4* __restrict__ moments, const ViewParams& vp = ViewParams{}) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= bp.npix) return;
     v3 result = mk3(0.f), alpha = mk3(0.f), normal = mk3(0.f), albedo = mk3(0.f);
@@ -601,8 +636,9 @@ PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const Batc
         albedo = mk3(al.x, al.y, al.z);
     }
     const uint32_t xy = bp.pixels[pix];
-    const uint32_t x = xy & 0xffffu, y = xy >> 16;
-    const size_t image_index = (size_t)y * fp.width + x;
+    const size_t image_index = (size_t)(xy >> 16) * fp.width + (xy & 0xffffu);
+    const PixelCamera cam = pixel_camera<VIEWS>(fp, vp, xy & 0xffffu, xy >> 16);
+    const uint32_t x = cam.x, y = cam.y;
     const float spp = (float)fp.spp;
     bool have = false; // a subframe was completed in this pass
     v3 accum_cur = mk3(0.f), normal_fin = mk3(0.f), albedo_fin = mk3(0.f);
@@ -635,12 +671,12 @@ PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const Batc
         albedo_fin = div3s(albedo, spp);
         alpha = div3s(alpha, spp);
         // backplate of the LAST sample's camera ray (:410)
-        uint32_t seed = tea4(y * (uint32_t)fp.width + x, subframe_index);
+        uint32_t seed = tea4(y * (uint32_t)cam.width + x, subframe_index);
         for (uint32_t k = 0; k < 2u * (fp.spp - 1u); ++k) lcg(seed);
         const float jx = rnd(seed), jy = rnd(seed);
-        const float dx = 2.0f * (((float)x + jx) / (float)fp.width) - 1.0f;
-        const float dy = 2.0f * (((float)y + jy) / (float)fp.height) - 1.0f;
-        const v3 dir = normalize3(add3(add3(scl3(fp.U, dx), scl3(fp.V, dy)), fp.W));
+        const float dx = 2.0f * (((float)x + jx) / (float)cam.width) - 1.0f;
+        const float dy = 2.0f * (((float)y + jy) / (float)cam.height) - 1.0f;
+        const v3 dir = normalize3(add3(add3(scl3(cam.U, dx), scl3(cam.V, dy)), cam.W));
         float pu, pv;
         probe_dir_to_uv(dir, pu, pv);
         const float4 bpx = probe_eval(fp.probe, pu, pv);
@@ -682,6 +718,14 @@ PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const Batc
 __global__ void __launch_bounds__(256) k_resolve(PathState st, FrameParams fp, BatchParams bp) { resolve_pixel<false>(st, fp, bp, nullptr); }
 __global__ void __launch_bounds__(256) k_resolve_moments(PathState st, FrameParams fp, BatchParams bp, float4* __restrict__ moments) {
     resolve_pixel<true>(st, fp, bp, moments);
+}
+__global__ void __launch_bounds__(256) k_resolve_views(PathState st, FrameParams fp, BatchParams bp, ViewParams vp) { resolve_pixel<false, true>(st, fp, bp, nullptr, vp); }
+// pt_set_view_cameras_device: n x 12 floats (eye, U, V, W) of the caller's device array into the camera part of the view records
+__global__ void __launch_bounds__(256) k_view_cameras(const float* __restrict__ cams, uint32_t n, pt_view* __restrict__ views) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * 12u) return;
+    const uint32_t v = i / 12u, k = i - v * 12u;
+    reinterpret_cast<float*>(views + v)[4u + k] = cams[i]; // x, y, width, height, then the twelve camera floats
 }
 
 // ------------------------------------------------------------------ foveated variant (HelloPathtracing_sv4_vmv23/)

@@ -154,6 +154,40 @@ def _mesh_transforms(transforms):
     return arr, len(pairs)
 
 
+def _view_array(views):
+    """pt_view[] for [(x, y, width, height, Camera), ...]: the camera's U, V, W are those setCamera would give it (take the view's own aspect)."""
+    arr = (_lib.View * max(1, len(views)))()
+    for k, (x, y, w, h, cam) in enumerate(views):
+        U, V, W = cam.UVWFrame()
+        arr[k].x, arr[k].y, arr[k].width, arr[k].height = int(x), int(y), int(w), int(h)
+        for name, val in (("eye", cam.eye), ("U", U), ("V", V), ("W", W)):
+            getattr(arr[k], name)[:] = [float(c) for c in val]
+    return arr
+
+
+def _camera_rows(cameras) -> np.ndarray:
+    """(n, 12) float32 rows eye, U, V, W for a list of Cameras or an array-like of that shape."""
+    if len(cameras) and isinstance(cameras[0], Camera):
+        cameras = [np.concatenate([np.asarray(c.eye, np.float32), *c.UVWFrame()]) for c in cameras]
+    rows = np.ascontiguousarray(cameras, np.float32)
+    if rows.ndim != 2 or rows.shape[1] != 12:
+        raise ValueError(f"setViewCameras: n cameras or an (n, 12) array (eye, U, V, W) is expected, got shape {rows.shape}")
+    return rows
+
+
+def _is_torch_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _views_list(L, ctx):
+    n = C.c_uint32()
+    L.pt_get_views(ctx, None, 0, C.byref(n))
+    arr = (_lib.View * max(1, n.value))()
+    L.pt_get_views(ctx, arr, n.value, None)
+    return [dict(x=v.x, y=v.y, width=v.width, height=v.height, eye=np.array(v.eye, np.float32), U=np.array(v.U, np.float32),
+                 V=np.array(v.V, np.float32), W=np.array(v.W, np.float32)) for v in arr[:n.value]]
+
+
 class SampleRenderer:
     def __init__(self, model: Model, device: int = 0):
         self._device = int(device)
@@ -233,6 +267,34 @@ class SampleRenderer:
     def setCameraUVW(self, eye, U, V, W):
         f3 = C.c_float * 3
         self._ck(self._L.pt_set_camera(self._ctx, C.byref(f3(*[float(x) for x in eye])), C.byref(f3(*[float(x) for x in U])), C.byref(f3(*[float(x) for x in V])), C.byref(f3(*[float(x) for x in W]))), "pt_set_camera")
+
+    # -- viewports (pt_set_views, include/pt_amd.h): several cameras in rectangles of one frame
+    def setViews(self, views):
+        """[(x, y, width, height, Camera), ...] after resize(): every render call then fills each rectangle as a frame of its own size with
+        its own camera would be filled, in one batch; pixels in no view are left alone.  [] returns to the single camera of setCamera."""
+        views = list(views)
+        self._ck(self._L.pt_set_views(self._ctx, _view_array(views) if views else None, len(views)), "pt_set_views")
+
+    def views(self):
+        """The current views as dicts x, y, width, height, eye, U, V, W (pt_get_views)."""
+        return _views_list(self._L, self._ctx)
+
+    def setViewCameras(self, cameras):
+        """New cameras for the current views, rectangles unchanged (the per-frame call): a list of Cameras, an (n, 12) array of eye, U, V, W
+        rows, or a CUDA float32 torch tensor of that shape on the context's GPU, which is read on the device (pt_set_view_cameras_device)."""
+        if _is_torch_tensor(cameras):
+            import torch
+
+            t = cameras
+            if not t.is_cuda or (t.device.index or 0) != self._device:
+                raise ValueError(f"setViewCameras: the tensor is on {t.device}, the context on GPU {self._device}")
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous():
+                raise ValueError(f"setViewCameras: a contiguous float32 (n, 12) tensor is expected, got {t.dtype} {tuple(t.shape)}")
+            torch.cuda.current_stream(t.device).synchronize()  # the library reads on its own stream: what torch enqueued must be complete
+            self._ck(self._L.pt_set_view_cameras_device(self._ctx, t.data_ptr(), t.shape[0]), "pt_set_view_cameras_device")
+            return
+        rows = _camera_rows(cameras)
+        self._ck(self._L.pt_set_view_cameras(self._ctx, rows.ctypes.data, rows.shape[0]), "pt_set_view_cameras")
 
     def setProbe(self, probe: ProbeData):
         if not probe.valid:
@@ -647,6 +709,22 @@ class MultiRenderer:
         U, V, W = camera.UVWFrame()
         f3 = C.c_float * 3
         self._ck(self._L.pt_multi_set_camera(self._m, C.byref(f3(*[float(x) for x in camera.eye])), C.byref(f3(*[float(x) for x in U])), C.byref(f3(*[float(x) for x in V])), C.byref(f3(*[float(x) for x in W]))), "pt_multi_set_camera")
+
+    def setViews(self, views):
+        """SampleRenderer.setViews on every rank (pt_multi_set_views), after resize(): each rank renders the view pixels of its own blocks."""
+        views = list(views)
+        self._ck(self._L.pt_multi_set_views(self._m, _view_array(views) if views else None, len(views)), "pt_multi_set_views")
+
+    def views(self):
+        return _views_list(self._L, C.c_void_p(self._L.pt_multi_ctx(self._m, 0)))
+
+    def setViewCameras(self, cameras):
+        """SampleRenderer.setViewCameras on every rank (pt_multi_set_view_cameras).  The ranks may sit on different GPUs, so a torch tensor
+        is copied to the host once and handed to every rank from there."""
+        if _is_torch_tensor(cameras):
+            cameras = cameras.detach().cpu().numpy()
+        rows = _camera_rows(cameras)
+        self._ck(self._L.pt_multi_set_view_cameras(self._m, rows.ctypes.data, rows.shape[0]), "pt_multi_set_view_cameras")
 
     def updateMeshes(self, vertices: dict, rebuild: bool = False) -> float:
         """SampleRenderer.updateMeshes on every rank (pt_multi_update_meshes); returns the slowest rank's kernel ms."""
