@@ -18,7 +18,7 @@
  * hipStreamNonBlocking: they do NOT synchronise with the null stream or with any stream of the
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
- * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device — read and write them on
+ * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -32,7 +32,9 @@
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
  * prefix) instead of pt_get_stats, which writes sizeof(pt_stats) of the LIBRARY's header
  * (pt_stats_size()).  0.2 -> 0.4: pt_stats grew by bvh_builder + reserved_ (8 bytes), pt_multi_stats by
- * enqueue_ms, threads, frames_handed_over.
+ * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
+ * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
+ * its camera setters, pt_render_gbuffer.  A caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -590,6 +592,61 @@ typedef struct pt_query_stats {
 } pt_query_stats;
 int pt_trace_device(pt_ctx* ctx, const float* dev_rays, uint32_t n, uint32_t flags /* pt_query_flags */, void* dev_out, pt_query_stats* stats /* may be NULL */);
 int pt_query_wait(pt_ctx* ctx, pt_query_stats* stats /* may be NULL */);
+
+/* FIRST-HIT G-BUFFER (no reference counterpart): what lies under the centre of every pixel of the frame, under the frame's camera or under
+ * each view's (pt_set_views) — ids, barycentrics and normal, depth, position, screen-space motion against the previous frame's cameras —
+ * written by one kernel into the caller's DEVICE planes.  What a synthetic-data pipeline stores beside the colour image, and what a
+ * head-mounted display loop or a temporal filter reprojects with.
+ * The ray of a pixel.  Frame pixel (X, Y) has local coordinates (x, y) in its camera: the frame's, or with views the camera of the pixel's
+ * view (x = X - v.x, y = Y - v.y, width and height the view's).  The ray is the raygen prologue's with both jitter values replaced by 0.5f:
+ *     dx = 2 * ((x + 0.5f) / width) - 1;  dy = 2 * ((y + 0.5f) / height) - 1;  dir = normalize3((U * dx + V * dy) + W)
+ *     origin eye, tmin 0.001f, tmax 1e16f
+ * float32, one rounding per operation, no fused multiply-add, dot = (x*x + y*y) + z*z, normalize3(v) = v * (1 / sqrt(dot(v, v))): float32
+ * NumPy evaluating this reproduces the `ray` plane bit for bit.
+ * Planes (caller-owned device memory of the context's device, frame-sized, indexed Y * width + X in frame coordinates; any subset, NULL =
+ * not wanted).  With (t, leaf) the closest hit of that ray as pt_trace defines it:
+ *   - ray:      the eight words o.xyz, tmin, d.xyz, tmax — pt_trace_device's ray layout;
+ *   - hit:      the pt_hit that pt_trace_device(PT_QUERY_CLOSEST) returns for that ray, all eight words (a miss: t = 1e16f, prim = mesh = -1,
+ *               the rest 0);
+ *   - depth:    t * dot3(dir, normalize3(W)), the distance along the viewing axis; a miss holds +inf (0x7f800000);
+ *   - position: (o.x + t*dir.x, o.y + t*dir.y, o.z + t*dir.z, 1.0f); a miss holds four zeros;
+ *   - motion:   where this surface point was in the previous image minus where it is now, in pixels of the pixel's own camera rectangle.
+ *               With the previous camera (e', U', V', W') of the pixel's view (of the frame without views), q = position - e' for a hit and
+ *               q = dir for a miss (the environment is a point at infinity):
+ *                   a = dot3(q, cross3(V', W'));  b = dot3(q, cross3(W', U'));  c = dot3(q, cross3(U', V'));  det = dot3(U', cross3(V', W'))
+ *                   px = (((a / c) + 1) * 0.5f) * width - 0.5f;  py = (((b / c) + 1) * 0.5f) * height - 0.5f
+ *                   motion = (px - (float)x, py - (float)y)
+ *               When c * det > 0 is false (behind the previous camera, c == 0, a NaN) both words are 0x7fc00000.  Motion is camera motion
+ *               over the CURRENT geometry; it knows nothing of geometry that moved.
+ * Which pixels: those a pt_render_mask with the same mask would render — the rank's owned pixels (pt_set_partition), view pixels only while
+ * views are set, whole blocks of block_mask (NULL: every block).  A pixel outside that set is not written in any plane.  Zero active
+ * pixels launch nothing and return PT_OK.
+ * Pointers and streams: each plane is checked as pt_trace_device checks its arrays (known to HIP, device memory of the context's device,
+ * 4-byte aligned, fitting what is left of its allocation) and the planes may not overlap one another; they are written on pt_stream(ctx)
+ * under the STREAM CONTRACT.  No wider alignment than 4 bytes is assumed (records are written with 16-byte stores at whatever address they have).
+ * prev_cameras and block_mask are HOST memory.
+ * Ordering and state: the call first waits for the frames in flight and completes queued queries, and is complete when it returns.  It sees
+ * the current geometry (after any pt_update_meshes*).  It neither reads nor writes the five frame buffers, the accumulation, the adaptive
+ * state, the schedule trial or the path state; pt_stats is as it was.  The traversal's stack-overflow bit gives PT_ERR_UNSUPPORTED, as in
+ * pt_trace.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; all five
+ * planes NULL; a plane that fails the pointer checks or overlaps another plane; motion without prev_cameras; num_prev_cameras different
+ * from max(1, view count) when prev_cameras is given; a non-finite previous camera value.
+ * stats: pixels written; hits among them; device time of the pass (hipEvents; the mask compaction included when there is a mask).
+ * Not part of this interface: an asynchronous variant, a pt_multi_* wrapper (per-rank calls through pt_multi_ctx work), G-buffers of the
+ * foveated launches, object-space motion. */
+typedef struct pt_gbuffer_desc {
+    void*  hit;       /* width*height x pt_hit (32 B)            or NULL */
+    float* depth;     /* width*height x f32                      or NULL */
+    float* position;  /* width*height x 4 f32                    or NULL */
+    float* motion;    /* width*height x 2 f32                    or NULL */
+    float* ray;       /* width*height x 8 f32 (pt_trace_device's ray layout) or NULL */
+    const float*   prev_cameras;     /* HOST, n x 12 (eye,U,V,W); required iff motion != NULL */
+    uint32_t       num_prev_cameras; /* 1 without views, else the view count */
+    const uint8_t* block_mask;       /* HOST, nbx*nby bytes as pt_render_mask, or NULL = every block */
+} pt_gbuffer_desc;
+typedef struct pt_gbuffer_stats { uint64_t pixels, hits; double kernel_ms; } pt_gbuffer_stats;
+int pt_render_gbuffer(pt_ctx* ctx, const pt_gbuffer_desc* desc, pt_gbuffer_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

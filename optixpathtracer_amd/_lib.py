@@ -25,7 +25,7 @@ EXPORTS = [
     "pt_update_meshes", "pt_multi_update_meshes",
     "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
-    "pt_trace_device", "pt_query_wait",
+    "pt_trace_device", "pt_query_wait", "pt_render_gbuffer",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -60,6 +60,22 @@ class QueryStats(C.Structure):  # pt_query_stats
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GBufferDesc(C.Structure):  # pt_gbuffer_desc
+    _fields_ = [("hit", C.c_void_p), ("depth", C.c_void_p), ("position", C.c_void_p), ("motion", C.c_void_p), ("ray", C.c_void_p),
+                ("prev_cameras", C.c_void_p), ("num_prev_cameras", C.c_uint32), ("block_mask", C.c_void_p)]
+
+
+class GBufferStats(C.Structure):  # pt_gbuffer_stats
+    _fields_ = [("pixels", C.c_uint64), ("hits", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_render_gbuffer: float32 words per pixel
+GBUFFER_PLANES = {"hit": 8, "depth": 1, "position": 4, "motion": 2, "ray": 8}
 
 
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
@@ -265,6 +281,7 @@ def load_library() -> C.CDLL:
     L.pt_download_adaptive.argtypes = [vp, i, vp, C.c_size_t]
     L.pt_trace_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(QueryStats)]
     L.pt_query_wait.argtypes = [vp, C.POINTER(QueryStats)]
+    L.pt_render_gbuffer.argtypes = [vp, C.POINTER(GBufferDesc), C.POINTER(GBufferStats)]
     L.pt_set_views.argtypes = [vp, C.POINTER(View), u32]
     L.pt_get_views.argtypes = [vp, C.POINTER(View), u32, C.POINTER(u32)]
     L.pt_set_view_cameras.argtypes = [vp, vp, u32]

@@ -281,6 +281,15 @@ class SampleRenderer {
         ck(pt_query_wait(ctx, &s));
         return s;
     }
+    // The first hit under every pixel's centre, under the frame's camera or each view's (pt_render_gbuffer): the planes of `d` are DEVICE
+    // memory of this context's device, frame-sized, any subset; prev_cameras and block_mask are host memory.  Synchronous; the frame buffers
+    // and the accumulation are left alone.  Returns the pixels written, the hits among them and the device time of the pass.
+    pt_gbuffer_stats renderGBuffer(const pt_gbuffer_desc& d, pt_gbuffer_stats* stats = nullptr) {
+        pt_gbuffer_stats s{};
+        ck(pt_render_gbuffer(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;

@@ -141,6 +141,18 @@ def _check_query_tensor(name, t, device: int, dtype, tail: tuple):
         raise ValueError(f"traceDevice: {name}: a contiguous {dtype} tensor of shape (n{''.join(f', {k}' for k in tail)}) is expected, got {t.dtype} {tuple(t.shape)}")
 
 
+def _check_gbuffer_tensor(name, t, device: int, shape: tuple):
+    """renderGBuffer: a CUDA float32 tensor on GPU `device` of exactly `shape`, dense (any storage offset) — checked before the library is called."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"renderGBuffer: {name}: a torch tensor or a device pointer is expected")
+    if not t.is_cuda or (t.device.index or 0) != device:
+        raise ValueError(f"renderGBuffer: {name}: the tensor is on {t.device}, the context on GPU {device}")
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"renderGBuffer: {name}: a contiguous torch.float32 tensor of shape {tuple(shape)} is expected, got {t.dtype} {tuple(t.shape)}")
+
+
 def _mesh_transforms(transforms):
     """pt_mesh_transform[] for {mesh_index: 3x4 or 4x4 array} (the last row of a 4x4 is dropped)."""
     pairs = _pairs(transforms)
@@ -614,6 +626,64 @@ class SampleRenderer:
         s = _lib.QueryStats()
         self._ck(self._L.pt_query_wait(self._ctx, C.byref(s)), "pt_query_wait")
         return s.as_dict()
+
+    def renderGBuffer(self, planes=("hit",), prev_cameras=None, mask=None, out=None) -> dict:
+        """The first hit under the centre of every pixel, written by one kernel into GPU tensors (pt_render_gbuffer, include/pt_amd.h).
+
+        planes: any of "hit" (h, w, 8: one 32-byte pt_hit per pixel), "depth" (h, w), "position" (h, w, 4), "motion" (h, w, 2) and "ray"
+        (h, w, 8), float32.  out: {plane: tensor} for planes the caller owns — CUDA float32 tensors of those shapes on the context's device,
+        dense, any 4-byte-aligned storage offset — or raw device pointers; the others are allocated with torch, zero-filled (pixels outside
+        the views, the mask or the rank's partition are not written).  prev_cameras, needed by "motion": the previous frame's camera — one
+        Camera or (12,) row eye, U, V, W without views, else one per view as setViewCameras takes them.  mask: 8x8 blocks as renderMask
+        takes them, None = every block.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
+        the planes are complete.  The frame buffers, the accumulation and the path state are left alone.
+        Returns {plane: tensor (None for a raw pointer), ..., "stats": {pixels, hits, kernel_ms}}."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        w, h = self.launchParams.frame.size
+        planes = tuple(planes)
+        out = dict(out or {})
+        for name in list(planes) + list(out):
+            if name not in _lib.GBUFFER_PLANES:
+                raise ValueError(f"renderGBuffer: unknown plane {name!r} (one of {', '.join(_lib.GBUFFER_PLANES)})")
+        if any(name not in planes for name in out):
+            raise ValueError("renderGBuffer: `out` names a plane that `planes` does not")
+        desc = _lib.GBufferDesc()
+        result = {}
+        for name in planes:
+            k = _lib.GBUFFER_PLANES[name]
+            t = out.get(name)
+            if t is None:
+                t = torch.zeros((h, w) if name == "depth" else (h, w, k), dtype=torch.float32, device=f"cuda:{dev}")
+            if isinstance(t, int):
+                ptr, result[name] = t, None
+            else:
+                _check_gbuffer_tensor(name, t, dev, (h, w) if name == "depth" else (h, w, k))
+                ptr, result[name] = t.data_ptr(), t
+            setattr(desc, name, ptr)
+        rows = None
+        if prev_cameras is not None:
+            if isinstance(prev_cameras, Camera) or (len(prev_cameras) == 12 and not isinstance(prev_cameras[0], Camera) and np.ndim(prev_cameras) == 1):
+                prev_cameras = [prev_cameras]  # one camera, or one (12,) row
+            rows = _camera_rows(prev_cameras)
+            desc.prev_cameras = rows.ctypes.data
+            desc.num_prev_cameras = rows.shape[0]
+        m = None
+        if mask is not None:
+            nby, nbx = self.blockGrid()
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.size != nby * nbx:
+                raise ValueError(f"renderGBuffer: the mask needs {nby} x {nbx} entries, got {m.size}")
+            desc.block_mask = m.ctypes.data
+        ev = torch.cuda.Event()  # what torch enqueued so far (a fill of the caller's planes) comes first, on the device
+        ev.record(torch.cuda.current_stream(dev))
+        self.waitEvent(ev.cuda_event)
+        stats = _lib.GBufferStats()
+        self._ck(self._L.pt_render_gbuffer(self._ctx, C.byref(desc), C.byref(stats)), "pt_render_gbuffer")
+        result["stats"] = stats.as_dict()
+        return result
 
     def evalTable(self, which, inp: np.ndarray, out_width: int, material=None, bsdf_mode=PT_BSDF_DISNEY) -> np.ndarray:
         inp = np.ascontiguousarray(inp, np.float32)
