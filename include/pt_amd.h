@@ -18,7 +18,7 @@
  * hipStreamNonBlocking: they do NOT synchronise with the null stream or with any stream of the
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
- * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer — read and write them on
+ * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -34,7 +34,7 @@
  * (pt_stats_size()).  0.2 -> 0.4: pt_stats grew by bvh_builder + reserved_ (8 bytes), pt_multi_stats by
  * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
- * its camera setters, pt_render_gbuffer.  A caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
+ * its camera setters, pt_render_gbuffer, pt_temporal_accumulate.  A caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -647,6 +647,76 @@ typedef struct pt_gbuffer_desc {
 } pt_gbuffer_desc;
 typedef struct pt_gbuffer_stats { uint64_t pixels, hits; double kernel_ms; } pt_gbuffer_stats;
 int pt_render_gbuffer(pt_ctx* ctx, const pt_gbuffer_desc* desc, pt_gbuffer_stats* stats /* may be NULL */);
+
+/* TEMPORAL ACCUMULATION (no reference counterpart): reproject last frame's accumulated colour to where each surface point was, check that it
+ * is the same surface, blend with a per-pixel history length, restart only the pixels that were disoccluded.  With pt_render_gbuffer in front
+ * (hit, position, motion) and pt_denoise behind, a complete reproject / accumulate / filter chain for cameras that move every frame; it works
+ * per view.  The call is stateless: every plane is caller-owned DEVICE memory of the context's device, frame-sized, indexed Y * width + X, and
+ * checked exactly as pt_render_gbuffer checks its planes (known to HIP, device memory of the context's device, 4-byte aligned — no wider
+ * alignment is assumed — fitting what is left of its allocation).  A pointer obtained from pt_device_buffer is accepted like any other.
+ * Which pixels: exactly those pt_render_gbuffer would write with the same mask — the rank's owned pixels, view pixels only while views are
+ * set, whole blocks of block_mask (HOST memory, NULL: every block).  No other pixel is written in any output.  Zero pixels launch nothing
+ * and return PT_OK.
+ * Each pixel works inside its own rectangle (x0, y0, wr, hr): its view (found by the pixel's 8x8 block), or the whole frame without views;
+ * (x, y) are its local coordinates there.  Arithmetic per pixel p — float32 throughout, one rounding per operation, no fused multiply-add,
+ * in exactly this order, dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; float32 NumPy evaluating this reproduces every output bit for bit:
+ *   1. c = color[p].xyz * color_scale.  With PT_TEMPORAL_CLEAR_COLOR the four words of color[p] become 0 after the read.
+ *   2. px = (float)x + motion[p].x;  py = (float)y + motion[p].y.  The lookup fails when (px >= -1 && px <= wr && py >= -1 && py <= hr) is
+ *      false (a NaN motion word fails this way).  Otherwise flx = floorf(px), ix = (int)flx, fx = px - flx, likewise fly, iy, fy;
+ *      wx0 = 1 - fx, wx1 = fx, wy0 = 1 - fy, wy1 = fy; tap weights w_ij = wx_i * wy_j.
+ *   3. Tap (i, j) is frame pixel q = (x0 + ix + i, y0 + iy + j).  It counts when it lies inside the rectangle, w_ij > 0, length_in[q] >= 1,
+ *      the three colour words of history_in[q] are finite (exponent-bit test) and the geometry agrees: with hit[p].prim < 0 (a miss) it
+ *      needs prev_hit[q].prim < 0; otherwise prev_hit[q].mesh == hit[p].mesh, dot3(ng_p, ng_q) >= normal_cos and
+ *      fabsf(dot3(ng_p, prev_position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t.
+ *   4. Tap order (0,0), (1,0), (0,1), (1,1); a tap that does not count contributes +0.0f.  Wsum = ((w00 + w10) + w01) + w11; Hsum the same
+ *      sum of w_ij * history_in[q] per component; nprev the minimum of length_in[q] over the counting taps;
+ *      valid = (at least one tap counts) && Wsum >= min_weight.
+ *   5. Valid: H = Hsum / Wsum; n = fminf(nprev, (float)(max_history - 1)); a = 1.0f / (n + 1.0f); out = H + (c - H) * a; len = n + 1.
+ *      Otherwise out = c, len = 1.
+ *   6. history_out[p] = (out, 1.0f); length_out[p] = len; frame_rgba8[p] = make_color(out); copy_out[p] = (out, 1.0f);
+ *      stats->reprojected counts the valid pixels.
+ * Overlap: each of the four outputs may overlap no other plane (the kernel gathers neighbours, so the caller ping-pongs history and
+ * length); color may overlap no other plane; the read-only planes may alias one another (prev_hit == hit, say).
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; a required
+ * plane NULL (all but frame_rgba8, copy_out and block_mask); a plane that fails the pointer checks; a forbidden overlap; unknown flag bits; a
+ * parameter out of its range or not finite.
+ * Ordering and state, as pt_render_gbuffer: the call first waits for the frames in flight and completes queued queries, runs on
+ * pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns; the previous planes must be complete before the call.  It reads
+ * and writes no context state except through the pointers the caller passed: the frame buffers, the accumulation, the adaptive state, the
+ * schedule trial and pt_stats are as they were.  A partitioned context needs no special case: pixels the rank never wrote keep
+ * length_in == 0, so those taps do not count, and a caller that all-gathers history and length gets a seamless image.
+ * Per-frame colour recipe.  The resolve of subframe k > 0 leaves prev + (clamp(c) - prev) / (k + 1) in the accumulation buffer.  To hand this
+ * pass one frame's colour: color = pt_device_buffer(PT_BUF_ACCUM), color_scale = (float)(k + 1) (1 for the frame rendered at subframe 0), and
+ * PT_TEMPORAL_CLEAR_COLOR so that the next frame's blend starts from zero.  Seeds then differ from frame to frame, and the recipe works with
+ * views, masks and partitions; the recovered colour differs from the frame's own by two roundings.  Without views, a full-frame
+ * pt_render_regions launch with redraw = 1 is the exact alternative.
+ * stats: pixels processed; valid pixels among them; device time of the pass (hipEvents; the mask compaction included when there is a mask).
+ * Not part of this interface: an asynchronous variant, a pt_multi_* wrapper, variance estimates, motion of moving geometry (the motion
+ * plane is camera motion only), any change to pt_denoise. */
+enum pt_temporal_flags { PT_TEMPORAL_CLEAR_COLOR = 1 };
+typedef struct pt_temporal_desc {
+    float* color;              /* w*h x 4  this frame's colour; read, and zeroed afterwards with PT_TEMPORAL_CLEAR_COLOR */
+    const float* motion;       /* w*h x 2  pt_render_gbuffer's motion plane of this frame */
+    const void*  hit;          /* w*h x pt_hit, this frame */
+    const float* position;     /* w*h x 4, this frame */
+    const void*  prev_hit;     /* previous frame's hit plane */
+    const float* prev_position;
+    const float* history_in;   /* w*h x 4  accumulated colour after the previous frame */
+    const float* length_in;    /* w*h f32  per-pixel history length (whole numbers; 0 = no history) */
+    float* history_out;        /* w*h x 4 */
+    float* length_out;         /* w*h */
+    uint32_t* frame_rgba8;     /* w*h or NULL: make_color(out) */
+    float* copy_out;           /* w*h x 4 or NULL: a second copy of (out,1), e.g. pt_device_buffer(PT_BUF_COLOR) for pt_denoise */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    float color_scale;         /* finite, > 0 */
+    float normal_cos;          /* [-1,1] */
+    float plane_eps;           /* finite, >= 0 */
+    float min_weight;          /* [0,1] */
+    uint32_t max_history;      /* 1..65535 */
+    uint32_t flags;            /* PT_TEMPORAL_CLEAR_COLOR = 1 */
+} pt_temporal_desc;
+typedef struct pt_temporal_stats { uint64_t pixels, reprojected; double kernel_ms; } pt_temporal_stats;
+int pt_temporal_accumulate(pt_ctx* ctx, const pt_temporal_desc* desc, pt_temporal_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

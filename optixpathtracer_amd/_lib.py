@@ -25,7 +25,7 @@ EXPORTS = [
     "pt_update_meshes", "pt_multi_update_meshes",
     "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
-    "pt_trace_device", "pt_query_wait", "pt_render_gbuffer",
+    "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -76,6 +76,29 @@ class GBufferStats(C.Structure):  # pt_gbuffer_stats
 
 # the planes of pt_render_gbuffer: float32 words per pixel
 GBUFFER_PLANES = {"hit": 8, "depth": 1, "position": 4, "motion": 2, "ray": 8}
+
+PT_TEMPORAL_CLEAR_COLOR = 1  # pt_temporal_flags
+
+
+class TemporalDesc(C.Structure):  # pt_temporal_desc
+    _fields_ = [("color", C.c_void_p), ("motion", C.c_void_p), ("hit", C.c_void_p), ("position", C.c_void_p), ("prev_hit", C.c_void_p),
+                ("prev_position", C.c_void_p), ("history_in", C.c_void_p), ("length_in", C.c_void_p), ("history_out", C.c_void_p),
+                ("length_out", C.c_void_p), ("frame_rgba8", C.c_void_p), ("copy_out", C.c_void_p), ("block_mask", C.c_void_p),
+                ("color_scale", C.c_float), ("normal_cos", C.c_float), ("plane_eps", C.c_float), ("min_weight", C.c_float),
+                ("max_history", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class TemporalStats(C.Structure):  # pt_temporal_stats
+    _fields_ = [("pixels", C.c_uint64), ("reprojected", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_temporal_accumulate: 32-bit words per pixel (frame_rgba8 holds packed bytes, the others float32)
+TEMPORAL_PLANES = {"color": 4, "motion": 2, "hit": 8, "position": 4, "prev_hit": 8, "prev_position": 4, "history_in": 4, "length_in": 1,
+                   "history_out": 4, "length_out": 1, "frame_rgba8": 1, "copy_out": 4}
+TEMPORAL_OUTPUTS = ("history_out", "length_out", "frame_rgba8", "copy_out")
 
 
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
@@ -282,6 +305,7 @@ def load_library() -> C.CDLL:
     L.pt_trace_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(QueryStats)]
     L.pt_query_wait.argtypes = [vp, C.POINTER(QueryStats)]
     L.pt_render_gbuffer.argtypes = [vp, C.POINTER(GBufferDesc), C.POINTER(GBufferStats)]
+    L.pt_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalDesc), C.POINTER(TemporalStats)]
     L.pt_set_views.argtypes = [vp, C.POINTER(View), u32]
     L.pt_get_views.argtypes = [vp, C.POINTER(View), u32, C.POINTER(u32)]
     L.pt_set_view_cameras.argtypes = [vp, vp, u32]

@@ -290,6 +290,15 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // Reproject / accumulate over a moving camera (pt_temporal_accumulate): every plane of `d` is DEVICE memory of this context's device,
+    // frame-sized; block_mask is host memory.  Stateless and synchronous; the caller ping-pongs history and length.  Returns the pixels
+    // processed, those that kept their history and the device time of the pass.
+    pt_temporal_stats temporalAccumulate(const pt_temporal_desc& d, pt_temporal_stats* stats = nullptr) {
+        pt_temporal_stats s{};
+        ck(pt_temporal_accumulate(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;

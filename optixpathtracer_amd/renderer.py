@@ -153,6 +153,19 @@ def _check_gbuffer_tensor(name, t, device: int, shape: tuple):
         raise ValueError(f"renderGBuffer: {name}: a contiguous torch.float32 tensor of shape {tuple(shape)} is expected, got {t.dtype} {tuple(t.shape)}")
 
 
+def _check_temporal_tensor(name, t, device: int, shapes: dict):
+    """temporalAccumulate: a CUDA tensor on GPU `device` whose (dtype, shape) is one of `shapes`, dense (any storage offset) — checked before the library is called."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"temporalAccumulate: {name}: a torch tensor or a device pointer is expected")
+    if not t.is_cuda or (t.device.index or 0) != device:
+        raise ValueError(f"temporalAccumulate: {name}: the tensor is on {t.device}, the context on GPU {device}")
+    if shapes.get(t.dtype) != tuple(t.shape) or not t.is_contiguous():
+        want = " or ".join(f"{d} tensor of shape {sh}" for d, sh in shapes.items())
+        raise ValueError(f"temporalAccumulate: {name}: a contiguous {want} is expected, got {t.dtype} {tuple(t.shape)}")
+
+
 def _mesh_transforms(transforms):
     """pt_mesh_transform[] for {mesh_index: 3x4 or 4x4 array} (the last row of a 4x4 is dropped)."""
     pairs = _pairs(transforms)
@@ -682,6 +695,74 @@ class SampleRenderer:
         self.waitEvent(ev.cuda_event)
         stats = _lib.GBufferStats()
         self._ck(self._L.pt_render_gbuffer(self._ctx, C.byref(desc), C.byref(stats)), "pt_render_gbuffer")
+        result["stats"] = stats.as_dict()
+        return result
+
+    def temporalAccumulate(self, color, motion, hit, position, prev_hit, prev_position, history_in, length_in, history_out=None, length_out=None,
+                           frame_rgba8=None, copy_out=None, mask=None, color_scale=1.0, normal_cos=0.9, plane_eps=0.01, min_weight=0.25,
+                           max_history=32, clear_color=False) -> dict:
+        """Reprojects last frame's accumulated colour along the motion plane, keeps it where it is the same surface and blends this frame's
+        colour in with a per-pixel history length (pt_temporal_accumulate, include/pt_amd.h: the arithmetic, in full).
+
+        Every plane is a CUDA tensor on the context's device — float32 (h, w, k), dense, any 4-byte-aligned storage offset — or a raw
+        device pointer (deviceBuffer(PT_BUF_ACCUM) as `color`, deviceBuffer(PT_BUF_COLOR) as `copy_out`): color (k = 4; read, and zeroed
+        afterwards with clear_color), motion (2), hit and position (8, 4: renderGBuffer's planes of this frame), prev_hit and prev_position
+        (last frame's), history_in (4) and length_in ((h, w)): what the previous call returned.  history_out and length_out are allocated
+        with torch, zero-filled, when None (pixels outside the views, the mask or the rank's partition are not written); they may overlap
+        no other plane, so a loop ping-pongs two pairs.  frame_rgba8 (int32 (h, w) or uint8 (h, w, 4)) and copy_out (4) are optional.
+        mask: 8x8 blocks as renderMask takes them, None = every block.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
+        the outputs are complete.  The frame buffers, the accumulation and the path state are left alone (unless passed in as planes).
+        Returns {"history_out", "length_out", "frame_rgba8", "copy_out": the tensor (None for a raw pointer or an absent plane),
+        "stats": {pixels, reprojected, kernel_ms}}."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        w, h = self.launchParams.frame.size
+        if history_out is None:
+            history_out = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        if length_out is None:
+            length_out = torch.zeros((h, w), dtype=torch.float32, device=f"cuda:{dev}")
+        given = dict(color=color, motion=motion, hit=hit, position=position, prev_hit=prev_hit, prev_position=prev_position, history_in=history_in,
+                     length_in=length_in, history_out=history_out, length_out=length_out, frame_rgba8=frame_rgba8, copy_out=copy_out)
+        desc = _lib.TemporalDesc()
+        result = {}
+        for name, t in given.items():
+            k = _lib.TEMPORAL_PLANES[name]
+            optional = name in ("frame_rgba8", "copy_out")
+            if t is None:
+                if not optional:
+                    raise ValueError(f"temporalAccumulate: {name} is required")
+                ptr = None
+            elif isinstance(t, int):
+                ptr = t
+            else:
+                if name == "frame_rgba8":
+                    shapes = {torch.int32: (h, w), torch.uint8: (h, w, 4)}
+                else:
+                    shapes = {torch.float32: (h, w) if k == 1 else (h, w, k)}
+                _check_temporal_tensor(name, t, dev, shapes)
+                ptr = t.data_ptr()
+            setattr(desc, name, ptr)
+            if name in _lib.TEMPORAL_OUTPUTS:
+                result[name] = None if t is None or isinstance(t, int) else t
+        m = None
+        if mask is not None:
+            nby, nbx = self.blockGrid()
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.size != nby * nbx:
+                raise ValueError(f"temporalAccumulate: the mask needs {nby} x {nbx} entries, got {m.size}")
+            desc.block_mask = m.ctypes.data
+        desc.color_scale, desc.normal_cos, desc.plane_eps, desc.min_weight = float(color_scale), float(normal_cos), float(plane_eps), float(min_weight)
+        if not 0 <= int(max_history) < 2**32:
+            raise ValueError("temporalAccumulate: max_history must be in [1,65535]")
+        desc.max_history = int(max_history)
+        desc.flags = _lib.PT_TEMPORAL_CLEAR_COLOR if clear_color else 0
+        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
+        ev.record(torch.cuda.current_stream(dev))
+        self.waitEvent(ev.cuda_event)
+        stats = _lib.TemporalStats()
+        self._ck(self._L.pt_temporal_accumulate(self._ctx, C.byref(desc), C.byref(stats)), "pt_temporal_accumulate")
         result["stats"] = stats.as_dict()
         return result
 
