@@ -18,7 +18,7 @@
  * hipStreamNonBlocking: they do NOT synchronise with the null stream or with any stream of the
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
- * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate — read and write them on
+ * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -34,7 +34,7 @@
  * (pt_stats_size()).  0.2 -> 0.4: pt_stats grew by bvh_builder + reserved_ (8 bytes), pt_multi_stats by
  * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
- * its camera setters, pt_render_gbuffer, pt_temporal_accumulate.  A caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
+ * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes.  A caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -717,6 +717,78 @@ typedef struct pt_temporal_desc {
 } pt_temporal_desc;
 typedef struct pt_temporal_stats { uint64_t pixels, reprojected; double kernel_ms; } pt_temporal_stats;
 int pt_temporal_accumulate(pt_ctx* ctx, const pt_temporal_desc* desc, pt_temporal_stats* stats /* may be NULL */);
+
+/* VARIANCE-GUIDED A-TROUS FILTER OVER THE G-BUFFER'S PLANES (no reference counterpart): the last stage of the reproject / accumulate / filter
+ * chain, for what pt_temporal_accumulate leaves.  Unlike pt_denoise it is guided by the exact first-hit planes of pt_render_gbuffer (hit,
+ * position) with the geometry tests of pt_temporal_accumulate — one notion of "same surface" for the whole chain —, its colour weight follows
+ * a per-pixel variance, no tap crosses a view border, and it works on exactly the pixel set pt_render_mask would render.  The call is
+ * stateless: every plane is caller-owned DEVICE memory of the context's device, frame-sized, indexed Y * width + X, and checked exactly as
+ * pt_render_gbuffer checks its planes (known to HIP, device memory of the context's device, 4-byte aligned — no wider alignment is assumed —
+ * fitting what is left of its allocation).  A pointer obtained from pt_device_buffer is accepted like any other.
+ * Which pixels: exactly those pt_render_gbuffer would write with the same mask — the rank's owned pixels, view pixels only while views are
+ * set, whole blocks of block_mask (HOST memory, NULL: every block).  No other pixel is written in out, scratch or frame_rgba8; inside the
+ * set the contents scratch is left with are unspecified.  Zero pixels launch nothing and return PT_OK.
+ * Each pixel works inside its own rectangle: its view (found by the pixel's 8x8 block), or the whole frame without views.
+ * Arithmetic per pixel p — float32 throughout, one rounding per operation, no fused multiply-add, in exactly this order; float32 NumPy
+ * evaluating this reproduces every output bit for bit (a NaN is a NaN: its sign and payload are not specified), with
+ *     dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;      lum(c) = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z;
+ *     sel_max0(v) = v > 0 ? v : 0;   sel_min80(v) = v < 80 ? v : 80   (a NaN gives 0 and 80: these are not fmaxf / fminf);
+ *     pt_expf: the one of pt_detmath.h.
+ *   Inert pixels.  p is inert when hit[p].prim < 0 or one of the three colour words of color[p] is not finite (exponent-bit test).  An inert
+ *     pixel's record is (color[p].xyz, 0) after every stage, it is written to out (and make_color'd) as it is, and it never counts as a tap.
+ *     stats->filtered counts the non-inert pixels of the set.
+ *   A tap q counts for p when q lies inside p's rectangle; q's 8x8 block belongs to the call's block set (owned by the rank, and named by
+ *     the mask if there is one); q is not inert; hit[q].mesh == hit[p].mesh; dot3(ng_p, ng_q) >= normal_cos; and
+ *     fabsf(dot3(ng_p, position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t.  p itself always counts.
+ *   Stage 0, prepare.  v_in = sel_max0(variance[p]).  When variance == NULL, or length != NULL && length[p] < (float)min_length, the
+ *     variance is estimated spatially instead and a non-inert p is counted in stats->spatial: over the 7x7 window at spacing 1, row-major (dy
+ *     outer, dx inner), over the taps that count, n += 1, s1 += lum(c_q), s2 += lum(c_q) * lum(c_q); then m = s1 / n and
+ *     v_in = sel_max0(s2 / n - m * m).  The record is (c_p.xyz, v_in).
+ *   Stage i = 0 .. iterations-1, one a-trous pass, step = 2^i, reading the previous stage's records (r, v):
+ *     1. g = G / K: G the sum of (k3[j] * k3[i]) * v_q over the 3x3 window at spacing 1, k3 = {0.25f, 0.5f, 0.25f}, row-major, over the taps
+ *        that count; K the same sum of k3[j] * k3[i]; each product k3[j] * k3[i] is formed first.
+ *     2. den = sigma_lum * sqrtf(g) + 1e-6f;  l_p = lum(r_p).
+ *     3. For the 25 taps q = p + step * (dx, dy), dy = -2..2 outer, dx = -2..2 inner, kern = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f}: a
+ *        tap that does not count contributes nothing; otherwise e = sel_min80(fabsf(l_p - lum(r_q)) / den);
+ *        w = pt_expf(-e) * (kern[dy+2] * kern[dx+2]);  S += r_q * w per component;  V += (w * w) * v_q;  W += w.
+ *     4. The new record is (S / W, V / (W * W)).
+ *   Output.  out[p] = the last stage's record (filtered rgb, filtered variance); frame_rgba8[p] = make_color(out[p].xyz).  Which of out /
+ *     scratch holds which intermediate stage is the implementation's business.
+ * variance is the caller's estimate of the variance of lum(color[p]).  The recipe of examples/svgf_loop.py: a second pt_temporal_accumulate
+ * over a moments plane (lum, lum * lum, 0, 1) with the same motion, hit and position planes gives reprojected moments (m1, m2), and
+ * variance = max(0, m2 - m1 * m1); length is that call's length_out, so that pixels disoccluded fewer than min_length frames ago, whose
+ * moments say nothing yet, take the spatial estimate.
+ * Overlap: out, scratch and frame_rgba8 may overlap no other plane; the read-only planes may alias one another.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; a required
+ * plane NULL (color, hit, position, out; scratch when iterations >= 1); a plane that fails the pointer checks; a forbidden overlap;
+ * flags != 0; a parameter out of its range or not finite.
+ * Ordering and state, as pt_temporal_accumulate: the call first waits for the frames in flight and completes queued queries, runs on
+ * pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns.  It reads and writes no context state except through the
+ * pointers the caller passed: the frame buffers, the accumulation, the adaptive state, the schedule trial and pt_stats are as they were.
+ * stats: pixels processed; non-inert pixels among them; those that took the spatial estimate; device time of all stages (hipEvents; the
+ * mask compaction included when there is a mask).
+ * Not part of this interface: an asynchronous variant, a pt_multi_* wrapper, albedo demodulation, neighbourhood clamping of the history,
+ * motion of moving geometry, any change to pt_denoise. */
+enum pt_filter_flags { PT_FILTER_RESERVED = 0 };   /* no flag defined yet: flags must be 0 */
+typedef struct pt_filter_desc {
+    const float* color;      /* w*h x 4  colour to filter (temporal's history_out / copy_out); .w is ignored */
+    const void*  hit;        /* w*h x pt_hit, this frame (pt_render_gbuffer) */
+    const float* position;   /* w*h x 4, this frame */
+    const float* variance;   /* w*h f32 or NULL: the caller's estimate of the variance of the luminance of color[p] */
+    const float* length;     /* w*h f32 or NULL: temporal's length_out */
+    float* out;              /* w*h x 4: (filtered rgb, filtered variance) */
+    float* scratch;          /* w*h x 4, required when iterations >= 1 (ping-pong), else may be NULL */
+    uint32_t* frame_rgba8;   /* w*h or NULL: make_color(out.rgb) */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    int32_t  iterations;     /* 0..6; pass i uses tap spacing 2^i; 0 = the prepared record only */
+    float    sigma_lum;      /* finite, > 0 */
+    float    normal_cos;     /* [-1,1] */
+    float    plane_eps;      /* finite, >= 0 */
+    uint32_t min_length;     /* 0..65535: where length[p] < min_length the variance is estimated spatially */
+    uint32_t flags;          /* 0 */
+} pt_filter_desc;
+typedef struct pt_filter_stats { uint64_t pixels, filtered, spatial; double kernel_ms; } pt_filter_stats;
+int pt_filter_planes(pt_ctx* ctx, const pt_filter_desc* desc, pt_filter_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -25,7 +25,7 @@ EXPORTS = [
     "pt_update_meshes", "pt_multi_update_meshes",
     "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
-    "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate",
+    "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate", "pt_filter_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -99,6 +99,25 @@ class TemporalStats(C.Structure):  # pt_temporal_stats
 TEMPORAL_PLANES = {"color": 4, "motion": 2, "hit": 8, "position": 4, "prev_hit": 8, "prev_position": 4, "history_in": 4, "length_in": 1,
                    "history_out": 4, "length_out": 1, "frame_rgba8": 1, "copy_out": 4}
 TEMPORAL_OUTPUTS = ("history_out", "length_out", "frame_rgba8", "copy_out")
+
+
+class FilterDesc(C.Structure):  # pt_filter_desc
+    _fields_ = [("color", C.c_void_p), ("hit", C.c_void_p), ("position", C.c_void_p), ("variance", C.c_void_p), ("length", C.c_void_p),
+                ("out", C.c_void_p), ("scratch", C.c_void_p), ("frame_rgba8", C.c_void_p), ("block_mask", C.c_void_p),
+                ("iterations", C.c_int32), ("sigma_lum", C.c_float), ("normal_cos", C.c_float), ("plane_eps", C.c_float),
+                ("min_length", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class FilterStats(C.Structure):  # pt_filter_stats
+    _fields_ = [("pixels", C.c_uint64), ("filtered", C.c_uint64), ("spatial", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_filter_planes: 32-bit words per pixel (frame_rgba8 holds packed bytes, the others float32)
+FILTER_PLANES = {"color": 4, "hit": 8, "position": 4, "variance": 1, "length": 1, "out": 4, "scratch": 4, "frame_rgba8": 1}
+FILTER_OUTPUTS = ("out", "scratch", "frame_rgba8")
 
 
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
@@ -306,6 +325,7 @@ def load_library() -> C.CDLL:
     L.pt_query_wait.argtypes = [vp, C.POINTER(QueryStats)]
     L.pt_render_gbuffer.argtypes = [vp, C.POINTER(GBufferDesc), C.POINTER(GBufferStats)]
     L.pt_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalDesc), C.POINTER(TemporalStats)]
+    L.pt_filter_planes.argtypes = [vp, C.POINTER(FilterDesc), C.POINTER(FilterStats)]
     L.pt_set_views.argtypes = [vp, C.POINTER(View), u32]
     L.pt_get_views.argtypes = [vp, C.POINTER(View), u32, C.POINTER(u32)]
     L.pt_set_view_cameras.argtypes = [vp, vp, u32]

@@ -299,6 +299,15 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The chain's filter (pt_filter_planes): a variance-guided a-trous filter over the G-buffer's exact planes, per view and on the pixel set
+    // of the mask.  Every plane of `d` is DEVICE memory of this context's device, frame-sized; block_mask is host memory.  Stateless and
+    // synchronous.  Returns the pixels processed, the non-inert ones, those whose variance was estimated spatially and the device time.
+    pt_filter_stats filterPlanes(const pt_filter_desc& d, pt_filter_stats* stats = nullptr) {
+        pt_filter_stats s{};
+        ck(pt_filter_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;

@@ -153,17 +153,17 @@ def _check_gbuffer_tensor(name, t, device: int, shape: tuple):
         raise ValueError(f"renderGBuffer: {name}: a contiguous torch.float32 tensor of shape {tuple(shape)} is expected, got {t.dtype} {tuple(t.shape)}")
 
 
-def _check_temporal_tensor(name, t, device: int, shapes: dict):
-    """temporalAccumulate: a CUDA tensor on GPU `device` whose (dtype, shape) is one of `shapes`, dense (any storage offset) — checked before the library is called."""
+def _check_temporal_tensor(name, t, device: int, shapes: dict, fn="temporalAccumulate"):
+    """temporalAccumulate, filterPlanes: a CUDA tensor on GPU `device` whose (dtype, shape) is one of `shapes`, dense (any storage offset) — checked before the library is called."""
     import torch
 
     if not isinstance(t, torch.Tensor):
-        raise TypeError(f"temporalAccumulate: {name}: a torch tensor or a device pointer is expected")
+        raise TypeError(f"{fn}: {name}: a torch tensor or a device pointer is expected")
     if not t.is_cuda or (t.device.index or 0) != device:
-        raise ValueError(f"temporalAccumulate: {name}: the tensor is on {t.device}, the context on GPU {device}")
+        raise ValueError(f"{fn}: {name}: the tensor is on {t.device}, the context on GPU {device}")
     if shapes.get(t.dtype) != tuple(t.shape) or not t.is_contiguous():
         want = " or ".join(f"{d} tensor of shape {sh}" for d, sh in shapes.items())
-        raise ValueError(f"temporalAccumulate: {name}: a contiguous {want} is expected, got {t.dtype} {tuple(t.shape)}")
+        raise ValueError(f"{fn}: {name}: a contiguous {want} is expected, got {t.dtype} {tuple(t.shape)}")
 
 
 def _mesh_transforms(transforms):
@@ -763,6 +763,73 @@ class SampleRenderer:
         self.waitEvent(ev.cuda_event)
         stats = _lib.TemporalStats()
         self._ck(self._L.pt_temporal_accumulate(self._ctx, C.byref(desc), C.byref(stats)), "pt_temporal_accumulate")
+        result["stats"] = stats.as_dict()
+        return result
+
+    def filterPlanes(self, color, hit, position, variance=None, length=None, out=None, scratch=None, frame=None, mask=None, iterations=5,
+                     sigma_lum=4.0, normal_cos=0.9, plane_eps=0.01, min_length=4) -> dict:
+        """The chain's filter: a variance-guided a-trous filter over the G-buffer's exact planes, per view and on the pixel set of the mask
+        (pt_filter_planes, include/pt_amd.h: the arithmetic, in full).
+
+        Every plane is a CUDA tensor on the context's device — float32, dense, any 4-byte-aligned storage offset — or a raw device
+        pointer (deviceBuffer(PT_BUF_COLOR) as `color`, deviceBuffer(PT_BUF_DENOISED) as `out`): color (h, w, 4), hit (h, w, 8) and
+        position (h, w, 4) (renderGBuffer's planes of this frame), variance and length ((h, w), optional: without a variance, and where
+        length < min_length, the variance is estimated over a 7x7 window).  out and scratch (h, w, 4) are allocated with torch,
+        zero-filled, when None (scratch only when iterations >= 1); pixels outside the views, the mask or the rank's partition are not
+        written.  frame (int32 (h, w) or uint8 (h, w, 4)) is optional.  mask: 8x8 blocks as renderMask takes them, None = every block.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
+        the outputs are complete.  The frame buffers, the accumulation and the path state are left alone (unless passed in as planes).
+        Returns {"out", "scratch", "frame_rgba8": the tensor (None for a raw pointer or an absent plane), "stats": {pixels, filtered,
+        spatial, kernel_ms}}."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        w, h = self.launchParams.frame.size
+        if not 0 <= int(iterations) <= 6:
+            raise ValueError("filterPlanes: iterations must be in [0,6]")
+        if out is None:
+            out = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        if scratch is None and int(iterations) >= 1:
+            scratch = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        given = dict(color=color, hit=hit, position=position, variance=variance, length=length, out=out, scratch=scratch, frame_rgba8=frame)
+        desc = _lib.FilterDesc()
+        result = {}
+        for name, t in given.items():
+            k = _lib.FILTER_PLANES[name]
+            if t is None:
+                if name in ("color", "hit", "position"):
+                    raise ValueError(f"filterPlanes: {name} is required")
+                ptr = None
+            elif isinstance(t, int):
+                ptr = t
+            else:
+                if name == "frame_rgba8":
+                    shapes = {torch.int32: (h, w), torch.uint8: (h, w, 4)}
+                else:
+                    shapes = {torch.float32: (h, w) if k == 1 else (h, w, k)}
+                _check_temporal_tensor(name, t, dev, shapes, "filterPlanes")
+                ptr = t.data_ptr()
+            setattr(desc, name, ptr)
+            if name in _lib.FILTER_OUTPUTS:
+                result[name] = None if t is None or isinstance(t, int) else t
+        m = None
+        if mask is not None:
+            nby, nbx = self.blockGrid()
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.size != nby * nbx:
+                raise ValueError(f"filterPlanes: the mask needs {nby} x {nbx} entries, got {m.size}")
+            desc.block_mask = m.ctypes.data
+        desc.iterations = int(iterations)
+        desc.sigma_lum, desc.normal_cos, desc.plane_eps = float(sigma_lum), float(normal_cos), float(plane_eps)
+        if not 0 <= int(min_length) < 2**32:
+            raise ValueError("filterPlanes: min_length must be in [0,65535]")
+        desc.min_length = int(min_length)
+        desc.flags = 0
+        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
+        ev.record(torch.cuda.current_stream(dev))
+        self.waitEvent(ev.cuda_event)
+        stats = _lib.FilterStats()
+        self._ck(self._L.pt_filter_planes(self._ctx, C.byref(desc), C.byref(stats)), "pt_filter_planes")
         result["stats"] = stats.as_dict()
         return result
 
