@@ -18,7 +18,8 @@
  * hipStreamNonBlocking: they do NOT synchronise with the null stream or with any stream of the
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
- * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes — read and write them on
+ * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes,
+ * pt_copy_vertices_device, pt_motion_planes — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -34,7 +35,8 @@
  * (pt_stats_size()).  0.2 -> 0.4: pt_stats grew by bvh_builder + reserved_ (8 bytes), pt_multi_stats by
  * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
- * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes.  A caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
+ * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes.  A
+ * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -617,7 +619,7 @@ int pt_query_wait(pt_ctx* ctx, pt_query_stats* stats /* may be NULL */);
  *                   px = (((a / c) + 1) * 0.5f) * width - 0.5f;  py = (((b / c) + 1) * 0.5f) * height - 0.5f
  *                   motion = (px - (float)x, py - (float)y)
  *               When c * det > 0 is false (behind the previous camera, c == 0, a NaN) both words are 0x7fc00000.  Motion is camera motion
- *               over the CURRENT geometry; it knows nothing of geometry that moved.
+ *               over the CURRENT geometry; it knows nothing of geometry that moved (pt_motion_planes below gives the planes for that).
  * Which pixels: those a pt_render_mask with the same mask would render — the rank's owned pixels (pt_set_partition), view pixels only while
  * views are set, whole blocks of block_mask (NULL: every block).  A pixel outside that set is not written in any plane.  Zero active
  * pixels launch nothing and return PT_OK.
@@ -634,7 +636,7 @@ int pt_query_wait(pt_ctx* ctx, pt_query_stats* stats /* may be NULL */);
  * from max(1, view count) when prev_cameras is given; a non-finite previous camera value.
  * stats: pixels written; hits among them; device time of the pass (hipEvents; the mask compaction included when there is a mask).
  * Not part of this interface: an asynchronous variant, a pt_multi_* wrapper (per-rank calls through pt_multi_ctx work), G-buffers of the
- * foveated launches, object-space motion. */
+ * foveated launches, object-space motion (a pass of its own: pt_motion_planes). */
 typedef struct pt_gbuffer_desc {
     void*  hit;       /* width*height x pt_hit (32 B)            or NULL */
     float* depth;     /* width*height x f32                      or NULL */
@@ -691,7 +693,7 @@ int pt_render_gbuffer(pt_ctx* ctx, const pt_gbuffer_desc* desc, pt_gbuffer_stats
  * views, masks and partitions; the recovered colour differs from the frame's own by two roundings.  Without views, a full-frame
  * pt_render_regions launch with redraw = 1 is the exact alternative.
  * stats: pixels processed; valid pixels among them; device time of the pass (hipEvents; the mask compaction included when there is a mask).
- * Not part of this interface: an asynchronous variant, a pt_multi_* wrapper, variance estimates, motion of moving geometry (the motion
+ * Not part of this interface: an asynchronous variant, a pt_multi_* wrapper, variance estimates, motion of moving geometry inside this call (the motion
  * plane is camera motion only), any change to pt_denoise. */
 enum pt_temporal_flags { PT_TEMPORAL_CLEAR_COLOR = 1 };
 typedef struct pt_temporal_desc {
@@ -789,6 +791,80 @@ typedef struct pt_filter_desc {
 } pt_filter_desc;
 typedef struct pt_filter_stats { uint64_t pixels, filtered, spatial; double kernel_ms; } pt_filter_stats;
 int pt_filter_planes(pt_ctx* ctx, const pt_filter_desc* desc, pt_filter_stats* stats /* may be NULL */);
+
+/* OBJECT MOTION FOR THE REPROJECTION CHAIN (no reference counterpart): the planes that let pt_temporal_accumulate follow geometry that moved
+ * between two frames (pt_update_meshes*, pt_transform_meshes).  pt_render_gbuffer's motion plane is camera motion over the current geometry:
+ * on a mesh that moved along its normal the temporal pass throws the history away (the plane test fails), on a mesh sliding in its own plane
+ * it keeps the history of another surface point.  pt_motion_planes takes this frame's hit plane and the PREVIOUS frame's vertices and says,
+ * per pixel, where the surface point under it was: in the previous image (motion), in space (prev_point) and with which normal
+ * (prev_surface).  The library keeps no previous-vertex state: the caller snapshots the vertices with pt_copy_vertices_device before the
+ * frame's pt_update_meshes* / pt_transform_meshes and ping-pongs the snapshot like prev_hit and prev_position.
+ *
+ * pt_vertex_count: the context's vertex and triangle totals over all meshes (either pointer may be NULL).  PT_ERR_INVALID for a null ctx.
+ * pt_copy_vertices_device: writes the context's current world-space vertices into caller-owned DEVICE memory: all meshes in mesh order,
+ * mesh m starting at the sum of num_vertices of the meshes before it, 3 floats per vertex.  bytes must equal vertices * 12.  dev_dst is
+ * checked exactly as pt_render_gbuffer checks a plane.  The call first waits for the frames in flight and completes queued queries, copies
+ * on pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns.  PT_ERR_INVALID (nothing copied) for a null ctx, wrong
+ * bytes, a pointer that fails the checks.
+ *
+ * pt_motion_planes.  Every plane is caller-owned DEVICE memory of the context's device, frame-sized, indexed Y * width + X, and checked exactly
+ * as pt_render_gbuffer checks its planes (known to HIP, device memory of the context's device, 4-byte aligned — no wider alignment is
+ * assumed — fitting what is left of its allocation); prev_vertices is checked against vertices * 12 bytes.  prev_cameras and block_mask are
+ * HOST memory.
+ * Which pixels: exactly those pt_temporal_accumulate would process with the same mask — the rank's owned pixels, view pixels only while views
+ * are set, whole blocks of block_mask (NULL: every block).  No other pixel is written in any output.  Zero pixels launch nothing and return
+ * PT_OK.  Each pixel works in its own rectangle: its view's (found by the pixel's 8x8 block), or the whole frame without views; (x, y) are
+ * its local coordinates there and width, height the rectangle's.
+ * Arithmetic per pixel p — float32 throughout, one rounding per operation, no fused multiply-add, in exactly this order, dot3, cross3 and
+ * normalize3 as in pt_render_gbuffer's text (cross3(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x)); float32 NumPy
+ * evaluating this reproduces every output bit for bit.  `triangles` is pt_vertex_count's:
+ *   - 0 <= hit[p].prim < triangles.  i_k = idx[3*prim + k], the triangle's global vertex indices (the mesh's own index + the mesh's first
+ *     vertex); p_k = prev_vertices[3*i_k ..];  u = hit[p].u, v = hit[p].v (the weights of vertex 1 and vertex 2);
+ *         w0 = (1.0f - u) - v;   Q = (p0*w0 + p1*u) + p2*v  per component;   ngp = normalize3(cross3(p1 - p0, p2 - p0))
+ *     (a degenerate previous triangle gives NaN words, as computed: the temporal pass's normal test then rejects the tap).
+ *     prev_point[p] = (Q, 1.0f);  prev_surface[p] = the eight words of hit[p] with words 5..7 (ng) replaced by ngp;
+ *     motion[p] = pt_render_gbuffer's projection block with q = Q - e', the previous camera (e', U', V', W') of the pixel's view, the
+ *     pixel's local (x, y) and the rectangle's width, height; when c * det > 0 is false both words are 0x7fc00000.
+ *     stats->hits counts these pixels.
+ *   - hit[p].prim < 0 (a miss).  prev_point[p] = four zeros;  prev_surface[p] = hit[p];  motion[p] = pt_render_gbuffer's for a miss: q = dir,
+ *     with dir rebuilt from the pixel's CURRENT camera by the G-buffer's ray expression — equal to pt_render_gbuffer's motion plane bit for
+ *     bit at every miss.
+ *   - hit[p].prim >= triangles.  The plane is caller memory and is not trusted: no address is formed from it.  Both motion words are
+ *     0x7fc00000, prev_point[p] is four zeros, prev_surface[p] = (hit[p].t, 0, 0, -1, -1, 0, 0, 0), and stats->stale counts the pixel.
+ * Feeding the chain.  pt_temporal_accumulate gets hit = prev_surface, position = prev_point, motion = motion; prev_hit and prev_position
+ * stay the previous frame's G-buffer planes.  Both sides of every surface test are then in the previous frame's space, and
+ * pt_temporal_accumulate itself is unchanged (its plane_eps * hit.t uses this frame's t, which prev_surface keeps).  pt_filter_planes keeps
+ * the CURRENT hit and position.  Loop order (examples/moving_geometry_loop.py): snapshot (pt_copy_vertices_device), move the geometry,
+ * render, pt_render_gbuffer, pt_motion_planes, pt_temporal_accumulate, pt_filter_planes.  With prev_vertices equal to the current vertices the
+ * planes are pt_render_gbuffer's up to the rounding of Q against o + t*dir.
+ * Overlap: motion, prev_point and prev_surface may overlap no other plane nor prev_vertices; hit and prev_vertices are only read.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; hit or
+ * prev_vertices NULL; all three outputs NULL; a plane that fails the pointer checks; a forbidden overlap; motion without prev_cameras;
+ * num_prev_cameras different from max(1, view count) when prev_cameras is given; a non-finite previous camera value; flags != 0.
+ * Ordering and state, as pt_temporal_accumulate: the call first waits for the frames in flight and completes queued queries, runs on
+ * pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns.  It sees the context's current index arrays (topology never
+ * changes) and reads no vertex of the context, only prev_vertices.  It reads and writes no context state except through the pointers the
+ * caller passed: the frame buffers, the accumulation, the adaptive state, the schedule trial and pt_stats are as they were.
+ * stats: pixels processed; hits and stale among them; device time of the pass (hipEvents; the mask compaction included when there is a mask).
+ * Not part of this interface: a pt_multi_* wrapper (per-rank calls through pt_multi_ctx work), an asynchronous variant, topology changes
+ * (the triangle under a prim index must be the same triangle in both frames), any change to pt_render_gbuffer, pt_temporal_accumulate,
+ * pt_filter_planes or pt_denoise. */
+int pt_vertex_count(const pt_ctx* ctx, uint32_t* vertices /* may be NULL */, uint32_t* triangles /* may be NULL */);
+int pt_copy_vertices_device(pt_ctx* ctx, float* dev_dst, size_t bytes);
+enum pt_motion_flags { PT_MOTION_RESERVED = 0 };   /* no flag defined yet: flags must be 0 */
+typedef struct pt_motion_desc {
+    const void*  hit;            /* w*h x pt_hit, this frame (pt_render_gbuffer); required */
+    const float* prev_vertices;  /* vertices x 3 f32, pt_copy_vertices_device's layout, of the previous frame; required */
+    float* motion;               /* w*h x 2  or NULL */
+    float* prev_point;           /* w*h x 4  or NULL: where the pixel's surface point was, (x, y, z, 1) */
+    void*  prev_surface;         /* w*h x pt_hit or NULL: hit[p] with ng replaced by the previous normal */
+    const float*   prev_cameras; /* HOST, n x 12 (eye,U,V,W); required iff motion != NULL */
+    uint32_t       num_prev_cameras; /* 1 without views, else the view count */
+    const uint8_t* block_mask;   /* HOST, as pt_render_gbuffer, or NULL */
+    uint32_t flags;              /* 0 */
+} pt_motion_desc;
+typedef struct pt_motion_stats { uint64_t pixels, hits, stale; double kernel_ms; } pt_motion_stats;
+int pt_motion_planes(pt_ctx* ctx, const pt_motion_desc* desc, pt_motion_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

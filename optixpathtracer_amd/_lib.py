@@ -26,6 +26,7 @@ EXPORTS = [
     "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
     "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate", "pt_filter_planes",
+    "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -118,6 +119,22 @@ class FilterStats(C.Structure):  # pt_filter_stats
 # the planes of pt_filter_planes: 32-bit words per pixel (frame_rgba8 holds packed bytes, the others float32)
 FILTER_PLANES = {"color": 4, "hit": 8, "position": 4, "variance": 1, "length": 1, "out": 4, "scratch": 4, "frame_rgba8": 1}
 FILTER_OUTPUTS = ("out", "scratch", "frame_rgba8")
+
+
+class MotionDesc(C.Structure):  # pt_motion_desc
+    _fields_ = [("hit", C.c_void_p), ("prev_vertices", C.c_void_p), ("motion", C.c_void_p), ("prev_point", C.c_void_p), ("prev_surface", C.c_void_p),
+                ("prev_cameras", C.c_void_p), ("num_prev_cameras", C.c_uint32), ("block_mask", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class MotionStats(C.Structure):  # pt_motion_stats
+    _fields_ = [("pixels", C.c_uint64), ("hits", C.c_uint64), ("stale", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the output planes of pt_motion_planes: float32 words per pixel
+MOTION_PLANES = {"motion": 2, "prev_point": 4, "prev_surface": 8}
 
 
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
@@ -326,6 +343,9 @@ def load_library() -> C.CDLL:
     L.pt_render_gbuffer.argtypes = [vp, C.POINTER(GBufferDesc), C.POINTER(GBufferStats)]
     L.pt_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalDesc), C.POINTER(TemporalStats)]
     L.pt_filter_planes.argtypes = [vp, C.POINTER(FilterDesc), C.POINTER(FilterStats)]
+    L.pt_vertex_count.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.pt_copy_vertices_device.argtypes = [vp, vp, C.c_size_t]
+    L.pt_motion_planes.argtypes = [vp, C.POINTER(MotionDesc), C.POINTER(MotionStats)]
     L.pt_set_views.argtypes = [vp, C.POINTER(View), u32]
     L.pt_get_views.argtypes = [vp, C.POINTER(View), u32, C.POINTER(u32)]
     L.pt_set_view_cameras.argtypes = [vp, vp, u32]

@@ -308,6 +308,24 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The context's current world-space vertices, all meshes in mesh order, into DEVICE memory of `bytes` = vertices * 12 bytes
+    // (pt_copy_vertices_device): the snapshot motionPlanes needs, taken before the frame's updateMeshes / transformMeshes.  With dev_dst ==
+    // nullptr only the count is returned.  Returns the number of vertices.
+    uint32_t copyVerticesDevice(float* dev_dst, size_t bytes) {
+        uint32_t nv = 0;
+        ck(pt_vertex_count(ctx, &nv, nullptr));
+        if (dev_dst) ck(pt_copy_vertices_device(ctx, dev_dst, bytes));
+        return nv;
+    }
+    // Object motion for the chain (pt_motion_planes): from this frame's hit plane and the previous frame's vertices, where each pixel's
+    // surface point was — motion, prev_point, prev_surface — for temporalAccumulate(hit = prev_surface, position = prev_point).  Stateless
+    // and synchronous.  Returns the pixels processed, the hits and the stale primitive indices among them and the device time.
+    pt_motion_stats motionPlanes(const pt_motion_desc& d, pt_motion_stats* stats = nullptr) {
+        pt_motion_stats s{};
+        ck(pt_motion_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;

@@ -833,6 +833,106 @@ class SampleRenderer:
         result["stats"] = stats.as_dict()
         return result
 
+    def vertexCount(self):
+        """(vertices, triangles) of the context, summed over its meshes (pt_vertex_count)."""
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.pt_vertex_count(self._ctx, C.byref(nv), C.byref(nt)), "pt_vertex_count")
+        return nv.value, nt.value
+
+    def copyVerticesDevice(self, out=None):
+        """The context's current world-space vertices, all meshes in mesh order, copied on the GPU into a float32 (vertices, 3) CUDA tensor
+        (pt_copy_vertices_device): the "previous vertices" of motionPlanes when taken before the frame's updateMeshes* / transformMeshes.
+        out: a tensor of that shape on the context's device (dense, any 4-byte-aligned storage offset) or a raw device pointer; allocated
+        with torch when None.  Waits for frames in flight; complete on return.  Returns the tensor (None for a raw pointer)."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        nv = sum(self._nv)
+        if out is None:
+            out = torch.empty((nv, 3), dtype=torch.float32, device=f"cuda:{dev}")
+        if isinstance(out, int):
+            ptr, result = out, None
+        else:
+            _check_temporal_tensor("out", out, dev, {torch.float32: (nv, 3)}, "copyVerticesDevice")
+            ptr, result = out.data_ptr(), out
+        ev = torch.cuda.Event()  # earlier users of `out` on torch's current stream come first, on the device
+        ev.record(torch.cuda.current_stream(dev))
+        self.waitEvent(ev.cuda_event)
+        self._ck(self._L.pt_copy_vertices_device(self._ctx, ptr, nv * 12), "pt_copy_vertices_device")
+        return result
+
+    def motionPlanes(self, hit, prev_vertices, prev_cameras=None, planes=("motion", "prev_point", "prev_surface"), mask=None, out=None) -> dict:
+        """Where each pixel's surface point was before the geometry moved (pt_motion_planes, include/pt_amd.h: the arithmetic, in full).
+
+        hit: this frame's renderGBuffer hit plane, float32 (h, w, 8); prev_vertices: the previous frame's vertices, float32 (vertices, 3)
+        (copyVerticesDevice before the geometry moved) — CUDA tensors on the context's device, dense, any 4-byte-aligned storage offset,
+        or raw device pointers.  planes: any of "motion" (h, w, 2), "prev_point" (h, w, 4), "prev_surface" (h, w, 8).  out: {plane: tensor
+        or raw pointer} for planes the caller owns; the others are allocated with torch, zero-filled (pixels outside the views, the mask
+        or the rank's partition are not written).  prev_cameras, needed by "motion": as renderGBuffer takes them.  mask: 8x8 blocks as
+        renderMask takes them, None = every block.
+        Feeding the chain: temporalAccumulate(hit=prev_surface, position=prev_point, motion=motion) with prev_hit and prev_position the
+        previous frame's G-buffer planes; filterPlanes keeps the current hit and position.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
+        the planes are complete.  The frame buffers, the accumulation and the path state are left alone.
+        Returns {plane: tensor (None for a raw pointer), ..., "stats": {pixels, hits, stale, kernel_ms}}."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        w, h = self.launchParams.frame.size
+        planes = tuple(planes)
+        out = dict(out or {})
+        for name in list(planes) + list(out):
+            if name not in _lib.MOTION_PLANES:
+                raise ValueError(f"motionPlanes: unknown plane {name!r} (one of {', '.join(_lib.MOTION_PLANES)})")
+        if any(name not in planes for name in out):
+            raise ValueError("motionPlanes: `out` names a plane that `planes` does not")
+        if not planes:
+            raise ValueError("motionPlanes: no plane asked for")
+        if "motion" in planes and prev_cameras is None:
+            raise ValueError("motionPlanes: motion needs prev_cameras")
+        desc = _lib.MotionDesc()
+        for name, t, shape in (("hit", hit, (h, w, 8)), ("prev_vertices", prev_vertices, (sum(self._nv), 3))):
+            if t is None:
+                raise ValueError(f"motionPlanes: {name} is required")
+            if not isinstance(t, int):
+                _check_temporal_tensor(name, t, dev, {torch.float32: shape}, "motionPlanes")
+                t = t.data_ptr()
+            setattr(desc, name, t)
+        result = {}
+        for name in planes:
+            k = _lib.MOTION_PLANES[name]
+            t = out.get(name)
+            if t is None:
+                t = torch.zeros((h, w, k), dtype=torch.float32, device=f"cuda:{dev}")
+            if isinstance(t, int):
+                ptr, result[name] = t, None
+            else:
+                _check_temporal_tensor(name, t, dev, {torch.float32: (h, w, k)}, "motionPlanes")
+                ptr, result[name] = t.data_ptr(), t
+            setattr(desc, name, ptr)
+        rows = None
+        if prev_cameras is not None:
+            if isinstance(prev_cameras, Camera) or (len(prev_cameras) == 12 and not isinstance(prev_cameras[0], Camera) and np.ndim(prev_cameras) == 1):
+                prev_cameras = [prev_cameras]  # one camera, or one (12,) row
+            rows = _camera_rows(prev_cameras)
+            desc.prev_cameras = rows.ctypes.data
+            desc.num_prev_cameras = rows.shape[0]
+        m = None
+        if mask is not None:
+            nby, nbx = self.blockGrid()
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.size != nby * nbx:
+                raise ValueError(f"motionPlanes: the mask needs {nby} x {nbx} entries, got {m.size}")
+            desc.block_mask = m.ctypes.data
+        desc.flags = 0
+        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
+        ev.record(torch.cuda.current_stream(dev))
+        self.waitEvent(ev.cuda_event)
+        stats = _lib.MotionStats()
+        self._ck(self._L.pt_motion_planes(self._ctx, C.byref(desc), C.byref(stats)), "pt_motion_planes")
+        result["stats"] = stats.as_dict()
+        return result
+
     def evalTable(self, which, inp: np.ndarray, out_width: int, material=None, bsdf_mode=PT_BSDF_DISNEY) -> np.ndarray:
         inp = np.ascontiguousarray(inp, np.float32)
         n = inp.shape[0]
