@@ -19,7 +19,7 @@
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
  * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes,
- * pt_copy_vertices_device, pt_motion_planes — read and write them on
+ * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -35,7 +35,8 @@
  * (pt_stats_size()).  0.2 -> 0.4: pt_stats grew by bvh_builder + reserved_ (8 bytes), pt_multi_stats by
  * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
- * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes.  A
+ * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
+ * pt_temporal_moments, pt_modulate_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -865,6 +866,105 @@ typedef struct pt_motion_desc {
 } pt_motion_desc;
 typedef struct pt_motion_stats { uint64_t pixels, hits, stale; double kernel_ms; } pt_motion_stats;
 int pt_motion_planes(pt_ctx* ctx, const pt_motion_desc* desc, pt_motion_stats* stats /* may be NULL */);
+
+/* THE SVGF TEMPORAL STAGE IN ONE PASS (no reference counterpart): what examples/svgf_loop.py assembles from three pt_temporal_accumulate
+ * calls and element-wise kernels — this frame's colour, the colour history, the luminance moments, the variance — as one kernel with one
+ * gather of the taps, plus the two things pt_temporal_accumulate and pt_filter_planes leave out: the colour is DEMODULATED by the first-hit
+ * albedo before it is accumulated (so pt_filter_planes works on irradiance-like values and keeps texture detail; pt_modulate_planes
+ * multiplies the albedo back in behind the filter), and the reprojected history can be CLAMPED to the neighbourhood of this frame's colour
+ * (so a history that passes the geometry tests but is stale — a moved shadow, a changed probe — does not ghost for max_history frames).
+ *
+ * pt_temporal_moments.  The call is stateless: every plane is caller-owned DEVICE memory of the context's device, frame-sized, indexed
+ * Y * width + X, and checked exactly as pt_render_gbuffer checks its planes (known to HIP, device memory of the context's device, 4-byte
+ * aligned — no wider alignment is assumed — fitting what is left of its allocation).  A pointer obtained from pt_device_buffer is accepted
+ * like any other (PT_BUF_ACCUM as color, PT_BUF_ALBEDO as albedo).
+ * Which pixels: exactly those pt_render_gbuffer would write with the same mask — the rank's owned pixels, view pixels only while views are
+ * set, whole blocks of block_mask (HOST memory, NULL: every block).  No other pixel is written in any output.  Zero pixels launch nothing
+ * and return PT_OK.
+ * Each pixel works inside its own rectangle (x0, y0, wr, hr): its view (found by the pixel's 8x8 block), or the whole frame without views;
+ * (x, y) are its local coordinates there.  Arithmetic per pixel p — float32 throughout, one rounding per operation, no fused multiply-add,
+ * in exactly this order; float32 NumPy evaluating this reproduces every output bit for bit (a NaN is a NaN: its sign and payload are not
+ * specified), with dot3, lum and sel_max0 as pt_temporal_accumulate and pt_filter_planes define them:
+ *   0. The demodulated colour d(q) of a frame pixel q, per component k of x, y, z: den(q).k = 1.0f when albedo == NULL; otherwise, with
+ *      a = albedo[q].k, den(q).k = a > albedo_min ? a : 1.0f (a NaN gives 1, a miss's zero gives 1);
+ *      d(q).k = (color[q].k * color_scale) / den(q).k — the multiplication first, then the division.
+ *   1. d_p = d(p); l = lum(d_p); m = (l, l * l).
+ *   2-4. pt_temporal_accumulate's steps 2, 3 and 4 verbatim (tap order (0,0), (1,0), (0,1), (1,1), sums of the shape ((. + .) + .) + .),
+ *      with two additions: a tap also needs both words of moments_in[q] finite (exponent-bit test), and Msum is formed like Hsum from
+ *      w_ij * moments_in[q] per component.  valid is defined as there.
+ *   5. Valid: H = Hsum / Wsum; M = Msum / Wsum; n = fminf(nprev, (float)(max_history - 1)); a = 1.0f / (n + 1.0f).
+ *   5b. Only with PT_TMOM_CLAMP and only for a valid pixel.  Over the 3x3 window at spacing 1 around p, row-major (dy outer, dx inner), a
+ *      window pixel q counts when q lies inside p's rectangle, q's 8x8 block belongs to the call's block set (pt_filter_planes's rule: owned
+ *      by the rank, and named by the mask if there is one) and the three words of d(q) are finite (exponent-bit test; p itself is a window
+ *      pixel like the others).  Per counting q: cnt += 1; s1.k += d(q).k; s2.k += d(q).k * d(q).k.  With cnt >= 1:
+ *      mu = s1 / cnt; sd = sqrtf(sel_max0(s2 / cnt - mu * mu)); lo = mu - clamp_k * sd; hi = mu + clamp_k * sd (the product first); per
+ *      channel H.k = H.k < lo.k ? lo.k : (H.k > hi.k ? hi.k : H.k).  stats->clamped counts the valid pixels for which one of the six
+ *      comparisons H.k < lo.k, H.k > hi.k was true.  The moments are not clamped.
+ *   5c. Valid: out = H + (d_p - H) * a; mo = M + (m - M) * a; len = n + 1.  Otherwise out = d_p; mo = m; len = 1.
+ *   6. history_out[p] = (out, 1.0f); moments_out[p] = mo; length_out[p] = len; variance_out[p] = sel_max0(mo.y - mo.x * mo.x);
+ *      stats->reprojected counts the valid pixels.
+ * Clear.  With PT_TMOM_CLEAR_COLOR the four words of color[p] are 0 on return for every pixel of the set.  No read of the call observes the
+ * clear (the window reads neighbours' colours: the clear is a second launch behind the kernel on the same stream).
+ * Overlap: the four outputs and color may overlap no other plane; the read-only planes may alias one another (prev_hit == hit, say).
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; a required
+ * plane NULL (all but albedo, variance_out and block_mask); a plane that fails the pointer checks; a forbidden overlap; unknown flag bits;
+ * a parameter out of its range or not finite — albedo_min negative or not finite; clamp_k negative or not finite when PT_TMOM_CLAMP is set
+ * (without the flag clamp_k is not read).
+ * Ordering and state, as pt_temporal_accumulate: the call first waits for the frames in flight and completes queued queries, runs on
+ * pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns; the previous planes must be complete before the call.  It reads
+ * and writes no context state except through the pointers the caller passed: the frame buffers, the accumulation, the adaptive state, the
+ * schedule trial and pt_stats are as they were.  The per-frame colour recipe of pt_temporal_accumulate (PT_BUF_ACCUM, color_scale = k + 1,
+ * the clear flag) holds word for word.  The chain (examples/svgf_albedo_loop.py): pt_render_gbuffer, render, pt_temporal_moments,
+ * pt_filter_planes on history_out with variance_out and length_out, pt_modulate_planes.
+ * stats: pixels processed; valid pixels among them; clamped pixels among those; device time of the pass and of the clear (hipEvents; the
+ * mask compaction included when there is a mask).
+ * Not part of this interface: an asynchronous variant, a pt_multi_* wrapper, clamping of the moments.
+ *
+ * pt_modulate_planes, the end of the chain: r.k = color[p].k * den(p).k with den exactly as step 0 above; out[p] = (r, color[p].w);
+ * frame_rgba8[p] = make_color(r).  At least one of out and frame_rgba8 is required.  The pass is pixel-local, so out may be exactly the
+ * address of color (in place); every other overlap of an output with a plane is refused.  Planes, pointer checks, pixel set, ordering and
+ * state are pt_temporal_moments's.  Refused with PT_ERR_INVALID (nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet;
+ * color NULL; both outputs NULL; a plane that fails the pointer checks; a forbidden overlap; flags != 0; albedo_min negative or not finite.
+ * stats: pixels processed; device time of the pass (the mask compaction included when there is a mask). */
+enum pt_tmom_flags { PT_TMOM_CLEAR_COLOR = 1, PT_TMOM_CLAMP = 2 };
+typedef struct pt_tmom_desc {
+    float* color;               /* w*h x 4  this frame's colour; zeroed afterwards with PT_TMOM_CLEAR_COLOR */
+    const float* albedo;        /* w*h x 4 or NULL (e.g. pt_device_buffer(PT_BUF_ALBEDO)) */
+    const float* motion;        /* w*h x 2  pt_render_gbuffer's (or pt_motion_planes's) motion plane of this frame */
+    const void*  hit;           /* w*h x pt_hit, this frame */
+    const float* position;      /* w*h x 4, this frame */
+    const void*  prev_hit;      /* previous frame's hit plane */
+    const float* prev_position;
+    const float* history_in;    /* w*h x 4  accumulated demodulated colour after the previous frame */
+    const float* moments_in;    /* w*h x 2  accumulated (lum, lum * lum) after the previous frame */
+    const float* length_in;     /* w*h      per-pixel history length (whole numbers; 0 = no history) */
+    float* history_out;         /* w*h x 4 */
+    float* moments_out;         /* w*h x 2 */
+    float* length_out;          /* w*h */
+    float* variance_out;        /* w*h or NULL */
+    const uint8_t* block_mask;  /* HOST, as pt_render_gbuffer, or NULL */
+    float color_scale;          /* finite, > 0 */
+    float albedo_min;           /* finite, >= 0 */
+    float normal_cos;           /* [-1,1] */
+    float plane_eps;            /* finite, >= 0 */
+    float min_weight;           /* [0,1] */
+    float clamp_k;              /* finite, >= 0; read only with PT_TMOM_CLAMP */
+    uint32_t max_history;       /* 1..65535 */
+    uint32_t flags;             /* pt_tmom_flags */
+} pt_tmom_desc;
+typedef struct pt_tmom_stats { uint64_t pixels, reprojected, clamped; double kernel_ms; } pt_tmom_stats;
+int pt_temporal_moments(pt_ctx* ctx, const pt_tmom_desc* desc, pt_tmom_stats* stats /* may be NULL */);
+typedef struct pt_modulate_desc {
+    const float* color;         /* w*h x 4  demodulated colour (pt_filter_planes's out); required */
+    const float* albedo;        /* w*h x 4 or NULL */
+    float* out;                 /* w*h x 4 or NULL; may be exactly color */
+    uint32_t* frame_rgba8;      /* w*h or NULL: make_color(r) */
+    const uint8_t* block_mask;  /* HOST, as pt_render_gbuffer, or NULL */
+    float albedo_min;           /* finite, >= 0 */
+    uint32_t flags;             /* 0 */
+} pt_modulate_desc;
+typedef struct pt_modulate_stats { uint64_t pixels; double kernel_ms; } pt_modulate_stats;
+int pt_modulate_planes(pt_ctx* ctx, const pt_modulate_desc* desc, pt_modulate_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -26,7 +26,7 @@ EXPORTS = [
     "pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices",
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
     "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate", "pt_filter_planes",
-    "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes",
+    "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes", "pt_temporal_moments", "pt_modulate_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -135,6 +135,48 @@ class MotionStats(C.Structure):  # pt_motion_stats
 
 # the output planes of pt_motion_planes: float32 words per pixel
 MOTION_PLANES = {"motion": 2, "prev_point": 4, "prev_surface": 8}
+
+
+PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
+
+
+class TMomDesc(C.Structure):  # pt_tmom_desc
+    _fields_ = [("color", C.c_void_p), ("albedo", C.c_void_p), ("motion", C.c_void_p), ("hit", C.c_void_p), ("position", C.c_void_p),
+                ("prev_hit", C.c_void_p), ("prev_position", C.c_void_p), ("history_in", C.c_void_p), ("moments_in", C.c_void_p),
+                ("length_in", C.c_void_p), ("history_out", C.c_void_p), ("moments_out", C.c_void_p), ("length_out", C.c_void_p),
+                ("variance_out", C.c_void_p), ("block_mask", C.c_void_p),
+                ("color_scale", C.c_float), ("albedo_min", C.c_float), ("normal_cos", C.c_float), ("plane_eps", C.c_float),
+                ("min_weight", C.c_float), ("clamp_k", C.c_float), ("max_history", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class TMomStats(C.Structure):  # pt_tmom_stats
+    _fields_ = [("pixels", C.c_uint64), ("reprojected", C.c_uint64), ("clamped", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_temporal_moments: float32 words per pixel
+TMOM_PLANES = {"color": 4, "albedo": 4, "motion": 2, "hit": 8, "position": 4, "prev_hit": 8, "prev_position": 4, "history_in": 4,
+               "moments_in": 2, "length_in": 1, "history_out": 4, "moments_out": 2, "length_out": 1, "variance_out": 1}
+TMOM_OUTPUTS = ("history_out", "moments_out", "length_out", "variance_out")
+
+
+class ModulateDesc(C.Structure):  # pt_modulate_desc
+    _fields_ = [("color", C.c_void_p), ("albedo", C.c_void_p), ("out", C.c_void_p), ("frame_rgba8", C.c_void_p), ("block_mask", C.c_void_p),
+                ("albedo_min", C.c_float), ("flags", C.c_uint32)]
+
+
+class ModulateStats(C.Structure):  # pt_modulate_stats
+    _fields_ = [("pixels", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_modulate_planes: 32-bit words per pixel (frame_rgba8 holds packed bytes, the others float32)
+MODULATE_PLANES = {"color": 4, "albedo": 4, "out": 4, "frame_rgba8": 1}
+MODULATE_OUTPUTS = ("out", "frame_rgba8")
 
 
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
@@ -346,6 +388,8 @@ def load_library() -> C.CDLL:
     L.pt_vertex_count.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.pt_copy_vertices_device.argtypes = [vp, vp, C.c_size_t]
     L.pt_motion_planes.argtypes = [vp, C.POINTER(MotionDesc), C.POINTER(MotionStats)]
+    L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
+    L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_set_views.argtypes = [vp, C.POINTER(View), u32]
     L.pt_get_views.argtypes = [vp, C.POINTER(View), u32, C.POINTER(u32)]
     L.pt_set_view_cameras.argtypes = [vp, vp, u32]

@@ -326,6 +326,23 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The SVGF temporal stage in one pass (pt_temporal_moments): demodulated colour, colour history, luminance moments and variance through
+    // one gather, with an optional clamp of the history to this frame's 3x3 neighbourhood.  Every plane of `d` is DEVICE memory of this
+    // context's device, frame-sized; block_mask is host memory.  Stateless and synchronous; the caller ping-pongs history, moments and
+    // length.  Returns the pixels processed, those that kept their history, the clamped ones among them and the device time.
+    pt_tmom_stats temporalMoments(const pt_tmom_desc& d, pt_tmom_stats* stats = nullptr) {
+        pt_tmom_stats s{};
+        ck(pt_temporal_moments(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
+    // The end of the chain (pt_modulate_planes): multiplies the albedo back into the filtered, demodulated colour; out may be color itself.
+    pt_modulate_stats modulatePlanes(const pt_modulate_desc& d, pt_modulate_stats* stats = nullptr) {
+        pt_modulate_stats s{};
+        ck(pt_modulate_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;

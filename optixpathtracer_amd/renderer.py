@@ -833,6 +833,130 @@ class SampleRenderer:
         result["stats"] = stats.as_dict()
         return result
 
+    def temporalMoments(self, color, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, albedo=None,
+                        history_out=None, moments_out=None, length_out=None, variance_out=None, variance=True, mask=None, color_scale=1.0,
+                        albedo_min=0.0, normal_cos=0.9, plane_eps=0.01, min_weight=0.25, clamp_k=None, max_history=32, clear_color=False) -> dict:
+        """The SVGF temporal stage in one pass: demodulates this frame's colour by the albedo, reprojects the colour history and the
+        luminance moments through one gather, optionally clamps the history to the 3x3 neighbourhood of this frame's colour, blends and
+        writes the variance (pt_temporal_moments, include/pt_amd.h: the arithmetic, in full).
+
+        Every plane is a CUDA tensor on the context's device — float32 (h, w, k), dense, any 4-byte-aligned storage offset — or a raw
+        device pointer (deviceBuffer(PT_BUF_ACCUM) as `color`, deviceBuffer(PT_BUF_ALBEDO) as `albedo`): color (k = 4; zeroed afterwards
+        with clear_color), albedo (4, optional), motion (2), hit and position (8, 4), prev_hit and prev_position (last frame's),
+        history_in (4), moments_in (2) and length_in ((h, w)): what the previous call returned.  history_out, moments_out, length_out
+        and (unless variance=False) variance_out are allocated with torch, zero-filled, when None (pixels outside the views, the mask or
+        the rank's partition are not written); they may overlap no other plane, so a loop ping-pongs two sets.  clamp_k: None = no clamp,
+        else the half-width of the clamp window in standard deviations.  mask: 8x8 blocks as renderMask takes them, None = every block.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
+        the outputs are complete.  The frame buffers, the accumulation and the path state are left alone (unless passed in as planes).
+        Returns {"history_out", "moments_out", "length_out", "variance_out": the tensor (None for a raw pointer or an absent plane),
+        "stats": {pixels, reprojected, clamped, kernel_ms}}."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        w, h = self.launchParams.frame.size
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=f"cuda:{dev}")  # noqa: E731
+        if history_out is None:
+            history_out = zeros(h, w, 4)
+        if moments_out is None:
+            moments_out = zeros(h, w, 2)
+        if length_out is None:
+            length_out = zeros(h, w)
+        if variance_out is None and variance:
+            variance_out = zeros(h, w)
+        given = dict(color=color, albedo=albedo, motion=motion, hit=hit, position=position, prev_hit=prev_hit, prev_position=prev_position,
+                     history_in=history_in, moments_in=moments_in, length_in=length_in, history_out=history_out, moments_out=moments_out,
+                     length_out=length_out, variance_out=variance_out)
+        desc = _lib.TMomDesc()
+        result = {}
+        for name, t in given.items():
+            k = _lib.TMOM_PLANES[name]
+            if t is None:
+                if name not in ("albedo", "variance_out"):
+                    raise ValueError(f"temporalMoments: {name} is required")
+                ptr = None
+            elif isinstance(t, int):
+                ptr = t
+            else:
+                _check_temporal_tensor(name, t, dev, {torch.float32: (h, w) if k == 1 else (h, w, k)}, "temporalMoments")
+                ptr = t.data_ptr()
+            setattr(desc, name, ptr)
+            if name in _lib.TMOM_OUTPUTS:
+                result[name] = None if t is None or isinstance(t, int) else t
+        m = None
+        if mask is not None:
+            nby, nbx = self.blockGrid()
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.size != nby * nbx:
+                raise ValueError(f"temporalMoments: the mask needs {nby} x {nbx} entries, got {m.size}")
+            desc.block_mask = m.ctypes.data
+        desc.color_scale, desc.albedo_min = float(color_scale), float(albedo_min)
+        desc.normal_cos, desc.plane_eps, desc.min_weight = float(normal_cos), float(plane_eps), float(min_weight)
+        desc.clamp_k = 0.0 if clamp_k is None else float(clamp_k)
+        if not 0 <= int(max_history) < 2**32:
+            raise ValueError("temporalMoments: max_history must be in [1,65535]")
+        desc.max_history = int(max_history)
+        desc.flags = (_lib.PT_TMOM_CLEAR_COLOR if clear_color else 0) | (_lib.PT_TMOM_CLAMP if clamp_k is not None else 0)
+        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
+        ev.record(torch.cuda.current_stream(dev))
+        self.waitEvent(ev.cuda_event)
+        stats = _lib.TMomStats()
+        self._ck(self._L.pt_temporal_moments(self._ctx, C.byref(desc), C.byref(stats)), "pt_temporal_moments")
+        result["stats"] = stats.as_dict()
+        return result
+
+    def modulatePlanes(self, color, albedo=None, out=None, frame=None, mask=None, albedo_min=0.0, write_out=True) -> dict:
+        """The end of the chain: multiplies the albedo back into a demodulated colour plane (pt_modulate_planes, include/pt_amd.h), with the
+        denominator rule of temporalMoments, and writes float colour and / or packed RGBA8.
+
+        color (h, w, 4) and albedo (h, w, 4, optional) are CUDA float32 tensors on the context's device — dense, any 4-byte-aligned storage
+        offset — or raw device pointers.  out (h, w, 4) is allocated with torch, zero-filled, when None and write_out is true; it may be
+        `color` itself (in place: the pass is pixel-local) and may overlap no plane otherwise.  frame (int32 (h, w) or uint8 (h, w, 4)) is
+        optional; with write_out=False it is the only output.  mask: 8x8 blocks as renderMask takes them, None = every block.
+        Ordering is on the device, as temporalMoments.  Returns {"out", "frame_rgba8": the tensor (None for a raw pointer or an absent
+        plane), "stats": {pixels, kernel_ms}}."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        w, h = self.launchParams.frame.size
+        if out is None and write_out:
+            out = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        if out is None and frame is None:
+            raise ValueError("modulatePlanes: no output asked for (out and frame are both None)")
+        given = dict(color=color, albedo=albedo, out=out, frame_rgba8=frame)
+        desc = _lib.ModulateDesc()
+        result = {}
+        for name, t in given.items():
+            if t is None:
+                if name == "color":
+                    raise ValueError("modulatePlanes: color is required")
+                ptr = None
+            elif isinstance(t, int):
+                ptr = t
+            else:
+                shapes = {torch.int32: (h, w), torch.uint8: (h, w, 4)} if name == "frame_rgba8" else {torch.float32: (h, w, 4)}
+                _check_temporal_tensor(name, t, dev, shapes, "modulatePlanes")
+                ptr = t.data_ptr()
+            setattr(desc, name, ptr)
+            if name in _lib.MODULATE_OUTPUTS:
+                result[name] = None if t is None or isinstance(t, int) else t
+        m = None
+        if mask is not None:
+            nby, nbx = self.blockGrid()
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.size != nby * nbx:
+                raise ValueError(f"modulatePlanes: the mask needs {nby} x {nbx} entries, got {m.size}")
+            desc.block_mask = m.ctypes.data
+        desc.albedo_min = float(albedo_min)
+        desc.flags = 0
+        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
+        ev.record(torch.cuda.current_stream(dev))
+        self.waitEvent(ev.cuda_event)
+        stats = _lib.ModulateStats()
+        self._ck(self._L.pt_modulate_planes(self._ctx, C.byref(desc), C.byref(stats)), "pt_modulate_planes")
+        result["stats"] = stats.as_dict()
+        return result
+
     def vertexCount(self):
         """(vertices, triangles) of the context, summed over its meshes (pt_vertex_count)."""
         nv, nt = C.c_uint32(), C.c_uint32()
