@@ -1,0 +1,146 @@
+// pt_pass.h — what the image-space passes (pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_motion_planes,
+// pt_temporal_moments, pt_modulate_planes) share on the host: the plane table and its checks, the previous cameras, the block table of a
+// call, and the run object that owns a call's temporaries and its timed span.  Host only.  Included by pt_lib.hip behind pt_api.hip: the
+// second part uses that file's context and file-local helpers; the first part needs no HIP header (tests/test_pass_planes.py compiles it
+// with a host compiler alone).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+// One plane of a pass.  required: a null pointer is refused.  exclusive: may overlap no other plane (what the pass writes or zeroes); planes
+// that are only read may alias one another.
+struct PassPlane {
+    const char* name;
+    const void* p;
+    size_t bytes;
+    bool required, exclusive;
+};
+
+// The first pair of planes (*first < *second, in table order) whose byte ranges intersect and of which at least one is exclusive.  Null
+// and zero-byte planes overlap nothing.  eq_a, eq_b: one pair that may be exactly equal (an in-place pass); offset against one another
+// they are reported like any other pair.
+static inline bool pass_planes_overlap(const PassPlane* pl, int n, int* first, int* second, int eq_a = -1, int eq_b = -1) {
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j) {
+            if (!pl[i].exclusive && !pl[j].exclusive) continue;
+            const uintptr_t a = reinterpret_cast<uintptr_t>(pl[i].p), b = reinterpret_cast<uintptr_t>(pl[j].p);
+            if (!a || !b || !pl[i].bytes || !pl[j].bytes) continue;
+            if (i == eq_a && j == eq_b && a == b) continue;
+            if (a < b + pl[j].bytes && b < a + pl[i].bytes) {
+                *first = i;
+                *second = j;
+                return true;
+            }
+        }
+    return false;
+}
+
+#ifdef __HIPCC__
+// Every plane that is given or required is a device pointer of the context's device with `bytes` behind it; then the overlap test.
+// fn: the entry point's name, as it stands in front of the colon of its messages.
+static int pass_planes_check(pt_ctx* ctx, const char* fn, const PassPlane* pl, int n, int eq_a = -1, int eq_b = -1) {
+    CK(hipSetDevice(ctx->device));
+    std::string err;
+    for (int i = 0; i < n; ++i)
+        if ((pl[i].p || pl[i].required) && query_pointer_validate(ctx, pl[i].p, pl[i].bytes, pl[i].name, err, fn, "a device copy") != PT_OK) return fail(ctx, PT_ERR_INVALID, err.c_str());
+    int i = 0, j = 0;
+    if (pass_planes_overlap(pl, n, &i, &j, eq_a, eq_b)) return fail(ctx, PT_ERR_INVALID, (std::string(fn) + ": " + pl[i].name + " and " + pl[j].name + " overlap").c_str());
+    return PT_OK;
+}
+
+// The previous frame's cameras (12 floats each: eye, U, V, W): one per view, one without views; a motion plane needs them.
+static uint32_t pass_camera_count(const pt_ctx* ctx) { return std::max(1u, ctx->vw.n); }
+static int pass_prev_cameras_check(pt_ctx* ctx, const char* fn, const void* motion, const float* prev_cameras, uint32_t num_prev_cameras) {
+    const std::string f = std::string(fn) + ": ";
+    const uint32_t ncams = pass_camera_count(ctx);
+    if (motion && !prev_cameras) return fail(ctx, PT_ERR_INVALID, (f + "motion needs prev_cameras").c_str());
+    if (!prev_cameras) return PT_OK;
+    if (num_prev_cameras != ncams)
+        return fail(ctx, PT_ERR_INVALID, (f + "num_prev_cameras is " + std::to_string(num_prev_cameras) + ", expected " + std::to_string(ncams) + (ctx->vw.n ? " (the view count)" : " (no views are set)")).c_str());
+    for (size_t k = 0; k < (size_t)12 * ncams; ++k)
+        if (!std::isfinite(prev_cameras[k])) return fail(ctx, PT_ERR_INVALID, (f + "prev_cameras: value " + std::to_string(k) + " is not finite").c_str());
+    return PT_OK;
+}
+
+// The call's block set, one byte per 8x8 block, for the `block` test of the filter's taps and of the clamp window: the rank's blocks (view
+// blocks only while views are set) that the mask names.  After subset_open.
+static std::vector<uint8_t> pass_block_set(const pt_ctx* ctx, const uint8_t* block_mask) {
+    const pt_ctx::Blocks& B = ctx->blk;
+    std::vector<uint8_t> inset(B.owned_flags.begin(), B.owned_flags.begin() + B.nblk);
+    if (block_mask)
+        for (uint32_t b = 0; b < B.nblk; ++b) inset[b] = (inset[b] && block_mask[b]) ? 1 : 0;
+    return inset;
+}
+
+static ViewParams pass_views(const pt_ctx* ctx) {
+    return ctx->vw.n ? ViewParams{ctx->vw.d_vblock, ctx->vw.d_views, (uint32_t)(ctx->width + 7) / 8u} : ViewParams{};
+}
+// Launches K<VIEWS, ...> on the run's stream with (args, the context's views); the trailing arguments are K's further template arguments.
+#define PASS_LAUNCH(run, grid, block, args, K, ...)                                                                                              \
+    do {                                                                                                                                         \
+        if ((run).ctx->vw.n) hipLaunchKernelGGL((K<true, ##__VA_ARGS__>), dim3(grid), dim3(block), 0, (run).ctx->stream, args, pass_views((run).ctx)); \
+        else hipLaunchKernelGGL((K<false, ##__VA_ARGS__>), dim3(grid), dim3(block), 0, (run).ctx->stream, args, ViewParams{});                       \
+    } while (0)
+
+// One call of a pass.  open, then whatever the pass uploads or clears for itself (into temporaries of `tmp`, on ctx->stream: all of it in
+// front of the timed span), select, the pass's launches over pixels[0, n), close.  The timed span runs from select's event to close's:
+// uploads and clears are outside it, the compaction of a mask is inside it.  Once open has enqueued something, the stream is waited for
+// before the temporaries are freed on every path, a failed one included.
+namespace {
+struct PassRun {
+    pt_ctx* ctx = nullptr;
+    DevScope tmp; // destroyed after ~PassRun has waited
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint8_t* d_counters = nullptr; // the pass's counter words, zeroed
+    const uint32_t* pixels = nullptr;
+    uint32_t n = 0;
+    float ms = 0.f;
+    bool live = false;
+    unsigned long long* counts() const { return reinterpret_cast<unsigned long long*>(d_counters); }
+
+    // frames in flight and queued queries finish first; the block table for the mask; the events; counter_bytes of zeroed counters
+    int open(pt_ctx* c, const char* fn, size_t counter_bytes) {
+        ctx = c;
+        const int rc = subset_open(ctx, fn, false, 0);
+        if (rc) return rc;
+        if (counter_bytes) CK(tmp.alloc(&d_counters, counter_bytes));
+        CK(tmp.event(&ev0));
+        CK(tmp.event(&ev1));
+        live = true;
+        if (counter_bytes) CK(hipMemsetAsync(d_counters, 0, counter_bytes, ctx->stream));
+        return PT_OK;
+    }
+    // the pixel list of the call: the whole frame's, or the compacted list of the mask's blocks
+    int select(const uint8_t* block_mask) {
+        pt_ctx::Blocks& B = ctx->blk;
+        if (block_mask) CK(hipMemcpyAsync(B.d_flags, block_mask, B.nblk, hipMemcpyHostToDevice, ctx->stream));
+        CK(hipEventRecord(ev0, ctx->stream));
+        pixels = ctx->frame_pixels();
+        n = ctx->frame_owned();
+        if (block_mask) {
+            const int rc = compact_enqueue(ctx, ctx->stream, B.d_flags, B.d_list, 1);
+            if (rc) return rc;
+            CK(hipStreamSynchronize(ctx->stream)); // the launch is sized on the host: it needs the count
+            pixels = B.d_list;
+            n = B.h_counts[0];
+        }
+        return PT_OK;
+    }
+    // e: the first error of the pass's own launches, if it asked for it.  h_counters: where the first `bytes` of the counters go.
+    int close(hipError_t e, void* h_counters = nullptr, size_t bytes = 0) {
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ev1, ctx->stream);
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(h_counters, d_counters, bytes, hipMemcpyDeviceToHost, ctx->stream);
+        const hipError_t es = hipStreamSynchronize(ctx->stream);
+        live = false;
+        CK(e);
+        CK(es);
+        CK(hipEventElapsedTime(&ms, ev0, ev1));
+        return PT_OK;
+    }
+    ~PassRun() {
+        if (live) hipStreamSynchronize(ctx->stream); // nothing of the call may still run when its temporaries go
+    }
+};
+} // namespace
+#endif

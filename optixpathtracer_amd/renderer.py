@@ -141,20 +141,9 @@ def _check_query_tensor(name, t, device: int, dtype, tail: tuple):
         raise ValueError(f"traceDevice: {name}: a contiguous {dtype} tensor of shape (n{''.join(f', {k}' for k in tail)}) is expected, got {t.dtype} {tuple(t.shape)}")
 
 
-def _check_gbuffer_tensor(name, t, device: int, shape: tuple):
-    """renderGBuffer: a CUDA float32 tensor on GPU `device` of exactly `shape`, dense (any storage offset) — checked before the library is called."""
-    import torch
-
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"renderGBuffer: {name}: a torch tensor or a device pointer is expected")
-    if not t.is_cuda or (t.device.index or 0) != device:
-        raise ValueError(f"renderGBuffer: {name}: the tensor is on {t.device}, the context on GPU {device}")
-    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f"renderGBuffer: {name}: a contiguous torch.float32 tensor of shape {tuple(shape)} is expected, got {t.dtype} {tuple(t.shape)}")
-
-
 def _check_temporal_tensor(name, t, device: int, shapes: dict, fn="temporalAccumulate"):
-    """temporalAccumulate, filterPlanes: a CUDA tensor on GPU `device` whose (dtype, shape) is one of `shapes`, dense (any storage offset) — checked before the library is called."""
+    """The plane check of every method that takes GPU planes: a CUDA tensor on GPU `device` whose (dtype, shape) is one of `shapes`, dense
+    (any storage offset) — checked before the library is called."""
     import torch
 
     if not isinstance(t, torch.Tensor):
@@ -613,10 +602,8 @@ class SampleRenderer:
             if out.shape[0] != n:
                 raise ValueError(f"traceDevice: out has {out.shape[0]} rows for {n} rays")
             optr = out.data_ptr()
-        if torch is not None:  # what torch enqueued so far — the rays' producer, earlier users of `out` — comes first, on the device
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            self.waitEvent(ev.cuda_event)
+        if torch is not None:  # the rays' producer, earlier users of `out`
+            self._after_torch()
         flags = (_lib.PT_QUERY_ANY if any_hit else _lib.PT_QUERY_CLOSEST) | (0 if wait else _lib.PT_QUERY_ASYNC)
         stats = _lib.QueryStats()
         self._ck(self._L.pt_trace_device(self._ctx, ptr, n, flags, optr, C.byref(stats) if wait else None), "pt_trace_device")
@@ -640,6 +627,74 @@ class SampleRenderer:
         self._ck(self._L.pt_query_wait(self._ctx, C.byref(s)), "pt_query_wait")
         return s.as_dict()
 
+    # ---- what the image-space passes share (renderGBuffer .. motionPlanes)
+    def _bind_planes(self, fn, desc, given, widths, required=(), outputs=(), alloc=()):
+        """Sets desc.<name> for every plane of `given` ({name: None, a raw device pointer or a tensor}, in the order they are checked in).
+        widths: floats per pixel ((h, w) for 1, else (h, w, k)) or a whole shape; frame_rgba8 is int32 (h, w) or uint8 (h, w, 4).
+        A plane of `alloc` that is None is allocated with torch, zero-filled.
+        Returns {name: the tensor, None for a raw pointer or an absent plane} for the planes of `outputs`."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        w, h = self.launchParams.frame.size
+        result = {}
+        for name, t in given.items():
+            k = widths[name]
+            shape = k if isinstance(k, tuple) else (h, w) if k == 1 else (h, w, k)
+            if t is None and name in alloc:
+                t = torch.zeros(shape, dtype=torch.float32, device=f"cuda:{dev}")
+            if t is None:
+                if name in required:
+                    raise ValueError(f"{fn}: {name} is required")
+                ptr = None
+            elif isinstance(t, int):
+                ptr = t
+            else:
+                shapes = {torch.int32: (h, w), torch.uint8: (h, w, 4)} if name == "frame_rgba8" else {torch.float32: shape}
+                _check_temporal_tensor(name, t, dev, shapes, fn)
+                ptr = t.data_ptr()
+            setattr(desc, name, ptr)
+            if name in outputs:
+                result[name] = None if t is None or isinstance(t, int) else t
+        return result
+
+    def _bind_mask(self, fn, desc, mask):
+        """desc.block_mask for 8x8 blocks as renderMask takes them; returns the array, which the caller keeps until the library has returned."""
+        if mask is None:
+            return None
+        nby, nbx = self.blockGrid()
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if m.size != nby * nbx:
+            raise ValueError(f"{fn}: the mask needs {nby} x {nbx} entries, got {m.size}")
+        desc.block_mask = m.ctypes.data
+        return m
+
+    @staticmethod
+    def _bind_prev_cameras(desc, prev_cameras):
+        """desc.prev_cameras for one Camera, one (12,) row or one per view; returns the rows, which the caller keeps as it keeps a mask."""
+        if prev_cameras is None:
+            return None
+        if isinstance(prev_cameras, Camera) or (len(prev_cameras) == 12 and not isinstance(prev_cameras[0], Camera) and np.ndim(prev_cameras) == 1):
+            prev_cameras = [prev_cameras]  # one camera, or one (12,) row
+        rows = _camera_rows(prev_cameras)
+        desc.prev_cameras = rows.ctypes.data
+        desc.num_prev_cameras = rows.shape[0]
+        return rows
+
+    def _after_torch(self):
+        """What torch enqueued so far on its current stream (the producers of the planes, a fill of the outputs) comes first, on the device."""
+        import torch
+
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(getattr(self, "_device", 0)))
+        self.waitEvent(ev.cuda_event)
+
+    def _run_pass(self, cname, desc, stats, result):
+        self._after_torch()
+        self._ck(getattr(self._L, cname)(self._ctx, C.byref(desc), C.byref(stats)), cname)
+        result["stats"] = stats.as_dict()
+        return result
+
     def renderGBuffer(self, planes=("hit",), prev_cameras=None, mask=None, out=None) -> dict:
         """The first hit under the centre of every pixel, written by one kernel into GPU tensors (pt_render_gbuffer, include/pt_amd.h).
 
@@ -652,10 +707,6 @@ class SampleRenderer:
         Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
         the planes are complete.  The frame buffers, the accumulation and the path state are left alone.
         Returns {plane: tensor (None for a raw pointer), ..., "stats": {pixels, hits, kernel_ms}}."""
-        import torch
-
-        dev = getattr(self, "_device", 0)
-        w, h = self.launchParams.frame.size
         planes = tuple(planes)
         out = dict(out or {})
         for name in list(planes) + list(out):
@@ -664,39 +715,10 @@ class SampleRenderer:
         if any(name not in planes for name in out):
             raise ValueError("renderGBuffer: `out` names a plane that `planes` does not")
         desc = _lib.GBufferDesc()
-        result = {}
-        for name in planes:
-            k = _lib.GBUFFER_PLANES[name]
-            t = out.get(name)
-            if t is None:
-                t = torch.zeros((h, w) if name == "depth" else (h, w, k), dtype=torch.float32, device=f"cuda:{dev}")
-            if isinstance(t, int):
-                ptr, result[name] = t, None
-            else:
-                _check_gbuffer_tensor(name, t, dev, (h, w) if name == "depth" else (h, w, k))
-                ptr, result[name] = t.data_ptr(), t
-            setattr(desc, name, ptr)
-        rows = None
-        if prev_cameras is not None:
-            if isinstance(prev_cameras, Camera) or (len(prev_cameras) == 12 and not isinstance(prev_cameras[0], Camera) and np.ndim(prev_cameras) == 1):
-                prev_cameras = [prev_cameras]  # one camera, or one (12,) row
-            rows = _camera_rows(prev_cameras)
-            desc.prev_cameras = rows.ctypes.data
-            desc.num_prev_cameras = rows.shape[0]
-        m = None
-        if mask is not None:
-            nby, nbx = self.blockGrid()
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.size != nby * nbx:
-                raise ValueError(f"renderGBuffer: the mask needs {nby} x {nbx} entries, got {m.size}")
-            desc.block_mask = m.ctypes.data
-        ev = torch.cuda.Event()  # what torch enqueued so far (a fill of the caller's planes) comes first, on the device
-        ev.record(torch.cuda.current_stream(dev))
-        self.waitEvent(ev.cuda_event)
-        stats = _lib.GBufferStats()
-        self._ck(self._L.pt_render_gbuffer(self._ctx, C.byref(desc), C.byref(stats)), "pt_render_gbuffer")
-        result["stats"] = stats.as_dict()
-        return result
+        result = self._bind_planes("renderGBuffer", desc, {name: out.get(name) for name in planes}, _lib.GBUFFER_PLANES, outputs=planes, alloc=planes)
+        rows = self._bind_prev_cameras(desc, prev_cameras)  # noqa: F841 (kept until the call has returned, as m is)
+        m = self._bind_mask("renderGBuffer", desc, mask)  # noqa: F841
+        return self._run_pass("pt_render_gbuffer", desc, _lib.GBufferStats(), result)
 
     def temporalAccumulate(self, color, motion, hit, position, prev_hit, prev_position, history_in, length_in, history_out=None, length_out=None,
                            frame_rgba8=None, copy_out=None, mask=None, color_scale=1.0, normal_cos=0.9, plane_eps=0.01, min_weight=0.25,
@@ -715,56 +737,18 @@ class SampleRenderer:
         the outputs are complete.  The frame buffers, the accumulation and the path state are left alone (unless passed in as planes).
         Returns {"history_out", "length_out", "frame_rgba8", "copy_out": the tensor (None for a raw pointer or an absent plane),
         "stats": {pixels, reprojected, kernel_ms}}."""
-        import torch
-
-        dev = getattr(self, "_device", 0)
-        w, h = self.launchParams.frame.size
-        if history_out is None:
-            history_out = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
-        if length_out is None:
-            length_out = torch.zeros((h, w), dtype=torch.float32, device=f"cuda:{dev}")
         given = dict(color=color, motion=motion, hit=hit, position=position, prev_hit=prev_hit, prev_position=prev_position, history_in=history_in,
                      length_in=length_in, history_out=history_out, length_out=length_out, frame_rgba8=frame_rgba8, copy_out=copy_out)
         desc = _lib.TemporalDesc()
-        result = {}
-        for name, t in given.items():
-            k = _lib.TEMPORAL_PLANES[name]
-            optional = name in ("frame_rgba8", "copy_out")
-            if t is None:
-                if not optional:
-                    raise ValueError(f"temporalAccumulate: {name} is required")
-                ptr = None
-            elif isinstance(t, int):
-                ptr = t
-            else:
-                if name == "frame_rgba8":
-                    shapes = {torch.int32: (h, w), torch.uint8: (h, w, 4)}
-                else:
-                    shapes = {torch.float32: (h, w) if k == 1 else (h, w, k)}
-                _check_temporal_tensor(name, t, dev, shapes)
-                ptr = t.data_ptr()
-            setattr(desc, name, ptr)
-            if name in _lib.TEMPORAL_OUTPUTS:
-                result[name] = None if t is None or isinstance(t, int) else t
-        m = None
-        if mask is not None:
-            nby, nbx = self.blockGrid()
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.size != nby * nbx:
-                raise ValueError(f"temporalAccumulate: the mask needs {nby} x {nbx} entries, got {m.size}")
-            desc.block_mask = m.ctypes.data
+        result = self._bind_planes("temporalAccumulate", desc, given, _lib.TEMPORAL_PLANES, set(given) - {"frame_rgba8", "copy_out"}, _lib.TEMPORAL_OUTPUTS,
+                                   alloc=("history_out", "length_out"))
+        m = self._bind_mask("temporalAccumulate", desc, mask)  # noqa: F841 (kept until the call has returned)
         desc.color_scale, desc.normal_cos, desc.plane_eps, desc.min_weight = float(color_scale), float(normal_cos), float(plane_eps), float(min_weight)
         if not 0 <= int(max_history) < 2**32:
             raise ValueError("temporalAccumulate: max_history must be in [1,65535]")
         desc.max_history = int(max_history)
         desc.flags = _lib.PT_TEMPORAL_CLEAR_COLOR if clear_color else 0
-        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
-        ev.record(torch.cuda.current_stream(dev))
-        self.waitEvent(ev.cuda_event)
-        stats = _lib.TemporalStats()
-        self._ck(self._L.pt_temporal_accumulate(self._ctx, C.byref(desc), C.byref(stats)), "pt_temporal_accumulate")
-        result["stats"] = stats.as_dict()
-        return result
+        return self._run_pass("pt_temporal_accumulate", desc, _lib.TemporalStats(), result)
 
     def filterPlanes(self, color, hit, position, variance=None, length=None, out=None, scratch=None, frame=None, mask=None, iterations=5,
                      sigma_lum=4.0, normal_cos=0.9, plane_eps=0.01, min_length=4) -> dict:
@@ -781,57 +765,20 @@ class SampleRenderer:
         the outputs are complete.  The frame buffers, the accumulation and the path state are left alone (unless passed in as planes).
         Returns {"out", "scratch", "frame_rgba8": the tensor (None for a raw pointer or an absent plane), "stats": {pixels, filtered,
         spatial, kernel_ms}}."""
-        import torch
-
-        dev = getattr(self, "_device", 0)
-        w, h = self.launchParams.frame.size
         if not 0 <= int(iterations) <= 6:
             raise ValueError("filterPlanes: iterations must be in [0,6]")
-        if out is None:
-            out = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
-        if scratch is None and int(iterations) >= 1:
-            scratch = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
         given = dict(color=color, hit=hit, position=position, variance=variance, length=length, out=out, scratch=scratch, frame_rgba8=frame)
         desc = _lib.FilterDesc()
-        result = {}
-        for name, t in given.items():
-            k = _lib.FILTER_PLANES[name]
-            if t is None:
-                if name in ("color", "hit", "position"):
-                    raise ValueError(f"filterPlanes: {name} is required")
-                ptr = None
-            elif isinstance(t, int):
-                ptr = t
-            else:
-                if name == "frame_rgba8":
-                    shapes = {torch.int32: (h, w), torch.uint8: (h, w, 4)}
-                else:
-                    shapes = {torch.float32: (h, w) if k == 1 else (h, w, k)}
-                _check_temporal_tensor(name, t, dev, shapes, "filterPlanes")
-                ptr = t.data_ptr()
-            setattr(desc, name, ptr)
-            if name in _lib.FILTER_OUTPUTS:
-                result[name] = None if t is None or isinstance(t, int) else t
-        m = None
-        if mask is not None:
-            nby, nbx = self.blockGrid()
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.size != nby * nbx:
-                raise ValueError(f"filterPlanes: the mask needs {nby} x {nbx} entries, got {m.size}")
-            desc.block_mask = m.ctypes.data
+        result = self._bind_planes("filterPlanes", desc, given, _lib.FILTER_PLANES, ("color", "hit", "position"), _lib.FILTER_OUTPUTS,
+                                   alloc=("out", "scratch") if int(iterations) >= 1 else ("out",))
+        m = self._bind_mask("filterPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
         desc.iterations = int(iterations)
         desc.sigma_lum, desc.normal_cos, desc.plane_eps = float(sigma_lum), float(normal_cos), float(plane_eps)
         if not 0 <= int(min_length) < 2**32:
             raise ValueError("filterPlanes: min_length must be in [0,65535]")
         desc.min_length = int(min_length)
         desc.flags = 0
-        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
-        ev.record(torch.cuda.current_stream(dev))
-        self.waitEvent(ev.cuda_event)
-        stats = _lib.FilterStats()
-        self._ck(self._L.pt_filter_planes(self._ctx, C.byref(desc), C.byref(stats)), "pt_filter_planes")
-        result["stats"] = stats.as_dict()
-        return result
+        return self._run_pass("pt_filter_planes", desc, _lib.FilterStats(), result)
 
     def temporalMoments(self, color, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, albedo=None,
                         history_out=None, moments_out=None, length_out=None, variance_out=None, variance=True, mask=None, color_scale=1.0,
@@ -851,45 +798,13 @@ class SampleRenderer:
         the outputs are complete.  The frame buffers, the accumulation and the path state are left alone (unless passed in as planes).
         Returns {"history_out", "moments_out", "length_out", "variance_out": the tensor (None for a raw pointer or an absent plane),
         "stats": {pixels, reprojected, clamped, kernel_ms}}."""
-        import torch
-
-        dev = getattr(self, "_device", 0)
-        w, h = self.launchParams.frame.size
-        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=f"cuda:{dev}")  # noqa: E731
-        if history_out is None:
-            history_out = zeros(h, w, 4)
-        if moments_out is None:
-            moments_out = zeros(h, w, 2)
-        if length_out is None:
-            length_out = zeros(h, w)
-        if variance_out is None and variance:
-            variance_out = zeros(h, w)
         given = dict(color=color, albedo=albedo, motion=motion, hit=hit, position=position, prev_hit=prev_hit, prev_position=prev_position,
                      history_in=history_in, moments_in=moments_in, length_in=length_in, history_out=history_out, moments_out=moments_out,
                      length_out=length_out, variance_out=variance_out)
         desc = _lib.TMomDesc()
-        result = {}
-        for name, t in given.items():
-            k = _lib.TMOM_PLANES[name]
-            if t is None:
-                if name not in ("albedo", "variance_out"):
-                    raise ValueError(f"temporalMoments: {name} is required")
-                ptr = None
-            elif isinstance(t, int):
-                ptr = t
-            else:
-                _check_temporal_tensor(name, t, dev, {torch.float32: (h, w) if k == 1 else (h, w, k)}, "temporalMoments")
-                ptr = t.data_ptr()
-            setattr(desc, name, ptr)
-            if name in _lib.TMOM_OUTPUTS:
-                result[name] = None if t is None or isinstance(t, int) else t
-        m = None
-        if mask is not None:
-            nby, nbx = self.blockGrid()
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.size != nby * nbx:
-                raise ValueError(f"temporalMoments: the mask needs {nby} x {nbx} entries, got {m.size}")
-            desc.block_mask = m.ctypes.data
+        result = self._bind_planes("temporalMoments", desc, given, _lib.TMOM_PLANES, set(given) - {"albedo", "variance_out"}, _lib.TMOM_OUTPUTS,
+                                   alloc=_lib.TMOM_OUTPUTS if variance else _lib.TMOM_OUTPUTS[:3])
+        m = self._bind_mask("temporalMoments", desc, mask)  # noqa: F841 (kept until the call has returned)
         desc.color_scale, desc.albedo_min = float(color_scale), float(albedo_min)
         desc.normal_cos, desc.plane_eps, desc.min_weight = float(normal_cos), float(plane_eps), float(min_weight)
         desc.clamp_k = 0.0 if clamp_k is None else float(clamp_k)
@@ -897,13 +812,7 @@ class SampleRenderer:
             raise ValueError("temporalMoments: max_history must be in [1,65535]")
         desc.max_history = int(max_history)
         desc.flags = (_lib.PT_TMOM_CLEAR_COLOR if clear_color else 0) | (_lib.PT_TMOM_CLAMP if clamp_k is not None else 0)
-        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
-        ev.record(torch.cuda.current_stream(dev))
-        self.waitEvent(ev.cuda_event)
-        stats = _lib.TMomStats()
-        self._ck(self._L.pt_temporal_moments(self._ctx, C.byref(desc), C.byref(stats)), "pt_temporal_moments")
-        result["stats"] = stats.as_dict()
-        return result
+        return self._run_pass("pt_temporal_moments", desc, _lib.TMomStats(), result)
 
     def modulatePlanes(self, color, albedo=None, out=None, frame=None, mask=None, albedo_min=0.0, write_out=True) -> dict:
         """The end of the chain: multiplies the albedo back into a demodulated colour plane (pt_modulate_planes, include/pt_amd.h), with the
@@ -915,47 +824,15 @@ class SampleRenderer:
         optional; with write_out=False it is the only output.  mask: 8x8 blocks as renderMask takes them, None = every block.
         Ordering is on the device, as temporalMoments.  Returns {"out", "frame_rgba8": the tensor (None for a raw pointer or an absent
         plane), "stats": {pixels, kernel_ms}}."""
-        import torch
-
-        dev = getattr(self, "_device", 0)
-        w, h = self.launchParams.frame.size
-        if out is None and write_out:
-            out = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
-        if out is None and frame is None:
+        if out is None and not write_out and frame is None:
             raise ValueError("modulatePlanes: no output asked for (out and frame are both None)")
         given = dict(color=color, albedo=albedo, out=out, frame_rgba8=frame)
         desc = _lib.ModulateDesc()
-        result = {}
-        for name, t in given.items():
-            if t is None:
-                if name == "color":
-                    raise ValueError("modulatePlanes: color is required")
-                ptr = None
-            elif isinstance(t, int):
-                ptr = t
-            else:
-                shapes = {torch.int32: (h, w), torch.uint8: (h, w, 4)} if name == "frame_rgba8" else {torch.float32: (h, w, 4)}
-                _check_temporal_tensor(name, t, dev, shapes, "modulatePlanes")
-                ptr = t.data_ptr()
-            setattr(desc, name, ptr)
-            if name in _lib.MODULATE_OUTPUTS:
-                result[name] = None if t is None or isinstance(t, int) else t
-        m = None
-        if mask is not None:
-            nby, nbx = self.blockGrid()
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.size != nby * nbx:
-                raise ValueError(f"modulatePlanes: the mask needs {nby} x {nbx} entries, got {m.size}")
-            desc.block_mask = m.ctypes.data
+        result = self._bind_planes("modulatePlanes", desc, given, _lib.MODULATE_PLANES, ("color",), _lib.MODULATE_OUTPUTS, alloc=("out",) if write_out else ())
+        m = self._bind_mask("modulatePlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
         desc.albedo_min = float(albedo_min)
         desc.flags = 0
-        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
-        ev.record(torch.cuda.current_stream(dev))
-        self.waitEvent(ev.cuda_event)
-        stats = _lib.ModulateStats()
-        self._ck(self._L.pt_modulate_planes(self._ctx, C.byref(desc), C.byref(stats)), "pt_modulate_planes")
-        result["stats"] = stats.as_dict()
-        return result
+        return self._run_pass("pt_modulate_planes", desc, _lib.ModulateStats(), result)
 
     def vertexCount(self):
         """(vertices, triangles) of the context, summed over its meshes (pt_vertex_count)."""
@@ -979,9 +856,7 @@ class SampleRenderer:
         else:
             _check_temporal_tensor("out", out, dev, {torch.float32: (nv, 3)}, "copyVerticesDevice")
             ptr, result = out.data_ptr(), out
-        ev = torch.cuda.Event()  # earlier users of `out` on torch's current stream come first, on the device
-        ev.record(torch.cuda.current_stream(dev))
-        self.waitEvent(ev.cuda_event)
+        self._after_torch()  # earlier users of `out`
         self._ck(self._L.pt_copy_vertices_device(self._ctx, ptr, nv * 12), "pt_copy_vertices_device")
         return result
 
@@ -999,10 +874,6 @@ class SampleRenderer:
         Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
         the planes are complete.  The frame buffers, the accumulation and the path state are left alone.
         Returns {plane: tensor (None for a raw pointer), ..., "stats": {pixels, hits, stale, kernel_ms}}."""
-        import torch
-
-        dev = getattr(self, "_device", 0)
-        w, h = self.launchParams.frame.size
         planes = tuple(planes)
         out = dict(out or {})
         for name in list(planes) + list(out):
@@ -1015,47 +886,13 @@ class SampleRenderer:
         if "motion" in planes and prev_cameras is None:
             raise ValueError("motionPlanes: motion needs prev_cameras")
         desc = _lib.MotionDesc()
-        for name, t, shape in (("hit", hit, (h, w, 8)), ("prev_vertices", prev_vertices, (sum(self._nv), 3))):
-            if t is None:
-                raise ValueError(f"motionPlanes: {name} is required")
-            if not isinstance(t, int):
-                _check_temporal_tensor(name, t, dev, {torch.float32: shape}, "motionPlanes")
-                t = t.data_ptr()
-            setattr(desc, name, t)
-        result = {}
-        for name in planes:
-            k = _lib.MOTION_PLANES[name]
-            t = out.get(name)
-            if t is None:
-                t = torch.zeros((h, w, k), dtype=torch.float32, device=f"cuda:{dev}")
-            if isinstance(t, int):
-                ptr, result[name] = t, None
-            else:
-                _check_temporal_tensor(name, t, dev, {torch.float32: (h, w, k)}, "motionPlanes")
-                ptr, result[name] = t.data_ptr(), t
-            setattr(desc, name, ptr)
-        rows = None
-        if prev_cameras is not None:
-            if isinstance(prev_cameras, Camera) or (len(prev_cameras) == 12 and not isinstance(prev_cameras[0], Camera) and np.ndim(prev_cameras) == 1):
-                prev_cameras = [prev_cameras]  # one camera, or one (12,) row
-            rows = _camera_rows(prev_cameras)
-            desc.prev_cameras = rows.ctypes.data
-            desc.num_prev_cameras = rows.shape[0]
-        m = None
-        if mask is not None:
-            nby, nbx = self.blockGrid()
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.size != nby * nbx:
-                raise ValueError(f"motionPlanes: the mask needs {nby} x {nbx} entries, got {m.size}")
-            desc.block_mask = m.ctypes.data
+        widths = dict(_lib.MOTION_PLANES, hit=8, prev_vertices=(sum(self._nv), 3))
+        self._bind_planes("motionPlanes", desc, dict(hit=hit, prev_vertices=prev_vertices), widths, ("hit", "prev_vertices"))
+        result = self._bind_planes("motionPlanes", desc, {name: out.get(name) for name in planes}, widths, outputs=planes, alloc=planes)
+        rows = self._bind_prev_cameras(desc, prev_cameras)  # noqa: F841 (kept until the call has returned, as m is)
+        m = self._bind_mask("motionPlanes", desc, mask)  # noqa: F841
         desc.flags = 0
-        ev = torch.cuda.Event()  # what torch enqueued so far (the producers of the planes, a fill of the outputs) comes first, on the device
-        ev.record(torch.cuda.current_stream(dev))
-        self.waitEvent(ev.cuda_event)
-        stats = _lib.MotionStats()
-        self._ck(self._L.pt_motion_planes(self._ctx, C.byref(desc), C.byref(stats)), "pt_motion_planes")
-        result["stats"] = stats.as_dict()
-        return result
+        return self._run_pass("pt_motion_planes", desc, _lib.MotionStats(), result)
 
     def evalTable(self, which, inp: np.ndarray, out_width: int, material=None, bsdf_mode=PT_BSDF_DISNEY) -> np.ndarray:
         inp = np.ascontiguousarray(inp, np.float32)

@@ -78,7 +78,7 @@ def test_python_facade_has_the_method():
     from optixpathtracer_amd import renderer as R
 
     assert callable(getattr(R.SampleRenderer, "renderGBuffer", None))
-    assert callable(getattr(R, "_check_gbuffer_tensor", None))
+    assert callable(getattr(R, "_check_temporal_tensor", None))  # the one plane checker of the facade
 
 
 def test_cxx_facade_compiles(tmp_path):

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/../optixpathtracer_amd/csrc"
 mkdir -p ../variants
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -fPIC -Wno-unused-result -Wno-unused-value $DEFS"
 # objects next to the library (inside the tree, not in a shared temporary directory); each compile's status is checked
-/opt/rocm/bin/hipcc $FLAGS -c pt_moments.hip -o ../variants/pt_api_$NAME.o & P1=$!
+/opt/rocm/bin/hipcc $FLAGS -c pt_lib.hip -o ../variants/pt_api_$NAME.o & P1=$!
 /opt/rocm/bin/hipcc $FLAGS -c pt_bvh_build.hip -o ../variants/pt_bvh_build_$NAME.o & P2=$!
 wait $P1
 wait $P2
