@@ -19,7 +19,7 @@
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
  * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes,
- * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes — read and write them on
+ * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -36,7 +36,7 @@
  * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
  * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
- * pt_temporal_moments, pt_modulate_planes.  A
+ * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -965,6 +965,134 @@ typedef struct pt_modulate_desc {
 } pt_modulate_desc;
 typedef struct pt_modulate_stats { uint64_t pixels; double kernel_ms; } pt_modulate_stats;
 int pt_modulate_planes(pt_ctx* ctx, const pt_modulate_desc* desc, pt_modulate_stats* stats /* may be NULL */);
+
+/* ADAPTIVE SAMPLING INSIDE THE REPROJECTION CHAIN (no reference counterpart): pt_sample_plan decides, BEFORE a frame is rendered, which 8x8
+ * blocks need new samples — where the history was lost, where it is short, where the accumulated estimate is still noisy —, and
+ * pt_temporal_carry is the temporal stage of the blocks that were not rendered: it carries their history, moments and length along the
+ * motion plane unchanged, so that the ping-pong of history_out / moments_out / length_out stays whole.  The rule is pt_render_adaptive's
+ * stopping rule per pixel, driven by the reprojected luminance moments of pt_temporal_moments and the history length in place of a per-context
+ * moments buffer and the subframe count; it works for a camera and for geometry that move every frame.  Neither call reads a colour plane.
+ *
+ * Both calls are stateless: every plane is caller-owned DEVICE memory of the context's device, frame-sized, indexed Y * width + X, and
+ * checked exactly as pt_render_gbuffer checks its planes (known to HIP, device memory of the context's device, 4-byte aligned — no wider
+ * alignment is assumed — fitting what is left of its allocation).  The eight read-only planes are pt_temporal_moments's: motion, hit,
+ * position (this frame's, pt_render_gbuffer / pt_motion_planes), prev_hit, prev_position (the previous frame's), history_in, moments_in,
+ * length_in (what the previous frame's pt_temporal_moments and pt_temporal_carry left).  All eight are required.
+ * Which pixels ("the set"): exactly those pt_render_gbuffer would write with the same mask — the rank's owned pixels, view pixels only while
+ * views are set, whole blocks of block_mask (HOST memory, nbx * nby bytes with nbx = (width + 7) / 8, nby = (height + 7) / 8, block (bx, by)
+ * at by * nbx + bx, non-zero = named; NULL: every block).  The call's block set: the blocks that hold at least one pixel of the set.
+ * Each pixel works inside its own rectangle (x0, y0, wr, hr): its view (found by the pixel's 8x8 block), or the whole frame without views;
+ * (x, y) are its local coordinates there.  Arithmetic — float32 throughout, one rounding per operation, no fused multiply-add, in exactly
+ * the order stated; float32 NumPy evaluating this reproduces every output bit for bit (a NaN is a NaN: its sign and payload are not
+ * specified), with dot3 and sel_max0 (sel_max0(v) = v > 0 ? v : 0, so a NaN gives 0) as pt_temporal_accumulate and pt_filter_planes define them.
+ *
+ * Step G, the gather, for a pixel p of the set — pt_temporal_moments's steps 2, 3 and 4, restated in full:
+ *   G1. px = (float)x + motion[p].x;  py = (float)y + motion[p].y.  The lookup fails (no tap counts) when
+ *       (px >= -1 && px <= wr && py >= -1 && py <= hr) is false (a NaN motion word fails this way).  Otherwise flx = floorf(px),
+ *       ix = (int)flx, fx = px - flx, likewise fly, iy, fy; wx0 = 1 - fx, wx1 = fx, wy0 = 1 - fy, wy1 = fy; tap weights w_ij = wx_i * wy_j.
+ *   G2. Tap (i, j) is frame pixel q = (x0 + ix + i, y0 + iy + j).  It counts when it lies inside the rectangle, w_ij > 0,
+ *       length_in[q] >= 1, the three colour words of history_in[q] and both words of moments_in[q] are finite (exponent-bit test) and the
+ *       geometry agrees: with hit[p].prim < 0 (a miss) it needs prev_hit[q].prim < 0; otherwise prev_hit[q].mesh == hit[p].mesh,
+ *       dot3(ng_p, ng_q) >= normal_cos and fabsf(dot3(ng_p, prev_position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t.
+ *   G3. Tap order (0,0), (1,0), (0,1), (1,1); a tap that does not count contributes +0.0f.  Wsum = ((w00 + w10) + w01) + w11; Hsum the same
+ *       sum of w_ij * history_in[q].xyz per component; Msum the same sum of w_ij * moments_in[q] per component; nprev the minimum of
+ *       length_in[q] over the counting taps;  valid = (at least one tap counts) && Wsum >= min_weight.
+ *   For a valid pixel H = Hsum / Wsum and M = Msum / Wsum, per component.
+ *
+ * pt_sample_plan: which blocks to render this frame.  Per pixel p of the set, after step G:
+ *   lost(p)  = !valid.
+ *   short(p) = valid && nprev < (float)min_length.
+ *   noisy(p), for a valid pixel that is not short: var = sel_max0(M.y - M.x * M.x); B = M.x + dark_floor;
+ *            rhs = (((threshold * threshold) * nprev) * B) * B; noisy = !(var <= rhs) — a NaN makes it noisy.  (pt_render_adaptive's rule
+ *            with the reprojected moments and the history length.)  Otherwise noisy(p) is false.
+ * Per block b = (bx, by) of the call's block set: L = the number of its lost pixels, S = the number of its short or noisy pixels (integer
+ * counts over the block's pixels of the set);
+ *   refresh = refresh_period > 0 && ((uint64)bx + 3 * (uint64)by + frame_index) % refresh_period == 0;
+ *   sampled = L >= 1 || S >= min_pixels || refresh;   block_mask_out[by * nbx + bx] = sampled ? 1 : 0.
+ * Every other block of the frame gets 0; block_mask_out (HOST memory, nbx * nby bytes, required) is written whole, once, when the call
+ * succeeds; it may be the array block_mask points to.  The refresh walks every block through a forced sample once per refresh_period
+ * frames when frame_index counts frames (0: never), whatever its statistics say.  A block with a lost pixel is always sampled: that is what
+ * lets pt_temporal_carry below never meet a pixel it cannot carry.
+ * stats: blocks — blocks of the call's block set; sampled — those with sampled; by_lost — L >= 1; by_need — not by_lost, S >= min_pixels;
+ * by_refresh — sampled by the refresh only (sampled = by_lost + by_need + by_refresh); pixels, lost, needy — the set's pixels, the lost
+ * ones, the short or noisy ones; kernel_ms — device time of the pass (hipEvents; the upload of the block set and the copy of the answer
+ * are outside it).
+ * Nothing on the device is written except temporaries of the call, so there are no overlap rules: the planes may alias one another.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written, block_mask_out untouched): a null ctx, desc or
+ * block_mask_out; no pt_resize yet; a plane NULL; a plane that fails the pointer checks; flags != 0; a parameter out of its range or not
+ * finite (the ranges stand beside the fields).
+ *
+ * pt_temporal_carry: the temporal stage for pixels that got no new sample.  Per pixel p of the set, after step G,
+ *   valid:      history_out[p] = (H, 1.0f); moments_out[p] = M; length_out[p] = nprev (the length is carried: not incremented, not capped);
+ *               variance_out[p] = sel_max0(M.y - M.x * M.x).
+ *   not valid:  history_out[p] = three NaN words and 1.0f (pt_filter_planes treats such a pixel as inert and as no tap for its neighbours;
+ *               the next frame's gather rejects it); moments_out[p] = (0, 0); length_out[p] = 0; variance_out[p] = 0; stats->lost counts it.
+ * No other pixel is written in any output; zero pixels launch nothing and return PT_OK.  GUARANTEE: called with the complement of a plan's
+ * block_mask_out (restricted by the plan's block_mask, if it had one), and the same planes and normal_cos / plane_eps / min_weight as that
+ * plan, lost is 0 — both calls evaluate the same step G on the same words, and the plan samples every block that holds a lost pixel.
+ * Overlap: the four outputs may overlap no other plane; the read-only planes may alias one another (prev_hit == hit, say).
+ * stats: pixels processed; carried — the valid ones; lost = pixels - carried; kernel_ms — device time of the pass (hipEvents; the mask
+ * compaction included when there is a mask).
+ * Refused with PT_ERR_INVALID (nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; a required plane NULL (all but
+ * variance_out and block_mask); a plane that fails the pointer checks; a forbidden overlap; flags != 0; a parameter out of its range.
+ *
+ * Ordering and state, both calls, as pt_temporal_moments: the call first waits for the frames in flight and completes queued queries, runs
+ * on pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns; the planes must be complete before the call.  It reads and
+ * writes no context state except through the pointers the caller passed.
+ * The loop (examples/adaptive_svgf_loop.py), per frame: pt_render_gbuffer; pt_sample_plan -> mask; pt_render_mask(mask);
+ * pt_temporal_moments(mask, color = PT_BUF_ACCUM, color_scale = k + 1, PT_TMOM_CLEAR_COLOR); pt_temporal_carry(the complement of mask);
+ * pt_filter_planes on all pixels.  With min_length = 65535 and min_pixels = 1 every block is sampled (a history is shorter than 65535 whenever
+ * max_history is) and the loop is the unmasked one, bit for bit.
+ * ALBEDO: run this loop with albedo = NULL in pt_temporal_moments and without pt_modulate_planes.  PT_BUF_ALBEDO is written by the render, so
+ * in a block that was not rendered it is stale: it holds the first-hit albedo of an older camera, and demodulating or remodulating with it
+ * would be wrong.  (A pixel-centre albedo plane derived from the hit plane is what lets this loop demodulate; it is not part of this
+ * interface.)
+ * Not part of this interface: asynchronous variants, pt_multi_* wrappers, masks in device memory, per-block sample counts. */
+typedef struct pt_plan_desc {
+    const float* motion;        /* w*h x 2  this frame's motion plane */
+    const void*  hit;           /* w*h x pt_hit, this frame */
+    const float* position;      /* w*h x 4, this frame */
+    const void*  prev_hit;      /* previous frame's hit plane */
+    const float* prev_position;
+    const float* history_in;    /* w*h x 4  accumulated colour after the previous frame */
+    const float* moments_in;    /* w*h x 2  accumulated (lum, lum * lum) after the previous frame */
+    const float* length_in;     /* w*h      per-pixel history length (whole numbers; 0 = no history) */
+    const uint8_t* block_mask;  /* HOST, as pt_render_gbuffer, or NULL */
+    uint8_t* block_mask_out;    /* HOST, nbx*nby bytes: 1 = sample the block; required */
+    float normal_cos;           /* [-1,1] */
+    float plane_eps;            /* finite, >= 0 */
+    float min_weight;           /* [0,1] */
+    float threshold;            /* finite, >= 0: the relative standard error a pixel is allowed (pt_adaptive_params.threshold) */
+    float dark_floor;           /* finite, >= 0 */
+    uint32_t min_length;        /* 0..65535: a history shorter than this always asks for samples */
+    uint32_t min_pixels;        /* 1..64: short or noisy pixels that make a block sampled */
+    uint32_t refresh_period;    /* 0..65535; 0 = no refresh */
+    uint32_t frame_index;       /* any value; only the refresh reads it */
+    uint32_t flags;             /* 0 */
+} pt_plan_desc;
+typedef struct pt_plan_stats { uint64_t blocks, sampled, by_lost, by_need, by_refresh, pixels, lost, needy; double kernel_ms; } pt_plan_stats;
+int pt_sample_plan(pt_ctx* ctx, const pt_plan_desc* desc, pt_plan_stats* stats /* may be NULL */);
+typedef struct pt_carry_desc {
+    const float* motion;        /* the eight read-only planes of pt_plan_desc */
+    const void*  hit;
+    const float* position;
+    const void*  prev_hit;
+    const float* prev_position;
+    const float* history_in;
+    const float* moments_in;
+    const float* length_in;
+    float* history_out;         /* w*h x 4 */
+    float* moments_out;         /* w*h x 2 */
+    float* length_out;          /* w*h */
+    float* variance_out;        /* w*h or NULL */
+    const uint8_t* block_mask;  /* HOST, as pt_render_gbuffer, or NULL */
+    float normal_cos;           /* [-1,1] */
+    float plane_eps;            /* finite, >= 0 */
+    float min_weight;           /* [0,1] */
+    uint32_t flags;             /* 0 */
+} pt_carry_desc;
+typedef struct pt_carry_stats { uint64_t pixels, carried, lost; double kernel_ms; } pt_carry_stats;
+int pt_temporal_carry(pt_ctx* ctx, const pt_carry_desc* desc, pt_carry_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

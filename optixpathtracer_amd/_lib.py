@@ -27,6 +27,7 @@ EXPORTS = [
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
     "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate", "pt_filter_planes",
     "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes", "pt_temporal_moments", "pt_modulate_planes",
+    "pt_sample_plan", "pt_temporal_carry",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -177,6 +178,43 @@ class ModulateStats(C.Structure):  # pt_modulate_stats
 # the planes of pt_modulate_planes: 32-bit words per pixel (frame_rgba8 holds packed bytes, the others float32)
 MODULATE_PLANES = {"color": 4, "albedo": 4, "out": 4, "frame_rgba8": 1}
 MODULATE_OUTPUTS = ("out", "frame_rgba8")
+
+
+class PlanDesc(C.Structure):  # pt_plan_desc
+    _fields_ = [("motion", C.c_void_p), ("hit", C.c_void_p), ("position", C.c_void_p), ("prev_hit", C.c_void_p), ("prev_position", C.c_void_p),
+                ("history_in", C.c_void_p), ("moments_in", C.c_void_p), ("length_in", C.c_void_p), ("block_mask", C.c_void_p),
+                ("block_mask_out", C.c_void_p),
+                ("normal_cos", C.c_float), ("plane_eps", C.c_float), ("min_weight", C.c_float), ("threshold", C.c_float), ("dark_floor", C.c_float),
+                ("min_length", C.c_uint32), ("min_pixels", C.c_uint32), ("refresh_period", C.c_uint32), ("frame_index", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class PlanStats(C.Structure):  # pt_plan_stats
+    _fields_ = [("blocks", C.c_uint64), ("sampled", C.c_uint64), ("by_lost", C.c_uint64), ("by_need", C.c_uint64), ("by_refresh", C.c_uint64),
+                ("pixels", C.c_uint64), ("lost", C.c_uint64), ("needy", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class CarryDesc(C.Structure):  # pt_carry_desc
+    _fields_ = [("motion", C.c_void_p), ("hit", C.c_void_p), ("position", C.c_void_p), ("prev_hit", C.c_void_p), ("prev_position", C.c_void_p),
+                ("history_in", C.c_void_p), ("moments_in", C.c_void_p), ("length_in", C.c_void_p), ("history_out", C.c_void_p),
+                ("moments_out", C.c_void_p), ("length_out", C.c_void_p), ("variance_out", C.c_void_p), ("block_mask", C.c_void_p),
+                ("normal_cos", C.c_float), ("plane_eps", C.c_float), ("min_weight", C.c_float), ("flags", C.c_uint32)]
+
+
+class CarryStats(C.Structure):  # pt_carry_stats
+    _fields_ = [("pixels", C.c_uint64), ("carried", C.c_uint64), ("lost", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_sample_plan and pt_temporal_carry: float32 words per pixel
+PLAN_PLANES = {"motion": 2, "hit": 8, "position": 4, "prev_hit": 8, "prev_position": 4, "history_in": 4, "moments_in": 2, "length_in": 1}
+CARRY_PLANES = dict(PLAN_PLANES, history_out=4, moments_out=2, length_out=1, variance_out=1)
+CARRY_OUTPUTS = ("history_out", "moments_out", "length_out", "variance_out")
 
 
 class AdaptiveParams(C.Structure):  # pt_adaptive_params
@@ -390,6 +428,8 @@ def load_library() -> C.CDLL:
     L.pt_motion_planes.argtypes = [vp, C.POINTER(MotionDesc), C.POINTER(MotionStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
+    L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]
+    L.pt_temporal_carry.argtypes = [vp, C.POINTER(CarryDesc), C.POINTER(CarryStats)]
     L.pt_set_views.argtypes = [vp, C.POINTER(View), u32]
     L.pt_get_views.argtypes = [vp, C.POINTER(View), u32, C.POINTER(u32)]
     L.pt_set_view_cameras.argtypes = [vp, vp, u32]

@@ -343,6 +343,23 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
+    // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
+    // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.
+    pt_plan_stats samplePlan(const pt_plan_desc& d, pt_plan_stats* stats = nullptr) {
+        pt_plan_stats s{};
+        ck(pt_sample_plan(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
+    // The temporal stage of the blocks that were not rendered (pt_temporal_carry): history, moments and length reprojected and written
+    // unchanged.  With the complement of a plan's mask and the plan's planes and parameters, `lost` is 0.
+    pt_carry_stats temporalCarry(const pt_carry_desc& d, pt_carry_stats* stats = nullptr) {
+        pt_carry_stats s{};
+        ck(pt_temporal_carry(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     static std::vector<pt_mesh_update> mesh_updates(const Model* model, const std::vector<uint32_t>& meshes) {
         static_assert(sizeof(float3) == 3 * sizeof(float), "TriangleMesh::vertex must stay float3-packed");
         std::vector<pt_mesh_update> u;

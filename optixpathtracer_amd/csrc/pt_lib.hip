@@ -15,3 +15,4 @@
 #include "pt_filter.hip"
 #include "pt_motion.hip"
 #include "pt_moments.hip"
+#include "pt_plan.hip"

@@ -834,6 +834,62 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_modulate_planes", desc, _lib.ModulateStats(), result)
 
+    def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
+                   plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
+                   frame_index=0) -> dict:
+        """Which 8x8 blocks of the coming frame need new samples (pt_sample_plan, include/pt_amd.h: the rule, in full): a block is sampled
+        when the reprojection of the history loses one of its pixels, when at least min_pixels of them have a history shorter than
+        min_length or reprojected luminance moments that still miss `threshold` (renderAdaptive's rule per pixel, with the history length
+        in place of the subframe count), or when the refresh (every refresh_period frames, by frame_index) names it.
+
+        The eight planes are temporalMoments's — motion, hit, position (renderGBuffer's of this frame), prev_hit, prev_position (last
+        frame's), history_in, moments_in, length_in (what last frame's temporalMoments and temporalCarry left) — as CUDA float32 tensors
+        on the context's device (dense, any 4-byte-aligned storage offset) or raw device pointers; none is written.  mask: 8x8 blocks as
+        renderMask takes them, None = every block; a block outside it is never sampled.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
+        the plan is complete.  Returns {"mask": uint8 (nby, nbx), what renderMask and the passes' `mask` take (its complement, within the
+        input mask, is temporalCarry's), "stats": {blocks, sampled, by_lost, by_need, by_refresh, pixels, lost, needy, kernel_ms}}."""
+        given = dict(motion=motion, hit=hit, position=position, prev_hit=prev_hit, prev_position=prev_position, history_in=history_in,
+                     moments_in=moments_in, length_in=length_in)
+        desc = _lib.PlanDesc()
+        self._bind_planes("samplePlan", desc, given, _lib.PLAN_PLANES, set(given))
+        m = self._bind_mask("samplePlan", desc, mask)  # noqa: F841 (kept until the call has returned)
+        for name, value, top in (("min_length", min_length, 65535), ("min_pixels", min_pixels, 64), ("refresh_period", refresh_period, 65535),
+                                 ("frame_index", frame_index, 2**32 - 1)):
+            if not 0 <= int(value) < 2**32:
+                raise ValueError(f"samplePlan: {name} must be in [{1 if name == 'min_pixels' else 0},{top}]")
+            setattr(desc, name, int(value))
+        desc.normal_cos, desc.plane_eps, desc.min_weight = float(normal_cos), float(plane_eps), float(min_weight)
+        desc.threshold, desc.dark_floor = float(threshold), float(dark_floor)
+        desc.flags = 0
+        nby, nbx = self.blockGrid()
+        out = np.zeros((nby, nbx), np.uint8)
+        desc.block_mask_out = out.ctypes.data
+        return self._run_pass("pt_sample_plan", desc, _lib.PlanStats(), dict(mask=out))
+
+    def temporalCarry(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, history_out=None, moments_out=None,
+                      length_out=None, variance_out=None, variance=True, mask=None, normal_cos=0.9, plane_eps=0.01, min_weight=0.25) -> dict:
+        """The temporal stage of the pixels that got no new sample (pt_temporal_carry, include/pt_amd.h): reprojects history, moments and
+        length along the motion plane exactly as temporalMoments does and writes them unchanged — the length is carried, not incremented;
+        a pixel whose history cannot be reprojected gets NaN colour words and length 0 and is counted in stats["lost"].  Called with the
+        complement of samplePlan's mask and samplePlan's planes and normal_cos / plane_eps / min_weight, lost is 0.
+
+        The planes are temporalMoments's without color and albedo, the outputs likewise: allocated with torch, zero-filled, when None
+        (variance_out unless variance=False); pixels outside the views, the mask or the rank's partition are not written, so the outputs
+        of a temporalMoments call on the plan's mask are completed in place by passing them here.  They may overlap no other plane.
+        Ordering is on the device, as temporalMoments.  Returns {"history_out", "moments_out", "length_out", "variance_out": the tensor
+        (None for a raw pointer or an absent plane), "stats": {pixels, carried, lost, kernel_ms}}."""
+        given = dict(motion=motion, hit=hit, position=position, prev_hit=prev_hit, prev_position=prev_position, history_in=history_in,
+                     moments_in=moments_in, length_in=length_in, history_out=history_out, moments_out=moments_out, length_out=length_out,
+                     variance_out=variance_out)
+        desc = _lib.CarryDesc()
+        result = self._bind_planes("temporalCarry", desc, given, _lib.CARRY_PLANES, set(given) - {"variance_out"}, _lib.CARRY_OUTPUTS,
+                                   alloc=_lib.CARRY_OUTPUTS if variance else _lib.CARRY_OUTPUTS[:3])
+        m = self._bind_mask("temporalCarry", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.normal_cos, desc.plane_eps, desc.min_weight = float(normal_cos), float(plane_eps), float(min_weight)
+        desc.flags = 0
+        return self._run_pass("pt_temporal_carry", desc, _lib.CarryStats(), result)
+
     def vertexCount(self):
         """(vertices, triangles) of the context, summed over its meshes (pt_vertex_count)."""
         nv, nt = C.c_uint32(), C.c_uint32()
