@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""adaptive_svgf_albedo_loop.py — adaptive_svgf_loop.py with demodulation: the SVGF loop that path-traces only the blocks that need samples
+AND filters irradiance rather than colour, so texture detail survives the a-trous filter.
+
+adaptive_svgf_loop.py cannot demodulate: PT_BUF_ALBEDO is written by the render, so in a block the plan left out it holds the first-hit albedo
+of an older camera.  surfacePlanes derives the albedo from this frame's hit plane instead — every pixel, this frame's camera, no rays — and
+that plane is what temporalMoments divides by and modulatePlanes multiplies back in.  Per frame:
+  1. renderGBuffer: hit, position and motion against LAST frame's camera;
+  2. surfacePlanes on all pixels: the albedo under every pixel's centre (the texcoord table is taken once, before the loop);
+  3. samplePlan: the 8x8 blocks that need samples;
+  4. renderMask(mask): this frame's samples for those blocks only, into the accumulation buffer;
+  5. temporalMoments on the mask with PT_BUF_ACCUM as the colour and the surface albedo: demodulated history, moments, length, variance;
+  6. temporalCarry on the mask's complement: the history is demodulated already and is carried unchanged;
+  7. filterPlanes on all pixels, on demodulated colour;
+  8. modulatePlanes with the surface albedo: the displayed frame.
+
+  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--out-dir .]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from optixpathtracer_amd import renderer as R  # noqa: E402
+from optixpathtracer_amd import scenes  # noqa: E402
+
+SCENES = {
+    "textured": (scenes.textured_scene, dict(eye=(3.0, 2.5, -4.5), lookat=(0.0, 0.6, 0.5), up=(0.0, 1.0, 0.0), fovY=45.0)),
+    "two_box": (lambda: scenes.two_box_scene(shadow_catcher=False), scenes.TWO_BOX_CAMERA),
+}
+
+
+def orbit(cam, angle):
+    """the camera turned by `angle` radians about the vertical axis through its look-at point"""
+    e, l = np.asarray(cam["eye"], np.float64), np.asarray(cam["lookat"], np.float64)
+    d = e - l
+    c, s = np.cos(angle), np.sin(angle)
+    return dict(cam, eye=(float(l[0] + c * d[0] + s * d[2]), float(e[1]), float(l[2] - s * d[0] + c * d[2])))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", choices=sorted(SCENES), default="textured")
+    ap.add_argument("--size", type=int, nargs=2, default=[960, 540])
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--spp", type=int, default=1)
+    ap.add_argument("--max-history", type=int, default=32)
+    ap.add_argument("--threshold", type=float, default=0.25, help="the relative standard error a pixel's accumulated luminance may keep")
+    ap.add_argument("--dark-floor", type=float, default=0.05)
+    ap.add_argument("--plan-min-length", type=int, default=4, help="a history shorter than this always asks for samples")
+    ap.add_argument("--min-pixels", type=int, default=8, help="short or noisy pixels that make a block sampled")
+    ap.add_argument("--refresh", type=int, default=16, help="every block is sampled once in this many frames; 0: no refresh")
+    ap.add_argument("--iterations", type=int, default=5)
+    ap.add_argument("--sigma-lum", type=float, default=4.0)
+    ap.add_argument("--min-length", type=int, default=4)
+    ap.add_argument("--out-dir", default=".")
+    args = ap.parse_args()
+    import torch
+
+    dev = "cuda:0"
+    w, h = args.size
+    make, cam0 = SCENES[args.scene]
+    sample = R.SampleRenderer(make())
+    sample.setProbe(scenes.sky_probe(1024, 512).BuildCDF())
+    sample.launchParams.samples_per_launch = args.spp
+    sample.resize((w, h))
+    sample.uploadAccum(np.zeros((h, w, 4), np.float32))
+
+    def planes(k):
+        return torch.zeros((h, w, k) if k > 1 else (h, w), device=dev)
+
+    # two sets of G-buffer planes (this frame's, last frame's), two of history, moments and length: everything is reused
+    gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2)) for _ in range(2)]
+    history, moments, length = [planes(4) for _ in range(2)], [planes(2) for _ in range(2)], [planes(1) for _ in range(2)]
+    variance, filtered, scratch, albedo, final = planes(1), planes(4), planes(4), planes(4), planes(4)
+    frame = torch.zeros((h, w), dtype=torch.int32, device=dev)
+    accum = sample.deviceBuffer(R.PT_BUF_ACCUM)
+    table = sample.copyTexcoordsDevice()  # the scene's texcoords per primitive: once, whatever moves later
+    cam = R.make_camera(cam0, w / h)
+    for k in range(args.frames):
+        prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
+        cur, old = gbuf[k & 1], gbuf[~k & 1]
+        i, o = k & 1, ~k & 1
+        sample.setCamera(cam)
+        g = sample.renderGBuffer(("hit", "position", "motion"), prev_cameras=prev, out=cur)
+        s = sample.surfacePlanes(cur["hit"], table, out=dict(albedo=albedo))
+        geo = (cur["motion"], cur["hit"], cur["position"], old["hit"], old["position"], history[i], moments[i], length[i])
+        outs = dict(history_out=history[o], moments_out=moments[o], length_out=length[o], variance_out=variance)
+        p = sample.samplePlan(*geo, threshold=args.threshold, dark_floor=args.dark_floor, min_length=args.plan_min_length, min_pixels=args.min_pixels,
+                              refresh_period=args.refresh, frame_index=k)
+        mask = p["mask"]
+        sample.launchParams.frame.subframe_index = k
+        rendered = sample.renderMask(mask)
+        t = sample.temporalMoments(accum, *geo, albedo=albedo, **outs, mask=mask, color_scale=float(k + 1), max_history=args.max_history, clear_color=True)
+        c = sample.temporalCarry(*geo, **outs, mask=mask == 0)
+        assert c["stats"]["lost"] == 0  # the plan samples every block that holds a pixel the carry could not carry
+        f = sample.filterPlanes(history[o], cur["hit"], cur["position"], variance=variance, length=length[o], out=filtered, scratch=scratch,
+                                iterations=args.iterations, sigma_lum=args.sigma_lum, min_length=args.min_length)
+        m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=frame)
+        ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
+        print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
+              f"{ss['textured']} of {ss['hits']} hits textured; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
+              f"plan {ps['kernel_ms']:.3f} ms, colour {sample.stats()['render_ms']:.2f} ms, temporal {ts['kernel_ms']:.3f} ms, "
+              f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms")
+    np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_final.npy"), final.cpu().numpy())
+    np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_frame.npy"), frame.cpu().numpy().view(np.uint32))
+    print(f"wrote adaptive_svgf_albedo_final.npy and adaptive_svgf_albedo_frame.npy to {args.out_dir}")
+    sample.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -19,7 +19,7 @@
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
  * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes,
- * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry — read and write them on
+ * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -36,7 +36,7 @@
  * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
  * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
- * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry.  A
+ * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -1045,8 +1045,8 @@ int pt_modulate_planes(pt_ctx* ctx, const pt_modulate_desc* desc, pt_modulate_st
  * max_history is) and the loop is the unmasked one, bit for bit.
  * ALBEDO: run this loop with albedo = NULL in pt_temporal_moments and without pt_modulate_planes.  PT_BUF_ALBEDO is written by the render, so
  * in a block that was not rendered it is stale: it holds the first-hit albedo of an older camera, and demodulating or remodulating with it
- * would be wrong.  (A pixel-centre albedo plane derived from the hit plane is what lets this loop demodulate; it is not part of this
- * interface.)
+ * would be wrong.  (pt_surface_planes below derives a pixel-centre albedo plane from the hit plane; with it the loop demodulates:
+ * examples/adaptive_svgf_albedo_loop.py.)
  * Not part of this interface: asynchronous variants, pt_multi_* wrappers, masks in device memory, per-block sample counts. */
 typedef struct pt_plan_desc {
     const float* motion;        /* w*h x 2  this frame's motion plane */
@@ -1093,6 +1093,86 @@ typedef struct pt_carry_desc {
 } pt_carry_desc;
 typedef struct pt_carry_stats { uint64_t pixels, carried, lost; double kernel_ms; } pt_carry_stats;
 int pt_temporal_carry(pt_ctx* ctx, const pt_carry_desc* desc, pt_carry_stats* stats /* may be NULL */);
+
+/* PIXEL-CENTRE ALBEDO FROM THE HIT PLANE (no reference counterpart): the albedo and the texcoord of the surface point under the centre of
+ * every pixel, computed from pt_render_gbuffer's hit plane alone.  PT_BUF_ALBEDO is written by the render — at a jittered sample, and only
+ * where the render went — so in a block that pt_sample_plan left out it holds the first-hit albedo of an older camera.  pt_surface_planes
+ * gives the plane that pt_temporal_moments and pt_modulate_planes need in such a loop: every pixel of the call, this frame's camera, no
+ * rays, no state.
+ *
+ * pt_copy_texcoords_device: writes the scene's texcoords per primitive into caller-owned DEVICE memory: triangles x 6 f32 in global
+ * primitive order (pt_hit.prim's), uv0.x, uv0.y, uv1.x, uv1.y, uv2.x, uv2.y — the texcoords of the primitive's three vertices as pt_create
+ * received them (mesh_desc.texcoord[index[3*prim + k]]; zeros for the vertices of a mesh without texcoords).  bytes must equal
+ * triangles * 24 (pt_vertex_count).  In a scene without a textured mesh (no mesh has both a texture id >= 0 and texcoords) the table is
+ * zero-filled.  dev_dst is checked exactly as pt_copy_vertices_device checks its destination (4-byte aligned is enough).  The call first
+ * waits for the frames in flight and completes queued queries, runs on pt_stream(ctx) under the STREAM CONTRACT and is complete when it
+ * returns.  The table depends on the scene only: pt_update_meshes* (refit or rebuild) and pt_transform_meshes leave it valid, so a loop
+ * takes it once.  PT_ERR_INVALID (nothing written) for a null ctx, wrong bytes, a pointer that fails the checks.
+ *
+ * pt_surface_planes.  Every plane is caller-owned DEVICE memory of the context's device, frame-sized, indexed Y * width + X, and checked
+ * exactly as pt_render_gbuffer checks its planes (4-byte aligned — no wider alignment is assumed); prim_texcoords is checked against
+ * triangles * 24 bytes.  block_mask is HOST memory.
+ * Which pixels: exactly those pt_motion_planes would process with the same mask — the rank's owned pixels, view pixels only while views are
+ * set, whole blocks of block_mask (NULL: every block).  No other pixel is written in either output.  Zero pixels launch nothing and return
+ * PT_OK.  The pass is pixel-local and reads no camera.
+ * Arithmetic per pixel p — float32 throughout, one rounding per operation, no fused multiply-add, in exactly this order; float32 NumPy
+ * evaluating this reproduces every output bit for bit.  `triangles` is pt_vertex_count's; only the first four words of hit[p] are read:
+ *   - hit[p].prim < 0 (a miss).  albedo[p] = (0, 0, 0, 1) — what the frame's resolve leaves in PT_BUF_ALBEDO for a primary miss, and what
+ *     pt_temporal_moments' denominator turns into 1;  texcoord[p] = (0, 0).
+ *   - hit[p].prim >= triangles.  The plane is caller memory and is not trusted: no address is formed from it.  The outputs are those of a
+ *     miss, and stats->stale counts the pixel.
+ *   - 0 <= hit[p].prim < triangles (stats->hits counts these).  mesh = the context's own mesh of primitive prim (hit[p].mesh is not read).
+ *       albedo[p] = (material[mesh].color, 1.0f);  texcoord[p] = (0, 0)
+ *     unless the mesh is textured (diffuse_texture_id = tid >= 0 AND texcoords, as the shade kernel decides it).  Then, with
+ *     u = hit[p].u, v = hit[p].v (the weights of vertex 1 and vertex 2) and c = prim_texcoords[6*prim ..]:
+ *         w0 = (1.0f - u) - v
+ *         s  = ((w0 * c[0]) + (u * c[2])) + (v * c[4])
+ *         t  = ((w0 * c[1]) + (u * c[3])) + (v * c[5])
+ *         albedo[p] = (tex2D(texture[tid], s, t).xyz, 1.0f);  texcoord[p] = (s, t)
+ *     and stats->textured counts the pixel.  This is the shade kernel's expression with the hit record's own barycentrics.
+ *   - tex2D(texture of W x H RGBA8 texels, s, t): wrap addressing, bilinear, 8 fractional bits, normalised bytes:
+ *         x  = (s - floorf(s)) * (float)W;             y  = (t - floorf(t)) * (float)H
+ *         xB = x - 0.5f;                               yB = y - 0.5f
+ *         fi = floorf(xB);                             fj = floorf(yB)
+ *         alpha = floorf(((xB - fi) * 256.0f) + 0.5f) * (1.0f / 256.0f)
+ *         beta  = floorf(((yB - fj) * 256.0f) + 0.5f) * (1.0f / 256.0f)
+ *         i0 = (int)fi mod W;  i1 = ((int)fi + 1) mod W;  j0 = (int)fj mod H;  j1 = ((int)fj + 1) mod H     (mod: the result in [0, W) / [0, H))
+ *         T(i, j)[k] = (float)(byte k of texel (i, j)) / 255.0f          (byte 0 = red = the lowest byte of the 32-bit texel; row 0 first)
+ *         out[k] = (((((1.0f - alpha) * (1.0f - beta)) * T(i0, j0)[k]) + ((alpha * (1.0f - beta)) * T(i1, j0)[k]))
+ *                   + (((1.0f - alpha) * beta) * T(i0, j1)[k])) + ((alpha * beta) * T(i1, j1)[k])
+ *     — pt_eval_table(which = 7) evaluates the same function for texture 0.
+ *   - Non-finite u or v in a caller's record (or texcoords that make s or t non-finite) fault nothing: the texel indices are clamped into
+ *     the image before any texel is read.  On a textured mesh texcoord[p] then holds s and t as computed (NaN or infinite) and
+ *     albedo[p].xyz are NaN (payload unspecified), albedo[p].w is 1.0f; on an untextured mesh u and v are not read at all.
+ * Overlap: albedo and texcoord may overlap no other plane nor prim_texcoords; hit and prim_texcoords are only read.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet;
+ * flags != 0; both outputs NULL; a plane that fails the pointer checks; a forbidden overlap; prim_texcoords NULL when the scene has a
+ * textured mesh.  On a scene without one prim_texcoords is ignored (NULL or not).
+ * Ordering and state, as pt_motion_planes: the call first waits for the frames in flight and completes queued queries, runs on
+ * pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns.  It reads the context's materials, textures and
+ * primitive-to-mesh table (none of which pt_update_meshes* changes) and writes no context state: the frame buffers, the accumulation, the
+ * adaptive state, the schedule trial and pt_stats are as they were.
+ * The loop (examples/adaptive_svgf_albedo_loop.py), per frame: pt_render_gbuffer; pt_surface_planes on all pixels; pt_sample_plan -> mask;
+ * pt_render_mask(mask); pt_temporal_moments(mask, albedo = the surface albedo); pt_temporal_carry(the complement of mask) — the history is
+ * demodulated already and is carried unchanged; pt_filter_planes; pt_modulate_planes(albedo = the surface albedo).
+ * Against PT_BUF_ALBEDO: that buffer averages the albedo at the JITTERED first hits of the frame's samples, this plane is the albedo at
+ * the pixel's centre; they agree bit for bit wherever every sample of the pixel meets one untextured mesh.
+ * stats: pixels processed; hits, stale and textured among them; device time of the pass (hipEvents; the mask compaction included when
+ * there is a mask).
+ * Not part of this interface: emission, roughness or normal planes, texture LOD (mip-mapping), an asynchronous variant, a pt_multi_*
+ * wrapper (per-rank calls through pt_multi_ctx work), any change to pt_render_gbuffer or pt_temporal_moments. */
+int pt_copy_texcoords_device(pt_ctx* ctx, float* dev_dst, size_t bytes);
+enum pt_surface_flags { PT_SURFACE_RESERVED = 0 };  /* no flag defined yet: flags must be 0 */
+typedef struct pt_surface_desc {
+    const void*  hit;             /* w*h x pt_hit, this frame (pt_render_gbuffer); required */
+    const float* prim_texcoords;  /* triangles x 6 f32 (pt_copy_texcoords_device); required iff the scene has a textured mesh */
+    float* albedo;                /* w*h x 4  or NULL */
+    float* texcoord;              /* w*h x 2  or NULL */
+    const uint8_t* block_mask;    /* HOST, as pt_render_gbuffer, or NULL */
+    uint32_t flags;               /* 0 */
+} pt_surface_desc;
+typedef struct pt_surface_stats { uint64_t pixels, hits, stale, textured; double kernel_ms; } pt_surface_stats;
+int pt_surface_planes(pt_ctx* ctx, const pt_surface_desc* desc, pt_surface_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -27,7 +27,7 @@ EXPORTS = [
     "pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive",
     "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate", "pt_filter_planes",
     "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes", "pt_temporal_moments", "pt_modulate_planes",
-    "pt_sample_plan", "pt_temporal_carry",
+    "pt_sample_plan", "pt_temporal_carry", "pt_copy_texcoords_device", "pt_surface_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -136,6 +136,22 @@ class MotionStats(C.Structure):  # pt_motion_stats
 
 # the output planes of pt_motion_planes: float32 words per pixel
 MOTION_PLANES = {"motion": 2, "prev_point": 4, "prev_surface": 8}
+
+
+class SurfaceDesc(C.Structure):  # pt_surface_desc
+    _fields_ = [("hit", C.c_void_p), ("prim_texcoords", C.c_void_p), ("albedo", C.c_void_p), ("texcoord", C.c_void_p), ("block_mask", C.c_void_p),
+                ("flags", C.c_uint32)]
+
+
+class SurfaceStats(C.Structure):  # pt_surface_stats
+    _fields_ = [("pixels", C.c_uint64), ("hits", C.c_uint64), ("stale", C.c_uint64), ("textured", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the output planes of pt_surface_planes: float32 words per pixel
+SURFACE_PLANES = {"albedo": 4, "texcoord": 2}
 
 
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
@@ -426,6 +442,8 @@ def load_library() -> C.CDLL:
     L.pt_vertex_count.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.pt_copy_vertices_device.argtypes = [vp, vp, C.c_size_t]
     L.pt_motion_planes.argtypes = [vp, C.POINTER(MotionDesc), C.POINTER(MotionStats)]
+    L.pt_copy_texcoords_device.argtypes = [vp, vp, C.c_size_t]
+    L.pt_surface_planes.argtypes = [vp, C.POINTER(SurfaceDesc), C.POINTER(SurfaceStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

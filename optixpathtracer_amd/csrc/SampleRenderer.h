@@ -326,6 +326,24 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The scene's texcoords per primitive, uv0.xy uv1.xy uv2.xy in global primitive order, into DEVICE memory of `bytes` = triangles * 24
+    // bytes (pt_copy_texcoords_device): the prim_texcoords of surfacePlanes; zeros for a scene without a textured mesh.  It depends on the
+    // scene only, so a loop takes it once.  With dev_dst == nullptr only the count is returned.  Returns the number of triangles.
+    uint32_t copyTexcoordsDevice(float* dev_dst, size_t bytes) {
+        uint32_t nt = 0;
+        ck(pt_vertex_count(ctx, nullptr, &nt));
+        if (dev_dst) ck(pt_copy_texcoords_device(ctx, dev_dst, bytes));
+        return nt;
+    }
+    // The albedo and the texcoord under every pixel's centre, from this frame's hit plane (pt_surface_planes): the material's colour, or the
+    // texture lookup at the barycentric texcoord on a textured mesh; valid in every pixel of the call, rendered or not.  Stateless and
+    // synchronous.  Returns the pixels processed, the hits, the stale primitive indices and the texture lookups among them and the device time.
+    pt_surface_stats surfacePlanes(const pt_surface_desc& d, pt_surface_stats* stats = nullptr) {
+        pt_surface_stats s{};
+        ck(pt_surface_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // The SVGF temporal stage in one pass (pt_temporal_moments): demodulated colour, colour history, luminance moments and variance through
     // one gather, with an optional clamp of the history to this frame's 3x3 neighbourhood.  Every plane of `d` is DEVICE memory of this
     // context's device, frame-sized; block_mask is host memory.  Stateless and synchronous; the caller ping-pongs history, moments and

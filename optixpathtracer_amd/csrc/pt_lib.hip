@@ -16,3 +16,4 @@
 #include "pt_motion.hip"
 #include "pt_moments.hip"
 #include "pt_plan.hip"
+#include "pt_surface.hip"

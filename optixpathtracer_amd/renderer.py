@@ -950,6 +950,59 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_motion_planes", desc, _lib.MotionStats(), result)
 
+    def copyTexcoordsDevice(self, out=None):
+        """The scene's texcoords per primitive, written on the GPU into a float32 (triangles, 6) CUDA tensor — uv0.xy, uv1.xy, uv2.xy in
+        global primitive order (pt_copy_texcoords_device): the `prim_texcoords` of surfacePlanes.  All zeros for a scene without a
+        textured mesh.  It depends on the scene only (updateMeshes*, transformMeshes, a rebuild leave it valid): take it once.
+        out: a tensor of that shape on the context's device (dense, any 4-byte-aligned storage offset) or a raw device pointer; allocated
+        with torch when None.  Waits for frames in flight; complete on return.  Returns the tensor (None for a raw pointer)."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        nt = self.vertexCount()[1]
+        if out is None:
+            out = torch.empty((nt, 6), dtype=torch.float32, device=f"cuda:{dev}")
+        if isinstance(out, int):
+            ptr, result = out, None
+        else:
+            _check_temporal_tensor("out", out, dev, {torch.float32: (nt, 6)}, "copyTexcoordsDevice")
+            ptr, result = out.data_ptr(), out
+        self._after_torch()  # earlier users of `out`
+        self._ck(self._L.pt_copy_texcoords_device(self._ctx, ptr, nt * 24), "pt_copy_texcoords_device")
+        return result
+
+    def surfacePlanes(self, hit, prim_texcoords=None, planes=("albedo",), mask=None, out=None) -> dict:
+        """The albedo and the texcoord under the centre of every pixel, from the hit plane (pt_surface_planes, include/pt_amd.h: the
+        arithmetic, in full): the material's colour, replaced by the texture lookup at the barycentric texcoord on a textured mesh;
+        (0, 0, 0, 1) at a miss.  Unlike deviceBuffer(PT_BUF_ALBEDO) it covers every pixel of the call under this frame's camera, whether
+        the render visited the pixel or not: the albedo of temporalMoments / modulatePlanes in a loop that renders only some blocks.
+
+        hit: this frame's renderGBuffer hit plane, float32 (h, w, 8); prim_texcoords: copyTexcoordsDevice's table, float32 (triangles, 6),
+        needed when the scene has a textured mesh — CUDA tensors on the context's device, dense, any 4-byte-aligned storage offset, or
+        raw device pointers.  planes: any of "albedo" (h, w, 4), "texcoord" (h, w, 2).  out: {plane: tensor or raw pointer} for planes
+        the caller owns; the others are allocated with torch, zero-filled (pixels outside the views, the mask or the rank's partition
+        are not written).  mask: 8x8 blocks as renderMask takes them, None = every block.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the call returns when
+        the planes are complete.  The frame buffers, the accumulation and the path state are left alone.
+        Returns {plane: tensor (None for a raw pointer), ..., "stats": {pixels, hits, stale, textured, kernel_ms}}."""
+        planes = tuple(planes)
+        out = dict(out or {})
+        for name in list(planes) + list(out):
+            if name not in _lib.SURFACE_PLANES:
+                raise ValueError(f"surfacePlanes: unknown plane {name!r} (one of {', '.join(_lib.SURFACE_PLANES)})")
+        if any(name not in planes for name in out):
+            raise ValueError("surfacePlanes: `out` names a plane that `planes` does not")
+        if not planes:
+            raise ValueError("surfacePlanes: no plane asked for")
+        desc = _lib.SurfaceDesc()
+        is_tensor = prim_texcoords is not None and not isinstance(prim_texcoords, int)  # (a raw pointer or None: no shape to check)
+        widths = dict(_lib.SURFACE_PLANES, hit=8, prim_texcoords=(self.vertexCount()[1] if is_tensor else 0, 6))
+        self._bind_planes("surfacePlanes", desc, dict(hit=hit, prim_texcoords=prim_texcoords), widths, ("hit",))
+        result = self._bind_planes("surfacePlanes", desc, {name: out.get(name) for name in planes}, widths, outputs=planes, alloc=planes)
+        m = self._bind_mask("surfacePlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.flags = 0
+        return self._run_pass("pt_surface_planes", desc, _lib.SurfaceStats(), result)
+
     def evalTable(self, which, inp: np.ndarray, out_width: int, material=None, bsdf_mode=PT_BSDF_DISNEY) -> np.ndarray:
         inp = np.ascontiguousarray(inp, np.float32)
         n = inp.shape[0]

@@ -1,0 +1,223 @@
+"""Pixel-centre albedo from the hit plane (pt_copy_texcoords_device, pt_surface_planes) without a GPU: the entry points are declared and
+exported, the ctypes mirrors match the compiler's layout, the header compiles as C99 and C++17 and states the arithmetic, a null context and a
+null description are refused before any device work, both facades have the methods; and the float32 NumPy reference (tests/surface_ref.py)
+is tied to the oracle: its tex2D equals orc_tex2d bit for bit on both (non-power-of-two) textures of the textured scene, and its outputs on
+hand-made records are the stated words."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import surface_ref as S
+from conftest import ROOT
+from optixpathtracer_amd import _lib, scenes
+
+f32 = np.float32
+DESC_FIELDS = ("hit", "prim_texcoords", "albedo", "texcoord", "block_mask", "flags")
+STATS_FIELDS = ("pixels", "hits", "stale", "textured", "kernel_ms")
+NEW = ("pt_copy_texcoords_device", "pt_surface_planes")
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
+
+
+def test_library_exports_the_entry_points():
+    L = _lib.load_library()
+    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    for name in NEW:
+        assert name in _lib.EXPORTS and hasattr(L, name)
+        assert name in _header().split("VERSIONING.")[1].split("*/")[0]
+        assert name in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+    assert re.search(r"int\s+pt_copy_texcoords_device\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*float\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*\)", src)
+    assert re.search(r"int\s+pt_surface_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_surface_desc\s*\*\s*\w+\s*,\s*pt_surface_stats\s*\*", src)
+    assert L.pt_version().startswith(b"ptamd 0.4")
+
+
+def test_struct_layouts_match_the_compiler(tmp_path):
+    D, St = _lib.SurfaceDesc, _lib.SurfaceStats
+    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in St._fields_] == list(STATS_FIELDS)
+    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(St)] + [getattr(St, n).offset for n in STATS_FIELDS]
+    assert mine == [48, 0, 8, 16, 24, 32, 40] + [40, 0, 8, 16, 24, 32]
+    fmt = " ".join(["%zu"] * len(mine))
+    args = ", ".join(["sizeof(pt_surface_desc)"] + [f"offsetof(pt_surface_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_surface_stats)"] +
+                     [f"offsetof(pt_surface_stats, {n})" for n in STATS_FIELDS])
+    src = tmp_path / "probe.c"
+    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
+    exe = tmp_path / "probe"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == mine
+    assert _lib.SURFACE_PLANES == S.WORDS and tuple(_lib.SURFACE_PLANES) == S.PLANES == DESC_FIELDS[2:4]
+
+
+def test_header_compiles_as_c99_and_cxx17(tmp_path):
+    body = ('#include "pt_amd.h"\n'
+            "int use(pt_ctx* c, const void* hit, float* table, float* albedo) {\n"
+            "    pt_surface_desc d = {0, 0, 0, 0, 0, 0u};\n"
+            "    pt_surface_stats s;\n"
+            "    uint32_t nt = 0;\n"
+            "    if (pt_vertex_count(c, 0, &nt) || pt_copy_texcoords_device(c, table, (size_t)nt * 24)) return -1;\n"
+            "    d.hit = hit; d.prim_texcoords = table; d.albedo = albedo; d.flags = PT_SURFACE_RESERVED;\n"
+            "    return pt_surface_planes(c, &d, &s) || s.textured > s.hits;\n"
+            "}\n")
+    (tmp_path / "h.c").write_text(body)
+    (tmp_path / "h.cpp").write_text(body)
+    inc = os.path.join(ROOT, "include")
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
+    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+
+
+def test_null_context_and_null_description_are_refused_without_a_gpu():
+    L = _lib.load_library()
+    d, s = _lib.SurfaceDesc(), _lib.SurfaceStats(7, 7, 7, 7, 7.0)
+    assert L.pt_surface_planes(None, C.byref(d), C.byref(s)) == -1
+    assert b"pt_surface_planes: null context" in L.pt_last_error(None)
+    assert L.pt_surface_planes(None, None, None) == -1
+    assert (s.pixels, s.hits, s.stale, s.textured, s.kernel_ms) == (7, 7, 7, 7, 7.0)
+    assert L.pt_copy_texcoords_device(None, None, 0) == -1
+    assert b"pt_copy_texcoords_device: null context" in L.pt_last_error(None)
+    # a null description is refused before the context is looked at (the text of pt_surface.hip; a live context needs a GPU), and the
+    # refusals stand in the order of the other passes
+    api = open(os.path.join(ROOT, "optixpathtracer_amd", "csrc", "pt_surface.hip")).read()
+    body = api.split('extern "C" int pt_surface_planes(')[1]
+    order = [body.index(k) for k in ("null description", "ctx->width", "unknown flag bits", "no plane asked for", "pass_planes_check(", "prim_texcoords is required", "run.open(")]
+    assert order == sorted(order)
+
+
+def test_facades_have_the_methods(tmp_path):
+    import torch  # noqa: F401
+
+    from optixpathtracer_amd import renderer as R
+    from test_temporal_cabi import _fake_cuda
+
+    for name in ("copyTexcoordsDevice", "surfacePlanes"):
+        assert callable(getattr(R.SampleRenderer, name, None))
+    r = object.__new__(R.SampleRenderer)
+    r._device, r.launchParams, r._nv = 0, R.LaunchParams(), [5, 3]
+    r.launchParams.frame.size = (4, 4)
+    hit = _fake_cuda((4, 4, 8))
+    with pytest.raises(ValueError, match="unknown plane 'depth'"):
+        r.surfacePlanes(hit, planes=("depth",))
+    with pytest.raises(ValueError, match="`out` names a plane that `planes` does not"):
+        r.surfacePlanes(hit, planes=("albedo",), out=dict(texcoord=1))
+    with pytest.raises(ValueError, match="no plane asked for"):
+        r.surfacePlanes(hit, planes=())
+    with pytest.raises(ValueError, match="hit is required"):
+        r.surfacePlanes(None)
+    with pytest.raises(ValueError, match=r"albedo: a contiguous torch.float32 tensor of shape \(4, 4, 4\) is expected"):
+        r.surfacePlanes(hit, out=dict(albedo=_fake_cuda((4, 4, 2))))
+    src = tmp_path / "facade.cpp"
+    src.write_text(
+        '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
+        "using namespace ptamd;\n"
+        "uint64_t surface(SampleRenderer& sample, pt_surface_desc d, float* table) {\n"
+        "    const uint32_t nt = sample.copyTexcoordsDevice(nullptr, 0);\n"
+        "    sample.copyTexcoordsDevice(table, (size_t)nt * 24);\n"
+        "    d.prim_texcoords = table;\n"
+        "    pt_surface_stats s{};\n"
+        "    sample.surfacePlanes(d, &s);\n"
+        "    return sample.surfacePlanes(d).textured + s.stale;\n"
+        "}\n"
+    )
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
+
+
+def test_header_states_the_arithmetic():
+    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    for item in ("w0 = (1.0f - u) - v", "s = ((w0 * c[0]) + (u * c[2])) + (v * c[4])", "t = ((w0 * c[1]) + (u * c[3])) + (v * c[5])",
+                 "albedo[p] = (tex2D(texture[tid], s, t).xyz, 1.0f); texcoord[p] = (s, t)", "albedo[p] = (material[mesh].color, 1.0f); texcoord[p] = (0, 0)",
+                 "albedo[p] = (0, 0, 0, 1)", "x = (s - floorf(s)) * (float)W; y = (t - floorf(t)) * (float)H", "xB = x - 0.5f; yB = y - 0.5f",
+                 "alpha = floorf(((xB - fi) * 256.0f) + 0.5f) * (1.0f / 256.0f)", "beta = floorf(((yB - fj) * 256.0f) + 0.5f) * (1.0f / 256.0f)",
+                 "T(i, j)[k] = (float)(byte k of texel (i, j)) / 255.0f",
+                 "out[k] = (((((1.0f - alpha) * (1.0f - beta)) * T(i0, j0)[k]) + ((alpha * (1.0f - beta)) * T(i1, j0)[k])) + (((1.0f - alpha) * beta) * T(i0, j1)[k])) + ((alpha * beta) * T(i1, j1)[k])",
+                 "no address is formed from it", "stats->stale counts the pixel", "stats->textured counts the pixel", "hit[p].mesh is not read",
+                 "bytes must equal triangles * 24", "float32 NumPy evaluating this reproduces every output bit for bit",
+                 "No other pixel is written in either output", "Zero pixels launch nothing and return PT_OK", "flags != 0",
+                 "albedo[p].xyz are NaN", "prim_texcoords is ignored", "examples/adaptive_svgf_albedo_loop.py", "a pt_multi_* wrapper", "texture LOD"):
+        assert item in text, item
+
+
+# ------------------------------------------------------------------ the reference's tex2D is the oracle's
+def _coordinates(W, H, seed):
+    rng = np.random.default_rng(seed)
+    below1 = np.nextafter(f32(1), f32(0))
+    k = np.arange(-W - 2, 2 * W + 3)
+    edges = np.concatenate([k / W, (k + 0.5) / W, k / H, (k + 0.5) / H]).astype(f32)
+    special = np.array([0, 1, -1, 2, -3, 7, 0.5, -0.5, 1.5, below1, -below1, below1 + 1, 1e-7, -1e-7, 1e-30, 123456.75, -98765.25, 1.0 / 128, 1.0 / 64], f32)
+    axis = np.concatenate([edges, special])
+    pairs = np.stack([rng.choice(axis, 2500), rng.choice(axis, 2500)], -1)
+    grid = np.stack(np.meshgrid(special, special), -1).reshape(-1, 2)
+    st = np.concatenate([rng.uniform(-3, 3, (2000, 2)).astype(f32), pairs, grid, np.stack([edges, edges[::-1]], -1)]).astype(f32)
+    assert (st < 0).any() and (st > 1).any() and (st == np.round(st)).all(-1).any() and (st == below1).any()
+    return st
+
+
+def test_reference_tex2d_is_the_oracles(orc_det):
+    model = scenes.textured_scene()
+    assert [t.pixel.shape for t in model.textures] == [(32, 64), (40, 48)]  # the second: neither side a power of two
+    total = 0
+    for k, tex in enumerate(model.textures):
+        px = np.ascontiguousarray(tex.pixel, np.uint32)
+        H, W = px.shape
+        st = _coordinates(W, H, 40 + k)
+        mine = S.tex2d(px, st[:, 0], st[:, 1])
+        ref = np.zeros((len(st), 4), f32)
+        out = np.zeros(4, f32)
+        flat = px.reshape(-1)
+        for i in range(len(st)):
+            orc_det.lib.orc_tex2d(flat, W, H, float(st[i, 0]), float(st[i, 1]), out)
+            ref[i] = out
+        neq = mine.view(np.uint32) != ref.view(np.uint32)
+        assert not neq.any(), f"texture {k}: {int(neq.any(-1).sum())} of {len(st)} coordinates differ, first {st[neq.any(-1)][:3]}"
+        assert 0.0 <= mine.min() and mine.max() <= 1.0 and (mine[:, 3] == 1).all()
+        total += len(st)
+    assert total > 8000
+
+
+# ------------------------------------------------------------------ the table and the pass on hand-made records
+def test_texcoord_table_from_a_model():
+    sc = S.scene_arrays(S.textured_scene())
+    assert sc["uv"].shape == (16, 6) and sc["mesh_tex"].tolist() == [0, 1, -1] and sc["tri_mesh"].tolist() == [0, 0, 1, 1] + [2] * 12
+    # _quads_to_mesh: triangles (0, 1, 2) and (0, 2, 3) of the quad's four corners
+    assert sc["uv"][0].tolist() == [-1.5, -1.5, 2.5, -1.5, 2.5, 2.5] and sc["uv"][1].tolist() == [-1.5, -1.5, 2.5, 2.5, -1.5, 2.5]
+    assert sc["uv"][3].tolist() == [0, 0, 1, 1, 0, 1] and not sc["uv"][4:].any()
+    # the scene as scenes.py builds it: the box has (zero) texcoords and names texture 0, so it is a textured mesh looked up at (0, 0)
+    assert S.scene_arrays(scenes.textured_scene())["mesh_tex"].tolist() == [0, 1, 0]
+    plain = S.scene_arrays(scenes.cornell_box())
+    assert plain["uv"].shape == (32, 6) and not plain["uv"].any() and (plain["mesh_tex"] == -1).all()
+
+
+def test_reference_gives_the_stated_words():
+    model = S.textured_scene()
+    sc = S.scene_arrays(model)
+    ntri = 16
+    h, w = 2, 6
+    hit = np.zeros((h, w, 8), f32)
+    words = hit.view(np.int32)
+    hit[..., 0] = 3
+    hit[..., 1], hit[..., 2] = 0.25, 0.5
+    words[..., 4] = 7  # the record's mesh word is not used
+    prims = np.array([[0, 3, 4, ntri - 1, ntri, 2**31 - 1], [-1, -2, -(2**31), 1, 2, 0]], np.int32)
+    words[..., 3] = prims
+    hit[1, 5, 1] = np.nan
+    px = np.ones((h, w), bool)
+    px[1, 4] = False
+    ref = S.surface_ref(hit, sc, px)
+    assert (ref["hits"], ref["stale"], ref["textured"]) == (6, 2, 4)
+    assert ref["kind"].tolist() == [[4, 4, 1, 1, 3, 3], [2, 2, 2, 4, 0, 4]]
+    flat = np.array([0, 0, 0, S.ONE], np.uint32)
+    for y, x in ((0, 4), (0, 5), (1, 0), (1, 1), (1, 2)):  # stale and misses: (0, 0, 0, 1) and (0, 0)
+        assert np.array_equal(ref["albedo"][y, x], flat) and not ref["texcoord"][y, x].any()
+    blue = np.array([0.3, 0.4, 0.8, 1.0], f32).view(np.uint32)
+    assert np.array_equal(ref["albedo"][0, 2], blue) and np.array_equal(ref["albedo"][0, 3], blue) and not ref["texcoord"][0, 2:4].any()
+    # primitive 0 of the ground: uv (-1.5, -1.5), (2.5, -1.5), (2.5, 2.5) at weights (0.25, 0.25, 0.5): (1.5, 0.5), exact in float32
+    assert ref["texcoord"][0, 0].view(f32).tolist() == [1.5, 0.5]
+    want = S.tex2d(sc["textures"][0], [f32(1.5)], [f32(0.5)])[0]
+    assert np.array_equal(ref["albedo"][0, 0, :3], want[:3].view(np.uint32)) and ref["albedo"][0, 0, 3] == S.ONE
+    assert (ref["albedo"][1, 4] == S.SENTINEL).all() and (ref["texcoord"][1, 4] == S.SENTINEL).all()
+    # NaN barycentrics on a textured primitive: NaN texcoords, NaN colour, w = 1
+    assert np.isnan(ref["texcoord"][1, 5].view(f32)).all() and np.isnan(ref["albedo"][1, 5, :3].view(f32)).all() and ref["albedo"][1, 5, 3] == S.ONE
