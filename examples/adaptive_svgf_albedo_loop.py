@@ -14,7 +14,10 @@ that plane is what temporalMoments divides by and modulatePlanes multiplies back
   7. filterPlanes on all pixels, on demodulated colour;
   8. modulatePlanes with the surface albedo: the displayed frame.
 
-  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--out-dir .]
+With --lod step 2 is surfaceLodPlanes: the albedo filtered over the pixel's footprint in texture space (a trilinear lookup in the mip pyramid,
+which is built once, before the loop), so a minified texture does not alias in the plane the loop divides by and multiplies back in.
+
+  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--out-dir .]
 """
 import argparse
 import os
@@ -56,6 +59,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--sigma-lum", type=float, default=4.0)
     ap.add_argument("--min-length", type=int, default=4)
+    ap.add_argument("--lod", action="store_true", help="footprint-filtered albedo (surfaceLodPlanes) instead of the point lookup of surfacePlanes")
+    ap.add_argument("--footprint-scale", type=float, default=1.0, help="with --lod: 1 = the pixel's own footprint")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args()
     import torch
@@ -79,6 +84,7 @@ def main():
     frame = torch.zeros((h, w), dtype=torch.int32, device=dev)
     accum = sample.deviceBuffer(R.PT_BUF_ACCUM)
     table = sample.copyTexcoordsDevice()  # the scene's texcoords per primitive: once, whatever moves later
+    mips = sample.copyTextureMipsDevice() if args.lod else None  # the mip pyramid of the scene's textures: once, too
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -86,7 +92,10 @@ def main():
         i, o = k & 1, ~k & 1
         sample.setCamera(cam)
         g = sample.renderGBuffer(("hit", "position", "motion"), prev_cameras=prev, out=cur)
-        s = sample.surfacePlanes(cur["hit"], table, out=dict(albedo=albedo))
+        if args.lod:
+            s = sample.surfaceLodPlanes(cur["hit"], table, mips, footprint_scale=args.footprint_scale, out=dict(albedo=albedo))
+        else:
+            s = sample.surfacePlanes(cur["hit"], table, out=dict(albedo=albedo))
         geo = (cur["motion"], cur["hit"], cur["position"], old["hit"], old["position"], history[i], moments[i], length[i])
         outs = dict(history_out=history[o], moments_out=moments[o], length_out=length[o], variance_out=variance)
         p = sample.samplePlan(*geo, threshold=args.threshold, dark_floor=args.dark_floor, min_length=args.plan_min_length, min_pixels=args.min_pixels,
@@ -102,7 +111,7 @@ def main():
         m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=frame)
         ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
         print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
-              f"{ss['textured']} of {ss['hits']} hits textured; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
+              f"{ss['textured']} of {ss['hits']} hits textured{', %d minified' % ss['minified'] if args.lod else ''}; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
               f"plan {ps['kernel_ms']:.3f} ms, colour {sample.stats()['render_ms']:.2f} ms, temporal {ts['kernel_ms']:.3f} ms, "
               f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms")
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_final.npy"), final.cpu().numpy())

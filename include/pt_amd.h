@@ -19,7 +19,8 @@
  * caller (the current stream of a tensor framework included).  Entry points that take HOST pointers are complete when
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
  * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes,
- * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes — read and write them on
+ * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
+ * pt_copy_texture_mips_device, pt_surface_lod_planes — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -36,7 +37,8 @@
  * enqueue_ms, threads, frames_handed_over.  Entry points added since keep "0.4" (the string names the struct layouts, which they did not
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
  * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
- * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes.  A
+ * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
+ * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -1159,8 +1161,9 @@ int pt_temporal_carry(pt_ctx* ctx, const pt_carry_desc* desc, pt_carry_stats* st
  * the pixel's centre; they agree bit for bit wherever every sample of the pixel meets one untextured mesh.
  * stats: pixels processed; hits, stale and textured among them; device time of the pass (hipEvents; the mask compaction included when
  * there is a mask).
- * Not part of this interface: emission, roughness or normal planes, texture LOD (mip-mapping), an asynchronous variant, a pt_multi_*
- * wrapper (per-rank calls through pt_multi_ctx work), any change to pt_render_gbuffer or pt_temporal_moments. */
+ * Not part of this interface: emission, roughness or normal planes, an asynchronous variant, a pt_multi_* wrapper (per-rank calls through
+ * pt_multi_ctx work), any change to pt_render_gbuffer or pt_temporal_moments.  texture LOD (mip-mapping) is a pass of its own:
+ * pt_surface_lod_planes below; this one stays the point lookup at full resolution. */
 int pt_copy_texcoords_device(pt_ctx* ctx, float* dev_dst, size_t bytes);
 enum pt_surface_flags { PT_SURFACE_RESERVED = 0 };  /* no flag defined yet: flags must be 0 */
 typedef struct pt_surface_desc {
@@ -1173,6 +1176,105 @@ typedef struct pt_surface_desc {
 } pt_surface_desc;
 typedef struct pt_surface_stats { uint64_t pixels, hits, stale, textured; double kernel_ms; } pt_surface_stats;
 int pt_surface_planes(pt_ctx* ctx, const pt_surface_desc* desc, pt_surface_stats* stats /* may be NULL */);
+
+/* FOOTPRINT-FILTERED ALBEDO (no reference counterpart): pt_surface_planes with a level of detail.  Where a texture is minified — a pixel
+ * covers many texels — the point lookup of pt_surface_planes shows one of them, and the plane aliases under every camera move.
+ * pt_surface_lod_planes derives the pixel's footprint in texture space from the hit plane, the context's CURRENT vertices and the pixel's
+ * camera, and looks the albedo up trilinearly in a box-filtered mip pyramid that the caller keeps.
+ *
+ * pt_texture_mips_layout: the pyramid's shape.  *textures = the number of textures of the scene; dims (HOST, textures x 4 uint32, may be
+ * NULL) receives per texture w, h, levels and the index of the first 16-byte texel of its level 1 in the pyramid;
+ * levels = 1 + floor(log2(max(w, h))); level k has w_k = max(1, w >> k) by h_k = max(1, h >> k) texels.  The pyramid holds, for textures
+ * in order, levels 1 .. levels-1, each row-major (row 0 first), 4 f32 per texel, contiguous; level 0 stays the context's RGBA8 texels.
+ * *bytes = 16 * the texels of all those levels: 0 for a scene without textures or with only 1 x 1 textures.  Any of the three outputs may
+ * be NULL.  The context keeps its textures' sizes in DEVICE memory only, so every call selects the context's device and reads those few
+ * bytes back with one blocking copy (tens of microseconds; the const in the signature says that no state of the renderer changes, not
+ * that the call is free).  The copy uses no stream of the context and waits for none: the sizes never change after pt_create, so the
+ * call may be made while frames are in flight and orders nothing.  A caller takes the layout once per scene.  PT_ERR_INVALID for a null ctx.
+ *
+ * pt_copy_texture_mips_device: builds the pyramid on the GPU into caller-owned DEVICE memory, one kernel launch per level on pt_stream(ctx).
+ * Texel (i, j) of level k+1, per channel, float32, one rounding per operation:
+ *         ((S(2i, 2j) + S(i1, 2j)) + (S(2i, j1) + S(i1, j1))) * 0.25f        i1 = min(2i + 1, w_k - 1);  j1 = min(2j + 1, h_k - 1)
+ * where S is level k, and at level 0 S = (float)byte / 255.0f.  An odd dimension drops its last row or column: w_k = 5 gives w_k+1 = 2 and
+ * column 4 of level k is in no texel of level k+1 (a 1-wide or 1-high level repeats its only column or row instead).  bytes must equal the
+ * layout's; dev_dst is checked exactly as pt_copy_texcoords_device checks its destination and must in addition be 16-byte aligned.
+ * bytes == 0 is a no-op that returns PT_OK (dev_dst is not looked at).  The call first waits for the frames in flight and completes queued
+ * queries, and is complete when it returns.  The pyramid depends on the scene only (no update of the geometry touches a texture), so a
+ * loop takes it once.  PT_ERR_INVALID (nothing written) for a null ctx, wrong bytes, a pointer that fails the checks.
+ *
+ * pt_surface_lod_planes.  Pixel set, rectangles, views, partitions and pointer checks are exactly pt_motion_planes's; every plane is
+ * caller-owned DEVICE memory of the context's device (4-byte aligned, frame-sized, indexed Y * width + X), prim_texcoords is checked
+ * against triangles * 24 bytes, mips against mips_bytes, which must equal the layout's, and mips must be 16-byte aligned; block_mask is
+ * HOST memory.  No other pixel is written in any output.  Zero pixels launch nothing and return PT_OK.
+ * The pass reads from the context its current vertices and indices (so it follows pt_update_meshes* and pt_transform_meshes), the
+ * materials, the primitive-to-mesh table, the textures, and the cameras: the frame's, or with views the camera and rectangle of the
+ * pixel's view (x, y below are then relative to the view's rectangle and wr, hr are its width and height; otherwise the frame's).  Every
+ * level address comes from the context's own texture sizes, never from caller memory, and hit[p].prim is compared with the triangle count
+ * before any address is formed from it.
+ * Arithmetic per pixel p — float32 throughout, one rounding per operation, no fused multiply-add, in exactly this order; float32 NumPy
+ * evaluating this reproduces every output bit for bit (tests/surface_lod_ref.py).  dot3(a, b) = ((a.x * b.x) + (a.y * b.y)) + (a.z * b.z);
+ * cross3(a, b) = ((a.y * b.z) - (a.z * b.y), (a.z * b.x) - (a.x * b.z), (a.x * b.y) - (a.y * b.x)); w0, s, t and tex2D as for pt_surface_planes.
+ *   - A miss, a stale record (prim >= triangles; stats->stale) and a hit on an untextured mesh: albedo[p] and texcoord[p] are
+ *     pt_surface_planes's, footprint[p] = (0, 0, 0, 0), lod[p] = 0.
+ *   - A hit on a textured mesh (stats->textured), with c = prim_texcoords[6*prim ..], p0, p1, p2 the primitive's current vertices, eye, U,
+ *     V, W the pixel's camera, W_t x H_t the texture's size and `levels` its level count:
+ *         texcoord[p] = (s, t)
+ *         d(a, b) = ((U * ((2.0f * (a / (float)wr)) - 1.0f)) + (V * ((2.0f * (b / (float)hr)) - 1.0f))) + W           (per component)
+ *         d_c = d((float)x + 0.5f, (float)y + 0.5f);  d_x = d((float)x + 1.5f, (float)y + 0.5f);  d_y = d((float)x + 0.5f, (float)y + 1.5f)
+ *         e1 = p1 - p0;  e2 = p2 - p0;  n = cross3(e1, e2);  nn = dot3(n, n);  hgt = dot3(n, p0 - eye)
+ *         t_r = hgt / dot3(n, d_r);  P_r = (d_r * t_r) + eye                                                           (r = c, x, y)
+ *         ok = t_c > 0 && t_x > 0 && t_y > 0
+ *         g = P_r - P_c;  du = dot3(cross3(g, e2), n) / nn;  dv = dot3(cross3(e1, g), n) / nn                          (r = x, y)
+ *         ds_r = (du * (c[2] - c[0])) + (dv * (c[4] - c[0]));  dt_r = (du * (c[3] - c[1])) + (dv * (c[5] - c[1]))
+ *         footprint[p] = (ds_x, dt_x, ds_y, dt_y)                  (as computed, whatever ok is: the texcoord step per pixel step in x and y)
+ *         rx = ((ds_x * (float)W_t) * (ds_x * (float)W_t)) + ((dt_x * (float)H_t) * (dt_x * (float)H_t));  ry likewise from ds_y, dt_y
+ *         rho2 = ok ? (rx > ry ? rx : ry) : +infinity
+ *         rho = sqrtf(rho2) * footprint_scale                      (sqrtf correctly rounded; +infinity * 0 is NaN)
+ *       Level 0:   if !(rho > 1.0f): albedo[p] = (tex2D(texture[tid], s, t).xyz, 1.0f), lod[p] = 0 — pt_surface_planes's value; a NaN
+ *                  lands here, and so does every pixel at footprint_scale = 0.
+ *       Coarsest:  else (stats->minified counts the pixel), with Lm = levels - 1, if !(rho < (float)(1 << Lm)): the coarsest level alone,
+ *                  albedo[p] = (tex2D_Lm(s, t).xyz, 1.0f), lod[p] = (float)Lm.
+ *       Trilinear: otherwise k = the unbiased exponent field of rho (bits 23..30 minus 127, so 2^k <= rho < 2^(k+1) and 0 <= k < Lm),
+ *                  m = rho with its exponent field set to 127 (in [1, 2)), frac = m - 1.0f,
+ *                  out = c_k + ((c_k+1 - c_k) * frac) per channel with c_j = tex2D_j(s, t), albedo[p] = (out.xyz, 1.0f),
+ *                  lod[p] = (float)k + frac.
+ *       tex2D_0 is tex2D of the RGBA8 texels.  tex2D_j for j >= 1 is the tex2D text with W, H replaced by w_j, h_j and T(i, j)[k] the
+ *       pyramid's float k of texel (i, j) of level j.
+ *     A zero-area primitive has n = 0, so t_r is NaN, ok is false and the coarsest level is taken (level 0 at footprint_scale = 0); the
+ *     footprint is NaN.  A ray parallel to the primitive's plane or meeting it behind the eye (a horizon pixel) makes ok false likewise.
+ *     Non-finite u or v fault nothing, as in pt_surface_planes.
+ * Overlap: the four outputs may overlap nothing; hit, prim_texcoords and mips are only read.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet;
+ * flags != 0; all four outputs NULL; footprint_scale negative or not finite; mips_bytes different from the layout's; a plane that fails
+ * the pointer checks; a forbidden overlap; prim_texcoords NULL when the scene has a textured mesh; mips NULL or not 16-byte aligned when
+ * the scene has a textured mesh and the layout's bytes are > 0.  On a scene without a textured mesh prim_texcoords, mips and mips_bytes
+ * are ignored.
+ * Ordering and state, as pt_surface_planes: waits for the frames in flight, runs on pt_stream(ctx) under the STREAM CONTRACT, is
+ * complete when it returns, and writes no context state.  Host work per call on a textured scene, in front of the timed span (so
+ * kernel_ms does not show it): the same readback of the texture sizes as pt_texture_mips_layout, and the upload of 128 bytes per texture
+ * (the first texel of every level) into the call's one temporary allocation, next to the counters.
+ * footprint_scale: 1 = the pixel's own footprint; 0 = pt_surface_planes's albedo and texcoord bit for bit.
+ * stats: pixels processed; hits, stale, textured and minified (rho > 1) among them; device time of the pass.
+ * Not part of this interface: anisotropic footprints (the larger axis picks the level), LOD in the frame path (PT_BUF_ALBEDO and the
+ * shading stay point lookups), emission, roughness or normal planes, a pt_multi_* wrapper. */
+int pt_texture_mips_layout(const pt_ctx* ctx, uint32_t* textures, uint32_t* dims /* HOST, textures x 4, may be NULL */, size_t* bytes);
+int pt_copy_texture_mips_device(pt_ctx* ctx, void* dev_dst, size_t bytes);
+enum pt_surface_lod_flags { PT_SURFACE_LOD_RESERVED = 0 };  /* no flag defined yet: flags must be 0 */
+typedef struct pt_surface_lod_desc {
+    const void*  hit;             /* w*h x pt_hit, this frame (pt_render_gbuffer); required */
+    const float* prim_texcoords;  /* triangles x 6 f32 (pt_copy_texcoords_device); required iff the scene has a textured mesh */
+    const void*  mips;            /* the pyramid (pt_copy_texture_mips_device); required iff textured and the layout's bytes > 0 */
+    size_t mips_bytes;            /* pt_texture_mips_layout's bytes */
+    float* albedo;                /* w*h x 4  or NULL */
+    float* texcoord;              /* w*h x 2  or NULL */
+    float* footprint;             /* w*h x 4  or NULL: ds/dx, dt/dx, ds/dy, dt/dy per pixel step */
+    float* lod;                   /* w*h x 1  or NULL */
+    const uint8_t* block_mask;    /* HOST, as pt_render_gbuffer, or NULL */
+    float footprint_scale;        /* finite, >= 0; 1 = the pixel's own footprint */
+    uint32_t flags;               /* 0 */
+} pt_surface_lod_desc;
+typedef struct pt_surface_lod_stats { uint64_t pixels, hits, stale, textured, minified; double kernel_ms; } pt_surface_lod_stats;
+int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* desc, pt_surface_lod_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

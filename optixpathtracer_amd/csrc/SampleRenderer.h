@@ -344,6 +344,30 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The shape of the texture mip pyramid (pt_texture_mips_layout): the bytes of the whole pyramid (0: no level above 0) and, when `dims`
+    // is given, per texture w, h, levels and the index of the first 16-byte texel of its level 1.  It depends on the scene only.
+    size_t textureMipsLayout(std::vector<uint32_t>* dims = nullptr) {
+        uint32_t n = 0;
+        size_t bytes = 0;
+        ck(pt_texture_mips_layout(ctx, &n, nullptr, &bytes));
+        if (dims) {
+            dims->assign((size_t)4 * n, 0u);
+            if (n) ck(pt_texture_mips_layout(ctx, nullptr, dims->data(), nullptr));
+        }
+        return bytes;
+    }
+    // The mip pyramid of the scene's textures, levels 1 and up, built on the GPU into DEVICE memory of `bytes` = textureMipsLayout()
+    // bytes, 16-byte aligned (pt_copy_texture_mips_device): the mips of surfaceLodPlanes.  A loop takes it once.
+    void copyTextureMipsDevice(void* dev_dst, size_t bytes) { ck(pt_copy_texture_mips_device(ctx, dev_dst, bytes)); }
+    // surfacePlanes with a level of detail (pt_surface_lod_planes): on a textured mesh the albedo is a trilinear lookup in the mip pyramid
+    // over the pixel's footprint in texture space; the footprint and the level can be had as planes.  Stateless and synchronous.  Returns
+    // the pixels processed, the hits, the stale records, the texture lookups and the minified ones among them and the device time.
+    pt_surface_lod_stats surfaceLodPlanes(const pt_surface_lod_desc& d, pt_surface_lod_stats* stats = nullptr) {
+        pt_surface_lod_stats s{};
+        ck(pt_surface_lod_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // The SVGF temporal stage in one pass (pt_temporal_moments): demodulated colour, colour history, luminance moments and variance through
     // one gather, with an optional clamp of the history to this frame's 3x3 neighbourhood.  Every plane of `d` is DEVICE memory of this
     // context's device, frame-sized; block_mask is host memory.  Stateless and synchronous; the caller ping-pongs history, moments and

@@ -17,3 +17,4 @@
 #include "pt_moments.hip"
 #include "pt_plan.hip"
 #include "pt_surface.hip"
+#include "pt_surface_lod.hip"

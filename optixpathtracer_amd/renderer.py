@@ -1003,6 +1003,70 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_surface_planes", desc, _lib.SurfaceStats(), result)
 
+    def textureMipsLayout(self):
+        """The shape of the texture mip pyramid (pt_texture_mips_layout): (dims, bytes) with dims a uint32 (textures, 4) array of w, h,
+        levels and the index of the first 16-byte texel of level 1, and bytes the size of the whole pyramid (0: no level above 0)."""
+        key = getattr(self._ctx, "value", self._ctx)
+        cached = getattr(self, "_mips_layout", None)  # a context's textures never change
+        if cached is None or cached[0] != key:
+            nt, nbytes = C.c_uint32(), C.c_size_t()
+            self._ck(self._L.pt_texture_mips_layout(self._ctx, C.byref(nt), None, C.byref(nbytes)), "pt_texture_mips_layout")
+            dims = np.zeros((nt.value, 4), np.uint32)
+            self._ck(self._L.pt_texture_mips_layout(self._ctx, None, dims.ctypes.data if nt.value else None, None), "pt_texture_mips_layout")
+            cached = self._mips_layout = (key, dims, nbytes.value)
+        return cached[1].copy(), cached[2]
+
+    def copyTextureMipsDevice(self, out=None):
+        """The box-filtered mip pyramid of the scene's textures, levels 1 and up, built on the GPU into a float32 (texels, 4) CUDA tensor
+        (pt_copy_texture_mips_device; the layout is textureMipsLayout's): the `mips` of surfaceLodPlanes.  It depends on the scene only:
+        take it once.  out: a tensor of that shape on the context's device (dense, 16-byte aligned) or a raw device pointer; allocated
+        with torch when None.  Waits for frames in flight; complete on return.  Returns the tensor (None for a raw pointer)."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        nbytes = self.textureMipsLayout()[1]
+        if out is None:
+            out = torch.empty((nbytes // 16, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        if isinstance(out, int):
+            ptr, result = out, None
+        else:
+            _check_temporal_tensor("out", out, dev, {torch.float32: (nbytes // 16, 4)}, "copyTextureMipsDevice")
+            ptr, result = out.data_ptr(), out
+        self._after_torch()  # earlier users of `out`
+        self._ck(self._L.pt_copy_texture_mips_device(self._ctx, ptr, nbytes), "pt_copy_texture_mips_device")
+        return result
+
+    def surfaceLodPlanes(self, hit, prim_texcoords=None, mips=None, planes=("albedo",), footprint_scale=1.0, mask=None, out=None) -> dict:
+        """surfacePlanes with a level of detail (pt_surface_lod_planes, include/pt_amd.h: the arithmetic, in full): on a textured mesh the
+        pixel's footprint in texture space is derived from the hit plane, the current vertices and the pixel's camera, and the albedo is
+        a trilinear lookup in the mip pyramid, so a minified texture no longer aliases.  Everything else is surfacePlanes's.
+
+        hit, prim_texcoords, mask, out: as surfacePlanes takes them.  mips: copyTextureMipsDevice's pyramid, float32 (texels, 4), needed
+        when the scene has a textured mesh and a texture larger than 1 x 1; a raw pointer stands for textureMipsLayout's bytes.
+        planes: any of "albedo" (h, w, 4), "texcoord" (h, w, 2), "footprint" (h, w, 4: ds/dx, dt/dx, ds/dy, dt/dy per pixel step),
+        "lod" (h, w).  footprint_scale: 1 = the pixel's own footprint, 0 = surfacePlanes's albedo bit for bit.
+        Returns {plane: tensor (None for a raw pointer), ..., "stats": {pixels, hits, stale, textured, minified, kernel_ms}}."""
+        planes = tuple(planes)
+        out = dict(out or {})
+        for name in list(planes) + list(out):
+            if name not in _lib.SURFACE_LOD_PLANES:
+                raise ValueError(f"surfaceLodPlanes: unknown plane {name!r} (one of {', '.join(_lib.SURFACE_LOD_PLANES)})")
+        if any(name not in planes for name in out):
+            raise ValueError("surfaceLodPlanes: `out` names a plane that `planes` does not")
+        if not planes:
+            raise ValueError("surfaceLodPlanes: no plane asked for")
+        desc = _lib.SurfaceLodDesc()
+        is_tensor = lambda t: t is not None and not isinstance(t, int)  # noqa: E731 (a raw pointer or None: no shape to check)
+        nbytes = self.textureMipsLayout()[1] if mips is not None else 0
+        widths = dict(_lib.SURFACE_LOD_PLANES, hit=8, prim_texcoords=(self.vertexCount()[1] if is_tensor(prim_texcoords) else 0, 6), mips=(nbytes // 16, 4))
+        self._bind_planes("surfaceLodPlanes", desc, dict(hit=hit, prim_texcoords=prim_texcoords, mips=mips), widths, ("hit",))
+        desc.mips_bytes = nbytes
+        result = self._bind_planes("surfaceLodPlanes", desc, {name: out.get(name) for name in planes}, widths, outputs=planes, alloc=planes)
+        m = self._bind_mask("surfaceLodPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.footprint_scale = float(footprint_scale)
+        desc.flags = 0
+        return self._run_pass("pt_surface_lod_planes", desc, _lib.SurfaceLodStats(), result)
+
     def evalTable(self, which, inp: np.ndarray, out_width: int, material=None, bsdf_mode=PT_BSDF_DISNEY) -> np.ndarray:
         inp = np.ascontiguousarray(inp, np.float32)
         n = inp.shape[0]
