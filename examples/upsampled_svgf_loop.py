@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""upsampled_svgf_loop.py — adaptive_svgf_albedo_loop.py with the path tracer at a fraction of the display resolution: the noisy,
+low-frequency part of the image (the demodulated irradiance) is traced, accumulated and filtered at size / scale, and brought to the display
+resolution under the guidance of a full-resolution G-buffer (upsamplePlanes).  The high-frequency parts are cheap to make at full
+resolution and are made there: the geometry edges by renderGBuffer (one traversal kernel, no shading), the texture detail by
+surface[Lod]Planes.
+
+Two SampleRenderers over one model: `lo` at size / scale and `hi` at size.  Per frame, on `lo`, steps 1-7 of adaptive_svgf_albedo_loop.py:
+  1. renderGBuffer: hit, position and motion against LAST frame's camera;
+  2. surfacePlanes (surfaceLodPlanes with --lod): the low-resolution albedo the demodulation divides by;
+  3. samplePlan;  4. renderMask(mask);  5. temporalMoments on the mask;  6. temporalCarry on its complement;
+  7. filterPlanes on all pixels: the filtered irradiance at low resolution.
+Per frame, on `hi`:
+  8. renderGBuffer: hit and position;
+  9. surfacePlanes (surfaceLodPlanes with --lod): the albedo under every display pixel;
+ 10. upsamplePlanes: the low-resolution irradiance on the display's pixels — four taps of the same surface where there are four, fewer
+     where an edge is near, the ring around them where there is none (rescued), another surface's value where that fails too (orphans);
+ 11. modulatePlanes with the full-resolution albedo: the displayed frame.
+`hi` never renders a colour sample.
+
+  python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--out-dir .]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from optixpathtracer_amd import renderer as R  # noqa: E402
+from optixpathtracer_amd import scenes  # noqa: E402
+
+SCENES = {
+    "textured": (scenes.textured_scene, dict(eye=(3.0, 2.5, -4.5), lookat=(0.0, 0.6, 0.5), up=(0.0, 1.0, 0.0), fovY=45.0)),
+    "two_box": (lambda: scenes.two_box_scene(shadow_catcher=False), scenes.TWO_BOX_CAMERA),
+    "terrain": (scenes.textured_terrain, scenes.TERRAIN_CAMERA),
+}
+PLAN = dict(threshold=0.25, dark_floor=0.05, min_length=4, min_pixels=8, refresh_period=16)
+
+
+def orbit(cam, angle):
+    """the camera turned by `angle` radians about the vertical axis through its look-at point"""
+    e, l = np.asarray(cam["eye"], np.float64), np.asarray(cam["lookat"], np.float64)
+    d = e - l
+    c, s = np.cos(angle), np.sin(angle)
+    return dict(cam, eye=(float(l[0] + c * d[0] + s * d[2]), float(e[1]), float(l[2] - s * d[0] + c * d[2])))
+
+
+class UpsampledLoop:
+    """The two renderers and every plane of the loop, allocated once; frame(k, prev, cam) runs one frame and returns its figures."""
+
+    def __init__(self, model, size, scale, lod=False, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32):
+        import torch
+
+        self.size, self.scale, self.lod = tuple(size), int(scale), lod
+        w, h = self.size
+        if w % self.scale or h % self.scale:
+            raise SystemExit(f"--size {w} {h} is not a multiple of --scale {self.scale}")
+        self.lo_size = lw, lh = w // self.scale, h // self.scale
+        self.plan = dict(PLAN, **(plan or {}))
+        self.filter = dict(iterations=iterations, sigma_lum=sigma_lum, min_length=min_length)
+        self.max_history = max_history
+        probe = probe if probe is not None else scenes.sky_probe(1024, 512).BuildCDF()
+        self.lo, self.hi = R.SampleRenderer(model), R.SampleRenderer(model)
+        self.lo.setProbe(probe)
+        self.lo.launchParams.samples_per_launch = spp
+        self.lo.resize(self.lo_size)
+        self.lo.uploadAccum(np.zeros((lh, lw, 4), np.float32))
+        self.hi.resize(self.size)  # no probe: the full-size renderer never shades
+
+        def planes(hh, ww, k):
+            return torch.zeros((hh, ww, k) if k > 1 else (hh, ww), device="cuda:0")
+
+        self.gbuf = [dict(hit=planes(lh, lw, 8), position=planes(lh, lw, 4), motion=planes(lh, lw, 2)) for _ in range(2)]
+        self.history, self.moments = [planes(lh, lw, 4) for _ in range(2)], [planes(lh, lw, 2) for _ in range(2)]
+        self.length = [planes(lh, lw, 1) for _ in range(2)]
+        self.variance, self.filtered, self.scratch, self.lo_albedo = planes(lh, lw, 1), planes(lh, lw, 4), planes(lh, lw, 4), planes(lh, lw, 4)
+        self.hi_gbuf = dict(hit=planes(h, w, 8), position=planes(h, w, 4))
+        self.albedo, self.upsampled, self.weight, self.final = planes(h, w, 4), planes(h, w, 4), planes(h, w, 1), planes(h, w, 4)
+        self.frame_rgba8 = torch.zeros((h, w), dtype=torch.int32, device="cuda:0")
+        self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
+        # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
+        self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
+        self.mips = {id(r): r.copyTextureMipsDevice() if lod else None for r in (self.lo, self.hi)}
+
+    def _albedo(self, r, hit, out):
+        if self.lod:
+            return r.surfaceLodPlanes(hit, self.table[id(r)], self.mips[id(r)], out=dict(albedo=out))["stats"]
+        return r.surfacePlanes(hit, self.table[id(r)], out=dict(albedo=out))["stats"]
+
+    def frame(self, k, prev, cam):
+        lo, hi = self.lo, self.hi
+        cur, old, i, o = self.gbuf[k & 1], self.gbuf[~k & 1], k & 1, ~k & 1
+        t0 = time.perf_counter()
+        # ---- the low-resolution chain (the aspect ratio is the same: a Camera serves both renderers)
+        lo.setCamera(cam)
+        g = lo.renderGBuffer(("hit", "position", "motion"), prev_cameras=prev, out=cur)["stats"]
+        s = self._albedo(lo, cur["hit"], self.lo_albedo)
+        geo = (cur["motion"], cur["hit"], cur["position"], old["hit"], old["position"], self.history[i], self.moments[i], self.length[i])
+        outs = dict(history_out=self.history[o], moments_out=self.moments[o], length_out=self.length[o], variance_out=self.variance)
+        p = lo.samplePlan(*geo, frame_index=k, **self.plan)
+        lo.launchParams.frame.subframe_index = k
+        rendered = lo.renderMask(p["mask"])
+        t = lo.temporalMoments(self.accum, *geo, albedo=self.lo_albedo, **outs, mask=p["mask"], color_scale=float(k + 1), max_history=self.max_history,
+                               clear_color=True)["stats"]
+        c = lo.temporalCarry(*geo, **outs, mask=p["mask"] == 0)["stats"]
+        assert c["lost"] == 0  # the plan samples every block that holds a pixel the carry could not carry
+        f = lo.filterPlanes(self.history[o], cur["hit"], cur["position"], variance=self.variance, length=self.length[o], out=self.filtered,
+                            scratch=self.scratch, **self.filter)["stats"]
+        t1 = time.perf_counter()
+        # ---- the display resolution: geometry, texture detail, the guided upsample, the product
+        hi.setCamera(cam)
+        G = hi.renderGBuffer(("hit", "position"), out=self.hi_gbuf)["stats"]
+        S = self._albedo(hi, self.hi_gbuf["hit"], self.albedo)
+        u = hi.upsamplePlanes(self.filtered, cur["hit"], cur["position"], self.hi_gbuf["hit"], self.hi_gbuf["position"], self.scale, out=self.upsampled,
+                              weight_out=self.weight)["stats"]
+        m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=self.frame_rgba8)["stats"]
+        t2 = time.perf_counter()
+        return dict(frame_ms=(t2 - t0) * 1e3, lo_ms=(t1 - t0) * 1e3, hi_ms=(t2 - t1) * 1e3, sampled=p["stats"]["sampled"], blocks=p["stats"]["blocks"],
+                    rendered=rendered, colour_ms=lo.stats()["render_ms"], lo_gbuffer_ms=g["kernel_ms"], lo_surface_ms=s["kernel_ms"],
+                    plan_ms=p["stats"]["kernel_ms"], temporal_ms=t["kernel_ms"], carry_ms=c["kernel_ms"], filter_ms=f["kernel_ms"],
+                    gbuffer_ms=G["kernel_ms"], surface_ms=S["kernel_ms"], upsample_ms=u["kernel_ms"], modulate_ms=m["kernel_ms"],
+                    pixels=u["pixels"], full=u["full"], rescued=u["rescued"], orphans=u["orphans"])
+
+    def close(self):
+        self.lo.close()
+        self.hi.close()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", choices=sorted(SCENES), default="textured")
+    ap.add_argument("--scale", type=int, choices=(2, 3, 4), default=2)
+    ap.add_argument("--size", type=int, nargs=2, default=[960, 540], help="the display size; a multiple of --scale")
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--spp", type=int, default=1)
+    ap.add_argument("--lod", action="store_true", help="footprint-filtered albedo (surfaceLodPlanes) at both resolutions")
+    ap.add_argument("--out-dir", default=".")
+    args = ap.parse_args(argv)
+    w, h = args.size
+    make, cam0 = SCENES[args.scene]
+    loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, spp=args.spp)
+    cam = R.make_camera(cam0, w / h)
+    for k in range(args.frames):
+        prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
+        x = loop.frame(k, prev, cam)
+        print(f"frame {k}: at {loop.lo_size[0]} x {loop.lo_size[1]}: {x['sampled']} of {x['blocks']} blocks sampled, {x['rendered']} pixels rendered; "
+              f"G-buffer {x['lo_gbuffer_ms']:.3f} ms, surface {x['lo_surface_ms']:.3f} ms, plan {x['plan_ms']:.3f} ms, colour {x['colour_ms']:.2f} ms, "
+              f"temporal {x['temporal_ms']:.3f} ms, carry {x['carry_ms']:.3f} ms, filter {x['filter_ms']:.3f} ms; at {w} x {h}: G-buffer "
+              f"{x['gbuffer_ms']:.3f} ms, surface {x['surface_ms']:.3f} ms, upsample {x['upsample_ms']:.3f} ms, modulate {x['modulate_ms']:.3f} ms; "
+              f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; frame {x['frame_ms']:.2f} ms")
+    np.save(os.path.join(args.out_dir, "upsampled_svgf_final.npy"), loop.final.cpu().numpy())
+    np.save(os.path.join(args.out_dir, "upsampled_svgf_frame.npy"), loop.frame_rgba8.cpu().numpy().view(np.uint32))
+    print(f"wrote upsampled_svgf_final.npy and upsampled_svgf_frame.npy to {args.out_dir}")
+    loop.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

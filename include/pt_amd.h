@@ -20,7 +20,7 @@
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
  * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes,
  * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
- * pt_copy_texture_mips_device, pt_surface_lod_planes — read and write them on
+ * pt_copy_texture_mips_device, pt_surface_lod_planes, pt_upsample_planes — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -38,7 +38,7 @@
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
  * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
  * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
- * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes.  A
+ * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_upsample_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -1275,6 +1275,78 @@ typedef struct pt_surface_lod_desc {
 } pt_surface_lod_desc;
 typedef struct pt_surface_lod_stats { uint64_t pixels, hits, stale, textured, minified; double kernel_ms; } pt_surface_lod_stats;
 int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* desc, pt_surface_lod_stats* stats /* may be NULL */);
+
+/* GUIDED UPSAMPLING (no reference counterpart): a low-resolution colour plane brought to the context's resolution under the guidance of
+ * both G-buffers — a joint-bilateral upsample.  The noisy, low-frequency part of the image (the demodulated irradiance) is traced and
+ * filtered by a second context of width/scale x height/scale over the same scene; the full-size context only makes a G-buffer and an
+ * albedo (pt_render_gbuffer, pt_surface[_lod]_planes), calls this pass, and multiplies the albedo back (pt_modulate_planes).  "Same
+ * surface" is the chain's single notion of it: mesh, normal and plane distance, exactly the tests of pt_temporal_accumulate and
+ * pt_filter_planes.  The call is made on the FULL-size context and is stateless: every plane is caller-owned DEVICE memory of the
+ * context's device, checked exactly as pt_render_gbuffer checks its planes (4-byte aligned, no wider alignment assumed); hit, position,
+ * out and weight_out are frame-sized and indexed Y * width + X, the three low-resolution planes hold lo_width * lo_height pixels and are
+ * indexed y * lo_width + x.  block_mask is HOST memory.
+ * Which pixels: exactly those pt_render_gbuffer would write with the same mask — the rank's owned pixels, view pixels only while views are
+ * set, whole blocks of block_mask (NULL: every block).  No other pixel of out or weight_out is written.  Zero pixels launch nothing and
+ * return PT_OK.
+ * Rectangles.  A pixel p = (X, Y) works inside its rectangle [x0,x1) x [y0,y1): its view (found by the pixel's 8x8 block), or the whole
+ * frame without views.  While views are set, every view's x, y, width and height must be multiples of scale.  The low-resolution
+ * rectangle is that rectangle divided by scale, [x0/s, x1/s) x [y0/s, y1/s) in a plane lo_width wide — what a low-resolution context holds
+ * whose views are the full-size ones divided by scale.  No tap leaves it.
+ * Arithmetic per pixel p, with s = scale — integers and float32, one rounding per operation, no fused multiply-add, in exactly this order,
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z as pt_temporal_accumulate and pt_filter_planes define it; float32 NumPy evaluating this
+ * reproduces every output bit for bit (tests/upsample_ref.py):
+ *   1. Per axis, in integers and one float32 division.  For x: a = X - x0; r = a % s; cx = x0/s + a/s (the low-res pixel that contains p);
+ *      t = (float)(2*r + 1 - s) / (float)(2*s).  If t < 0: i = cx - 1, fx = t + 1.0f.  Else i = cx, fx = t.  Likewise for y: cy, j, fy.
+ *      (The centre of p lies at (a + 0.5)/s - 0.5 in low-res pixel units; i is its floor, fx its fraction.)
+ *   2. A low-res pixel q counts for p when q lies inside the low-resolution rectangle; the three colour words of lo_color[q] are finite
+ *      (exponent-bit test); and either both are misses (hit[p].prim < 0 and lo_hit[q].prim < 0) or both are hits (hit[p].prim >= 0 and
+ *      lo_hit[q].prim >= 0) with lo_hit[q].mesh == hit[p].mesh, dot3(ng_p, ng_q) >= normal_cos and
+ *      fabsf(dot3(ng_p, lo_position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t — the distance is the full-res pixel's, as in the
+ *      filter.  There is no block test on q: the low-res plane is the caller's and is complete, or inert where it is not.
+ *   3. Bilinear stage.  The taps are q = (i + dx, j + dy) in the order (0,0), (1,0), (0,1), (1,1); wx = dx ? fx : 1.0f - fx;
+ *      wy = dy ? fy : 1.0f - fy; w = wx * wy.  A tap with w == 0 does not count (scale 3, the centre residue).  For a tap that counts,
+ *      S += lo_color[q] * w per component (all four words) and W += w; a tap that does not count contributes nothing.
+ *      If W > 0: out[p] = S / W per component, weight_out[p] = W.  stats->full counts the pixels whose four taps all counted.
+ *   4. Rescue, when W == 0.  The 16 low-res pixels q = (i + dx, j + dy), dy = -1..2 outer, dx = -1..2 inner, go through the test of 2
+ *      unweighted: for one that counts S += lo_color[q] per component and N += 1.0f.  If N > 0: out[p] = S / N, weight_out[p] = 0.0f and
+ *      the pixel is counted in stats->rescued.
+ *   5. Orphan, when the rescue finds none either.  out[p] = lo_color[(cx, cy)], the four words as they are (the low-res pixel that
+ *      contains p); weight_out[p] = -1.0f; the pixel is counted in stats->orphans.  A caller can turn weight_out < 0 into a block mask and
+ *      path-trace those blocks on the full-size context.
+ * What the output means: where weight_out > 0 the pixel holds an interpolation of the low-res pixels of its own surface around it, where
+ * it is 0 an average of such pixels from one ring further out, where it is -1 a value of another surface.  A miss is interpolated from
+ * misses: the environment is not evaluated per pixel.
+ * Overlap: out and weight_out may overlap no other plane; the read-only planes may alias one another.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; a required
+ * plane NULL (all but weight_out and block_mask); a plane that fails the pointer checks (the low-res planes against lo_width * lo_height
+ * pixels); a forbidden overlap; scale outside 2..4; lo_width * scale != width or lo_height * scale != height (the message holds both
+ * sizes); a view rectangle that is not a multiple of scale (the message names the view); flags != 0; a parameter out of its range or not
+ * finite.
+ * Ordering and state, as pt_filter_planes: the call first waits for the frames in flight and completes queued queries, runs on
+ * pt_stream(ctx) under the STREAM CONTRACT and is complete when it returns; the low-res planes, made on another context's stream, must be
+ * complete before the call.  It reads and writes no context state except through the pointers the caller passed: the frame buffers, the
+ * accumulation, the adaptive state, the schedule trial and pt_stats are as they were.
+ * stats: pixels processed; hits (hit[p].prim >= 0) among them; full, rescued and orphans as above (pixels - full - rescued - orphans took
+ * the bilinear stage with fewer than four taps); device time of the pass (hipEvents; the mask compaction included when there is a mask).
+ * Not part of this interface: an asynchronous variant; a pt_multi_* wrapper (per-rank calls work when the rank holds the whole low-res
+ * image); per-pixel evaluation of the probe on misses; non-integer scales; a low-res block set; the refill of the orphans. */
+enum pt_upsample_flags { PT_UPSAMPLE_RESERVED = 0 };  /* no flag defined yet: flags must be 0 */
+typedef struct pt_upsample_desc {
+    const float* lo_color;     /* lw*lh x 4: what is upsampled (the low-res chain's pt_filter_planes out); required */
+    const void*  lo_hit;       /* lw*lh x pt_hit: the low-res frame's G-buffer; required */
+    const float* lo_position;  /* lw*lh x 4; required */
+    const void*  hit;          /* w*h x pt_hit: this context's G-buffer of the same frame; required */
+    const float* position;     /* w*h x 4; required */
+    float*    out;             /* w*h x 4; required, exclusive */
+    float*    weight_out;      /* w*h f32 or NULL, exclusive: W of the bilinear stage; 0.0f rescued; -1.0f orphan */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    uint32_t  lo_width, lo_height, scale;   /* scale 2..4; lo_width*scale == width, lo_height*scale == height */
+    float     normal_cos;      /* [-1,1] */
+    float     plane_eps;       /* finite, >= 0 */
+    uint32_t  flags;           /* 0 */
+} pt_upsample_desc;
+typedef struct pt_upsample_stats { uint64_t pixels, hits, full, rescued, orphans; double kernel_ms; } pt_upsample_stats;
+int pt_upsample_planes(pt_ctx* ctx, const pt_upsample_desc* desc, pt_upsample_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -368,6 +368,15 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // Guided upsampling (pt_upsample_planes), on the FULL-size renderer: a low-resolution colour plane (a second renderer's filterPlanes
+    // out) brought to this resolution under both G-buffers with the chain's mesh / normal / plane tests.  Stateless and synchronous.
+    // Returns the pixels processed, the hits, and how many took four taps, the rescue and the orphan branch, and the device time.
+    pt_upsample_stats upsamplePlanes(const pt_upsample_desc& d, pt_upsample_stats* stats = nullptr) {
+        pt_upsample_stats s{};
+        ck(pt_upsample_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // The SVGF temporal stage in one pass (pt_temporal_moments): demodulated colour, colour history, luminance moments and variance through
     // one gather, with an optional clamp of the history to this frame's 3x3 neighbourhood.  Every plane of `d` is DEVICE memory of this
     // context's device, frame-sized; block_mask is host memory.  Stateless and synchronous; the caller ping-pongs history, moments and

@@ -18,3 +18,4 @@
 #include "pt_plan.hip"
 #include "pt_surface.hip"
 #include "pt_surface_lod.hip"
+#include "pt_upsample.hip"

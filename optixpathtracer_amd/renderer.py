@@ -780,6 +780,42 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_filter_planes", desc, _lib.FilterStats(), result)
 
+    def upsamplePlanes(self, lo_color, lo_hit, lo_position, hit, position, scale, out=None, weight_out=None, mask=None, normal_cos=0.9,
+                       plane_eps=0.01) -> dict:
+        """Guided upsampling: brings a low-resolution colour plane to this renderer's resolution with a joint-bilateral rule over both
+        G-buffers — mesh, normal and plane distance, the tests of temporalAccumulate and filterPlanes — per view and on the pixel set of the
+        mask (pt_upsample_planes, include/pt_amd.h: the arithmetic, in full).  Called on the FULL-size renderer.
+
+        Every plane is a CUDA tensor on the context's device — float32, dense, any 4-byte-aligned storage offset — or a raw device
+        pointer.  lo_color (h/scale, w/scale, 4), lo_hit (.., 8) and lo_position (.., 4) come from a second renderer of that size over
+        the same model (its filterPlanes out, its renderGBuffer planes of the same frame; with views, its views are this renderer's divided
+        by scale); hit (h, w, 8) and position (h, w, 4) are this renderer's renderGBuffer planes.  scale is 2, 3 or 4 and divides the
+        frame's size (and every view's rectangle).  out (h, w, 4) is allocated with torch, zero-filled, when None; weight_out ((h, w),
+        optional) receives the bilinear stage's weight sum, 0 for a rescued pixel and -1 for an orphan; pixels outside the views, the mask
+        or the rank's partition are not written.  mask: 8x8 blocks as renderMask takes them, None = every block.
+        Ordering is on the device: the library's stream waits for what torch has enqueued on its current stream; the low-res renderer's
+        calls are complete when they return; the call returns when the outputs are complete.  The frame buffers, the accumulation and the
+        path state are left alone (unless passed in as planes).
+        Returns {"out", "weight_out": the tensor (None for a raw pointer or an absent plane), "stats": {pixels, hits, full, rescued,
+        orphans, kernel_ms}}."""
+        s = int(scale)
+        if not 2 <= s <= 4:
+            raise ValueError("upsamplePlanes: scale must be in [2,4]")
+        w, h = self.launchParams.frame.size
+        if w % s or h % s:
+            raise ValueError(f"upsamplePlanes: scale {s} does not divide the frame's {w} x {h}")
+        lw, lh = w // s, h // s
+        widths = dict(_lib.UPSAMPLE_PLANES, lo_color=(lh, lw, 4), lo_hit=(lh, lw, 8), lo_position=(lh, lw, 4))
+        given = dict(lo_color=lo_color, lo_hit=lo_hit, lo_position=lo_position, hit=hit, position=position, out=out, weight_out=weight_out)
+        desc = _lib.UpsampleDesc()
+        result = self._bind_planes("upsamplePlanes", desc, given, widths, ("lo_color", "lo_hit", "lo_position", "hit", "position"), _lib.UPSAMPLE_OUTPUTS,
+                                   alloc=("out",))
+        m = self._bind_mask("upsamplePlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.lo_width, desc.lo_height, desc.scale = lw, lh, s
+        desc.normal_cos, desc.plane_eps = float(normal_cos), float(plane_eps)
+        desc.flags = 0
+        return self._run_pass("pt_upsample_planes", desc, _lib.UpsampleStats(), result)
+
     def temporalMoments(self, color, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, albedo=None,
                         history_out=None, moments_out=None, length_out=None, variance_out=None, variance=True, mask=None, color_scale=1.0,
                         albedo_min=0.0, normal_cos=0.9, plane_eps=0.01, min_weight=0.25, clamp_k=None, max_history=32, clear_color=False) -> dict:
