@@ -2,7 +2,7 @@
 // every plane the caller's.  k_filter_prepare makes the record (colour, variance) of every pixel of the set, k_filter_pass is one a-trous
 // pass at tap spacing `step`; the passes ping-pong between the caller's `out` and `scratch`.
 #pragma once
-#include "pt_temporal.h"
+#include "pt_pass_dev.h"
 
 // One thread per entry of the frame's pixel list, as k_temporal.  The list is in 8x8-block order, so a wave is one block, and the lanes' tap
 // (dx, dy) is the same block displaced by step * (dx, dy): eight runs of eight neighbouring pixels, 128 contiguous bytes of each 16-byte
@@ -36,59 +36,25 @@ struct FilterArgs {
 
 #define FL_INERT_BITS 0xbf800000u // -1.0f
 
-PT_DEV float fl_lum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
-PT_DEV float fl_max0(float v) { return v > 0.0f ? v : 0.0f; }
 PT_DEV float fl_min80(float v) { return v < 80.0f ? v : 80.0f; }
 
-// the pixel's side of the tap tests
+// the pixel's side of the tap tests (pt_pass_dev.h): the pixel and its rectangle; mesh, normal, position, plane bound
 struct FilterPixel {
-    int X, Y, x0, y0, x1, y1; // the pixel, its rectangle [x0, x1) x [y0, y1), all in frame coordinates
-    int mesh;
-    v3 ng, P;
-    float plane_max;
+    PassPixel px;
+    SurfaceKey key;
 };
-
-template <bool VIEWS>
-PT_DEV FilterPixel fl_pixel(const FilterArgs& a, const ViewParams& vp, uint32_t xy) {
-    FilterPixel p;
-    p.X = (int)(xy & 0xffffu);
-    p.Y = (int)(xy >> 16);
-    p.x0 = 0;
-    p.y0 = 0;
-    p.x1 = a.width;
-    p.y1 = a.height;
-    if (VIEWS) {
-        const uint32_t vi = vp.vblock[(uint32_t)(p.Y >> 3) * vp.nbx + (uint32_t)(p.X >> 3)]; // the list holds view pixels only: never 0xffff
-        p.x0 = vp.views[vi].x;
-        p.y0 = vp.views[vi].y;
-        p.x1 = p.x0 + vp.views[vi].width;
-        p.y1 = p.y0 + vp.views[vi].height;
-    }
-    return p;
-}
+// An inert pixel never gets here, so the key is never a miss's; the first half of the hit record gives its t alone.
 PT_DEV void fl_guides(const FilterArgs& a, FilterPixel& p, size_t pi) {
-    const float t = a.hit[8 * pi];
-    const float4 hb = tp_load4(a.hit + 8 * pi + 4);
-    const float4 P = tp_load4(a.position + 4 * pi);
-    p.mesh = __float_as_int(hb.x);
-    p.ng = mk3(hb.y, hb.z, hb.w);
-    p.P = mk3(P.x, P.y, P.z);
-    p.plane_max = a.plane_eps * t;
+    p.key = surface_key(false, a.hit[8 * pi], tp_load4(a.hit + 8 * pi + 4), tp_load4(a.position + 4 * pi), a.plane_eps);
 }
 // rect and block: is (qx, qy) a pixel whose planes and record may be looked at
-PT_DEV bool fl_reachable(const FilterArgs& a, const FilterPixel& p, int qx, int qy) {
-    if (qx < p.x0 || qx >= p.x1 || qy < p.y0 || qy >= p.y1) return false;
-    return a.inset[(uint32_t)(qy >> 3) * a.nbx + (uint32_t)(qx >> 3)] != 0;
-}
+PT_DEV bool fl_reachable(const FilterArgs& a, const FilterPixel& p, int qx, int qy) { return pass_reachable(p.px, a.inset, a.nbx, qx, qy); }
 // mesh, normal, plane
 PT_DEV bool fl_same_surface(const FilterArgs& a, const FilterPixel& p, size_t q) {
-    const float4 qb = tp_load4(a.hit + 8 * q + 4);
-    if (__float_as_int(qb.x) != p.mesh || !(dot3(p.ng, mk3(qb.y, qb.z, qb.w)) >= a.normal_cos)) return false;
-    const float4 Q = tp_load4(a.position + 4 * q);
-    return fabsf(dot3(p.ng, mk3(Q.x - p.P.x, Q.y - p.P.y, Q.z - p.P.z))) <= p.plane_max;
+    return same_facet(p.key, a.hit, q, a.normal_cos) && same_plane(p.key, a.position, q);
 }
 PT_DEV bool fl_inert_input(const FilterArgs& a, size_t q, float4 c) {
-    return __float_as_int(a.hit[8 * q + 3]) < 0 || !(tp_finite(c.x) && tp_finite(c.y) && tp_finite(c.z));
+    return hit_is_miss(a.hit[8 * q + 3]) || !(tp_finite(c.x) && tp_finite(c.y) && tp_finite(c.z));
 }
 PT_DEV void fl_store(const FilterArgs& a, size_t pi, float4 rec, bool inert) {
     if (inert) rec.w = a.last ? 0.0f : __uint_as_float(FL_INERT_BITS);
@@ -103,8 +69,9 @@ __global__ void __launch_bounds__(256) k_filter_prepare(FilterArgs a, ViewParams
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     bool live = false, spatial = false;
     if (i < a.n) {
-        FilterPixel p = fl_pixel<VIEWS>(a, vp, a.pixels[i]);
-        const size_t pi = (size_t)p.Y * (size_t)a.width + (size_t)p.X;
+        FilterPixel p;
+        p.px = pass_pixel<VIEWS>(vp, a.pixels[i], a.width, a.height);
+        const size_t pi = (size_t)p.px.Y * (size_t)a.width + (size_t)p.px.X;
         const float4 c = tp_load4(a.color + 4 * pi);
         live = !fl_inert_input(a, pi, c);
         float v = 0.0f;
@@ -117,7 +84,7 @@ __global__ void __launch_bounds__(256) k_filter_prepare(FilterArgs a, ViewParams
                 float n = 0.0f, s1 = 0.0f, s2 = 0.0f;
                 for (int dy = -3; dy <= 3; ++dy)
                     for (int dx = -3; dx <= 3; ++dx) {
-                        const int qx = p.X + dx, qy = p.Y + dy;
+                        const int qx = (int)p.px.X + dx, qy = (int)p.px.Y + dy;
                         bool counts = (dx | dy) == 0;
                         float4 cq = c;
                         if (!counts && fl_reachable(a, p, qx, qy)) {
@@ -138,11 +105,7 @@ __global__ void __launch_bounds__(256) k_filter_prepare(FilterArgs a, ViewParams
         }
         fl_store(a, pi, make_float4(c.x, c.y, c.z, v), !live);
     }
-    const unsigned long long lm = __ballot(live), sm = __ballot(spatial);
-    if ((threadIdx.x & 63u) == 0u) {
-        if (lm) atomicAdd(a.counts, (unsigned long long)__popcll(lm));
-        if (sm) atomicAdd(a.counts + 1, (unsigned long long)__popcll(sm));
-    }
+    pass_tally(a.counts, {live, spatial});
 #endif
 }
 
@@ -152,8 +115,9 @@ __global__ void __launch_bounds__(256) k_filter_pass(FilterArgs a, ViewParams vp
 #if __HIP_DEVICE_COMPILE__
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= a.n) return;
-    FilterPixel p = fl_pixel<VIEWS>(a, vp, a.pixels[i]);
-    const size_t pi = (size_t)p.Y * (size_t)a.width + (size_t)p.X;
+    FilterPixel p;
+    p.px = pass_pixel<VIEWS>(vp, a.pixels[i], a.width, a.height);
+    const size_t pi = (size_t)p.px.Y * (size_t)a.width + (size_t)p.px.X;
     const float4 r = tp_load4(a.src + 4 * pi);
     if (__float_as_uint(r.w) == FL_INERT_BITS) {
         fl_store(a, pi, r, true);
@@ -169,7 +133,7 @@ __global__ void __launch_bounds__(256) k_filter_pass(FilterArgs a, ViewParams vp
             const float kk = (dy ? 0.25f : 0.5f) * (dx ? 0.25f : 0.5f);
             float vq = r.w;
             bool counts = (dx | dy) == 0;
-            const int qx = p.X + dx, qy = p.Y + dy;
+            const int qx = (int)p.px.X + dx, qy = (int)p.px.Y + dy;
             if (!counts && fl_reachable(a, p, qx, qy)) {
                 const size_t q = (size_t)qy * (size_t)a.width + (size_t)qx;
                 vq = a.src[4 * q + 3];
@@ -195,7 +159,7 @@ __global__ void __launch_bounds__(256) k_filter_pass(FilterArgs a, ViewParams vp
             const float kk = ky * kx;
             float4 rq = r;
             bool counts = (dx | dy) == 0;
-            const int qx = p.X + a.step * dx, qy = p.Y + a.step * dy;
+            const int qx = (int)p.px.X + a.step * dx, qy = (int)p.px.Y + a.step * dy;
             if (!counts && fl_reachable(a, p, qx, qy)) {
                 const size_t q = (size_t)qy * (size_t)a.width + (size_t)qx;
                 rq = tp_load4(a.src + 4 * q);

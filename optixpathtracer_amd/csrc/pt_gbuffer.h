@@ -2,6 +2,7 @@
 #pragma once
 #include "pt_bvh8.h"
 #include "pt_kernels.h"
+#include "pt_pass_dev.h"
 
 // One wave per 64 consecutive entries of the frame's pixel list (8x8-block order: a full packet is one block's frustum).  Each lane builds
 // its ray in registers from the pixel word and the camera (generate_path's expression with both jitter values 0.5f), the wave traverses
@@ -26,13 +27,6 @@ struct GBufferArgs {
     const float* prev;       // [max(1, views)][12] eye, U, V, W of the previous frame; null when no motion plane is asked for
     float *hit, *depth, *position, *motion, *ray; // the planes, null = not asked for
 };
-
-// Four (two) words to a plane that is only known to be 4-byte aligned, as ONE store: a copy of known size with alignment 4 compiles to
-// global_store_dwordx4 (dwordx2), which the hardware takes at any 4-byte address — a plane at a 16-byte address gets 16-byte-aligned stores
-// from the same instruction, so there is no second code path.  (Two paths chosen by a flag were tried first: the compiler merged them into
-// dword stores, 23 per pixel for the five planes.)
-PT_DEV void gb_store4(float* p, float4 v) { __builtin_memcpy(p, &v, 16); }
-PT_DEV void gb_store2(float* p, float2 v) { __builtin_memcpy(p, &v, 8); }
 
 // the camera of frame pixel (X, Y), its coordinates in that camera's image and the index of its previous camera (pixel_camera, pt_kernels.h)
 struct GBufferCamera {
@@ -84,7 +78,7 @@ __global__ void __launch_bounds__(64) k_gbuffer(GBufferArgs a, ViewParams vp) {
         float4 o4 = make_float4(0.f, 0.f, 0.f, 1.f), d4 = make_float4(0.f, 0.f, 1.f, -1.f); // the neutral ray of a lane past the end
         if (valid) {
             xy = a.pixels[pos];
-            const GBufferCamera cam = gbuffer_camera<VIEWS>(a, vp, xy & 0xffffu, xy >> 16);
+            const GBufferCamera cam = gbuffer_camera<VIEWS>(a, vp, pass_x(xy), pass_y(xy));
             const float dx = 2.0f * (((float)cam.x + 0.5f) / (float)cam.width) - 1.0f;
             const float dy = 2.0f * (((float)cam.y + 0.5f) / (float)cam.height) - 1.0f;
             const v3 dir = normalize3(add3(add3(scl3(cam.U, dx), scl3(cam.V, dy)), cam.W));
@@ -196,7 +190,7 @@ __global__ void __launch_bounds__(64) k_gbuffer(GBufferArgs a, ViewParams vp) {
         // ---------------- (best, bleaf) -> the planes; which planes are wanted is uniform for the launch
         const bool is_hit = valid && bleaf >= 0;
         if (valid) {
-            const uint32_t X = xy & 0xffffu, Y = xy >> 16;
+            const uint32_t X = pass_x(xy), Y = pass_y(xy);
             const size_t pi = (size_t)Y * (size_t)a.width + X;
             const v3 ray_o = r.o, ray_dir = r.d;
             if (a.ray) {

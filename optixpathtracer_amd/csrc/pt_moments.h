@@ -2,13 +2,11 @@
 // reproject colour AND luminance moments through one gather, clamp the history to the 3x3 neighbourhood of this frame's colour, blend, write the
 // variance — and the remodulation pass that ends the chain behind pt_filter_planes.  Stateless, every plane the caller's.
 #pragma once
-#include "pt_filter.h"
+#include "pt_pass_dev.h"
 
 // k_tmom: one thread per entry of the frame's pixel list, the shape of k_temporal (pt_temporal.h): the list is in 8x8-block order, so a wave
-// is one block and the four-tap footprints of its lanes fall into one displaced neighbourhood.  The tap loop is k_temporal's, restated: a tap
-// is read cheapest word first — the history length (4 bytes), the previous hit record's mesh and normal (16 bytes; the primitive word alone
-// under a miss), prev_position (16 bytes) — and only a tap that survived the geometry tests loads its moments (8 bytes) and its history
-// (16 bytes).  What three pt_temporal_accumulate calls gathered three times is gathered once.
+// is one block and the four-tap footprints of its lanes fall into one displaced neighbourhood.  Steps 2 to 4 are rp_gather<true>
+// (pt_pass_dev.h), k_temporal's gather with the moments plane: what three pt_temporal_accumulate calls gathered three times is gathered once.
 //
 // CLAMP is a template parameter: the 3x3 window of demodulated colours, its up to nine colour and nine albedo loads and its six sums exist
 // only in that instantiation, behind the tap loop, when the taps' registers are dead; the other one does not pay a register for it.  The
@@ -25,15 +23,14 @@
 struct TMomArgs {
     const uint32_t* pixels; // x | y << 16 in frame coordinates, block order
     uint32_t n;
-    int width, height; // the frame: the planes are indexed Y * width + X
+    GatherPlanes g;
     const float* color;
     const float* albedo; // or null
-    const float *motion, *hit, *position, *prev_hit, *prev_position, *history_in, *moments_in, *length_in;
     float *history_out, *moments_out, *length_out;
     float* variance_out;  // or null
     const uint8_t* inset; // [nbx * nby] 1 = the block belongs to the call's set (CLAMP only)
     uint32_t nbx;
-    float color_scale, albedo_min, normal_cos, plane_eps, min_weight, clamp_k;
+    float color_scale, albedo_min, clamp_k;
     float max_n;                // (float)(max_history - 1)
     unsigned long long* counts; // {reprojected, clamped}, zero at launch; one atomic per wave each
 };
@@ -57,110 +54,35 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) k_tm
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     bool valid = false, clamped = false;
     if (i < a.n) {
-        const uint32_t xy = a.pixels[i];
-        const uint32_t X = xy & 0xffffu, Y = xy >> 16;
         // the pixel's rectangle: its view (found by block, as k_temporal finds it) or the whole frame
-        int x0 = 0, y0 = 0, wr = a.width, hr = a.height;
-        if (VIEWS) {
-            const uint32_t vi = vp.vblock[(Y >> 3) * vp.nbx + (X >> 3)]; // the list holds view pixels only: never 0xffff
-            x0 = vp.views[vi].x;
-            y0 = vp.views[vi].y;
-            wr = vp.views[vi].width;
-            hr = vp.views[vi].height;
-        }
-        const int x = (int)X - x0, y = (int)Y - y0;
-        const size_t p = (size_t)Y * (size_t)a.width + X;
+        const PassPixel px = pass_pixel<VIEWS>(vp, a.pixels[i], a.g.width, a.g.height);
+        const size_t p = (size_t)px.Y * (size_t)a.g.width + px.X;
         // ---------------- 0, 1. this frame: demodulated colour, luminance, moments
         const v3 d = tm_demod(a.color, a.albedo, p, a.color_scale, a.albedo_min);
         const float l = fl_lum(d.x, d.y, d.z);
         const float m1 = l, m2 = l * l;
-        // ---------------- 2. previous position
-        const float2 mv = tp_load2(a.motion + 2 * p);
-        const float px = (float)x + mv.x, py = (float)y + mv.y;
-        float wsum = 0.0f, nprev = 0.0f;
-        v3 hsum = mk3(0.0f);
-        float msx = 0.0f, msy = 0.0f;
-        bool any = false;
-        if (px >= -1.0f && px <= (float)wr && py >= -1.0f && py <= (float)hr) { // a NaN fails
-            const float flx = floorf(px), fly = floorf(py);
-            const int ix = (int)flx, iy = (int)fly;
-            const float fx = px - flx, fy = py - fly;
-            const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
-            const float4 ha = tp_load4(a.hit + 8 * p), hb = tp_load4(a.hit + 8 * p + 4); // t, u, v, prim | mesh, ng.xyz
-            const float4 P = tp_load4(a.position + 4 * p);
-            const bool miss = __float_as_int(ha.w) < 0;
-            const v3 ng = mk3(hb.y, hb.z, hb.w);
-            const float plane_max = a.plane_eps * ha.x;
-            float wt[4], mx[4], my[4];
-            v3 ht[4];
-            // ---------------- 3. which taps count; order (0,0), (1,0), (0,1), (1,1)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ti = k & 1, tj = k >> 1;
-                const int tx = ix + ti, ty = iy + tj;
-                const float w = wx[ti] * wy[tj];
-                wt[k] = 0.0f;
-                mx[k] = 0.0f;
-                my[k] = 0.0f;
-                ht[k] = mk3(0.0f);
-                if (tx >= 0 && tx < wr && ty >= 0 && ty < hr && w > 0.0f) {
-                    const size_t q = (size_t)(y0 + ty) * (size_t)a.width + (size_t)(x0 + tx);
-                    const float len = a.length_in[q];
-                    if (len >= 1.0f) {
-                        bool alive;
-                        if (miss) {
-                            alive = __float_as_int(a.prev_hit[8 * q + 3]) < 0;
-                        } else {
-                            const float4 qb = tp_load4(a.prev_hit + 8 * q + 4);
-                            alive = __float_as_int(qb.x) == __float_as_int(hb.x) && dot3(ng, mk3(qb.y, qb.z, qb.w)) >= a.normal_cos;
-                            if (alive) {
-                                const float4 Q = tp_load4(a.prev_position + 4 * q);
-                                alive = fabsf(dot3(ng, mk3(Q.x - P.x, Q.y - P.y, Q.z - P.z))) <= plane_max;
-                            }
-                        }
-                        if (alive) {
-                            const float2 mq = tp_load2(a.moments_in + 2 * q);
-                            const float4 hq = tp_load4(a.history_in + 4 * q);
-                            if (tp_finite(hq.x) && tp_finite(hq.y) && tp_finite(hq.z) && tp_finite(mq.x) && tp_finite(mq.y)) {
-                                wt[k] = w;
-                                ht[k] = mk3(w * hq.x, w * hq.y, w * hq.z);
-                                mx[k] = w * mq.x;
-                                my[k] = w * mq.y;
-                                nprev = any ? fminf(nprev, len) : len;
-                                any = true;
-                            }
-                        }
-                    }
-                }
-            }
-            // ---------------- 4. sums, in tap order
-            wsum = ((wt[0] + wt[1]) + wt[2]) + wt[3];
-            hsum = mk3(((ht[0].x + ht[1].x) + ht[2].x) + ht[3].x, ((ht[0].y + ht[1].y) + ht[2].y) + ht[3].y, ((ht[0].z + ht[1].z) + ht[2].z) + ht[3].z);
-            msx = ((mx[0] + mx[1]) + mx[2]) + mx[3];
-            msy = ((my[0] + my[1]) + my[2]) + my[3];
-        }
-        valid = any && wsum >= a.min_weight;
+        // ---------------- 2, 3, 4. previous position, taps, sums
+        const Gather g = rp_gather<true>(a.g, px);
+        valid = g.valid;
         v3 out = d;
         float mo1 = m1, mo2 = m2, len = 1.0f;
         if (valid) {
             // ---------------- 5. the reprojected history
-            v3 H = mk3(hsum.x / wsum, hsum.y / wsum, hsum.z / wsum);
-            const float M1 = msx / wsum, M2 = msy / wsum;
-            const float n = fminf(nprev, a.max_n);
+            v3 H = mk3(g.hsum.x / g.wsum, g.hsum.y / g.wsum, g.hsum.z / g.wsum);
+            const float M1 = g.msx / g.wsum, M2 = g.msy / g.wsum;
+            const float n = fminf(g.nprev, a.max_n);
             const float al = 1.0f / (n + 1.0f);
             if (CLAMP) {
                 // ---------------- 5b. clamp to this frame's 3x3 neighbourhood, row-major
                 float cnt = 0.0f;
                 v3 s1 = mk3(0.0f), s2 = mk3(0.0f);
-                const int x1 = x0 + wr, y1 = y0 + hr;
 #pragma unroll
                 for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
                     for (int dx = -1; dx <= 1; ++dx) {
-                        const int qx = (int)X + dx, qy = (int)Y + dy;
-                        if (qx < x0 || qx >= x1 || qy < y0 || qy >= y1) continue;
-                        if (a.inset[(uint32_t)(qy >> 3) * a.nbx + (uint32_t)(qx >> 3)] == 0) continue;
-                        const v3 dq = (dx | dy) == 0 ? d : tm_demod(a.color, a.albedo, (size_t)qy * (size_t)a.width + (size_t)qx, a.color_scale, a.albedo_min);
+                        const int qx = (int)px.X + dx, qy = (int)px.Y + dy;
+                        if (!pass_reachable(px, a.inset, a.nbx, qx, qy)) continue;
+                        const v3 dq = (dx | dy) == 0 ? d : tm_demod(a.color, a.albedo, (size_t)qy * (size_t)a.g.width + (size_t)qx, a.color_scale, a.albedo_min);
                         if (tp_finite(dq.x) && tp_finite(dq.y) && tp_finite(dq.z)) {
                             cnt += 1.0f;
                             s1 = mk3(s1.x + dq.x, s1.y + dq.y, s1.z + dq.z);
@@ -188,12 +110,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) k_tm
         a.length_out[p] = len;
         if (a.variance_out) a.variance_out[p] = fl_max0(mo2 - mo1 * mo1);
     }
-    const unsigned long long vm = __ballot(valid);
-    if ((threadIdx.x & 63u) == 0u && vm) atomicAdd(a.counts, (unsigned long long)__popcll(vm));
-    if (CLAMP) {
-        const unsigned long long cm = __ballot(clamped);
-        if ((threadIdx.x & 63u) == 0u && cm) atomicAdd(a.counts + 1, (unsigned long long)__popcll(cm));
-    }
+    pass_tally(a.counts, {valid, clamped}); // clamped: never without CLAMP
 #endif
 }
 
@@ -203,7 +120,7 @@ __global__ void __launch_bounds__(256) k_clear4(const uint32_t* pixels, uint32_t
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint32_t xy = pixels[i];
-    const size_t p = (size_t)(xy >> 16) * (size_t)width + (xy & 0xffffu);
+    const size_t p = (size_t)pass_y(xy) * (size_t)width + pass_x(xy);
     gb_store4(color + 4 * p, make_float4(0.f, 0.f, 0.f, 0.f));
 #endif
 }
@@ -226,7 +143,7 @@ __global__ void __launch_bounds__(256) k_modulate(ModulateArgs a) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= a.n) return;
     const uint32_t xy = a.pixels[i];
-    const size_t p = (size_t)(xy >> 16) * (size_t)a.width + (xy & 0xffffu);
+    const size_t p = (size_t)pass_y(xy) * (size_t)a.width + pass_x(xy);
     const float4 c = tp_load4(a.color + 4 * p);
     v3 r = mk3(c.x, c.y, c.z); // den = 1 without an albedo plane: x * 1.0f is x
     if (a.albedo) {

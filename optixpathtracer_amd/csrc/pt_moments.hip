@@ -51,10 +51,11 @@ extern "C" int pt_temporal_moments(pt_ctx* ctx, const pt_tmom_desc* desc, pt_tmo
     const uint32_t n = run.n;
     hipError_t e = hipSuccess;
     if (n != 0) {
-        const TMomArgs ta{run.pixels, n, ctx->width, ctx->height, desc->color, desc->albedo, desc->motion, reinterpret_cast<const float*>(desc->hit), desc->position,
-                          reinterpret_cast<const float*>(desc->prev_hit), desc->prev_position, desc->history_in, desc->moments_in, desc->length_in,
-                          desc->history_out, desc->moments_out, desc->length_out, desc->variance_out, d_inset, B.nbx, desc->color_scale, desc->albedo_min,
-                          desc->normal_cos, desc->plane_eps, desc->min_weight, clamp ? desc->clamp_k : 0.f, (float)(desc->max_history - 1u), run.counts()};
+        const TMomArgs ta{run.pixels, n,
+                          {desc->motion, reinterpret_cast<const float*>(desc->hit), desc->position, reinterpret_cast<const float*>(desc->prev_hit), desc->prev_position,
+                           desc->history_in, desc->moments_in, desc->length_in, ctx->width, ctx->height, desc->normal_cos, desc->plane_eps, desc->min_weight},
+                          desc->color, desc->albedo, desc->history_out, desc->moments_out, desc->length_out, desc->variance_out, d_inset, B.nbx, desc->color_scale,
+                          desc->albedo_min, clamp ? desc->clamp_k : 0.f, (float)(desc->max_history - 1u), run.counts()};
         const unsigned grid = (n + 255u) / 256u;
         if (clamp) PASS_LAUNCH(run, grid, 256, ta, k_tmom, true);
         else PASS_LAUNCH(run, grid, 256, ta, k_tmom, false);

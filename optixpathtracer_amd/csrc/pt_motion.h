@@ -1,7 +1,7 @@
 // pt_motion_planes (include/pt_amd.h): where each pixel's surface point was before the geometry moved — the motion plane, the previous
 // point and the previous normal that let pt_temporal_accumulate follow a moving mesh — in ONE kernel, stateless, every plane the caller's.
 #pragma once
-#include "pt_temporal.h"
+#include "pt_pass_dev.h"
 
 // One thread per entry of the frame's pixel list, 256 threads per block, no LDS, no scratch: the shape of k_temporal.  A pixel reads its
 // hit record (two 16-byte loads), three indices of the context's index array and nine floats of the caller's previous vertices; in
@@ -32,11 +32,10 @@ __global__ void __launch_bounds__(256) k_motion(MotionArgs a, ViewParams vp) {
     bool is_hit = false, is_stale = false;
     if (i < a.n) {
         const uint32_t xy = a.pixels[i];
-        const uint32_t X = xy & 0xffffu, Y = xy >> 16;
-        const size_t p = (size_t)Y * (size_t)a.width + X;
+        const size_t p = (size_t)pass_y(xy) * (size_t)a.width + pass_x(xy);
         const float4 ha = tp_load4(a.hit + 8 * p), hb = tp_load4(a.hit + 8 * p + 4); // t, u, v, prim | mesh, ng.xyz
         const int32_t prim = __float_as_int(ha.w);
-        const bool miss = prim < 0;
+        const bool miss = hit_is_miss(ha.w);
         is_hit = !miss && (uint32_t)prim < a.ntri;
         is_stale = !miss && !is_hit;
         v3 Q = mk3(0.0f);
@@ -60,17 +59,13 @@ __global__ void __launch_bounds__(256) k_motion(MotionArgs a, ViewParams vp) {
         if (a.motion) {
             float mx = __uint_as_float(0x7fc00000u), my = mx;
             if (!is_stale) {
-                // the pixel's camera: its view's (found by block, as k_gbuffer<true> finds it) or the frame's
-                uint32_t x = X, y = Y, ci = 0u;
-                int wr = a.width, hr = a.height;
+                // the pixel's camera: its view's or the frame's
+                const PassPixel px = pass_pixel<VIEWS>(vp, xy, a.width, a.height);
+                const uint32_t x = px.X - (uint32_t)px.x0, y = px.Y - (uint32_t)px.y0, ci = px.view;
+                const int wr = px.wr, hr = px.hr;
                 v3 eU = a.U, eV = a.V, eW = a.W;
                 if (VIEWS) {
-                    ci = vp.vblock[(Y >> 3) * vp.nbx + (X >> 3)]; // the list holds view pixels only: never 0xffff
-                    const pt_view vw = vp.views[ci];
-                    x = X - (uint32_t)vw.x;
-                    y = Y - (uint32_t)vw.y;
-                    wr = vw.width;
-                    hr = vw.height;
+                    const pt_view& vw = vp.views[ci];
                     eU = mk3(vw.U[0], vw.U[1], vw.U[2]);
                     eV = mk3(vw.V[0], vw.V[1], vw.V[2]);
                     eW = mk3(vw.W[0], vw.W[1], vw.W[2]);
@@ -96,10 +91,6 @@ __global__ void __launch_bounds__(256) k_motion(MotionArgs a, ViewParams vp) {
             gb_store2(a.motion + 2 * p, make_float2(mx, my));
         }
     }
-    const unsigned long long hm = __ballot(is_hit), sm = __ballot(is_stale);
-    if ((threadIdx.x & 63u) == 0u) {
-        if (hm) atomicAdd(a.counts, (unsigned long long)__popcll(hm));
-        if (sm) atomicAdd(a.counts + 1, (unsigned long long)__popcll(sm));
-    }
+    pass_tally(a.counts, {is_hit, is_stale});
 #endif
 }

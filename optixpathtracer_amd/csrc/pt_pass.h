@@ -1,5 +1,5 @@
 // pt_pass.h — what the image-space passes (pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_motion_planes,
-// pt_temporal_moments, pt_modulate_planes) share on the host: the plane table and its checks, the previous cameras, the block table of a
+// pt_temporal_moments, pt_modulate_planes, ...) share on the host (pt_pass_dev.h: on the device): the plane table and its checks, the previous cameras, the block table of a
 // call, and the run object that owns a call's temporaries and its timed span.  Host only.  Included by pt_lib.hip behind pt_api.hip: the
 // second part uses that file's context and file-local helpers; the first part needs no HIP header (tests/test_pass_planes.py compiles it
 // with a host compiler alone).
@@ -36,6 +36,8 @@ static inline bool pass_planes_overlap(const PassPlane* pl, int n, int* first, i
 }
 
 #ifdef __HIPCC__
+#include "pt_pass_dev.h" // PASS_SLOTS: the device side of the passes, and the layout of a tally in slots
+
 // Every plane that is given or required is a device pointer of the context's device with `bytes` behind it; then the overlap test.
 // fn: the entry point's name, as it stands in front of the colon of its messages.
 static int pass_planes_check(pt_ctx* ctx, const char* fn, const PassPlane* pl, int n, int eq_a = -1, int eq_b = -1) {
@@ -86,6 +88,7 @@ static ViewParams pass_views(const pt_ctx* ctx) {
 // front of the timed span), select, the pass's launches over pixels[0, n), close.  The timed span runs from select's event to close's:
 // uploads and clears are outside it, the compaction of a mask is inside it.  Once open has enqueued something, the stream is waited for
 // before the temporaries are freed on every path, a failed one included.
+#define PASS_SLOT_BYTES (PASS_SLOTS * 8 * sizeof(unsigned long long))
 namespace {
 struct PassRun {
     pt_ctx* ctx = nullptr;
@@ -137,6 +140,17 @@ struct PassRun {
         CK(es);
         CK(hipEventElapsedTime(&ms, ev0, ev1));
         return PT_OK;
+    }
+    // close for a pass whose counters are PASS_SLOTS slots of 8 words at the front of d_counters (PASS_SLOT_BYTES; pass_slot, pt_pass_dev.h):
+    // sum[j] becomes word j of every slot, added up
+    int close_slots(unsigned long long* sum, int words) {
+        unsigned long long h_slots[PASS_SLOTS * 8] = {};
+        const int rc = close(hipSuccess, h_slots, sizeof(h_slots));
+        for (int j = 0; j < words; ++j) {
+            sum[j] = 0;
+            for (uint32_t k = 0; k < PASS_SLOTS; ++k) sum[j] += h_slots[8 * k + j];
+        }
+        return rc;
     }
     ~PassRun() {
         if (live) hipStreamSynchronize(ctx->stream); // nothing of the call may still run when its temporaries go

@@ -2,7 +2,7 @@
 // shade kernel's first hit would write to PT_BUF_ALBEDO for that barycentric point, for every pixel of the call and under this frame's
 // camera, whether the render visited the pixel or not.  ONE kernel, stateless, every plane the caller's.
 #pragma once
-#include "pt_temporal.h"
+#include "pt_pass_dev.h"
 
 // One thread per entry of the frame's pixel list, 256 threads per block, no scratch: the shape of k_motion.  Loads go cheapest first and
 // each one decides whether the next is needed: the first 16 bytes of the hit record (t, u, v, prim; the second half — mesh, ng — is
@@ -30,12 +30,8 @@ struct SurfaceArgs {
     const float* prim_uv;       // [triangles][6], the caller's table (TEX only)
     const DevTex* textures;     // (TEX only)
     float *albedo, *texcoord;   // the planes, null = not asked for
-    unsigned long long* counts; // [SURFACE_SLOTS][8]: [0] hits, [1] stale, [2] textured of a slot; zero at launch; the host adds the slots up
+    unsigned long long* counts; // [PASS_SLOTS][8]: [0] hits, [1] stale, [2] textured of a slot (pass_slot); zero at launch
 };
-// One 64-bit atomic per wave and non-zero count, into the wave's slot of 64 (64 bytes apart: QuerySlot's layout, pt_kernels.h).  Into ONE
-// word the 32 400 waves of a 1080p frame serialise at about 10 ns an atomic: 0.32 ms per counter whatever the kernel reads, measured —
-// which is all of k_motion's time there (profiles/surface.md).
-#define SURFACE_SLOTS 64u
 
 template <bool TEX>
 __global__ void __launch_bounds__(256) k_surface(SurfaceArgs a) {
@@ -49,11 +45,10 @@ __global__ void __launch_bounds__(256) k_surface(SurfaceArgs a) {
     bool is_hit = false, is_stale = false, is_tex = false;
     if (i < a.n) {
         const uint32_t xy = a.pixels[i];
-        const uint32_t X = xy & 0xffffu, Y = xy >> 16;
-        const size_t p = (size_t)Y * (size_t)a.width + X;
+        const size_t p = (size_t)pass_y(xy) * (size_t)a.width + pass_x(xy);
         const float4 ha = tp_load4(a.hit + 8 * p); // t, u, v, prim
         const int32_t prim = __float_as_int(ha.w);
-        const bool miss = prim < 0;
+        const bool miss = hit_is_miss(ha.w);
         is_hit = !miss && (uint32_t)prim < a.ntri;
         is_stale = !miss && !is_hit;
         float4 alb = make_float4(0.f, 0.f, 0.f, 1.0f);
@@ -81,12 +76,6 @@ __global__ void __launch_bounds__(256) k_surface(SurfaceArgs a) {
         if (a.albedo) gb_store4(a.albedo + 4 * p, alb);
         if (a.texcoord) gb_store2(a.texcoord + 2 * p, tc);
     }
-    const unsigned long long hm = __ballot(is_hit), sm = __ballot(is_stale), tm = __ballot(is_tex);
-    if ((threadIdx.x & 63u) == 0u) {
-        unsigned long long* slot = a.counts + 8u * ((blockIdx.x * 4u + (threadIdx.x >> 6)) & (SURFACE_SLOTS - 1u));
-        if (hm) atomicAdd(slot, (unsigned long long)__popcll(hm));
-        if (sm) atomicAdd(slot + 1, (unsigned long long)__popcll(sm));
-        if (TEX && tm) atomicAdd(slot + 2, (unsigned long long)__popcll(tm));
-    }
+    pass_tally(pass_slot(a.counts), {is_hit, is_stale, is_tex}); // is_tex: never without TEX
 #endif
 }

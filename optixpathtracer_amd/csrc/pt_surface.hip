@@ -56,7 +56,7 @@ extern "C" int pt_surface_planes(pt_ctx* ctx, const pt_surface_desc* desc, pt_su
     if (rc) return rc;
     if (tex && !desc->prim_texcoords) return fail(ctx, PT_ERR_INVALID, (fn + "the scene has a textured mesh: prim_texcoords is required (pt_copy_texcoords_device)").c_str());
     PassRun run;
-    rc = run.open(ctx, "pt_surface_planes", SURFACE_SLOTS * 8 * sizeof(unsigned long long)); // per slot: hits, stale, textured
+    rc = run.open(ctx, "pt_surface_planes", PASS_SLOT_BYTES); // per slot: hits, stale, textured
     if (rc) return rc;
     rc = run.select(desc->block_mask);
     if (rc) return rc;
@@ -69,13 +69,10 @@ extern "C" int pt_surface_planes(pt_ctx* ctx, const pt_surface_desc* desc, pt_su
         if (tex) hipLaunchKernelGGL(k_surface<true>, dim3(grid), dim3(256), 0, ctx->stream, sa);
         else hipLaunchKernelGGL(k_surface<false>, dim3(grid), dim3(256), 0, ctx->stream, sa);
     }
-    unsigned long long h_slots[SURFACE_SLOTS * 8] = {};
-    rc = run.close(hipSuccess, h_slots, sizeof(h_slots));
+    unsigned long long sum[3];
+    rc = run.close_slots(sum, 3);
     if (rc) return rc;
     if (stats) {
-        unsigned long long sum[3] = {0, 0, 0};
-        for (uint32_t k = 0; k < SURFACE_SLOTS; ++k)
-            for (int j = 0; j < 3; ++j) sum[j] += h_slots[8 * k + j];
         stats->pixels = n;
         stats->hits = sum[0];
         stats->stale = sum[1];

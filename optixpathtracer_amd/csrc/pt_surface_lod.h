@@ -33,7 +33,7 @@ static inline uint64_t lod_layout(const int* wh, uint32_t n, uint32_t* dims) {
 }
 
 #ifdef __HIPCC__
-#include "pt_temporal.h"
+#include "pt_pass_dev.h"
 
 // ------------------------------------------------------------------ the pyramid
 // One thread per texel of the level written, 256 per block, one launch per level: a kernel boundary is the only ordering needed.  Texel
@@ -97,11 +97,8 @@ struct SurfaceLodArgs {
     v3 eye, U, V, W;            // the frame's camera (unused with views)
     float scale;                // footprint_scale
     float *albedo, *texcoord, *footprint, *lod; // the planes, null = not asked for
-    unsigned long long* counts; // [SURFACE_LOD_SLOTS][8]: [0] hits, [1] stale, [2] textured, [3] minified of a slot; zero at launch
+    unsigned long long* counts; // [PASS_SLOTS][8]: [0] hits, [1] stale, [2] textured, [3] minified of a slot (pass_slot); zero at launch
 };
-// One 64-bit atomic per wave and non-zero count, into the wave's slot of 64 (64 bytes apart), as k_surface: into one word the waves of a
-// 1080p frame serialise (0.32 ms per counter, profiles/surface.md).
-#define SURFACE_LOD_SLOTS 64u
 
 // the header's tex2D on level k >= 1: W x H float4 texels, row-major
 PT_DEV float4 lod_tex2d(const float4* T, int W, int H, float s, float t) {
@@ -145,11 +142,10 @@ __global__ void __launch_bounds__(256) k_surface_lod(SurfaceLodArgs a, ViewParam
     bool is_hit = false, is_stale = false, is_tex = false, is_min = false;
     if (i < a.n) {
         const uint32_t xy = a.pixels[i];
-        const uint32_t X = xy & 0xffffu, Y = xy >> 16;
-        const size_t p = (size_t)Y * (size_t)a.width + X;
+        const size_t p = (size_t)pass_y(xy) * (size_t)a.width + pass_x(xy);
         const float4 ha = tp_load4(a.hit + 8 * p); // t, u, v, prim
         const int32_t prim = __float_as_int(ha.w);
-        const bool miss = prim < 0;
+        const bool miss = hit_is_miss(ha.w);
         is_hit = !miss && (uint32_t)prim < a.ntri;
         is_stale = !miss && !is_hit;
         float4 alb = make_float4(0.f, 0.f, 0.f, 1.0f), fp = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -169,16 +165,13 @@ __global__ void __launch_bounds__(256) k_surface_lod(SurfaceLodArgs a, ViewParam
                 const float s = ((w0 * c[0]) + (u * c[2])) + (v * c[4]);
                 const float t = ((w0 * c[1]) + (u * c[3])) + (v * c[5]);
                 tc = make_float2(s, t);
-                // the pixel's camera: its view's (found by block, as k_motion finds it) or the frame's
-                uint32_t x = X, y = Y;
-                int wr = a.width, hr = a.height;
+                // the pixel's camera: its view's or the frame's.  Looked up here, where the few pixels that need it are
+                const PassPixel px = pass_pixel<VIEWS>(vp, xy, a.width, a.height);
+                const uint32_t x = px.X - (uint32_t)px.x0, y = px.Y - (uint32_t)px.y0;
+                const int wr = px.wr, hr = px.hr;
                 v3 eye = a.eye, eU = a.U, eV = a.V, eW = a.W;
                 if (VIEWS) {
-                    const pt_view vw = vp.views[vp.vblock[(Y >> 3) * vp.nbx + (X >> 3)]]; // the list holds view pixels only: never 0xffff
-                    x = X - (uint32_t)vw.x;
-                    y = Y - (uint32_t)vw.y;
-                    wr = vw.width;
-                    hr = vw.height;
+                    const pt_view& vw = vp.views[px.view];
                     eye = mk3(vw.eye[0], vw.eye[1], vw.eye[2]);
                     eU = mk3(vw.U[0], vw.U[1], vw.U[2]);
                     eV = mk3(vw.V[0], vw.V[1], vw.V[2]);
@@ -236,14 +229,7 @@ __global__ void __launch_bounds__(256) k_surface_lod(SurfaceLodArgs a, ViewParam
         if (a.footprint) gb_store4(a.footprint + 4 * p, fp);
         if (a.lod) a.lod[p] = lod;
     }
-    const unsigned long long hm = __ballot(is_hit), sm = __ballot(is_stale), tm = __ballot(is_tex), mm = __ballot(is_min);
-    if ((threadIdx.x & 63u) == 0u) {
-        unsigned long long* slot = a.counts + 8u * ((blockIdx.x * 4u + (threadIdx.x >> 6)) & (SURFACE_LOD_SLOTS - 1u));
-        if (hm) atomicAdd(slot, (unsigned long long)__popcll(hm));
-        if (sm) atomicAdd(slot + 1, (unsigned long long)__popcll(sm));
-        if (TEX && tm) atomicAdd(slot + 2, (unsigned long long)__popcll(tm));
-        if (TEX && mm) atomicAdd(slot + 3, (unsigned long long)__popcll(mm));
-    }
+    pass_tally(pass_slot(a.counts), {is_hit, is_stale, is_tex, is_min}); // is_tex, is_min: never without TEX
 #endif
 }
 #endif // __HIPCC__

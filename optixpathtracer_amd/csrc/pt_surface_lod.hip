@@ -123,7 +123,7 @@ extern "C" int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* des
             }
         }
     }
-    const size_t slot_bytes = SURFACE_LOD_SLOTS * 8 * sizeof(unsigned long long); // per slot: hits, stale, textured, minified
+    const size_t slot_bytes = PASS_SLOT_BYTES; // per slot: hits, stale, textured, minified
     PassRun run;
     rc = run.open(ctx, "pt_surface_lod_planes", slot_bytes + sizeof(uint32_t) * first.size());
     if (rc) return rc;
@@ -144,13 +144,10 @@ extern "C" int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* des
         if (tex) PASS_LAUNCH(run, grid, 256, sa, k_surface_lod, true);
         else PASS_LAUNCH(run, grid, 256, sa, k_surface_lod, false);
     }
-    unsigned long long h_slots[SURFACE_LOD_SLOTS * 8] = {};
-    rc = run.close(hipSuccess, h_slots, sizeof(h_slots));
+    unsigned long long sum[4];
+    rc = run.close_slots(sum, 4);
     if (rc) return rc;
     if (stats) {
-        unsigned long long sum[4] = {0, 0, 0, 0};
-        for (uint32_t k = 0; k < SURFACE_LOD_SLOTS; ++k)
-            for (int j = 0; j < 4; ++j) sum[j] += h_slots[8 * k + j];
         stats->pixels = n;
         stats->hits = sum[0];
         stats->stale = sum[1];

@@ -36,9 +36,10 @@ extern "C" int pt_temporal_accumulate(pt_ctx* ctx, const pt_temporal_desc* desc,
     if (rc) return rc;
     const uint32_t n = run.n;
     if (n != 0) {
-        const TemporalArgs ta{run.pixels, n, ctx->width, ctx->height, desc->color, desc->motion, reinterpret_cast<const float*>(desc->hit), desc->position,
-                              reinterpret_cast<const float*>(desc->prev_hit), desc->prev_position, desc->history_in, desc->length_in, desc->history_out, desc->length_out,
-                              desc->frame_rgba8, desc->copy_out, desc->color_scale, desc->normal_cos, desc->plane_eps, desc->min_weight,
+        const TemporalArgs ta{run.pixels, n,
+                              {desc->motion, reinterpret_cast<const float*>(desc->hit), desc->position, reinterpret_cast<const float*>(desc->prev_hit), desc->prev_position,
+                               desc->history_in, nullptr, desc->length_in, ctx->width, ctx->height, desc->normal_cos, desc->plane_eps, desc->min_weight},
+                              desc->color, desc->history_out, desc->length_out, desc->frame_rgba8, desc->copy_out, desc->color_scale,
                               (float)(desc->max_history - 1u), desc->flags & (uint32_t)PT_TEMPORAL_CLEAR_COLOR, run.counts()};
         const unsigned grid = (n + 255u) / 256u;
         PASS_LAUNCH(run, grid, 256, ta, k_temporal);

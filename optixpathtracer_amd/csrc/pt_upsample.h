@@ -2,7 +2,7 @@
 // guidance of both G-buffers — ONE kernel, stateless, every plane the caller's.  The "same surface" tests are those of k_temporal and
 // k_filter_pass (mesh, normal, plane distance), so the chain keeps its single notion of a surface across the change of resolution.
 #pragma once
-#include "pt_temporal.h"
+#include "pt_pass_dev.h"
 
 // One thread per entry of the frame's pixel list, 256 per block, as k_filter_prepare.  The list is in 8x8-block order, so a wave is one
 // full-resolution block and its taps fall into a window of at most (8 / s + 3)^2 low-resolution pixels: the reuse between the lanes of a wave
@@ -24,22 +24,17 @@ struct UpsampleArgs {
     float* out;
     float* weight_out;          // or null
     float normal_cos, plane_eps;
-    unsigned long long* counts; // [UPSAMPLE_SLOTS][8]: [0] hits, [1] full, [2] rescued, [3] orphans of a slot; zero at launch
+    unsigned long long* counts; // [PASS_SLOTS][8]: [0] hits, [1] full, [2] rescued, [3] orphans of a slot (pass_slot); zero at launch
 };
-// One 64-bit atomic per wave and non-zero count, into the wave's slot of 64 (64 bytes apart), as k_surface_lod.
-#define UPSAMPLE_SLOTS 64u
 
 // a / s for 0 <= a < 65536 and s in 2..4 without a division: 3 * 43691 = 2^17 + 1, so (a * 43691) >> 17 = floor(a / 3 + a / (3 * 2^17)),
 // and the second term stays below 1/6 while the fraction of a / 3 is at most 2/3
 PT_DEV int up_div(int a, int s) { return s == 2 ? a >> 1 : s == 4 ? a >> 2 : (int)(((uint32_t)a * 43691u) >> 17); }
 
-// the pixel's side of the tap tests, and its low-resolution rectangle [lx0, lx1) x [ly0, ly1)
+// the pixel's low-resolution rectangle [lx0, lx1) x [ly0, ly1), and its side of the tap tests
 struct UpsamplePixel {
     int lx0, ly0, lx1, ly1;
-    bool miss;
-    int mesh;
-    v3 ng, P;
-    float plane_max;
+    SurfaceKey key;
 };
 
 // One axis of the header: the low-res pixel that holds the coordinate (c), the first tap (i) and the weight of the second tap (f).
@@ -62,14 +57,12 @@ PT_DEV void up_axis(int X, int x0, int s, int& c, int& i, float& f) {
 PT_DEV bool up_counts(const UpsampleArgs& a, const UpsamplePixel& p, int qx, int qy, float4& c) {
     if (qx < p.lx0 || qx >= p.lx1 || qy < p.ly0 || qy >= p.ly1) return false;
     const size_t q = (size_t)qy * (size_t)a.lo_width + (size_t)qx;
-    if (p.miss) {
-        if (__float_as_int(a.lo_hit[8 * q + 3]) >= 0) return false;
+    if (p.key.miss) {
+        if (!hit_is_miss(a.lo_hit[8 * q + 3])) return false;
     } else {
-        const float4 qb = tp_load4(a.lo_hit + 8 * q + 4);
-        if (__float_as_int(qb.x) != p.mesh || !(dot3(p.ng, mk3(qb.y, qb.z, qb.w)) >= a.normal_cos)) return false;
-        if (__float_as_int(a.lo_hit[8 * q + 3]) < 0) return false;
-        const float4 Q = tp_load4(a.lo_position + 4 * q);
-        if (!(fabsf(dot3(p.ng, mk3(Q.x - p.P.x, Q.y - p.P.y, Q.z - p.P.z))) <= p.plane_max)) return false;
+        if (!same_facet(p.key, a.lo_hit, q, a.normal_cos)) return false;
+        if (hit_is_miss(a.lo_hit[8 * q + 3])) return false;
+        if (!same_plane(p.key, a.lo_position, q)) return false;
     }
     c = tp_load4(a.lo_color + 4 * q);
     return tp_finite(c.x) && tp_finite(c.y) && tp_finite(c.z);
@@ -81,33 +74,21 @@ __global__ void __launch_bounds__(256) k_upsample(UpsampleArgs a, ViewParams vp)
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     bool is_hit = false, is_full = false, is_rescued = false, is_orphan = false;
     if (idx < a.n) {
-        const uint32_t xy = a.pixels[idx];
-        const int X = (int)(xy & 0xffffu), Y = (int)(xy >> 16);
-        int x0 = 0, y0 = 0, x1 = a.width, y1 = a.height;
-        if (VIEWS) {
-            const uint32_t vi = vp.vblock[(uint32_t)(Y >> 3) * vp.nbx + (uint32_t)(X >> 3)]; // the list holds view pixels only: never 0xffff
-            x0 = vp.views[vi].x;
-            y0 = vp.views[vi].y;
-            x1 = x0 + vp.views[vi].width;
-            y1 = y0 + vp.views[vi].height;
-        }
+        const PassPixel px = pass_pixel<VIEWS>(vp, a.pixels[idx], a.width, a.height);
+        const int X = (int)px.X, Y = (int)px.Y, x0 = px.x0, y0 = px.y0;
         const int s = a.scale;
         UpsamplePixel p;
         p.lx0 = up_div(x0, s);
         p.ly0 = up_div(y0, s);
-        p.lx1 = up_div(x1, s);
-        p.ly1 = up_div(y1, s);
+        p.lx1 = up_div(x0 + px.wr, s);
+        p.ly1 = up_div(y0 + px.hr, s);
         const size_t pi = (size_t)Y * (size_t)a.width + (size_t)X;
         const float4 ha = tp_load4(a.hit + 8 * pi), hb = tp_load4(a.hit + 8 * pi + 4); // t, u, v, prim | mesh, ng.xyz
-        p.miss = __float_as_int(ha.w) < 0;
-        p.mesh = __float_as_int(hb.x);
-        p.ng = mk3(hb.y, hb.z, hb.w);
-        p.P = mk3(0.0f);
-        p.plane_max = a.plane_eps * ha.x;
-        is_hit = !p.miss;
-        if (is_hit) {
+        is_hit = !hit_is_miss(ha.w);
+        p.key = surface_key(!is_hit, ha.x, hb, make_float4(0.0f, 0.0f, 0.0f, 0.0f), a.plane_eps);
+        if (is_hit) { // the position only for a hit, and its three words only
             const float4 P = tp_load4(a.position + 4 * pi);
-            p.P = mk3(P.x, P.y, P.z);
+            p.key.P = mk3(P.x, P.y, P.z);
         }
         int cx, cy, i, j;
         float fx, fy;
@@ -168,13 +149,6 @@ __global__ void __launch_bounds__(256) k_upsample(UpsampleArgs a, ViewParams vp)
         gb_store4(a.out + 4 * pi, o);
         if (a.weight_out) a.weight_out[pi] = wo;
     }
-    const unsigned long long hm = __ballot(is_hit), fm = __ballot(is_full), rm = __ballot(is_rescued), om = __ballot(is_orphan);
-    if ((threadIdx.x & 63u) == 0u) {
-        unsigned long long* slot = a.counts + 8u * ((blockIdx.x * 4u + (threadIdx.x >> 6)) & (UPSAMPLE_SLOTS - 1u));
-        if (hm) atomicAdd(slot, (unsigned long long)__popcll(hm));
-        if (fm) atomicAdd(slot + 1, (unsigned long long)__popcll(fm));
-        if (rm) atomicAdd(slot + 2, (unsigned long long)__popcll(rm));
-        if (om) atomicAdd(slot + 3, (unsigned long long)__popcll(om));
-    }
+    pass_tally(pass_slot(a.counts), {is_hit, is_full, is_rescued, is_orphan});
 #endif
 }

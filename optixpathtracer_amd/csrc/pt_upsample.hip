@@ -32,9 +32,8 @@ extern "C" int pt_upsample_planes(pt_ctx* ctx, const pt_upsample_desc* desc, pt_
                                  {"weight_out", desc->weight_out, npix * 4, false, true}};
     int rc = pass_planes_check(ctx, "pt_upsample_planes", planes, 7);
     if (rc) return rc;
-    const size_t slot_bytes = UPSAMPLE_SLOTS * 8 * sizeof(unsigned long long); // per slot: hits, full, rescued, orphans
     PassRun run;
-    rc = run.open(ctx, "pt_upsample_planes", slot_bytes);
+    rc = run.open(ctx, "pt_upsample_planes", PASS_SLOT_BYTES); // per slot: hits, full, rescued, orphans
     if (rc) return rc;
     rc = run.select(desc->block_mask);
     if (rc) return rc;
@@ -45,13 +44,10 @@ extern "C" int pt_upsample_planes(pt_ctx* ctx, const pt_upsample_desc* desc, pt_
                               desc->plane_eps, run.counts()};
         PASS_LAUNCH(run, (n + 255u) / 256u, 256, ua, k_upsample);
     }
-    unsigned long long h_slots[UPSAMPLE_SLOTS * 8] = {};
-    rc = run.close(hipSuccess, h_slots, sizeof(h_slots));
+    unsigned long long sum[4];
+    rc = run.close_slots(sum, 4);
     if (rc) return rc;
     if (stats) {
-        unsigned long long sum[4] = {0, 0, 0, 0};
-        for (uint32_t k = 0; k < UPSAMPLE_SLOTS; ++k)
-            for (int j = 0; j < 4; ++j) sum[j] += h_slots[8 * k + j];
         stats->pixels = n;
         stats->hits = sum[0];
         stats->full = sum[1];
