@@ -29,6 +29,7 @@ static thread_local std::string g_create_error;
 
 struct LaunchCounts {
     uint32_t trace = 0, shadow = 0, shade = 0, fused = 0;
+    uint32_t carry = 0; // k_shade launches that carried the paths' sums (PT_CARRY_SUMS)
 };
 
 // A host thread that enqueues on behalf of a context (pt_multi: one per rank; a synchronous frame: one per pixel chunk).  A frame is 21
@@ -188,8 +189,10 @@ struct pt_ctx {
             float4 *rayO = nullptr, *rayD = nullptr, *thr = nullptr;
             uint4* rf = nullptr;
             float2* hit = nullptr;
+            float4 *c0 = nullptr, *c1 = nullptr; // carried sums (PathState::c0)
         } X[2];
         float4 *shO = nullptr, *shD = nullptr, *shPend = nullptr;
+        uint32_t* svis = nullptr; // carried sums: the visibility word of every shadow-queue position
         uint32_t *queueA = nullptr, *queueB = nullptr, *squeue = nullptr;
         uint32_t* squeueB = nullptr; // asynchronous shadow rays: one shadow queue per bounce
         uint32_t* ovf3 = nullptr;
@@ -238,6 +241,7 @@ struct pt_ctx {
     // the bounce loop of a small frame as ONE persistent kernel (pt_fused.h): PT_FUSED=0 never / 1 (default) synchronous frames of at most
     // fused_max_paths paths (PT_FUSED_MAX_PATHS), as one pass / 2 every pass the kernel covers, chunked as usual (tests); fused_cap: window entries per wave (PT_FUSED_CAP, a multiple of 64; default: 128 or 64 by frame size)
     int fused = 1;
+    bool carry_sums = true; // PT_CARRY_SUMS: the launch chain carries the paths' sums with their queue entries (where eligible: carry_eligible)
     uint64_t fused_max_paths = 2500000;
     uint32_t fused_cap = 0; // 0: by frame size (enqueue_chunk)
     float fused_max_cost = 22.f; // PT_FUSED_MAX_COST: fused_one_pass only for trees whose calibration rays cost at most this many steps (see sched_choose)
@@ -592,6 +596,7 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
         if (const char* e = getenv("PT_CAM_GRID")) ctx->cam_grid = atoi(e);
         if (const char* e = getenv("PT_ENQUEUE_THREADS")) ctx->enqueue_threads = atoi(e);
         if (const char* e = getenv("PT_FUSED")) ctx->fused = atoi(e);
+        if (const char* e = getenv("PT_CARRY_SUMS")) ctx->carry_sums = atoi(e) != 0;
         if (const char* e = getenv("PT_FUSED_MAX_PATHS")) ctx->fused_max_paths = strtoull(e, nullptr, 10);
         if (const char* e = getenv("PT_FUSED_GRID")) ctx->fused_grid = atoi(e);
         if (const char* e = getenv("PT_FUSED_MAX_COST")) ctx->fused_max_cost = (float)atof(e);
@@ -634,8 +639,8 @@ static void free_path_state(pt_ctx* ctx) {
         if (b.stream2) hipStreamSynchronize(b.stream2);
         if (b.stream3) hipStreamSynchronize(b.stream3);
         PathState& s = b.st;
-        for (auto& x : b.X) { dfree(x.rayO); dfree(x.rayD); dfree(x.thr); dfree(x.rf); dfree(x.hit); }
-        dfree(b.shO); dfree(b.shD); dfree(b.shPend); dfree(s.pflags);
+        for (auto& x : b.X) { dfree(x.rayO); dfree(x.rayD); dfree(x.thr); dfree(x.rf); dfree(x.hit); dfree(x.c0); dfree(x.c1); }
+        dfree(b.shO); dfree(b.shD); dfree(b.shPend); dfree(b.svis); dfree(s.pflags);
         dfree(s.direct); dfree(s.indirect); dfree(s.alpha); dfree(s.nrm); dfree(s.alb); dfree(s.prdN); dfree(s.prdA);
         dfree(b.queueA); dfree(b.queueB); dfree(b.squeue); dfree(b.counters); dfree(b.ovf); dfree(b.ovf2);
         dfree(b.squeueB); dfree(b.ovf3); dfree(s.sO); dfree(s.sD); dfree(s.pendB); dfree(s.vis);
@@ -1072,6 +1077,10 @@ static int assign_streams(pt_ctx* ctx, int nsets) {
 // for — so an application that alternates schedules (a fused-size synchronous frame = one set holding the whole frame; a foveated or
 // pipelined frame = three sets) re-allocates at most once per dimension and never again (the one-set / three-set switch used
 // to drain, free and re-allocate every buffer on every alternation).  pt_stats.path_state_allocs counts the (re-)allocations.
+// Carried sums (PT_CARRY_SUMS): scenes without shadow catchers; the chunks of a frame take them when its shadow rays are
+// placed in the unified launch (enqueue_chunk).  Decided by what pt_create saw, so the arrays exist whenever a frame may want them.
+static bool carry_eligible(const pt_ctx* ctx) { return ctx->carry_sums && !ctx->has_catcher; }
+
 static int ensure_path_state(pt_ctx* ctx, int nsets, uint32_t cap, uint32_t pix_cap) {
     // one queue-counter slot per bounce plus the "would continue" slot; shadow-catcher scenes get two more for the extra
     // iterations of paths that passed through catcher surfaces (enqueue_chunk)
@@ -1102,6 +1111,10 @@ static int ensure_path_state(pt_ctx* ctx, int nsets, uint32_t cap, uint32_t pix_
         PathState& s = b.st;
         for (auto& x : b.X) { CK(dalloc(&x.rayO, qsize)); CK(dalloc(&x.rayD, qsize)); CK(dalloc(&x.thr, qsize)); CK(dalloc(&x.rf, qsize)); CK(dalloc(&x.hit, qsize)); }
         CK(dalloc(&b.shO, qsize)); CK(dalloc(&b.shD, qsize)); CK(dalloc(&b.shPend, qsize)); CK(dalloc(&s.pflags, cap));
+        if (carry_eligible(ctx)) {
+            for (auto& x : b.X) { CK(dalloc(&x.c0, qsize)); CK(dalloc(&x.c1, qsize)); }
+            CK(dalloc(&b.svis, qsize));
+        }
         CK(dalloc(&s.direct, cap)); CK(dalloc(&s.indirect, cap)); CK(dalloc(&s.nrm, cap)); CK(dalloc(&s.alb, cap));
         if (ctx->has_catcher) { CK(dalloc(&s.alpha, cap)); CK(dalloc(&s.prdN, cap)); CK(dalloc(&s.prdA, cap)); }
         CK(dalloc(&b.queueA, qsize)); CK(dalloc(&b.queueB, qsize)); CK(dalloc(&b.squeue, qsize));
@@ -1175,12 +1188,15 @@ static PathState stream_view(const pt_ctx::BatchSet& bs, int k) {
     PathState s = bs.st;
     s.rayO = bs.X[k].rayO; s.rayD = bs.X[k].rayD; s.thr = bs.X[k].thr; s.rf = bs.X[k].rf; s.hit = bs.X[k].hit;
     s.shO = bs.shO; s.shD = bs.shD; s.shPend = bs.shPend;
+    s.c0 = bs.X[k].c0; s.c1 = bs.X[k].c1; s.svis = bs.svis;
     return s;
 }
 template <int MODE>
-static void launch_shade(const pt_ctx* ctx, hipStream_t s, const PathState& st, const ShadeParams& sp) {
+static void launch_shade(const pt_ctx* ctx, hipStream_t s, const PathState& st, const ShadeParams& sp, bool carry) {
     const unsigned lds = (unsigned)shade_lds_bytes(sp.probe);
-    if (ctx->has_catcher)
+    if (carry)
+        hipLaunchKernelGGL(k_shade_carry<MODE>, dim3(GRID), dim3(256), lds, s, st, sp);
+    else if (ctx->has_catcher)
         hipLaunchKernelGGL((k_shade<MODE, true>), dim3(GRID), dim3(256), lds, s, st, sp);
     else
         hipLaunchKernelGGL((k_shade<MODE, false>), dim3(GRID), dim3(256), lds, s, st, sp);
@@ -1281,7 +1297,8 @@ struct ChainPass {
     // (the hit records index the leaf triangles of the structure that was traversed)
     ShadeParams shade_params(QView q, QView next, QView shadow, const pt_ctx::BatchSet::StreamBuf* out, int aov, int first) const {
         ShadeParams sp{ctx->bvh.tris8, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin, q, next, shadow,
-                       out ? out->rayO : nullptr, out ? out->rayD : nullptr, out ? out->thr : nullptr, out ? out->rf : nullptr, aov, first};
+                       out ? out->rayO : nullptr, out ? out->rayD : nullptr, out ? out->thr : nullptr, out ? out->rf : nullptr, aov, first,
+                       out ? out->c0 : nullptr, out ? out->c1 : nullptr, 0, 0};
         return sp;
     }
     void closest(int k, QView q, int b, unsigned long long* dbg) {
@@ -1289,12 +1306,16 @@ struct ChainPass {
         launch_closest(ctx, bs.stream, trace_args(k, q, QView{}, b, bs.ovf, dbg, 0), tgrid, pass_paths);
         ++lc.trace;
     }
-    void shade(QView next, QView shadow, int aov, int first) {
-        const ShadeParams sp = shade_params(qcur, next, shadow, &bs.X[sin ^ 1], aov, first);
+    // carry: the launch keeps the paths' sums in their queue entries (k_shade_carry); second / last: the chain's second / last launch
+    void shade(QView next, QView shadow, int aov, int first, bool carry = false, bool second = false, bool last = false) {
+        ShadeParams sp = shade_params(qcur, next, shadow, &bs.X[sin ^ 1], aov, first);
+        sp.second = second ? 1 : 0;
+        sp.last = last ? 1 : 0;
         SpanGuard g(ctx, CLS_SHADE, bs.stream);
-        if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) launch_shade<PT_BSDF_LAMBERT>(ctx, bs.stream, stream_view(bs, sin), sp);
-        else launch_shade<PT_BSDF_DISNEY>(ctx, bs.stream, stream_view(bs, sin), sp);
+        if (ctx->opt.bsdf_mode == PT_BSDF_LAMBERT) launch_shade<PT_BSDF_LAMBERT>(ctx, bs.stream, stream_view(bs, sin), sp, carry);
+        else launch_shade<PT_BSDF_DISNEY>(ctx, bs.stream, stream_view(bs, sin), sp, carry);
         ++lc.shade;
+        if (carry) ++lc.carry;
     }
     void shadow(hipStream_t s, QView q, int b, uint32_t* ovf, unsigned long long* dbg, int bounce) {
         SpanGuard g(ctx, CLS_SHADOW, s);
@@ -1332,6 +1353,8 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
     // read the ray arrays); the next shade waits for both.  Async (split_shadow = 2): from their own records on one of two side streams as
     // soon as k_shade(b) has written them, and nothing waits for them before k_resolve.
     enum { UNIFIED, SPLIT, ASYNC } const placement = ctx->cap_async ? ASYNC : ctx->opt.split_shadow == 0 ? UNIFIED : SPLIT;
+    // carried sums: the unified launches only report visibility, k_shade keeps the sums with the path (the fused loop keeps the write-back)
+    const bool carry = carry_eligible(ctx) && placement == UNIFIED && !fused && bs.svis != nullptr && qsize < (1ull << 30);
     // depth d = 0..max_depth traces in the reference (the trace at depth == max_depth can only matter
     // through a shadow-catcher pass-through or alpha; without catcher materials it is provably dead and skipped)
     // (a foveated launch of the sv / sv2 variants starts its paths at depth 1: that many fewer bounces are live)
@@ -1398,7 +1421,7 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
                     P.closest(P.sin, P.qcur, b, nullptr);
                     if (ev_shadow_done) hipStreamWaitEvent(bs.stream, ev_shadow_done, 0); // shade overwrites what shadow(b-1) reads
                 }
-                P.shade(qnext, qshadow, aov, (b == 0) ? 1 : 0);
+                P.shade(qnext, qshadow, aov, (b == 0) ? 1 : 0, carry, b == 1, b == last_bounce);
                 if (placement == SPLIT) {
                     ev_shadow_done = P.side_shadow(bs.stream2, qshadow, b, bs.ovf2, 0);
                 } else if (placement == ASYNC) {
@@ -1406,7 +1429,9 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
                     if (b < last_bounce) P.closest(P.sin ^ 1, qnext, b + 1, ctx->dbg);
                 } else if (b < last_bounce) {
                     SpanGuard g(ctx, CLS_TRACE, bs.stream);
-                    launch_trace8<TR_UNIFIED>(bs.stream, tgrid, P.trace_args(P.sin ^ 1, qnext, qshadow, b + 1, bs.ovf, ctx->dbg, 0));
+                    const Trace8Args ta = P.trace_args(P.sin ^ 1, qnext, qshadow, b + 1, bs.ovf, ctx->dbg, 0);
+                    if (carry) hipLaunchKernelGGL(k_trace8_vis, dim3(tgrid), dim3(64), 0, bs.stream, ta);
+                    else launch_trace8<TR_UNIFIED>(bs.stream, tgrid, ta);
                     ++lc.trace;
                 } else {
                     P.shadow(bs.stream, qshadow, b, bs.ovf, ctx->dbg, 0);
@@ -1732,7 +1757,7 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
             int wrc = 0;
             for (uint32_t c = 1; c < nchunks; ++c) wrc |= enqueue_worker_wait(ctx->chunk_workers[c - 1].get());
             if (wrc != 0) return fail(ctx, PT_ERR_HIP, "pt_render: a chunk's enqueue thread failed");
-            for (const LaunchCounts& l : lcs) { lc.trace += l.trace; lc.shadow += l.shadow; lc.shade += l.shade; lc.fused += l.fused; }
+            for (const LaunchCounts& l : lcs) { lc.trace += l.trace; lc.shadow += l.shadow; lc.shade += l.shade; lc.fused += l.fused; lc.carry += l.carry; }
         } else {
             uint32_t k = 0;
             for (uint32_t pix0 = 0; pix0 < owned; pix0 += Np, ++k)
@@ -1829,7 +1854,7 @@ static int render_finish(pt_ctx* ctx, int slot = 0) {
     hipEventElapsedTime(&ms, ev_begin, ev_end);
     st.render_ms = ms;
     sched_record(ctx, slot, ms);
-    st.schedule = ctx->sched_flags;
+    st.schedule = ctx->sched_flags | (lc.carry ? 0x200u : 0u);
     st.sched_chain_ms = ctx->sched.best[0];
     st.sched_fused_ms = ctx->sched.best[1];
     double cls_ms[4] = {0, 0, 0, 0};

@@ -253,7 +253,7 @@ struct Trace8Args {
 // LOCAL = true (pt_fused.h): the wave traverses a private window of the queue arrays — entries [woff, woff + ln1) of `a.queue`'s arrays and, in
 // TR_UNIFIED, the shadow entries [woff, woff + ln2) of `a.queue2`'s — on its own: no sub-queue prefix, no chunk counter, every ray taken by
 // this wave (its spare lanes steal from the first iteration it has fewer rays than lanes).  Spill stack and fault word are the launch's.
-template <int MODE, bool LOCAL>
+template <int MODE, bool LOCAL, bool CARRY = false>
 PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t nw, const uint32_t ln1, const uint32_t ln2, const uint32_t woff) {
     __shared__ uint32_t s_stack[PT8_LDS_DEPTH * 2 * 64];
     __shared__ uint32_t s_prefix[PT_NSUB + 1];
@@ -359,6 +359,15 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     auto write_result = [&](float rbest, int32_t rprim) {
         if (MODE == TR_SHADOW_APPLY || (MODE == TR_UNIFIED && shadow_lane)) {
             const bool occluded = rprim != 0;
+#ifdef PT_ABL_NO_SHADOW_WB
+            // timing-attribution build (like the PT_ABL_* of k_shade, images wrong by construction): what the write-back of the unified launch's
+            // shadow lanes costs the frame — the most that carrying the sums with the path (PT_CARRY_SUMS) can give
+            if (MODE == TR_UNIFIED) return;
+#endif
+            if (MODE == TR_UNIFIED && CARRY) { // carried sums (PT_CARRY_SUMS): one visibility word per shadow ray, dense; k_shade adds the contribution
+                st_st<PT_NT_TRACE_ST>(&a.st.svis[slot], occluded ? 0u : 1u);
+                return;
+            }
             const uint32_t ps = (MODE == TR_UNIFIED ? a.queue2 : a.queue).base[slot]; // the path slot of this shadow-queue entry
             if (a.st.vis) { // asynchronous shadow records: only publish the visibility, k_resolve sums in bounce order
                 if (!occluded) atomicOr(&a.st.vis[ps], 1u << a.bounce);
@@ -827,6 +836,16 @@ k_trace8(Trace8Args a) {
     a.hist = a.dbg ? a.dbg + 53 : nullptr;
 #endif
     trace8_wave<MODE, false>(a, blockIdx.x, gridDim.x, 0u, 0u, 0u);
+}
+// k_trace8<TR_UNIFIED> of a chain with carried sums (PT_CARRY_SUMS): a shadow lane's write-back is one visibility word, st.svis[position in queue2].
+// A kernel of its own and not a launch argument: with both write-backs in one kernel the loop kept 20 instead of 12 bytes of scratch and the
+// frame was 2 % slower than without the change; this one has none (96 VGPRs as before).
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT8_WAVES_PER_EU, PT8_WAVES_PER_EU)))
+k_trace8_vis(Trace8Args a) {
+#if PT_DEBUG_WAVELOG + 0 == 3
+    a.hist = a.dbg ? a.dbg + 53 : nullptr;
+#endif
+    trace8_wave<TR_UNIFIED, false, true>(a, blockIdx.x, gridDim.x, 0u, 0u, 0u);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------

@@ -370,6 +370,10 @@ template <bool NT> PT_DEV void st_st(float2* p, float2 a) {
     const pt_f2v v = {a.x, a.y};
     __builtin_nontemporal_store(v, reinterpret_cast<pt_f2v*>(p));
 }
+template <bool NT> PT_DEV void st_st(uint32_t* p, uint32_t a) {
+    if (!NT) { *p = a; return; }
+    __builtin_nontemporal_store(a, p);
+}
 template <bool NT> PT_DEV void st_st(uint4* p, uint4 a) {
     if (!NT) { *p = a; return; }
     const pt_u4v v = {a.x, a.y, a.z, a.w};

@@ -35,6 +35,15 @@ struct PathState {
     uint4* rf;     // Random seed1, seed2 | depth | flags << 8 | unused
     // the shadow rays of the bounce, in the order of the shadow queue: origin, direction (tmin .01, tmax 1e16), pending NEE contribution xyz | kind
     float4 *shO, *shD, *shPend;
+    // Carried sums (PT_CARRY_SUMS; unified shadow placement, scenes without shadow catchers): the path's running sum and the contribution of
+    // its last shadow ray travel with the queue entry, 32 bytes — c0 = (sum.xyz, pend.x), c1 = (pend.yz, bits of sq << 2 | kind, -), sq = the
+    // ray's position in the shadow queue, kind = 0 (no pending ray) / PEND_DIRECT / PEND_INDIRECT.  `sum` is the DIRECT sum in the record the
+    // chain's first launch writes (nothing has been added to the indirect sum yet) and the INDIRECT sum afterwards: the direct sum is complete
+    // once the second launch has seen the first shadow ray's visibility, and goes to direct[slot] there.  The unified traversal launch
+    // stores svis[sq] = 1 (visible) or 0 for every shadow ray it traces; the next k_shade adds pend where svis[sq] says so; indirect[slot]
+    // is written once, when the path ends (or in the chain's last launch).
+    float4 *c0, *c1;
+    uint32_t* svis; // by position in the shadow queue
     // ---- by path slot
     uint32_t* pflags; // FLAG_CULLED (generate) | FLAG_HIT0 (first hit): what the resolve kernels need of a path's flags
     float4 *direct, *indirect, *nrm, *alb;
@@ -260,6 +269,10 @@ struct ShadeParams {
     uint4* oRf;
     int aov;            // write the first-hit normal/albedo (the foveated variants only keep accum/frame)
     int first;          // the queue holds camera rays: throughput (1,1,1) and eta 1 are not read (the generate kernels do not write them)
+    // carried sums (k_shade_carry; PathState::c0): the continuing paths' records, beside oThr / oRf
+    float4 *oC0, *oC1;
+    int second;         // the chain's second launch: the incoming records hold the direct sums
+    int last;           // the chain's last launch: every path writes its sums to direct / indirect, its shadow ray goes out with shPend (TR_SHADOW_APPLY adds it)
 };
 
 // wave-aggregated queue append: one atomic per wave (over the lanes that are active at the call: it may sit in divergent code).  Returns the
@@ -292,6 +305,12 @@ PT_DEV uint32_t queue_push(bool pred, uint32_t value, const QView& q) {
     return pos;
 }
 
+// Carried sums: a finished sum goes to its slot array, one store.  A sum of three +0 is the value the generate kernels left in the slot and is
+// not written (a sum is never -0: it starts at +0, and +0 + (±0) = +0).
+PT_DEV void flush_sum(float4* acc, uint32_t p, v3 sum) {
+    if ((__float_as_uint(sum.x) | __float_as_uint(sum.y) | __float_as_uint(sum.z)) != 0u) st_st<PT_NT_SHADE_ST>(&acc[p], make_float4(sum.x, sum.y, sum.z, 0.f));
+}
+
 // __miss__radiance (:209-235): prd.normal = prd.albedo = 0 (adds nothing at depth 0), DONE
 template <bool CATCHER>
 PT_DEV void shade_miss(const PathState& st, const ShadeParams& sp, uint32_t pos, uint32_t p) {
@@ -309,13 +328,38 @@ PT_DEV void shade_miss(const PathState& st, const ShadeParams& sp, uint32_t pos,
 // __miss__radiance plus the raygen loop's bookkeeping).  A path that continues is pushed into next_queue and its state written at the
 // position of that entry; a pending shadow ray is pushed into shadow_queue with its record (or, with asynchronous shadow rays, written
 // to the per-bounce record of the slot).
-template <int MODE, bool CATCHER, bool LOCAL = false>
+// CARRY (the launch chain with unified shadow placement, scenes without catchers): direct / indirect are not touched bounce by bounce — the
+// path's sums come in with its queue entry, take the previous bounce's contribution if its shadow ray was visible (st.svis, written by the
+// traversal launch in between; the additions and their order are those of k_trace8's write-back), and go on with the entry or, when the path
+// ends, to the slot arrays.
+template <int MODE, bool CATCHER, bool LOCAL = false, bool CARRY = false>
 PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMarg& pm, const float* u8lut, uint32_t pos, uint32_t p, float2 h) {
+    static_assert(!CARRY || (!CATCHER && !LOCAL), "carried sums: launch chain of a scene without shadow catchers only");
     const int32_t leaf = __float_as_int(h.y);
+    v3 sum = mk3(0.f); // the sum that travels with the path: direct in the first launch, indirect afterwards (PathState::c0)
+    if (CARRY && !sp.first) {
+        const float4 r0 = st_ld<PT_NT_SHADE_LD>(&st.c0[pos]), r1 = st_ld<PT_NT_SHADE_LD>(&st.c1[pos]);
+        sum = mk3(r0.x, r0.y, r0.z);
+        const uint32_t sk = __float_as_uint(r1.z);
+        const bool add = (sk & 3u) != 0u && st.svis[sk >> 2] != 0u;
+        const bool to_direct = (sk & 3u) == (uint32_t)PEND_DIRECT; // (second launch only: later contributions are indirect)
+        if (sp.second) {
+            v3 isum = mk3(0.f);
+            if (add && to_direct) sum = mk3(sum.x + r0.w, sum.y + r1.x, sum.z + r1.y);
+            if (add && !to_direct) isum = mk3(isum.x + r0.w, isum.y + r1.x, isum.z + r1.y);
+            flush_sum(st.direct, p, sum); // emission and the first contribution: nothing is added to it after this
+            sum = isum;
+        } else if (add) {
+            sum = mk3(sum.x + r0.w, sum.y + r1.x, sum.z + r1.y);
+        }
+    }
     if (leaf < 0) {
         shade_miss<CATCHER>(st, sp, pos, p);
+        if (CARRY) flush_sum(sp.first ? st.direct : st.indirect, p, sum);
         return;
     }
+    v3 pend_out = mk3(0.f);
+    uint32_t sk_out = 0u; // position in the shadow queue << 2 | kind of the contribution that waits for this bounce's shadow ray
     bool push_next = false;
     const uint4 rf = st_ld<PT_NT_SHADE_LD>(&st.rf[pos]);
     int depth = (int)(rf.z & 0xffu);
@@ -484,13 +528,22 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
                 // radiance = T*lightSample (+ emission on primary hits) is added to direct/indirect (:432-437)
                 // only when the path goes on; the visibility-dependent part is deferred to the traversal kernel's write-back (k_trace8).
                 if (primary && emissive) {
-                    const float4 dd = st.direct[p];
-                    st.direct[p] = make_float4(dd.x + mat.emission[0], dd.y + mat.emission[1], dd.z + mat.emission[2], 0.f);
+                    if (CARRY) { // (a primary hit: the chain's first launch, `sum` is the direct sum)
+                        sum = mk3(sum.x + mat.emission[0], sum.y + mat.emission[1], sum.z + mat.emission[2]);
+                    } else {
+                        const float4 dd = st.direct[p];
+                        st.direct[p] = make_float4(dd.x + mat.emission[0], dd.y + mat.emission[1], dd.z + mat.emission[2], 0.f);
+                    }
                 }
                 if (has_val) {
                     const float4 pe = make_float4(contrib.x, contrib.y, contrib.z, __int_as_float(depth == 0 ? PEND_DIRECT : PEND_INDIRECT));
                     const uint32_t sq = queue_push<LOCAL>(true, p, sp.shadow_queue);
-                    if (st.vis) { // asynchronous shadow rays: a self-contained record of this bounce, by slot (the queue entry names the slot)
+                    if (CARRY && !sp.last) { // the contribution stays with the path; the next k_shade adds it if the ray was visible
+                        st_st<PT_NT_SHADE_ST>(&st.shO[sq], make_float4(P.x, P.y, P.z, 0.f));
+                        st_st<PT_NT_SHADE_ST>(&st.shD[sq], make_float4(wi.x, wi.y, wi.z, 0.f));
+                        pend_out = contrib;
+                        sk_out = (sq << 2) | (uint32_t)(depth == 0 ? PEND_DIRECT : PEND_INDIRECT);
+                    } else if (st.vis) { // asynchronous shadow rays: a self-contained record of this bounce, by slot (the queue entry names the slot)
                         const size_t bi = (size_t)depth * st.bstride + p;
                         st.sO[bi] = make_float4(P.x, P.y, P.z, 0.f);
                         st.sD[bi] = make_float4(wi.x, wi.y, wi.z, 0.f);
@@ -533,6 +586,14 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
         st_st<PT_NT_SHADE_ST>(&sp.oThr[nq], thr_out);
         st_st<PT_NT_SHADE_ST>(&sp.oRf[nq], make_uint4(rng_out.x, rng_out.y, (uint32_t)depth | (flags << 8), 0u));
     }
+    if (CARRY) {
+        if (push_next && !sp.last) {
+            st_st<PT_NT_SHADE_ST>(&sp.oC0[nq], make_float4(sum.x, sum.y, sum.z, pend_out.x));
+            st_st<PT_NT_SHADE_ST>(&sp.oC1[nq], make_float4(pend_out.y, pend_out.z, __uint_as_float(sk_out), 0.f));
+        } else {
+            flush_sum(sp.first ? st.direct : st.indirect, p, sum); // the path ends here, or the chain does (its last shadow ray is added by TR_SHADOW_APPLY, by slot)
+        }
+    }
 }
 
 // k_shade waits on memory half of the time (dense state, then the triangle record and the probe search's scattered lines): 5 waves per SIMD
@@ -548,8 +609,9 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
 #define PT_LDS_PROBE_ROWS 2048
 #endif
 
-template <int MODE, bool CATCHER>
-__global__ void __launch_bounds__(256) PT_SHADE_ATTR k_shade(PathState st, ShadeParams sp) {
+// the body of the shade kernels (k_shade, k_shade_carry below)
+template <int MODE, bool CATCHER, bool CARRY>
+PT_DEV void shade_queue(const PathState& st, const ShadeParams& sp) {
     __shared__ uint32_t s_prefix[PT_NSUB + 1];
     __shared__ float s_u8[256]; // textured scenes: (float)b / 255.0f for the 256 byte values (tex2d_wrap_linear)
     extern __shared__ __attribute__((aligned(16))) float s_marg[]; // sized at launch for the probe in use (shade_lds_bytes): 8.8 KB for 1024 rows
@@ -584,9 +646,19 @@ __global__ void __launch_bounds__(256) PT_SHADE_ATTR k_shade(PathState st, Shade
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nround; i += gridDim.x * blockDim.x) {
         if (i < n) {
             const uint32_t pos = qreader_pos(sp.queue, s_prefix, i);
-            shade_path<MODE, CATCHER>(st, sp, pm, u8lut, pos, qslot(sp.queue, pos), st_ld<PT_NT_SHADE_LD>(&st.hit[pos]));
+            shade_path<MODE, CATCHER, false, CARRY>(st, sp, pm, u8lut, pos, qslot(sp.queue, pos), st_ld<PT_NT_SHADE_LD>(&st.hit[pos]));
         }
     }
+}
+
+template <int MODE, bool CATCHER>
+__global__ void __launch_bounds__(256) PT_SHADE_ATTR k_shade(PathState st, ShadeParams sp) {
+    shade_queue<MODE, CATCHER, false>(st, sp);
+}
+// the launch chain with carried sums (PT_CARRY_SUMS; scenes without shadow catchers, unified shadow placement)
+template <int MODE>
+__global__ void __launch_bounds__(256) PT_SHADE_ATTR k_shade_carry(PathState st, ShadeParams sp) {
+    shade_queue<MODE, false, true>(st, sp);
 }
 
 // ------------------------------------------------------------------ resolve
