@@ -16,8 +16,10 @@ that plane is what temporalMoments divides by and modulatePlanes multiplies back
 
 With --lod step 2 is surfaceLodPlanes: the albedo filtered over the pixel's footprint in texture space (a trilinear lookup in the mip pyramid,
 which is built once, before the loop), so a minified texture does not alias in the plane the loop divides by and multiplies back in.
+With --aniso N (which implies --lod) it is surfaceAnisoPlanes: up to N such lookups along the footprint's longer axis, so a ground seen at a
+grazing angle is not blurred across that axis.
 
-  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--out-dir .]
+  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--out-dir .]
 """
 import argparse
 import os
@@ -60,9 +62,11 @@ def main():
     ap.add_argument("--sigma-lum", type=float, default=4.0)
     ap.add_argument("--min-length", type=int, default=4)
     ap.add_argument("--lod", action="store_true", help="footprint-filtered albedo (surfaceLodPlanes) instead of the point lookup of surfacePlanes")
+    ap.add_argument("--aniso", type=int, default=0, metavar="N", help="implies --lod: up to N (1..16) lookups along the footprint's longer axis (surfaceAnisoPlanes)")
     ap.add_argument("--footprint-scale", type=float, default=1.0, help="with --lod: 1 = the pixel's own footprint")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args()
+    args.lod = args.lod or args.aniso > 0
     import torch
 
     dev = "cuda:0"
@@ -92,7 +96,9 @@ def main():
         i, o = k & 1, ~k & 1
         sample.setCamera(cam)
         g = sample.renderGBuffer(("hit", "position", "motion"), prev_cameras=prev, out=cur)
-        if args.lod:
+        if args.aniso:
+            s = sample.surfaceAnisoPlanes(cur["hit"], table, mips, max_aniso=args.aniso, footprint_scale=args.footprint_scale, out=dict(albedo=albedo))
+        elif args.lod:
             s = sample.surfaceLodPlanes(cur["hit"], table, mips, footprint_scale=args.footprint_scale, out=dict(albedo=albedo))
         else:
             s = sample.surfacePlanes(cur["hit"], table, out=dict(albedo=albedo))
@@ -111,7 +117,7 @@ def main():
         m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=frame)
         ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
         print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
-              f"{ss['textured']} of {ss['hits']} hits textured{', %d minified' % ss['minified'] if args.lod else ''}; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
+              f"{ss['textured']} of {ss['hits']} hits textured{', %d minified' % ss['minified'] if args.lod else ''}{', %d taps' % ss['taps'] if args.aniso else ''}; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
               f"plan {ps['kernel_ms']:.3f} ms, colour {sample.stats()['render_ms']:.2f} ms, temporal {ts['kernel_ms']:.3f} ms, "
               f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms")
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_final.npy"), final.cpu().numpy())

@@ -7,18 +7,18 @@ surface[Lod]Planes.
 
 Two SampleRenderers over one model: `lo` at size / scale and `hi` at size.  Per frame, on `lo`, steps 1-7 of adaptive_svgf_albedo_loop.py:
   1. renderGBuffer: hit, position and motion against LAST frame's camera;
-  2. surfacePlanes (surfaceLodPlanes with --lod): the low-resolution albedo the demodulation divides by;
+  2. surfacePlanes (surfaceLodPlanes with --lod, surfaceAnisoPlanes with --aniso N): the low-resolution albedo the demodulation divides by;
   3. samplePlan;  4. renderMask(mask);  5. temporalMoments on the mask;  6. temporalCarry on its complement;
   7. filterPlanes on all pixels: the filtered irradiance at low resolution.
 Per frame, on `hi`:
   8. renderGBuffer: hit and position;
-  9. surfacePlanes (surfaceLodPlanes with --lod): the albedo under every display pixel;
+  9. surfacePlanes (surfaceLodPlanes with --lod, surfaceAnisoPlanes with --aniso N): the albedo under every display pixel;
  10. upsamplePlanes: the low-resolution irradiance on the display's pixels — four taps of the same surface where there are four, fewer
      where an edge is near, the ring around them where there is none (rescued), another surface's value where that fails too (orphans);
  11. modulatePlanes with the full-resolution albedo: the displayed frame.
 `hi` never renders a colour sample.
 
-  python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--out-dir .]
+  python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--out-dir .]
 """
 import argparse
 import os
@@ -51,10 +51,11 @@ def orbit(cam, angle):
 class UpsampledLoop:
     """The two renderers and every plane of the loop, allocated once; frame(k, prev, cam) runs one frame and returns its figures."""
 
-    def __init__(self, model, size, scale, lod=False, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32):
+    def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32):
         import torch
 
-        self.size, self.scale, self.lod = tuple(size), int(scale), lod
+        lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
+        self.size, self.scale, self.lod, self.aniso = tuple(size), int(scale), lod, int(aniso)
         w, h = self.size
         if w % self.scale or h % self.scale:
             raise SystemExit(f"--size {w} {h} is not a multiple of --scale {self.scale}")
@@ -86,6 +87,8 @@ class UpsampledLoop:
         self.mips = {id(r): r.copyTextureMipsDevice() if lod else None for r in (self.lo, self.hi)}
 
     def _albedo(self, r, hit, out):
+        if self.aniso:
+            return r.surfaceAnisoPlanes(hit, self.table[id(r)], self.mips[id(r)], max_aniso=self.aniso, out=dict(albedo=out))["stats"]
         if self.lod:
             return r.surfaceLodPlanes(hit, self.table[id(r)], self.mips[id(r)], out=dict(albedo=out))["stats"]
         return r.surfacePlanes(hit, self.table[id(r)], out=dict(albedo=out))["stats"]
@@ -137,11 +140,12 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--spp", type=int, default=1)
     ap.add_argument("--lod", action="store_true", help="footprint-filtered albedo (surfaceLodPlanes) at both resolutions")
+    ap.add_argument("--aniso", type=int, default=0, metavar="N", help="implies --lod: up to N (1..16) lookups along the footprint's longer axis (surfaceAnisoPlanes)")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
     make, cam0 = SCENES[args.scene]
-    loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, spp=args.spp)
+    loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)

@@ -20,7 +20,7 @@
  * they return.  Entry points that take or return DEVICE pointers — pt_pack, pt_unpack, pt_pack_async,
  * pt_unpack_display, pt_render_device, pt_device_buffer, pt_display_buffer, pt_update_meshes_device, pt_trace_device, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes,
  * pt_copy_vertices_device, pt_motion_planes, pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
- * pt_copy_texture_mips_device, pt_surface_lod_planes, pt_upsample_planes — read and write them on
+ * pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes — read and write them on
  * pt_stream(ctx), so:
  *   - a buffer the caller PRODUCED on another stream (the receive buffer of an all-gather, a buffer a
  *     memset just cleared) must be complete before the call: synchronise that stream on the host, or
@@ -38,7 +38,7 @@
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
  * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
  * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
- * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_upsample_planes.  A
+ * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -1256,7 +1256,8 @@ int pt_surface_planes(pt_ctx* ctx, const pt_surface_desc* desc, pt_surface_stats
  * (the first texel of every level) into the call's one temporary allocation, next to the counters.
  * footprint_scale: 1 = the pixel's own footprint; 0 = pt_surface_planes's albedo and texcoord bit for bit.
  * stats: pixels processed; hits, stale, textured and minified (rho > 1) among them; device time of the pass.
- * Not part of this interface: anisotropic footprints (the larger axis picks the level), LOD in the frame path (PT_BUF_ALBEDO and the
+ * Not part of this interface: anisotropic footprints (the larger axis picks the level; pt_surface_aniso_planes below takes several taps
+ * along it), LOD in the frame path (PT_BUF_ALBEDO and the
  * shading stay point lookups), emission, roughness or normal planes, a pt_multi_* wrapper. */
 int pt_texture_mips_layout(const pt_ctx* ctx, uint32_t* textures, uint32_t* dims /* HOST, textures x 4, may be NULL */, size_t* bytes);
 int pt_copy_texture_mips_device(pt_ctx* ctx, void* dev_dst, size_t bytes);
@@ -1276,6 +1277,72 @@ typedef struct pt_surface_lod_desc {
 } pt_surface_lod_desc;
 typedef struct pt_surface_lod_stats { uint64_t pixels, hits, stale, textured, minified; double kernel_ms; } pt_surface_lod_stats;
 int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* desc, pt_surface_lod_stats* stats /* may be NULL */);
+
+/* ANISOTROPIC FOOTPRINT-FILTERED ALBEDO (no reference counterpart): pt_surface_lod_planes with several taps along the footprint's longer
+ * axis.  pt_surface_lod_planes lets the longer of the pixel's two footprint axes pick the level, so a ground seen at a grazing angle is
+ * blurred along the shorter axis as well.  pt_surface_aniso_planes takes N <= max_aniso lookups spread along the longer axis, each at the
+ * level that a footprint N times shorter picks, and averages them: the filter's extent along the longer axis stays the pixel's, across
+ * it the filter narrows by up to max_aniso.
+ * It uses the pyramid of pt_texture_mips_layout / pt_copy_texture_mips_device unchanged.  The pixel set, rectangles, views, partitions,
+ * pointer checks, what is read from the context, ordering and state are exactly pt_surface_lod_planes's, and so are albedo, texcoord,
+ * footprint, lod, block_mask, footprint_scale, mips and mips_bytes; taps is one more frame-sized output of 1 f32 per pixel.  Every tap
+ * address comes from the context's own texture sizes, never from caller memory: hit[p].prim is compared with the triangle count before any
+ * address is formed from it, and the texel indices are clamped into their level before a texel is read — the tap texcoords are
+ * caller-influenced floats and may be anything.
+ * Arithmetic per pixel p — float32 throughout, one rounding per operation, no fused multiply-add, in exactly this order; float32 NumPy
+ * evaluating this reproduces every output bit for bit (tests/surface_aniso_ref.py):
+ *   - A miss, a stale record and a hit on an untextured mesh: albedo, texcoord, footprint and lod hold pt_surface_lod_planes's values and
+ *     taps[p] = 0.
+ *   - A hit on a textured mesh, with s, t, ds_x, dt_x, ds_y, dt_y, rx, ry, ok, W_t, H_t and Lm = levels - 1 of pt_surface_lod_planes's text:
+ *         texcoord[p] = (s, t);  footprint[p] = (ds_x, dt_x, ds_y, dt_y)
+ *         xm = rx > ry                                    (pt_surface_lod_planes's own comparison: a tie takes y)
+ *         r_maj2 = xm ? rx : ry;  r_min2 = xm ? ry : rx;  (a_s, a_t) = xm ? (ds_x, dt_x) : (ds_y, dt_y)
+ *         rho_maj = (ok ? sqrtf(r_maj2) : +infinity) * footprint_scale;  rho_min = sqrtf(r_min2) * footprint_scale
+ *         if !(rho_maj > 1.0f) or !ok: N = 1              (level 0 or the coarsest level, exactly as pt_surface_lod_planes)
+ *         else q = rho_maj / rho_min;  N = (q <= (float)max_aniso) ? (uint)ceilf(q) : max_aniso        (+infinity and NaN take max_aniso)
+ *         rho = rho_maj / (float)N                        (N = 1: rho_maj itself, no division)
+ *       The level choice is pt_surface_lod_planes's, taken from this rho: level 0 if !(rho > 1.0f), with lod[p] = 0; else the coarsest
+ *       level alone if !(rho < (float)(1 << Lm)), with lod[p] = (float)Lm; otherwise trilinear with k and frac from rho's bits,
+ *       c = c_k + ((c_k+1 - c_k) * frac) per channel and lod[p] = (float)k + frac.
+ *         tap i = 0 .. N-1:  o_i = (float)(2i + 1 - N) / (float)(2N)         (the numerator a signed integer: one rounding, the division's)
+ *                            (s_i, t_i) = (s + ((o_i * footprint_scale) * a_s), t + ((o_i * footprint_scale) * a_t))
+ *                            N = 1: the tap is (s, t) itself, with no arithmetic (a non-finite axis does not reach it)
+ *         c_i = that level choice evaluated at (s_i, t_i);  acc = c_0;  acc = acc + c_i for i = 1 .. N-1 in order;  out = acc / (float)N
+ *                            (N = 1: out = c_0, no division)
+ *         albedo[p] = (out.xyz, 1.0f);  taps[p] = (float)N
+ *     stats->minified counts rho_maj > 1.0f — the pixels pt_surface_lod_planes counts, whatever max_aniso is; stats->anisotropic counts
+ *     N > 1; stats->taps is the sum of N over the textured pixels.
+ *     The offsets o_i are symmetric about 0 bit for bit (o_i = -o_(N-1-i); the middle tap of an odd N is 0) and lie inside (-0.5, 0.5):
+ *     the taps are the centres of N equal pieces of the longer axis through the pixel's centre.  A primitive whose texcoords are collinear can have rho_min = 0: q is +infinity and N = max_aniso.  ok
+ *     false (a horizon pixel, a zero-area primitive) takes the coarsest level with one tap, as pt_surface_lod_planes does.  Non-finite
+ *     tap texcoords fault nothing: albedo[p].xyz are then NaN.
+ * max_aniso = 1 gives pt_surface_lod_planes's four planes bit for bit; footprint_scale = 0 gives pt_surface_planes's albedo and texcoord
+ * bit for bit (rho_maj is 0 or NaN, so N = 1 and level 0).
+ * Overlap: the five outputs may overlap nothing; hit, prim_texcoords and mips are only read.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): everything pt_surface_lod_planes refuses, with
+ * this function's name in the text (all FIVE outputs NULL for "no plane asked for"); max_aniso 0 or above 16; a taps plane that fails the
+ * pointer checks or overlaps another plane.
+ * stats: pixels processed; hits, stale, textured, minified, anisotropic among them; taps as above; device time of the pass.
+ * Not part of this interface: an elliptical (EWA) weighting of the taps, anisotropy in the frame path's own lookup, a pt_multi_* wrapper,
+ * an asynchronous variant. */
+enum pt_surface_aniso_flags { PT_SURFACE_ANISO_RESERVED = 0 };  /* no flag defined yet: flags must be 0 */
+typedef struct pt_surface_aniso_desc {   /* pt_surface_lod_desc's fields in its order, then taps, max_aniso, flags */
+    const void*  hit;             /* w*h x pt_hit, this frame (pt_render_gbuffer); required */
+    const float* prim_texcoords;  /* triangles x 6 f32 (pt_copy_texcoords_device); required iff the scene has a textured mesh */
+    const void*  mips;            /* the pyramid (pt_copy_texture_mips_device); required iff textured and the layout's bytes > 0 */
+    size_t mips_bytes;            /* pt_texture_mips_layout's bytes */
+    float* albedo;                /* w*h x 4  or NULL */
+    float* texcoord;              /* w*h x 2  or NULL */
+    float* footprint;             /* w*h x 4  or NULL: ds/dx, dt/dx, ds/dy, dt/dy per pixel step */
+    float* lod;                   /* w*h x 1  or NULL */
+    const uint8_t* block_mask;    /* HOST, as pt_render_gbuffer, or NULL */
+    float footprint_scale;        /* finite, >= 0; 1 = the pixel's own footprint */
+    float* taps;                  /* w*h x 1  or NULL: the number of taps N taken, as a float; 0 where no texture was read */
+    uint32_t max_aniso;           /* 1..16 */
+    uint32_t flags;               /* 0 */
+} pt_surface_aniso_desc;
+typedef struct pt_surface_aniso_stats { uint64_t pixels, hits, stale, textured, minified, anisotropic, taps; double kernel_ms; } pt_surface_aniso_stats;
+int pt_surface_aniso_planes(pt_ctx* ctx, const pt_surface_aniso_desc* desc, pt_surface_aniso_stats* stats /* may be NULL */);
 
 /* GUIDED UPSAMPLING (no reference counterpart): a low-resolution colour plane brought to the context's resolution under the guidance of
  * both G-buffers — a joint-bilateral upsample.  The noisy, low-frequency part of the image (the demodulated irradiance) is traced and

@@ -28,7 +28,7 @@ EXPORTS = [
     "pt_trace_device", "pt_query_wait", "pt_render_gbuffer", "pt_temporal_accumulate", "pt_filter_planes",
     "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes", "pt_temporal_moments", "pt_modulate_planes",
     "pt_sample_plan", "pt_temporal_carry", "pt_copy_texcoords_device", "pt_surface_planes",
-    "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes",
+    "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes", "pt_surface_aniso_planes",
     "pt_upsample_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
@@ -172,6 +172,24 @@ class SurfaceLodStats(C.Structure):  # pt_surface_lod_stats
 
 # the output planes of pt_surface_lod_planes: float32 words per pixel
 SURFACE_LOD_PLANES = {"albedo": 4, "texcoord": 2, "footprint": 4, "lod": 1}
+
+
+class SurfaceAnisoDesc(C.Structure):  # pt_surface_aniso_desc
+    _fields_ = [("hit", C.c_void_p), ("prim_texcoords", C.c_void_p), ("mips", C.c_void_p), ("mips_bytes", C.c_size_t), ("albedo", C.c_void_p),
+                ("texcoord", C.c_void_p), ("footprint", C.c_void_p), ("lod", C.c_void_p), ("block_mask", C.c_void_p),
+                ("footprint_scale", C.c_float), ("taps", C.c_void_p), ("max_aniso", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SurfaceAnisoStats(C.Structure):  # pt_surface_aniso_stats
+    _fields_ = [("pixels", C.c_uint64), ("hits", C.c_uint64), ("stale", C.c_uint64), ("textured", C.c_uint64), ("minified", C.c_uint64),
+                ("anisotropic", C.c_uint64), ("taps", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the output planes of pt_surface_aniso_planes: float32 words per pixel
+SURFACE_ANISO_PLANES = {"albedo": 4, "texcoord": 2, "footprint": 4, "lod": 1, "taps": 1}
 
 
 class UpsampleDesc(C.Structure):  # pt_upsample_desc
@@ -486,6 +504,7 @@ def load_library() -> C.CDLL:
     L.pt_texture_mips_layout.argtypes = [vp, C.POINTER(u32), vp, C.POINTER(C.c_size_t)]
     L.pt_copy_texture_mips_device.argtypes = [vp, vp, C.c_size_t]
     L.pt_surface_lod_planes.argtypes = [vp, C.POINTER(SurfaceLodDesc), C.POINTER(SurfaceLodStats)]
+    L.pt_surface_aniso_planes.argtypes = [vp, C.POINTER(SurfaceAnisoDesc), C.POINTER(SurfaceAnisoStats)]
     L.pt_upsample_planes.argtypes = [vp, C.POINTER(UpsampleDesc), C.POINTER(UpsampleStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]

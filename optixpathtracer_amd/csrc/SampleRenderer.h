@@ -368,6 +368,15 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // surfaceLodPlanes with up to d.max_aniso lookups along the longer axis of the pixel's footprint (pt_surface_aniso_planes): a texture
+    // seen at a grazing angle is no longer blurred across that axis.  Stateless and synchronous.  Returns surfaceLodPlanes's counters, the
+    // pixels that took more than one lookup, the sum of the lookups and the device time.
+    pt_surface_aniso_stats surfaceAnisoPlanes(const pt_surface_aniso_desc& d, pt_surface_aniso_stats* stats = nullptr) {
+        pt_surface_aniso_stats s{};
+        ck(pt_surface_aniso_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Guided upsampling (pt_upsample_planes), on the FULL-size renderer: a low-resolution colour plane (a second renderer's filterPlanes
     // out) brought to this resolution under both G-buffers with the chain's mesh / normal / plane tests.  Stateless and synchronous.
     // Returns the pixels processed, the hits, and how many took four taps, the rescue and the orphan branch, and the device time.

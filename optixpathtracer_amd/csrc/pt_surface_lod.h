@@ -1,6 +1,7 @@
-// pt_texture_mips_layout, pt_copy_texture_mips_device and pt_surface_lod_planes (include/pt_amd.h): a box-filtered mip pyramid of the
-// context's textures in caller memory, and the albedo under every pixel's centre filtered over the pixel's footprint in texture space
-// (k_surface_lod) — pt_surface_planes with a level of detail.  Stateless, every plane the caller's.
+// pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes and pt_surface_aniso_planes (include/pt_amd.h): a box-filtered
+// mip pyramid of the context's textures in caller memory, and the albedo under every pixel's centre filtered over the pixel's footprint in
+// texture space — pt_surface_planes with a level of detail (k_surface_lod), and with several taps along the footprint's longer axis
+// (k_surface_aniso).  Stateless, every plane the caller's.
 //
 // The first part is host only and needs no HIP header (tests/test_surface_lod_cabi.py compiles it with a host compiler alone).
 #pragma once
@@ -130,6 +131,56 @@ PT_DEV v3 lod_ray(v3 U, v3 V, v3 W, float a, float b, float wr, float hr) {
     return add3(add3(scl3(U, dx), scl3(V, dy)), W);
 }
 
+// The footprint of one textured hit, the header's text from w0 to rx, ry: what k_surface_lod and k_surface_aniso share.  prim is in range
+// and tid >= 0 (the caller has tested both).
+struct LodFoot {
+    float s, t, ds_x, dt_x, ds_y, dt_y, rx, ry;
+    bool ok;
+    DevTex tx;
+};
+template <bool VIEWS>
+PT_DEV LodFoot lod_footprint(const SurfaceLodArgs& a, const ViewParams& vp, uint32_t xy, int32_t prim, float u, float v, int tid) {
+    float c[6]; // uv0.xy, uv1.xy, uv2.xy
+    __builtin_memcpy(c, a.prim_uv + 6 * (size_t)prim, 24);
+    const float w0 = (1.0f - u) - v;
+    const float s = ((w0 * c[0]) + (u * c[2])) + (v * c[4]);
+    const float t = ((w0 * c[1]) + (u * c[3])) + (v * c[5]);
+    // the pixel's camera: its view's or the frame's.  Looked up here, where the few pixels that need it are
+    const PassPixel px = pass_pixel<VIEWS>(vp, xy, a.width, a.height);
+    const uint32_t x = px.X - (uint32_t)px.x0, y = px.Y - (uint32_t)px.y0;
+    const int wr = px.wr, hr = px.hr;
+    v3 eye = a.eye, eU = a.U, eV = a.V, eW = a.W;
+    if (VIEWS) {
+        const pt_view& vw = vp.views[px.view];
+        eye = mk3(vw.eye[0], vw.eye[1], vw.eye[2]);
+        eU = mk3(vw.U[0], vw.U[1], vw.U[2]);
+        eV = mk3(vw.V[0], vw.V[1], vw.V[2]);
+        eW = mk3(vw.W[0], vw.W[1], vw.W[2]);
+    }
+    const uint32_t i0 = a.idx[3u * (size_t)prim], i1 = a.idx[3u * (size_t)prim + 1], i2 = a.idx[3u * (size_t)prim + 2];
+    const float *f0 = a.verts + 3 * (size_t)i0, *f1 = a.verts + 3 * (size_t)i1, *f2 = a.verts + 3 * (size_t)i2;
+    const v3 p0 = mk3(f0[0], f0[1], f0[2]), p1 = mk3(f1[0], f1[1], f1[2]), p2 = mk3(f2[0], f2[1], f2[2]);
+    const v3 e1 = sub3(p1, p0), e2 = sub3(p2, p0), nrm = cross3(e1, e2);
+    const float nn = dot3(nrm, nrm), hgt = dot3(nrm, sub3(p0, eye));
+    const float fx = (float)x, fy = (float)y, fw = (float)wr, fh = (float)hr;
+    const v3 dc = lod_ray(eU, eV, eW, fx + 0.5f, fy + 0.5f, fw, fh), dx = lod_ray(eU, eV, eW, fx + 1.5f, fy + 0.5f, fw, fh),
+             dy = lod_ray(eU, eV, eW, fx + 0.5f, fy + 1.5f, fw, fh);
+    const float t_c = hgt / dot3(nrm, dc), t_x = hgt / dot3(nrm, dx), t_y = hgt / dot3(nrm, dy);
+    const v3 Pc = add3(scl3(dc, t_c), eye), Px = add3(scl3(dx, t_x), eye), Py = add3(scl3(dy, t_y), eye);
+    const bool ok = t_c > 0.0f && t_x > 0.0f && t_y > 0.0f;
+    const float c20 = c[2] - c[0], c40 = c[4] - c[0], c31 = c[3] - c[1], c51 = c[5] - c[1];
+    const v3 gx = sub3(Px, Pc), gy = sub3(Py, Pc);
+    const float dux = dot3(cross3(gx, e2), nrm) / nn, dvx = dot3(cross3(e1, gx), nrm) / nn;
+    const float duy = dot3(cross3(gy, e2), nrm) / nn, dvy = dot3(cross3(e1, gy), nrm) / nn;
+    const float ds_x = dux * c20 + dvx * c40, dt_x = dux * c31 + dvx * c51;
+    const float ds_y = duy * c20 + dvy * c40, dt_y = duy * c31 + dvy * c51;
+    const DevTex tx = a.textures[tid];
+    const float Wt = (float)tx.w, Ht = (float)tx.h;
+    const float rx = (ds_x * Wt) * (ds_x * Wt) + (dt_x * Ht) * (dt_x * Ht);
+    const float ry = (ds_y * Wt) * (ds_y * Wt) + (dt_y * Ht) * (dt_y * Ht);
+    return LodFoot{s, t, ds_x, dt_x, ds_y, dt_y, rx, ry, ok, tx};
+}
+
 template <bool VIEWS, bool TEX>
 __global__ void __launch_bounds__(256) k_surface_lod(SurfaceLodArgs a, ViewParams vp) {
 #if __HIP_DEVICE_COMPILE__
@@ -158,47 +209,12 @@ __global__ void __launch_bounds__(256) k_surface_lod(SurfaceLodArgs a, ViewParam
             if (TEX) tid = a.mesh_tex[mesh];
             if (TEX && tid >= 0) {
                 is_tex = true;
-                float c[6]; // uv0.xy, uv1.xy, uv2.xy
-                __builtin_memcpy(c, a.prim_uv + 6 * (size_t)prim, 24);
-                const float u = ha.y, v = ha.z;
-                const float w0 = (1.0f - u) - v;
-                const float s = ((w0 * c[0]) + (u * c[2])) + (v * c[4]);
-                const float t = ((w0 * c[1]) + (u * c[3])) + (v * c[5]);
+                const LodFoot f = lod_footprint<VIEWS>(a, vp, xy, prim, ha.y, ha.z, tid);
+                const float s = f.s, t = f.t, rx = f.rx, ry = f.ry;
+                const bool ok = f.ok;
+                const DevTex tx = f.tx;
                 tc = make_float2(s, t);
-                // the pixel's camera: its view's or the frame's.  Looked up here, where the few pixels that need it are
-                const PassPixel px = pass_pixel<VIEWS>(vp, xy, a.width, a.height);
-                const uint32_t x = px.X - (uint32_t)px.x0, y = px.Y - (uint32_t)px.y0;
-                const int wr = px.wr, hr = px.hr;
-                v3 eye = a.eye, eU = a.U, eV = a.V, eW = a.W;
-                if (VIEWS) {
-                    const pt_view& vw = vp.views[px.view];
-                    eye = mk3(vw.eye[0], vw.eye[1], vw.eye[2]);
-                    eU = mk3(vw.U[0], vw.U[1], vw.U[2]);
-                    eV = mk3(vw.V[0], vw.V[1], vw.V[2]);
-                    eW = mk3(vw.W[0], vw.W[1], vw.W[2]);
-                }
-                const uint32_t i0 = a.idx[3u * (size_t)prim], i1 = a.idx[3u * (size_t)prim + 1], i2 = a.idx[3u * (size_t)prim + 2];
-                const float *f0 = a.verts + 3 * (size_t)i0, *f1 = a.verts + 3 * (size_t)i1, *f2 = a.verts + 3 * (size_t)i2;
-                const v3 p0 = mk3(f0[0], f0[1], f0[2]), p1 = mk3(f1[0], f1[1], f1[2]), p2 = mk3(f2[0], f2[1], f2[2]);
-                const v3 e1 = sub3(p1, p0), e2 = sub3(p2, p0), nrm = cross3(e1, e2);
-                const float nn = dot3(nrm, nrm), hgt = dot3(nrm, sub3(p0, eye));
-                const float fx = (float)x, fy = (float)y, fw = (float)wr, fh = (float)hr;
-                const v3 dc = lod_ray(eU, eV, eW, fx + 0.5f, fy + 0.5f, fw, fh), dx = lod_ray(eU, eV, eW, fx + 1.5f, fy + 0.5f, fw, fh),
-                         dy = lod_ray(eU, eV, eW, fx + 0.5f, fy + 1.5f, fw, fh);
-                const float t_c = hgt / dot3(nrm, dc), t_x = hgt / dot3(nrm, dx), t_y = hgt / dot3(nrm, dy);
-                const v3 Pc = add3(scl3(dc, t_c), eye), Px = add3(scl3(dx, t_x), eye), Py = add3(scl3(dy, t_y), eye);
-                const bool ok = t_c > 0.0f && t_x > 0.0f && t_y > 0.0f;
-                const float c20 = c[2] - c[0], c40 = c[4] - c[0], c31 = c[3] - c[1], c51 = c[5] - c[1];
-                const v3 gx = sub3(Px, Pc), gy = sub3(Py, Pc);
-                const float dux = dot3(cross3(gx, e2), nrm) / nn, dvx = dot3(cross3(e1, gx), nrm) / nn;
-                const float duy = dot3(cross3(gy, e2), nrm) / nn, dvy = dot3(cross3(e1, gy), nrm) / nn;
-                const float ds_x = dux * c20 + dvx * c40, dt_x = dux * c31 + dvx * c51;
-                const float ds_y = duy * c20 + dvy * c40, dt_y = duy * c31 + dvy * c51;
-                fp = make_float4(ds_x, dt_x, ds_y, dt_y);
-                const DevTex tx = a.textures[tid];
-                const float Wt = (float)tx.w, Ht = (float)tx.h;
-                const float rx = (ds_x * Wt) * (ds_x * Wt) + (dt_x * Ht) * (dt_x * Ht);
-                const float ry = (ds_y * Wt) * (ds_y * Wt) + (dt_y * Ht) * (dt_y * Ht);
+                fp = make_float4(f.ds_x, f.dt_x, f.ds_y, f.dt_y);
                 const float rho2 = ok ? (rx > ry ? rx : ry) : __uint_as_float(0x7f800000u);
                 const float rho = sqrtf(rho2) * a.scale;
                 float4 o;
@@ -230,6 +246,131 @@ __global__ void __launch_bounds__(256) k_surface_lod(SurfaceLodArgs a, ViewParam
         if (a.lod) a.lod[p] = lod;
     }
     pass_tally(pass_slot(a.counts), {is_hit, is_stale, is_tex, is_min}); // is_tex, is_min: never without TEX
+#endif
+}
+// ------------------------------------------------------------------ the anisotropic pass
+// pt_surface_aniso_planes: k_surface_lod with N <= max_aniso <= 16 taps along the footprint's major axis, each the level choice of
+// rho_maj / N.  Same thread layout, same order of loads, same LDS table; the pyramid, level_first, lod_level and lod_footprint are the
+// sibling's.  The tap loop has a runtime trip count and stays a loop (no unroll): three accumulators, no array, no scratch.  A wave is one
+// 8 x 8 block of pixels, so its lanes take similar N and their taps overlap in texture space: the reuse is left to L1/L2, as in k_filter
+// and k_upsample, with no LDS window (profiles/surface_aniso.md has the measurement).  Every tap address is formed as the sibling forms
+// its own: level k <= Lm of the context's texture tid through level_first, texel indices clamped into the level — the tap's texcoord is
+// a caller-influenced float and may be anything.
+struct SurfaceAnisoArgs {
+    SurfaceLodArgs lod; // counts: [0] hits, [1] stale, [2] textured, [3] minified, [4] anisotropic, [5] the sum of N - 1 of a slot
+    float* taps;        // null = not asked for
+    uint32_t max_aniso; // 1..16
+};
+
+template <bool VIEWS, bool TEX>
+__global__ void __launch_bounds__(256) k_surface_aniso(SurfaceAnisoArgs aa, ViewParams vp) {
+#if __HIP_DEVICE_COMPILE__
+    const SurfaceLodArgs& a = aa.lod;
+    __shared__ float s_u8[TEX ? 256 : 1];
+    if (TEX) {
+        s_u8[threadIdx.x] = (float)threadIdx.x / 255.0f;
+        __syncthreads();
+    }
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool is_hit = false, is_stale = false, is_tex = false, is_min = false;
+    uint32_t N = 0; // the taps of a textured pixel; 0 where no texture is read
+    if (i < a.n) {
+        const uint32_t xy = a.pixels[i];
+        const size_t p = (size_t)pass_y(xy) * (size_t)a.width + pass_x(xy);
+        const float4 ha = tp_load4(a.hit + 8 * p); // t, u, v, prim
+        const int32_t prim = __float_as_int(ha.w);
+        const bool miss = hit_is_miss(ha.w);
+        is_hit = !miss && (uint32_t)prim < a.ntri;
+        is_stale = !miss && !is_hit;
+        float4 alb = make_float4(0.f, 0.f, 0.f, 1.0f), fp = make_float4(0.f, 0.f, 0.f, 0.f);
+        float2 tc = make_float2(0.f, 0.f);
+        float lod = 0.f;
+        if (is_hit) {
+            const uint32_t mesh = a.tri_mesh[prim];
+            const float* col = a.mats[mesh].color;
+            int tid = -1;
+            if (TEX) tid = a.mesh_tex[mesh];
+            if (TEX && tid >= 0) {
+                is_tex = true;
+                const LodFoot f = lod_footprint<VIEWS>(a, vp, xy, prim, ha.y, ha.z, tid);
+                const float s = f.s, t = f.t;
+                const DevTex tx = f.tx;
+                tc = make_float2(s, t);
+                fp = make_float4(f.ds_x, f.dt_x, f.ds_y, f.dt_y);
+                const bool xm = f.rx > f.ry; // the sibling's own comparison: a tie takes y
+                const float r_maj2 = xm ? f.rx : f.ry, r_min2 = xm ? f.ry : f.rx;
+                const float a_s = xm ? f.ds_x : f.ds_y, a_t = xm ? f.dt_x : f.dt_y;
+                const float rho_maj = (f.ok ? sqrtf(r_maj2) : __uint_as_float(0x7f800000u)) * a.scale;
+                is_min = rho_maj > 1.0f;
+                N = 1u;
+                if (is_min && f.ok) {
+                    const float rho_min = sqrtf(r_min2) * a.scale;
+                    const float q = rho_maj / rho_min; // >= 1, +inf on a degenerate minor axis, NaN on a NaN one
+                    N = (q <= (float)aa.max_aniso) ? (uint32_t)ceilf(q) : aa.max_aniso;
+                }
+                const float rho = N > 1u ? rho_maj / (float)N : rho_maj;
+                // the level choice of rho, the sibling's three cases: level k alone, or k and k + 1 blended by frac
+                uint32_t k = 0u;
+                bool tri = false;
+                float frac = 0.f;
+                if (rho > 1.0f) { // (a NaN stays at level 0)
+                    const uint32_t Lm = 31u - (uint32_t)__clz(max(tx.w, tx.h));
+                    if (!(rho < (float)(1u << Lm))) { // the coarsest level alone (+inf too)
+                        k = Lm;
+                        lod = (float)Lm;
+                    } else {
+                        const uint32_t bits = __float_as_uint(rho);
+                        k = min(((bits >> 23) & 0xffu) - 127u, Lm - 1u);
+                        frac = __uint_as_float((bits & 0x007fffffu) | 0x3f800000u) - 1.0f;
+                        tri = true;
+                        lod = (float)k + frac;
+                    }
+                }
+                const float two_n = (float)(2u * N);
+                float ax = 0.f, ay = 0.f, az = 0.f;
+#pragma nounroll
+                for (uint32_t j = 0; j < N; ++j) {
+                    float sj = s, tj = t; // N = 1: the tap is (s, t) itself, no arithmetic on the axis
+                    if (N > 1u) {
+                        const float o = (float)((int)(2u * j + 1u) - (int)N) / two_n;
+                        const float os = o * a.scale;
+                        sj = s + os * a_s;
+                        tj = t + os * a_t;
+                    }
+                    float4 c = lod_level(a, tx, tid, k, sj, tj, s_u8);
+                    if (tri) {
+                        const float4 cn = lod_level(a, tx, tid, k + 1u, sj, tj, s_u8);
+                        c = make_float4(c.x + (cn.x - c.x) * frac, c.y + (cn.y - c.y) * frac, c.z + (cn.z - c.z) * frac, 1.0f);
+                    }
+                    ax = j ? ax + c.x : c.x;
+                    ay = j ? ay + c.y : c.y;
+                    az = j ? az + c.z : c.z;
+                }
+                if (N > 1u) {
+                    const float fn = (float)N;
+                    ax = ax / fn, ay = ay / fn, az = az / fn;
+                }
+                alb = make_float4(ax, ay, az, 1.0f);
+            } else {
+                alb = make_float4(col[0], col[1], col[2], 1.0f);
+            }
+        }
+        if (a.albedo) gb_store4(a.albedo + 4 * p, alb);
+        if (a.texcoord) gb_store2(a.texcoord + 2 * p, tc);
+        if (a.footprint) gb_store4(a.footprint + 4 * p, fp);
+        if (a.lod) a.lod[p] = lod;
+        if (aa.taps) aa.taps[p] = (float)N;
+    }
+    unsigned long long* slot = pass_slot(a.counts);
+    pass_tally(slot, {is_hit, is_stale, is_tex, is_min, N > 1u}); // the last three: never without TEX
+    if (TEX) { // the wave's taps beyond the first, the sum of N - 1 (<= 15: four bits), one ballot per bit; every lane arrives here.  The
+               // host adds the textured pixels: a wave without an anisotropic pixel issues the sibling's atomics and no more
+        const uint32_t extra = N > 1u ? N - 1u : 0u;
+        unsigned long long sum = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; ++b) sum += (unsigned long long)__popcll(__ballot((extra >> b) & 1u)) << b;
+        if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(slot + 5, sum);
+    }
 #endif
 }
 #endif // __HIPCC__

@@ -1,5 +1,6 @@
-// pt_texture_mips_layout, pt_copy_texture_mips_device and pt_surface_lod_planes: the mip pyramid of the context's textures in caller
-// memory (k_mip_from_tiles, k_mip_reduce) and the footprint-filtered albedo under every pixel's centre (k_surface_lod).  Part of pt_lib.hip.
+// pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes and pt_surface_aniso_planes: the mip pyramid of the context's
+// textures in caller memory (k_mip_from_tiles, k_mip_reduce) and the footprint-filtered albedo under every pixel's centre, with one lookup
+// (k_surface_lod) or several along the footprint's longer axis (k_surface_aniso).  Part of pt_lib.hip.
 #include "pt_surface_lod.h"
 
 // The context keeps its texture records on the device only (DevTex: w, h next to the tiles' address); they never change after pt_create.
@@ -76,40 +77,54 @@ extern "C" int pt_copy_texture_mips_device(pt_ctx* ctx, void* dev_dst, size_t by
     return PT_OK;
 }
 
-extern "C" int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* desc, pt_surface_lod_stats* stats) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_surface_lod_planes: null context");
-    if (!desc) return fail(ctx, PT_ERR_INVALID, "pt_surface_lod_planes: null description");
-    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_surface_lod_planes: no frame size yet (pt_resize)");
-    const std::string fn = "pt_surface_lod_planes: ";
-    if (desc->flags != 0u) return fail(ctx, PT_ERR_INVALID, (fn + "unknown flag bits " + std::to_string(desc->flags)).c_str());
-    if (!desc->albedo && !desc->texcoord && !desc->footprint && !desc->lod)
-        return fail(ctx, PT_ERR_INVALID, (fn + "no plane asked for (albedo, texcoord, footprint, lod are all null)").c_str());
-    if (!(std::isfinite(desc->footprint_scale) && desc->footprint_scale >= 0.0f)) return fail(ctx, PT_ERR_INVALID, (fn + "footprint_scale must be finite and >= 0").c_str());
+// What pt_surface_lod_planes and pt_surface_aniso_planes share on the host: every check behind the null tests, the level_first upload,
+// the pixel set, the launch and the counters.  aniso = false is the isotropic pass (k_surface_lod, four counters, no taps plane, no max_aniso).
+struct LodCall {
+    const char* name;
+    const void* hit;
+    const float* prim_texcoords;
+    const void* mips;
+    size_t mips_bytes;
+    float *albedo, *texcoord, *footprint, *lod, *taps;
+    const uint8_t* block_mask;
+    float footprint_scale;
+    uint32_t flags, max_aniso;
+    bool aniso;
+};
+static int lod_call(pt_ctx* ctx, const LodCall& d, unsigned long long (&sum)[6], uint32_t* pixels, double* ms) {
+    const bool aniso = d.aniso;
+    const std::string fn = std::string(d.name) + ": ";
+    if (d.flags != 0u) return fail(ctx, PT_ERR_INVALID, (fn + "unknown flag bits " + std::to_string(d.flags)).c_str());
+    if (aniso && (d.max_aniso < 1u || d.max_aniso > 16u)) return fail(ctx, PT_ERR_INVALID, (fn + "max_aniso must be 1..16, not " + std::to_string(d.max_aniso)).c_str());
+    if (!d.albedo && !d.texcoord && !d.footprint && !d.lod && !d.taps)
+        return fail(ctx, PT_ERR_INVALID, (fn + "no plane asked for (albedo, texcoord, footprint, lod" + (aniso ? ", taps" : "") + " are all null)").c_str());
+    if (!(std::isfinite(d.footprint_scale) && d.footprint_scale >= 0.0f)) return fail(ctx, PT_ERR_INVALID, (fn + "footprint_scale must be finite and >= 0").c_str());
     const bool tex = ctx->d_textris != nullptr; // the scene has a textured mesh (d_mesh_tex exists with it)
     std::vector<DevTex> textures;
     std::vector<uint32_t> dims;
     size_t mips_bytes = 0;
     int rc = PT_OK;
-    if (tex) rc = lod_layout_of(ctx, "pt_surface_lod_planes", textures, dims, &mips_bytes);
+    if (tex) rc = lod_layout_of(ctx, d.name, textures, dims, &mips_bytes);
     if (rc) return rc;
     const bool pyr = tex && mips_bytes != 0;
-    if (pyr && desc->mips && desc->mips_bytes != mips_bytes)
+    if (pyr && d.mips && d.mips_bytes != mips_bytes)
         return fail(ctx, PT_ERR_INVALID, (fn + "mips_bytes must equal pt_texture_mips_layout's " + std::to_string(mips_bytes)).c_str());
     const size_t npix = (size_t)ctx->width * ctx->height;
-    // exclusive: may overlap no other plane (the four written ones); hit, prim_texcoords and mips are only read.  On an untextured scene
+    // exclusive: may overlap no other plane (the written ones); hit, prim_texcoords and mips are only read.  On an untextured scene
     // prim_texcoords and mips are not looked at at all, nor is mips where no texture has a level above 0.
-    const PassPlane planes[7] = {{"hit", desc->hit, npix * sizeof(pt_hit), true, false},
-                                 {"prim_texcoords", tex ? desc->prim_texcoords : nullptr, sizeof(PrimUV) * (size_t)ctx->ntri, false, false},
-                                 {"mips", pyr ? desc->mips : nullptr, mips_bytes, false, false},
-                                 {"albedo", desc->albedo, npix * 16, false, true},
-                                 {"texcoord", desc->texcoord, npix * 8, false, true},
-                                 {"footprint", desc->footprint, npix * 16, false, true},
-                                 {"lod", desc->lod, npix * 4, false, true}};
-    rc = pass_planes_check(ctx, "pt_surface_lod_planes", planes, 7);
+    const PassPlane planes[8] = {{"hit", d.hit, npix * sizeof(pt_hit), true, false},
+                                 {"prim_texcoords", tex ? d.prim_texcoords : nullptr, sizeof(PrimUV) * (size_t)ctx->ntri, false, false},
+                                 {"mips", pyr ? d.mips : nullptr, mips_bytes, false, false},
+                                 {"albedo", d.albedo, npix * 16, false, true},
+                                 {"texcoord", d.texcoord, npix * 8, false, true},
+                                 {"footprint", d.footprint, npix * 16, false, true},
+                                 {"lod", d.lod, npix * 4, false, true},
+                                 {"taps", d.taps, npix * 4, false, true}};
+    rc = pass_planes_check(ctx, d.name, planes, aniso ? 8 : 7);
     if (rc) return rc;
-    if (tex && !desc->prim_texcoords) return fail(ctx, PT_ERR_INVALID, (fn + "the scene has a textured mesh: prim_texcoords is required (pt_copy_texcoords_device)").c_str());
-    if (pyr && !desc->mips) return fail(ctx, PT_ERR_INVALID, (fn + "the scene has a textured mesh: mips is required (pt_copy_texture_mips_device)").c_str());
-    if (pyr && (reinterpret_cast<uintptr_t>(desc->mips) & 15u)) return fail(ctx, PT_ERR_INVALID, (fn + "mips is not 16-byte aligned").c_str());
+    if (tex && !d.prim_texcoords) return fail(ctx, PT_ERR_INVALID, (fn + "the scene has a textured mesh: prim_texcoords is required (pt_copy_texcoords_device)").c_str());
+    if (pyr && !d.mips) return fail(ctx, PT_ERR_INVALID, (fn + "the scene has a textured mesh: mips is required (pt_copy_texture_mips_device)").c_str());
+    if (pyr && (reinterpret_cast<uintptr_t>(d.mips) & 15u)) return fail(ctx, PT_ERR_INVALID, (fn + "mips is not 16-byte aligned").c_str());
     // The first texel of every level >= 1, from the context's sizes: 128 bytes per texture behind the counter slots, in the call's one
     // temporary allocation.  `first` outlives the run (declared in front of it), so the upload needs no wait of its own.
     std::vector<uint32_t> first;
@@ -123,29 +138,50 @@ extern "C" int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* des
             }
         }
     }
-    const size_t slot_bytes = PASS_SLOT_BYTES; // per slot: hits, stale, textured, minified
+    const size_t slot_bytes = PASS_SLOT_BYTES; // per slot: hits, stale, textured, minified (anisotropic, taps beyond the first)
     PassRun run;
-    rc = run.open(ctx, "pt_surface_lod_planes", slot_bytes + sizeof(uint32_t) * first.size());
+    rc = run.open(ctx, d.name, slot_bytes + sizeof(uint32_t) * first.size());
     if (rc) return rc;
     const uint32_t* d_first = nullptr;
     if (tex) {
         d_first = reinterpret_cast<const uint32_t*>(run.d_counters + slot_bytes);
         CK(hipMemcpyAsync(run.d_counters + slot_bytes, first.data(), sizeof(uint32_t) * first.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    rc = run.select(desc->block_mask);
+    rc = run.select(d.block_mask);
     if (rc) return rc;
     const uint32_t n = run.n;
     if (n != 0) {
-        const SurfaceLodArgs sa{run.pixels, n, ctx->width, ctx->height, reinterpret_cast<const float*>(desc->hit), ctx->d_tri_mesh, ctx->ntri, ctx->d_mats,
-                                tex ? ctx->d_mesh_tex : nullptr, tex ? desc->prim_texcoords : nullptr, tex ? ctx->d_textures : nullptr,
-                                tex ? ctx->d_idx : nullptr, tex ? ctx->d_verts : nullptr, pyr ? reinterpret_cast<const float4*>(desc->mips) : nullptr, d_first,
-                                ctx->eye, ctx->U, ctx->V, ctx->W, desc->footprint_scale, desc->albedo, desc->texcoord, desc->footprint, desc->lod, run.counts()};
+        const SurfaceLodArgs sa{run.pixels, n, ctx->width, ctx->height, reinterpret_cast<const float*>(d.hit), ctx->d_tri_mesh, ctx->ntri, ctx->d_mats,
+                                tex ? ctx->d_mesh_tex : nullptr, tex ? d.prim_texcoords : nullptr, tex ? ctx->d_textures : nullptr,
+                                tex ? ctx->d_idx : nullptr, tex ? ctx->d_verts : nullptr, pyr ? reinterpret_cast<const float4*>(d.mips) : nullptr, d_first,
+                                ctx->eye, ctx->U, ctx->V, ctx->W, d.footprint_scale, d.albedo, d.texcoord, d.footprint, d.lod, run.counts()};
         const unsigned grid = (n + 255u) / 256u;
-        if (tex) PASS_LAUNCH(run, grid, 256, sa, k_surface_lod, true);
-        else PASS_LAUNCH(run, grid, 256, sa, k_surface_lod, false);
+        if (aniso) {
+            const SurfaceAnisoArgs aa{sa, d.taps, d.max_aniso};
+            if (tex) PASS_LAUNCH(run, grid, 256, aa, k_surface_aniso, true);
+            else PASS_LAUNCH(run, grid, 256, aa, k_surface_aniso, false);
+        } else {
+            if (tex) PASS_LAUNCH(run, grid, 256, sa, k_surface_lod, true);
+            else PASS_LAUNCH(run, grid, 256, sa, k_surface_lod, false);
+        }
     }
-    unsigned long long sum[4];
-    rc = run.close_slots(sum, 4);
+    rc = run.close_slots(sum, aniso ? 6 : 4);
+    if (rc) return rc;
+    *pixels = n;
+    *ms = run.ms;
+    return PT_OK;
+}
+
+extern "C" int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* desc, pt_surface_lod_stats* stats) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_surface_lod_planes: null context");
+    if (!desc) return fail(ctx, PT_ERR_INVALID, "pt_surface_lod_planes: null description");
+    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_surface_lod_planes: no frame size yet (pt_resize)");
+    const LodCall d{"pt_surface_lod_planes", desc->hit, desc->prim_texcoords, desc->mips, desc->mips_bytes, desc->albedo, desc->texcoord, desc->footprint,
+                    desc->lod, nullptr, desc->block_mask, desc->footprint_scale, desc->flags, 0u, false};
+    unsigned long long sum[6] = {};
+    uint32_t n = 0;
+    double ms = 0.0;
+    const int rc = lod_call(ctx, d, sum, &n, &ms);
     if (rc) return rc;
     if (stats) {
         stats->pixels = n;
@@ -153,7 +189,31 @@ extern "C" int pt_surface_lod_planes(pt_ctx* ctx, const pt_surface_lod_desc* des
         stats->stale = sum[1];
         stats->textured = sum[2];
         stats->minified = sum[3];
-        stats->kernel_ms = run.ms;
+        stats->kernel_ms = ms;
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_surface_aniso_planes(pt_ctx* ctx, const pt_surface_aniso_desc* desc, pt_surface_aniso_stats* stats) {
+    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_surface_aniso_planes: null context");
+    if (!desc) return fail(ctx, PT_ERR_INVALID, "pt_surface_aniso_planes: null description");
+    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_surface_aniso_planes: no frame size yet (pt_resize)");
+    const LodCall d{"pt_surface_aniso_planes", desc->hit, desc->prim_texcoords, desc->mips, desc->mips_bytes, desc->albedo, desc->texcoord, desc->footprint,
+                    desc->lod, desc->taps, desc->block_mask, desc->footprint_scale, desc->flags, desc->max_aniso, true};
+    unsigned long long sum[6] = {};
+    uint32_t n = 0;
+    double ms = 0.0;
+    const int rc = lod_call(ctx, d, sum, &n, &ms);
+    if (rc) return rc;
+    if (stats) {
+        stats->pixels = n;
+        stats->hits = sum[0];
+        stats->stale = sum[1];
+        stats->textured = sum[2];
+        stats->minified = sum[3];
+        stats->anisotropic = sum[4];
+        stats->taps = sum[2] + sum[5]; // one tap per textured pixel, and the taps beyond it
+        stats->kernel_ms = ms;
     }
     return PT_OK;
 }

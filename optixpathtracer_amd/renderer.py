@@ -1103,6 +1103,39 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_surface_lod_planes", desc, _lib.SurfaceLodStats(), result)
 
+    def surfaceAnisoPlanes(self, hit, prim_texcoords=None, mips=None, max_aniso=8, planes=("albedo",), footprint_scale=1.0, mask=None, out=None) -> dict:
+        """surfaceLodPlanes with up to max_aniso (1..16) lookups along the longer axis of the pixel's footprint (pt_surface_aniso_planes,
+        include/pt_amd.h: the arithmetic, in full): each lookup takes the level of a footprint N times shorter, so a texture seen at a
+        grazing angle is no longer blurred across the longer axis.  max_aniso = 1 is surfaceLodPlanes bit for bit.
+
+        hit, prim_texcoords, mips, mask, out, footprint_scale: as surfaceLodPlanes takes them.  planes: any of surfaceLodPlanes's and
+        "taps" (h, w): the number of lookups taken, 0 where no texture was read.
+        Returns {plane: tensor (None for a raw pointer), ..., "stats": {pixels, hits, stale, textured, minified, anisotropic, taps,
+        kernel_ms}}."""
+        planes = tuple(planes)
+        out = dict(out or {})
+        for name in list(planes) + list(out):
+            if name not in _lib.SURFACE_ANISO_PLANES:
+                raise ValueError(f"surfaceAnisoPlanes: unknown plane {name!r} (one of {', '.join(_lib.SURFACE_ANISO_PLANES)})")
+        if any(name not in planes for name in out):
+            raise ValueError("surfaceAnisoPlanes: `out` names a plane that `planes` does not")
+        if not planes:
+            raise ValueError("surfaceAnisoPlanes: no plane asked for")
+        if int(max_aniso) != max_aniso or not 1 <= int(max_aniso) <= 16:
+            raise ValueError(f"surfaceAnisoPlanes: max_aniso must be an integer in 1..16, not {max_aniso!r}")
+        desc = _lib.SurfaceAnisoDesc()
+        is_tensor = lambda t: t is not None and not isinstance(t, int)  # noqa: E731 (a raw pointer or None: no shape to check)
+        nbytes = self.textureMipsLayout()[1] if mips is not None else 0
+        widths = dict(_lib.SURFACE_ANISO_PLANES, hit=8, prim_texcoords=(self.vertexCount()[1] if is_tensor(prim_texcoords) else 0, 6), mips=(nbytes // 16, 4))
+        self._bind_planes("surfaceAnisoPlanes", desc, dict(hit=hit, prim_texcoords=prim_texcoords, mips=mips), widths, ("hit",))
+        desc.mips_bytes = nbytes
+        result = self._bind_planes("surfaceAnisoPlanes", desc, {name: out.get(name) for name in planes}, widths, outputs=planes, alloc=planes)
+        m = self._bind_mask("surfaceAnisoPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.footprint_scale = float(footprint_scale)
+        desc.max_aniso = int(max_aniso)
+        desc.flags = 0
+        return self._run_pass("pt_surface_aniso_planes", desc, _lib.SurfaceAnisoStats(), result)
+
     def evalTable(self, which, inp: np.ndarray, out_width: int, material=None, bsdf_mode=PT_BSDF_DISNEY) -> np.ndarray:
         inp = np.ascontiguousarray(inp, np.float32)
         n = inp.shape[0]
