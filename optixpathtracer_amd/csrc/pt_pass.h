@@ -90,11 +90,46 @@ static ViewParams pass_views(const pt_ctx* ctx) {
 // before the temporaries are freed on every path, a failed one included.
 #define PASS_SLOT_BYTES (PASS_SLOTS * 8 * sizeof(unsigned long long))
 namespace {
+// The counter words of the passes, recycled: a pass that allocated and freed its own waited, in hipFree, for every stream of the device —
+// the caller's included, which have nothing to do with a pass.  A block goes back to the list when its pass is over and is never freed: a
+// few KiB for every pass that ever ran at the same time on a device.
+struct PassCounterBlock {
+    int device;
+    size_t bytes;
+    uint8_t* ptr;
+};
+struct PassCounterPool {
+    std::mutex mu;
+    std::vector<PassCounterBlock> idle;
+    // the caller has made `device` current
+    hipError_t take(int device, size_t bytes, PassCounterBlock* out) {
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            for (size_t i = 0; i < idle.size(); ++i)
+                if (idle[i].device == device && idle[i].bytes >= bytes) {
+                    *out = idle[i];
+                    idle.erase(idle.begin() + (ptrdiff_t)i);
+                    return hipSuccess;
+                }
+        }
+        *out = PassCounterBlock{device, bytes, nullptr};
+        return dalloc(&out->ptr, bytes);
+    }
+    void give(const PassCounterBlock& b) {
+        std::lock_guard<std::mutex> lock(mu);
+        idle.push_back(b);
+    }
+};
+inline PassCounterPool& pass_counter_pool() {
+    static PassCounterPool pool;
+    return pool;
+}
 struct PassRun {
     pt_ctx* ctx = nullptr;
     DevScope tmp; // destroyed after ~PassRun has waited
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint8_t* d_counters = nullptr; // the pass's counter words, zeroed
+    PassCounterBlock block{0, 0, nullptr}; // where they live (pass_counter_pool)
     const uint32_t* pixels = nullptr;
     uint32_t n = 0;
     float ms = 0.f;
@@ -106,7 +141,10 @@ struct PassRun {
         ctx = c;
         const int rc = subset_open(ctx, fn, false, 0);
         if (rc) return rc;
-        if (counter_bytes) CK(tmp.alloc(&d_counters, counter_bytes));
+        if (counter_bytes) {
+            CK(pass_counter_pool().take(ctx->device, counter_bytes, &block));
+            d_counters = block.ptr;
+        }
         CK(tmp.event(&ev0));
         CK(tmp.event(&ev1));
         live = true;
@@ -154,6 +192,7 @@ struct PassRun {
     }
     ~PassRun() {
         if (live) hipStreamSynchronize(ctx->stream); // nothing of the call may still run when its temporaries go
+        if (block.ptr) pass_counter_pool().give(block);
     }
 };
 } // namespace

@@ -4,12 +4,14 @@
 #include "pt_surface_lod.h"
 
 // The context keeps its texture records on the device only (DevTex: w, h next to the tiles' address); they never change after pt_create.
-// Every size below comes from them, so no level address depends on anything the caller passes.
+// Every size below comes from them, so no level address depends on anything the caller passes.  They are fetched on the context's stream:
+// a blocking hipMemcpy runs on the null stream and made every call wait for whatever the caller had enqueued there.
 static int lod_textures(pt_ctx* ctx, std::vector<DevTex>& tex) {
     tex.resize(ctx->d_tex_pixels.size());
     if (tex.empty()) return PT_OK;
     CK(hipSetDevice(ctx->device));
-    CK(hipMemcpy(tex.data(), ctx->d_textures, sizeof(DevTex) * tex.size(), hipMemcpyDeviceToHost));
+    CK(hipMemcpyAsync(tex.data(), ctx->d_textures, sizeof(DevTex) * tex.size(), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
 static int lod_layout_of(pt_ctx* ctx, const char* fn, std::vector<DevTex>& tex, std::vector<uint32_t>& dims, size_t* bytes) {

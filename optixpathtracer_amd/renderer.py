@@ -295,7 +295,8 @@ class SampleRenderer:
 
     def setViewCameras(self, cameras):
         """New cameras for the current views, rectangles unchanged (the per-frame call): a list of Cameras, an (n, 12) array of eye, U, V, W
-        rows, or a CUDA float32 torch tensor of that shape on the context's GPU, which is read on the device (pt_set_view_cameras_device)."""
+        rows, or a CUDA float32 torch tensor of that shape on the context's GPU, which is read on the device (pt_set_view_cameras_device)
+        after torch's current stream has been synchronised on the host."""
         if _is_torch_tensor(cameras):
             import torch
 
@@ -530,7 +531,8 @@ class SampleRenderer:
     def updateMeshesDevice(self, vertices, rebuild: bool = False) -> float:
         """updateMeshes with the vertices in GPU memory (pt_update_meshes_device): {mesh_index: tensor} with CUDA float32 contiguous
         (num_vertices, 3) torch tensors on the context's device, or {mesh_index: (device pointer, num_vertices)}.  A tensor's current
-        torch stream is synchronised first; a raw pointer's producer must be complete.  Non-finite coordinates are found on the GPU."""
+        torch stream is synchronised on the host first; a raw pointer gets no synchronise: its producer must be complete, or ordered with
+        waitEvent(event recorded behind it) before the call.  Non-finite coordinates are found on the GPU."""
         ups, n, keep = _device_updates(vertices, getattr(self, "_device", 0))
         ms = C.c_double()
         self._ck(self._L.pt_update_meshes_device(self._ctx, ups if n else None, n, _lib.PT_UPDATE_REBUILD if rebuild else _lib.PT_UPDATE_REFIT, C.byref(ms)),
@@ -577,7 +579,8 @@ class SampleRenderer:
         (float32 (n, 3)) and "record", the (n, 8) tensor itself; prim is -1 for a miss (t = the ray's tmax) and -2 for an invalid ray (a
         non-finite word, a direction of length zero).  For an any-hit query the int32 tensor.  None when `out` was a raw pointer.
         Ordering is on the device: for a tensor, the library's stream waits for an event recorded on torch's current stream (no host
-        synchronise); a raw pointer's producer must be complete.  wait=True returns when the results are complete, wait=False after
+        synchronise); with raw pointers for both rays and out nothing is waited for: their producers must be complete, or ordered with
+        waitEvent(event recorded behind them) before the call.  wait=True returns when the results are complete, wait=False after
         enqueueing (several queries may be queued): torch's current stream is then made to wait for the query, so torch work enqueued
         afterwards on that stream sees the results; queryWait() waits on the host and returns the statistics (after a wait=True call
         they are in self.queryStats)."""
