@@ -18,8 +18,10 @@ With --lod step 2 is surfaceLodPlanes: the albedo filtered over the pixel's foot
 which is built once, before the loop), so a minified texture does not alias in the plane the loop divides by and multiplies back in.
 With --aniso N (which implies --lod) it is surfaceAnisoPlanes: up to N such lookups along the footprint's longer axis, so a ground seen at a
 grazing angle is not blurred across that axis.
+With --edge-aa a step 9 follows, the last pass before display: edgeAaPlanes blends the silhouettes, creases and depth steps of the displayed
+frame — which shows the surface under each pixel's centre alone — by the share of the pixel that the nearer triangle's edge cuts off.
 
-  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--out-dir .]
+  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--edge-aa] [--out-dir .]
 """
 import argparse
 import os
@@ -64,6 +66,7 @@ def main():
     ap.add_argument("--lod", action="store_true", help="footprint-filtered albedo (surfaceLodPlanes) instead of the point lookup of surfacePlanes")
     ap.add_argument("--aniso", type=int, default=0, metavar="N", help="implies --lod: up to N (1..16) lookups along the footprint's longer axis (surfaceAnisoPlanes)")
     ap.add_argument("--footprint-scale", type=float, default=1.0, help="with --lod: 1 = the pixel's own footprint")
+    ap.add_argument("--edge-aa", action="store_true", help="geometric edge antialiasing (edgeAaPlanes) as the last pass before display")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args()
     args.lod = args.lod or args.aniso > 0
@@ -85,6 +88,7 @@ def main():
     gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2)) for _ in range(2)]
     history, moments, length = [planes(4) for _ in range(2)], [planes(2) for _ in range(2)], [planes(1) for _ in range(2)]
     variance, filtered, scratch, albedo, final = planes(1), planes(4), planes(4), planes(4), planes(4)
+    modulated = planes(4) if args.edge_aa else None  # step 8's output where step 9 follows it
     frame = torch.zeros((h, w), dtype=torch.int32, device=dev)
     accum = sample.deviceBuffer(R.PT_BUF_ACCUM)
     table = sample.copyTexcoordsDevice()  # the scene's texcoords per primitive: once, whatever moves later
@@ -114,12 +118,17 @@ def main():
         assert c["stats"]["lost"] == 0  # the plan samples every block that holds a pixel the carry could not carry
         f = sample.filterPlanes(history[o], cur["hit"], cur["position"], variance=variance, length=length[o], out=filtered, scratch=scratch,
                                 iterations=args.iterations, sigma_lum=args.sigma_lum, min_length=args.min_length)
-        m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=frame)
+        if args.edge_aa:
+            m = sample.modulatePlanes(filtered, albedo=albedo, out=modulated)
+            e = sample.edgeAaPlanes(modulated, cur["hit"], cur["position"], out=final, frame=frame)["stats"]
+        else:
+            m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=frame)
         ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
         print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
               f"{ss['textured']} of {ss['hits']} hits textured{', %d minified' % ss['minified'] if args.lod else ''}{', %d taps' % ss['taps'] if args.aniso else ''}; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
               f"plan {ps['kernel_ms']:.3f} ms, colour {sample.stats()['render_ms']:.2f} ms, temporal {ts['kernel_ms']:.3f} ms, "
-              f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms")
+              f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms"
+              + (f", edge aa {e['kernel_ms']:.3f} ms ({e['blended']} of {e['boundary']} boundary pixels blended)" if args.edge_aa else ""))
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_final.npy"), final.cpu().numpy())
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_frame.npy"), frame.cpu().numpy().view(np.uint32))
     print(f"wrote adaptive_svgf_albedo_final.npy and adaptive_svgf_albedo_frame.npy to {args.out_dir}")

@@ -15,10 +15,12 @@ Per frame, on `hi`:
   9. surfacePlanes (surfaceLodPlanes with --lod, surfaceAnisoPlanes with --aniso N): the albedo under every display pixel;
  10. upsamplePlanes: the low-resolution irradiance on the display's pixels — four taps of the same surface where there are four, fewer
      where an edge is near, the ring around them where there is none (rescued), another surface's value where that fails too (orphans);
- 11. modulatePlanes with the full-resolution albedo: the displayed frame.
+ 11. modulatePlanes with the full-resolution albedo: the displayed frame;
+ 12. with --edge-aa, edgeAaPlanes as the last pass before display: the silhouettes, creases and depth steps of that frame, which show the
+     surface under each pixel's centre alone, blended by the share of the pixel that the nearer triangle's edge cuts off.
 `hi` never renders a colour sample.
 
-  python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--out-dir .]
+  python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa] [--out-dir .]
 """
 import argparse
 import os
@@ -51,11 +53,13 @@ def orbit(cam, angle):
 class UpsampledLoop:
     """The two renderers and every plane of the loop, allocated once; frame(k, prev, cam) runs one frame and returns its figures."""
 
-    def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32):
+    def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
+                 edge_aa=False):
         import torch
 
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
         self.size, self.scale, self.lod, self.aniso = tuple(size), int(scale), lod, int(aniso)
+        self.edge_aa = bool(edge_aa)
         w, h = self.size
         if w % self.scale or h % self.scale:
             raise SystemExit(f"--size {w} {h} is not a multiple of --scale {self.scale}")
@@ -80,6 +84,7 @@ class UpsampledLoop:
         self.variance, self.filtered, self.scratch, self.lo_albedo = planes(lh, lw, 1), planes(lh, lw, 4), planes(lh, lw, 4), planes(lh, lw, 4)
         self.hi_gbuf = dict(hit=planes(h, w, 8), position=planes(h, w, 4))
         self.albedo, self.upsampled, self.weight, self.final = planes(h, w, 4), planes(h, w, 4), planes(h, w, 1), planes(h, w, 4)
+        self.modulated = planes(h, w, 4) if self.edge_aa else None  # step 11's output where step 12 follows it
         self.frame_rgba8 = torch.zeros((h, w), dtype=torch.int32, device="cuda:0")
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
@@ -119,13 +124,19 @@ class UpsampledLoop:
         S = self._albedo(hi, self.hi_gbuf["hit"], self.albedo)
         u = hi.upsamplePlanes(self.filtered, cur["hit"], cur["position"], self.hi_gbuf["hit"], self.hi_gbuf["position"], self.scale, out=self.upsampled,
                               weight_out=self.weight)["stats"]
-        m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=self.frame_rgba8)["stats"]
+        if self.edge_aa:
+            m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.modulated)["stats"]
+            e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=self.frame_rgba8)["stats"]
+        else:
+            m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=self.frame_rgba8)["stats"]
+            e = dict(kernel_ms=0.0, boundary=0, blended=0)
         t2 = time.perf_counter()
         return dict(frame_ms=(t2 - t0) * 1e3, lo_ms=(t1 - t0) * 1e3, hi_ms=(t2 - t1) * 1e3, sampled=p["stats"]["sampled"], blocks=p["stats"]["blocks"],
                     rendered=rendered, colour_ms=lo.stats()["render_ms"], lo_gbuffer_ms=g["kernel_ms"], lo_surface_ms=s["kernel_ms"],
                     plan_ms=p["stats"]["kernel_ms"], temporal_ms=t["kernel_ms"], carry_ms=c["kernel_ms"], filter_ms=f["kernel_ms"],
                     gbuffer_ms=G["kernel_ms"], surface_ms=S["kernel_ms"], upsample_ms=u["kernel_ms"], modulate_ms=m["kernel_ms"],
-                    pixels=u["pixels"], full=u["full"], rescued=u["rescued"], orphans=u["orphans"])
+                    pixels=u["pixels"], full=u["full"], rescued=u["rescued"], orphans=u["orphans"], edge_aa_ms=e["kernel_ms"], boundary=e["boundary"],
+                    blended=e["blended"])
 
     def close(self):
         self.lo.close()
@@ -141,11 +152,12 @@ def main(argv=None):
     ap.add_argument("--spp", type=int, default=1)
     ap.add_argument("--lod", action="store_true", help="footprint-filtered albedo (surfaceLodPlanes) at both resolutions")
     ap.add_argument("--aniso", type=int, default=0, metavar="N", help="implies --lod: up to N (1..16) lookups along the footprint's longer axis (surfaceAnisoPlanes)")
+    ap.add_argument("--edge-aa", action="store_true", help="geometric edge antialiasing (edgeAaPlanes) as the last pass before display")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
     make, cam0 = SCENES[args.scene]
-    loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp)
+    loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp, edge_aa=args.edge_aa)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -154,7 +166,9 @@ def main(argv=None):
               f"G-buffer {x['lo_gbuffer_ms']:.3f} ms, surface {x['lo_surface_ms']:.3f} ms, plan {x['plan_ms']:.3f} ms, colour {x['colour_ms']:.2f} ms, "
               f"temporal {x['temporal_ms']:.3f} ms, carry {x['carry_ms']:.3f} ms, filter {x['filter_ms']:.3f} ms; at {w} x {h}: G-buffer "
               f"{x['gbuffer_ms']:.3f} ms, surface {x['surface_ms']:.3f} ms, upsample {x['upsample_ms']:.3f} ms, modulate {x['modulate_ms']:.3f} ms; "
-              f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; frame {x['frame_ms']:.2f} ms")
+              f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; "
+              + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
+              + f"frame {x['frame_ms']:.2f} ms")
     np.save(os.path.join(args.out_dir, "upsampled_svgf_final.npy"), loop.final.cpu().numpy())
     np.save(os.path.join(args.out_dir, "upsampled_svgf_frame.npy"), loop.frame_rgba8.cpu().numpy().view(np.uint32))
     print(f"wrote upsampled_svgf_final.npy and upsampled_svgf_frame.npy to {args.out_dir}")

@@ -29,6 +29,8 @@
  *     points (pt_pack, pt_unpack, pt_render_device), and after pt_pack_wait / pt_display_sync for the
  *     asynchronous ones; to consume it on another stream without a host wait, enqueue the consumer
  *     on pt_stream(ctx) or make that stream wait for an event recorded on pt_stream(ctx).
+ * pt_edge_aa_planes takes DEVICE pointers under the same contract: it is one more entry point of the list above (its ordering case
+ * stands with its other GPU tests, in tests/test_gpu_edge_aa.py).
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -38,7 +40,7 @@
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
  * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
  * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
- * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes.  A
+ * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes, pt_edge_aa_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -1415,6 +1417,83 @@ typedef struct pt_upsample_desc {
 } pt_upsample_desc;
 typedef struct pt_upsample_stats { uint64_t pixels, hits, full, rescued, orphans; double kernel_ms; } pt_upsample_stats;
 int pt_upsample_planes(pt_ctx* ctx, const pt_upsample_desc* desc, pt_upsample_stats* stats /* may be NULL */);
+
+/* GEOMETRIC EDGE ANTIALIASING (no reference counterpart): the chain's final image with its silhouettes, creases and depth steps smoothed
+ * from the hit plane alone.  Every plane of the chain describes the surface under the CENTRE of a pixel, so the final image has one-sample
+ * staircases along every edge of the geometry.  Where a pixel and one of its four neighbours show different surfaces, pt_edge_aa_planes
+ * intersects the centre ray of the pixel on the far side with the plane of the NEARER surface's triangle: the barycentric that changes
+ * sign between the two centres gives the place where the triangle's edge crosses the line between them, and a pixel whose own half of that
+ * line is crossed takes the matching share of the neighbour's colour.  No jitter, no history, no second frame: the pass is stateless.
+ * The pixel set, rectangles, views, partitions and pointer checks are exactly pt_motion_planes's; every plane is caller-owned DEVICE memory
+ * of the context's device (4-byte aligned, frame-sized, indexed Y * width + X); block_mask is HOST memory.  No pixel outside the set is
+ * written in any output.  Zero pixels launch nothing and return PT_OK.
+ * The pass reads from the context its CURRENT vertices and indices (so it follows pt_update_meshes* and pt_transform_meshes) and the
+ * cameras: the frame's, or with views the camera and rectangle of the pixel's view (x, y below are then relative to the view's rectangle
+ * and wr, hr are its width and height; otherwise the frame's).  hit[..].prim is compared with the triangle count before any address is
+ * formed from it, for the pixel's record and for a neighbour's alike.
+ * Arithmetic per pixel p of the set — float32 throughout, one rounding per operation, no fused multiply-add, in exactly this order;
+ * float32 NumPy evaluating this reproduces every output bit for bit (tests/edge_aa_ref.py).  dot3, cross3, d(a, b) and, of a primitive
+ * with current vertices p0, p1, p2, e1, e2, n, nn, hgt are as in pt_surface_lod_planes's text; sel_max0 is as in pt_filter_planes.  A
+ * record is a miss when its prim is negative and a hit otherwise (a stale record, prim >= triangles, is a hit here).
+ *   1. c_p = color[p].xyz.  If one of its three words is not finite (exponent-bit test): out[p] = (c_p, 1.0f), edge[p] = (0, 0), done.
+ *   2. Directions k = 0..3 with (dx, dy) = (-1, 0), (+1, 0), (0, -1), (0, +1) and q = p + (dx, dy).  Direction k is a candidate when q lies
+ *      inside p's rectangle; q's 8x8 block is in the call's block set (the rank's blocks that block_mask names); color[q].xyz is finite;
+ *      p and q are not both misses; and p and q are not the same surface.  Same surface: both are hits and either
+ *      hit[q].prim == hit[p].prim, or the chain's test holds from p's side: hit[q].mesh == hit[p].mesh and
+ *      dot3(ng_p, ng_q) >= normal_cos and fabsf(dot3(ng_p, position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t.  A NaN in either
+ *      comparison makes it false: the surfaces differ and the direction stays a candidate.  stats->boundary counts the pixels with at
+ *      least one candidate.
+ *   3. For a candidate, the owner o of the edge is the nearer surface: q if p is a miss; p if q is a miss; otherwise p when
+ *      hit[p].t <= hit[q].t, else q (a NaN on either side makes the comparison false: q owns).  r is the other pixel of the pair.  A stale
+ *      owner record (prim >= triangles) drops the direction.  With the owner's primitive and (x_r, y_r) the local coordinates of r:
+ *         d_r = d((float)x_r + 0.5f, (float)y_r + 0.5f)
+ *         t_r = hgt / dot3(n, d_r);  the direction is dropped unless t_r > 0                                    (a NaN drops it)
+ *         P_r = (d_r * t_r) + eye;  g = P_r - p0
+ *         u_r = dot3(cross3(g, e2), n) / nn;  v_r = dot3(cross3(e1, g), n) / nn
+ *         b_r = ((1.0f - u_r) - v_r, u_r, v_r)
+ *         b_o = (sel_max0((1.0f - u_o) - v_o), sel_max0(u_o), sel_max0(v_o))                                   (u_o, v_o from hit[o])
+ *      For i = 0, 1, 2 in order with b_r[i] < 0 (a NaN fails: that i is skipped): s_i = b_o[i] / (b_o[i] - b_r[i]).  s is the first such
+ *      s_i, replaced by a later one when s_i < s: the smallest, a strict < keeps the first, a NaN s_i never replaces and a first NaN s_i
+ *      is never replaced.  If there is no such i, the direction is dropped.
+ *         dist = (o is p) ? s : 1.0f - s
+ *      The direction has weight w_k = 0.5f - dist when dist < 0.5f; otherwise it is dropped (a NaN fails the comparison and drops it).
+ *      b_o[i] >= 0 > b_r[i], so 0 <= s <= 1 and 0 < w_k <= 0.5.
+ *   4. The direction with the largest w_k wins; a strict > keeps the first.  No direction: out[p] = (c_p, 1.0f), edge[p] = (0, 0).
+ *      Otherwise, with q the winner's neighbour and w its weight: out[p].xyz = c_p + ((c_q - c_p) * w) per component, out[p].w = 1.0f,
+ *      edge[p] = (w, (float)(k + 1)); stats->blended counts these.  In every case, step 1's included, frame_rgba8[p] = make_color(out[p].xyz),
+ *      the frame path's own transform (sRGB, 8 bits, alpha 255).
+ *   5. stats->hits and stats->stale count p's own record, as the surface passes do (prim in range; prim >= triangles).  A zero-area
+ *      owner primitive (nn == 0: t_r is 0 / 0), a ray parallel to the owner's plane or meeting it behind the eye, and non-finite u, v of
+ *      either record all end in a dropped direction through the comparisons above, which a NaN fails.  None of them faults.
+ * What the output means: dist is the place of the owner's edge on the line from p's centre (0) to q's centre (1).  The edge at dist < 0.5
+ * lies in p's own half, and the far side of it, 0.5 - dist of the pixel's width along that line, shows q's surface.  Only the strongest of
+ * the four directions is used: summing several overcorrects at corners.
+ * Overlap: out, edge and frame_rgba8 may overlap nothing (the kernel gathers neighbours of color, so there is no in-place form); the
+ * read-only planes may alias one another.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; color,
+ * hit, position or out NULL; a plane that fails the pointer checks; a forbidden overlap; flags != 0; normal_cos outside [-1, 1] or NaN;
+ * plane_eps negative or not finite.
+ * Ordering and state, as pt_motion_planes and pt_surface_lod_planes: waits for the frames in flight, runs on pt_stream(ctx) under the
+ * STREAM CONTRACT, is complete when it returns, and writes no context state.
+ * stats: pixels processed; hits and stale among them; boundary and blended as above; device time of the pass.
+ * Not part of this interface: jittered or temporal antialiasing; edges that are no triangle edge (interpenetrating surfaces, shadow and
+ * texture edges); sub-pixel triangles; blending with more than one neighbour; an asynchronous variant; a pt_multi_* wrapper (per-rank calls
+ * work, and a neighbour in another rank's block does not count). */
+enum pt_edge_aa_flags { PT_EDGE_AA_RESERVED = 0 };  /* no flag defined yet: flags must be 0 */
+typedef struct pt_edge_aa_desc {
+    const float* color;        /* w*h x 4: the image to antialias (pt_modulate_planes's out); .w is ignored; required */
+    const void*  hit;          /* w*h x pt_hit, this frame (pt_render_gbuffer); required */
+    const float* position;     /* w*h x 4, this frame; required */
+    float*    out;             /* w*h x 4; required, exclusive */
+    float*    edge;            /* w*h x 2 or NULL, exclusive: the weight w and the direction code k + 1 (0, 0 where nothing was blended) */
+    uint32_t* frame_rgba8;     /* w*h or NULL, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    float     normal_cos;      /* [-1,1] */
+    float     plane_eps;       /* finite, >= 0 */
+    uint32_t  flags;           /* 0 */
+} pt_edge_aa_desc;
+typedef struct pt_edge_aa_stats { uint64_t pixels, hits, stale, boundary, blended; double kernel_ms; } pt_edge_aa_stats;
+int pt_edge_aa_planes(pt_ctx* ctx, const pt_edge_aa_desc* desc, pt_edge_aa_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -29,7 +29,7 @@ EXPORTS = [
     "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes", "pt_temporal_moments", "pt_modulate_planes",
     "pt_sample_plan", "pt_temporal_carry", "pt_copy_texcoords_device", "pt_surface_planes",
     "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes", "pt_surface_aniso_planes",
-    "pt_upsample_planes",
+    "pt_upsample_planes", "pt_edge_aa_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -209,6 +209,24 @@ class UpsampleStats(C.Structure):  # pt_upsample_stats
 # the planes of pt_upsample_planes: float32 words per pixel (the lo_ planes at the low resolution, the others frame-sized)
 UPSAMPLE_PLANES = {"lo_color": 4, "lo_hit": 8, "lo_position": 4, "hit": 8, "position": 4, "out": 4, "weight_out": 1}
 UPSAMPLE_OUTPUTS = ("out", "weight_out")
+
+
+class EdgeAaDesc(C.Structure):  # pt_edge_aa_desc
+    _fields_ = [("color", C.c_void_p), ("hit", C.c_void_p), ("position", C.c_void_p), ("out", C.c_void_p), ("edge", C.c_void_p),
+                ("frame_rgba8", C.c_void_p), ("block_mask", C.c_void_p), ("normal_cos", C.c_float), ("plane_eps", C.c_float), ("flags", C.c_uint32)]
+
+
+class EdgeAaStats(C.Structure):  # pt_edge_aa_stats
+    _fields_ = [("pixels", C.c_uint64), ("hits", C.c_uint64), ("stale", C.c_uint64), ("boundary", C.c_uint64), ("blended", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_edge_aa_planes: 32-bit words per pixel
+EDGE_AA_PLANES = {"color": 4, "hit": 8, "position": 4, "out": 4, "edge": 2, "frame_rgba8": 1}
+EDGE_AA_OUTPUTS = ("out", "edge", "frame_rgba8")
 
 
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
@@ -506,6 +524,7 @@ def load_library() -> C.CDLL:
     L.pt_surface_lod_planes.argtypes = [vp, C.POINTER(SurfaceLodDesc), C.POINTER(SurfaceLodStats)]
     L.pt_surface_aniso_planes.argtypes = [vp, C.POINTER(SurfaceAnisoDesc), C.POINTER(SurfaceAnisoStats)]
     L.pt_upsample_planes.argtypes = [vp, C.POINTER(UpsampleDesc), C.POINTER(UpsampleStats)]
+    L.pt_edge_aa_planes.argtypes = [vp, C.POINTER(EdgeAaDesc), C.POINTER(EdgeAaStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

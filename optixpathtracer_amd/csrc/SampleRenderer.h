@@ -403,6 +403,15 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // Geometric edge antialiasing, the last pass before display (pt_edge_aa_planes): where a pixel and a neighbour show different surfaces,
+    // the nearer triangle's edge is located between the two pixel centres and the pixel takes the matching share of the neighbour's colour.
+    // d.out may not be d.color.  Returns the pixel, boundary and blended counts and the device time.
+    pt_edge_aa_stats edgeAaPlanes(const pt_edge_aa_desc& d, pt_edge_aa_stats* stats = nullptr) {
+        pt_edge_aa_stats s{};
+        ck(pt_edge_aa_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

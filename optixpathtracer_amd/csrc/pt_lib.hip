@@ -19,3 +19,4 @@
 #include "pt_surface.hip"
 #include "pt_surface_lod.hip"
 #include "pt_upsample.hip"
+#include "pt_edge_aa.hip"

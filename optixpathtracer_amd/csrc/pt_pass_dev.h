@@ -60,6 +60,12 @@ PT_DEV bool pass_reachable(const PassPixel& p, const uint8_t* inset, uint32_t nb
     return inset[(uint32_t)(qy >> 3) * nbx + (uint32_t)(qx >> 3)] != 0;
 }
 
+// The header's d(a, b): the camera ray through the point (a, b), in pixels, of a rectangle wr x hr (k_surface_lod, k_surface_aniso, k_edge_aa)
+PT_DEV v3 lod_ray(v3 U, v3 V, v3 W, float a, float b, float wr, float hr) {
+    const float dx = 2.0f * (a / wr) - 1.0f, dy = 2.0f * (b / hr) - 1.0f;
+    return add3(add3(scl3(U, dx), scl3(V, dy)), W);
+}
+
 // ------------------------------------------------------------------ the surface key and the chain's "same surface"
 // A pt_hit is t, u, v, prim | mesh, ng.xyz: a negative primitive word is a miss.  The key is the pixel's side of the tests; a tap q of a
 // hit is the same surface when same_facet and same_plane hold.  They are two functions so that a kernel orders its loads itself, cheapest

@@ -126,10 +126,6 @@ PT_DEV float4 lod_level(const SurfaceLodArgs& a, const DevTex& tx, int tid, uint
     const float4* T = a.mips + a.level_first[(uint32_t)tid * LOD_MAX_LEVELS + k];
     return lod_tex2d(T, max(1, tx.w >> k), max(1, tx.h >> k), s, t);
 }
-PT_DEV v3 lod_ray(v3 U, v3 V, v3 W, float a, float b, float wr, float hr) {
-    const float dx = 2.0f * (a / wr) - 1.0f, dy = 2.0f * (b / hr) - 1.0f;
-    return add3(add3(scl3(U, dx), scl3(V, dy)), W);
-}
 
 // The footprint of one textured hit, the header's text from w0 to rx, ry: what k_surface_lod and k_surface_aniso share.  prim is in range
 // and tid >= 0 (the caller has tested both).

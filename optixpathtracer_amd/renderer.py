@@ -873,6 +873,28 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_modulate_planes", desc, _lib.ModulateStats(), result)
 
+    def edgeAaPlanes(self, color, hit, position, out=None, edge=None, frame=None, mask=None, normal_cos=0.9, plane_eps=0.01) -> dict:
+        """Geometric edge antialiasing, the last pass before display: where a pixel and one of its four neighbours show different surfaces,
+        the nearer surface's triangle edge is located between the two pixel centres from the hit plane, the current vertices and the
+        pixel's camera, and the pixel takes the matching share of that neighbour's colour (pt_edge_aa_planes, include/pt_amd.h: the rule,
+        in full).  Stateless: no jitter, no history.
+
+        color (h, w, 4: modulatePlanes's out), hit (h, w, 8) and position (h, w, 4) (renderGBuffer's planes of this frame) are CUDA float32
+        tensors on the context's device — dense, any 4-byte-aligned storage offset — or raw device pointers.  out (h, w, 4) is allocated
+        with torch, zero-filled, when None; it may NOT be `color` (the pass reads neighbours).  edge ((h, w, 2), optional) receives the
+        blend weight and the direction code 1..4 (0, 0 where nothing was blended); frame (int32 (h, w) or uint8 (h, w, 4)) is optional.
+        Pixels outside the views, the mask or the rank's partition are not written, and a neighbour there never counts.  mask: 8x8 blocks
+        as renderMask takes them, None = every block.  normal_cos, plane_eps: the chain's "same surface" test, as filterPlanes.
+        Ordering is on the device, as temporalMoments.  Returns {"out", "edge", "frame_rgba8": the tensor (None for a raw pointer or an
+        absent plane), "stats": {pixels, hits, stale, boundary, blended, kernel_ms}}."""
+        given = dict(color=color, hit=hit, position=position, out=out, edge=edge, frame_rgba8=frame)
+        desc = _lib.EdgeAaDesc()
+        result = self._bind_planes("edgeAaPlanes", desc, given, _lib.EDGE_AA_PLANES, ("color", "hit", "position"), _lib.EDGE_AA_OUTPUTS, alloc=("out",))
+        m = self._bind_mask("edgeAaPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.normal_cos, desc.plane_eps = float(normal_cos), float(plane_eps)
+        desc.flags = 0
+        return self._run_pass("pt_edge_aa_planes", desc, _lib.EdgeAaStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
