@@ -104,6 +104,48 @@ PT_HD float pt_cosf(float x) {
     return c;
 }
 
+/* A whole latitude circle under a tangent plane.  With (st, ct) = pt_sincosf(theta) and (sp, cp) = pt_sincosf(phi), the
+ * direction d(phi) = (-st*cp, ct, -st*sp) has, for a normal n of length <= 1 + 2^-20,
+ *     d . n  <=  ct*ny + |st| * sqrt(nx^2 + nz^2) * sqrt(sp^2 + cp^2)          (Cauchy-Schwarz on the horizontal part)
+ * for every phi.  pt_below_horizon evaluates the right-hand side with sqrt(sp^2 + cp^2) taken as 1 and asks for it to lie below
+ * -PT_HORIZON_MARGIN; then the three-product, two-sum float evaluation of d . n (in any order, without contraction) is <= 0 for
+ * EVERY phi.  What the margin has to cover, with u = 2^-24:
+ *   - sp^2 + cp^2 above 1: each polynomial is within 2 ulp (2.4e-7) of the true value, so sqrt(sp^2 + cp^2) <= 1 + 4e-7;
+ *     the products st*cp, st*sp round once more (u): together <= 5e-7 * |st| * sqrt(nx^2 + nz^2) <= 5e-7;
+ *   - the float evaluation of d . n: <= 3u * (|dx nx| + |dy ny| + |dz nz|) <= 3u * sqrt(3) = 3.1e-7;
+ *   - the float evaluation of the bound (seven operations, the longest chain five): <= 5u * (|ct ny| + |st| h) <= 5u * sqrt(2)
+ *     = 4.3e-7; a square that underflows (|nx| < 2^-63) moves h by less than 2^-62.
+ * Sum: 1.3e-6.  The margin is 1e-4: 75 times that, and the rows it gives up are a band of 1e-4 rad around the circle that
+ * touches the plane.  A NaN in n makes the comparison false; n = 0 gives 0 < -margin, false.
+ * (tests/horizon_host.cpp checks the claim over whole probes, every row and column.) */
+#define PT_HORIZON_MARGIN 1.0e-4f
+PT_HD int pt_below_horizon(float st, float ct, float nx, float ny, float nz) {
+    return ct * ny + pt_fabsf(st) * sqrtf(nx * nx + nz * nz) < -PT_HORIZON_MARGIN;
+}
+
+/* The same for an ARC of the circle: the columns c0 .. c1 of a probe `width` columns wide, phi(c) = c / width * 2 pi.  The horizontal part
+ * of d . n is g(phi) = -st * (cos(phi) nx + sin(phi) nz), a sinusoid of amplitude a = |st| sqrt(nx^2 + nz^2), so for every phi of the arc
+ *     d . n  <=  ct*ny + g(phi_m) + a * |phi - phi_m|  <=  ct*ny + g(phi_m) + a * dphi
+ * with phi_m the arc's middle and dphi its half width.  pt_column_arc gives (sin, cos)(phi_m) and dphi for columns c0 .. c1, phi_m by the
+ * expression the sampler uses for a column (u = c / width, phi = u * 2 * pi); pt_below_horizon_arc holds when that bound, or the whole
+ * circle's, is below -PT_HORIZON_MARGIN.  On top of the list above the margin covers: the float value of a column's phi against
+ * 2 pi c / width (three roundings of a number <= 6.3 and the float pi: 2e-6 rad, at both ends: <= 4e-6 * a), sin / cos of phi_m and of the
+ * column (2.4e-7 each on |nx| + |nz| <= 1.42, twice: 1e-6), the rounding of dphi (3u relative) and of the ten operations of the bound on
+ * magnitudes that sum to at most 9 when dphi is a whole turn (4.3e-6).  Sum with the above: 1.1e-5, a ninth of the margin. */
+PT_HD void pt_column_arc(int c0, int c1, int width, float* spm, float* cpm, float* dphi) {
+    const float um = (float)(c0 + c1) * 0.5f / (float)width;
+    const float phim = um * 2.0f * PT_PIF;
+    pt_sincosf(phim, spm, cpm);
+    *dphi = (float)(c1 - c0) * 0.5f / (float)width * 2.0f * PT_PIF;
+}
+PT_HD int pt_below_horizon_arc(float st, float ct, float spm, float cpm, float dphi, float nx, float ny, float nz) {
+    const float a = pt_fabsf(st) * sqrtf(nx * nx + nz * nz);
+    const float v = ct * ny;
+    const float circle = v + a;
+    const float arc = v + (-st * cpm * nx + -st * spm * nz) + a * dphi;
+    return (circle < arc ? circle : arc) < -PT_HORIZON_MARGIN;
+}
+
 /* asin on [-1,1] */
 PT_HD float pt_asinf(float xx) {
     float a = pt_fabsf(xx);

@@ -1299,6 +1299,9 @@ struct ChainPass {
         ShadeParams sp{ctx->bvh.tris8, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin, q, next, shadow,
                        out ? out->rayO : nullptr, out ? out->rayD : nullptr, out ? out->thr : nullptr, out ? out->rf : nullptr, aov, first,
                        out ? out->c0 : nullptr, out ? out->c1 : nullptr, 0, 0};
+#ifdef PT_DEBUG_STATS
+        sp.dbg = ctx->dbg;
+#endif
         return sp;
     }
     void closest(int k, QView q, int b, unsigned long long* dbg) {
@@ -1477,7 +1480,8 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
             for (hipEvent_t e : *before_resolve) hipStreamWaitEvent(bs.stream, e, 0);
         {
             SpanGuard g(ctx, CLS_OTHER, bs.stream);
-            // counters[last_bounce+1] holds paths that would have continued: not traced, not counted
+            // counters[last_bounce+1] holds the count of the paths that would have continued (no entries: shade_path's queue_count): not traced,
+            // not counted as rays — as shaded hits they are, the count is the last term of k_accum_stats' sum with count_hits = 1
             if (!fused) hipLaunchKernelGGL(k_accum_stats, dim3(1), dim3(64), 0, bs.stream, bs.counters, nq, last_bounce + 1, 1, bs.totals);
             if (job)
                 hipLaunchKernelGGL(k_resolve_region, dim3((job->nl + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, job->var, job->l0, job->nl);
@@ -1793,6 +1797,9 @@ static int debug_report(pt_ctx* ctx) {
         if (h[53] + h[54] + h[55] + h[56]) // -DPT_DEBUG_WAVELOG=3 builds
             fprintf(stderr, "[pt_render] traversal iterations by lanes active at their start (<=8 | <=16 | <=32 | more): %llu %llu %llu %llu; cycles: %llu %llu %llu %llu\n",
                     h[53], h[54], h[55], h[56], h[57], h[58], h[59], h[60]);
+        if (h[61]) // PT_DEBUG_STATS builds
+            fprintf(stderr, "[pt_render] closest-hit programs %llu, light sample's arc below the surface (column search skipped) %llu = %.2f %%, of them the whole latitude circle %llu = %.2f %%\n",
+                    h[61], h[62], 100.0 * (double)h[62] / (double)h[61], h[47], 100.0 * (double)h[47] / (double)h[61]);
         if (h[48])
             fprintf(stderr, "[pt_render] camera packets %llu: node steps %.1f per packet (%.1f lanes hit something), triangle tests %.1f per packet (%.1f lanes inside the leaf's box)\n",
                     h[48], (double)h[49] / h[48], h[49] ? (double)h[52] / h[49] : 0.0, (double)h[50] / h[48], h[50] ? (double)h[51] / h[50] : 0.0);

@@ -189,13 +189,19 @@ PT_DEV float fresnel_dielectric(float VDotN, float etaI, float etaT) {
 }
 
 // BSDFPdf :151-192 (Lambert :127-133)
+// the value for dot(L, n) <= 0, which depends on the material alone: shade_path asks for it before the light sample's direction exists
+template <int MODE>
+PT_DEV float bsdf_pdf_back(const pt_material& mat) {
+    if (MODE == PT_BSDF_LAMBERT) return 0.0f;
+    float bsdfPdf = 0.0f;
+    float brdfPdf = kInv2Pi * mat.subsurface * 0.5f;
+    return lerpf(brdfPdf, bsdfPdf, mat.transmission);
+}
 template <int MODE>
 PT_DEV float bsdf_pdf(const pt_material& mat, float etaI, float etaO, v3 n, v3 V, v3 L) {
     if (MODE == PT_BSDF_LAMBERT) return (dot3(L, n) <= 0.0f) ? 0.0f : kInv2Pi;
     if (dot3(L, n) <= 0.0f) {
-        float bsdfPdf = 0.0f;
-        float brdfPdf = kInv2Pi * mat.subsurface * 0.5f;
-        return lerpf(brdfPdf, bsdfPdf, mat.transmission);
+        return bsdf_pdf_back<MODE>(mat);
     } else {
         float F = fresnel_dielectric(dot3(n, V), etaI, etaO);
         const float a = fmaxf(0.001f, mat.roughness);
@@ -421,13 +427,22 @@ PT_DEV void probe_dir_to_uv(v3 dir, float& u, float& v) {
     v = theta * kInvPi;
 }
 // :48-58
-PT_DEV v3 probe_uv_to_dir(float u, float v) {
+// in two steps: the row fixes the latitude (sin and cos of theta: wi.y and the length of wi's horizontal part), the column the longitude —
+// ProbeSample knows the first after its row search, before any column line is fetched (probe_row_sincos, shade_path)
+PT_DEV void probe_v_sincos(float v, float& st, float& ct) {
     float theta = v * kPi;
-    float phi = u * 2.0f * kPi;
-    float st, ct, sp, cp;
     pt_sincosf(theta, &st, &ct);
+}
+PT_DEV v3 probe_u_to_dir(float u, float st, float ct) {
+    float phi = u * 2.0f * kPi;
+    float sp, cp;
     pt_sincosf(phi, &sp, &cp);
     return mk3(-st * cp, ct, -st * sp);
+}
+PT_DEV v3 probe_uv_to_dir(float u, float v) {
+    float st, ct;
+    probe_v_sincos(v, st, ct);
+    return probe_u_to_dir(u, st, ct);
 }
 PT_DEV int clampi(int v, int a, int b) { return v < a ? a : (v > b ? b : v); }
 // :61-67
@@ -517,7 +532,23 @@ PT_DEV void probe_search_begin(const DevProbe& p, const ProbeMarg& pm, Rng& rand
 // every non-decreasing row (and for an all-NaN row: every `<` is false → 0) — the index is 6 l + (entries < r2 in line l) with l = the number
 // of lines whose LAST entry is < r2, and r2 in [k/gk, (k+1)/gk) pins l between the two counts the guide stores for the cell's ends.
 // Dependent memory steps: guide (2 x u16, adjacent) → the candidate lines' cdf (24 bytes; the second and third only where needed) → the texel, in the line just read.
-PT_DEV void probe_search_end(const DevProbe& p, const ProbeMarg& pm, int row, int lo, int hi, float value, v3& dir, v3& color, float& pdf) {
+// (st, ct) = probe_row_sincos(p, row): the row's sine and cosine, shared with the caller's test of the row against the surface (shade_path)
+PT_DEV void probe_row_sincos(const DevProbe& p, int row, float& st, float& ct) {
+    float v = row / (float)p.height;
+    probe_v_sincos(v, st, ct);
+}
+// The columns probe_search_end can return for the guide's counts (lo, hi) of probe_search_begin: it looks in the lines lo .. hi after its
+// clamp to the row's last line, the column is 6 l + (entries of line l below the value), and a column past the width becomes width - 1,
+// which lies in the last line.  [6 lo, 6 hi + 6]: one column more than the lines hold.
+PT_DEV void probe_cell_columns(const DevProbe& p, int lo, int hi, int& c0, int& c1) {
+    const int last = p.lpr - 1;
+    lo = lo < last ? lo : last;
+    hi = hi < last ? hi : last;
+    hi = hi > lo ? hi : lo; // (counts out of order cannot come from k_probe_guide; the search would then stay in line lo)
+    c0 = lo * PT_LINE_COLS;
+    c1 = hi * PT_LINE_COLS + PT_LINE_COLS;
+}
+PT_DEV void probe_search_end(const DevProbe& p, const ProbeMarg& pm, int row, int lo, int hi, float value, float st, float ct, v3& dir, v3& color, float& pdf) {
     const ProbeLine* __restrict__ rl = p.lines + (size_t)row * p.lpr;
 #ifdef PT_EXP_NO_SEARCH
     const int l = lo;
@@ -550,19 +581,19 @@ PT_DEV void probe_search_end(const DevProbe& p, const ProbeMarg& pm, int row, in
     color = mk3(px.x, px.y, px.z);
     pdf = px.w * pm.pdfY[row];
     float u = col / (float)p.width;
-    float v = row / (float)p.height;
-    float sinTheta = pt_sinf(v * kPi);
+    float sinTheta = st; // pt_sinf(v * kPi) with v = row / height: the sine of probe_row_sincos's call
     if (sinTheta == 0.0f)
         pdf = 0.0f;
     else
         pdf *= (p.width * p.height) / (2.0f * kPi * kPi * sinTheta);
-    dir = probe_uv_to_dir(u, v);
+    dir = probe_u_to_dir(u, st, ct);
 }
 PT_DEV void probe_sample(const DevProbe& p, const ProbeMarg& pm, v3& dir, v3& color, float& pdf, Rng& rand) {
     int row, lo, hi;
-    float r2;
+    float r2, st, ct;
     probe_search_begin(p, pm, rand, row, lo, hi, r2);
-    probe_search_end(p, pm, row, lo, hi, r2, dir, color, pdf);
+    probe_row_sincos(p, row, st, ct);
+    probe_search_end(p, pm, row, lo, hi, r2, st, ct, dir, color, pdf);
 }
 
 // ------------------------------------------------------------------ software tex2D (SimplePathtracer.cpp:603-654 settings)

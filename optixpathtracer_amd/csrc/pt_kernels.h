@@ -272,7 +272,11 @@ struct ShadeParams {
     // carried sums (k_shade_carry; PathState::c0): the continuing paths' records, beside oThr / oRf
     float4 *oC0, *oC1;
     int second;         // the chain's second launch: the incoming records hold the direct sums
-    int last;           // the chain's last launch: every path writes its sums to direct / indirect, its shadow ray goes out with shPend (TR_SHADOW_APPLY adds it)
+    int last;           // the chain's last launch: every path writes its sums to direct / indirect, its shadow ray goes out with shPend (TR_SHADOW_APPLY adds it);
+                        // without shadow catchers the paths it would queue are never traced: they are counted, nothing of them is stored
+#ifdef PT_DEBUG_STATS
+    unsigned long long* dbg; // Trace8Args::dbg (null without PT_DEBUG_COUNTS)
+#endif
 };
 
 // wave-aggregated queue append: one atomic per wave (over the lanes that are active at the call: it may sit in divergent code).  Returns the
@@ -303,6 +307,12 @@ PT_DEV uint32_t queue_push(bool pred, uint32_t value, const QView& q) {
     const uint32_t pos = sub * q.sub_cap + base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
     if (pred) q.base[pos] = value;
     return pos;
+}
+// the count of queue_push without the entries: for a queue that is only ever counted
+PT_DEV void queue_count(bool pred, const QView& q) {
+    const unsigned long long mask = __ballot(pred);
+    if (mask == 0ull) return;
+    if (__lane_id() == (uint32_t)__ffsll((long long)mask) - 1u) atomicAdd(q.counts + (blockIdx.x & (PT_NSUB - 1)) * PT_CSTRIDE, (uint32_t)__popcll(mask));
 }
 
 // Carried sums: a finished sum goes to its slot array, one store.  A sum of three +0 is the value the generate kernels left in the slot and is
@@ -448,17 +458,49 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
             const float outEta = (rayEta == 1.0f) ? material_ior(mat) : 1.0f;
             const v3 wo = neg3(ray_dir);
             // SampleLights / SampleShadow (:252-334) up to the visibility test
-            v3 wi, skyColor;
-            float skyPdf;
-            // (started at the reference's position: −0.3 % frame; the candidate lines' loads started early as well: 18 more live registers, spills, slower)
-#ifdef PT_ABL_NO_PROBE
-            wi = mk3(0.f, 1.f, 0.f); skyColor = mk3(1.f, 1.f, 1.f); skyPdf = 1.f + ps_r2;
-#else
-            probe_search_end(sp.probe, pm, ps_row, ps_lo, ps_hi, ps_r2, wi, skyColor, skyPdf);
-#endif
+            v3 wi = mk3(0.f);
             bool has_val = false;
             v3 val = mk3(0.f);
-            {
+            // The row fixes the sample's latitude, the guide's two counts the lines its column can lie in: an arc of that latitude circle, a few
+            // degrees wide.  When the whole arc (or the whole circle) lies under the tangent plane (pt_below_horizon_arc, include/pt_detmath.h:
+            // dot(wi, N) <= 0 for every column the search can return) and the material's pdf for such a direction is not positive, nothing below
+            // depends on the column, the texel, the pdf or the BSDF value: has_val stays false, no shadow ray, nothing added.  The rest of the
+            // column search — the lines and the texel, scattered loads — is then not made (a branch: the lanes that skip issue no address; both
+            // random numbers are already drawn).
+#ifdef PT_ABL_NO_PROBE
+            const bool below = false;
+#else
+            float ps_st, ps_ct;
+            probe_row_sincos(sp.probe, ps_row, ps_st, ps_ct);
+            bool below = false;
+            if (!(bsdf_pdf_back<MODE>(mat) > 0.0f)) { // (a material with a positive back pdf never skips: it does not pay for the arc either)
+                float ps_spm, ps_cpm, ps_dphi;
+                int ps_c0, ps_c1;
+                probe_cell_columns(sp.probe, ps_lo, ps_hi, ps_c0, ps_c1);
+                pt_column_arc(ps_c0, ps_c1, sp.probe.width, &ps_spm, &ps_cpm, &ps_dphi);
+                below = pt_below_horizon_arc(ps_st, ps_ct, ps_spm, ps_cpm, ps_dphi, N.x, N.y, N.z);
+            }
+#endif
+#if defined(PT_DEBUG_STATS) && !defined(PT_ABL_NO_PROBE)
+            if (sp.dbg) { // [61] closest-hit programs run, [62] of them with the light sample's arc below the surface, [47] its whole circle (PT_DEBUG_COUNTS prints them)
+                const unsigned long long am = __ballot(true), bm = __ballot(below);
+                const unsigned long long cm = __ballot(below && pt_below_horizon(ps_st, ps_ct, N.x, N.y, N.z));
+                if (__lane_id() == (uint32_t)__ffsll((long long)am) - 1u) {
+                    atomicAdd(&sp.dbg[61], (unsigned long long)__popcll(am));
+                    if (bm) atomicAdd(&sp.dbg[62], (unsigned long long)__popcll(bm));
+                    if (cm) atomicAdd(&sp.dbg[47], (unsigned long long)__popcll(cm));
+                }
+            }
+#endif
+            if (!below) {
+                v3 skyColor;
+                float skyPdf;
+                // (started at the reference's position: −0.3 % frame; the candidate lines' loads started early as well: 18 more live registers, spills, slower)
+#ifdef PT_ABL_NO_PROBE
+                wi = mk3(0.f, 1.f, 0.f); skyColor = mk3(1.f, 1.f, 1.f); skyPdf = 1.f + ps_r2;
+#else
+                probe_search_end(sp.probe, pm, ps_row, ps_lo, ps_hi, ps_r2, ps_st, ps_ct, wi, skyColor, skyPdf);
+#endif
                 const float bsdfPdf = bsdf_pdf<MODE>(mat, rayEta, outEta, N, wo, wi);
                 const v3 f = bsdf_eval<MODE>(mat, albedo, rayEta, outEta, N, wo, wi);
                 if (bsdfPdf > 0.0f) {
@@ -481,9 +523,14 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
             basis_from_vector(N, u, v);
             bsdf_sample<MODE>(mat, rayEta, outEta, u, v, N, wo, bsdfDir, bsdfPdf, rand);
             v3 T_new = T_old;
+            // A path that would go on from the chain's last launch, or in the fused loop from a hit at the depth cutoff, is never traced (scenes
+            // without shadow catchers: enqueue_chunk makes no further launch, the loop does not queue it).  It is counted as a shaded hit below;
+            // the direction's BSDF value, the new throughput and the state of the next bounce are not computed.  bsdf_sample itself stays: its
+            // pdf decides FLAG_DONE, and with that whether this hit's shadow ray exists, and it advances nothing that is read afterwards.
+            const bool cut = !CATCHER && (LOCAL ? depth + 1 >= sp.max_depth : sp.last != 0);
             if (bsdfPdf <= 0.0f) {
                 flags |= FLAG_DONE; // :570-573
-            } else {
+            } else if (!cut) {
                 const v3 f = bsdf_eval<MODE>(mat, albedo, rayEta, outEta, N, wo, bsdfDir);
                 if (dot3(bsdfDir, N) <= 0.0f) rayEta = outEta;
                 T_new = mul3(T_old, div3s(scl3(f, fabsf(dot3(N, bsdfDir))), bsdfPdf));
@@ -574,6 +621,11 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
             __hip_atomic_store(hc, __hip_atomic_load(hc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) + (uint32_t)__popcll(cm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
         if (!CATCHER && depth >= sp.max_depth) push_next = false;
+    }
+    if (!CATCHER && !LOCAL && sp.last) {
+        // the chain's last launch: no launch reads this queue, its count is the last term of shaded_hits (k_accum_stats) — counted, not stored
+        queue_count(push_next, sp.next_queue);
+        push_next = false;
     }
     const uint32_t nq = queue_push<LOCAL>(push_next, p, sp.next_queue);
 #ifdef PT_ABL_NO_STATE_ST
