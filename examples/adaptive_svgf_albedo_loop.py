@@ -20,8 +20,13 @@ With --aniso N (which implies --lod) it is surfaceAnisoPlanes: up to N such look
 grazing angle is not blurred across that axis.
 With --edge-aa a step 9 follows, the last pass before display: edgeAaPlanes blends the silhouettes, creases and depth steps of the displayed
 frame — which shows the surface under each pixel's centre alone — by the share of the pixel that the nearer triangle's edge cuts off.
+With --auto-exposure [--tonemap aces|reinhard|linear] the displayed frame is tonemapPlanes's, behind --edge-aa when both are given: the
+linear frame is metered (exposurePlanes: a histogram of log2 luminance, its trimmed mean, an exposure that adapts from frame to frame) and
+shown through the operator under that exposure.  The exposure state ping-pongs between two device arrays and never visits the host on the
+way from the meter to the tone mapper (the value printed per frame is read back for the printing alone).
 
-  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--edge-aa] [--out-dir .]
+  python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--edge-aa]
+                                                [--auto-exposure] [--tonemap aces|reinhard|linear] [--out-dir .]
 """
 import argparse
 import os
@@ -67,6 +72,8 @@ def main():
     ap.add_argument("--aniso", type=int, default=0, metavar="N", help="implies --lod: up to N (1..16) lookups along the footprint's longer axis (surfaceAnisoPlanes)")
     ap.add_argument("--footprint-scale", type=float, default=1.0, help="with --lod: 1 = the pixel's own footprint")
     ap.add_argument("--edge-aa", action="store_true", help="geometric edge antialiasing (edgeAaPlanes) as the last pass before display")
+    ap.add_argument("--auto-exposure", action="store_true", help="meter the linear frame (exposurePlanes) and display it through tonemapPlanes")
+    ap.add_argument("--tonemap", choices=["aces", "reinhard", "linear"], default="aces", help="with --auto-exposure: the display operator")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args()
     args.lod = args.lod or args.aniso > 0
@@ -90,6 +97,8 @@ def main():
     variance, filtered, scratch, albedo, final = planes(1), planes(4), planes(4), planes(4), planes(4)
     modulated = planes(4) if args.edge_aa else None  # step 8's output where step 9 follows it
     frame = torch.zeros((h, w), dtype=torch.int32, device=dev)
+    hist = torch.zeros((1, 256), dtype=torch.int32, device=dev)  # --auto-exposure: the meter's histogram and the two exposure states
+    state = [torch.zeros((1, 4), device=dev) for _ in range(2)]
     accum = sample.deviceBuffer(R.PT_BUF_ACCUM)
     table = sample.copyTexcoordsDevice()  # the scene's texcoords per primitive: once, whatever moves later
     mips = sample.copyTextureMipsDevice() if args.lod else None  # the mip pyramid of the scene's textures: once, too
@@ -118,17 +127,23 @@ def main():
         assert c["stats"]["lost"] == 0  # the plan samples every block that holds a pixel the carry could not carry
         f = sample.filterPlanes(history[o], cur["hit"], cur["position"], variance=variance, length=length[o], out=filtered, scratch=scratch,
                                 iterations=args.iterations, sigma_lum=args.sigma_lum, min_length=args.min_length)
+        shown = None if args.auto_exposure else frame  # with --auto-exposure the tone mapper writes the displayed frame
         if args.edge_aa:
             m = sample.modulatePlanes(filtered, albedo=albedo, out=modulated)
-            e = sample.edgeAaPlanes(modulated, cur["hit"], cur["position"], out=final, frame=frame)["stats"]
+            e = sample.edgeAaPlanes(modulated, cur["hit"], cur["position"], out=final, frame=shown)["stats"]
         else:
-            m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=frame)
+            m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=shown)
+        if args.auto_exposure:
+            x = sample.exposurePlanes(final, cur["hit"], hist=hist, state_in=state[i] if k else None, state_out=state[o], rate_up=0.25, rate_down=0.5)["stats"]
+            tm = sample.tonemapPlanes(final, state=state[o], frame=frame, op=args.tonemap, write_out=False)["stats"]
         ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
         print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
               f"{ss['textured']} of {ss['hits']} hits textured{', %d minified' % ss['minified'] if args.lod else ''}{', %d taps' % ss['taps'] if args.aniso else ''}; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
               f"plan {ps['kernel_ms']:.3f} ms, colour {sample.stats()['render_ms']:.2f} ms, temporal {ts['kernel_ms']:.3f} ms, "
               f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms"
-              + (f", edge aa {e['kernel_ms']:.3f} ms ({e['blended']} of {e['boundary']} boundary pixels blended)" if args.edge_aa else ""))
+              + (f", edge aa {e['kernel_ms']:.3f} ms ({e['blended']} of {e['boundary']} boundary pixels blended)" if args.edge_aa else "")
+              + (f", exposure {x['kernel_ms']:.3f} ms (ev {float(state[o][0, 0]):+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
+                 f"tone map {tm['kernel_ms']:.3f} ms ({tm['clipped']} pixels clipped)" if args.auto_exposure else ""))
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_final.npy"), final.cpu().numpy())
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_frame.npy"), frame.cpu().numpy().view(np.uint32))
     print(f"wrote adaptive_svgf_albedo_final.npy and adaptive_svgf_albedo_frame.npy to {args.out_dir}")

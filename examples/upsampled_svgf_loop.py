@@ -17,10 +17,15 @@ Per frame, on `hi`:
      where an edge is near, the ring around them where there is none (rescued), another surface's value where that fails too (orphans);
  11. modulatePlanes with the full-resolution albedo: the displayed frame;
  12. with --edge-aa, edgeAaPlanes as the last pass before display: the silhouettes, creases and depth steps of that frame, which show the
-     surface under each pixel's centre alone, blended by the share of the pixel that the nearer triangle's edge cuts off.
+     surface under each pixel's centre alone, blended by the share of the pixel that the nearer triangle's edge cuts off;
+ 13. with --auto-exposure [--tonemap aces|reinhard|linear], behind step 12 when both are given: exposurePlanes meters the linear frame (a
+     histogram of log2 luminance, its trimmed mean, an exposure that adapts from frame to frame) and tonemapPlanes writes the displayed
+     frame through the operator under that exposure.  The exposure state ping-pongs between two device arrays and goes from the meter to
+     the tone mapper without visiting the host (the value in the printed line is read back for the printing alone).
 `hi` never renders a colour sample.
 
-  python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa] [--out-dir .]
+  python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa]
+                                          [--auto-exposure] [--tonemap aces|reinhard|linear] [--out-dir .]
 """
 import argparse
 import os
@@ -54,12 +59,13 @@ class UpsampledLoop:
     """The two renderers and every plane of the loop, allocated once; frame(k, prev, cam) runs one frame and returns its figures."""
 
     def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
-                 edge_aa=False):
+                 edge_aa=False, auto_exposure=False, tonemap="aces"):
         import torch
 
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
         self.size, self.scale, self.lod, self.aniso = tuple(size), int(scale), lod, int(aniso)
         self.edge_aa = bool(edge_aa)
+        self.auto_exposure, self.tonemap = bool(auto_exposure), tonemap
         w, h = self.size
         if w % self.scale or h % self.scale:
             raise SystemExit(f"--size {w} {h} is not a multiple of --scale {self.scale}")
@@ -86,6 +92,9 @@ class UpsampledLoop:
         self.albedo, self.upsampled, self.weight, self.final = planes(h, w, 4), planes(h, w, 4), planes(h, w, 1), planes(h, w, 4)
         self.modulated = planes(h, w, 4) if self.edge_aa else None  # step 11's output where step 12 follows it
         self.frame_rgba8 = torch.zeros((h, w), dtype=torch.int32, device="cuda:0")
+        # step 13's histogram and its two exposure states (ev, E, mean log2 luminance, pixels metered); cur: the one the last frame wrote
+        self.hist = torch.zeros((1, 256), dtype=torch.int32, device="cuda:0")
+        self.state, self.cur = [torch.zeros((1, 4), device="cuda:0") for _ in range(2)], 0
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
         self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
@@ -124,19 +133,29 @@ class UpsampledLoop:
         S = self._albedo(hi, self.hi_gbuf["hit"], self.albedo)
         u = hi.upsamplePlanes(self.filtered, cur["hit"], cur["position"], self.hi_gbuf["hit"], self.hi_gbuf["position"], self.scale, out=self.upsampled,
                               weight_out=self.weight)["stats"]
+        shown = None if self.auto_exposure else self.frame_rgba8  # with auto exposure the tone mapper writes the displayed frame
         if self.edge_aa:
             m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.modulated)["stats"]
-            e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=self.frame_rgba8)["stats"]
+            e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=shown)["stats"]
         else:
-            m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=self.frame_rgba8)["stats"]
+            m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=shown)["stats"]
             e = dict(kernel_ms=0.0, boundary=0, blended=0)
+        if self.auto_exposure:
+            x = hi.exposurePlanes(self.final, self.hi_gbuf["hit"], hist=self.hist, state_in=self.state[i] if k else None, state_out=self.state[o],
+                                  rate_up=0.25, rate_down=0.5)["stats"]
+            tm = hi.tonemapPlanes(self.final, state=self.state[o], frame=self.frame_rgba8, op=self.tonemap, write_out=False)["stats"]
+            self.cur = o
+        else:
+            x, tm = dict(kernel_ms=0.0, skipped=0, under=0, over=0), dict(kernel_ms=0.0, clipped=0)
         t2 = time.perf_counter()
+        ev = float(self.state[self.cur][0, 0]) if self.auto_exposure else 0.0  # read back for the caller's printing, outside the timed frame
         return dict(frame_ms=(t2 - t0) * 1e3, lo_ms=(t1 - t0) * 1e3, hi_ms=(t2 - t1) * 1e3, sampled=p["stats"]["sampled"], blocks=p["stats"]["blocks"],
                     rendered=rendered, colour_ms=lo.stats()["render_ms"], lo_gbuffer_ms=g["kernel_ms"], lo_surface_ms=s["kernel_ms"],
                     plan_ms=p["stats"]["kernel_ms"], temporal_ms=t["kernel_ms"], carry_ms=c["kernel_ms"], filter_ms=f["kernel_ms"],
                     gbuffer_ms=G["kernel_ms"], surface_ms=S["kernel_ms"], upsample_ms=u["kernel_ms"], modulate_ms=m["kernel_ms"],
                     pixels=u["pixels"], full=u["full"], rescued=u["rescued"], orphans=u["orphans"], edge_aa_ms=e["kernel_ms"], boundary=e["boundary"],
-                    blended=e["blended"])
+                    blended=e["blended"], exposure_ms=x["kernel_ms"], tonemap_ms=tm["kernel_ms"], ev=ev, skipped=x["skipped"], under=x["under"],
+                    over=x["over"], clipped=tm["clipped"])
 
     def close(self):
         self.lo.close()
@@ -153,11 +172,14 @@ def main(argv=None):
     ap.add_argument("--lod", action="store_true", help="footprint-filtered albedo (surfaceLodPlanes) at both resolutions")
     ap.add_argument("--aniso", type=int, default=0, metavar="N", help="implies --lod: up to N (1..16) lookups along the footprint's longer axis (surfaceAnisoPlanes)")
     ap.add_argument("--edge-aa", action="store_true", help="geometric edge antialiasing (edgeAaPlanes) as the last pass before display")
+    ap.add_argument("--auto-exposure", action="store_true", help="meter the linear frame (exposurePlanes) and display it through tonemapPlanes")
+    ap.add_argument("--tonemap", choices=["aces", "reinhard", "linear"], default="aces", help="with --auto-exposure: the display operator")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
     make, cam0 = SCENES[args.scene]
-    loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp, edge_aa=args.edge_aa)
+    loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp, edge_aa=args.edge_aa,
+                         auto_exposure=args.auto_exposure, tonemap=args.tonemap)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -168,6 +190,8 @@ def main(argv=None):
               f"{x['gbuffer_ms']:.3f} ms, surface {x['surface_ms']:.3f} ms, upsample {x['upsample_ms']:.3f} ms, modulate {x['modulate_ms']:.3f} ms; "
               f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; "
               + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
+              + (f"exposure {x['exposure_ms']:.3f} ms (ev {x['ev']:+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
+                 f"tone map {x['tonemap_ms']:.3f} ms ({x['clipped']} pixels clipped); " if loop.auto_exposure else "")
               + f"frame {x['frame_ms']:.2f} ms")
     np.save(os.path.join(args.out_dir, "upsampled_svgf_final.npy"), loop.final.cpu().numpy())
     np.save(os.path.join(args.out_dir, "upsampled_svgf_frame.npy"), loop.frame_rgba8.cpu().numpy().view(np.uint32))

@@ -30,7 +30,8 @@
  *     asynchronous ones; to consume it on another stream without a host wait, enqueue the consumer
  *     on pt_stream(ctx) or make that stream wait for an event recorded on pt_stream(ctx).
  * pt_edge_aa_planes takes DEVICE pointers under the same contract: it is one more entry point of the list above (its ordering case
- * stands with its other GPU tests, in tests/test_gpu_edge_aa.py).
+ * stands with its other GPU tests, in tests/test_gpu_edge_aa.py).  So do pt_exposure_planes and pt_tonemap_planes (their ordering
+ * cases: tests/test_gpu_exposure.py).
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -40,7 +41,8 @@
  * change): pt_render_mask / pt_*adaptive*, pt_update_meshes_device / pt_transform_meshes, pt_trace_device / pt_query_wait, pt_set_views and
  * its camera setters, pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_vertex_count, pt_copy_vertices_device, pt_motion_planes,
  * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
- * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes, pt_edge_aa_planes.  A
+ * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes, pt_edge_aa_planes,
+ * pt_exposure_planes, pt_tonemap_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
  */
 #ifndef PT_AMD_H
@@ -1494,6 +1496,99 @@ typedef struct pt_edge_aa_desc {
 } pt_edge_aa_desc;
 typedef struct pt_edge_aa_stats { uint64_t pixels, hits, stale, boundary, blended; double kernel_ms; } pt_edge_aa_stats;
 int pt_edge_aa_planes(pt_ctx* ctx, const pt_edge_aa_desc* desc, pt_edge_aa_stats* stats /* may be NULL */);
+
+/* AUTO EXPOSURE AND DISPLAY TONE MAPPING (no reference counterpart: the reference's sv4 Reinhard write takes an exposure the caller already
+ * knows).  The chain's colour planes are linear radiance under an HDR probe, without an upper bound; pt_modulate_planes and
+ * pt_edge_aa_planes end in make_color, which shows the part of that range inside [0, 1] at exposure 1.  pt_exposure_planes METERS a colour
+ * plane — a histogram of log2 luminance per view — and ADAPTS an exposure per view from it; pt_tonemap_planes APPLIES that exposure and a
+ * display operator.  Both are stateless: the planes, the histogram and the exposure state are caller-owned DEVICE memory of the context's
+ * device (4-byte aligned; the planes frame-sized, indexed Y * width + X); block_mask is HOST memory.  The exposure travels from the meter to
+ * the tone mapper through `state` in device memory: no host round trip.  The pixel set, views, partitions and pointer checks are exactly
+ * pt_modulate_planes's; nv = max(1, the view count), and a pixel's view is 0 without views.  No pixel outside the set is written.
+ *
+ * pt_exposure_planes.  hist: nv x PT_EXPOSURE_BINS uint32; state_in (or NULL) and state_out: nv x 4 float (ev, E, m, n).
+ * Flags: PT_EXPOSURE_ACCUMULATE — hist is not zeroed first (several planes or several calls into one histogram);
+ * PT_EXPOSURE_FROM_HISTOGRAM — no metering, hist is read as given (color, hit and block_mask must then be NULL; ACCUMULATE has no effect):
+ * each rank of a partitioned frame meters its own pixels, the caller all-reduces the integer histograms, and every rank derives the same
+ * exposure.  Otherwise hist is zeroed, also when the set is empty (zero pixels launch no metering kernel; the adaptation still runs).
+ * Metering, per pixel p of the set, into its view's histogram, in this order:
+ *   1. If hit is given and hit[p].prim is negative (a miss), the pixel is not counted: stats->skipped.  prim is compared for its sign only;
+ *      no address is formed from it.
+ *   2. c = color[p].xyz.  If one of its three words is not finite (exponent-bit test), the pixel is not counted: stats->nonfinite.
+ *   3. Y = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z, float32, one rounding per operation, no fused multiply-add.
+ *      If !(Y > 0): bin 0.  If Y is not finite (the sum overflowed): bin 255.  Otherwise k = (int)(bits(Y) >> 20) - 887 and the bin is
+ *      0 for k < 1, 255 for k > 254, else k: the exponent and the top three mantissa bits, eight bins per stop.  Bin 1 starts at 2^-16,
+ *      bin 254 ends below 2^15.75 on the piecewise-linear log2 of step 4 below (at 1.75 * 2^15); denormals land in bin 0.  Every bin is an integer function of the bit pattern: no transcendental.
+ *   4. hist[view][bin] += 1 (integer adds: the order does not matter, which is what makes the histogram bit-reproducible; no float is
+ *      accumulated anywhere).  stats->under counts bin 0, stats->over bin 255; stats->pixels is the size of the set.
+ * Adaptation, per view v, on the histogram words c[0..255] as uint64, integer arithmetic until the last step:
+ *   1. N = sum c[i].
+ *   2. lo = N * low_permille / 1000 and hi = N * high_permille / 1000 (integer division).
+ *   3. Walking up from bin 0, take = min(c[i], lo) is removed from c[i] and from lo; then walking down from bin 255 likewise with hi.
+ *   4. n = sum over 1..254 of c[i]; S = sum over 1..254 of c[i] * (2i - 1).  Bin i stands for log2 luminance -16 + (2i - 1) / 16, its
+ *      middle on the piecewise-linear log2 (exponent plus mantissa fraction), which is off from the true log2 by at most 0.09 stops.
+ *   5. ev_prev = state_in[4v].  If n == 0: m = state_in[4v + 2], or a NaN (0x7fc00000) when state_in is NULL; ev = ev_prev when state_in is
+ *      given and ev_prev is finite, else 0.0f.
+ *   6. Otherwise q = (S << 12) / n in uint64 (q < 2^21); m = (float)q * (1.0f / 65536.0f) - 16.0f; t = key_log2 - m;
+ *      t = t < ev_min ? ev_min : t; t = t > ev_max ? ev_max : t.  If state_in is NULL or ev_prev is not finite: ev = t.  Else
+ *      r = (t > ev_prev) ? rate_up : rate_down and ev = ev_prev + ((t - ev_prev) * r).
+ *   7. E = pt_expf(ev * 0.69314718f), include/pt_detmath.h's function (the same header compiled for the host gives the same bits).
+ *   8. state_out[4v .. 4v + 3] = (ev, E, m, (float)n).  state_out may be exactly state_in.
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; hist or
+ * state_out NULL; color NULL without FROM_HISTOGRAM; color, hit or block_mask given with it; a plane that fails the pointer checks; a
+ * forbidden overlap (hist and state_out overlap nothing, except state_out exactly state_in); an unknown flag bit;
+ * low_permille + high_permille > 999; key_log2 not finite; ev_min or ev_max outside [-24, 24] or NaN, or ev_min > ev_max; a rate outside
+ * [0, 1] or NaN.
+ *
+ * pt_tonemap_planes.  state: pt_exposure_planes's state_out, or NULL.  out may be exactly color (the pass is pixel-local); at least one
+ * of out and frame_rgba8 is given.  Per pixel p of the set, float32, one rounding per operation:
+ *   1. E_v = state ? state[4 * view + 1] : 1.0f; an E_v that is not finite or not > 0 counts as 1.0f.   2. s = E_v * exposure.
+ *   3. Per component: x = c * s; x = x > 0 ? x : 0 (a NaN becomes 0); x = x < 65504.0f ? x : 65504.0f (an inf becomes 65504).
+ *   4. PT_TONEMAP_LINEAR: y = x.  PT_TONEMAP_REINHARD: the frame path's own operator on the whole colour,
+ *      L = (0.2126f * x.r + 0.7152f * x.g) + 0.0722f * x.b; i = 1.0f / (1.0f + L / white); y = (x * 1.0f) * i per component (so that
+ *      pt_render_regions with tonemap = 1 and this pass leave the same bytes).  PT_TONEMAP_ACES (Narkowicz's fit), per component:
+ *      a = x * (2.51f * x + 0.03f); b = x * (2.43f * x + 0.59f) + 0.14f; y = a / b.
+ *   5. out[p] = (y, 1.0f); frame_rgba8[p] = make_color(y), the frame path's transform (clamp, sRGB, 8 bits, alpha 255).
+ *      stats->clipped counts the pixels with a component of y above 1.
+ * Refused with PT_ERR_INVALID likewise: a null ctx or desc; no pt_resize yet; color NULL; out and frame_rgba8 both NULL; a plane that
+ * fails the pointer checks; a forbidden overlap (out and frame_rgba8 overlap nothing, except out exactly color); flags != 0; an unknown
+ * op; exposure or white not finite or not > 0.
+ * Ordering and state, both entry points, as pt_modulate_planes: they wait for the frames in flight, run on pt_stream(ctx) under the STREAM
+ * CONTRACT, are complete when they return, and write no context state.
+ * Not part of this interface: spatially varying or centre-weighted metering; local tone mapping; bloom; a colour-managed output other than
+ * sRGB; an asynchronous variant; a pt_multi_* wrapper (per-rank calls and FROM_HISTOGRAM serve a partitioned frame). */
+#define PT_EXPOSURE_BINS 256
+enum pt_exposure_flags { PT_EXPOSURE_ACCUMULATE = 1, PT_EXPOSURE_FROM_HISTOGRAM = 2 };
+typedef struct pt_exposure_desc {
+    const float* color;        /* w*h x 4: linear radiance (.w ignored); required unless FROM_HISTOGRAM */
+    const void*  hit;          /* w*h x pt_hit or NULL: misses are not metered */
+    uint32_t*    hist;         /* nv x PT_EXPOSURE_BINS; required, exclusive */
+    const float* state_in;     /* nv x 4 or NULL: the previous frame's state_out */
+    float*       state_out;    /* nv x 4: ev, E = 2^ev, m (mean log2 luminance), n (pixels metered after trimming); required */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    uint32_t  low_permille, high_permille; /* shares of the histogram trimmed at its dark and bright ends; sum <= 999 */
+    float     key_log2;        /* log2 of the luminance the mean is mapped to (log2(0.18) = -2.47); finite */
+    float     ev_min, ev_max;  /* [-24, 24], ev_min <= ev_max */
+    float     rate_up, rate_down; /* [0, 1]: the share of the step taken per call towards a larger / smaller ev */
+    uint32_t  flags;           /* pt_exposure_flags */
+} pt_exposure_desc;
+typedef struct pt_exposure_stats { uint64_t pixels, skipped, nonfinite, under, over; double kernel_ms; } pt_exposure_stats;
+int pt_exposure_planes(pt_ctx* ctx, const pt_exposure_desc* desc, pt_exposure_stats* stats /* may be NULL */);
+
+enum pt_tonemap_op { PT_TONEMAP_LINEAR = 0, PT_TONEMAP_REINHARD = 1, PT_TONEMAP_ACES = 2 };
+typedef struct pt_tonemap_desc {
+    const float* color;        /* w*h x 4: linear radiance (.w ignored); required */
+    const float* state;        /* nv x 4 (pt_exposure_planes's state_out) or NULL */
+    float*    out;             /* w*h x 4 or NULL, exclusive except that it may be exactly color */
+    uint32_t* frame_rgba8;     /* w*h or NULL, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    float     exposure;        /* finite, > 0: multiplies the metered exposure */
+    float     white;           /* finite, > 0: PT_TONEMAP_REINHARD's white point */
+    uint32_t  op;              /* pt_tonemap_op */
+    uint32_t  flags;           /* 0 */
+} pt_tonemap_desc;
+typedef struct pt_tonemap_stats { uint64_t pixels, clipped; double kernel_ms; } pt_tonemap_stats;
+int pt_tonemap_planes(pt_ctx* ctx, const pt_tonemap_desc* desc, pt_tonemap_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -29,7 +29,7 @@ EXPORTS = [
     "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes", "pt_temporal_moments", "pt_modulate_planes",
     "pt_sample_plan", "pt_temporal_carry", "pt_copy_texcoords_device", "pt_surface_planes",
     "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes", "pt_surface_aniso_planes",
-    "pt_upsample_planes", "pt_edge_aa_planes",
+    "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -227,6 +227,44 @@ class EdgeAaStats(C.Structure):  # pt_edge_aa_stats
 # the planes of pt_edge_aa_planes: 32-bit words per pixel
 EDGE_AA_PLANES = {"color": 4, "hit": 8, "position": 4, "out": 4, "edge": 2, "frame_rgba8": 1}
 EDGE_AA_OUTPUTS = ("out", "edge", "frame_rgba8")
+
+
+PT_EXPOSURE_BINS = 256
+PT_EXPOSURE_ACCUMULATE, PT_EXPOSURE_FROM_HISTOGRAM = 1, 2  # pt_exposure_flags
+PT_TONEMAP_LINEAR, PT_TONEMAP_REINHARD, PT_TONEMAP_ACES = 0, 1, 2  # pt_tonemap_op
+TONEMAP_OPS = {"linear": PT_TONEMAP_LINEAR, "reinhard": PT_TONEMAP_REINHARD, "aces": PT_TONEMAP_ACES}
+
+
+class ExposureDesc(C.Structure):  # pt_exposure_desc
+    _fields_ = [("color", C.c_void_p), ("hit", C.c_void_p), ("hist", C.c_void_p), ("state_in", C.c_void_p), ("state_out", C.c_void_p),
+                ("block_mask", C.c_void_p), ("low_permille", C.c_uint32), ("high_permille", C.c_uint32), ("key_log2", C.c_float),
+                ("ev_min", C.c_float), ("ev_max", C.c_float), ("rate_up", C.c_float), ("rate_down", C.c_float), ("flags", C.c_uint32)]
+
+
+class ExposureStats(C.Structure):  # pt_exposure_stats
+    _fields_ = [("pixels", C.c_uint64), ("skipped", C.c_uint64), ("nonfinite", C.c_uint64), ("under", C.c_uint64), ("over", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class TonemapDesc(C.Structure):  # pt_tonemap_desc
+    _fields_ = [("color", C.c_void_p), ("state", C.c_void_p), ("out", C.c_void_p), ("frame_rgba8", C.c_void_p), ("block_mask", C.c_void_p),
+                ("exposure", C.c_float), ("white", C.c_float), ("op", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class TonemapStats(C.Structure):  # pt_tonemap_stats
+    _fields_ = [("pixels", C.c_uint64), ("clipped", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the frame-sized planes of pt_exposure_planes and pt_tonemap_planes: 32-bit words per pixel (hist and the state words are per view)
+EXPOSURE_PLANES = {"color": 4, "hit": 8}
+TONEMAP_PLANES = {"color": 4, "out": 4, "frame_rgba8": 1}
+TONEMAP_OUTPUTS = ("out", "frame_rgba8")
 
 
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
@@ -525,6 +563,8 @@ def load_library() -> C.CDLL:
     L.pt_surface_aniso_planes.argtypes = [vp, C.POINTER(SurfaceAnisoDesc), C.POINTER(SurfaceAnisoStats)]
     L.pt_upsample_planes.argtypes = [vp, C.POINTER(UpsampleDesc), C.POINTER(UpsampleStats)]
     L.pt_edge_aa_planes.argtypes = [vp, C.POINTER(EdgeAaDesc), C.POINTER(EdgeAaStats)]
+    L.pt_exposure_planes.argtypes = [vp, C.POINTER(ExposureDesc), C.POINTER(ExposureStats)]
+    L.pt_tonemap_planes.argtypes = [vp, C.POINTER(TonemapDesc), C.POINTER(TonemapStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

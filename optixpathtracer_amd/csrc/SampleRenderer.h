@@ -412,6 +412,22 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // Auto exposure (pt_exposure_planes): meters d.color into d.hist, a histogram of log2 luminance per view, and adapts an exposure per
+    // view from its trimmed mean into d.state_out (ev, E, mean log2 luminance, pixels metered), all DEVICE memory of the caller's.
+    pt_exposure_stats exposurePlanes(const pt_exposure_desc& d, pt_exposure_stats* stats = nullptr) {
+        pt_exposure_stats s{};
+        ck(pt_exposure_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
+    // The display operator under the metered exposure (pt_tonemap_planes): d.state is exposurePlanes's state_out, read on the device;
+    // d.out may be d.color.  Returns the pixel and clipped counts and the device time.
+    pt_tonemap_stats tonemapPlanes(const pt_tonemap_desc& d, pt_tonemap_stats* stats = nullptr) {
+        pt_tonemap_stats s{};
+        ck(pt_tonemap_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

@@ -20,3 +20,4 @@
 #include "pt_surface_lod.hip"
 #include "pt_upsample.hip"
 #include "pt_edge_aa.hip"
+#include "pt_exposure.hip"

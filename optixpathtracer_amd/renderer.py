@@ -895,6 +895,68 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_edge_aa_planes", desc, _lib.EdgeAaStats(), result)
 
+    def _view_words(self, fn, name, t, dtype, width, alloc=False):
+        """A per-view array of pt_exposure_planes / pt_tonemap_planes: (max(1, views), width) of dtype, a tensor, a raw pointer or None."""
+        import torch
+
+        dev = getattr(self, "_device", 0)
+        count = C.c_uint32(0)
+        if getattr(self, "_ctx", None):
+            self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
+        nv = max(1, count.value)
+        if t is None and alloc:
+            t = torch.zeros((nv, width), dtype=dtype, device=f"cuda:{dev}")
+        if t is None or isinstance(t, int):
+            return t, None
+        _check_temporal_tensor(name, t, dev, {dtype: (nv, width)}, fn)
+        return t.data_ptr(), t
+
+    def exposurePlanes(self, color=None, hit=None, hist=None, state_in=None, state_out=None, mask=None, low_permille=50, high_permille=20,
+                       key_log2=-2.4739312, ev_min=-16.0, ev_max=16.0, rate_up=1.0, rate_down=1.0, accumulate=False, from_histogram=False) -> dict:
+        """Auto exposure: meters `color` into a histogram of log2 luminance per view (eight bins a stop, integer counts) and adapts an
+        exposure per view from its trimmed mean (pt_exposure_planes, include/pt_amd.h: the rule, in full).  Stateless: the caller keeps
+        hist and the state.
+
+        color (h, w, 4) and hit ((h, w, 8), optional: misses are not metered) are CUDA float32 tensors or raw device pointers.  hist is an
+        int32 (views, 256) tensor and state_in / state_out float32 (views, 4) tensors (ev, E = 2^ev, mean log2 luminance, pixels metered)
+        with views = max(1, the view count), or raw pointers; hist and state_out are allocated when None; state_out may be state_in.
+        accumulate: hist is not zeroed first.  from_histogram: no metering, hist is read as given (the all-reduced histogram of a
+        partitioned frame); color, hit and mask must then be None.  tonemapPlanes reads state_out on the device.
+        Returns {"hist", "state_out": the tensor (None for a raw pointer), "stats": {pixels, skipped, nonfinite, under, over, kernel_ms}}."""
+        import torch
+
+        desc = _lib.ExposureDesc()
+        self._bind_planes("exposurePlanes", desc, dict(color=color, hit=hit), _lib.EXPOSURE_PLANES, () if from_histogram else ("color",))
+        desc.hist, th = self._view_words("exposurePlanes", "hist", hist, torch.int32, _lib.PT_EXPOSURE_BINS, alloc=True)
+        desc.state_in, _ = self._view_words("exposurePlanes", "state_in", state_in, torch.float32, 4)
+        desc.state_out, ts = self._view_words("exposurePlanes", "state_out", state_out, torch.float32, 4, alloc=True)
+        m = self._bind_mask("exposurePlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.low_permille, desc.high_permille = int(low_permille), int(high_permille)
+        desc.key_log2, desc.ev_min, desc.ev_max = float(key_log2), float(ev_min), float(ev_max)
+        desc.rate_up, desc.rate_down = float(rate_up), float(rate_down)
+        desc.flags = (_lib.PT_EXPOSURE_ACCUMULATE if accumulate else 0) | (_lib.PT_EXPOSURE_FROM_HISTOGRAM if from_histogram else 0)
+        return self._run_pass("pt_exposure_planes", desc, _lib.ExposureStats(), dict(hist=th, state_out=ts))
+
+    def tonemapPlanes(self, color, state=None, out=None, frame=None, mask=None, op="aces", exposure=1.0, white=1.0, write_out=True) -> dict:
+        """The display operator under the metered exposure (pt_tonemap_planes, include/pt_amd.h): per pixel the colour times its view's
+        E (state[view][1], read on the device; 1 when state is None) times `exposure`, clamped to [0, 65504], through op — "linear",
+        "reinhard" (the frame path's operator, with `white`) or "aces" (Narkowicz's fit) — into out (h, w, 4; may be `color` itself;
+        allocated when None and write_out) and / or frame (int32 (h, w) or uint8 (h, w, 4): sRGB, 8 bits).
+        Returns {"out", "frame_rgba8": the tensor (None for a raw pointer or an absent plane), "stats": {pixels, clipped, kernel_ms}}."""
+        import torch
+
+        if op not in _lib.TONEMAP_OPS:
+            raise ValueError(f"tonemapPlanes: unknown operator {op!r} (one of {', '.join(_lib.TONEMAP_OPS)})")
+        if out is None and frame is None and not write_out:
+            raise ValueError("tonemapPlanes: no output asked for (out and frame are both None)")
+        given = dict(color=color, out=out, frame_rgba8=frame)
+        desc = _lib.TonemapDesc()
+        result = self._bind_planes("tonemapPlanes", desc, given, _lib.TONEMAP_PLANES, ("color",), _lib.TONEMAP_OUTPUTS, alloc=("out",) if write_out else ())
+        desc.state, _ = self._view_words("tonemapPlanes", "state", state, torch.float32, 4)
+        m = self._bind_mask("tonemapPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.exposure, desc.white, desc.op, desc.flags = float(exposure), float(white), _lib.TONEMAP_OPS[op], 0
+        return self._run_pass("pt_tonemap_planes", desc, _lib.TonemapStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
