@@ -1362,7 +1362,12 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
     // through a shadow-catcher pass-through or alpha; without catcher materials it is provably dead and skipped)
     // (a foveated launch of the sv / sv2 variants starts its paths at depth 1: that many fewer bounces are live)
     const int depth0 = job ? job->var.initial_depth : 0;
-    const int last_bounce = (ctx->has_catcher ? ctx->opt.max_depth : ctx->opt.max_depth - 1) - depth0;
+    // max_depth = 0 (scenes without catchers): the reference still runs the closest-hit program of the camera ray — the first-hit normal and
+    // albedo are added, alpha becomes 1 — and breaks before any radiance is added (deviceProgram.cu:424-430).  The bounce-0 shade is then
+    // the chain's first and last launch: it sets FLAG_HIT0 and the AOVs, ends every path (depth >= max_depth) ahead of its light sample's
+    // use, so no shadow ray exists and no shadow launch is made.
+    const int last_bounce = std::max(0, (ctx->has_catcher ? ctx->opt.max_depth : ctx->opt.max_depth - 1) - depth0);
+    const bool lit = ctx->has_catcher || ctx->opt.max_depth > 0; // some launch of the chain can queue a shadow ray
     const int aov = job ? (job->var.write_aov && job->var.initial_depth == 0 ? 1 : 0) : 1;
     for (uint32_t s0 = 0; s0 < spp; s0 += S) {
         const uint32_t Sc = std::min(S, spp - s0);
@@ -1425,10 +1430,13 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
                     if (ev_shadow_done) hipStreamWaitEvent(bs.stream, ev_shadow_done, 0); // shade overwrites what shadow(b-1) reads
                 }
                 P.shade(qnext, qshadow, aov, (b == 0) ? 1 : 0, carry, b == 1, b == last_bounce);
-                if (placement == SPLIT) {
+                if (!lit) {
+                    // (max_depth = 0: the shadow queue stays empty)
+                } else if (placement == SPLIT) {
                     ev_shadow_done = P.side_shadow(bs.stream2, qshadow, b, bs.ovf2, 0);
                 } else if (placement == ASYNC) {
-                    shadow_done.push_back(P.side_shadow((b & 1) ? bs.stream3 : bs.stream2, qshadow, b, (b & 1) ? bs.ovf3 : bs.ovf2, b));
+                    // (the records and visibility bits are addressed by the path's depth, which a foveated launch of the sv / sv2 variants starts at 1)
+                    shadow_done.push_back(P.side_shadow((b & 1) ? bs.stream3 : bs.stream2, qshadow, b, (b & 1) ? bs.ovf3 : bs.ovf2, b + depth0));
                     if (b < last_bounce) P.closest(P.sin ^ 1, qnext, b + 1, ctx->dbg);
                 } else if (b < last_bounce) {
                     SpanGuard g(ctx, CLS_TRACE, bs.stream);
