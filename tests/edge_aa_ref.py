@@ -4,8 +4,10 @@ calls the kernel under test.  The float64 half at the end (the crossing of a tri
 expression of the header."""
 import numpy as np
 
+import conftest  # noqa: F401  (puts the repository's root on sys.path)
 import surface_ref as S
 from motion_ref import _cross, _dot
+from optixpathtracer_amd import scenes
 from surface_lod_ref import _rays, camera_rays64
 
 f32 = np.float32
@@ -179,3 +181,18 @@ def box_average(plane, S_):
 
 def rms(a, b):
     return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
+
+
+# ------------------------------------------------------------------ the inputs and the figure the tests share (tests/test_edge_aa_cabi.py measures and pins it)
+W, H = 131, 59
+SUPER = 8
+# measured 0.30530 (rms 0.009637 after the rule, 0.031566 before it; 1140 boundary pixels, 556 blended, of 7729); the owner inverted gives
+# 0.71213, every weight forced to 0 gives 1.00000, against the bound (1 + R_EDGE) / 2 = 0.6525: see
+# test_reference_output_is_closer_to_the_supersampled_truth.  With a 4 x 4 supersample as the truth the same rule gives 0.43955 (recorded only).
+R_EDGE = 0.305
+INPUTS = {"cornell": (scenes.cornell_box, scenes.CORNELL_CAMERA), "textured": (S.textured_scene, dict(eye=(2.0, 0.35, -3.0), lookat=(0.0, 0.2, 0.5), up=(0.0, 1.0, 0.0), fovY=35.0))}
+
+
+def supersampled_truth(albedo_big, s=SUPER):
+    """(s*h, s*w, >=3) float32 pixel-centre albedo of the s times larger frame -> (h, w, 3) float64"""
+    return box_average(np.asarray(albedo_big)[..., 0:3], s)

@@ -17,7 +17,7 @@ from optixpathtracer_amd import _lib  # noqa: E402
 assert os.path.dirname(os.path.abspath(optixpathtracer_amd.__file__)).startswith(tree), optixpathtracer_amd.__file__
 print("library:", _lib.LIB_PATH)
 sys.path.insert(1, here)
-import test_gpu_horizon as T  # noqa: E402
+import horizon_cases as T  # noqa: E402
 
 
 class Env:

@@ -73,8 +73,7 @@ def header_outputs(lib, prefix, seed, n=300):
 def main():
     sys.path.insert(0, ROOT)
     sys.path.insert(0, TESTS)
-    import test_hdrloader
-    import test_objloader as T
+    import loader_inputs as T
 
     from oracle import orc
 
@@ -83,7 +82,7 @@ def main():
         raise SystemExit("oracle/_ref/libptref.so with the Model.cpp and stb_image shims is missing: run `make -C oracle ref` where the reference's sources lie")
     G = {"header_seed": HEADER_SEED}
     with tempfile.TemporaryDirectory() as d:
-        G["hdr_live"] = [digest(orc.ref_loadf(R, path)) for path in test_hdrloader.hdr_live_inputs(d)]
+        G["hdr_live"] = [digest(orc.ref_loadf(R, path)) for path in T.hdr_live_inputs(d)]
     G["obj_fixture"] = {}
     for name in ("basic", "concave", "numbers", "quirks"):
         G["obj_fixture"][name] = model_digest(*orc.ref_load_obj(R, os.path.join(T.FIX, name + ".obj")))

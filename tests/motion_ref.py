@@ -127,7 +127,7 @@ def fill_uv(rec, model, row, w, h):
     """A copy of the hit plane `rec` (h, w, 8) with u, v filled by the header's expression for pt_hit, from the ray of each pixel's centre
     under the camera row: A = v0 - o, B = v1 - o, C = v2 - o; Uw = dot(d, cross(C, B)), Vw = dot(d, cross(A, C)), Ww = dot(d, cross(B, A));
     det = (Uw + Vw) + Ww; u = Vw / det; v = Ww / det"""
-    import test_gpu_gbuffer as G
+    import gbuffer_ref as G
 
     verts, idx = model_arrays(model)
     rays = G._np_rays(row, w, h)
@@ -149,7 +149,7 @@ def fill_uv(rec, model, row, w, h):
 
 def cpu_planes(orc, model, size, cam_dict, prev_dict):
     """temporal_ref.cpu_planes with u, v of both hit planes filled in (that helper leaves them 0)"""
-    import test_gpu_gbuffer as G
+    import gbuffer_ref as G
 
     w, h = size
     P = T.cpu_planes(orc, model, size, cam_dict, prev_dict)

@@ -257,3 +257,35 @@ def hand_made_verts(model):
     k = list(HAND_PRIMS).index("zero_area")
     verts[idx[k]] = np.array(HAND_COLLAPSED, f32)
     return verts, idx
+
+
+# ------------------------------------------------------------------ the inputs, checks and the figure the tests share (tests/test_surface_aniso_cabi.py measures and pins them)
+W, H = 131, 59
+GRAZING_CAMERA = dict(eye=(2.0, 0.35, -3.0), lookat=(0.0, 0.2, 0.5), up=(0.0, 1.0, 0.0), fovY=35.0)
+# measured 0.19391 (rms 0.0122 anisotropic, 0.0627 isotropic, 3081 pixels, N >= 3 on 0.824 of them); the taps along the minor axis give 0.0809
+# (1.290 x isotropic), N forced to 1 gives 0.0627 (1.000 x): see test_anisotropic_albedo_of_the_reference_is_closer_to_the_pixel_average.
+# Under the non-grazing camera of tests/test_surface_lod_cabi.py (131 x 61): ratio 0.21688 (0.0125 against 0.0578, 2535 pixels), recorded only.
+R_ANISO = 0.194
+
+
+def ground_truth(c, w, h, q):
+    """the 16 x 16 float64 supersample of the ground's texture over the pixels q"""
+    Y, X = np.nonzero(q)
+    tri, uv = c["verts"][c["idx"][0]], c["sc"]["uv"][0].reshape(3, 2)
+    return SL.supersample64(c["sc"]["textures"][0], c["row"], w, h, X.astype(np.float64), Y.astype(np.float64), tri, uv, 16)
+
+
+# ------------------------------------------------------------------ the hand-made inputs of the GPU test
+def check_hand_made(n_plane, lod_plane, where, max_aniso):
+    """every primitive of surface_aniso_ref.HAND_PRIMS that names an expected N (and lod) shows it on all of its pixels"""
+    for name, (_, _, _, n8, n16, lod) in HAND_PRIMS.items():
+        want = {8: n8, 16: n16}[max_aniso]
+        on = where[name]
+        assert on.sum() >= 10, name
+        if want is not None:
+            assert (n_plane[on] == want).all(), (name, max_aniso, np.unique(n_plane[on]).tolist(), want)
+        if lod is not None and max_aniso == 8:
+            assert (lod_plane[on] == f32(lod)).all(), (name, np.unique(lod_plane[on]).tolist(), lod)
+    assert (n_plane[7] == 1).all() and (n_plane[6] >= 8).all(), ("rows 7 and 6", max_aniso)  # the horizon row: ok is false; the row above it: grazing, q between 8.x and 16.x
+    for name in ("miss", "miss_2", "stale_ntri", "stale_max"):
+        assert (n_plane[where[name]] == 0).all() and (lod_plane[where[name]] == 0).all(), name

@@ -5,7 +5,9 @@ Model's host arrays (surface_ref.scene_arrays, motion_ref.model_arrays); the flo
 neighbours) uses no expression of the header."""
 import numpy as np
 
+import motion_ref as M
 import surface_ref as S
+from gbuffer_ref import _row
 from motion_ref import _cross, _dot
 
 f32 = np.float32
@@ -255,3 +257,53 @@ def neighbour_footprints(texcoord, prim_plane, kind):
     fx[:, :-1] = tc[:, 1:] - tc[:, :-1]
     fy[:-1, :] = tc[1:, :] - tc[:-1, :]
     return fx, okx, fy, oky
+
+
+# ------------------------------------------------------------------ the inputs, checks and figures the tests share (tests/test_surface_lod_cabi.py measures and pins them)
+W, H = 131, 61
+FOOT_MEASURED = 8.35e-7  # measured 8.345e-07 on footprints up to 0.157, see test_footprints_of_the_reference_are_the_neighbour_differences
+FOOT_BOUND = 4 * FOOT_MEASURED
+R_REF = 0.797  # measured 0.79705 (rms 0.0578 filtered, 0.0725 point, 2535 pixels), see test_filtered_albedo_of_the_reference_is_closer_to_the_pixel_average
+_CPU_CASE = {}
+
+
+def cpu_case(orc):
+    """the textured scene's CPU-built planes with the reference's planes at footprint_scale 1 and 0"""
+    if "c" not in _CPU_CASE:
+        from geometry_cases import textured_case
+
+        c = dict(textured_case(orc))
+        c["verts"], c["idx"] = M.model_arrays(c["model"])
+        c["row"] = _row(c["cam"], W / H)
+        frame = np.ones((H, W), bool)
+        c["lod"] = surface_lod_ref(c["hit"], c["sc"], c["verts"], c["idx"], [(0, 0, W, H)], [c["row"]], frame)
+        c["point"] = surface_lod_ref(c["hit"], c["sc"], c["verts"], c["idx"], [(0, 0, W, H)], [c["row"]], frame, scale=0.0)
+        c["surface"] = S.surface_ref(c["hit"], c["sc"], frame)
+        _CPU_CASE["c"] = c
+    return _CPU_CASE["c"]
+
+
+def check_footprints(footprint, texcoord, prim, kind):
+    """The footprint plane against the texcoord plane alone, float64: on pixels whose right (lower) neighbour is a textured hit on the same
+    primitive, texcoord[neighbour] - texcoord[p] is the x (y) footprint.  Returns dict(err: the largest absolute difference per component;
+    nx, ny: pixels compared; size: the largest |footprint| component compared)."""
+    fx, okx, fy, oky = neighbour_footprints(texcoord, prim, kind)
+    fp = np.asarray(footprint, np.float64)
+    ex, ey = np.abs(fp[..., 0:2] - fx)[okx], np.abs(fp[..., 2:4] - fy)[oky]
+    return dict(err=float(max(ex.max(), ey.max())), nx=int(okx.sum()), ny=int(oky.sum()), size=float(max(np.abs(fx[okx]).max(), np.abs(fy[oky]).max())))
+
+
+def ground_pixels(mesh):
+    """ground (mesh 0) pixels whose 3 x 3 hit neighbourhood lies on the ground mesh"""
+    h, w = mesh.shape
+    pad = np.pad(mesh, 1, mode="constant", constant_values=-1)
+    q = np.ones((h, w), bool)
+    for dy in range(3):
+        for dx in range(3):
+            q &= pad[dy:dy + h, dx:dx + w] == 0
+    return q
+
+
+def rms_against(albedo_bits, truth, q):
+    d = albedo_bits.view(f32)[..., :3][q].astype(np.float64) - truth
+    return float(np.sqrt((d * d).mean()))

@@ -10,6 +10,7 @@ SENTINEL = T.SENTINEL
 PLANES = ("albedo", "texcoord")
 WORDS = {"albedo": 4, "texcoord": 2}
 ONE = 0x3F800000
+TEX_CAMERA = dict(eye=(2.0, 1.5, -3.0), lookat=(0.0, 0.6, 0.5), up=(0.0, 1.0, 0.0), fovY=35.0)  # the camera the tests put on textured_scene()
 
 
 def textured_scene():

@@ -161,10 +161,10 @@ def random_history(rng, h, w):
 
 def cpu_planes(orc, model, size, cam_dict, prev_dict):
     """The planes renderGBuffer gives for `cam_dict` (motion against `prev_dict`) and for `prev_dict`, built without a GPU: the CPU checker's
-    trace_closest for (t, prim), float32 NumPy for position and motion (the G-buffer formulas of the header, tests/test_gpu_gbuffer.py), the
+    trace_closest for (t, prim), float32 NumPy for position and motion (the G-buffer formulas of the header, tests/gbuffer_ref.py), the
     mesh from the primitive's place in mesh order, ng = normalize3(cross3(v1 - v0, v2 - v0)).  Good for counting which pixels reproject and
     why the others do not; the GPU tests take their planes from renderGBuffer."""
-    import test_gpu_gbuffer as G
+    import gbuffer_ref as G
 
     w, h = size
     sc = orc.make_scene(model, use_bvh=True)
@@ -193,7 +193,7 @@ def cpu_planes(orc, model, size, cam_dict, prev_dict):
 
 # ------------------------------------------------------------------ the real-plane inputs of tests/test_gpu_temporal.py
 def forward(cam_dict, f, dx=0.25):
-    """test_gpu_gbuffer's _moved (the eye shifted by dx in x) after a dolly of the eye by the fraction f towards the look-at point: the
+    """gbuffer_ref._moved (the eye shifted by dx in x) after a dolly of the eye by the fraction f towards the look-at point: the
     current frame then sees more than the previous one did (lookups leave the image), parallax disoccludes, and for f large enough the
     nearest surface points lie behind the previous camera (NaN motion)."""
     e, l = np.asarray(cam_dict["eye"], np.float64), np.asarray(cam_dict["lookat"], np.float64)

@@ -3,70 +3,13 @@ pt_adaptive_stats match the compiler's layout, a null context is refused before 
 numpy float32 transcription of the stopping rule (include/pt_amd.h states it operation by operation).  The transcription is the checker of
 the policy: tests/test_gpu_adaptive.py compares every decision of the GPU kernel with it."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+from adaptive_ref import block_slots, butterfly, rule_sides, stop_rule
+from cabi_kit import check_layout, compile_facade, header
 from optixpathtracer_amd import _lib
-
-
-# ------------------------------------------------------------------ the stopping rule, transcribed
-def block_slots(image, fill=0):
-    """(h, w, ...) -> (nby * nbx, 64, ...): slot l of block by * nbx + bx is the pixel (8 bx + (l & 7), 8 by + (l >> 3)); `fill` outside the image."""
-    h, w = image.shape[:2]
-    nby, nbx = (h + 7) // 8, (w + 7) // 8
-    pad = np.full((nby * 8, nbx * 8) + image.shape[2:], fill, image.dtype)
-    pad[:h, :w] = image
-    rest = tuple(range(4, pad.ndim + 2))
-    return pad.reshape((nby, 8, nbx, 8) + image.shape[2:]).transpose((0, 2, 1, 3) + rest).reshape((nby * nbx, 64) + image.shape[2:])
-
-
-def butterfly(a):
-    """for off = 32 .. 1: slot[l] += slot[l ^ off], float32, over the last axis of 64 slots"""
-    idx = np.arange(64)
-    a = a.astype(np.float32)
-    for off in (32, 16, 8, 4, 2, 1):
-        a = a + a[:, idx ^ off]
-    return a[:, 0]
-
-
-def rule_sides(moments, blocks):
-    """What the rule is built from, for the given block ids, as float32 arrays: n (the block's subframe count), V and M (the butterfly sums of
-    the per-pixel variances and means) and N (the block's pixel count)."""
-    f = np.float32
-    h, w = moments.shape[:2]
-    inside = block_slots(np.ones((h, w), bool), False)[blocks]
-    mo = block_slots(np.ascontiguousarray(moments, np.float32))[blocks]
-    n = mo[:, 0, 0].astype(f)
-    with np.errstate(all="ignore"):
-        m = (mo[:, :, 1] / n[:, None]).astype(f)
-        q = (mo[:, :, 2] / n[:, None]).astype(f)
-        mm = (m * m).astype(f)
-        v = np.maximum(f(0), (q - mm).astype(f)).astype(f)
-    m = np.where(inside, m, f(0)).astype(f)
-    v = np.where(inside, v, f(0)).astype(f)
-    return n, butterfly(v), butterfly(m), inside.sum(1).astype(f)
-
-
-def stop_rule(moments, blocks, threshold, dark_floor, min_subframes, max_subframes):
-    """True for the blocks (ids in `blocks`, all rendered by the call) that stop.  Every line is one float32 operation."""
-    f = np.float32
-    n, V, M, N = rule_sides(moments, blocks)
-    fl = (f(dark_floor) * N).astype(f)
-    B = (M + fl).astype(f)
-    lhs = (V * N).astype(f)
-    t2 = f(f(threshold) * f(threshold))
-    n1 = (n - f(1)).astype(f)
-    rhs = (t2 * n1).astype(f)
-    rhs = (rhs * B).astype(f)
-    rhs = (rhs * B).astype(f)
-    stop = (n >= f(min_subframes)) & (lhs <= rhs)
-    if max_subframes > 0:
-        stop |= n >= f(max_subframes)
-    return stop
 
 
 def _moments(h, w, n, values):
@@ -122,12 +65,8 @@ def test_rule_sums_are_the_documented_butterfly():
 
 
 # ------------------------------------------------------------------ the C boundary
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_header_declares_the_entry_points():
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name in ("pt_render_mask", "pt_adaptive_begin", "pt_render_adaptive", "pt_adaptive_end", "pt_download_adaptive"):
         assert re.search(r"int\s+%s\s*\(\s*pt_ctx\s*\*" % name, src), name
         assert name in _lib.EXPORTS
@@ -139,20 +78,9 @@ def test_header_declares_the_entry_points():
 
 
 def test_adaptive_struct_layouts_match_the_compiler(tmp_path):
-    src = tmp_path / "probe.c"
-    src.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\n'
-        'int main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(pt_adaptive_params), offsetof(pt_adaptive_params, threshold), '
-        "offsetof(pt_adaptive_params, dark_floor), offsetof(pt_adaptive_params, min_subframes), offsetof(pt_adaptive_params, max_subframes));\n"
-        'printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(pt_adaptive_stats), offsetof(pt_adaptive_stats, blocks), offsetof(pt_adaptive_stats, active_blocks), '
-        "offsetof(pt_adaptive_stats, active_pixels), offsetof(pt_adaptive_stats, pixel_subframes), offsetof(pt_adaptive_stats, decide_ms)); return 0; }\n"
-    )
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    P, S = _lib.AdaptiveParams, _lib.AdaptiveStats
-    assert got[:5] == [C.sizeof(P), P.threshold.offset, P.dark_floor.offset, P.min_subframes.offset, P.max_subframes.offset]
-    assert got[5:] == [C.sizeof(S), S.blocks.offset, S.active_blocks.offset, S.active_pixels.offset, S.pixel_subframes.offset, S.decide_ms.offset]
+    check_layout(tmp_path, [(_lib.AdaptiveParams, "pt_adaptive_params", ("threshold", "dark_floor", "min_subframes", "max_subframes")),
+                            (_lib.AdaptiveStats, "pt_adaptive_stats", ("blocks", "active_blocks", "active_pixels", "pixel_subframes", "decide_ms"))],
+                 [16, 0, 4, 8, 12] + [32, 0, 4, 8, 16, 24])
 
 
 def test_null_context_is_refused_without_a_gpu():
@@ -175,8 +103,8 @@ def test_null_context_is_refused_without_a_gpu():
 
 
 def test_facade_mask_and_adaptive_compile(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t progressive(SampleRenderer& sample, std::vector<uint32_t>& pixels) {\n"
@@ -196,4 +124,3 @@ def test_facade_mask_and_adaptive_compile(tmp_path):
         "    return st.pixel_subframes + active;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from cabi_kit import compile_facade, header
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -18,12 +19,8 @@ HIT_FIELDS = ("t", "u", "v", "prim", "mesh", "ng")
 STATS_FIELDS = ("rays", "hits", "invalid_rays", "stage_ms", "trace_ms", "attrib_ms", "state_bytes")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_header_declares_the_query_entry_points():
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert re.search(r"int\s+pt_trace_device\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+float\s*\*", src)
     assert re.search(r"int\s+pt_query_wait\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*pt_query_stats\s*\*", src)
     assert "PT_QUERY_CLOSEST = 0" in src and "PT_QUERY_ANY = 1" in src and "PT_QUERY_ASYNC = 2" in src
@@ -38,7 +35,7 @@ def test_header_declares_the_query_entry_points():
 
 def test_header_states_the_barycentric_expression():
     """The arithmetic NumPy parity rests on, and the pointer contract, are part of the header."""
-    text = " ".join(_header().split())
+    text = " ".join(header().split())
     assert "det = (Uw + Vw) + Ww; u = Vw / det; v = Ww / det" in text
     assert "Uw = dot(d, cross(C, B)), Vw = dot(d, cross(A, C)), Ww = dot(d, cross(B, A))" in text
     assert "pt_trace_device" in text.split("STREAM CONTRACT")[1].split("VERSIONING")[0]
@@ -122,8 +119,8 @@ def test_python_facade_checks_tensors_before_calling_the_library():
 
 
 def test_facade_trace_device_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t pick(SampleRenderer& sample, const float* d_rays, uint32_t n, pt_hit* d_hits, int32_t* d_occluded) {\n"
@@ -135,4 +132,3 @@ def test_facade_trace_device_compiles(tmp_path):
         "    return a.hits + b.hits + b.invalid_rays + b.state_bytes;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)

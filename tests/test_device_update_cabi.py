@@ -8,18 +8,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from cabi_kit import compile_facade, header
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
 NAMES = ("pt_update_meshes_device", "pt_transform_meshes", "pt_multi_transform_meshes", "pt_download_vertices")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_header_declares_the_device_update_entry_points():
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert re.search(r"int\s+pt_update_meshes_device\s*\(\s*pt_ctx\s*\*", src)
     assert re.search(r"int\s+pt_transform_meshes\s*\(\s*pt_ctx\s*\*", src)
     assert re.search(r"int\s+pt_multi_transform_meshes\s*\(\s*pt_multi\s*\*", src)
@@ -35,7 +32,7 @@ def test_header_declares_the_device_update_entry_points():
 
 def test_header_states_the_transform_order():
     """The arithmetic contract NumPy parity rests on is part of the header."""
-    text = " ".join(_header().split())
+    text = " ".join(header().split())
     assert "x' = ((m[0]*x + m[1]*y) + m[2]*z) + m[3]" in text
     assert "hipPointerGetAttributes" in text and "4-byte aligned" in text
 
@@ -92,8 +89,8 @@ def test_python_facade_marshals_matrices():
 
 
 def test_facade_device_updates_compile(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "double animate(SampleRenderer& sample, MultiSampleRenderer& multi, const float* d_vertices, uint32_t nv) {\n"
@@ -107,4 +104,3 @@ def test_facade_device_updates_compile(tmp_path):
         "    return ms;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)

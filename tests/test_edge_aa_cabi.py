@@ -3,7 +3,7 @@ compiler's layout, the header compiles as C99 and C++17 and states the rule, nul
 have the method; and the float32 NumPy reference (tests/edge_aa_ref.py) is held against a float64 restatement of the crossing (s and b_r)
 on CPU-built planes (motion_ref.cpu_planes) of the Cornell box and of the textured scene.
 
-This file records one figure for tests/test_gpu_edge_aa.py, from the references alone — no bound comes from a kernel's output;
+This file pins one figure (kept in tests/edge_aa_ref.py) for tests/test_gpu_edge_aa.py, from the references alone — no bound comes from a kernel's output;
 profiles/edge_aa.md holds the same figure:
 
   R_EDGE: rms(reference output - truth) / rms(colour - truth) over the whole 131 x 59 frame of the Cornell box, on CPU-built planes.  The
@@ -12,9 +12,7 @@ profiles/edge_aa.md holds the same figure:
   rms(out - truth) <= ((1 + R_EDGE) / 2) * rms(colour - truth) on the GPU's own planes.  The rule with the owner inverted and the rule with
   every weight forced to 0 both miss that bound (shown below)."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,50 +20,30 @@ import pytest
 import edge_aa_ref as E
 import motion_ref as M
 import surface_ref as S
-from conftest import ROOT
-from optixpathtracer_amd import _lib, scenes
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_section
+from edge_aa_ref import INPUTS, R_EDGE, SUPER, H, W, supersampled_truth
+from gbuffer_ref import _row
+from optixpathtracer_amd import _lib
 
 f32 = np.float32
-W, H = 131, 59
-SUPER = 8
 DESC_FIELDS = ("color", "hit", "position", "out", "edge", "frame_rgba8", "block_mask", "normal_cos", "plane_eps", "flags")
 STATS_FIELDS = ("pixels", "hits", "stale", "boundary", "blended", "kernel_ms")
 NAME = "pt_edge_aa_planes"
 
-# measured 0.30530 (rms 0.009637 after the rule, 0.031566 before it; 1140 boundary pixels, 556 blended, of 7729); the owner inverted gives
-# 0.71213, every weight forced to 0 gives 1.00000, against the bound (1 + R_EDGE) / 2 = 0.6525: see
-# test_reference_output_is_closer_to_the_supersampled_truth.  With a 4 x 4 supersample as the truth the same rule gives 0.43955 (recorded only).
-R_EDGE = 0.305
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
 
 def test_library_exports_the_entry_point():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert NAME in _lib.EXPORTS and hasattr(L, NAME)
-    assert NAME in _header().split("VERSIONING.")[1].split("*/")[0]
-    assert NAME in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+    assert NAME in header().split("VERSIONING.")[1].split("*/")[0]
+    assert NAME in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     assert re.search(r"int\s+pt_edge_aa_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_edge_aa_desc\s*\*\s*\w+\s*,\s*pt_edge_aa_stats\s*\*", src)
     assert b"0.4" in L.pt_version()
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, St = _lib.EdgeAaDesc, _lib.EdgeAaStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in St._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(St)] + [getattr(St, n).offset for n in STATS_FIELDS]
-    assert mine == [72, 0, 8, 16, 24, 32, 40, 48, 56, 60, 64] + [48, 0, 8, 16, 24, 32, 40]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_edge_aa_desc)"] + [f"offsetof(pt_edge_aa_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_edge_aa_stats)"] +
-                     [f"offsetof(pt_edge_aa_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.EdgeAaDesc, "pt_edge_aa_desc", DESC_FIELDS), (_lib.EdgeAaStats, "pt_edge_aa_stats", STATS_FIELDS)],
+                 [72, 0, 8, 16, 24, 32, 40, 48, 56, 60, 64] + [48, 0, 8, 16, 24, 32, 40])
     assert {k: _lib.EDGE_AA_PLANES[k] for k in E.PLANES} == E.WORDS and _lib.EDGE_AA_OUTPUTS == E.PLANES
 
 
@@ -78,11 +56,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.flags = PT_EDGE_AA_RESERVED;\n"
             "    return pt_edge_aa_planes(c, &d, &s) || s.blended > s.boundary || s.hits + s.stale > s.pixels;\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_arguments_are_refused_without_a_gpu():
@@ -98,21 +72,18 @@ def test_facades_have_the_method(tmp_path):
     import torch  # noqa: F401
 
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     assert callable(getattr(R.SampleRenderer, "edgeAaPlanes", None)) and callable(getattr(R._RankView, "edgeAaPlanes", None))
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams, r._nv = 0, R.LaunchParams(), [5, 3]
-    r.launchParams.frame.size = (4, 4)
-    color, hit, position = _fake_cuda((4, 4, 4)), _fake_cuda((4, 4, 8)), _fake_cuda((4, 4, 4))
+    r = bare_renderer()
+    color, hit, position = fake_cuda((4, 4, 4)), fake_cuda((4, 4, 8)), fake_cuda((4, 4, 4))
     with pytest.raises(ValueError, match="hit is required"):
         r.edgeAaPlanes(color, None, position)
     with pytest.raises(ValueError, match="color is required"):
         r.edgeAaPlanes(None, hit, position)
     with pytest.raises(ValueError, match=r"edge: a contiguous torch.float32 tensor of shape \(4, 4, 2\) is expected"):
-        r.edgeAaPlanes(color, hit, position, out=_fake_cuda((4, 4, 4)), edge=_fake_cuda((4, 4)))
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+        r.edgeAaPlanes(color, hit, position, out=fake_cuda((4, 4, 4)), edge=fake_cuda((4, 4)))
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t aa(SampleRenderer& sample, pt_edge_aa_desc d) {\n"
@@ -122,12 +93,10 @@ def test_facades_have_the_method(tmp_path):
         "    return sample.edgeAaPlanes(d).blended + s.boundary;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_rule():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
-    text = text.split("GEOMETRIC EDGE ANTIALIASING")[1].split("The acceleration structure as the traversal kernels see it")[0]
+    text = header_section("GEOMETRIC EDGE ANTIALIASING", "The acceleration structure as the traversal kernels see it")
     for item in ("(dx, dy) = (-1, 0), (+1, 0), (0, -1), (0, +1)", "exponent-bit test", "p and q are not both misses", "hit[q].prim == hit[p].prim",
                  "dot3(ng_p, ng_q) >= normal_cos", "fabsf(dot3(ng_p, position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t",
                  "stats->boundary counts the pixels with at least one candidate", "hit[p].t <= hit[q].t, else q", "q owns",
@@ -145,14 +114,11 @@ def test_header_states_the_rule():
 
 # ------------------------------------------------------------------ the reference on CPU-built planes
 _CACHE = {}
-INPUTS = {"cornell": (scenes.cornell_box, scenes.CORNELL_CAMERA), "textured": (S.textured_scene, dict(eye=(2.0, 0.35, -3.0), lookat=(0.0, 0.2, 0.5), up=(0.0, 1.0, 0.0), fovY=35.0))}
 
 
 def cpu_case(orc, name):
     """the scene's CPU-built planes at W x H under its camera, the pixel-centre albedo as the colour, and the reference's result"""
     if name not in _CACHE:
-        from test_gpu_gbuffer import _row
-
         make, cam = INPUTS[name]
         model = make()
         c = dict(model=model, sc=S.scene_arrays(model), cam=cam, row=_row(cam, W / H))
@@ -169,11 +135,6 @@ def cpu_case(orc, name):
 
 def ref_args(c, w=W, h=H):
     return (c["hit"], c["position"], c["color"], c["verts"], c["idx"], [(0, 0, w, h)], [c["row"]], np.ones((h, w), bool))
-
-
-def supersampled_truth(albedo_big, s=SUPER):
-    """(s*h, s*w, >=3) float32 pixel-centre albedo of the s times larger frame -> (h, w, 3) float64"""
-    return E.box_average(np.asarray(albedo_big)[..., 0:3], s)
 
 
 @pytest.mark.parametrize("name", ["cornell", "textured"])

@@ -3,15 +3,13 @@ the ctypes mirrors match the compiler's layout, the header compiles as C99 and C
 any device work, both facades have the methods; and properties of the NumPy reference (tests/exposure_ref.py) that pin what the rules
 mean.  No bound here comes from a kernel's output: (f)'s are derived from the operators' formulas in the test's own docstring."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import exposure_ref as X
-from conftest import ROOT
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_section
 from optixpathtracer_amd import _lib
 
 f32 = np.float32
@@ -24,17 +22,13 @@ T_DESC = ("color", "state", "out", "frame_rgba8", "block_mask", "exposure", "whi
 T_STATS = ("pixels", "clipped", "kernel_ms")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_library_exports_the_entry_points():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name, stem in zip(NAMES, ("exposure", "tonemap")):
         assert name in _lib.EXPORTS and hasattr(L, name)
-        assert name in _header().split("VERSIONING.")[1].split("*/")[0]
-        assert name in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+        assert name in header().split("VERSIONING.")[1].split("*/")[0]
+        assert name in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
         assert re.search(rf"int\s+{name}\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_{stem}_desc\s*\*\s*\w+\s*,\s*pt_{stem}_stats\s*\*", src)
     assert b"0.4" in L.pt_version()
     assert (_lib.PT_EXPOSURE_BINS, _lib.PT_EXPOSURE_ACCUMULATE, _lib.PT_EXPOSURE_FROM_HISTOGRAM) == (256, 1, 2) == (X.BINS, 1, 2)
@@ -44,21 +38,9 @@ def test_library_exports_the_entry_points():
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    structs = (("pt_exposure_desc", _lib.ExposureDesc, E_DESC), ("pt_exposure_stats", _lib.ExposureStats, E_STATS),
-               ("pt_tonemap_desc", _lib.TonemapDesc, T_DESC), ("pt_tonemap_stats", _lib.TonemapStats, T_STATS))
-    mine, args = [], []
-    for cname, S, fields in structs:
-        assert [n for n, _ in S._fields_] == list(fields)
-        mine += [C.sizeof(S)] + [getattr(S, n).offset for n in fields]
-        args += [f"sizeof({cname})"] + [f"offsetof({cname}, {n})" for n in fields]
-    assert mine == [80, 0, 8, 16, 24, 32, 40, 48, 52, 56, 60, 64, 68, 72, 76] + [48, 0, 8, 16, 24, 32, 40] + [56, 0, 8, 16, 24, 32, 40, 44, 48, 52] + [24, 0, 8, 16]
-    fmt = " ".join(["%zu"] * len(mine))
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {", ".join(args)}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    structs = [(_lib.ExposureDesc, "pt_exposure_desc", E_DESC), (_lib.ExposureStats, "pt_exposure_stats", E_STATS),
+               (_lib.TonemapDesc, "pt_tonemap_desc", T_DESC), (_lib.TonemapStats, "pt_tonemap_stats", T_STATS)]
+    check_layout(tmp_path, structs, [80, 0, 8, 16, 24, 32, 40, 48, 52, 56, 60, 64, 68, 72, 76] + [48, 0, 8, 16, 24, 32, 40] + [56, 0, 8, 16, 24, 32, 40, 44, 48, 52] + [24, 0, 8, 16])
     assert _lib.EXPOSURE_PLANES == {"color": 4, "hit": 8} and _lib.TONEMAP_PLANES == {"color": 4, "out": 4, "frame_rgba8": 1}
     assert _lib.TONEMAP_OUTPUTS == ("out", "frame_rgba8")
 
@@ -78,11 +60,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    return pt_exposure_planes(c, &d, &s) || pt_tonemap_planes(c, &t, &ts) || s.under + s.over + s.skipped + s.nonfinite > s.pixels\n"
             "           || ts.clipped > ts.pixels || bins[0] != 1u;\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_arguments_are_refused_without_a_gpu():
@@ -103,26 +81,23 @@ def test_facades_have_the_methods(tmp_path):
     import torch  # noqa: F401
 
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     for name in ("exposurePlanes", "tonemapPlanes"):
         assert callable(getattr(R.SampleRenderer, name, None)) and callable(getattr(R._RankView, name, None))
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams, r._nv = 0, R.LaunchParams(), [5, 3]
-    r.launchParams.frame.size = (4, 4)
-    color = _fake_cuda((4, 4, 4))
+    r = bare_renderer()
+    color = fake_cuda((4, 4, 4))
     with pytest.raises(ValueError, match="color is required"):
         r.exposurePlanes(None)
     with pytest.raises(ValueError, match=r"hit: a contiguous torch.float32 tensor of shape \(4, 4, 8\) is expected"):
-        r.exposurePlanes(color, hit=_fake_cuda((4, 4, 4)))
+        r.exposurePlanes(color, hit=fake_cuda((4, 4, 4)))
     with pytest.raises(ValueError, match="color is required"):
         r.tonemapPlanes(None)
     with pytest.raises(ValueError, match="unknown operator 'filmic'"):
         r.tonemapPlanes(color, op="filmic")
     with pytest.raises(ValueError, match="no output asked for"):
         r.tonemapPlanes(color, write_out=False)
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t expose(SampleRenderer& sample, pt_exposure_desc d, pt_tonemap_desc t) {\n"
@@ -136,12 +111,10 @@ def test_facades_have_the_methods(tmp_path):
         "    return sample.exposurePlanes(d).under + s.over + sample.tonemapPlanes(t).clipped + ts.pixels;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_rules():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
-    text = text.split("AUTO EXPOSURE AND DISPLAY TONE MAPPING")[1].split("The acceleration structure as the traversal kernels see it")[0]
+    text = header_section("AUTO EXPOSURE AND DISPLAY TONE MAPPING", "The acceleration structure as the traversal kernels see it")
     for item in ("nv = max(1, the view count)", "hist: nv x PT_EXPOSURE_BINS uint32", "PT_EXPOSURE_ACCUMULATE — hist is not zeroed first",
                  "PT_EXPOSURE_FROM_HISTOGRAM — no metering, hist is read as given", "all-reduces the integer histograms",
                  "hit[p].prim is negative (a miss), the pixel is not counted: stats->skipped", "no address is formed from it", "exponent-bit test",

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import filter_ref as F
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -22,35 +23,20 @@ DESC_FIELDS = ("color", "hit", "position", "variance", "length", "out", "scratch
 STATS_FIELDS = ("pixels", "filtered", "spatial", "kernel_ms")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_library_exports_the_entry_point():
     L = _lib.load_library()
     assert "pt_filter_planes" in _lib.EXPORTS and hasattr(L, "pt_filter_planes")
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert re.search(r"int\s+pt_filter_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_filter_desc\s*\*\s*\w+\s*,\s*pt_filter_stats\s*\*", src)
     assert re.search(r"PT_FILTER_RESERVED\s*=\s*0\b", src)
     assert L.pt_version().startswith(b"ptamd 0.4")
-    assert "pt_filter_planes" in _header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
-    assert "pt_filter_planes" in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+    assert "pt_filter_planes" in header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
+    assert "pt_filter_planes" in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, S = _lib.FilterDesc, _lib.FilterStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in S._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(S)] + [getattr(S, n).offset for n in STATS_FIELDS]
-    assert mine == [96] + [8 * k for k in range(9)] + [72, 76, 80, 84, 88, 92] + [32, 0, 8, 16, 24]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_filter_desc)"] + [f"offsetof(pt_filter_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_filter_stats)"] +
-                     [f"offsetof(pt_filter_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.FilterDesc, "pt_filter_desc", DESC_FIELDS), (_lib.FilterStats, "pt_filter_stats", STATS_FIELDS)],
+                 [96] + [8 * k for k in range(9)] + [72, 76, 80, 84, 88, 92] + [32, 0, 8, 16, 24])
     assert set(_lib.FILTER_PLANES) == set(DESC_FIELDS[:8]) and _lib.FILTER_OUTPUTS == ("out", "scratch", "frame_rgba8")
 
 
@@ -62,11 +48,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.color = color; d.hit = hit; d.out = out; d.flags = PT_FILTER_RESERVED;\n"
             "    return pt_filter_planes(c, &d, &s);\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -82,22 +64,6 @@ def test_null_context_and_null_description_are_refused_without_a_gpu():
     assert body.index("null description") < body.index("ctx->width")
 
 
-def _fake_cuda(shape, dtype=None):
-    """A CPU tensor that reports CUDA device 0: enough for the checks that run before the library is called."""
-    import torch
-
-    class Fake(torch.Tensor):
-        @property
-        def is_cuda(self):
-            return True
-
-        @property
-        def device(self):
-            return torch.device("cuda", 0)
-
-    return torch.zeros(shape, dtype=dtype or torch.float32).as_subclass(Fake)
-
-
 def test_python_facade_checks_its_arguments():
     import torch
 
@@ -105,10 +71,8 @@ def test_python_facade_checks_its_arguments():
 
     assert callable(getattr(R.SampleRenderer, "filterPlanes", None))
     # the method on an object without a context: what it refuses, it refuses before the library is called
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams = 0, R.LaunchParams()
-    r.launchParams.frame.size = (4, 4)
-    ok = dict(color=_fake_cuda((4, 4, 4)), hit=_fake_cuda((4, 4, 8)), position=_fake_cuda((4, 4, 4)), out=1, scratch=1)
+    r = bare_renderer()
+    ok = dict(color=fake_cuda((4, 4, 4)), hit=fake_cuda((4, 4, 8)), position=fake_cuda((4, 4, 4)), out=1, scratch=1)
     with pytest.raises(ValueError, match="filterPlanes: hit is required"):
         r.filterPlanes(**dict(ok, hit=None))
     with pytest.raises(TypeError, match="filterPlanes: color: a torch tensor or a device pointer"):
@@ -120,13 +84,13 @@ def test_python_facade_checks_its_arguments():
         r.filterPlanes(**ok)
     r._device = 0
     with pytest.raises(ValueError, match=r"filterPlanes: variance: a contiguous torch.float32 tensor of shape \(4, 4\) is expected"):
-        r.filterPlanes(**ok, variance=_fake_cuda((4, 4, 1)))
+        r.filterPlanes(**ok, variance=fake_cuda((4, 4, 1)))
     with pytest.raises(ValueError, match="filterPlanes: length: a contiguous torch.float32"):
-        r.filterPlanes(**ok, length=_fake_cuda((4, 4), torch.float64))
+        r.filterPlanes(**ok, length=fake_cuda((4, 4), torch.float64))
     with pytest.raises(ValueError, match="filterPlanes: hit: a contiguous"):
-        r.filterPlanes(**dict(ok, hit=_fake_cuda((8, 4, 4)).permute(2, 1, 0)))
+        r.filterPlanes(**dict(ok, hit=fake_cuda((8, 4, 4)).permute(2, 1, 0)))
     with pytest.raises(ValueError, match="frame_rgba8: a contiguous torch.int32 tensor of shape .4, 4. or torch.uint8 tensor of shape .4, 4, 4. is expected"):
-        r.filterPlanes(**ok, frame=_fake_cuda((4, 4)))
+        r.filterPlanes(**ok, frame=fake_cuda((4, 4)))
     with pytest.raises(ValueError, match="iterations must be in"):
         r.filterPlanes(**ok, iterations=7)
     with pytest.raises(ValueError, match="the mask needs"):
@@ -135,8 +99,8 @@ def test_python_facade_checks_its_arguments():
 
 
 def test_cxx_facade_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t filter(SampleRenderer& sample, pt_filter_desc d) {\n"
@@ -146,11 +110,10 @@ def test_cxx_facade_compiles(tmp_path):
         "    return sample.filterPlanes(d).filtered + s.spatial;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("lum(c) = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z", "sel_max0(v) = v > 0 ? v : 0", "sel_min80(v) = v < 80 ? v : 80",
                  "these are not fmaxf / fminf", "p is inert when hit[p].prim < 0", "exponent-bit test", "p itself always counts",
                  "fabsf(dot3(ng_p, position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t", "length[p] < (float)min_length",

@@ -7,8 +7,8 @@ pt_version() stays "ptamd 0.4": five existing tests pin that string, and it name
 import ctypes as C
 import os
 import re
-import subprocess
 
+from cabi_kit import check_layout, compile_c99_and_cxx17, compile_facade, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -16,33 +16,18 @@ DESC_FIELDS = ("hit", "depth", "position", "motion", "ray", "prev_cameras", "num
 STATS_FIELDS = ("pixels", "hits", "kernel_ms")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_library_exports_the_entry_point():
     L = _lib.load_library()
     assert "pt_render_gbuffer" in _lib.EXPORTS and hasattr(L, "pt_render_gbuffer")
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert re.search(r"int\s+pt_render_gbuffer\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_gbuffer_desc\s*\*\s*\w+\s*,\s*pt_gbuffer_stats\s*\*", src)
     assert L.pt_version().startswith(b"ptamd 0.4")
-    assert "pt_render_gbuffer" in _header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
+    assert "pt_render_gbuffer" in header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, S = _lib.GBufferDesc, _lib.GBufferStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in S._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(S)] + [getattr(S, n).offset for n in STATS_FIELDS]
-    assert mine == [64, 0, 8, 16, 24, 32, 40, 48, 56, 24, 0, 8, 16]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_gbuffer_desc)"] + [f"offsetof(pt_gbuffer_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_gbuffer_stats)"] +
-                     [f"offsetof(pt_gbuffer_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.GBufferDesc, "pt_gbuffer_desc", DESC_FIELDS), (_lib.GBufferStats, "pt_gbuffer_stats", STATS_FIELDS)],
+                 [64, 0, 8, 16, 24, 32, 40, 48, 56, 24, 0, 8, 16])
     assert _lib.GBUFFER_PLANES == {"hit": 8, "depth": 1, "position": 4, "motion": 2, "ray": 8} and C.sizeof(_lib.Hit) == 4 * _lib.GBUFFER_PLANES["hit"]
 
 
@@ -54,11 +39,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.depth = depth; d.prev_cameras = prev; d.num_prev_cameras = 1;\n"
             "    return pt_render_gbuffer(c, &d, &s);\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -82,8 +63,8 @@ def test_python_facade_has_the_method():
 
 
 def test_cxx_facade_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t first_hits(SampleRenderer& sample, float* d_depth, float* d_motion, const float* prev) {\n"
@@ -97,11 +78,10 @@ def test_cxx_facade_compiles(tmp_path):
         "    return sample.renderGBuffer(d).hits + s.pixels;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("dx = 2 * ((x + 0.5f) / width) - 1", "tmin 0.001f, tmax 1e16f", "t * dot3(dir, normalize3(W))", "a miss holds +inf (0x7f800000)",
                  "px = (((a / c) + 1) * 0.5f) * width - 0.5f", "both words are 0x7fc00000", "A pixel outside that set is not written in any plane",
                  "Zero active pixels launch nothing and return PT_OK", "all five planes NULL", "motion without prev_cameras",

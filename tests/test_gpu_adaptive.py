@@ -5,9 +5,9 @@ blocks must leave, in those blocks, the bits of the full frames — in all five 
 import numpy as np
 import pytest
 
+from adaptive_ref import block_slots, rule_sides, stop_rule
 from conftest import assert_bits_equal
 from optixpathtracer_amd import scenes
-from test_adaptive_cabi import block_slots, rule_sides, stop_rule
 
 pytestmark = pytest.mark.gpu
 

@@ -6,28 +6,9 @@ import numpy as np
 import pytest
 
 from optixpathtracer_amd import scenes
+from scene_kit import _canonical
 
 pytestmark = pytest.mark.gpu
-
-
-def _canonical(nodes_bytes, tris_bytes):
-    """The exported tree without its node numbering: k_collapse8 hands out child and triangle ranges with atomic counters, so the order
-    of the nodes inside a level (and of the leaf-triangle groups) differs from build to build.  Walk from the root in slot order and
-    emit every node's content (grid, masks, planes) and its leaf triangles: equal trees give equal bytes."""
-    N = np.frombuffer(nodes_bytes, np.uint32).reshape(-1, 20)
-    T = np.frombuffer(tris_bytes, np.uint32).reshape(-1, 12)
-    out_nodes, out_tris = [], []
-    stack = [0]
-    while stack:
-        i = stack.pop()
-        nd = N[i]
-        child_base, tri_base, leafbits, imask = int(nd[4]), int(nd[5]), int(nd[6]), int(nd[7]) >> 16
-        out_nodes.append(np.concatenate([nd[:4], nd[6:]]))
-        ntri = bin(leafbits).count("1")
-        out_tris.append(T[tri_base:tri_base + ntri])
-        kids = [child_base + k for k in range(bin(imask).count("1"))]
-        stack.extend(reversed(kids))
-    return np.concatenate(out_nodes).tobytes(), np.concatenate(out_tris).tobytes(), len(out_nodes)
 
 
 def _export(model, monkeypatch, **env):

@@ -20,9 +20,9 @@ import numpy as np
 import pytest
 
 from conftest import assert_bits_equal
+from depth_limit_scene import CAMERA, DEEP_DEPTHS, LAMBERT, SPP_DEEP, SPP_EDGE, S_DEEP, S_EDGE, H, W, checker_frame, sky, skylight_box
 from optixpathtracer_amd import scenes
-from test_depth_limit_scene import CAMERA, DEEP_DEPTHS, H, LAMBERT, S_DEEP, S_EDGE, SPP_DEEP, SPP_EDGE, W, checker_frame, sky, skylight_box
-from test_gpu_parity import _check_sched, _compare, _gpu_render, _oracle_render, _renderer
+from parity_kit import _check_sched, _compare, _gpu_render, _oracle_render, _renderer
 
 pytestmark = pytest.mark.gpu
 

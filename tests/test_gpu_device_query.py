@@ -9,12 +9,11 @@ import pytest
 import torch
 
 from conftest import assert_bits_equal
-from optixpathtracer_amd import _lib
+from gpu_kit import _dev_all
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_device_update import M1, _dev_all, _np_transform
-from test_gpu_parity import _compare, _gpu_render, _random_rays, _renderer
-from test_gpu_refit import _wave, _with_vertices
+from parity_kit import _compare, _gpu_render, _random_rays, _renderer
+from scene_kit import M1, _np_transform, _wave, _with_vertices
 
 pytestmark = pytest.mark.gpu
 

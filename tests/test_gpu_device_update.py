@@ -5,11 +5,11 @@ import numpy as np
 import pytest
 import torch
 
-from optixpathtracer_amd import renderer as R
+from gpu_kit import _dev, _dev_all
 from optixpathtracer_amd import scenes
-from test_gpu_builder import _canonical
-from test_gpu_parity import _compare, _gpu_render, _oracle_render, _renderer
-from test_gpu_refit import _moved, _wave, _with_vertices
+from optixpathtracer_amd import renderer as R
+from parity_kit import _compare, _gpu_render, _oracle_render, _renderer
+from scene_kit import M1, _affine, _canonical, _moved_mesh, _np_transform, _wave, _with_vertices
 
 pytestmark = pytest.mark.gpu
 
@@ -34,51 +34,7 @@ def clean_env(monkeypatch):
     return monkeypatch
 
 
-def _dev(v):
-    return torch.from_numpy(np.ascontiguousarray(v, np.float32)).to("cuda:0")
-
-
-def _dev_offset(v):
-    """The same tensor as a view one float into a larger allocation: 4-byte aligned, not 16-byte aligned."""
-    v = np.ascontiguousarray(v, np.float32)
-    buf = torch.zeros(v.size + 1, dtype=torch.float32, device="cuda:0")
-    t = buf[1:].view(len(v), 3)
-    t.copy_(torch.from_numpy(v))
-    assert t.is_contiguous() and t.data_ptr() % 16 == 4
-    return t
-
-
-def _dev_all(verts: dict, offset_mesh=None):
-    return {k: (_dev_offset(v) if k == offset_mesh else _dev(v)) for k, v in verts.items()}
-
-
-def _np_transform(M, v):
-    """The header's expression in float32, one rounding per operation: x' = ((m0 x + m1 y) + m2 z) + m3, ..."""
-    M = np.asarray(M, np.float32)[:3]
-    v = np.asarray(v, np.float32)
-    x, y, z = v[:, 0], v[:, 1], v[:, 2]
-    out = np.empty_like(v)
-    for r in range(3):
-        m = M[r]
-        out[:, r] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]
-    assert out.dtype == np.float32
-    return out
-
-
-def _affine(axis, angle, scale, translate):
-    """translate . rotate(axis, angle) . scale as a float32 3x4, composed in float64."""
-    a = np.asarray(axis, np.float64)
-    a /= np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    Rm = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
-    M = np.zeros((3, 4))
-    M[:, :3] = Rm @ np.diag(scale)
-    M[:, 3] = translate
-    return M.astype(np.float32)
-
-
 IDENTITY = np.eye(4, dtype=np.float32)[:3]
-M1 = _affine((1.0, 2.0, -0.5), 0.7, (1.3, 0.8, 1.1), (0.4, 0.25, -0.3))
 M2 = _affine((-0.3, 1.0, 0.9), -1.1, (0.9, 1.2, 0.7), (-0.2, 0.1, 0.5))
 
 
@@ -95,7 +51,7 @@ def _same_vertices(r, model, expect: dict, rest=False):
 
 def _same_tree(a, b):
     """Two contexts' trees, byte for byte up to the numbering of the nodes: k_collapse8 hands out node and triangle ranges with atomic
-    counters, so two builds of one scene number their nodes differently (test_gpu_builder._canonical), and a refit keeps the numbering."""
+    counters, so two builds of one scene number their nodes differently (scene_kit._canonical), and a refit keeps the numbering."""
     (n0, t0), (n1, t1) = a.exportBVH(), b.exportBVH()
     assert n0.shape == n1.shape and t0.shape == t1.shape
     assert _canonical(n0.tobytes(), t0.tobytes()) == _canonical(n1.tobytes(), t1.tobytes())
@@ -118,7 +74,7 @@ def test_device_update_equals_host_update(ptlib, clean_env, terrain, scene, rebu
     _same_tree(d, h)
     # a raw pointer with its vertex count, one mesh of several
     k = len(model.meshes) - 1
-    one = _moved(model, k, (0.25, -0.5, 0.125))
+    one = _moved_mesh(model, k, (0.25, -0.5, 0.125))
     t = _dev(one[k])
     d.updateMeshesDevice({k: (t.data_ptr(), len(one[k]))}, rebuild=rebuild)
     h.updateMeshes(one, rebuild=rebuild)
@@ -147,7 +103,7 @@ def test_device_update_render_equals_fresh_build_and_checker(ptlib, orc_det, cle
 
 def test_device_update_shadow_catcher_scene(ptlib, orc_det, clean_env, probe):
     A = scenes.two_box_scene(shadow_catcher=True)
-    up = _moved(A, len(A.meshes) - 1, (0.35, 0.1, -0.2))
+    up = _moved_mesh(A, len(A.meshes) - 1, (0.35, 0.1, -0.2))
     B = _with_vertices(A, up)
     cam = scenes.TWO_BOX_CAMERA
     r = _renderer(A, probe, cam, W, H)
@@ -236,13 +192,13 @@ def test_rest_against_current(ptlib, clean_env):
     r.transformMeshes({1: M1})
     _same_vertices(r, A, {0: both, 1: _np_transform(M1, v1)})
     # an explicit update resets that mesh's rest positions (host and device path), the other mesh's stay
-    e0 = _moved(A, 0, (0.5, 0.25, -0.75))[0]
+    e0 = _moved_mesh(A, 0, (0.5, 0.25, -0.75))[0]
     r.updateMeshes({0: e0})
     _same_vertices(r, A, {0: e0}, rest=True)
     _same_vertices(r, A, {0: e0, 1: _np_transform(M1, v1)})
     r.transformMeshes({0: M2})
     _same_vertices(r, A, {0: _np_transform(M2, e0), 1: _np_transform(M1, v1)})
-    e1 = _moved(A, 1, (-0.125, 0.0, 0.375))[1]
+    e1 = _moved_mesh(A, 1, (-0.125, 0.0, 0.375))[1]
     r.updateMeshesDevice({1: _dev(e1)})
     _same_vertices(r, A, {0: e0, 1: e1}, rest=True)
     r.transformMeshes({1: M2, 0: IDENTITY})

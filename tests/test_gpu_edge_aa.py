@@ -3,7 +3,7 @@ outside the chosen set shows as a lost sentinel), with tests/edge_aa_ref.py: flo
 renderGBuffer gave (or hand-made ones), the current vertices and the cameras.  All five counters are compared exactly.  NaN words compare as
 NaN (payloads are not specified).  Frames are 131 x 59 and smaller.
 
-One check carries a meaning beyond the reference, with its bound recorded by tests/test_edge_aa_cabi.py from the references alone: the
+One check carries a meaning beyond the reference, with its bound (edge_aa_ref.R_EDGE) measured by tests/test_edge_aa_cabi.py from the references alone: the
 output is closer than the input to the 8 x 8 supersampled albedo (R_EDGE)."""
 import ctypes as C
 
@@ -14,14 +14,18 @@ import torch
 import edge_aa_ref as E
 import motion_ref as M
 import surface_ref as S
-from optixpathtracer_amd import _lib
+from edge_aa_ref import INPUTS, R_EDGE, SUPER, H, W, supersampled_truth
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame_mask
+from gpu_kit import bits3 as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import same_words as _same
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from gpu_kit import words_differ as _differ
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_edge_aa_cabi import INPUTS, R_EDGE, SUPER, H, W, supersampled_truth
-from test_gpu_device_update import _affine
-from test_gpu_gbuffer import _hip_runtime, _renderer
-from test_gpu_temporal import _upload
-from test_gpu_views import RECTS
+from scene_kit import RECTS, _affine
 
 pytestmark = pytest.mark.gpu
 
@@ -31,38 +35,9 @@ COUNTERS = ("pixels", "hits", "stale", "boundary", "blended")
 NAN, INF = f32(np.nan), f32(np.inf)
 
 
-def _bits(t):
-    a = t.cpu().numpy().view(np.uint32)
-    return a.reshape(a.shape[0], a.shape[1], -1)
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _frame(w=W, h=H):
-    return np.ones((h, w), bool)
-
-
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane; offset: one float into its allocation (4-byte aligned only)"""
-    n = h * w * E.WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = buf[1:] if offset else buf[:-1]
-    t = t.view((h, w, E.WORDS[name]) if E.WORDS[name] > 1 else (h, w))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t.view(torch.int32) if name == "frame_rgba8" else t
-
-
-def _differ(a, b):
-    with np.errstate(all="ignore"):
-        return (a != b) & ~(np.isnan(a.view(f32)) & np.isnan(b.view(f32)))
-
-
-def _same(got, ref, what):
-    for name, a in got.items():
-        neq = _differ(a, ref[name]) if name != "frame_rgba8" else a != ref[name]
-        assert a.shape == ref[name].shape and not neq.any(), f"{what}: {name} differs in {int(neq.sum())} words, first at {np.argwhere(neq)[:3].tolist()}"
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, E.WORDS[name]), offset, torch.int32 if name == "frame_rgba8" else torch.float32)
 
 
 class _Case:
@@ -129,8 +104,8 @@ def _check_edge_plane(got, pixels, what):
         assert not (pixels & (full == k + 1) & ~neighbour_in_set).any(), f"{what}: a pixel was blended with a neighbour outside the set (direction {k})"
 
 
-def _pixel_mask(block_mask, h=H, w=W):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:h, :w]
+def _frame(w=W, h=H):
+    return whole_frame_mask(h, w)
 
 
 # ------------------------------------------------------------------ 1. the pass against the reference
@@ -279,7 +254,7 @@ def test_block_mask_and_rank_1_of_3(ptlib, orc_det):
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.5
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     ref, got, st = _run(c.r, orc_det, c, px, "a random block mask", mask=mask)
     assert 0 < st["pixels"] < W * H and all((got[n][~px] == SENTINEL).all() for n in E.PLANES)
     _check_edge_plane(got, px, "a random block mask")
@@ -452,7 +427,7 @@ def test_under_a_busy_torch_stream(ptlib, orc_det, mode):
     """tests/test_gpu_stream_contract.py's protocol for this entry point: the three inputs are produced, and the three outputs
     sentinel-filled, by work still pending on torch's current stream when the call is made; the result equals the synchronous call's, and
     that equals the reference"""
-    from test_gpu_stream_contract import _pin, _res
+    from stream_kit import _pin, _res
 
     c = _case("cornell")
     outs = {n: _filled(n, H, W) for n in E.PLANES}

@@ -10,12 +10,16 @@ import pytest
 import torch
 
 import exposure_ref as X
-from optixpathtracer_amd import _lib
+from gpu_kit import filled, pixel_mask, plane_shape
+from gpu_kit import bits3 as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from gpu_kit import words_differ as _differ
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_gbuffer import _hip_runtime, _renderer
-from test_gpu_temporal import _upload
-from test_gpu_views import RECTS
+from scene_kit import RECTS
 
 pytestmark = pytest.mark.gpu
 
@@ -26,15 +30,6 @@ GUARD = 4  # sentinel words on either side of hist and of the state
 SENTINEL = X.SENTINEL
 CAM = scenes.CORNELL_CAMERA
 PRM = dict(low_permille=50, high_permille=20, key_log2=-2.4739312, ev_min=-16.0, ev_max=16.0, rate_up=1.0, rate_down=1.0)
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _differ(a, b):
-    with np.errstate(all="ignore"):
-        return (a != b) & ~(np.isnan(a.view(f32)) & np.isnan(b.view(f32)))
 
 
 def _guarded(rows, width, dtype, offset=False, content=None):
@@ -58,16 +53,7 @@ def _guards_intact(buf, t, what):
 
 def _plane(name, h, w, offset=False):
     """a sentinel-filled output plane of the tone mapper"""
-    k = 4 if name == "out" else 1
-    buf = torch.full((4 * (h * w * k + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = (buf[1:] if offset else buf[:-1]).view((h, w, k) if k > 1 else (h, w))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t.view(torch.int32) if name == "frame_rgba8" else t
-
-
-def _bits(t):
-    a = _np(t).view(u32)
-    return a.reshape(a.shape[0], a.shape[1], -1)
+    return filled(plane_shape(h, w, 4 if name == "out" else 1), offset, torch.int32 if name == "frame_rgba8" else torch.float32)
 
 
 def _all(h=H, w=W):
@@ -162,10 +148,6 @@ def _cornell():
 def _plain(size):
     """a renderer of the given size on the Cornell box; no frame is rendered"""
     return _renderer(scenes.cornell_box(), size, CAM)
-
-
-def _pixel_mask(block_mask, h=H, w=W):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:h, :w]
 
 
 # ------------------------------------------------------------------ 1. the meter and the adaptation against the reference
@@ -322,14 +304,14 @@ def test_block_masks_partitions_and_accumulate(ptlib, orc_det):
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.5
     mask[0, 0] = mask[nby - 1, nbx - 1] = True
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     gh, gs, st = _meter(c.r, c.color, px, "a random block mask", hit=c.hit, mask=mask)
     assert 0 < st["pixels"] < W * H
     _tone(c.r, orc_det, c.color, px, "a random block mask", state=gs, mask=mask, op="aces")
     # ACCUMULATE over two calls equals one call on the union mask
     other = ~mask
     h1, _, _ = _meter(c.r, c.color, px, "the first half", hit=c.hit, mask=mask)
-    h2, s2, _ = _meter(c.r, c.color, _pixel_mask(other), "the second half, accumulated", hit=c.hit, mask=other, hist0=h1, accumulate=True)
+    h2, s2, _ = _meter(c.r, c.color, pixel_mask(other, h=H, w=W), "the second half, accumulated", hit=c.hit, mask=other, hist0=h1, accumulate=True)
     hw, sw, _ = _meter(c.r, c.color, _all(), "the whole frame", hit=c.hit)
     assert np.array_equal(h2, hw) and np.array_equal(s2.view(u32), sw.view(u32))
     # the empty mask: nothing is metered, the histogram is zeroed, the adaptation runs on it
@@ -386,7 +368,7 @@ def test_out_exactly_color(ptlib, orc_det):
     nby, nbx = c.r.blockGrid()
     mask = np.random.default_rng(9).random((nby, nbx)) < 0.6
     _tone(c.r, orc_det, c.color, _all(), "in place", in_place=True, op="aces", exposure=2.0)
-    _tone(c.r, orc_det, c.color, _pixel_mask(mask), "in place under a mask", in_place=True, mask=mask, op="reinhard")
+    _tone(c.r, orc_det, c.color, pixel_mask(mask, h=H, w=W), "in place under a mask", in_place=True, mask=mask, op="reinhard")
 
 
 def test_rendering_state_is_left_alone(ptlib):
@@ -547,7 +529,7 @@ def test_refusals(ptlib):
 def test_under_a_busy_torch_stream(ptlib, orc_det, mode):
     """tests/test_gpu_stream_contract.py's protocol for both entry points: the inputs are produced, and the outputs sentinel-filled, by work
     still pending on torch's current stream when the call is made; the result equals the synchronous call's, and that equals the reference"""
-    from test_gpu_stream_contract import _pin, _res
+    from stream_kit import _pin, _res
 
     c = _cornell()
     state = np.array([[0.5, 1.5, 0.0, 0.0]], f32)

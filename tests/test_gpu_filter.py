@@ -16,47 +16,30 @@ import pytest
 import torch
 
 import filter_ref as F
-from optixpathtracer_amd import _lib
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame
+from gpu_kit import bits as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_gbuffer import _hip_runtime, _renderer, _views_and_prev
-from test_gpu_views import RECTS
+from pass_cases import FILTER_INPUTS
+from pass_cases import filter_case as _case
+from scene_kit import RECTS, _views_and_prev
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 W, H = 131, 61
 SENTINEL = F.SENTINEL
-INPUTS = ("color", "hit", "position", "variance", "length")
 WORDS = _lib.FILTER_PLANES
 
 
 # ------------------------------------------------------------------ GPU helpers
-def _upload(a, offset=False):
-    """a float32 array as a CUDA tensor; offset: one float into its allocation (4-byte aligned only)"""
-    a = np.array(a, f32)  # (a copy: the shared planes are read-only)
-    buf = torch.empty(a.size + 1, dtype=torch.float32, device="cuda:0")
-    t = (buf[1:] if offset else buf[:-1]).view(a.shape)
-    t.copy_(torch.from_numpy(a))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t
-
-
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane"""
-    n = h * w * WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = buf[1:] if offset else buf[:-1]
-    t = t.view((h, w) if WORDS[name] == 1 else (h, w, WORDS[name]))
-    return t.view(torch.int32) if name == "frame_rgba8" else t
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _np(t):
-    return t.cpu().numpy()
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, WORDS[name]), offset, torch.int32 if name == "frame_rgba8" else torch.float32)
 
 
 def _same(out, frame, scratch, ref, pixels, what):
@@ -72,7 +55,7 @@ def _run(r, orc, planes, rects, pixels, what, mask=None, blocks=None, offset=Fal
     """uploads the planes, calls filterPlanes into sentinel-filled outputs, compares out and frame_rgba8 with the NumPy reference over the
     whole frame and scratch outside the set with its sentinel; returns (reference, stats)"""
     h, w = planes["hit"].shape[:2]
-    dev = {k: _upload(planes[k], offset) for k in INPUTS if planes.get(k) is not None}
+    dev = {k: _upload(planes[k], offset) for k in FILTER_INPUTS if planes.get(k) is not None}
     its = prm.get("iterations", F.DEFAULTS["iterations"])
     out = _filled("out", h, w, offset)
     scratch = _filled("scratch", h, w, offset) if its >= 1 else None
@@ -87,24 +70,8 @@ def _run(r, orc, planes, rects, pixels, what, mask=None, blocks=None, offset=Fal
     return ref, st
 
 
-_CASES = {}
-
-
-def _case(name):
-    """The input's renderer and its G-buffer planes with random colour, variance and length planes.  Built once; the arrays are read-only."""
-    if name not in _CASES:
-        make, size, cam, prm, seed = F.real_inputs()[name]
-        r = _renderer(make(), size, cam)
-        g = r.renderGBuffer(("hit", "position"))
-        planes = F.with_random_planes(dict(hit=_np(g["hit"]), position=_np(g["position"])), seed)
-        for a in planes.values():
-            a.setflags(write=False)
-        _CASES[name] = (r, planes, prm)
-    return _CASES[name]
-
-
 def _frame(w=W, h=H):
-    return [(0, 0, w, h)], np.ones((h, w), bool)
+    return whole_frame(w, h)
 
 
 # ------------------------------------------------------------------ 1. real planes
@@ -192,17 +159,13 @@ def test_views(ptlib, orc_det):
 
 
 # ------------------------------------------------------------------ 4. masks and partition
-def _pixel_mask(block_mask):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:H, :W]
-
-
 def test_masks(ptlib, orc_det):
     r, planes, prm = _case("two_box")
     nby, nbx = r.blockGrid()
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True  # corner and edge blocks, the 3-wide column and the 5-high row
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     ref, st = _run(r, orc_det, planes, [(0, 0, W, H)], px, "a random block mask", mask=mask, blocks=mask, **prm)
     assert 0 < st["pixels"] < W * H and ref["taps"]["block"].sum() > 0 and (ref["out"][~px] == SENTINEL).all()
     _run(r, orc_det, planes, [(0, 0, W, H)], px, "the mask, two passes", mask=mask, blocks=mask, iterations=2, **prm)
@@ -243,7 +206,7 @@ def test_context_buffers_as_planes(ptlib, orc_det):
     r.denoise(iterations=1)  # allocates PT_BUF_DENOISED
     nby, nbx = r.blockGrid()
     mask = np.random.default_rng(9).random((nby, nbx)) < 0.5
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     kinds = (R.PT_BUF_ACCUM, R.PT_BUF_FRAME, R.PT_BUF_COLOR, R.PT_BUF_NORMAL, R.PT_BUF_ALBEDO, R.PT_BUF_DENOISED)
     before = {k: r.download(k).view(np.uint32) for k in kinds}
     dev = {k: _upload(planes[k]) for k in ("hit", "position", "variance", "length")}
@@ -364,7 +327,7 @@ def test_refusals(ptlib, orc_det):
     _, planes, prm = _case("two_box")
     L = _lib.load_library()
     r = R.SampleRenderer(scenes.two_box_scene(shadow_catcher=False))
-    dev = {k: _upload(planes[k]) for k in INPUTS}
+    dev = {k: _upload(planes[k]) for k in FILTER_INPUTS}
     out = {k: _filled(k, H, W) for k in _lib.FILTER_OUTPUTS}
     ptr = {k: t.data_ptr() for k, t in list(dev.items()) + list(out.items())}
     good = dict(ptr, iterations=5, sigma_lum=4.0, normal_cos=0.9, plane_eps=0.01, min_length=4, flags=0)

@@ -16,21 +16,21 @@ import numpy as np
 import pytest
 import torch
 
-from optixpathtracer_amd import _lib
+from gbuffer_ref import PLANES, QNAN, _behind, _moved, _np_planes, _np_rays, _row
+from gpu_kit import filled, pixel_mask, plane_shape
+from gpu_kit import bits as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_device_update import M1, _np_transform
-from test_gpu_refit import _with_vertices
-from test_gpu_views import RECTS, _cam_dicts
+from scene_kit import M1, RECTS, _cam_dicts, _np_transform, _views_and_prev, _with_vertices
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 W, H = 131, 61
-PLANES = ("hit", "depth", "position", "motion", "ray")
 WORDS = _lib.GBUFFER_PLANES
 SENTINEL = 0xA5A5A5A5
-QNAN = 0x7FC00000
 INPUTS = {
     "two_box": (lambda: scenes.two_box_scene(shadow_catcher=False), (W, H), scenes.TWO_BOX_CAMERA, (4862, 3129)),
     "cornell": (scenes.cornell_box, (67, 45), scenes.CORNELL_CAMERA, (1899, 1116)),
@@ -39,94 +39,10 @@ INPUTS = {
 VIEW_COUNTS = [(1429, 828), (1172, 771), (301, 203), (25, 10)]
 
 
-# ------------------------------------------------------------------ float32 NumPy: the header's expressions, one rounding per operation
-def _row(cam_dict, aspect):
-    return R._camera_rows([R.make_camera(cam_dict, aspect)])[0]
-
-
-def _dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
-def _cross(a, b):
-    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2], a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
-
-
-def _normalize(v):
-    return v * (f32(1.0) / np.sqrt(_dot(v, v)))[..., None]
-
-
-def _np_rays(row, w, h):
-    """(h, w, 8): origin eye, tmin 0.001f, dir = normalize3((U*dx + V*dy) + W), tmax 1e16f"""
-    row = np.asarray(row, f32)
-    eye, U, V, Wv = row[0:3], row[3:6], row[6:9], row[9:12]
-    dx = f32(2.0) * ((np.arange(w, dtype=f32) + f32(0.5)) / f32(w)) - f32(1.0)
-    dy = f32(2.0) * ((np.arange(h, dtype=f32) + f32(0.5)) / f32(h)) - f32(1.0)
-    d = (U[None, None, :] * dx[None, :, None] + V[None, None, :] * dy[:, None, None]) + Wv[None, None, :]
-    d = _normalize(d)
-    rays = np.empty((h, w, 8), f32)
-    rays[..., 0:3] = eye
-    rays[..., 3] = f32(0.001)
-    rays[..., 4:7] = d
-    rays[..., 7] = f32(1e16)
-    assert d.dtype == f32
-    return rays
-
-
-def _np_planes(rays, t, hit, row, prev):
-    """depth (h, w), position (h, w, 4), motion (h, w, 2) as uint32 bits, from the NumPy rays, the checker's t and hit mask, the camera row and
-    the previous camera row"""
-    h, w = hit.shape
-    row, prev = np.asarray(row, f32), np.asarray(prev, f32)
-    o, d = rays[..., 0:3], rays[..., 4:7]
-    t = np.asarray(t, f32).reshape(h, w)
-    depth = np.where(hit, t * _dot(d, _normalize(row[9:12])[None, None, :]), f32(np.inf)).astype(f32)
-    P = o + t[..., None] * d
-    position = np.zeros((h, w, 4), f32)
-    position[..., 0:3] = np.where(hit[..., None], P, f32(0.0))
-    position[..., 3] = np.where(hit, f32(1.0), f32(0.0))
-    pe, pU, pV, pW = prev[0:3], prev[3:6], prev[6:9], prev[9:12]
-    q = np.where(hit[..., None], P - pe, d).astype(f32)
-    VxW = _cross(pV, pW)
-    with np.errstate(all="ignore"):
-        a, b, c, det = _dot(q, VxW), _dot(q, _cross(pW, pU)), _dot(q, _cross(pU, pV)), _dot(pU, VxW)
-        px = (((a / c) + f32(1.0)) * f32(0.5)) * f32(w) - f32(0.5)
-        py = (((b / c) + f32(1.0)) * f32(0.5)) * f32(h) - f32(0.5)
-        mx = px - np.arange(w, dtype=f32)[None, :]
-        my = py - np.arange(h, dtype=f32)[:, None]
-        ok = c * det > 0
-    for x in (depth, P, a, c, px, mx, my):
-        assert x.dtype == f32
-    motion = np.stack([mx, my], -1).view(np.uint32).copy()
-    motion[~ok] = QNAN
-    return depth.view(np.uint32), position.view(np.uint32), motion, ok
-
-
-def _moved(cam_dict, dx=0.25):
-    ex, ey, ez = cam_dict["eye"]
-    return dict(cam_dict, eye=(ex + dx, ey, ez))
-
-
-def _behind(cam_dict):
-    """behind the scene, looking away from it: the eye mirrored through the look-at point, keeping the viewing direction"""
-    e, l = np.asarray(cam_dict["eye"], np.float64), np.asarray(cam_dict["lookat"], np.float64)
-    far = l + 4.0 * (l - e)
-    return dict(cam_dict, eye=tuple(far), lookat=tuple(far + (l - e)))
-
-
 # ------------------------------------------------------------------ GPU helpers
 def _filled(name, h, w, offset=False):
-    """A sentinel-filled plane; offset: one float into its allocation (4-byte aligned only)"""
-    n = h * w * WORDS[name]
-    buf = torch.full((4 * (n + (1 if offset else 0)),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = buf[1:] if offset else buf
-    t = t.view((h, w) if name == "depth" else (h, w, WORDS[name]))
-    assert t.is_contiguous() and (t.data_ptr() % 16 == 4 if offset else t.data_ptr() % 16 == 0)
-    return t
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, WORDS[name]), offset)
 
 
 def _gbuffer(r, planes=PLANES, prev=None, mask=None, offset=False):
@@ -136,15 +52,6 @@ def _gbuffer(r, planes=PLANES, prev=None, mask=None, offset=False):
     res = r.renderGBuffer(planes, prev_cameras=prev, mask=mask, out=out)
     assert all(res[p] is out[p] for p in planes)
     return {p: _bits(out[p]) for p in planes}, res["stats"]
-
-
-def _renderer(model, size, cam_dict, partition=None):
-    r = R.SampleRenderer(model)
-    if partition:
-        r.setPartition(*partition)
-    r.resize(size)
-    r.setCamera(R.make_camera(cam_dict, size[0] / size[1]))
-    return r
 
 
 def _same(got, want, what, where=None):
@@ -261,13 +168,6 @@ def test_each_plane_alone(ptlib, orc_det, plane):
     assert stats["hits"] == c.counts[0] and stats["pixels"] == W * H
 
 
-# ------------------------------------------------------------------ 4. views
-def _views_and_prev():
-    views = [(x, y, w, h, R.make_camera(cd, w / h)) for (x, y, w, h), cd in zip(RECTS, _cam_dicts())]
-    prev = np.stack([_row(_moved(cd, 0.1 * (k + 1)), w / h) for k, ((x, y, w, h), cd) in enumerate(zip(RECTS, _cam_dicts()))])
-    return views, prev
-
-
 _VIEW_WANT = {}
 
 
@@ -309,10 +209,6 @@ def test_views(ptlib, monkeypatch, packets):
 
 
 # ------------------------------------------------------------------ 5. mask
-def _pixel_mask(block_mask):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:H, :W]
-
-
 def test_mask(ptlib, orc_det):
     c = _case("two_box", orc_det)
     nby, nbx = c.r.blockGrid()
@@ -320,7 +216,7 @@ def test_mask(ptlib, orc_det):
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True  # corner and edge blocks, the 3-wide column and the 5-high row
     mask[1, 1] = False
     got, stats = _gbuffer(c.r, prev=c.prev, mask=mask)
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     _same(got, c.full, "masked-in pixels", px)
     _untouched(got, ~px, "mask")
     c.r.setProbe(scenes.sky_probe(64, 32).BuildCDF())  # (renderMask renders; the G-buffer pass needs no probe)
@@ -421,19 +317,6 @@ def test_after_a_geometry_update(ptlib, orc_det, rebuild):
     r.close()
     _same(got, want, "after transformMeshes")
     assert stats["hits"] == wstats["hits"] and not np.array_equal(want["hit"], c.full["hit"])  # the update moved something under the camera
-
-
-# ------------------------------------------------------------------ 10. refusals
-def _hip_runtime():
-    """the HIP runtime this process already uses, for one allocation of an exact size"""
-    for line in open("/proc/self/maps"):
-        if "libamdhip64" in line:
-            hip = C.CDLL(line.split()[-1])
-            hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-            hip.hipFree.argtypes = [C.c_void_p]
-            hip.hipMemGetAddressRange.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
-            return hip
-    raise RuntimeError("no HIP runtime is loaded")
 
 
 def test_refusals(ptlib, orc_det):

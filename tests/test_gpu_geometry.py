@@ -14,15 +14,17 @@ import pytest
 import torch
 
 import filter_ref as F
+import geometry_cases as GC
 import geometry_ref as G64
 import plan_ref as PL
 import surface_ref as S
 import temporal_ref as T
-import test_geometry_cabi as GC
-from optixpathtracer_amd import renderer as R
+from gbuffer_ref import _row
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
 from optixpathtracer_amd import scenes
-from test_gpu_device_update import _np_transform
-from test_gpu_gbuffer import _renderer, _row
+from optixpathtracer_amd import renderer as R
+from scene_kit import _np_transform
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +32,6 @@ f32 = np.float32
 W, H = GC.W, GC.H
 FRAME = (0, 0, W, H)
 DEV = "cuda:0"
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def _is_hit(hit):
@@ -139,11 +137,9 @@ def test_object_motion(ptlib, name, route):
 
 # ------------------------------------------------------------------ T3: barycentrics and texcoords
 def test_barycentrics_and_texcoords(ptlib):
-    from test_gpu_surface import TEX_CAMERA
-
     model = S.textured_scene()
     GC.check_texcoords_tell_v1_from_v2(model)
-    r = _renderer(model, (W, H), TEX_CAMERA)
+    r = _renderer(model, (W, H), S.TEX_CAMERA)
     g = r.renderGBuffer(("hit", "position"))
     sp = r.surfacePlanes(g["hit"], r.copyTexcoordsDevice(), planes=("texcoord",))
     res = GC.check_barycentrics(_np(g["hit"]), _np(g["position"]), _np(sp["texcoord"]), model, GC.TEXTURED_MESHES)

@@ -16,48 +16,32 @@ import torch
 
 import moments_ref as MR
 import temporal_ref as T
-from optixpathtracer_amd import _lib
+from gbuffer_ref import _row
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame
+from gpu_kit import bits as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_gbuffer import _hip_runtime, _renderer, _row
+from pass_cases import MOMENTS_INPUTS, moments_kwargs
+from pass_cases import moments_case as _case
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 W, H = 131, 61
 SENTINEL = MR.SENTINEL
-INPUTS = ("color", "albedo", "motion", "hit", "position", "prev_hit", "prev_position", "history_in", "moments_in", "length_in")
 WORDS = dict(_lib.TMOM_PLANES, out=4, frame_rgba8=1)
 FLAGS = [dict(), dict(clear=True), dict(clamp=True), dict(clamp=True, clear=True)]
 FLAG_IDS = ["plain", "clear", "clamp", "clamp-clear"]
 
 
 # ------------------------------------------------------------------ GPU helpers
-def _upload(a, offset=False):
-    """a float32 array as a CUDA tensor; offset: one float into its allocation (4-byte aligned only)"""
-    a = np.array(a, f32)  # (a copy: the shared planes are read-only)
-    buf = torch.empty(a.size + 1, dtype=torch.float32, device="cuda:0")
-    t = (buf[1:] if offset else buf[:-1]).view(a.shape)
-    t.copy_(torch.from_numpy(a))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t
-
-
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane"""
-    n = h * w * WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = buf[1:] if offset else buf[:-1]
-    t = t.view((h, w) if WORDS[name] == 1 else (h, w, WORDS[name]))
-    return t.view(torch.int32) if name == "frame_rgba8" else t
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _np(t):
-    return t.cpu().numpy()
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, WORDS[name]), offset, torch.int32 if name == "frame_rgba8" else torch.float32)
 
 
 def _same(got, ref, what):
@@ -68,24 +52,16 @@ def _same(got, ref, what):
         assert a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs from float32 NumPy in {int((a != b).sum())} words"
 
 
-def _kw(prm):
-    """moments_ref's parameters as temporalMoments takes them: the two flags are clear_color and a clamp_k that is not None"""
-    kw = {k: v for k, v in prm.items() if k not in ("clear", "clamp", "clamp_k")}
-    kw["clear_color"] = bool(prm.get("clear"))
-    kw["clamp_k"] = prm.get("clamp_k", MR.DEFAULTS["clamp_k"]) if prm.get("clamp") else None
-    return kw
-
-
 def _run(r, planes, rects, pixels, what, mask=None, blocks=None, offset=False, outputs=MR.OUTPUTS, **prm):
     """uploads the planes, calls temporalMoments into sentinel-filled outputs, compares every output, the colour plane and the counters
     with the NumPy reference over the whole frame; returns (reference, stats, the outputs' bits)"""
     h, w = planes["length_in"].shape
-    dev = {k: _upload(planes[k], offset) for k in INPUTS if planes.get(k) is not None}
+    dev = {k: _upload(planes[k], offset) for k in MOMENTS_INPUTS if planes.get(k) is not None}
     for k in ("prev_hit", "prev_position"):  # read-only planes may alias one another
         if planes[k] is planes[k[5:]]:
             dev[k] = dev[k[5:]]
     out = {k: _filled(k, h, w, offset) for k in outputs}
-    res = r.temporalMoments(**dev, **out, variance="variance_out" in outputs, mask=mask, **_kw(prm))
+    res = r.temporalMoments(**dev, **out, variance="variance_out" in outputs, mask=mask, **moments_kwargs(prm))
     assert all(res[k] is out[k] for k in outputs)
     ref = MR.moments_ref(planes, rects, pixels, blocks=blocks, **prm)
     got = {k: _bits(out[k]) for k in outputs}
@@ -95,32 +71,6 @@ def _run(r, planes, rects, pixels, what, mask=None, blocks=None, offset=False, o
     assert (st["pixels"], st["reprojected"], st["clamped"]) == want, (what, st, want)
     assert st["kernel_ms"] > 0 if st["pixels"] else st["kernel_ms"] >= 0
     return ref, st, got
-
-
-_CASES = {}
-
-
-def _case(name):
-    """The input's renderer and its G-buffer planes of the current and of the previous camera, with random colour, history, moments and
-    albedo.  Built once; the arrays are read-only."""
-    if name not in _CASES:
-        make, size, cam, prev, _, seed = T.real_inputs()[name]
-        w, h = size
-        r = _renderer(make(), size, cam)
-        cur = r.renderGBuffer(("hit", "position", "motion"), prev_cameras=_row(prev, w / h))
-        r.setCamera(R.make_camera(prev, w / h))
-        old = r.renderGBuffer(("hit", "position"))
-        r.setCamera(R.make_camera(cam, w / h))
-        planes = MR.with_random_inputs(dict(motion=_np(cur["motion"]), hit=_np(cur["hit"]), position=_np(cur["position"]), prev_hit=_np(old["hit"]),
-                                            prev_position=_np(old["position"])), seed)
-        for a in planes.values():
-            a.setflags(write=False)
-        _CASES[name] = (r, planes, MR.real_params(name))
-    return _CASES[name]
-
-
-def _frame(w=W, h=H):
-    return [(0, 0, w, h)], np.ones((h, w), bool)
 
 
 def _flat(w, h, seed):
@@ -139,6 +89,10 @@ def _synthetic(w, h):
     planes = T.synthetic_planes(w, h, 7 + w)
     rng = np.random.default_rng(70 + w)
     return dict(planes, moments_in=MR.random_moments(rng, h, w), albedo=MR.random_albedo(rng, h, w))
+
+
+def _frame(w=W, h=H):
+    return whole_frame(w, h)
 
 
 # ------------------------------------------------------------------ 1. real planes, the four flag combinations
@@ -164,8 +118,8 @@ def test_optional_planes_and_the_ends_of_the_ranges(ptlib):
     _run(r, planes, rects, px, "clamp_k 0", clamp=True, **dict(base, clamp_k=0.0, albedo_min=0.0, min_weight=0.0))
     _run(r, planes, rects, px, "the other ends", clamp=True, **dict(base, clamp_k=1e6, albedo_min=2.0, min_weight=1.0, normal_cos=-1.0, max_history=1))
     # without the flag clamp_k is not read: a NaN there is not refused
-    dev = {k: _upload(planes[k]) for k in INPUTS}
-    res = r.temporalMoments(**dev, **dict(_kw(base), clamp_k=None))
+    dev = {k: _upload(planes[k]) for k in MOMENTS_INPUTS}
+    res = r.temporalMoments(**dev, **dict(moments_kwargs(base), clamp_k=None))
     d = _lib.TMomDesc()
     for k, t in list(dev.items()) + [(k, res[k]) for k in MR.OUTPUTS]:
         setattr(d, k, t.data_ptr())
@@ -187,7 +141,7 @@ def test_reduces_to_two_temporal_accumulate_calls(ptlib, name):
     r, planes, base = _case(name)
     h, w = planes["length_in"].shape
     prm = dict(plane_eps=base.get("plane_eps", 0.01), color_scale=2.0, max_history=8)
-    dev = {k: _upload(planes[k]) for k in INPUTS if k != "albedo"}
+    dev = {k: _upload(planes[k]) for k in MOMENTS_INPUTS if k != "albedo"}
     fused = r.temporalMoments(**dev, **prm)
     geo = [dev[k] for k in ("motion", "hit", "position", "prev_hit", "prev_position")]
     col = r.temporalAccumulate(dev["color"], *geo, dev["history_in"], dev["length_in"], **prm)
@@ -250,17 +204,13 @@ def test_two_views_side_by_side(ptlib):
 
 
 # ------------------------------------------------------------------ 5. masks and partition
-def _pixel_mask(block_mask, h=H, w=W):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:h, :w]
-
-
 def test_masks(ptlib):
     r, planes, base = _case("two_box")
     nby, nbx = r.blockGrid()
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True  # corner and edge blocks, the 3-wide column and the 5-high row
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     color = planes["color"].copy()
     color[~px, :3] = 1e6  # the excluded blocks: the window does not count them
     p = dict(planes, color=color)
@@ -316,7 +266,7 @@ def test_clear_is_behind_every_read(ptlib, size):
     nby, nbx = r.blockGrid()
     mask = np.ones((nby, nbx), bool)
     mask[nby - 1, 1] = mask[0, nbx - 2] = False
-    px = _pixel_mask(mask, h, w)
+    px = pixel_mask(mask, h=h, w=w)
     rects = [(0, 0, w, h)]
     _, _, plain = _run(r, planes, rects, px, "without the clear", mask=mask, blocks=mask, clamp=True, **base)
     ref, _, cleared = _run(r, planes, rects, px, "with the clear", mask=mask, blocks=mask, clamp=True, clear=True, **base)
@@ -356,12 +306,12 @@ def test_context_buffers_as_planes(ptlib, orc_det):
     planes["prev_hit"], planes["prev_position"] = planes["hit"], planes["position"]
     nby, nbx = r.blockGrid()
     mask = np.random.default_rng(9).random((nby, nbx)) < 0.6
-    px = _pixel_mask(mask, h, w)
+    px = pixel_mask(mask, h=h, w=w)
     prm = dict(color_scale=3.0, albedo_min=0.05, clamp=True, clamp_k=1.5, clear=True)
-    dev = {k: _upload(planes[k]) for k in INPUTS if k not in ("color", "albedo", "prev_hit", "prev_position")}
+    dev = {k: _upload(planes[k]) for k in MOMENTS_INPUTS if k not in ("color", "albedo", "prev_hit", "prev_position")}
     out = {k: _filled(k, h, w) for k in MR.OUTPUTS}
     res = r.temporalMoments(color=r.deviceBuffer(R.PT_BUF_ACCUM), albedo=r.deviceBuffer(R.PT_BUF_ALBEDO), prev_hit=dev["hit"], prev_position=dev["position"],
-                            **dev, **out, mask=mask, **_kw(prm))
+                            **dev, **out, mask=mask, **moments_kwargs(prm))
     ref = MR.moments_ref(planes, [(0, 0, w, h)], px, blocks=mask, **prm)
     _same({k: _bits(out[k]) for k in MR.OUTPUTS}, ref, "context buffers")
     st = res["stats"]
@@ -426,7 +376,7 @@ def test_refusals(ptlib):
     _, planes, base = _case("two_box")
     L = _lib.load_library()
     r = R.SampleRenderer(scenes.two_box_scene(shadow_catcher=False))
-    dev = {k: _upload(planes[k]) for k in INPUTS}
+    dev = {k: _upload(planes[k]) for k in MOMENTS_INPUTS}
     out = {k: _filled(k, H, W) for k in MR.OUTPUTS}
     color_before = _bits(dev["color"])
     ptr = {k: t.data_ptr() for k, t in list(dev.items()) + list(out.items())}
@@ -451,7 +401,7 @@ def test_refusals(ptlib):
     r.resize((W, H))
     r.setCamera(R.make_camera(scenes.TWO_BOX_CAMERA, W / H))
     assert L.pt_temporal_moments(r._ctx, None, None) == -1 and "null description" in L.pt_last_error(r._ctx).decode()
-    for name in INPUTS + MR.OUTPUTS:
+    for name in MOMENTS_INPUTS + MR.OUTPUTS:
         if name not in ("albedo", "variance_out"):
             refused(f"{name} null", f"{name} is null", **{name: None})
     host = np.zeros((H, W, 4), f32)
@@ -494,12 +444,12 @@ def test_refusals(ptlib):
     # a valid call afterwards still works, into the same planes; read-only planes may alias (prev_hit == hit)
     rects, px = _frame()
     p = dict(planes, prev_hit=planes["hit"], prev_position=planes["position"])
-    res = r.temporalMoments(**dict(dev, prev_hit=dev["hit"], prev_position=dev["position"]), **out, **_kw(dict(base, clamp=True)))
+    res = r.temporalMoments(**dict(dev, prev_hit=dev["hit"], prev_position=dev["position"]), **out, **moments_kwargs(dict(base, clamp=True)))
     ref = MR.moments_ref(p, rects, px, clamp=True, **base)
     _same({k: _bits(out[k]) for k in MR.OUTPUTS}, ref, "a valid call after the refusals")
     assert res["stats"]["reprojected"] == ref["reprojected"] and res["stats"]["clamped"] == ref["clamped"]
     # ... and so does one that lets the facade allocate its outputs (zero-filled)
-    res = r.temporalMoments(**dev, **_kw(base))
+    res = r.temporalMoments(**dev, **moments_kwargs(base))
     _same({k: _bits(res[k]) for k in MR.OUTPUTS}, MR.moments_ref(planes, rects, px, fill=0, **base), "allocated outputs")
     r.close()
 
@@ -539,7 +489,7 @@ def test_modulate_planes(ptlib, orc_det):
     nby, nbx = r.blockGrid()
     mask = rng.random((nby, nbx)) < 0.4
     mask[nby - 1, nbx - 1] = True
-    _modulate(r, orc_det, color, planes["albedo"], _pixel_mask(mask), "a block mask", mask=mask)
+    _modulate(r, orc_det, color, planes["albedo"], pixel_mask(mask, h=H, w=W), "a block mask", mask=mask)
     none = np.zeros((nby, nbx), bool)
     _modulate(r, orc_det, color, planes["albedo"], np.zeros((H, W), bool), "the empty mask", mask=none)
     # the stated branches of the denominator
@@ -550,8 +500,7 @@ def test_modulate_planes(ptlib, orc_det):
 
 
 def test_modulate_planes_with_views(ptlib, orc_det):
-    from test_gpu_gbuffer import _views_and_prev
-    from test_gpu_views import RECTS
+    from scene_kit import RECTS, _views_and_prev
 
     r = _renderer(scenes.two_box_scene(shadow_catcher=False), (W, H), scenes.TWO_BOX_CAMERA)
     views, _ = _views_and_prev()

@@ -5,7 +5,7 @@ arrays.  No tolerance anywhere; the hand-made plane with NaN barycentrics compar
 
 Inputs, 131 x 61 (17 x 8 blocks, last column 3 wide, last row 5 high): the two-box scene with its unit box (mesh 0) turned by 0.2 rad about y
 and shifted by (0.1, 0.15, -0.05); voxel_terrain(n=64, target_tris=20000) with its largest band (mesh 3) turned by 0.03 rad and shifted by
-(1.5, 0.8, -1.0).  Previous camera: the eye 0.25 to the side (test_gpu_gbuffer._moved)."""
+(1.5, 0.8, -1.0).  Previous camera: the eye 0.25 to the side (gbuffer_ref._moved)."""
 import ctypes as C
 
 import numpy as np
@@ -14,41 +14,30 @@ import torch
 
 import motion_ref as M
 import temporal_ref as T
-from optixpathtracer_amd import _lib
+from gbuffer_ref import _moved, _row
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame
+from gpu_kit import bits as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_device_update import _affine, _np_transform
-from test_gpu_gbuffer import _hip_runtime, _moved, _renderer, _row
-from test_gpu_temporal import _upload
-from test_gpu_views import RECTS, _cam_dicts
+from pass_cases import _vertices
+from pass_cases import motion_case as _case
+from scene_kit import RECTS, _cam_dicts, _np_transform
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 W, H = 131, 61
 SENTINEL = M.SENTINEL
-INPUTS = {
-    "two_box": (lambda: scenes.two_box_scene(shadow_catcher=False), scenes.TWO_BOX_CAMERA, 0, _affine((0.0, 1.0, 0.0), 0.2, (1.0, 1.0, 1.0), (0.1, 0.15, -0.05))),
-    "terrain": (lambda: scenes.voxel_terrain(n=64, target_tris=20000), scenes.TERRAIN_CAMERA, 3, _affine((0.0, 1.0, 0.0), 0.03, (1.0, 1.0, 1.0), (1.5, 0.8, -1.0))),
-}
 
 
 # ------------------------------------------------------------------ GPU helpers
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane; offset: one float into its allocation (4-byte aligned only)"""
-    n = h * w * M.WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = (buf[1:] if offset else buf[:-1]).view((h, w, M.WORDS[name]))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _np(t):
-    return t.cpu().numpy()
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, M.WORDS[name]), offset)
 
 
 def _same(got, ref, what, nan_aware=False):
@@ -78,46 +67,8 @@ def _run(r, idx, hit, prev_vertices, rects, pixels, what, cams=None, prev_cams=N
     return ref, got, st
 
 
-def _vertices(r, model):
-    return M.stack_vertices([r.downloadVertices(k) for k in range(len(model.meshes))])
-
-
-class _Case:
-    pass
-
-
-_CASES = {}
-
-
-def _case(name):
-    """The input after one step of the loop: the previous frame's G-buffer planes, the snapshot of its vertices, the mesh moved with a refit,
-    this frame's G-buffer planes under the current camera.  Built once; the arrays are read-only."""
-    if name not in _CASES:
-        make, cam, mesh, A = INPUTS[name]
-        c = _Case()
-        c.model, c.cam, c.prev, c.mesh, c.A = make(), cam, _moved(cam), mesh, A
-        c.row, c.prev_row = _row(c.cam, W / H), _row(c.prev, W / H)
-        c.verts0, c.idx = M.model_arrays(c.model)
-        c.r = r = _renderer(c.model, (W, H), c.prev)
-        old = r.renderGBuffer(("hit", "position"))
-        c.snapshot = r.copyVerticesDevice()
-        c.after_create = _np(c.snapshot)
-        r.transformMeshes({mesh: A})
-        c.verts1 = _vertices(r, c.model)
-        c.after_refit = _np(r.copyVerticesDevice())
-        r.setCamera(R.make_camera(cam, W / H))
-        cur = r.renderGBuffer(("hit", "position", "motion"), prev_cameras=c.prev_row)
-        c.gstats = cur["stats"]
-        c.old = {k: _np(old[k]) for k in ("hit", "position")}
-        c.cur = {k: _np(cur[k]) for k in ("hit", "position", "motion")}
-        for a in [c.verts0, c.verts1, c.idx, c.after_create, c.after_refit] + list(c.old.values()) + list(c.cur.values()):
-            a.setflags(write=False)
-        _CASES[name] = c
-    return _CASES[name]
-
-
 def _frame(w=W, h=H):
-    return [(0, 0, w, h)], np.ones((h, w), bool)
+    return whole_frame(w, h)
 
 
 # ------------------------------------------------------------------ 1. the snapshot
@@ -218,17 +169,13 @@ def test_two_views_with_different_previous_cameras(ptlib):
     r.close()
 
 
-def _pixel_mask(block_mask):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:H, :W]
-
-
 def test_block_mask(ptlib):
     c = _case("terrain")
     nby, nbx = c.r.blockGrid()
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True  # corner and edge blocks, the 3-wide column and the 5-high row
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     ref, got, st = _run(c.r, c.idx, c.cur["hit"], c.after_create, [(0, 0, W, H)], px, "a random block mask", cams=[c.row], prev_cams=[c.prev_row], mask=mask)
     assert 0 < st["pixels"] < W * H
     for name in M.PLANES:

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from optixpathtracer_amd import scenes
-from test_gpu_parity import _compare, _gpu_render, _oracle_render, _renderer
+from parity_kit import _compare, _gpu_render, _oracle_render, _renderer
 
 pytestmark = pytest.mark.gpu
 

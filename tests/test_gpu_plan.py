@@ -15,11 +15,14 @@ import torch
 
 import plan_ref as PR
 import temporal_ref as T
-from optixpathtracer_amd import _lib
+from gpu_kit import filled, plane_shape
+from gpu_kit import bits as _bits
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_gbuffer import _renderer, _row
-from test_gpu_moments import _bits, _filled, _np, _upload
+from pass_cases import plan_case as _case
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +34,11 @@ ALL = np.ones((H, W), bool)
 
 
 # ------------------------------------------------------------------ GPU helpers
+def _filled(name, h, w, offset=False):
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, _lib.CARRY_PLANES[name]), offset)
+
+
 def _dev(planes, offset=False):
     dev = {k: _upload(planes[k], offset) for k in PR.INPUTS}
     for k in ("prev_hit", "prev_position"):  # read-only planes may alias one another
@@ -70,28 +78,6 @@ def _carry(r, planes, rects, pixels, what, mask=None, offset=False, dev=None, ou
     assert {k: st[k] for k in PR.CARRY_STATS} == ref["stats"], (what, st, ref["stats"])
     assert st["kernel_ms"] > 0 if st["pixels"] else st["kernel_ms"] >= 0
     return ref, got, st
-
-
-_CASES = {}
-
-
-def _case(name):
-    """The input's renderer, its G-buffer planes of the current and of the previous camera (the mild move) with a block history, and the
-    gather parameters.  Built once; the arrays are read-only."""
-    if name not in _CASES:
-        make, size, cam, prev, prm, seed = PR.real_case(name)
-        w, h = size
-        r = _renderer(make(), size, cam)
-        cur = r.renderGBuffer(("hit", "position", "motion"), prev_cameras=_row(prev, w / h))
-        r.setCamera(R.make_camera(prev, w / h))
-        old = r.renderGBuffer(("hit", "position"))
-        r.setCamera(R.make_camera(cam, w / h))
-        planes = PR.with_block_history(dict(motion=_np(cur["motion"]), hit=_np(cur["hit"]), position=_np(cur["position"]), prev_hit=_np(old["hit"]),
-                                            prev_position=_np(old["position"])), seed)
-        for a in planes.values():
-            a.setflags(write=False)
-        _CASES[name] = (r, planes, prm)
-    return _CASES[name]
 
 
 def _complement(mask, within=None):
@@ -253,7 +239,7 @@ def _both(r, planes, rects, pixels, what, prm, in_mask=None, offset=False, outpu
 
 
 def test_two_views(ptlib):
-    from test_gpu_views import RECTS
+    from scene_kit import RECTS
 
     _, planes, prm = _case("two_box")
     rects = RECTS[:2]  # (0, 0, 61, 37) and (64, 0, 67, 29): origins on the 8-grid, no side a multiple of 8

@@ -1,43 +1,18 @@
 """In-place vertex updates (pt_update_meshes): a refitted tree must render the same bits as a fresh pt_create over the moved vertices —
 and as the CPU checker — because a hit does not depend on the tree (closest t, lowest primitive on ties, hits confined to the triangle's
 padded box).  A refit over unchanged vertices gives the tree back byte for byte; a rebuild gives the fresh build's tree."""
-import copy
-
 import numpy as np
 import pytest
 
 from conftest import assert_bits_equal
-from optixpathtracer_amd import renderer as R
 from optixpathtracer_amd import scenes
-from test_gpu_builder import _canonical
-from test_gpu_parity import _compare, _gpu_render, _oracle_render, _renderer
+from optixpathtracer_amd import renderer as R
+from parity_kit import _compare, _gpu_render, _oracle_render, _renderer
+from scene_kit import _aimed_rays, _canonical, _moved_mesh, _wave, _with_vertices
 
 pytestmark = pytest.mark.gpu
 
 W, H = 96, 64
-
-
-def _with_vertices(model, verts: dict):
-    m = copy.deepcopy(model)
-    for k, v in verts.items():
-        m.meshes[k].vertex = np.ascontiguousarray(v, np.float32)
-    return m
-
-
-def _wave(model, amp, phase=0.0, seed=7):
-    """Seeded smooth displacement of every vertex (a travelling wave across the scene)."""
-    rng = np.random.default_rng(seed)
-    k = rng.uniform(0.03, 0.08, 3)
-    out = {}
-    for i, m in enumerate(model.meshes):
-        v = np.asarray(m.vertex, np.float64)
-        d = amp * np.stack([np.sin(k[0] * v[:, 2] + phase), np.sin(k[1] * v[:, 0] + 1.3 * phase), np.cos(k[2] * v[:, 0] + k[2] * v[:, 2] + phase)], 1)
-        out[i] = (v + d).astype(np.float32)
-    return out
-
-
-def _moved(model, mesh, offset):
-    return {mesh: (np.asarray(model.meshes[mesh].vertex, np.float32) + np.float32(offset)).astype(np.float32)}
 
 
 def _all(model):
@@ -85,7 +60,7 @@ def test_identity_refit_small_scenes(ptlib, clean_env):
     for model in (scenes.cornell_box(), scenes.two_box_scene()):
         r = R.SampleRenderer(model)
         n0, t0 = r.exportBVH()
-        r.updateMeshes(_moved(model, 0, (3.0, -1.0, 2.0)))
+        r.updateMeshes(_moved_mesh(model, 0, (3.0, -1.0, 2.0)))
         r.updateMeshes(_all(model))
         n1, t1 = r.exportBVH()
         assert n1.tobytes() == n0.tobytes() and t1.tobytes() == t0.tobytes()
@@ -111,7 +86,7 @@ def test_refit_render_equals_fresh_build_and_checker(ptlib, orc_det, clean_env, 
 
 def test_refit_shadow_catcher_scene(ptlib, orc_det, clean_env, probe):
     A = scenes.two_box_scene(shadow_catcher=True)
-    up = _moved(A, len(A.meshes) - 1, (0.35, 0.1, -0.2))
+    up = _moved_mesh(A, len(A.meshes) - 1, (0.35, 0.1, -0.2))
     B = _with_vertices(A, up)
     cam = scenes.TWO_BOX_CAMERA
     r = _renderer(A, probe, cam, W, H)
@@ -145,20 +120,6 @@ def test_textured_scene_update(ptlib, orc_det, clean_env, probe, rebuild):
     g = _gpu_render(r, 2)
     _compare(g, _gpu_render(_renderer(B, probe, scenes.TERRAIN_CAMERA, W, H), 2))
     _compare(g, _oracle_render(orc_det, B, probe, scenes.TERRAIN_CAMERA, W, H, 2))
-
-
-def _random_rays(model, n, seed):
-    rng = np.random.default_rng(seed)
-    v = model.flatten()[0]
-    lo, hi = v.min(0), v.max(0)
-    o = rng.uniform(lo - 0.2 * (hi - lo), hi + 0.2 * (hi - lo), (n, 3))
-    t = v[rng.integers(0, len(v), n)]
-    d = t - o
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    rays = np.zeros((n, 8), np.float32)
-    rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, 1e-3, d, 1e30
-    rays[n // 2:, 7] = rng.uniform(1, 200, n - n // 2)  # segments for the any-hit query
-    return rays
 
 
 def _check_enclosure(nodes, tris):
@@ -199,7 +160,7 @@ def test_queries_after_refit(ptlib, orc_det, clean_env, terrain):
     B = _with_vertices(terrain, _wave(terrain, 2.5, 0.9))
     r = R.SampleRenderer(terrain)
     r.updateMeshes(_all(B))
-    rays = _random_rays(B, 20000, 3)
+    rays = _aimed_rays(B, 20000, 3)
     sc = orc_det.make_scene(B)
     (t, prim), _ = r.trace(rays)
     ot, oprim = orc_det.trace_closest(sc, rays)
@@ -239,7 +200,7 @@ def test_hostile_updates_render_exactly(ptlib, clean_env, probe, case):
         v = np.asarray(A.meshes[1].vertex, np.float32)
         up = {1: np.repeat(v[:1], len(v), 0)}
     else:
-        up = _moved(A, 2, (1e4, 0.0, 0.0))
+        up = _moved_mesh(A, 2, (1e4, 0.0, 0.0))
     B = _with_vertices(A, up)
     r = _renderer(A, probe, cam, W, H)
     _gpu_render(r, 2)

@@ -29,22 +29,24 @@ Filler numbers seen on an MI355X: 0.0729 ms per repeat of big.add_(1.0); host wa
 unpackDisplay) and 0.179 ms (filterPlanes, two iterations; renderDevice 0.174, updateMeshesDevice 0.11 - 0.13, the other passes 0.04 -
 0.12, traceDevice 0.06 - 0.10, the device copies 0.03 - 0.07), so 50 x the wall time stayed under 10 ms and every filler was the minimum:
 10.0 ms = 139 repeats."""
-import contextlib
 import ctypes as C
 import importlib.util
 import os
 import re
-import time
 
 import numpy as np
 import pytest
 import torch
 
-import busy_stream as busy
 from conftest import ROOT
-from optixpathtracer_amd import _lib
+from gbuffer_ref import PLANES, _moved
+from gpu_kit import filled, hip_runtime, plane_renderer, plane_shape, to_numpy
+from gpu_kit import differ as _differ
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
+from pass_cases import FILTER_INPUTS, MOMENTS_INPUTS, filter_case, moments_case, moments_kwargs, motion_case, plan_case, surface_aniso_case, upsample_case
+from scene_kit import VIEW_H, VIEW_W, _aimed_rays, _cam_dicts, _rows, _views, _wave
+from stream_kit import _dev, _pin, _raw, _res, _same, _snapshot
 
 gpu = pytest.mark.gpu
 f32 = np.float32
@@ -62,190 +64,10 @@ def covers(*names):
 
 
 # ------------------------------------------------------------------ the protocol
-def _differ(a, b):
-    if a.dtype != f32:  # (packed pixels, records of integers, a block mask: as they are)
-        return a != b
-    a, b = a.view(np.uint32), b.view(np.uint32)
-    with np.errstate(all="ignore"):
-        return (a != b) & ~(np.isnan(a.view(f32)) & np.isnan(b.view(f32)))
-
-
-def _snapshot(res):
-    """{name: the words of a tensor or an array, "stats": the counters (no times)} of what a call returned"""
-    got = {}
-    for k, v in res.items():
-        if v is None:
-            continue
-        if k == "stats":
-            got[k] = {s: x for s, x in v.items() if not s.endswith("_ms")}
-        elif isinstance(v, torch.Tensor):
-            got[k] = v.cpu().numpy().copy()
-        else:
-            got[k] = np.array(v, copy=True)
-    return got
-
-
-def _same(got, ref, what):
-    assert got.keys() == ref.keys(), (what, sorted(got), sorted(ref))
-    for k, a in got.items():
-        if k == "stats":
-            assert a == ref[k], f"{what}: counters {a} against the reference call's {ref[k]}"
-            continue
-        assert a.shape == ref[k].shape and a.dtype == ref[k].dtype, (what, k)
-        neq = _differ(a, ref[k])
-        if neq.any():
-            sent = int((a.view(np.uint32) == SENTINEL).sum()) if a.dtype.itemsize == 4 else 0
-            raise AssertionError(f"{what}: {k} differs from the reference call in {int(neq.sum())} of {a.size} words ({sent} words hold the sentinel)")
-
-
-def _differs(a, b):
-    return any(k != "stats" and _differ(v, b[k]).any() for k, v in a.items())
-
-
-def _sentinel(t):
-    t.view(torch.uint8).fill_(0xA5)
-
-
-def _dev(a):
-    """an array's bytes as a CUDA tensor of its shape, 16-byte aligned; uploaded synchronously"""
-    a = np.ascontiguousarray(a)
-    assert a.dtype.itemsize == 4
-    t = torch.empty(a.shape, dtype=torch.float32 if a.dtype == f32 else torch.int32, device="cuda:0")
-    t.copy_(torch.from_numpy(a.view(f32 if a.dtype == f32 else np.int32).copy()))
-    assert t.is_contiguous() and t.data_ptr() % 16 == 0
-    return t
-
-
-def _raw(shape, dtype=torch.float32):
-    return torch.zeros(shape, dtype=dtype, device="cuda:0")
-
-
-_BESIDE = {}  # case -> {mode: did the library's stream run beside torch's}
-
-
-@contextlib.contextmanager
-def _stream(mode, r, what):
-    """default: torch's default stream.  side: a fresh side stream, of up to three the first that runs beside the library's; a case whose
-    default run (if it was made) and side run were both behind the library's stream cannot see a lost ordering and fails.  teeth: the first
-    of the default stream and three fresh ones that runs beside the library's, which the test needs."""
-    lib = r.stream
-    seen = _BESIDE.setdefault(what, {})
-    if mode == "default":
-        seen[mode] = busy.concurrent(lib, what)
-        yield
-        return
-    if mode == "teeth" and busy.concurrent(lib, what):
-        yield
-        return
-    for _ in range(3):
-        side = torch.cuda.Stream()
-        with torch.cuda.stream(side):
-            beside = busy.concurrent(lib, what)
-        if beside:
-            break
-    if mode == "teeth":
-        assert beside, f"{what}: none of torch's default stream and three fresh streams runs beside the library's: a lost ordering cannot show"
-    else:
-        seen[mode] = beside
-        assert any(seen.values()), f"{what}: the library's stream ran behind torch's on every stream tried ({seen}): the case cannot see a lost ordering"
-    with torch.cuda.stream(side):
-        yield
-
-
-def _pin(what, mode, r, B, outs, call, A=None, raw=False, broken=False):
-    """The eight steps (module docstring).  B: {name: array}, the inputs' content; A: the stale content (zeros where not given); outs:
-    {name: tensor}; call(dev, outs, returned) makes the facade call on the tensors of dev and outs, calls returned() as soon as the
-    synchronous entry point is back, and returns {name: tensor or array, "stats": dict}.  raw: the call hands raw pointers over, so the
-    ordering is pt_wait_event(E), the C-level half of the contract.  broken: the ordering has been taken out (test_the_pin_has_teeth) — no
-    pending fill, E still pending after the call, outputs equal S.  Returns (R, what the ordered call gave)."""
-    per = busy.repeat_ms()
-    dev = {k: _dev(v) for k, v in B.items()}
-    staged = {k: _dev(v) for k, v in B.items()}
-    stale = {k: _dev((A or {}).get(k, np.zeros_like(v))) for k, v in B.items()}
-    flags = []
-
-    def sync_call():
-        for t in outs.values():
-            _sentinel(t)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = call(dev, outs, lambda: flags.append(time.perf_counter()))
-        return _snapshot(res), flags[-1] - t0  # (the host wall time of the entry point itself: up to returned())
-
-    sync_call()  # (first use of the entry point by this context: allocations, code loading)
-    ref, wall = sync_call()  # 1
-    S = None
-    if B:  # 2
-        for k, t in dev.items():
-            t.copy_(stale[k])
-        S, _ = sync_call()
-        assert _differs(S, ref), f"{what}: stale inputs give the reference's outputs: the case cannot tell stale from fresh"
-    else:
-        assert not broken
-        for t in outs.values():
-            t.zero_()
-    assert len(flags) == (3 if B else 2), f"{what}: the case never said when its entry point returned"
-    ms = busy.length_ms(wall, what)
-    torch.cuda.synchronize()  # 3
-    with _stream(mode, r, what):
-        if broken:
-            for t in outs.values():
-                _sentinel(t)
-            torch.cuda.synchronize()
-        n = busy.filler(ms)  # 4
-        for k, t in dev.items():
-            t.copy_(staged[k])
-        if not broken:
-            for t in outs.values():
-                _sentinel(t)
-        E = torch.cuda.Event()
-        E.record()
-        pending = not E.query()  # 5
-        print(f"{what} [{mode}]: {per:.4f} ms per repeat, reference call {wall * 1e3:.3f} ms on the host, filler {ms:.1f} ms = {n} repeats")
-        assert pending, f"{what}: the filler ({n} repeats, {ms:.1f} ms) had ended before the call was made"
-        if raw:
-            r.waitEvent(E.cuda_event)
-        state = []
-        res = call(dev, outs, lambda: state.append(E.query()))  # 6
-        torch.cuda.synchronize()
-        got = _snapshot(res)
-    assert len(state) == 1
-    if broken:
-        assert not state[0], f"{what}: with the ordering removed the call still ended behind the pending work"
-        _same(got, S, f"{what}, ordering removed: stale outputs expected")
-    else:
-        assert state[0], f"{what}: the call returned while the work it had to wait for was still pending"  # 7
-        _same(got, ref, what)  # 8
-    return ref, got
-
-
-def _res(res, outs):
-    return dict({k: outs[k] for k in outs}, stats=res["stats"])
-
-
 # ------------------------------------------------------------------ inputs: the existing small cases, built once
-def _moments_case():
-    import test_gpu_moments as TM
-
-    return TM._case("two_box")
-
-
-def _plan_case():
-    import test_gpu_plan as TP
-
-    return TP._case("two_box")
-
-
-def _textured():
-    import test_gpu_surface_aniso as TA
-
-    return TA._case("textured")
-
-
-def _moving():
-    import test_gpu_motion as TMo
-
-    return TMo._case("two_box")
+def _filled(words, name, h, w):
+    """a sentinel-filled output plane of a pass, from the pass's table of words per pixel"""
+    return filled(plane_shape(h, w, words[name]), dtype=torch.int32 if name == "frame_rgba8" else torch.float32)
 
 
 def _size(r):
@@ -259,15 +81,13 @@ def _size(r):
 @pytest.mark.parametrize("mode", MODES)
 def test_temporal_accumulate(ptlib, mode):
     """`color` is the context's own accumulation buffer (pt_device_buffer), a raw pointer; the seven other inputs are pending tensors"""
-    from test_gpu_temporal import _filled
-
-    r, planes, _ = _moments_case()
+    r, planes, _ = moments_case("two_box")
     h, w = _size(r)
     r.uploadAccum(planes["color"])
     color = r.deviceBuffer(R.PT_BUF_ACCUM)
     assert color
     B = {k: planes[k] for k in ("motion", "hit", "position", "prev_hit", "prev_position", "history_in", "length_in")}
-    outs = {k: _filled(k, h, w) for k in _lib.TEMPORAL_OUTPUTS}
+    outs = {k: _filled(_lib.TEMPORAL_PLANES, k, h, w) for k in _lib.TEMPORAL_OUTPUTS}
 
     def call(dev, outs, returned):
         res = r.temporalAccumulate(color, **dev, **outs)
@@ -281,18 +101,16 @@ def test_temporal_accumulate(ptlib, mode):
 @covers("pt_temporal_moments")
 @pytest.mark.parametrize("mode", MODES)
 def test_temporal_moments(ptlib, mode):
-    from test_gpu_moments import INPUTS, _filled, _kw
-
-    r, planes, prm = _moments_case()
+    r, planes, prm = moments_case("two_box")
     h, w = _size(r)
-    outs = {k: _filled(k, h, w) for k in _lib.TMOM_OUTPUTS}
+    outs = {k: _filled(_lib.TMOM_PLANES, k, h, w) for k in _lib.TMOM_OUTPUTS}
 
     def call(dev, outs, returned):
-        res = r.temporalMoments(**dev, **outs, **_kw(dict(prm, clamp=True)))
+        res = r.temporalMoments(**dev, **outs, **moments_kwargs(dict(prm, clamp=True)))
         returned()
         return _res(res, outs)
 
-    _pin("temporalMoments", mode, r, {k: planes[k] for k in INPUTS}, outs, call)
+    _pin("temporalMoments", mode, r, {k: planes[k] for k in MOMENTS_INPUTS}, outs, call)
 
 
 @gpu
@@ -300,11 +118,9 @@ def test_temporal_moments(ptlib, mode):
 @pytest.mark.parametrize("mode", MODES)
 def test_temporal_carry(ptlib, mode):
     import plan_ref as PR
-    from test_gpu_moments import _filled
-
-    r, planes, prm = _plan_case()
+    r, planes, prm = plan_case("two_box")
     h, w = _size(r)
-    outs = {k: _filled(k, h, w) for k in _lib.CARRY_OUTPUTS}
+    outs = {k: _filled(_lib.CARRY_PLANES, k, h, w) for k in _lib.CARRY_OUTPUTS}
 
     def call(dev, outs, returned):
         res = r.temporalCarry(**dev, **outs, **prm)
@@ -321,7 +137,7 @@ def test_sample_plan(ptlib, mode):
     """no device output: the plan's mask comes back on the host, so only the inputs' producer is pending"""
     import plan_ref as PR
 
-    r, planes, prm = _plan_case()
+    r, planes, prm = plan_case("two_box")
 
     def call(dev, outs, returned):
         res = r.samplePlan(**dev, **dict(PR.REAL_PLAN, **prm))
@@ -336,29 +152,25 @@ def test_sample_plan(ptlib, mode):
 @covers("pt_filter_planes")
 @pytest.mark.parametrize("mode", MODES)
 def test_filter_planes(ptlib, mode):
-    import test_gpu_filter as TF
-
-    r, planes, prm = TF._case("two_box")
+    r, planes, prm = filter_case("two_box")
     h, w = _size(r)
-    outs = dict(out=TF._filled("out", h, w), scratch=TF._filled("scratch", h, w), frame_rgba8=TF._filled("frame_rgba8", h, w))
+    outs = {k: _filled(_lib.FILTER_PLANES, k, h, w) for k in ("out", "scratch", "frame_rgba8")}
 
     def call(dev, outs, returned):
         res = r.filterPlanes(**dev, out=outs["out"], scratch=outs["scratch"], frame=outs["frame_rgba8"], iterations=2, **prm)
         returned()
         return _res(res, outs)
 
-    _pin("filterPlanes", mode, r, {k: planes[k] for k in TF.INPUTS}, outs, call)
+    _pin("filterPlanes", mode, r, {k: planes[k] for k in FILTER_INPUTS}, outs, call)
 
 
 @gpu
 @covers("pt_modulate_planes")
 @pytest.mark.parametrize("mode", MODES)
 def test_modulate_planes(ptlib, mode):
-    from test_gpu_moments import _filled
-
-    r, planes, _ = _moments_case()
+    r, planes, _ = moments_case("two_box")
     h, w = _size(r)
-    outs = dict(out=_filled("out", h, w), frame_rgba8=_filled("frame_rgba8", h, w))
+    outs = {k: _filled(dict(out=4, frame_rgba8=1), k, h, w) for k in ("out", "frame_rgba8")}
 
     def call(dev, outs, returned):
         res = r.modulatePlanes(dev["color"], albedo=dev["albedo"], out=outs["out"], frame=outs["frame_rgba8"])
@@ -373,11 +185,9 @@ def test_modulate_planes(ptlib, mode):
 @pytest.mark.parametrize("mode", MODES)
 def test_motion_planes(ptlib, mode):
     import motion_ref as M
-    from test_gpu_motion import _filled
-
-    c = _moving()
+    c = motion_case("two_box")
     h, w = _size(c.r)
-    outs = {k: _filled(k, h, w) for k in M.PLANES}
+    outs = {k: _filled(M.WORDS, k, h, w) for k in M.PLANES}
 
     def call(dev, outs, returned):
         res = c.r.motionPlanes(dev["hit"], dev["prev_vertices"], prev_cameras=c.prev_row, planes=M.PLANES, out=outs)
@@ -388,20 +198,18 @@ def test_motion_planes(ptlib, mode):
 
 
 def _surface(fn, planes, mode, broken=False, **kw):
-    from test_gpu_surface_aniso import _filled, _np
-
-    c = _textured()
+    c = surface_aniso_case("textured")
     h, w = _size(c.r)
-    outs = {k: _filled(k, h, w) for k in planes}
+    outs = {k: _filled(planes, k, h, w) for k in planes}
 
     def call(dev, outs, returned):
         res = getattr(c.r, fn)(dev["hit"], dev["prim_texcoords"], *([dev["mips"]] if "mips" in dev else []), planes=tuple(planes), out=outs, **kw)
         returned()
         return _res(res, outs)
 
-    B = dict(hit=c.hit, prim_texcoords=_np(c.table))
+    B = dict(hit=c.hit, prim_texcoords=to_numpy(c.table))
     if fn != "surfacePlanes":
-        B["mips"] = _np(c.mips)
+        B["mips"] = to_numpy(c.mips)
     return _pin(fn, mode, c.r, B, outs, call, broken=broken)
 
 
@@ -434,11 +242,9 @@ def test_surface_aniso_planes(ptlib, mode):
 @pytest.mark.parametrize("mode", MODES)
 def test_upsample_planes_into_planes_the_facade_allocates(ptlib, mode):
     """out=None: the facade's torch.zeros lands behind the filler as well, and the pass behind it"""
-    import test_gpu_upsample as TU
-
-    r, lo, hi = TU._case("two_box", 2)
+    r, lo, hi = upsample_case("two_box", 2)
     h, w = _size(r)
-    outs = dict(weight_out=TU._filled("weight_out", h, w))
+    outs = dict(weight_out=_filled(_lib.UPSAMPLE_PLANES, "weight_out", h, w))
 
     def call(dev, outs, returned):
         res = r.upsamplePlanes(**dev, scale=2, out=None, weight_out=outs["weight_out"])
@@ -461,11 +267,9 @@ def _no_sentinel_where_the_reference_wrote(ref, got):
 @covers("pt_render_gbuffer")
 @pytest.mark.parametrize("mode", MODES)
 def test_render_gbuffer(ptlib, mode):
-    from test_gpu_gbuffer import PLANES, _filled
-
-    c = _textured()
+    c = surface_aniso_case("textured")
     h, w = _size(c.r)
-    outs = {k: _filled(k, h, w) for k in PLANES}
+    outs = {k: _filled(_lib.GBUFFER_PLANES, k, h, w) for k in PLANES}
 
     def call(dev, outs, returned):
         res = c.r.renderGBuffer(PLANES, prev_cameras=c.row, out=outs)
@@ -482,7 +286,7 @@ def test_render_gbuffer(ptlib, mode):
 @pytest.mark.parametrize("fn", ["copyVerticesDevice", "copyTexcoordsDevice", "copyTextureMipsDevice"])
 @pytest.mark.parametrize("mode", MODES)
 def test_device_copies(ptlib, mode, fn):
-    c = _textured()
+    c = surface_aniso_case("textured")
     nv, nt = c.r.vertexCount()
     shape = dict(copyVerticesDevice=(nv, 3), copyTexcoordsDevice=(nt, 6), copyTextureMipsDevice=(c.r.textureMipsLayout()[1] // 16, 4))[fn]
     assert shape[0] > 0
@@ -500,9 +304,7 @@ def test_device_copies(ptlib, mode, fn):
 
 # ------------------------------------------------------------------ ray queries
 def _rays(model):
-    from test_gpu_refit import _random_rays
-
-    return _random_rays(model, RAYS, 5)
+    return _aimed_rays(model, RAYS, 5)
 
 
 @gpu
@@ -510,7 +312,7 @@ def _rays(model):
 @pytest.mark.parametrize("any_hit", [False, True], ids=["closest", "any"])
 @pytest.mark.parametrize("mode", MODES)
 def test_trace_device(ptlib, mode, any_hit):
-    c = _moving()
+    c = motion_case("two_box")
     outs = dict(out=_raw((RAYS,), torch.int32) if any_hit else _raw((RAYS, 8)))
 
     def call(dev, outs, returned):
@@ -528,7 +330,7 @@ def test_trace_device(ptlib, mode, any_hit):
 def test_trace_device_without_wait_then_a_clone_on_the_same_stream(ptlib, mode):
     """wait=False: the query is only enqueued; torch's current stream is made to wait for it, so a clone enqueued directly behind the call,
     with no host wait, holds the reference's records"""
-    c = _moving()
+    c = motion_case("two_box")
     outs = dict(out=_raw((RAYS, 8)))
 
     def call(dev, outs, returned):
@@ -546,7 +348,7 @@ def test_trace_device_without_wait_then_a_clone_on_the_same_stream(ptlib, mode):
 @covers("pt_trace_device")
 @pytest.mark.parametrize("mode", MODES)
 def test_trace_device_raw_pointers_behind_wait_event(ptlib, mode):
-    c = _moving()
+    c = motion_case("two_box")
     outs = dict(out=_raw((RAYS, 8)))
 
     def call(dev, outs, returned):
@@ -559,11 +361,8 @@ def test_trace_device_raw_pointers_behind_wait_event(ptlib, mode):
 
 # ------------------------------------------------------------------ geometry and cameras from device memory
 def _update_case(mode, raw):
-    from test_gpu_gbuffer import _renderer
-    from test_gpu_refit import _wave
-
     model = scenes.two_box_scene(shadow_catcher=False)
-    r = _renderer(model, (131, 61), scenes.TWO_BOX_CAMERA)
+    r = plane_renderer(model, (131, 61), scenes.TWO_BOX_CAMERA)
     mesh = 0
     rest = np.ascontiguousarray(model.meshes[mesh].vertex, f32)
     moved = _wave(model, 0.05)[mesh]
@@ -580,7 +379,7 @@ def _update_case(mode, raw):
     assert np.array_equal(got["vertices"][first:first + nv].view(np.uint32), moved.view(np.uint32))
     # R came from this context, refitted to the rest vertices and back in between: equal only if a refit depends on nothing but the current
     # vertices (tests/test_gpu_refit.py pins that).  So also: a second context, updated once, after a host synchronise.
-    other = _renderer(model, (131, 61), scenes.TWO_BOX_CAMERA)
+    other = plane_renderer(model, (131, 61), scenes.TWO_BOX_CAMERA)
     t = _dev(moved)
     torch.cuda.synchronize()
     other.updateMeshesDevice({mesh: t})
@@ -610,10 +409,7 @@ def test_update_meshes_device_raw_pointer_behind_wait_event(ptlib, mode):
 @covers("pt_set_view_cameras_device")
 @pytest.mark.parametrize("mode", MODES)
 def test_set_view_cameras_from_a_tensor(ptlib, mode):
-    from test_gpu_gbuffer import _moved, _renderer
-    from test_gpu_views import H, W, _cam_dicts, _rows, _views
-
-    r = _renderer(scenes.two_box_scene(shadow_catcher=False), (W, H), scenes.TWO_BOX_CAMERA)
+    r = plane_renderer(scenes.two_box_scene(shadow_catcher=False), (VIEW_W, VIEW_H), scenes.TWO_BOX_CAMERA)
     r.setViews(_views())
     rows = _rows(_views([_moved(c) for c in _cam_dicts()]))
 
@@ -678,10 +474,8 @@ def test_pack_and_render_into_a_buffer_whose_fill_is_pending(ptlib, mode, fn):
 @pytest.mark.parametrize("mode", MODES)
 def test_unpack_display_from_a_buffer_whose_producer_is_pending(ptlib, mode):
     """pt_unpack_display + pt_display_sync + pt_download_display; what pt_display_buffer points to is the same image once the sync is back"""
-    from test_gpu_gbuffer import _hip_runtime
-
     r, padded, (h, w) = _rendered()
-    hip = _hip_runtime()
+    hip = hip_runtime()
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     src = np.random.default_rng(17).integers(1, 0x7F000000, padded).astype(np.int32)
 

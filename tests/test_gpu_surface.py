@@ -6,7 +6,7 @@ words as NaN (payloads are not specified).
 
 Inputs, 131 x 61 (17 x 8 blocks, last column 3 wide, last row 5 high):
   textured: surface_ref.textured_scene() — scenes.textured_scene() with the box's zero texcoords removed, so the box names a texture, has no
-            texcoords and keeps its colour, as that scene's docstring says — under TEX_CAMERA: 7991 pixels, 1844 misses, 5055 on the texture
+            texcoords and keeps its colour, as that scene's docstring says — under S.TEX_CAMERA: 7991 pixels, 1844 misses, 5055 on the texture
             path (ground 2916, wall 2139), 1092 on the colour path (the box), counted with the CPU checker before the first GPU run;
   cornell:  the untextured Cornell box under CORNELL_CAMERA: 3481 hit pixels, 2897 of them with a 3 x 3 neighbourhood on one mesh; at those
             PT_BUF_ALBEDO of a 1-spp frame equals the plane in every bit (0 mismatches; 34 of the other 584 hit pixels differ: the jittered
@@ -19,39 +19,29 @@ import torch
 
 import surface_ref as S
 import temporal_ref as T
-from optixpathtracer_amd import _lib
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame_mask
+from gpu_kit import bits as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_device_update import _affine
-from test_gpu_gbuffer import _hip_runtime, _renderer
-from test_gpu_temporal import _upload
-from test_gpu_views import RECTS, _cam_dicts
+from pass_cases import _hand_made
+from pass_cases import surface_case as _case
+from scene_kit import RECTS, _affine, _cam_dicts
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 W, H = 131, 61
 SENTINEL = S.SENTINEL
-TEX_CAMERA = dict(eye=(2.0, 1.5, -3.0), lookat=(0.0, 0.6, 0.5), up=(0.0, 1.0, 0.0), fovY=35.0)
-INPUTS = {"textured": (S.textured_scene, TEX_CAMERA), "cornell": (scenes.cornell_box, scenes.CORNELL_CAMERA)}
 
 
 # ------------------------------------------------------------------ GPU helpers
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane; offset: one float into its allocation (4-byte aligned only)"""
-    n = h * w * S.WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = (buf[1:] if offset else buf[:-1]).view((h, w, S.WORDS[name]))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _np(t):
-    return t.cpu().numpy()
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, S.WORDS[name]), offset)
 
 
 def _same(got, ref, what, nan_aware=False):
@@ -80,38 +70,8 @@ def _run(r, sc, hit, pixels, what, planes=S.PLANES, mask=None, offset=False, nan
     return ref, got, st
 
 
-class _Case:
-    pass
-
-
-_CASES = {}
-
-
-def _case(name):
-    """The model, its reference arrays, a renderer under the input's camera, its hit plane and its texcoord table.  Built once; the arrays
-    are read-only."""
-    if name not in _CASES:
-        make, cam = INPUTS[name]
-        c = _Case()
-        c.model, c.cam = make(), cam
-        c.sc = S.scene_arrays(c.model)
-        c.r = _renderer(c.model, (W, H), cam)
-        g = c.r.renderGBuffer(("hit",))
-        c.gstats = g["stats"]
-        c.hit = _np(g["hit"])
-        c.table = _np(c.r.copyTexcoordsDevice())
-        for a in [c.hit, c.table] + [v for v in c.sc.values() if isinstance(v, np.ndarray)]:
-            a.setflags(write=False)
-        _CASES[name] = c
-    return _CASES[name]
-
-
 def _frame(w=W, h=H):
-    return np.ones((h, w), bool)
-
-
-def _pixel_mask(block_mask, h=H, w=W):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:h, :w]
+    return whole_frame_mask(h, w)
 
 
 # ------------------------------------------------------------------ 1. the texcoord table
@@ -188,47 +148,6 @@ def test_texture_0_through_the_table_evaluator(ptlib):
     assert np.array_equal(_bits(res["albedo"])[on0][:, :3], rgba.view(np.uint32)[:, :3])
 
 
-# ------------------------------------------------------------------ 4. hand-made hit planes
-def _hand_made(sc, h=H, w=W, seed=29):
-    """(hit plane, category (h, w)): sixteen categories, one pixel in sixteen each, interleaved so that every wave holds all of them"""
-    rng = np.random.default_rng(seed)
-    ntri = len(sc["tri_mesh"])
-    ys, xs = np.mgrid[0:h, 0:w]
-    cat = (xs + 3 * ys) % 16
-    hit = np.zeros((h, w, 8), f32)
-    words = hit.view(np.int32)
-    hit[..., 0] = rng.random((h, w), dtype=f32) * 5 + 1
-    words[..., 4] = rng.integers(-3, 9, (h, w))  # the record's mesh word is never used
-    hit[..., 5:8] = rng.random((h, w, 3), dtype=f32)
-    by_mesh = [np.nonzero(sc["tri_mesh"] == m)[0] for m in range(3)]
-    textured = np.concatenate([by_mesh[0], by_mesh[1]])
-    prim = rng.choice(textured, (h, w)).astype(np.int64)
-    u, v = rng.random((h, w), dtype=f32) * f32(0.5), rng.random((h, w), dtype=f32) * f32(0.5)
-    corners = {0: (0, 0), 1: (1, 0), 2: (0, 1)}
-    for k, (cu, cv) in corners.items():
-        u[cat == k], v[cat == k] = cu, cv
-    e = rng.integers(0, 3, (h, w))
-    s = rng.random((h, w), dtype=f32)
-    u[cat == 3] = np.where(e == 0, s, np.where(e == 1, f32(0), s))[cat == 3]  # the three edges: v = 0, u = 0, u + v = 1
-    v[cat == 3] = np.where(e == 0, f32(0), np.where(e == 1, s, f32(1) - s))[cat == 3]
-    # primitive 0 (the ground, texture 0, 64 x 32): s = 4 (u + v) - 1.5, t = 4 v - 1.5, exact for multiples of 1/256
-    prim[(cat == 4) | (cat == 5)] = 0
-    u[cat == 4], v[cat == 4] = 0.25, 0.375  # (s, t) = (1, 0): exact integers
-    a, b = rng.integers(0, 129, (h, w)), rng.integers(0, 129, (h, w))
-    u[cat == 5], v[cat == 5] = (a / 256).astype(f32)[cat == 5], (b / 256).astype(f32)[cat == 5]  # texel borders and centres
-    for k, m in ((6, 0), (7, 1), (8, 2)):
-        prim[cat == k] = rng.choice(by_mesh[m], (h, w))[cat == k]
-    prim[cat == 9], prim[cat == 10], prim[cat == 11], prim[cat == 12] = -1, ntri, 0x7FFFFFFF, -2
-    u[cat == 13] = np.nan
-    v[cat == 14] = np.where(rng.random((h, w)) < 0.5, f32(np.inf), f32(-np.inf))[cat == 14]
-    prim[cat == 15] = rng.integers(0, ntri, (h, w))[cat == 15]
-    nan_box = (cat == 15) & (sc["tri_mesh"][np.clip(prim, 0, ntri - 1)] == 2) & (xs % 2 == 0)
-    u[nan_box] = np.nan  # non-finite barycentrics on the colour path: not read
-    hit[..., 1], hit[..., 2] = u, v
-    words[..., 3] = prim.astype(np.int32)
-    return hit, cat, nan_box
-
-
 def test_hand_made_hit_planes(ptlib):
     c = _case("textured")
     hit, cat, nan_box = _hand_made(c.sc)
@@ -258,7 +177,7 @@ def test_hand_made_hit_planes(ptlib):
     nby, nbx = c.r.blockGrid()
     mask = np.random.default_rng(6).random((nby, nbx)) < 0.5
     mask[0, 0] = mask[nby - 1, nbx - 1] = True
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     _, got, st = _run(c.r, c.sc, hit, px, "hand-made, masked", mask=mask, nan_aware=True)
     assert 0 < st["pixels"] < n and all((got[k][~px] == SENTINEL).all() for k in S.PLANES)
 
@@ -298,7 +217,7 @@ def test_block_mask(ptlib):
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True  # corner and edge blocks, the 3-wide column and the 5-high row
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     _, got, st = _run(c.r, c.sc, c.hit, px, "a random block mask", mask=mask)
     assert 0 < st["pixels"] < W * H
     for name in S.PLANES:
@@ -323,7 +242,7 @@ def test_two_views_off_the_block_grid(ptlib):
     r = _renderer(c.model, (W, H), c.cam)
     rects = RECTS[:2]
     assert any(v % 8 for rect in rects for v in rect)
-    r.setViews([(x, y, w, h, R.make_camera(dict(cd, **{k: TEX_CAMERA[k] for k in ("eye", "lookat", "fovY")}), w / h)) for (x, y, w, h), cd in zip(rects, _cam_dicts())])
+    r.setViews([(x, y, w, h, R.make_camera(dict(cd, **{k: S.TEX_CAMERA[k] for k in ("eye", "lookat", "fovY")}), w / h)) for (x, y, w, h), cd in zip(rects, _cam_dicts())])
     inside = np.zeros((H, W), bool)
     for x, y, w, h in rects:
         inside[y:y + h, x:x + w] = True
@@ -403,8 +322,8 @@ def _loop(model, cam0, frames, adaptive, plan):
 
 
 def test_loop_with_every_block_sampled_is_the_unmasked_chain(ptlib):
-    a = _loop(S.textured_scene(), TEX_CAMERA, 3, True, dict(min_length=65535, min_pixels=1))
-    b = _loop(S.textured_scene(), TEX_CAMERA, 3, False, None)
+    a = _loop(S.textured_scene(), S.TEX_CAMERA, 3, True, dict(min_length=65535, min_pixels=1))
+    b = _loop(S.textured_scene(), S.TEX_CAMERA, 3, False, None)
     for k, (x, y) in enumerate(zip(a, b)):
         assert x["plan"]["sampled"] == x["plan"]["blocks"]
         for n in x["bits"]:
@@ -413,7 +332,7 @@ def test_loop_with_every_block_sampled_is_the_unmasked_chain(ptlib):
 
 
 def test_loop_under_a_real_plan_fills_every_hit_pixel(ptlib):
-    frames = _loop(S.textured_scene(), TEX_CAMERA, 6, True, dict(threshold=1e3, dark_floor=1.0, min_length=2, min_pixels=8))
+    frames = _loop(S.textured_scene(), S.TEX_CAMERA, 6, True, dict(threshold=1e3, dark_floor=1.0, min_length=2, min_pixels=8))
     skipped = [f["plan"]["blocks"] - f["plan"]["sampled"] for f in frames]
     print("blocks left unrendered per frame:", skipped)
     assert max(skipped[2:]) > 0

@@ -14,20 +14,25 @@ import numpy as np
 import pytest
 import torch
 
-import motion_ref as M
 import surface_aniso_ref as SA
 import surface_lod_ref as SL
 import surface_ref as S
 from conftest import ROOT
-from optixpathtracer_amd import _lib
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame_mask
+from gpu_kit import bits3 as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import same_words as _same
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from gpu_kit import words_differ as _differ
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_device_update import _affine
-from test_gpu_gbuffer import _hip_runtime, _renderer
-from test_gpu_temporal import _upload
-from test_gpu_views import RECTS
-from test_surface_aniso_cabi import GRAZING_CAMERA, R_ANISO, H, W, check_hand_made, ground_truth
-from test_surface_lod_cabi import ground_pixels, rms_against
+from pass_cases import _Case
+from pass_cases import surface_aniso_case as _case
+from scene_kit import RECTS, _affine
+from surface_aniso_ref import GRAZING_CAMERA, R_ANISO, H, W, check_hand_made, ground_truth
+from surface_lod_ref import ground_pixels, rms_against
 
 pytestmark = pytest.mark.gpu
 
@@ -36,67 +41,9 @@ SENTINEL = S.SENTINEL
 COUNTERS = ("pixels", "hits", "stale", "textured", "minified", "anisotropic", "taps")
 
 
-def _bits(t):
-    a = t.cpu().numpy().view(np.uint32)
-    return a.reshape(a.shape[0], a.shape[1], -1)
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _frame(w=W, h=H):
-    return np.ones((h, w), bool)
-
-
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane; offset: one float into its allocation (4-byte aligned only)"""
-    n = h * w * SA.WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = buf[1:] if offset else buf[:-1]
-    t = t.view((h, w, SA.WORDS[name]) if SA.WORDS[name] > 1 else (h, w))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t
-
-
-def _differ(a, b):
-    with np.errstate(all="ignore"):
-        return (a != b) & ~(np.isnan(a.view(f32)) & np.isnan(b.view(f32)))
-
-
-def _same(got, ref, what):
-    for name, a in got.items():
-        neq = _differ(a, ref[name])
-        assert a.shape == ref[name].shape and not neq.any(), f"{what}: {name} differs in {int(neq.sum())} words, first at {np.argwhere(neq)[:3].tolist()}"
-
-
-class _Case:
-    pass
-
-
-_CASES = {}
-INPUTS = {"textured": (S.textured_scene, GRAZING_CAMERA), "cornell": (scenes.cornell_box, scenes.CORNELL_CAMERA)}
-
-
-def _case(name):
-    """the model, its reference arrays, a renderer under the input's camera at W x H, its hit plane, its texcoord table and its pyramid.
-    Built once; the arrays are read-only."""
-    if name not in _CASES:
-        make, cam = INPUTS[name]
-        c = _Case()
-        c.model, c.cam = make(), cam
-        c.sc = S.scene_arrays(c.model)
-        c.verts, c.idx = M.model_arrays(c.model)
-        c.r = _renderer(c.model, (W, H), cam)
-        c.row = R._camera_rows([R.make_camera(cam, W / H)])[0]
-        g = c.r.renderGBuffer(("hit",))
-        c.gstats, c.hit = g["stats"], _np(g["hit"])
-        c.table = c.r.copyTexcoordsDevice()
-        c.bytes = c.r.textureMipsLayout()[1]
-        c.mips = c.r.copyTextureMipsDevice()
-        c.hit.setflags(write=False)
-        _CASES[name] = c
-    return _CASES[name]
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, SA.WORDS[name]), offset)
 
 
 def _run(r, c, hit, pixels, what, max_aniso=8, planes=SA.PLANES, mask=None, scale=1.0, verts=None, rects=None, cams=None, offset=False, sc=None, idx=None,
@@ -119,8 +66,8 @@ def _run(r, c, hit, pixels, what, max_aniso=8, planes=SA.PLANES, mask=None, scal
     return ref, got, st
 
 
-def _pixel_mask(block_mask, h=H, w=W):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:h, :w]
+def _frame(w=W, h=H):
+    return whole_frame_mask(h, w)
 
 
 # ------------------------------------------------------------------ 1. the pass against the reference
@@ -188,7 +135,7 @@ def test_block_mask_and_rank_1_of_3(ptlib):
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     _, got, st = _run(c.r, c, c.hit, px, "a random block mask", mask=mask)
     assert 0 < st["pixels"] < W * H and all((got[n][~px] == SENTINEL).all() for n in SA.PLANES)
     _, _, st = _run(c.r, c, c.hit, np.zeros((H, W), bool), "the empty mask", mask=np.zeros((nby, nbx), bool))

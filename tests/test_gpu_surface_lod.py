@@ -17,15 +17,20 @@ import motion_ref as M
 import surface_lod_ref as SL
 import surface_ref as S
 import temporal_ref as T
-from optixpathtracer_amd import _lib
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame_mask
+from gpu_kit import bits as _bits
+from gpu_kit import bits3 as _plane_bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import same_words as _same
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_device_update import _affine
-from test_gpu_gbuffer import _hip_runtime, _renderer
-from test_gpu_surface import TEX_CAMERA, H, W, _bits, _case, _frame, _hand_made, _np, _pixel_mask
-from test_gpu_temporal import _upload
-from test_gpu_views import RECTS
-from test_surface_lod_cabi import FOOT_BOUND, R_REF, check_footprints, ground_pixels, rms_against
+from pass_cases import H, W, _hand_made
+from pass_cases import surface_case as _case
+from scene_kit import RECTS, _affine
+from surface_lod_ref import FOOT_BOUND, R_REF, check_footprints, ground_pixels, rms_against
 
 pytestmark = pytest.mark.gpu
 
@@ -34,22 +39,8 @@ SENTINEL = S.SENTINEL
 
 
 def _filled(name, h, w):
-    n = h * w * SL.WORDS[name]
-    t = torch.full((4 * n,), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    return t.view((h, w, SL.WORDS[name]) if SL.WORDS[name] > 1 else (h, w))
-
-
-def _plane_bits(t):
-    a = _bits(t)
-    return a.reshape(a.shape[0], a.shape[1], -1)
-
-
-def _same(got, ref, what):
-    for name, a in got.items():
-        b = ref[name]
-        with np.errstate(all="ignore"):
-            neq = (a != b) & ~(np.isnan(a.view(f32)) & np.isnan(b.view(f32)))
-        assert a.shape == b.shape and not neq.any(), f"{what}: {name} differs from float32 NumPy in {int(neq.sum())} words, first at {np.argwhere(neq)[:3].tolist()}"
+    """a sentinel-filled plane of the pass"""
+    return filled(plane_shape(h, w, SL.WORDS[name]))
 
 
 class _Lod:
@@ -60,7 +51,7 @@ _LOD = {}
 
 
 def _lod_case(name):
-    """test_gpu_surface's case with what the LOD pass needs beside it: the model's vertices and indices, the camera row, the pyramid"""
+    """pass_cases.surface_case with what the LOD pass needs beside it: the model's vertices and indices, the camera row, the pyramid"""
     if name not in _LOD:
         c = _case(name)
         k = _Lod()
@@ -88,6 +79,10 @@ def _run(r, k, hit, pixels, what, planes=SL.PLANES, mask=None, scale=1.0, verts=
     want = (int(np.asarray(pixels).sum()), ref["hits"], ref["stale"], ref["textured"], ref["minified"])
     assert (st["pixels"], st["hits"], st["stale"], st["textured"], st["minified"]) == want, (what, st, want)
     return ref, got, st
+
+
+def _frame(w=W, h=H):
+    return whole_frame_mask(h, w)
 
 
 # ------------------------------------------------------------------ 1. the pyramid
@@ -161,7 +156,7 @@ def test_two_views_off_the_block_grid_with_different_cameras(ptlib):
     c = k.c
     r = _renderer(c.model, (W, H), c.cam)
     rects = RECTS[:2]
-    cams = [R.make_camera(TEX_CAMERA, rects[0][2] / rects[0][3]), R.make_camera(dict(TEX_CAMERA, eye=(-1.5, 2.5, -3.5), fovY=50.0), rects[1][2] / rects[1][3])]
+    cams = [R.make_camera(S.TEX_CAMERA, rects[0][2] / rects[0][3]), R.make_camera(dict(S.TEX_CAMERA, eye=(-1.5, 2.5, -3.5), fovY=50.0), rects[1][2] / rects[1][3])]
     r.setViews([(x, y, w, h, cam) for (x, y, w, h), cam in zip(rects, cams)])
     rows = R._camera_rows(cams)
     assert not np.array_equal(rows[0], rows[1])
@@ -188,7 +183,7 @@ def test_block_mask_and_rank_1_of_3(ptlib):
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     _, got, st = _run(c.r, k, c.hit, px, "a random block mask", mask=mask)
     assert 0 < st["pixels"] < W * H and all((got[n][~px] == SENTINEL).all() for n in SL.PLANES)
     _, _, st = _run(c.r, k, c.hit, np.zeros((H, W), bool), "the empty mask", mask=np.zeros((nby, nbx), bool))
@@ -247,7 +242,7 @@ def test_hand_made_hit_planes(ptlib):
     t_c = ((tri[..., 0, :] - row[0:3]) * nrm).sum(-1) / (d * nrm).sum(-1)
     behind = tex & (t_c < -1e-3)
     assert behind.sum() > 200 and (lod[behind] == Lm[behind]).all() and np.isfinite(fp[behind]).all()
-    _, got, st = _run(c.r, k, hit, _pixel_mask(np.ones(c.r.blockGrid(), bool)), "hand-made, a full mask", mask=np.ones(c.r.blockGrid(), bool))
+    _, got, st = _run(c.r, k, hit, pixel_mask(np.ones(c.r.blockGrid(), bool), h=H, w=W), "hand-made, a full mask", mask=np.ones(c.r.blockGrid(), bool))
 
 
 def test_horizon_pixels_whose_offset_ray_misses_the_plane(ptlib):
@@ -502,10 +497,10 @@ def test_loop_with_lod_fills_every_hit_pixel(ptlib):
     var, filt, scratch, albedo = z(1), z(4), z(4), z(4)
     table, mips = r.copyTexcoordsDevice(), r.copyTextureMipsDevice()
     accum = r.deviceBuffer(R.PT_BUF_ACCUM)
-    cam = R.make_camera(TEX_CAMERA, W / H)
+    cam = R.make_camera(S.TEX_CAMERA, W / H)
     skipped = []
     for n in range(5):
-        prev, cam = cam, R.make_camera(T.forward(TEX_CAMERA, 0.01 * n, dx=0.02 * n), W / H)
+        prev, cam = cam, R.make_camera(T.forward(S.TEX_CAMERA, 0.01 * n, dx=0.02 * n), W / H)
         cur, old, i, o = gbuf[n & 1], gbuf[~n & 1], n & 1, ~n & 1
         r.setCamera(cam)
         r.renderGBuffer(("hit", "position", "motion"), prev_cameras=prev, out=cur)

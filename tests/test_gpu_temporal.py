@@ -7,7 +7,7 @@ lengths 0..9 with zeros, a few NaN and inf words).  Valid / invalid pixels and, 
 as tests/test_temporal_cabi.py counts them on CPU-built planes (the test asserts the same coverage on the GPU's planes and prints its counts):
   two_box 131 x 61, dolly 0.65, plane_eps 0:  1240 / 6751  rect 3895 nolookup 102 length 1478 history 160 miss 1835 mesh 213 normal 11 plane 722 min_weight 264
   terrain 131 x 61, dolly 0.5:                2113 / 5878  rect 3385 nolookup 717 length 1031 history 152 miss 1458 mesh 122 normal 186 plane 39 min_weight 299
-  two_box, previous camera behind the scene (test_gpu_gbuffer._behind): every hit pixel's motion is NaN, 0 valid"""
+  two_box, previous camera behind the scene (gbuffer_ref._behind): every hit pixel's motion is NaN, 0 valid"""
 import ctypes as C
 
 import numpy as np
@@ -15,11 +15,16 @@ import pytest
 import torch
 
 import temporal_ref as T
-from optixpathtracer_amd import _lib
+from gbuffer_ref import _behind, _row
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame
+from gpu_kit import bits as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import to_numpy as _np
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_gbuffer import _behind, _hip_runtime, _renderer, _row, _views_and_prev
-from test_gpu_views import RECTS
+from scene_kit import RECTS, _views_and_prev
 
 pytestmark = pytest.mark.gpu
 
@@ -31,27 +36,9 @@ WORDS = _lib.TEMPORAL_PLANES
 
 
 # ------------------------------------------------------------------ GPU helpers
-def _upload(a, offset=False):
-    """a float32 array as a CUDA tensor; offset: one float into its allocation (4-byte aligned only)"""
-    a = np.array(a, f32)  # (a copy: the shared planes are read-only)
-    buf = torch.empty(a.size + 1, dtype=torch.float32, device="cuda:0")
-    t = (buf[1:] if offset else buf[:-1]).view(a.shape)
-    t.copy_(torch.from_numpy(a))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t
-
-
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane"""
-    n = h * w * WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = buf[1:] if offset else buf[:-1]
-    t = t.view((h, w) if WORDS[name] == 1 else (h, w, WORDS[name]))
-    return t.view(torch.int32) if name == "frame_rgba8" else t
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, WORDS[name]), offset, torch.int32 if name == "frame_rgba8" else torch.float32)
 
 
 def _same(got, ref, what):
@@ -82,10 +69,6 @@ def _run(r, orc, planes, rects, pixels, what, mask=None, offset=False, outputs=T
     return ref, st
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
 _CASES = {}
 
 
@@ -111,7 +94,7 @@ def _case(name):
 
 
 def _frame(w=W, h=H):
-    return [(0, 0, w, h)], np.ones((h, w), bool)
+    return whole_frame(w, h)
 
 
 # ------------------------------------------------------------------ 1. real planes
@@ -197,17 +180,13 @@ def test_views(ptlib, orc_det):
 
 
 # ------------------------------------------------------------------ 4. masks and partition
-def _pixel_mask(block_mask):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:H, :W]
-
-
 def test_masks(ptlib, orc_det):
     r, planes, prm = _case("two_box")
     nby, nbx = r.blockGrid()
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True  # corner and edge blocks, the 3-wide column and the 5-high row
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     ref, st = _run(r, orc_det, planes, [(0, 0, W, H)], px, "a random block mask", mask=mask, clear=True, **prm)
     assert 0 < st["pixels"] < W * H and (ref["history_out"][~px] == SENTINEL).all() and not (ref["length_out"][px] == SENTINEL).any()
     _, st = _run(r, orc_det, planes, [(0, 0, W, H)], np.zeros((H, W), bool), "the empty mask", mask=np.zeros((nby, nbx), bool), clear=True, **prm)
@@ -243,7 +222,7 @@ def test_context_buffers_as_planes(ptlib, orc_det):
     r = _renderer(make(), size, cam)
     nby, nbx = r.blockGrid()
     mask = np.random.default_rng(9).random((nby, nbx)) < 0.5
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     r.uploadAccum(planes["color"])
     before = {k: r.download(k).view(np.uint32) for k in (R.PT_BUF_ACCUM, R.PT_BUF_FRAME, R.PT_BUF_COLOR, R.PT_BUF_NORMAL, R.PT_BUF_ALBEDO)}
     assert np.array_equal(before[R.PT_BUF_ACCUM], planes["color"].view(np.uint32))

@@ -9,7 +9,7 @@ import pytest
 
 from conftest import assert_bits_equal
 from optixpathtracer_amd import objloader, scenes
-from test_gpu_parity import _compare, _gpu_render, _oracle_render, _renderer
+from parity_kit import _compare, _gpu_render, _oracle_render, _renderer
 
 pytestmark = pytest.mark.gpu
 

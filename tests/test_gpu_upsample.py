@@ -19,10 +19,17 @@ import torch
 import filter_ref as F
 import upsample_ref as U
 from conftest import ROOT
-from optixpathtracer_amd import _lib
+from gpu_kit import filled, pixel_mask, plane_shape, whole_frame
+from gpu_kit import bits as _bits
+from gpu_kit import hip_runtime as _hip_runtime
+from gpu_kit import plane_renderer as _renderer
+from gpu_kit import upload as _upload
+from optixpathtracer_amd import _lib, scenes
 from optixpathtracer_amd import renderer as R
-from optixpathtracer_amd import scenes
-from test_gpu_gbuffer import _hip_runtime, _renderer
+from pass_cases import _UPSAMPLE as _CASES
+from pass_cases import _hit_and_position as _gbuffer
+from pass_cases import _upsample_model as _model
+from pass_cases import upsample_case as _case
 
 pytestmark = pytest.mark.gpu
 
@@ -35,30 +42,9 @@ VIEWS = ((0, 0, 60, 36), (96, 0, 36, 48))
 
 
 # ------------------------------------------------------------------ GPU helpers
-def _upload(a, offset=False):
-    """a float32 array as a CUDA tensor; offset: one float into its allocation (4-byte aligned only)"""
-    a = np.array(a, f32)
-    buf = torch.empty(a.size + 1, dtype=torch.float32, device="cuda:0")
-    t = (buf[1:] if offset else buf[:-1]).view(a.shape)
-    t.copy_(torch.from_numpy(a))
-    assert t.is_contiguous() and t.data_ptr() % 16 == (4 if offset else 0)
-    return t
-
-
 def _filled(name, h, w, offset=False):
-    """a sentinel-filled output plane"""
-    n = h * w * WORDS[name]
-    buf = torch.full((4 * (n + 1),), 0xA5, dtype=torch.uint8, device="cuda:0").view(torch.float32)
-    t = buf[1:] if offset else buf[:-1]
-    return t.view((h, w) if WORDS[name] == 1 else (h, w, WORDS[name]))
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _np(t):
-    return t.cpu().numpy()
+    """a sentinel-filled plane of the pass; offset: one float into its allocation (4-byte aligned only)"""
+    return filled(plane_shape(h, w, WORDS[name]), offset)
 
 
 def _run(r, lo, hi, s, rects, pixels, what, mask=None, offset=False, weight=True, **prm):
@@ -83,45 +69,8 @@ def _run(r, lo, hi, s, rects, pixels, what, mask=None, offset=False, weight=True
     return ref, st
 
 
-def _model(name):
-    return {"two_box": (lambda: scenes.two_box_scene(shadow_catcher=False), scenes.TWO_BOX_CAMERA),
-            "terrain": (lambda: scenes.voxel_terrain(n=64, target_tris=20000), scenes.TERRAIN_CAMERA)}[name]
-
-
-_CASES = {}
-
-
-def _gbuffer(r):
-    g = r.renderGBuffer(("hit", "position"))
-    return dict(hit=_np(g["hit"]), position=_np(g["position"]))
-
-
-def _case(name, s):
-    """(the full-size renderer, lo planes with a random colour, hi planes) of `name` at 132 x 60 over 132/s x 60/s: two contexts over one
-    model.  Built once; the arrays are read-only."""
-    if (name, s) not in _CASES:
-        make, cam = _model(name)
-        if name not in _CASES:
-            model = make()
-            r = _renderer(model, (W, H), cam)
-            _CASES[name] = (model, r, _gbuffer(r))
-        model, r, hi = _CASES[name]
-        low = _renderer(model, (W // s, H // s), cam)
-        lo = _gbuffer(low)
-        low.close()
-        lo["color"] = F.random_planes(np.random.default_rng(50 + s), H // s, W // s)[0]
-        for a in list(lo.values()) + list(hi.values()):
-            a.setflags(write=False)
-        _CASES[(name, s)] = (r, lo, hi)
-    return _CASES[(name, s)]
-
-
 def _frame(w=W, h=H):
-    return [(0, 0, w, h)], np.ones((h, w), bool)
-
-
-def _pixel_mask(block_mask, w=W, h=H):
-    return np.repeat(np.repeat(block_mask, 8, 0), 8, 1)[:h, :w]
+    return whole_frame(w, h)
 
 
 # ------------------------------------------------------------------ 1. real planes
@@ -197,7 +146,7 @@ def test_block_mask(ptlib):
     mask = np.random.default_rng(5).random((nby, nbx)) < 0.4
     mask[0, 0] = mask[nby - 1, nbx - 1] = mask[0, nbx - 1] = mask[nby - 1, 3] = True  # corner and edge blocks, the 4-wide column and the 4-high row
     mask[1, 1] = False
-    px = _pixel_mask(mask)
+    px = pixel_mask(mask, h=H, w=W)
     ref, st = _run(r, lo, hi, 3, [(0, 0, W, H)], px, "a random block mask", mask=mask)
     assert 0 < st["pixels"] < W * H and (ref["out"][~px] == SENTINEL).all()
     # the low-res plane has no block set: a masked pixel gets what it gets in the whole frame

@@ -14,36 +14,16 @@ import pytest
 
 from conftest import assert_bits_equal
 from optixpathtracer_amd import scenes
-from test_gpu_parity import _oracle_render
+from parity_kit import _oracle_render
+from scene_kit import RECTS, VIEW_H, VIEW_W, _cam_dicts, _rows, _views
 
 pytestmark = pytest.mark.gpu
 
-W, H, SPP, NSUB = 131, 61, 2, 3
+W, H, SPP, NSUB = VIEW_W, VIEW_H, 2, 3
 NBX, NBY = (W + 7) // 8, (H + 7) // 8
-RECTS = [(0, 0, 61, 37), (64, 0, 67, 29), (0, 40, 24, 21), (72, 32, 7, 5)]
 CASES = [(False, "0"), (False, "1"), (True, "0"), (True, "1")]
 IDS = ["plain-chain", "plain-fused", "catcher-chain", "catcher-fused"]
 STAT_SUMS = ("paths", "radiance_rays", "shadow_rays", "shaded_hits")
-
-
-def _cam_dicts():
-    base = scenes.TWO_BOX_CAMERA
-    ex, ey, ez = base["eye"]
-    return [dict(base, eye=(ex + 0.1, ey, ez)), dict(base, eye=(ex - 0.1, ey, ez)), dict(base, fovY=55.0), dict(base, eye=(2.0, 3.0, -4.5))]
-
-
-def _views(cams=None):
-    from optixpathtracer_amd import renderer as R
-
-    cams = cams or _cam_dicts()
-    return [(x, y, w, h, R.make_camera(c, w / h)) for (x, y, w, h), c in zip(RECTS, cams)]
-
-
-def _rows(views):
-    """the (n, 12) eye, U, V, W rows of a list of views"""
-    from optixpathtracer_amd import renderer as R
-
-    return R._camera_rows([v[4] for v in views])
 
 
 def _probe():

@@ -1,6 +1,7 @@
 """loadProbe restatement: RGBE decode (flat and RLE scanlines), stb_image's conversion, alpha = 1."""
 import numpy as np
 
+from loader_inputs import _golden_module, hdr_live_inputs
 from optixpathtracer_amd import hdrloader, scenes
 
 
@@ -65,31 +66,6 @@ def test_load_hdr_golden(name):
     ref = G["hdr_" + name]
     assert a.shape == ref.shape and a.dtype == np.float32 and a.tobytes() == ref.tobytes()
     assert (a[..., 3] == 1).all()
-
-
-def _golden_module(name):
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, "golden", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def hdr_live_inputs(d):
-    """The 40 random RGBE images of test_load_hdr_live_random, flat and run-length encoded, written under d (seeded): their paths."""
-    mod = _golden_module("make_model_golden")
-    rng = np.random.default_rng(5)
-    for it in range(40):
-        h, w = int(rng.integers(1, 12)), int(rng.choice([1, 7, 8, 9, 33, 128, 129, 500]))
-        rgbe = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
-        if it % 3 == 0:
-            rgbe[:, : w // 2] = rgbe[:, :1]  # long runs
-        if it % 4 == 0:
-            rgbe[..., 3] = rng.choice([0, 1, 127, 128, 129, 255], (h, w))
-        path = os.path.join(d, f"r{it}.hdr")
-        (mod.write_rle_hdr if (it % 2 == 0 and w >= 8) else mod.write_flat_hdr)(path, rgbe)
-        yield path
 
 
 def test_load_hdr_live_random(tmp_path):

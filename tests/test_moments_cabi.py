@@ -7,13 +7,13 @@ window counts exactly the pixels the header says, and the inputs of tests/test_g
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import moments_ref as MR
 import temporal_ref as T
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -27,18 +27,14 @@ MOD_STATS_FIELDS = ("pixels", "kernel_ms")
 NEW = ("pt_temporal_moments", "pt_modulate_planes")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 # ------------------------------------------------------------------ surface
 def test_library_exports_the_entry_points():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name in NEW:
         assert name in _lib.EXPORTS and hasattr(L, name)
-        assert name in _header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
-        assert name in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+        assert name in header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
+        assert name in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     assert re.search(r"int\s+pt_temporal_moments\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_tmom_desc\s*\*\s*\w*\s*,\s*pt_tmom_stats\s*\*", src)
     assert re.search(r"int\s+pt_modulate_planes\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_modulate_desc\s*\*\s*\w*\s*,\s*pt_modulate_stats\s*\*", src)
     assert re.search(r"enum\s+pt_tmom_flags\s*\{\s*PT_TMOM_CLEAR_COLOR\s*=\s*1\s*,\s*PT_TMOM_CLAMP\s*=\s*2\s*\}", src)
@@ -47,23 +43,9 @@ def test_library_exports_the_entry_points():
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    got_all, mine_all, args = [], [], []
-    for D, fields, cname, want in ((_lib.TMomDesc, DESC_FIELDS, "pt_tmom_desc", [152] + list(range(0, 120, 8)) + [120, 124, 128, 132, 136, 140, 144, 148]),
-                                   (_lib.TMomStats, STATS_FIELDS, "pt_tmom_stats", [32, 0, 8, 16, 24]),
-                                   (_lib.ModulateDesc, MOD_FIELDS, "pt_modulate_desc", [48, 0, 8, 16, 24, 32, 40, 44]),
-                                   (_lib.ModulateStats, MOD_STATS_FIELDS, "pt_modulate_stats", [16, 0, 8])):
-        assert [n for n, _ in D._fields_] == list(fields)
-        mine = [C.sizeof(D)] + [getattr(D, n).offset for n in fields]
-        assert mine == want, (cname, mine)
-        mine_all += mine
-        args += [f"sizeof({cname})"] + [f"offsetof({cname}, {n})" for n in fields]
-    fmt = " ".join(["%zu"] * len(mine_all))
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {", ".join(args)}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got_all = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got_all == mine_all
+    check_layout(tmp_path, [(_lib.TMomDesc, "pt_tmom_desc", DESC_FIELDS), (_lib.TMomStats, "pt_tmom_stats", STATS_FIELDS),
+                            (_lib.ModulateDesc, "pt_modulate_desc", MOD_FIELDS), (_lib.ModulateStats, "pt_modulate_stats", MOD_STATS_FIELDS)],
+                 [152] + list(range(0, 120, 8)) + [120, 124, 128, 132, 136, 140, 144, 148] + [32, 0, 8, 16, 24] + [48, 0, 8, 16, 24, 32, 40, 44] + [16, 0, 8])
     assert tuple(_lib.TMOM_PLANES) == DESC_FIELDS[:14] and _lib.TMOM_OUTPUTS == MR.OUTPUTS == DESC_FIELDS[10:14]
     assert {k: _lib.TMOM_PLANES[k] for k in MR.OUTPUTS} == MR.WORDS
     assert tuple(_lib.MODULATE_PLANES) == MOD_FIELDS[:4] and _lib.MODULATE_OUTPUTS == MOD_FIELDS[2:4]
@@ -82,11 +64,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    m.color = outs; m.albedo = albedo; m.out = outs; m.frame_rgba8 = frame;\n"
             "    return pt_modulate_planes(c, &m, &ms);\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -111,25 +89,22 @@ def test_python_facade_checks_its_arguments():
     import torch
 
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     for name in ("temporalMoments", "modulatePlanes"):
         assert callable(getattr(R.SampleRenderer, name, None))
     # on an object without a context: what the methods refuse, they refuse before the library is called
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams = 0, R.LaunchParams()
-    r.launchParams.frame.size = (4, 4)
+    r = bare_renderer()
     outs = dict(history_out=1, moments_out=1, length_out=1, variance_out=1)
     with pytest.raises(ValueError, match="temporalMoments: motion is required"):
         r.temporalMoments(1, None, 1, 1, 1, 1, 1, 1, 1, **outs)
     with pytest.raises(ValueError, match="temporalMoments: moments_in is required"):
         r.temporalMoments(1, 1, 1, 1, 1, 1, 1, None, 1, **outs)
     with pytest.raises(ValueError, match=r"temporalMoments: moments_in: a contiguous torch.float32 tensor of shape \(4, 4, 2\) is expected"):
-        r.temporalMoments(1, 1, 1, 1, 1, 1, 1, _fake_cuda((4, 4, 4)), 1, **outs)
+        r.temporalMoments(1, 1, 1, 1, 1, 1, 1, fake_cuda((4, 4, 4)), 1, **outs)
     with pytest.raises(ValueError, match=r"temporalMoments: albedo: a contiguous torch.float32 tensor of shape \(4, 4, 4\) is expected"):
-        r.temporalMoments(1, 1, 1, 1, 1, 1, 1, 1, 1, albedo=_fake_cuda((4, 4, 3)), **outs)
+        r.temporalMoments(1, 1, 1, 1, 1, 1, 1, 1, 1, albedo=fake_cuda((4, 4, 3)), **outs)
     with pytest.raises(ValueError, match=r"variance_out: a contiguous torch.float32 tensor of shape \(4, 4\) is expected"):
-        r.temporalMoments(1, 1, 1, 1, 1, 1, 1, 1, 1, **dict(outs, variance_out=_fake_cuda((4, 4, 1))))
+        r.temporalMoments(1, 1, 1, 1, 1, 1, 1, 1, 1, **dict(outs, variance_out=fake_cuda((4, 4, 1))))
     with pytest.raises(TypeError, match="temporalMoments: color: a torch tensor or a device pointer"):
         r.temporalMoments(np.zeros((4, 4, 4), f32), 1, 1, 1, 1, 1, 1, 1, 1, **outs)
     with pytest.raises(ValueError, match="temporalMoments: hit: the tensor is on cpu"):
@@ -144,19 +119,19 @@ def test_python_facade_checks_its_arguments():
     with pytest.raises(ValueError, match="modulatePlanes: color is required"):
         r.modulatePlanes(None, out=1)
     with pytest.raises(ValueError, match=r"modulatePlanes: albedo: a contiguous torch.float32 tensor of shape \(4, 4, 4\) is expected"):
-        r.modulatePlanes(1, albedo=_fake_cuda((4, 4)), out=1)
+        r.modulatePlanes(1, albedo=fake_cuda((4, 4)), out=1)
     with pytest.raises(ValueError, match="modulatePlanes: frame_rgba8: a contiguous torch.int32 tensor of shape .4, 4. or torch.uint8"):
-        r.modulatePlanes(1, out=1, frame=_fake_cuda((4, 4)))
+        r.modulatePlanes(1, out=1, frame=fake_cuda((4, 4)))
     with pytest.raises(ValueError, match="modulatePlanes: the mask needs"):
         r.modulatePlanes(1, out=1, mask=np.ones((2, 2)))
     with pytest.raises(ValueError, match="the context on GPU 1"):
         r._device = 1
-        r.modulatePlanes(_fake_cuda((4, 4, 4)), out=1)
+        r.modulatePlanes(fake_cuda((4, 4, 4)), out=1)
 
 
 def test_cxx_facade_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t stage(SampleRenderer& sample, pt_tmom_desc d, pt_modulate_desc m) {\n"
@@ -168,11 +143,10 @@ def test_cxx_facade_compiles(tmp_path):
         "    return sample.temporalMoments(d).clamped + s.reprojected + sample.modulatePlanes(m).pixels + ms.pixels;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("den(q).k = 1.0f when albedo == NULL", "den(q).k = a > albedo_min ? a : 1.0f", "a NaN gives 1, a miss's zero gives 1",
                  "d(q).k = (color[q].k * color_scale) / den(q).k", "the multiplication first, then the division",
                  "d_p = d(p); l = lum(d_p); m = (l, l * l)", "both words of moments_in[q] finite (exponent-bit test)",

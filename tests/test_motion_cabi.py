@@ -7,13 +7,13 @@ give the stated words."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import motion_ref as M
 import temporal_ref as T
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -23,18 +23,14 @@ STATS_FIELDS = ("pixels", "hits", "stale", "kernel_ms")
 NEW = ("pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_library_exports_the_entry_points():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name in NEW:
         assert name in _lib.EXPORTS and hasattr(L, name)
-        assert name in _header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
+        assert name in header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
     for name in NEW[1:]:  # the two that take device pointers
-        assert name in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+        assert name in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     assert re.search(r"int\s+pt_vertex_count\s*\(\s*const\s+pt_ctx\s*\*\s*\w+\s*,\s*uint32_t\s*\*\s*\w+\s*,\s*uint32_t\s*\*\s*\w+\s*\)", src)
     assert re.search(r"int\s+pt_copy_vertices_device\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*float\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*\)", src)
     assert re.search(r"int\s+pt_motion_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_motion_desc\s*\*\s*\w+\s*,\s*pt_motion_stats\s*\*", src)
@@ -42,19 +38,8 @@ def test_library_exports_the_entry_points():
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, S = _lib.MotionDesc, _lib.MotionStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in S._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(S)] + [getattr(S, n).offset for n in STATS_FIELDS]
-    assert mine == [72, 0, 8, 16, 24, 32, 40, 48, 56, 64] + [32, 0, 8, 16, 24]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_motion_desc)"] + [f"offsetof(pt_motion_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_motion_stats)"] +
-                     [f"offsetof(pt_motion_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.MotionDesc, "pt_motion_desc", DESC_FIELDS), (_lib.MotionStats, "pt_motion_stats", STATS_FIELDS)],
+                 [72, 0, 8, 16, 24, 32, 40, 48, 56, 64] + [32, 0, 8, 16, 24])
     assert _lib.MOTION_PLANES == M.WORDS and tuple(_lib.MOTION_PLANES) == M.PLANES == DESC_FIELDS[2:5]
 
 
@@ -68,11 +53,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.hit = hit; d.prev_vertices = snapshot; d.motion = motion; d.prev_cameras = cams; d.flags = PT_MOTION_RESERVED;\n"
             "    return pt_motion_planes(c, &d, &s);\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -97,15 +78,12 @@ def test_python_facade_checks_its_arguments():
     import torch
 
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     for name in ("copyVerticesDevice", "motionPlanes", "vertexCount"):
         assert callable(getattr(R.SampleRenderer, name, None))
     # on an object without a context: what the methods refuse, they refuse before the library is called
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams, r._nv = 0, R.LaunchParams(), [5, 3]
-    r.launchParams.frame.size = (4, 4)
-    hit, pv = _fake_cuda((4, 4, 8)), _fake_cuda((8, 3))
+    r = bare_renderer()
+    hit, pv = fake_cuda((4, 4, 8)), fake_cuda((8, 3))
     with pytest.raises(ValueError, match="unknown plane 'depth'"):
         r.motionPlanes(hit, pv, planes=("depth",))
     with pytest.raises(ValueError, match="`out` names a plane that `planes` does not"):
@@ -121,22 +99,22 @@ def test_python_facade_checks_its_arguments():
     with pytest.raises(ValueError, match="motionPlanes: hit: the tensor is on cpu"):
         r.motionPlanes(torch.zeros((4, 4, 8)), pv, planes=("prev_point",))
     with pytest.raises(ValueError, match=r"prev_vertices: a contiguous torch.float32 tensor of shape \(8, 3\) is expected"):
-        r.motionPlanes(hit, _fake_cuda((7, 3)), planes=("prev_point",))
+        r.motionPlanes(hit, fake_cuda((7, 3)), planes=("prev_point",))
     with pytest.raises(ValueError, match=r"prev_surface: a contiguous torch.float32 tensor of shape \(4, 4, 8\) is expected"):
-        r.motionPlanes(hit, pv, planes=("prev_surface",), out=dict(prev_surface=_fake_cuda((4, 4, 4))))
+        r.motionPlanes(hit, pv, planes=("prev_surface",), out=dict(prev_surface=fake_cuda((4, 4, 4))))
     with pytest.raises(ValueError, match="the mask needs"):
         r.blockGrid = lambda: (1, 1)
-        r.motionPlanes(hit, pv, planes=("prev_point",), out=dict(prev_point=_fake_cuda((4, 4, 4))), mask=np.ones((2, 2)))
+        r.motionPlanes(hit, pv, planes=("prev_point",), out=dict(prev_point=fake_cuda((4, 4, 4))), mask=np.ones((2, 2)))
     with pytest.raises(ValueError, match=r"copyVerticesDevice: out: a contiguous torch.float32 tensor of shape \(8, 3\) is expected"):
-        r.copyVerticesDevice(out=_fake_cuda((8, 4)))
+        r.copyVerticesDevice(out=fake_cuda((8, 4)))
     with pytest.raises(ValueError, match="the context on GPU 1"):
         r._device = 1
-        r.copyVerticesDevice(out=_fake_cuda((8, 3)))
+        r.copyVerticesDevice(out=fake_cuda((8, 3)))
 
 
 def test_cxx_facade_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t motion(SampleRenderer& sample, pt_motion_desc d, float* snapshot) {\n"
@@ -148,11 +126,10 @@ def test_cxx_facade_compiles(tmp_path):
         "    return sample.motionPlanes(d).hits + s.stale;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("w0 = (1.0f - u) - v; Q = (p0*w0 + p1*u) + p2*v per component; ngp = normalize3(cross3(p1 - p0, p2 - p0))",
                  "i_k = idx[3*prim + k]", "prev_point[p] = (Q, 1.0f)", "with words 5..7 (ng) replaced by ngp", "q = Q - e'",
                  "equal to pt_render_gbuffer's motion plane bit for bit at every miss", "no address is formed from it",
@@ -186,7 +163,7 @@ def _four_taps_on_mesh(motion, prev_mesh, mesh):
 
 
 def test_normal_wise_move_keeps_the_history(orc_det):
-    import test_gpu_gbuffer as G
+    import gbuffer_ref as G
 
     w, h = M.QUAD_SIZE
     cam = M.QUAD_CAMERA
@@ -232,7 +209,7 @@ STATIC_BOUND_PX = 4 * STATIC_MEASURED_PX
 
 
 def test_static_geometry_gives_the_gbuffer_motion(orc_det):
-    import test_gpu_gbuffer as G
+    import gbuffer_ref as G
 
     worst = 0.0
     for name, (make, size, cam, prev, _, _) in T.real_inputs().items():

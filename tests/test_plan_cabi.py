@@ -7,7 +7,6 @@ often enough."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import pytest
 import moments_ref as MR
 import plan_ref as PR
 import temporal_ref as T
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -25,41 +25,23 @@ CARRY_FIELDS = PR.INPUTS + PR.OUTPUTS + ("block_mask", "normal_cos", "plane_eps"
 NEW = ("pt_sample_plan", "pt_temporal_carry")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 # ------------------------------------------------------------------ surface
 def test_library_exports_the_entry_points():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name in NEW:
         assert name in _lib.EXPORTS and hasattr(L, name)
-        assert name in _header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
-        assert name in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+        assert name in header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
+        assert name in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     assert re.search(r"int\s+pt_sample_plan\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_plan_desc\s*\*\s*\w*\s*,\s*pt_plan_stats\s*\*", src)
     assert re.search(r"int\s+pt_temporal_carry\s*\(\s*pt_ctx\s*\*\s*\w*\s*,\s*const\s+pt_carry_desc\s*\*\s*\w*\s*,\s*pt_carry_stats\s*\*", src)
     assert L.pt_version().startswith(b"ptamd 0.4")
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    mine_all, args = [], []
-    for D, fields, cname, want in ((_lib.PlanDesc, PLAN_FIELDS, "pt_plan_desc", [120] + list(range(0, 80, 8)) + list(range(80, 120, 4))),
-                                   (_lib.PlanStats, PR.PLAN_STATS + ("kernel_ms",), "pt_plan_stats", [72] + list(range(0, 72, 8))),
-                                   (_lib.CarryDesc, CARRY_FIELDS, "pt_carry_desc", [120] + list(range(0, 104, 8)) + [104, 108, 112, 116]),
-                                   (_lib.CarryStats, PR.CARRY_STATS + ("kernel_ms",), "pt_carry_stats", [32, 0, 8, 16, 24])):
-        assert [n for n, _ in D._fields_] == list(fields)
-        mine = [C.sizeof(D)] + [getattr(D, n).offset for n in fields]
-        assert mine == want, (cname, mine)
-        mine_all += mine
-        args += [f"sizeof({cname})"] + [f"offsetof({cname}, {n})" for n in fields]
-    fmt = " ".join(["%zu"] * len(mine_all))
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {", ".join(args)}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine_all
+    check_layout(tmp_path, [(_lib.PlanDesc, "pt_plan_desc", PLAN_FIELDS), (_lib.PlanStats, "pt_plan_stats", PR.PLAN_STATS + ("kernel_ms",)),
+                            (_lib.CarryDesc, "pt_carry_desc", CARRY_FIELDS), (_lib.CarryStats, "pt_carry_stats", PR.CARRY_STATS + ("kernel_ms",))],
+                 [120] + list(range(0, 80, 8)) + list(range(80, 120, 4)) + [72] + list(range(0, 72, 8)) + [120] + list(range(0, 104, 8)) + [104, 108, 112, 116] + [32, 0, 8, 16, 24])
     assert tuple(_lib.PLAN_PLANES) == PR.INPUTS and tuple(_lib.CARRY_PLANES) == PR.INPUTS + PR.OUTPUTS and _lib.CARRY_OUTPUTS == PR.OUTPUTS
     assert {k: _lib.CARRY_PLANES[k] for k in PR.OUTPUTS} == PR.WORDS == {k: _lib.TMOM_PLANES[k] for k in PR.OUTPUTS}
     assert all(_lib.PLAN_PLANES[k] == _lib.TMOM_PLANES[k] for k in PR.INPUTS)
@@ -78,11 +60,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    if (pt_temporal_carry(c, &k, &ks)) return -1;\n"
             "    return ks.lost == ks.pixels - ks.carried ? 0 : -1;\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -105,18 +83,15 @@ def test_null_context_and_null_description_are_refused_without_a_gpu():
 
 def test_python_facade_checks_its_arguments():
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     for name in ("samplePlan", "temporalCarry"):
         assert callable(getattr(R.SampleRenderer, name, None))
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams = 0, R.LaunchParams()
-    r.launchParams.frame.size = (4, 4)
+    r = bare_renderer()
     r.blockGrid = lambda: (1, 1)
     with pytest.raises(ValueError, match="samplePlan: motion is required"):
         r.samplePlan(None, 1, 1, 1, 1, 1, 1, 1)
     with pytest.raises(ValueError, match=r"samplePlan: moments_in: a contiguous torch.float32 tensor of shape \(4, 4, 2\) is expected"):
-        r.samplePlan(1, 1, 1, 1, 1, 1, _fake_cuda((4, 4, 4)), 1)
+        r.samplePlan(1, 1, 1, 1, 1, 1, fake_cuda((4, 4, 4)), 1)
     with pytest.raises(ValueError, match="samplePlan: the mask needs"):
         r.samplePlan(1, 1, 1, 1, 1, 1, 1, 1, mask=np.ones((2, 2)))
     with pytest.raises(ValueError, match=r"samplePlan: min_pixels must be in \[1,64\]"):
@@ -127,14 +102,14 @@ def test_python_facade_checks_its_arguments():
     with pytest.raises(ValueError, match="temporalCarry: length_in is required"):
         r.temporalCarry(1, 1, 1, 1, 1, 1, 1, None, **outs)
     with pytest.raises(ValueError, match=r"temporalCarry: variance_out: a contiguous torch.float32 tensor of shape \(4, 4\) is expected"):
-        r.temporalCarry(1, 1, 1, 1, 1, 1, 1, 1, **dict(outs, variance_out=_fake_cuda((4, 4, 1))))
+        r.temporalCarry(1, 1, 1, 1, 1, 1, 1, 1, **dict(outs, variance_out=fake_cuda((4, 4, 1))))
     with pytest.raises(ValueError, match="temporalCarry: the mask needs"):
         r.temporalCarry(1, 1, 1, 1, 1, 1, 1, 1, mask=np.ones((2, 2)), **outs)
 
 
 def test_cxx_facade_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t stage(SampleRenderer& sample, pt_plan_desc d, pt_carry_desc k) {\n"
@@ -145,11 +120,10 @@ def test_cxx_facade_compiles(tmp_path):
         "    return sample.samplePlan(d).sampled + s.by_lost + sample.temporalCarry(k).carried + ks.lost;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("px = (float)x + motion[p].x; py = (float)y + motion[p].y", "tap weights w_ij = wx_i * wy_j",
                  "the three colour words of history_in[q] and both words of moments_in[q] are finite (exponent-bit test)",
                  "Tap order (0,0), (1,0), (0,1), (1,1)", "Wsum = ((w00 + w10) + w01) + w11",

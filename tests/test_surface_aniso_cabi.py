@@ -3,7 +3,7 @@ match the compiler's layout, the header compiles as C99 and C++17 and states the
 both facades have the method; and the float32 NumPy reference (tests/surface_aniso_ref.py) is held against the two passes it must fall back
 to, against a float64 restatement of its tap offsets, and against a float64 supersample of the pixel.
 
-This file records one figure for tests/test_gpu_surface_aniso.py, from the references alone, on CPU-built planes of the textured scene's
+This file pins one figure (kept in tests/surface_aniso_ref.py) for tests/test_gpu_surface_aniso.py, from the references alone, on CPU-built planes of the textured scene's
 ground under GRAZING_CAMERA (temporal_ref.cpu_planes through motion_ref.cpu_planes, under the library's own camera) — no bound comes from a kernel's output;
 profiles/surface_aniso.md holds the same figure:
 
@@ -12,9 +12,7 @@ profiles/surface_aniso.md holds the same figure:
   The GPU test asserts rms(aniso) <= ((1 + R_ANISO) / 2) * rms(lod) on the GPU's own planes.  The same taps laid along the minor axis and
   the rule with N forced to 1 both miss that bound (shown below)."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,54 +21,34 @@ import motion_ref as M
 import surface_aniso_ref as SA
 import surface_lod_ref as SL
 import surface_ref as S
-from conftest import ROOT
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_section
+from gbuffer_ref import _row
 from optixpathtracer_amd import _lib
-from test_surface_lod_cabi import ground_pixels, rms_against
+from surface_aniso_ref import GRAZING_CAMERA, R_ANISO, H, W, check_hand_made, ground_truth
+from surface_lod_ref import ground_pixels, rms_against
 
 f32 = np.float32
-W, H = 131, 59
-GRAZING_CAMERA = dict(eye=(2.0, 0.35, -3.0), lookat=(0.0, 0.2, 0.5), up=(0.0, 1.0, 0.0), fovY=35.0)
 DESC_FIELDS = ("hit", "prim_texcoords", "mips", "mips_bytes", "albedo", "texcoord", "footprint", "lod", "block_mask", "footprint_scale", "taps", "max_aniso",
                "flags")
 STATS_FIELDS = ("pixels", "hits", "stale", "textured", "minified", "anisotropic", "taps", "kernel_ms")
 NAME = "pt_surface_aniso_planes"
 
-# measured 0.19391 (rms 0.0122 anisotropic, 0.0627 isotropic, 3081 pixels, N >= 3 on 0.824 of them); the taps along the minor axis give 0.0809
-# (1.290 x isotropic), N forced to 1 gives 0.0627 (1.000 x): see test_anisotropic_albedo_of_the_reference_is_closer_to_the_pixel_average.
-# Under the non-grazing camera of tests/test_surface_lod_cabi.py (131 x 61): ratio 0.21688 (0.0125 against 0.0578, 2535 pixels), recorded only.
-R_ANISO = 0.194
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
 
 def test_library_exports_the_entry_point():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert NAME in _lib.EXPORTS and hasattr(L, NAME)
-    assert NAME in _header().split("VERSIONING.")[1].split("*/")[0]
-    assert NAME in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+    assert NAME in header().split("VERSIONING.")[1].split("*/")[0]
+    assert NAME in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     assert re.search(r"int\s+pt_surface_aniso_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_surface_aniso_desc\s*\*\s*\w+\s*,\s*pt_surface_aniso_stats\s*\*", src)
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, St = _lib.SurfaceAnisoDesc, _lib.SurfaceAnisoStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in St._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(St)] + [getattr(St, n).offset for n in STATS_FIELDS]
-    assert mine == [96, 0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 88, 92] + [64, 0, 8, 16, 24, 32, 40, 48, 56]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_surface_aniso_desc)"] + [f"offsetof(pt_surface_aniso_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_surface_aniso_stats)"] +
-                     [f"offsetof(pt_surface_aniso_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.SurfaceAnisoDesc, "pt_surface_aniso_desc", DESC_FIELDS), (_lib.SurfaceAnisoStats, "pt_surface_aniso_stats", STATS_FIELDS)],
+                 [96, 0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 88, 92] + [64, 0, 8, 16, 24, 32, 40, 48, 56])
     assert _lib.SURFACE_ANISO_PLANES == SA.WORDS and tuple(_lib.SURFACE_ANISO_PLANES) == SA.PLANES
     # the first ten fields are pt_surface_lod_desc's, at its offsets; that struct and its stats keep their layout
-    Dl = _lib.SurfaceLodDesc
+    D, Dl = _lib.SurfaceAnisoDesc, _lib.SurfaceLodDesc
     assert [(n, getattr(D, n).offset) for n in DESC_FIELDS[:10]] == [(n, getattr(Dl, n).offset) for n, _ in Dl._fields_[:10]]
     assert C.sizeof(Dl) == 80 and C.sizeof(_lib.SurfaceLodStats) == 48 and _lib.SURFACE_LOD_PLANES == SL.WORDS
 
@@ -84,11 +62,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.flags = PT_SURFACE_ANISO_RESERVED;\n"
             "    return pt_surface_aniso_planes(c, &d, &s) || s.anisotropic > s.minified || s.taps < s.textured;\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_arguments_are_refused_without_a_gpu():
@@ -104,13 +78,10 @@ def test_facades_have_the_method(tmp_path):
     import torch  # noqa: F401
 
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     assert callable(getattr(R.SampleRenderer, "surfaceAnisoPlanes", None))
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams, r._nv = 0, R.LaunchParams(), [5, 3]
-    r.launchParams.frame.size = (4, 4)
-    hit = _fake_cuda((4, 4, 8))
+    r = bare_renderer()
+    hit = fake_cuda((4, 4, 8))
     with pytest.raises(ValueError, match="unknown plane 'depth'"):
         r.surfaceAnisoPlanes(hit, planes=("depth",))
     with pytest.raises(ValueError, match="`out` names a plane that `planes` does not"):
@@ -123,9 +94,9 @@ def test_facades_have_the_method(tmp_path):
     with pytest.raises(ValueError, match="hit is required"):
         r.surfaceAnisoPlanes(None)
     with pytest.raises(ValueError, match=r"taps: a contiguous torch.float32 tensor of shape \(4, 4\) is expected"):
-        r.surfaceAnisoPlanes(hit, planes=("taps",), out=dict(taps=_fake_cuda((4, 4, 2))))
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+        r.surfaceAnisoPlanes(hit, planes=("taps",), out=dict(taps=fake_cuda((4, 4, 2))))
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t aniso(SampleRenderer& sample, pt_surface_aniso_desc d) {\n"
@@ -135,12 +106,10 @@ def test_facades_have_the_method(tmp_path):
         "    return sample.surfaceAnisoPlanes(d).anisotropic + s.taps;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_rule():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
-    text = text.split("ANISOTROPIC FOOTPRINT-FILTERED ALBEDO")[1].split("GUIDED UPSAMPLING")[0]
+    text = header_section("ANISOTROPIC FOOTPRINT-FILTERED ALBEDO", "GUIDED UPSAMPLING")
     for item in ("xm = rx > ry", "a tie takes y", "r_maj2 = xm ? rx : ry; r_min2 = xm ? ry : rx; (a_s, a_t) = xm ? (ds_x, dt_x) : (ds_y, dt_y)",
                  "rho_maj = (ok ? sqrtf(r_maj2) : +infinity) * footprint_scale; rho_min = sqrtf(r_min2) * footprint_scale",
                  "if !(rho_maj > 1.0f) or !ok: N = 1", "q = rho_maj / rho_min; N = (q <= (float)max_aniso) ? (uint)ceilf(q) : max_aniso",
@@ -183,8 +152,6 @@ def _args(c, w, h):
 def grazing_case(orc):
     """the textured scene's CPU-built planes under GRAZING_CAMERA at W x H, with the isotropic reference and the anisotropic one at 8"""
     if "g" not in _CACHE:
-        from test_gpu_gbuffer import _row
-
         model = S.textured_scene()
         c = dict(model=model, sc=S.scene_arrays(model), cam=GRAZING_CAMERA)
         c["hit"] = M.cpu_planes(orc, model, (W, H), GRAZING_CAMERA, GRAZING_CAMERA)["hit"]
@@ -196,19 +163,8 @@ def grazing_case(orc):
     return _CACHE["g"]
 
 
-def ground_truth(c, w, h, q):
-    """the 16 x 16 float64 supersample of the ground's texture over the pixels q"""
-    Y, X = np.nonzero(q)
-    tri, uv = c["verts"][c["idx"][0]], c["sc"]["uv"][0].reshape(3, 2)
-    return SL.supersample64(c["sc"]["textures"][0], c["row"], w, h, X.astype(np.float64), Y.astype(np.float64), tri, uv, 16)
-
-
 def test_reference_at_max_aniso_1_is_the_isotropic_reference(orc_det):
-    from test_surface_lod_cabi import H as HL
-    from test_surface_lod_cabi import W as WL
-    from test_surface_lod_cabi import _case
-
-    for c, w, h in ((grazing_case(orc_det), W, H), (_case(orc_det), WL, HL)):
+    for c, w, h in ((grazing_case(orc_det), W, H), (SL.cpu_case(orc_det), SL.W, SL.H)):
         one = SA.surface_aniso_ref(*_args(c, w, h), max_aniso=1)
         for name in SL.PLANES:
             assert np.array_equal(one[name], c["lod"][name]), name
@@ -271,32 +227,13 @@ def test_anisotropic_albedo_of_the_reference_is_closer_to_the_pixel_average(orc_
 
 
 def test_anisotropic_albedo_under_the_non_grazing_camera_is_no_worse(orc_det):
-    from test_surface_lod_cabi import H as HL
-    from test_surface_lod_cabi import W as WL
-    from test_surface_lod_cabi import _case
-
-    c = dict(_case(orc_det))
-    c["aniso"] = SA.surface_aniso_ref(*_args(c, WL, HL), max_aniso=8)
-    q, _, _, e_iso, e_aniso = _quality(c, WL, HL, "the non-grazing camera")  # measured: see R_ANISO's comment
+    c = dict(SL.cpu_case(orc_det))
+    c["aniso"] = SA.surface_aniso_ref(*_args(c, SL.W, SL.H), max_aniso=8)
+    q, _, _, e_iso, e_aniso = _quality(c, SL.W, SL.H, "the non-grazing camera")  # measured: see R_ANISO's comment
     assert q.sum() > 2000 and e_aniso <= e_iso
 
 
 # ------------------------------------------------------------------ the hand-made inputs of the GPU test
-def check_hand_made(n_plane, lod_plane, where, max_aniso):
-    """every primitive of surface_aniso_ref.HAND_PRIMS that names an expected N (and lod) shows it on all of its pixels"""
-    for name, (_, _, _, n8, n16, lod) in SA.HAND_PRIMS.items():
-        want = {8: n8, 16: n16}[max_aniso]
-        on = where[name]
-        assert on.sum() >= 10, name
-        if want is not None:
-            assert (n_plane[on] == want).all(), (name, max_aniso, np.unique(n_plane[on]).tolist(), want)
-        if lod is not None and max_aniso == 8:
-            assert (lod_plane[on] == f32(lod)).all(), (name, np.unique(lod_plane[on]).tolist(), lod)
-    assert (n_plane[7] == 1).all() and (n_plane[6] >= 8).all()  # the horizon row: ok is false; the row above it: grazing, q between 8.x and 16.x
-    for name in ("miss", "miss_2", "stale_ntri", "stale_max"):
-        assert (n_plane[where[name]] == 0).all() and (lod_plane[where[name]] == 0).all(), name
-
-
 def test_hand_made_inputs_place_every_case_of_the_rule():
     model = SA.hand_made_model()
     sc = S.scene_arrays(model)

@@ -6,12 +6,12 @@ hand-made records are the stated words."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import surface_ref as S
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib, scenes
 
@@ -21,36 +21,21 @@ STATS_FIELDS = ("pixels", "hits", "stale", "textured", "kernel_ms")
 NEW = ("pt_copy_texcoords_device", "pt_surface_planes")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_library_exports_the_entry_points():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name in NEW:
         assert name in _lib.EXPORTS and hasattr(L, name)
-        assert name in _header().split("VERSIONING.")[1].split("*/")[0]
-        assert name in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+        assert name in header().split("VERSIONING.")[1].split("*/")[0]
+        assert name in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     assert re.search(r"int\s+pt_copy_texcoords_device\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*float\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*\)", src)
     assert re.search(r"int\s+pt_surface_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_surface_desc\s*\*\s*\w+\s*,\s*pt_surface_stats\s*\*", src)
     assert L.pt_version().startswith(b"ptamd 0.4")
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, St = _lib.SurfaceDesc, _lib.SurfaceStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in St._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(St)] + [getattr(St, n).offset for n in STATS_FIELDS]
-    assert mine == [48, 0, 8, 16, 24, 32, 40] + [40, 0, 8, 16, 24, 32]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_surface_desc)"] + [f"offsetof(pt_surface_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_surface_stats)"] +
-                     [f"offsetof(pt_surface_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.SurfaceDesc, "pt_surface_desc", DESC_FIELDS), (_lib.SurfaceStats, "pt_surface_stats", STATS_FIELDS)],
+                 [48, 0, 8, 16, 24, 32, 40] + [40, 0, 8, 16, 24, 32])
     assert _lib.SURFACE_PLANES == S.WORDS and tuple(_lib.SURFACE_PLANES) == S.PLANES == DESC_FIELDS[2:4]
 
 
@@ -64,11 +49,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.hit = hit; d.prim_texcoords = table; d.albedo = albedo; d.flags = PT_SURFACE_RESERVED;\n"
             "    return pt_surface_planes(c, &d, &s) || s.textured > s.hits;\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -92,14 +73,11 @@ def test_facades_have_the_methods(tmp_path):
     import torch  # noqa: F401
 
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     for name in ("copyTexcoordsDevice", "surfacePlanes"):
         assert callable(getattr(R.SampleRenderer, name, None))
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams, r._nv = 0, R.LaunchParams(), [5, 3]
-    r.launchParams.frame.size = (4, 4)
-    hit = _fake_cuda((4, 4, 8))
+    r = bare_renderer()
+    hit = fake_cuda((4, 4, 8))
     with pytest.raises(ValueError, match="unknown plane 'depth'"):
         r.surfacePlanes(hit, planes=("depth",))
     with pytest.raises(ValueError, match="`out` names a plane that `planes` does not"):
@@ -109,9 +87,9 @@ def test_facades_have_the_methods(tmp_path):
     with pytest.raises(ValueError, match="hit is required"):
         r.surfacePlanes(None)
     with pytest.raises(ValueError, match=r"albedo: a contiguous torch.float32 tensor of shape \(4, 4, 4\) is expected"):
-        r.surfacePlanes(hit, out=dict(albedo=_fake_cuda((4, 4, 2))))
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+        r.surfacePlanes(hit, out=dict(albedo=fake_cuda((4, 4, 2))))
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t surface(SampleRenderer& sample, pt_surface_desc d, float* table) {\n"
@@ -123,11 +101,10 @@ def test_facades_have_the_methods(tmp_path):
         "    return sample.surfacePlanes(d).textured + s.stale;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_arithmetic():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("w0 = (1.0f - u) - v", "s = ((w0 * c[0]) + (u * c[2])) + (v * c[4])", "t = ((w0 * c[1]) + (u * c[3])) + (v * c[5])",
                  "albedo[p] = (tex2D(texture[tid], s, t).xyz, 1.0f); texcoord[p] = (s, t)", "albedo[p] = (material[mesh].color, 1.0f); texcoord[p] = (0, 0)",
                  "albedo[p] = (0, 0, 0, 1)", "x = (s - floorf(s)) * (float)W; y = (t - floorf(t)) * (float)H", "xB = x - 0.5f; yB = y - 0.5f",

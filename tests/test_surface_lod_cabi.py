@@ -3,7 +3,7 @@ declared and exported, the ctypes mirrors match the compiler's layout, the heade
 arguments are refused before any device work, the layout is the hand-computed one, both facades have the methods; and the float32 NumPy
 reference (tests/surface_lod_ref.py) is held against float64 geometry that shares no expression with it.
 
-This file records two figures for tests/test_gpu_surface_lod.py, both from the reference alone, on CPU-built planes of the textured scene
+This file pins two figures (kept in tests/surface_lod_ref.py) for tests/test_gpu_surface_lod.py, both from the reference alone, on CPU-built planes of the textured scene
 (test_geometry_cabi.textured_case) — no bound comes from a kernel's output; profiles/surface_lod.md holds the same figures:
 
   FOOT_MEASURED: the largest |footprint - (texcoord[neighbour] - texcoord[p])| per component, over the pixels whose right (lower)
@@ -21,54 +21,35 @@ import subprocess
 import numpy as np
 import pytest
 
-import motion_ref as M
 import surface_lod_ref as SL
 import surface_ref as S
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
+from surface_lod_ref import FOOT_BOUND, FOOT_MEASURED, R_REF, H, W, check_footprints, cpu_case, ground_pixels, rms_against
 
 f32 = np.float32
-W, H = 131, 61
 DESC_FIELDS = ("hit", "prim_texcoords", "mips", "mips_bytes", "albedo", "texcoord", "footprint", "lod", "block_mask", "footprint_scale", "flags")
 STATS_FIELDS = ("pixels", "hits", "stale", "textured", "minified", "kernel_ms")
 NEW = ("pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes")
 
-FOOT_MEASURED = 8.35e-7  # measured 8.345e-07 on footprints up to 0.157, see test_footprints_of_the_reference_are_the_neighbour_differences
-FOOT_BOUND = 4 * FOOT_MEASURED
-R_REF = 0.797  # measured 0.79705 (rms 0.0578 filtered, 0.0725 point, 2535 pixels), see test_filtered_albedo_of_the_reference_is_closer_to_the_pixel_average
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
 
 def test_library_exports_the_entry_points():
     L = _lib.load_library()
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name in NEW:
         assert name in _lib.EXPORTS and hasattr(L, name)
-        assert name in _header().split("VERSIONING.")[1].split("*/")[0]
+        assert name in header().split("VERSIONING.")[1].split("*/")[0]
     for name in NEW[1:]:
-        assert name in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+        assert name in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     assert re.search(r"int\s+pt_texture_mips_layout\s*\(\s*const\s+pt_ctx\s*\*\s*\w+\s*,\s*uint32_t\s*\*\s*\w+\s*,\s*uint32_t\s*\*\s*\w+\s*,\s*size_t\s*\*\s*\w+\s*\)", src)
     assert re.search(r"int\s+pt_copy_texture_mips_device\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*\)", src)
     assert re.search(r"int\s+pt_surface_lod_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_surface_lod_desc\s*\*\s*\w+\s*,\s*pt_surface_lod_stats\s*\*", src)
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, St = _lib.SurfaceLodDesc, _lib.SurfaceLodStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in St._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(St)] + [getattr(St, n).offset for n in STATS_FIELDS]
-    assert mine == [80, 0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76] + [48, 0, 8, 16, 24, 32, 40]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_surface_lod_desc)"] + [f"offsetof(pt_surface_lod_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_surface_lod_stats)"] +
-                     [f"offsetof(pt_surface_lod_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.SurfaceLodDesc, "pt_surface_lod_desc", DESC_FIELDS), (_lib.SurfaceLodStats, "pt_surface_lod_stats", STATS_FIELDS)],
+                 [80, 0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76] + [48, 0, 8, 16, 24, 32, 40])
     assert _lib.SURFACE_LOD_PLANES == SL.WORDS and tuple(_lib.SURFACE_LOD_PLANES) == SL.PLANES
     # pt_surface_planes keeps its layout
     assert _lib.SURFACE_PLANES == S.WORDS and C.sizeof(_lib.SurfaceDesc) == 48 and C.sizeof(_lib.SurfaceStats) == 40
@@ -86,11 +67,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.flags = PT_SURFACE_LOD_RESERVED;\n"
             "    return pt_surface_lod_planes(c, &d, &s) || s.minified > s.textured;\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_arguments_are_refused_without_a_gpu():
@@ -160,14 +137,11 @@ def test_facades_have_the_methods(tmp_path):
     import torch  # noqa: F401
 
     from optixpathtracer_amd import renderer as R
-    from test_temporal_cabi import _fake_cuda
 
     for name in ("textureMipsLayout", "copyTextureMipsDevice", "surfaceLodPlanes"):
         assert callable(getattr(R.SampleRenderer, name, None))
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams, r._nv = 0, R.LaunchParams(), [5, 3]
-    r.launchParams.frame.size = (4, 4)
-    hit = _fake_cuda((4, 4, 8))
+    r = bare_renderer()
+    hit = fake_cuda((4, 4, 8))
     with pytest.raises(ValueError, match="unknown plane 'depth'"):
         r.surfaceLodPlanes(hit, planes=("depth",))
     with pytest.raises(ValueError, match="`out` names a plane that `planes` does not"):
@@ -177,9 +151,9 @@ def test_facades_have_the_methods(tmp_path):
     with pytest.raises(ValueError, match="hit is required"):
         r.surfaceLodPlanes(None)
     with pytest.raises(ValueError, match=r"lod: a contiguous torch.float32 tensor of shape \(4, 4\) is expected"):
-        r.surfaceLodPlanes(hit, planes=("lod",), out=dict(lod=_fake_cuda((4, 4, 2))))
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+        r.surfaceLodPlanes(hit, planes=("lod",), out=dict(lod=fake_cuda((4, 4, 2))))
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t lod(SampleRenderer& sample, pt_surface_lod_desc d, void* mips) {\n"
@@ -193,11 +167,10 @@ def test_facades_have_the_methods(tmp_path):
         "    return sample.surfaceLodPlanes(d).minified + s.stale;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_arithmetic():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("levels = 1 + floor(log2(max(w, h)))", "w_k = max(1, w >> k)", "((S(2i, 2j) + S(i1, 2j)) + (S(2i, j1) + S(i1, j1))) * 0.25f",
                  "i1 = min(2i + 1, w_k - 1); j1 = min(2j + 1, h_k - 1)", "S = (float)byte / 255.0f", "An odd dimension drops its last row or column",
                  "must in addition be 16-byte aligned", "bytes == 0 is a no-op that returns PT_OK", "one blocking copy", "may be made while frames are in flight",
@@ -216,28 +189,8 @@ def test_header_states_the_arithmetic():
 
 
 # ------------------------------------------------------------------ the reference on CPU-built planes
-_CACHE = {}
-
-
-def _case(orc):
-    """the textured scene's CPU-built planes with the reference's planes at footprint_scale 1 and 0"""
-    if "c" not in _CACHE:
-        from test_geometry_cabi import textured_case
-        from test_gpu_gbuffer import _row
-
-        c = dict(textured_case(orc))
-        c["verts"], c["idx"] = M.model_arrays(c["model"])
-        c["row"] = _row(c["cam"], W / H)
-        frame = np.ones((H, W), bool)
-        c["lod"] = SL.surface_lod_ref(c["hit"], c["sc"], c["verts"], c["idx"], [(0, 0, W, H)], [c["row"]], frame)
-        c["point"] = SL.surface_lod_ref(c["hit"], c["sc"], c["verts"], c["idx"], [(0, 0, W, H)], [c["row"]], frame, scale=0.0)
-        c["surface"] = S.surface_ref(c["hit"], c["sc"], frame)
-        _CACHE["c"] = c
-    return _CACHE["c"]
-
-
 def test_reference_at_scale_0_and_at_a_large_scale(orc_det):
-    c = _case(orc_det)
+    c = cpu_case(orc_det)
     for name in ("albedo", "texcoord"):  # footprint_scale = 0: pt_surface_planes's planes bit for bit
         assert np.array_equal(c["point"][name], c["surface"][name])
     assert not c["point"]["lod"].any() and c["point"]["minified"] == 0 and np.array_equal(c["point"]["footprint"], c["lod"]["footprint"])
@@ -254,18 +207,8 @@ def test_reference_at_scale_0_and_at_a_large_scale(orc_det):
     assert big["minified"] == big["textured"]
 
 
-def check_footprints(footprint, texcoord, prim, kind):
-    """The footprint plane against the texcoord plane alone, float64: on pixels whose right (lower) neighbour is a textured hit on the same
-    primitive, texcoord[neighbour] - texcoord[p] is the x (y) footprint.  Returns dict(err: the largest absolute difference per component;
-    nx, ny: pixels compared; size: the largest |footprint| component compared)."""
-    fx, okx, fy, oky = SL.neighbour_footprints(texcoord, prim, kind)
-    fp = np.asarray(footprint, np.float64)
-    ex, ey = np.abs(fp[..., 0:2] - fx)[okx], np.abs(fp[..., 2:4] - fy)[oky]
-    return dict(err=float(max(ex.max(), ey.max())), nx=int(okx.sum()), ny=int(oky.sum()), size=float(max(np.abs(fx[okx]).max(), np.abs(fy[oky]).max())))
-
-
 def test_footprints_of_the_reference_are_the_neighbour_differences(orc_det):
-    c = _case(orc_det)
+    c = cpu_case(orc_det)
     prim = np.ascontiguousarray(c["hit"], f32).view(np.int32)[..., 3]
     kind = c["lod"]["kind"]
     fp, tc = c["lod"]["footprint"].view(f32), c["lod"]["texcoord"].view(f32)
@@ -280,24 +223,8 @@ def test_footprints_of_the_reference_are_the_neighbour_differences(orc_det):
     assert swapped["err"] > 100 * FOOT_BOUND and halved["err"] > 100 * FOOT_BOUND
 
 
-def ground_pixels(mesh):
-    """ground (mesh 0) pixels whose 3 x 3 hit neighbourhood lies on the ground mesh"""
-    h, w = mesh.shape
-    pad = np.pad(mesh, 1, mode="constant", constant_values=-1)
-    q = np.ones((h, w), bool)
-    for dy in range(3):
-        for dx in range(3):
-            q &= pad[dy:dy + h, dx:dx + w] == 0
-    return q
-
-
-def rms_against(albedo_bits, truth, q):
-    d = albedo_bits.view(f32)[..., :3][q].astype(np.float64) - truth
-    return float(np.sqrt((d * d).mean()))
-
-
 def test_filtered_albedo_of_the_reference_is_closer_to_the_pixel_average(orc_det):
-    c = _case(orc_det)
+    c = cpu_case(orc_det)
     q = ground_pixels(c["lod"]["mesh"])
     Y, X = np.nonzero(q)
     tri = c["verts"][c["idx"][0]]

@@ -6,12 +6,12 @@ tests/test_gpu_temporal.py, rebuilt here with the CPU checker, exercise every re
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import temporal_ref as T
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -21,35 +21,20 @@ DESC_FIELDS = ("color", "motion", "hit", "position", "prev_hit", "prev_position"
 STATS_FIELDS = ("pixels", "reprojected", "kernel_ms")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_library_exports_the_entry_point():
     L = _lib.load_library()
     assert "pt_temporal_accumulate" in _lib.EXPORTS and hasattr(L, "pt_temporal_accumulate")
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert re.search(r"int\s+pt_temporal_accumulate\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_temporal_desc\s*\*\s*\w+\s*,\s*pt_temporal_stats\s*\*", src)
     assert re.search(r"PT_TEMPORAL_CLEAR_COLOR\s*=\s*1\b", src) and _lib.PT_TEMPORAL_CLEAR_COLOR == 1
     assert L.pt_version().startswith(b"ptamd 0.4")
-    assert "pt_temporal_accumulate" in _header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
-    assert "pt_temporal_accumulate" in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+    assert "pt_temporal_accumulate" in header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
+    assert "pt_temporal_accumulate" in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, S = _lib.TemporalDesc, _lib.TemporalStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in S._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(S)] + [getattr(S, n).offset for n in STATS_FIELDS]
-    assert mine == [128] + [8 * k for k in range(13)] + [104, 108, 112, 116, 120, 124] + [24, 0, 8, 16]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_temporal_desc)"] + [f"offsetof(pt_temporal_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_temporal_stats)"] +
-                     [f"offsetof(pt_temporal_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.TemporalDesc, "pt_temporal_desc", DESC_FIELDS), (_lib.TemporalStats, "pt_temporal_stats", STATS_FIELDS)],
+                 [128] + [8 * k for k in range(13)] + [104, 108, 112, 116, 120, 124] + [24, 0, 8, 16])
     assert set(_lib.TEMPORAL_PLANES) == set(DESC_FIELDS[:12]) and set(_lib.TEMPORAL_OUTPUTS) == set(T.OUTPUTS)
 
 
@@ -61,11 +46,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.color = color; d.motion = motion; d.history_out = out; d.flags = PT_TEMPORAL_CLEAR_COLOR;\n"
             "    return pt_temporal_accumulate(c, &d, &s);\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -81,22 +62,6 @@ def test_null_context_and_null_description_are_refused_without_a_gpu():
     assert body.index("null description") < body.index("ctx->width")
 
 
-def _fake_cuda(shape, dtype=None):
-    """A CPU tensor that reports CUDA device 0: enough for the checks that run before the library is called."""
-    import torch
-
-    class Fake(torch.Tensor):
-        @property
-        def is_cuda(self):
-            return True
-
-        @property
-        def device(self):
-            return torch.device("cuda", 0)
-
-    return torch.zeros(shape, dtype=dtype or torch.float32).as_subclass(Fake)
-
-
 def test_python_facade_checks_its_arguments():
     import torch
 
@@ -107,29 +72,27 @@ def test_python_facade_checks_its_arguments():
         R._check_temporal_tensor("color", np.zeros((4, 4, 4), f32), 0, {torch.float32: (4, 4, 4)})
     with pytest.raises(ValueError, match="motion: the tensor is on cpu"):
         R._check_temporal_tensor("motion", torch.zeros((4, 4, 2)), 0, {torch.float32: (4, 4, 2)})
-    R._check_temporal_tensor("motion", _fake_cuda((4, 4, 2)), 0, {torch.float32: (4, 4, 2)})
+    R._check_temporal_tensor("motion", fake_cuda((4, 4, 2)), 0, {torch.float32: (4, 4, 2)})
     with pytest.raises(ValueError, match="the context on GPU 1"):
-        R._check_temporal_tensor("motion", _fake_cuda((4, 4, 2)), 1, {torch.float32: (4, 4, 2)})
+        R._check_temporal_tensor("motion", fake_cuda((4, 4, 2)), 1, {torch.float32: (4, 4, 2)})
     with pytest.raises(ValueError, match="frame_rgba8: a contiguous torch.int32 tensor of shape .4, 4. or torch.uint8 tensor of shape .4, 4, 4. is expected"):
-        R._check_temporal_tensor("frame_rgba8", _fake_cuda((4, 4)), 0, {torch.int32: (4, 4), torch.uint8: (4, 4, 4)})
+        R._check_temporal_tensor("frame_rgba8", fake_cuda((4, 4)), 0, {torch.int32: (4, 4), torch.uint8: (4, 4, 4)})
     with pytest.raises(ValueError, match="hit: a contiguous"):
-        R._check_temporal_tensor("hit", _fake_cuda((8, 4, 4)).permute(2, 1, 0), 0, {torch.float32: (4, 4, 8)})
+        R._check_temporal_tensor("hit", fake_cuda((8, 4, 4)).permute(2, 1, 0), 0, {torch.float32: (4, 4, 8)})
     # the method itself, on an object without a context: what it refuses, it refuses before the library is called
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams = 0, R.LaunchParams()
-    r.launchParams.frame.size = (4, 4)
+    r = bare_renderer()
     with pytest.raises(ValueError, match="motion is required"):
         r.temporalAccumulate(1, None, 1, 1, 1, 1, 1, 1, history_out=1, length_out=1)
     with pytest.raises(ValueError, match=r"length_in: a contiguous torch.float32 tensor of shape \(4, 4\) is expected"):
-        r.temporalAccumulate(1, 1, 1, 1, 1, 1, 1, _fake_cuda((4, 4, 1)), history_out=1, length_out=1)
+        r.temporalAccumulate(1, 1, 1, 1, 1, 1, 1, fake_cuda((4, 4, 1)), history_out=1, length_out=1)
     with pytest.raises(ValueError, match="the mask needs"):
         r.blockGrid = lambda: (1, 1)
         r.temporalAccumulate(1, 1, 1, 1, 1, 1, 1, 1, history_out=1, length_out=1, mask=np.ones((2, 2)))
 
 
 def test_cxx_facade_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t reproject(SampleRenderer& sample, pt_temporal_desc d) {\n"
@@ -139,11 +102,10 @@ def test_cxx_facade_compiles(tmp_path):
         "    return sample.temporalAccumulate(d).reprojected + s.pixels;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("c = color[p].xyz * color_scale", "px >= -1 && px <= wr && py >= -1 && py <= hr", "flx = floorf(px), ix = (int)flx, fx = px - flx",
                  "length_in[q] >= 1", "exponent-bit test", "dot3(ng_p, ng_q) >= normal_cos",
                  "fabsf(dot3(ng_p, prev_position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t", "Wsum = ((w00 + w10) + w01) + w11",

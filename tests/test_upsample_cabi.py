@@ -8,13 +8,13 @@ interpolation is."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import temporal_ref as T
 import upsample_ref as U
+from cabi_kit import bare_renderer, check_layout, compile_c99_and_cxx17, compile_facade, fake_cuda, header, header_text
 from conftest import ROOT
 from optixpathtracer_amd import _lib
 
@@ -25,37 +25,22 @@ STATS_FIELDS = ("pixels", "hits", "full", "rescued", "orphans", "kernel_ms")
 SCALES = (2, 3, 4)
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
-
-
 def test_library_exports_the_entry_point():
     L = _lib.load_library()
     assert "pt_upsample_planes" in _lib.EXPORTS and hasattr(L, "pt_upsample_planes")
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     assert re.search(r"int\s+pt_upsample_planes\s*\(\s*pt_ctx\s*\*\s*\w+\s*,\s*const\s+pt_upsample_desc\s*\*\s*\w+\s*,\s*pt_upsample_stats\s*\*", src)
     assert re.search(r"PT_UPSAMPLE_RESERVED\s*=\s*0\b", src)
     assert L.pt_version().startswith(b"ptamd 0.4")
-    assert "pt_upsample_planes" in _header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
-    assert "pt_upsample_planes" in _header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
+    assert "pt_upsample_planes" in header().split("VERSIONING.")[1].split("*/")[0]  # the note names it among the entry points added at 0.4
+    assert "pt_upsample_planes" in header().split("STREAM CONTRACT.")[1].split("VERSIONING.")[0]
     lib = open(os.path.join(ROOT, "optixpathtracer_amd", "csrc", "pt_lib.hip")).read()
     assert '#include "pt_upsample.hip"' in lib
 
 
 def test_struct_layouts_match_the_compiler(tmp_path):
-    D, S = _lib.UpsampleDesc, _lib.UpsampleStats
-    assert [n for n, _ in D._fields_] == list(DESC_FIELDS) and [n for n, _ in S._fields_] == list(STATS_FIELDS)
-    mine = [C.sizeof(D)] + [getattr(D, n).offset for n in DESC_FIELDS] + [C.sizeof(S)] + [getattr(S, n).offset for n in STATS_FIELDS]
-    assert mine == [88] + [8 * k for k in range(8)] + [64, 68, 72, 76, 80, 84] + [48, 0, 8, 16, 24, 32, 40]
-    fmt = " ".join(["%zu"] * len(mine))
-    args = ", ".join(["sizeof(pt_upsample_desc)"] + [f"offsetof(pt_upsample_desc, {n})" for n in DESC_FIELDS] + ["sizeof(pt_upsample_stats)"] +
-                     [f"offsetof(pt_upsample_stats, {n})" for n in STATS_FIELDS])
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\nint main(void) {{ printf("{fmt}\\n", {args}); return 0; }}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == mine
+    check_layout(tmp_path, [(_lib.UpsampleDesc, "pt_upsample_desc", DESC_FIELDS), (_lib.UpsampleStats, "pt_upsample_stats", STATS_FIELDS)],
+                 [88] + [8 * k for k in range(8)] + [64, 68, 72, 76, 80, 84] + [48, 0, 8, 16, 24, 32, 40])
     assert set(_lib.UPSAMPLE_PLANES) == set(DESC_FIELDS[:7]) and _lib.UPSAMPLE_OUTPUTS == ("out", "weight_out")
 
 
@@ -67,11 +52,7 @@ def test_header_compiles_as_c99_and_cxx17(tmp_path):
             "    d.lo_color = lo; d.hit = hit; d.out = out; d.flags = PT_UPSAMPLE_RESERVED;\n"
             "    return pt_upsample_planes(c, &d, &s);\n"
             "}\n")
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_and_null_description_are_refused_without_a_gpu():
@@ -89,33 +70,15 @@ def test_null_context_and_null_description_are_refused_without_a_gpu():
         assert body.index(text) < body.index("run.open"), text
 
 
-def _fake_cuda(shape, dtype=None):
-    """A CPU tensor that reports CUDA device 0: enough for the checks that run before the library is called."""
-    import torch
-
-    class Fake(torch.Tensor):
-        @property
-        def is_cuda(self):
-            return True
-
-        @property
-        def device(self):
-            return torch.device("cuda", 0)
-
-    return torch.zeros(shape, dtype=dtype or torch.float32).as_subclass(Fake)
-
-
 def test_python_facade_checks_its_arguments():
     import torch
 
     from optixpathtracer_amd import renderer as R
 
     assert callable(getattr(R.SampleRenderer, "upsamplePlanes", None))
-    r = object.__new__(R.SampleRenderer)
-    r._device, r.launchParams = 0, R.LaunchParams()
-    r.launchParams.frame.size = (12, 8)
-    ok = dict(lo_color=_fake_cuda((4, 6, 4)), lo_hit=_fake_cuda((4, 6, 8)), lo_position=_fake_cuda((4, 6, 4)), hit=_fake_cuda((8, 12, 8)),
-              position=_fake_cuda((8, 12, 4)), scale=2, out=1)
+    r = bare_renderer(size=(12, 8))
+    ok = dict(lo_color=fake_cuda((4, 6, 4)), lo_hit=fake_cuda((4, 6, 8)), lo_position=fake_cuda((4, 6, 4)), hit=fake_cuda((8, 12, 8)),
+              position=fake_cuda((8, 12, 4)), scale=2, out=1)
     for bad in (1, 5, 0):
         with pytest.raises(ValueError, match=r"upsamplePlanes: scale must be in \[2,4\]"):
             r.upsamplePlanes(**dict(ok, scale=bad))
@@ -129,21 +92,21 @@ def test_python_facade_checks_its_arguments():
         r.upsamplePlanes(**dict(ok, position=torch.zeros((8, 12, 4))))
     # the low-res planes are checked against the low-res shape, the others against the frame's
     with pytest.raises(ValueError, match=r"upsamplePlanes: lo_color: a contiguous torch.float32 tensor of shape \(4, 6, 4\) is expected"):
-        r.upsamplePlanes(**dict(ok, lo_color=_fake_cuda((8, 12, 4))))
+        r.upsamplePlanes(**dict(ok, lo_color=fake_cuda((8, 12, 4))))
     with pytest.raises(ValueError, match=r"upsamplePlanes: lo_color: a contiguous torch.float32 tensor of shape \(2, 3, 4\) is expected"):
         r.upsamplePlanes(**dict(ok, scale=4))
     with pytest.raises(ValueError, match=r"upsamplePlanes: hit: a contiguous torch.float32 tensor of shape \(8, 12, 8\) is expected"):
-        r.upsamplePlanes(**dict(ok, hit=_fake_cuda((4, 6, 8))))
+        r.upsamplePlanes(**dict(ok, hit=fake_cuda((4, 6, 8))))
     with pytest.raises(ValueError, match=r"upsamplePlanes: weight_out: a contiguous torch.float32 tensor of shape \(8, 12\) is expected"):
-        r.upsamplePlanes(**ok, weight_out=_fake_cuda((8, 12, 1)))
+        r.upsamplePlanes(**ok, weight_out=fake_cuda((8, 12, 1)))
     with pytest.raises(ValueError, match="the mask needs"):
         r.blockGrid = lambda: (1, 2)
         r.upsamplePlanes(**ok, mask=np.ones((2, 2)))
 
 
 def test_cxx_facade_compiles(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "uint64_t upsample(SampleRenderer& sample, pt_upsample_desc d) {\n"
@@ -153,11 +116,10 @@ def test_cxx_facade_compiles(tmp_path):
         "    return sample.upsamplePlanes(d).orphans + s.rescued;\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     for item in ("a = X - x0; r = a % s; cx = x0/s + a/s", "t = (float)(2*r + 1 - s) / (float)(2*s)", "If t < 0: i = cx - 1, fx = t + 1.0f. Else i = cx, fx = t",
                  "fabsf(dot3(ng_p, lo_position[q].xyz - position[p].xyz)) <= plane_eps * hit[p].t", "lo_hit[q].mesh == hit[p].mesh",
                  "hit[p].prim < 0 and lo_hit[q].prim < 0", "There is no block test on q", "in the order (0,0), (1,0), (0,1), (1,1)",

@@ -2,25 +2,19 @@
 layout, the header still compiles as C99 and as C++17, a null context is refused before any device work, both facades have the new methods —
 and the header carries the contract tests/test_gpu_views.py checks on the GPU (what a view pixel holds, the refusal list)."""
 import ctypes as C
-import os
 import re
-import subprocess
 
-from conftest import ROOT
+from cabi_kit import check_layout, compile_c99_and_cxx17, compile_facade, header, header_text
 from optixpathtracer_amd import _lib
 
 NAMES = ("pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "pt_amd.h")).read()
 
 
 def test_library_exports_the_entry_points():
     L = _lib.load_library()
     for name in NAMES:
         assert name in _lib.EXPORTS and hasattr(L, name), name
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     for name in NAMES:
         first = "pt_multi" if name.startswith("pt_multi") else "pt_ctx"
         assert re.search(r"int\s+%s\s*\(\s*(const\s+)?%s\s*\*" % (name, first), src), name
@@ -29,28 +23,12 @@ def test_library_exports_the_entry_points():
 
 
 def test_view_struct_layout_matches_the_compiler(tmp_path):
-    V = _lib.View
-    assert C.sizeof(V) == 64
-    assert [getattr(V, n).offset for n in ("x", "y", "width", "height", "eye", "U", "V", "W")] == [0, 4, 8, 12, 16, 28, 40, 52]
-    src = tmp_path / "probe.c"
-    src.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "pt_amd.h"\n'
-        'int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(pt_view), offsetof(pt_view, x), offsetof(pt_view, y), '
-        "offsetof(pt_view, width), offsetof(pt_view, height), offsetof(pt_view, eye), offsetof(pt_view, U), offsetof(pt_view, V), offsetof(pt_view, W)); return 0; }\n"
-    )
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [64, 0, 4, 8, 12, 16, 28, 40, 52]
+    check_layout(tmp_path, [(_lib.View, "pt_view", ("x", "y", "width", "height", "eye", "U", "V", "W"))], [64, 0, 4, 8, 12, 16, 28, 40, 52])
 
 
 def test_header_compiles_as_c99_and_cxx17(tmp_path):
     body = '#include "pt_amd.h"\nint use(pt_ctx* c) { pt_view v = {0, 0, 8, 8, {0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}}; return pt_set_views(c, &v, 1); }\n'
-    (tmp_path / "h.c").write_text(body)
-    (tmp_path / "h.cpp").write_text(body)
-    inc = os.path.join(ROOT, "include")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.c")], check=True)
-    subprocess.run(["g++", "-std=c++17", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", inc, str(tmp_path / "h.cpp")], check=True)
+    compile_c99_and_cxx17(tmp_path, body)
 
 
 def test_null_context_is_refused_without_a_gpu():
@@ -85,8 +63,8 @@ def test_python_facades_have_the_methods():
 
 
 def test_cxx_facades_compile(tmp_path):
-    src = tmp_path / "facade.cpp"
-    src.write_text(
+    compile_facade(
+        tmp_path,
         '#include "optixpathtracer_amd/csrc/SampleRenderer.h"\n'
         "using namespace ptamd;\n"
         "void stereo(SampleRenderer& sample, MultiSampleRenderer& multi, const Camera& left, const Camera& right) {\n"
@@ -99,11 +77,10 @@ def test_cxx_facades_compile(tmp_path):
         "    multi.setViews(views);\n"
         "}\n"
     )
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", ROOT, "-I", os.path.join(ROOT, "include"), str(src)], check=True)
 
 
 def test_header_states_the_contract():
-    text = " ".join(re.sub(r"^\s*\*", " ", _header(), flags=re.M).split())
+    text = header_text()
     assert "A pixel in no view is not touched in any buffer by any render call" in text
     for item in ("a null context", "null `views` with n > 0", "no pt_resize yet", "n > PT_MAX_VIEWS", "x or y negative or not a multiple of 8",
                  "width or height < 1", "a rectangle leaving the frame", "two rectangles sharing a pixel"):

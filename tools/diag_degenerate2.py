@@ -1,7 +1,7 @@
 """Why does a ray miss in the tiny_in_huge / collinear cases?  Walks the exported 8-wide tree towards the expected primitive in float64."""
 import sys, numpy as np
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
-import test_gpu_parity as T
+import parity_kit as T
 from optixpathtracer_amd import scenes
 from optixpathtracer_amd.renderer import SampleRenderer
 from oracle import orc
