@@ -83,6 +83,82 @@ static void enqueue_worker_stop(EnqueueWorker* w) {
     if (w->th.joinable()) w->th.join();
 }
 
+// The one owner of device memory, pinned host memory and events in this library: whatever it handed out is freed, in the order it was
+// handed out, by release(), by the destructor, or when another owner is moved in.  A moved-from owner is empty.  alloc is the only caller
+// of hipMalloc in this translation unit, which is what makes PT_ALLOC_FAIL_AT (test hook) reach every allocation: with
+// PT_ALLOC_FAIL_AT=k the k-th alloc since the variable's value last changed returns hipErrorOutOfMemory without calling hipMalloc.  Host
+// only: nothing fails on the device.  Unset, it costs one getenv per allocation.
+struct DevOwner {
+    struct Item { void* p; int kind; }; // 0 device memory, 1 pinned host memory, 2 event
+    std::vector<Item> items;
+    DevOwner() = default;
+    DevOwner(DevOwner&& o) noexcept { items.swap(o.items); } // (no copies: the move members delete them)
+    DevOwner& operator=(DevOwner&& o) noexcept {
+        if (this != &o) {
+            release();
+            items.swap(o.items);
+        }
+        return *this;
+    }
+    ~DevOwner() { release(); }
+    static bool fail_injected() {
+        static std::atomic<bool> armed{false}; // the variable was set at the last look
+        static std::mutex mu;
+        static std::string seen;
+        static long count = 0;
+        const char* e = getenv("PT_ALLOC_FAIL_AT");
+        if (!e && !armed.load(std::memory_order_relaxed)) return false;
+        std::lock_guard<std::mutex> lk(mu);
+        if (seen != (e ? e : "")) count = 0;
+        seen = e ? e : "";
+        armed.store(e != nullptr, std::memory_order_relaxed);
+        return e && ++count == atol(e);
+    }
+    template <typename T>
+    hipError_t alloc(T** p, size_t n) {
+        if (fail_injected()) return hipErrorOutOfMemory;
+        hipError_t e = hipMalloc((void**)p, sizeof(T) * (n ? n : 1));
+        if (e == hipSuccess) items.push_back({(void*)*p, 0});
+        return e;
+    }
+    template <typename T>
+    hipError_t pinned(T** p, size_t n) {
+        hipError_t e = hipHostMalloc((void**)p, sizeof(T) * n);
+        if (e == hipSuccess) items.push_back({(void*)*p, 1});
+        return e;
+    }
+    hipError_t event(hipEvent_t* ev, unsigned flags = 0) {
+        hipError_t e = flags ? hipEventCreateWithFlags(ev, flags) : hipEventCreate(ev);
+        if (e == hipSuccess) items.push_back({(void*)*ev, 2});
+        return e;
+    }
+    static void free_item(const Item& it) {
+        if (it.kind == 0) hipFree(it.p);
+        else if (it.kind == 1) hipHostFree(it.p);
+        else hipEventDestroy((hipEvent_t)it.p);
+    }
+    void release() {
+        for (const Item& it : items) free_item(it);
+        items.clear();
+    }
+    // frees one allocation ahead of the others (an array that is replaced while its group lives) and nulls the pointer
+    template <typename T>
+    void drop(T*& p) {
+        for (size_t i = 0; i < items.size(); ++i)
+            if (items[i].p == (void*)p) {
+                free_item(items[i]);
+                items.erase(items.begin() + (ptrdiff_t)i);
+                break;
+            }
+        p = nullptr;
+    }
+    // takes over what another owner holds (a staged update that is committed)
+    void adopt(DevOwner&& o) {
+        items.insert(items.end(), o.items.begin(), o.items.end());
+        o.items.clear();
+    }
+};
+
 struct pt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -95,41 +171,56 @@ struct pt_ctx {
     uint32_t ntri = 0, nmesh = 0;
     size_t nvert = 0;
     std::vector<uint32_t> mesh_vbase, mesh_nv; // per mesh: first vertex in the global vertex space, vertex count (pt_update_meshes)
-    float* d_verts = nullptr;
-    float* d_rest = nullptr;         // rest positions (pt_transform_meshes), allocated by the first transform: until then d_verts stands for them
-    uint8_t* d_stage = nullptr;      // k_stage_vertices: the non-finite report word, then the call's segment table (grown on demand)
-    size_t stage_cap = 0;
-    uint32_t* h_stage_bad = nullptr; // pinned: the report word, read after the synchronisation update_stage makes anyway
-    uint32_t* d_idx = nullptr;
-    uint32_t* d_tri_mesh = nullptr;
-    pt_material* d_mats = nullptr;
+    // Device memory is owned by lifetime: one group per lifetime, each a plain struct of a DevOwner and its typed pointers whose
+    // default-constructed value means "not there"; freeing a group is `grp = Group{}`.  An entry point that replaces a group first resets it
+    // AND the fields the rest of the library reads as "this exists" (width / height, owned / padded, pr.dev, vw.n, ad.on, set_cap /
+    // set_pix_cap, blk.d_spans, q.cap), then allocates in place, and publishes those fields last: a failure in between leaves what a fresh
+    // context has, never a pointer to freed memory.
+    struct Scene {
+        DevOwner mem;
+        float* d_verts = nullptr;
+        float* d_rest = nullptr;         // rest positions (pt_transform_meshes), allocated by the first transform: until then d_verts stands for them
+        uint8_t* d_stage = nullptr;      // k_stage_vertices: the non-finite report word, then the call's segment table (grown on demand)
+        size_t stage_cap = 0;
+        uint32_t* h_stage_bad = nullptr; // pinned: the report word, read after the synchronisation update_stage makes anyway
+        uint32_t* d_idx = nullptr;
+        uint32_t* d_tri_mesh = nullptr;
+        pt_material* d_mats = nullptr;
+        // textures
+        int32_t* d_mesh_tex = nullptr;
+        TexTri* d_textris = nullptr;
+        DevTex* d_textures = nullptr;
+        std::vector<uint32_t*> d_tex_pixels;
+        DevTex tex0{};
+        float4* d_tri_nrm = nullptr; // per leaf triangle of the traversal structure: (geometric normal, mesh) for k_shade
+    } sc;
     bool has_catcher = false;
-    // textures
-    int32_t* d_mesh_tex = nullptr;
-    PrimUV* d_uvs = nullptr;   // per primitive, only until the leaf-ordered records are emitted
-    TexTri* d_textris = nullptr;
-    DevTex* d_textures = nullptr;
-    std::vector<uint32_t*> d_tex_pixels;
-    DevTex tex0{};
     PtBvh bvh;
     double bvh_build_ms = 0;
     double create_ms = 0; // host time of the whole pt_create after the scene was flattened: uploads, code-object loads of a first use, the build, the stream probes
     // probe
-    DevProbe probe{};
-    float4* d_probe_data = nullptr;
-    float *d_pdfX = nullptr, *d_cdfX = nullptr, *d_pdfY = nullptr, *d_cdfY = nullptr, *d_c64Y = nullptr, *d_c8Y = nullptr;
-    float4* d_tri_nrm = nullptr; // per leaf triangle of the traversal structure: (geometric normal, mesh) for k_shade
-    ProbeLine* d_lines = nullptr; // ProbeSample's column tables: six columns' cdf + (rgb, pdfX) per 128-byte line
-    uint16_t* d_guide = nullptr;
+    struct Probe {
+        DevOwner mem;
+        float4* d_probe_data = nullptr;
+        float *d_pdfX = nullptr, *d_cdfX = nullptr, *d_pdfY = nullptr, *d_cdfY = nullptr, *d_c64Y = nullptr, *d_c8Y = nullptr;
+        ProbeLine* d_lines = nullptr; // ProbeSample's column tables: six columns' cdf + (rgb, pdfX) per 128-byte line
+        uint16_t* d_guide = nullptr;
+        DevProbe dev{}; // what every k_shade launch receives by value; dev.data != null: a probe is set (published last, finish_probe)
+    } pr;
     // frame
     int width = 0, height = 0;
-    float4 *accum = nullptr, *color = nullptr, *normal = nullptr, *albedo = nullptr;
-    uint32_t* frame = nullptr;
-    float4 *denoised = nullptr, *denoise_tmp = nullptr; // allocated by the first pt_denoise at the current size
+    struct Frame {
+        DevOwner mem;
+        float4 *accum = nullptr, *color = nullptr, *normal = nullptr, *albedo = nullptr;
+        uint32_t* frame = nullptr;
+        float4 *denoised = nullptr, *denoise_tmp = nullptr; // allocated by the first pt_denoise at the current size
+        uint32_t* d_pixels = nullptr;     // this rank's pixel list
+        uint32_t* d_all_pixels = nullptr; // world * padded, rank-major (0xffffffff = pad)
+        void* display[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // the display hand-off's copies, below
+    } fb;
     // Display hand-off that overlaps the next frame (pt_pack_async / pt_unpack_display): the second set of frame buffers.  A frame's
     // strips are packed behind its last kernel on the context's stream, later frames' resolves wait for that pack before they
     // overwrite the frame buffers, and the gathered strips of all ranks are scattered into `display[which]`, which no render writes.
-    void* display[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_packed[2] = {nullptr, nullptr}; // behind the pack of hand-off slot 0 / 1
     hipEvent_t ev_displayed = nullptr;            // behind the newest pt_unpack_display
     hipEvent_t ev_pack_guard = nullptr;           // the newest pack still to be waited for by later resolves (null: none)
@@ -137,11 +228,10 @@ struct pt_ctx {
     // partition
     int rank = 0, world = 1, tile_w = 64, tile_h = 16;
     uint32_t owned = 0, padded = 0;
-    uint32_t* d_pixels = nullptr;     // this rank's pixel list
-    uint32_t* d_all_pixels = nullptr; // world * padded, rank-major (0xffffffff = pad)
     // Block masks (pt_render_mask, pt_render_adaptive): where each 8x8 block's pixels sit in d_pixels, and what the compaction kernels work
     // on.  Built by the first call that needs them at the current size and partition, freed with the frame buffers.
     struct Blocks {
+        DevOwner mem;
         uint32_t nbx = 0, nby = 0, nblk = 0, owned_blocks = 0;
         BlockSpan* d_spans = nullptr;  // [nblk] (size 0: another rank's block)
         uint8_t* d_flags = nullptr;    // [nblk] the caller's mask of the pt_render_mask call under way
@@ -156,6 +246,7 @@ struct pt_ctx {
     // Viewports (pt_set_views): n > 0 while views are set.  A frame then runs over d_pixels / owned below instead of the rank's whole list: the
     // view pixels of the blocks the rank owns, in the order of build_pixel_lists.  Freed with the frame buffers.
     struct Views {
+        DevOwner mem;
         uint32_t n = 0;
         std::vector<pt_view> host;    // what pt_get_views returns (the device camera feed copies its values back)
         std::vector<uint16_t> vblock; // [nbx * nby] the view of each 8x8 block, 0xffff: none
@@ -164,11 +255,12 @@ struct pt_ctx {
         uint32_t* d_pixels = nullptr;
         uint32_t owned = 0;
     } vw;
-    const uint32_t* frame_pixels() const { return vw.n ? vw.d_pixels : d_pixels; } // the pixel list of a whole frame
+    const uint32_t* frame_pixels() const { return vw.n ? vw.d_pixels : fb.d_pixels; } // the pixel list of a whole frame
     uint32_t frame_owned() const { return vw.n ? vw.owned : owned; }
     // pt_adaptive_begin .. pt_adaptive_end.  `list` / `count` are what the NEXT pt_render_adaptive renders: the compaction that follows a
     // call's decision is enqueued behind that call's frame and its count comes back with the frame's own final synchronisation.
     struct Adaptive {
+        DevOwner mem;
         bool on = false;
         pt_adaptive_params prm{};
         float4* d_moments = nullptr; // [width * height] {n, s1, s2, 0}
@@ -181,6 +273,7 @@ struct pt_ctx {
     // path state: NSETS independent batch sets; pixel chunks of one frame are dealt round-robin to the sets and each
     // set runs on its own pair of streams, so one chunk's kernel tails overlap with the other chunks' bulk work
     struct BatchSet {
+        DevOwner mem;
         hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr;
         PathState st{}; // the arrays indexed by path slot; the stream pointers are filled per launch (stream_view)
         // what a path carries from bounce to bounce, in queue order (pt_kernels.h PathState): X[0] travels with queueA, X[1] with queueB
@@ -214,12 +307,17 @@ struct pt_ctx {
     bool cap_catcher = false, cap_async = false;
     int nq = 0;
     // [frame slot 0..2][batch set 0..15][4]: [0] radiance rays, [1] shadow rays, [2] low word = traversal fault bits (pt_bvh8.h push), [3] shaded hits
-    unsigned long long* d_totals = nullptr;
-    unsigned long long* h_totals = nullptr; // pinned host copy, same shape: filled by an asynchronous copy behind each frame (a blocking hipMemcpy would wait for the NEXT frame too)
+    struct Totals {
+        DevOwner mem;
+        unsigned long long* d_totals = nullptr;
+        unsigned long long* h_totals = nullptr; // pinned host copy, same shape: filled by an asynchronous copy behind each frame (a blocking hipMemcpy would wait for the NEXT frame too)
+    } tot;
+    DevOwner misc; // what lives as long as the context and stands alone: ovf, dbg, the hand-off events, the frame slots' event pools
     uint32_t* ovf = nullptr; // spill stacks for pt_trace queries
     // pt_trace_device: the query state.  Allocated by the first query, grown when a query has more rays than any before it, freed by
     // pt_destroy: a query of the same or a smaller size allocates nothing (pt_query_stats.state_bytes).
     struct Query {
+        DevOwner mem, rays;                      // block, h_counters and the events; the four arrays that grow with the largest query
         float4 *rayO = nullptr, *rayD = nullptr; // the rays as staged by k_stage_rays: what the traversal reads
         float2* hit = nullptr;                   // its (t, leaf) records
         unsigned long long* mark = nullptr;      // [ceil(cap / 64)] one bit per ray: invalid, staged as the neutral ray
@@ -326,10 +424,6 @@ static int fail(pt_ctx* ctx, int code, const char* msg) {
     return code;
 }
 
-template <typename T>
-static hipError_t dalloc(T** p, size_t n) {
-    return hipMalloc((void**)p, sizeof(T) * (n ? n : 1));
-}
 // The library's streams are created hipStreamNonBlocking: they neither wait for nor hold up the null stream — an application (or torch)
 // working on the default stream next to the renderer would otherwise serialise with every frame in flight, and an exchange of frame
 // k-1 could not overlap the rendering of frame k.  So nothing here may rely on the null stream's implicit ordering: clears go through
@@ -339,32 +433,6 @@ static hipError_t dclear(hipStream_t stream, void* p, size_t bytes) {
     return e == hipSuccess ? hipStreamSynchronize(stream) : e;
 }
 static hipError_t stream_create(hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
-template <typename T>
-static void dfree(T*& p) {
-    if (p) hipFree((void*)p);
-    p = nullptr;
-}
-
-// frees temporaries of the query entry points on every exit path
-struct DevScope {
-    std::vector<void*> ptrs;
-    std::vector<hipEvent_t> events;
-    template <typename T>
-    hipError_t alloc(T** p, size_t n) {
-        hipError_t e = dalloc(p, n);
-        if (e == hipSuccess) ptrs.push_back((void*)*p);
-        return e;
-    }
-    hipError_t event(hipEvent_t* ev) {
-        hipError_t e = hipEventCreate(ev);
-        if (e == hipSuccess) events.push_back(*ev);
-        return e;
-    }
-    ~DevScope() {
-        for (void* p : ptrs) hipFree(p);
-        for (hipEvent_t e : events) hipEventDestroy(e);
-    }
-};
 
 extern "C" const char* pt_version(void) { return "ptamd 0.4 (gfx950 wavefront path tracer)"; }
 
@@ -385,7 +453,7 @@ static size_t counter_words(int nq) {
 static size_t ovf_words(const pt_ctx* ctx);
 static const int PT_MAX_SETS = 16;
 static const int PT_MAX_FRAMES = 3;
-static unsigned long long* totals_of(pt_ctx* ctx, int slot, int set) { return ctx->d_totals + ((size_t)slot * PT_MAX_SETS + set) * 4; }
+static unsigned long long* totals_of(pt_ctx* ctx, int slot, int set) { return ctx->tot.d_totals + ((size_t)slot * PT_MAX_SETS + set) * 4; }
 static uint32_t* fault_word(pt_ctx* ctx) { return reinterpret_cast<uint32_t*>(totals_of(ctx, 0, 0) + 2); } // pt_trace queries
 static uint32_t* fault_word(pt_ctx::BatchSet& bs) { return reinterpret_cast<uint32_t*>(bs.totals + 2); }
 static int drain(pt_ctx* ctx);
@@ -494,7 +562,8 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
             return bail(PT_ERR_HIP);                                        \
         }                                                                   \
     } while (0)
-    DevScope tmp;
+    DevOwner tmp, uv_mem; // uv_mem: the per-primitive texcoords, only until the leaf-ordered records are emitted
+    PrimUV* d_uvs = nullptr;
     CKC(hipSetDevice(device));
     if (const char* e = getenv("PT_STREAM_SHIFT")) { // test hook: streams created (and kept) ahead of the context's own shift the hardware-queue phase
         static std::vector<hipStream_t> ahead;
@@ -523,24 +592,24 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
         ctx->mesh_vbase.push_back(vb);
         ctx->mesh_nv.push_back(scene->meshes[m].num_vertices);
     }
-    CKC(dalloc(&ctx->d_verts, 3 * nv));
-    CKC(dalloc(&ctx->d_idx, 3 * nt));
-    CKC(dalloc(&ctx->d_tri_mesh, nt));
-    CKC(dalloc(&ctx->d_mats, fs.mats.size()));
-    CKC(hipMemcpy(ctx->d_verts, fs.verts.data(), sizeof(float) * 3 * nv, hipMemcpyHostToDevice));
-    CKC(hipMemcpy(ctx->d_idx, fs.idx.data(), sizeof(uint32_t) * 3 * nt, hipMemcpyHostToDevice));
-    CKC(hipMemcpy(ctx->d_tri_mesh, fs.tri_mesh.data(), sizeof(uint32_t) * nt, hipMemcpyHostToDevice));
-    CKC(hipMemcpy(ctx->d_mats, fs.mats.data(), sizeof(pt_material) * fs.mats.size(), hipMemcpyHostToDevice));
+    CKC(ctx->sc.mem.alloc(&ctx->sc.d_verts, 3 * nv));
+    CKC(ctx->sc.mem.alloc(&ctx->sc.d_idx, 3 * nt));
+    CKC(ctx->sc.mem.alloc(&ctx->sc.d_tri_mesh, nt));
+    CKC(ctx->sc.mem.alloc(&ctx->sc.d_mats, fs.mats.size()));
+    CKC(hipMemcpy(ctx->sc.d_verts, fs.verts.data(), sizeof(float) * 3 * nv, hipMemcpyHostToDevice));
+    CKC(hipMemcpy(ctx->sc.d_idx, fs.idx.data(), sizeof(uint32_t) * 3 * nt, hipMemcpyHostToDevice));
+    CKC(hipMemcpy(ctx->sc.d_tri_mesh, fs.tri_mesh.data(), sizeof(uint32_t) * nt, hipMemcpyHostToDevice));
+    CKC(hipMemcpy(ctx->sc.d_mats, fs.mats.data(), sizeof(pt_material) * fs.mats.size(), hipMemcpyHostToDevice));
     {   // textures (createTextures, SimplePathtracer.cpp:603-654) and per-primitive texcoords (buildSBT :430-447)
         if (fs.any_tex) {
             float* d_tc = nullptr;
             CKC(tmp.alloc(&d_tc, 2 * nv));
             CKC(hipMemcpy(d_tc, fs.tc.data(), sizeof(float) * 2 * nv, hipMemcpyHostToDevice));
-            CKC(dalloc(&ctx->d_uvs, nt));
-            hipLaunchKernelGGL(k_emit_uvs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, d_tc, ctx->d_idx, (uint32_t)nt, ctx->d_uvs);
+            CKC(uv_mem.alloc(&d_uvs, nt));
+            hipLaunchKernelGGL(k_emit_uvs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, d_tc, ctx->sc.d_idx, (uint32_t)nt, d_uvs);
             CKC(hipStreamSynchronize(ctx->stream));
-            CKC(dalloc(&ctx->d_mesh_tex, fs.mesh_tex.size()));
-            CKC(hipMemcpy(ctx->d_mesh_tex, fs.mesh_tex.data(), sizeof(int32_t) * fs.mesh_tex.size(), hipMemcpyHostToDevice));
+            CKC(ctx->sc.mem.alloc(&ctx->sc.d_mesh_tex, fs.mesh_tex.size()));
+            CKC(hipMemcpy(ctx->sc.d_mesh_tex, fs.mesh_tex.data(), sizeof(int32_t) * fs.mesh_tex.size(), hipMemcpyHostToDevice));
         }
         std::vector<DevTex> tex(scene->num_textures);
         for (uint32_t t = 0; t < scene->num_textures; ++t) {
@@ -550,15 +619,15 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
             std::vector<uint32_t> tiled((size_t)tiles_x * tiles_y * 32, 0u);
             for (int y = 0; y < td.height; ++y)
                 for (int x = 0; x < td.width; ++x) tiled[tex_tiled_index(x, y, tiles_x)] = td.pixel[(size_t)y * td.width + x];
-            CKC(dalloc(&px, tiled.size()));
-            ctx->d_tex_pixels.push_back(px);
+            CKC(ctx->sc.mem.alloc(&px, tiled.size()));
+            ctx->sc.d_tex_pixels.push_back(px);
             CKC(hipMemcpy(px, tiled.data(), sizeof(uint32_t) * tiled.size(), hipMemcpyHostToDevice));
             tex[t] = DevTex{px, td.width, td.height, tiles_x};
         }
         if (!tex.empty()) {
-            CKC(dalloc(&ctx->d_textures, tex.size()));
-            CKC(hipMemcpy(ctx->d_textures, tex.data(), sizeof(DevTex) * tex.size(), hipMemcpyHostToDevice));
-            ctx->tex0 = tex[0];
+            CKC(ctx->sc.mem.alloc(&ctx->sc.d_textures, tex.size()));
+            CKC(hipMemcpy(ctx->sc.d_textures, tex.data(), sizeof(DevTex) * tex.size(), hipMemcpyHostToDevice));
+            ctx->sc.tex0 = tex[0];
         }
     }
     hipEvent_t e0, e1;
@@ -566,22 +635,22 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
     CKC(tmp.event(&e1));
     if (warm_thread.joinable()) warm_thread.join(); // (whatever of the code-object load the upload did not cover is waited for here, outside bvh_build_ms but inside create_ms)
     CKC(hipEventRecord(e0, ctx->stream));
-    CKC(pt_bvh_build(ctx->d_verts, ctx->d_idx, ctx->d_tri_mesh, (uint32_t)nt, ctx->stream, &ctx->bvh));
-    CKC(dalloc(&ctx->d_tri_nrm, (size_t)ctx->bvh.num_tris8));
-    hipLaunchKernelGGL(k_shade_normals, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->bvh.num_tris8, ctx->d_tri_nrm);
-    if (ctx->d_uvs) { // textured scene: the 64-byte records a textured hit reads, in leaf order
-        CKC(dalloc(&ctx->d_textris, (size_t)ctx->bvh.num_tris8));
-        hipLaunchKernelGGL(k_emit_textris, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->d_uvs, ctx->bvh.num_tris8, ctx->d_textris);
+    CKC(pt_bvh_build(ctx->sc.d_verts, ctx->sc.d_idx, ctx->sc.d_tri_mesh, (uint32_t)nt, ctx->stream, &ctx->bvh));
+    CKC(ctx->sc.mem.alloc(&ctx->sc.d_tri_nrm, (size_t)ctx->bvh.num_tris8));
+    hipLaunchKernelGGL(k_shade_normals, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->bvh.num_tris8, ctx->sc.d_tri_nrm);
+    if (d_uvs) { // textured scene: the 64-byte records a textured hit reads, in leaf order
+        CKC(ctx->sc.mem.alloc(&ctx->sc.d_textris, (size_t)ctx->bvh.num_tris8));
+        hipLaunchKernelGGL(k_emit_textris, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, d_uvs, ctx->bvh.num_tris8, ctx->sc.d_textris);
     }
     CKC(hipEventRecord(e1, ctx->stream));
     CKC(hipStreamSynchronize(ctx->stream));
     float ms = 0;
     hipEventElapsedTime(&ms, e0, e1);
     ctx->bvh_build_ms = ms;
-    dfree(ctx->d_uvs);
-    CKC(dalloc(&ctx->d_totals, (size_t)PT_MAX_FRAMES * PT_MAX_SETS * 4));
-    CKC(dclear(ctx->stream, ctx->d_totals, sizeof(unsigned long long) * PT_MAX_FRAMES * PT_MAX_SETS * 4));
-    CKC(hipHostMalloc((void**)&ctx->h_totals, sizeof(unsigned long long) * PT_MAX_FRAMES * PT_MAX_SETS * 4));
+    uv_mem.release();
+    CKC(ctx->tot.mem.alloc(&ctx->tot.d_totals, (size_t)PT_MAX_FRAMES * PT_MAX_SETS * 4));
+    CKC(dclear(ctx->stream, ctx->tot.d_totals, sizeof(unsigned long long) * PT_MAX_FRAMES * PT_MAX_SETS * 4));
+    CKC(ctx->tot.mem.pinned(&ctx->tot.h_totals, (size_t)PT_MAX_FRAMES * PT_MAX_SETS * 4));
     {
         hipDeviceProp_t prop;
         CKC(hipGetDeviceProperties(&prop, device));
@@ -609,7 +678,7 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
             if (sscanf(e, "%lf,%lf", &c, &f) == 2 && c > 0 && f > 0) { ctx->sched_fake[0] = c; ctx->sched_fake[1] = f; }
         }
         if (const char* e = getenv("PT_FUSED_CAP")) ctx->fused_cap = std::min(4096u, std::max(64u, ((uint32_t)atoi(e) + 63u) & ~63u));
-        CKC(dalloc(&ctx->ovf, ovf_words(ctx)));
+        CKC(ctx->misc.alloc(&ctx->ovf, ovf_words(ctx)));
         ctx->ovf_depth = PT8_OVF_DEPTH;
         if (const char* e = getenv("PT_STACK_CAP")) ctx->ovf_depth = std::max(0, std::min(PT8_OVF_DEPTH, atoi(e) - (PT8_LDS_DEPTH - ctx->lds_skip)));
         if (const char* e = getenv("PT_STACK_NOCHECK")) ctx->stack_check = atoi(e) == 0;
@@ -633,52 +702,21 @@ extern "C" int pt_create(const pt_scene_desc* scene, int device, pt_ctx** out_ct
     return create_from_flat(fs, device, out_ctx);
 }
 
-static void free_path_state(pt_ctx* ctx) {
-    for (auto& b : ctx->sets) {
-        if (b.stream) hipStreamSynchronize(b.stream);
-        if (b.stream2) hipStreamSynchronize(b.stream2);
-        if (b.stream3) hipStreamSynchronize(b.stream3);
-        PathState& s = b.st;
-        for (auto& x : b.X) { dfree(x.rayO); dfree(x.rayD); dfree(x.thr); dfree(x.rf); dfree(x.hit); dfree(x.c0); dfree(x.c1); }
-        dfree(b.shO); dfree(b.shD); dfree(b.shPend); dfree(b.svis); dfree(s.pflags);
-        dfree(s.direct); dfree(s.indirect); dfree(s.alpha); dfree(s.nrm); dfree(s.alb); dfree(s.prdN); dfree(s.prdA);
-        dfree(b.queueA); dfree(b.queueB); dfree(b.squeue); dfree(b.counters); dfree(b.ovf); dfree(b.ovf2);
-        dfree(b.squeueB); dfree(b.ovf3); dfree(s.sO); dfree(s.sD); dfree(s.pendB); dfree(s.vis);
-        dfree(b.pixResult); dfree(b.pixAlpha); dfree(b.pixNormal); dfree(b.pixAlbedo);
-    }
-    ctx->sets.clear();
-    ctx->set_cap = ctx->set_pix_cap = 0;
+// Nothing may still run on a batch set's streams when its arrays go.
+static void sync_sets(pt_ctx* ctx) {
+    for (auto& b : ctx->sets)
+        for (hipStream_t st : {b.stream, b.stream2, b.stream3})
+            if (st) hipStreamSynchronize(st);
 }
-static void free_adaptive(pt_ctx* ctx) {
-    pt_ctx::Adaptive& ad = ctx->ad;
-    dfree(ad.d_moments); dfree(ad.d_active); dfree(ad.d_list);
-    if (ad.ev0) hipEventDestroy(ad.ev0);
-    if (ad.ev1) hipEventDestroy(ad.ev1);
-    ad = pt_ctx::Adaptive{};
-}
-static void free_blocks(pt_ctx* ctx) {
-    free_adaptive(ctx);
-    pt_ctx::Blocks& b = ctx->blk;
-    dfree(b.d_spans); dfree(b.d_flags); dfree(b.d_offsets); dfree(b.d_parts); dfree(b.d_list); dfree(b.d_counts);
-    if (b.h_counts) hipHostFree(b.h_counts);
-    b = pt_ctx::Blocks{};
-}
-static void free_views(pt_ctx* ctx) {
-    pt_ctx::Views& v = ctx->vw;
-    dfree(v.d_views); dfree(v.d_vblock); dfree(v.d_pixels);
-    v = pt_ctx::Views{};
-}
-static void free_frame(pt_ctx* ctx) {
-    free_blocks(ctx);
-    free_views(ctx);
-    for (void*& d : ctx->display) {
-        if (d) hipFree(d);
-        d = nullptr;
-    }
+// The frame and everything sized by it (the block table, the adaptive state, the views), as on a fresh context.
+static void unset_frame(pt_ctx* ctx) {
+    ctx->ad = pt_ctx::Adaptive{};
+    ctx->blk = pt_ctx::Blocks{};
+    ctx->vw = pt_ctx::Views{};
+    ctx->fb = pt_ctx::Frame{};
     ctx->ev_pack_guard = nullptr;
-    dfree(ctx->accum); dfree(ctx->color); dfree(ctx->normal); dfree(ctx->albedo); dfree(ctx->frame);
-    dfree(ctx->denoised); dfree(ctx->denoise_tmp);
-    dfree(ctx->d_pixels); dfree(ctx->d_all_pixels);
+    ctx->width = ctx->height = 0;
+    ctx->owned = ctx->padded = 0;
 }
 
 extern "C" int pt_destroy(pt_ctx* ctx) {
@@ -688,32 +726,14 @@ extern "C" int pt_destroy(pt_ctx* ctx) {
     for (auto& w : ctx->chunk_workers) enqueue_worker_stop(w.get());
     ctx->chunk_workers.clear();
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    free_path_state(ctx);
+    sync_sets(ctx);
+    ctx->sets.clear();
     for (hipStream_t st : ctx->set_streams) if (st) hipStreamDestroy(st);
     for (hipStream_t st : ctx->side_streams) if (st) hipStreamDestroy(st);
-    free_frame(ctx);
-    dfree(ctx->d_verts); dfree(ctx->d_idx); dfree(ctx->d_tri_mesh); dfree(ctx->d_mats);
-    dfree(ctx->d_rest); dfree(ctx->d_stage);
-    if (ctx->h_stage_bad) hipHostFree(ctx->h_stage_bad);
-    dfree(ctx->d_mesh_tex); dfree(ctx->d_uvs); dfree(ctx->d_textris); dfree(ctx->d_textures);
-    for (uint32_t*& px : ctx->d_tex_pixels) dfree(px);
     pt_bvh_free(&ctx->bvh);
-    dfree(ctx->d_tri_nrm);
-    dfree(ctx->d_probe_data); dfree(ctx->d_pdfX); dfree(ctx->d_cdfX); dfree(ctx->d_pdfY); dfree(ctx->d_cdfY);
-    dfree(ctx->d_c64Y); dfree(ctx->d_c8Y); dfree(ctx->d_lines); dfree(ctx->d_guide);
-    dfree(ctx->d_totals);
-    if (ctx->h_totals) hipHostFree(ctx->h_totals);
-    dfree(ctx->ovf);
-    dfree(ctx->dbg);
-    dfree(ctx->q.rayO); dfree(ctx->q.rayD); dfree(ctx->q.hit); dfree(ctx->q.mark); dfree(ctx->q.block);
-    if (ctx->q.h_counters) hipHostFree(ctx->q.h_counters);
-    for (hipEvent_t e : ctx->q.events) hipEventDestroy(e);
-    for (auto& pool : ctx->ev_pools)
-        for (hipEvent_t e : pool) hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->ev_packed[0], ctx->ev_packed[1], ctx->ev_displayed})
-        if (e) hipEventDestroy(e);
-    if (ctx->stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t stream = ctx->stream;
+    delete ctx; // every group frees what it owns
+    if (stream) hipStreamDestroy(stream);
     return PT_OK;
 }
 
@@ -797,7 +817,6 @@ extern "C" int pt_uvw_frame(const float eye[3], const float lookat[3], const flo
 
 // finish a probe upload: build the block-search accelerators and publish the device view
 static int finish_probe(pt_ctx* ctx, int w, int h) {
-    dfree(ctx->d_c64Y); dfree(ctx->d_c8Y); dfree(ctx->d_lines); dfree(ctx->d_guide);
     const int ncy = h / PT_CDF_BLOCK, ncy_pad = (ncy + 7) & ~7;
     const bool oky = (h % PT_CDF_BLOCK) == 0 && h >= PT_CDF_BLOCK;
     const bool enabled = getenv("PT_NO_BLOCKED_SEARCH") == nullptr;
@@ -811,85 +830,96 @@ static int finish_probe(pt_ctx* ctx, int w, int h) {
     }
     const int gpitch = gk + 2; // k = 0..gk, padded to an even count
     {
-        CK(dalloc(&ctx->d_lines, (size_t)h * lpr + 1)); // + 1: a non-monotone row handed to pt_set_probe can index one texel past its line
-        CK(dalloc(&ctx->d_guide, (size_t)h * gpitch));
-        CK(hipMemsetAsync(ctx->d_lines + (size_t)h * lpr, 0, sizeof(ProbeLine), ctx->stream));
-        hipLaunchKernelGGL(k_probe_lines, dim3((unsigned)(((size_t)h * lpr + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_probe_data, ctx->d_pdfX,
-                           ctx->d_cdfX, h, w, lpr, ctx->d_lines);
-        hipLaunchKernelGGL(k_probe_guide, dim3((unsigned)(((size_t)h * gpitch + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_lines, h, lpr, gk,
-                           gpitch, ctx->d_guide);
+        CK(ctx->pr.mem.alloc(&ctx->pr.d_lines, (size_t)h * lpr + 1)); // + 1: a non-monotone row handed to pt_set_probe can index one texel past its line
+        CK(ctx->pr.mem.alloc(&ctx->pr.d_guide, (size_t)h * gpitch));
+        CK(hipMemsetAsync(ctx->pr.d_lines + (size_t)h * lpr, 0, sizeof(ProbeLine), ctx->stream));
+        hipLaunchKernelGGL(k_probe_lines, dim3((unsigned)(((size_t)h * lpr + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pr.d_probe_data, ctx->pr.d_pdfX,
+                           ctx->pr.d_cdfX, h, w, lpr, ctx->pr.d_lines);
+        hipLaunchKernelGGL(k_probe_guide, dim3((unsigned)(((size_t)h * gpitch + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pr.d_lines, h, lpr, gk,
+                           gpitch, ctx->pr.d_guide);
     }
     if (oky && enabled) {
-        CK(dalloc(&ctx->d_c64Y, (size_t)ncy_pad));
-        CK(dalloc(&ctx->d_c8Y, (size_t)(h / 8)));
-        hipLaunchKernelGGL(k_probe_coarse, dim3((ncy_pad + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_cdfY, 1, h, PT_CDF_BLOCK, ncy_pad, ctx->d_c64Y);
-        hipLaunchKernelGGL(k_probe_coarse, dim3((h / 8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_cdfY, 1, h, 8, h / 8, ctx->d_c8Y);
+        CK(ctx->pr.mem.alloc(&ctx->pr.d_c64Y, (size_t)ncy_pad));
+        CK(ctx->pr.mem.alloc(&ctx->pr.d_c8Y, (size_t)(h / 8)));
+        hipLaunchKernelGGL(k_probe_coarse, dim3((ncy_pad + 255) / 256), dim3(256), 0, ctx->stream, ctx->pr.d_cdfY, 1, h, PT_CDF_BLOCK, ncy_pad, ctx->pr.d_c64Y);
+        hipLaunchKernelGGL(k_probe_coarse, dim3((h / 8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->pr.d_cdfY, 1, h, 8, h / 8, ctx->pr.d_c8Y);
     }
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());
-    ctx->probe = DevProbe{w, h, ctx->d_probe_data, ctx->d_pdfX, ctx->d_cdfX, ctx->d_pdfY, ctx->d_cdfY, ctx->d_c64Y, ctx->d_c8Y, ncy,
-                          ctx->d_lines, ctx->d_guide, lpr, gk, gpitch};
+    ctx->pr.dev = DevProbe{w, h, ctx->pr.d_probe_data, ctx->pr.d_pdfX, ctx->pr.d_cdfX, ctx->pr.d_pdfY, ctx->pr.d_cdfY, ctx->pr.d_c64Y, ctx->pr.d_c8Y, ncy,
+                          ctx->pr.d_lines, ctx->pr.d_guide, lpr, gk, gpitch};
     return PT_OK;
+}
+
+// What pt_set_probe and pt_set_probe_image share: the checks, then the old probe goes — the context has no probe until finish_probe
+// publishes the new one, so a failure on the way leaves "no probe set" — the five arrays are allocated and `fill` writes them (tmp: what
+// it needs until the tables are built).
+template <class Fill>
+static int replace_probe(pt_ctx* ctx, const char* fn, bool valid, int w, int h, bool image, Fill fill) {
+    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
+    const std::string f = std::string(fn) + ": ";
+    if (!valid || w <= 0 || h <= 0) return fail(ctx, PT_ERR_INVALID, (f + "Probe Data is not valid").c_str());
+    if ((long long)w * h >= (1ll << 31)) return fail(ctx, PT_ERR_UNSUPPORTED, (f + "probe too large").c_str());
+    if (w > 65535 * PT_LINE_COLS) return fail(ctx, PT_ERR_UNSUPPORTED, (f + "probe wider than 393210 columns").c_str()); // u16 line counts in the guide
+    CK(hipSetDevice(ctx->device));
+    if (image) CK(hipStreamSynchronize(ctx->stream)); // (its kernels run on the context's stream)
+    pt_ctx::Probe& P = ctx->pr;
+    P = pt_ctx::Probe{};
+    auto build = [&]() -> int {
+        DevOwner tmp;
+        const size_t n = (size_t)w * h;
+        CK(P.mem.alloc(&P.d_probe_data, n));
+        CK(P.mem.alloc(&P.d_pdfX, n));
+        CK(P.mem.alloc(&P.d_cdfX, n));
+        CK(P.mem.alloc(&P.d_pdfY, (size_t)h));
+        CK(P.mem.alloc(&P.d_cdfY, (size_t)h));
+        const int rc = fill(tmp, n);
+        return rc ? rc : finish_probe(ctx, w, h);
+    };
+    const int rc = build();
+    if (rc) {
+        hipStreamSynchronize(ctx->stream); // the table kernels that were enqueued
+        P = pt_ctx::Probe{}; // a probe that failed half way is no probe
+    }
+    return rc;
 }
 
 extern "C" int pt_set_probe(pt_ctx* ctx, const float* data, const float* pdfX, const float* cdfX, const float* pdfY,
                             const float* cdfY, int w, int h) {
     if (!ctx) return PT_ERR_INVALID;
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    if (!data || !pdfX || !cdfX || !pdfY || !cdfY || w <= 0 || h <= 0) return fail(ctx, PT_ERR_INVALID, "pt_set_probe: Probe Data is not valid");
-    if ((long long)w * h >= (1ll << 31)) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_set_probe: probe too large");
-    if (w > 65535 * PT_LINE_COLS) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_set_probe: probe wider than 393210 columns"); // u16 line counts in the guide
-    CK(hipSetDevice(ctx->device));
-    dfree(ctx->d_probe_data); dfree(ctx->d_pdfX); dfree(ctx->d_cdfX); dfree(ctx->d_pdfY); dfree(ctx->d_cdfY);
-    const size_t n = (size_t)w * h;
-    CK(dalloc(&ctx->d_probe_data, n));
-    CK(dalloc(&ctx->d_pdfX, n));
-    CK(dalloc(&ctx->d_cdfX, n));
-    CK(dalloc(&ctx->d_pdfY, (size_t)h));
-    CK(dalloc(&ctx->d_cdfY, (size_t)h));
-    CK(hipMemcpy(ctx->d_probe_data, data, sizeof(float4) * n, hipMemcpyHostToDevice));
-    CK(hipMemcpy(ctx->d_pdfX, pdfX, sizeof(float) * n, hipMemcpyHostToDevice));
-    CK(hipMemcpy(ctx->d_cdfX, cdfX, sizeof(float) * n, hipMemcpyHostToDevice));
-    CK(hipMemcpy(ctx->d_pdfY, pdfY, sizeof(float) * h, hipMemcpyHostToDevice));
-    CK(hipMemcpy(ctx->d_cdfY, cdfY, sizeof(float) * h, hipMemcpyHostToDevice));
-    return finish_probe(ctx, w, h);
+    return replace_probe(ctx, "pt_set_probe", data && pdfX && cdfX && pdfY && cdfY, w, h, false, [&](DevOwner&, size_t n) -> int {
+        CK(hipMemcpy(ctx->pr.d_probe_data, data, sizeof(float4) * n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(ctx->pr.d_pdfX, pdfX, sizeof(float) * n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(ctx->pr.d_cdfX, cdfX, sizeof(float) * n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(ctx->pr.d_pdfY, pdfY, sizeof(float) * h, hipMemcpyHostToDevice));
+        CK(hipMemcpy(ctx->pr.d_cdfY, cdfY, sizeof(float) * h, hipMemcpyHostToDevice));
+        return PT_OK;
+    });
 }
 
 extern "C" int pt_set_probe_image(pt_ctx* ctx, const float* data, int w, int h) {
     if (!ctx) return PT_ERR_INVALID;
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    if (!data || w <= 0 || h <= 0) return fail(ctx, PT_ERR_INVALID, "pt_set_probe_image: Probe Data is not valid");
-    if ((long long)w * h >= (1ll << 31)) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_set_probe_image: probe too large");
-    if (w > 65535 * PT_LINE_COLS) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_set_probe_image: probe wider than 393210 columns"); // u16 line counts in the guide
-    CK(hipSetDevice(ctx->device));
-    CK(hipStreamSynchronize(ctx->stream));
-    dfree(ctx->d_probe_data); dfree(ctx->d_pdfX); dfree(ctx->d_cdfX); dfree(ctx->d_pdfY); dfree(ctx->d_cdfY);
-    const size_t n = (size_t)w * h;
-    DevScope tmp;
-    float* rowTotal = nullptr;
-    CK(dalloc(&ctx->d_probe_data, n));
-    CK(dalloc(&ctx->d_pdfX, n));
-    CK(dalloc(&ctx->d_cdfX, n));
-    CK(dalloc(&ctx->d_pdfY, (size_t)h));
-    CK(dalloc(&ctx->d_cdfY, (size_t)h));
-    CK(tmp.alloc(&rowTotal, (size_t)h));
-    CK(hipMemcpy(ctx->d_probe_data, data, sizeof(float4) * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_cdf_rows, dim3(h), dim3(64), 0, ctx->stream, ctx->d_probe_data, w, h, ctx->d_pdfX, ctx->d_cdfX, rowTotal);
-    hipLaunchKernelGGL(k_cdf_marginal, dim3(1), dim3(64), 0, ctx->stream, rowTotal, h, ctx->d_pdfY, ctx->d_cdfY);
-    CK(hipStreamSynchronize(ctx->stream));
-    CK(hipGetLastError());
-    return finish_probe(ctx, w, h);
+    return replace_probe(ctx, "pt_set_probe_image", data != nullptr, w, h, true, [&](DevOwner& tmp, size_t n) -> int {
+        float* rowTotal = nullptr;
+        CK(tmp.alloc(&rowTotal, (size_t)h));
+        CK(hipMemcpy(ctx->pr.d_probe_data, data, sizeof(float4) * n, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_cdf_rows, dim3(h), dim3(64), 0, ctx->stream, ctx->pr.d_probe_data, w, h, ctx->pr.d_pdfX, ctx->pr.d_cdfX, rowTotal);
+        hipLaunchKernelGGL(k_cdf_marginal, dim3(1), dim3(64), 0, ctx->stream, rowTotal, h, ctx->pr.d_pdfY, ctx->pr.d_cdfY);
+        CK(hipStreamSynchronize(ctx->stream));
+        CK(hipGetLastError());
+        return PT_OK;
+    });
 }
 
 extern "C" int pt_get_probe_cdf(pt_ctx* ctx, float* pdfX, float* cdfX, float* pdfY, float* cdfY) {
     if (!ctx) return PT_ERR_INVALID;
-    if (!ctx->probe.data) return fail(ctx, PT_ERR_INVALID, "pt_get_probe_cdf: no probe set");
+    if (!ctx->pr.dev.data) return fail(ctx, PT_ERR_INVALID, "pt_get_probe_cdf: no probe set");
     CK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)ctx->probe.width * ctx->probe.height;
-    if (pdfX) CK(hipMemcpy(pdfX, ctx->d_pdfX, sizeof(float) * n, hipMemcpyDeviceToHost));
-    if (cdfX) CK(hipMemcpy(cdfX, ctx->d_cdfX, sizeof(float) * n, hipMemcpyDeviceToHost));
-    if (pdfY) CK(hipMemcpy(pdfY, ctx->d_pdfY, sizeof(float) * ctx->probe.height, hipMemcpyDeviceToHost));
-    if (cdfY) CK(hipMemcpy(cdfY, ctx->d_cdfY, sizeof(float) * ctx->probe.height, hipMemcpyDeviceToHost));
+    const size_t n = (size_t)ctx->pr.dev.width * ctx->pr.dev.height;
+    if (pdfX) CK(hipMemcpy(pdfX, ctx->pr.d_pdfX, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (cdfX) CK(hipMemcpy(cdfX, ctx->pr.d_cdfX, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (pdfY) CK(hipMemcpy(pdfY, ctx->pr.d_pdfY, sizeof(float) * ctx->pr.dev.height, hipMemcpyDeviceToHost));
+    if (cdfY) CK(hipMemcpy(cdfY, ctx->pr.d_cdfY, sizeof(float) * ctx->pr.dev.height, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -930,6 +960,35 @@ static void build_pixel_lists(int w, int h, int world, int tile_w, int tile_h, s
         }
 }
 
+// the frame buffers and pixel lists of pt_resize, into the emptied frame group
+static int build_frame(pt_ctx* ctx, int width, int height) {
+    pt_ctx::Frame& F = ctx->fb;
+    const size_t n = (size_t)width * height;
+    CK(F.mem.alloc(&F.accum, n));
+    CK(F.mem.alloc(&F.color, n));
+    CK(F.mem.alloc(&F.normal, n));
+    CK(F.mem.alloc(&F.albedo, n));
+    CK(F.mem.alloc(&F.frame, n));
+    CK(hipMemsetAsync(F.accum, 0, sizeof(float4) * n, ctx->stream));
+    CK(hipMemsetAsync(F.color, 0, sizeof(float4) * n, ctx->stream));
+    CK(hipMemsetAsync(F.normal, 0, sizeof(float4) * n, ctx->stream));
+    CK(hipMemsetAsync(F.albedo, 0, sizeof(float4) * n, ctx->stream));
+    CK(dclear(ctx->stream, F.frame, sizeof(uint32_t) * n));
+    std::vector<std::vector<uint32_t>> lists;
+    build_pixel_lists(width, height, ctx->world, ctx->tile_w, ctx->tile_h, lists);
+    size_t padded = 0;
+    for (auto& l : lists) padded = std::max(padded, l.size());
+    const uint32_t owned = (uint32_t)lists[ctx->rank].size();
+    CK(F.mem.alloc(&F.d_pixels, (size_t)owned));
+    if (owned) CK(hipMemcpy(F.d_pixels, lists[ctx->rank].data(), sizeof(uint32_t) * owned, hipMemcpyHostToDevice));
+    std::vector<uint32_t> all((size_t)ctx->world * padded, 0xffffffffu);
+    for (int r = 0; r < ctx->world; ++r) std::copy(lists[r].begin(), lists[r].end(), all.begin() + (size_t)r * padded);
+    CK(F.mem.alloc(&F.d_all_pixels, all.size()));
+    if (!all.empty()) CK(hipMemcpy(F.d_all_pixels, all.data(), sizeof(uint32_t) * all.size(), hipMemcpyHostToDevice));
+    ctx->owned = owned;
+    ctx->padded = (uint32_t)padded;
+    return PT_OK;
+}
 extern "C" int pt_resize(pt_ctx* ctx, int width, int height) {
     if (!ctx) return PT_ERR_INVALID;
     { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
@@ -937,30 +996,13 @@ extern "C" int pt_resize(pt_ctx* ctx, int width, int height) {
     if (width < 0 || height < 0 || width > 65535 || height > 65535) return fail(ctx, PT_ERR_INVALID, "pt_resize: size out of range");
     CK(hipSetDevice(ctx->device));
     CK(hipStreamSynchronize(ctx->stream));
-    free_frame(ctx);
-    const size_t n = (size_t)width * height;
-    CK(dalloc(&ctx->accum, n));
-    CK(dalloc(&ctx->color, n));
-    CK(dalloc(&ctx->normal, n));
-    CK(dalloc(&ctx->albedo, n));
-    CK(dalloc(&ctx->frame, n));
-    CK(hipMemsetAsync(ctx->accum, 0, sizeof(float4) * n, ctx->stream));
-    CK(hipMemsetAsync(ctx->color, 0, sizeof(float4) * n, ctx->stream));
-    CK(hipMemsetAsync(ctx->normal, 0, sizeof(float4) * n, ctx->stream));
-    CK(hipMemsetAsync(ctx->albedo, 0, sizeof(float4) * n, ctx->stream));
-    CK(dclear(ctx->stream, ctx->frame, sizeof(uint32_t) * n));
-    std::vector<std::vector<uint32_t>> lists;
-    build_pixel_lists(width, height, ctx->world, ctx->tile_w, ctx->tile_h, lists);
-    size_t padded = 0;
-    for (auto& l : lists) padded = std::max(padded, l.size());
-    ctx->owned = (uint32_t)lists[ctx->rank].size();
-    ctx->padded = (uint32_t)padded;
-    CK(dalloc(&ctx->d_pixels, (size_t)ctx->owned));
-    if (ctx->owned) CK(hipMemcpy(ctx->d_pixels, lists[ctx->rank].data(), sizeof(uint32_t) * ctx->owned, hipMemcpyHostToDevice));
-    std::vector<uint32_t> all((size_t)ctx->world * padded, 0xffffffffu);
-    for (int r = 0; r < ctx->world; ++r) std::copy(lists[r].begin(), lists[r].end(), all.begin() + (size_t)r * padded);
-    CK(dalloc(&ctx->d_all_pixels, all.size()));
-    if (!all.empty()) CK(hipMemcpy(ctx->d_all_pixels, all.data(), sizeof(uint32_t) * all.size(), hipMemcpyHostToDevice));
+    unset_frame(ctx);
+    const int rc = build_frame(ctx, width, height);
+    if (rc) {
+        hipStreamSynchronize(ctx->stream); // the clears that were enqueued
+        unset_frame(ctx);
+        return rc;
+    }
     ctx->width = width;
     ctx->height = height;
     return PT_OK;
@@ -1012,8 +1054,9 @@ static int pick_streams(pt_ctx* ctx, int nsets) {
     const char* pe = getenv("PT_STREAM_PROBE");
     if (pe && atoi(pe) == 0) return PT_OK;
     std::lock_guard<std::mutex> probe_lock(g_probe_mu);
+    DevOwner tmp;
     long long* d_stamps = nullptr;
-    CK(hipMalloc(&d_stamps, 2 * sizeof(long long)));
+    CK(tmp.alloc(&d_stamps, 2));
     CK(hipStreamSynchronize(ctx->stream));
     // the streams that already carry frames stay; new ones must be concurrent with all of them (re-probed when the number of sets grows)
     std::vector<hipStream_t> chosen{ctx->stream}, spare;
@@ -1029,7 +1072,7 @@ static int pick_streams(pt_ctx* ctx, int nsets) {
             if (!streams_concurrent(c, st, d_stamps)) { ok = false; break; }
         (ok ? chosen : spare).push_back(st);
     }
-    hipFree(d_stamps);
+    tmp.release();
     (void)hipGetLastError();
     if (getenv("PT_DEBUG"))
         fprintf(stderr, "[ptamd] pick_streams: %d sets, %d streams created, %zu mutually concurrent (want %d), %zu to the side\n", nsets, attempts, chosen.size(), want, spare.size());
@@ -1081,6 +1124,35 @@ static int assign_streams(pt_ctx* ctx, int nsets) {
 // placed in the unified launch (enqueue_chunk).  Decided by what pt_create saw, so the arrays exist whenever a frame may want them.
 static bool carry_eligible(const pt_ctx* ctx) { return ctx->carry_sums && !ctx->has_catcher; }
 
+// the streams and arrays of the (empty) batch sets
+static int build_path_state(pt_ctx* ctx, int nsets, uint32_t cap, uint32_t pix_cap, int nq, bool async) {
+    const size_t qsize = (size_t)PT_NSUB * ctx->sub_cap;
+    if (const int rc = assign_streams(ctx, nsets)) return rc;
+    for (auto& b : ctx->sets) {
+        PathState& s = b.st;
+        for (auto& x : b.X) { CK(b.mem.alloc(&x.rayO, qsize)); CK(b.mem.alloc(&x.rayD, qsize)); CK(b.mem.alloc(&x.thr, qsize)); CK(b.mem.alloc(&x.rf, qsize)); CK(b.mem.alloc(&x.hit, qsize)); }
+        CK(b.mem.alloc(&b.shO, qsize)); CK(b.mem.alloc(&b.shD, qsize)); CK(b.mem.alloc(&b.shPend, qsize)); CK(b.mem.alloc(&s.pflags, cap));
+        if (carry_eligible(ctx)) {
+            for (auto& x : b.X) { CK(b.mem.alloc(&x.c0, qsize)); CK(b.mem.alloc(&x.c1, qsize)); }
+            CK(b.mem.alloc(&b.svis, qsize));
+        }
+        CK(b.mem.alloc(&s.direct, cap)); CK(b.mem.alloc(&s.indirect, cap)); CK(b.mem.alloc(&s.nrm, cap)); CK(b.mem.alloc(&s.alb, cap));
+        if (ctx->has_catcher) { CK(b.mem.alloc(&s.alpha, cap)); CK(b.mem.alloc(&s.prdN, cap)); CK(b.mem.alloc(&s.prdA, cap)); }
+        CK(b.mem.alloc(&b.queueA, qsize)); CK(b.mem.alloc(&b.queueB, qsize)); CK(b.mem.alloc(&b.squeue, qsize));
+        CK(b.mem.alloc(&b.counters, counter_words(nq)));
+        CK(b.mem.alloc(&b.ovf, ovf_words(ctx))); CK(b.mem.alloc(&b.ovf2, ovf_words(ctx)));
+        CK(b.mem.alloc(&b.pixResult, pix_cap)); CK(b.mem.alloc(&b.pixAlpha, pix_cap)); CK(b.mem.alloc(&b.pixNormal, pix_cap)); CK(b.mem.alloc(&b.pixAlbedo, pix_cap));
+        if (async) {
+            CK(b.mem.alloc(&s.sO, (size_t)nq * cap)); CK(b.mem.alloc(&s.sD, (size_t)nq * cap)); CK(b.mem.alloc(&s.pendB, (size_t)nq * cap));
+            CK(b.mem.alloc(&s.vis, cap));
+            s.bstride = cap;
+            CK(b.mem.alloc(&b.squeueB, (size_t)nq * qsize));
+            CK(b.mem.alloc(&b.ovf3, ovf_words(ctx)));
+        }
+    }
+    return PT_OK;
+}
+
 static int ensure_path_state(pt_ctx* ctx, int nsets, uint32_t cap, uint32_t pix_cap) {
     // one queue-counter slot per bounce plus the "would continue" slot; shadow-catcher scenes get two more for the extra
     // iterations of paths that passed through catcher surfaces (enqueue_chunk)
@@ -1089,45 +1161,22 @@ static int ensure_path_state(pt_ctx* ctx, int nsets, uint32_t cap, uint32_t pix_
     if ((int)ctx->sets.size() >= nsets && cap <= ctx->set_cap && pix_cap <= ctx->set_pix_cap && nq <= ctx->nq &&
         (!ctx->has_catcher || ctx->cap_catcher) && async == ctx->cap_async)
         return assign_streams(ctx, (int)ctx->sets.size());
-    {
-        int rc = drain(ctx); // frames in flight still use the old buffers
-        if (rc) return rc;
-    }
+    if (const int rc = drain(ctx)) return rc; // frames in flight still use the old buffers
     nsets = std::max(nsets, (int)ctx->sets.size());
     cap = std::max(cap, ctx->set_cap);
     pix_cap = std::max(pix_cap, ctx->set_pix_cap);
     nq = std::max(nq, ctx->nq);
     ++ctx->path_state_allocs;
-    free_path_state(ctx);
-    CK(dclear(ctx->stream, ctx->d_totals, sizeof(unsigned long long) * PT_MAX_FRAMES * PT_MAX_SETS * 4)); // slices of sets that no longer exist
+    sync_sets(ctx);
+    ctx->sets.clear();
+    ctx->set_cap = ctx->set_pix_cap = 0; // published again at the end: until then the context has no path state
+    CK(dclear(ctx->stream, ctx->tot.d_totals, sizeof(unsigned long long) * PT_MAX_FRAMES * PT_MAX_SETS * 4)); // slices of sets that no longer exist
     ctx->sets.resize(nsets);
     ctx->sub_cap = cap / PT_NSUB + 8192 + 1; // a sub-queue receives at most cap/64 + 32 workgroups * 256 entries
-    const size_t qsize = (size_t)PT_NSUB * ctx->sub_cap;
-    {
-        int rc = assign_streams(ctx, nsets);
-        if (rc) return rc;
-    }
-    for (auto& b : ctx->sets) {
-        PathState& s = b.st;
-        for (auto& x : b.X) { CK(dalloc(&x.rayO, qsize)); CK(dalloc(&x.rayD, qsize)); CK(dalloc(&x.thr, qsize)); CK(dalloc(&x.rf, qsize)); CK(dalloc(&x.hit, qsize)); }
-        CK(dalloc(&b.shO, qsize)); CK(dalloc(&b.shD, qsize)); CK(dalloc(&b.shPend, qsize)); CK(dalloc(&s.pflags, cap));
-        if (carry_eligible(ctx)) {
-            for (auto& x : b.X) { CK(dalloc(&x.c0, qsize)); CK(dalloc(&x.c1, qsize)); }
-            CK(dalloc(&b.svis, qsize));
-        }
-        CK(dalloc(&s.direct, cap)); CK(dalloc(&s.indirect, cap)); CK(dalloc(&s.nrm, cap)); CK(dalloc(&s.alb, cap));
-        if (ctx->has_catcher) { CK(dalloc(&s.alpha, cap)); CK(dalloc(&s.prdN, cap)); CK(dalloc(&s.prdA, cap)); }
-        CK(dalloc(&b.queueA, qsize)); CK(dalloc(&b.queueB, qsize)); CK(dalloc(&b.squeue, qsize));
-        CK(dalloc(&b.counters, counter_words(nq)));
-        CK(dalloc(&b.ovf, ovf_words(ctx))); CK(dalloc(&b.ovf2, ovf_words(ctx)));
-        CK(dalloc(&b.pixResult, pix_cap)); CK(dalloc(&b.pixAlpha, pix_cap)); CK(dalloc(&b.pixNormal, pix_cap)); CK(dalloc(&b.pixAlbedo, pix_cap));
-        if (async) {
-            CK(dalloc(&s.sO, (size_t)nq * cap)); CK(dalloc(&s.sD, (size_t)nq * cap)); CK(dalloc(&s.pendB, (size_t)nq * cap));
-            CK(dalloc(&s.vis, cap));
-            s.bstride = cap;
-            CK(dalloc(&b.squeueB, (size_t)nq * qsize));
-            CK(dalloc(&b.ovf3, ovf_words(ctx)));
-        }
+    const int rc = build_path_state(ctx, nsets, cap, pix_cap, nq, async);
+    if (rc) {
+        ctx->sets.clear(); // all of it or nothing (the streams stay: they belong to the context)
+        return rc;
     }
     ctx->cap_async = async;
     ctx->cap_catcher = ctx->has_catcher;
@@ -1142,8 +1191,8 @@ enum { CLS_TRACE = 0, CLS_SHADOW = 1, CLS_SHADE = 2, CLS_OTHER = 3 };
 static hipEvent_t next_event(pt_ctx* ctx) {
     auto& pool = ctx->ev_pools[ctx->cur_slot];
     if (ctx->ev_used == pool.size()) {
-        hipEvent_t e;
-        hipEventCreate(&e);
+        hipEvent_t e = nullptr;
+        ctx->misc.event(&e);
         pool.push_back(e);
     }
     return pool[ctx->ev_used++];
@@ -1238,7 +1287,7 @@ struct RegionJob { // non-null: one launch-index range of a foveated launch inst
 struct ChunkMode {
     bool fused_frame = false; // the frame is one fused pass
     bool adapt_grid = false;  // whole frames in flight (frames_in_flight = 3): traversal grids sized by the pass
-    const uint32_t* pixels = nullptr; // the frame's pixel list (null: the rank's whole list, ctx->d_pixels)
+    const uint32_t* pixels = nullptr; // the frame's pixel list (null: the rank's whole list, ctx->fb.d_pixels)
     float4* moments = nullptr;        // pt_render_adaptive: the resolve records the per-pixel moments
     ViewParams vp{};                  // viewports (pt_set_views): the *_views kernels generate and resolve (null: the frame's single camera)
 };
@@ -1296,7 +1345,7 @@ struct ChainPass {
     }
     // (the hit records index the leaf triangles of the structure that was traversed)
     ShadeParams shade_params(QView q, QView next, QView shadow, const pt_ctx::BatchSet::StreamBuf* out, int aov, int first) const {
-        ShadeParams sp{ctx->bvh.tris8, ctx->d_tri_nrm, ctx->d_mats, ctx->d_mesh_tex, ctx->d_textris, ctx->d_textures, ctx->probe, ctx->opt.max_depth, tmin, q, next, shadow,
+        ShadeParams sp{ctx->bvh.tris8, ctx->sc.d_tri_nrm, ctx->sc.d_mats, ctx->sc.d_mesh_tex, ctx->sc.d_textris, ctx->sc.d_textures, ctx->pr.dev, ctx->opt.max_depth, tmin, q, next, shadow,
                        out ? out->rayO : nullptr, out ? out->rayD : nullptr, out ? out->thr : nullptr, out ? out->rf : nullptr, aov, first,
                        out ? out->c0 : nullptr, out ? out->c1 : nullptr, 0, 0};
 #ifdef PT_DEBUG_STATS
@@ -1379,7 +1428,7 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
         // (never above trace_grid: the spill stacks are sized for trace_grid waves and the kernels are compiled for that occupancy)
         const unsigned tgrid = !mode.adapt_grid ? (unsigned)ctx->trace_grid
             : (unsigned)std::min<uint64_t>((uint64_t)ctx->trace_grid, std::max<uint64_t>((uint64_t)ctx->trace_grid_min, pass_paths / (64ull * (uint64_t)ctx->grid_chunks)));
-        BatchParams bp{(mode.pixels ? mode.pixels : ctx->d_pixels) + pix0, npix, s0, Sc, ctx->has_catcher ? 1 : 0, bs.pixResult, bs.pixAlpha, bs.pixNormal, bs.pixAlbedo};
+        BatchParams bp{(mode.pixels ? mode.pixels : ctx->fb.d_pixels) + pix0, npix, s0, Sc, ctx->has_catcher ? 1 : 0, bs.pixResult, bs.pixAlpha, bs.pixNormal, bs.pixAlbedo};
         hipMemsetAsync(bs.counters, 0, sizeof(uint32_t) * counter_words(nq), bs.stream);
         ChainPass P{ctx, bs, bvh_dev(ctx), job ? job->var.cull_back_occlusion : 0, job ? job->var.radiance_tmin : 0.001f, tgrid, pass_paths,
                     bs.counters, bs.counters + (size_t)nq * CS, bs.counters + (size_t)2 * nq * CS, nq, lc,
@@ -1524,7 +1573,7 @@ static int frame_open(pt_ctx* ctx, int slot, bool pipelined, const char* what, c
     ctx->fr[slot].active = 0;
     if (ctx->width == 0) return PT_OK;
     if (bad_args) return fail(ctx, PT_ERR_INVALID, bad_args);
-    if (!ctx->probe.data) return fail(ctx, PT_ERR_INVALID, (std::string(what) + ": no probe set (setProbe)").c_str());
+    if (!ctx->pr.dev.data) return fail(ctx, PT_ERR_INVALID, (std::string(what) + ": no probe set (setProbe)").c_str());
     CK(hipSetDevice(ctx->device));
     return PT_OK;
 }
@@ -1563,7 +1612,7 @@ static int frame_close(pt_ctx* ctx, int slot, hipEvent_t ev_begin, int nsets, hi
         int rc = (*tail)(end_stream);
         if (rc) return rc;
     }
-    CK(hipMemcpyAsync(ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4, totals_of(ctx, slot, 0), sizeof(unsigned long long) * PT_MAX_SETS * 4, hipMemcpyDeviceToHost, end_stream));
+    CK(hipMemcpyAsync(ctx->tot.h_totals + (size_t)slot * PT_MAX_SETS * 4, totals_of(ctx, slot, 0), sizeof(unsigned long long) * PT_MAX_SETS * 4, hipMemcpyDeviceToHost, end_stream));
     hipEvent_t ev_end = next_event(ctx);
     CK(hipEventRecord(ev_end, end_stream));
     if (resolved_kind >= 0) {
@@ -1714,7 +1763,7 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
         if (rc) return rc;
     }
     if (getenv("PT_DEBUG_COUNTS")) {
-        if (!ctx->dbg) CK(dalloc(&ctx->dbg, 64 + (size_t)8 * PT_WAVELOG_CAP)); // 64 counters + the per-wave log of PT_DEBUG_STATS builds
+        if (!ctx->dbg) CK(ctx->misc.alloc(&ctx->dbg, 64 + (size_t)8 * PT_WAVELOG_CAP)); // 64 counters + the per-wave log of PT_DEBUG_STATS builds
         CK(dclear(ctx->stream, ctx->dbg, 512));
     }
     // a whole frame's chunks (one, unless spp x pixels exceed max_paths) all go to the stream of this frame's set
@@ -1724,8 +1773,8 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
     hipEvent_t ev_begin;
     rc = frame_begin(ctx, slot, pipelined, used, whole_stream, &ev_begin);
     if (rc) return rc;
-    FrameParams fp{ctx->accum, ctx->frame, ctx->color, ctx->normal, ctx->albedo, ctx->width, ctx->height, subframe_index,
-                   ctx->eye, ctx->U, ctx->V, ctx->W, spp, ctx->probe};
+    FrameParams fp{ctx->fb.accum, ctx->fb.frame, ctx->fb.color, ctx->fb.normal, ctx->fb.albedo, ctx->width, ctx->height, subframe_index,
+                   ctx->eye, ctx->U, ctx->V, ctx->W, spp, ctx->pr.dev};
     LaunchCounts lc;
     // What the resolves of a frame in flight wait for.  Chunk c of consecutive pt_render frames runs on the same stream, which orders their
     // resolves; a foveated frame (pt_render_regions) deals its launches to the streams differently, so after one of those every resolve waits
@@ -1844,7 +1893,7 @@ static int render_finish(pt_ctx* ctx, int slot = 0) {
         return PT_ERR_HIP;
     }
     CK(hipGetLastError());
-    const unsigned long long* per_set = ctx->h_totals + (size_t)slot * PT_MAX_SETS * 4; // copied behind the frame's last kernel, before ev_end
+    const unsigned long long* per_set = ctx->tot.h_totals + (size_t)slot * PT_MAX_SETS * 4; // copied behind the frame's last kernel, before ev_end
     unsigned long long totals[4] = {0, 0, 0, 0};
     for (int i = 0; i < fr.nsets; ++i) { // the frame's sets only: a frame in flight clears only theirs, the others may hold an older frame's counts
         totals[0] += per_set[i * 4 + 0];
@@ -1992,7 +2041,7 @@ extern "C" int pt_render_device(pt_ctx* ctx, uint32_t spp, uint32_t subframe_ind
     if (rc != PT_OK) return rc;
     if (ctx->width == 0) return PT_OK; // not resized yet: render() silently returns (:77)
     CK(hipSetDevice(ctx->device));
-    CK(hipMemcpyAsync(dev_rgba8, ctx->frame, sizeof(uint32_t) * (size_t)ctx->width * ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+    CK(hipMemcpyAsync(dev_rgba8, ctx->fb.frame, sizeof(uint32_t) * (size_t)ctx->width * ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -2052,8 +2101,8 @@ static int regions_enqueue(pt_ctx* ctx, const pt_region* regions, uint32_t n, co
     if (pipelined && ctx->ev_pack_guard) prev_done.push_back(ctx->ev_pack_guard);
     for (uint32_t r = 0; r < n; ++r) {
         const pt_region& g = regions[r];
-        FrameParams fp{ctx->accum, ctx->frame, ctx->color, ctx->normal, ctx->albedo, ctx->width, ctx->height, g.subframe_index,
-                       ctx->eye, ctx->U, ctx->V, ctx->W, g.spp, ctx->probe};
+        FrameParams fp{ctx->fb.accum, ctx->fb.frame, ctx->fb.color, ctx->fb.normal, ctx->fb.albedo, ctx->width, ctx->height, g.subframe_index,
+                       ctx->eye, ctx->U, ctx->V, ctx->W, g.spp, ctx->pr.dev};
         RegionJob job;
         job.rg = RegionParams{g.launch_w, g.launch_h, g.factor_x, g.factor_y, g.fill_size, g.cx, g.cy, g.r_inner, g.r_outer, g.offset_x, g.offset_y, g.redraw, g.spp, g.subframe_index};
         job.var = var;
@@ -2128,21 +2177,21 @@ static int build_blocks(pt_ctx* ctx) {
             B.owned_blocks += size ? 1u : 0u;
         }
     if (at != ctx->frame_owned()) return fail(ctx, PT_ERR_INVALID, "block table does not match the pixel list");
-    CK(dalloc(&B.d_spans, (size_t)B.nblk));
-    CK(dalloc(&B.d_flags, (size_t)B.nblk));
-    CK(dalloc(&B.d_offsets, (size_t)B.nblk));
+    CK(B.mem.alloc(&B.d_spans, (size_t)B.nblk));
+    CK(B.mem.alloc(&B.d_flags, (size_t)B.nblk));
+    CK(B.mem.alloc(&B.d_offsets, (size_t)B.nblk));
     B.nparts = (B.nblk + 255u) / 256u;
-    CK(dalloc(&B.d_parts, (size_t)2 * B.nparts));
-    CK(dalloc(&B.d_list, (size_t)ctx->owned));
-    CK(dalloc(&B.d_counts, (size_t)2));
-    CK(hipHostMalloc((void**)&B.h_counts, sizeof(uint32_t) * 2));
+    CK(B.mem.alloc(&B.d_parts, (size_t)2 * B.nparts));
+    CK(B.mem.alloc(&B.d_list, (size_t)ctx->owned));
+    CK(B.mem.alloc(&B.d_counts, (size_t)2));
+    CK(B.mem.pinned(&B.h_counts, 2));
     CK(hipMemcpy(B.d_spans, spans.data(), sizeof(BlockSpan) * B.nblk, hipMemcpyHostToDevice));
     return PT_OK;
 }
 static int ensure_blocks(pt_ctx* ctx) {
     if (ctx->blk.d_spans) return PT_OK;
-    const int rc = build_blocks(ctx);
-    if (rc) free_blocks(ctx); // all of it or nothing: the next call starts over
+    const int rc = build_blocks(ctx); // (into the empty group: d_spans, its first allocation, is what says "built")
+    if (rc) ctx->blk = pt_ctx::Blocks{}; // all of it or nothing: the next call starts over
     return rc;
 }
 // flags -> compacted list + counts, then the copy of `words` counts (1: pixels; 2: and blocks) to the pinned host words; all on stream s
@@ -2188,6 +2237,25 @@ extern "C" int pt_render_mask(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index
     return subset_render(ctx, spp, subframe_index, sub, host_rgba8);
 }
 
+// the arrays and events of pt_adaptive_begin and the first active list, into the emptied group
+static int adaptive_build(pt_ctx* ctx) {
+    pt_ctx::Blocks& B = ctx->blk;
+    pt_ctx::Adaptive& A = ctx->ad;
+    const size_t n = (size_t)ctx->width * ctx->height;
+    CK(A.mem.alloc(&A.d_moments, n));
+    CK(A.mem.alloc(&A.d_active, (size_t)B.nblk));
+    CK(A.mem.alloc(&A.d_list, (size_t)ctx->owned));
+    CK(A.mem.event(&A.ev0));
+    CK(A.mem.event(&A.ev1));
+    CK(hipMemsetAsync(A.d_moments, 0, sizeof(float4) * n, ctx->stream));
+    CK(hipMemcpyAsync(A.d_active, B.owned_flags.data(), B.nblk, hipMemcpyHostToDevice, ctx->stream)); // (blocks of other ranks are never active)
+    const int rc = compact_enqueue(ctx, ctx->stream, A.d_active, A.d_list, 2);
+    if (rc) return rc;
+    CK(hipStreamSynchronize(ctx->stream));
+    A.count = B.h_counts[0];
+    A.active_blocks = B.h_counts[1];
+    return PT_OK;
+}
 extern "C" int pt_adaptive_begin(pt_ctx* ctx, const pt_adaptive_params* prm) {
     if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_adaptive_begin: null context");
     if (!prm) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: null parameters");
@@ -2197,25 +2265,15 @@ extern "C" int pt_adaptive_begin(pt_ctx* ctx, const pt_adaptive_params* prm) {
     if (ctx->vw.n) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_adaptive_begin: not with viewports set (pt_set_views)");
     int rc = subset_open(ctx, "pt_adaptive_begin", false, 0);
     if (rc) return rc;
-    free_adaptive(ctx);
-    pt_ctx::Blocks& B = ctx->blk;
-    pt_ctx::Adaptive& A = ctx->ad;
-    const size_t n = (size_t)ctx->width * ctx->height;
-    CK(dalloc(&A.d_moments, n));
-    CK(dalloc(&A.d_active, (size_t)B.nblk));
-    CK(dalloc(&A.d_list, (size_t)ctx->owned));
-    CK(hipEventCreate(&A.ev0));
-    CK(hipEventCreate(&A.ev1));
-    CK(hipMemsetAsync(A.d_moments, 0, sizeof(float4) * n, ctx->stream));
-    CK(hipMemcpyAsync(A.d_active, B.owned_flags.data(), B.nblk, hipMemcpyHostToDevice, ctx->stream)); // (blocks of other ranks are never active)
-    rc = compact_enqueue(ctx, ctx->stream, A.d_active, A.d_list, 2);
-    if (rc) return rc;
-    CK(hipStreamSynchronize(ctx->stream));
-    A.count = B.h_counts[0];
-    A.active_blocks = B.h_counts[1];
-    A.prm = *prm;
-    A.pixel_subframes = 0;
-    A.on = true;
+    ctx->ad = pt_ctx::Adaptive{};
+    rc = adaptive_build(ctx);
+    if (rc) {
+        hipStreamSynchronize(ctx->stream); // what was enqueued on the arrays
+        ctx->ad = pt_ctx::Adaptive{};
+        return rc;
+    }
+    ctx->ad.prm = *prm;
+    ctx->ad.on = true;
     return PT_OK;
 }
 
@@ -2267,7 +2325,7 @@ extern "C" int pt_adaptive_end(pt_ctx* ctx) {
         CK(hipSetDevice(ctx->device));
         CK(hipStreamSynchronize(ctx->stream));
     }
-    free_adaptive(ctx);
+    ctx->ad = pt_ctx::Adaptive{};
     return PT_OK;
 }
 
@@ -2291,12 +2349,12 @@ extern "C" int pt_download_adaptive(pt_ctx* ctx, int which, void* host, size_t b
 
 static void* buffer_ptr(pt_ctx* ctx, int which, size_t* elem) {
     switch (which) {
-        case PT_BUF_ACCUM: *elem = 16; return ctx->accum;
-        case PT_BUF_FRAME: *elem = 4; return ctx->frame;
-        case PT_BUF_COLOR: *elem = 16; return ctx->color;
-        case PT_BUF_NORMAL: *elem = 16; return ctx->normal;
-        case PT_BUF_ALBEDO: *elem = 16; return ctx->albedo;
-        case PT_BUF_DENOISED: *elem = 16; return ctx->denoised;
+        case PT_BUF_ACCUM: *elem = 16; return ctx->fb.accum;
+        case PT_BUF_FRAME: *elem = 4; return ctx->fb.frame;
+        case PT_BUF_COLOR: *elem = 16; return ctx->fb.color;
+        case PT_BUF_NORMAL: *elem = 16; return ctx->fb.normal;
+        case PT_BUF_ALBEDO: *elem = 16; return ctx->fb.albedo;
+        case PT_BUF_DENOISED: *elem = 16; return ctx->fb.denoised;
     }
     *elem = 0;
     return nullptr;
@@ -2324,9 +2382,9 @@ extern "C" int pt_download(pt_ctx* ctx, int which, void* host, size_t bytes) {
 extern "C" int pt_upload_accum(pt_ctx* ctx, const float* host, size_t bytes) {
     if (!ctx || !host) return PT_ERR_INVALID;
     { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    if (!ctx->accum || bytes != 16 * (size_t)ctx->width * ctx->height) return fail(ctx, PT_ERR_INVALID, "pt_upload_accum: byte count does not match the frame size");
+    if (!ctx->fb.accum || bytes != 16 * (size_t)ctx->width * ctx->height) return fail(ctx, PT_ERR_INVALID, "pt_upload_accum: byte count does not match the frame size");
     CK(hipSetDevice(ctx->device));
-    CK(hipMemcpy(ctx->accum, host, bytes, hipMemcpyHostToDevice));
+    CK(hipMemcpy(ctx->fb.accum, host, bytes, hipMemcpyHostToDevice));
     return PT_OK;
 }
 
@@ -2336,7 +2394,7 @@ extern "C" int pt_tonemap_sqrt(pt_ctx* ctx, uint32_t* host_rgba8) {
     if (ctx->width == 0) return PT_OK;
     CK(hipSetDevice(ctx->device));
     const uint32_t n = (uint32_t)ctx->width * ctx->height;
-    hipLaunchKernelGGL(k_tonemap_sqrt, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->accum, ctx->frame, n);
+    hipLaunchKernelGGL(k_tonemap_sqrt, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->fb.accum, ctx->fb.frame, n);
     CK(hipStreamSynchronize(ctx->stream));
     if (host_rgba8) return pt_download(ctx, PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)n);
     return PT_OK;
@@ -2353,32 +2411,33 @@ extern "C" int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, uint32_t* h
     if (prm->epilogue < 0 || prm->epilogue > 2) return fail(ctx, PT_ERR_INVALID, "pt_denoise: unknown epilogue");
     CK(hipSetDevice(ctx->device));
     const size_t n = (size_t)ctx->width * ctx->height;
-    if (!ctx->denoised) {
-        CK(dalloc(&ctx->denoised, n));
-        CK(dalloc(&ctx->denoise_tmp, n));
+    if (!ctx->fb.denoise_tmp) { // (the second of the pair: both or neither)
+        ctx->fb.mem.drop(ctx->fb.denoised);
+        CK(ctx->fb.mem.alloc(&ctx->fb.denoised, n));
+        CK(ctx->fb.mem.alloc(&ctx->fb.denoise_tmp, n));
     }
-    DevScope tmp;
+    DevOwner tmp;
     hipEvent_t e0, e1;
     CK(tmp.event(&e0));
     CK(tmp.event(&e1));
-    const float4* src = prm->input == PT_BUF_COLOR ? ctx->color : ctx->accum;
+    const float4* src = prm->input == PT_BUF_COLOR ? ctx->fb.color : ctx->fb.accum;
     CK(hipEventRecord(e0, ctx->stream));
-    if (prm->iterations == 0) CK(hipMemcpyAsync(ctx->denoised, src, sizeof(float4) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    if (prm->iterations == 0) CK(hipMemcpyAsync(ctx->fb.denoised, src, sizeof(float4) * n, hipMemcpyDeviceToDevice, ctx->stream));
     // ping-pong so that the last pass lands in `denoised`
-    float4* bufs[2] = {ctx->denoised, ctx->denoise_tmp};
+    float4* bufs[2] = {ctx->fb.denoised, ctx->fb.denoise_tmp};
     int cur = (prm->iterations & 1) ? 0 : 1;
     const dim3 grid((ctx->width + 31) / 32, (ctx->height + 7) / 8), block(256);
     for (int i = 0; i < prm->iterations; ++i) {
         const float sc = prm->sigma_color / (float)(1 << i), sn = prm->sigma_normal * (float)(1 << i);
         AtrousParams ap{ctx->width, ctx->height, 1 << i, 1.0f / (sc * sc), 1.0f / (sn * sn), 1.0f / (prm->sigma_albedo * prm->sigma_albedo)};
-        hipLaunchKernelGGL(k_atrous, grid, block, 0, ctx->stream, src, ctx->normal, ctx->albedo, bufs[cur], ap);
+        hipLaunchKernelGGL(k_atrous, grid, block, 0, ctx->stream, src, ctx->fb.normal, ctx->fb.albedo, bufs[cur], ap);
         src = bufs[cur];
         cur ^= 1;
     }
     if (prm->epilogue == 1)
-        hipLaunchKernelGGL(k_tonemap_sqrt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->denoised, ctx->frame, (uint32_t)n);
+        hipLaunchKernelGGL(k_tonemap_sqrt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->fb.denoised, ctx->fb.frame, (uint32_t)n);
     else if (prm->epilogue == 2)
-        hipLaunchKernelGGL(k_make_color, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->denoised, ctx->frame, (uint32_t)n);
+        hipLaunchKernelGGL(k_make_color, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->fb.denoised, ctx->fb.frame, (uint32_t)n);
     CK(hipEventRecord(e1, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());
@@ -2430,7 +2489,7 @@ static int pack_async_enqueue(pt_ctx* ctx, int which, void* dev_dst, int slot) {
     if (nf >= 0) CK(hipStreamWaitEvent(ctx->stream, ctx->fr[nf].ev_end, 0)); // the newest frame enqueued; earlier ones end before it writes the buffers
     int rc = pack_launch(ctx, which, dev_dst);
     if (rc != PT_OK) return rc;
-    if (!ctx->ev_packed[slot]) CK(hipEventCreateWithFlags(&ctx->ev_packed[slot], hipEventDisableTiming));
+    if (!ctx->ev_packed[slot]) CK(ctx->misc.event(&ctx->ev_packed[slot], hipEventDisableTiming));
     CK(hipEventRecord(ctx->ev_packed[slot], ctx->stream));
     ctx->ev_pack_guard = ctx->ev_packed[slot];
     return PT_OK;
@@ -2451,18 +2510,20 @@ static int unpack_display_enqueue(pt_ctx* ctx, int which, const void* dev_src_al
     if (!elem || ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_unpack_display: unknown buffer or not resized");
     CK(hipSetDevice(ctx->device));
     const size_t npx = (size_t)ctx->width * ctx->height;
-    if (!ctx->display[which]) {
-        CK(hipMalloc(&ctx->display[which], npx * elem));
-        CK(hipMemsetAsync(ctx->display[which], 0, npx * elem, ctx->stream));
+    if (!ctx->fb.display[which]) {
+        uint8_t* d = nullptr;
+        CK(ctx->fb.mem.alloc(&d, npx * elem));
+        CK(hipMemsetAsync(d, 0, npx * elem, ctx->stream));
+        ctx->fb.display[which] = d;
     }
     const uint32_t n = ctx->padded * (uint32_t)ctx->world;
     if (n) {
         if (elem == 16)
-            hipLaunchKernelGGL((k_unpack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float4*)ctx->display[which], ctx->d_all_pixels, n, ctx->width, (const float4*)dev_src_all);
+            hipLaunchKernelGGL((k_unpack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float4*)ctx->fb.display[which], ctx->fb.d_all_pixels, n, ctx->width, (const float4*)dev_src_all);
         else
-            hipLaunchKernelGGL((k_unpack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)ctx->display[which], ctx->d_all_pixels, n, ctx->width, (const uint32_t*)dev_src_all);
+            hipLaunchKernelGGL((k_unpack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)ctx->fb.display[which], ctx->fb.d_all_pixels, n, ctx->width, (const uint32_t*)dev_src_all);
     }
-    if (!ctx->ev_displayed) CK(hipEventCreateWithFlags(&ctx->ev_displayed, hipEventDisableTiming));
+    if (!ctx->ev_displayed) CK(ctx->misc.event(&ctx->ev_displayed, hipEventDisableTiming));
     CK(hipEventRecord(ctx->ev_displayed, ctx->stream));
     return PT_OK;
 }
@@ -2479,16 +2540,16 @@ extern "C" int pt_display_sync(pt_ctx* ctx) {
 }
 extern "C" void* pt_display_buffer(pt_ctx* ctx, int which) {
     if (!ctx || which < 0 || which > PT_BUF_DENOISED) return nullptr;
-    return ctx->display[which];
+    return ctx->fb.display[which];
 }
 extern "C" int pt_download_display(pt_ctx* ctx, int which, void* host, size_t bytes) {
     if (!ctx || !host) return PT_ERR_INVALID;
     const size_t elem = buffer_elem(which);
-    if (!elem || !ctx->display[which]) return fail(ctx, PT_ERR_INVALID, "pt_download_display: nothing has been handed over into this buffer");
+    if (!elem || !ctx->fb.display[which]) return fail(ctx, PT_ERR_INVALID, "pt_download_display: nothing has been handed over into this buffer");
     if (bytes != elem * (size_t)ctx->width * ctx->height) return fail(ctx, PT_ERR_INVALID, "pt_download_display: byte count does not match the frame size");
     int rc = pt_display_sync(ctx);
     if (rc != PT_OK) return rc;
-    CK(hipMemcpy(host, ctx->display[which], bytes, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(host, ctx->fb.display[which], bytes, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -2501,9 +2562,9 @@ static int pack_launch(pt_ctx* ctx, int which, void* dev_dst) {
     const uint32_t n = ctx->owned;
     if (n) {
         if (elem == 16)
-            hipLaunchKernelGGL((k_pack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)p, ctx->d_pixels, n, ctx->width, (float4*)dev_dst);
+            hipLaunchKernelGGL((k_pack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)p, ctx->fb.d_pixels, n, ctx->width, (float4*)dev_dst);
         else
-            hipLaunchKernelGGL((k_pack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)p, ctx->d_pixels, n, ctx->width, (uint32_t*)dev_dst);
+            hipLaunchKernelGGL((k_pack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)p, ctx->fb.d_pixels, n, ctx->width, (uint32_t*)dev_dst);
     }
     return PT_OK;
 }
@@ -2516,9 +2577,9 @@ static int unpack_launch(pt_ctx* ctx, int which, const void* dev_src_all) {
     const uint32_t n = ctx->padded * (uint32_t)ctx->world;
     if (n) {
         if (elem == 16)
-            hipLaunchKernelGGL((k_unpack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float4*)p, ctx->d_all_pixels, n, ctx->width, (const float4*)dev_src_all);
+            hipLaunchKernelGGL((k_unpack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float4*)p, ctx->fb.d_all_pixels, n, ctx->width, (const float4*)dev_src_all);
         else
-            hipLaunchKernelGGL((k_unpack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)p, ctx->d_all_pixels, n, ctx->width, (const uint32_t*)dev_src_all);
+            hipLaunchKernelGGL((k_unpack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)p, ctx->fb.d_all_pixels, n, ctx->width, (const uint32_t*)dev_src_all);
     }
     return PT_OK;
 }
@@ -2563,7 +2624,7 @@ extern "C" int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit,
     CK(hipSetDevice(ctx->device));
     if (iters < 1) iters = 1;
     // temporary state just for the query
-    DevScope tmp;
+    DevOwner tmp;
     float4 *dO = nullptr, *dD = nullptr;
     float2* dHit = nullptr;
     uint32_t *dCount = nullptr, *dWork = nullptr;
@@ -2591,7 +2652,7 @@ extern "C" int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit,
         CK(dclear(ctx->stream, dDbg, 512));
     }
     CK(hipMemsetAsync(dWork, 0, sizeof(uint32_t) * iters, ctx->stream));
-    CK(hipMemsetAsync(ctx->d_totals + 2, 0, sizeof(unsigned long long), ctx->stream));
+    CK(hipMemsetAsync(ctx->tot.d_totals + 2, 0, sizeof(unsigned long long), ctx->stream));
     CK(hipEventRecord(e0, ctx->stream));
     for (int it = 0; it < iters; ++it) {
         {
@@ -2611,7 +2672,7 @@ extern "C" int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit,
     if (kernel_ms) *kernel_ms = ms / iters;
     {
         unsigned long long fault = 0;
-        CK(hipMemcpy(&fault, ctx->d_totals + 2, sizeof(fault), hipMemcpyDeviceToHost));
+        CK(hipMemcpy(&fault, ctx->tot.d_totals + 2, sizeof(fault), hipMemcpyDeviceToHost));
         if (fault & 1ull) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_trace: traversal stack overflow: the acceleration structure is deeper than the traversal stack");
     }
     if (dDbg) {
@@ -2694,14 +2755,15 @@ static const size_t PT_QUERY_BLOCK = sizeof(QueryCounters) + 128; // the counter
 static int query_reserve(pt_ctx* ctx, uint32_t n) {
     pt_ctx::Query& q = ctx->q;
     if (!q.block) {
+        DevOwner fresh;
         uint8_t* block = nullptr;
         QueryCounters* h = nullptr;
-        CK(dalloc(&block, PT_QUERY_BLOCK));
-        if (hipHostMalloc((void**)&h, sizeof(QueryCounters)) != hipSuccess) {
+        CK(fresh.alloc(&block, PT_QUERY_BLOCK));
+        if (fresh.pinned(&h, 1) != hipSuccess) {
             (void)hipGetLastError();
-            dfree(block);
             return fail(ctx, PT_ERR_HIP, "pt_trace_device: out of pinned host memory for the counters");
         }
+        q.mem.adopt(std::move(fresh));
         q.block = block;
         q.h_counters = h;
         q.bytes += PT_QUERY_BLOCK;
@@ -2709,23 +2771,23 @@ static int query_reserve(pt_ctx* ctx, uint32_t n) {
     if (n > q.cap) {
         // queued queries still use the old arrays: they finish first (only a query larger than every one before it comes here)
         { int rc_ = query_complete(ctx); if (rc_ != PT_OK) return rc_; }
+        DevOwner grown; // allocated aside and moved in: a failure leaves the smaller state as it was (the query state is small)
         float4 *o = nullptr, *d = nullptr;
         float2* h = nullptr;
         unsigned long long* m = nullptr;
         const size_t words = ((size_t)n + 63) / 64;
-        if (dalloc(&o, n) != hipSuccess || dalloc(&d, n) != hipSuccess || dalloc(&h, n) != hipSuccess || dalloc(&m, words) != hipSuccess) {
+        if (grown.alloc(&o, n) != hipSuccess || grown.alloc(&d, n) != hipSuccess || grown.alloc(&h, n) != hipSuccess || grown.alloc(&m, words) != hipSuccess) {
             (void)hipGetLastError();
-            dfree(o); dfree(d); dfree(h); dfree(m);
             return fail(ctx, PT_ERR_HIP, "pt_trace_device: out of device memory for the query state");
         }
-        dfree(q.rayO); dfree(q.rayD); dfree(q.hit); dfree(q.mark);
+        q.rays = std::move(grown);
         q.rayO = o; q.rayD = d; q.hit = h; q.mark = m;
         q.cap = n;
         q.bytes = PT_QUERY_BLOCK + (size_t)n * (2 * sizeof(float4) + sizeof(float2)) + words * sizeof(unsigned long long);
     }
     while (q.events.size() < 4 * ((size_t)q.pending + 1)) {
-        hipEvent_t e;
-        CK(hipEventCreate(&e));
+        hipEvent_t e = nullptr;
+        CK(q.mem.event(&e));
         q.events.push_back(e);
     }
     return PT_OK;
@@ -2788,7 +2850,7 @@ extern "C" int pt_trace_device(pt_ctx* ctx, const float* dev_rays, uint32_t n, u
         if (any_hit) hipLaunchKernelGGL((k_trace8<TR_ANY_QUERY>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
         else hipLaunchKernelGGL((k_trace8<TR_CLOSEST>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
         CK(hipEventRecord(e[2], ctx->stream));
-        hipLaunchKernelGGL(k_hit_attributes, dim3(sgrid), dim3(256), 0, ctx->stream, q.hit, q.rayO, q.rayD, q.mark, ctx->bvh.tris8, ctx->d_tri_nrm, n, (int)any_hit,
+        hipLaunchKernelGGL(k_hit_attributes, dim3(sgrid), dim3(256), 0, ctx->stream, q.hit, q.rayO, q.rayD, q.mark, ctx->bvh.tris8, ctx->sc.d_tri_nrm, n, (int)any_hit,
                            (int)((reinterpret_cast<uintptr_t>(dev_out) & 15u) == 0), dev_out, counters);
         CK(hipEventRecord(e[3], ctx->stream));
         CK(hipGetLastError());
@@ -2831,8 +2893,9 @@ extern "C" int pt_set_views(pt_ctx* ctx, const pt_view* views, uint32_t n) {
     }
     CK(hipSetDevice(ctx->device));
     CK(hipStreamSynchronize(ctx->stream));
-    free_blocks(ctx); // the block spans follow the frame's pixel list; implies pt_adaptive_end
-    free_views(ctx);
+    ctx->ad = pt_ctx::Adaptive{}; // the block spans follow the frame's pixel list; implies pt_adaptive_end
+    ctx->blk = pt_ctx::Blocks{};
+    ctx->vw = pt_ctx::Views{};
     ctx->sched_pending.valid = false;
     if (n == 0) return PT_OK;
     // the view pixel list in the order of build_pixel_lists: whole blocks, block order kept, only pixels inside their view, only owned blocks
@@ -2854,15 +2917,15 @@ extern "C" int pt_set_views(pt_ctx* ctx, const pt_view* views, uint32_t n) {
     V.vblock = vblock;
     V.owned = (uint32_t)list.size();
     int rc = PT_OK;
-    hipError_t e = dalloc(&V.d_views, (size_t)n);
-    if (e == hipSuccess) e = dalloc(&V.d_vblock, vblock.size());
-    if (e == hipSuccess) e = dalloc(&V.d_pixels, list.size());
+    hipError_t e = V.mem.alloc(&V.d_views, (size_t)n);
+    if (e == hipSuccess) e = V.mem.alloc(&V.d_vblock, vblock.size());
+    if (e == hipSuccess) e = V.mem.alloc(&V.d_pixels, list.size());
     if (e == hipSuccess) e = hipMemcpy(V.d_views, V.host.data(), sizeof(pt_view) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(V.d_vblock, vblock.data(), sizeof(uint16_t) * vblock.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && !list.empty()) e = hipMemcpy(V.d_pixels, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         ctx->err = std::string("pt_set_views: ") + hipGetErrorString(e);
-        free_views(ctx); // all of it or nothing
+        ctx->vw = pt_ctx::Views{}; // all of it or nothing
         rc = PT_ERR_HIP;
     } else {
         V.n = n;
@@ -2922,12 +2985,12 @@ extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void*
     {
         int rc = drain(ctx);
         if (rc) return rc;
-        Node80* tmp80 = nullptr;
-        CK(hipMalloc((void**)&tmp80, nodes_bytes));
-        hipLaunchKernelGGL(k_nodes_to80, dim3((ctx->bvh.num_nodes8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.nodes8, ctx->bvh.num_nodes8, ctx->bvh.grid, tmp80);
+        DevOwner tmp;
+        uint8_t* tmp80 = nullptr;
+        CK(tmp.alloc(&tmp80, nodes_bytes));
+        hipLaunchKernelGGL(k_nodes_to80, dim3((ctx->bvh.num_nodes8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.nodes8, ctx->bvh.num_nodes8, ctx->bvh.grid, reinterpret_cast<Node80*>(tmp80));
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) e = hipMemcpy(nodes, tmp80, nodes_bytes, hipMemcpyDeviceToHost);
-        hipFree(tmp80);
         CK(e);
     }
 #else
@@ -2943,6 +3006,7 @@ extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void*
 // with its side arrays — without touching the context; update_commit then refits in place or swaps the new tree in, and only a failing HIP
 // runtime can stop it half way.
 struct MeshUpdate {
+    DevOwner mem;           // the arrays below, until update_commit hands them to the scene
     float* d_new = nullptr; // the whole vertex array with the updated meshes
     PtBvh nb;               // PT_UPDATE_REBUILD: the new tree and its side arrays
     float4* nrm = nullptr;
@@ -2952,7 +3016,7 @@ struct MeshUpdate {
     std::vector<std::pair<size_t, size_t>> explicit_ranges; // (first float, floats) of the meshes given explicitly: they become rest positions too
     double stage_ms = 0;    // k_stage_vertices
     std::vector<uint8_t> table; // its report word and segment table on the host: alive until the stream has been waited for
-    void discard() { dfree(d_new); pt_bvh_free(&nb); dfree(nrm); dfree(textris); dfree(rest); }
+    ~MeshUpdate() { pt_bvh_free(&nb); } // whatever was not committed
 };
 
 // What update_stage writes into the named meshes: host arrays (copied), device arrays or transforms (k_stage_vertices).
@@ -3038,13 +3102,13 @@ static int device_pointers_validate(pt_ctx* ctx, const pt_mesh_update* up, uint3
 // Enqueues k_stage_vertices for a device or transform source into U.d_new (which already holds the current vertices), its report word's
 // copy to pinned memory, and the events around the kernel.  Nothing of the context changes: the table and the word are scratch.
 static int stage_on_device(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hipEvent_t e0, hipEvent_t e1) {
-    const float* from = ctx->d_verts;
+    const float* from = ctx->sc.d_verts;
     if (S.xform) {
-        if (!ctx->d_rest) { // the first transform of the context: its rest positions are the vertices as they are now
-            CK(dalloc(&U.rest, 3 * ctx->nvert));
-            CK(hipMemcpyAsync(U.rest, ctx->d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
+        if (!ctx->sc.d_rest) { // the first transform of the context: its rest positions are the vertices as they are now
+            CK(U.mem.alloc(&U.rest, 3 * ctx->nvert));
+            CK(hipMemcpyAsync(U.rest, ctx->sc.d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
         } else if (S.from == PT_FROM_REST) {
-            from = ctx->d_rest;
+            from = ctx->sc.d_rest;
         }
     }
     const size_t bytes = 16 + sizeof(StageSeg) * (size_t)S.n; // the report word (in a 16-byte line of its own), then the table
@@ -3073,30 +3137,30 @@ static int stage_on_device(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hi
         waves += (g.count + PT_STAGE_CHUNK - 1) / PT_STAGE_CHUNK;
     }
     if (waves > 0xfffffffcull) { ctx->err = std::string(S.fn) + ": too many vertices for one call"; return PT_ERR_UNSUPPORTED; }
-    if (!ctx->h_stage_bad) CK(hipHostMalloc((void**)&ctx->h_stage_bad, sizeof(uint32_t)));
-    if (ctx->stage_cap < bytes) {
+    if (!ctx->sc.h_stage_bad) CK(ctx->sc.mem.pinned(&ctx->sc.h_stage_bad, 1));
+    if (ctx->sc.stage_cap < bytes) {
         uint8_t* grown = nullptr;
-        CK(dalloc(&grown, bytes));
-        dfree(ctx->d_stage);
-        ctx->d_stage = grown;
-        ctx->stage_cap = bytes;
+        CK(ctx->sc.mem.alloc(&grown, bytes));
+        ctx->sc.mem.drop(ctx->sc.d_stage);
+        ctx->sc.d_stage = grown;
+        ctx->sc.stage_cap = bytes;
     }
-    *ctx->h_stage_bad = PT_STAGE_NONE;
-    CK(hipMemcpyAsync(ctx->d_stage, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream)); 
+    *ctx->sc.h_stage_bad = PT_STAGE_NONE;
+    CK(hipMemcpyAsync(ctx->sc.d_stage, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream)); 
     CK(hipEventRecord(e0, ctx->stream));
     if (waves) {
-        hipLaunchKernelGGL(k_stage_vertices, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, ctx->stream, reinterpret_cast<const StageSeg*>(ctx->d_stage + 16), S.n,
-                           (uint32_t)waves, reinterpret_cast<uint32_t*>(ctx->d_stage));
+        hipLaunchKernelGGL(k_stage_vertices, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, ctx->stream, reinterpret_cast<const StageSeg*>(ctx->sc.d_stage + 16), S.n,
+                           (uint32_t)waves, reinterpret_cast<uint32_t*>(ctx->sc.d_stage));
         CK(hipGetLastError());
     }
     CK(hipEventRecord(e1, ctx->stream));
-    CK(hipMemcpyAsync(ctx->h_stage_bad, ctx->d_stage, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipMemcpyAsync(ctx->sc.h_stage_bad, ctx->sc.d_stage, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     return PT_OK;
 }
 
 // after a synchronisation of the stream: did k_stage_vertices write a non-finite coordinate?
 static int stage_verdict(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hipEvent_t e0, hipEvent_t e1) {
-    const uint32_t bad = *ctx->h_stage_bad;
+    const uint32_t bad = *ctx->sc.h_stage_bad;
     if (bad != PT_STAGE_NONE) {
         const uint32_t mesh = bad < S.n ? (S.xform ? S.xform[bad].mesh : S.dev[bad].mesh) : bad;
         ctx->err = std::string(S.fn) + ": non-finite coordinate in mesh " + std::to_string(mesh) + (S.xform ? " after the transform" : "");
@@ -3111,9 +3175,9 @@ static int stage_verdict(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hipE
 static int update_stage(pt_ctx* ctx, const UpdateSource& S, int mode, MeshUpdate& U) {
     { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames enqueued before the call render the old geometry
     CK(hipSetDevice(ctx->device));
-    CK(dalloc(&U.d_new, 3 * ctx->nvert));
-    CK(hipMemcpyAsync(U.d_new, ctx->d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
-    DevScope tmp;
+    CK(U.mem.alloc(&U.d_new, 3 * ctx->nvert));
+    CK(hipMemcpyAsync(U.d_new, ctx->sc.d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
+    DevOwner tmp;
     hipEvent_t s0 = nullptr, s1 = nullptr;
     if (S.host) {
         for (uint32_t k = 0; k < S.n; ++k) {
@@ -3142,15 +3206,15 @@ static int update_stage(pt_ctx* ctx, const UpdateSource& S, int mode, MeshUpdate
     CK(tmp.event(&e0));
     CK(tmp.event(&e1));
     CK(hipEventRecord(e0, ctx->stream));
-    CK(pt_bvh_build(U.d_new, ctx->d_idx, ctx->d_tri_mesh, ctx->ntri, ctx->stream, &U.nb));
+    CK(pt_bvh_build(U.d_new, ctx->sc.d_idx, ctx->sc.d_tri_mesh, ctx->ntri, ctx->stream, &U.nb));
     const uint32_t nt8 = U.nb.num_tris8;
-    CK(dalloc(&U.nrm, (size_t)nt8));
+    CK(U.mem.alloc(&U.nrm, (size_t)nt8));
     hipLaunchKernelGGL(k_shade_normals, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.nb.tris8, nt8, U.nrm);
-    if (ctx->d_textris) { // the texcoords per primitive, from the old tree's records, then the records in the new leaf order
+    if (ctx->sc.d_textris) { // the texcoords per primitive, from the old tree's records, then the records in the new leaf order
         PrimUV* uvs = nullptr;
         CK(tmp.alloc(&uvs, (size_t)ctx->ntri));
-        CK(dalloc(&U.textris, (size_t)nt8));
-        hipLaunchKernelGGL(k_textris_to_uvs, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->d_textris, ctx->bvh.num_tris8, uvs);
+        CK(U.mem.alloc(&U.textris, (size_t)nt8));
+        hipLaunchKernelGGL(k_textris_to_uvs, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->sc.d_textris, ctx->bvh.num_tris8, uvs);
         hipLaunchKernelGGL(k_emit_textris, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.nb.tris8, uvs, nt8, U.textris);
     }
     CK(hipGetLastError());
@@ -3167,31 +3231,25 @@ static int update_stage(pt_ctx* ctx, const UpdateSource& S, int mode, MeshUpdate
     return PT_OK;
 }
 
-static int update_stage(pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, MeshUpdate& U) {
-    UpdateSource S{"pt_update_meshes"};
-    S.host = up;
-    S.n = n;
-    return update_stage(ctx, S, mode, U);
-}
 
 static int update_commit(pt_ctx* ctx, int mode, MeshUpdate& U, double* kernel_ms) {
     CK(hipSetDevice(ctx->device));
     double ms = U.build_ms;
-    if (ctx->d_rest && !U.explicit_ranges.empty()) { // positions given explicitly are rest positions from now on
+    if (ctx->sc.d_rest && !U.explicit_ranges.empty()) { // positions given explicitly are rest positions from now on
         for (const auto& r : U.explicit_ranges)
-            CK(hipMemcpyAsync(ctx->d_rest + r.first, U.d_new + r.first, sizeof(float) * r.second, hipMemcpyDeviceToDevice, ctx->stream));
+            CK(hipMemcpyAsync(ctx->sc.d_rest + r.first, U.d_new + r.first, sizeof(float) * r.second, hipMemcpyDeviceToDevice, ctx->stream));
         if (mode != PT_UPDATE_REFIT) CK(hipStreamSynchronize(ctx->stream)); // (the refit below waits)
     }
     if (mode == PT_UPDATE_REFIT) {
-        DevScope tmp;
+        DevOwner tmp;
         hipEvent_t e0, e1;
         CK(tmp.event(&e0));
         CK(tmp.event(&e1));
         CK(hipEventRecord(e0, ctx->stream));
-        CK(pt_bvh_refit_begin(&ctx->bvh, U.d_new, ctx->d_idx, ctx->ntri, ctx->stream));
+        CK(pt_bvh_refit_begin(&ctx->bvh, U.d_new, ctx->sc.d_idx, ctx->ntri, ctx->stream));
         const uint32_t nt8 = ctx->bvh.num_tris8;
-        hipLaunchKernelGGL(k_refit_leaves, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.d_new, ctx->d_idx, nt8, const_cast<LeafTri*>(ctx->bvh.tris8),
-                           ctx->d_tri_nrm, ctx->d_textris);
+        hipLaunchKernelGGL(k_refit_leaves, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.d_new, ctx->sc.d_idx, nt8, const_cast<LeafTri*>(ctx->bvh.tris8),
+                           ctx->sc.d_tri_nrm, ctx->sc.d_textris);
         CK(hipGetLastError());
         CK(pt_bvh_refit_nodes(&ctx->bvh, ctx->stream));
         CK(hipEventRecord(e1, ctx->stream));
@@ -3203,38 +3261,37 @@ static int update_commit(pt_ctx* ctx, int mode, MeshUpdate& U, double* kernel_ms
         pt_bvh_free(&ctx->bvh);
         ctx->bvh = std::move(U.nb);
         U.nb = PtBvh{};
-        dfree(ctx->d_tri_nrm);
-        ctx->d_tri_nrm = U.nrm;
-        U.nrm = nullptr;
+        ctx->sc.mem.drop(ctx->sc.d_tri_nrm);
+        ctx->sc.d_tri_nrm = U.nrm;
         if (U.textris) {
-            dfree(ctx->d_textris);
-            ctx->d_textris = U.textris;
-            U.textris = nullptr;
+            ctx->sc.mem.drop(ctx->sc.d_textris);
+            ctx->sc.d_textris = U.textris;
         }
         ctx->bvh_build_ms = U.build_ms;
     }
-    dfree(ctx->d_verts);
-    ctx->d_verts = U.d_new;
-    U.d_new = nullptr;
-    if (U.rest) {
-        ctx->d_rest = U.rest;
-        U.rest = nullptr;
-    }
+    ctx->sc.mem.drop(ctx->sc.d_verts);
+    ctx->sc.d_verts = U.d_new;
+    if (U.rest) ctx->sc.d_rest = U.rest;
+    ctx->sc.mem.adopt(std::move(U.mem)); // the scene owns the new arrays from here on
     ctx->sched = pt_ctx::Sched{}; // the tree's traversal cost changed: the chain/fused trial starts over
     if (kernel_ms) *kernel_ms = ms + U.stage_ms;
     return PT_OK;
 }
 
+static int update_run(pt_ctx* ctx, const UpdateSource& S, int mode, double* kernel_ms) {
+    MeshUpdate U; // what is not committed goes with it
+    const int rc = update_stage(ctx, S, mode, U);
+    return rc == PT_OK ? update_commit(ctx, mode, U, kernel_ms) : rc;
+}
 extern "C" int pt_update_meshes(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
     if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_update_meshes: null context");
     std::string err;
     int rc = update_validate(ctx, updates, n, mode, err);
     if (rc != PT_OK) return fail(ctx, rc, err.c_str());
-    MeshUpdate U;
-    rc = update_stage(ctx, updates, n, mode, U);
-    if (rc == PT_OK) rc = update_commit(ctx, mode, U, kernel_ms);
-    U.discard();
-    return rc;
+    UpdateSource S{"pt_update_meshes"};
+    S.host = updates;
+    S.n = n;
+    return update_run(ctx, S, mode, kernel_ms);
 }
 
 extern "C" int pt_update_meshes_device(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
@@ -3246,11 +3303,7 @@ extern "C" int pt_update_meshes_device(pt_ctx* ctx, const pt_mesh_update* update
     UpdateSource S{"pt_update_meshes_device"};
     S.dev = updates;
     S.n = n;
-    MeshUpdate U;
-    rc = update_stage(ctx, S, mode, U);
-    if (rc == PT_OK) rc = update_commit(ctx, mode, U, kernel_ms);
-    U.discard();
-    return rc;
+    return update_run(ctx, S, mode, kernel_ms);
 }
 
 extern "C" int pt_transform_meshes(pt_ctx* ctx, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms) {
@@ -3262,11 +3315,7 @@ extern "C" int pt_transform_meshes(pt_ctx* ctx, const pt_mesh_transform* t, uint
     S.xform = t;
     S.from = source;
     S.n = n;
-    MeshUpdate U;
-    rc = update_stage(ctx, S, mode, U);
-    if (rc == PT_OK) rc = update_commit(ctx, mode, U, kernel_ms);
-    U.discard();
-    return rc;
+    return update_run(ctx, S, mode, kernel_ms);
 }
 
 extern "C" int pt_download_vertices(pt_ctx* ctx, uint32_t mesh, int rest, float* host, size_t bytes) {
@@ -3277,7 +3326,7 @@ extern "C" int pt_download_vertices(pt_ctx* ctx, uint32_t mesh, int rest, float*
     if (bytes != sizeof(float) * 3 * (size_t)ctx->mesh_nv[mesh]) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: bytes must equal num_vertices * 12");
     if (bytes == 0) return PT_OK;
     CK(hipSetDevice(ctx->device));
-    const float* from = rest && ctx->d_rest ? ctx->d_rest : ctx->d_verts; // before the first transform the vertices are their own rest positions
+    const float* from = rest && ctx->sc.d_rest ? ctx->sc.d_rest : ctx->sc.d_verts; // before the first transform the vertices are their own rest positions
     CK(hipMemcpy(host, from + 3 * (size_t)ctx->mesh_vbase[mesh], bytes, hipMemcpyDeviceToHost));
     return PT_OK;
 }
@@ -3288,10 +3337,10 @@ extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material
     static const int in_w[9] = {11, 9, 1, 3, 3, 3, 2, 2, 3}, out_w[9] = {4, 6, 9, 6, 1, 1, 8, 4, 1};
     if (which < 0 || which > 8) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: unknown table");
     if (which <= 1 && !material) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: material required");
-    if ((which == 2 || which == 3 || which == 8) && !ctx->probe.data) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: no probe set");
-    if (which == 7 && !ctx->tex0.pixel) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: the scene has no texture");
+    if ((which == 2 || which == 3 || which == 8) && !ctx->pr.dev.data) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: no probe set");
+    if (which == 7 && !ctx->sc.tex0.pixel) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: the scene has no texture");
     CK(hipSetDevice(ctx->device));
-    DevScope tmp;
+    DevOwner tmp;
     float *dIn = nullptr, *dOut = nullptr;
     CK(tmp.alloc(&dIn, (size_t)n * in_w[which]));
     CK(tmp.alloc(&dOut, (size_t)n * out_w[which]));
@@ -3308,13 +3357,13 @@ extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material
             if (bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_table_sample<PT_BSDF_LAMBERT>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
             else hipLaunchKernelGGL((k_table_sample<PT_BSDF_DISNEY>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
             break;
-        case 2: hipLaunchKernelGGL(k_table_probe_sample, g, b, 0, ctx->stream, ctx->probe, dIn, n, dOut); break;
-        case 3: hipLaunchKernelGGL(k_table_probe_eval, g, b, 0, ctx->stream, ctx->probe, dIn, n, dOut); break;
+        case 2: hipLaunchKernelGGL(k_table_probe_sample, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
+        case 3: hipLaunchKernelGGL(k_table_probe_eval, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
         case 4: hipLaunchKernelGGL(k_table_color, g, b, 0, ctx->stream, dIn, n, dOut); break;
         case 5: hipLaunchKernelGGL(k_table_math, g, b, 0, ctx->stream, dIn, n, dOut); break;
         case 6: hipLaunchKernelGGL(k_table_rng, g, b, 0, ctx->stream, dIn, n, dOut); break;
-        case 7: hipLaunchKernelGGL(k_table_tex, g, b, 0, ctx->stream, ctx->tex0, dIn, n, dOut); break;
-        case 8: hipLaunchKernelGGL(k_table_probe_pdf, g, b, 0, ctx->stream, ctx->probe, dIn, n, dOut); break;
+        case 7: hipLaunchKernelGGL(k_table_tex, g, b, 0, ctx->stream, ctx->sc.tex0, dIn, n, dOut); break;
+        case 8: hipLaunchKernelGGL(k_table_probe_pdf, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
     }
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());
@@ -3388,40 +3437,9 @@ Rccl& rccl() {
 thread_local std::string g_multi_error;
 } // namespace
 
-namespace {
-// One host thread per rank (pt_multi): a frame is ~60 launches and events per device, so enqueueing the devices one after the other
-// from one thread costs ndev x (60 x 5-8 us) — at a 1/8 share of a 1080p frame (1.3-1.8 ms of GPU work) more than the frame itself.
-// Every rank's thread enqueues its own device; the calling thread posts a job to each and waits for all.
-struct RankWorker {
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::function<int()> job;
-    bool has_job = false, done = false, quit = false;
-    int rc = PT_OK;
-    double ms = 0; // host time of the last job
-};
-void rank_worker_main(RankWorker* w, int device) {
-    (void)hipSetDevice(device);
-    std::unique_lock<std::mutex> lk(w->mu);
-    for (;;) {
-        w->cv.wait(lk, [&] { return w->has_job || w->quit; });
-        if (w->quit) return;
-        std::function<int()> job = std::move(w->job);
-        w->has_job = false;
-        lk.unlock();
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = job();
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        lk.lock();
-        w->rc = rc;
-        w->ms = ms;
-        w->done = true;
-        w->cv.notify_all();
-    }
-}
-} // namespace
-
+// One host thread per rank (pt_multi, an EnqueueWorker each): a frame is ~60 launches and events per device, so enqueueing the devices one
+// after the other from one thread costs ndev x (60 x 5-8 us) — at a 1/8 share of a 1080p frame (1.3-1.8 ms of GPU work) more than the frame
+// itself.  Every rank's thread enqueues its own device; the calling thread posts a job to each and waits for all.
 struct pt_multi {
     std::vector<pt_ctx*> ctx;
     std::vector<int> devices;
@@ -3429,17 +3447,21 @@ struct pt_multi {
     bool distinct = true;           // no device appears twice (RCCL's requirement)
     std::vector<ncclComm_t> comms;  // per rank (empty until the first RCCL gather)
     int exchange_pref = 0;          // PT_MULTI_EXCHANGE: 0 auto, 1 rccl, 2 peer copies
-    std::vector<void*> send, recv;  // per rank: padded * 16 bytes, world * padded * 16 bytes (the synchronous pt_multi_gather)
-    uint32_t padded = 0;
+    // The exchange strips of the current frame size: freed and rebuilt by pt_multi_resize.  send.empty(): not resized.
+    struct Strips { std::vector<uint8_t*> send, recv; };
+    struct Exchange {
+        std::vector<DevOwner> mem;      // per rank: what the rank's device holds of the arrays and events below
+        std::vector<uint8_t*> send, recv; // per rank: padded * 16 bytes, world * padded * 16 bytes (the synchronous pt_multi_gather)
+        uint32_t padded = 0;
+        Strips hand[2][6];              // the overlapped hand-off (below): [slot][pt_buffer], allocated on first use
+        std::vector<hipEvent_t> xfer_done[2]; // peer-copy exchange: rank r's copies of slot s are complete
+    } ex;
     double gather_ms = 0;
     int last_exchange = PT_EXCHANGE_NONE;
-    std::vector<std::unique_ptr<RankWorker>> workers; // empty: single rank or PT_MULTI_THREADS=0 (everything on the calling thread)
+    std::vector<std::unique_ptr<EnqueueWorker>> workers; // empty: single rank or PT_MULTI_THREADS=0 (everything on the calling thread)
     double enqueue_ms = 0;          // host time of the enqueue phase of the last render: the slowest rank's
     // Overlapped hand-off (frames in flight + a gather mask): frame k's strips are packed behind frame k (pt_pack_async) into the
     // buffers of slot k & 1 and exchanged + scattered into the ranks' DISPLAY buffers by the NEXT render call, while frame k+1 renders.
-    struct Strips { std::vector<void*> send, recv; };
-    Strips hand[2][6];              // [slot][pt_buffer], allocated on first use
-    std::vector<hipEvent_t> xfer_done[2]; // peer-copy exchange: rank r's copies of slot s are complete
     int pending_slot = -1;          // slot whose strips are packed (or being packed) but not yet exchanged
     uint32_t pending_mask = 0;
     uint64_t handed = 0;            // frames handed over through the overlapped path
@@ -3466,35 +3488,27 @@ extern "C" int pt_multi_size(const pt_multi* m) { return m ? (int)m->ctx.size() 
 extern "C" pt_ctx* pt_multi_ctx(pt_multi* m, int rank) { return (m && rank >= 0 && rank < (int)m->ctx.size()) ? m->ctx[rank] : nullptr; }
 
 static int multi_present_pending(pt_multi* m, bool wait);
-static void multi_free_exchange(pt_multi* m) {
+// the communicators: made by the first RCCL exchange
+static int multi_comms(pt_multi* m) {
+    if (!m->comms.empty()) return PT_OK;
+    m->comms.assign(m->ctx.size(), nullptr);
+    const ncclResult_t e = rccl().CommInitAll(m->comms.data(), (int)m->ctx.size(), m->devices.data());
+    if (e == ncclSuccess) return PT_OK;
+    m->comms.clear();
+    return mfail(m, PT_ERR_HIP, std::string("ncclCommInitAll: ") + rccl().GetErrorString(e));
+}
+static void multi_unset_exchange(pt_multi* m) {
     for (size_t r = 0; r < m->ctx.size(); ++r) { // pending packs / exchanges run on the contexts' streams
         hipSetDevice(m->devices[r]);
         if (m->ctx[r] && m->ctx[r]->stream) hipStreamSynchronize(m->ctx[r]->stream);
     }
-    for (size_t r = 0; r < m->send.size(); ++r) {
+    for (size_t r = 0; r < m->ex.mem.size(); ++r) {
         hipSetDevice(m->devices[r]);
-        if (m->send[r]) hipFree(m->send[r]);
-        if (m->recv[r]) hipFree(m->recv[r]);
+        m->ex.mem[r].release();
     }
-    m->send.clear();
-    m->recv.clear();
-    for (int sl = 0; sl < 2; ++sl) {
-        for (auto& st : m->hand[sl]) {
-            for (size_t r = 0; r < st.send.size(); ++r) {
-                hipSetDevice(m->devices[r]);
-                if (st.send[r]) hipFree(st.send[r]);
-                if (st.recv[r]) hipFree(st.recv[r]);
-            }
-            st.send.clear();
-            st.recv.clear();
-        }
-        for (hipEvent_t e : m->xfer_done[sl])
-            if (e) hipEventDestroy(e);
-        m->xfer_done[sl].clear();
-    }
+    m->ex = pt_multi::Exchange{};
     m->pending_slot = -1;
     m->pending_mask = 0;
-    m->padded = 0;
 }
 
 // fn(rank) for every rank, concurrently on the ranks' threads (or one after the other on the calling thread); returns the first
@@ -3510,20 +3524,10 @@ static int multi_run(pt_multi* m, const std::function<int(int)>& fn, const char*
             slow += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); // serial: the times add up
         }
     } else {
+        for (int r = 0; r < world; ++r) enqueue_worker_post(m->workers[r].get(), [&fn, r] { return fn(r); });
         for (int r = 0; r < world; ++r) {
-            RankWorker& w = *m->workers[r];
-            std::lock_guard<std::mutex> lk(w.mu);
-            w.job = [&fn, r] { return fn(r); };
-            w.has_job = true;
-            w.done = false;
-            w.cv.notify_all();
-        }
-        for (int r = 0; r < world; ++r) {
-            RankWorker& w = *m->workers[r];
-            std::unique_lock<std::mutex> lk(w.mu);
-            w.cv.wait(lk, [&] { return w.done; });
-            rcs[r] = w.rc;
-            slow = std::max(slow, w.ms);
+            rcs[r] = enqueue_worker_wait(m->workers[r].get());
+            slow = std::max(slow, m->workers[r]->ms); // (written before `done`, which the wait has seen)
         }
     }
     if (max_ms) *max_ms = slow;
@@ -3534,16 +3538,9 @@ static int multi_run(pt_multi* m, const std::function<int(int)>& fn, const char*
 
 extern "C" int pt_multi_destroy(pt_multi* m) {
     if (!m) return PT_OK;
-    for (auto& w : m->workers) {
-        {
-            std::lock_guard<std::mutex> lk(w->mu);
-            w->quit = true;
-            w->cv.notify_all();
-        }
-        if (w->th.joinable()) w->th.join();
-    }
+    for (auto& w : m->workers) enqueue_worker_stop(w.get());
     m->workers.clear();
-    multi_free_exchange(m);
+    multi_unset_exchange(m);
     if (!m->comms.empty() && rccl().ok())
         for (ncclComm_t c : m->comms)
             if (c) rccl().CommDestroy(c);
@@ -3589,8 +3586,8 @@ extern "C" int pt_create_multi(const pt_scene_desc* scene, const int* devices, i
     const char* te = getenv("PT_MULTI_THREADS");
     if (ndev > 1 && !(te && atoi(te) == 0))
         for (int r = 0; r < ndev; ++r) {
-            m->workers.emplace_back(new RankWorker());
-            m->workers.back()->th = std::thread(rank_worker_main, m->workers.back().get(), devices[r]);
+            m->workers.emplace_back(new EnqueueWorker());
+            m->workers.back()->th = std::thread(enqueue_worker_main, m->workers.back().get(), devices[r]);
         }
     *out = m;
     return PT_OK;
@@ -3652,32 +3649,48 @@ extern "C" int pt_multi_resize(pt_multi* m, int width, int height, int tile_w, i
     if (tile_w == 0) tile_w = 64;
     if (tile_h == 0) tile_h = 16;
     const int world = (int)m->ctx.size();
-    multi_free_exchange(m);
-    for (int r = 0; r < world; ++r) {
-        pt_ctx* c = m->ctx[r];
-        c->width = c->height = 0; // pt_set_partition then only records the partition; pt_resize applies it
-        int rc = mctx(m, r, pt_set_partition(c, r, world, tile_w, tile_h), "pt_multi_resize");
-        if (rc == PT_OK) rc = mctx(m, r, pt_resize(c, width, height), "pt_multi_resize");
-        if (rc) return rc;
+    multi_unset_exchange(m);
+    std::vector<uint8_t*> send(world, nullptr), recv(world, nullptr);
+    m->ex.mem.resize(world);
+    auto build = [&]() -> int {
+        for (int r = 0; r < world; ++r) {
+            pt_ctx* c = m->ctx[r];
+            c->width = c->height = 0; // pt_set_partition then only records the partition; pt_resize applies it
+            int rc = mctx(m, r, pt_set_partition(c, r, world, tile_w, tile_h), "pt_multi_resize");
+            if (rc == PT_OK) rc = mctx(m, r, pt_resize(c, width, height), "pt_multi_resize");
+            if (rc) return rc;
+        }
+        const size_t padded = m->ctx[0]->padded;
+        for (int r = 0; r < world; ++r) {
+            MCK(m, hipSetDevice(m->devices[r]));
+            MCK(m, m->ex.mem[r].alloc(&send[r], std::max<size_t>(16, padded * 16)));
+            MCK(m, m->ex.mem[r].alloc(&recv[r], std::max<size_t>(16, (size_t)world * padded * 16)));
+        }
+        return PT_OK;
+    };
+    const int rc = build();
+    if (rc) { // every rank is as before its first resize: none keeps a frame that the others, or the strips, lack
+        for (pt_ctx* c : m->ctx) drain(c); // (a rank the loop did not reach may have frames in flight)
+        multi_unset_exchange(m);           // (waits for the ranks' streams)
+        for (int r = 0; r < world; ++r) {
+            hipSetDevice(m->devices[r]);
+            unset_frame(m->ctx[r]);
+        }
+        return rc;
     }
-    m->padded = m->ctx[0]->padded;
-    m->send.assign(world, nullptr);
-    m->recv.assign(world, nullptr);
-    for (int r = 0; r < world; ++r) {
-        MCK(m, hipSetDevice(m->devices[r]));
-        MCK(m, hipMalloc(&m->send[r], std::max<size_t>(16, (size_t)m->padded * 16)));
-        MCK(m, hipMalloc(&m->recv[r], std::max<size_t>(16, (size_t)world * m->padded * 16)));
-    }
+    m->ex.padded = m->ctx[0]->padded;
+    m->ex.send = send;
+    m->ex.recv = recv;
     return PT_OK;
 }
 
 extern "C" int pt_multi_gather(pt_multi* m, int which) {
     if (!m) return PT_ERR_INVALID;
     const int world = (int)m->ctx.size();
-    if (m->send.empty()) return mfail(m, PT_ERR_INVALID, "pt_multi_gather: not resized");
+    if (m->ex.send.empty()) return mfail(m, PT_ERR_INVALID, "pt_multi_gather: not resized");
     size_t elem = 0;
     if (!buffer_ptr(m->ctx[0], which, &elem)) return mfail(m, PT_ERR_INVALID, "pt_multi_gather: unknown buffer");
-    const size_t bytes = (size_t)m->padded * elem; // one rank's packed strip (padded to the largest share: same on every rank)
+    const size_t bytes = (size_t)m->ex.padded * elem; // one rank's packed strip (padded to the largest share: same on every rank)
     {
         int rc = multi_present_pending(m, true); // a frame of the overlapped path that was still waiting for its hand-over
         if (rc) return rc;
@@ -3688,9 +3701,10 @@ extern "C" int pt_multi_gather(pt_multi* m, int which) {
     }
     const auto t0 = std::chrono::steady_clock::now();
     for (int r = 0; r < world; ++r) {
-        int rc = mctx(m, r, pack_launch(m->ctx[r], which, m->send[r]), "pt_multi_gather(pack)");
+        int rc = mctx(m, r, pack_launch(m->ctx[r], which, m->ex.send[r]), "pt_multi_gather(pack)");
         if (rc) return rc;
     }
+    DevOwner tmp; // the peer copies' events: they must outlive the waits, so they go when the streams have been synchronised, below
     bool use_rccl = m->exchange_pref == 1 || (m->exchange_pref == 0 && m->distinct && world > 1);
     if (use_rccl && (!rccl().ok() || !m->distinct)) {
         if (m->exchange_pref == 1) return mfail(m, PT_ERR_UNSUPPORTED, !m->distinct ? "pt_multi_gather: RCCL needs distinct devices" : "pt_multi_gather: librccl not found");
@@ -3698,19 +3712,12 @@ extern "C" int pt_multi_gather(pt_multi* m, int which) {
     }
     if (use_rccl) {
         Rccl& R = rccl();
-        if (m->comms.empty()) {
-            m->comms.assign(world, nullptr);
-            const ncclResult_t e = R.CommInitAll(m->comms.data(), world, m->devices.data());
-            if (e != ncclSuccess) {
-                m->comms.clear();
-                return mfail(m, PT_ERR_HIP, std::string("ncclCommInitAll: ") + R.GetErrorString(e));
-            }
-        }
+        if (int rc = multi_comms(m)) return rc;
         // one all-gather of `bytes` per rank: with 8 GPUs each of the 7 xGMI links of a GPU carries one strip
         ncclResult_t e = R.GroupStart();
         for (int r = 0; r < world && e == ncclSuccess; ++r) {
             MCK(m, hipSetDevice(m->devices[r]));
-            e = R.AllGather(m->send[r], m->recv[r], bytes, kNcclUint8, m->comms[r], m->ctx[r]->stream);
+            e = R.AllGather(m->ex.send[r], m->ex.recv[r], bytes, kNcclUint8, m->comms[r], m->ctx[r]->stream);
         }
         const ncclResult_t e2 = R.GroupEnd();
         if (e != ncclSuccess || e2 != ncclSuccess) return mfail(m, PT_ERR_HIP, std::string("ncclAllGather: ") + R.GetErrorString(e != ncclSuccess ? e : e2));
@@ -3722,11 +3729,11 @@ extern "C" int pt_multi_gather(pt_multi* m, int which) {
         for (int r = 0; r < world; ++r) {
             MCK(m, hipSetDevice(m->devices[r]));
             for (int p = 0; p < world; ++p) {
-                char* dst = (char*)m->recv[p] + (size_t)r * bytes;
-                if (m->devices[p] == m->devices[r]) MCK(m, hipMemcpyAsync(dst, m->send[r], bytes, hipMemcpyDeviceToDevice, m->ctx[r]->stream));
-                else MCK(m, hipMemcpyPeerAsync(dst, m->devices[p], m->send[r], m->devices[r], bytes, m->ctx[r]->stream));
+                char* dst = (char*)m->ex.recv[p] + (size_t)r * bytes;
+                if (m->devices[p] == m->devices[r]) MCK(m, hipMemcpyAsync(dst, m->ex.send[r], bytes, hipMemcpyDeviceToDevice, m->ctx[r]->stream));
+                else MCK(m, hipMemcpyPeerAsync(dst, m->devices[p], m->ex.send[r], m->devices[r], bytes, m->ctx[r]->stream));
             }
-            MCK(m, hipEventCreateWithFlags(&done[r], hipEventDisableTiming));
+            MCK(m, tmp.event(&done[r], hipEventDisableTiming));
             MCK(m, hipEventRecord(done[r], m->ctx[r]->stream));
         }
         for (int p = 0; p < world; ++p) {
@@ -3734,22 +3741,10 @@ extern "C" int pt_multi_gather(pt_multi* m, int which) {
             for (int r = 0; r < world; ++r)
                 if (r != p) MCK(m, hipStreamWaitEvent(m->ctx[p]->stream, done[r], 0));
         }
-        // the events must outlive the waits: destroyed after the streams are synchronised below
-        for (int r = 0; r < world; ++r) {
-            int rc = mctx(m, r, unpack_launch(m->ctx[r], which, m->recv[r]), "pt_multi_gather(unpack)");
-            if (rc) return rc;
-        }
-        for (int r = 0; r < world; ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            MCK(m, hipStreamSynchronize(m->ctx[r]->stream));
-        }
-        for (int r = 0; r < world; ++r) hipEventDestroy(done[r]);
         m->last_exchange = PT_EXCHANGE_PEER_COPY;
-        m->gather_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return PT_OK;
     }
     for (int r = 0; r < world; ++r) {
-        int rc = mctx(m, r, unpack_launch(m->ctx[r], which, m->recv[r]), "pt_multi_gather(unpack)");
+        int rc = mctx(m, r, unpack_launch(m->ctx[r], which, m->ex.recv[r]), "pt_multi_gather(unpack)");
         if (rc) return rc;
     }
     for (int r = 0; r < world; ++r) {
@@ -3774,24 +3769,40 @@ static int multi_after_render(pt_multi* m, uint32_t gather_mask, uint32_t* host_
 
 // ---- overlapped hand-off (frames in flight + something to hand over): everything below only ENQUEUES on the ranks' own streams
 static int multi_ensure_strips(pt_multi* m, int slot, int which) {
-    pt_multi::Strips& st = m->hand[slot][which];
+    pt_multi::Exchange& X = m->ex;
+    pt_multi::Strips& st = X.hand[slot][which];
     const int world = (int)m->ctx.size();
+    if (X.send.empty()) return mfail(m, PT_ERR_INVALID, "pt_multi: not resized"); // X.padded sizes the strips
     if ((int)st.send.size() == world) return PT_OK;
     const size_t elem = buffer_elem(which);
-    st.send.assign(world, nullptr);
-    st.recv.assign(world, nullptr);
-    for (int r = 0; r < world; ++r) {
-        MCK(m, hipSetDevice(m->devices[r]));
-        MCK(m, hipMalloc(&st.send[r], std::max<size_t>(16, (size_t)m->padded * elem)));
-        MCK(m, hipMalloc(&st.recv[r], std::max<size_t>(16, (size_t)world * m->padded * elem)));
-    }
-    if (m->xfer_done[slot].empty()) {
-        m->xfer_done[slot].assign(world, nullptr);
+    // built aside and published whole: strips that are half there would pass for complete
+    std::vector<uint8_t*> send(world, nullptr), recv(world, nullptr);
+    std::vector<hipEvent_t> done(X.xfer_done[slot].empty() ? world : 0, nullptr);
+    auto build = [&]() -> int {
         for (int r = 0; r < world; ++r) {
             MCK(m, hipSetDevice(m->devices[r]));
-            MCK(m, hipEventCreateWithFlags(&m->xfer_done[slot][r], hipEventDisableTiming));
+            MCK(m, X.mem[r].alloc(&send[r], std::max<size_t>(16, (size_t)X.padded * elem)));
+            MCK(m, X.mem[r].alloc(&recv[r], std::max<size_t>(16, (size_t)world * X.padded * elem)));
         }
+        for (size_t r = 0; r < done.size(); ++r) {
+            MCK(m, hipSetDevice(m->devices[r]));
+            MCK(m, X.mem[r].event(&done[r], hipEventDisableTiming));
+        }
+        return PT_OK;
+    };
+    const int rc = build();
+    if (rc) {
+        for (int r = 0; r < world; ++r) {
+            hipSetDevice(m->devices[r]);
+            X.mem[r].drop(send[r]);
+            X.mem[r].drop(recv[r]);
+            if (!done.empty()) X.mem[r].drop(done[r]);
+        }
+        return rc;
     }
+    st.send = send;
+    st.recv = recv;
+    if (!done.empty()) X.xfer_done[slot] = done;
     return PT_OK;
 }
 static bool multi_use_rccl(pt_multi* m, int* err) {
@@ -3807,21 +3818,14 @@ static bool multi_use_rccl(pt_multi* m, int* err) {
 // the strips of `slot` (packed on every rank's stream) -> all ranks' receive buffers -> the ranks' display buffers
 static int multi_exchange_display(pt_multi* m, int slot, int which) {
     const int world = (int)m->ctx.size();
-    pt_multi::Strips& st = m->hand[slot][which];
-    const size_t bytes = (size_t)m->padded * buffer_elem(which);
+    pt_multi::Strips& st = m->ex.hand[slot][which];
+    const size_t bytes = (size_t)m->ex.padded * buffer_elem(which);
     int err;
     const bool use_rccl = multi_use_rccl(m, &err);
     if (err) return err;
     if (use_rccl) {
         Rccl& R = rccl();
-        if (m->comms.empty()) {
-            m->comms.assign(world, nullptr);
-            const ncclResult_t e = R.CommInitAll(m->comms.data(), world, m->devices.data());
-            if (e != ncclSuccess) {
-                m->comms.clear();
-                return mfail(m, PT_ERR_HIP, std::string("ncclCommInitAll: ") + R.GetErrorString(e));
-            }
-        }
+        if (int rc = multi_comms(m)) return rc;
         ncclResult_t e = R.GroupStart();
         for (int r = 0; r < world && e == ncclSuccess; ++r) {
             MCK(m, hipSetDevice(m->devices[r]));
@@ -3838,12 +3842,12 @@ static int multi_exchange_display(pt_multi* m, int slot, int which) {
                 if (m->devices[p] == m->devices[r]) MCK(m, hipMemcpyAsync(dst, st.send[r], bytes, hipMemcpyDeviceToDevice, m->ctx[r]->stream));
                 else MCK(m, hipMemcpyPeerAsync(dst, m->devices[p], st.send[r], m->devices[r], bytes, m->ctx[r]->stream));
             }
-            MCK(m, hipEventRecord(m->xfer_done[slot][r], m->ctx[r]->stream));
+            MCK(m, hipEventRecord(m->ex.xfer_done[slot][r], m->ctx[r]->stream));
         }
         for (int p = 0; p < world; ++p) {
             MCK(m, hipSetDevice(m->devices[p]));
             for (int r = 0; r < world; ++r)
-                if (r != p) MCK(m, hipStreamWaitEvent(m->ctx[p]->stream, m->xfer_done[slot][r], 0));
+                if (r != p) MCK(m, hipStreamWaitEvent(m->ctx[p]->stream, m->ex.xfer_done[slot][r], 0));
         }
         m->last_exchange = PT_EXCHANGE_PEER_COPY;
     }
@@ -3884,7 +3888,7 @@ static int multi_pack_newest(pt_multi* m, uint32_t mask) {
             int rc = multi_ensure_strips(m, use, which);
             if (rc) return rc;
             for (size_t r = 0; r < m->ctx.size(); ++r) {
-                rc = mctx(m, (int)r, pack_async_enqueue(m->ctx[r], which, m->hand[use][which].send[r], use), "pt_multi(pack)");
+                rc = mctx(m, (int)r, pack_async_enqueue(m->ctx[r], which, m->ex.hand[use][which].send[r], use), "pt_multi(pack)");
                 if (rc) return rc;
             }
         }
@@ -4005,45 +4009,40 @@ extern "C" int pt_multi_get_stats(const pt_multi* m, pt_multi_stats* out) {
     return PT_OK;
 }
 
-extern "C" int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
-    if (!m) return PT_ERR_INVALID;
+// stage on every rank, then commit on every rank: an update that one rank refuses changes none
+static int multi_update(pt_multi* m, const UpdateSource& S, int mode, double* kernel_ms, const char* what) {
     const int world = (int)m->ctx.size();
-    std::string err;
-    int rc = update_validate(m->ctx[0], updates, n, mode, err);
-    if (rc != PT_OK) return mfail(m, rc, err);
+    int rc = PT_OK;
     std::vector<MeshUpdate> U(world);
-    auto discard = [&] { for (auto& u : U) u.discard(); };
-    for (int r = 0; r < world && rc == PT_OK; ++r) rc = mctx(m, r, update_stage(m->ctx[r], updates, n, mode, U[r]), "pt_multi_update_meshes");
+    for (int r = 0; r < world && rc == PT_OK; ++r) rc = mctx(m, r, update_stage(m->ctx[r], S, mode, U[r]), what);
     double slow = 0;
     for (int r = 0; r < world && rc == PT_OK; ++r) {
         double ms = 0;
-        rc = mctx(m, r, update_commit(m->ctx[r], mode, U[r], &ms), "pt_multi_update_meshes");
+        rc = mctx(m, r, update_commit(m->ctx[r], mode, U[r], &ms), what);
         slow = std::max(slow, ms);
     }
-    discard();
     if (rc == PT_OK && kernel_ms) *kernel_ms = slow;
     return rc;
+}
+extern "C" int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
+    if (!m) return PT_ERR_INVALID;
+    std::string err;
+    const int rc = update_validate(m->ctx[0], updates, n, mode, err);
+    if (rc != PT_OK) return mfail(m, rc, err);
+    UpdateSource S{"pt_update_meshes"};
+    S.host = updates;
+    S.n = n;
+    return multi_update(m, S, mode, kernel_ms, "pt_multi_update_meshes");
 }
 
 extern "C" int pt_multi_transform_meshes(pt_multi* m, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms) {
     if (!m) { (void)fail(nullptr, PT_ERR_INVALID, "pt_multi_transform_meshes: null pt_multi"); return mfail(nullptr, PT_ERR_INVALID, "pt_multi_transform_meshes: null pt_multi"); }
-    const int world = (int)m->ctx.size();
     std::string err;
-    int rc = transform_validate(m->ctx[0], t, n, source, mode, err, "pt_multi_transform_meshes");
+    const int rc = transform_validate(m->ctx[0], t, n, source, mode, err, "pt_multi_transform_meshes");
     if (rc != PT_OK) return mfail(m, rc, err);
     UpdateSource S{"pt_multi_transform_meshes"};
     S.xform = t;
     S.from = source;
     S.n = n;
-    std::vector<MeshUpdate> U(world);
-    for (int r = 0; r < world && rc == PT_OK; ++r) rc = mctx(m, r, update_stage(m->ctx[r], S, mode, U[r]), "pt_multi_transform_meshes");
-    double slow = 0;
-    for (int r = 0; r < world && rc == PT_OK; ++r) {
-        double ms = 0;
-        rc = mctx(m, r, update_commit(m->ctx[r], mode, U[r], &ms), "pt_multi_transform_meshes");
-        slow = std::max(slow, ms);
-    }
-    for (auto& u : U) u.discard();
-    if (rc == PT_OK && kernel_ms) *kernel_ms = slow;
-    return rc;
+    return multi_update(m, S, mode, kernel_ms, "pt_multi_transform_meshes");
 }

@@ -32,7 +32,7 @@ extern "C" int pt_edge_aa_planes(pt_ctx* ctx, const pt_edge_aa_desc* desc, pt_ed
     if (rc) return rc;
     const uint32_t n = run.n;
     if (n != 0) {
-        const EdgeAaArgs ea{run.pixels, n, ctx->width, ctx->height, desc->color, reinterpret_cast<const float*>(desc->hit), desc->position, ctx->d_idx, ctx->d_verts,
+        const EdgeAaArgs ea{run.pixels, n, ctx->width, ctx->height, desc->color, reinterpret_cast<const float*>(desc->hit), desc->position, ctx->sc.d_idx, ctx->sc.d_verts,
                             ctx->ntri, ctx->eye, ctx->U, ctx->V, ctx->W, desc->out, desc->edge, desc->frame_rgba8, d_inset, B.nbx, desc->normal_cos, desc->plane_eps,
                             run.counts()};
         PASS_LAUNCH(run, (n + 255u) / 256u, 256, ea, k_edge_aa);

@@ -33,7 +33,7 @@ extern "C" int pt_render_gbuffer(pt_ctx* ctx, const pt_gbuffer_desc* desc, pt_gb
     if (n != 0) {
         QueryCounters* counters = reinterpret_cast<QueryCounters*>(run.d_counters);
         uint32_t* work = reinterpret_cast<uint32_t*>(run.d_counters + sizeof(QueryCounters));
-        GBufferArgs ga{run.pixels, n, bvh_dev(ctx), ctx->d_tri_nrm, work, counters, ctx->width, ctx->height, ctx->eye, ctx->U, ctx->V, ctx->W,
+        GBufferArgs ga{run.pixels, n, bvh_dev(ctx), ctx->sc.d_tri_nrm, work, counters, ctx->width, ctx->height, ctx->eye, ctx->U, ctx->V, ctx->W,
                        d_prev, reinterpret_cast<float*>(desc->hit), desc->depth, desc->position, desc->motion, desc->ray};
         // the packet kernel at every size, its grid sized as launch_closest sizes k_trace8_cam's
         const unsigned tgrid = (unsigned)ctx->trace_grid;

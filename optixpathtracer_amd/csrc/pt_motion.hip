@@ -21,7 +21,7 @@ extern "C" int pt_copy_vertices_device(pt_ctx* ctx, float* dev_dst, size_t bytes
     int rc = drain(ctx); // frames in flight and queued queries finish first
     if (rc) return rc;
     CK(hipSetDevice(ctx->device));
-    if (bytes) CK(hipMemcpyAsync(dev_dst, ctx->d_verts, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (bytes) CK(hipMemcpyAsync(dev_dst, ctx->sc.d_verts, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -57,7 +57,7 @@ extern "C" int pt_motion_planes(pt_ctx* ctx, const pt_motion_desc* desc, pt_moti
     if (rc) return rc;
     const uint32_t n = run.n;
     if (n != 0) {
-        const MotionArgs ma{run.pixels, n, ctx->width, ctx->height, reinterpret_cast<const float*>(desc->hit), desc->prev_vertices, ctx->d_idx, ctx->ntri,
+        const MotionArgs ma{run.pixels, n, ctx->width, ctx->height, reinterpret_cast<const float*>(desc->hit), desc->prev_vertices, ctx->sc.d_idx, ctx->ntri,
                             ctx->eye, ctx->U, ctx->V, ctx->W, d_prev, desc->motion, desc->prev_point, reinterpret_cast<float*>(desc->prev_surface), run.counts()};
         const unsigned grid = (n + 255u) / 256u;
         PASS_LAUNCH(run, grid, 256, ma, k_motion);

@@ -113,7 +113,10 @@ struct PassCounterPool {
                 }
         }
         *out = PassCounterBlock{device, bytes, nullptr};
-        return dalloc(&out->ptr, bytes);
+        DevOwner own;
+        const hipError_t e = own.alloc(&out->ptr, bytes);
+        own.items.clear(); // never freed (above): the block outlives every owner
+        return e;
     }
     void give(const PassCounterBlock& b) {
         std::lock_guard<std::mutex> lock(mu);
@@ -126,7 +129,7 @@ inline PassCounterPool& pass_counter_pool() {
 }
 struct PassRun {
     pt_ctx* ctx = nullptr;
-    DevScope tmp; // destroyed after ~PassRun has waited
+    DevOwner tmp; // destroyed after ~PassRun has waited
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint8_t* d_counters = nullptr; // the pass's counter words, zeroed
     PassCounterBlock block{0, 0, nullptr}; // where they live (pass_counter_pool)

@@ -18,17 +18,17 @@ extern "C" int pt_copy_texcoords_device(pt_ctx* ctx, float* dev_dst, size_t byte
     int rc = drain(ctx); // frames in flight and queued queries finish first
     if (rc) return rc;
     CK(hipSetDevice(ctx->device));
-    if (!ctx->d_textris) { // no textured mesh: no texcoord is ever read
+    if (!ctx->sc.d_textris) { // no textured mesh: no texcoord is ever read
         if (bytes) CK(hipMemsetAsync(dev_dst, 0, bytes, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         return PT_OK;
     }
     if (ctx->bvh.num_tris8 != ctx->ntri) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_copy_texcoords_device: the tree does not hold one leaf record per primitive");
-    DevScope tmp;
+    DevOwner tmp;
     PrimUV* uvs = reinterpret_cast<PrimUV*>(dev_dst);
     const bool staged = (reinterpret_cast<uintptr_t>(dev_dst) & 7u) != 0; // the kernel stores 8-byte pairs: a 4-byte-aligned destination gets a copy
     if (staged) CK(tmp.alloc(&uvs, (size_t)ctx->ntri));
-    hipLaunchKernelGGL(k_textris_to_uvs, dim3((ctx->ntri + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->d_textris, ctx->ntri, uvs);
+    hipLaunchKernelGGL(k_textris_to_uvs, dim3((ctx->ntri + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->sc.d_textris, ctx->ntri, uvs);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && staged) e = hipMemcpyAsync(dev_dst, uvs, bytes, hipMemcpyDeviceToDevice, ctx->stream);
     const hipError_t es = hipStreamSynchronize(ctx->stream); // before the temporary goes, on every path
@@ -44,7 +44,7 @@ extern "C" int pt_surface_planes(pt_ctx* ctx, const pt_surface_desc* desc, pt_su
     const std::string fn = "pt_surface_planes: ";
     if (desc->flags != 0u) return fail(ctx, PT_ERR_INVALID, (fn + "unknown flag bits " + std::to_string(desc->flags)).c_str());
     if (!desc->albedo && !desc->texcoord) return fail(ctx, PT_ERR_INVALID, (fn + "no plane asked for (albedo and texcoord are both null)").c_str());
-    const bool tex = ctx->d_textris != nullptr; // the scene has a textured mesh (d_mesh_tex exists with it)
+    const bool tex = ctx->sc.d_textris != nullptr; // the scene has a textured mesh (d_mesh_tex exists with it)
     const size_t npix = (size_t)ctx->width * ctx->height;
     // exclusive: may overlap no other plane (the two written ones); hit and prim_texcoords are only read.  On an untextured scene
     // prim_texcoords is not looked at at all.
@@ -62,8 +62,8 @@ extern "C" int pt_surface_planes(pt_ctx* ctx, const pt_surface_desc* desc, pt_su
     if (rc) return rc;
     const uint32_t n = run.n;
     if (n != 0) {
-        const SurfaceArgs sa{run.pixels, n, ctx->width, reinterpret_cast<const float*>(desc->hit), ctx->d_tri_mesh, ctx->ntri, ctx->d_mats,
-                             tex ? ctx->d_mesh_tex : nullptr, tex ? desc->prim_texcoords : nullptr, tex ? ctx->d_textures : nullptr,
+        const SurfaceArgs sa{run.pixels, n, ctx->width, reinterpret_cast<const float*>(desc->hit), ctx->sc.d_tri_mesh, ctx->ntri, ctx->sc.d_mats,
+                             tex ? ctx->sc.d_mesh_tex : nullptr, tex ? desc->prim_texcoords : nullptr, tex ? ctx->sc.d_textures : nullptr,
                              desc->albedo, desc->texcoord, run.counts()};
         const unsigned grid = (n + 255u) / 256u;
         if (tex) hipLaunchKernelGGL(k_surface<true>, dim3(grid), dim3(256), 0, ctx->stream, sa);

@@ -7,10 +7,10 @@
 // Every size below comes from them, so no level address depends on anything the caller passes.  They are fetched on the context's stream:
 // a blocking hipMemcpy runs on the null stream and made every call wait for whatever the caller had enqueued there.
 static int lod_textures(pt_ctx* ctx, std::vector<DevTex>& tex) {
-    tex.resize(ctx->d_tex_pixels.size());
+    tex.resize(ctx->sc.d_tex_pixels.size());
     if (tex.empty()) return PT_OK;
     CK(hipSetDevice(ctx->device));
-    CK(hipMemcpyAsync(tex.data(), ctx->d_textures, sizeof(DevTex) * tex.size(), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipMemcpyAsync(tex.data(), ctx->sc.d_textures, sizeof(DevTex) * tex.size(), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     return PT_OK;
 }
@@ -101,7 +101,7 @@ static int lod_call(pt_ctx* ctx, const LodCall& d, unsigned long long (&sum)[6],
     if (!d.albedo && !d.texcoord && !d.footprint && !d.lod && !d.taps)
         return fail(ctx, PT_ERR_INVALID, (fn + "no plane asked for (albedo, texcoord, footprint, lod" + (aniso ? ", taps" : "") + " are all null)").c_str());
     if (!(std::isfinite(d.footprint_scale) && d.footprint_scale >= 0.0f)) return fail(ctx, PT_ERR_INVALID, (fn + "footprint_scale must be finite and >= 0").c_str());
-    const bool tex = ctx->d_textris != nullptr; // the scene has a textured mesh (d_mesh_tex exists with it)
+    const bool tex = ctx->sc.d_textris != nullptr; // the scene has a textured mesh (d_mesh_tex exists with it)
     std::vector<DevTex> textures;
     std::vector<uint32_t> dims;
     size_t mips_bytes = 0;
@@ -153,9 +153,9 @@ static int lod_call(pt_ctx* ctx, const LodCall& d, unsigned long long (&sum)[6],
     if (rc) return rc;
     const uint32_t n = run.n;
     if (n != 0) {
-        const SurfaceLodArgs sa{run.pixels, n, ctx->width, ctx->height, reinterpret_cast<const float*>(d.hit), ctx->d_tri_mesh, ctx->ntri, ctx->d_mats,
-                                tex ? ctx->d_mesh_tex : nullptr, tex ? d.prim_texcoords : nullptr, tex ? ctx->d_textures : nullptr,
-                                tex ? ctx->d_idx : nullptr, tex ? ctx->d_verts : nullptr, pyr ? reinterpret_cast<const float4*>(d.mips) : nullptr, d_first,
+        const SurfaceLodArgs sa{run.pixels, n, ctx->width, ctx->height, reinterpret_cast<const float*>(d.hit), ctx->sc.d_tri_mesh, ctx->ntri, ctx->sc.d_mats,
+                                tex ? ctx->sc.d_mesh_tex : nullptr, tex ? d.prim_texcoords : nullptr, tex ? ctx->sc.d_textures : nullptr,
+                                tex ? ctx->sc.d_idx : nullptr, tex ? ctx->sc.d_verts : nullptr, pyr ? reinterpret_cast<const float4*>(d.mips) : nullptr, d_first,
                                 ctx->eye, ctx->U, ctx->V, ctx->W, d.footprint_scale, d.albedo, d.texcoord, d.footprint, d.lod, run.counts()};
         const unsigned grid = (n + 255u) / 256u;
         if (aniso) {

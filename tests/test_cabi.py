@@ -83,6 +83,24 @@ def test_product_never_imports_the_oracle():
                     assert pat not in s, f"{f} references the checker ({pat})"
 
 
+def test_device_memory_has_one_owner():
+    """pt_api.hip and pt_pass.h allocate and free device memory, pinned memory and events only inside DevOwner: every group of the context
+    frees what it owns when it is reset or destroyed, so there is no list of frees to keep in step with the allocations (and
+    PT_ALLOC_FAIL_AT, read by DevOwner::alloc, reaches every allocation site)."""
+    calls = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventCreate(", "hipEventCreateWithFlags(", "hipEventDestroy(")
+    exceptions = {}  # {(file, call): reason}: none — the frame slots' event pools and pick_streams' stamp words are owned like everything else
+    csrc = os.path.join(ROOT, "optixpathtracer_amd", "csrc")
+    for name in ("pt_api.hip", "pt_pass.h"):
+        s = open(os.path.join(csrc, name)).read()
+        if name == "pt_api.hip":  # the owner's definition: from its first line to the closing brace at the start of a line
+            a = s.index("struct DevOwner {")
+            b = s.index("\n};\n", a)
+            assert all(c in s[a:b] for c in calls), "the owner no longer wraps every call"
+            s = s[:a] + s[b:]
+        for c in calls:
+            assert c not in s or (name, c) in exceptions, f"{name} calls {c[:-1]} outside DevOwner"
+
+
 def test_headers_compile_as_c99_and_cxx17(tmp_path):
     """include/pt_amd.h is a plain C header; the C++ facade over it (the reference's SampleRenderer surface) compiles
     with a host compiler alone — no hipcc, no torch types on the application side."""
