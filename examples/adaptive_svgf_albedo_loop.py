@@ -24,9 +24,14 @@ With --auto-exposure [--tonemap aces|reinhard|linear] the displayed frame is ton
 linear frame is metered (exposurePlanes: a histogram of log2 luminance, its trimmed mean, an exposure that adapts from frame to frame) and
 shown through the operator under that exposure.  The exposure state ping-pongs between two device arrays and never visits the host on the
 way from the meter to the tone mapper (the value printed per frame is read back for the printing alone).
+With --bloom [--bloom-threshold T --bloom-levels N] bloomPlanes sits behind modulate / edge AA and in front of the tone map: the part of the
+linear frame above T (on luminance exposed by the PREVIOUS frame's exposure state: this frame's is not metered yet) is spread over a pyramid
+of N levels and added back.  The meter still reads the frame without bloom, the tone mapper the one with it; without --auto-exposure the
+bloomed frame is displayed through the linear operator at exposure 1.
 
   python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--edge-aa]
-                                                [--auto-exposure] [--tonemap aces|reinhard|linear] [--out-dir .]
+                                                [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
+                                                [--bloom-levels N] [--out-dir .]
 """
 import argparse
 import os
@@ -74,6 +79,9 @@ def main():
     ap.add_argument("--edge-aa", action="store_true", help="geometric edge antialiasing (edgeAaPlanes) as the last pass before display")
     ap.add_argument("--auto-exposure", action="store_true", help="meter the linear frame (exposurePlanes) and display it through tonemapPlanes")
     ap.add_argument("--tonemap", choices=["aces", "reinhard", "linear"], default="aces", help="with --auto-exposure: the display operator")
+    ap.add_argument("--bloom", action="store_true", help="bloom (bloomPlanes) behind modulate / edge AA and in front of the tone map")
+    ap.add_argument("--bloom-threshold", type=float, default=1.0, metavar="T", help="with --bloom: the exposed luminance above which a pixel blooms")
+    ap.add_argument("--bloom-levels", type=int, default=6, metavar="N", help="with --bloom: the levels of the pyramid (1..8)")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args()
     args.lod = args.lod or args.aniso > 0
@@ -99,6 +107,8 @@ def main():
     frame = torch.zeros((h, w), dtype=torch.int32, device=dev)
     hist = torch.zeros((1, 256), dtype=torch.int32, device=dev)  # --auto-exposure: the meter's histogram and the two exposure states
     state = [torch.zeros((1, 4), device=dev) for _ in range(2)]
+    bloomed = planes(4) if args.bloom else None  # --bloom: its output and its scratch pyramid
+    pyramid = torch.zeros((sample.bloomLayout(args.bloom_levels)[1] // 16, 4), device=dev) if args.bloom else None
     accum = sample.deviceBuffer(R.PT_BUF_ACCUM)
     table = sample.copyTexcoordsDevice()  # the scene's texcoords per primitive: once, whatever moves later
     mips = sample.copyTextureMipsDevice() if args.lod else None  # the mip pyramid of the scene's textures: once, too
@@ -127,25 +137,35 @@ def main():
         assert c["stats"]["lost"] == 0  # the plan samples every block that holds a pixel the carry could not carry
         f = sample.filterPlanes(history[o], cur["hit"], cur["position"], variance=variance, length=length[o], out=filtered, scratch=scratch,
                                 iterations=args.iterations, sigma_lum=args.sigma_lum, min_length=args.min_length)
-        shown = None if args.auto_exposure else frame  # with --auto-exposure the tone mapper writes the displayed frame
+        shown = None if args.auto_exposure or args.bloom else frame  # with --auto-exposure or --bloom the tone mapper writes the displayed frame
         if args.edge_aa:
             m = sample.modulatePlanes(filtered, albedo=albedo, out=modulated)
             e = sample.edgeAaPlanes(modulated, cur["hit"], cur["position"], out=final, frame=shown)["stats"]
         else:
             m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=shown)
+        lit = final
+        if args.bloom:
+            b = sample.bloomPlanes(final, state=state[i] if args.auto_exposure and k else None, out=bloomed, scratch=pyramid, threshold=args.bloom_threshold,
+                                   levels=args.bloom_levels)["stats"]
+            lit = bloomed
         if args.auto_exposure:
             x = sample.exposurePlanes(final, cur["hit"], hist=hist, state_in=state[i] if k else None, state_out=state[o], rate_up=0.25, rate_down=0.5)["stats"]
-            tm = sample.tonemapPlanes(final, state=state[o], frame=frame, op=args.tonemap, write_out=False)["stats"]
+            tm = sample.tonemapPlanes(lit, state=state[o], frame=frame, op=args.tonemap, write_out=False)["stats"]
+        elif args.bloom:
+            sample.tonemapPlanes(lit, frame=frame, op="linear", write_out=False)
         ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
         print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
               f"{ss['textured']} of {ss['hits']} hits textured{', %d minified' % ss['minified'] if args.lod else ''}{', %d taps' % ss['taps'] if args.aniso else ''}; G-buffer {g['stats']['kernel_ms']:.3f} ms, surface {ss['kernel_ms']:.3f} ms, "
               f"plan {ps['kernel_ms']:.3f} ms, colour {sample.stats()['render_ms']:.2f} ms, temporal {ts['kernel_ms']:.3f} ms, "
               f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms"
               + (f", edge aa {e['kernel_ms']:.3f} ms ({e['blended']} of {e['boundary']} boundary pixels blended)" if args.edge_aa else "")
+              + (f", bloom {b['kernel_ms']:.3f} ms ({b['bright']} of {b['sources']} pixels bright)" if args.bloom else "")
               + (f", exposure {x['kernel_ms']:.3f} ms (ev {float(state[o][0, 0]):+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
                  f"tone map {tm['kernel_ms']:.3f} ms ({tm['clipped']} pixels clipped)" if args.auto_exposure else ""))
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_final.npy"), final.cpu().numpy())
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_frame.npy"), frame.cpu().numpy().view(np.uint32))
+    if args.bloom:
+        np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_bloomed.npy"), bloomed.cpu().numpy())
     print(f"wrote adaptive_svgf_albedo_final.npy and adaptive_svgf_albedo_frame.npy to {args.out_dir}")
     sample.close()
 

@@ -22,10 +22,15 @@ Per frame, on `hi`:
      histogram of log2 luminance, its trimmed mean, an exposure that adapts from frame to frame) and tonemapPlanes writes the displayed
      frame through the operator under that exposure.  The exposure state ping-pongs between two device arrays and goes from the meter to
      the tone mapper without visiting the host (the value in the printed line is read back for the printing alone).
+ 14. with --bloom [--bloom-threshold T --bloom-levels N], behind step 12 and in front of step 13's tone map: bloomPlanes spreads the part
+     of the linear frame above T (on luminance exposed by the PREVIOUS frame's exposure state: this frame's is not metered yet) over a
+     pyramid of N levels and adds it back; the meter still reads the frame without bloom, the tone mapper the one with it.  Without
+     --auto-exposure the bloomed frame is displayed through the linear operator at exposure 1.
 `hi` never renders a colour sample.
 
   python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa]
-                                          [--auto-exposure] [--tonemap aces|reinhard|linear] [--out-dir .]
+                                          [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
+                                          [--bloom-levels N] [--out-dir .]
 """
 import argparse
 import os
@@ -59,13 +64,14 @@ class UpsampledLoop:
     """The two renderers and every plane of the loop, allocated once; frame(k, prev, cam) runs one frame and returns its figures."""
 
     def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
-                 edge_aa=False, auto_exposure=False, tonemap="aces"):
+                 edge_aa=False, auto_exposure=False, tonemap="aces", bloom=False, bloom_threshold=1.0, bloom_levels=6):
         import torch
 
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
         self.size, self.scale, self.lod, self.aniso = tuple(size), int(scale), lod, int(aniso)
         self.edge_aa = bool(edge_aa)
         self.auto_exposure, self.tonemap = bool(auto_exposure), tonemap
+        self.bloom, self.bloom_prm = bool(bloom), dict(threshold=float(bloom_threshold), levels=int(bloom_levels))
         w, h = self.size
         if w % self.scale or h % self.scale:
             raise SystemExit(f"--size {w} {h} is not a multiple of --scale {self.scale}")
@@ -95,6 +101,9 @@ class UpsampledLoop:
         # step 13's histogram and its two exposure states (ev, E, mean log2 luminance, pixels metered); cur: the one the last frame wrote
         self.hist = torch.zeros((1, 256), dtype=torch.int32, device="cuda:0")
         self.state, self.cur = [torch.zeros((1, 4), device="cuda:0") for _ in range(2)], 0
+        # step 14's output and its scratch pyramid
+        self.bloomed = planes(h, w, 4) if self.bloom else None
+        self.pyramid = torch.zeros((self.hi.bloomLayout(self.bloom_prm["levels"])[1] // 16, 4), device="cuda:0") if self.bloom else None
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
         self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
@@ -133,20 +142,29 @@ class UpsampledLoop:
         S = self._albedo(hi, self.hi_gbuf["hit"], self.albedo)
         u = hi.upsamplePlanes(self.filtered, cur["hit"], cur["position"], self.hi_gbuf["hit"], self.hi_gbuf["position"], self.scale, out=self.upsampled,
                               weight_out=self.weight)["stats"]
-        shown = None if self.auto_exposure else self.frame_rgba8  # with auto exposure the tone mapper writes the displayed frame
+        shown = None if self.auto_exposure or self.bloom else self.frame_rgba8  # with auto exposure or bloom the tone mapper writes the displayed frame
         if self.edge_aa:
             m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.modulated)["stats"]
             e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=shown)["stats"]
         else:
             m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=shown)["stats"]
             e = dict(kernel_ms=0.0, boundary=0, blended=0)
+        lit = self.final
+        if self.bloom:
+            b = hi.bloomPlanes(self.final, state=self.state[i] if self.auto_exposure and k else None, out=self.bloomed, scratch=self.pyramid,
+                               **self.bloom_prm)["stats"]
+            lit = self.bloomed
+        else:
+            b = dict(kernel_ms=0.0, bright=0)
         if self.auto_exposure:
             x = hi.exposurePlanes(self.final, self.hi_gbuf["hit"], hist=self.hist, state_in=self.state[i] if k else None, state_out=self.state[o],
                                   rate_up=0.25, rate_down=0.5)["stats"]
-            tm = hi.tonemapPlanes(self.final, state=self.state[o], frame=self.frame_rgba8, op=self.tonemap, write_out=False)["stats"]
+            tm = hi.tonemapPlanes(lit, state=self.state[o], frame=self.frame_rgba8, op=self.tonemap, write_out=False)["stats"]
             self.cur = o
         else:
             x, tm = dict(kernel_ms=0.0, skipped=0, under=0, over=0), dict(kernel_ms=0.0, clipped=0)
+            if self.bloom:
+                tm = hi.tonemapPlanes(lit, frame=self.frame_rgba8, op="linear", write_out=False)["stats"]
         t2 = time.perf_counter()
         ev = float(self.state[self.cur][0, 0]) if self.auto_exposure else 0.0  # read back for the caller's printing, outside the timed frame
         return dict(frame_ms=(t2 - t0) * 1e3, lo_ms=(t1 - t0) * 1e3, hi_ms=(t2 - t1) * 1e3, sampled=p["stats"]["sampled"], blocks=p["stats"]["blocks"],
@@ -155,7 +173,7 @@ class UpsampledLoop:
                     gbuffer_ms=G["kernel_ms"], surface_ms=S["kernel_ms"], upsample_ms=u["kernel_ms"], modulate_ms=m["kernel_ms"],
                     pixels=u["pixels"], full=u["full"], rescued=u["rescued"], orphans=u["orphans"], edge_aa_ms=e["kernel_ms"], boundary=e["boundary"],
                     blended=e["blended"], exposure_ms=x["kernel_ms"], tonemap_ms=tm["kernel_ms"], ev=ev, skipped=x["skipped"], under=x["under"],
-                    over=x["over"], clipped=tm["clipped"])
+                    over=x["over"], clipped=tm["clipped"], bloom_ms=b["kernel_ms"], bright=b["bright"])
 
     def close(self):
         self.lo.close()
@@ -174,12 +192,16 @@ def main(argv=None):
     ap.add_argument("--edge-aa", action="store_true", help="geometric edge antialiasing (edgeAaPlanes) as the last pass before display")
     ap.add_argument("--auto-exposure", action="store_true", help="meter the linear frame (exposurePlanes) and display it through tonemapPlanes")
     ap.add_argument("--tonemap", choices=["aces", "reinhard", "linear"], default="aces", help="with --auto-exposure: the display operator")
+    ap.add_argument("--bloom", action="store_true", help="bloom (bloomPlanes) behind modulate / edge AA and in front of the tone map")
+    ap.add_argument("--bloom-threshold", type=float, default=1.0, metavar="T", help="with --bloom: the exposed luminance above which a pixel blooms")
+    ap.add_argument("--bloom-levels", type=int, default=6, metavar="N", help="with --bloom: the levels of the pyramid (1..8)")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
     make, cam0 = SCENES[args.scene]
     loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp, edge_aa=args.edge_aa,
-                         auto_exposure=args.auto_exposure, tonemap=args.tonemap)
+                         auto_exposure=args.auto_exposure, tonemap=args.tonemap, bloom=args.bloom, bloom_threshold=args.bloom_threshold,
+                         bloom_levels=args.bloom_levels)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -190,6 +212,7 @@ def main(argv=None):
               f"{x['gbuffer_ms']:.3f} ms, surface {x['surface_ms']:.3f} ms, upsample {x['upsample_ms']:.3f} ms, modulate {x['modulate_ms']:.3f} ms; "
               f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; "
               + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
+              + (f"bloom {x['bloom_ms']:.3f} ms ({x['bright']} bright pixels); " if loop.bloom else "")
               + (f"exposure {x['exposure_ms']:.3f} ms (ev {x['ev']:+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
                  f"tone map {x['tonemap_ms']:.3f} ms ({x['clipped']} pixels clipped); " if loop.auto_exposure else "")
               + f"frame {x['frame_ms']:.2f} ms")

@@ -31,7 +31,8 @@
  *     on pt_stream(ctx) or make that stream wait for an event recorded on pt_stream(ctx).
  * pt_edge_aa_planes takes DEVICE pointers under the same contract: it is one more entry point of the list above (its ordering case
  * stands with its other GPU tests, in tests/test_gpu_edge_aa.py).  So do pt_exposure_planes and pt_tonemap_planes (their ordering
- * cases: tests/test_gpu_exposure.py).
+ * cases: tests/test_gpu_exposure.py).  pt_bloom_planes takes DEVICE pointers under the same contract, too (its ordering cases:
+ * tests/test_gpu_bloom.py); pt_bloom_layout touches no device memory.
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -43,7 +44,8 @@
  * pt_temporal_moments, pt_modulate_planes, pt_sample_plan, pt_temporal_carry, pt_copy_texcoords_device, pt_surface_planes,
  * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes, pt_edge_aa_planes,
  * pt_exposure_planes, pt_tonemap_planes.  A
- * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.
+ * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.  pt_bloom_layout and pt_bloom_planes were added
+ * in the same way and keep "0.4" as well.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -1555,8 +1557,8 @@ int pt_edge_aa_planes(pt_ctx* ctx, const pt_edge_aa_desc* desc, pt_edge_aa_stats
  * op; exposure or white not finite or not > 0.
  * Ordering and state, both entry points, as pt_modulate_planes: they wait for the frames in flight, run on pt_stream(ctx) under the STREAM
  * CONTRACT, are complete when they return, and write no context state.
- * Not part of this interface: spatially varying or centre-weighted metering; local tone mapping; bloom; a colour-managed output other than
- * sRGB; an asynchronous variant; a pt_multi_* wrapper (per-rank calls and FROM_HISTOGRAM serve a partitioned frame). */
+ * Not part of this interface: spatially varying or centre-weighted metering; local tone mapping; bloom (pt_bloom_planes below, in front of
+ * the tone mapper); a colour-managed output other than sRGB; an asynchronous variant; a pt_multi_* wrapper (per-rank calls and FROM_HISTOGRAM serve a partitioned frame). */
 #define PT_EXPOSURE_BINS 256
 enum pt_exposure_flags { PT_EXPOSURE_ACCUMULATE = 1, PT_EXPOSURE_FROM_HISTOGRAM = 2 };
 typedef struct pt_exposure_desc {
@@ -1589,6 +1591,87 @@ typedef struct pt_tonemap_desc {
 } pt_tonemap_desc;
 typedef struct pt_tonemap_stats { uint64_t pixels, clipped; double kernel_ms; } pt_tonemap_stats;
 int pt_tonemap_planes(pt_ctx* ctx, const pt_tonemap_desc* desc, pt_tonemap_stats* stats /* may be NULL */);
+
+/* BLOOM (no reference counterpart).  Under an HDR probe a sun disc, a window or an emitter lies stops above the key; pt_tonemap_planes
+ * compresses it to a hard-edged white shape and nothing of its energy reaches the pixels around it.  pt_bloom_planes spreads the part of
+ * the colour plane above a threshold over a pyramid of levels and adds it back: out = color + a * (the filtered bright part).  It is
+ * stateless like every pass here: the planes, the state and the scratch pyramid are caller-owned DEVICE memory of the context's device
+ * (4-byte aligned, the scratch 16-byte aligned; the planes frame-sized, indexed Y * width + X); block_mask is HOST memory.  It runs behind
+ * pt_modulate_planes / pt_edge_aa_planes and in front of pt_tonemap_planes: the bloom stays in scene-linear units, so `out` goes through
+ * pt_tonemap_planes with the same state.  Float32 throughout, one rounding per operation, no fused multiply-add, in the stated order.
+ *
+ * Rectangles.  Each view's rectangle (x0, y0, w_0, h_0) has a pyramid of its own; without views there is one rectangle, the whole frame;
+ * nv = max(1, the view count).  Level k = 1 .. levels has w_k = (w_{k-1} + 1) / 2 and h_k = (h_{k-1} + 1) / 2 (integer division): sizes
+ * bottom out at 1 and the level count is not reduced.  No tap ever leaves its rectangle: indices clamp to it, so a bright pixel in one eye
+ * of a stereo pair puts nothing into the other.
+ * pt_bloom_layout gives the scratch: *bytes for `levels` levels of every view, view after view, level 1 first, each level w_k * h_k texels
+ * of 16 bytes (x, y, z, 0) in row order; dims (HOST, nv x PT_BLOOM_MAX_LEVELS x 4, may be NULL) receives w_k, h_k, the index of the
+ * level's first 16-byte texel and 0 for k = 1 .. levels, and zeros for the levels above.  It refuses (PT_ERR_INVALID) a null ctx or
+ * bytes, a context without pt_resize, and levels outside 1 .. PT_BLOOM_MAX_LEVELS.
+ *
+ * What is read, what is written.  The pyramid reads EVERY pixel of every rectangle from color, whether or not the rank owns it or the mask
+ * names it; the set decides only which pixels of out are written.  The set is exactly pt_modulate_planes's: owned pixels, view pixels
+ * while views are set, whole blocks of the mask.  Bloom is not local: the ranks of a partitioned frame all-gather their colour first and
+ * then each composites its own pixels, and a masked call still sees the light of the blocks it does not write.  stats->sources is the
+ * number of rectangle pixels read, stats->pixels the size of the set.  The whole scratch is written by every call, also with an empty set.
+ *
+ * Source.  For each rectangle pixel q, B(q):
+ *   1. c = color[q].xyz.  If one of its three words is not finite (exponent-bit test): B = 0 and stats->nonfinite counts it — one NaN must
+ *      not spread through the pyramid.
+ *   2. Per component: x = c > 0 ? c : 0; x = x < clamp ? x : clamp (one firefly must not own the frame).
+ *   3. s = E_v * exposure, E_v read exactly as pt_tonemap_planes step 1 reads it (state ? state[4 * view + 1] : 1.0f; not finite or not > 0
+ *      counts as 1.0f).
+ *   4. Y = ((0.2126f * x.r + 0.7152f * x.g) + 0.0722f * x.b) * s; d = Y - threshold.
+ *   5. t = d + knee; t = t > 0 ? t : 0; t = t < 2.0f * knee ? t : 2.0f * knee.
+ *   6. t = (t * t) / (4.0f * knee + 1e-4f).
+ *   7. m = t > d ? t : d; m = m > 0 ? m : 0.
+ *   8. g = m / (Y > 1e-4f ? Y : 1e-4f); B = x * g per component.
+ *   9. stats->bright counts g > 0.
+ * g is 0 at and below threshold - knee, and Y * g rises with Y.  For knee <= threshold g stays within [0, 1]; a knee larger than the
+ * threshold reaches below Y = 0, where g = m / Y exceeds 1 for dim pixels while their contribution m stays below knee / 4.
+ * Down.  D_0 = B.  Texel (i, j) of D_k from D_{k-1}: columns 2i - 1, 2i, 2i + 1, 2i + 2, each clamped to [0, w_{k-1} - 1], rows likewise
+ * from j; with S0 .. S3 the four columns of a row, r = ((S0 + 3.0f * S1) + 3.0f * S2) + S3; with r0 .. r3 the four rows,
+ * v = ((r0 + 3.0f * r1) + 3.0f * r2) + r3; D_k = v * (1.0f / 64.0f).
+ * Up, in place in the scratch.  U_levels = D_levels; for k = levels - 1 down to 1: U_k = D_k + spread * up_k(U_{k+1}).  up_k at texel
+ * (x, y) of level k: i = x >> 1; i2 = (x & 1) ? min(i + 1, w_{k+1} - 1) : max(i - 1, 0); j and j2 likewise from y and h_{k+1};
+ * up = 0.75f * (0.75f * U(i, j) + 0.25f * U(i2, j)) + 0.25f * (0.75f * U(i, j2) + 0.25f * U(i2, j2)).  After the call level k of the
+ * scratch holds U_k.
+ * Composite.  For a pixel p of the set, with (x, y) its coordinates in its rectangle: out[p].xyz = color[p].xyz + a * up_0(U_1) and
+ * out[p].w = 1.0f, where a = intensity * (1.0f / n) with n = 1; repeat levels - 1 times: n = n * spread + 1 (float32, on the host): a
+ * constant source of value B comes back as intensity * B.  color[p] enters raw: a NaN pixel stays NaN, and the tone mapper turns it into 0.
+ * out may be exactly color: the pyramid is complete before the first pixel is written.
+ *
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx, desc, color, out or scratch; no
+ * pt_resize yet; a plane that fails the pointer checks; scratch not 16-byte aligned; a forbidden overlap (out and scratch overlap nothing,
+ * except out exactly color); flags != 0; levels outside 1 .. PT_BLOOM_MAX_LEVELS; exposure or clamp not finite or not > 0; threshold, knee
+ * or intensity not finite or < 0; spread outside [0, 1] or NaN.
+ * Ordering and state, as pt_tonemap_planes: the call waits for the frames in flight, runs on pt_stream(ctx) under the STREAM CONTRACT, is
+ * complete when it returns, and writes no context state.
+ * Not part of this interface: lens-flare or anamorphic shapes and a dirt mask; sources restricted by the hit plane (sky only, emitters
+ * only); temporal smoothing of the pyramid; a pyramid kept across calls; an asynchronous variant; a pt_multi_* wrapper (per-rank calls work
+ * once the colour is gathered); the composite fused into pt_tonemap_planes. */
+#define PT_BLOOM_MAX_LEVELS 8
+/* scratch pyramid in caller memory: bytes for `levels` levels of every view (or of the frame without views);
+ * dims (HOST, nv x PT_BLOOM_MAX_LEVELS x 4: w_k, h_k, first float4 of the level, 0; may be NULL) */
+int pt_bloom_layout(const pt_ctx* ctx, uint32_t levels, uint32_t* dims, size_t* bytes);
+
+typedef struct pt_bloom_desc {
+    const float* color;      /* w*h x 4 linear radiance (.w ignored); required */
+    const float* state;      /* nv x 4 (pt_exposure_planes's state_out) or NULL */
+    float*       out;        /* w*h x 4; required; exclusive except that it may be exactly color */
+    void*        scratch;    /* pt_bloom_layout's bytes, 16-byte aligned; required, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    float exposure;          /* finite, > 0: multiplies the metered exposure, as in pt_tonemap_desc */
+    float threshold;         /* finite, >= 0, on exposed luminance */
+    float knee;              /* finite, >= 0 */
+    float clamp;             /* finite, > 0: source radiance is clamped to it (one firefly must not own the frame) */
+    float spread;            /* [0, 1]: weight of each coarser level relative to the next finer one */
+    float intensity;         /* finite, >= 0 */
+    uint32_t levels;         /* 1..PT_BLOOM_MAX_LEVELS */
+    uint32_t flags;          /* 0 */
+} pt_bloom_desc;
+typedef struct pt_bloom_stats { uint64_t pixels, sources, bright, nonfinite; double kernel_ms; } pt_bloom_stats;
+int pt_bloom_planes(pt_ctx* ctx, const pt_bloom_desc* desc, pt_bloom_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

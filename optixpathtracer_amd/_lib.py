@@ -29,7 +29,7 @@ EXPORTS = [
     "pt_vertex_count", "pt_copy_vertices_device", "pt_motion_planes", "pt_temporal_moments", "pt_modulate_planes",
     "pt_sample_plan", "pt_temporal_carry", "pt_copy_texcoords_device", "pt_surface_planes",
     "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes", "pt_surface_aniso_planes",
-    "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes",
+    "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes", "pt_bloom_layout", "pt_bloom_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -265,6 +265,27 @@ class TonemapStats(C.Structure):  # pt_tonemap_stats
 EXPOSURE_PLANES = {"color": 4, "hit": 8}
 TONEMAP_PLANES = {"color": 4, "out": 4, "frame_rgba8": 1}
 TONEMAP_OUTPUTS = ("out", "frame_rgba8")
+
+
+PT_BLOOM_MAX_LEVELS = 8
+
+
+class BloomDesc(C.Structure):  # pt_bloom_desc
+    _fields_ = [("color", C.c_void_p), ("state", C.c_void_p), ("out", C.c_void_p), ("scratch", C.c_void_p), ("block_mask", C.c_void_p),
+                ("exposure", C.c_float), ("threshold", C.c_float), ("knee", C.c_float), ("clamp", C.c_float), ("spread", C.c_float),
+                ("intensity", C.c_float), ("levels", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class BloomStats(C.Structure):  # pt_bloom_stats
+    _fields_ = [("pixels", C.c_uint64), ("sources", C.c_uint64), ("bright", C.c_uint64), ("nonfinite", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the frame-sized planes of pt_bloom_planes: 32-bit words per pixel (the scratch pyramid is pt_bloom_layout's, the state words per view)
+BLOOM_PLANES = {"color": 4, "out": 4}
+BLOOM_OUTPUTS = ("out",)
 
 
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
@@ -565,6 +586,8 @@ def load_library() -> C.CDLL:
     L.pt_edge_aa_planes.argtypes = [vp, C.POINTER(EdgeAaDesc), C.POINTER(EdgeAaStats)]
     L.pt_exposure_planes.argtypes = [vp, C.POINTER(ExposureDesc), C.POINTER(ExposureStats)]
     L.pt_tonemap_planes.argtypes = [vp, C.POINTER(TonemapDesc), C.POINTER(TonemapStats)]
+    L.pt_bloom_layout.argtypes = [vp, u32, vp, C.POINTER(C.c_size_t)]
+    L.pt_bloom_planes.argtypes = [vp, C.POINTER(BloomDesc), C.POINTER(BloomStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

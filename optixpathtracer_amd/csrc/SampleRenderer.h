@@ -428,6 +428,22 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The size in bytes of bloomPlanes's scratch pyramid for `levels` levels of every view (pt_bloom_layout); dims (host memory,
+    // views x PT_BLOOM_MAX_LEVELS x 4: w, h, first 16-byte texel, 0) may be null.
+    size_t bloomLayout(uint32_t levels, uint32_t* dims = nullptr) {
+        size_t bytes = 0;
+        ck(pt_bloom_layout(ctx, levels, dims, &bytes));
+        return bytes;
+    }
+    // Bloom in front of the tone mapper (pt_bloom_planes): the part of d.color above d.threshold, spread over a pyramid per view in
+    // d.scratch (bloomLayout's bytes, 16-byte aligned) and added back into d.out, which may be d.color.  Returns the pixels written, the
+    // source pixels read, the bright and the non-finite ones among them and the device time.
+    pt_bloom_stats bloomPlanes(const pt_bloom_desc& d, pt_bloom_stats* stats = nullptr) {
+        pt_bloom_stats s{};
+        ck(pt_bloom_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

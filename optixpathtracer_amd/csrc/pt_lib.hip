@@ -21,3 +21,4 @@
 #include "pt_upsample.hip"
 #include "pt_edge_aa.hip"
 #include "pt_exposure.hip"
+#include "pt_bloom.hip"

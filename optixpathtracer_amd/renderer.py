@@ -957,6 +957,54 @@ class SampleRenderer:
         desc.exposure, desc.white, desc.op, desc.flags = float(exposure), float(white), _lib.TONEMAP_OPS[op], 0
         return self._run_pass("pt_tonemap_planes", desc, _lib.TonemapStats(), result)
 
+    def bloomLayout(self, levels=6):
+        """The shape of bloomPlanes's scratch pyramid (pt_bloom_layout): (dims, bytes) with dims a uint32 (views, 8, 4) array of w, h, the
+        index of the level's first 16-byte texel and 0 per level (zeros above `levels`), views = max(1, the view count), and bytes the
+        size of the scratch for `levels` levels of every view."""
+        levels = int(levels)
+        if not 1 <= levels <= _lib.PT_BLOOM_MAX_LEVELS:
+            raise ValueError(f"bloomLayout: levels must be 1..{_lib.PT_BLOOM_MAX_LEVELS}, not {levels}")
+        count, nbytes = C.c_uint32(0), C.c_size_t()
+        self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
+        dims = np.zeros((max(1, count.value), _lib.PT_BLOOM_MAX_LEVELS, 4), np.uint32)
+        self._ck(self._L.pt_bloom_layout(self._ctx, levels, dims.ctypes.data, C.byref(nbytes)), "pt_bloom_layout")
+        return dims, nbytes.value
+
+    def bloomPlanes(self, color, state=None, out=None, scratch=None, mask=None, exposure=1.0, threshold=1.0, knee=0.5, clamp=65504.0,
+                    spread=0.7, intensity=0.25, levels=6) -> dict:
+        """Bloom in front of the tone mapper (pt_bloom_planes, include/pt_amd.h: the rule, in full): the part of `color` whose exposed
+        luminance lies above `threshold` (soft over `knee`, the source clamped to `clamp`) is filtered down a pyramid of `levels` levels
+        per view and back up, each coarser level weighing `spread` of the next finer one, and added to the colour: out = color +
+        intensity * bloom, scene-linear, for tonemapPlanes with the same state.
+
+        color (h, w, 4) is a CUDA float32 tensor or a raw device pointer; state as tonemapPlanes takes it (the exposure is read on the
+        device; 1 when None).  out (h, w, 4) may be `color` itself; allocated when None.  scratch: a float32 (texels, 4) tensor with
+        16 * texels = bloomLayout(levels)'s bytes, 16-byte aligned, or a raw pointer; allocated when None.  After the call it holds the
+        pyramid U_1 .. U_levels of every view.  The pyramid reads every pixel of every view whatever the mask and the rank's partition:
+        they decide only which pixels of out are written (a partitioned frame gathers its colour first).
+        Returns {"out", "scratch": the tensor (None for a raw pointer), "stats": {pixels, sources, bright, nonfinite, kernel_ms}}."""
+        import torch
+
+        levels = int(levels)
+        if not 1 <= levels <= _lib.PT_BLOOM_MAX_LEVELS:
+            raise ValueError(f"bloomPlanes: levels must be 1..{_lib.PT_BLOOM_MAX_LEVELS}, not {levels}")
+        desc = _lib.BloomDesc()
+        result = self._bind_planes("bloomPlanes", desc, dict(color=color, out=out), _lib.BLOOM_PLANES, ("color",), _lib.BLOOM_OUTPUTS, alloc=("out",))
+        desc.state, _ = self._view_words("bloomPlanes", "state", state, torch.float32, 4)
+        dev = getattr(self, "_device", 0)
+        if isinstance(scratch, int):
+            desc.scratch, result["scratch"] = scratch, None
+        else:
+            texels = self.bloomLayout(levels)[1] // 16
+            if scratch is None:
+                scratch = torch.empty((texels, 4), dtype=torch.float32, device=f"cuda:{dev}")
+            _check_temporal_tensor("scratch", scratch, dev, {torch.float32: (texels, 4)}, "bloomPlanes")
+            desc.scratch, result["scratch"] = scratch.data_ptr(), scratch
+        m = self._bind_mask("bloomPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.exposure, desc.threshold, desc.knee, desc.clamp = float(exposure), float(threshold), float(knee), float(clamp)
+        desc.spread, desc.intensity, desc.levels, desc.flags = float(spread), float(intensity), levels, 0
+        return self._run_pass("pt_bloom_planes", desc, _lib.BloomStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
