@@ -1,6 +1,13 @@
-// pt_api.hip — the C ABI of libptamd.so (include/pt_amd.h): context, device memory, and the
-// per-frame wavefront schedule that replaces SampleRenderer::render()'s single optixLaunch
-// (SimplePathtracer.cpp:73-97).
+// pt_api.hip — the frame path of libptamd.so's C ABI (include/pt_amd.h): the context and the owner of its device memory, create / destroy,
+// options, probe, camera, partition and resize, and the per-frame wavefront schedule that replaces SampleRenderer::render()'s single
+// optixLaunch (SimplePathtracer.cpp:73-97) behind pt_render, pt_render_batch, pt_render_device and pt_render_regions; with them the
+// buffer access (pt_device_buffer, pt_download, pt_upload_accum), pt_stream / pt_wait_event and pt_get_stats.  First part of pt_lib.hip.
+//
+// This is the one host file among the kernel sources that bench.py hashes: an edit here un-gates the counter figures of the bench line.
+// So code goes in here only if a default pt_render frame runs it.  Everything else of the C ABI lives in the area files that pt_lib.hip
+// includes behind this one (pt_subset.hip, pt_post.hip, pt_handoff.hip, pt_query.hip, pt_views.hip, pt_inspect.hip, pt_update.hip,
+// pt_multi.hip); they use the context, fail, CK, drain, buffer_ptr and bvh_dev from here, and nothing here calls into them except drain,
+// through the forward declaration of query_complete.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <chrono>
@@ -2147,206 +2154,6 @@ extern "C" int pt_render_regions(pt_ctx* ctx, const pt_region* regions, uint32_t
     return PT_OK;
 }
 
-// ------------------------------------------------------------------ block masks and adaptive stopping
-// the block table of the current size and partition: block b's pixels are d_pixels[start, start + size) (build_pixel_lists walks the same order)
-static int build_blocks(pt_ctx* ctx) {
-    pt_ctx::Blocks& B = ctx->blk;
-    const int w = ctx->width, h = ctx->height;
-    B.nbx = (uint32_t)(w + 7) / 8u;
-    B.nby = (uint32_t)(h + 7) / 8u;
-    B.nblk = B.nbx * B.nby;
-    std::vector<BlockSpan> spans(B.nblk);
-    uint32_t at = 0;
-    B.owned_blocks = 0;
-    for (uint32_t by = 0; by < B.nby; ++by)
-        for (uint32_t bx = 0; bx < B.nbx; ++bx) {
-            const int owner = (int)(((bx * 8u) / (uint32_t)ctx->tile_w + (by * 8u) / (uint32_t)ctx->tile_h) % (uint32_t)ctx->world);
-            uint32_t size = owner == ctx->rank ? (uint32_t)(std::min(8, w - (int)bx * 8) * std::min(8, h - (int)by * 8)) : 0u;
-            if (size && ctx->vw.n) { // viewports: the block's pixels inside its view (the order of the view pixel list, pt_set_views)
-                const uint16_t vi = ctx->vw.vblock[by * B.nbx + bx];
-                if (vi == 0xffffu) {
-                    size = 0u;
-                } else {
-                    const pt_view& v = ctx->vw.host[vi];
-                    size = (uint32_t)(std::min(8, v.x + v.width - (int)bx * 8) * std::min(8, v.y + v.height - (int)by * 8));
-                }
-            }
-            spans[by * B.nbx + bx] = BlockSpan{at, size};
-            B.owned_flags.push_back(size ? 1 : 0);
-            at += size;
-            B.owned_blocks += size ? 1u : 0u;
-        }
-    if (at != ctx->frame_owned()) return fail(ctx, PT_ERR_INVALID, "block table does not match the pixel list");
-    CK(B.mem.alloc(&B.d_spans, (size_t)B.nblk));
-    CK(B.mem.alloc(&B.d_flags, (size_t)B.nblk));
-    CK(B.mem.alloc(&B.d_offsets, (size_t)B.nblk));
-    B.nparts = (B.nblk + 255u) / 256u;
-    CK(B.mem.alloc(&B.d_parts, (size_t)2 * B.nparts));
-    CK(B.mem.alloc(&B.d_list, (size_t)ctx->owned));
-    CK(B.mem.alloc(&B.d_counts, (size_t)2));
-    CK(B.mem.pinned(&B.h_counts, 2));
-    CK(hipMemcpy(B.d_spans, spans.data(), sizeof(BlockSpan) * B.nblk, hipMemcpyHostToDevice));
-    return PT_OK;
-}
-static int ensure_blocks(pt_ctx* ctx) {
-    if (ctx->blk.d_spans) return PT_OK;
-    const int rc = build_blocks(ctx); // (into the empty group: d_spans, its first allocation, is what says "built")
-    if (rc) ctx->blk = pt_ctx::Blocks{}; // all of it or nothing: the next call starts over
-    return rc;
-}
-// flags -> compacted list + counts, then the copy of `words` counts (1: pixels; 2: and blocks) to the pinned host words; all on stream s
-static int compact_enqueue(pt_ctx* ctx, hipStream_t s, const uint8_t* d_flags, uint32_t* d_list, int words) {
-    pt_ctx::Blocks& B = ctx->blk;
-    uint32_t *part_pix = B.d_parts, *part_blk = B.d_parts + B.nparts;
-    hipLaunchKernelGGL(k_mask_partials, dim3(B.nparts), dim3(256), 0, s, d_flags, B.d_spans, B.nblk, B.d_offsets, part_pix, part_blk);
-    hipLaunchKernelGGL(k_mask_scan_parts, dim3(1), dim3(1024), 0, s, part_pix, part_blk, B.nparts, B.d_counts);
-    hipLaunchKernelGGL(k_mask_compact, dim3((B.nblk + 3u) / 4u), dim3(256), 0, s, d_flags, B.d_spans, B.nblk, B.d_offsets, part_pix, ctx->frame_pixels(), d_list);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(B.h_counts, B.d_counts, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s));
-    return PT_OK;
-}
-// what pt_render_mask and the adaptive entry points refuse alike; leaves the context drained and its device current
-static int subset_open(pt_ctx* ctx, const char* what, bool check_spp, uint32_t spp) {
-    int rc = drain(ctx); // synchronous: frames in flight (pt_options.frames_in_flight) finish first
-    if (rc) return rc;
-    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, (std::string(what) + ": no frame size yet (pt_resize)").c_str());
-    if (check_spp && (spp == 0 || spp > 4096)) return fail(ctx, PT_ERR_INVALID, (std::string(what) + ": samples_per_launch must be in [1,4096]").c_str());
-    CK(hipSetDevice(ctx->device));
-    return ensure_blocks(ctx);
-}
-static int subset_render(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, const PixelSubset& sub, uint32_t* host_rgba8) {
-    int rc = render_enqueue(ctx, spp, subframe_index, 0, 0, 1, &sub);
-    if (rc == PT_OK) rc = render_finish(ctx);
-    if (rc != PT_OK) return rc;
-    if (host_rgba8) return pt_download(ctx, PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)ctx->width * ctx->height);
-    return PT_OK;
-}
-
-extern "C" int pt_render_mask(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, const uint8_t* block_mask, uint32_t* host_rgba8, uint32_t* active_pixels) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_render_mask: null context");
-    if (!block_mask) return fail(ctx, PT_ERR_INVALID, "pt_render_mask: null block mask");
-    int rc = subset_open(ctx, "pt_render_mask", true, spp);
-    if (rc) return rc;
-    pt_ctx::Blocks& B = ctx->blk;
-    CK(hipMemcpyAsync(B.d_flags, block_mask, B.nblk, hipMemcpyHostToDevice, ctx->stream));
-    rc = compact_enqueue(ctx, ctx->stream, B.d_flags, B.d_list, 1);
-    if (rc) return rc;
-    CK(hipStreamSynchronize(ctx->stream)); // the chunking is decided on the host: it needs the count
-    const PixelSubset sub{B.d_list, B.h_counts[0], nullptr, nullptr};
-    if (active_pixels) *active_pixels = sub.count;
-    return subset_render(ctx, spp, subframe_index, sub, host_rgba8);
-}
-
-// the arrays and events of pt_adaptive_begin and the first active list, into the emptied group
-static int adaptive_build(pt_ctx* ctx) {
-    pt_ctx::Blocks& B = ctx->blk;
-    pt_ctx::Adaptive& A = ctx->ad;
-    const size_t n = (size_t)ctx->width * ctx->height;
-    CK(A.mem.alloc(&A.d_moments, n));
-    CK(A.mem.alloc(&A.d_active, (size_t)B.nblk));
-    CK(A.mem.alloc(&A.d_list, (size_t)ctx->owned));
-    CK(A.mem.event(&A.ev0));
-    CK(A.mem.event(&A.ev1));
-    CK(hipMemsetAsync(A.d_moments, 0, sizeof(float4) * n, ctx->stream));
-    CK(hipMemcpyAsync(A.d_active, B.owned_flags.data(), B.nblk, hipMemcpyHostToDevice, ctx->stream)); // (blocks of other ranks are never active)
-    const int rc = compact_enqueue(ctx, ctx->stream, A.d_active, A.d_list, 2);
-    if (rc) return rc;
-    CK(hipStreamSynchronize(ctx->stream));
-    A.count = B.h_counts[0];
-    A.active_blocks = B.h_counts[1];
-    return PT_OK;
-}
-extern "C" int pt_adaptive_begin(pt_ctx* ctx, const pt_adaptive_params* prm) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_adaptive_begin: null context");
-    if (!prm) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: null parameters");
-    if (!(prm->threshold >= 0.f) || !std::isfinite(prm->threshold)) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: threshold must be finite and >= 0");
-    if (!(prm->dark_floor >= 0.f) || !std::isfinite(prm->dark_floor)) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: dark_floor must be finite and >= 0");
-    if (prm->min_subframes < 2) return fail(ctx, PT_ERR_INVALID, "pt_adaptive_begin: min_subframes must be at least 2");
-    if (ctx->vw.n) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_adaptive_begin: not with viewports set (pt_set_views)");
-    int rc = subset_open(ctx, "pt_adaptive_begin", false, 0);
-    if (rc) return rc;
-    ctx->ad = pt_ctx::Adaptive{};
-    rc = adaptive_build(ctx);
-    if (rc) {
-        hipStreamSynchronize(ctx->stream); // what was enqueued on the arrays
-        ctx->ad = pt_ctx::Adaptive{};
-        return rc;
-    }
-    ctx->ad.prm = *prm;
-    ctx->ad.on = true;
-    return PT_OK;
-}
-
-extern "C" int pt_render_adaptive(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, uint32_t* host_rgba8, pt_adaptive_stats* out) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_render_adaptive: null context");
-    if (!ctx->ad.on) return fail(ctx, PT_ERR_INVALID, "pt_render_adaptive: call pt_adaptive_begin first");
-    int rc = subset_open(ctx, "pt_render_adaptive", true, spp);
-    if (rc) return rc;
-    pt_ctx::Blocks& B = ctx->blk;
-    pt_ctx::Adaptive& A = ctx->ad;
-    const uint32_t rendered = A.count;
-    PixelSubset sub{A.d_list, rendered, A.d_moments, nullptr};
-    if (rendered) // behind the frame's last kernel: decide for the blocks just rendered, then compact for the next call (in place: every reader of the list has finished)
-        sub.tail = [ctx](hipStream_t s) -> int {
-            pt_ctx::Blocks& B = ctx->blk;
-            pt_ctx::Adaptive& A = ctx->ad;
-            const AdaptParams ap{A.prm.threshold, A.prm.dark_floor, (float)A.prm.min_subframes, (float)A.prm.max_subframes};
-            CK(hipEventRecord(A.ev0, s));
-            hipLaunchKernelGGL(k_adapt_decide, dim3((B.nblk + 3u) / 4u), dim3(256), 0, s, A.d_moments, A.d_active, B.d_spans, B.nblk, B.nbx, ctx->width, ctx->height, ap);
-            int rc = compact_enqueue(ctx, s, A.d_active, A.d_list, 2);
-            if (rc) return rc;
-            CK(hipEventRecord(A.ev1, s));
-            return PT_OK;
-        };
-    rc = subset_render(ctx, spp, subframe_index, sub, host_rgba8);
-    if (rc) return rc;
-    float ms = 0.f;
-    if (rendered) {
-        A.count = B.h_counts[0];
-        A.active_blocks = B.h_counts[1];
-        A.pixel_subframes += rendered;
-        CK(hipEventElapsedTime(&ms, A.ev0, A.ev1));
-    }
-    if (out) {
-        out->blocks = B.owned_blocks;
-        out->active_blocks = A.active_blocks;
-        out->active_pixels = rendered;
-        out->pixel_subframes = A.pixel_subframes;
-        out->decide_ms = ms;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_adaptive_end(pt_ctx* ctx) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_adaptive_end: null context");
-    int rc = drain(ctx);
-    if (rc) return rc;
-    if (ctx->ad.on) {
-        CK(hipSetDevice(ctx->device));
-        CK(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->ad = pt_ctx::Adaptive{};
-    return PT_OK;
-}
-
-extern "C" int pt_download_adaptive(pt_ctx* ctx, int which, void* host, size_t bytes) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_download_adaptive: null context");
-    if (!host) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: null destination");
-    if (!ctx->ad.on) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: call pt_adaptive_begin first");
-    const pt_ctx::Blocks& B = ctx->blk;
-    CK(hipSetDevice(ctx->device));
-    if (which == PT_ADAPT_MOMENTS) {
-        if (bytes != sizeof(float4) * (size_t)ctx->width * ctx->height) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: byte count does not match the frame size");
-        CK(hipMemcpy(host, ctx->ad.d_moments, bytes, hipMemcpyDeviceToHost));
-    } else if (which == PT_ADAPT_ACTIVE) {
-        if (bytes != (size_t)B.nblk) return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: byte count does not match the block grid");
-        CK(hipMemcpy(host, ctx->ad.d_active, bytes, hipMemcpyDeviceToHost));
-    } else {
-        return fail(ctx, PT_ERR_INVALID, "pt_download_adaptive: unknown array");
-    }
-    return PT_OK;
-}
-
 static void* buffer_ptr(pt_ctx* ctx, int which, size_t* elem) {
     switch (which) {
         case PT_BUF_ACCUM: *elem = 16; return ctx->fb.accum;
@@ -2388,202 +2195,6 @@ extern "C" int pt_upload_accum(pt_ctx* ctx, const float* host, size_t bytes) {
     return PT_OK;
 }
 
-extern "C" int pt_tonemap_sqrt(pt_ctx* ctx, uint32_t* host_rgba8) {
-    if (!ctx) return PT_ERR_INVALID;
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    if (ctx->width == 0) return PT_OK;
-    CK(hipSetDevice(ctx->device));
-    const uint32_t n = (uint32_t)ctx->width * ctx->height;
-    hipLaunchKernelGGL(k_tonemap_sqrt, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->fb.accum, ctx->fb.frame, n);
-    CK(hipStreamSynchronize(ctx->stream));
-    if (host_rgba8) return pt_download(ctx, PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)n);
-    return PT_OK;
-}
-
-// OptiXDenoiser::exec() + the computeFinalPixelColors call of render(target) (SimplePathtracer.cpp:104-105)
-extern "C" int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, uint32_t* host_rgba8, double* kernel_ms) {
-    if (!ctx || !prm) return PT_ERR_INVALID;
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    if (ctx->width == 0) return PT_OK;
-    if (prm->iterations < 0 || prm->iterations > 8) return fail(ctx, PT_ERR_INVALID, "pt_denoise: iterations must be in [0,8]");
-    if (!(prm->sigma_color > 0.f) || !(prm->sigma_normal > 0.f) || !(prm->sigma_albedo > 0.f)) return fail(ctx, PT_ERR_INVALID, "pt_denoise: sigmas must be positive");
-    if (prm->input != PT_BUF_COLOR && prm->input != PT_BUF_ACCUM) return fail(ctx, PT_ERR_INVALID, "pt_denoise: input must be PT_BUF_COLOR or PT_BUF_ACCUM");
-    if (prm->epilogue < 0 || prm->epilogue > 2) return fail(ctx, PT_ERR_INVALID, "pt_denoise: unknown epilogue");
-    CK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)ctx->width * ctx->height;
-    if (!ctx->fb.denoise_tmp) { // (the second of the pair: both or neither)
-        ctx->fb.mem.drop(ctx->fb.denoised);
-        CK(ctx->fb.mem.alloc(&ctx->fb.denoised, n));
-        CK(ctx->fb.mem.alloc(&ctx->fb.denoise_tmp, n));
-    }
-    DevOwner tmp;
-    hipEvent_t e0, e1;
-    CK(tmp.event(&e0));
-    CK(tmp.event(&e1));
-    const float4* src = prm->input == PT_BUF_COLOR ? ctx->fb.color : ctx->fb.accum;
-    CK(hipEventRecord(e0, ctx->stream));
-    if (prm->iterations == 0) CK(hipMemcpyAsync(ctx->fb.denoised, src, sizeof(float4) * n, hipMemcpyDeviceToDevice, ctx->stream));
-    // ping-pong so that the last pass lands in `denoised`
-    float4* bufs[2] = {ctx->fb.denoised, ctx->fb.denoise_tmp};
-    int cur = (prm->iterations & 1) ? 0 : 1;
-    const dim3 grid((ctx->width + 31) / 32, (ctx->height + 7) / 8), block(256);
-    for (int i = 0; i < prm->iterations; ++i) {
-        const float sc = prm->sigma_color / (float)(1 << i), sn = prm->sigma_normal * (float)(1 << i);
-        AtrousParams ap{ctx->width, ctx->height, 1 << i, 1.0f / (sc * sc), 1.0f / (sn * sn), 1.0f / (prm->sigma_albedo * prm->sigma_albedo)};
-        hipLaunchKernelGGL(k_atrous, grid, block, 0, ctx->stream, src, ctx->fb.normal, ctx->fb.albedo, bufs[cur], ap);
-        src = bufs[cur];
-        cur ^= 1;
-    }
-    if (prm->epilogue == 1)
-        hipLaunchKernelGGL(k_tonemap_sqrt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->fb.denoised, ctx->fb.frame, (uint32_t)n);
-    else if (prm->epilogue == 2)
-        hipLaunchKernelGGL(k_make_color, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->fb.denoised, ctx->fb.frame, (uint32_t)n);
-    CK(hipEventRecord(e1, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    CK(hipGetLastError());
-    float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
-    if (kernel_ms) *kernel_ms = ms;
-    if (host_rgba8 && prm->epilogue) return pt_download(ctx, PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * n);
-    return PT_OK;
-}
-
-extern "C" int pt_owned_pixels(const pt_ctx* ctx, uint32_t* owned, uint32_t* padded) {
-    if (!ctx) return PT_ERR_INVALID;
-    if (owned) *owned = ctx->owned;
-    if (padded) *padded = ctx->padded;
-    return PT_OK;
-}
-
-static int pack_launch(pt_ctx* ctx, int which, void* dev_dst);
-static int unpack_launch(pt_ctx* ctx, int which, const void* dev_src_all);
-extern "C" int pt_pack(pt_ctx* ctx, int which, void* dev_dst) {
-    if (!ctx || !dev_dst) return PT_ERR_INVALID;
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    int rc = pack_launch(ctx, which, dev_dst);
-    if (rc != PT_OK) return rc;
-    CK(hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-extern "C" int pt_unpack(pt_ctx* ctx, int which, const void* dev_src_all) {
-    if (!ctx || !dev_src_all) return PT_ERR_INVALID;
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    int rc = unpack_launch(ctx, which, dev_src_all);
-    if (rc != PT_OK) return rc;
-    CK(hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-static int newest_active(pt_ctx* ctx) {
-    int o = -1;
-    for (int i = 0; i < PT_MAX_FRAMES; ++i)
-        if (ctx->fr[i].active && (o < 0 || ctx->fr[i].seq > ctx->fr[o].seq)) o = i;
-    return o;
-}
-static size_t buffer_elem(int which) { return which == PT_BUF_FRAME ? 4 : ((which >= 0 && which <= PT_BUF_DENOISED) ? 16 : 0); }
-
-// ---- overlapped display hand-off (include/pt_amd.h): nothing here waits for a frame on the host
-static int pack_async_enqueue(pt_ctx* ctx, int which, void* dev_dst, int slot) {
-    if (slot < 0 || slot > 1) return fail(ctx, PT_ERR_INVALID, "pt_pack_async: slot must be 0 or 1");
-    CK(hipSetDevice(ctx->device));
-    const int nf = newest_active(ctx);
-    if (nf >= 0) CK(hipStreamWaitEvent(ctx->stream, ctx->fr[nf].ev_end, 0)); // the newest frame enqueued; earlier ones end before it writes the buffers
-    int rc = pack_launch(ctx, which, dev_dst);
-    if (rc != PT_OK) return rc;
-    if (!ctx->ev_packed[slot]) CK(ctx->misc.event(&ctx->ev_packed[slot], hipEventDisableTiming));
-    CK(hipEventRecord(ctx->ev_packed[slot], ctx->stream));
-    ctx->ev_pack_guard = ctx->ev_packed[slot];
-    return PT_OK;
-}
-extern "C" int pt_pack_async(pt_ctx* ctx, int which, void* dev_dst, int slot) {
-    if (!ctx || !dev_dst) return PT_ERR_INVALID;
-    return pack_async_enqueue(ctx, which, dev_dst, slot);
-}
-extern "C" int pt_pack_wait(pt_ctx* ctx, int slot) {
-    if (!ctx || slot < 0 || slot > 1) return PT_ERR_INVALID;
-    if (!ctx->ev_packed[slot]) return PT_OK;
-    CK(hipSetDevice(ctx->device));
-    CK(hipEventSynchronize(ctx->ev_packed[slot]));
-    return PT_OK;
-}
-static int unpack_display_enqueue(pt_ctx* ctx, int which, const void* dev_src_all) {
-    const size_t elem = buffer_elem(which);
-    if (!elem || ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_unpack_display: unknown buffer or not resized");
-    CK(hipSetDevice(ctx->device));
-    const size_t npx = (size_t)ctx->width * ctx->height;
-    if (!ctx->fb.display[which]) {
-        uint8_t* d = nullptr;
-        CK(ctx->fb.mem.alloc(&d, npx * elem));
-        CK(hipMemsetAsync(d, 0, npx * elem, ctx->stream));
-        ctx->fb.display[which] = d;
-    }
-    const uint32_t n = ctx->padded * (uint32_t)ctx->world;
-    if (n) {
-        if (elem == 16)
-            hipLaunchKernelGGL((k_unpack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float4*)ctx->fb.display[which], ctx->fb.d_all_pixels, n, ctx->width, (const float4*)dev_src_all);
-        else
-            hipLaunchKernelGGL((k_unpack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)ctx->fb.display[which], ctx->fb.d_all_pixels, n, ctx->width, (const uint32_t*)dev_src_all);
-    }
-    if (!ctx->ev_displayed) CK(ctx->misc.event(&ctx->ev_displayed, hipEventDisableTiming));
-    CK(hipEventRecord(ctx->ev_displayed, ctx->stream));
-    return PT_OK;
-}
-extern "C" int pt_unpack_display(pt_ctx* ctx, int which, const void* dev_src_all) {
-    if (!ctx || !dev_src_all) return PT_ERR_INVALID;
-    return unpack_display_enqueue(ctx, which, dev_src_all);
-}
-extern "C" int pt_display_sync(pt_ctx* ctx) {
-    if (!ctx) return PT_ERR_INVALID;
-    if (!ctx->ev_displayed) return PT_OK;
-    CK(hipSetDevice(ctx->device));
-    CK(hipEventSynchronize(ctx->ev_displayed));
-    return PT_OK;
-}
-extern "C" void* pt_display_buffer(pt_ctx* ctx, int which) {
-    if (!ctx || which < 0 || which > PT_BUF_DENOISED) return nullptr;
-    return ctx->fb.display[which];
-}
-extern "C" int pt_download_display(pt_ctx* ctx, int which, void* host, size_t bytes) {
-    if (!ctx || !host) return PT_ERR_INVALID;
-    const size_t elem = buffer_elem(which);
-    if (!elem || !ctx->fb.display[which]) return fail(ctx, PT_ERR_INVALID, "pt_download_display: nothing has been handed over into this buffer");
-    if (bytes != elem * (size_t)ctx->width * ctx->height) return fail(ctx, PT_ERR_INVALID, "pt_download_display: byte count does not match the frame size");
-    int rc = pt_display_sync(ctx);
-    if (rc != PT_OK) return rc;
-    CK(hipMemcpy(host, ctx->fb.display[which], bytes, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// the kernels alone, on the context's stream (pt_multi_gather chains pack -> exchange -> unpack without host waits)
-static int pack_launch(pt_ctx* ctx, int which, void* dev_dst) {
-    size_t elem;
-    void* p = buffer_ptr(ctx, which, &elem);
-    if (!p) return fail(ctx, PT_ERR_INVALID, "pt_pack: unknown buffer or not resized");
-    CK(hipSetDevice(ctx->device));
-    const uint32_t n = ctx->owned;
-    if (n) {
-        if (elem == 16)
-            hipLaunchKernelGGL((k_pack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)p, ctx->fb.d_pixels, n, ctx->width, (float4*)dev_dst);
-        else
-            hipLaunchKernelGGL((k_pack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)p, ctx->fb.d_pixels, n, ctx->width, (uint32_t*)dev_dst);
-    }
-    return PT_OK;
-}
-
-static int unpack_launch(pt_ctx* ctx, int which, const void* dev_src_all) {
-    size_t elem;
-    void* p = buffer_ptr(ctx, which, &elem);
-    if (!p) return fail(ctx, PT_ERR_INVALID, "pt_unpack: unknown buffer or not resized");
-    CK(hipSetDevice(ctx->device));
-    const uint32_t n = ctx->padded * (uint32_t)ctx->world;
-    if (n) {
-        if (elem == 16)
-            hipLaunchKernelGGL((k_unpack<float4>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float4*)p, ctx->fb.d_all_pixels, n, ctx->width, (const float4*)dev_src_all);
-        else
-            hipLaunchKernelGGL((k_unpack<uint32_t>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)p, ctx->fb.d_all_pixels, n, ctx->width, (const uint32_t*)dev_src_all);
-    }
-    return PT_OK;
-}
-
 extern "C" int pt_get_stats(const pt_ctx* ctx, pt_stats* out) {
     if (!ctx || !out) return PT_ERR_INVALID;
     {
@@ -2614,1435 +2225,4 @@ extern "C" int pt_get_stats_n(const pt_ctx* ctx, void* out, size_t out_bytes) {
     memcpy(out, &s, out_bytes < sizeof(s) ? out_bytes : sizeof(s)); // fields are only ever appended: a caller built against an older header gets its prefix
     if (out_bytes > sizeof(s)) memset((char*)out + sizeof(s), 0, out_bytes - sizeof(s));
     return PT_OK;
-}
-
-extern "C" int pt_trace(pt_ctx* ctx, const float* rays, uint32_t n, int any_hit, float* t_out, int32_t* prim_out, int iters,
-                        double* kernel_ms) {
-    if (!ctx || !rays || !prim_out || (!any_hit && !t_out)) return PT_ERR_INVALID;
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    if (n == 0) return PT_OK;
-    CK(hipSetDevice(ctx->device));
-    if (iters < 1) iters = 1;
-    // temporary state just for the query
-    DevOwner tmp;
-    float4 *dO = nullptr, *dD = nullptr;
-    float2* dHit = nullptr;
-    uint32_t *dCount = nullptr, *dWork = nullptr;
-    unsigned long long* dDbg = nullptr;
-    hipEvent_t e0, e1;
-    CK(tmp.alloc(&dO, n)); CK(tmp.alloc(&dD, n)); CK(tmp.alloc(&dHit, n)); CK(tmp.alloc(&dCount, 1));
-    CK(tmp.alloc(&dWork, (size_t)iters));
-    CK(tmp.event(&e0));
-    CK(tmp.event(&e1));
-    std::vector<float4> hO(n), hD(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        const float* r = &rays[8 * (size_t)i];
-        hO[i] = make_float4(r[0], r[1], r[2], r[3]);
-        hD[i] = make_float4(r[4], r[5], r[6], r[7]);
-    }
-    CK(hipMemcpy(dO, hO.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
-    CK(hipMemcpy(dD, hD.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
-    CK(hipMemcpy(dCount, &n, 4, hipMemcpyHostToDevice));
-    PathState st{};
-    st.rayO = dO;
-    st.rayD = dD;
-    st.hit = dHit;
-    if (getenv("PT_DEBUG_COUNTS")) {
-        CK(tmp.alloc(&dDbg, 64));
-        CK(dclear(ctx->stream, dDbg, 512));
-    }
-    CK(hipMemsetAsync(dWork, 0, sizeof(uint32_t) * iters, ctx->stream));
-    CK(hipMemsetAsync(ctx->tot.d_totals + 2, 0, sizeof(unsigned long long), ctx->stream));
-    CK(hipEventRecord(e0, ctx->stream));
-    for (int it = 0; it < iters; ++it) {
-        {
-            Trace8Args ta{st, bvh_dev(ctx), QView{nullptr, dCount, 0}, QView{}, dWork + it, ctx->ovf, 0, dDbg, 0, ctx->lds_skip, ctx->ovf_depth, fault_word(ctx), ctx->bvh.num_nodes8};
-            if (any_hit) hipLaunchKernelGGL((k_trace8<TR_ANY_QUERY>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
-            else hipLaunchKernelGGL((k_trace8<TR_CLOSEST>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
-        }
-    }
-    CK(hipEventRecord(e1, ctx->stream));
-    if (!any_hit) { // hit records name leaf triangles; the caller wants optixGetPrimitiveIndex
-        hipLaunchKernelGGL(k_hits_to_prims, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dHit, ctx->bvh.tris8, n);
-    }
-    CK(hipStreamSynchronize(ctx->stream));
-    CK(hipGetLastError());
-    float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
-    if (kernel_ms) *kernel_ms = ms / iters;
-    {
-        unsigned long long fault = 0;
-        CK(hipMemcpy(&fault, ctx->tot.d_totals + 2, sizeof(fault), hipMemcpyDeviceToHost));
-        if (fault & 1ull) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_trace: traversal stack overflow: the acceleration structure is deeper than the traversal stack");
-    }
-    if (dDbg) {
-        unsigned long long h[8];
-        CK(hipMemcpy(h, dDbg, 64, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[pt_trace] rays %u x %d: node steps/ray %.2f, tri tests/ray %.2f, pushes/ray %.2f, max stack %llu, max steps of one ray %llu, "
-                "wave loop iterations max %llu mean %.1f (waves %llu)\n", n, iters,
-                (double)h[0] / n / iters, (double)h[1] / n / iters, (double)h[3] / n / iters, h[2], h[4], h[5], h[7] ? (double)h[6] / h[7] : 0.0, h[7] / iters);
-    }
-    if (any_hit) {
-        std::vector<float2> hh(n);
-        CK(hipMemcpy(hh.data(), dHit, sizeof(float2) * n, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n; ++i) memcpy(&prim_out[i], &hh[i].y, 4);
-    } else {
-        std::vector<float2> hh(n);
-        CK(hipMemcpy(hh.data(), dHit, sizeof(float2) * n, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n; ++i) {
-            t_out[i] = hh[i].x;
-            memcpy(&prim_out[i], &hh[i].y, 4);
-        }
-    }
-    return PT_OK;
-}
-
-// ------------------------------------------------------------------ pt_trace_device: queries from and to the caller's device arrays
-// One array of the call: memory of the context's device that HIP knows, 4-byte aligned, inside its allocation (pt_update_meshes_device's checks).
-static int query_pointer_validate(pt_ctx* ctx, const void* p, size_t bytes, const char* who, std::string& err, const char* fn = "pt_trace_device", const char* host_fn = "pt_trace") {
-    const std::string name = std::string(fn) + ": " + who;
-    if (!p) { err = name + " is null"; return PT_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(p) & 3u) { err = name + " is not 4-byte aligned"; return PT_ERR_INVALID; }
-    hipPointerAttribute_t at;
-    const hipError_t pe = hipPointerGetAttributes(&at, p);
-    if (pe != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError(); // an unknown pointer leaves hipErrorInvalidValue behind
-        err = name + " is not device memory (for host arrays use " + std::string(host_fn) + ")";
-        return PT_ERR_INVALID;
-    }
-    if (at.device != ctx->device) { err = name + " is memory of device " + std::to_string(at.device) + ", the context is on device " + std::to_string(ctx->device); return PT_ERR_INVALID; }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return PT_OK; }
-    const size_t off = (size_t)((const char*)p - (const char*)base);
-    if (off > size || bytes > size - off) { err = name + " has fewer than " + std::to_string(bytes) + " bytes left in its allocation"; return PT_ERR_INVALID; }
-    return PT_OK;
-}
-
-// Waits for the queued queries and adds what they counted to q.acc; reports the traversal's fault bit.  The host's only wait of a query.
-static int query_complete(pt_ctx* ctx) {
-    pt_ctx::Query& q = ctx->q;
-    if (q.pending == 0) return PT_OK;
-    const uint32_t pending = q.pending;
-    const uint64_t rays = q.pending_rays;
-    q.pending = 0; // whatever happens below, these queries are not waited for twice
-    q.pending_rays = 0;
-    CK(hipSetDevice(ctx->device));
-    CK(hipMemcpyAsync(q.h_counters, q.block, sizeof(QueryCounters), hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    CK(hipGetLastError());
-    for (uint32_t k = 0; k < pending; ++k) {
-        float a = 0, b = 0, c = 0;
-        const hipEvent_t* e = &q.events[4 * (size_t)k];
-        CK(hipEventElapsedTime(&a, e[0], e[1]));
-        CK(hipEventElapsedTime(&b, e[1], e[2]));
-        CK(hipEventElapsedTime(&c, e[2], e[3]));
-        q.acc.stage_ms += a;
-        q.acc.trace_ms += b;
-        q.acc.attrib_ms += c;
-    }
-    q.acc.rays += rays;
-    for (const QuerySlot& sl : q.h_counters->slot) {
-        q.acc.hits += sl.hits;
-        q.acc.invalid_rays += sl.invalid;
-    }
-    if (q.h_counters->fault & 1u) return fail(ctx, PT_ERR_UNSUPPORTED, "pt_trace_device: traversal stack overflow: the acceleration structure is deeper than the traversal stack");
-    return PT_OK;
-}
-
-static const size_t PT_QUERY_BLOCK = sizeof(QueryCounters) + 128; // the counters, the count word, the chunk counter
-// room for n rays and for one more queued query's events; on failure nothing of the context has changed
-static int query_reserve(pt_ctx* ctx, uint32_t n) {
-    pt_ctx::Query& q = ctx->q;
-    if (!q.block) {
-        DevOwner fresh;
-        uint8_t* block = nullptr;
-        QueryCounters* h = nullptr;
-        CK(fresh.alloc(&block, PT_QUERY_BLOCK));
-        if (fresh.pinned(&h, 1) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, PT_ERR_HIP, "pt_trace_device: out of pinned host memory for the counters");
-        }
-        q.mem.adopt(std::move(fresh));
-        q.block = block;
-        q.h_counters = h;
-        q.bytes += PT_QUERY_BLOCK;
-    }
-    if (n > q.cap) {
-        // queued queries still use the old arrays: they finish first (only a query larger than every one before it comes here)
-        { int rc_ = query_complete(ctx); if (rc_ != PT_OK) return rc_; }
-        DevOwner grown; // allocated aside and moved in: a failure leaves the smaller state as it was (the query state is small)
-        float4 *o = nullptr, *d = nullptr;
-        float2* h = nullptr;
-        unsigned long long* m = nullptr;
-        const size_t words = ((size_t)n + 63) / 64;
-        if (grown.alloc(&o, n) != hipSuccess || grown.alloc(&d, n) != hipSuccess || grown.alloc(&h, n) != hipSuccess || grown.alloc(&m, words) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, PT_ERR_HIP, "pt_trace_device: out of device memory for the query state");
-        }
-        q.rays = std::move(grown);
-        q.rayO = o; q.rayD = d; q.hit = h; q.mark = m;
-        q.cap = n;
-        q.bytes = PT_QUERY_BLOCK + (size_t)n * (2 * sizeof(float4) + sizeof(float2)) + words * sizeof(unsigned long long);
-    }
-    while (q.events.size() < 4 * ((size_t)q.pending + 1)) {
-        hipEvent_t e = nullptr;
-        CK(q.mem.event(&e));
-        q.events.push_back(e);
-    }
-    return PT_OK;
-}
-
-static void query_report(pt_ctx* ctx, pt_query_stats* stats) {
-    if (stats) {
-        *stats = ctx->q.acc;
-        stats->state_bytes = ctx->q.bytes;
-    }
-    ctx->q.acc = pt_query_stats{};
-}
-
-extern "C" int pt_query_wait(pt_ctx* ctx, pt_query_stats* stats) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_query_wait: null context");
-    const int rc = query_complete(ctx);
-    query_report(ctx, stats);
-    return rc;
-}
-
-extern "C" int pt_trace_device(pt_ctx* ctx, const float* dev_rays, uint32_t n, uint32_t flags, void* dev_out, pt_query_stats* stats) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_trace_device: null context");
-    if (flags & ~(uint32_t)(PT_QUERY_ANY | PT_QUERY_ASYNC)) return fail(ctx, PT_ERR_INVALID, "pt_trace_device: unknown flag bits");
-    const bool any_hit = (flags & PT_QUERY_ANY) != 0, async = (flags & PT_QUERY_ASYNC) != 0;
-    if (n > 0x80000000u) return fail(ctx, PT_ERR_INVALID, "pt_trace_device: more than 2^31 rays in one call");
-    if (n != 0) {
-        CK(hipSetDevice(ctx->device));
-        const size_t in_bytes = (size_t)n * 32, out_bytes = (size_t)n * (any_hit ? sizeof(int32_t) : sizeof(pt_hit));
-        std::string err;
-        int rc = query_pointer_validate(ctx, dev_rays, in_bytes, "dev_rays", err);
-        if (rc == PT_OK) rc = query_pointer_validate(ctx, dev_out, out_bytes, "dev_out", err);
-        if (rc == PT_OK) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(dev_rays), b = reinterpret_cast<uintptr_t>(dev_out);
-            if (a < b + out_bytes && b < a + in_bytes) { err = "pt_trace_device: dev_rays and dev_out overlap"; rc = PT_ERR_INVALID; }
-        }
-        if (rc != PT_OK) return fail(ctx, rc, err.c_str());
-    }
-    { int rc_ = drain_frames(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight finish first, like pt_trace; queued queries keep running
-    if (n != 0) {
-        { int rc_ = query_reserve(ctx, n); if (rc_ != PT_OK) return rc_; }
-        pt_ctx::Query& q = ctx->q;
-        QueryCounters* counters = reinterpret_cast<QueryCounters*>(q.block);
-        uint32_t* count = reinterpret_cast<uint32_t*>(q.block + sizeof(QueryCounters));
-        uint32_t* work = reinterpret_cast<uint32_t*>(q.block + sizeof(QueryCounters) + 64);
-        const hipEvent_t* e = &q.events[4 * (size_t)q.pending];
-        if (q.pending == 0) CK(hipMemsetAsync(counters, 0, sizeof(QueryCounters), ctx->stream)); // the counters sum over the queries up to the next wait
-        // The staged rays, the hit records, the marks, the count word and the chunk counter are reused by every query.  That is safe with
-        // several queries queued because all of a query's kernels run on pt_stream(ctx), in order: query k+1's staging kernel starts after
-        // query k's attribute kernel has read the last of them.
-        const unsigned sgrid = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 2048); // grid-stride above 2048 workgroups
-        CK(hipEventRecord(e[0], ctx->stream));
-        hipLaunchKernelGGL(k_stage_rays, dim3(sgrid), dim3(256), 0, ctx->stream, dev_rays, n, (int)((reinterpret_cast<uintptr_t>(dev_rays) & 15u) == 0), q.rayO, q.rayD,
-                           q.mark, count, work, counters);
-        CK(hipEventRecord(e[1], ctx->stream));
-        PathState st{};
-        st.rayO = q.rayO;
-        st.rayD = q.rayD;
-        st.hit = q.hit;
-        Trace8Args ta{st, bvh_dev(ctx), QView{nullptr, count, 0}, QView{}, work, ctx->ovf, 0, nullptr, 0, ctx->lds_skip, ctx->ovf_depth, &counters->fault, ctx->bvh.num_nodes8};
-        if (any_hit) hipLaunchKernelGGL((k_trace8<TR_ANY_QUERY>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
-        else hipLaunchKernelGGL((k_trace8<TR_CLOSEST>), dim3(ctx->trace_grid), dim3(64), 0, ctx->stream, ta);
-        CK(hipEventRecord(e[2], ctx->stream));
-        hipLaunchKernelGGL(k_hit_attributes, dim3(sgrid), dim3(256), 0, ctx->stream, q.hit, q.rayO, q.rayD, q.mark, ctx->bvh.tris8, ctx->sc.d_tri_nrm, n, (int)any_hit,
-                           (int)((reinterpret_cast<uintptr_t>(dev_out) & 15u) == 0), dev_out, counters);
-        CK(hipEventRecord(e[3], ctx->stream));
-        CK(hipGetLastError());
-        ++q.pending;
-        q.pending_rays += n;
-    }
-    if (async) return PT_OK;
-    const int rc = query_complete(ctx);
-    query_report(ctx, stats);
-    return rc;
-}
-
-// ------------------------------------------------------------------ viewports: several cameras in rectangles of one frame
-static int upload_views(pt_ctx* ctx) {
-    CK(hipMemcpy(ctx->vw.d_views, ctx->vw.host.data(), sizeof(pt_view) * ctx->vw.n, hipMemcpyHostToDevice));
-    return PT_OK;
-}
-extern "C" int pt_set_views(pt_ctx* ctx, const pt_view* views, uint32_t n) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_set_views: null context");
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames in flight (pt_options.frames_in_flight) finish first
-    if (n && !views) return fail(ctx, PT_ERR_INVALID, "pt_set_views: null views");
-    if (n && ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_set_views: no frame size yet (pt_resize)");
-    if (n > PT_MAX_VIEWS) return fail(ctx, PT_ERR_INVALID, "pt_set_views: more than PT_MAX_VIEWS views");
-    const int w = ctx->width, h = ctx->height;
-    const uint32_t nbx = (uint32_t)(w + 7) / 8u, nby = (uint32_t)(h + 7) / 8u;
-    std::vector<uint16_t> vblock((size_t)nbx * nby, (uint16_t)0xffffu);
-    for (uint32_t i = 0; i < n; ++i) {
-        const pt_view& v = views[i];
-        const std::string who = "pt_set_views: view " + std::to_string(i);
-        if (v.x < 0 || v.y < 0 || (v.x & 7) || (v.y & 7)) return fail(ctx, PT_ERR_INVALID, (who + ": x and y must be non-negative multiples of 8").c_str());
-        if (v.width < 1 || v.height < 1) return fail(ctx, PT_ERR_INVALID, (who + ": width and height must be at least 1").c_str());
-        if (v.x >= w || v.y >= h || v.width > w - v.x || v.height > h - v.y) return fail(ctx, PT_ERR_INVALID, (who + ": the rectangle leaves the frame").c_str());
-        // origins sit on the block grid, so two views that touch the same block both hold its first pixel
-        for (uint32_t by = (uint32_t)v.y / 8u; by <= (uint32_t)(v.y + v.height - 1) / 8u; ++by)
-            for (uint32_t bx = (uint32_t)v.x / 8u; bx <= (uint32_t)(v.x + v.width - 1) / 8u; ++bx) {
-                uint16_t& b = vblock[(size_t)by * nbx + bx];
-                if (b != 0xffffu) return fail(ctx, PT_ERR_INVALID, (who + " shares pixels with view " + std::to_string(b)).c_str());
-                b = (uint16_t)i;
-            }
-    }
-    CK(hipSetDevice(ctx->device));
-    CK(hipStreamSynchronize(ctx->stream));
-    ctx->ad = pt_ctx::Adaptive{}; // the block spans follow the frame's pixel list; implies pt_adaptive_end
-    ctx->blk = pt_ctx::Blocks{};
-    ctx->vw = pt_ctx::Views{};
-    ctx->sched_pending.valid = false;
-    if (n == 0) return PT_OK;
-    // the view pixel list in the order of build_pixel_lists: whole blocks, block order kept, only pixels inside their view, only owned blocks
-    std::vector<uint32_t> list;
-    for (uint32_t by = 0; by < nby; ++by)
-        for (uint32_t bx = 0; bx < nbx; ++bx) {
-            const uint16_t vi = vblock[(size_t)by * nbx + bx];
-            const int owner = (int)(((bx * 8u) / (uint32_t)ctx->tile_w + (by * 8u) / (uint32_t)ctx->tile_h) % (uint32_t)ctx->world);
-            if (vi == 0xffffu || owner != ctx->rank) continue;
-            const pt_view& v = views[vi];
-            for (int iy = 0; iy < 8; ++iy)
-                for (int ix = 0; ix < 8; ++ix) {
-                    const int x = (int)bx * 8 + ix, y = (int)by * 8 + iy;
-                    if (x < v.x + v.width && y < v.y + v.height) list.push_back((uint32_t)x | ((uint32_t)y << 16));
-                }
-        }
-    pt_ctx::Views& V = ctx->vw;
-    V.host.assign(views, views + n);
-    V.vblock = vblock;
-    V.owned = (uint32_t)list.size();
-    int rc = PT_OK;
-    hipError_t e = V.mem.alloc(&V.d_views, (size_t)n);
-    if (e == hipSuccess) e = V.mem.alloc(&V.d_vblock, vblock.size());
-    if (e == hipSuccess) e = V.mem.alloc(&V.d_pixels, list.size());
-    if (e == hipSuccess) e = hipMemcpy(V.d_views, V.host.data(), sizeof(pt_view) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(V.d_vblock, vblock.data(), sizeof(uint16_t) * vblock.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !list.empty()) e = hipMemcpy(V.d_pixels, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ctx->err = std::string("pt_set_views: ") + hipGetErrorString(e);
-        ctx->vw = pt_ctx::Views{}; // all of it or nothing
-        rc = PT_ERR_HIP;
-    } else {
-        V.n = n;
-    }
-    return rc;
-}
-
-extern "C" int pt_get_views(const pt_ctx* ctx, pt_view* out, uint32_t cap, uint32_t* n) {
-    if (!ctx) return PT_ERR_INVALID;
-    if (n) *n = ctx->vw.n;
-    if (out)
-        for (uint32_t i = 0; i < std::min(cap, ctx->vw.n); ++i) out[i] = ctx->vw.host[i];
-    return PT_OK;
-}
-
-static int view_cameras_open(pt_ctx* ctx, const char* fn, uint32_t n) {
-    int rc = drain(ctx); // frames in flight read the view records
-    if (rc) return rc;
-    if (n != ctx->vw.n) return fail(ctx, PT_ERR_INVALID, (std::string(fn) + ": n must equal the current view count (pt_set_views)").c_str());
-    CK(hipSetDevice(ctx->device));
-    return PT_OK;
-}
-extern "C" int pt_set_view_cameras(pt_ctx* ctx, const float* cams, uint32_t n) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_set_view_cameras: null context");
-    int rc = view_cameras_open(ctx, "pt_set_view_cameras", n);
-    if (rc || n == 0) return rc;
-    if (!cams) return fail(ctx, PT_ERR_INVALID, "pt_set_view_cameras: null cameras");
-    for (uint32_t i = 0; i < n; ++i) memcpy(ctx->vw.host[i].eye, cams + (size_t)i * 12, sizeof(float) * 12);
-    return upload_views(ctx);
-}
-extern "C" int pt_set_view_cameras_device(pt_ctx* ctx, const float* dev_cams, uint32_t n) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_set_view_cameras_device: null context");
-    int rc = view_cameras_open(ctx, "pt_set_view_cameras_device", n);
-    if (rc || n == 0) return rc;
-    std::string err;
-    rc = query_pointer_validate(ctx, dev_cams, sizeof(float) * 12 * (size_t)n, "dev_cams", err, "pt_set_view_cameras_device", "pt_set_view_cameras");
-    if (rc) return fail(ctx, rc, err.c_str());
-    pt_ctx::Views& V = ctx->vw;
-    hipLaunchKernelGGL(k_view_cameras, dim3((n * 12u + 255u) / 256u), dim3(256), 0, ctx->stream, dev_cams, n, V.d_views);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(V.host.data(), V.d_views, sizeof(pt_view) * n, hipMemcpyDeviceToHost, ctx->stream)); // what pt_get_views reports
-    CK(hipStreamSynchronize(ctx->stream));
-    return PT_OK;
-}
-
-extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes, uint32_t* num_nodes, uint32_t* num_tris) {
-    if (!ctx) return PT_ERR_INVALID;
-    // the exported layout is the documented 80-byte node whatever the kernels traverse (PT8_NODE64: converted on the device, box for box)
-    static_assert(sizeof(Node80) == 80 && sizeof(LeafTri) == 48, "exported layout");
-    if (num_nodes) *num_nodes = ctx->bvh.num_nodes8;
-    if (num_tris) *num_tris = ctx->bvh.num_tris8;
-    if (!nodes && !tris) return PT_OK;
-    if (!nodes || !tris || nodes_bytes != sizeof(Node80) * (size_t)ctx->bvh.num_nodes8 || tris_bytes != sizeof(LeafTri) * (size_t)ctx->bvh.num_tris8)
-        return fail(ctx, PT_ERR_INVALID, "pt_export_bvh: buffer sizes must be num_nodes * 80 and num_tris * 48 bytes");
-    CK(hipSetDevice(ctx->device));
-#if PT8_NODE64
-    {
-        int rc = drain(ctx);
-        if (rc) return rc;
-        DevOwner tmp;
-        uint8_t* tmp80 = nullptr;
-        CK(tmp.alloc(&tmp80, nodes_bytes));
-        hipLaunchKernelGGL(k_nodes_to80, dim3((ctx->bvh.num_nodes8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.nodes8, ctx->bvh.num_nodes8, ctx->bvh.grid, reinterpret_cast<Node80*>(tmp80));
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(nodes, tmp80, nodes_bytes, hipMemcpyDeviceToHost);
-        CK(e);
-    }
-#else
-    CK(hipMemcpy(nodes, ctx->bvh.nodes8, nodes_bytes, hipMemcpyDeviceToHost));
-#endif
-    CK(hipMemcpy(tris, ctx->bvh.tris8, tris_bytes, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// ------------------------------------------------------------------ in-place vertex updates (pt_update_meshes, include/pt_amd.h)
-// Two phases, so that an update is atomic on one context and on all ranks of a pt_multi: update_stage validates, drains the frames in
-// flight and prepares everything that can fail — the new vertex array in a scratch buffer, the refit's side arrays, or the whole rebuilt tree
-// with its side arrays — without touching the context; update_commit then refits in place or swaps the new tree in, and only a failing HIP
-// runtime can stop it half way.
-struct MeshUpdate {
-    DevOwner mem;           // the arrays below, until update_commit hands them to the scene
-    float* d_new = nullptr; // the whole vertex array with the updated meshes
-    PtBvh nb;               // PT_UPDATE_REBUILD: the new tree and its side arrays
-    float4* nrm = nullptr;
-    TexTri* textris = nullptr;
-    double build_ms = 0;
-    float* rest = nullptr;  // the first transform of a context: the rest array, a copy of the vertices before the call
-    std::vector<std::pair<size_t, size_t>> explicit_ranges; // (first float, floats) of the meshes given explicitly: they become rest positions too
-    double stage_ms = 0;    // k_stage_vertices
-    std::vector<uint8_t> table; // its report word and segment table on the host: alive until the stream has been waited for
-    ~MeshUpdate() { pt_bvh_free(&nb); } // whatever was not committed
-};
-
-// What update_stage writes into the named meshes: host arrays (copied), device arrays or transforms (k_stage_vertices).
-struct UpdateSource {
-    const char* fn;                             // the entry point, for messages
-    const pt_mesh_update* host = nullptr;       // pt_update_meshes
-    const pt_mesh_update* dev = nullptr;        // pt_update_meshes_device
-    const pt_mesh_transform* xform = nullptr;   // pt_transform_meshes
-    int from = PT_FROM_REST;
-    uint32_t n = 0;
-};
-
-// host-side checks, shared by every rank (they share the scene's mesh table)
-static int update_validate(const pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, int mode, std::string& err, const char* fn = "pt_update_meshes",
-                           bool host_vertices = true) {
-    const std::string f = std::string(fn) + ": ";
-    if (!up || n == 0) { err = f + "no updates"; return PT_ERR_INVALID; }
-    if (mode != PT_UPDATE_REFIT && mode != PT_UPDATE_REBUILD) { err = f + "mode must be PT_UPDATE_REFIT or PT_UPDATE_REBUILD"; return PT_ERR_INVALID; }
-    std::vector<char> seen(ctx->nmesh, 0);
-    for (uint32_t k = 0; k < n; ++k) {
-        const pt_mesh_update& u = up[k];
-        if (u.mesh >= ctx->nmesh) { err = f + "mesh index " + std::to_string(u.mesh) + " out of range"; return PT_ERR_INVALID; }
-        if (seen[u.mesh]) { err = f + "mesh " + std::to_string(u.mesh) + " named twice"; return PT_ERR_INVALID; }
-        seen[u.mesh] = 1;
-        if (!u.vertex) { err = f + "null vertex pointer"; return PT_ERR_INVALID; }
-        if (u.num_vertices != ctx->mesh_nv[u.mesh]) {
-            err = f + "mesh " + std::to_string(u.mesh) + " has " + std::to_string(ctx->mesh_nv[u.mesh]) + " vertices, the update " + std::to_string(u.num_vertices);
-            return PT_ERR_INVALID;
-        }
-        if (host_vertices) {
-            for (size_t i = 0; i < 3 * (size_t)u.num_vertices; ++i)
-                if (!std::isfinite(u.vertex[i])) { err = f + "non-finite coordinate in mesh " + std::to_string(u.mesh); return PT_ERR_INVALID; }
-        } else if ((uintptr_t)u.vertex & 3u) {
-            err = f + "the vertex pointer of mesh " + std::to_string(u.mesh) + " is not 4-byte aligned";
-            return PT_ERR_INVALID;
-        }
-    }
-    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = f + "refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
-    return PT_OK;
-}
-
-static int transform_validate(const pt_ctx* ctx, const pt_mesh_transform* t, uint32_t n, int source, int mode, std::string& err, const char* fn) {
-    const std::string f = std::string(fn) + ": ";
-    if (!t || n == 0) { err = f + "no transforms"; return PT_ERR_INVALID; }
-    if (source != PT_FROM_REST && source != PT_FROM_CURRENT) { err = f + "source must be PT_FROM_REST or PT_FROM_CURRENT"; return PT_ERR_INVALID; }
-    if (mode != PT_UPDATE_REFIT && mode != PT_UPDATE_REBUILD) { err = f + "mode must be PT_UPDATE_REFIT or PT_UPDATE_REBUILD"; return PT_ERR_INVALID; }
-    std::vector<char> seen(ctx->nmesh, 0);
-    for (uint32_t k = 0; k < n; ++k) {
-        if (t[k].mesh >= ctx->nmesh) { err = f + "mesh index " + std::to_string(t[k].mesh) + " out of range"; return PT_ERR_INVALID; }
-        if (seen[t[k].mesh]) { err = f + "mesh " + std::to_string(t[k].mesh) + " named twice"; return PT_ERR_INVALID; }
-        seen[t[k].mesh] = 1;
-        for (int i = 0; i < 12; ++i)
-            if (!std::isfinite(t[k].m[i])) { err = f + "non-finite matrix entry for mesh " + std::to_string(t[k].mesh); return PT_ERR_INVALID; }
-    }
-    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = f + "refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
-    return PT_OK;
-}
-
-// pt_update_meshes_device: every pointer must be memory of the context's device that HIP knows, checked before any device work (as
-// pt_render_device checks its buffer) — a host pointer handed to a kernel is a fault, not an error code.  Where HIP tells the extent of
-// the allocation, the array has to lie inside it.
-static int device_pointers_validate(pt_ctx* ctx, const pt_mesh_update* up, uint32_t n, std::string& err) {
-    CK(hipSetDevice(ctx->device));
-    for (uint32_t k = 0; k < n; ++k) {
-        const std::string who = "pt_update_meshes_device: the vertex pointer of mesh " + std::to_string(up[k].mesh);
-        hipPointerAttribute_t at;
-        const hipError_t pe = hipPointerGetAttributes(&at, up[k].vertex);
-        if (pe != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void)hipGetLastError(); // an unknown pointer leaves hipErrorInvalidValue behind
-            err = who + " is not device memory (for host arrays use pt_update_meshes)";
-            return PT_ERR_INVALID;
-        }
-        if (at.device != ctx->device) { err = who + " is memory of device " + std::to_string(at.device) + ", the context is on device " + std::to_string(ctx->device); return PT_ERR_INVALID; }
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)up[k].vertex) != hipSuccess) { (void)hipGetLastError(); continue; }
-        const size_t off = (size_t)((const char*)up[k].vertex - (const char*)base), bytes = sizeof(float) * 3 * (size_t)up[k].num_vertices;
-        if (off > size || bytes > size - off) { err = who + " has fewer than num_vertices * 12 bytes left in its allocation"; return PT_ERR_INVALID; }
-    }
-    return PT_OK;
-}
-
-// Enqueues k_stage_vertices for a device or transform source into U.d_new (which already holds the current vertices), its report word's
-// copy to pinned memory, and the events around the kernel.  Nothing of the context changes: the table and the word are scratch.
-static int stage_on_device(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hipEvent_t e0, hipEvent_t e1) {
-    const float* from = ctx->sc.d_verts;
-    if (S.xform) {
-        if (!ctx->sc.d_rest) { // the first transform of the context: its rest positions are the vertices as they are now
-            CK(U.mem.alloc(&U.rest, 3 * ctx->nvert));
-            CK(hipMemcpyAsync(U.rest, ctx->sc.d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
-        } else if (S.from == PT_FROM_REST) {
-            from = ctx->sc.d_rest;
-        }
-    }
-    const size_t bytes = 16 + sizeof(StageSeg) * (size_t)S.n; // the report word (in a 16-byte line of its own), then the table
-    std::vector<uint8_t>& host = U.table;
-    host.assign(bytes, 0);
-    *reinterpret_cast<uint32_t*>(host.data()) = PT_STAGE_NONE;
-    StageSeg* segs = reinterpret_cast<StageSeg*>(host.data() + 16);
-    uint64_t waves = 0;
-    for (uint32_t k = 0; k < S.n; ++k) {
-        const uint32_t mesh = S.xform ? S.xform[k].mesh : S.dev[k].mesh;
-        const size_t first = 3 * (size_t)ctx->mesh_vbase[mesh];
-        StageSeg& g = segs[k];
-        g.dst = U.d_new + first;
-        g.first_wave = (uint32_t)waves;
-        g.order = k;
-        if (S.xform) {
-            g.src = from + first;
-            g.count = ctx->mesh_nv[mesh];
-            g.xform = 1;
-            memcpy(g.m, S.xform[k].m, sizeof(g.m));
-        } else {
-            g.src = S.dev[k].vertex;
-            g.count = 3 * (uint64_t)ctx->mesh_nv[mesh];
-            U.explicit_ranges.emplace_back(first, (size_t)g.count);
-        }
-        waves += (g.count + PT_STAGE_CHUNK - 1) / PT_STAGE_CHUNK;
-    }
-    if (waves > 0xfffffffcull) { ctx->err = std::string(S.fn) + ": too many vertices for one call"; return PT_ERR_UNSUPPORTED; }
-    if (!ctx->sc.h_stage_bad) CK(ctx->sc.mem.pinned(&ctx->sc.h_stage_bad, 1));
-    if (ctx->sc.stage_cap < bytes) {
-        uint8_t* grown = nullptr;
-        CK(ctx->sc.mem.alloc(&grown, bytes));
-        ctx->sc.mem.drop(ctx->sc.d_stage);
-        ctx->sc.d_stage = grown;
-        ctx->sc.stage_cap = bytes;
-    }
-    *ctx->sc.h_stage_bad = PT_STAGE_NONE;
-    CK(hipMemcpyAsync(ctx->sc.d_stage, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream)); 
-    CK(hipEventRecord(e0, ctx->stream));
-    if (waves) {
-        hipLaunchKernelGGL(k_stage_vertices, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, ctx->stream, reinterpret_cast<const StageSeg*>(ctx->sc.d_stage + 16), S.n,
-                           (uint32_t)waves, reinterpret_cast<uint32_t*>(ctx->sc.d_stage));
-        CK(hipGetLastError());
-    }
-    CK(hipEventRecord(e1, ctx->stream));
-    CK(hipMemcpyAsync(ctx->sc.h_stage_bad, ctx->sc.d_stage, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    return PT_OK;
-}
-
-// after a synchronisation of the stream: did k_stage_vertices write a non-finite coordinate?
-static int stage_verdict(pt_ctx* ctx, const UpdateSource& S, MeshUpdate& U, hipEvent_t e0, hipEvent_t e1) {
-    const uint32_t bad = *ctx->sc.h_stage_bad;
-    if (bad != PT_STAGE_NONE) {
-        const uint32_t mesh = bad < S.n ? (S.xform ? S.xform[bad].mesh : S.dev[bad].mesh) : bad;
-        ctx->err = std::string(S.fn) + ": non-finite coordinate in mesh " + std::to_string(mesh) + (S.xform ? " after the transform" : "");
-        return PT_ERR_INVALID;
-    }
-    float ms = 0;
-    CK(hipEventElapsedTime(&ms, e0, e1));
-    U.stage_ms = ms;
-    return PT_OK;
-}
-
-static int update_stage(pt_ctx* ctx, const UpdateSource& S, int mode, MeshUpdate& U) {
-    { int rc_ = drain(ctx); if (rc_ != PT_OK) return rc_; } // frames enqueued before the call render the old geometry
-    CK(hipSetDevice(ctx->device));
-    CK(U.mem.alloc(&U.d_new, 3 * ctx->nvert));
-    CK(hipMemcpyAsync(U.d_new, ctx->sc.d_verts, sizeof(float) * 3 * ctx->nvert, hipMemcpyDeviceToDevice, ctx->stream));
-    DevOwner tmp;
-    hipEvent_t s0 = nullptr, s1 = nullptr;
-    if (S.host) {
-        for (uint32_t k = 0; k < S.n; ++k) {
-            const size_t first = 3 * (size_t)ctx->mesh_vbase[S.host[k].mesh], floats = 3 * (size_t)S.host[k].num_vertices;
-            CK(hipMemcpyAsync(U.d_new + first, S.host[k].vertex, sizeof(float) * floats, hipMemcpyHostToDevice, ctx->stream));
-            U.explicit_ranges.emplace_back(first, floats);
-        }
-    } else {
-        CK(tmp.event(&s0));
-        CK(tmp.event(&s1));
-        const int rc = stage_on_device(ctx, S, U, s0, s1);
-        if (rc != PT_OK) return rc;
-    }
-    if (mode == PT_UPDATE_REFIT) {
-        CK(pt_bvh_refit_alloc(&ctx->bvh));
-        CK(hipStreamSynchronize(ctx->stream));
-        return S.host ? PT_OK : stage_verdict(ctx, S, U, s0, s1);
-    }
-    if (!S.host) { // the builder must never see a non-finite vertex: the verdict comes before the build, at the price of one wait
-        CK(hipStreamSynchronize(ctx->stream));
-        const int rc = stage_verdict(ctx, S, U, s0, s1);
-        if (rc != PT_OK) return rc;
-    }
-    // rebuild: pt_create's build and side arrays over the new vertices, into a tree of its own
-    hipEvent_t e0, e1;
-    CK(tmp.event(&e0));
-    CK(tmp.event(&e1));
-    CK(hipEventRecord(e0, ctx->stream));
-    CK(pt_bvh_build(U.d_new, ctx->sc.d_idx, ctx->sc.d_tri_mesh, ctx->ntri, ctx->stream, &U.nb));
-    const uint32_t nt8 = U.nb.num_tris8;
-    CK(U.mem.alloc(&U.nrm, (size_t)nt8));
-    hipLaunchKernelGGL(k_shade_normals, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.nb.tris8, nt8, U.nrm);
-    if (ctx->sc.d_textris) { // the texcoords per primitive, from the old tree's records, then the records in the new leaf order
-        PrimUV* uvs = nullptr;
-        CK(tmp.alloc(&uvs, (size_t)ctx->ntri));
-        CK(U.mem.alloc(&U.textris, (size_t)nt8));
-        hipLaunchKernelGGL(k_textris_to_uvs, dim3((ctx->bvh.num_tris8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.tris8, ctx->sc.d_textris, ctx->bvh.num_tris8, uvs);
-        hipLaunchKernelGGL(k_emit_textris, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.nb.tris8, uvs, nt8, U.textris);
-    }
-    CK(hipGetLastError());
-    CK(hipEventRecord(e1, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    CK(hipEventElapsedTime(&ms, e0, e1));
-    U.build_ms = ms;
-    char msg[160];
-    if (check_tree_depth(ctx, msg, sizeof(msg), &U.nb) != PT_OK) {
-        ctx->err = std::string(S.fn) + ": " + msg;
-        return PT_ERR_UNSUPPORTED;
-    }
-    return PT_OK;
-}
-
-
-static int update_commit(pt_ctx* ctx, int mode, MeshUpdate& U, double* kernel_ms) {
-    CK(hipSetDevice(ctx->device));
-    double ms = U.build_ms;
-    if (ctx->sc.d_rest && !U.explicit_ranges.empty()) { // positions given explicitly are rest positions from now on
-        for (const auto& r : U.explicit_ranges)
-            CK(hipMemcpyAsync(ctx->sc.d_rest + r.first, U.d_new + r.first, sizeof(float) * r.second, hipMemcpyDeviceToDevice, ctx->stream));
-        if (mode != PT_UPDATE_REFIT) CK(hipStreamSynchronize(ctx->stream)); // (the refit below waits)
-    }
-    if (mode == PT_UPDATE_REFIT) {
-        DevOwner tmp;
-        hipEvent_t e0, e1;
-        CK(tmp.event(&e0));
-        CK(tmp.event(&e1));
-        CK(hipEventRecord(e0, ctx->stream));
-        CK(pt_bvh_refit_begin(&ctx->bvh, U.d_new, ctx->sc.d_idx, ctx->ntri, ctx->stream));
-        const uint32_t nt8 = ctx->bvh.num_tris8;
-        hipLaunchKernelGGL(k_refit_leaves, dim3((nt8 + 255) / 256), dim3(256), 0, ctx->stream, U.d_new, ctx->sc.d_idx, nt8, const_cast<LeafTri*>(ctx->bvh.tris8),
-                           ctx->sc.d_tri_nrm, ctx->sc.d_textris);
-        CK(hipGetLastError());
-        CK(pt_bvh_refit_nodes(&ctx->bvh, ctx->stream));
-        CK(hipEventRecord(e1, ctx->stream));
-        CK(pt_bvh_refit_end(&ctx->bvh, ctx->stream)); // waits; the new bounds and padding
-        float fms = 0;
-        CK(hipEventElapsedTime(&fms, e0, e1));
-        ms = fms;
-    } else {
-        pt_bvh_free(&ctx->bvh);
-        ctx->bvh = std::move(U.nb);
-        U.nb = PtBvh{};
-        ctx->sc.mem.drop(ctx->sc.d_tri_nrm);
-        ctx->sc.d_tri_nrm = U.nrm;
-        if (U.textris) {
-            ctx->sc.mem.drop(ctx->sc.d_textris);
-            ctx->sc.d_textris = U.textris;
-        }
-        ctx->bvh_build_ms = U.build_ms;
-    }
-    ctx->sc.mem.drop(ctx->sc.d_verts);
-    ctx->sc.d_verts = U.d_new;
-    if (U.rest) ctx->sc.d_rest = U.rest;
-    ctx->sc.mem.adopt(std::move(U.mem)); // the scene owns the new arrays from here on
-    ctx->sched = pt_ctx::Sched{}; // the tree's traversal cost changed: the chain/fused trial starts over
-    if (kernel_ms) *kernel_ms = ms + U.stage_ms;
-    return PT_OK;
-}
-
-static int update_run(pt_ctx* ctx, const UpdateSource& S, int mode, double* kernel_ms) {
-    MeshUpdate U; // what is not committed goes with it
-    const int rc = update_stage(ctx, S, mode, U);
-    return rc == PT_OK ? update_commit(ctx, mode, U, kernel_ms) : rc;
-}
-extern "C" int pt_update_meshes(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_update_meshes: null context");
-    std::string err;
-    int rc = update_validate(ctx, updates, n, mode, err);
-    if (rc != PT_OK) return fail(ctx, rc, err.c_str());
-    UpdateSource S{"pt_update_meshes"};
-    S.host = updates;
-    S.n = n;
-    return update_run(ctx, S, mode, kernel_ms);
-}
-
-extern "C" int pt_update_meshes_device(pt_ctx* ctx, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_update_meshes_device: null context");
-    std::string err;
-    int rc = update_validate(ctx, updates, n, mode, err, "pt_update_meshes_device", /*host_vertices=*/false);
-    if (rc == PT_OK) rc = device_pointers_validate(ctx, updates, n, err);
-    if (rc != PT_OK) return err.empty() ? rc : fail(ctx, rc, err.c_str());
-    UpdateSource S{"pt_update_meshes_device"};
-    S.dev = updates;
-    S.n = n;
-    return update_run(ctx, S, mode, kernel_ms);
-}
-
-extern "C" int pt_transform_meshes(pt_ctx* ctx, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_transform_meshes: null context");
-    std::string err;
-    int rc = transform_validate(ctx, t, n, source, mode, err, "pt_transform_meshes");
-    if (rc != PT_OK) return fail(ctx, rc, err.c_str());
-    UpdateSource S{"pt_transform_meshes"};
-    S.xform = t;
-    S.from = source;
-    S.n = n;
-    return update_run(ctx, S, mode, kernel_ms);
-}
-
-extern "C" int pt_download_vertices(pt_ctx* ctx, uint32_t mesh, int rest, float* host, size_t bytes) {
-    if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_download_vertices: null context");
-    if (!host) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: null buffer");
-    if (mesh >= ctx->nmesh) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: mesh index out of range");
-    if (rest != 0 && rest != 1) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: rest must be 0 or 1");
-    if (bytes != sizeof(float) * 3 * (size_t)ctx->mesh_nv[mesh]) return fail(ctx, PT_ERR_INVALID, "pt_download_vertices: bytes must equal num_vertices * 12");
-    if (bytes == 0) return PT_OK;
-    CK(hipSetDevice(ctx->device));
-    const float* from = rest && ctx->sc.d_rest ? ctx->sc.d_rest : ctx->sc.d_verts; // before the first transform the vertices are their own rest positions
-    CK(hipMemcpy(host, from + 3 * (size_t)ctx->mesh_vbase[mesh], bytes, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material, int bsdf_mode, const float* in, uint32_t n, float* out) {
-    if (!ctx || !in || !out) return PT_ERR_INVALID;
-    if (n == 0) return PT_OK;
-    static const int in_w[9] = {11, 9, 1, 3, 3, 3, 2, 2, 3}, out_w[9] = {4, 6, 9, 6, 1, 1, 8, 4, 1};
-    if (which < 0 || which > 8) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: unknown table");
-    if (which <= 1 && !material) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: material required");
-    if ((which == 2 || which == 3 || which == 8) && !ctx->pr.dev.data) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: no probe set");
-    if (which == 7 && !ctx->sc.tex0.pixel) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: the scene has no texture");
-    CK(hipSetDevice(ctx->device));
-    DevOwner tmp;
-    float *dIn = nullptr, *dOut = nullptr;
-    CK(tmp.alloc(&dIn, (size_t)n * in_w[which]));
-    CK(tmp.alloc(&dOut, (size_t)n * out_w[which]));
-    CK(hipMemcpy(dIn, in, sizeof(float) * (size_t)n * in_w[which], hipMemcpyHostToDevice));
-    const dim3 g((n + 127) / 128), b(128);
-    pt_material mat{};
-    if (material) mat = *material;
-    switch (which) {
-        case 0:
-            if (bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_table_bsdf<PT_BSDF_LAMBERT>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
-            else hipLaunchKernelGGL((k_table_bsdf<PT_BSDF_DISNEY>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
-            break;
-        case 1:
-            if (bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_table_sample<PT_BSDF_LAMBERT>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
-            else hipLaunchKernelGGL((k_table_sample<PT_BSDF_DISNEY>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
-            break;
-        case 2: hipLaunchKernelGGL(k_table_probe_sample, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
-        case 3: hipLaunchKernelGGL(k_table_probe_eval, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
-        case 4: hipLaunchKernelGGL(k_table_color, g, b, 0, ctx->stream, dIn, n, dOut); break;
-        case 5: hipLaunchKernelGGL(k_table_math, g, b, 0, ctx->stream, dIn, n, dOut); break;
-        case 6: hipLaunchKernelGGL(k_table_rng, g, b, 0, ctx->stream, dIn, n, dOut); break;
-        case 7: hipLaunchKernelGGL(k_table_tex, g, b, 0, ctx->stream, ctx->sc.tex0, dIn, n, dOut); break;
-        case 8: hipLaunchKernelGGL(k_table_probe_pdf, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
-    }
-    CK(hipStreamSynchronize(ctx->stream));
-    CK(hipGetLastError());
-    CK(hipMemcpy(out, dOut, sizeof(float) * (size_t)n * out_w[which], hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// ===================================================================================================================
-// pt_multi: N contexts in one process (include/pt_amd.h).  No reference counterpart: the reference is single-GPU.
-#include <dlfcn.h>
-// declarations only: the pointer types below are RCCL's own, the library itself is opened at run time
-#if __has_include(<rccl/rccl.h>)
-#include <rccl/rccl.h>
-#else // a box without RCCL's headers: the six prototypes as rccl.h (2.x) declares them, so that libptamd still builds (single-GPU path, peer copies)
-typedef struct ncclComm* ncclComm_t;
-typedef enum { ncclSuccess = 0 } ncclResult_t;
-typedef enum { ncclInt8 = 0, ncclChar = 0, ncclUint8 = 1 } ncclDataType_t;
-extern "C" {
-ncclResult_t ncclCommInitAll(ncclComm_t* comm, int ndev, const int* devlist);
-ncclResult_t ncclCommDestroy(ncclComm_t comm);
-ncclResult_t ncclGroupStart();
-ncclResult_t ncclGroupEnd();
-ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
-const char* ncclGetErrorString(ncclResult_t result);
-}
-#endif
-
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
-
-namespace {
-// the six RCCL entry points the exchange needs, resolved at run time: libptamd must load (and the single-GPU path must
-// work) on a box without librccl, and a process that already holds torch's bundled librccl must not get a second copy.
-// The pointer types are decltype of rccl.h's declarations, so a signature change breaks the build instead of the call.
-struct Rccl {
-    void* lib = nullptr;
-    decltype(&ncclCommInitAll) CommInitAll = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclAllGather) AllGather = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    bool ok() const { return lib && CommInitAll && CommDestroy && GroupStart && GroupEnd && AllGather && GetErrorString; }
-};
-const ncclDataType_t kNcclUint8 = ncclUint8;
-
-Rccl& rccl() {
-    static Rccl r;
-    static bool tried = false;
-    if (!tried) {
-        tried = true;
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            r.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (r.lib) break;
-        }
-        if (r.lib) {
-            r.CommInitAll = (decltype(r.CommInitAll))dlsym(r.lib, "ncclCommInitAll");
-            r.CommDestroy = (decltype(r.CommDestroy))dlsym(r.lib, "ncclCommDestroy");
-            r.GroupStart = (decltype(r.GroupStart))dlsym(r.lib, "ncclGroupStart");
-            r.GroupEnd = (decltype(r.GroupEnd))dlsym(r.lib, "ncclGroupEnd");
-            r.AllGather = (decltype(r.AllGather))dlsym(r.lib, "ncclAllGather");
-            r.GetErrorString = (decltype(r.GetErrorString))dlsym(r.lib, "ncclGetErrorString");
-        }
-    }
-    return r;
-}
-thread_local std::string g_multi_error;
-} // namespace
-
-// One host thread per rank (pt_multi, an EnqueueWorker each): a frame is ~60 launches and events per device, so enqueueing the devices one
-// after the other from one thread costs ndev x (60 x 5-8 us) — at a 1/8 share of a 1080p frame (1.3-1.8 ms of GPU work) more than the frame
-// itself.  Every rank's thread enqueues its own device; the calling thread posts a job to each and waits for all.
-struct pt_multi {
-    std::vector<pt_ctx*> ctx;
-    std::vector<int> devices;
-    std::string err;
-    bool distinct = true;           // no device appears twice (RCCL's requirement)
-    std::vector<ncclComm_t> comms;  // per rank (empty until the first RCCL gather)
-    int exchange_pref = 0;          // PT_MULTI_EXCHANGE: 0 auto, 1 rccl, 2 peer copies
-    // The exchange strips of the current frame size: freed and rebuilt by pt_multi_resize.  send.empty(): not resized.
-    struct Strips { std::vector<uint8_t*> send, recv; };
-    struct Exchange {
-        std::vector<DevOwner> mem;      // per rank: what the rank's device holds of the arrays and events below
-        std::vector<uint8_t*> send, recv; // per rank: padded * 16 bytes, world * padded * 16 bytes (the synchronous pt_multi_gather)
-        uint32_t padded = 0;
-        Strips hand[2][6];              // the overlapped hand-off (below): [slot][pt_buffer], allocated on first use
-        std::vector<hipEvent_t> xfer_done[2]; // peer-copy exchange: rank r's copies of slot s are complete
-    } ex;
-    double gather_ms = 0;
-    int last_exchange = PT_EXCHANGE_NONE;
-    std::vector<std::unique_ptr<EnqueueWorker>> workers; // empty: single rank or PT_MULTI_THREADS=0 (everything on the calling thread)
-    double enqueue_ms = 0;          // host time of the enqueue phase of the last render: the slowest rank's
-    // Overlapped hand-off (frames in flight + a gather mask): frame k's strips are packed behind frame k (pt_pack_async) into the
-    // buffers of slot k & 1 and exchanged + scattered into the ranks' DISPLAY buffers by the NEXT render call, while frame k+1 renders.
-    int pending_slot = -1;          // slot whose strips are packed (or being packed) but not yet exchanged
-    uint32_t pending_mask = 0;
-    uint64_t handed = 0;            // frames handed over through the overlapped path
-    uint64_t packs = 0;             // pack rounds enqueued (slot = packs & 1)
-};
-
-static int mfail(pt_multi* m, int code, const std::string& msg) {
-    if (m) m->err = msg; else g_multi_error = msg;
-    return code;
-}
-// forward a per-context failure
-static int mctx(pt_multi* m, int r, int rc, const char* what) {
-    if (rc == PT_OK) return PT_OK;
-    return mfail(m, rc, std::string(what) + " (rank " + std::to_string(r) + ", device " + std::to_string(m->devices[r]) + "): " + m->ctx[r]->err);
-}
-#define MCK(m, call)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return mfail(m, PT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-extern "C" const char* pt_multi_last_error(const pt_multi* m) { return m ? m->err.c_str() : g_multi_error.c_str(); }
-extern "C" int pt_multi_size(const pt_multi* m) { return m ? (int)m->ctx.size() : 0; }
-extern "C" pt_ctx* pt_multi_ctx(pt_multi* m, int rank) { return (m && rank >= 0 && rank < (int)m->ctx.size()) ? m->ctx[rank] : nullptr; }
-
-static int multi_present_pending(pt_multi* m, bool wait);
-// the communicators: made by the first RCCL exchange
-static int multi_comms(pt_multi* m) {
-    if (!m->comms.empty()) return PT_OK;
-    m->comms.assign(m->ctx.size(), nullptr);
-    const ncclResult_t e = rccl().CommInitAll(m->comms.data(), (int)m->ctx.size(), m->devices.data());
-    if (e == ncclSuccess) return PT_OK;
-    m->comms.clear();
-    return mfail(m, PT_ERR_HIP, std::string("ncclCommInitAll: ") + rccl().GetErrorString(e));
-}
-static void multi_unset_exchange(pt_multi* m) {
-    for (size_t r = 0; r < m->ctx.size(); ++r) { // pending packs / exchanges run on the contexts' streams
-        hipSetDevice(m->devices[r]);
-        if (m->ctx[r] && m->ctx[r]->stream) hipStreamSynchronize(m->ctx[r]->stream);
-    }
-    for (size_t r = 0; r < m->ex.mem.size(); ++r) {
-        hipSetDevice(m->devices[r]);
-        m->ex.mem[r].release();
-    }
-    m->ex = pt_multi::Exchange{};
-    m->pending_slot = -1;
-    m->pending_mask = 0;
-}
-
-// fn(rank) for every rank, concurrently on the ranks' threads (or one after the other on the calling thread); returns the first
-// failing rank's status, forwarded with its message.  max_ms: host time of the slowest rank.
-static int multi_run(pt_multi* m, const std::function<int(int)>& fn, const char* what, double* max_ms = nullptr) {
-    const int world = (int)m->ctx.size();
-    std::vector<int> rcs(world, PT_OK);
-    double slow = 0;
-    if (m->workers.empty()) {
-        for (int r = 0; r < world; ++r) {
-            const auto t0 = std::chrono::steady_clock::now();
-            rcs[r] = fn(r);
-            slow += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); // serial: the times add up
-        }
-    } else {
-        for (int r = 0; r < world; ++r) enqueue_worker_post(m->workers[r].get(), [&fn, r] { return fn(r); });
-        for (int r = 0; r < world; ++r) {
-            rcs[r] = enqueue_worker_wait(m->workers[r].get());
-            slow = std::max(slow, m->workers[r]->ms); // (written before `done`, which the wait has seen)
-        }
-    }
-    if (max_ms) *max_ms = slow;
-    for (int r = 0; r < world; ++r)
-        if (rcs[r] != PT_OK) return mctx(m, r, rcs[r], what);
-    return PT_OK;
-}
-
-extern "C" int pt_multi_destroy(pt_multi* m) {
-    if (!m) return PT_OK;
-    for (auto& w : m->workers) enqueue_worker_stop(w.get());
-    m->workers.clear();
-    multi_unset_exchange(m);
-    if (!m->comms.empty() && rccl().ok())
-        for (ncclComm_t c : m->comms)
-            if (c) rccl().CommDestroy(c);
-    for (pt_ctx* c : m->ctx) pt_destroy(c);
-    delete m;
-    return PT_OK;
-}
-
-extern "C" int pt_create_multi(const pt_scene_desc* scene, const int* devices, int ndev, pt_multi** out) {
-    if (!out || !devices || ndev < 1 || ndev > 64) return mfail(nullptr, PT_ERR_INVALID, "pt_create_multi: need 1..64 devices and an output pointer");
-    FlatScene fs; // ONE host-side flatten + validation, shared by all ranks
-    int rc = flatten_scene(scene, fs);
-    if (rc != PT_OK) return mfail(nullptr, rc, g_create_error);
-    pt_multi* m = new pt_multi();
-    m->devices.assign(devices, devices + ndev);
-    for (int a = 0; a < ndev; ++a)
-        for (int b = a + 1; b < ndev; ++b)
-            if (devices[a] == devices[b]) m->distinct = false;
-    if (const char* e = getenv("PT_MULTI_EXCHANGE")) m->exchange_pref = !strcmp(e, "rccl") ? 1 : (!strcmp(e, "peer") ? 2 : 0);
-    for (int r = 0; r < ndev; ++r) {
-        pt_ctx* c = nullptr;
-        rc = create_from_flat(fs, devices[r], &c);
-        if (rc != PT_OK) {
-            const std::string msg = "pt_create_multi: rank " + std::to_string(r) + ": " + g_create_error;
-            pt_multi_destroy(m);
-            return mfail(nullptr, rc, msg);
-        }
-        m->ctx.push_back(c);
-    }
-    // direct device-to-device copies between distinct devices need peer access (xGMI); failure is not fatal — hipMemcpyPeerAsync
-    // then stages through the host
-    if (m->distinct && ndev > 1)
-        for (int a = 0; a < ndev; ++a) {
-            hipSetDevice(devices[a]);
-            for (int b = 0; b < ndev; ++b) {
-                int can = 0;
-                if (a != b && hipDeviceCanAccessPeer(&can, devices[a], devices[b]) == hipSuccess && can) {
-                    hipError_t e = hipDeviceEnablePeerAccess(devices[b], 0);
-                    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
-                }
-            }
-        }
-    const char* te = getenv("PT_MULTI_THREADS");
-    if (ndev > 1 && !(te && atoi(te) == 0))
-        for (int r = 0; r < ndev; ++r) {
-            m->workers.emplace_back(new EnqueueWorker());
-            m->workers.back()->th = std::thread(enqueue_worker_main, m->workers.back().get(), devices[r]);
-        }
-    *out = m;
-    return PT_OK;
-}
-
-extern "C" int pt_multi_set_options(pt_multi* m, const pt_options* opt) {
-    if (!m || !opt) return PT_ERR_INVALID;
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        int rc = mctx(m, (int)r, pt_set_options(m->ctx[r], opt), "pt_multi_set_options");
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-extern "C" int pt_multi_set_probe(pt_multi* m, const float* data, const float* pdfX, const float* cdfX, const float* pdfY, const float* cdfY, int w, int h) {
-    if (!m) return PT_ERR_INVALID;
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        int rc = mctx(m, (int)r, pt_set_probe(m->ctx[r], data, pdfX, cdfX, pdfY, cdfY, w, h), "pt_multi_set_probe");
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-extern "C" int pt_multi_set_probe_image(pt_multi* m, const float* data, int w, int h) {
-    if (!m) return PT_ERR_INVALID;
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        int rc = mctx(m, (int)r, pt_set_probe_image(m->ctx[r], data, w, h), "pt_multi_set_probe_image");
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-extern "C" int pt_multi_set_camera(pt_multi* m, const float eye[3], const float U[3], const float V[3], const float W[3]) {
-    if (!m) return PT_ERR_INVALID;
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        int rc = mctx(m, (int)r, pt_set_camera(m->ctx[r], eye, U, V, W), "pt_multi_set_camera");
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_multi_set_views(pt_multi* m, const pt_view* views, uint32_t n) {
-    if (!m) return PT_ERR_INVALID;
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        int rc = mctx(m, (int)r, pt_set_views(m->ctx[r], views, n), "pt_multi_set_views");
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-extern "C" int pt_multi_set_view_cameras(pt_multi* m, const float* cams, uint32_t n) {
-    if (!m) return PT_ERR_INVALID;
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        int rc = mctx(m, (int)r, pt_set_view_cameras(m->ctx[r], cams, n), "pt_multi_set_view_cameras");
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_multi_resize(pt_multi* m, int width, int height, int tile_w, int tile_h) {
-    if (!m) return PT_ERR_INVALID;
-    if (width == 0 || height == 0) return PT_OK;
-    if (tile_w == 0) tile_w = 64;
-    if (tile_h == 0) tile_h = 16;
-    const int world = (int)m->ctx.size();
-    multi_unset_exchange(m);
-    std::vector<uint8_t*> send(world, nullptr), recv(world, nullptr);
-    m->ex.mem.resize(world);
-    auto build = [&]() -> int {
-        for (int r = 0; r < world; ++r) {
-            pt_ctx* c = m->ctx[r];
-            c->width = c->height = 0; // pt_set_partition then only records the partition; pt_resize applies it
-            int rc = mctx(m, r, pt_set_partition(c, r, world, tile_w, tile_h), "pt_multi_resize");
-            if (rc == PT_OK) rc = mctx(m, r, pt_resize(c, width, height), "pt_multi_resize");
-            if (rc) return rc;
-        }
-        const size_t padded = m->ctx[0]->padded;
-        for (int r = 0; r < world; ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            MCK(m, m->ex.mem[r].alloc(&send[r], std::max<size_t>(16, padded * 16)));
-            MCK(m, m->ex.mem[r].alloc(&recv[r], std::max<size_t>(16, (size_t)world * padded * 16)));
-        }
-        return PT_OK;
-    };
-    const int rc = build();
-    if (rc) { // every rank is as before its first resize: none keeps a frame that the others, or the strips, lack
-        for (pt_ctx* c : m->ctx) drain(c); // (a rank the loop did not reach may have frames in flight)
-        multi_unset_exchange(m);           // (waits for the ranks' streams)
-        for (int r = 0; r < world; ++r) {
-            hipSetDevice(m->devices[r]);
-            unset_frame(m->ctx[r]);
-        }
-        return rc;
-    }
-    m->ex.padded = m->ctx[0]->padded;
-    m->ex.send = send;
-    m->ex.recv = recv;
-    return PT_OK;
-}
-
-extern "C" int pt_multi_gather(pt_multi* m, int which) {
-    if (!m) return PT_ERR_INVALID;
-    const int world = (int)m->ctx.size();
-    if (m->ex.send.empty()) return mfail(m, PT_ERR_INVALID, "pt_multi_gather: not resized");
-    size_t elem = 0;
-    if (!buffer_ptr(m->ctx[0], which, &elem)) return mfail(m, PT_ERR_INVALID, "pt_multi_gather: unknown buffer");
-    const size_t bytes = (size_t)m->ex.padded * elem; // one rank's packed strip (padded to the largest share: same on every rank)
-    {
-        int rc = multi_present_pending(m, true); // a frame of the overlapped path that was still waiting for its hand-over
-        if (rc) return rc;
-    }
-    for (int r = 0; r < world; ++r) { // frames in flight (pt_options.frames_in_flight) are not ordered before the contexts' own streams
-        int rc = mctx(m, r, drain(m->ctx[r]), "pt_multi_gather");
-        if (rc) return rc;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int r = 0; r < world; ++r) {
-        int rc = mctx(m, r, pack_launch(m->ctx[r], which, m->ex.send[r]), "pt_multi_gather(pack)");
-        if (rc) return rc;
-    }
-    DevOwner tmp; // the peer copies' events: they must outlive the waits, so they go when the streams have been synchronised, below
-    bool use_rccl = m->exchange_pref == 1 || (m->exchange_pref == 0 && m->distinct && world > 1);
-    if (use_rccl && (!rccl().ok() || !m->distinct)) {
-        if (m->exchange_pref == 1) return mfail(m, PT_ERR_UNSUPPORTED, !m->distinct ? "pt_multi_gather: RCCL needs distinct devices" : "pt_multi_gather: librccl not found");
-        use_rccl = false;
-    }
-    if (use_rccl) {
-        Rccl& R = rccl();
-        if (int rc = multi_comms(m)) return rc;
-        // one all-gather of `bytes` per rank: with 8 GPUs each of the 7 xGMI links of a GPU carries one strip
-        ncclResult_t e = R.GroupStart();
-        for (int r = 0; r < world && e == ncclSuccess; ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            e = R.AllGather(m->ex.send[r], m->ex.recv[r], bytes, kNcclUint8, m->comms[r], m->ctx[r]->stream);
-        }
-        const ncclResult_t e2 = R.GroupEnd();
-        if (e != ncclSuccess || e2 != ncclSuccess) return mfail(m, PT_ERR_HIP, std::string("ncclAllGather: ") + R.GetErrorString(e != ncclSuccess ? e : e2));
-        m->last_exchange = PT_EXCHANGE_RCCL;
-    } else {
-        // every rank writes its strip into slot r of every rank's receive buffer (direct peer writes over xGMI; a plain
-        // device-to-device copy when both ranks live on one device), then every rank waits for all writers
-        std::vector<hipEvent_t> done(world);
-        for (int r = 0; r < world; ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            for (int p = 0; p < world; ++p) {
-                char* dst = (char*)m->ex.recv[p] + (size_t)r * bytes;
-                if (m->devices[p] == m->devices[r]) MCK(m, hipMemcpyAsync(dst, m->ex.send[r], bytes, hipMemcpyDeviceToDevice, m->ctx[r]->stream));
-                else MCK(m, hipMemcpyPeerAsync(dst, m->devices[p], m->ex.send[r], m->devices[r], bytes, m->ctx[r]->stream));
-            }
-            MCK(m, tmp.event(&done[r], hipEventDisableTiming));
-            MCK(m, hipEventRecord(done[r], m->ctx[r]->stream));
-        }
-        for (int p = 0; p < world; ++p) {
-            MCK(m, hipSetDevice(m->devices[p]));
-            for (int r = 0; r < world; ++r)
-                if (r != p) MCK(m, hipStreamWaitEvent(m->ctx[p]->stream, done[r], 0));
-        }
-        m->last_exchange = PT_EXCHANGE_PEER_COPY;
-    }
-    for (int r = 0; r < world; ++r) {
-        int rc = mctx(m, r, unpack_launch(m->ctx[r], which, m->ex.recv[r]), "pt_multi_gather(unpack)");
-        if (rc) return rc;
-    }
-    for (int r = 0; r < world; ++r) {
-        MCK(m, hipSetDevice(m->devices[r]));
-        MCK(m, hipStreamSynchronize(m->ctx[r]->stream));
-    }
-    m->gather_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return PT_OK;
-}
-
-static int multi_after_render(pt_multi* m, uint32_t gather_mask, uint32_t* host_rgba8) {
-    if (host_rgba8) gather_mask |= 1u << PT_BUF_FRAME;
-    if (m->ctx[0]->width == 0) return PT_OK;
-    for (int which = 0; which <= PT_BUF_DENOISED; ++which)
-        if (gather_mask & (1u << which)) {
-            int rc = pt_multi_gather(m, which);
-            if (rc) return rc;
-        }
-    if (host_rgba8) return mctx(m, 0, pt_download(m->ctx[0], PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)m->ctx[0]->width * m->ctx[0]->height), "pt_multi_render(download)");
-    return PT_OK;
-}
-
-// ---- overlapped hand-off (frames in flight + something to hand over): everything below only ENQUEUES on the ranks' own streams
-static int multi_ensure_strips(pt_multi* m, int slot, int which) {
-    pt_multi::Exchange& X = m->ex;
-    pt_multi::Strips& st = X.hand[slot][which];
-    const int world = (int)m->ctx.size();
-    if (X.send.empty()) return mfail(m, PT_ERR_INVALID, "pt_multi: not resized"); // X.padded sizes the strips
-    if ((int)st.send.size() == world) return PT_OK;
-    const size_t elem = buffer_elem(which);
-    // built aside and published whole: strips that are half there would pass for complete
-    std::vector<uint8_t*> send(world, nullptr), recv(world, nullptr);
-    std::vector<hipEvent_t> done(X.xfer_done[slot].empty() ? world : 0, nullptr);
-    auto build = [&]() -> int {
-        for (int r = 0; r < world; ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            MCK(m, X.mem[r].alloc(&send[r], std::max<size_t>(16, (size_t)X.padded * elem)));
-            MCK(m, X.mem[r].alloc(&recv[r], std::max<size_t>(16, (size_t)world * X.padded * elem)));
-        }
-        for (size_t r = 0; r < done.size(); ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            MCK(m, X.mem[r].event(&done[r], hipEventDisableTiming));
-        }
-        return PT_OK;
-    };
-    const int rc = build();
-    if (rc) {
-        for (int r = 0; r < world; ++r) {
-            hipSetDevice(m->devices[r]);
-            X.mem[r].drop(send[r]);
-            X.mem[r].drop(recv[r]);
-            if (!done.empty()) X.mem[r].drop(done[r]);
-        }
-        return rc;
-    }
-    st.send = send;
-    st.recv = recv;
-    if (!done.empty()) X.xfer_done[slot] = done;
-    return PT_OK;
-}
-static bool multi_use_rccl(pt_multi* m, int* err) {
-    const int world = (int)m->ctx.size();
-    bool use_rccl = m->exchange_pref == 1 || (m->exchange_pref == 0 && m->distinct && world > 1);
-    *err = PT_OK;
-    if (use_rccl && (!rccl().ok() || !m->distinct)) {
-        if (m->exchange_pref == 1) *err = mfail(m, PT_ERR_UNSUPPORTED, !m->distinct ? "pt_multi: RCCL needs distinct devices" : "pt_multi: librccl not found");
-        use_rccl = false;
-    }
-    return use_rccl;
-}
-// the strips of `slot` (packed on every rank's stream) -> all ranks' receive buffers -> the ranks' display buffers
-static int multi_exchange_display(pt_multi* m, int slot, int which) {
-    const int world = (int)m->ctx.size();
-    pt_multi::Strips& st = m->ex.hand[slot][which];
-    const size_t bytes = (size_t)m->ex.padded * buffer_elem(which);
-    int err;
-    const bool use_rccl = multi_use_rccl(m, &err);
-    if (err) return err;
-    if (use_rccl) {
-        Rccl& R = rccl();
-        if (int rc = multi_comms(m)) return rc;
-        ncclResult_t e = R.GroupStart();
-        for (int r = 0; r < world && e == ncclSuccess; ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            e = R.AllGather(st.send[r], st.recv[r], bytes, kNcclUint8, m->comms[r], m->ctx[r]->stream);
-        }
-        const ncclResult_t e2 = R.GroupEnd();
-        if (e != ncclSuccess || e2 != ncclSuccess) return mfail(m, PT_ERR_HIP, std::string("ncclAllGather: ") + R.GetErrorString(e != ncclSuccess ? e : e2));
-        m->last_exchange = PT_EXCHANGE_RCCL;
-    } else {
-        for (int r = 0; r < world; ++r) {
-            MCK(m, hipSetDevice(m->devices[r]));
-            for (int p = 0; p < world; ++p) {
-                char* dst = (char*)st.recv[p] + (size_t)r * bytes;
-                if (m->devices[p] == m->devices[r]) MCK(m, hipMemcpyAsync(dst, st.send[r], bytes, hipMemcpyDeviceToDevice, m->ctx[r]->stream));
-                else MCK(m, hipMemcpyPeerAsync(dst, m->devices[p], st.send[r], m->devices[r], bytes, m->ctx[r]->stream));
-            }
-            MCK(m, hipEventRecord(m->ex.xfer_done[slot][r], m->ctx[r]->stream));
-        }
-        for (int p = 0; p < world; ++p) {
-            MCK(m, hipSetDevice(m->devices[p]));
-            for (int r = 0; r < world; ++r)
-                if (r != p) MCK(m, hipStreamWaitEvent(m->ctx[p]->stream, m->ex.xfer_done[slot][r], 0));
-        }
-        m->last_exchange = PT_EXCHANGE_PEER_COPY;
-    }
-    for (int r = 0; r < world; ++r) {
-        int rc = mctx(m, r, unpack_display_enqueue(m->ctx[r], which, st.recv[r]), "pt_multi(unpack_display)");
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-// exchange what the previous call packed (if anything) and wait until it is on display
-static int multi_present_pending(pt_multi* m, bool wait) {
-    if (m->pending_slot < 0) return PT_OK;
-    const int slot = m->pending_slot;
-    const uint32_t mask = m->pending_mask;
-    m->pending_slot = -1;
-    m->pending_mask = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int which = 0; which <= PT_BUF_DENOISED; ++which)
-        if (mask & (1u << which)) {
-            int rc = multi_exchange_display(m, slot, which);
-            if (rc) return rc;
-        }
-    ++m->handed;
-    if (wait)
-        for (size_t r = 0; r < m->ctx.size(); ++r) {
-            int rc = mctx(m, (int)r, pt_display_sync(m->ctx[r]), "pt_multi(display)");
-            if (rc) return rc;
-        }
-    m->gather_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return PT_OK;
-}
-static int multi_pack_newest(pt_multi* m, uint32_t mask) {
-    // the slots alternate: the other slot's strips were exchanged by this call a moment ago (they may still be in flight), this slot's
-    // were put on display — and waited for — one call earlier
-    const int use = (int)(m->packs++ & 1);
-    for (int which = 0; which <= PT_BUF_DENOISED; ++which)
-        if (mask & (1u << which)) {
-            int rc = multi_ensure_strips(m, use, which);
-            if (rc) return rc;
-            for (size_t r = 0; r < m->ctx.size(); ++r) {
-                rc = mctx(m, (int)r, pack_async_enqueue(m->ctx[r], which, m->ex.hand[use][which].send[r], use), "pt_multi(pack)");
-                if (rc) return rc;
-            }
-        }
-    m->pending_slot = use;
-    m->pending_mask = mask;
-    return PT_OK;
-}
-
-// One frame (or launch chain of `count` subframes, or — regions != null — one foveated frame) on every rank.
-static int multi_render_common(pt_multi* m, uint32_t spp, uint32_t subframe_index, uint32_t count, const pt_region* regions, uint32_t nreg,
-                               const pt_variant* variant, uint32_t gather_mask, uint32_t* host_rgba8, const char* what) {
-    const int world = (int)m->ctx.size();
-    if (world == 0) return PT_OK;
-    if (host_rgba8) gather_mask |= 1u << PT_BUF_FRAME;
-    if (gather_mask >> (PT_BUF_DENOISED + 1)) return mfail(m, PT_ERR_INVALID, std::string(what) + ": unknown buffer in gather_mask");
-    const int F = frames_mode(m->ctx[0]);
-    auto enqueue = [&](int r, int slot, int mode) {
-        pt_ctx* c = m->ctx[r];
-        return regions ? regions_enqueue(c, regions, nreg, variant, slot, mode != 0) : render_enqueue(c, spp, subframe_index, slot, mode, count);
-    };
-    auto enqueue_pipelined = [&](int r) { return enqueue_next_slot(m->ctx[r], F, [&](int slot) { return enqueue(r, slot, F); }); };
-    if (F > 1 && gather_mask == 0) {
-        // pure throughput (nothing is handed over after this frame): pt_options.frames_in_flight applies on every device
-        int rc = multi_present_pending(m, true); // a frame of an earlier call that was waiting for its hand-over
-        int rc1 = multi_run(m, enqueue_pipelined, what, &m->enqueue_ms);
-        int rc2 = multi_run(m, [&](int r) { return pipelined_wait(m->ctx[r], F); }, what);
-        return rc ? rc : (rc1 ? rc1 : rc2);
-    }
-    if (F > 1) {
-        // Frames in flight AND a hand-over: frame k is enqueued, then the strips frame k-1 packed behind itself are exchanged and
-        // scattered into the display buffers while frame k renders, then frame k's pack is enqueued behind frame k.  The call
-        // returns when frame k-1 is on display (host_rgba8 receives it) and at most F-1 frames are still running.
-        int rc = multi_run(m, enqueue_pipelined, what, &m->enqueue_ms);
-        if (rc) return rc;
-        const bool had = m->pending_slot >= 0;
-        rc = multi_present_pending(m, true);
-        if (rc) return rc;
-        if (m->ctx[0]->width) {
-            rc = multi_pack_newest(m, gather_mask);
-            if (rc) return rc;
-        }
-        rc = multi_run(m, [&](int r) { return pipelined_wait(m->ctx[r], F); }, what);
-        if (rc) return rc;
-        if (host_rgba8 && had && m->ctx[0]->width)
-            return mctx(m, 0, pt_download_display(m->ctx[0], PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)m->ctx[0]->width * m->ctx[0]->height), what);
-        return PT_OK;
-    }
-    // synchronous frames: every rank enqueues and finishes its own frame on its own thread, then the hand-over
-    int rc = multi_present_pending(m, true);
-    if (rc) return rc;
-    rc = multi_run(m, [&](int r) { return enqueue(r, 0, 0); }, what, &m->enqueue_ms);
-    int rc2 = multi_run(m, [&](int r) { return render_finish(m->ctx[r]); }, what); // every rank's frame is waited for, also after a failure
-    if (rc || rc2) return rc ? rc : rc2;
-    return multi_after_render(m, gather_mask, host_rgba8);
-}
-
-extern "C" int pt_multi_render(pt_multi* m, uint32_t spp, uint32_t subframe_index, uint32_t gather_mask, uint32_t* host_rgba8) {
-    return pt_multi_render_batch(m, spp, subframe_index, 1, gather_mask, host_rgba8);
-}
-
-extern "C" int pt_multi_render_batch(pt_multi* m, uint32_t spp, uint32_t subframe_index, uint32_t count, uint32_t gather_mask, uint32_t* host_rgba8) {
-    if (!m) return PT_ERR_INVALID;
-    return multi_render_common(m, spp, subframe_index, count, nullptr, 0, nullptr, gather_mask, host_rgba8, "pt_multi_render");
-}
-
-extern "C" int pt_multi_render_regions(pt_multi* m, const pt_region* regions, uint32_t n, const pt_variant* variant, uint32_t gather_mask, uint32_t* host_rgba8) {
-    if (!m || (!regions && n)) return PT_ERR_INVALID;
-    if (!m->ctx.empty() && m->ctx[0]->vw.n) return mfail(m, PT_ERR_UNSUPPORTED, "pt_multi_render_regions: not with viewports set (pt_multi_set_views)");
-    return multi_render_common(m, 0, 0, 1, regions, n, variant, gather_mask, host_rgba8, "pt_multi_render_regions");
-}
-
-// the frame that is still waiting for its hand-over (overlapped path) is exchanged and put on display
-extern "C" int pt_multi_flush(pt_multi* m, uint32_t* host_rgba8) {
-    if (!m) return PT_ERR_INVALID;
-    const bool had = m->pending_slot >= 0;
-    const bool frame = had && (m->pending_mask & (1u << PT_BUF_FRAME));
-    int rc = multi_present_pending(m, true);
-    if (rc) return rc;
-    if (host_rgba8 && frame && !m->ctx.empty() && m->ctx[0]->width)
-        return mctx(m, 0, pt_download_display(m->ctx[0], PT_BUF_FRAME, host_rgba8, sizeof(uint32_t) * (size_t)m->ctx[0]->width * m->ctx[0]->height), "pt_multi_flush");
-    return PT_OK;
-}
-
-extern "C" int pt_multi_get_stats(const pt_multi* m, pt_multi_stats* out) {
-    if (!m || !out) return PT_ERR_INVALID;
-    memset(out, 0, sizeof(*out));
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        pt_stats s;
-        pt_get_stats(m->ctx[r], &s);
-        out->sum.radiance_rays += s.radiance_rays;
-        out->sum.shadow_rays += s.shadow_rays;
-        out->sum.shaded_hits += s.shaded_hits;
-        out->sum.paths += s.paths;
-        out->sum.frames += s.frames; // frames x ranks
-        out->sum.total_radiance_rays += s.total_radiance_rays;
-        out->sum.total_shadow_rays += s.total_shadow_rays;
-        out->sum.render_ms = std::max(out->sum.render_ms, s.render_ms);
-        out->sum.trace_ms = std::max(out->sum.trace_ms, s.trace_ms);
-        out->sum.shadow_ms = std::max(out->sum.shadow_ms, s.shadow_ms);
-        out->sum.shade_ms = std::max(out->sum.shade_ms, s.shade_ms);
-        out->sum.other_ms = std::max(out->sum.other_ms, s.other_ms);
-        out->sum.trace_launches += s.trace_launches;
-        out->sum.shadow_launches += s.shadow_launches;
-        out->sum.shade_launches += s.shade_launches;
-        out->sum.fused_passes += s.fused_passes;
-        out->sum.bvh_nodes = s.bvh_nodes;
-        out->sum.bvh_bytes = s.bvh_bytes;
-        out->sum.bvh_levels = s.bvh_levels;
-        out->sum.bvh_builder = s.bvh_builder;
-        out->sum.bvh_build_ms = std::max(out->sum.bvh_build_ms, s.bvh_build_ms);
-    }
-    out->gather_ms = m->gather_ms;
-    out->exchange = m->last_exchange;
-    out->ndev = (int)m->ctx.size();
-    out->enqueue_ms = m->enqueue_ms;
-    out->threads = (int32_t)m->workers.size();
-    out->frames_handed_over = m->handed;
-    return PT_OK;
-}
-
-// stage on every rank, then commit on every rank: an update that one rank refuses changes none
-static int multi_update(pt_multi* m, const UpdateSource& S, int mode, double* kernel_ms, const char* what) {
-    const int world = (int)m->ctx.size();
-    int rc = PT_OK;
-    std::vector<MeshUpdate> U(world);
-    for (int r = 0; r < world && rc == PT_OK; ++r) rc = mctx(m, r, update_stage(m->ctx[r], S, mode, U[r]), what);
-    double slow = 0;
-    for (int r = 0; r < world && rc == PT_OK; ++r) {
-        double ms = 0;
-        rc = mctx(m, r, update_commit(m->ctx[r], mode, U[r], &ms), what);
-        slow = std::max(slow, ms);
-    }
-    if (rc == PT_OK && kernel_ms) *kernel_ms = slow;
-    return rc;
-}
-extern "C" int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates, uint32_t n, int mode, double* kernel_ms) {
-    if (!m) return PT_ERR_INVALID;
-    std::string err;
-    const int rc = update_validate(m->ctx[0], updates, n, mode, err);
-    if (rc != PT_OK) return mfail(m, rc, err);
-    UpdateSource S{"pt_update_meshes"};
-    S.host = updates;
-    S.n = n;
-    return multi_update(m, S, mode, kernel_ms, "pt_multi_update_meshes");
-}
-
-extern "C" int pt_multi_transform_meshes(pt_multi* m, const pt_mesh_transform* t, uint32_t n, int source, int mode, double* kernel_ms) {
-    if (!m) { (void)fail(nullptr, PT_ERR_INVALID, "pt_multi_transform_meshes: null pt_multi"); return mfail(nullptr, PT_ERR_INVALID, "pt_multi_transform_meshes: null pt_multi"); }
-    std::string err;
-    const int rc = transform_validate(m->ctx[0], t, n, source, mode, err, "pt_multi_transform_meshes");
-    if (rc != PT_OK) return mfail(m, rc, err);
-    UpdateSource S{"pt_multi_transform_meshes"};
-    S.xform = t;
-    S.from = source;
-    S.n = n;
-    return multi_update(m, S, mode, kernel_ms, "pt_multi_transform_meshes");
 }

@@ -1,0 +1,70 @@
+// Looking inside a context, for tests and tools: pt_export_bvh (the wide BVH in its documented layout) and pt_eval_table (the device's
+// BSDF, probe, colour, math, RNG and texture functions evaluated over a table of inputs).  Part of pt_lib.hip.
+extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes, uint32_t* num_nodes, uint32_t* num_tris) {
+    if (!ctx) return PT_ERR_INVALID;
+    // the exported layout is the documented 80-byte node whatever the kernels traverse (PT8_NODE64: converted on the device, box for box)
+    static_assert(sizeof(Node80) == 80 && sizeof(LeafTri) == 48, "exported layout");
+    if (num_nodes) *num_nodes = ctx->bvh.num_nodes8;
+    if (num_tris) *num_tris = ctx->bvh.num_tris8;
+    if (!nodes && !tris) return PT_OK;
+    if (!nodes || !tris || nodes_bytes != sizeof(Node80) * (size_t)ctx->bvh.num_nodes8 || tris_bytes != sizeof(LeafTri) * (size_t)ctx->bvh.num_tris8)
+        return fail(ctx, PT_ERR_INVALID, "pt_export_bvh: buffer sizes must be num_nodes * 80 and num_tris * 48 bytes");
+    CK(hipSetDevice(ctx->device));
+#if PT8_NODE64
+    {
+        int rc = drain(ctx);
+        if (rc) return rc;
+        DevOwner tmp;
+        uint8_t* tmp80 = nullptr;
+        CK(tmp.alloc(&tmp80, nodes_bytes));
+        hipLaunchKernelGGL(k_nodes_to80, dim3((ctx->bvh.num_nodes8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.nodes8, ctx->bvh.num_nodes8, ctx->bvh.grid, reinterpret_cast<Node80*>(tmp80));
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(nodes, tmp80, nodes_bytes, hipMemcpyDeviceToHost);
+        CK(e);
+    }
+#else
+    CK(hipMemcpy(nodes, ctx->bvh.nodes8, nodes_bytes, hipMemcpyDeviceToHost));
+#endif
+    CK(hipMemcpy(tris, ctx->bvh.tris8, tris_bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material, int bsdf_mode, const float* in, uint32_t n, float* out) {
+    if (!ctx || !in || !out) return PT_ERR_INVALID;
+    if (n == 0) return PT_OK;
+    static const int in_w[9] = {11, 9, 1, 3, 3, 3, 2, 2, 3}, out_w[9] = {4, 6, 9, 6, 1, 1, 8, 4, 1};
+    if (which < 0 || which > 8) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: unknown table");
+    if (which <= 1 && !material) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: material required");
+    if ((which == 2 || which == 3 || which == 8) && !ctx->pr.dev.data) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: no probe set");
+    if (which == 7 && !ctx->sc.tex0.pixel) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: the scene has no texture");
+    CK(hipSetDevice(ctx->device));
+    DevOwner tmp;
+    float *dIn = nullptr, *dOut = nullptr;
+    CK(tmp.alloc(&dIn, (size_t)n * in_w[which]));
+    CK(tmp.alloc(&dOut, (size_t)n * out_w[which]));
+    CK(hipMemcpy(dIn, in, sizeof(float) * (size_t)n * in_w[which], hipMemcpyHostToDevice));
+    const dim3 g((n + 127) / 128), b(128);
+    pt_material mat{};
+    if (material) mat = *material;
+    switch (which) {
+        case 0:
+            if (bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_table_bsdf<PT_BSDF_LAMBERT>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
+            else hipLaunchKernelGGL((k_table_bsdf<PT_BSDF_DISNEY>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
+            break;
+        case 1:
+            if (bsdf_mode == PT_BSDF_LAMBERT) hipLaunchKernelGGL((k_table_sample<PT_BSDF_LAMBERT>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
+            else hipLaunchKernelGGL((k_table_sample<PT_BSDF_DISNEY>), g, b, 0, ctx->stream, mat, dIn, n, dOut);
+            break;
+        case 2: hipLaunchKernelGGL(k_table_probe_sample, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
+        case 3: hipLaunchKernelGGL(k_table_probe_eval, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
+        case 4: hipLaunchKernelGGL(k_table_color, g, b, 0, ctx->stream, dIn, n, dOut); break;
+        case 5: hipLaunchKernelGGL(k_table_math, g, b, 0, ctx->stream, dIn, n, dOut); break;
+        case 6: hipLaunchKernelGGL(k_table_rng, g, b, 0, ctx->stream, dIn, n, dOut); break;
+        case 7: hipLaunchKernelGGL(k_table_tex, g, b, 0, ctx->stream, ctx->sc.tex0, dIn, n, dOut); break;
+        case 8: hipLaunchKernelGGL(k_table_probe_pdf, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
+    }
+    CK(hipStreamSynchronize(ctx->stream));
+    CK(hipGetLastError());
+    CK(hipMemcpy(out, dOut, sizeof(float) * (size_t)n * out_w[which], hipMemcpyDeviceToHost));
+    return PT_OK;
+}

@@ -83,15 +83,27 @@ def test_product_never_imports_the_oracle():
                     assert pat not in s, f"{f} references the checker ({pat})"
 
 
+CSRC = os.path.join(ROOT, "optixpathtracer_amd", "csrc")
+
+
+def _quoted_includes(name):
+    """The #include "..." lines of a file under csrc/, as paths relative to csrc/."""
+    src = open(os.path.join(CSRC, name)).read()
+    return [os.path.normpath(os.path.join(os.path.dirname(name), inc)) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src, flags=re.M)]
+
+
 def test_device_memory_has_one_owner():
-    """pt_api.hip and pt_pass.h allocate and free device memory, pinned memory and events only inside DevOwner: every group of the context
-    frees what it owns when it is reset or destroyed, so there is no list of frees to keep in step with the allocations (and
-    PT_ALLOC_FAIL_AT, read by DevOwner::alloc, reaches every allocation site)."""
+    """The library's device translation unit (every file pt_lib.hip includes: pt_api.hip, the area files, pt_pass.h and the pass files)
+    allocates and frees device memory, pinned memory and events only inside DevOwner: every group of the context frees what it owns when
+    it is reset or destroyed, so there is no list of frees to keep in step with the allocations (and PT_ALLOC_FAIL_AT, read by
+    DevOwner::alloc, reaches every allocation site)."""
     calls = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventCreate(", "hipEventCreateWithFlags(", "hipEventDestroy(")
     exceptions = {}  # {(file, call): reason}: none — the frame slots' event pools and pick_streams' stamp words are owned like everything else
-    csrc = os.path.join(ROOT, "optixpathtracer_amd", "csrc")
-    for name in ("pt_api.hip", "pt_pass.h"):
-        s = open(os.path.join(csrc, name)).read()
+    names = _quoted_includes("pt_lib.hip")
+    passes = [n for n in names if n.endswith(".hip") and os.path.exists(os.path.join(CSRC, n[:-4] + ".h"))]
+    assert names[0] == "pt_api.hip" and "pt_pass.h" in names and len(names) >= 22 and len(passes) >= 12
+    for name in names:
+        s = open(os.path.join(CSRC, name)).read()
         if name == "pt_api.hip":  # the owner's definition: from its first line to the closing brace at the start of a line
             a = s.index("struct DevOwner {")
             b = s.index("\n};\n", a)
@@ -99,6 +111,33 @@ def test_device_memory_has_one_owner():
             s = s[:a] + s[b:]
         for c in calls:
             assert c not in s or (name, c) in exceptions, f"{name} calls {c[:-1]} outside DevOwner"
+
+
+def test_makefile_rebuilds_the_library_for_every_source_of_pt_lib():
+    """Every file pt_lib.hip includes, and every header those files include (transitively), is a prerequisite of the Makefile's
+    %.o: %.hip rule: a file missing there means a stale libptamd.so after an edit.  The Makefile is read as text."""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    var = dict(re.findall(r"^(\w+)\s*\??=[ \t]*(.*)$", mk, flags=re.M))
+
+    def expand(text):
+        for _ in range(8):
+            text = re.sub(r"\$\((\w+)\)", lambda m: var.get(m.group(1), ""), text)
+        return text
+
+    rule = re.search(r"^%\.o:\s*%\.hip\s+(.*)$", mk, flags=re.M)
+    assert rule, "no %.o: %.hip rule"
+    prereq = {os.path.normpath(p) for p in expand(rule.group(1)).split()}
+    need, todo = set(), _quoted_includes("pt_lib.hip")
+    assert len(todo) >= 22
+    while todo:
+        name = todo.pop()
+        if name not in need:
+            need.add(name)
+            assert os.path.exists(os.path.join(CSRC, name)), name
+            todo += _quoted_includes(name)
+    assert {"pt_api.hip", "pt_multi.hip", "pt_pass.h", "pt_bloom.hip", "pt_bloom.h", "pt_pass_dev.h", "pt_kernels.h"} <= need
+    missing = sorted(need - prereq)
+    assert not missing, f"csrc/Makefile: the %.o: %.hip rule lacks {missing}"
 
 
 def test_headers_compile_as_c99_and_cxx17(tmp_path):
