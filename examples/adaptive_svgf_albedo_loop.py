@@ -28,10 +28,12 @@ With --bloom [--bloom-threshold T --bloom-levels N] bloomPlanes sits behind modu
 linear frame above T (on luminance exposed by the PREVIOUS frame's exposure state: this frame's is not metered yet) is spread over a pyramid
 of N levels and added back.  The meter still reads the frame without bloom, the tone mapper the one with it; without --auto-exposure the
 bloomed frame is displayed through the linear operator at exposure 1.
+With --motion-blur [--shutter F --blur-taps N] motionBlurPlanes sits behind edge AA and bloom and in front of the tone map: the linear frame
+is blurred along the G-buffer's motion plane (the camera's orbit here), depth-aware, over F of the frame interval with N taps a pixel.
 
   python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--edge-aa]
                                                 [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
-                                                [--bloom-levels N] [--out-dir .]
+                                                [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N] [--out-dir .]
 """
 import argparse
 import os
@@ -82,6 +84,9 @@ def main():
     ap.add_argument("--bloom", action="store_true", help="bloom (bloomPlanes) behind modulate / edge AA and in front of the tone map")
     ap.add_argument("--bloom-threshold", type=float, default=1.0, metavar="T", help="with --bloom: the exposed luminance above which a pixel blooms")
     ap.add_argument("--bloom-levels", type=int, default=6, metavar="N", help="with --bloom: the levels of the pyramid (1..8)")
+    ap.add_argument("--motion-blur", action="store_true", help="motion blur (motionBlurPlanes) behind edge AA / bloom and in front of the tone map")
+    ap.add_argument("--shutter", type=float, default=0.5, metavar="F", help="with --motion-blur: the open fraction of the frame interval, in [0, 4]")
+    ap.add_argument("--blur-taps", type=int, default=12, metavar="N", help="with --motion-blur: taps per pixel (1..64)")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args()
     args.lod = args.lod or args.aniso > 0
@@ -100,7 +105,8 @@ def main():
         return torch.zeros((h, w, k) if k > 1 else (h, w), device=dev)
 
     # two sets of G-buffer planes (this frame's, last frame's), two of history, moments and length: everything is reused
-    gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2)) for _ in range(2)]
+    gplanes = ("hit", "position", "motion") + (("depth",) if args.motion_blur else ())
+    gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2), **(dict(depth=planes(1)) if args.motion_blur else {})) for _ in range(2)]
     history, moments, length = [planes(4) for _ in range(2)], [planes(2) for _ in range(2)], [planes(1) for _ in range(2)]
     variance, filtered, scratch, albedo, final = planes(1), planes(4), planes(4), planes(4), planes(4)
     modulated = planes(4) if args.edge_aa else None  # step 8's output where step 9 follows it
@@ -109,6 +115,8 @@ def main():
     state = [torch.zeros((1, 4), device=dev) for _ in range(2)]
     bloomed = planes(4) if args.bloom else None  # --bloom: its output and its scratch pyramid
     pyramid = torch.zeros((sample.bloomLayout(args.bloom_levels)[1] // 16, 4), device=dev) if args.bloom else None
+    blurred = planes(4) if args.motion_blur else None  # --motion-blur: its output and its scratch (tile and neighbourhood maxima)
+    tiles = torch.zeros((sample.motionBlurLayout()[1] // 8, 2), device=dev) if args.motion_blur else None
     accum = sample.deviceBuffer(R.PT_BUF_ACCUM)
     table = sample.copyTexcoordsDevice()  # the scene's texcoords per primitive: once, whatever moves later
     mips = sample.copyTextureMipsDevice() if args.lod else None  # the mip pyramid of the scene's textures: once, too
@@ -118,7 +126,7 @@ def main():
         cur, old = gbuf[k & 1], gbuf[~k & 1]
         i, o = k & 1, ~k & 1
         sample.setCamera(cam)
-        g = sample.renderGBuffer(("hit", "position", "motion"), prev_cameras=prev, out=cur)
+        g = sample.renderGBuffer(gplanes, prev_cameras=prev, out=cur)
         if args.aniso:
             s = sample.surfaceAnisoPlanes(cur["hit"], table, mips, max_aniso=args.aniso, footprint_scale=args.footprint_scale, out=dict(albedo=albedo))
         elif args.lod:
@@ -137,7 +145,8 @@ def main():
         assert c["stats"]["lost"] == 0  # the plan samples every block that holds a pixel the carry could not carry
         f = sample.filterPlanes(history[o], cur["hit"], cur["position"], variance=variance, length=length[o], out=filtered, scratch=scratch,
                                 iterations=args.iterations, sigma_lum=args.sigma_lum, min_length=args.min_length)
-        shown = None if args.auto_exposure or args.bloom else frame  # with --auto-exposure or --bloom the tone mapper writes the displayed frame
+        # with --auto-exposure, --bloom or --motion-blur the tone mapper writes the displayed frame
+        shown = None if args.auto_exposure or args.bloom or args.motion_blur else frame
         if args.edge_aa:
             m = sample.modulatePlanes(filtered, albedo=albedo, out=modulated)
             e = sample.edgeAaPlanes(modulated, cur["hit"], cur["position"], out=final, frame=shown)["stats"]
@@ -148,10 +157,13 @@ def main():
             b = sample.bloomPlanes(final, state=state[i] if args.auto_exposure and k else None, out=bloomed, scratch=pyramid, threshold=args.bloom_threshold,
                                    levels=args.bloom_levels)["stats"]
             lit = bloomed
+        if args.motion_blur:
+            mb = sample.motionBlurPlanes(lit, cur["motion"], cur["depth"], out=blurred, scratch=tiles, shutter=args.shutter, taps=args.blur_taps)["stats"]
+            lit = blurred
         if args.auto_exposure:
             x = sample.exposurePlanes(final, cur["hit"], hist=hist, state_in=state[i] if k else None, state_out=state[o], rate_up=0.25, rate_down=0.5)["stats"]
             tm = sample.tonemapPlanes(lit, state=state[o], frame=frame, op=args.tonemap, write_out=False)["stats"]
-        elif args.bloom:
+        elif args.bloom or args.motion_blur:
             sample.tonemapPlanes(lit, frame=frame, op="linear", write_out=False)
         ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
         print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
@@ -160,12 +172,15 @@ def main():
               f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms"
               + (f", edge aa {e['kernel_ms']:.3f} ms ({e['blended']} of {e['boundary']} boundary pixels blended)" if args.edge_aa else "")
               + (f", bloom {b['kernel_ms']:.3f} ms ({b['bright']} of {b['sources']} pixels bright)" if args.bloom else "")
+              + (f", motion blur {mb['kernel_ms']:.3f} ms ({mb['moving']} of {mb['pixels']} pixels gather)" if args.motion_blur else "")
               + (f", exposure {x['kernel_ms']:.3f} ms (ev {float(state[o][0, 0]):+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
                  f"tone map {tm['kernel_ms']:.3f} ms ({tm['clipped']} pixels clipped)" if args.auto_exposure else ""))
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_final.npy"), final.cpu().numpy())
     np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_frame.npy"), frame.cpu().numpy().view(np.uint32))
     if args.bloom:
         np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_bloomed.npy"), bloomed.cpu().numpy())
+    if args.motion_blur:
+        np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_blurred.npy"), blurred.cpu().numpy())
     print(f"wrote adaptive_svgf_albedo_final.npy and adaptive_svgf_albedo_frame.npy to {args.out_dir}")
     sample.close()
 

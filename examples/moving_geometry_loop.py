@@ -10,11 +10,13 @@ Per frame, in this order:
   5. motion planes:  motionPlanes(hit, snapshot) — where each pixel's surface point was: motion, prev_point, prev_surface
   6. temporal:       temporalAccumulate(hit=prev_surface, position=prev_point, motion=motion), prev_hit / prev_position last frame's G-buffer
   7. filter:         filterPlanes with the CURRENT hit and position
+  8. motion blur:    (--motion-blur) motionBlurPlanes(filtered, the motion of step 5, the G-buffer's depth), so the moved box blurs, then
+                     tonemapPlanes into the displayed frame
 A second history is kept with the camera-only planes of step 4, on the same colour, and the share of pixels that kept their history is
 printed for both routes: on the box the camera-only route loses it every frame (the plane test fails where the surface moved along its
 normal) or keeps the history of another surface point (a face sliding in its own plane).
 
-  python3 examples/moving_geometry_loop.py [--size 640 360] [--frames 8] [--spp 1] [--out-dir .]
+  python3 examples/moving_geometry_loop.py [--size 640 360] [--frames 8] [--spp 1] [--out-dir .] [--motion-blur [--shutter 0.5] [--blur-taps 12]]
 """
 import argparse
 import os
@@ -49,6 +51,9 @@ def main():
     ap.add_argument("--max-history", type=int, default=32)
     ap.add_argument("--iterations", type=int, default=4)
     ap.add_argument("--out-dir", default=".")
+    ap.add_argument("--motion-blur", action="store_true", help="blur the filtered colour along the motion planes' motion (motionBlurPlanes)")
+    ap.add_argument("--shutter", type=float, default=0.5, help="the open fraction of the frame interval, in [0, 4]")
+    ap.add_argument("--blur-taps", type=int, default=12)
     args = ap.parse_args()
     import torch
 
@@ -64,7 +69,10 @@ def main():
     def planes(k):
         return torch.zeros((h, w, k) if k > 1 else (h, w), device=dev)
 
-    gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2)) for _ in range(2)]
+    gplanes = ("hit", "position", "motion") + (("depth",) if args.motion_blur else ())
+    gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2), **(dict(depth=planes(1)) if args.motion_blur else {})) for _ in range(2)]
+    blurred = planes(4) if args.motion_blur else None
+    blur_scratch = torch.zeros((sample.motionBlurLayout()[1] // 8, 2), device=dev) if args.motion_blur else None
     mot = dict(motion=planes(2), prev_point=planes(4), prev_surface=planes(8))
     snapshot = torch.zeros((sample.vertexCount()[0], 3), device=dev)
     # two histories on the same colour: [0] with the object motion, [1] camera-only
@@ -83,7 +91,7 @@ def main():
         sample.setCamera(cam)
         sample.launchParams.frame.subframe_index = k
         sample.render()                                                                 # 3
-        g = sample.renderGBuffer(("hit", "position", "motion"), prev_cameras=prev_cam, out=cur)   # 4
+        g = sample.renderGBuffer(gplanes, prev_cameras=prev_cam, out=cur)               # 4
         m = sample.motionPlanes(cur["hit"], snapshot, prev_cameras=prev_cam, out=mot)   # 5
         # this frame's own colour as a tensor (the per-frame colour recipe of include/pt_amd.h against an empty history)
         sample.temporalAccumulate(sample.deviceBuffer(R.PT_BUF_ACCUM), cur["motion"], cur["hit"], cur["position"], old["hit"], old["position"], none4, none1,
@@ -94,6 +102,12 @@ def main():
                                        history_out=history[1][o], length_out=length[1][o], max_history=args.max_history)
         f = sample.filterPlanes(history[0][o], cur["hit"], cur["position"], length=length[0][o], out=filtered, scratch=scratch, frame=frame,
                                 iterations=args.iterations)                                                                         # 7
+        if args.motion_blur:                                                                                                        # 8
+            b = sample.motionBlurPlanes(filtered, mot["motion"], cur["depth"], out=blurred, scratch=blur_scratch, shutter=args.shutter, taps=args.blur_taps)
+            sample.tonemapPlanes(blurred, frame=frame, op="reinhard", write_out=False)
+            bs = b["stats"]
+            print(f"frame {k}: motion blur {bs['kernel_ms']:.3f} ms, {100.0 * bs['moving'] / max(1, bs['pixels']):.1f} % of the pixels gather, "
+                  f"{bs['taps'] / max(1, bs['moving']):.1f} taps each count, {bs['unknown']} pixels without a motion")
         on_box = cur["hit"].view(torch.int32)[..., 4] == box
         nbox = max(1, int(on_box.sum()))
         kept = [int((length[j][o][on_box] >= 2).sum()) for j in (0, 1)]
@@ -104,7 +118,9 @@ def main():
     np.save(os.path.join(args.out_dir, "moving_history.npy"), history[0][args.frames & 1].cpu().numpy())
     np.save(os.path.join(args.out_dir, "moving_filtered.npy"), filtered.cpu().numpy())
     np.save(os.path.join(args.out_dir, "moving_frame.npy"), frame.cpu().numpy().view(np.uint32))
-    print(f"wrote moving_history.npy, moving_filtered.npy and moving_frame.npy to {args.out_dir}")
+    if args.motion_blur:
+        np.save(os.path.join(args.out_dir, "moving_blurred.npy"), blurred.cpu().numpy())
+    print(f"wrote moving_history.npy, moving_filtered.npy{', moving_blurred.npy' if args.motion_blur else ''} and moving_frame.npy to {args.out_dir}")
     sample.close()
 
 

@@ -26,11 +26,14 @@ Per frame, on `hi`:
      of the linear frame above T (on luminance exposed by the PREVIOUS frame's exposure state: this frame's is not metered yet) over a
      pyramid of N levels and adds it back; the meter still reads the frame without bloom, the tone mapper the one with it.  Without
      --auto-exposure the bloomed frame is displayed through the linear operator at exposure 1.
+ 15. with --motion-blur [--shutter F --blur-taps N], behind steps 12 and 14 and in front of the tone map: step 7's G-buffer also writes
+     depth and motion at the display resolution, and motionBlurPlanes blurs the linear frame along that motion, depth-aware, over F of
+     the frame interval with N taps a pixel.
 `hi` never renders a colour sample.
 
   python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa]
                                           [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
-                                          [--bloom-levels N] [--out-dir .]
+                                          [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N] [--out-dir .]
 """
 import argparse
 import os
@@ -64,7 +67,8 @@ class UpsampledLoop:
     """The two renderers and every plane of the loop, allocated once; frame(k, prev, cam) runs one frame and returns its figures."""
 
     def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
-                 edge_aa=False, auto_exposure=False, tonemap="aces", bloom=False, bloom_threshold=1.0, bloom_levels=6):
+                 edge_aa=False, auto_exposure=False, tonemap="aces", bloom=False, bloom_threshold=1.0, bloom_levels=6,
+                 motion_blur=False, shutter=0.5, blur_taps=12):
         import torch
 
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
@@ -72,6 +76,7 @@ class UpsampledLoop:
         self.edge_aa = bool(edge_aa)
         self.auto_exposure, self.tonemap = bool(auto_exposure), tonemap
         self.bloom, self.bloom_prm = bool(bloom), dict(threshold=float(bloom_threshold), levels=int(bloom_levels))
+        self.motion_blur, self.blur_prm = bool(motion_blur), dict(shutter=float(shutter), taps=int(blur_taps))
         w, h = self.size
         if w % self.scale or h % self.scale:
             raise SystemExit(f"--size {w} {h} is not a multiple of --scale {self.scale}")
@@ -94,7 +99,7 @@ class UpsampledLoop:
         self.history, self.moments = [planes(lh, lw, 4) for _ in range(2)], [planes(lh, lw, 2) for _ in range(2)]
         self.length = [planes(lh, lw, 1) for _ in range(2)]
         self.variance, self.filtered, self.scratch, self.lo_albedo = planes(lh, lw, 1), planes(lh, lw, 4), planes(lh, lw, 4), planes(lh, lw, 4)
-        self.hi_gbuf = dict(hit=planes(h, w, 8), position=planes(h, w, 4))
+        self.hi_gbuf = dict(hit=planes(h, w, 8), position=planes(h, w, 4), **(dict(depth=planes(h, w, 1), motion=planes(h, w, 2)) if self.motion_blur else {}))
         self.albedo, self.upsampled, self.weight, self.final = planes(h, w, 4), planes(h, w, 4), planes(h, w, 1), planes(h, w, 4)
         self.modulated = planes(h, w, 4) if self.edge_aa else None  # step 11's output where step 12 follows it
         self.frame_rgba8 = torch.zeros((h, w), dtype=torch.int32, device="cuda:0")
@@ -104,6 +109,9 @@ class UpsampledLoop:
         # step 14's output and its scratch pyramid
         self.bloomed = planes(h, w, 4) if self.bloom else None
         self.pyramid = torch.zeros((self.hi.bloomLayout(self.bloom_prm["levels"])[1] // 16, 4), device="cuda:0") if self.bloom else None
+        # step 15's output and its scratch (tile and neighbourhood maxima)
+        self.blurred = planes(h, w, 4) if self.motion_blur else None
+        self.tiles = torch.zeros((self.hi.motionBlurLayout()[1] // 8, 2), device="cuda:0") if self.motion_blur else None
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
         self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
@@ -138,11 +146,15 @@ class UpsampledLoop:
         t1 = time.perf_counter()
         # ---- the display resolution: geometry, texture detail, the guided upsample, the product
         hi.setCamera(cam)
-        G = hi.renderGBuffer(("hit", "position"), out=self.hi_gbuf)["stats"]
+        if self.motion_blur:
+            G = hi.renderGBuffer(("hit", "position", "depth", "motion"), prev_cameras=prev, out=self.hi_gbuf)["stats"]
+        else:
+            G = hi.renderGBuffer(("hit", "position"), out=self.hi_gbuf)["stats"]
         S = self._albedo(hi, self.hi_gbuf["hit"], self.albedo)
         u = hi.upsamplePlanes(self.filtered, cur["hit"], cur["position"], self.hi_gbuf["hit"], self.hi_gbuf["position"], self.scale, out=self.upsampled,
                               weight_out=self.weight)["stats"]
-        shown = None if self.auto_exposure or self.bloom else self.frame_rgba8  # with auto exposure or bloom the tone mapper writes the displayed frame
+        # with auto exposure, bloom or motion blur the tone mapper writes the displayed frame
+        shown = None if self.auto_exposure or self.bloom or self.motion_blur else self.frame_rgba8
         if self.edge_aa:
             m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.modulated)["stats"]
             e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=shown)["stats"]
@@ -156,6 +168,11 @@ class UpsampledLoop:
             lit = self.bloomed
         else:
             b = dict(kernel_ms=0.0, bright=0)
+        if self.motion_blur:
+            mb = hi.motionBlurPlanes(lit, self.hi_gbuf["motion"], self.hi_gbuf["depth"], out=self.blurred, scratch=self.tiles, **self.blur_prm)["stats"]
+            lit = self.blurred
+        else:
+            mb = dict(kernel_ms=0.0, moving=0)
         if self.auto_exposure:
             x = hi.exposurePlanes(self.final, self.hi_gbuf["hit"], hist=self.hist, state_in=self.state[i] if k else None, state_out=self.state[o],
                                   rate_up=0.25, rate_down=0.5)["stats"]
@@ -163,7 +180,7 @@ class UpsampledLoop:
             self.cur = o
         else:
             x, tm = dict(kernel_ms=0.0, skipped=0, under=0, over=0), dict(kernel_ms=0.0, clipped=0)
-            if self.bloom:
+            if self.bloom or self.motion_blur:
                 tm = hi.tonemapPlanes(lit, frame=self.frame_rgba8, op="linear", write_out=False)["stats"]
         t2 = time.perf_counter()
         ev = float(self.state[self.cur][0, 0]) if self.auto_exposure else 0.0  # read back for the caller's printing, outside the timed frame
@@ -173,7 +190,8 @@ class UpsampledLoop:
                     gbuffer_ms=G["kernel_ms"], surface_ms=S["kernel_ms"], upsample_ms=u["kernel_ms"], modulate_ms=m["kernel_ms"],
                     pixels=u["pixels"], full=u["full"], rescued=u["rescued"], orphans=u["orphans"], edge_aa_ms=e["kernel_ms"], boundary=e["boundary"],
                     blended=e["blended"], exposure_ms=x["kernel_ms"], tonemap_ms=tm["kernel_ms"], ev=ev, skipped=x["skipped"], under=x["under"],
-                    over=x["over"], clipped=tm["clipped"], bloom_ms=b["kernel_ms"], bright=b["bright"])
+                    over=x["over"], clipped=tm["clipped"], bloom_ms=b["kernel_ms"], bright=b["bright"],
+                    motion_blur_ms=mb["kernel_ms"], moving=mb["moving"])
 
     def close(self):
         self.lo.close()
@@ -195,13 +213,16 @@ def main(argv=None):
     ap.add_argument("--bloom", action="store_true", help="bloom (bloomPlanes) behind modulate / edge AA and in front of the tone map")
     ap.add_argument("--bloom-threshold", type=float, default=1.0, metavar="T", help="with --bloom: the exposed luminance above which a pixel blooms")
     ap.add_argument("--bloom-levels", type=int, default=6, metavar="N", help="with --bloom: the levels of the pyramid (1..8)")
+    ap.add_argument("--motion-blur", action="store_true", help="motion blur (motionBlurPlanes) behind edge AA / bloom and in front of the tone map")
+    ap.add_argument("--shutter", type=float, default=0.5, metavar="F", help="with --motion-blur: the open fraction of the frame interval, in [0, 4]")
+    ap.add_argument("--blur-taps", type=int, default=12, metavar="N", help="with --motion-blur: taps per pixel (1..64)")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
     make, cam0 = SCENES[args.scene]
     loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp, edge_aa=args.edge_aa,
                          auto_exposure=args.auto_exposure, tonemap=args.tonemap, bloom=args.bloom, bloom_threshold=args.bloom_threshold,
-                         bloom_levels=args.bloom_levels)
+                         bloom_levels=args.bloom_levels, motion_blur=args.motion_blur, shutter=args.shutter, blur_taps=args.blur_taps)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -213,11 +234,14 @@ def main(argv=None):
               f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; "
               + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
               + (f"bloom {x['bloom_ms']:.3f} ms ({x['bright']} bright pixels); " if loop.bloom else "")
+              + (f"motion blur {x['motion_blur_ms']:.3f} ms ({x['moving']} pixels gather); " if loop.motion_blur else "")
               + (f"exposure {x['exposure_ms']:.3f} ms (ev {x['ev']:+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
                  f"tone map {x['tonemap_ms']:.3f} ms ({x['clipped']} pixels clipped); " if loop.auto_exposure else "")
               + f"frame {x['frame_ms']:.2f} ms")
     np.save(os.path.join(args.out_dir, "upsampled_svgf_final.npy"), loop.final.cpu().numpy())
     np.save(os.path.join(args.out_dir, "upsampled_svgf_frame.npy"), loop.frame_rgba8.cpu().numpy().view(np.uint32))
+    if loop.motion_blur:
+        np.save(os.path.join(args.out_dir, "upsampled_svgf_blurred.npy"), loop.blurred.cpu().numpy())
     print(f"wrote upsampled_svgf_final.npy and upsampled_svgf_frame.npy to {args.out_dir}")
     loop.close()
     return 0

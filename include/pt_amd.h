@@ -32,7 +32,8 @@
  * pt_edge_aa_planes takes DEVICE pointers under the same contract: it is one more entry point of the list above (its ordering case
  * stands with its other GPU tests, in tests/test_gpu_edge_aa.py).  So do pt_exposure_planes and pt_tonemap_planes (their ordering
  * cases: tests/test_gpu_exposure.py).  pt_bloom_planes takes DEVICE pointers under the same contract, too (its ordering cases:
- * tests/test_gpu_bloom.py); pt_bloom_layout touches no device memory.
+ * tests/test_gpu_bloom.py); pt_bloom_layout touches no device memory.  pt_motion_blur_planes takes DEVICE pointers under the same contract
+ * (its ordering cases: tests/test_gpu_motion_blur.py); pt_motion_blur_layout touches no device memory.
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -45,7 +46,7 @@
  * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes, pt_edge_aa_planes,
  * pt_exposure_planes, pt_tonemap_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.  pt_bloom_layout and pt_bloom_planes were added
- * in the same way and keep "0.4" as well.
+ * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -1672,6 +1673,101 @@ typedef struct pt_bloom_desc {
 } pt_bloom_desc;
 typedef struct pt_bloom_stats { uint64_t pixels, sources, bright, nonfinite; double kernel_ms; } pt_bloom_stats;
 int pt_bloom_planes(pt_ctx* ctx, const pt_bloom_desc* desc, pt_bloom_stats* stats /* may be NULL */);
+
+/* MOTION BLUR (no reference counterpart).  The motion plane of pt_render_gbuffer / pt_motion_planes is used by the reprojection passes to
+ * REMOVE the effect of motion; every frame of the chain has a shutter time of zero, and a loop whose camera or meshes move looks like a
+ * stop-motion sequence.  pt_motion_blur_planes blurs each pixel of a linear colour plane along the dominant motion around it, after McGuire
+ * et al., "A Reconstruction Filter for Plausible Motion Blur" (2012): tile maximum, neighbourhood maximum, then a depth-aware gather.  It
+ * runs behind pt_edge_aa_planes / pt_bloom_planes and in front of pt_tonemap_planes.  Stateless like every pass here: the planes and the
+ * scratch are caller-owned DEVICE memory of the context's device (4-byte aligned, the scratch 8-byte aligned; the planes frame-sized,
+ * indexed Y * width + X); block_mask is HOST memory.  Float32 throughout, one rounding per operation, no fused multiply-add, sqrtf and /
+ * correctly rounded (pt_detmath.h's contract), in the stated order; max(a, b) is a > b ? a : b, min(a, b) is a < b ? a : b, and
+ * clamp01(x) is x = x > 0 ? x : 0; x = x < 1 ? x : 1 (a NaN becomes 0).
+ *
+ * Rectangles and tiles.  Each view's rectangle (x0, y0, wr, hr) has a tile grid of its own, anchored at the rectangle's origin; without
+ * views there is one rectangle, the whole frame; nv = max(1, the view count).  The grid is tw = (wr + 15) / 16 by th = (hr + 15) / 16
+ * tiles of PT_MOTION_BLUR_TILE = 16 pixels a side, partial at the right and at the bottom.  No tap and no tile neighbour ever leaves its
+ * rectangle: a fast object in one eye of a stereo pair puts nothing into the other, and a view holds the bits a context of its own size
+ * would hold.
+ * pt_motion_blur_layout gives the scratch: view after view, a plane T of tw * th texels of 8 bytes (V.x, V.y) in row order, then a plane
+ * N of the same size; *bytes is their sum.  dims (HOST, nv x 4, may be NULL) receives tw, th, the index of T's first 8-byte texel and the
+ * index of N's.  It refuses (PT_ERR_INVALID) a null ctx or bytes and a context without pt_resize.
+ *
+ * What is read, what is written.  The tile pass reads EVERY pixel of every rectangle from motion, whether or not the rank owns it or the
+ * mask names it, and a tap of the gather reads color, motion and depth wherever in the rectangle it lands; the set decides only which pixels
+ * of out are written.  The set is exactly pt_modulate_planes's: owned pixels, view pixels while views are set, whole blocks of the mask.
+ * The ranks of a partitioned frame all-gather colour, motion and depth first.  stats->sources is the number of rectangle pixels read by
+ * the tile pass, stats->pixels the size of the set.  The whole scratch is written by every call, also with an empty set.
+ *
+ * The host computes hs = 0.5f * shutter, R = max_blur and R2 = R * R.
+ *   1. Velocity V(q), l2(q) of a rectangle pixel q, from m = motion[q] (previous minus current position, in pixels).  If one of the two
+ *      words of m is not finite (exponent-bit test): V = (0, 0), l2 = 0, and stats->unknown counts it (in the tile pass: once per rectangle
+ *      pixel).  Otherwise V = m * hs per component — the half-spread: the blur is centred on the current position — then per component
+ *      v = v < -4096.0f ? -4096.0f : v; v = v > 4096.0f ? 4096.0f : v (l2 cannot overflow); l2 = V.x * V.x + V.y * V.y.  If l2 > R2:
+ *      s = R / sqrtf(l2); V = V * s per component; l2 = V.x * V.x + V.y * V.y again, from the scaled V.
+ *   2. Tile maximum.  T(i, j) is the V of greatest l2 among the pixels of tile (i, j) that lie inside the rectangle; ties go to the first
+ *      pixel in row order.
+ *   3. Neighbourhood maximum.  N(i, j) is the T of greatest l2 = T.x * T.x + T.y * T.y over the 3 x 3 tiles around (i, j) that exist in
+ *      the rectangle's grid, visited in row order with a strict >: the first maximum wins.  Because R <= PT_MOTION_BLUR_TILE nothing
+ *      farther away can reach the tile.
+ *   4. Gather, for a pixel p of the set with (x, y) its coordinates in its rectangle: c = color[p].xyz; vN = N(x / 16, y / 16);
+ *      n2 = vN.x * vN.x + vN.y * vN.y.  If n2 > 0.25f is false, or a word of c is not finite: out[p] = (c, 1.0f), raw, and that is all.
+ *      Otherwise stats->moving counts p, and
+ *        lN = sqrtf(n2); lp = max(sqrtf(l2(p)), 0.5f); wp = 1.0f / lp; zp = Z(depth[p]);
+ *        Z(d) = (d > 1e-6f && d <= FLT_MAX) ? d : FLT_MAX — a NaN, an inf, 0 and negatives all become FLT_MAX (a miss holds +inf);
+ *        sum = (0, 0, 0); Wt = 0; then for tap i = 0 .. taps - 1, in this order:
+ *          a = ((float)i + 0.5f) + j;  t = (2.0f * a) / (float)taps - 1.0f;
+ *          qx = (int)floorf(((float)x + vN.x * t) + 0.5f), clamped to [0, wr - 1]; qy = (int)floorf(((float)y + vN.y * t) + 0.5f), clamped
+ *          to [0, hr - 1]; q is that pixel of the rectangle.
+ *          If a word of color[q].xyz is not finite the tap is skipped and stats->nonfinite counts it.  Otherwise
+ *          d = fabsf(t) * lN; lq = max(sqrtf(l2(q)), 0.5f), with V(q) recomputed by step 1; zq = Z(depth[q]);
+ *          e = depth_soft * min(zp, zq);
+ *          fg = clamp01(1.0f - (zq - zp) / e); bg = clamp01(1.0f - (zp - zq) / e);
+ *          cone(l) = clamp01(1.0f - d / l);
+ *          cyl(l) = 1.0f - (u * u) * (3.0f - 2.0f * u), with u = clamp01((d - 0.95f * l) / (1.05f * l - 0.95f * l));
+ *          w = (fg * cone(lq) + bg * cone(lp)) + (cyl(lq) * cyl(lp)) * 2.0f;
+ *          sum = sum + color[q].xyz * w per component; Wt = Wt + w; stats->taps counts w > 0.
+ *      The jitter j is 0.0f without PT_MOTION_BLUR_JITTER.  With it, j = (float)(h >> 8) * 5.9604644775390625e-8f - 0.5f (2^-24: j lies in
+ *      [-0.5, 0.5)), where h is this hash of the LOCAL coordinates and the seed, exact in uint32 arithmetic:
+ *          h = ((uint32_t)x * 0x9E3779B1u) ^ ((uint32_t)y * 0x85EBCA77u) ^ (seed * 0xC2B2AE3Du);
+ *          h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16.
+ *      If Wt == 0: out[p].xyz = c exactly.  Else out[p].xyz = (c * wp + sum) / (wp + Wt) per component.  out[p].w = 1.0f.
+ * Zero motion, an all-unknown motion plane and shutter = 0 give out = (color.xyz, 1) bit for bit, with T and N all zero.  A pixel that
+ * stands still (lp = 0.5) in front of a moving background takes nothing from it once a tap is 0.525 pixels away: with an even tap count and
+ * lN / taps >= 0.525 it keeps its bits (Wt == 0).  Every weight is >= 0, so a finite out[p] lies within the range of the finite colours
+ * up to the roundings of its sums; a non-finite motion, depth or colour word reaches no pixel but the one that holds the bad colour.
+ *
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx, desc, color, motion, depth, out or
+ * scratch; no pt_resize yet; a plane that fails the pointer checks; scratch not 8-byte aligned; any overlap that involves out or scratch
+ * (out may NOT be color: the gather reads neighbours); flag bits other than PT_MOTION_BLUR_JITTER; shutter not finite or outside [0, 4];
+ * max_blur not finite or outside [1, PT_MOTION_BLUR_TILE]; depth_soft not finite or outside (0, 1]; taps outside 1 .. 64.
+ * Ordering and state, as pt_bloom_planes: the call waits for the frames in flight, runs on pt_stream(ctx) under the STREAM CONTRACT, is
+ * complete when it returns, and writes no context state.
+ * Not part of this interface: the paper's refinement of the neighbour maximum (off-diagonal tiles only when they point at the centre);
+ * more than one dominant direction per tile; sub-pixel (bilinear) taps; blur of the bloom pyramid; an asynchronous variant; a pt_multi_*
+ * wrapper (per-rank calls work once colour, motion and depth are gathered); camera-shutter curves. */
+#define PT_MOTION_BLUR_TILE 16
+typedef enum pt_motion_blur_flags { PT_MOTION_BLUR_JITTER = 1 } pt_motion_blur_flags;
+/* scratch in caller memory: bytes for T and N of every view (or of the frame without views);
+ * dims (HOST, nv x 4: tw, th, first 8-byte texel of T, first 8-byte texel of N; may be NULL) */
+int pt_motion_blur_layout(const pt_ctx* ctx, uint32_t* dims, size_t* bytes);
+
+typedef struct pt_motion_blur_desc {
+    const float* color;      /* w*h x 4 linear radiance (.w ignored); required */
+    const float* motion;     /* w*h x 2, pt_render_gbuffer's / pt_motion_planes's format (a NaN pair: unknown); required */
+    const float* depth;      /* w*h, the G-buffer's depth (a miss holds +inf); required */
+    float*       out;        /* w*h x 4; required; exclusive (it may NOT be color) */
+    void*        scratch;    /* pt_motion_blur_layout's bytes, 8-byte aligned; required, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    float shutter;           /* finite, in [0, 4]: the open fraction of the frame interval */
+    float max_blur;          /* finite, in [1, PT_MOTION_BLUR_TILE]: R, in pixels */
+    float depth_soft;        /* finite, in (0, 1]: the relative depth extent over which foreground turns into background */
+    uint32_t taps;           /* 1..64 */
+    uint32_t seed;           /* of the jitter's hash */
+    uint32_t flags;          /* pt_motion_blur_flags */
+} pt_motion_blur_desc;
+typedef struct pt_motion_blur_stats { uint64_t pixels, sources, unknown, moving, taps, nonfinite; double kernel_ms; } pt_motion_blur_stats;
+int pt_motion_blur_planes(pt_ctx* ctx, const pt_motion_blur_desc* desc, pt_motion_blur_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

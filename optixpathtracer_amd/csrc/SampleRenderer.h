@@ -444,6 +444,23 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The size in bytes of motionBlurPlanes's scratch, T and N of every view (pt_motion_blur_layout); dims (host memory, views x 4: tw, th,
+    // the first 8-byte texel of T, the first of N) may be null.
+    size_t motionBlurLayout(uint32_t* dims = nullptr) {
+        size_t bytes = 0;
+        ck(pt_motion_blur_layout(ctx, dims, &bytes));
+        return bytes;
+    }
+    // Motion blur in front of the tone mapper (pt_motion_blur_planes): d.color blurred along the fastest motion (d.motion) of the tiles
+    // around each pixel, depth-aware (d.depth), into d.out, which may not be d.color; d.scratch is motionBlurLayout's bytes, 8-byte
+    // aligned.  Returns the pixels written, the rectangle pixels read, the unknown-motion ones among them, the pixels that gathered, the
+    // taps that counted and the non-finite ones skipped, and the device time.
+    pt_motion_blur_stats motionBlurPlanes(const pt_motion_blur_desc& d, pt_motion_blur_stats* stats = nullptr) {
+        pt_motion_blur_stats s{};
+        ck(pt_motion_blur_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

@@ -37,3 +37,4 @@
 #include "pt_edge_aa.hip"
 #include "pt_exposure.hip"
 #include "pt_bloom.hip"
+#include "pt_motion_blur.hip"

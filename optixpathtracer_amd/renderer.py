@@ -1005,6 +1005,60 @@ class SampleRenderer:
         desc.spread, desc.intensity, desc.levels, desc.flags = float(spread), float(intensity), levels, 0
         return self._run_pass("pt_bloom_planes", desc, _lib.BloomStats(), result)
 
+    def motionBlurLayout(self):
+        """The shape of motionBlurPlanes's scratch (pt_motion_blur_layout): (dims, bytes) with dims a uint32 (views, 4) array of tw, th, the
+        index of T's first 8-byte texel and the index of N's, views = max(1, the view count), and bytes the size of the scratch."""
+        count, nbytes = C.c_uint32(0), C.c_size_t()
+        self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
+        dims = np.zeros((max(1, count.value), 4), np.uint32)
+        self._ck(self._L.pt_motion_blur_layout(self._ctx, dims.ctypes.data, C.byref(nbytes)), "pt_motion_blur_layout")
+        return dims, nbytes.value
+
+    def motionBlurPlanes(self, color, motion, depth, out=None, scratch=None, mask=None, shutter=0.5, max_blur=16.0, depth_soft=0.05, taps=12,
+                         seed=0, jitter=False) -> dict:
+        """Motion blur behind edgeAaPlanes / bloomPlanes and in front of tonemapPlanes (pt_motion_blur_planes, include/pt_amd.h: the rule,
+        in full): each pixel of `color` is blurred along the fastest motion of the 16 x 16 tiles around it — `shutter` of the frame
+        interval, centred on the current position, at most `max_blur` pixels to either side — by a depth-aware gather of `taps` pixels.
+
+        color (h, w, 4), motion ((h, w, 2): renderGBuffer's or motionPlanes's) and depth ((h, w): renderGBuffer's) are CUDA float32 tensors
+        on the context's device — dense, any 4-byte-aligned storage offset — or raw device pointers.  out (h, w, 4) is allocated with
+        torch, zero-filled, when None; it may NOT be `color` (the pass reads neighbours).  scratch: a float32 (texels, 2) tensor with
+        8 * texels = motionBlurLayout()'s bytes, 8-byte aligned, or a raw pointer; allocated when None.  After the call it holds the tile
+        maxima T and the neighbourhood maxima N of every view.  The tile pass reads every pixel of every view whatever the mask and the
+        rank's partition: they decide only which pixels of out are written (a partitioned frame gathers its three planes first).
+        jitter: each pixel's taps are shifted by a hash of its coordinates and `seed`.
+        Returns {"out", "scratch": the tensor (None for a raw pointer), "stats": {pixels, sources, unknown, moving, taps, nonfinite,
+        kernel_ms}}."""
+        import torch
+
+        taps, seed = int(taps), int(seed)
+        if not 1 <= taps <= 64:
+            raise ValueError(f"motionBlurPlanes: taps must be 1..64, not {taps}")
+        if not 0 <= seed < 2**32:
+            raise ValueError("motionBlurPlanes: seed must be in [0,4294967295]")
+        if not 0.0 <= float(shutter) <= 4.0:
+            raise ValueError("motionBlurPlanes: shutter must be in [0,4]")
+        if not 1.0 <= float(max_blur) <= _lib.PT_MOTION_BLUR_TILE:
+            raise ValueError(f"motionBlurPlanes: max_blur must be in [1,{_lib.PT_MOTION_BLUR_TILE}]")
+        if not 0.0 < float(depth_soft) <= 1.0:
+            raise ValueError("motionBlurPlanes: depth_soft must be in (0,1]")
+        desc = _lib.MotionBlurDesc()
+        result = self._bind_planes("motionBlurPlanes", desc, dict(color=color, motion=motion, depth=depth, out=out), _lib.MOTION_BLUR_PLANES,
+                                   ("color", "motion", "depth"), _lib.MOTION_BLUR_OUTPUTS, alloc=("out",))
+        dev = getattr(self, "_device", 0)
+        if isinstance(scratch, int):
+            desc.scratch, result["scratch"] = scratch, None
+        else:
+            texels = self.motionBlurLayout()[1] // 8
+            if scratch is None:
+                scratch = torch.empty((texels, 2), dtype=torch.float32, device=f"cuda:{dev}")
+            _check_temporal_tensor("scratch", scratch, dev, {torch.float32: (texels, 2)}, "motionBlurPlanes")
+            desc.scratch, result["scratch"] = scratch.data_ptr(), scratch
+        m = self._bind_mask("motionBlurPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.shutter, desc.max_blur, desc.depth_soft = float(shutter), float(max_blur), float(depth_soft)
+        desc.taps, desc.seed, desc.flags = taps, seed, _lib.PT_MOTION_BLUR_JITTER if jitter else 0
+        return self._run_pass("pt_motion_blur_planes", desc, _lib.MotionBlurStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
