@@ -30,10 +30,15 @@ of N levels and added back.  The meter still reads the frame without bloom, the 
 bloomed frame is displayed through the linear operator at exposure 1.
 With --motion-blur [--shutter F --blur-taps N] motionBlurPlanes sits behind edge AA and bloom and in front of the tone map: the linear frame
 is blurred along the G-buffer's motion plane (the camera's orbit here), depth-aware, over F of the frame interval with N taps a pixel.
+With --dof [--focus F | --autofocus] [--aperture K] [--dof-taps N] dofPlanes sits behind edge AA and in front of bloom, motion blur and the
+tone map, so that bright out-of-focus points bloom as discs: each pixel gathers N taps of a disc of the largest blur circle around it,
+K * |1 - F / depth| pixels, from the G-buffer's depth plane.  With --autofocus F follows the depth under the frame's centre, smoothed over
+frames (one float read back per frame); on a miss it returns to --focus.
 
   python3 examples/adaptive_svgf_albedo_loop.py [--scene textured|two_box] [--size 960 540] [--frames 16] [--spp 1] [--threshold 0.25] [--lod] [--aniso N] [--edge-aa]
                                                 [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
-                                                [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N] [--out-dir .]
+                                                [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N]
+                                                [--dof] [--focus F | --autofocus] [--aperture K] [--dof-taps N] [--out-dir .]
 """
 import argparse
 import os
@@ -58,6 +63,17 @@ def orbit(cam, angle):
     d = e - l
     c, s = np.cos(angle), np.sin(angle)
     return dict(cam, eye=(float(l[0] + c * d[0] + s * d[2]), float(e[1]), float(l[2] - s * d[0] + c * d[2])))
+
+
+def autofocus(depth, rects, fallback, previous, rate=0.25):
+    """The focus distance of each rectangle (x0, y0, w, h) of a depth plane: the depth under its centre — `fallback` where that is a miss —
+    approached from `previous` (None: taken at once) by `rate` a frame.  Reads one float per rectangle back."""
+    now = []
+    for v, (x0, y0, w, h) in enumerate(rects):
+        d = float(depth[y0 + h // 2, x0 + w // 2])
+        target = d if np.isfinite(d) and d > 0.0 else float(fallback)
+        now.append(target if previous is None else previous[v] + rate * (target - previous[v]))
+    return now
 
 
 def main():
@@ -87,6 +103,11 @@ def main():
     ap.add_argument("--motion-blur", action="store_true", help="motion blur (motionBlurPlanes) behind edge AA / bloom and in front of the tone map")
     ap.add_argument("--shutter", type=float, default=0.5, metavar="F", help="with --motion-blur: the open fraction of the frame interval, in [0, 4]")
     ap.add_argument("--blur-taps", type=int, default=12, metavar="N", help="with --motion-blur: taps per pixel (1..64)")
+    ap.add_argument("--dof", action="store_true", help="depth of field (dofPlanes) behind edge AA and in front of bloom, motion blur and the tone map")
+    ap.add_argument("--focus", type=float, default=4.0, metavar="F", help="with --dof: the depth that is sharp (with --autofocus: where the centre is a miss)")
+    ap.add_argument("--autofocus", action="store_true", help="with --dof: focus on the depth under the frame's centre, smoothed over frames")
+    ap.add_argument("--aperture", type=float, default=6.0, metavar="K", help="with --dof: the blur-circle radius in pixels of a point at infinity")
+    ap.add_argument("--dof-taps", type=int, default=32, metavar="N", help="with --dof: taps per pixel (1..64)")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args()
     args.lod = args.lod or args.aniso > 0
@@ -105,8 +126,8 @@ def main():
         return torch.zeros((h, w, k) if k > 1 else (h, w), device=dev)
 
     # two sets of G-buffer planes (this frame's, last frame's), two of history, moments and length: everything is reused
-    gplanes = ("hit", "position", "motion") + (("depth",) if args.motion_blur else ())
-    gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2), **(dict(depth=planes(1)) if args.motion_blur else {})) for _ in range(2)]
+    gplanes = ("hit", "position", "motion") + (("depth",) if args.motion_blur or args.dof else ())
+    gbuf = [dict(hit=planes(8), position=planes(4), motion=planes(2), **(dict(depth=planes(1)) if args.motion_blur or args.dof else {})) for _ in range(2)]
     history, moments, length = [planes(4) for _ in range(2)], [planes(2) for _ in range(2)], [planes(1) for _ in range(2)]
     variance, filtered, scratch, albedo, final = planes(1), planes(4), planes(4), planes(4), planes(4)
     modulated = planes(4) if args.edge_aa else None  # step 8's output where step 9 follows it
@@ -117,6 +138,9 @@ def main():
     pyramid = torch.zeros((sample.bloomLayout(args.bloom_levels)[1] // 16, 4), device=dev) if args.bloom else None
     blurred = planes(4) if args.motion_blur else None  # --motion-blur: its output and its scratch (tile and neighbourhood maxima)
     tiles = torch.zeros((sample.motionBlurLayout()[1] // 8, 2), device=dev) if args.motion_blur else None
+    lens = planes(4) if args.dof else None  # --dof: its output, its scratch (tile and neighbourhood maxima of the blur radius), the focus
+    discs = torch.zeros((sample.dofLayout()[1] // 4,), device=dev) if args.dof else None
+    focus = None
     accum = sample.deviceBuffer(R.PT_BUF_ACCUM)
     table = sample.copyTexcoordsDevice()  # the scene's texcoords per primitive: once, whatever moves later
     mips = sample.copyTextureMipsDevice() if args.lod else None  # the mip pyramid of the scene's textures: once, too
@@ -145,16 +169,20 @@ def main():
         assert c["stats"]["lost"] == 0  # the plan samples every block that holds a pixel the carry could not carry
         f = sample.filterPlanes(history[o], cur["hit"], cur["position"], variance=variance, length=length[o], out=filtered, scratch=scratch,
                                 iterations=args.iterations, sigma_lum=args.sigma_lum, min_length=args.min_length)
-        # with --auto-exposure, --bloom or --motion-blur the tone mapper writes the displayed frame
-        shown = None if args.auto_exposure or args.bloom or args.motion_blur else frame
+        # with --auto-exposure, --dof, --bloom or --motion-blur the tone mapper writes the displayed frame
+        shown = None if args.auto_exposure or args.dof or args.bloom or args.motion_blur else frame
         if args.edge_aa:
             m = sample.modulatePlanes(filtered, albedo=albedo, out=modulated)
             e = sample.edgeAaPlanes(modulated, cur["hit"], cur["position"], out=final, frame=shown)["stats"]
         else:
             m = sample.modulatePlanes(filtered, albedo=albedo, out=final, frame=shown)
         lit = final
+        if args.dof:
+            focus = autofocus(cur["depth"], [(0, 0, w, h)], args.focus, focus) if args.autofocus else [args.focus]
+            df = sample.dofPlanes(lit, cur["depth"], out=lens, scratch=discs, focus=focus[0], aperture=args.aperture, taps=args.dof_taps)["stats"]
+            lit = lens
         if args.bloom:
-            b = sample.bloomPlanes(final, state=state[i] if args.auto_exposure and k else None, out=bloomed, scratch=pyramid, threshold=args.bloom_threshold,
+            b = sample.bloomPlanes(lit, state=state[i] if args.auto_exposure and k else None, out=bloomed, scratch=pyramid, threshold=args.bloom_threshold,
                                    levels=args.bloom_levels)["stats"]
             lit = bloomed
         if args.motion_blur:
@@ -163,7 +191,7 @@ def main():
         if args.auto_exposure:
             x = sample.exposurePlanes(final, cur["hit"], hist=hist, state_in=state[i] if k else None, state_out=state[o], rate_up=0.25, rate_down=0.5)["stats"]
             tm = sample.tonemapPlanes(lit, state=state[o], frame=frame, op=args.tonemap, write_out=False)["stats"]
-        elif args.bloom or args.motion_blur:
+        elif args.dof or args.bloom or args.motion_blur:
             sample.tonemapPlanes(lit, frame=frame, op="linear", write_out=False)
         ps, ss, ts, cs, fs = p["stats"], s["stats"], t["stats"], c["stats"], f["stats"]
         print(f"frame {k}: {ps['sampled']} of {ps['blocks']} blocks sampled, {rendered} pixels rendered, {cs['carried']} carried, "
@@ -171,6 +199,7 @@ def main():
               f"plan {ps['kernel_ms']:.3f} ms, colour {sample.stats()['render_ms']:.2f} ms, temporal {ts['kernel_ms']:.3f} ms, "
               f"carry {cs['kernel_ms']:.3f} ms, filter {fs['kernel_ms']:.3f} ms, modulate {m['stats']['kernel_ms']:.3f} ms"
               + (f", edge aa {e['kernel_ms']:.3f} ms ({e['blended']} of {e['boundary']} boundary pixels blended)" if args.edge_aa else "")
+              + (f", depth of field {df['kernel_ms']:.3f} ms ({df['gathered']} of {df['pixels']} pixels gather, focus {focus[0]:.3f})" if args.dof else "")
               + (f", bloom {b['kernel_ms']:.3f} ms ({b['bright']} of {b['sources']} pixels bright)" if args.bloom else "")
               + (f", motion blur {mb['kernel_ms']:.3f} ms ({mb['moving']} of {mb['pixels']} pixels gather)" if args.motion_blur else "")
               + (f", exposure {x['kernel_ms']:.3f} ms (ev {float(state[o][0, 0]):+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
@@ -181,6 +210,8 @@ def main():
         np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_bloomed.npy"), bloomed.cpu().numpy())
     if args.motion_blur:
         np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_blurred.npy"), blurred.cpu().numpy())
+    if args.dof:
+        np.save(os.path.join(args.out_dir, "adaptive_svgf_albedo_dof.npy"), lens.cpu().numpy())
     print(f"wrote adaptive_svgf_albedo_final.npy and adaptive_svgf_albedo_frame.npy to {args.out_dir}")
     sample.close()
 

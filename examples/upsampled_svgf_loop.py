@@ -29,11 +29,16 @@ Per frame, on `hi`:
  15. with --motion-blur [--shutter F --blur-taps N], behind steps 12 and 14 and in front of the tone map: step 7's G-buffer also writes
      depth and motion at the display resolution, and motionBlurPlanes blurs the linear frame along that motion, depth-aware, over F of
      the frame interval with N taps a pixel.
+ 16. with --dof [--focus F | --autofocus] [--aperture K] [--dof-taps N], behind step 12 and in front of steps 14, 15 and the tone map (so
+     that bright out-of-focus points bloom as discs): step 7's G-buffer also writes depth, and dofPlanes gathers each pixel over a disc of
+     the largest blur circle around it, K * |1 - F / depth| pixels, with N taps.  With --autofocus F follows the depth under the frame's
+     centre, smoothed over frames (one float read back per frame); on a miss it returns to --focus.
 `hi` never renders a colour sample.
 
   python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa]
                                           [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
-                                          [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N] [--out-dir .]
+                                          [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N]
+                                          [--dof] [--focus F | --autofocus] [--aperture K] [--dof-taps N] [--out-dir .]
 """
 import argparse
 import os
@@ -55,6 +60,17 @@ SCENES = {
 PLAN = dict(threshold=0.25, dark_floor=0.05, min_length=4, min_pixels=8, refresh_period=16)
 
 
+def autofocus(depth, rects, fallback, previous, rate=0.25):
+    """The focus distance of each rectangle (x0, y0, w, h) of a depth plane: the depth under its centre — `fallback` where that is a miss —
+    approached from `previous` (None: taken at once) by `rate` a frame.  Reads one float per rectangle back."""
+    now = []
+    for v, (x0, y0, w, h) in enumerate(rects):
+        d = float(depth[y0 + h // 2, x0 + w // 2])
+        target = d if np.isfinite(d) and d > 0.0 else float(fallback)
+        now.append(target if previous is None else previous[v] + rate * (target - previous[v]))
+    return now
+
+
 def orbit(cam, angle):
     """the camera turned by `angle` radians about the vertical axis through its look-at point"""
     e, l = np.asarray(cam["eye"], np.float64), np.asarray(cam["lookat"], np.float64)
@@ -68,7 +84,7 @@ class UpsampledLoop:
 
     def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
                  edge_aa=False, auto_exposure=False, tonemap="aces", bloom=False, bloom_threshold=1.0, bloom_levels=6,
-                 motion_blur=False, shutter=0.5, blur_taps=12):
+                 motion_blur=False, shutter=0.5, blur_taps=12, dof=False, focus=4.0, autofocus=False, aperture=6.0, dof_taps=32):
         import torch
 
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
@@ -77,6 +93,8 @@ class UpsampledLoop:
         self.auto_exposure, self.tonemap = bool(auto_exposure), tonemap
         self.bloom, self.bloom_prm = bool(bloom), dict(threshold=float(bloom_threshold), levels=int(bloom_levels))
         self.motion_blur, self.blur_prm = bool(motion_blur), dict(shutter=float(shutter), taps=int(blur_taps))
+        self.dof, self.dof_prm = bool(dof), dict(aperture=float(aperture), taps=int(dof_taps))
+        self.focus, self.autofocus, self.focus_now = float(focus), bool(autofocus), None
         w, h = self.size
         if w % self.scale or h % self.scale:
             raise SystemExit(f"--size {w} {h} is not a multiple of --scale {self.scale}")
@@ -99,7 +117,8 @@ class UpsampledLoop:
         self.history, self.moments = [planes(lh, lw, 4) for _ in range(2)], [planes(lh, lw, 2) for _ in range(2)]
         self.length = [planes(lh, lw, 1) for _ in range(2)]
         self.variance, self.filtered, self.scratch, self.lo_albedo = planes(lh, lw, 1), planes(lh, lw, 4), planes(lh, lw, 4), planes(lh, lw, 4)
-        self.hi_gbuf = dict(hit=planes(h, w, 8), position=planes(h, w, 4), **(dict(depth=planes(h, w, 1), motion=planes(h, w, 2)) if self.motion_blur else {}))
+        self.hi_gbuf = dict(hit=planes(h, w, 8), position=planes(h, w, 4), **(dict(depth=planes(h, w, 1)) if self.motion_blur or self.dof else {}),
+                            **(dict(motion=planes(h, w, 2)) if self.motion_blur else {}))
         self.albedo, self.upsampled, self.weight, self.final = planes(h, w, 4), planes(h, w, 4), planes(h, w, 1), planes(h, w, 4)
         self.modulated = planes(h, w, 4) if self.edge_aa else None  # step 11's output where step 12 follows it
         self.frame_rgba8 = torch.zeros((h, w), dtype=torch.int32, device="cuda:0")
@@ -112,6 +131,9 @@ class UpsampledLoop:
         # step 15's output and its scratch (tile and neighbourhood maxima)
         self.blurred = planes(h, w, 4) if self.motion_blur else None
         self.tiles = torch.zeros((self.hi.motionBlurLayout()[1] // 8, 2), device="cuda:0") if self.motion_blur else None
+        # step 16's output and its scratch (tile and neighbourhood maxima of the blur radius)
+        self.lens = planes(h, w, 4) if self.dof else None
+        self.discs = torch.zeros((self.hi.dofLayout()[1] // 4,), device="cuda:0") if self.dof else None
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
         self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
@@ -148,13 +170,15 @@ class UpsampledLoop:
         hi.setCamera(cam)
         if self.motion_blur:
             G = hi.renderGBuffer(("hit", "position", "depth", "motion"), prev_cameras=prev, out=self.hi_gbuf)["stats"]
+        elif self.dof:
+            G = hi.renderGBuffer(("hit", "position", "depth"), out=self.hi_gbuf)["stats"]
         else:
             G = hi.renderGBuffer(("hit", "position"), out=self.hi_gbuf)["stats"]
         S = self._albedo(hi, self.hi_gbuf["hit"], self.albedo)
         u = hi.upsamplePlanes(self.filtered, cur["hit"], cur["position"], self.hi_gbuf["hit"], self.hi_gbuf["position"], self.scale, out=self.upsampled,
                               weight_out=self.weight)["stats"]
-        # with auto exposure, bloom or motion blur the tone mapper writes the displayed frame
-        shown = None if self.auto_exposure or self.bloom or self.motion_blur else self.frame_rgba8
+        # with auto exposure, depth of field, bloom or motion blur the tone mapper writes the displayed frame
+        shown = None if self.auto_exposure or self.dof or self.bloom or self.motion_blur else self.frame_rgba8
         if self.edge_aa:
             m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.modulated)["stats"]
             e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=shown)["stats"]
@@ -162,8 +186,15 @@ class UpsampledLoop:
             m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=shown)["stats"]
             e = dict(kernel_ms=0.0, boundary=0, blended=0)
         lit = self.final
+        if self.dof:
+            w, h = self.size
+            self.focus_now = autofocus(self.hi_gbuf["depth"], [(0, 0, w, h)], self.focus, self.focus_now) if self.autofocus else [self.focus]
+            df = hi.dofPlanes(lit, self.hi_gbuf["depth"], out=self.lens, scratch=self.discs, focus=self.focus_now[0], **self.dof_prm)["stats"]
+            lit = self.lens
+        else:
+            df = dict(kernel_ms=0.0, gathered=0)
         if self.bloom:
-            b = hi.bloomPlanes(self.final, state=self.state[i] if self.auto_exposure and k else None, out=self.bloomed, scratch=self.pyramid,
+            b = hi.bloomPlanes(lit, state=self.state[i] if self.auto_exposure and k else None, out=self.bloomed, scratch=self.pyramid,
                                **self.bloom_prm)["stats"]
             lit = self.bloomed
         else:
@@ -180,7 +211,7 @@ class UpsampledLoop:
             self.cur = o
         else:
             x, tm = dict(kernel_ms=0.0, skipped=0, under=0, over=0), dict(kernel_ms=0.0, clipped=0)
-            if self.bloom or self.motion_blur:
+            if self.dof or self.bloom or self.motion_blur:
                 tm = hi.tonemapPlanes(lit, frame=self.frame_rgba8, op="linear", write_out=False)["stats"]
         t2 = time.perf_counter()
         ev = float(self.state[self.cur][0, 0]) if self.auto_exposure else 0.0  # read back for the caller's printing, outside the timed frame
@@ -191,7 +222,8 @@ class UpsampledLoop:
                     pixels=u["pixels"], full=u["full"], rescued=u["rescued"], orphans=u["orphans"], edge_aa_ms=e["kernel_ms"], boundary=e["boundary"],
                     blended=e["blended"], exposure_ms=x["kernel_ms"], tonemap_ms=tm["kernel_ms"], ev=ev, skipped=x["skipped"], under=x["under"],
                     over=x["over"], clipped=tm["clipped"], bloom_ms=b["kernel_ms"], bright=b["bright"],
-                    motion_blur_ms=mb["kernel_ms"], moving=mb["moving"])
+                    motion_blur_ms=mb["kernel_ms"], moving=mb["moving"], dof_ms=df["kernel_ms"], gathered=df["gathered"],
+                    focus=self.focus_now[0] if self.dof else 0.0)
 
     def close(self):
         self.lo.close()
@@ -216,13 +248,19 @@ def main(argv=None):
     ap.add_argument("--motion-blur", action="store_true", help="motion blur (motionBlurPlanes) behind edge AA / bloom and in front of the tone map")
     ap.add_argument("--shutter", type=float, default=0.5, metavar="F", help="with --motion-blur: the open fraction of the frame interval, in [0, 4]")
     ap.add_argument("--blur-taps", type=int, default=12, metavar="N", help="with --motion-blur: taps per pixel (1..64)")
+    ap.add_argument("--dof", action="store_true", help="depth of field (dofPlanes) behind edge AA and in front of bloom, motion blur and the tone map")
+    ap.add_argument("--focus", type=float, default=4.0, metavar="F", help="with --dof: the depth that is sharp (with --autofocus: where the centre is a miss)")
+    ap.add_argument("--autofocus", action="store_true", help="with --dof: focus on the depth under the frame's centre, smoothed over frames")
+    ap.add_argument("--aperture", type=float, default=6.0, metavar="K", help="with --dof: the blur-circle radius in pixels of a point at infinity")
+    ap.add_argument("--dof-taps", type=int, default=32, metavar="N", help="with --dof: taps per pixel (1..64)")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
     make, cam0 = SCENES[args.scene]
     loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp, edge_aa=args.edge_aa,
                          auto_exposure=args.auto_exposure, tonemap=args.tonemap, bloom=args.bloom, bloom_threshold=args.bloom_threshold,
-                         bloom_levels=args.bloom_levels, motion_blur=args.motion_blur, shutter=args.shutter, blur_taps=args.blur_taps)
+                         bloom_levels=args.bloom_levels, motion_blur=args.motion_blur, shutter=args.shutter, blur_taps=args.blur_taps,
+                         dof=args.dof, focus=args.focus, autofocus=args.autofocus, aperture=args.aperture, dof_taps=args.dof_taps)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -233,6 +271,7 @@ def main(argv=None):
               f"{x['gbuffer_ms']:.3f} ms, surface {x['surface_ms']:.3f} ms, upsample {x['upsample_ms']:.3f} ms, modulate {x['modulate_ms']:.3f} ms; "
               f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; "
               + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
+              + (f"depth of field {x['dof_ms']:.3f} ms ({x['gathered']} pixels gather, focus {x['focus']:.3f}); " if loop.dof else "")
               + (f"bloom {x['bloom_ms']:.3f} ms ({x['bright']} bright pixels); " if loop.bloom else "")
               + (f"motion blur {x['motion_blur_ms']:.3f} ms ({x['moving']} pixels gather); " if loop.motion_blur else "")
               + (f"exposure {x['exposure_ms']:.3f} ms (ev {x['ev']:+.3f}, {x['skipped']} misses skipped, {x['under']} under, {x['over']} over), "
@@ -242,6 +281,8 @@ def main(argv=None):
     np.save(os.path.join(args.out_dir, "upsampled_svgf_frame.npy"), loop.frame_rgba8.cpu().numpy().view(np.uint32))
     if loop.motion_blur:
         np.save(os.path.join(args.out_dir, "upsampled_svgf_blurred.npy"), loop.blurred.cpu().numpy())
+    if loop.dof:
+        np.save(os.path.join(args.out_dir, "upsampled_svgf_dof.npy"), loop.lens.cpu().numpy())
     print(f"wrote upsampled_svgf_final.npy and upsampled_svgf_frame.npy to {args.out_dir}")
     loop.close()
     return 0

@@ -33,7 +33,8 @@
  * stands with its other GPU tests, in tests/test_gpu_edge_aa.py).  So do pt_exposure_planes and pt_tonemap_planes (their ordering
  * cases: tests/test_gpu_exposure.py).  pt_bloom_planes takes DEVICE pointers under the same contract, too (its ordering cases:
  * tests/test_gpu_bloom.py); pt_bloom_layout touches no device memory.  pt_motion_blur_planes takes DEVICE pointers under the same contract
- * (its ordering cases: tests/test_gpu_motion_blur.py); pt_motion_blur_layout touches no device memory.
+ * (its ordering cases: tests/test_gpu_motion_blur.py); pt_motion_blur_layout touches no device memory.  pt_dof_planes takes DEVICE pointers
+ * under the same contract (its ordering cases: tests/test_gpu_dof.py); pt_dof_layout touches no device memory.
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -46,7 +47,7 @@
  * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes, pt_edge_aa_planes,
  * pt_exposure_planes, pt_tonemap_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.  pt_bloom_layout and pt_bloom_planes were added
- * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes.
+ * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes, and pt_dof_layout and pt_dof_planes.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -1768,6 +1769,110 @@ typedef struct pt_motion_blur_desc {
 } pt_motion_blur_desc;
 typedef struct pt_motion_blur_stats { uint64_t pixels, sources, unknown, moving, taps, nonfinite; double kernel_ms; } pt_motion_blur_stats;
 int pt_motion_blur_planes(pt_ctx* ctx, const pt_motion_blur_desc* desc, pt_motion_blur_stats* stats /* may be NULL */);
+
+/* DEPTH OF FIELD (no reference counterpart).  The frame path's camera is a pinhole (it is pinned to the reference's device programs), so
+ * every frame of the chain is sharp from the near plane to the sky.  pt_dof_planes gives the chain a thin lens as a post pass: each pixel of
+ * a linear colour plane gathers a disc of up to 64 taps whose radius is the largest blur circle around it, with a foreground/background rule
+ * that decides who may bleed over whom.  It is motion blur's family — tile maximum, neighbourhood maximum, then a variable gather — with a
+ * 2-D disc for the line.  It runs behind pt_edge_aa_planes and in front of pt_bloom_planes, pt_motion_blur_planes and pt_tonemap_planes, so
+ * that bright out-of-focus points bloom as discs.  Stateless like every pass here: the planes and the scratch are caller-owned DEVICE memory
+ * of the context's device (4-byte aligned; the planes frame-sized, indexed Y * width + X); block_mask and view_focus are HOST memory.
+ * Float32 throughout, one rounding per operation, no fused multiply-add, sqrtf and / correctly rounded (pt_detmath.h's contract), in the
+ * stated order; max(a, b) is a > b ? a : b, min(a, b) is a < b ? a : b, and clamp01(x) is x = x > 0 ? x : 0; x = x < 1 ? x : 1 (a NaN
+ * becomes 0).
+ *
+ * The lens.  depth is pt_render_gbuffer's: distance along the viewing axis, which is the thin lens's z.  A point at depth z seen through a
+ * lens of aperture diameter A and focal length f focused at distance s has a blur circle of diameter A * f / (s - f) * |1 - s / z| on the
+ * sensor.  `aperture` folds the lens into one number, the blur-circle RADIUS in pixels of a point at infinity:
+ *     K = 0.5 * A * f / (s - f) * px_per_unit        (px_per_unit: pixels per unit of length on the sensor, frame height / sensor height)
+ * and `focus` is s in depth units.  Autofocus is the caller's: read depth under a view's centre and smooth it over frames.
+ *
+ * Rectangles and tiles are exactly motion blur's.  Each view's rectangle (x0, y0, wr, hr) has a tile grid of its own, anchored at the
+ * rectangle's origin; without views there is one rectangle, the whole frame; nv = max(1, the view count).  The grid is tw = (wr + 15) / 16
+ * by th = (hr + 15) / 16 tiles of PT_DOF_TILE = 16 pixels a side, partial at the right and at the bottom.  No tap and no tile neighbour ever
+ * leaves its rectangle, and a view holds the bits a context of its own size would hold.
+ * pt_dof_layout gives the scratch: view after view, a plane T of tw * th floats of 4 bytes in row order, then a plane N of the same size;
+ * *bytes is their sum.  dims (HOST, nv x 4, may be NULL) receives tw, th, the index of T's first 4-byte texel and the index of N's.  It
+ * refuses (PT_ERR_INVALID) a null ctx or bytes and a context without pt_resize.
+ *
+ * What is read, what is written.  The tile pass reads EVERY pixel of every rectangle from depth, whether or not the rank owns it or the mask
+ * names it, and a tap of the gather reads depth and color wherever in the rectangle it lands; the set decides only which pixels of out are
+ * written.  The set is exactly pt_modulate_planes's: owned pixels, view pixels while views are set, whole blocks of the mask.  The ranks of
+ * a partitioned frame all-gather colour and depth first.  stats->sources is the number of rectangle pixels read by the tile pass,
+ * stats->pixels the size of the set.  The whole scratch is written by every call, also with an empty set.
+ *
+ * The host computes K = aperture + 0.0f (a -0 becomes +0), R = max_radius, PI = 3.14159274f, and per view Fv = view_focus ? view_focus[v]
+ * : focus.
+ *   1. Blur radius r(q) of a rectangle pixel q: z = Z(depth[q]) with motion blur's Z(d) = (d > 1e-6f && d <= FLT_MAX) ? d : FLT_MAX — a NaN,
+ *      an inf, 0 and negatives all become FLT_MAX: a miss (+inf) is far; r = K * fabsf(1.0f - Fv / z); r = r < R ? r : R.  Fv <= 1e30 and
+ *      z > 1e-6, so Fv / z cannot overflow: r is never NaN and r >= 0 (K times a finite number, possibly +inf, then the minimum).
+ *   2. Tile maximum.  T(i, j) = max r over the pixels of tile (i, j) that lie inside the rectangle: a maximum of non-negative, non-NaN
+ *      floats, so it is independent of the order of the reduction.
+ *   3. Neighbourhood maximum.  N(i, j) = max T over the 3 x 3 tiles around (i, j) that exist in the rectangle's grid.  Because
+ *      R <= PT_DOF_TILE nothing farther away can reach the tile.
+ *   4. Gather, for a pixel p of the set with (x, y) its coordinates in its rectangle: c = color[p].xyz; rN = N(x / 16, y / 16).
+ *      If rN > 0.5f is false, or a word of c is not finite (exponent-bit test): out[p] = (c, 1.0f), raw, and that is all.
+ *      Otherwise stats->gathered counts p, and
+ *        rp = r(p); zp = Z(depth[p]); area(r) = max((r * r) * PI, 1.0f); wp = 1.0f / area(rp);
+ *        At = ((rN * rN) * PI) / (float)taps — the disc area one tap stands for;
+ *        sum = (0, 0, 0); Wt = 0; then for tap i = 0 .. taps - 1, in this order:
+ *          rho = sqrtf(((float)i + 0.5f) / (float)taps); d = rN * rho;
+ *          qx = (int)floorf(((float)x + d * D[i + k0].x) + 0.5f), clamped to [0, wr - 1]; qy = (int)floorf(((float)y + d * D[i + k0].y) +
+ *          0.5f), clamped to [0, hr - 1]; q is that pixel of the rectangle.
+ *          rq = r(q); zq = Z(depth[q]);
+ *          re = zq > zp ? rp : rq — a tap behind p is seen through p's own blur, a tap in front of p spreads by its own;
+ *          cov = clamp01((re - d) + 0.5f); w = (cov * At) / area(re).
+ *          If w > 0 is false the tap is done: its colour is never looked at.
+ *          Otherwise, if a word of color[q].xyz is not finite the tap is skipped and stats->nonfinite counts it.
+ *          Otherwise sum = sum + color[q].xyz * w per component; Wt = Wt + w; stats->taps counts it.
+ *      If Wt == 0: out[p].xyz = c exactly.  Else out[p].xyz = (c * wp + sum) / (wp + Wt) per component.  out[p].w = 1.0f.
+ *      The directions D[0 .. 127] are a Vogel spiral by recurrence, so that nobody's cosf enters the bits: D[0] = (1, 0) and
+ *          D[n + 1] = (D[n].x * C - D[n].y * S, D[n].x * S + D[n].y * C),
+ *      each component two products and one sum (a difference for x), rounded separately, in this order, with C = -0x1.79886ap-1f (bits
+ *      0xBF3CC435, -0.73736888) and S = 0x1.59d9dep-1f (bits 0x3F2CECEF, 0.67549032) the floats nearest to the cosine and the sine of the
+ *      golden angle pi (3 - sqrt 5).  Over 128 steps the norm drifts by less than 3e-6.
+ *      The jitter k0 is 0 without PT_DOF_JITTER.  With it, k0 = h & 63 — the whole pattern turned by k0 golden angles — where h is motion
+ *      blur's hash of the LOCAL coordinates and the seed, exact in uint32 arithmetic:
+ *          h = ((uint32_t)x * 0x9E3779B1u) ^ ((uint32_t)y * 0x85EBCA77u) ^ (seed * 0xC2B2AE3Du);
+ *          h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16.
+ * aperture = 0, and a depth plane equal to the focus everywhere, give out = (color.xyz, 1) bit for bit, with T and N all +0.  Every r, T
+ * and N lies in [0, R], and N >= T for the tile itself.  Every weight is >= 0, so a finite out[p] lies within the range of the finite
+ * colours up to the roundings of its sums.  A pixel in focus (rp = 0) in front of a blurred background keeps its bits once the first tap is
+ * half a pixel away, rN * sqrtf(0.5f / taps) >= 0.5: every tap then has cov = 0 or lands on a pixel with r = 0 at d >= 0.5.  A blurred
+ * foreground reaches at most ceil(rq + 0.5) pixels outside its edge.  A hostile word in depth, or a non-finite colour, reaches no pixel but
+ * the one that holds the bad colour.
+ *
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx, desc, color, depth, out or scratch;
+ * no pt_resize yet; a plane that fails the pointer checks; any overlap that involves out or scratch (out may NOT be color: the gather reads
+ * neighbours); flag bits other than PT_DOF_JITTER; focus, or any view_focus[v], not finite or outside (0, 1e30]; aperture not finite or
+ * outside [0, 4096]; max_radius not finite or outside [1, PT_DOF_TILE]; taps outside 1 .. 64.
+ * Ordering and state, as pt_motion_blur_planes: the call waits for the frames in flight, runs on pt_stream(ctx) under the STREAM CONTRACT,
+ * is complete when it returns, and writes no context state.
+ * Not part of this interface: hexagonal or cat-eye bokeh; a separate near-field layer and background reconstruction behind blurred
+ * foregrounds; sub-pixel (bilinear) taps; a half-resolution pre-filter; per-view apertures; motion blur that knows the blur circle; an
+ * asynchronous variant; a pt_multi_* wrapper (per-rank calls work once colour and depth are gathered). */
+#define PT_DOF_TILE 16
+typedef enum pt_dof_flags { PT_DOF_JITTER = 1 } pt_dof_flags;
+/* scratch in caller memory: bytes for T and N of every view (or of the frame without views);
+ * dims (HOST, nv x 4: tw, th, first 4-byte texel of T, first 4-byte texel of N; may be NULL) */
+int pt_dof_layout(const pt_ctx* ctx, uint32_t* dims, size_t* bytes);
+
+typedef struct pt_dof_desc {
+    const float* color;        /* w*h x 4 linear radiance (.w ignored); required */
+    const float* depth;        /* w*h, the G-buffer's depth (a miss holds +inf); required */
+    float*       out;          /* w*h x 4; required; exclusive (it may NOT be color) */
+    void*        scratch;      /* pt_dof_layout's bytes, 4-byte aligned; required, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    const float* view_focus;   /* HOST, nv floats: a focus distance per view; NULL: `focus` for all */
+    float focus;               /* finite, in (0, 1e30]: the distance (depth units) that is sharp */
+    float aperture;            /* finite, in [0, 4096]: K, the blur-circle RADIUS in pixels of a point at infinity */
+    float max_radius;          /* finite, in [1, PT_DOF_TILE]: R, in pixels */
+    uint32_t taps;             /* 1..64 */
+    uint32_t seed;             /* of the jitter's hash */
+    uint32_t flags;            /* pt_dof_flags */
+} pt_dof_desc;
+typedef struct pt_dof_stats { uint64_t pixels, sources, gathered, taps, nonfinite; double kernel_ms; } pt_dof_stats;
+int pt_dof_planes(pt_ctx* ctx, const pt_dof_desc* desc, pt_dof_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -31,6 +31,7 @@ EXPORTS = [
     "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes", "pt_surface_aniso_planes",
     "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes", "pt_bloom_layout", "pt_bloom_planes",
     "pt_motion_blur_layout", "pt_motion_blur_planes",
+    "pt_dof_layout", "pt_dof_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -310,6 +311,29 @@ class MotionBlurStats(C.Structure):  # pt_motion_blur_stats
 # the frame-sized planes of pt_motion_blur_planes: 32-bit words per pixel (the scratch, T and N of every view, is pt_motion_blur_layout's)
 MOTION_BLUR_PLANES = {"color": 4, "motion": 2, "depth": 1, "out": 4}
 MOTION_BLUR_OUTPUTS = ("out",)
+
+
+PT_DOF_TILE = 16
+PT_DOF_JITTER = 1  # pt_dof_flags
+
+
+class DofDesc(C.Structure):  # pt_dof_desc
+    _fields_ = [("color", C.c_void_p), ("depth", C.c_void_p), ("out", C.c_void_p), ("scratch", C.c_void_p), ("block_mask", C.c_void_p),
+                ("view_focus", C.c_void_p), ("focus", C.c_float), ("aperture", C.c_float), ("max_radius", C.c_float), ("taps", C.c_uint32),
+                ("seed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class DofStats(C.Structure):  # pt_dof_stats
+    _fields_ = [("pixels", C.c_uint64), ("sources", C.c_uint64), ("gathered", C.c_uint64), ("taps", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the frame-sized planes of pt_dof_planes: 32-bit words per pixel (the scratch, T and N of every view, is pt_dof_layout's)
+DOF_PLANES = {"color": 4, "depth": 1, "out": 4}
+DOF_OUTPUTS = ("out",)
 
 
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
@@ -614,6 +638,8 @@ def load_library() -> C.CDLL:
     L.pt_bloom_planes.argtypes = [vp, C.POINTER(BloomDesc), C.POINTER(BloomStats)]
     L.pt_motion_blur_layout.argtypes = [vp, vp, C.POINTER(C.c_size_t)]
     L.pt_motion_blur_planes.argtypes = [vp, C.POINTER(MotionBlurDesc), C.POINTER(MotionBlurStats)]
+    L.pt_dof_layout.argtypes = [vp, vp, C.POINTER(C.c_size_t)]
+    L.pt_dof_planes.argtypes = [vp, C.POINTER(DofDesc), C.POINTER(DofStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

@@ -461,6 +461,28 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // dofPlanes's `aperture` of a thin lens: K = 0.5 * A * f / (s - f) * px_per_unit, the blur-circle radius in pixels of a point at
+    // infinity, with A = focal_length / f_number, s = focus (> focal_length, the same units) and px_per_unit = frame_height / sensor_height.
+    static float dofAperture(float focal_length, float f_number, float focus, float sensor_height, float frame_height) {
+        return 0.5f * (focal_length / f_number) * focal_length / (focus - focal_length) * (frame_height / sensor_height);
+    }
+    // The size in bytes of dofPlanes's scratch, T and N of every view (pt_dof_layout); dims (host memory, views x 4: tw, th, the first
+    // 4-byte texel of T, the first of N) may be null.
+    size_t dofLayout(uint32_t* dims = nullptr) {
+        size_t bytes = 0;
+        ck(pt_dof_layout(ctx, dims, &bytes));
+        return bytes;
+    }
+    // Depth of field behind edge antialiasing and in front of bloom, motion blur and the tone mapper (pt_dof_planes): d.color gathered over
+    // a disc of the largest blur circle (from d.depth, d.focus and d.aperture) of the tiles around each pixel, into d.out, which may not be
+    // d.color; d.scratch is dofLayout's bytes.  Returns the pixels written, the rectangle pixels read, the pixels that gathered, the taps
+    // that counted and the non-finite ones skipped, and the device time.
+    pt_dof_stats dofPlanes(const pt_dof_desc& d, pt_dof_stats* stats = nullptr) {
+        pt_dof_stats s{};
+        ck(pt_dof_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

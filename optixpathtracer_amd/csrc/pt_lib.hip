@@ -38,3 +38,4 @@
 #include "pt_exposure.hip"
 #include "pt_bloom.hip"
 #include "pt_motion_blur.hip"
+#include "pt_dof.hip"

@@ -1059,6 +1059,85 @@ class SampleRenderer:
         desc.taps, desc.seed, desc.flags = taps, seed, _lib.PT_MOTION_BLUR_JITTER if jitter else 0
         return self._run_pass("pt_motion_blur_planes", desc, _lib.MotionBlurStats(), result)
 
+    @staticmethod
+    def dofAperture(focal_length, f_number, focus, sensor_height, frame_height):
+        """dofPlanes's `aperture` of a thin lens: K = 0.5 * A * f / (s - f) * px_per_unit, the blur-circle radius in pixels of a point at
+        infinity, with A = focal_length / f_number the aperture's diameter, f = focal_length, s = focus (all three in the depth plane's
+        units, s > f) and px_per_unit = frame_height / sensor_height (sensor_height in the same units)."""
+        f, n, s, sensor, h = float(focal_length), float(f_number), float(focus), float(sensor_height), float(frame_height)
+        if not (f > 0.0 and n > 0.0 and sensor > 0.0 and h > 0.0 and s > f):
+            raise ValueError("dofAperture: focal_length, f_number, sensor_height and frame_height must be > 0 and focus > focal_length")
+        return 0.5 * (f / n) * f / (s - f) * (h / sensor)
+
+    def dofLayout(self):
+        """The shape of dofPlanes's scratch (pt_dof_layout): (dims, bytes) with dims a uint32 (views, 4) array of tw, th, the index of T's
+        first 4-byte texel and the index of N's, views = max(1, the view count), and bytes the size of the scratch."""
+        count, nbytes = C.c_uint32(0), C.c_size_t()
+        self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
+        dims = np.zeros((max(1, count.value), 4), np.uint32)
+        self._ck(self._L.pt_dof_layout(self._ctx, dims.ctypes.data, C.byref(nbytes)), "pt_dof_layout")
+        return dims, nbytes.value
+
+    def dofPlanes(self, color, depth, out=None, scratch=None, mask=None, focus=None, aperture=None, max_radius=16.0, taps=32, seed=0,
+                  jitter=False, view_focus=None) -> dict:
+        """Depth of field behind edgeAaPlanes and in front of bloomPlanes, motionBlurPlanes and tonemapPlanes (pt_dof_planes,
+        include/pt_amd.h: the rule, in full): each pixel of `color` gathers `taps` pixels of a disc whose radius is the largest blur
+        circle of the 16 x 16 tiles around it, at most `max_radius` pixels.  A pixel at depth z has the blur radius
+        aperture * |1 - focus / z|: `focus` is the depth that is sharp, `aperture` the radius in pixels of a point at infinity
+        (dofAperture computes it from a lens).  A tap behind the pixel is seen through the pixel's own blur, a tap in front spreads by
+        its own.
+
+        color (h, w, 4) and depth ((h, w): renderGBuffer's) are CUDA float32 tensors on the context's device — dense, any
+        4-byte-aligned storage offset — or raw device pointers.  out (h, w, 4) is allocated with torch, zero-filled, when None; it may
+        NOT be `color` (the pass reads neighbours).  scratch: a float32 (texels,) tensor with 4 * texels = dofLayout()'s bytes, or a raw
+        pointer; allocated when None.  After the call it holds the tile maxima T and the neighbourhood maxima N of every view.  The tile
+        pass reads every pixel of every view whatever the mask and the rank's partition: they decide only which pixels of out are
+        written (a partitioned frame gathers its two planes first).  view_focus: a focus distance per view (max(1, the view count)
+        floats), None: `focus` for all.  jitter: each pixel's pattern is turned by a hash of its coordinates and `seed`.
+        Returns {"out", "scratch": the tensor (None for a raw pointer), "stats": {pixels, sources, gathered, taps, nonfinite,
+        kernel_ms}}."""
+        import torch
+
+        if focus is None or aperture is None:
+            raise ValueError("dofPlanes: focus and aperture are required")
+        taps, seed = int(taps), int(seed)
+        if not 1 <= taps <= 64:
+            raise ValueError(f"dofPlanes: taps must be 1..64, not {taps}")
+        if not 0 <= seed < 2**32:
+            raise ValueError("dofPlanes: seed must be in [0,4294967295]")
+        if not 0.0 < float(focus) <= 1e30:
+            raise ValueError("dofPlanes: focus must be in (0,1e30]")
+        if not 0.0 <= float(aperture) <= 4096.0:
+            raise ValueError("dofPlanes: aperture must be in [0,4096]")
+        if not 1.0 <= float(max_radius) <= _lib.PT_DOF_TILE:
+            raise ValueError(f"dofPlanes: max_radius must be in [1,{_lib.PT_DOF_TILE}]")
+        desc = _lib.DofDesc()
+        result = self._bind_planes("dofPlanes", desc, dict(color=color, depth=depth, out=out), _lib.DOF_PLANES, ("color", "depth"),
+                                   _lib.DOF_OUTPUTS, alloc=("out",))
+        dev = getattr(self, "_device", 0)
+        if isinstance(scratch, int):
+            desc.scratch, result["scratch"] = scratch, None
+        else:
+            dims, nbytes = self.dofLayout()
+            if scratch is None:
+                scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=f"cuda:{dev}")
+            _check_temporal_tensor("scratch", scratch, dev, {torch.float32: (nbytes // 4,)}, "dofPlanes")
+            desc.scratch, result["scratch"] = scratch.data_ptr(), scratch
+        vf = None
+        if view_focus is not None:
+            count = C.c_uint32(0)
+            self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
+            vf = np.ascontiguousarray(view_focus, np.float32).reshape(-1)
+            if vf.size != max(1, count.value):
+                raise ValueError(f"dofPlanes: view_focus has {vf.size} values, expected {max(1, count.value)}")
+            if not ((vf > 0) & (vf <= np.float32(1e30))).all():
+                raise ValueError("dofPlanes: view_focus must be in (0,1e30]")
+            desc.view_focus = vf.ctypes.data  # (vf is kept until the call has returned)
+        m = self._bind_mask("dofPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.focus, desc.aperture, desc.max_radius = float(focus), float(aperture), float(max_radius)
+        desc.taps, desc.seed, desc.flags = taps, seed, _lib.PT_DOF_JITTER if jitter else 0
+        return self._run_pass("pt_dof_planes", desc, _lib.DofStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
