@@ -16,13 +16,12 @@ static uint32_t bloom_tail_texels() {
 // The rectangles (each view's, or the frame) and their levels: tab is [nv][BLOOM_STRIDE], entries past `levels` zero.  Returns the
 // pyramid's size in float4.
 static uint64_t bloom_table(const pt_ctx* ctx, uint32_t levels, std::vector<BloomLevel>& tab) {
-    const uint32_t nv = pass_camera_count(ctx);
-    tab.assign((size_t)nv * BLOOM_STRIDE, BloomLevel{0u, 0u, 0u, 0u});
+    const std::vector<PassRect> rects = pass_rects(ctx);
+    tab.assign(rects.size() * BLOOM_STRIDE, BloomLevel{0u, 0u, 0u, 0u});
     uint64_t at = 0;
-    for (uint32_t v = 0; v < nv; ++v) {
-        BloomLevel* t = tab.data() + (size_t)v * BLOOM_STRIDE;
-        if (ctx->vw.n) t[0] = BloomLevel{(uint32_t)ctx->vw.host[v].width, (uint32_t)ctx->vw.host[v].height, 0u, (uint32_t)ctx->vw.host[v].x | ((uint32_t)ctx->vw.host[v].y << 16)};
-        else t[0] = BloomLevel{(uint32_t)ctx->width, (uint32_t)ctx->height, 0u, 0u};
+    for (size_t v = 0; v < rects.size(); ++v) {
+        BloomLevel* t = tab.data() + v * BLOOM_STRIDE;
+        t[0] = BloomLevel{rects[v].w, rects[v].h, 0u, pass_rect_org(rects[v])};
         for (uint32_t k = 1; k <= levels; ++k) {
             t[k] = BloomLevel{(t[k - 1].w + 1u) / 2u, (t[k - 1].h + 1u) / 2u, (uint32_t)at, 0u};
             at += (uint64_t)t[k].w * t[k].h;

@@ -1,24 +1,14 @@
 // pt_dof_layout and pt_dof_planes (include/pt_amd.h): a thin lens behind the pinhole frame path, as a post pass over colour and depth.
 // Motion blur's family with a disc for the line.  Three kernels: k_dof_tile reduces every 16 x 16 tile of every rectangle to its largest
-// blur radius (T), k_dof_neighbour takes the largest T of the 3 x 3 tiles around each tile (N), k_dof_gather<VIEWS> runs over the call's
-// pixel list and gathers `taps` pixels of a disc of radius N.  T and N are planes of floats in the caller's scratch; the view table
-// (DofView, one per rectangle) and the tap table (DofTaps) are temporaries of the call in device memory.  One launch covers all views:
-// blockIdx.y is the view, and a block past the end of its view's grid leaves at once.  Everything works in a rectangle's own coordinates,
-// which is what keeps a tap and a tile neighbour from leaving it.
+// blur radius (T), k_tile_neighbour<float> takes the largest T of the 3 x 3 tiles around each tile (N), k_dof_gather<VIEWS> runs over the
+// call's pixel list and gathers `taps` pixels of a disc of radius N.  T and N are planes of floats in the caller's scratch; the view table
+// (TileView, one per rectangle, aux = the view's focus distance) and the tap table (DofTaps) are temporaries of the call in device memory.
 //
-// DofView is MblurView (pt_motion_blur.h) with 4-byte texels and the view's focus distance in the spare word; it is a copy of those few
-// lines, not a shared header: a pass header includes no other pass's, and sharing would have meant renaming motion blur's own.
+// The view table, a tile kernel's pixels, the neighbour kernel, the tap's address, the counters' way out, Z(depth), the hash and the
+// clamp are the tiled passes' scaffold in pt_pass_dev.h, shared with motion blur.  What stands here is depth of field's own: the radius
+// rule, the tile's reduction, the disc's taps and their weights.
 #pragma once
-#include <cfloat>
-
 #include "pt_pass_dev.h"
-
-struct DofView {
-    uint32_t w, h, org;  // the rectangle; org = x0 | y0 << 16 in the frame
-    uint32_t tw, th;     // its tile grid
-    uint32_t offT, offN; // the first float of T and of N in the scratch
-    float focus;         // Fv
-};
 
 // The host's table of a call: the spiral's directions D[0 .. 127] by the header's recurrence, and rho[i] = sqrtf((i + 0.5f) / taps).  Both
 // are the header's operations, done once on the host (built with -ffp-contract=off like the device code) instead of per lane and tap.
@@ -33,7 +23,6 @@ struct DofParams {
 
 #define DOF_PI 3.14159274f
 
-PT_DEV float dof_depth(float d) { return (d > 1e-6f && d <= FLT_MAX) ? d : FLT_MAX; }
 // Step 1 of the header, from Z(depth)
 PT_DEV float dof_radius(float z, float focus, const DofParams& k) {
     const float r = k.K * fabsf(1.0f - focus / z);
@@ -43,28 +32,15 @@ PT_DEV float dof_area(float r) {
     const float a = (r * r) * DOF_PI;
     return a > 1.0f ? a : 1.0f;
 }
-PT_DEV float dof_clamp01(float x) {
-    x = x > 0.0f ? x : 0.0f;
-    return x < 1.0f ? x : 1.0f;
-}
-PT_DEV uint32_t dof_hash(uint32_t x, uint32_t y, uint32_t seed) {
-    uint32_t h = (x * 0x9E3779B1u) ^ (y * 0x85EBCA77u) ^ (seed * 0xC2B2AE3Du);
-    h ^= h >> 16;
-    h *= 0x7FEB352Du;
-    h ^= h >> 15;
-    h *= 0x846CA68Bu;
-    h ^= h >> 16;
-    return h;
-}
 
 // ------------------------------------------------------------------ k_dof_tile: T, the largest blur radius of each tile
-// k_mblur_tile's shape as it was measured: one WAVE per tile, four tiles to a workgroup of 256 threads; lane l takes the four pixels
-// (l & 3) * 4 .. + 3 of the tile's row l >> 2, four 4-byte loads that are all in flight before the first is used.  r >= 0 is never NaN, so
-// the maximum does not depend on the order of the reduction and needs no key: a pixel outside the rectangle (a partial tile) contributes
-// 0, six shuffle steps take the maximum across the wave, and lane 0 writes it (pixel 0 of a tile is always inside).  No LDS, no barrier.
-// sources is added up in a scalar register from ballots and leaves through pass_slot with one atomic per wave.
+// k_mblur_tile's shape as it was measured: one WAVE per tile, four tiles to a workgroup of 256 threads; a lane's four pixels (tile_pixel)
+// are four 4-byte loads that are all in flight before the first is used.  r >= 0 is never NaN, so the maximum does not depend on the order
+// of the reduction and needs no key: a pixel outside the rectangle (a partial tile) contributes 0, six shuffle steps take the maximum
+// across the wave, and lane 0 writes it (pixel 0 of a tile is always inside).  No LDS, no barrier.  sources is added up in a scalar
+// register from ballots and leaves through pass_slot with one atomic per wave.
 struct DofTileArgs {
-    const DofView* tab;
+    const TileView* tab;
     int width; // of the frame: the planes are indexed Y * width + X
     const float* depth;
     float* scratch;
@@ -75,26 +51,22 @@ struct DofTileArgs {
 
 __global__ void __launch_bounds__(256) k_dof_tile(DofTileArgs a) {
 #if __HIP_DEVICE_COMPILE__
-    const DofView L = a.tab[blockIdx.y];
+    const TileView L = a.tab[blockIdx.y];
     const uint32_t tile = blockIdx.x * DOF_TILES_PER_BLOCK + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (tile >= L.tw * L.th) return; // the whole wave; the kernel has no barrier
-    const uint32_t ti = tile % L.tw, tj = tile / L.tw;
-    const uint32_t lx = (lane & 3u) * 4u, ly = lane >> 2;
-    const uint32_t y = tj * 16u + ly;
     float d[4];
     bool in[4];
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
-        const uint32_t x = ti * 16u + lx + k;
-        in[k] = x < L.w && y < L.h;
-        const uint32_t sx = in[k] ? x : 0u, sy = in[k] ? y : 0u; // (outside: the rectangle's pixel (0, 0), loaded and dropped)
-        d[k] = a.depth[(size_t)((L.org >> 16) + sy) * (size_t)a.width + (size_t)((L.org & 0xffffu) + sx)];
+        const TilePixel t = tile_pixel(L, a.width, tile, lane, k);
+        in[k] = t.in;
+        d[k] = a.depth[t.p];
     }
     float best = 0.0f;
     uint32_t nin = 0u; // wave-uniform
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
-        const float r = in[k] ? dof_radius(dof_depth(d[k]), L.focus, a.k) : 0.0f;
+        const float r = in[k] ? dof_radius(pass_depth(d[k]), L.aux, a.k) : 0.0f;
         best = r > best ? r : best;
         nin += (uint32_t)__popcll(__ballot(in[k]));
     }
@@ -110,60 +82,26 @@ __global__ void __launch_bounds__(256) k_dof_tile(DofTileArgs a) {
 #endif
 }
 
-// ------------------------------------------------------------------ k_dof_neighbour: N, the largest T of the 3 x 3 tiles around a tile
-// One thread per tile, up to nine 4-byte loads.  Tiny and launch-bound; a kernel of its own for k_mblur_neighbour's reason: folded into the
-// gather every wave would redo the nine loads for a value that 256 pixels share, and N has to reach the scratch either way.
-struct DofNeighbourArgs {
-    const DofView* tab;
-    float* scratch;
-};
-
-__global__ void __launch_bounds__(256) k_dof_neighbour(DofNeighbourArgs a) {
-#if __HIP_DEVICE_COMPILE__
-    const DofView L = a.tab[blockIdx.y];
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= L.tw * L.th) return;
-    const int ti = (int)(i % L.tw), tj = (int)(i / L.tw);
-    float best = 0.0f;
-#pragma unroll
-    for (int dj = -1; dj <= 1; ++dj)
-#pragma unroll
-        for (int di = -1; di <= 1; ++di) {
-            const int u = ti + di, v = tj + dj;
-            if (u < 0 || u >= (int)L.tw || v < 0 || v >= (int)L.th) continue;
-            const float t = a.scratch[(size_t)L.offT + (size_t)v * L.tw + (size_t)u];
-            best = t > best ? t : best;
-        }
-    a.scratch[(size_t)L.offN + i] = best;
-#endif
-}
-
 // ------------------------------------------------------------------ k_dof_gather: step 4, over the call's pixel list
 // k_mblur_gather's shape: one thread per entry of the pixel list.  rN is uniform over a tile, so where the list hands a wave one 8 x 8
 // block the early exit, d and (without jitter) the tap's offset are the same in every lane.  A tap loads the depth (4 bytes) first; the
 // colour (16 bytes) is loaded only where the weight is positive, which the rule allows: a tap outside its own blur circle never looks at
 // its colour.  (Issuing both loads together in front of the first use gives the same bits and, measured, the same time within the spread
-// of the runs: profiles/dof.md.  The branch stays: it saves the 16 bytes wherever a tap does not count.)  The three counters are added up
-// across the wave by shuffles and leave with one atomic per wave and non-zero counter; every lane reaches them.
+// of the runs: profiles/dof.md.  The branch stays: it saves the 16 bytes wherever a tap does not count.)  The three counters leave through
+// pass_tally_sums; every lane reaches it.
 struct DofGatherArgs {
     const uint32_t* pixels;
     uint32_t n;
     int width, height;
     const float *color, *depth;
     float* out;
-    const DofView* tab;
+    const TileView* tab;
     const DofTaps* tt;
     const float* scratch;
     DofParams k;
     uint32_t taps, seed, jitter;
     unsigned long long* counts;
 };
-
-PT_DEV uint32_t dof_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 template <bool VIEWS>
 __global__ void __launch_bounds__(256) k_dof_gather(DofGatherArgs a, ViewParams vp) {
@@ -174,32 +112,29 @@ __global__ void __launch_bounds__(256) k_dof_gather(DofGatherArgs a, ViewParams 
         const PassPixel px = pass_pixel<VIEWS>(vp, a.pixels[i], a.width, a.height);
         const size_t p = (size_t)px.Y * (size_t)a.width + px.X;
         const int x = (int)px.X - px.x0, y = (int)px.Y - px.y0;
-        const DofView L = a.tab[px.view];
+        const TileView L = a.tab[px.view];
         const float4 c = tp_load4(a.color + 4 * p);
         const float rN = a.scratch[(size_t)L.offN + (size_t)(y >> 4) * L.tw + (size_t)(x >> 4)];
         v3 o = mk3(c.x, c.y, c.z);
         if (rN > 0.5f && tp_finite(c.x) && tp_finite(c.y) && tp_finite(c.z)) {
             ngathered = 1u;
-            const float zp = dof_depth(a.depth[p]);
-            const float rp = dof_radius(zp, L.focus, a.k);
+            const float zp = pass_depth(a.depth[p]);
+            const float rp = dof_radius(zp, L.aux, a.k);
             const float wp = 1.0f / dof_area(rp);
             const float At = ((rN * rN) * DOF_PI) / (float)a.taps;
-            const uint32_t k0 = a.jitter ? dof_hash((uint32_t)x, (uint32_t)y, a.seed) & 63u : 0u;
+            const uint32_t k0 = a.jitter ? pass_hash((uint32_t)x, (uint32_t)y, a.seed) & 63u : 0u;
             const float fx = (float)x, fy = (float)y;
             v3 sum = mk3(0.0f);
             float Wt = 0.0f;
             for (uint32_t k = 0; k < a.taps; ++k) {
                 const float d = rN * a.tt->rho[k];
                 const float2 D = a.tt->D[k + k0];
-                int qx = (int)floorf((fx + d * D.x) + 0.5f), qy = (int)floorf((fy + d * D.y) + 0.5f);
-                qx = qx < 0 ? 0 : qx > px.wr - 1 ? px.wr - 1 : qx;
-                qy = qy < 0 ? 0 : qy > px.hr - 1 ? px.hr - 1 : qy;
-                const size_t q = (size_t)(px.y0 + qy) * (size_t)a.width + (size_t)(px.x0 + qx);
+                const size_t q = pass_tap(px, a.width, fx + d * D.x, fy + d * D.y);
                 const float dq = a.depth[q];
-                const float zq = dof_depth(dq);
-                const float rq = dof_radius(zq, L.focus, a.k);
+                const float zq = pass_depth(dq);
+                const float rq = dof_radius(zq, L.aux, a.k);
                 const float re = zq > zp ? rp : rq;
-                const float cov = dof_clamp01((re - d) + 0.5f);
+                const float cov = pass_clamp01((re - d) + 0.5f);
                 const float w = (cov * At) / dof_area(re);
                 if (!(w > 0.0f)) continue;
                 const float4 cq = tp_load4(a.color + 4 * q);
@@ -218,14 +153,7 @@ __global__ void __launch_bounds__(256) k_dof_gather(DofGatherArgs a, ViewParams 
         }
         gb_store4(a.out + 4 * p, make_float4(o.x, o.y, o.z, 1.0f));
     }
-    ngathered = dof_wave_sum(ngathered);
-    ntaps = dof_wave_sum(ntaps);
-    nnonfinite = dof_wave_sum(nnonfinite);
-    if ((threadIdx.x & 63u) == 0u) {
-        unsigned long long* slot = pass_slot(a.counts);
-        if (ngathered) atomicAdd(slot + 1, (unsigned long long)ngathered);
-        if (ntaps) atomicAdd(slot + 2, (unsigned long long)ntaps);
-        if (nnonfinite) atomicAdd(slot + 3, (unsigned long long)nnonfinite);
-    }
+    const uint32_t counted[3] = {ngathered, ntaps, nnonfinite};
+    pass_tally_sums(a.counts, 1u, counted); // words 1 .. 3
 #endif
 }

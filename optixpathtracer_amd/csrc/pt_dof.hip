@@ -1,25 +1,8 @@
-// pt_dof_layout and pt_dof_planes: the tile maxima (k_dof_tile), the neighbourhood maxima (k_dof_neighbour) and the gather (k_dof_gather)
-// of every view, T and N in caller memory.  Part of pt_lib.hip.
+// pt_dof_layout and pt_dof_planes: the tile maxima (k_dof_tile), the neighbourhood maxima (k_tile_neighbour<float>) and the gather
+// (k_dof_gather) of every view, T and N in caller memory.  Part of pt_lib.hip.
 #include "pt_dof.h"
 
-// The rectangles (each view's, or the frame) with their tile grids and where their T and N start; mblur_table's arithmetic over 4-byte
-// texels (pt_dof.h says why it is a copy).  focus is left for the caller.  Returns the scratch's size in floats.
-static uint64_t dof_table(const pt_ctx* ctx, std::vector<DofView>& tab) {
-    const uint32_t nv = pass_camera_count(ctx);
-    tab.assign(nv, DofView{});
-    uint64_t at = 0;
-    for (uint32_t v = 0; v < nv; ++v) {
-        DofView& t = tab[v];
-        if (ctx->vw.n) t.w = (uint32_t)ctx->vw.host[v].width, t.h = (uint32_t)ctx->vw.host[v].height, t.org = (uint32_t)ctx->vw.host[v].x | ((uint32_t)ctx->vw.host[v].y << 16);
-        else t.w = (uint32_t)ctx->width, t.h = (uint32_t)ctx->height, t.org = 0u;
-        t.tw = (t.w + PT_DOF_TILE - 1u) / PT_DOF_TILE;
-        t.th = (t.h + PT_DOF_TILE - 1u) / PT_DOF_TILE;
-        t.offT = (uint32_t)at;
-        t.offN = (uint32_t)(at + (uint64_t)t.tw * t.th);
-        at += 2u * (uint64_t)t.tw * t.th;
-    }
-    return at;
-}
+static_assert(PT_DOF_TILE == PASS_TILE, "pt_dof_planes works on the tiled passes' tiles");
 
 // The header's D and rho, operation for operation: every product and every sum is a float32 statement of its own (and the build does not
 // contract them).
@@ -34,21 +17,7 @@ static void dof_taps(DofTaps& t, uint32_t taps) {
     for (uint32_t i = 0; i < 64u; ++i) t.rho[i] = i < taps ? sqrtf(((float)i + 0.5f) / ftaps) : 0.0f;
 }
 
-extern "C" int pt_dof_layout(const pt_ctx* cctx, uint32_t* dims, size_t* bytes) {
-    if (!cctx) return fail(nullptr, PT_ERR_INVALID, "pt_dof_layout: null context");
-    pt_ctx* ctx = const_cast<pt_ctx*>(cctx); // (the error text only)
-    if (!bytes) return fail(ctx, PT_ERR_INVALID, "pt_dof_layout: bytes is null");
-    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_dof_layout: no frame size yet (pt_resize)");
-    std::vector<DofView> tab;
-    const uint64_t texels = dof_table(ctx, tab);
-    if (dims)
-        for (size_t v = 0; v < tab.size(); ++v) {
-            uint32_t* d = dims + 4 * v;
-            d[0] = tab[v].tw, d[1] = tab[v].th, d[2] = tab[v].offT, d[3] = tab[v].offN;
-        }
-    *bytes = (size_t)texels * 4;
-    return PT_OK;
-}
+extern "C" int pt_dof_layout(const pt_ctx* ctx, uint32_t* dims, size_t* bytes) { return pass_tile_layout(ctx, "pt_dof_layout", 4, dims, bytes); }
 
 extern "C" int pt_dof_planes(pt_ctx* ctx, const pt_dof_desc* desc, pt_dof_stats* stats) {
     if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_dof_planes: null context");
@@ -62,12 +31,12 @@ extern "C" int pt_dof_planes(pt_ctx* ctx, const pt_dof_desc* desc, pt_dof_stats*
     if (!std::isfinite(desc->max_radius) || !(desc->max_radius >= 1.f && desc->max_radius <= (float)PT_DOF_TILE))
         return fail(ctx, PT_ERR_INVALID, (fn + "max_radius must be finite and in [1," + std::to_string(PT_DOF_TILE) + "]").c_str());
     if (desc->taps < 1u || desc->taps > 64u) return fail(ctx, PT_ERR_INVALID, (fn + "taps must be 1..64, not " + std::to_string(desc->taps)).c_str());
-    std::vector<DofView> tab;
-    const uint64_t texels = dof_table(ctx, tab);
-    const uint32_t nv = pass_camera_count(ctx);
-    for (uint32_t v = 0; v < nv; ++v) {
-        tab[v].focus = desc->view_focus ? desc->view_focus[v] : desc->focus;
-        if (!focus_ok(tab[v].focus)) return fail(ctx, PT_ERR_INVALID, (fn + "view_focus[" + std::to_string(v) + "] must be finite and in (0,1e30]").c_str());
+    std::vector<TileView> tab;
+    const uint64_t texels = pass_tile_views(ctx, tab);
+    const uint32_t nv = (uint32_t)tab.size();
+    for (uint32_t v = 0; v < nv; ++v) { // aux: Fv
+        tab[v].aux = desc->view_focus ? desc->view_focus[v] : desc->focus;
+        if (!focus_ok(tab[v].aux)) return fail(ctx, PT_ERR_INVALID, (fn + "view_focus[" + std::to_string(v) + "] must be finite and in (0,1e30]").c_str());
     }
     const size_t npix = (size_t)ctx->width * ctx->height;
     // exclusive: may overlap no other plane (the two written ones); out may not be color either: the gather reads neighbours
@@ -78,25 +47,24 @@ extern "C" int pt_dof_planes(pt_ctx* ctx, const pt_dof_desc* desc, pt_dof_stats*
     int rc = pass_planes_check(ctx, "pt_dof_planes", planes, 4);
     if (rc) return rc;
     const DofParams k{desc->aperture + 0.0f, desc->max_radius};
-    uint32_t tiles = 0; // the largest view's
-    for (uint32_t v = 0; v < nv; ++v) tiles = std::max(tiles, tab[v].tw * tab[v].th);
+    const uint32_t tiles = pass_tile_max(tab);
     DofTaps tt;
     dof_taps(tt, desc->taps);
     PassRun run;
     rc = run.open(ctx, "pt_dof_planes", PASS_SLOT_BYTES); // per slot: sources, gathered, taps, nonfinite
     if (rc) return rc;
-    DofView* d_tab = nullptr;
+    TileView* d_tab = nullptr;
     DofTaps* d_tt = nullptr;
     CK(run.tmp.alloc(&d_tab, tab.size()));
     CK(run.tmp.alloc(&d_tt, 1));
-    CK(hipMemcpyAsync(d_tab, tab.data(), sizeof(DofView) * tab.size(), hipMemcpyHostToDevice, ctx->stream)); // (tab and tt live until the call has waited)
+    CK(hipMemcpyAsync(d_tab, tab.data(), sizeof(TileView) * tab.size(), hipMemcpyHostToDevice, ctx->stream)); // (tab and tt live until the call has waited)
     CK(hipMemcpyAsync(d_tt, &tt, sizeof(DofTaps), hipMemcpyHostToDevice, ctx->stream));
     rc = run.select(desc->block_mask);
     if (rc) return rc;
     const uint32_t n = run.n;
     float* scratch = reinterpret_cast<float*>(desc->scratch);
     hipLaunchKernelGGL(k_dof_tile, dim3((tiles + DOF_TILES_PER_BLOCK - 1u) / DOF_TILES_PER_BLOCK, nv), dim3(256), 0, ctx->stream, DofTileArgs{d_tab, ctx->width, desc->depth, scratch, k, run.counts()});
-    hipLaunchKernelGGL(k_dof_neighbour, dim3((tiles + 255u) / 256u, nv), dim3(256), 0, ctx->stream, DofNeighbourArgs{d_tab, scratch});
+    hipLaunchKernelGGL(k_tile_neighbour<float>, dim3((tiles + 255u) / 256u, nv), dim3(256), 0, ctx->stream, TileNeighbourArgs<float>{d_tab, scratch});
     if (n != 0) {
         const DofGatherArgs ga{run.pixels, n, ctx->width, ctx->height, desc->color, desc->depth, desc->out, d_tab, d_tt, scratch, k,
                                desc->taps, desc->seed, desc->flags & (uint32_t)PT_DOF_JITTER, run.counts()};

@@ -11,8 +11,9 @@
 // of pt_kernels.h are first used.
 //
 // What a pass needs beside the context (counters, a table or two, two events) is allocated per call and freed on every exit path by the
-// scaffold of pt_pass.h, outside the timed span.  No pass file includes another (what their kernels share is pt_pass_dev.h); a new pass is
-// one more line here (and in the Makefile's PASSES).
+// scaffold of pt_pass.h, outside the timed span.  No pass file includes another: what their kernels share is pt_pass_dev.h, the scaffold of
+// the tiled passes (motion blur, depth of field) included, with its host side in pt_pass.h.  A new pass is one more line here (and in the
+// Makefile's PASSES).
 #include "pt_api.hip"
 #include "pt_subset.hip"
 #include "pt_post.hip"

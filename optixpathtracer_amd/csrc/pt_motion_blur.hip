@@ -1,41 +1,10 @@
-// pt_motion_blur_layout and pt_motion_blur_planes: the tile maxima (k_mblur_tile), the neighbourhood maxima (k_mblur_neighbour) and the
-// gather (k_mblur_gather) of every view, T and N in caller memory.  Part of pt_lib.hip.
+// pt_motion_blur_layout and pt_motion_blur_planes: the tile maxima (k_mblur_tile), the neighbourhood maxima (k_tile_neighbour<float2>) and
+// the gather (k_mblur_gather) of every view, T and N in caller memory.  Part of pt_lib.hip.
 #include "pt_motion_blur.h"
 
-// The rectangles (each view's, or the frame) with their tile grids and where their T and N start.  Returns the scratch's size in 8-byte
-// texels.
-static uint64_t mblur_table(const pt_ctx* ctx, std::vector<MblurView>& tab) {
-    const uint32_t nv = pass_camera_count(ctx);
-    tab.assign(nv, MblurView{});
-    uint64_t at = 0;
-    for (uint32_t v = 0; v < nv; ++v) {
-        MblurView& t = tab[v];
-        if (ctx->vw.n) t.w = (uint32_t)ctx->vw.host[v].width, t.h = (uint32_t)ctx->vw.host[v].height, t.org = (uint32_t)ctx->vw.host[v].x | ((uint32_t)ctx->vw.host[v].y << 16);
-        else t.w = (uint32_t)ctx->width, t.h = (uint32_t)ctx->height, t.org = 0u;
-        t.tw = (t.w + PT_MOTION_BLUR_TILE - 1u) / PT_MOTION_BLUR_TILE;
-        t.th = (t.h + PT_MOTION_BLUR_TILE - 1u) / PT_MOTION_BLUR_TILE;
-        t.offT = (uint32_t)at;
-        t.offN = (uint32_t)(at + (uint64_t)t.tw * t.th);
-        at += 2u * (uint64_t)t.tw * t.th;
-    }
-    return at;
-}
+static_assert(PT_MOTION_BLUR_TILE == PASS_TILE, "pt_motion_blur_planes works on the tiled passes' tiles");
 
-extern "C" int pt_motion_blur_layout(const pt_ctx* cctx, uint32_t* dims, size_t* bytes) {
-    if (!cctx) return fail(nullptr, PT_ERR_INVALID, "pt_motion_blur_layout: null context");
-    pt_ctx* ctx = const_cast<pt_ctx*>(cctx); // (the error text only)
-    if (!bytes) return fail(ctx, PT_ERR_INVALID, "pt_motion_blur_layout: bytes is null");
-    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, "pt_motion_blur_layout: no frame size yet (pt_resize)");
-    std::vector<MblurView> tab;
-    const uint64_t texels = mblur_table(ctx, tab);
-    if (dims)
-        for (size_t v = 0; v < tab.size(); ++v) {
-            uint32_t* d = dims + 4 * v;
-            d[0] = tab[v].tw, d[1] = tab[v].th, d[2] = tab[v].offT, d[3] = tab[v].offN;
-        }
-    *bytes = (size_t)texels * 8;
-    return PT_OK;
-}
+extern "C" int pt_motion_blur_layout(const pt_ctx* ctx, uint32_t* dims, size_t* bytes) { return pass_tile_layout(ctx, "pt_motion_blur_layout", 8, dims, bytes); }
 
 extern "C" int pt_motion_blur_planes(pt_ctx* ctx, const pt_motion_blur_desc* desc, pt_motion_blur_stats* stats) {
     if (!ctx) return fail(nullptr, PT_ERR_INVALID, "pt_motion_blur_planes: null context");
@@ -48,10 +17,10 @@ extern "C" int pt_motion_blur_planes(pt_ctx* ctx, const pt_motion_blur_desc* des
         return fail(ctx, PT_ERR_INVALID, (fn + "max_blur must be finite and in [1," + std::to_string(PT_MOTION_BLUR_TILE) + "]").c_str());
     if (!std::isfinite(desc->depth_soft) || !(desc->depth_soft > 0.f && desc->depth_soft <= 1.f)) return fail(ctx, PT_ERR_INVALID, (fn + "depth_soft must be finite and in (0,1]").c_str());
     if (desc->taps < 1u || desc->taps > 64u) return fail(ctx, PT_ERR_INVALID, (fn + "taps must be 1..64, not " + std::to_string(desc->taps)).c_str());
-    std::vector<MblurView> tab;
-    const uint64_t texels = mblur_table(ctx, tab);
+    std::vector<TileView> tab;
+    const uint64_t texels = pass_tile_views(ctx, tab);
     const size_t npix = (size_t)ctx->width * ctx->height;
-    const uint32_t nv = pass_camera_count(ctx);
+    const uint32_t nv = (uint32_t)tab.size();
     // exclusive: may overlap no other plane (the two written ones); out may not be color either: the gather reads neighbours
     const PassPlane planes[5] = {{"color", desc->color, npix * 16, true, false},
                                  {"motion", desc->motion, npix * 8, true, false},
@@ -62,20 +31,19 @@ extern "C" int pt_motion_blur_planes(pt_ctx* ctx, const pt_motion_blur_desc* des
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(desc->scratch) & 7u) return fail(ctx, PT_ERR_INVALID, (fn + "scratch is not 8-byte aligned").c_str());
     const MblurParams k{0.5f * desc->shutter, desc->max_blur, desc->max_blur * desc->max_blur};
-    uint32_t tiles = 0; // the largest view's
-    for (uint32_t v = 0; v < nv; ++v) tiles = std::max(tiles, tab[v].tw * tab[v].th);
+    const uint32_t tiles = pass_tile_max(tab);
     PassRun run;
     rc = run.open(ctx, "pt_motion_blur_planes", PASS_SLOT_BYTES); // per slot: sources, unknown, moving, taps, nonfinite
     if (rc) return rc;
-    MblurView* d_tab = nullptr;
+    TileView* d_tab = nullptr;
     CK(run.tmp.alloc(&d_tab, tab.size()));
-    CK(hipMemcpyAsync(d_tab, tab.data(), sizeof(MblurView) * tab.size(), hipMemcpyHostToDevice, ctx->stream)); // (tab lives until the call has waited)
+    CK(hipMemcpyAsync(d_tab, tab.data(), sizeof(TileView) * tab.size(), hipMemcpyHostToDevice, ctx->stream)); // (tab lives until the call has waited)
     rc = run.select(desc->block_mask);
     if (rc) return rc;
     const uint32_t n = run.n;
     float2* scratch = reinterpret_cast<float2*>(desc->scratch);
     hipLaunchKernelGGL(k_mblur_tile, dim3((tiles + MBLUR_TILES_PER_BLOCK - 1u) / MBLUR_TILES_PER_BLOCK, nv), dim3(256), 0, ctx->stream, MblurTileArgs{d_tab, ctx->width, desc->motion, scratch, k, run.counts()});
-    hipLaunchKernelGGL(k_mblur_neighbour, dim3((tiles + 255u) / 256u, nv), dim3(256), 0, ctx->stream, MblurNeighbourArgs{d_tab, scratch});
+    hipLaunchKernelGGL(k_tile_neighbour<float2>, dim3((tiles + 255u) / 256u, nv), dim3(256), 0, ctx->stream, TileNeighbourArgs<float2>{d_tab, scratch});
     if (n != 0) {
         const MblurGatherArgs ga{run.pixels, n, ctx->width, ctx->height, desc->color, desc->motion, desc->depth, desc->out, d_tab, scratch, k, desc->depth_soft,
                                  desc->taps, desc->seed, desc->flags & (uint32_t)PT_MOTION_BLUR_JITTER, run.counts()};

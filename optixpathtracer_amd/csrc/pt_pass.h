@@ -1,11 +1,13 @@
 // pt_pass.h — what the image-space passes (pt_render_gbuffer, pt_temporal_accumulate, pt_filter_planes, pt_motion_planes,
-// pt_temporal_moments, pt_modulate_planes, ...) share on the host (pt_pass_dev.h: on the device): the plane table and its checks, the previous cameras, the block table of a
-// call, and the run object that owns a call's temporaries and its timed span.  Host only.  Included by pt_lib.hip behind pt_api.hip: the
-// second part uses that file's context and file-local helpers; the first part needs no HIP header (tests/test_pass_planes.py compiles it
-// with a host compiler alone).
+// pt_temporal_moments, pt_modulate_planes, ...) share on the host (pt_pass_dev.h: on the device): the plane table and its checks, the rectangles and the view
+// table of the tiled passes, the previous cameras, the block table of a call, and the run object that owns a call's temporaries and its
+// timed span.  Host only.  Included by pt_lib.hip behind pt_api.hip: the second part uses that file's context and file-local helpers; the
+// first part (the overlap routine, pass_tile_table) needs no HIP header (tests/test_pass_planes.py compiles it with a host compiler alone).
 #pragma once
 #include <cstddef>
 #include <cstdint>
+
+#include "pt_pass_dev.h" // the device side of the passes: TileView for any compiler, the rest (PASS_SLOTS, the layout of a tally in slots) for hipcc
 
 // One plane of a pass.  required: a null pointer is refused.  exclusive: may overlap no other plane (what the pass writes or zeroes); planes
 // that are only read may alias one another.
@@ -35,9 +37,31 @@ static inline bool pass_planes_overlap(const PassPlane* pl, int n, int* first, i
     return false;
 }
 
-#ifdef __HIPCC__
-#include "pt_pass_dev.h" // PASS_SLOTS: the device side of the passes, and the layout of a tally in slots
+// A rectangle of the frame that a pass works in: a view's, or the whole frame.  Its origin as the device tables carry it: x | y << 16.
+struct PassRect {
+    uint32_t x, y, w, h;
+};
+static inline uint32_t pass_rect_org(const PassRect& r) { return r.x | (r.y << 16); }
 
+// The view table of a tiled pass (TileView, pt_pass_dev.h): every rectangle with its grid of tile x tile tiles and where its T and its N
+// start in the scratch — T and N of the first rectangle, then of the second, one texel per tile each.  aux is left 0 for the pass.
+// Returns the scratch's size in texels.
+static inline uint64_t pass_tile_table(const PassRect* rects, uint32_t n, uint32_t tile, TileView* out) {
+    uint64_t at = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+        TileView& t = out[v];
+        t = TileView{};
+        t.w = rects[v].w, t.h = rects[v].h, t.org = pass_rect_org(rects[v]);
+        t.tw = (t.w + tile - 1u) / tile;
+        t.th = (t.h + tile - 1u) / tile;
+        t.offT = (uint32_t)at;
+        t.offN = (uint32_t)(at + (uint64_t)t.tw * t.th);
+        at += 2u * (uint64_t)t.tw * t.th;
+    }
+    return at;
+}
+
+#ifdef __HIPCC__
 // Every plane that is given or required is a device pointer of the context's device with `bytes` behind it; then the overlap test.
 // fn: the entry point's name, as it stands in front of the colon of its messages.
 static int pass_planes_check(pt_ctx* ctx, const char* fn, const PassPlane* pl, int n, int eq_a = -1, int eq_b = -1) {
@@ -52,6 +76,42 @@ static int pass_planes_check(pt_ctx* ctx, const char* fn, const PassPlane* pl, i
 
 // The previous frame's cameras (12 floats each: eye, U, V, W): one per view, one without views; a motion plane needs them.
 static uint32_t pass_camera_count(const pt_ctx* ctx) { return std::max(1u, ctx->vw.n); }
+// Each view's rectangle, or the frame's: pass_camera_count(ctx) of them
+static std::vector<PassRect> pass_rects(const pt_ctx* ctx) {
+    std::vector<PassRect> r(pass_camera_count(ctx), PassRect{0u, 0u, (uint32_t)ctx->width, (uint32_t)ctx->height});
+    for (uint32_t v = 0; v < ctx->vw.n; ++v) r[v] = PassRect{(uint32_t)ctx->vw.host[v].x, (uint32_t)ctx->vw.host[v].y, (uint32_t)ctx->vw.host[v].width, (uint32_t)ctx->vw.host[v].height};
+    return r;
+}
+// The view table of a tiled pass over the context's rectangles; returns the scratch's size in texels
+static uint64_t pass_tile_views(const pt_ctx* ctx, std::vector<TileView>& tab) {
+    const std::vector<PassRect> rects = pass_rects(ctx);
+    tab.resize(rects.size());
+    return pass_tile_table(rects.data(), (uint32_t)rects.size(), PASS_TILE, tab.data());
+}
+// The largest view's tile count: what sizes the x of a grid whose y is the view
+static uint32_t pass_tile_max(const std::vector<TileView>& tab) {
+    uint32_t tiles = 0;
+    for (const TileView& t : tab) tiles = std::max(tiles, t.tw * t.th);
+    return tiles;
+}
+// The body of pt_motion_blur_layout and pt_dof_layout: dims gets tw, th, offT, offN per view, bytes the scratch's size
+static int pass_tile_layout(const pt_ctx* cctx, const char* fn, size_t texel_bytes, uint32_t* dims, size_t* bytes) {
+    const std::string f = std::string(fn) + ": ";
+    if (!cctx) return fail(nullptr, PT_ERR_INVALID, (f + "null context").c_str());
+    pt_ctx* ctx = const_cast<pt_ctx*>(cctx); // (the error text only)
+    if (!bytes) return fail(ctx, PT_ERR_INVALID, (f + "bytes is null").c_str());
+    if (ctx->width == 0) return fail(ctx, PT_ERR_INVALID, (f + "no frame size yet (pt_resize)").c_str());
+    std::vector<TileView> tab;
+    const uint64_t texels = pass_tile_views(ctx, tab);
+    if (dims)
+        for (size_t v = 0; v < tab.size(); ++v) {
+            uint32_t* d = dims + 4 * v;
+            d[0] = tab[v].tw, d[1] = tab[v].th, d[2] = tab[v].offT, d[3] = tab[v].offN;
+        }
+    *bytes = (size_t)texels * texel_bytes;
+    return PT_OK;
+}
+
 static int pass_prev_cameras_check(pt_ctx* ctx, const char* fn, const void* motion, const float* prev_cameras, uint32_t num_prev_cameras) {
     const std::string f = std::string(fn) + ": ";
     const uint32_t ncams = pass_camera_count(ctx);

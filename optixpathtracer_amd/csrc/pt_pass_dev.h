@@ -1,10 +1,27 @@
 // pt_pass_dev.h — what the image-space passes share on the device (pt_pass.h is the host's side): the 16-byte loads and stores, the decode of a
-// pixel-list entry and its view, the surface key with the chain's two "same surface" predicates, the reprojection gather, and the per-wave
-// tally.  Every pass header includes this file and no other pass's kernel; nothing the frame path is compiled from includes it.
+// pixel-list entry and its view, the surface key with the chain's two "same surface" predicates, the reprojection gather, the per-wave
+// tally, and the scaffold of the tiled passes (motion blur, depth of field).  Every pass header includes this file and no other pass's
+// kernel; nothing the frame path is compiled from includes it.
 //
 // Everything here is PT_DEV (forced inline) and written in the order the public header gives, one float32 rounding per operation
 // (-ffp-contract=off is part of the library's flags), so a kernel built on these pieces keeps the bits its tests/*_ref.py reference pins.
 #pragma once
+#include <cstdint>
+
+// The view table of a tiled pass, one entry per rectangle: the one structure here that the host fills (pass_tile_table, pt_pass.h) and the
+// device reads, so it stands in front of the HIP headers, where a host compiler alone can see it.  T and N are planes of one texel per
+// tile, PASS_TILE x PASS_TILE pixels, in the caller's scratch.
+#define PASS_TILE 16u
+struct TileView {
+    uint32_t w, h, org;  // the rectangle; org = x0 | y0 << 16 in the frame
+    uint32_t tw, th;     // its tile grid
+    uint32_t offT, offN; // the first texel of T and of N in the scratch
+    float aux;           // the pass's own word per view: depth of field's focus distance, 0 for motion blur
+};
+
+#ifdef __HIPCC__
+#include <cfloat>
+
 #include "pt_kernels.h"
 
 // ------------------------------------------------------------------ loads and stores
@@ -195,3 +212,109 @@ PT_DEV void pass_tally(unsigned long long* words, const bool (&flag)[N]) {
 }
 // counts: [PASS_SLOTS][8], zero at launch; 256-thread blocks
 PT_DEV unsigned long long* pass_slot(unsigned long long* counts) { return counts + 8u * ((blockIdx.x * 4u + (threadIdx.x >> 6)) & (PASS_SLOTS - 1u)); }
+
+// ------------------------------------------------------------------ tiled passes
+// What k_mblur_* and k_dof_* share: a pass reduces every PASS_TILE x PASS_TILE tile of every rectangle to one texel (T), takes the greatest T
+// of the 3 x 3 tiles around each tile (N), and gathers along or around N over the call's pixel list.  One launch covers all views:
+// blockIdx.y is the view, and a block past the end of its view's grid leaves at once.  Everything works in a rectangle's own coordinates,
+// which is what keeps a tap and a tile neighbour from leaving it.  What differs stays in the pass's header: what a tile is reduced to and
+// how (k_mblur_tile's 64-bit key, k_dof_tile's plain maximum), the tap rule, the weights.
+PT_DEV float pass_depth(float d) { return (d > 1e-6f && d <= FLT_MAX) ? d : FLT_MAX; } // Z(depth) of the header
+PT_DEV float pass_clamp01(float x) {
+    x = x > 0.0f ? x : 0.0f;
+    return x < 1.0f ? x : 1.0f;
+}
+PT_DEV uint32_t pass_hash(uint32_t x, uint32_t y, uint32_t seed) {
+    uint32_t h = (x * 0x9E3779B1u) ^ (y * 0x85EBCA77u) ^ (seed * 0xC2B2AE3Du);
+    h ^= h >> 16;
+    h *= 0x7FEB352Du;
+    h ^= h >> 15;
+    h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    return h;
+}
+PT_DEV uint32_t pass_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// A tile kernel is one WAVE per tile: lane l takes the four pixels (l & 3) * 4 + k, k = 0 .. 3, of the tile's row l >> 2, so lane * 4 + k is
+// the pixel's row-order index in the tile.  in: the pixel lies in the rectangle (a partial tile); p: its index in a plane of the frame
+// (Y * width + X).  A pixel outside has the p of the rectangle's pixel (0, 0), to be loaded and dropped.  Pixel 0 of a tile is always inside.
+struct TilePixel {
+    bool in;
+    size_t p;
+};
+PT_DEV TilePixel tile_pixel(const TileView& L, int width, uint32_t tile, uint32_t lane, uint32_t k) {
+    const uint32_t x = (tile % L.tw) * PASS_TILE + (lane & 3u) * 4u + k, y = (tile / L.tw) * PASS_TILE + (lane >> 2);
+    const bool in = x < L.w && y < L.h;
+    const uint32_t sx = in ? x : 0u, sy = in ? y : 0u;
+    return TilePixel{in, (size_t)((L.org >> 16) + sy) * (size_t)width + (size_t)((L.org & 0xffffu) + sx)};
+}
+
+// k_tile_neighbour<Texel>: N, the T of greatest key of the 3 x 3 tiles around a tile that exist.  One thread per tile, up to nine loads,
+// row order, the first existing tile taken, then strict >: among equal keys the first in row order wins, which is what decides motion blur's
+// N (float2, key l2).  Depth of field's (float, key the value itself) does not depend on it: every T is a radius K * |..| clamped to R with
+// K = aperture + 0.0f, so it is >= +0, never NaN and never -0, and the first of several equal floats has the bits of all of them — the
+// same bits as a maximum that starts from 0.  The launch is tiny and launch-bound; it is a kernel of its own because folded into the gather
+// every wave would redo the nine loads for a value that 256 pixels share, and N has to reach the scratch either way.
+PT_DEV float tile_key(float t) { return t; }
+PT_DEV float tile_key(float2 t) { return t.x * t.x + t.y * t.y; }
+template <typename Texel>
+struct TileNeighbourArgs {
+    const TileView* tab;
+    Texel* scratch;
+};
+template <typename Texel>
+__global__ void __launch_bounds__(256) k_tile_neighbour(TileNeighbourArgs<Texel> a) {
+#if __HIP_DEVICE_COMPILE__
+    const TileView L = a.tab[blockIdx.y];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= L.tw * L.th) return;
+    const int ti = (int)(i % L.tw), tj = (int)(i / L.tw);
+    Texel best{};
+    float bestk = 0.0f;
+    bool any = false;
+#pragma unroll
+    for (int dj = -1; dj <= 1; ++dj)
+#pragma unroll
+        for (int di = -1; di <= 1; ++di) {
+            const int u = ti + di, v = tj + dj;
+            if (u < 0 || u >= (int)L.tw || v < 0 || v >= (int)L.th) continue;
+            const Texel t = a.scratch[(size_t)L.offT + (size_t)v * L.tw + (size_t)u];
+            const float key = tile_key(t);
+            if (!any || key > bestk) {
+                best = t;
+                bestk = key;
+                any = true;
+            }
+        }
+    a.scratch[(size_t)L.offN + i] = best;
+#endif
+}
+
+// A gather's tap: the position (fx, fy) in the rectangle's coordinates, as the pass's rule computed it, rounded to the nearest pixel,
+// clamped to the rectangle; returns that pixel's index in a plane of the frame.
+PT_DEV size_t pass_tap(const PassPixel& px, int width, float fx, float fy) {
+    int qx = (int)floorf(fx + 0.5f), qy = (int)floorf(fy + 0.5f);
+    qx = qx < 0 ? 0 : qx > px.wr - 1 ? px.wr - 1 : qx;
+    qy = qy < 0 ? 0 : qy > px.hr - 1 ? px.hr - 1 : qy;
+    return (size_t)(px.y0 + qy) * (size_t)width + (size_t)(px.x0 + qx);
+}
+
+// A gather's epilogue: per-lane counts (sums, not flags: pass_tally is for those), added up across the wave by shuffles and added to words
+// first .. first + N - 1 of the wave's slot by one atomic per non-zero sum.  EVERY lane of the wave must reach the call.
+template <int N>
+PT_DEV void pass_tally_sums(unsigned long long* counts, uint32_t first, const uint32_t (&n)[N]) {
+    uint32_t s[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) s[j] = pass_wave_sum(n[j]);
+    if ((threadIdx.x & 63u) == 0u) {
+        unsigned long long* slot = pass_slot(counts) + first;
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            if (s[j]) atomicAdd(slot + j, (unsigned long long)s[j]);
+    }
+}
+#endif // __HIPCC__

@@ -895,15 +895,19 @@ class SampleRenderer:
         desc.flags = 0
         return self._run_pass("pt_edge_aa_planes", desc, _lib.EdgeAaStats(), result)
 
+    def _view_count(self):
+        """max(1, the view count): how many rectangles, cameras and per-view words a pass works with"""
+        count = C.c_uint32(0)
+        if getattr(self, "_ctx", None):
+            self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
+        return max(1, count.value)
+
     def _view_words(self, fn, name, t, dtype, width, alloc=False):
         """A per-view array of pt_exposure_planes / pt_tonemap_planes: (max(1, views), width) of dtype, a tensor, a raw pointer or None."""
         import torch
 
         dev = getattr(self, "_device", 0)
-        count = C.c_uint32(0)
-        if getattr(self, "_ctx", None):
-            self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
-        nv = max(1, count.value)
+        nv = self._view_count()
         if t is None and alloc:
             t = torch.zeros((nv, width), dtype=dtype, device=f"cuda:{dev}")
         if t is None or isinstance(t, int):
@@ -957,6 +961,28 @@ class SampleRenderer:
         desc.exposure, desc.white, desc.op, desc.flags = float(exposure), float(white), _lib.TONEMAP_OPS[op], 0
         return self._run_pass("pt_tonemap_planes", desc, _lib.TonemapStats(), result)
 
+    def _bind_scratch(self, fn, desc, result, scratch, shape):
+        """desc.scratch and result["scratch"] of a pass with a scratch plane: a raw pointer as it is, or a float32 tensor of shape() — the
+        pass's layout, asked for only then — allocated when None."""
+        import torch
+
+        if isinstance(scratch, int):
+            desc.scratch, result["scratch"] = scratch, None
+            return
+        dev = getattr(self, "_device", 0)
+        shape = shape()
+        if scratch is None:
+            scratch = torch.empty(shape, dtype=torch.float32, device=f"cuda:{dev}")
+        _check_temporal_tensor("scratch", scratch, dev, {torch.float32: shape}, fn)
+        desc.scratch, result["scratch"] = scratch.data_ptr(), scratch
+
+    def _tile_layout(self, cname):
+        """(dims, bytes) of a tiled pass's scratch: motionBlurLayout and dofLayout"""
+        nbytes = C.c_size_t()
+        dims = np.zeros((self._view_count(), 4), np.uint32)
+        self._ck(getattr(self._L, cname)(self._ctx, dims.ctypes.data, C.byref(nbytes)), cname)
+        return dims, nbytes.value
+
     def bloomLayout(self, levels=6):
         """The shape of bloomPlanes's scratch pyramid (pt_bloom_layout): (dims, bytes) with dims a uint32 (views, 8, 4) array of w, h, the
         index of the level's first 16-byte texel and 0 per level (zeros above `levels`), views = max(1, the view count), and bytes the
@@ -964,9 +990,8 @@ class SampleRenderer:
         levels = int(levels)
         if not 1 <= levels <= _lib.PT_BLOOM_MAX_LEVELS:
             raise ValueError(f"bloomLayout: levels must be 1..{_lib.PT_BLOOM_MAX_LEVELS}, not {levels}")
-        count, nbytes = C.c_uint32(0), C.c_size_t()
-        self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
-        dims = np.zeros((max(1, count.value), _lib.PT_BLOOM_MAX_LEVELS, 4), np.uint32)
+        nbytes = C.c_size_t()
+        dims = np.zeros((self._view_count(), _lib.PT_BLOOM_MAX_LEVELS, 4), np.uint32)
         self._ck(self._L.pt_bloom_layout(self._ctx, levels, dims.ctypes.data, C.byref(nbytes)), "pt_bloom_layout")
         return dims, nbytes.value
 
@@ -991,15 +1016,7 @@ class SampleRenderer:
         desc = _lib.BloomDesc()
         result = self._bind_planes("bloomPlanes", desc, dict(color=color, out=out), _lib.BLOOM_PLANES, ("color",), _lib.BLOOM_OUTPUTS, alloc=("out",))
         desc.state, _ = self._view_words("bloomPlanes", "state", state, torch.float32, 4)
-        dev = getattr(self, "_device", 0)
-        if isinstance(scratch, int):
-            desc.scratch, result["scratch"] = scratch, None
-        else:
-            texels = self.bloomLayout(levels)[1] // 16
-            if scratch is None:
-                scratch = torch.empty((texels, 4), dtype=torch.float32, device=f"cuda:{dev}")
-            _check_temporal_tensor("scratch", scratch, dev, {torch.float32: (texels, 4)}, "bloomPlanes")
-            desc.scratch, result["scratch"] = scratch.data_ptr(), scratch
+        self._bind_scratch("bloomPlanes", desc, result, scratch, lambda: (self.bloomLayout(levels)[1] // 16, 4))
         m = self._bind_mask("bloomPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
         desc.exposure, desc.threshold, desc.knee, desc.clamp = float(exposure), float(threshold), float(knee), float(clamp)
         desc.spread, desc.intensity, desc.levels, desc.flags = float(spread), float(intensity), levels, 0
@@ -1008,11 +1025,7 @@ class SampleRenderer:
     def motionBlurLayout(self):
         """The shape of motionBlurPlanes's scratch (pt_motion_blur_layout): (dims, bytes) with dims a uint32 (views, 4) array of tw, th, the
         index of T's first 8-byte texel and the index of N's, views = max(1, the view count), and bytes the size of the scratch."""
-        count, nbytes = C.c_uint32(0), C.c_size_t()
-        self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
-        dims = np.zeros((max(1, count.value), 4), np.uint32)
-        self._ck(self._L.pt_motion_blur_layout(self._ctx, dims.ctypes.data, C.byref(nbytes)), "pt_motion_blur_layout")
-        return dims, nbytes.value
+        return self._tile_layout("pt_motion_blur_layout")
 
     def motionBlurPlanes(self, color, motion, depth, out=None, scratch=None, mask=None, shutter=0.5, max_blur=16.0, depth_soft=0.05, taps=12,
                          seed=0, jitter=False) -> dict:
@@ -1029,8 +1042,6 @@ class SampleRenderer:
         jitter: each pixel's taps are shifted by a hash of its coordinates and `seed`.
         Returns {"out", "scratch": the tensor (None for a raw pointer), "stats": {pixels, sources, unknown, moving, taps, nonfinite,
         kernel_ms}}."""
-        import torch
-
         taps, seed = int(taps), int(seed)
         if not 1 <= taps <= 64:
             raise ValueError(f"motionBlurPlanes: taps must be 1..64, not {taps}")
@@ -1045,15 +1056,7 @@ class SampleRenderer:
         desc = _lib.MotionBlurDesc()
         result = self._bind_planes("motionBlurPlanes", desc, dict(color=color, motion=motion, depth=depth, out=out), _lib.MOTION_BLUR_PLANES,
                                    ("color", "motion", "depth"), _lib.MOTION_BLUR_OUTPUTS, alloc=("out",))
-        dev = getattr(self, "_device", 0)
-        if isinstance(scratch, int):
-            desc.scratch, result["scratch"] = scratch, None
-        else:
-            texels = self.motionBlurLayout()[1] // 8
-            if scratch is None:
-                scratch = torch.empty((texels, 2), dtype=torch.float32, device=f"cuda:{dev}")
-            _check_temporal_tensor("scratch", scratch, dev, {torch.float32: (texels, 2)}, "motionBlurPlanes")
-            desc.scratch, result["scratch"] = scratch.data_ptr(), scratch
+        self._bind_scratch("motionBlurPlanes", desc, result, scratch, lambda: (self.motionBlurLayout()[1] // 8, 2))
         m = self._bind_mask("motionBlurPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
         desc.shutter, desc.max_blur, desc.depth_soft = float(shutter), float(max_blur), float(depth_soft)
         desc.taps, desc.seed, desc.flags = taps, seed, _lib.PT_MOTION_BLUR_JITTER if jitter else 0
@@ -1072,11 +1075,7 @@ class SampleRenderer:
     def dofLayout(self):
         """The shape of dofPlanes's scratch (pt_dof_layout): (dims, bytes) with dims a uint32 (views, 4) array of tw, th, the index of T's
         first 4-byte texel and the index of N's, views = max(1, the view count), and bytes the size of the scratch."""
-        count, nbytes = C.c_uint32(0), C.c_size_t()
-        self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
-        dims = np.zeros((max(1, count.value), 4), np.uint32)
-        self._ck(self._L.pt_dof_layout(self._ctx, dims.ctypes.data, C.byref(nbytes)), "pt_dof_layout")
-        return dims, nbytes.value
+        return self._tile_layout("pt_dof_layout")
 
     def dofPlanes(self, color, depth, out=None, scratch=None, mask=None, focus=None, aperture=None, max_radius=16.0, taps=32, seed=0,
                   jitter=False, view_focus=None) -> dict:
@@ -1096,8 +1095,6 @@ class SampleRenderer:
         floats), None: `focus` for all.  jitter: each pixel's pattern is turned by a hash of its coordinates and `seed`.
         Returns {"out", "scratch": the tensor (None for a raw pointer), "stats": {pixels, sources, gathered, taps, nonfinite,
         kernel_ms}}."""
-        import torch
-
         if focus is None or aperture is None:
             raise ValueError("dofPlanes: focus and aperture are required")
         taps, seed = int(taps), int(seed)
@@ -1114,22 +1111,12 @@ class SampleRenderer:
         desc = _lib.DofDesc()
         result = self._bind_planes("dofPlanes", desc, dict(color=color, depth=depth, out=out), _lib.DOF_PLANES, ("color", "depth"),
                                    _lib.DOF_OUTPUTS, alloc=("out",))
-        dev = getattr(self, "_device", 0)
-        if isinstance(scratch, int):
-            desc.scratch, result["scratch"] = scratch, None
-        else:
-            dims, nbytes = self.dofLayout()
-            if scratch is None:
-                scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=f"cuda:{dev}")
-            _check_temporal_tensor("scratch", scratch, dev, {torch.float32: (nbytes // 4,)}, "dofPlanes")
-            desc.scratch, result["scratch"] = scratch.data_ptr(), scratch
+        self._bind_scratch("dofPlanes", desc, result, scratch, lambda: (self.dofLayout()[1] // 4,))
         vf = None
         if view_focus is not None:
-            count = C.c_uint32(0)
-            self._L.pt_get_views(self._ctx, None, 0, C.byref(count))
             vf = np.ascontiguousarray(view_focus, np.float32).reshape(-1)
-            if vf.size != max(1, count.value):
-                raise ValueError(f"dofPlanes: view_focus has {vf.size} values, expected {max(1, count.value)}")
+            if vf.size != self._view_count():
+                raise ValueError(f"dofPlanes: view_focus has {vf.size} values, expected {self._view_count()}")
             if not ((vf > 0) & (vf <= np.float32(1e30))).all():
                 raise ValueError("dofPlanes: view_focus must be in (0,1e30]")
             desc.view_focus = vf.ctypes.data  # (vf is kept until the call has returned)

@@ -3,22 +3,13 @@ tests/test_bloom_cabi.py and tests/test_gpu_bloom.py.  A helper, not a test; it 
 arrays and float32 scalars, one rounding per operation, in the header's order (NumPy never contracts a product and a sum)."""
 import numpy as np
 
+from tile_ref import SENTINEL, finite, rectangles  # noqa: F401 (SENTINEL: for the tests)
+
 f32 = np.float32
 u32 = np.uint32
 MAX_LEVELS = 8
-SENTINEL = u32(0xA5A5A5A5)
 COUNTERS = ("pixels", "sources", "bright", "nonfinite")
 DEFAULTS = dict(exposure=1.0, threshold=1.0, knee=0.5, clamp=65504.0, spread=0.7, intensity=0.25, levels=6)
-
-
-def finite(a):
-    """the exponent-bit test"""
-    return (np.ascontiguousarray(a, f32).view(u32) & u32(0x7F800000)) != u32(0x7F800000)
-
-
-def rectangles(rects, h, w):
-    """the views' rectangles (x0, y0, w0, h0), or the frame"""
-    return [tuple(int(v) for v in r) for r in rects] if rects else [(0, 0, w, h)]
 
 
 def layout(rects, h, w, levels):

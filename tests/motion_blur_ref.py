@@ -4,36 +4,19 @@ is float32 arrays and float32 scalars, one rounding per operation, in the header
 sqrt and its division are correctly rounded).  Vectorised over the pixels of a rectangle; the only loops are over the taps and the tiles."""
 import numpy as np
 
+import tile_ref
+from tile_ref import FLT_MAX, SENTINEL, TILE, clamp01, depth_z, finite, hash32, rectangles  # noqa: F401 (kept as this module's names)
+
 f32 = np.float32
 u32 = np.uint32
-TILE = 16
 JITTER = 1
-SENTINEL = u32(0xA5A5A5A5)
-FLT_MAX = np.finfo(f32).max
 COUNTERS = ("pixels", "sources", "unknown", "moving", "taps", "nonfinite")
 DEFAULTS = dict(shutter=0.5, max_blur=16.0, depth_soft=0.05, taps=12, seed=0, jitter=False)
 
 
-def finite(a):
-    """the exponent-bit test"""
-    return (np.ascontiguousarray(a, f32).view(u32) & u32(0x7F800000)) != u32(0x7F800000)
-
-
-def rectangles(rects, h, w):
-    """the views' rectangles (x0, y0, wr, hr), or the frame"""
-    return [tuple(int(v) for v in r) for r in rects] if rects else [(0, 0, w, h)]
-
-
 def layout(rects, h, w):
     """(dims (nv, 4) uint32: tw, th, first 8-byte texel of T, first of N; bytes)"""
-    rs = rectangles(rects, h, w)
-    dims = np.zeros((len(rs), 4), u32)
-    at = 0
-    for v, (_, _, wr, hr) in enumerate(rs):
-        tw, th = (wr + TILE - 1) // TILE, (hr + TILE - 1) // TILE
-        dims[v] = (tw, th, at, at + tw * th)
-        at += 2 * tw * th
-    return dims, 8 * at
+    return tile_ref.layout(rects, h, w, 8)
 
 
 def velocity(m, shutter, max_blur):
@@ -90,36 +73,11 @@ def neighbour_max(T):
     return N
 
 
-def hash32(x, y, seed):
-    """the header's hash, in uint64 arithmetic masked to 32 bits"""
-    M = np.uint64(0xFFFFFFFF)
-    x, y = np.asarray(x, np.uint64), np.asarray(y, np.uint64)
-    h = ((x * np.uint64(0x9E3779B1)) & M) ^ ((y * np.uint64(0x85EBCA77)) & M) ^ ((np.uint64(seed) * np.uint64(0xC2B2AE3D)) & M)
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x7FEB352D)) & M
-    h ^= h >> np.uint64(15)
-    h = (h * np.uint64(0x846CA68B)) & M
-    h ^= h >> np.uint64(16)
-    return h.astype(u32)
-
-
 def jitter_of(x, y, seed):
     """j in [-0.5, 0.5) of the local coordinates"""
     j = (hash32(x, y, seed) >> u32(8)).astype(f32) * f32(2.0 ** -24) - f32(0.5)
     assert j.dtype == f32
     return j
-
-
-def depth_z(d):
-    d = np.ascontiguousarray(d, f32)
-    with np.errstate(all="ignore"):
-        return np.where((d > f32(1e-6)) & (d <= FLT_MAX), d, FLT_MAX).astype(f32)
-
-
-def clamp01(x):
-    with np.errstate(all="ignore"):
-        x = np.where(x > 0, x, f32(0)).astype(f32)
-        return np.where(x < 1, x, f32(1)).astype(f32)
 
 
 def length(l2):

@@ -1,8 +1,10 @@
-"""The overlap routine of the image-space passes (csrc/pt_pass.h, the part that needs no HIP header) without a GPU: a stand-alone host
-program, compiled with g++ alone, runs pass_planes_overlap over small plane tables and prints the first offending pair of each."""
+"""The overlap routine and the tile table of the image-space passes (csrc/pt_pass.h, the part that needs no HIP header) without a GPU:
+stand-alone host programs, compiled with g++ alone, run pass_planes_overlap over small plane tables and print the first offending pair of
+each, and pass_tile_table over small sets of rectangles and print every view's entry."""
 import os
 import subprocess
 
+import tile_ref
 from conftest import ROOT
 
 # (what, eq_a, eq_b, rows of (name, address, bytes, required, exclusive)) -> the first offending pair in table order, or None
@@ -43,3 +45,37 @@ def test_overlap_routine_on_the_host(tmp_path):
     for (what, _, _, _, want), line in zip(CASES, got):
         assert line == ("none" if want is None else " ".join(want)), (what, line)
     assert got[len(CASES)] == "1" and got[len(CASES) + 1:] == [""]
+
+
+# (frame (h, w), the views' rectangles (x0, y0, wr, hr) or None): one tile, a full tile, a partial column, partial tiles both ways, and two
+# views of odd sizes of which one lies off the origin
+TILE_CASES = [((1, 1), None), ((16, 16), None), ((16, 17), None), ((49, 33), None), ((64, 64), [(0, 0, 33, 49), (40, 3, 15, 17)])]
+
+
+def test_tile_table_on_the_host(tmp_path):
+    """pass_tile_table, the view table of the tiled passes (motion blur, depth of field), against tests/tile_ref.py's layout: the tile
+    grid, where T and N of every view start, the texel total, and the origin packed as x | y << 16; aux is left 0."""
+    body = ['#include <cstdio>', '#include <cstring>', '#include "pt_pass.h"', "int main() {",
+            '    static_assert(sizeof(TileView) == 32, "the device reads eight words per view");']
+    for k, ((h, w), rects) in enumerate(TILE_CASES):
+        rs = tile_ref.rectangles(rects, h, w)
+        body += [f"    const PassRect r{k}[] = {{{', '.join(f'{{{x}u, {y}u, {wr}u, {hr}u}}' for x, y, wr, hr in rs)}}};",
+                 f"    TileView t{k}[{len(rs)}];",
+                 f"    memset(t{k}, 0xff, sizeof(t{k}));",
+                 f'    printf("%llu\\n", (unsigned long long)pass_tile_table(r{k}, {len(rs)}, PASS_TILE, t{k}));',
+                 f'    for (const TileView& t : t{k}) printf("%u %u %u %u %u %u %u %d\\n", t.tw, t.th, t.offT, t.offN, t.org, t.w, t.h, t.aux == 0.0f);']
+    body += ["    return 0;", "}"]
+    src = tmp_path / "tiles.cpp"
+    src.write_text("\n".join(body) + "\n")
+    exe = tmp_path / "tiles"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "optixpathtracer_amd", "csrc"), str(src), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
+    want = []
+    for (h, w), rects in TILE_CASES:
+        dims, nbytes = tile_ref.layout(rects, h, w, 1)  # one byte a texel: the texel total
+        want.append(str(nbytes))
+        for (x, y, wr, hr), (tw, th, at_t, at_n) in zip(tile_ref.rectangles(rects, h, w), dims.tolist()):
+            assert (tw, th) == (-(-wr // tile_ref.TILE), -(-hr // tile_ref.TILE)) and at_n == at_t + tw * th
+            want.append(f"{tw} {th} {at_t} {at_n} {x | y << 16} {wr} {hr} 1")
+    assert got == want + [""]
+    assert want[:2] == ["2", "1 1 0 1 0 1 1 1"] and want[-1] == f"1 2 24 26 {40 | 3 << 16} 15 17 1"  # the reference itself, at both ends
