@@ -384,6 +384,11 @@ struct pt_ctx {
     int enqueue_threads = 1; // PT_ENQUEUE_THREADS: 0 one enqueue thread, 1 one thread per pixel chunk for small synchronous frames (default), 2 at every size
     int trace_grid_min = 2048, grid_chunks = 6; // PT_GRID_MIN / PT_GRID_CHUNKS (tuning hooks): smallest persistent grid, chunks of 64 paths per wave aimed at
     int lds_skip = 0; // PT_STACK_LDS_SKIP (test hook, pt_bvh8.h)
+    // Launch shapes of the kernels around the traversal launches.  shade_wg: threads per workgroup of k_shade / k_shade_carry
+    // (PT_SHADE_WG = 64 | 128 | 256); shade_lean: their LDS copy of the probe's marginal arrays without pdfY (PT_SHADE_LDS = full | lean);
+    // small_wg: k_generate, k_generate_views and the resolve kernels in 64-thread workgroups (PT_SMALL_WG = 0 | 1)
+    int shade_wg = 128;
+    bool shade_lean = true, small_wg = false;
     int ovf_depth = 0; // spill levels of the traversal stack (PT8_OVF_DEPTH; test hook PT_STACK_CAP lowers the total capacity)
     int stack_check = 1; // PT_STACK_NOCHECK=1 (test hook): skip the build-time depth check so that the in-kernel fault flag is reached
     // stats + timing
@@ -665,6 +670,22 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
         if (const char* e = getenv("PT_TRACE_WAVES")) wpe = atoi(e);
         if (const char* e = getenv("PT_GRID_MIN")) ctx->trace_grid_min = std::max(64, atoi(e));
         if (const char* e = getenv("PT_GRID_CHUNKS")) ctx->grid_chunks = std::max(1, atoi(e));
+        if (const char* e = getenv("PT_SHADE_WG")) {
+            const int wg = atoi(e);
+            if (wg != 64 && wg != 128 && wg != 256) {
+                ctx->err = "pt_create: PT_SHADE_WG must be 64, 128 or 256";
+                return bail(PT_ERR_UNSUPPORTED);
+            }
+            ctx->shade_wg = wg;
+        }
+        if (const char* e = getenv("PT_SHADE_LDS")) {
+            if (strcmp(e, "full") && strcmp(e, "lean")) {
+                ctx->err = "pt_create: PT_SHADE_LDS must be full or lean";
+                return bail(PT_ERR_UNSUPPORTED);
+            }
+            ctx->shade_lean = !strcmp(e, "lean");
+        }
+        if (const char* e = getenv("PT_SMALL_WG")) ctx->small_wg = atoi(e) != 0;
         if (const char* e = getenv("PT_STACK_LDS_SKIP")) ctx->lds_skip = std::max(0, std::min(PT8_LDS_DEPTH, atoi(e)));
         ctx->trace_grid = prop.multiProcessorCount * 4 * wpe;
         if (const char* e = getenv("PT_CAM_PACKETS")) ctx->cam_packets = atoi(e) != 0;
@@ -1179,7 +1200,7 @@ static int ensure_path_state(pt_ctx* ctx, int nsets, uint32_t cap, uint32_t pix_
     ctx->set_cap = ctx->set_pix_cap = 0; // published again at the end: until then the context has no path state
     CK(dclear(ctx->stream, ctx->tot.d_totals, sizeof(unsigned long long) * PT_MAX_FRAMES * PT_MAX_SETS * 4)); // slices of sets that no longer exist
     ctx->sets.resize(nsets);
-    ctx->sub_cap = cap / PT_NSUB + 8192 + 1; // a sub-queue receives at most cap/64 + 32 workgroups * 256 entries
+    ctx->sub_cap = cap / PT_NSUB + 8192 + 1; // a sub-queue receives at most cap/64 + 32 workgroups * 256 entries (64 x 128, 128 x 64: the same 8192 threads of a launch in every shape, launch_shade_wg)
     const int rc = build_path_state(ctx, nsets, cap, pix_cap, nq, async);
     if (rc) {
         ctx->sets.clear(); // all of it or nothing (the streams stay: they belong to the context)
@@ -1234,10 +1255,10 @@ struct SpanGuard {
 
 static const int GRID = 256 * 8;
 
-// dynamic LDS of k_shade: its copy of the probe's marginal arrays (cdfY, pdfY, c8Y, c64Y), or nothing when they stay in global memory
-static size_t shade_lds_bytes(const DevProbe& p) {
-    if (!p.c64Y || p.height > PT_LDS_PROBE_ROWS) return 0;
-    return sizeof(float) * ((size_t)2 * p.height + p.height / 8 + ((p.ncy + 7) & ~7));
+// dynamic LDS of k_shade: its copy of the probe's marginal arrays (shade_marg_words: none when they stay in global memory) and, in textured
+// scenes, the 256 byte values as floats
+static size_t shade_lds_bytes(const ShadeParams& sp) {
+    return sizeof(float) * ((size_t)shade_marg_words(sp.probe, sp.lean != 0u) + (sp.mesh_tex ? 256u : 0u));
 }
 // the path state a launch sees: the slot-indexed arrays plus the radiance stream of its input queue (X[k]) and the shadow stream
 static PathState stream_view(const pt_ctx::BatchSet& bs, int k) {
@@ -1247,15 +1268,26 @@ static PathState stream_view(const pt_ctx::BatchSet& bs, int k) {
     s.c0 = bs.X[k].c0; s.c1 = bs.X[k].c1; s.svis = bs.svis;
     return s;
 }
+// One shade launch in workgroups of WG threads.  grid x WG stays GRID * 256 threads, so the grid-stride loop hands every thread (and every
+// wave) the queue entries it has in the 256-thread shape; only the sub-queue a workgroup appends to (blockIdx.x % PT_NSUB) moves.
+template <int MODE, int WG>
+static void launch_shade_wg(const pt_ctx* ctx, hipStream_t s, const PathState& st, const ShadeParams& sp, bool carry) {
+    const unsigned lds = (unsigned)shade_lds_bytes(sp);
+    const dim3 grid(GRID * (256 / WG)), block(WG);
+    if (carry)
+        hipLaunchKernelGGL((k_shade_carry<MODE, WG>), grid, block, lds, s, st, sp);
+    else if (ctx->has_catcher)
+        hipLaunchKernelGGL((k_shade<MODE, true, WG>), grid, block, lds, s, st, sp);
+    else
+        hipLaunchKernelGGL((k_shade<MODE, false, WG>), grid, block, lds, s, st, sp);
+}
 template <int MODE>
 static void launch_shade(const pt_ctx* ctx, hipStream_t s, const PathState& st, const ShadeParams& sp, bool carry) {
-    const unsigned lds = (unsigned)shade_lds_bytes(sp.probe);
-    if (carry)
-        hipLaunchKernelGGL(k_shade_carry<MODE>, dim3(GRID), dim3(256), lds, s, st, sp);
-    else if (ctx->has_catcher)
-        hipLaunchKernelGGL((k_shade<MODE, true>), dim3(GRID), dim3(256), lds, s, st, sp);
-    else
-        hipLaunchKernelGGL((k_shade<MODE, false>), dim3(GRID), dim3(256), lds, s, st, sp);
+    switch (ctx->shade_wg) {
+    case 64: launch_shade_wg<MODE, 64>(ctx, s, st, sp, carry); break;
+    case 128: launch_shade_wg<MODE, 128>(ctx, s, st, sp, carry); break;
+    default: launch_shade_wg<MODE, 256>(ctx, s, st, sp, carry); break;
+    }
 }
 
 // Closest-hit launch of a bounce chain.  The identity queue of bounce 0 holds camera rays in pixel-block order: they are traversed as
@@ -1354,7 +1386,7 @@ struct ChainPass {
     ShadeParams shade_params(QView q, QView next, QView shadow, const pt_ctx::BatchSet::StreamBuf* out, int aov, int first) const {
         ShadeParams sp{ctx->bvh.tris8, ctx->sc.d_tri_nrm, ctx->sc.d_mats, ctx->sc.d_mesh_tex, ctx->sc.d_textris, ctx->sc.d_textures, ctx->pr.dev, ctx->opt.max_depth, tmin, q, next, shadow,
                        out ? out->rayO : nullptr, out ? out->rayD : nullptr, out ? out->thr : nullptr, out ? out->rf : nullptr, aov, first,
-                       out ? out->c0 : nullptr, out ? out->c1 : nullptr, 0, 0};
+                       out ? out->c0 : nullptr, out ? out->c1 : nullptr, 0, 0, ctx->shade_lean ? 1u : 0u};
 #ifdef PT_DEBUG_STATS
         sp.dbg = ctx->dbg;
 #endif
@@ -1435,6 +1467,7 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
         // (never above trace_grid: the spill stacks are sized for trace_grid waves and the kernels are compiled for that occupancy)
         const unsigned tgrid = !mode.adapt_grid ? (unsigned)ctx->trace_grid
             : (unsigned)std::min<uint64_t>((uint64_t)ctx->trace_grid, std::max<uint64_t>((uint64_t)ctx->trace_grid_min, pass_paths / (64ull * (uint64_t)ctx->grid_chunks)));
+        const unsigned ewg = ctx->small_wg ? 64u : 256u; // workgroup of the kernels at the two ends of the pass (PT_SMALL_WG): they index by blockDim
         BatchParams bp{(mode.pixels ? mode.pixels : ctx->fb.d_pixels) + pix0, npix, s0, Sc, ctx->has_catcher ? 1 : 0, bs.pixResult, bs.pixAlpha, bs.pixNormal, bs.pixAlbedo};
         hipMemsetAsync(bs.counters, 0, sizeof(uint32_t) * counter_words(nq), bs.stream);
         ChainPass P{ctx, bs, bvh_dev(ctx), job ? job->var.cull_back_occlusion : 0, job ? job->var.radiance_tmin : 0.001f, tgrid, pass_paths,
@@ -1471,9 +1504,9 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
                 if (job)
                     hipLaunchKernelGGL(k_generate_region, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, P.tmin, (uint32_t)job->var.initial_depth, job->l0, job->nl, P.qcur);
                 else if (mode.vp.views)
-                    hipLaunchKernelGGL(k_generate_views, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0, mode.vp);
+                    hipLaunchKernelGGL(k_generate_views, dim3(GRID * (256 / ewg)), dim3(ewg), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0, mode.vp);
                 else
-                    hipLaunchKernelGGL(k_generate, dim3(GRID), dim3(256), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0);
+                    hipLaunchKernelGGL(k_generate, dim3(GRID * (256 / ewg)), dim3(ewg), 0, bs.stream, stream_view(bs, 1), fp, bp, bs.counters + 0);
             }
             hipEvent_t ev_shadow_done = nullptr; // split: behind the previous bounce's shadow rays
             std::vector<hipEvent_t> shadow_done; // async: behind every bounce's shadow rays
@@ -1548,13 +1581,13 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
             // not counted as rays — as shaded hits they are, the count is the last term of k_accum_stats' sum with count_hits = 1
             if (!fused) hipLaunchKernelGGL(k_accum_stats, dim3(1), dim3(64), 0, bs.stream, bs.counters, nq, last_bounce + 1, 1, bs.totals);
             if (job)
-                hipLaunchKernelGGL(k_resolve_region, dim3((job->nl + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, job->var, job->l0, job->nl);
+                hipLaunchKernelGGL(k_resolve_region, dim3((job->nl + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, job->var, job->l0, job->nl);
             else if (mode.moments)
-                hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp, mode.moments);
+                hipLaunchKernelGGL(k_resolve_moments, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp, mode.moments);
             else if (mode.vp.views)
-                hipLaunchKernelGGL(k_resolve_views, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp, mode.vp);
+                hipLaunchKernelGGL(k_resolve_views, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp, mode.vp);
             else
-                hipLaunchKernelGGL(k_resolve, dim3((npix + 255) / 256), dim3(256), 0, bs.stream, bs.st, fp, bp);
+                hipLaunchKernelGGL(k_resolve, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp);
         }
     }
 }

@@ -274,6 +274,7 @@ struct ShadeParams {
     int second;         // the chain's second launch: the incoming records hold the direct sums
     int last;           // the chain's last launch: every path writes its sums to direct / indirect, its shadow ray goes out with shPend (TR_SHADOW_APPLY adds it);
                         // without shadow catchers the paths it would queue are never traced: they are counted, nothing of them is stored
+    uint32_t lean;      // k_shade's LDS layout: 0 the full copy of the probe's marginal arrays, 1 without pdfY (PT_SHADE_LDS, shade_marg_words)
 #ifdef PT_DEBUG_STATS
     unsigned long long* dbg; // Trace8Args::dbg (null without PT_DEBUG_COUNTS)
 #endif
@@ -661,33 +662,44 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
 #define PT_LDS_PROBE_ROWS 2048
 #endif
 
-// the body of the shade kernels (k_shade, k_shade_carry below)
-template <int MODE, bool CATCHER, bool CARRY>
+// words of the marginal arrays in k_shade's dynamic LDS (0: they stay in global memory); the host sizes the launch with the same function.
+// Full layout: cdfY, pdfY, c8Y, c64Y.  Lean layout (ShadeParams::lean): without pdfY, which is read once per light sample, not searched.
+__host__ __device__ inline uint32_t shade_marg_words(const DevProbe& p, bool lean) {
+    if (!p.c64Y || p.height > PT_LDS_PROBE_ROWS) return 0u;
+    return (uint32_t)((lean ? 1 : 2) * p.height + p.height / 8 + ((p.ncy + 7) & ~7));
+}
+
+// the body of the shade kernels (k_shade, k_shade_carry below), for workgroups of WG threads (64, 128 or 256: launch_shade keeps
+// grid x WG constant, so the grid-stride loop gives a thread the same entries in every shape, and a wave the same 64)
+template <int MODE, bool CATCHER, bool CARRY, int WG>
 PT_DEV void shade_queue(const PathState& st, const ShadeParams& sp) {
+    static_assert(WG == 64 || WG == 128 || WG == 256, "qreader_init needs a whole wave; launch_shade scales the grid for these three");
     __shared__ uint32_t s_prefix[PT_NSUB + 1];
-    __shared__ float s_u8[256]; // textured scenes: (float)b / 255.0f for the 256 byte values (tex2d_wrap_linear)
-    extern __shared__ __attribute__((aligned(16))) float s_marg[]; // sized at launch for the probe in use (shade_lds_bytes): 8.8 KB for 1024 rows
+    // sized at launch (launch_shade): the marginal arrays of the probe in use (8.8 KB for 1024 rows, 4.7 KB lean), then, in textured scenes
+    // only, (float)b / 255.0f for the 256 byte values (tex2d_wrap_linear)
+    extern __shared__ __attribute__((aligned(16))) float s_marg[];
+    const bool lean = sp.lean != 0u;
     const float* u8lut = nullptr;
     if (sp.mesh_tex) { // ordered before its readers by the barrier of qreader_init below
-        s_u8[threadIdx.x & 255u] = (float)(threadIdx.x & 255u) / 255.0f;
+        float* s_u8 = s_marg + shade_marg_words(sp.probe, lean);
+        for (uint32_t b = threadIdx.x; b < 256u; b += WG) s_u8[b] = (float)b / 255.0f;
         u8lut = s_u8;
     }
     ProbeMarg pm = probe_marg_global(sp.probe);
     if (sp.probe.c64Y && sp.probe.height <= PT_LDS_PROBE_ROWS) {
         // ProbeSample's row search (cdfY through its 64- and 8-entry count tables) and pdfY from LDS: 3 of the 6 dependent
-        // loads of the lookup stay on the CU (hard part 3)
+        // loads of the lookup stay on the CU (hard part 3); lean: the search only, 2 of the 6
         const int h = sp.probe.height, h8 = h / 8, n64 = (sp.probe.ncy + 7) & ~7;
         float* s_cdfY = s_marg;
         float* s_pdfY = s_cdfY + h;
-        float* s_c8Y = s_pdfY + h;
+        float* s_c8Y = lean ? s_pdfY : s_pdfY + h;
         float* s_c64Y = s_c8Y + h8;
-        for (int k = threadIdx.x; k < h; k += blockDim.x) {
-            s_cdfY[k] = sp.probe.cdfY[k];
-            s_pdfY[k] = sp.probe.pdfY[k];
-        }
-        for (int k = threadIdx.x; k < h8; k += blockDim.x) s_c8Y[k] = sp.probe.c8Y[k];
-        for (int k = threadIdx.x; k < n64; k += blockDim.x) s_c64Y[k] = sp.probe.c64Y[k];
-        pm = ProbeMarg{s_cdfY, s_pdfY, s_c64Y, s_c8Y};
+        for (int k = threadIdx.x; k < h; k += WG) s_cdfY[k] = sp.probe.cdfY[k];
+        if (!lean)
+            for (int k = threadIdx.x; k < h; k += WG) s_pdfY[k] = sp.probe.pdfY[k];
+        for (int k = threadIdx.x; k < h8; k += WG) s_c8Y[k] = sp.probe.c8Y[k];
+        for (int k = threadIdx.x; k < n64; k += WG) s_c64Y[k] = sp.probe.c64Y[k];
+        pm = ProbeMarg{s_cdfY, lean ? sp.probe.pdfY : s_pdfY, s_c64Y, s_c8Y};
     }
     const uint32_t n = qreader_init(sp.queue, s_prefix); // ends in a workgroup barrier (identity queue: see below)
     if (sp.queue.base == nullptr) __syncthreads();
@@ -703,14 +715,14 @@ PT_DEV void shade_queue(const PathState& st, const ShadeParams& sp) {
     }
 }
 
-template <int MODE, bool CATCHER>
-__global__ void __launch_bounds__(256) PT_SHADE_ATTR k_shade(PathState st, ShadeParams sp) {
-    shade_queue<MODE, CATCHER, false>(st, sp);
+template <int MODE, bool CATCHER, int WG = 256>
+__global__ void __launch_bounds__(WG) PT_SHADE_ATTR k_shade(PathState st, ShadeParams sp) {
+    shade_queue<MODE, CATCHER, false, WG>(st, sp);
 }
 // the launch chain with carried sums (PT_CARRY_SUMS; scenes without shadow catchers, unified shadow placement)
-template <int MODE>
-__global__ void __launch_bounds__(256) PT_SHADE_ATTR k_shade_carry(PathState st, ShadeParams sp) {
-    shade_queue<MODE, false, true>(st, sp);
+template <int MODE, int WG = 256>
+__global__ void __launch_bounds__(WG) PT_SHADE_ATTR k_shade_carry(PathState st, ShadeParams sp) {
+    shade_queue<MODE, false, true, WG>(st, sp);
 }
 
 // ------------------------------------------------------------------ resolve
