@@ -34,7 +34,9 @@
  * cases: tests/test_gpu_exposure.py).  pt_bloom_planes takes DEVICE pointers under the same contract, too (its ordering cases:
  * tests/test_gpu_bloom.py); pt_bloom_layout touches no device memory.  pt_motion_blur_planes takes DEVICE pointers under the same contract
  * (its ordering cases: tests/test_gpu_motion_blur.py); pt_motion_blur_layout touches no device memory.  pt_dof_planes takes DEVICE pointers
- * under the same contract (its ordering cases: tests/test_gpu_dof.py); pt_dof_layout touches no device memory.
+ * under the same contract (its ordering cases: tests/test_gpu_dof.py); pt_dof_layout touches no device memory.  pt_lens_warp_planes takes
+ * DEVICE pointers under the same contract (its ordering cases: tests/test_gpu_lens_warp.py); pt_warp_matrix is host arithmetic and touches
+ * no device at all.
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -47,7 +49,8 @@
  * pt_texture_mips_layout, pt_copy_texture_mips_device, pt_surface_lod_planes, pt_surface_aniso_planes, pt_upsample_planes, pt_edge_aa_planes,
  * pt_exposure_planes, pt_tonemap_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.  pt_bloom_layout and pt_bloom_planes were added
- * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes, and pt_dof_layout and pt_dof_planes.
+ * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes, and pt_dof_layout and pt_dof_planes,
+ * and pt_lens_warp_planes and pt_warp_matrix.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -1873,6 +1876,88 @@ typedef struct pt_dof_desc {
 } pt_dof_desc;
 typedef struct pt_dof_stats { uint64_t pixels, sources, gathered, taps, nonfinite; double kernel_ms; } pt_dof_stats;
 int pt_dof_planes(pt_ctx* ctx, const pt_dof_desc* desc, pt_dof_stats* stats /* may be NULL */);
+
+/* LENS WARP AND LATE REPROJECTION (no reference counterpart).  The chain ends in a tone-mapped PINHOLE image per view, which no head-mounted
+ * display can show: its lenses bend the image, each colour a little differently, and by scan-out the head has turned.  pt_lens_warp_planes
+ * is the last pass, behind pt_tonemap_planes: per view it resamples the display colour through (a) a radial polynomial around the lens
+ * centre, with its own coefficients for red, green and blue (lens pre-distortion and chromatic-aberration correction), and (b) a 3x3
+ * matrix in the view's pixel coordinates (rotational late reprojection, "timewarp": pt_warp_matrix below builds it from two cameras).  The
+ * same pass gives a synthetic-data user a camera with radial distortion.  Both map an OUTPUT pixel to the SOURCE point its colour comes
+ * from, so the pass is a gather: three data-dependent sub-pixel positions per pixel, bilinear or Catmull-Rom.  The frame path's camera
+ * stays the reference's pinhole, as for depth of field.  Stateless like every pass here: the planes are caller-owned DEVICE memory of the
+ * context's device (4-byte aligned, frame-sized, indexed Y * width + X); block_mask and lenses are HOST memory.
+ *
+ * Rule, per pixel.  The pixel set, the views, the partitions, the pointer checks and nv = max(1, the view count) are exactly
+ * pt_modulate_planes's.  A pixel p of the set lies in rectangle (x0, y0, wr, hr) of view v at local (x, y); without views the rectangle is
+ * the frame.  Arithmetic is float32, one rounding per operation, no fused multiply-add, / correctly rounded (pt_detmath.h's contract), in
+ * this order.  For channel ch = 0, 1, 2 with (k1, k2, k3) = lenses[v].k[ch], (cx, cy) = center, (irx, iry) = inv_radius and H = warp:
+ *   1. px = (float)x + 0.5f; py = (float)y + 0.5f; qx = px - cx; qy = py - cy.
+ *   2. ax = qx * irx; ay = qy * iry; r2 = ax * ax + ay * ay; g = r2 * (k1 + r2 * (k2 + r2 * k3)).
+ *   3. ux = px + qx * g; uy = py + qy * g.  Written like this, k = 0 gives ux = px bit for bit.
+ *   4. a = (H[0]*ux + H[1]*uy) + H[2]; b = (H[3]*ux + H[4]*uy) + H[5]; c = (H[6]*ux + H[7]*uy) + H[8].
+ *   5. The channel is OUTSIDE unless c > 0.  Then sx = a / c; sy = b / c, and the channel is outside unless
+ *      sx >= 0 && sx <= (float)wr && sy >= 0 && sy <= (float)hr.  Every comparison is written so that a NaN is outside.  No float is
+ *      converted to int and no address is formed before this test has passed.
+ *   6. fx = sx - 0.5f; fy = sy - 0.5f; flx = floorf(fx); fly = floorf(fy); ix = (int)flx; iy = (int)fly; tx = fx - flx; ty = fy - fly.
+ *   7. Bilinear (no flag).  Taps are (ix + i, iy + j) for i, j in {0, 1}, each coordinate clamped to the rectangle ([0, wr - 1], [0, hr - 1]).
+ *      Weights are wx = {1.0f - tx, tx}, wy likewise, and w_ij = wx[i] * wy[j].  Channel word c_ij of color at the tap is read as 0.0f
+ *      if it is not finite (exponent-bit test); stats->nonfinite counts such words, once per channel and tap that read them.
+ *      val = ((c00*w00 + c10*w10) + c01*w01) + c11*w11.  All four taps are always read.
+ *   8. Bicubic (PT_LENS_WARP_BICUBIC, Catmull-Rom, separable).  Taps are ix - 1 .. ix + 2 by iy - 1 .. iy + 2, clamped to the rectangle.
+ *      w0 = ((-0.5f*t + 1.0f)*t - 0.5f)*t; w1 = ((1.5f*t - 2.5f)*t)*t + 1.0f; w2 = ((-1.5f*t + 2.0f)*t + 0.5f)*t; w3 = ((0.5f*t - 0.5f)*t)*t,
+ *      in x from tx (wx0 .. wx3) and in y from ty (wy0 .. wy3).  Row j: row_j = ((c0j*wx0 + c1j*wx1) + c2j*wx2) + c3j*wx3.
+ *      val = ((row0*wy0 + row1*wy1) + row2*wy2) + row3*wy3.  Non-finite words are handled as in step 7.
+ *   9. The channel's value is val, or border[ch] when outside.  out[p] = (r, g, b, all three inside ? 1.0f : 0.0f);
+ *      frame_rgba8[p] = make_color(r, g, b).  stats->outside counts pixels with .w == 0; stats->pixels is the size of the set.
+ * No tap leaves its view's rectangle.  A tap reads color wherever in the rectangle it lands, whether or not the rank owns that pixel or the
+ * mask names it: the set decides only what is written (the rule depth of field and motion blur state; the ranks of a partitioned frame
+ * all-gather the colour first).  lenses == NULL stands for k = 0 and warp = identity for every view; that, or explicit lenses with k = 0
+ * and the identity matrix, gives out.xyz equal to color.xyz (finite words) with .w = 1: steps 1 to 6 return fx == x and fy == y exactly,
+ * so tx = ty = 0 and the one tap of weight 1 is the pixel itself; the only bit that may differ is a -0 that becomes +0.  Coefficients as
+ * large as 1e6 make r2 and g overflow: the pixel comes out outside, nothing faults.  A matrix that turns the camera by more than 90
+ * degrees has c <= 0 over part of the frame: that part is border colour.  inv_radius = 0 switches the polynomial off (r2 = 0).
+ * When the three k rows of every view are equal word for word, the three channels share one source point and the library computes it once;
+ * the bits are the same.
+ *
+ * Refused with PT_ERR_INVALID (nothing enqueued, nothing written, message prefixed "pt_lens_warp_planes: "): a null ctx, desc or color, or
+ * both outputs null; no pt_resize yet; a plane that fails the pointer checks; any overlap that involves out or frame_rgba8 (out may NOT be
+ * color: the gather reads neighbours); an unknown flag bit; a non-finite border; per view: any non-finite field, inv_radius < 0, |center|
+ * or |k| above 1e6, or reserved != 0.
+ * Ordering and state, as pt_dof_planes: the call waits for the frames in flight, runs on pt_stream(ctx) under the STREAM CONTRACT, is
+ * complete when it returns, and writes no context state.
+ *
+ * pt_warp_matrix is a host function: no context, no GPU.  Cameras are eye, U, V, W as pt_set_camera takes them; the eyes are ignored, so
+ * the reprojection is rotational.  src_cam is the camera the frame was rendered with, dst_cam the camera at scan-out.  In float64, with P
+ * the matrix that maps (nx, ny) in [-1, 1]^2 to pixels (px = (nx + 1) * width / 2, likewise y):
+ *     H = P * [U V W]_src^-1 * [U' V' W']_dst * P^-1,
+ * each entry rounded to float32 once.  No rescaling and no sign change, because step 5 tests c > 0.  If the words of U, V, W of the two
+ * cameras are equal word for word the result is the identity exactly (checked first).  PT_ERR_INVALID (text in pt_last_error(NULL)) for
+ * null pointers, zero sizes, non-finite input, a source matrix whose |det| is below 1e-12 times the product of its column norms, or an
+ * entry that does not fit float32.
+ * Not part of this interface: positional reprojection with the depth plane; tangential (decentring) terms and mesh-based warps; the exact
+ * inverse of a camera-calibration model (a dataset user fits output -> source coefficients); vignette compensation; a fusion into
+ * pt_tonemap_planes's kernel; an asynchronous variant; a pt_multi_* wrapper (per-rank calls work once the colour is gathered). */
+typedef enum pt_lens_warp_flags { PT_LENS_WARP_BICUBIC = 1 } pt_lens_warp_flags;
+typedef struct pt_lens_view {       /* 96 bytes, HOST */
+    float center[2];     /* lens centre in the view's own pixel coordinates (pixel centres at +0.5) */
+    float inv_radius[2]; /* 1 / (the pixel distance at which r = 1), per axis; >= 0 */
+    float k[3][3];       /* k[channel][0..2] = k1, k2, k3 for r, g, b */
+    float warp[9];       /* row-major 3x3 in the view's pixel coordinates: output pixel -> source pixel */
+    float reserved[2];   /* 0 */
+} pt_lens_view;
+typedef struct pt_lens_warp_desc {
+    const float* color;        /* w*h x 4 (.w ignored); required */
+    float*       out;          /* w*h x 4 or NULL; exclusive (it may NOT be color: the gather reads neighbours) */
+    uint32_t*    frame_rgba8;  /* w*h or NULL; exclusive; at least one of out, frame_rgba8 */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    const pt_lens_view* lenses;/* HOST, nv entries, or NULL: k = 0 and warp = identity for every view */
+    float    border[3];        /* finite: the colour of a channel whose source point is outside */
+    uint32_t flags;            /* pt_lens_warp_flags */
+} pt_lens_warp_desc;
+typedef struct pt_lens_warp_stats { uint64_t pixels, outside, nonfinite; double kernel_ms; } pt_lens_warp_stats;
+int pt_lens_warp_planes(pt_ctx* ctx, const pt_lens_warp_desc* desc, pt_lens_warp_stats* stats /* may be NULL */);
+/* host only: out = the warp of a frame rendered under src_cam and shown under dst_cam (12 floats each: eye, U, V, W) */
+int pt_warp_matrix(const float src_cam[12], const float dst_cam[12], uint32_t width, uint32_t height, float out[9]);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

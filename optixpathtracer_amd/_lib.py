@@ -31,7 +31,7 @@ EXPORTS = [
     "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes", "pt_surface_aniso_planes",
     "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes", "pt_bloom_layout", "pt_bloom_planes",
     "pt_motion_blur_layout", "pt_motion_blur_planes",
-    "pt_dof_layout", "pt_dof_planes",
+    "pt_dof_layout", "pt_dof_planes", "pt_lens_warp_planes", "pt_warp_matrix",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -334,6 +334,31 @@ class DofStats(C.Structure):  # pt_dof_stats
 # the frame-sized planes of pt_dof_planes: 32-bit words per pixel (the scratch, T and N of every view, is pt_dof_layout's)
 DOF_PLANES = {"color": 4, "depth": 1, "out": 4}
 DOF_OUTPUTS = ("out",)
+
+
+PT_LENS_WARP_BICUBIC = 1  # pt_lens_warp_flags
+
+
+class LensView(C.Structure):  # pt_lens_view
+    _fields_ = [("center", C.c_float * 2), ("inv_radius", C.c_float * 2), ("k", (C.c_float * 3) * 3), ("warp", C.c_float * 9),
+                ("reserved", C.c_float * 2)]
+
+
+class LensWarpDesc(C.Structure):  # pt_lens_warp_desc
+    _fields_ = [("color", C.c_void_p), ("out", C.c_void_p), ("frame_rgba8", C.c_void_p), ("block_mask", C.c_void_p), ("lenses", C.c_void_p),
+                ("border", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+class LensWarpStats(C.Structure):  # pt_lens_warp_stats
+    _fields_ = [("pixels", C.c_uint64), ("outside", C.c_uint64), ("nonfinite", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the planes of pt_lens_warp_planes: 32-bit words per pixel (frame_rgba8 holds packed bytes, the others float32)
+LENS_WARP_PLANES = {"color": 4, "out": 4, "frame_rgba8": 1}
+LENS_WARP_OUTPUTS = ("out", "frame_rgba8")
 
 
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
@@ -640,6 +665,8 @@ def load_library() -> C.CDLL:
     L.pt_motion_blur_planes.argtypes = [vp, C.POINTER(MotionBlurDesc), C.POINTER(MotionBlurStats)]
     L.pt_dof_layout.argtypes = [vp, vp, C.POINTER(C.c_size_t)]
     L.pt_dof_planes.argtypes = [vp, C.POINTER(DofDesc), C.POINTER(DofStats)]
+    L.pt_lens_warp_planes.argtypes = [vp, C.POINTER(LensWarpDesc), C.POINTER(LensWarpStats)]
+    L.pt_warp_matrix.argtypes = [vp, vp, u32, u32, vp]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

@@ -483,6 +483,22 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // Lens pre-distortion, chromatic-aberration correction and rotational late reprojection, the last pass of the chain, behind the tone
+    // mapper (pt_lens_warp_planes): per view and colour channel a radial polynomial around the lens centre, then a 3x3 matrix in pixel
+    // coordinates (warpMatrix), name the source point that d.color is resampled at, into d.out and / or d.frame_rgba8, neither of which
+    // may be d.color.  d.lenses is HOST memory, one pt_lens_view per view, or null.  Returns the pixels written, those with a channel
+    // outside its rectangle, the non-finite words read as 0, and the device time.
+    pt_lens_warp_stats lensWarpPlanes(const pt_lens_warp_desc& d, pt_lens_warp_stats* stats = nullptr) {
+        pt_lens_warp_stats s{};
+        ck(pt_lens_warp_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
+    // lensWarpPlanes's matrix of a camera turn (pt_warp_matrix, host only): out maps a pixel under dst_cam to the pixel of the frame
+    // rendered under src_cam (12 floats each: eye, U, V, W); the eyes are ignored.
+    static void warpMatrix(const float src_cam[12], const float dst_cam[12], uint32_t width, uint32_t height, float out[9]) {
+        if (pt_warp_matrix(src_cam, dst_cam, width, height, out) != PT_OK) throw std::runtime_error(pt_last_error(nullptr));
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

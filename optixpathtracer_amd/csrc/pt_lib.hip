@@ -40,3 +40,4 @@
 #include "pt_bloom.hip"
 #include "pt_motion_blur.hip"
 #include "pt_dof.hip"
+#include "pt_lens_warp.hip"

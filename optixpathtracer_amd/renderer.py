@@ -1125,6 +1125,43 @@ class SampleRenderer:
         desc.taps, desc.seed, desc.flags = taps, seed, _lib.PT_DOF_JITTER if jitter else 0
         return self._run_pass("pt_dof_planes", desc, _lib.DofStats(), result)
 
+    def lensWarpPlanes(self, color, out=None, frame=None, mask=None, lenses=None, border=(0.0, 0.0, 0.0), bicubic=False) -> dict:
+        """The last pass of the chain, behind tonemapPlanes: lens pre-distortion with per-channel coefficients (chromatic-aberration
+        correction) and rotational late reprojection for a head-mounted display, or radial distortion for a synthetic camera
+        (pt_lens_warp_planes, include/pt_amd.h: the rule, in full).  Each output pixel finds, per colour channel, the source point of its
+        view's lens (make_lens: a radial polynomial around the lens centre, then a 3x3 matrix in pixel coordinates, e.g. warpMatrix's) and
+        resamples `color` there, bilinear or (bicubic=True) Catmull-Rom; a channel whose source point lies outside the view's rectangle
+        takes `border`.
+
+        color (h, w, 4) is a CUDA float32 tensor on the context's device — dense, any 4-byte-aligned storage offset — or a raw device
+        pointer.  out (h, w, 4; .w is 1 where all three channels were inside, else 0) and frame (int32 (h, w) or uint8 (h, w, 4)) are
+        optional; out is allocated with torch, zero-filled, when neither is given; neither may be `color` (the pass reads neighbours).
+        lenses: one pt_lens_view per view (max(1, the view count) of them: make_lens's, or anything np.asarray turns into (views, 24)
+        float32), None: no distortion and the identity matrix.  A tap reads `color` wherever in its view's rectangle it lands; the mask
+        and the rank's partition decide only which pixels are written.  mask: 8x8 blocks as renderMask takes them, None = every block.
+        Ordering is on the device, as temporalMoments.  Returns {"out", "frame_rgba8": the tensor (None for a raw pointer or an absent
+        plane), "stats": {pixels, outside, nonfinite, kernel_ms}}."""
+        given = dict(color=color, out=out, frame_rgba8=frame)
+        desc = _lib.LensWarpDesc()
+        result = self._bind_planes("lensWarpPlanes", desc, given, _lib.LENS_WARP_PLANES, ("color",), _lib.LENS_WARP_OUTPUTS,
+                                   alloc=("out",) if frame is None else ())
+        table = None
+        if lenses is not None:
+            if isinstance(lenses, _lib.LensView):
+                lenses = [lenses]
+            rows = [np.frombuffer(bytes(v), np.float32) if isinstance(v, _lib.LensView) else np.asarray(v, np.float32).reshape(-1) for v in lenses]
+            if len(rows) != self._view_count() or any(r.size != 24 for r in rows):
+                raise ValueError(f"lensWarpPlanes: lenses must be {self._view_count()} records of 24 floats (one pt_lens_view per view)")
+            table = np.ascontiguousarray(np.stack(rows), np.float32)
+            desc.lenses = table.ctypes.data  # (table is kept until the call has returned)
+        border = tuple(float(b) for b in border)
+        if len(border) != 3:
+            raise ValueError("lensWarpPlanes: border must be three floats")
+        desc.border[0], desc.border[1], desc.border[2] = border
+        m = self._bind_mask("lensWarpPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.flags = _lib.PT_LENS_WARP_BICUBIC if bicubic else 0
+        return self._run_pass("pt_lens_warp_planes", desc, _lib.LensWarpStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
@@ -1573,3 +1610,45 @@ class MultiRenderer:
 
 def make_camera(cam: dict, aspect: float) -> Camera:
     return Camera(cam["eye"], cam["lookat"], cam["up"], cam["fovY"], aspect)
+
+
+def warpMatrix(src_cam, dst_cam, size) -> np.ndarray:
+    """The 3x3 matrix (row-major (9,) float32, output pixel -> source pixel of a size = (width, height) rectangle) that shows a frame
+    rendered under src_cam as dst_cam sees it, for a pt_lens_view's `warp` (pt_warp_matrix, include/pt_amd.h).  Each camera is a Camera
+    or a (12,) row eye, U, V, W; the eyes are ignored: the reprojection is rotational.  Host arithmetic, no GPU."""
+    rows = [_camera_rows([c])[0] if isinstance(c, Camera) else np.ascontiguousarray(c, np.float32).reshape(-1) for c in (src_cam, dst_cam)]
+    if any(r.size != 12 for r in rows):
+        raise ValueError("warpMatrix: a Camera or 12 floats (eye, U, V, W) is expected per camera")
+    out = np.zeros(9, np.float32)
+    L = _lib.load_library()
+    if L.pt_warp_matrix(rows[0].ctypes.data, rows[1].ctypes.data, int(size[0]), int(size[1]), out.ctypes.data):
+        raise RuntimeError(L.pt_last_error(None).decode())
+    return out
+
+
+def make_lens(size, k=(0.0, 0.0, 0.0), center=None, radius=None, warp=None) -> "_lib.LensView":
+    """A pt_lens_view for a view's rectangle of size = (width, height).  k: (k1, k2, k3) for all three channels, or three such rows for
+    red, green and blue.  center: the lens centre in the rectangle's pixel coordinates (default: its middle).  radius: the pixel distance at
+    which r = 1, one number or one per axis (default: half the width, on both axes); 0 or inf switches the polynomial off.  warp: a 3x3
+    matrix in pixel coordinates, output pixel -> source pixel (warpMatrix's; default: the identity)."""
+    w, h = float(size[0]), float(size[1])
+    kk = np.asarray(k, np.float32)
+    if kk.shape == (3,):
+        kk = np.stack([kk] * 3)
+    if kk.shape != (3, 3):
+        raise ValueError("make_lens: k is (k1, k2, k3) or three such rows (red, green, blue)")
+    cx, cy = (0.5 * w, 0.5 * h) if center is None else (float(center[0]), float(center[1]))
+    rad = (0.5 * w, 0.5 * w) if radius is None else (float(radius), float(radius)) if np.ndim(radius) == 0 else (float(radius[0]), float(radius[1]))
+    H = np.eye(3, dtype=np.float32).reshape(-1) if warp is None else np.asarray(warp, np.float32).reshape(-1)
+    if H.size != 9:
+        raise ValueError("make_lens: warp is a 3x3 matrix")
+    v = _lib.LensView()
+    v.center[0], v.center[1] = cx, cy
+    for a in (0, 1):
+        v.inv_radius[a] = 0.0 if rad[a] == 0.0 else float(np.float32(1.0) / np.float32(rad[a]))
+    for ch in range(3):
+        for j in range(3):
+            v.k[ch][j] = float(kk[ch, j])
+    for j in range(9):
+        v.warp[j] = float(H[j])
+    return v
