@@ -33,9 +33,15 @@ Per frame, on `hi`:
      that bright out-of-focus points bloom as discs): step 7's G-buffer also writes depth, and dofPlanes gathers each pixel over a disc of
      the largest blur circle around it, K * |1 - F / depth| pixels, with N taps.  With --autofocus F follows the depth under the frame's
      centre, smoothed over frames (one float read back per frame); on a miss it returns to --focus.
+ 17. with --ao [--ao-rays N --ao-radius R], between steps 10 and 11: step 8's G-buffer also writes motion, and aoPlanes shoots N short
+     any-hit rays a pixel through `hi`'s tree, jittered by the frame index — the contact shadows that are smaller than a low-resolution
+     pixel and so never arrive through step 10.  The occlusion is a colour (ao, ao, ao, 1): temporalAccumulate and filterPlanes treat it
+     as they treat one, and modulatePlanes multiplies it into the upsampled irradiance, before the albedo.  (modulatePlanes reads a
+     factor of exactly 0 as 1, its rule for a miss's albedo, so the filtered occlusion is kept above 2^-10.)
 `hi` never renders a colour sample.
 
   python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa]
+                                          [--ao] [--ao-rays N] [--ao-radius R]
                                           [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
                                           [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N]
                                           [--dof] [--focus F | --autofocus] [--aperture K] [--dof-taps N] [--out-dir .]
@@ -84,9 +90,11 @@ class UpsampledLoop:
 
     def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
                  edge_aa=False, auto_exposure=False, tonemap="aces", bloom=False, bloom_threshold=1.0, bloom_levels=6,
-                 motion_blur=False, shutter=0.5, blur_taps=12, dof=False, focus=4.0, autofocus=False, aperture=6.0, dof_taps=32):
+                 motion_blur=False, shutter=0.5, blur_taps=12, dof=False, focus=4.0, autofocus=False, aperture=6.0, dof_taps=32,
+                 ao=False, ao_rays=4, ao_radius=0.5):
         import torch
 
+        self.ao, self.ao_prm = bool(ao), dict(rays=int(ao_rays), radius=float(ao_radius))
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
         self.size, self.scale, self.lod, self.aniso = tuple(size), int(scale), lod, int(aniso)
         self.edge_aa = bool(edge_aa)
@@ -134,6 +142,14 @@ class UpsampledLoop:
         # step 16's output and its scratch (tile and neighbourhood maxima of the blur radius)
         self.lens = planes(h, w, 4) if self.dof else None
         self.discs = torch.zeros((self.hi.dofLayout()[1] // 4,), device="cuda:0") if self.dof else None
+        # step 17: the G-buffer ping-pongs (the reprojection needs last frame's hit and position) and carries motion; the raw, the
+        # accumulated and the filtered occlusion, the batch of rays, and the irradiance with the occlusion in it
+        if self.ao:
+            self.hi_gbufs = [dict(self.hi_gbuf, motion=self.hi_gbuf.get("motion", planes(h, w, 2))),
+                             dict({n: torch.zeros_like(t) for n, t in self.hi_gbuf.items()}, motion=planes(h, w, 2))]
+            self.ao_raw, self.ao_filtered, self.ao_scratch, self.shaded = (planes(h, w, 4) for _ in range(4))
+            self.ao_history, self.ao_length = [planes(h, w, 4) for _ in range(2)], [planes(h, w, 1) for _ in range(2)]
+            self.ao_batch = torch.zeros((self.hi.aoLayout(self.ao_prm["rays"]) // 4,), device="cuda:0")
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
         self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
@@ -168,7 +184,10 @@ class UpsampledLoop:
         t1 = time.perf_counter()
         # ---- the display resolution: geometry, texture detail, the guided upsample, the product
         hi.setCamera(cam)
-        if self.motion_blur:
+        if self.ao:
+            self.hi_gbuf, hi_old = self.hi_gbufs[i], self.hi_gbufs[o]
+            G = hi.renderGBuffer(tuple(self.hi_gbuf), prev_cameras=prev, out=self.hi_gbuf)["stats"]
+        elif self.motion_blur:
             G = hi.renderGBuffer(("hit", "position", "depth", "motion"), prev_cameras=prev, out=self.hi_gbuf)["stats"]
         elif self.dof:
             G = hi.renderGBuffer(("hit", "position", "depth"), out=self.hi_gbuf)["stats"]
@@ -177,13 +196,28 @@ class UpsampledLoop:
         S = self._albedo(hi, self.hi_gbuf["hit"], self.albedo)
         u = hi.upsamplePlanes(self.filtered, cur["hit"], cur["position"], self.hi_gbuf["hit"], self.hi_gbuf["position"], self.scale, out=self.upsampled,
                               weight_out=self.weight)["stats"]
+        irradiance = self.upsampled
+        if self.ao:
+            hg = self.hi_gbuf
+            a = hi.aoPlanes(hg["hit"], hg["position"], out=self.ao_raw, scratch=self.ao_batch, jitter=True, seed=k, **self.ao_prm)["stats"]
+            ta = hi.temporalAccumulate(self.ao_raw, hg["motion"], hg["hit"], hg["position"], hi_old["hit"], hi_old["position"], self.ao_history[i],
+                                       self.ao_length[i], history_out=self.ao_history[o], length_out=self.ao_length[o], max_history=self.max_history)["stats"]
+            fa = hi.filterPlanes(self.ao_history[o], hg["hit"], hg["position"], length=self.ao_length[o], out=self.ao_filtered, scratch=self.ao_scratch,
+                                 iterations=3, sigma_lum=self.filter["sigma_lum"], min_length=self.filter["min_length"])["stats"]
+            self.ao_filtered[..., 0:3].clamp_(min=2.0 ** -10)  # (modulatePlanes reads a factor of 0 as 1)
+            ma = hi.modulatePlanes(self.upsampled, albedo=self.ao_filtered, out=self.shaded)["stats"]
+            irradiance = self.shaded
+            ao = dict(ao_ms=a["kernel_ms"], ao_trace_ms=a["trace_ms"], ao_rays=a["rays"], ao_occluded=a["occluded"], ao_batches=a["batches"],
+                      ao_chain_ms=ta["kernel_ms"] + fa["kernel_ms"] + ma["kernel_ms"])
+        else:
+            ao = dict(ao_ms=0.0, ao_trace_ms=0.0, ao_rays=0, ao_occluded=0, ao_batches=0, ao_chain_ms=0.0)
         # with auto exposure, depth of field, bloom or motion blur the tone mapper writes the displayed frame
         shown = None if self.auto_exposure or self.dof or self.bloom or self.motion_blur else self.frame_rgba8
         if self.edge_aa:
-            m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.modulated)["stats"]
+            m = hi.modulatePlanes(irradiance, albedo=self.albedo, out=self.modulated)["stats"]
             e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=shown)["stats"]
         else:
-            m = hi.modulatePlanes(self.upsampled, albedo=self.albedo, out=self.final, frame=shown)["stats"]
+            m = hi.modulatePlanes(irradiance, albedo=self.albedo, out=self.final, frame=shown)["stats"]
             e = dict(kernel_ms=0.0, boundary=0, blended=0)
         lit = self.final
         if self.dof:
@@ -223,7 +257,7 @@ class UpsampledLoop:
                     blended=e["blended"], exposure_ms=x["kernel_ms"], tonemap_ms=tm["kernel_ms"], ev=ev, skipped=x["skipped"], under=x["under"],
                     over=x["over"], clipped=tm["clipped"], bloom_ms=b["kernel_ms"], bright=b["bright"],
                     motion_blur_ms=mb["kernel_ms"], moving=mb["moving"], dof_ms=df["kernel_ms"], gathered=df["gathered"],
-                    focus=self.focus_now[0] if self.dof else 0.0)
+                    focus=self.focus_now[0] if self.dof else 0.0, **ao)
 
     def close(self):
         self.lo.close()
@@ -253,6 +287,9 @@ def main(argv=None):
     ap.add_argument("--autofocus", action="store_true", help="with --dof: focus on the depth under the frame's centre, smoothed over frames")
     ap.add_argument("--aperture", type=float, default=6.0, metavar="K", help="with --dof: the blur-circle radius in pixels of a point at infinity")
     ap.add_argument("--dof-taps", type=int, default=32, metavar="N", help="with --dof: taps per pixel (1..64)")
+    ap.add_argument("--ao", action="store_true", help="ray-traced ambient occlusion (aoPlanes) at the display resolution, multiplied into the upsampled irradiance")
+    ap.add_argument("--ao-rays", type=int, default=4, metavar="N", help="with --ao: rays per pixel and frame (1..32)")
+    ap.add_argument("--ao-radius", type=float, default=0.5, metavar="R", help="with --ao: the rays' length, world units")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
@@ -260,7 +297,8 @@ def main(argv=None):
     loop = UpsampledLoop(make(), (w, h), args.scale, lod=args.lod, aniso=args.aniso, spp=args.spp, edge_aa=args.edge_aa,
                          auto_exposure=args.auto_exposure, tonemap=args.tonemap, bloom=args.bloom, bloom_threshold=args.bloom_threshold,
                          bloom_levels=args.bloom_levels, motion_blur=args.motion_blur, shutter=args.shutter, blur_taps=args.blur_taps,
-                         dof=args.dof, focus=args.focus, autofocus=args.autofocus, aperture=args.aperture, dof_taps=args.dof_taps)
+                         dof=args.dof, focus=args.focus, autofocus=args.autofocus, aperture=args.aperture, dof_taps=args.dof_taps,
+                         ao=args.ao, ao_rays=args.ao_rays, ao_radius=args.ao_radius)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -270,6 +308,8 @@ def main(argv=None):
               f"temporal {x['temporal_ms']:.3f} ms, carry {x['carry_ms']:.3f} ms, filter {x['filter_ms']:.3f} ms; at {w} x {h}: G-buffer "
               f"{x['gbuffer_ms']:.3f} ms, surface {x['surface_ms']:.3f} ms, upsample {x['upsample_ms']:.3f} ms, modulate {x['modulate_ms']:.3f} ms; "
               f"of {x['pixels']} pixels full {x['full']} rescued {x['rescued']} orphans {x['orphans']}; "
+              + (f"occlusion {x['ao_ms']:.3f} ms (traversal {x['ao_trace_ms']:.3f} ms, {x['ao_occluded']} of {x['ao_rays']} rays occluded, {x['ao_batches']} batches), "
+                 f"its accumulation, filter and product {x['ao_chain_ms']:.3f} ms; " if loop.ao else "")
               + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
               + (f"depth of field {x['dof_ms']:.3f} ms ({x['gathered']} pixels gather, focus {x['focus']:.3f}); " if loop.dof else "")
               + (f"bloom {x['bloom_ms']:.3f} ms ({x['bright']} bright pixels); " if loop.bloom else "")
@@ -283,6 +323,8 @@ def main(argv=None):
         np.save(os.path.join(args.out_dir, "upsampled_svgf_blurred.npy"), loop.blurred.cpu().numpy())
     if loop.dof:
         np.save(os.path.join(args.out_dir, "upsampled_svgf_dof.npy"), loop.lens.cpu().numpy())
+    if loop.ao:
+        np.save(os.path.join(args.out_dir, "upsampled_svgf_ao.npy"), loop.ao_filtered.cpu().numpy())
     print(f"wrote upsampled_svgf_final.npy and upsampled_svgf_frame.npy to {args.out_dir}")
     loop.close()
     return 0

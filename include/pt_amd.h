@@ -36,7 +36,8 @@
  * (its ordering cases: tests/test_gpu_motion_blur.py); pt_motion_blur_layout touches no device memory.  pt_dof_planes takes DEVICE pointers
  * under the same contract (its ordering cases: tests/test_gpu_dof.py); pt_dof_layout touches no device memory.  pt_lens_warp_planes takes
  * DEVICE pointers under the same contract (its ordering cases: tests/test_gpu_lens_warp.py); pt_warp_matrix is host arithmetic and touches
- * no device at all.
+ * no device at all.  pt_ao_planes takes DEVICE pointers under the same contract (its ordering case: tests/test_gpu_ao.py); pt_ao_layout
+ * touches no device memory.
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -50,7 +51,7 @@
  * pt_exposure_planes, pt_tonemap_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.  pt_bloom_layout and pt_bloom_planes were added
  * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes, and pt_dof_layout and pt_dof_planes,
- * and pt_lens_warp_planes and pt_warp_matrix.
+ * and pt_lens_warp_planes and pt_warp_matrix, and pt_ao_layout and pt_ao_planes.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -1958,6 +1959,89 @@ typedef struct pt_lens_warp_stats { uint64_t pixels, outside, nonfinite; double 
 int pt_lens_warp_planes(pt_ctx* ctx, const pt_lens_warp_desc* desc, pt_lens_warp_stats* stats /* may be NULL */);
 /* host only: out = the warp of a frame rendered under src_cam and shown under dst_cam (12 floats each: eye, U, V, W) */
 int pt_warp_matrix(const float src_cam[12], const float dst_cam[12], uint32_t width, uint32_t height, float out[9]);
+
+/* AMBIENT OCCLUSION FROM THE G-BUFFER (no reference counterpart).  Every other pass of the chain is an image filter; this one asks the
+ * acceleration structure a new question.  Per pixel of a hit it shoots `rays` short any-hit rays over the cosine-weighted hemisphere around
+ * the geometric normal, through the context's CURRENT tree (it follows pt_update_meshes* and pt_transform_meshes), and writes the open
+ * fraction.  It is what a caller could build from pt_trace_device(PT_QUERY_ANY) — occ_k below is by definition that call's answer — without
+ * 32 bytes a ray in and 4 out through the caller's memory, a second staging, a validation kernel over rays the library built itself, an
+ * attribute kernel, and an unbounded ray buffer: the rays are built in registers from the hit plane, traced in bounded batches and reduced
+ * per pixel.  In the upsampled loop (examples/upsampled_svgf_loop.py --ao) the full-size context computes it, so contact shadows smaller than
+ * a low-resolution pixel reach the display; a dataset user gets an occlusion AOV.  Stateless like every pass here: the planes and the scratch
+ * are caller-owned DEVICE memory of the context's device (the planes 4-byte aligned, frame-sized, indexed Y * width + X; the scratch 16-byte
+ * aligned); block_mask is HOST memory.
+ *
+ * The pixel set is pt_edge_aa_planes's: the pixels a pt_render_mask with the same mask would render — the rank's owned pixels, view pixels
+ * only while views are set, whole blocks of block_mask.  The pass reads hit and position of this frame's pt_render_gbuffer, the cameras of the
+ * context (for the eye of the pixel's view) and the current tree.  It reads no vertices: the normal is pt_hit.ng, and no address is formed
+ * from prim, which is looked at for its sign only (a stale prim >= the triangle count is processed like any other hit).
+ *
+ * Rule.  Float32 throughout, one rounding per operation, no fused multiply-add, sqrtf and / correctly rounded (pt_detmath.h's contract), with
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, normalize3(v) = v * (1 / sqrt(dot3(v, v))) as in pt_render_gbuffer's text, sel_max0(v) = v > 0
+ * ? v : 0 as in pt_filter_planes's, and "finite" the exponent-bit test (exponent bits not all ones).  Per pixel p of the set, with LOCAL
+ * coordinates (x, y) in its rectangle and E the eye of p's camera (the frame's, or with views the one of p's view):
+ *   1. h = hit[p].  If h.prim < 0 (a miss): ao = 1.0f, out = (1, 1, 1, 1), bent = (0, 0, 0, 1); stats->skipped counts it; it shoots no ray.
+ *   2. P = position[p].xyz, n0 = h.ng, t = h.t.  If one of those seven words is not finite, or t > 0 is false: the same outputs as a miss;
+ *      stats->nonfinite counts it; it shoots no ray.
+ *   3. Face the viewer: s = dot3(n0, E - P); n = (s < 0) ? -n0 : n0.
+ *   4. The frame, branch-free but for the sign, no transcendental:
+ *        sg = (n.z >= 0) ? 1.0f : -1.0f;  a = -1.0f / (sg + n.z);  b = (n.x * n.y) * a;
+ *        T = (1.0f + (sg * (n.x * n.x)) * a,  sg * b,  (-sg) * n.x);   B = (b,  sg + (n.y * n.y) * a,  -n.y).
+ *   5. The origin: O = P + n * (bias * t) per component, the product first and then the sum.
+ *   6. For sample k = 0 .. rays - 1, a cosine-weighted direction from depth of field's spiral (no table and no constant of its own):
+ *        rho_k = sqrtf(((float)k + 0.5f) / (float)rays);  Dk = D[(k + k0) & 127], D being pt_dof_planes's recurrence; k0 = 0 without
+ *        PT_AO_JITTER, with it k0 = h & 63 where h is pt_dof_planes's hash of the LOCAL coordinates (x, y) and seed;
+ *        a_k = rho_k * Dk.x;  b_k = rho_k * Dk.y;  c_k = sqrtf(sel_max0(1.0f - (a_k*a_k + b_k*b_k)));
+ *        w = ((T * a_k) + (B * b_k)) + (n * c_k) per component;  d_k = normalize3(w).
+ *      The ray is (O, tmin = 0.0f, d_k, tmax = radius), in pt_trace_device's eight words.
+ *   7. The ray is tested with pt_trace_device's validity rule: the eight words finite, dot3(d_k, d_k) and 1.0f / dot3(d_k, d_k) finite and not
+ *      zero.  An invalid ray is not traced; it counts as unoccluded, and stats->invalid counts it.
+ *   8. occ_k is exactly what pt_trace_device(PT_QUERY_ANY) returns for that ray over the current geometry (1 occluded, 0 not).  Back faces
+ *      count.
+ *   9. open = the number of rays with occ_k == 0 (the invalid ones included);  ao = (float)open / (float)rays;
+ *      bent.xyz = S / (float)rays per component, where S starts at +0 and adds d_k per component, for k ascending, over the unoccluded VALID
+ *      rays only (the mean unoccluded direction, not normalised);  bent.w = ao;  out = (ao, ao, ao, 1.0f).
+ * stats->pixels is the size of the set; traced the pixels that passed steps 1 and 2 (pixels = skipped + nonfinite + traced); rays the rays
+ * traced (traced * rays - invalid); occluded those with occ_k == 1.
+ *
+ * Batches and scratch.  The pixel list is cut into batches of floor(M / rays) pixels, M = max_rays_in_flight or, when that is 0,
+ * PT_AO_DEFAULT_RAYS_IN_FLIGHT.  For each batch, in stream order, the pass generates the rays, traces them (the traversal kernel and grid
+ * of pt_trace_device) and reduces them; stats->batches says how many ran.  The scratch holds ONE batch — a 256-byte head (the traversal's
+ * count word, its work counter, the fault word, zeroed by the call), then per ray slot an origin and a direction of 16 bytes and a record of
+ * 8, then 8 bytes per batch pixel — and nothing per frame pixel.  pt_ao_layout returns its size for min(floor(M / rays), frame pixels) pixels
+ * a batch: 256 + pixels * (40 * rays + 8), rounded up to 16.  The result does not depend on M, bit for bit.
+ *
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; hit, position
+ * or scratch NULL; ao, out and bent all NULL; a plane that fails the pointer checks; a written plane or the scratch overlapping anything;
+ * a scratch that is not 16-byte aligned or smaller than the layout; rays outside 1 .. PT_AO_MAX_RAYS; max_rays_in_flight non-zero and below
+ * rays; radius not finite or not > 0; bias negative or not finite; an unknown flag bit.  The traversal's stack-overflow bit gives
+ * PT_ERR_UNSUPPORTED, as in pt_trace.
+ * Ordering and state, as pt_render_gbuffer: the call waits for the frames in flight and completes queued queries (their counts stay for
+ * pt_query_wait), runs on pt_stream(ctx) under the STREAM CONTRACT, is complete when it returns, and touches neither the context's query
+ * state, nor the frame buffers, nor pt_stats.  For zero pixels it launches nothing and returns PT_OK.
+ * Not part of this interface: distance-weighted occlusion; a shading normal; reflections or shadows towards the probe; an asynchronous
+ * variant; a pt_multi_* wrapper (per-rank calls work: each rank traces the whole tree for its own pixels). */
+#define PT_AO_MAX_RAYS 32
+#define PT_AO_DEFAULT_RAYS_IN_FLIGHT 8388608u /* 2^23 rays: 336 MB of ray slots and 8 bytes a batch pixel, or the frame's if that is less */
+typedef enum pt_ao_flags { PT_AO_JITTER = 1 } pt_ao_flags;
+typedef struct pt_ao_desc {
+    const void*  hit;          /* w*h x pt_hit, required */
+    const float* position;     /* w*h x 4, required */
+    float* ao;                 /* w*h      or NULL, exclusive */
+    float* out;                /* w*h x 4  or NULL, exclusive: (ao, ao, ao, 1.0f) — what pt_modulate_planes / the filters take as a colour */
+    float* bent;               /* w*h x 4  or NULL, exclusive: mean unoccluded direction (not normalised), .w = ao */
+    void*  scratch;            /* pt_ao_layout's bytes, 16-byte aligned, required, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    uint32_t rays;             /* 1 .. PT_AO_MAX_RAYS per pixel */
+    uint32_t max_rays_in_flight; /* 0 = PT_AO_DEFAULT_RAYS_IN_FLIGHT; else >= rays: bounds the scratch */
+    float radius;              /* finite, > 0: the rays' tmax, world units */
+    float bias;                /* finite, >= 0: the origin is lifted by bias * hit.t along the normal */
+    uint32_t seed;             /* PT_AO_JITTER: e.g. the frame index */
+    uint32_t flags;            /* pt_ao_flags */
+} pt_ao_desc;
+typedef struct pt_ao_stats { uint64_t pixels, traced, skipped, nonfinite, rays, occluded, invalid, batches; double kernel_ms, trace_ms; } pt_ao_stats;
+int pt_ao_layout(const pt_ctx* ctx, uint32_t rays, uint32_t max_rays_in_flight, size_t* bytes);
+int pt_ao_planes(pt_ctx* ctx, const pt_ao_desc* desc, pt_ao_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

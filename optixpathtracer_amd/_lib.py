@@ -31,7 +31,7 @@ EXPORTS = [
     "pt_texture_mips_layout", "pt_copy_texture_mips_device", "pt_surface_lod_planes", "pt_surface_aniso_planes",
     "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes", "pt_bloom_layout", "pt_bloom_planes",
     "pt_motion_blur_layout", "pt_motion_blur_planes",
-    "pt_dof_layout", "pt_dof_planes", "pt_lens_warp_planes", "pt_warp_matrix",
+    "pt_dof_layout", "pt_dof_planes", "pt_lens_warp_planes", "pt_warp_matrix", "pt_ao_layout", "pt_ao_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -361,6 +361,30 @@ LENS_WARP_PLANES = {"color": 4, "out": 4, "frame_rgba8": 1}
 LENS_WARP_OUTPUTS = ("out", "frame_rgba8")
 
 
+PT_AO_MAX_RAYS = 32
+PT_AO_DEFAULT_RAYS_IN_FLIGHT = 1 << 23
+PT_AO_JITTER = 1  # pt_ao_flags
+
+
+class AoDesc(C.Structure):  # pt_ao_desc
+    _fields_ = [("hit", C.c_void_p), ("position", C.c_void_p), ("ao", C.c_void_p), ("out", C.c_void_p), ("bent", C.c_void_p),
+                ("scratch", C.c_void_p), ("block_mask", C.c_void_p), ("rays", C.c_uint32), ("max_rays_in_flight", C.c_uint32),
+                ("radius", C.c_float), ("bias", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class AoStats(C.Structure):  # pt_ao_stats
+    _fields_ = [("pixels", C.c_uint64), ("traced", C.c_uint64), ("skipped", C.c_uint64), ("nonfinite", C.c_uint64), ("rays", C.c_uint64),
+                ("occluded", C.c_uint64), ("invalid", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double), ("trace_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the frame-sized planes of pt_ao_planes: 32-bit words per pixel (the scratch, one batch of rays, is pt_ao_layout's)
+AO_PLANES = {"hit": 8, "position": 4, "ao": 1, "out": 4, "bent": 4}
+AO_OUTPUTS = ("ao", "out", "bent")
+
+
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
 
 
@@ -667,6 +691,8 @@ def load_library() -> C.CDLL:
     L.pt_dof_planes.argtypes = [vp, C.POINTER(DofDesc), C.POINTER(DofStats)]
     L.pt_lens_warp_planes.argtypes = [vp, C.POINTER(LensWarpDesc), C.POINTER(LensWarpStats)]
     L.pt_warp_matrix.argtypes = [vp, vp, u32, u32, vp]
+    L.pt_ao_layout.argtypes = [vp, u32, u32, C.POINTER(C.c_size_t)]
+    L.pt_ao_planes.argtypes = [vp, C.POINTER(AoDesc), C.POINTER(AoStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

@@ -499,6 +499,22 @@ class SampleRenderer {
     static void warpMatrix(const float src_cam[12], const float dst_cam[12], uint32_t width, uint32_t height, float out[9]) {
         if (pt_warp_matrix(src_cam, dst_cam, width, height, out) != PT_OK) throw std::runtime_error(pt_last_error(nullptr));
     }
+    // The size in bytes of aoPlanes's scratch: one batch of rays (pt_ao_layout); max_rays_in_flight 0 is the library's default.
+    size_t aoLayout(uint32_t rays, uint32_t max_rays_in_flight = 0) {
+        size_t bytes = 0;
+        ck(pt_ao_layout(ctx, rays, max_rays_in_flight, &bytes));
+        return bytes;
+    }
+    // Ray-traced ambient occlusion from the G-buffer (pt_ao_planes): every pixel of a hit in d.hit shoots d.rays any-hit rays of length
+    // d.radius over the cosine-weighted hemisphere around its geometric normal, through the current tree, into d.ao, d.out (ao as a colour)
+    // and / or d.bent; d.scratch is aoLayout's bytes, 16-byte aligned.  Returns the pixels, those traced, skipped (misses) and non-finite,
+    // the rays traced, occluded and invalid, the batches, and the device times of the pass and of its traversal launches.
+    pt_ao_stats aoPlanes(const pt_ao_desc& d, pt_ao_stats* stats = nullptr) {
+        pt_ao_stats s{};
+        ck(pt_ao_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

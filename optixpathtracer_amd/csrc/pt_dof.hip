@@ -4,15 +4,9 @@
 
 static_assert(PT_DOF_TILE == PASS_TILE, "pt_dof_planes works on the tiled passes' tiles");
 
-// The header's D and rho, operation for operation: every product and every sum is a float32 statement of its own (and the build does not
-// contract them).
+// The header's D (pass_spiral, pt_pass.h) and rho, operation for operation.
 static void dof_taps(DofTaps& t, uint32_t taps) {
-    const float C = -0x1.79886ap-1f, S = 0x1.59d9dep-1f;
-    t.D[0] = make_float2(1.0f, 0.0f);
-    for (int n = 0; n + 1 < 128; ++n) {
-        const float xc = t.D[n].x * C, ys = t.D[n].y * S, xs = t.D[n].x * S, yc = t.D[n].y * C;
-        t.D[n + 1] = make_float2(xc - ys, xs + yc);
-    }
+    pass_spiral(t.D);
     const float ftaps = (float)taps;
     for (uint32_t i = 0; i < 64u; ++i) t.rho[i] = i < taps ? sqrtf(((float)i + 0.5f) / ftaps) : 0.0f;
 }

@@ -41,3 +41,4 @@
 #include "pt_motion_blur.hip"
 #include "pt_dof.hip"
 #include "pt_lens_warp.hip"
+#include "pt_ao.hip"

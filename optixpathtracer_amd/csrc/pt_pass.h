@@ -112,6 +112,17 @@ static int pass_tile_layout(const pt_ctx* cctx, const char* fn, size_t texel_byt
     return PT_OK;
 }
 
+// The Vogel spiral's directions D[0 .. 127] of depth of field's header text (ambient occlusion samples its hemisphere with the same table),
+// operation for operation: every product and every sum is a float32 statement of its own (and the build does not contract them).
+static void pass_spiral(float2* D) {
+    const float C = -0x1.79886ap-1f, S = 0x1.59d9dep-1f;
+    D[0] = make_float2(1.0f, 0.0f);
+    for (int n = 0; n + 1 < 128; ++n) {
+        const float xc = D[n].x * C, ys = D[n].y * S, xs = D[n].x * S, yc = D[n].y * C;
+        D[n + 1] = make_float2(xc - ys, xs + yc);
+    }
+}
+
 static int pass_prev_cameras_check(pt_ctx* ctx, const char* fn, const void* motion, const float* prev_cameras, uint32_t num_prev_cameras) {
     const std::string f = std::string(fn) + ": ";
     const uint32_t ncams = pass_camera_count(ctx);

@@ -1162,6 +1162,49 @@ class SampleRenderer:
         desc.flags = _lib.PT_LENS_WARP_BICUBIC if bicubic else 0
         return self._run_pass("pt_lens_warp_planes", desc, _lib.LensWarpStats(), result)
 
+    def aoLayout(self, rays, max_rays_in_flight=0):
+        """The size in bytes of aoPlanes's scratch (pt_ao_layout): one batch of min(floor(M / rays), frame pixels) pixels, M =
+        max_rays_in_flight or the library's default (_lib.PT_AO_DEFAULT_RAYS_IN_FLIGHT) when 0."""
+        nbytes = C.c_size_t()
+        self._ck(self._L.pt_ao_layout(self._ctx, int(rays), int(max_rays_in_flight), C.byref(nbytes)), "pt_ao_layout")
+        return nbytes.value
+
+    def aoPlanes(self, hit, position, ao=None, out=None, bent=None, scratch=None, mask=None, rays=4, radius=None, bias=1e-3, seed=0,
+                 jitter=False, max_rays_in_flight=0) -> dict:
+        """Ray-traced ambient occlusion from the G-buffer (pt_ao_planes, include/pt_amd.h: the rule, in full): every pixel of a hit shoots
+        `rays` any-hit rays of length `radius` (world units) over the cosine-weighted hemisphere around its geometric normal, through
+        the context's current tree, from the hit position lifted by bias * hit.t along the normal.  ao is the fraction that got away
+        (1 for a miss), out the same as a colour (ao, ao, ao, 1) for temporalAccumulate / filterPlanes / modulatePlanes, bent the mean
+        unoccluded direction (not normalised) with ao in .w.
+
+        hit (h, w, 8) and position (h, w, 4) are renderGBuffer's planes of this frame: CUDA float32 tensors on the context's device —
+        dense, any 4-byte-aligned storage offset — or raw device pointers.  ao (h, w), out and bent (h, w, 4) are optional; out is
+        allocated with torch, zero-filled, when none of the three is given.  scratch: a float32 (bytes / 4,) tensor of
+        aoLayout(rays, max_rays_in_flight) bytes, 16-byte aligned, or a raw pointer; allocated when None.  The rays are traced in batches
+        of at most max_rays_in_flight (0: the library's default); the result does not depend on it.  jitter: each pixel's pattern is
+        turned by a hash of its coordinates and `seed` (e.g. the frame index).  mask: 8x8 blocks as renderMask takes them, None = every
+        block.  Ordering is on the device, as temporalMoments.
+        Returns {"ao", "out", "bent": the tensors (None for a raw pointer or an absent plane), "scratch", "stats": {pixels, traced,
+        skipped, nonfinite, rays, occluded, invalid, batches, kernel_ms, trace_ms}}."""
+        if radius is None:
+            raise ValueError("aoPlanes: radius is required")
+        rays, seed, max_rays_in_flight = int(rays), int(seed), int(max_rays_in_flight)
+        if not 1 <= rays <= _lib.PT_AO_MAX_RAYS:
+            raise ValueError(f"aoPlanes: rays must be 1..{_lib.PT_AO_MAX_RAYS}, not {rays}")
+        if not 0 <= seed < 2**32:
+            raise ValueError("aoPlanes: seed must be in [0,4294967295]")
+        if not 0 <= max_rays_in_flight < 2**32 or 0 < max_rays_in_flight < rays:
+            raise ValueError("aoPlanes: max_rays_in_flight must be 0 or in [rays,4294967295]")
+        given = dict(hit=hit, position=position, ao=ao, out=out, bent=bent)
+        desc = _lib.AoDesc()
+        result = self._bind_planes("aoPlanes", desc, given, _lib.AO_PLANES, ("hit", "position"), _lib.AO_OUTPUTS,
+                                   alloc=("out",) if ao is None and bent is None else ())
+        self._bind_scratch("aoPlanes", desc, result, scratch, lambda: (self.aoLayout(rays, max_rays_in_flight) // 4,))
+        m = self._bind_mask("aoPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.rays, desc.max_rays_in_flight, desc.radius, desc.bias = rays, max_rays_in_flight, float(radius), float(bias)
+        desc.seed, desc.flags = seed, _lib.PT_AO_JITTER if jitter else 0
+        return self._run_pass("pt_ao_planes", desc, _lib.AoStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
