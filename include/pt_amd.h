@@ -197,6 +197,9 @@ typedef struct pt_stats {
     double create_ms;       /* host time of pt_create from the flattened scene to the finished context: uploads, the acceleration structure
                              * (bvh_build_ms is the part between its first and last kernel), the probes that pick the streams — and, in the first
                              * pt_create of a process, what loading the library's code objects costs beyond the time the scene upload hides */
+    uint32_t marg_lds_words_full; /* 4-byte words of the probe's marginal (row) arrays a shade workgroup copies to LDS, in the full layout and in */
+    uint32_t marg_lds_words_lean; /* the lean one (PT_SHADE_LDS); 0: no probe set, or its row search reads global memory (more than 2048 rows, or a
+                             * row count that is no multiple of 64) */
 } pt_stats;
 
 /* SampleRenderer::SampleRenderer(const Model*) (SimplePathtracer.cpp:39-71): uploads the meshes
@@ -2181,7 +2184,12 @@ const char* pt_obj_last_error(void);
  *  which = 6: tea4/lcg/Random in: n x {a bits, b bits} out: n x {tea4(a,b), lcg state, rnd, Randf bits...} (8)
  *  which = 7: tex2D of scene texture 0 in: n x {s,t} (2) out: n x rgba (4)
  *  which = 8: ProbePdf (Probe.cuh:69-93; unused by the reference's device code) in: n x dir[3] out: n x pdf (1)
- * material applies to which 0,1; the context's probe to 2,3,8. All arrays are host memory. */
+ *  which = 9, 10, 11: ProbeSample's row and column search at chosen random numbers  in: n x {r1,r2} (2), each in [0,1)
+ *      out: n x {row, lo, hi, column (int32 bits), r, g, b, pdfX of texel (row, column), pdfY[row]} (9); lo, hi = the guide's line counts for
+ *      r2's cell, before the clamp to the row's last line.  9 searches the marginal arrays in global memory; 10 and 11 search the copy a
+ *      shade workgroup holds in LDS (PT_SHADE_WG threads; 10 the full layout, 11 the lean one, whatever PT_SHADE_LDS says), or the global
+ *      arrays where pt_stats.marg_lds_words_full / _lean is 0
+ * material applies to which 0,1; the context's probe to 2,3,8-11. All arrays are host memory. */
 int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material, int bsdf_mode, const float* in, uint32_t n,
                   float* out);
 

@@ -552,6 +552,7 @@ class Stats(C.Structure):
         ("frames", C.c_uint64), ("total_radiance_rays", C.c_uint64), ("total_shadow_rays", C.c_uint64),
         ("bvh_builder", C.c_uint32), ("fused_passes", C.c_uint32), ("path_state_allocs", C.c_uint32),
         ("bvh_challengers_skipped", C.c_uint32), ("schedule", C.c_uint32), ("sched_chain_ms", C.c_double), ("sched_fused_ms", C.c_double), ("create_ms", C.c_double),
+        ("marg_lds_words_full", C.c_uint32), ("marg_lds_words_lean", C.c_uint32),
     ]
 
     def as_dict(self):

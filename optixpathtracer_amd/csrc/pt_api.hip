@@ -2246,6 +2246,8 @@ extern "C" int pt_get_stats(const pt_ctx* ctx, pt_stats* out) {
     out->path_state_allocs = ctx->path_state_allocs;
     out->bvh_challengers_skipped = (uint32_t)ctx->bvh.challengers_skipped;
     out->create_ms = ctx->create_ms;
+    out->marg_lds_words_full = ctx->pr.dev.data ? shade_marg_words(ctx->pr.dev, false) : 0u;
+    out->marg_lds_words_lean = ctx->pr.dev.data ? shade_marg_words(ctx->pr.dev, true) : 0u;
     return PT_OK;
 }
 

@@ -510,10 +510,8 @@ PT_DEV float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); 
 // (hit record → triangle → material): begin = the two random numbers, the row (marginal search, LDS in k_shade) and the guide loads;
 // end = the candidate lines, column, texel, pdf and direction.  probe_sample runs the two back to back.  (Plain scalars, no struct:
 // conditional expressions over struct members are compiled as selects of addresses and park the struct in scratch.)
-PT_DEV void probe_search_begin(const DevProbe& p, const ProbeMarg& pm, Rng& rand, int& row_out, int& lo_out, int& hi_out, float& r2_out) {
-    float r1, r2;
-    sample2d(rand, r1, r2);
-    r2_out = r2;
+// probe_search_rows: begin's search for given random numbers (r1, r2) in [0, 1) — also pt_eval_table 9-11, which query it at chosen values
+PT_DEV void probe_search_rows(const DevProbe& p, const ProbeMarg& pm, float r1, float r2, int& row_out, int& lo_out, int& hi_out) {
 #ifdef PT_EXP_NO_SEARCH
     row_out = (int)(r1 * p.height);
     lo_out = hi_out = (int)(r2 * p.width) / PT_LINE_COLS;
@@ -527,6 +525,12 @@ PT_DEV void probe_search_begin(const DevProbe& p, const ProbeMarg& pm, Rng& rand
     lo_out = g[0];
     hi_out = g[1];
 #endif
+}
+PT_DEV void probe_search_begin(const DevProbe& p, const ProbeMarg& pm, Rng& rand, int& row_out, int& lo_out, int& hi_out, float& r2_out) {
+    float r1, r2;
+    sample2d(rand, r1, r2);
+    r2_out = r2;
+    probe_search_rows(p, pm, r1, r2, row_out, lo_out, hi_out);
 }
 // Column lower bound of r2 in the row through the line layout: the same index as the reference's binary search (LowerBound :119-136) for
 // every non-decreasing row (and for an all-NaN row: every `<` is false → 0) — the index is 6 l + (entries < r2 in line l) with l = the number
@@ -548,8 +552,8 @@ PT_DEV void probe_cell_columns(const DevProbe& p, int lo, int hi, int& c0, int& 
     c0 = lo * PT_LINE_COLS;
     c1 = hi * PT_LINE_COLS + PT_LINE_COLS;
 }
-PT_DEV void probe_search_end(const DevProbe& p, const ProbeMarg& pm, int row, int lo, int hi, float value, float st, float ct, v3& dir, v3& color, float& pdf) {
-    const ProbeLine* __restrict__ rl = p.lines + (size_t)row * p.lpr;
+// probe_search_column: the line and the column (clamped to the row's last) that end settles on — also pt_eval_table 9-11
+PT_DEV void probe_search_column(const DevProbe& p, const ProbeLine* __restrict__ rl, int lo, int hi, float value, int& l_out, int& col_out) {
 #ifdef PT_EXP_NO_SEARCH
     const int l = lo;
     int col = (int)(value * p.width);
@@ -577,6 +581,13 @@ PT_DEV void probe_search_end(const DevProbe& p, const ProbeMarg& pm, int row, in
               (s1.x < value ? 1 : 0) + (s1.y < value ? 1 : 0);
 #endif
     if (col > p.width - 1) col = p.width - 1;
+    l_out = l;
+    col_out = col;
+}
+PT_DEV void probe_search_end(const DevProbe& p, const ProbeMarg& pm, int row, int lo, int hi, float value, float st, float ct, v3& dir, v3& color, float& pdf) {
+    const ProbeLine* __restrict__ rl = p.lines + (size_t)row * p.lpr;
+    int l, col;
+    probe_search_column(p, rl, lo, hi, value, l, col);
     const float4 px = rl[l].px[col - l * PT_LINE_COLS];
     color = mk3(px.x, px.y, px.z);
     pdf = px.w * pm.pdfY[row];

@@ -32,10 +32,13 @@ extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void*
 extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material, int bsdf_mode, const float* in, uint32_t n, float* out) {
     if (!ctx || !in || !out) return PT_ERR_INVALID;
     if (n == 0) return PT_OK;
-    static const int in_w[9] = {11, 9, 1, 3, 3, 3, 2, 2, 3}, out_w[9] = {4, 6, 9, 6, 1, 1, 8, 4, 1};
-    if (which < 0 || which > 8) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: unknown table");
+    static const int in_w[12] = {11, 9, 1, 3, 3, 3, 2, 2, 3, 2, 2, 2}, out_w[12] = {4, 6, 9, 6, 1, 1, 8, 4, 1, 9, 9, 9};
+    if (which < 0 || which > 11) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: unknown table");
     if (which <= 1 && !material) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: material required");
-    if ((which == 2 || which == 3 || which == 8) && !ctx->pr.dev.data) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: no probe set");
+    if ((which == 2 || which == 3 || which >= 8) && !ctx->pr.dev.data) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: no probe set");
+    if (which >= 9) // the searches index their tables with these: random numbers, as sample2d draws them
+        for (size_t k = 0; k < 2 * (size_t)n; ++k)
+            if (!(in[k] >= 0.0f && in[k] < 1.0f)) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: r1 and r2 must be in [0,1)");
     if (which == 7 && !ctx->sc.tex0.pixel) return fail(ctx, PT_ERR_INVALID, "pt_eval_table: the scene has no texture");
     CK(hipSetDevice(ctx->device));
     DevOwner tmp;
@@ -62,6 +65,18 @@ extern "C" int pt_eval_table(pt_ctx* ctx, int which, const pt_material* material
         case 6: hipLaunchKernelGGL(k_table_rng, g, b, 0, ctx->stream, dIn, n, dOut); break;
         case 7: hipLaunchKernelGGL(k_table_tex, g, b, 0, ctx->stream, ctx->sc.tex0, dIn, n, dOut); break;
         case 8: hipLaunchKernelGGL(k_table_probe_pdf, g, b, 0, ctx->stream, ctx->pr.dev, dIn, n, dOut); break;
+        case 9: case 10: case 11: { // in workgroups of k_shade's size, with its dynamic LDS for the layout asked for (launch_shade_wg)
+            const int layout = which - 9;
+            const unsigned lds = layout ? (unsigned)(sizeof(float) * shade_marg_words(ctx->pr.dev, layout == 2)) : 0u;
+            const unsigned wg = (unsigned)ctx->shade_wg;
+            const dim3 sg((n + wg - 1) / wg), sb(wg);
+            switch (ctx->shade_wg) {
+            case 64: hipLaunchKernelGGL((k_table_probe_search<64>), sg, sb, lds, ctx->stream, ctx->pr.dev, layout, dIn, n, dOut); break;
+            case 128: hipLaunchKernelGGL((k_table_probe_search<128>), sg, sb, lds, ctx->stream, ctx->pr.dev, layout, dIn, n, dOut); break;
+            default: hipLaunchKernelGGL((k_table_probe_search<256>), sg, sb, lds, ctx->stream, ctx->pr.dev, layout, dIn, n, dOut); break;
+            }
+            break;
+        }
     }
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());

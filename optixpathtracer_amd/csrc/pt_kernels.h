@@ -668,6 +668,29 @@ __host__ __device__ inline uint32_t shade_marg_words(const DevProbe& p, bool lea
     if (!p.c64Y || p.height > PT_LDS_PROBE_ROWS) return 0u;
     return (uint32_t)((lean ? 1 : 2) * p.height + p.height / 8 + ((p.ncy + 7) & ~7));
 }
+// A workgroup of WG threads copies the probe's marginal arrays to s_marg, its shade_marg_words(probe, lean) words of dynamic LDS, and returns
+// where ProbeSample reads them: the copy, or the global arrays where no words are held.  The caller's next workgroup barrier orders the
+// copy before its readers.  (k_shade, and pt_eval_table 10 / 11, which queries the search through this copy.)
+template <int WG>
+PT_DEV ProbeMarg shade_marg_fill(const DevProbe& probe, bool lean, float* s_marg) {
+    ProbeMarg pm = probe_marg_global(probe);
+    if (probe.c64Y && probe.height <= PT_LDS_PROBE_ROWS) {
+        // ProbeSample's row search (cdfY through its 64- and 8-entry count tables) and pdfY from LDS: 3 of the 6 dependent
+        // loads of the lookup stay on the CU (SURVEY.md section 7, hard part 3); lean: the search only, 2 of the 6
+        const int h = probe.height, h8 = h / 8, n64 = (probe.ncy + 7) & ~7;
+        float* s_cdfY = s_marg;
+        float* s_pdfY = s_cdfY + h;
+        float* s_c8Y = lean ? s_pdfY : s_pdfY + h;
+        float* s_c64Y = s_c8Y + h8;
+        for (int k = threadIdx.x; k < h; k += WG) s_cdfY[k] = probe.cdfY[k];
+        if (!lean)
+            for (int k = threadIdx.x; k < h; k += WG) s_pdfY[k] = probe.pdfY[k];
+        for (int k = threadIdx.x; k < h8; k += WG) s_c8Y[k] = probe.c8Y[k];
+        for (int k = threadIdx.x; k < n64; k += WG) s_c64Y[k] = probe.c64Y[k];
+        pm = ProbeMarg{s_cdfY, lean ? probe.pdfY : s_pdfY, s_c64Y, s_c8Y};
+    }
+    return pm;
+}
 
 // the body of the shade kernels (k_shade, k_shade_carry below), for workgroups of WG threads (64, 128 or 256: launch_shade keeps
 // grid x WG constant, so the grid-stride loop gives a thread the same entries in every shape, and a wave the same 64)
@@ -685,22 +708,7 @@ PT_DEV void shade_queue(const PathState& st, const ShadeParams& sp) {
         for (uint32_t b = threadIdx.x; b < 256u; b += WG) s_u8[b] = (float)b / 255.0f;
         u8lut = s_u8;
     }
-    ProbeMarg pm = probe_marg_global(sp.probe);
-    if (sp.probe.c64Y && sp.probe.height <= PT_LDS_PROBE_ROWS) {
-        // ProbeSample's row search (cdfY through its 64- and 8-entry count tables) and pdfY from LDS: 3 of the 6 dependent
-        // loads of the lookup stay on the CU (SURVEY.md section 7, hard part 3); lean: the search only, 2 of the 6
-        const int h = sp.probe.height, h8 = h / 8, n64 = (sp.probe.ncy + 7) & ~7;
-        float* s_cdfY = s_marg;
-        float* s_pdfY = s_cdfY + h;
-        float* s_c8Y = lean ? s_pdfY : s_pdfY + h;
-        float* s_c64Y = s_c8Y + h8;
-        for (int k = threadIdx.x; k < h; k += WG) s_cdfY[k] = sp.probe.cdfY[k];
-        if (!lean)
-            for (int k = threadIdx.x; k < h; k += WG) s_pdfY[k] = sp.probe.pdfY[k];
-        for (int k = threadIdx.x; k < h8; k += WG) s_c8Y[k] = sp.probe.c8Y[k];
-        for (int k = threadIdx.x; k < n64; k += WG) s_c64Y[k] = sp.probe.c64Y[k];
-        pm = ProbeMarg{s_cdfY, lean ? sp.probe.pdfY : s_pdfY, s_c64Y, s_c8Y};
-    }
+    const ProbeMarg pm = shade_marg_fill<WG>(sp.probe, lean, s_marg);
     const uint32_t n = qreader_init(sp.queue, s_prefix); // ends in a workgroup barrier (identity queue: see below)
     if (sp.queue.base == nullptr) __syncthreads();
     const uint32_t nround = (n + 63u) & ~63u; // whole waves stay in the loop so ballots see every lane
@@ -1586,6 +1594,26 @@ __global__ void k_table_probe_pdf(DevProbe probe, const float* __restrict__ in, 
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     out[i] = probe_pdf(probe, mk3(in[3 * (size_t)i], in[3 * (size_t)i + 1], in[3 * (size_t)i + 2]));
+}
+// ProbeSample's two searches at chosen random numbers (pt_eval_table 9-11): probe_search_rows, then probe_search_column, through the global
+// marginal arrays (layout 0) or through k_shade's LDS copy of them (1 full, 2 lean: shade_marg_fill in a workgroup of k_shade's size)
+template <int WG>
+__global__ void __launch_bounds__(WG) k_table_probe_search(DevProbe probe, int layout, const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float s_marg[];
+    const ProbeMarg pm = layout ? shade_marg_fill<WG>(probe, layout == 2, s_marg) : probe_marg_global(probe);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float r2 = in[2 * (size_t)i + 1];
+    int row, lo, hi, l, col;
+    probe_search_rows(probe, pm, in[2 * (size_t)i], r2, row, lo, hi);
+    const ProbeLine* __restrict__ rl = probe.lines + (size_t)row * probe.lpr;
+    probe_search_column(probe, rl, lo, hi, r2, l, col);
+    const float4 px = rl[l].px[col - l * PT_LINE_COLS];
+    float* o = &out[9 * (size_t)i];
+    o[0] = __int_as_float(row); o[1] = __int_as_float(lo); o[2] = __int_as_float(hi); o[3] = __int_as_float(col);
+    o[4] = px.x; o[5] = px.y; o[6] = px.z; o[7] = px.w;
+    o[8] = pm.pdfY[row];
 }
 __global__ void k_table_color(const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import probe_search_ref as PS
 from optixpathtracer_amd import scenes
 
 
@@ -210,12 +211,9 @@ def test_atrous_filter_properties(kind, orc_libm, orc_det):
 
 def test_probe_line_search_model_equals_lower_bound():
     """The device layout of ProbeSample's column search (pt_device.h: 128-byte lines of six columns + a u16 guide per row) restated in
-    numpy: for every row kind the reference's BuildCDF can produce — smooth, flat stretches, all-NaN — and widths around the line size,
-    guide -> candidate lines -> count gives the index of the reference's LowerBound (Probe.cuh:119-136).  Pins the ALGORITHM on the CPU; the
-    kernel itself is compared bit for bit on the GPU (test_probe_tables)."""
-    from optixpathtracer_amd import scenes
-
-    G = 6
+    numpy (probe_search_ref.column_model): for every row kind the reference's BuildCDF can produce — smooth, flat stretches, all-NaN — and
+    widths around the line size, guide -> candidate lines -> count gives the index of the reference's LowerBound (Probe.cuh:119-136).
+    Pins the ALGORITHM on the CPU; the kernel itself is compared bit for bit on the GPU (test_probe_tables, tests/test_gpu_probe_search.py)."""
 
     def lower_bound_ref(row, v):  # Probe.cuh:119-136
         lo, hi = 0, len(row)
@@ -227,30 +225,6 @@ def test_probe_line_search_model_equals_lower_bound():
                 hi = mid
         return lo
 
-    def model(row, v, gk):
-        w = len(row)
-        lpr = (w + G - 1) // G
-        cdf = np.full(lpr * G, np.inf, np.float32)
-        cdf[:w] = row
-        last = cdf.reshape(lpr, G)[:, G - 1]
-        with np.errstate(invalid="ignore"):
-            guide = np.array([int(np.sum(last < np.float32(k / gk))) for k in range(gk + 1)])  # counts: NaN compares false
-            k = min(int(np.float32(v) * np.float32(gk)), gk - 1)
-            lo, hi = min(guide[k], lpr - 1), min(guide[k + 1], lpr - 1)
-            while hi - lo > 2:
-                mid = lo + (hi - lo) // 2
-                if last[mid] < v:
-                    lo = mid + 1
-                else:
-                    hi = mid
-            i1 = min(lo + 1, hi)
-            l = lo
-            if i1 > lo and last[lo] < v:
-                l = i1
-                if hi > i1 and last[i1] < v:
-                    l = hi
-            return l * G + int(np.sum(cdf[l * G:(l + 1) * G] < v))
-
     rng = np.random.default_rng(11)
     probes = [scenes.spots_probe(1000, 16), scenes.spots_probe(4099, 4, fill=0.002), scenes.spots_probe(7, 5, fill=0.5), scenes.spots_probe(13, 3, fill=0.3),
               scenes.constant_probe(5, 4), scenes.constant_probe(6, 8), scenes.sky_probe(256, 8), scenes.disc_probe(100, 10)]
@@ -258,18 +232,65 @@ def test_probe_line_search_model_equals_lower_bound():
         p = pr.BuildCDF()
         w, h = p.width, p.height
         cdfx = np.asarray(p.cdfValuesX, np.float32).reshape(h, w)
-        gk = 64
-        while gk < 4096 and gk * 2 < w:
-            gk *= 2
+        gk = PS.guide_size(w)
         for row in cdfx:
             vs = np.concatenate([rng.random(40, dtype=np.float32), row[np.isfinite(row)][:8], np.float32([0.0, np.nextafter(np.float32(1), np.float32(0))])])
-            for v in vs:
-                if not (0.0 <= v < 1.0):
-                    continue
-                with np.errstate(invalid="ignore"):
-                    ref = lower_bound_ref(row, np.float32(v))
-                got = model(row, np.float32(v), gk)
-                assert min(got, w) == ref or (got >= w and ref == w), (w, v, got, ref)
+            vs = vs[(vs >= 0.0) & (vs < 1.0)]
+            got = PS.column_model(row, vs, gk)["col"]
+            with np.errstate(invalid="ignore"):
+                ref = np.array([lower_bound_ref(row, v) for v in vs])
+            assert np.array_equal(PS.lower_bound(row, vs), ref)  # the vectorised reference is the loop
+            assert (np.minimum(got, w) == ref).all(), (w, vs[np.minimum(got, w) != ref][:3])
+
+
+@pytest.mark.parametrize("name", list(PS.CASES))
+def test_probe_search_models_equal_lower_bound_at_every_edge(name):
+    """Both device structures restated in numpy — lower_bound_blocked over the count tables k_probe_coarse builds (c64Y padded with +inf,
+    the binary search over more than 32 blocks, the group capped at 7) and the guide / line search of the columns — against the literal
+    LowerBound on the cases and value sets the GPU test sends through the kernels (probe_search_ref): every CDF entry, every guide-cell edge,
+    and their float32 neighbours."""
+    c = PS.case(name)
+    p = c["probe"]
+    row, col, lo, hi = PS.model(p, c["q"])
+    assert np.array_equal(row, c["row"]), (name, c["q"][row != c["row"]][:3])
+    assert np.array_equal(col, c["col"]), (name, c["q"][col != c["col"]][:3])
+    lpr = (p.width + PS.LINE_COLS - 1) // PS.LINE_COLS
+    line = c["col"] // PS.LINE_COLS
+    assert (lo <= hi).all() and (hi <= lpr).all() and (np.minimum(lo, lpr - 1) <= line).all() and (line <= np.minimum(hi, lpr - 1)).all()
+
+
+def test_probe_search_row_model_takes_every_path():
+    """the row model's own branches on the case list: padded count tables, exactly 32 blocks, the binary search over 33, no tables at all,
+    and the exit past the last block"""
+    ncy = {n: (PS.row_tables(PS.arrays(PS.case(n)["probe"])[0]) or (None, None, 0))[2] for n in PS.CASES}
+    assert ncy["sky_13x64"] == 1 and ncy["spots_130x192"] == 3 and ncy["spots_12x512"] == 8 and ncy["spots_7x2048"] == 32 and ncy["spots_6x2112"] == 33
+    assert ncy["disc_100x50"] == 0 and ncy["spots_4099x8"] == 0 and ncy["constant_5x4"] == 0
+    short = PS.case("dyadic_200x64_short")
+    assert (short["lby"] == 64).any() and (short["lbx"] == 200).any()
+    total = dict.fromkeys(PS.BRANCHES, 0)
+    for n in PS.CASES:  # and the column model's, with the guide counts of the model (the GPU test repeats this with the kernel's)
+        c = PS.case(n)
+        _, _, lo, hi = PS.model(c["probe"], c["q"])
+        for k, v in PS.branch_counts(c["probe"], c["q"], c["lby"], c["lbx"], lo, hi).items():
+            total[k] += v
+    assert all(total.values()), total
+
+
+@pytest.mark.parametrize("name", list(PS.CASES))
+def test_probe_search_queries_have_teeth(name):
+    """a LowerBound with `<` written as `<=` differs from the reference on the case's queries (every case has finite entries), and so do
+    the models with one of the device's details changed: the guide counted with `<=`, c64Y padded with 0 instead of +inf"""
+    c = PS.case(name)
+    p, q = c["probe"], c["q"]
+    row, col, _, _ = PS.expected(p, q, le=True)
+    assert (row != c["row"]).any() or (col != c["col"]).any(), name
+    if name in ("constant_8x64", "dyadic_200x64", "dyadic_65x128", "dyadic_200x64_short"):  # dyadic entries: lines end ON guide-cell edges
+        _, gcol, _, _ = PS.model(p, q, guide_le=True)
+        assert (gcol != c["col"]).any(), name
+    t = PS.row_tables(PS.arrays(p)[0])
+    if t is not None and t[2] % 8 and t[2] <= 32:
+        prow, _, _, _ = PS.model(p, q, pad=0.0)
+        assert (prow != c["row"]).any(), name
 
 
 def _census_rays(orc, sc, cam, n_cam, rng):
