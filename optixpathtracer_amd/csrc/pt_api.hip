@@ -473,9 +473,17 @@ static int stack_capacity8(const pt_ctx* ctx) { return (PT8_LDS_DEPTH - ctx->lds
 
 // The traversal stack is finite (k_trace8: one pushed group per level of the wide tree).  A tree deeper than the stack is refused
 // here, loudly, instead of being traversed with dropped entries.
+// So is a tree whose node or leaf-triangle array does not fit 4 GiB (53 M nodes, 89 M leaf triangles): the per-ray kernels address both
+// by a 32-bit byte offset from the array's wave-uniform base (trace8_wave).
 static int check_tree_depth(pt_ctx* ctx, char* msg, size_t msg_len, const PtBvh* bvh = nullptr) {
+    const PtBvh* tree = bvh ? bvh : &ctx->bvh;
+    if ((uint64_t)tree->num_nodes8 * sizeof(Node8) > 0xffffffffull || (uint64_t)tree->num_tris8 * sizeof(LeafTri) > 0xffffffffull) {
+        snprintf(msg, msg_len, "acceleration structure has %llu nodes and %llu leaf triangles, an array of more than 4 GiB", (unsigned long long)tree->num_nodes8,
+                 (unsigned long long)tree->num_tris8);
+        return PT_ERR_UNSUPPORTED;
+    }
     if (!ctx->stack_check) return PT_OK;
-    const int levels = (bvh ? bvh : &ctx->bvh)->levels8;
+    const int levels = tree->levels8;
     if (levels > stack_capacity8(ctx)) {
         snprintf(msg, msg_len, "acceleration structure has %d levels, the traversal stack holds %d", levels, stack_capacity8(ctx));
         return PT_ERR_UNSUPPORTED;

@@ -249,6 +249,15 @@ struct Trace8Args {
 #endif
 };
 
+// the traversal stack's two homes, each a pointer type of its own address space (the host pass only parses the device code)
+#if __HIP_DEVICE_COMPILE__
+typedef __attribute__((address_space(3))) uint32_t* Lds32;
+typedef __attribute__((address_space(1))) uint32_t* Global32;
+#else
+typedef uint32_t* Lds32;
+typedef uint32_t* Global32;
+#endif
+
 // The traversal of one persistent wave.  LOCAL = false: wave `wid` of `nw` of a launch over the queues of `a` (k_trace8 below).
 // LOCAL = true (pt_fused.h): the wave traverses a private window of the queue arrays — entries [woff, woff + ln1) of `a.queue`'s arrays and, in
 // TR_UNIFIED, the shadow entries [woff, woff + ln2) of `a.queue2`'s — on its own: no sub-queue prefix, no chunk counter, every ray taken by
@@ -328,31 +337,43 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     unsigned long long h_i0 = 0, h_i1 = 0, h_i2 = 0, h_i3 = 0, h_c0 = 0, h_c1 = 0, h_c2 = 0, h_c3 = 0;
 #endif
 
+    // a record's address is the array's wave-uniform base plus a 32-bit byte offset (pt_create refuses arrays of more than 4 GiB): one multiply, no 64-bit pair
+    const char* const node_bytes = reinterpret_cast<const char*>(a.bvh.nodes);
+    const char* const tri_bytes = reinterpret_cast<const char*>(a.bvh.tris);
+    // The hot stack is LDS and nothing else: the two words of a level are 64 dwords apart, one two-word LDS access per push or pop.  The spill
+    // levels go through a pointer that is global by TYPE: with two generic pointers the compiler merged the LDS and the spill address of a
+    // pop's second word into one and read it with a flat load (and a full wait, outstanding stores included) on the chain pop -> child
+    // select -> node address -> loads.  The spill path and the full stack are the cold branch, with global accesses and a wait of their own.
+    const Lds32 lds_stack = (Lds32)s_stack;
+    const Global32 ovf_stack = (Global32)a.ovf;
     auto push = [&](uint32_t v0, uint32_t v1) {
         PT_STAT(++c_push; if ((uint32_t)sp + 1 > c_maxsp) c_maxsp = sp + 1;)
         if (sp < lds_depth) {
-            s_stack[(sp * 2) * 64 + lane] = v0;
-            s_stack[(sp * 2 + 1) * 64 + lane] = v1;
+            lds_stack[(sp * 2) * 64 + lane] = v0;
+            lds_stack[(sp * 2 + 1) * 64 + lane] = v1;
+            ++sp;
         } else if (sp < lds_depth + a.ovf_depth) {
-            a.ovf[(size_t)((sp - lds_depth) * 2) * gstride + gtid] = v0;
-            a.ovf[(size_t)((sp - lds_depth) * 2 + 1) * gstride + gtid] = v1;
+            ovf_stack[(size_t)((sp - lds_depth) * 2) * gstride + gtid] = v0;
+            ovf_stack[(size_t)((sp - lds_depth) * 2 + 1) * gstride + gtid] = v1;
+            ++sp;
         } else {
             // Stack full: pt_create refuses trees deeper than the stack, so this is unreachable unless that check is
             // bypassed; the entry is dropped WITHOUT advancing sp (pops stay matched, no stray read) and the launch is
             // reported as failed instead of returning a silently wrong image.
             atomicOr(a.fault, 1u);
-            return;
         }
-        ++sp;
     };
     auto pop = [&](uint32_t& v0, uint32_t& v1) { // caller checked sp > sb
         --sp;
         if (sp < lds_depth) {
-            v0 = s_stack[(sp * 2) * 64 + lane];
-            v1 = s_stack[(sp * 2 + 1) * 64 + lane];
+            v0 = lds_stack[(sp * 2) * 64 + lane];
+            v1 = lds_stack[(sp * 2 + 1) * 64 + lane];
         } else {
-            v0 = a.ovf[(size_t)((sp - lds_depth) * 2) * gstride + gtid];
-            v1 = a.ovf[(size_t)((sp - lds_depth) * 2 + 1) * gstride + gtid];
+            v0 = ovf_stack[(size_t)((sp - lds_depth) * 2) * gstride + gtid];
+            v1 = ovf_stack[(size_t)((sp - lds_depth) * 2 + 1) * gstride + gtid];
+            // vmcnt(0), other counters untouched, HERE: left to the compiler the wait lands behind the branch, where the LDS pops wait with the
+            // spill pops — for the result stores of the rays that finished in this iteration too
+            __builtin_amdgcn_s_waitcnt(0x0f70);
         }
     };
     // write the ray's result: (best, bprim) = closest hit / occlusion flag
@@ -639,10 +660,11 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
             // run with complementary half-empty masks.  (Running BOTH types per iteration in the tail phase, their loads in flight together,
             // was measured: no gain — a lone wave of 64 rays takes 40 us either way.)
             const bool node_turn = __popcll(m_node) >= PT8_TRI_BIAS * __popcll(m_tri);
-            const bool tri_turn = !node_turn;
-            // ---- phase 1: addresses and loads (r0..r4 hold a node for node lanes, r0..r2 a triangle for triangle lanes)
-            float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, r3 = r0, r4 = r0;
-            bool do_node = false;
+            // The step type is wave-uniform, so each type keeps its record's words in a scope of its own, from the loads to the arithmetic under
+            // one predicate.  (Shared registers r0..r4, loaded in a phase 1 and read in a phase 2 under a second predicate, had to hold a value
+            // on every path: 2 x 20 v_mov 0 per iteration, and a wait for all vector memory at the top of the loop — the finished rays' result
+            // stores included — to order those moves behind the previous iteration's loads.)
+            PT_WLOG(unsigned long long w_b = w_a; unsigned long long w_c = w_a;)
             if (want_node && node_turn) {
                 if (g_hits == 0u) {
                     if (sp == SB) {
@@ -668,73 +690,62 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                     if (g_hits != 0u) push(g_base, g_imask | (g_hits << 8));
                     PT_STAT(++c_nodes; ++c_ray;)
 #if PT8_NODE64
-                    const float4* nd = reinterpret_cast<const float4*>(&a.bvh.nodes[idx]); // one 64-byte line: header, then the planes
-                    r0 = nd[0]; r2 = nd[1]; r3 = nd[2]; r4 = nd[3];
+                    const float4* nd = reinterpret_cast<const float4*>(node_bytes + idx * (uint32_t)sizeof(Node8)); // one 64-byte line: header, then the planes
+                    const float4 n0 = nd[0], n2 = nd[1], n3 = nd[2], n4 = nd[3];
+                    PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
+                    const NodeHdr nh = node_hdr(make_uint4(__float_as_uint(n0.x), __float_as_uint(n0.y), __float_as_uint(n0.z), __float_as_uint(n0.w)), a.bvh.grid);
 #else
-                    const Node8* nd = &a.bvh.nodes[idx];
-                    r0 = nd->n0; r1 = nd->n1; r2 = nd->n2; r3 = nd->n3; r4 = nd->n4;
+                    const Node8* nd = reinterpret_cast<const Node8*>(node_bytes + idx * (uint32_t)sizeof(Node8));
+                    const float4 n0 = nd->n0, n1 = nd->n1, n2 = nd->n2, n3 = nd->n3, n4 = nd->n4;
+                    PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
+                    const NodeHdr nh = node_hdr(n0, n1);
 #endif
-                    do_node = true;
+                    const uint32_t imask = nh.imask;
+                    const float ax = nh.sx * r.idir.x, ay = nh.sy * r.idir.y, az = nh.sz * r.idir.z;
+                    const float bx = (nh.ox - r.o.x) * r.idir.x, by = (nh.oy - r.o.y) * r.idir.y, bz = (nh.oz - r.o.z) * r.idir.z;
+                    // near/far planes per axis follow the direction sign
+                    const bool nx = r.idir.x < 0.0f, ny = r.idir.y < 0.0f, nz = r.idir.z < 0.0f;
+                    const uint32_t lox0 = __float_as_uint(n2.x), lox1 = __float_as_uint(n2.y), loy0 = __float_as_uint(n2.z), loy1 = __float_as_uint(n2.w);
+                    const uint32_t loz0 = __float_as_uint(n3.x), loz1 = __float_as_uint(n3.y), hix0 = __float_as_uint(n3.z), hix1 = __float_as_uint(n3.w);
+                    const uint32_t hiy0 = __float_as_uint(n4.x), hiy1 = __float_as_uint(n4.y), hiz0 = __float_as_uint(n4.z), hiz1 = __float_as_uint(n4.w);
+                    const uint32_t nearx[2] = {nx ? hix0 : lox0, nx ? hix1 : lox1}, farx[2] = {nx ? lox0 : hix0, nx ? lox1 : hix1};
+                    const uint32_t neary[2] = {ny ? hiy0 : loy0, ny ? hiy1 : loy1}, fary[2] = {ny ? loy0 : hiy0, ny ? loy1 : hiy1};
+                    const uint32_t nearz[2] = {nz ? hiz0 : loz0, nz ? hiz1 : loz1}, farz[2] = {nz ? loz0 : hiz0, nz ? loz1 : hiz1};
+                    // No extra widening of the far plane here: the 8-bit grid (rounded outward from boxes already padded
+                    // by 2^-16 of the scene size) is orders of magnitude coarser than the rounding of these products.
+                    // (Measured and rejected, twice: two children per v_pk_fma_f32 — 24 packed instead of 48 scalar FMAs, conversions landing in adjacent
+                    // registers, no packing moves: traversal 5 % SLOWER in round 3 (0.847 vs 0.807 ms per launch).  The packed FP32 FMA does not issue
+                    // at twice the scalar rate here, and the register pairs add 7 spills.)
+                    uint32_t miss = 0u; // sign bits of tfar - tnear, slot 7 first (one subtract + one funnel shift per child)
+#pragma unroll
+                    for (int s = 7; s >= 0; --s) {
+                        const int w = s >> 2, k = s & 3;
+                        const float tnx = __builtin_fmaf(u8f(nearx[w], k), ax, bx), tfx = __builtin_fmaf(u8f(farx[w], k), ax, bx);
+                        const float tny = __builtin_fmaf(u8f(neary[w], k), ay, by), tfy = __builtin_fmaf(u8f(fary[w], k), ay, by);
+                        const float tnz = __builtin_fmaf(u8f(nearz[w], k), az, bz), tfz = __builtin_fmaf(u8f(farz[w], k), az, bz);
+                        const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
+                        const float tf = fminf(fminf(tfx, tfy), fminf(tfz, best));
+                        miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(tf - tn), 31u);
+                    }
+                    const uint32_t hm = miss ^ 0xffu; // hit mask in slot positions
+                    const uint32_t hits = hm & imask;
+                    // triangles of the leaf children that were hit
+                    g_base = nh.child_base;
+                    g_imask = imask;
+                    g_hits = hits;
+                    t_base = nh.tri_base;
+                    t_bits = nh.lbits;
+                    t_mask = leaf_pending(hm, nh.lbits);
                 }
             }
-            const bool do_tri = want_tri && tri_turn;
-            if (do_tri) {
+            if (want_tri && !node_turn) {
                 const uint32_t bit = (uint32_t)__ffs((int)t_mask) - 1u;
                 t_mask &= t_mask - 1u;
                 PT_STAT(++c_tris; ++c_ray;)
                 const uint32_t leaf = leaf_of(t_base, t_bits, bit);
-                const LeafTri* tp = &a.bvh.tris[leaf];
-                r0 = tp->t0; r1 = tp->t1; r2 = tp->t2;
-                r3.x = __uint_as_float(leaf); // rides to phase 2 in a register the node lanes keep live anyway
-            }
-            PT_WLOG(const unsigned long long w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); const unsigned long long w_c = clock64();)
-            // ---- phase 2: the arithmetic
-            if (do_node) {
-                const float4 n2 = r2, n3 = r3, n4 = r4;
-#if PT8_NODE64
-                const NodeHdr nh = node_hdr(make_uint4(__float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z), __float_as_uint(r0.w)), a.bvh.grid);
-#else
-                const NodeHdr nh = node_hdr(r0, r1);
-#endif
-                const uint32_t imask = nh.imask;
-                const float ax = nh.sx * r.idir.x, ay = nh.sy * r.idir.y, az = nh.sz * r.idir.z;
-                const float bx = (nh.ox - r.o.x) * r.idir.x, by = (nh.oy - r.o.y) * r.idir.y, bz = (nh.oz - r.o.z) * r.idir.z;
-                // near/far planes per axis follow the direction sign
-                const bool nx = r.idir.x < 0.0f, ny = r.idir.y < 0.0f, nz = r.idir.z < 0.0f;
-                const uint32_t lox0 = __float_as_uint(n2.x), lox1 = __float_as_uint(n2.y), loy0 = __float_as_uint(n2.z), loy1 = __float_as_uint(n2.w);
-                const uint32_t loz0 = __float_as_uint(n3.x), loz1 = __float_as_uint(n3.y), hix0 = __float_as_uint(n3.z), hix1 = __float_as_uint(n3.w);
-                const uint32_t hiy0 = __float_as_uint(n4.x), hiy1 = __float_as_uint(n4.y), hiz0 = __float_as_uint(n4.z), hiz1 = __float_as_uint(n4.w);
-                const uint32_t nearx[2] = {nx ? hix0 : lox0, nx ? hix1 : lox1}, farx[2] = {nx ? lox0 : hix0, nx ? lox1 : hix1};
-                const uint32_t neary[2] = {ny ? hiy0 : loy0, ny ? hiy1 : loy1}, fary[2] = {ny ? loy0 : hiy0, ny ? loy1 : hiy1};
-                const uint32_t nearz[2] = {nz ? hiz0 : loz0, nz ? hiz1 : loz1}, farz[2] = {nz ? loz0 : hiz0, nz ? loz1 : hiz1};
-                // No extra widening of the far plane here: the 8-bit grid (rounded outward from boxes already padded
-                // by 2^-16 of the scene size) is orders of magnitude coarser than the rounding of these products.
-                // (Measured and rejected, twice: two children per v_pk_fma_f32 — 24 packed instead of 48 scalar FMAs, conversions landing in adjacent
-                // registers, no packing moves: traversal 5 % SLOWER in round 3 (0.847 vs 0.807 ms per launch).  The packed FP32 FMA does not issue
-                // at twice the scalar rate here, and the register pairs add 7 spills.)
-                uint32_t miss = 0u; // sign bits of tfar - tnear, slot 7 first (one subtract + one funnel shift per child)
-#pragma unroll
-                for (int s = 7; s >= 0; --s) {
-                    const int w = s >> 2, k = s & 3;
-                    const float tnx = __builtin_fmaf(u8f(nearx[w], k), ax, bx), tfx = __builtin_fmaf(u8f(farx[w], k), ax, bx);
-                    const float tny = __builtin_fmaf(u8f(neary[w], k), ay, by), tfy = __builtin_fmaf(u8f(fary[w], k), ay, by);
-                    const float tnz = __builtin_fmaf(u8f(nearz[w], k), az, bz), tfz = __builtin_fmaf(u8f(farz[w], k), az, bz);
-                    const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
-                    const float tf = fminf(fminf(tfx, tfy), fminf(tfz, best));
-                    miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(tf - tn), 31u);
-                }
-                const uint32_t hm = miss ^ 0xffu; // hit mask in slot positions
-                const uint32_t hits = hm & imask;
-                // triangles of the leaf children that were hit
-                g_base = nh.child_base;
-                g_imask = imask;
-                g_hits = hits;
-                t_base = nh.tri_base;
-                t_bits = nh.lbits;
-                t_mask = leaf_pending(hm, nh.lbits);
-            }
-            if (do_tri) {
-                const float4 ta = r0, tb = r1, tc = r2;
+                const LeafTri* tp = reinterpret_cast<const LeafTri*>(tri_bytes + leaf * (uint32_t)sizeof(LeafTri));
+                const float4 ta = tp->t0, tb = tp->t1, tc = tp->t2;
+                PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
                 float t, det;
                 const v3 v0 = mk3(ta.x, ta.y, ta.z), v1 = mk3(ta.w, tb.x, tb.y), v2 = mk3(tb.z, tb.w, tc.x);
                 if (tri_test_det(r, v0, v1, v2, t, det)) {
@@ -748,7 +759,7 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                     } else if (t > tmin && (t < best || (t == best && bprim >= 0 && prim < bprim)) && hit_in_box(r, v0, v1, v2, a.bvh.hit_pad, t)) {
                         best = t;
                         bprim = prim;
-                        bleaf = (int32_t)__float_as_uint(r3.x);
+                        bleaf = (int32_t)leaf;
 #if PT8_STEAL
                         if (stealing) {
                             const unsigned long long key = local_key();
