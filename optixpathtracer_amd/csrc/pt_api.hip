@@ -37,6 +37,7 @@ static thread_local std::string g_create_error;
 struct LaunchCounts {
     uint32_t trace = 0, shadow = 0, shade = 0, fused = 0;
     uint32_t carry = 0; // k_shade launches that carried the paths' sums (PT_CARRY_SUMS)
+    uint32_t hitword = 0; // passes whose paths kept a first-hit word instead of nrm / alb (PT_LEAN_FIRST)
 };
 
 // A host thread that enqueues on behalf of a context (pt_multi: one per rank; a synchronous frame: one per pixel chunk).  A frame is 21
@@ -347,6 +348,7 @@ struct pt_ctx {
     // fused_max_paths paths (PT_FUSED_MAX_PATHS), as one pass / 2 every pass the kernel covers, chunked as usual (tests); fused_cap: window entries per wave (PT_FUSED_CAP, a multiple of 64; default: 128 or 64 by frame size)
     int fused = 1;
     bool carry_sums = true; // PT_CARRY_SUMS: the launch chain carries the paths' sums with their queue entries (where eligible: carry_eligible)
+    bool lean_first = true; // PT_LEAN_FIRST: the first-hit normal and albedo as one word per path, rebuilt by the resolve kernels (where eligible: hitword_eligible)
     uint64_t fused_max_paths = 2500000;
     uint32_t fused_cap = 0; // 0: by frame size (enqueue_chunk)
     float fused_max_cost = 22.f; // PT_FUSED_MAX_COST: fused_one_pass only for trees whose calibration rays cost at most this many steps (see sched_choose)
@@ -702,6 +704,7 @@ static int create_from_flat(const FlatScene& fs, int device, pt_ctx** out_ctx) {
         if (const char* e = getenv("PT_ENQUEUE_THREADS")) ctx->enqueue_threads = atoi(e);
         if (const char* e = getenv("PT_FUSED")) ctx->fused = atoi(e);
         if (const char* e = getenv("PT_CARRY_SUMS")) ctx->carry_sums = atoi(e) != 0;
+        if (const char* e = getenv("PT_LEAN_FIRST")) ctx->lean_first = atoi(e) != 0;
         if (const char* e = getenv("PT_FUSED_MAX_PATHS")) ctx->fused_max_paths = strtoull(e, nullptr, 10);
         if (const char* e = getenv("PT_FUSED_GRID")) ctx->fused_grid = atoi(e);
         if (const char* e = getenv("PT_FUSED_MAX_COST")) ctx->fused_max_cost = (float)atof(e);
@@ -1159,6 +1162,9 @@ static int assign_streams(pt_ctx* ctx, int nsets) {
 // Carried sums (PT_CARRY_SUMS): scenes without shadow catchers; the chunks of a frame take them when its shadow rays are
 // placed in the unified launch (enqueue_chunk).  Decided by what pt_create saw, so the arrays exist whenever a frame may want them.
 static bool carry_eligible(const pt_ctx* ctx) { return ctx->carry_sums && !ctx->has_catcher; }
+// The first-hit word instead of nrm / alb (PathState::hitword): the depth-0 normal and albedo must be functions of the hit triangle alone — no
+// catcher pass-throughs that re-add them, no texture lookups.  Foveated launches keep the arrays (enqueue_chunk), which every set still has.
+static bool hitword_eligible(const pt_ctx* ctx) { return ctx->lean_first && !ctx->has_catcher && !ctx->sc.d_mesh_tex; }
 
 // the streams and arrays of the (empty) batch sets
 static int build_path_state(pt_ctx* ctx, int nsets, uint32_t cap, uint32_t pix_cap, int nq, bool async) {
@@ -1465,6 +1471,11 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
     const int last_bounce = std::max(0, (ctx->has_catcher ? ctx->opt.max_depth : ctx->opt.max_depth - 1) - depth0);
     const bool lit = ctx->has_catcher || ctx->opt.max_depth > 0; // some launch of the chain can queue a shadow ray
     const int aov = job ? (job->var.write_aov && job->var.initial_depth == 0 ? 1 : 0) : 1;
+    // The first-hit word (PT_LEAN_FIRST): plain frames of eligible scenes; a foveated launch keeps pflags / nrm / alb.  The set's PathState
+    // carries the layout to every launch of the chunk (it is copied at each launch).
+    bs.st.hitword = hitword_eligible(ctx) && !job ? 1u : 0u;
+    lc.hitword += bs.st.hitword;
+    const HitTables ht{ctx->sc.d_tri_nrm, ctx->sc.d_mats};
     for (uint32_t s0 = 0; s0 < spp; s0 += S) {
         const uint32_t Sc = std::min(S, spp - s0);
         // Persistent traversal waves of this pass's launches.  A synchronous frame wants the full grid (5 waves per SIMD): its latency is what
@@ -1591,11 +1602,11 @@ static void enqueue_chunk(pt_ctx* ctx, pt_ctx::BatchSet& bs, const FrameParams& 
             if (job)
                 hipLaunchKernelGGL(k_resolve_region, dim3((job->nl + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, job->rg, PartParams{ctx->rank, ctx->world, ctx->tile_w, ctx->tile_h}, job->var, job->l0, job->nl);
             else if (mode.moments)
-                hipLaunchKernelGGL(k_resolve_moments, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp, mode.moments);
+                hipLaunchKernelGGL(k_resolve_moments, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp, ht, mode.moments);
             else if (mode.vp.views)
-                hipLaunchKernelGGL(k_resolve_views, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp, mode.vp);
+                hipLaunchKernelGGL(k_resolve_views, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp, ht, mode.vp);
             else
-                hipLaunchKernelGGL(k_resolve, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp);
+                hipLaunchKernelGGL(k_resolve, dim3((npix + ewg - 1) / ewg), dim3(ewg), 0, bs.stream, bs.st, fp, bp, ht);
         }
     }
 }
@@ -1866,7 +1877,7 @@ static int render_enqueue(pt_ctx* ctx, uint32_t spp, uint32_t subframe_index, in
             int wrc = 0;
             for (uint32_t c = 1; c < nchunks; ++c) wrc |= enqueue_worker_wait(ctx->chunk_workers[c - 1].get());
             if (wrc != 0) return fail(ctx, PT_ERR_HIP, "pt_render: a chunk's enqueue thread failed");
-            for (const LaunchCounts& l : lcs) { lc.trace += l.trace; lc.shadow += l.shadow; lc.shade += l.shade; lc.fused += l.fused; lc.carry += l.carry; }
+            for (const LaunchCounts& l : lcs) { lc.trace += l.trace; lc.shadow += l.shadow; lc.shade += l.shade; lc.fused += l.fused; lc.carry += l.carry; lc.hitword += l.hitword; }
         } else {
             uint32_t k = 0;
             for (uint32_t pix0 = 0; pix0 < owned; pix0 += Np, ++k)
@@ -1966,7 +1977,7 @@ static int render_finish(pt_ctx* ctx, int slot = 0) {
     hipEventElapsedTime(&ms, ev_begin, ev_end);
     st.render_ms = ms;
     sched_record(ctx, slot, ms);
-    st.schedule = ctx->sched_flags | (lc.carry ? 0x200u : 0u);
+    st.schedule = ctx->sched_flags | (lc.carry ? 0x200u : 0u) | (lc.hitword ? 0x400u : 0u);
     st.sched_chain_ms = ctx->sched.best[0];
     st.sched_fused_ms = ctx->sched.best[1];
     double cls_ms[4] = {0, 0, 0, 0};

@@ -60,7 +60,14 @@ struct PathState {
     float4 *sO, *sD, *pendB;
     uint32_t* vis;
     uint32_t bstride;
+    // The first-hit word (PT_LEAN_FIRST; plain frames of scenes without catchers and without textures): hitword != 0 — pflags
+    // holds the path's FIRST-HIT WORD and nrm / alb are not touched.  HITWORD_NONE (generate: no hit yet; a miss leaves it) or
+    // leaf | flip << 31 of the depth-0 hit, flip = the sign bit of dot(-dir, N_0) as faceforward3's copysignf sees it.  The resolve kernels
+    // rebuild 0 + (±N_0) and 0 + mats[mesh].color from tri_nrm[leaf] (first_hit_aovs).  pt_create refuses more than 89 M leaf triangles,
+    // so no index reaches the code.
+    uint32_t hitword;
 };
+#define HITWORD_NONE 0xffffffffu
 
 struct FrameParams { // LaunchParams (LaunchParams.h:51-79) minus the OptiX handle and the dead light
     float4* accum;
@@ -215,7 +222,7 @@ PT_DEV void generate_path(const PathState& st, const FrameParams& fp, const Batc
     st.rayO[pos] = make_float4(cam.eye.x, cam.eye.y, cam.eye.z, 0.001f);
     st.rayD[pos] = make_float4(dir.x, dir.y, dir.z, 1e16f);
     st.rf[pos] = make_uint4(r.seed1, r.seed2, 0u, 0u);
-    st.pflags[i] = 0u;
+    st.pflags[i] = st.hitword ? HITWORD_NONE : 0u;
     if (st.vis) st.vis[i] = 0u;
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     st.direct[i] = z;
@@ -328,7 +335,7 @@ PT_DEV void shade_miss(const PathState& st, const ShadeParams& sp, uint32_t pos,
     if (CATCHER) {
         st.prdN[p] = make_float4(0.f, 0.f, 0.f, 0.f);
         st.prdA[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else if (sp.aov && (reinterpret_cast<const uint32_t*>(st.rf + pos)[2] & 0xffu) == 0u) { // primary miss: normal += 0, albedo += 0 (:424-427)
+    } else if (sp.aov && !st.hitword && (reinterpret_cast<const uint32_t*>(st.rf + pos)[2] & 0xffu) == 0u) { // primary miss: normal += 0, albedo += 0 (:424-427); first-hit word: stays HITWORD_NONE
         st.nrm[p] = make_float4(0.f, 0.f, 0.f, 0.f);
         st.alb[p] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -420,7 +427,11 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
         thr_out = th;
         const v3 ray_o = mk3(o4.x, o4.y, o4.z), ray_dir = mk3(d4.x, d4.y, d4.z);
         const v3 N_0 = mk3(tn.x, tn.y, tn.z); // normalize(cross(v1 - v0, v2 - v0)) (:491), evaluated once per triangle by the same device code
-        const v3 N = faceforward3(N_0, neg3(ray_dir), N_0);
+        const float ffd = dot3(neg3(ray_dir), N_0);
+        const v3 N = scl3(N_0, copysignf(1.0f, ffd)); // faceforward3(N_0, -ray_dir, N_0), its dot product named for the first-hit word
+        // The first-hit word (PathState::hitword) in the place of the FLAG_HIT0 store below: the triangle and the side the resolve kernels rebuild
+        // the depth-0 normal and albedo from.  Stored here, where the dot product dies, so that it holds no register across the light sample.
+        if (!CATCHER && st.hitword && !(flags & FLAG_HIT0)) st.pflags[p] = (uint32_t)leaf | (__float_as_uint(ffd) & 0x80000000u);
         const v3 P = add3(ray_o, scl3(ray_dir, h.x));
         P_out = P;
         const bool is_catcher = (mat.flags & 1) != 0;
@@ -515,7 +526,7 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
             if (CATCHER) {
                 if (!is_catcher) st.alpha[p] = make_float4(1.f, 1.f, 1.f, 0.f); // :547
             } else {
-                if (!(flags & FLAG_HIT0)) st.pflags[p] = FLAG_HIT0; // :547 — every hit assigns the same value: one bit, written by the path's first hit
+                if (!(flags & FLAG_HIT0) && !st.hitword) st.pflags[p] = FLAG_HIT0; // :547 — every hit assigns the same value: one bit, written by the path's first hit (or the first-hit word, above)
                 flags |= FLAG_HIT0;
             }
             const bool primary = (flags & FLAG_SECONDARY) == 0;
@@ -550,7 +561,7 @@ PT_DEV void shade_path(const PathState& st, const ShadeParams& sp, const ProbeMa
                     const float4 a = st.nrm[p], b = st.alb[p];
                     st.nrm[p] = make_float4(a.x + N.x, a.y + N.y, a.z + N.z, 0.f);
                     st.alb[p] = make_float4(b.x + albedo.x, b.y + albedo.y, b.z + albedo.z, 0.f);
-                } else if (sp.aov) { // the only depth-0 closest hit of this path: 0 + x, written once (0 + -0 = +0 as in the sum)
+                } else if (sp.aov && !st.hitword) { // the only depth-0 closest hit of this path: 0 + x, written once (0 + -0 = +0 as in the sum)
                     st.nrm[p] = make_float4(0.f + N.x, 0.f + N.y, 0.f + N.z, 0.f);
                     st.alb[p] = make_float4(0.f + albedo.x, 0.f + albedo.y, 0.f + albedo.z, 0.f);
                 }
@@ -757,6 +768,23 @@ PT_DEV void record_moments(float4* __restrict__ moments, size_t image_index, v3 
     m.z = m.z + x * x;
     moments[image_index] = m;
 }
+// What the resolve kernels need of the scene to rebuild the first-hit normal and albedo from the first-hit word (PathState::hitword)
+struct HitTables {
+    const float4* tri_nrm;     // ShadeParams::tri_nrm
+    const pt_material* mats;
+};
+// The depth-0 normal and albedo of a path from its first-hit word, as shade_path stored them: 0 + N_0 * (±1) (faceforward3's product) and
+// 0 + mat.color.  A path that hit nothing adds +0, the value the primary miss used to store.  Returns prd.alpha's bit.
+PT_DEV bool first_hit_aovs(const HitTables& ht, uint32_t word, float4& nn, float4& al) {
+    nn = al = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (word == HITWORD_NONE) return false;
+    const float4 tn = ht.tri_nrm[word & 0x7fffffffu];
+    const pt_material* mat = ht.mats + __float_as_int(tn.w);
+    const float s = __uint_as_float(0x3f800000u | (word & 0x80000000u)); // copysignf(1, dot(-dir, N_0))
+    nn = make_float4(0.f + tn.x * s, 0.f + tn.y * s, 0.f + tn.z * s, 0.f);
+    al = make_float4(0.f + mat->color[0], 0.f + mat->color[1], 0.f + mat->color[2], 0.f);
+    return true;
+}
 // One pass over bp.S virtual samples of every pixel of the chunk.  Samples are summed in order; whenever a subframe's last sample
 // has been added the raygen epilogue runs for that subframe (:445-474) — blending with the PREVIOUS subframe's accum value, which is
 // the register of this loop when the previous subframe was completed in the same pass and accum_buffer otherwise — so that a batch
@@ -767,7 +795,7 @@ PT_DEV void record_moments(float4* __restrict__ moments, size_t image_index, v3 
 // flag is a template parameter so that k_resolve itself stays the code it was.
 // VIEWS (k_resolve_views, frames with viewports): the backplate's ray is the one of the pixel's view; the buffers are indexed by frame pixel.
 template <bool MOMENTS, bool VIEWS = false>
-PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const BatchParams& bp, float4* __restrict__ moments, const ViewParams& vp = ViewParams{}) {
+PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const BatchParams& bp, const HitTables& ht, float4* __restrict__ moments, const ViewParams& vp = ViewParams{}) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= bp.npix) return;
     v3 result = mk3(0.f), alpha = mk3(0.f), normal = mk3(0.f), albedo = mk3(0.f);
@@ -789,13 +817,19 @@ PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const Batc
     for (uint32_t vl = 0; vl < bp.S; ++vl) {
         const uint32_t i = vl * bp.npix + pix;
         float4 d = st.direct[i], in = st.indirect[i];
-        const float4 nn = st.nrm[i], al = st.alb[i];
-        float4 a;
-        if (st.prdN) {
-            a = st.alpha[i];
-        } else {
-            const float hit0 = (st.pflags[i] & FLAG_HIT0) ? 1.0f : 0.0f;
+        float4 nn, al, a;
+        if (st.hitword) {
+            const float hit0 = first_hit_aovs(ht, st.pflags[i], nn, al) ? 1.0f : 0.0f;
             a = make_float4(hit0, hit0, hit0, 0.f);
+        } else {
+            nn = st.nrm[i];
+            al = st.alb[i];
+            if (st.prdN) {
+                a = st.alpha[i];
+            } else {
+                const float hit0 = (st.pflags[i] & FLAG_HIT0) ? 1.0f : 0.0f;
+                a = make_float4(hit0, hit0, hit0, 0.f);
+            }
         }
         apply_visible_contributions(st, i, d, in);
         // result += directLight + indirectLight; alpha += prd.alpha (:445-446)
@@ -859,11 +893,11 @@ PT_DEV void resolve_pixel(const PathState& st, const FrameParams& fp, const Batc
     fp.color[image_index] = make_float4(accum_cur.x, accum_cur.y, accum_cur.z, 1.0f);
     fp.albedo[image_index] = make_float4(albedo_fin.x, albedo_fin.y, albedo_fin.z, 1.0f);
 }
-__global__ void __launch_bounds__(256) k_resolve(PathState st, FrameParams fp, BatchParams bp) { resolve_pixel<false>(st, fp, bp, nullptr); }
-__global__ void __launch_bounds__(256) k_resolve_moments(PathState st, FrameParams fp, BatchParams bp, float4* __restrict__ moments) {
-    resolve_pixel<true>(st, fp, bp, moments);
+__global__ void __launch_bounds__(256) k_resolve(PathState st, FrameParams fp, BatchParams bp, HitTables ht) { resolve_pixel<false>(st, fp, bp, ht, nullptr); }
+__global__ void __launch_bounds__(256) k_resolve_moments(PathState st, FrameParams fp, BatchParams bp, HitTables ht, float4* __restrict__ moments) {
+    resolve_pixel<true>(st, fp, bp, ht, moments);
 }
-__global__ void __launch_bounds__(256) k_resolve_views(PathState st, FrameParams fp, BatchParams bp, ViewParams vp) { resolve_pixel<false, true>(st, fp, bp, nullptr, vp); }
+__global__ void __launch_bounds__(256) k_resolve_views(PathState st, FrameParams fp, BatchParams bp, HitTables ht, ViewParams vp) { resolve_pixel<false, true>(st, fp, bp, ht, nullptr, vp); }
 // pt_set_view_cameras_device: n x 12 floats (eye, U, V, W) of the caller's device array into the camera part of the view records
 __global__ void __launch_bounds__(256) k_view_cameras(const float* __restrict__ cams, uint32_t n, pt_view* __restrict__ views) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
