@@ -2073,8 +2073,7 @@ int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void* tris, size
  *   - PT_UPDATE_REFIT keeps the tree's topology and recomputes its boxes on the GPU (leaf triangles, then one launch per level, deepest
  *     first).  Images are those of a fresh pt_create over the new vertices, bit for bit (a hit does not depend on the tree); the traversal
  *     cost grows as the vertices drift from where the tree was built — rebuild when frames get slower.  The calibration cost is kept,
- *     the on-line chain/fused schedule trial starts over.  Builds with PT8_NODE64 return PT_ERR_UNSUPPORTED (that node's origin grid is
- *     fixed to the scene bounds of the build);
+ *     the on-line chain/fused schedule trial starts over;
  *   - PT_UPDATE_REBUILD runs the whole build of pt_create over the new vertices (calibration, stack-depth check, pt_stats.bvh_build_ms)
  *     into a new tree, then swaps it in;
  *   - kernel_ms (may be NULL): device time of the update (hipEvents around its kernels; the host-to-device copy is not included). */
@@ -2100,7 +2099,7 @@ int pt_multi_update_meshes(pt_multi* m, const pt_mesh_update* updates, uint32_t 
  *   - only vertex positions change;
  *   - one call does ONE refit or ONE rebuild and is atomic: on any error the context is exactly as before;
  *   - it waits for the frames in flight and is complete when it returns; accum_buffer is left alone;
- *   - the on-line chain/fused schedule trial starts over; PT_UPDATE_REFIT on a PT8_NODE64 build returns PT_ERR_UNSUPPORTED;
+ *   - the on-line chain/fused schedule trial starts over;
  *   - kernel_ms (may be NULL) covers the staging kernel as well as the refit or the build.
  * Device pointers:
  *   - the library reads them on pt_stream(ctx), under the STREAM CONTRACT: an array produced on another stream must be complete, or ordered

@@ -1312,11 +1312,7 @@ static void launch_trace8(hipStream_t stream, unsigned tgrid, const Trace8Args& 
     hipLaunchKernelGGL((k_trace8<MODE>), dim3(tgrid), dim3(64), 0, stream, ta);
 }
 static Bvh8Dev bvh_dev(const pt_ctx* ctx) {
-#if PT8_NODE64
-    return Bvh8Dev{ctx->bvh.nodes8, ctx->bvh.tris8, 0.5f * ctx->bvh.pad, ctx->bvh.grid};
-#else
     return Bvh8Dev{ctx->bvh.nodes8, ctx->bvh.tris8, 0.5f * ctx->bvh.pad};
-#endif
 }
 static void launch_closest(pt_ctx* ctx, hipStream_t stream, const Trace8Args& ta, unsigned tgrid, uint64_t paths) {
     if (ta.queue.base == nullptr && ctx->cam_packets && paths >= ctx->cam_min_paths) {
@@ -1910,9 +1906,6 @@ static int debug_report(pt_ctx* ctx) {
                 fclose(f);
             }
         }
-        if (h[53] + h[54] + h[55] + h[56]) // -DPT_DEBUG_WAVELOG=3 builds
-            fprintf(stderr, "[pt_render] traversal iterations by lanes active at their start (<=8 | <=16 | <=32 | more): %llu %llu %llu %llu; cycles: %llu %llu %llu %llu\n",
-                    h[53], h[54], h[55], h[56], h[57], h[58], h[59], h[60]);
         if (h[61]) // PT_DEBUG_STATS builds
             fprintf(stderr, "[pt_render] closest-hit programs %llu, light sample's arc below the surface (column search skipped) %llu = %.2f %%, of them the whole latitude circle %llu = %.2f %%\n",
                     h[61], h[62], 100.0 * (double)h[62] / (double)h[61], h[47], 100.0 * (double)h[47] / (double)h[61]);

@@ -29,38 +29,11 @@
 #else
 #include "pt_kernels.h"
 #endif
-#include "pt_host.h" // Grid8
 
-// The documented 80-byte node (above): what pt_export_bvh hands out whatever the kernels traverse
-struct Node80 {
+// The 80-byte node documented above: what the kernels traverse and what pt_export_bvh hands out
+struct Node8 {
     float4 n0, n1, n2, n3, n4;
 };
-// One-line node (PT8_NODE64, round 5): the same eight quantised child boxes in 64 bytes, 64-byte aligned — four
-// 16-byte loads from ONE line instead of five from a record that straddles two 128-byte lines four times in eight; the node array
-// shrinks by 20 %.  What pays for it: the grid origin is no longer three floats but three integers on a grid over the scene's (padded)
-// bounds (14 / 13 / 14 bits, rounded DOWN so the box only grows, by less than 1 / 8192 of the scene per axis), the grid steps are powers
-// of two (a 5-bit exponent per axis above the tree's base exponent: up to twice as coarse as the 80-byte node's 8-significant-bit
-// steps), child and triangle bases have 24 bits (16.7 M nodes / leaf triangles), and the triangle counts of the leaf slots are two bit
-// planes (count = b0 + 2 b1) instead of three unary bits per slot.
-//   h.x: child_base | imask << 24
-//   h.y: tri_base | ex << 24 | oy[0:3] << 29
-//   h.z: b0 | b1 << 8 | ey << 16 | ez << 21 | oy[3:9] << 26
-//   h.w: ox | oz << 14 | oy[9:13] << 28
-//   q0, q1, q2: qlo.x[8] qlo.y[8] | qlo.z[8] qhi.x[8] | qhi.y[8] qhi.z[8] — the 80-byte node's n2, n3, n4
-// origin.a = fma(o.a, gstep.a, glo.a), step.a = 2^(ebase + e.a - 127): Bvh8Dev carries glo, gstep, ebase.
-struct Node64 {
-    uint4 h, q0, q1, q2;
-};
-#ifndef PT8_NODE64
-#define PT8_NODE64 0
-#endif
-#if PT8_NODE64
-struct Node8 : Node64 {};
-#else
-struct Node8 : Node80 {};
-#endif
-#define PT8_GRID_BITS_XZ 14
-#define PT8_GRID_BITS_Y 13
 #ifndef PT8_LEAF_MAX
 #define PT8_LEAF_MAX 3
 #endif
@@ -72,45 +45,14 @@ struct Bvh8Dev {
     const Node8* nodes;
     const LeafTri* tris;
     float hit_pad; // half the builder's box padding (pt_bvh.h tri_test_det)
-#if PT8_NODE64
-    Grid8 grid;
-#endif
 };
 
-// What a traversal step needs of a node's first 16 / 32 bytes, in either layout
+// What a traversal step needs of a node's first 32 bytes
 struct NodeHdr {
     float ox, oy, oz, sx, sy, sz;
     uint32_t imask, child_base, tri_base;
-    uint32_t lbits; // triangle counts of the leaf slots: 80-byte node: bit 3 s + k = slot s holds more than k; one-line node: b0 | b1 << 8
+    uint32_t lbits; // triangle counts of the leaf slots: bit 3 s + k = slot s holds more than k
 };
-#if PT8_NODE64
-PT_DEV NodeHdr node_hdr(const uint4 h, const Grid8& b) {
-    NodeHdr n;
-    n.child_base = h.x & 0xffffffu;
-    n.imask = h.x >> 24;
-    n.tri_base = h.y & 0xffffffu;
-    n.lbits = h.z & 0xffffu;
-    n.sx = __uint_as_float((b.ebase + ((h.y >> 24) & 31u)) << 23);
-    n.sy = __uint_as_float((b.ebase + ((h.z >> 16) & 31u)) << 23);
-    n.sz = __uint_as_float((b.ebase + ((h.z >> 21) & 31u)) << 23);
-    const uint32_t oyq = (h.y >> 29) | ((h.z >> 26) << 3) | ((h.w >> 28) << 9);
-    n.ox = __builtin_fmaf((float)(h.w & 0x3fffu), b.gstep[0], b.glo[0]);
-    n.oy = __builtin_fmaf((float)oyq, b.gstep[1], b.glo[1]);
-    n.oz = __builtin_fmaf((float)((h.w >> 14) & 0x3fffu), b.gstep[2], b.glo[2]);
-    return n;
-}
-// pending (slot, k) pairs of the leaf slots in `hm`: bit 8 k + s
-PT_DEV uint32_t leaf_pending(uint32_t hm, uint32_t lbits) {
-    const uint32_t b0 = lbits & 0xffu, b1 = lbits >> 8;
-    return ((b0 | b1) & hm) | ((b1 & hm) << 8) | ((b0 & b1 & hm) << 16);
-}
-PT_DEV uint32_t leaf_first(uint32_t tri_base, uint32_t lbits, uint32_t s) { // index of the first triangle of leaf slot s
-    const uint32_t low = (1u << s) - 1u;
-    return tri_base + (uint32_t)__popc(lbits & low) + 2u * (uint32_t)__popc((lbits >> 8) & low);
-}
-PT_DEV uint32_t leaf_of(uint32_t tri_base, uint32_t lbits, uint32_t bit) { return leaf_first(tri_base, lbits, bit & 7u) + (bit >> 3); }
-PT_DEV uint32_t leaf_count(uint32_t lbits, uint32_t s) { return ((lbits >> s) & 1u) + 2u * ((lbits >> (8u + s)) & 1u); }
-#else
 PT_DEV NodeHdr node_hdr(const float4 n0, const float4 n1) {
     NodeHdr n;
     const uint32_t e01 = __float_as_uint(n0.w), e2m = __float_as_uint(n1.w);
@@ -132,27 +74,6 @@ PT_DEV uint32_t leaf_pending(uint32_t hm, uint32_t lbits) {
 PT_DEV uint32_t leaf_of(uint32_t tri_base, uint32_t lbits, uint32_t bit) { return tri_base + (uint32_t)__popc(lbits & ((1u << bit) - 1u)); }
 PT_DEV uint32_t leaf_first(uint32_t tri_base, uint32_t lbits, uint32_t s) { return leaf_of(tri_base, lbits, 3u * s); }
 PT_DEV uint32_t leaf_count(uint32_t lbits, uint32_t s) { return (uint32_t)__popc((lbits >> (3u * s)) & 7u); }
-#endif
-
-#if PT8_NODE64
-// pt_export_bvh / PT_DEBUG_BVH: one-line nodes as the documented 80-byte records — the same origin and (power-of-two) steps as floats,
-// the same planes, the leaf counts as three unary bits per slot: the tree the kernels traverse, box for box
-static __global__ void k_nodes_to80(const Node64* __restrict__ in, uint32_t n, Grid8 b, Node80* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Node64 nd = in[i];
-    const NodeHdr h = node_hdr(nd.h, b);
-    uint32_t leafbits = 0u;
-    for (uint32_t s = 0; s < 8u; ++s) leafbits |= ((1u << leaf_count(h.lbits, s)) - 1u) << (3u * s);
-    Node80 o;
-    o.n0 = make_float4(h.ox, h.oy, h.oz, __uint_as_float((__float_as_uint(h.sx) >> 16) | (__float_as_uint(h.sy) & 0xffff0000u)));
-    o.n1 = make_float4(__uint_as_float(h.child_base), __uint_as_float(h.tri_base), __uint_as_float(leafbits), __uint_as_float((__float_as_uint(h.sz) >> 16) | (h.imask << 16)));
-    o.n2 = make_float4(__uint_as_float(nd.q0.x), __uint_as_float(nd.q0.y), __uint_as_float(nd.q0.z), __uint_as_float(nd.q0.w));
-    o.n3 = make_float4(__uint_as_float(nd.q1.x), __uint_as_float(nd.q1.y), __uint_as_float(nd.q1.z), __uint_as_float(nd.q1.w));
-    o.n4 = make_float4(__uint_as_float(nd.q2.x), __uint_as_float(nd.q2.y), __uint_as_float(nd.q2.z), __uint_as_float(nd.q2.w));
-    out[i] = o;
-}
-#endif
 
 #ifndef PT_BVH8_NODE_ONLY
 #ifndef PT8_LDS_DEPTH
@@ -168,12 +89,6 @@ static __global__ void k_nodes_to80(const Node64* __restrict__ in, uint32_t n, G
 #ifndef PT8_MIN_CHUNK
 #define PT8_MIN_CHUNK 64
 #endif
-#ifndef PT8_INTERLEAVE
-#define PT8_INTERLEAVE 0 // > 0: launches of one static chunk per wave and at least this many rays deal their rays to the waves round robin
-#endif
-#ifndef PT8_WIDE_MIN
-#define PT8_WIDE_MIN 64 // rays per wave at least in a launch smaller than the grid (64: one full chunk per wave, as before)
-#endif
 #define PT8_CHUNK 512
 #ifndef PT8_WAVES_PER_EU
 #define PT8_WAVES_PER_EU 5
@@ -187,32 +102,19 @@ static __global__ void k_nodes_to80(const Node64* __restrict__ in, uint32_t n, G
 // writes the ray's result.  The answer is the minimum over the same set of accepted triangles whatever the split, so
 // images do not change by a bit; what changes is that a 500-step ray that used to hold its wave (and the launch: 9 launches
 // per frame, each as long as its longest ray) for 500 iterations is traversed by up to 64 lanes.
-#ifndef PT8_STEAL
-#define PT8_STEAL 1
-#endif
 // (a lane may be robbed from its first step: requiring 24 / 64 prior steps of the victim cost +13 % / +26 % frame time at a 1/8 share)
-#ifndef PT8_DEFER_WRITE
-#define PT8_DEFER_WRITE 1
-#endif
 #ifndef PT8_STEAL_PERIOD
 #define PT8_STEAL_PERIOD 3 // traversal iterations between two steal rounds while lanes are idle
 #endif
 
 // The stealing phase is where a small launch spends its whole life, one wave per SIMD, and there every stall is paid in full (per-wave cycle
 // log, profiles/r5_15_tail_cycles.md: of 4500 cycles per iteration only 650 wait for the step's own loads).
-// PT8_STEAL_WSYNC: the lanes of a steal round talk through LDS only and the workgroup IS one wave, whose LDS operations execute in order — a
+// PT8_WAVE_SYNC: the lanes of a steal round talk through LDS only and the workgroup IS one wave, whose LDS operations execute in order — a
 //   compiler-level barrier orders them; __syncthreads() also drains every outstanding global load and store (vmcnt(0)), twice per round:
 //   1/8 share 1.803 -> 1.781 ms, full frame 7.881 -> 7.844.
 // (Measured and rejected with it: writing back the rays that finish in the stealing phase together, at the top of the outer loop, like those
 // that finish before it, instead of one by one where they finish: 1/8 share 1.78 -> 1.90 ms, full frame 7.84 -> 8.16.)
-#ifndef PT8_STEAL_WSYNC
-#define PT8_STEAL_WSYNC 1
-#endif
-#if PT8_STEAL_WSYNC
 #define PT8_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-#else
-#define PT8_WAVE_SYNC() __syncthreads()
-#endif
 
 #define PT_WAVELOG_CAP (1u << 20)
 #ifdef PT_DEBUG_STATS
@@ -220,7 +122,7 @@ static __global__ void k_nodes_to80(const Node64* __restrict__ in, uint32_t n, G
 #else
 #define PT_STAT(x)
 #endif
-// PT_DEBUG_WAVELOG builds (tools/r5_wavelog.sh): every traversal wave logs its start, the start of its stealing phase, its end and its loop
+// -DPT_DEBUG_WAVELOG builds (tools/r5_wavelog.sh): every traversal wave logs its start, the start of its stealing phase, its end and its loop
 // iterations — one atomic per WAVE, so launch timing stays what it is (PT_DEBUG_STATS pays same-address atomics per ray: 10 x the frame time)
 #if defined(PT_DEBUG_STATS) || defined(PT_DEBUG_WAVELOG)
 #define PT_WLOG(x) x
@@ -244,9 +146,6 @@ struct Trace8Args {
     int ovf_depth;  // spill levels available (PT8_OVF_DEPTH; the test hook PT_STACK_CAP lowers it)
     uint32_t* fault; // device word: bit 0 set when a push found the stack full — the host turns it into PT_ERR_UNSUPPORTED
     uint32_t num_nodes;
-#if PT_DEBUG_WAVELOG + 0 == 3
-    unsigned long long* hist; // dbg + 53 (set from dbg by the kernels' entry points; survives the fused loop's `dbg = nullptr`)
-#endif
 };
 
 // the traversal stack's two homes, each a pointer type of its own address space (the host pass only parses the device code)
@@ -267,13 +166,11 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     __shared__ uint32_t s_stack[PT8_LDS_DEPTH * 2 * 64];
     __shared__ uint32_t s_prefix[PT_NSUB + 1];
     __shared__ uint32_t s_prefix2[PT_NSUB + 1];
-#if PT8_STEAL
     __shared__ unsigned long long s_key[64]; // per owner lane: merged result of the ray that lane loaded
     __shared__ uint32_t s_cnt[64];           // per owner lane: co-workers still traversing that ray
     __shared__ int32_t s_leaf[64];           // per owner lane: leaf triangle of the hit s_key holds (written by whoever lowered the key — one wave per
                                              // workgroup, so after every lane's atomic minimum exactly the lanes whose key IS the minimum write it)
     __shared__ uint32_t s_vlane[64];         // steal round: victim lane by rank
-#endif
     const uint32_t lane = threadIdx.x;
     const uint32_t gtid = blockIdx.x * 64u + lane;
     const uint32_t gstride = gridDim.x * 64u;
@@ -284,16 +181,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     const uint32_t n = n1 + n2;
     uint32_t chunk = (n / (nw * 2u)) & ~(uint32_t)(PT8_MIN_CHUNK < 64 ? PT8_MIN_CHUNK - 1 : 63);
     chunk = chunk < (uint32_t)PT8_MIN_CHUNK ? (uint32_t)PT8_MIN_CHUNK : (chunk > (uint32_t)PT8_CHUNK ? (uint32_t)PT8_CHUNK : chunk);
-#if PT8_WIDE_MIN < 64
-    // Wide start (round 5): a launch with fewer rays than the grid has lanes is not throughput-bound but as long as its slowest ray's chain of
-    // dependent steps (1.5 us each with a lone wave on a SIMD).  Such a launch is spread over more waves — ceil(n / waves) rays each, at least
-    // PT8_WIDE_MIN — whose spare lanes take stack entries of the wave's rays from the first iteration on (the stealing phase below), so a
-    // ray's subtrees are traversed side by side.  The split is static: no chunk counter is touched.
-    if (n < nw * 64u) {
-        chunk = ((n + nw - 1u) / nw + 15u) & ~15u;
-        chunk = chunk < (uint32_t)PT8_WIDE_MIN ? (uint32_t)PT8_WIDE_MIN : chunk;
-    }
-#endif
     if (LOCAL) chunk = n; // one chunk: this wave's
     const bool no_share = (unsigned long long)wid * chunk >= n; // this wave has no chunk of its own
     const uint32_t nchunks = (n + chunk - 1u) / chunk;
@@ -323,19 +210,15 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
 #define SET_OWNER(v) (misc = (misc & ~0xffu) | (uint32_t)(v))
 #define SET_SB(v) (misc = (misc & 0x00ffffffu) | ((uint32_t)(v) << 24))
     uint32_t slot = 0; // position of the lane's ray in its queue's arrays (PathState)
-#if PT8_DEFER_WRITE
     bool unwritten = false; // this lane holds a finished ray whose result is not written yet
-#endif
     PT_STAT(uint32_t c_nodes = 0; uint32_t c_tris = 0; uint32_t c_maxsp = 0; uint32_t c_push = 0; uint32_t c_ray = 0; uint32_t c_raymax = 0; uint32_t c_iters = 0;
             uint32_t c_act = 0; uint32_t c_exec = 0; uint32_t c_nodeit = 0;)
     PT_WLOG(const unsigned long long w_t0 = wall_clock64(); unsigned long long w_tex = 0; uint32_t w_iters = 0;)
-    PT_WLOG(unsigned long long w_cw = 0; unsigned long long w_cr = 0; unsigned long long w_cs = 0; uint32_t w_np = 0;) // -DPT_DEBUG_WAVELOG=2: cycles in the loop-top write-back | refill | steal round, outer passes
+    // cycles in the loop-top write-back | refill | steal round, outer passes: what the fine log wrote out (tools/patches/fine_wave_log.patch).  Its probes —
+    // a clock read and a full wait after the write-back and after the refill — stay in the log that is left, whose machine code and timings
+    // (profiles/r5_15_tail_cycles.md) are thereby what they were; the sums themselves go nowhere.
+    PT_WLOG(unsigned long long w_cw = 0; unsigned long long w_cr = 0; unsigned long long w_cs = 0; uint32_t w_np = 0;)
     PT_WLOG(unsigned long long w_c01 = 0; unsigned long long w_c12 = 0; unsigned long long w_c23 = 0; const unsigned long long w_c0 = clock64();) // shader-clock cycles: vote + pop + addresses | waiting for the loads | arithmetic
-#if PT_DEBUG_WAVELOG + 0 == 3
-    // round 6 (sizing a several-lanes-per-ray mode): iterations and cycles of this wave by the number of lanes that held a ray (or a stolen share of one)
-    // at the top of the iteration: <= 8 | <= 16 | <= 32 | more — summed over all waves and launches of a frame in dbg[53..60]
-    unsigned long long h_i0 = 0, h_i1 = 0, h_i2 = 0, h_i3 = 0, h_c0 = 0, h_c1 = 0, h_c2 = 0, h_c3 = 0;
-#endif
 
     // a record's address is the array's wave-uniform base plus a 32-bit byte offset (pt_create refuses arrays of more than 4 GiB): one multiply, no 64-bit pair
     const char* const node_bytes = reinterpret_cast<const char*>(a.bvh.nodes);
@@ -380,11 +263,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     auto write_result = [&](float rbest, int32_t rprim) {
         if (MODE == TR_SHADOW_APPLY || (MODE == TR_UNIFIED && shadow_lane)) {
             const bool occluded = rprim != 0;
-#ifdef PT_ABL_NO_SHADOW_WB
-            // timing-attribution build (like the PT_ABL_* of k_shade, images wrong by construction): what the write-back of the unified launch's
-            // shadow lanes costs the frame — the most that carrying the sums with the path (PT_CARRY_SUMS) can give
-            if (MODE == TR_UNIFIED) return;
-#endif
             if (MODE == TR_UNIFIED && CARRY) { // carried sums (PT_CARRY_SUMS): one visibility word per shadow ray, dense; k_shade adds the contribution
                 st_st<PT_NT_TRACE_ST>(&a.st.svis[slot], occluded ? 0u : 1u);
                 return;
@@ -411,17 +289,14 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
         }
     };
     const auto is_shadow = [&]() { return MODE == TR_SHADOW_APPLY || MODE == TR_ANY_QUERY || (MODE == TR_UNIFIED && shadow_lane); };
-#if PT8_STEAL
     // 64-bit result key: closest hit = (bits of t) << 32 | primitive (t > 0, so the bits order like the floats; "no hit" is
     // (tmax, -1) = the largest key of the ray); shadow ray = 0 occluded / ~0 not occluded
     auto local_key = [&]() -> unsigned long long {
         if (is_shadow()) return bprim != 0 ? 0ull : ~0ull;
         return ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)bprim;
     };
-#endif
     // this lane is done with its (share of the) ray
     auto finish = [&]() {
-#if PT8_STEAL
         if (stealing) {
             atomicMin(&s_key[OWNER], local_key());
             if (atomicSub(&s_cnt[OWNER], 1u) == 1u) { // the last co-worker publishes the merged result
@@ -432,15 +307,10 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
             active = false;
             return;
         }
-#endif
-#if PT8_DEFER_WRITE
         // Before the stealing phase the result is not written here: a finish reached by one or two lanes at a time would stall the whole
         // wave on the write-back's dependent loads (pending contribution -> accumulator).  The lane keeps (slot, best, bprim) — it is
         // idle until the next refill — and all finished lanes write together at the top of the loop.
         unwritten = true;
-#else
-        write_result(best, is_shadow() ? bprim : bleaf);
-#endif
         active = false;
         PT_STAT(if (c_ray > c_raymax) c_raymax = c_ray;
                 if (a.dbg) atomicAdd(&a.dbg[(is_shadow() ? 32 : 16) + (31 - __clz((int)(c_ray | 1u)))], 1ull);
@@ -451,11 +321,7 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     auto start_ray = [&](float ox, float oy, float oz, float dx, float dy, float dz) {
         r.o = mk3(ox, oy, oz);
         r.d = mk3(dx, dy, dz);
-#ifdef PT8_IEEE_IDIR
-        r.idir = mk3(1.0f / dx, 1.0f / dy, 1.0f / dz);
-#else
         r.idir = mk3(__builtin_amdgcn_rcpf(dx), __builtin_amdgcn_rcpf(dy), __builtin_amdgcn_rcpf(dz));
-#endif
         r.dn = scl3(r.d, 1.0f / dot3(r.d, r.d));
         if (!(fabsf(dx) > 1e-30f)) r.idir.x = copysignf(1e30f, dx);
         if (!(fabsf(dy) > 1e-30f)) r.idir.y = copysignf(1e30f, dy);
@@ -469,12 +335,10 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
 
     for (;;) {
         PT_WLOG(const unsigned long long w_p0 = clock64(); ++w_np;)
-#if PT8_DEFER_WRITE
         if (unwritten) { // results of the rays that finished since the last pass: all finished lanes at once
             write_result(best, is_shadow() ? bprim : bleaf);
             unwritten = false;
         }
-#endif
         PT_WLOG(__builtin_amdgcn_s_waitcnt(0); const unsigned long long w_p1 = clock64(); w_cw += w_p1 - w_p0;)
         // ---------------- refill idle lanes
         const unsigned long long idle = __ballot(!active);
@@ -498,18 +362,8 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
             const uint32_t first = chunk_next;
             chunk_next += take;
             if (chunk_next == chunk_end && nchunks <= nw) exhausted = true; // the wave's only chunk is taken: its spare lanes start stealing at once
-#if PT8_INTERLEAVE
-            // A launch of one static chunk per wave: wave w's lane l takes ray l * (waves with a share) + w instead of ray 64 w + l, so every wave
-            // holds rays from all over the queue — which is in image order: a wave of 64 neighbouring camera rays that all graze the terrain has
-            // no idle lane to help (max / mean wave time 2.7-3.4 in camera launches of a 1/8 share, profiles/r5_01_wavelog_w8.txt).
-            const bool spread = nchunks <= nw && chunk == 64u && n >= (uint32_t)PT8_INTERLEAVE;
-            const uint32_t gi_spread = lane * (nchunks < nw ? nchunks : nw) + wid;
-            if (!active && (spread ? gi_spread < n : rank < take)) {
-                const uint32_t gi = spread ? gi_spread : first + rank;
-#else
             if (!active && rank < take) {
                 const uint32_t gi = first + rank;
-#endif
                 if (LOCAL) {
                     shadow_lane = (MODE == TR_SHADOW_APPLY) || (MODE == TR_UNIFIED && gi < n2);
                     slot = woff + ((MODE == TR_UNIFIED && !shadow_lane) ? gi - n2 : gi);
@@ -561,7 +415,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
             }
         }
         PT_WLOG(__builtin_amdgcn_s_waitcnt(0); const unsigned long long w_p2 = clock64(); w_cr += w_p2 - w_p1;)
-#if PT8_STEAL
         if (exhausted) {
             if (!stealing) { // the wave took its last chunk: from here on its rays are shared work
                 stealing = true;
@@ -633,7 +486,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                 }
             }
         }
-#endif
         PT_WLOG(w_cs += clock64() - w_p2;)
         unsigned long long act = __ballot(active);
         if (act == 0ull) break;
@@ -641,7 +493,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
         uint32_t it = 0;
         // ---------------- traverse
         do {
-#if PT8_STEAL
             if (stealing && active) { // pick up what the ray's other workers found
                 const unsigned long long k = s_key[OWNER];
                 if (is_shadow()) {
@@ -651,7 +502,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                     bprim = (int32_t)(uint32_t)k;
                 }
             }
-#endif
             PT_WLOG(const unsigned long long w_a = clock64();)
             const bool want_tri = active && t_mask != 0u;
             const bool want_node = active && t_mask == 0u; // node step also covers "group empty → pop"
@@ -689,17 +539,10 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                     const uint32_t idx = g_base + (uint32_t)__popc(g_imask & (h - 1u));
                     if (g_hits != 0u) push(g_base, g_imask | (g_hits << 8));
                     PT_STAT(++c_nodes; ++c_ray;)
-#if PT8_NODE64
-                    const float4* nd = reinterpret_cast<const float4*>(node_bytes + idx * (uint32_t)sizeof(Node8)); // one 64-byte line: header, then the planes
-                    const float4 n0 = nd[0], n2 = nd[1], n3 = nd[2], n4 = nd[3];
-                    PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
-                    const NodeHdr nh = node_hdr(make_uint4(__float_as_uint(n0.x), __float_as_uint(n0.y), __float_as_uint(n0.z), __float_as_uint(n0.w)), a.bvh.grid);
-#else
                     const Node8* nd = reinterpret_cast<const Node8*>(node_bytes + idx * (uint32_t)sizeof(Node8));
                     const float4 n0 = nd->n0, n1 = nd->n1, n2 = nd->n2, n3 = nd->n3, n4 = nd->n4;
                     PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
                     const NodeHdr nh = node_hdr(n0, n1);
-#endif
                     const uint32_t imask = nh.imask;
                     const float ax = nh.sx * r.idir.x, ay = nh.sy * r.idir.y, az = nh.sz * r.idir.z;
                     const float bx = (nh.ox - r.o.x) * r.idir.x, by = (nh.oy - r.o.y) * r.idir.y, bz = (nh.oz - r.o.z) * r.idir.z;
@@ -760,13 +603,11 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                         best = t;
                         bprim = prim;
                         bleaf = (int32_t)leaf;
-#if PT8_STEAL
                         if (stealing) {
                             const unsigned long long key = local_key();
                             atomicMin(&s_key[OWNER], key);
                             if (s_key[OWNER] == key) s_leaf[OWNER] = bleaf;
                         }
-#endif
                     }
                 }
             }
@@ -777,19 +618,10 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                 c_nodeit += node_step ? 1u : 0u;
             })
             PT_WLOG(++w_iters; w_c01 += w_b - w_a; w_c12 += w_c - w_b; w_c23 += clock64() - w_c;)
-#if PT_DEBUG_WAVELOG + 0 == 3
-            {
-                const uint32_t nact = (uint32_t)__popcll(act); // lanes that were active when the iteration began
-                const unsigned long long dt = clock64() - w_a;
-                if (nact <= 8u) { ++h_i0; h_c0 += dt; } else if (nact <= 16u) { ++h_i1; h_c1 += dt; } else if (nact <= 32u) { ++h_i2; h_c2 += dt; } else { ++h_i3; h_c3 += dt; }
-            }
-#endif
             act = __ballot(active);
             ++it;
-#if PT8_STEAL
             // with idle lanes around, return to the steal round every PT8_STEAL_PERIOD iterations
             if (stealing && act != ~0ull && it >= (uint32_t)PT8_STEAL_PERIOD) break;
-#endif
         } while ((uint32_t)__popcll(act) >= thresh);
     }
     PT_STAT(if (a.dbg) {
@@ -807,25 +639,14 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
             atomicAdd(&a.dbg[10], (unsigned long long)c_nodeit);
         }
     })
-#if PT_DEBUG_WAVELOG + 0 == 3
-    if (a.hist && lane == 0) {
-        atomicAdd(&a.hist[0], h_i0); atomicAdd(&a.hist[1], h_i1); atomicAdd(&a.hist[2], h_i2); atomicAdd(&a.hist[3], h_i3);
-        atomicAdd(&a.hist[4], h_c0); atomicAdd(&a.hist[5], h_c1); atomicAdd(&a.hist[6], h_c2); atomicAdd(&a.hist[7], h_c3);
-    }
-#endif
     PT_WLOG(if (a.dbg && lane == 0) {
         // per-wave log (tools/r5_wavelog.py): [64 + 8 k ...] = work pointer (names the launch), mode and rays of the launch, start, end, start
         // of the stealing phase (100 MHz clock), loop iterations, ticks spent hungry, cells taken | cells donated << 32
         const unsigned long long k = atomicAdd(&a.dbg[63], 1ull);
         if (k < (unsigned long long)PT_WAVELOG_CAP) {
             unsigned long long* w = a.dbg + 64 + 8 * k;
-#if PT_DEBUG_WAVELOG + 0 == 2
-            w[6] = (w_cw << 32) | (w_cr & 0xffffffffull); // cycles in the loop-top write-back | in the refill
-            w[7] = (w_cs << 32) | w_np;                   // cycles in the steal round | outer passes
-#else
             w[6] = (w_c01 << 32) | (w_c12 & 0xffffffffull); // cycles in vote + pop + addresses | cycles waiting for the step's loads
             w[7] = (w_c23 << 32) | ((clock64() - w_c0 - w_c01 - w_c12 - w_c23) & 0xffffffffull); // cycles in the arithmetic | outside the steps (refill, steal rounds, write-back)
-#endif
             w[0] = (unsigned long long)(uintptr_t)a.work;
             w[1] = ((unsigned long long)MODE << 32) | n;
             w[2] = w_t0;
@@ -843,9 +664,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
 template <int MODE>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT8_WAVES_PER_EU, PT8_WAVES_PER_EU)))
 k_trace8(Trace8Args a) {
-#if PT_DEBUG_WAVELOG + 0 == 3
-    a.hist = a.dbg ? a.dbg + 53 : nullptr;
-#endif
     trace8_wave<MODE, false>(a, blockIdx.x, gridDim.x, 0u, 0u, 0u);
 }
 // k_trace8<TR_UNIFIED> of a chain with carried sums (PT_CARRY_SUMS): a shadow lane's write-back is one visibility word, st.svis[position in queue2].
@@ -853,9 +671,6 @@ k_trace8(Trace8Args a) {
 // frame was 2 % slower than without the change; this one has none (96 VGPRs as before).
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT8_WAVES_PER_EU, PT8_WAVES_PER_EU)))
 k_trace8_vis(Trace8Args a) {
-#if PT_DEBUG_WAVELOG + 0 == 3
-    a.hist = a.dbg ? a.dbg + 53 : nullptr;
-#endif
     trace8_wave<TR_UNIFIED, false, true>(a, blockIdx.x, gridDim.x, 0u, 0u, 0u);
 }
 
@@ -881,7 +696,6 @@ k_trace8_vis(Trace8Args a) {
 #if __HIP_DEVICE_COMPILE__
 typedef const __attribute__((address_space(4))) Node8* ConstNode8;     // constant address space: s_load
 typedef const __attribute__((address_space(4))) LeafTri* ConstLeafTri;
-typedef const __attribute__((address_space(4))) float4* ConstF4;
 #endif
 __global__ void __launch_bounds__(64) k_trace8_cam(Trace8Args a) {
 #if __HIP_DEVICE_COMPILE__
@@ -896,9 +710,7 @@ __global__ void __launch_bounds__(64) k_trace8_cam(Trace8Args a) {
     uint32_t per = npk / (gridDim.x * 4u);
     per = per < 4u ? 4u : (per > 16u ? 16u : per);
     uint32_t pk = blockIdx.x * per, pk_end = pk + per;
-#if !PT8_NODE64
     const ConstNode8 nodes = (ConstNode8)(uintptr_t)a.bvh.nodes;
-#endif
     const ConstLeafTri tris = (ConstLeafTri)(uintptr_t)a.bvh.tris;
     for (;;) {
         if (pk == pk_end) {
@@ -959,14 +771,8 @@ __global__ void __launch_bounds__(64) k_trace8_cam(Trace8Args a) {
                 else atomicOr(a.fault, 1u);
                 sp = sp < PT8_CAM_STACK ? sp + 1 : sp;
             }
-#if PT8_NODE64
-            const ConstF4 np = (ConstF4)(uintptr_t)(a.bvh.nodes + idx);
-            const float4 hq = np[0], n2 = np[1], n3 = np[2], n4 = np[3];
-            const NodeHdr nh = node_hdr(make_uint4(__float_as_uint(hq.x), __float_as_uint(hq.y), __float_as_uint(hq.z), __float_as_uint(hq.w)), a.bvh.grid);
-#else
             const float4 n0 = nodes[idx].n0, n1 = nodes[idx].n1, n2 = nodes[idx].n2, n3 = nodes[idx].n3, n4 = nodes[idx].n4;
             const NodeHdr nh = node_hdr(n0, n1);
-#endif
             const uint32_t imask = nh.imask;
             const float ax = nh.sx * r.idir.x, ay = nh.sy * r.idir.y, az = nh.sz * r.idir.z;
             const float bx = (nh.ox - r.o.x) * r.idir.x, by = (nh.oy - r.o.y) * r.idir.y, bz = (nh.oz - r.o.z) * r.idir.z;

@@ -20,6 +20,14 @@
 #include "pt_bvh8.h"
 #include "pt_host.h"
 
+// What is left of the retired one-line node (tools/patches/one_line_node.patch): its origin grid was a by-value argument of k_collapse8,
+// k_single_node8, k_calibrate8 and k_refit_single.  The 28 bytes stay in their argument lists, always zero and never read, so that the
+// kernels' argument layout — and with it their machine code — is what it was.
+struct Grid8 {
+    float glo[3], gstep[3];
+    uint32_t ebase;
+};
+
 namespace {
 
 // scene bounds from k_bounds' ordered uints, and the padding of every box: 2^-16 of the largest |coordinate| (the refit derives it on the
@@ -512,32 +520,9 @@ __global__ void k_collapse8(const Task8* __restrict__ tin, uint32_t nin, Task8* 
     const uint32_t child_base = nint ? atomicAdd(&counters[1], nint) : 0u;
     const uint32_t tri_base = ntri ? atomicAdd(&counters[2], ntri) : 0u;
     const uint32_t task_base = nint ? atomicAdd(&counters[0], nint) : 0u;
-#if PT8_NODE64
-    // one-line node: the origin on the scene grid, rounded down (never above the node's padded lower corner), and the smallest power-of-two
-    // step whose 255 multiples reach the upper corner from there; both exactly as the traversal kernels decode them (node_hdr)
-    uint32_t oq[3], e5[3];
-    float step[3];
-    for (int a = 0; a < 3; ++a) {
-        const uint32_t cells = 1u << (a == 1 ? PT8_GRID_BITS_Y : PT8_GRID_BITS_XZ);
-        float fq = floorf((lo[a] - grid.glo[a]) / grid.gstep[a]);
-        fq = fminf(fmaxf(fq, 0.f), (float)(cells - 1u));
-        uint32_t q0 = (uint32_t)fq;
-        while (q0 > 0u && __builtin_fmaf((float)q0, grid.gstep[a], grid.glo[a]) > lo[a]) --q0;
-        oq[a] = q0;
-        lo[a] = __builtin_fmaf((float)q0, grid.gstep[a], grid.glo[a]); // the grid's origin from here on
-        uint32_t e = 0u;
-        for (; e < 31u; ++e) {
-            const float st = __uint_as_float((grid.ebase + e) << 23);
-            if (lo[a] + 255.0f * st >= hi[a]) break;
-        }
-        e5[a] = e;
-        step[a] = __uint_as_float((grid.ebase + e) << 23);
-    }
-#else
     uint32_t eb[3]; // upper 16 bits of the step
     float step[3];
     node_steps80(lo, hi, eb, step);
-#endif
     uint32_t q[6][2] = {{0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}, {0u, 0u}, {0u, 0u}, {0u, 0u}};
     uint32_t leafbits = 0u;
     uint32_t toff = 0, irank = 0;
@@ -558,25 +543,11 @@ __global__ void k_collapse8(const Task8* __restrict__ tin, uint32_t nin, Task8* 
         }
     }
     Node8 nd;
-#if PT8_NODE64
-    uint32_t b0 = 0u, b1 = 0u; // count planes of the leaf slots
-    for (int s = 0; s < 8; ++s) {
-        const uint32_t c = (uint32_t)__popc((leafbits >> (3 * s)) & 7u);
-        b0 |= (c & 1u) << s;
-        b1 |= (c >> 1) << s;
-    }
-    nd.h = make_uint4(child_base | (imask << 24), tri_base | (e5[0] << 24) | ((oq[1] & 7u) << 29),
-                      b0 | (b1 << 8) | (e5[1] << 16) | (e5[2] << 21) | (((oq[1] >> 3) & 63u) << 26), oq[0] | (oq[2] << 14) | ((oq[1] >> 9) << 28));
-    nd.q0 = make_uint4(q[0][0], q[0][1], q[1][0], q[1][1]);
-    nd.q1 = make_uint4(q[2][0], q[2][1], q[3][0], q[3][1]);
-    nd.q2 = make_uint4(q[4][0], q[4][1], q[5][0], q[5][1]);
-#else
     nd.n0 = make_float4(lo[0], lo[1], lo[2], __uint_as_float(eb[0] | (eb[1] << 16)));
     nd.n1 = make_float4(__uint_as_float(child_base), __uint_as_float(tri_base), __uint_as_float(leafbits), __uint_as_float(eb[2] | (imask << 16)));
     nd.n2 = make_float4(__uint_as_float(q[0][0]), __uint_as_float(q[0][1]), __uint_as_float(q[1][0]), __uint_as_float(q[1][1]));
     nd.n3 = make_float4(__uint_as_float(q[2][0]), __uint_as_float(q[2][1]), __uint_as_float(q[3][0]), __uint_as_float(q[3][1]));
     nd.n4 = make_float4(__uint_as_float(q[4][0]), __uint_as_float(q[4][1]), __uint_as_float(q[5][0]), __uint_as_float(q[5][1]));
-#endif
     nodes[task.widx] = nd;
 }
 
@@ -756,26 +727,8 @@ __global__ void __launch_bounds__(1024) k_ploc_tail(const int* __restrict__ cl_i
 }
 
 // scenes with <= PT8_LEAF_MAX triangles: one node, one leaf child
-__device__ void single_node8(int n, const float* bounds6, float pad, Node8* __restrict__ nodes, Grid8 grid) {
+__device__ void single_node8(int n, const float* bounds6, float pad, Node8* __restrict__ nodes) {
     float lo[3], hi[3];
-#if PT8_NODE64
-    uint32_t e5[3];
-    for (int a = 0; a < 3; ++a) { // origin = the grid's own origin (cell 0), slot 0 = the whole 255-step range
-        hi[a] = bounds6[3 + a] + pad;
-        uint32_t e = 0u;
-        for (; e < 31u; ++e)
-            if (grid.glo[a] + 255.0f * __uint_as_float((grid.ebase + e) << 23) >= hi[a]) break;
-        e5[a] = e;
-    }
-    const uint32_t c = (uint32_t)n; // 1..3 triangles in slot 0
-    Node8 nd;
-    nd.h = make_uint4(0u, e5[0] << 24, (c & 1u) | ((c >> 1) << 8) | (e5[1] << 16) | (e5[2] << 21), 0u);
-    nd.q0 = make_uint4(0xffffff00u, 0xffffffffu, 0xffffff00u, 0xffffffffu);
-    nd.q1 = make_uint4(0xffffff00u, 0xffffffffu, 0x000000ffu, 0u);
-    nd.q2 = make_uint4(0x000000ffu, 0u, 0x000000ffu, 0u);
-    nodes[0] = nd;
-    (void)lo;
-#else
     uint32_t eb[3];
     for (int a = 0; a < 3; ++a) {
         lo[a] = bounds6[a] - pad;
@@ -794,11 +747,10 @@ __device__ void single_node8(int n, const float* bounds6, float pad, Node8* __re
     nd.n3 = make_float4(__uint_as_float(qlo), __uint_as_float(0xffffffffu), __uint_as_float(qhi), __uint_as_float(0u));
     nd.n4 = make_float4(__uint_as_float(qhi), __uint_as_float(0u), __uint_as_float(qhi), __uint_as_float(0u));
     nodes[0] = nd;
-#endif
 }
 __global__ void k_single_node8(int n, const float* __restrict__ bounds6, float pad, Node8* __restrict__ nodes, Grid8 grid) {
     if (threadIdx.x || blockIdx.x) return;
-    single_node8(n, bounds6, pad, nodes, grid);
+    single_node8(n, bounds6, pad, nodes);
 }
 
 // ---- choosing between two hierarchies by measurement (pt_bvh_build, PT_BVH_BUILDER unset).  The SAH cost of the collapsed tree
@@ -873,15 +825,10 @@ __global__ void __launch_bounds__(64) k_calibrate8(const Node8* __restrict__ nod
         while (sp) {
             const Node8 nd = nodes[stack[--sp]];
             ++nsteps;
-#if PT8_NODE64
-            const NodeHdr nh = node_hdr(nd.h, grid);
-            const uint32_t q[12] = {nd.q0.x, nd.q0.y, nd.q0.z, nd.q0.w, nd.q1.x, nd.q1.y, nd.q1.z, nd.q1.w, nd.q2.x, nd.q2.y, nd.q2.z, nd.q2.w};
-#else
             const NodeHdr nh = node_hdr(nd.n0, nd.n1);
             const uint32_t q[12] = {__float_as_uint(nd.n2.x), __float_as_uint(nd.n2.y), __float_as_uint(nd.n2.z), __float_as_uint(nd.n2.w),
                                     __float_as_uint(nd.n3.x), __float_as_uint(nd.n3.y), __float_as_uint(nd.n3.z), __float_as_uint(nd.n3.w),
                                     __float_as_uint(nd.n4.x), __float_as_uint(nd.n4.y), __float_as_uint(nd.n4.z), __float_as_uint(nd.n4.w)};
-#endif
             const float sx = nh.sx, sy = nh.sy, sz = nh.sz;
             const uint32_t imask = nh.imask;
             uint32_t hits = 0;
@@ -1116,7 +1063,7 @@ static hipError_t build_bvh8(int n, int root, const int* left, const int* right,
     std::vector<uint32_t> level_off(1, 0u); // round r emits the nodes [level_off[r], level_off[r + 1]): the tasks it was handed
     while (nin) {
         hipLaunchKernelGGL(k_collapse8, dim3((nin + 63) / 64), dim3(64), 0, stream, ta, nin, tb, counters, n, left, right, cnt, box, pad, dec,
-                           tris_sorted, nodes, tris8, out->grid);
+                           tris_sorted, nodes, tris8, Grid8{});
         HIPCHK(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         nin = hc[0];
@@ -1129,22 +1076,11 @@ static hipError_t build_bvh8(int n, int root, const int* left, const int* right,
     HIPCHK(hipGetLastError());
     if (getenv("PT_DEBUG_BVH")) { // slot occupancy of the wide tree
         auto fbits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-        std::vector<Node80> h(hc[1]);
+        std::vector<Node8> h(hc[1]);
         HIPCHK(hipStreamSynchronize(stream)); // the library's streams do not synchronise with the null stream
-#if PT8_NODE64
-        {
-            Node80* tmp80 = nullptr;
-            HIPCHK(hipMalloc(&tmp80, sizeof(Node80) * h.size()));
-            hipLaunchKernelGGL(k_nodes_to80, dim3((hc[1] + 255) / 256), dim3(256), 0, stream, nodes, hc[1], out->grid, tmp80);
-            HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipMemcpy(h.data(), tmp80, sizeof(Node80) * h.size(), hipMemcpyDeviceToHost));
-            hipFree(tmp80);
-        }
-#else
         HIPCHK(hipMemcpy(h.data(), nodes, sizeof(Node8) * h.size(), hipMemcpyDeviceToHost));
-#endif
         unsigned long long fill[9] = {0}, leafsz[9] = {0}, nint = 0, nleaf = 0;
-        for (const Node80& nd : h) {
+        for (const Node8& nd : h) {
             const uint32_t imask = fbits(nd.n1.w) >> 16;
             const uint32_t qlo[2] = {fbits(nd.n2.x), fbits(nd.n2.y)}, qhi[2] = {fbits(nd.n3.z), fbits(nd.n3.w)};
             const uint32_t leafbits = fbits(nd.n1.z);
@@ -1918,7 +1854,6 @@ struct PhaseClock {
 };
 
 hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint32_t* d_tri_mesh, uint32_t ntri, hipStream_t stream, PtBvh* out) {
-    if (PT8_NODE64 && ntri > (1u << 24)) return hipErrorInvalidValue; // one-line nodes address 2^24 nodes and leaf triangles
     const int n = (int)ntri;
     const int B = 256;
     PhaseClock pc(stream);
@@ -1947,26 +1882,6 @@ hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint3
     HIPCHK(hipStreamSynchronize(stream));
     const float pad = bounds_pad(hb, out->bounds);
     out->pad = pad;
-#if PT8_NODE64
-    {
-        // the one-line nodes' origin grid: over the scene's bounds widened by twice the padding (every node box lies inside), 2^14 / 2^13 / 2^14
-        // cells; base exponent: 255 steps of 2^(ebase + 31 - 127) span twice the largest extent, so the root always finds its step
-        float maxext = 0.f;
-        for (int a = 0; a < 3; ++a) {
-            const float glo = out->bounds[a] - 2.0f * pad, ghi = out->bounds[3 + a] + 2.0f * pad;
-            const float cells = (float)(1u << (a == 1 ? PT8_GRID_BITS_Y : PT8_GRID_BITS_XZ));
-            float gs = (ghi - glo) / cells * (1.0f + 1.0f / 262144.0f);
-            if (!(gs > 1e-37f)) gs = 1e-37f;
-            out->grid.glo[a] = glo;
-            out->grid.gstep[a] = gs;
-            maxext = fmaxf(maxext, ghi - glo);
-        }
-        int e = 0;
-        if (maxext > 0.f) frexpf(2.0f * maxext / 255.0f, &e); // 2^(e-1) <= x < 2^e
-        int eb = e + 127 - 31;
-        out->grid.ebase = (uint32_t)std::max(1, std::min(223, eb));
-    }
-#endif
     pc.mark("bounds, morton, sort");
 
     LeafTri* tris = nullptr;
@@ -1982,7 +1897,7 @@ hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint3
         HIPCHK(tmalloc(&dbounds, sizeof(float) * 6));
         HIPCHK(hipMemcpyAsync(dbounds, out->bounds, sizeof(float) * 6, hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemcpyAsync(tris8, tris, sizeof(LeafTri) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(k_single_node8, dim3(1), dim3(64), 0, stream, n, dbounds, pad, nodes8, out->grid);
+        hipLaunchKernelGGL(k_single_node8, dim3(1), dim3(64), 0, stream, n, dbounds, pad, nodes8, Grid8{});
         out->nodes8 = nodes8; out->tris8 = tris8; out->num_nodes8 = 1; out->num_tris8 = (uint32_t)n; out->levels8 = 1;
         out->level_off = {0u, 1u};
         HIPCHK(hipStreamSynchronize(stream));
@@ -2056,7 +1971,6 @@ hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint3
             for (int cand = 0; cand < ncand; ++cand) {
                 const int kind = kinds[cand];
                 PtBvh alt;
-                alt.grid = out->grid; // same scene, same origin grid
                 hipError_t pe = kind == 1 ? build_ploc(n, left, right, box, cnt, stream, &root) : build_sah(n, left, right, box, cnt, out->bounds, stream, &root);
                 pc.mark(kind == 1 ? "ploc hierarchy" : "sah hierarchy");
                 if (pe == hipSuccess) pe = build_bvh8(n, root, left, right, cnt, box, pad, tris, stream, &alt);
@@ -2073,7 +1987,7 @@ hipError_t pt_bvh_build(const float* d_verts, const uint32_t* d_idx, const uint3
                 HIPCHK(tmalloc(&counts, sizeof(hcnt)));
                 HIPCHK(hipMemsetAsync(counts, 0, sizeof(hcnt), stream));
                 const uint32_t nrays = 1u << 16;
-                hipLaunchKernelGGL(k_calibrate8, dim3(2 * (nrays / 64)), dim3(64), 0, stream, out->nodes8, out->tris8, alt.nodes8, alt.tris8, tris, (uint32_t)n, nrays, 0.5f * pad, counts, out->grid, calib_mode, sphere);
+                hipLaunchKernelGGL(k_calibrate8, dim3(2 * (nrays / 64)), dim3(64), 0, stream, out->nodes8, out->tris8, alt.nodes8, alt.tris8, tris, (uint32_t)n, nrays, 0.5f * pad, counts, Grid8{}, calib_mode, sphere);
                 HIPCHK(hipMemcpyAsync(hcnt, counts, sizeof(hcnt), hipMemcpyDeviceToHost, stream));
                 HIPCHK(hipStreamSynchronize(stream));
                 tfree(counts);
@@ -2160,7 +2074,6 @@ __global__ void k_refit_nodes(uint32_t first, uint32_t count, Node8* __restrict_
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     const uint32_t i = first + t;
-#if !PT8_NODE64
     float sb[6];
     const float pad = bounds_pad(refit, sb);
     Node8 nd = nodes[i];
@@ -2204,19 +2117,17 @@ __global__ void k_refit_nodes(uint32_t first, uint32_t count, Node8* __restrict_
     nd.n4 = make_float4(__uint_as_float(q[4][0]), __uint_as_float(q[4][1]), __uint_as_float(q[5][0]), __uint_as_float(q[5][1]));
     nodes[i] = nd;
     for (int a = 0; a < 6; ++a) exact[(size_t)i * 6 + a] = ex[a];
-#endif
 }
 // scenes of at most PT8_LEAF_MAX triangles: the build's single node (k_single_node8) over the new scene bounds
 __global__ void k_refit_single(int n, Node8* __restrict__ nodes, const uint32_t* __restrict__ refit, Grid8 grid) {
     if (threadIdx.x || blockIdx.x) return;
     float sb[6];
     const float pad = bounds_pad(refit, sb);
-    single_node8(n, sb, pad, nodes, grid);
+    single_node8(n, sb, pad, nodes);
 }
 } // namespace
 
 hipError_t pt_bvh_refit_alloc(PtBvh* b) {
-    if (PT8_NODE64) return hipErrorNotSupported; // the one-line nodes' origin grid is fixed to the scene bounds of the build
     if (b->level_off.size() < 2 || b->level_off.back() != b->num_nodes8) return hipErrorInvalidValue;
     if (!b->d_refit) HIPCHK(hipMalloc(&b->d_refit, sizeof(uint32_t) * 8));
     if (!b->d_exact) HIPCHK(hipMalloc(&b->d_exact, sizeof(float) * 6 * (size_t)b->num_nodes8));
@@ -2232,7 +2143,7 @@ hipError_t pt_bvh_refit_begin(PtBvh* b, const float* d_verts, const uint32_t* d_
 }
 hipError_t pt_bvh_refit_nodes(PtBvh* b, hipStream_t stream) {
     if (b->num_tris8 <= PT8_LEAF_MAX && b->num_nodes8 == 1) {
-        hipLaunchKernelGGL(k_refit_single, dim3(1), dim3(64), 0, stream, (int)b->num_tris8, const_cast<Node8*>(b->nodes8), b->d_refit, b->grid);
+        hipLaunchKernelGGL(k_refit_single, dim3(1), dim3(64), 0, stream, (int)b->num_tris8, const_cast<Node8*>(b->nodes8), b->d_refit, Grid8{});
         return hipGetLastError();
     }
     for (int d = (int)b->level_off.size() - 2; d >= 0; --d) { // ~8 small launches: the kernel boundary is the only ordering needed

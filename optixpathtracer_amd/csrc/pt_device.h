@@ -512,10 +512,6 @@ PT_DEV float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); 
 // conditional expressions over struct members are compiled as selects of addresses and park the struct in scratch.)
 // probe_search_rows: begin's search for given random numbers (r1, r2) in [0, 1) — also pt_eval_table 9-11, which query it at chosen values
 PT_DEV void probe_search_rows(const DevProbe& p, const ProbeMarg& pm, float r1, float r2, int& row_out, int& lo_out, int& hi_out) {
-#ifdef PT_EXP_NO_SEARCH
-    row_out = (int)(r1 * p.height);
-    lo_out = hi_out = (int)(r2 * p.width) / PT_LINE_COLS;
-#else
     int row = pm.c64Y ? lower_bound_blocked(pm.cdfY, p.height, pm.c64Y, p.ncy, pm.c8Y, r1) : lower_bound(pm.cdfY, 0, p.height, r1);
     if (row > p.height - 1) row = p.height - 1; // row/col clamped: unreachable for a valid CDF, guards a degenerate probe
     row_out = row;
@@ -524,7 +520,6 @@ PT_DEV void probe_search_rows(const DevProbe& p, const ProbeMarg& pm, float r1, 
     const uint16_t* __restrict__ g = p.guide + (size_t)row * p.gpitch + k;
     lo_out = g[0];
     hi_out = g[1];
-#endif
 }
 PT_DEV void probe_search_begin(const DevProbe& p, const ProbeMarg& pm, Rng& rand, int& row_out, int& lo_out, int& hi_out, float& r2_out) {
     float r1, r2;
@@ -554,10 +549,6 @@ PT_DEV void probe_cell_columns(const DevProbe& p, int lo, int hi, int& c0, int& 
 }
 // probe_search_column: the line and the column (clamped to the row's last) that end settles on — also pt_eval_table 9-11
 PT_DEV void probe_search_column(const DevProbe& p, const ProbeLine* __restrict__ rl, int lo, int hi, float value, int& l_out, int& col_out) {
-#ifdef PT_EXP_NO_SEARCH
-    const int l = lo;
-    int col = (int)(value * p.width);
-#else
     const int last = p.lpr - 1;
     lo = lo < last ? lo : last; // count == lpr: every line ends below the cell; the last line then yields column >= width
     hi = hi < last ? hi : last;
@@ -579,7 +570,6 @@ PT_DEV void probe_search_column(const DevProbe& p, const ProbeLine* __restrict__
     }
     int col = l * PT_LINE_COLS + (s0.x < value ? 1 : 0) + (s0.y < value ? 1 : 0) + (s0.z < value ? 1 : 0) + (s0.w < value ? 1 : 0) +
               (s1.x < value ? 1 : 0) + (s1.y < value ? 1 : 0);
-#endif
     if (col > p.width - 1) col = p.width - 1;
     l_out = l;
     col_out = col;

@@ -56,9 +56,7 @@ __global__ void __launch_bounds__(64) k_gbuffer(GBufferArgs a, ViewParams vp) {
     uint32_t per = npk / (gridDim.x * 4u);
     per = per < 4u ? 4u : (per > 16u ? 16u : per);
     uint32_t pk = blockIdx.x * per, pk_end = pk + per;
-#if !PT8_NODE64
     const ConstNode8 nodes = (ConstNode8)(uintptr_t)a.bvh.nodes;
-#endif
     const ConstLeafTri tris = (ConstLeafTri)(uintptr_t)a.bvh.tris;
     uint32_t nhit = 0; // lane 0: hits of this wave's packets
     for (;;) {
@@ -126,14 +124,8 @@ __global__ void __launch_bounds__(64) k_gbuffer(GBufferArgs a, ViewParams vp) {
                 else atomicOr(&a.counters->fault, 1u);
                 sp = sp < PT8_CAM_STACK ? sp + 1 : sp;
             }
-#if PT8_NODE64
-            const ConstF4 np = (ConstF4)(uintptr_t)(a.bvh.nodes + idx);
-            const float4 hq = np[0], n2 = np[1], n3 = np[2], n4 = np[3];
-            const NodeHdr nh = node_hdr(make_uint4(__float_as_uint(hq.x), __float_as_uint(hq.y), __float_as_uint(hq.z), __float_as_uint(hq.w)), a.bvh.grid);
-#else
             const float4 n0 = nodes[idx].n0, n1 = nodes[idx].n1, n2 = nodes[idx].n2, n3 = nodes[idx].n3, n4 = nodes[idx].n4;
             const NodeHdr nh = node_hdr(n0, n1);
-#endif
             const uint32_t imask = nh.imask;
             const float ax = nh.sx * r.idir.x, ay = nh.sy * r.idir.y, az = nh.sz * r.idir.z;
             const float bx = (nh.ox - r.o.x) * r.idir.x, by = (nh.oy - r.o.y) * r.idir.y, bz = (nh.oz - r.o.z) * r.idir.z;

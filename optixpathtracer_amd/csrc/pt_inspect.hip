@@ -2,29 +2,15 @@
 // BSDF, probe, colour, math, RNG and texture functions evaluated over a table of inputs).  Part of pt_lib.hip.
 extern "C" int pt_export_bvh(pt_ctx* ctx, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes, uint32_t* num_nodes, uint32_t* num_tris) {
     if (!ctx) return PT_ERR_INVALID;
-    // the exported layout is the documented 80-byte node whatever the kernels traverse (PT8_NODE64: converted on the device, box for box)
-    static_assert(sizeof(Node80) == 80 && sizeof(LeafTri) == 48, "exported layout");
+    // the exported layout is the documented 80-byte node, the one the kernels traverse
+    static_assert(sizeof(Node8) == 80 && sizeof(LeafTri) == 48, "exported layout");
     if (num_nodes) *num_nodes = ctx->bvh.num_nodes8;
     if (num_tris) *num_tris = ctx->bvh.num_tris8;
     if (!nodes && !tris) return PT_OK;
-    if (!nodes || !tris || nodes_bytes != sizeof(Node80) * (size_t)ctx->bvh.num_nodes8 || tris_bytes != sizeof(LeafTri) * (size_t)ctx->bvh.num_tris8)
+    if (!nodes || !tris || nodes_bytes != sizeof(Node8) * (size_t)ctx->bvh.num_nodes8 || tris_bytes != sizeof(LeafTri) * (size_t)ctx->bvh.num_tris8)
         return fail(ctx, PT_ERR_INVALID, "pt_export_bvh: buffer sizes must be num_nodes * 80 and num_tris * 48 bytes");
     CK(hipSetDevice(ctx->device));
-#if PT8_NODE64
-    {
-        int rc = drain(ctx);
-        if (rc) return rc;
-        DevOwner tmp;
-        uint8_t* tmp80 = nullptr;
-        CK(tmp.alloc(&tmp80, nodes_bytes));
-        hipLaunchKernelGGL(k_nodes_to80, dim3((ctx->bvh.num_nodes8 + 255) / 256), dim3(256), 0, ctx->stream, ctx->bvh.nodes8, ctx->bvh.num_nodes8, ctx->bvh.grid, reinterpret_cast<Node80*>(tmp80));
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(nodes, tmp80, nodes_bytes, hipMemcpyDeviceToHost);
-        CK(e);
-    }
-#else
     CK(hipMemcpy(nodes, ctx->bvh.nodes8, nodes_bytes, hipMemcpyDeviceToHost));
-#endif
     CK(hipMemcpy(tris, ctx->bvh.tris8, tris_bytes, hipMemcpyDeviceToHost));
     return PT_OK;
 }

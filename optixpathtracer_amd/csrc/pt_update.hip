@@ -54,7 +54,6 @@ static int update_validate(const pt_ctx* ctx, const pt_mesh_update* up, uint32_t
             return PT_ERR_INVALID;
         }
     }
-    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = f + "refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
     return PT_OK;
 }
 
@@ -71,7 +70,6 @@ static int transform_validate(const pt_ctx* ctx, const pt_mesh_transform* t, uin
         for (int i = 0; i < 12; ++i)
             if (!std::isfinite(t[k].m[i])) { err = f + "non-finite matrix entry for mesh " + std::to_string(t[k].mesh); return PT_ERR_INVALID; }
     }
-    if (mode == PT_UPDATE_REFIT && PT8_NODE64) { err = f + "refit is not supported with one-line nodes (PT8_NODE64): rebuild"; return PT_ERR_UNSUPPORTED; }
     return PT_OK;
 }
 
