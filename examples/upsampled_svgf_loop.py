@@ -38,10 +38,16 @@ Per frame, on `hi`:
      pixel and so never arrive through step 10.  The occlusion is a colour (ao, ao, ao, 1): temporalAccumulate and filterPlanes treat it
      as they treat one, and modulatePlanes multiplies it into the upsampled irradiance, before the albedo.  (modulatePlanes reads a
      factor of exactly 0 as 1, its rule for a miss's albedo, so the filtered occlusion is kept above 2^-10.)
+ 18. with --reflect [--reflect-mesh K --reflectivity F], behind steps 11 and 12 and in front of everything that follows them: `hi` gets the
+     probe, reflectPlanes shoots every pixel's mirror ray through `hi`'s tree into a second G-buffer (hit2) and the probe's radiance where
+     the ray escapes (sky), and step 9's pass runs once more, on hit2, for the reflected surface's albedo.  The reflection's colour is sky
+     where the ray escaped and that albedo times the mean of step 10's irradiance elsewhere; it is blended with weight F into the pixels
+     of mesh K — in torch: the composition is this example's, not a rule of the library.  The displayed frame then comes from the tone
+     mapper, as with steps 14 to 16.
 `hi` never renders a colour sample.
 
   python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa]
-                                          [--ao] [--ao-rays N] [--ao-radius R]
+                                          [--ao] [--ao-rays N] [--ao-radius R] [--reflect] [--reflect-mesh K] [--reflectivity F]
                                           [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
                                           [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N]
                                           [--dof] [--focus F | --autofocus] [--aperture K] [--dof-taps N] [--out-dir .]
@@ -91,10 +97,11 @@ class UpsampledLoop:
     def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
                  edge_aa=False, auto_exposure=False, tonemap="aces", bloom=False, bloom_threshold=1.0, bloom_levels=6,
                  motion_blur=False, shutter=0.5, blur_taps=12, dof=False, focus=4.0, autofocus=False, aperture=6.0, dof_taps=32,
-                 ao=False, ao_rays=4, ao_radius=0.5):
+                 ao=False, ao_rays=4, ao_radius=0.5, reflect=False, reflect_mesh=0, reflectivity=0.5):
         import torch
 
         self.ao, self.ao_prm = bool(ao), dict(rays=int(ao_rays), radius=float(ao_radius))
+        self.reflect, self.reflect_mesh, self.reflectivity = bool(reflect), int(reflect_mesh), float(reflectivity)
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
         self.size, self.scale, self.lod, self.aniso = tuple(size), int(scale), lod, int(aniso)
         self.edge_aa = bool(edge_aa)
@@ -117,6 +124,8 @@ class UpsampledLoop:
         self.lo.resize(self.lo_size)
         self.lo.uploadAccum(np.zeros((lh, lw, 4), np.float32))
         self.hi.resize(self.size)  # no probe: the full-size renderer never shades
+        if self.reflect:
+            self.hi.setProbe(probe)  # (but step 18's escaped mirror rays look it up)
 
         def planes(hh, ww, k):
             return torch.zeros((hh, ww, k) if k > 1 else (hh, ww), device="cuda:0")
@@ -150,6 +159,10 @@ class UpsampledLoop:
             self.ao_raw, self.ao_filtered, self.ao_scratch, self.shaded = (planes(h, w, 4) for _ in range(4))
             self.ao_history, self.ao_length = [planes(h, w, 4) for _ in range(2)], [planes(h, w, 1) for _ in range(2)]
             self.ao_batch = torch.zeros((self.hi.aoLayout(self.ao_prm["rays"]) // 4,), device="cuda:0")
+        # step 18: the second G-buffer's hit plane, the probe's radiance, the reflected surface's albedo, the reflection's colour, the rays' batch
+        if self.reflect:
+            self.hit2, self.sky, self.albedo2, self.reflection = planes(h, w, 8), planes(h, w, 4), planes(h, w, 4), planes(h, w, 4)
+            self.reflect_batch = torch.zeros((self.hi.reflectLayout() // 4,), device="cuda:0")
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
         self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
@@ -212,13 +225,33 @@ class UpsampledLoop:
         else:
             ao = dict(ao_ms=0.0, ao_trace_ms=0.0, ao_rays=0, ao_occluded=0, ao_batches=0, ao_chain_ms=0.0)
         # with auto exposure, depth of field, bloom or motion blur the tone mapper writes the displayed frame
-        shown = None if self.auto_exposure or self.dof or self.bloom or self.motion_blur else self.frame_rgba8
+        shown = None if self.auto_exposure or self.dof or self.bloom or self.motion_blur or self.reflect else self.frame_rgba8
         if self.edge_aa:
             m = hi.modulatePlanes(irradiance, albedo=self.albedo, out=self.modulated)["stats"]
             e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=shown)["stats"]
         else:
             m = hi.modulatePlanes(irradiance, albedo=self.albedo, out=self.final, frame=shown)["stats"]
             e = dict(kernel_ms=0.0, boundary=0, blended=0)
+        if self.reflect:
+            import torch
+
+            hg = self.hi_gbuf
+            rf = hi.reflectPlanes(hg["hit"], hg["position"], hit2=self.hit2, sky=self.sky, scratch=self.reflect_batch)["stats"]
+            rs = self._albedo(hi, self.hit2, self.albedo2)  # every pass that reads a hit plane works on the second G-buffer
+            escaped = self.sky[..., 3:4] == 1.0
+            seen = escaped | (self.hit2.view(torch.int32)[..., 3:4] >= 0)  # the pixels whose mirror ray was traced
+            mean = irradiance[..., 0:3].mean(dim=(0, 1))
+            self.reflection[..., 0:3] = torch.where(escaped, self.sky[..., 0:3], self.albedo2[..., 0:3] * mean)
+            self.reflection[..., 3] = seen[..., 0].to(torch.float32)
+            words = hg["hit"].view(torch.int32)
+            mirror = (words[..., 3:4] >= 0) & (words[..., 4:5] == self.reflect_mesh) & seen
+            F = self.reflectivity
+            self.final[..., 0:3] = torch.where(mirror, (1.0 - F) * self.final[..., 0:3] + F * self.reflection[..., 0:3], self.final[..., 0:3])
+            self.mirrored = mirror  # (counted by the caller, outside the timed frame)
+            rfl = dict(reflect_ms=rf["kernel_ms"], reflect_trace_ms=rf["trace_ms"], reflect_hits=rf["hits"], reflect_escaped=rf["escaped"],
+                       reflect_batches=rf["batches"], reflect_surface_ms=rs["kernel_ms"])
+        else:
+            rfl = dict(reflect_ms=0.0, reflect_trace_ms=0.0, reflect_hits=0, reflect_escaped=0, reflect_batches=0, reflect_surface_ms=0.0)
         lit = self.final
         if self.dof:
             w, h = self.size
@@ -245,7 +278,7 @@ class UpsampledLoop:
             self.cur = o
         else:
             x, tm = dict(kernel_ms=0.0, skipped=0, under=0, over=0), dict(kernel_ms=0.0, clipped=0)
-            if self.dof or self.bloom or self.motion_blur:
+            if self.dof or self.bloom or self.motion_blur or self.reflect:
                 tm = hi.tonemapPlanes(lit, frame=self.frame_rgba8, op="linear", write_out=False)["stats"]
         t2 = time.perf_counter()
         ev = float(self.state[self.cur][0, 0]) if self.auto_exposure else 0.0  # read back for the caller's printing, outside the timed frame
@@ -257,7 +290,7 @@ class UpsampledLoop:
                     blended=e["blended"], exposure_ms=x["kernel_ms"], tonemap_ms=tm["kernel_ms"], ev=ev, skipped=x["skipped"], under=x["under"],
                     over=x["over"], clipped=tm["clipped"], bloom_ms=b["kernel_ms"], bright=b["bright"],
                     motion_blur_ms=mb["kernel_ms"], moving=mb["moving"], dof_ms=df["kernel_ms"], gathered=df["gathered"],
-                    focus=self.focus_now[0] if self.dof else 0.0, **ao)
+                    focus=self.focus_now[0] if self.dof else 0.0, **ao, **rfl, mirrored=int(self.mirrored.sum()) if self.reflect else 0)
 
     def close(self):
         self.lo.close()
@@ -290,6 +323,9 @@ def main(argv=None):
     ap.add_argument("--ao", action="store_true", help="ray-traced ambient occlusion (aoPlanes) at the display resolution, multiplied into the upsampled irradiance")
     ap.add_argument("--ao-rays", type=int, default=4, metavar="N", help="with --ao: rays per pixel and frame (1..32)")
     ap.add_argument("--ao-radius", type=float, default=0.5, metavar="R", help="with --ao: the rays' length, world units")
+    ap.add_argument("--reflect", action="store_true", help="mirror reflections (reflectPlanes) at the display resolution, blended into the pixels of one mesh")
+    ap.add_argument("--reflect-mesh", type=int, default=0, metavar="K", help="with --reflect: the mesh that mirrors")
+    ap.add_argument("--reflectivity", type=float, default=0.5, metavar="F", help="with --reflect: the reflection's weight in that mesh's pixels, in [0, 1]")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
@@ -298,7 +334,8 @@ def main(argv=None):
                          auto_exposure=args.auto_exposure, tonemap=args.tonemap, bloom=args.bloom, bloom_threshold=args.bloom_threshold,
                          bloom_levels=args.bloom_levels, motion_blur=args.motion_blur, shutter=args.shutter, blur_taps=args.blur_taps,
                          dof=args.dof, focus=args.focus, autofocus=args.autofocus, aperture=args.aperture, dof_taps=args.dof_taps,
-                         ao=args.ao, ao_rays=args.ao_rays, ao_radius=args.ao_radius)
+                         ao=args.ao, ao_rays=args.ao_rays, ao_radius=args.ao_radius, reflect=args.reflect, reflect_mesh=args.reflect_mesh,
+                         reflectivity=args.reflectivity)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -311,6 +348,8 @@ def main(argv=None):
               + (f"occlusion {x['ao_ms']:.3f} ms (traversal {x['ao_trace_ms']:.3f} ms, {x['ao_occluded']} of {x['ao_rays']} rays occluded, {x['ao_batches']} batches), "
                  f"its accumulation, filter and product {x['ao_chain_ms']:.3f} ms; " if loop.ao else "")
               + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
+              + (f"reflection {x['reflect_ms']:.3f} ms (traversal {x['reflect_trace_ms']:.3f} ms, {x['reflect_hits']} rays hit, {x['reflect_escaped']} escaped, "
+                 f"{x['reflect_batches']} batches), its surface pass {x['reflect_surface_ms']:.3f} ms, {x['mirrored']} pixels mirror; " if loop.reflect else "")
               + (f"depth of field {x['dof_ms']:.3f} ms ({x['gathered']} pixels gather, focus {x['focus']:.3f}); " if loop.dof else "")
               + (f"bloom {x['bloom_ms']:.3f} ms ({x['bright']} bright pixels); " if loop.bloom else "")
               + (f"motion blur {x['motion_blur_ms']:.3f} ms ({x['moving']} pixels gather); " if loop.motion_blur else "")
@@ -325,6 +364,8 @@ def main(argv=None):
         np.save(os.path.join(args.out_dir, "upsampled_svgf_dof.npy"), loop.lens.cpu().numpy())
     if loop.ao:
         np.save(os.path.join(args.out_dir, "upsampled_svgf_ao.npy"), loop.ao_filtered.cpu().numpy())
+    if loop.reflect:
+        np.save(os.path.join(args.out_dir, "upsampled_svgf_reflection.npy"), loop.reflection.cpu().numpy())
     print(f"wrote upsampled_svgf_final.npy and upsampled_svgf_frame.npy to {args.out_dir}")
     loop.close()
     return 0

@@ -37,7 +37,8 @@
  * under the same contract (its ordering cases: tests/test_gpu_dof.py); pt_dof_layout touches no device memory.  pt_lens_warp_planes takes
  * DEVICE pointers under the same contract (its ordering cases: tests/test_gpu_lens_warp.py); pt_warp_matrix is host arithmetic and touches
  * no device at all.  pt_ao_planes takes DEVICE pointers under the same contract (its ordering case: tests/test_gpu_ao.py); pt_ao_layout
- * touches no device memory.
+ * touches no device memory.  pt_reflect_planes takes DEVICE pointers under the same contract (its ordering case:
+ * tests/test_gpu_reflect.py); pt_reflect_layout touches no device memory.
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -51,7 +52,8 @@
  * pt_exposure_planes, pt_tonemap_planes.  A
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.  pt_bloom_layout and pt_bloom_planes were added
  * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes, and pt_dof_layout and pt_dof_planes,
- * and pt_lens_warp_planes and pt_warp_matrix, and pt_ao_layout and pt_ao_planes.
+ * and pt_lens_warp_planes and pt_warp_matrix, and pt_ao_layout and pt_ao_planes, and
+ * pt_reflect_layout and pt_reflect_planes.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -2046,6 +2048,83 @@ typedef struct pt_ao_desc {
 typedef struct pt_ao_stats { uint64_t pixels, traced, skipped, nonfinite, rays, occluded, invalid, batches; double kernel_ms, trace_ms; } pt_ao_stats;
 int pt_ao_layout(const pt_ctx* ctx, uint32_t rays, uint32_t max_rays_in_flight, size_t* bytes);
 int pt_ao_planes(pt_ctx* ctx, const pt_ao_desc* desc, pt_ao_stats* stats /* may be NULL */);
+
+/* MIRROR REFLECTIONS FROM THE G-BUFFER (no reference counterpart).  The second pass of the chain that asks the acceleration structure: per
+ * pixel of a hit it shoots ONE ray, the mirror image of the eye ray about the geometric normal, through the context's CURRENT tree (it
+ * follows pt_update_meshes* and pt_transform_meshes), and writes what that ray sees as a SECOND G-BUFFER: a pt_hit plane, a position plane,
+ * the ray itself, and the probe's radiance where the ray escapes.  It is what a caller could build from pt_trace_device(PT_QUERY_CLOSEST) —
+ * hit2 below is by definition that call's answer — without 32 bytes a ray through the caller's memory, a second staging, a validation kernel
+ * over rays the library built itself, a scatter of linear records back to the frame, and an unbounded ray buffer.  Every pass that reads a
+ * hit plane (pt_surface_planes for the reflected surface's albedo, pt_ao_planes, ...) works on hit2 / position2 unchanged
+ * (examples/upsampled_svgf_loop.py --reflect).  Stateless like every pass here: the planes and the scratch are caller-owned DEVICE memory of
+ * the context's device (the planes 4-byte aligned, frame-sized, indexed Y * width + X; the scratch 16-byte aligned); block_mask is HOST memory.
+ *
+ * The pixel set is pt_ao_planes's and pt_edge_aa_planes's: the pixels a pt_render_mask with the same mask would render — the rank's owned
+ * pixels, view pixels only while views are set, whole blocks of block_mask.  A pixel outside the set is not written in any plane.  The pass
+ * reads hit and position of this frame's pt_render_gbuffer, the cameras of the context (for the eye of the pixel's view), the current tree
+ * and, for sky, the probe.  No address is formed from hit's prim, which is looked at for its sign only (a stale prim >= the triangle count
+ * is processed like any other hit).
+ *
+ * Rule.  Float32 throughout, one rounding per operation, no fused multiply-add, sqrtf and / correctly rounded (pt_detmath.h's contract), with
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, normalize3(v) = v * (1 / sqrt(dot3(v, v))) as in pt_render_gbuffer's text, and "finite" the
+ * exponent-bit test (exponent bits not all ones).  The EMPTY RECORD is hit2 = {t 0, u 0, v 0, prim -1, mesh -1, ng 0}, position2 = (0, 0, 0, 0),
+ * sky = (0, 0, 0, 0), ray = the neutral ray (0, 0, 0, 1, 0, 0, 1, -1).  Per pixel p of the set, with E the eye of p's camera (the frame's,
+ * or with views the one of p's view):
+ *   1. h = hit[p].  If h.prim < 0 (a miss): the empty record; stats->skipped counts it; it shoots no ray.
+ *   2. P = position[p].xyz, n0 = h.ng, t = h.t.  If one of those seven words is not finite, or t > 0 is false: the empty record;
+ *      stats->nonfinite counts it; it shoots no ray.
+ *   3. Face the viewer: s = dot3(n0, E - P); n = (s < 0) ? -n0 : n0.  (pt_ao_planes's step 3.)
+ *   4. The mirror direction: d = normalize3(P - E); c = dot3(d, n); k = 2.0f * c;
+ *      r = normalize3((d.x - n.x*k, d.y - n.y*k, d.z - n.z*k)).
+ *   5. The origin: O = P + n * (bias * t) per component, the product first and then the sum.  The ray is (O, tmin = 0.0f, r, tmax =
+ *      max_distance), in pt_trace_device's eight words.
+ *   6. The ray is tested with pt_trace_device's validity rule: the eight words finite, dot3(r, r) and 1.0f / dot3(r, r) finite and not zero.
+ *      An invalid ray is not traced: hit2 = {t 0, u 0, v 0, prim -2, mesh -1, ng 0}, position2 = 0, sky = 0, ray = its own eight words as
+ *      computed; stats->invalid counts it.
+ *   7. hit2 is exactly the pt_hit that pt_trace_device(PT_QUERY_CLOSEST) returns for that ray over the current geometry, all eight words:
+ *      for a hit t2, the barycentrics u, v, prim, mesh and the geometric normal of the triangle; for an escaped ray t = max_distance,
+ *      prim = mesh = -1 and 0 in the rest.  Back faces count.
+ *   8. position2 = (O.x + t2*r.x, O.y + t2*r.y, O.z + t2*r.z, 1.0f) for a hit, the product first and then the sum; (0, 0, 0, 0) otherwise.
+ *   9. sky: for an escaped valid ray the probe's texel along r, by the frame's miss program (what pt_eval_table 3 returns for r, columns
+ *      2..4): (texel.x, texel.y, texel.z, 1.0f); for a hit (0, 0, 0, 0).  sky.w therefore says where the ray escaped.
+ * stats->pixels is the size of the set; traced the pixels that passed steps 1 and 2 (pixels = skipped + nonfinite + traced, and traced =
+ * invalid + hits + escaped); hits the rays that hit, escaped the valid rays that did not.
+ *
+ * Batches and scratch.  The pixel list is cut into batches of M pixels, M = max_rays_in_flight or, when that is 0,
+ * PT_REFLECT_DEFAULT_RAYS_IN_FLIGHT.  For each batch, in stream order, the pass generates the rays, traces them (the traversal kernel and
+ * grid of pt_trace_device) and resolves them; stats->batches says how many ran.  The scratch holds ONE batch — a 256-byte head (the
+ * traversal's count word, its work counter, the fault word, zeroed by the call), then per ray slot an origin and a direction of 16 bytes and
+ * a record of 8, then 4 bytes per batch pixel — and nothing per frame pixel.  pt_reflect_layout returns its size for min(M, frame pixels)
+ * pixels a batch: 256 + pixels * 44, rounded up to 16.  The result does not depend on M, bit for bit.
+ *
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): a null ctx or desc; no pt_resize yet; hit, position
+ * or scratch NULL; hit2, position2, ray and sky all NULL; a plane that fails the pointer checks; a written plane or the scratch overlapping
+ * anything; a scratch that is not 16-byte aligned or smaller than the layout; bias negative or not finite; max_distance not finite or not
+ * > 0; an unknown flag bit; sky asked for while the context has no probe ("no probe set (setProbe)": without sky a context without a probe
+ * works).  The traversal's stack-overflow bit gives PT_ERR_UNSUPPORTED, as in pt_trace.
+ * Ordering and state, as pt_ao_planes: the call waits for the frames in flight and completes queued queries (their counts stay for
+ * pt_query_wait), runs on pt_stream(ctx) under the STREAM CONTRACT, is complete when it returns, and touches neither the context's query
+ * state, nor the frame buffers, nor pt_stats.  For zero pixels it launches nothing and returns PT_OK.
+ * Not part of this interface: a shading or bent normal as input; glossy lobes (several rays a pixel); refraction; lighting of the reflected
+ * surface; an asynchronous variant; a pt_multi_* wrapper (per-rank calls work: each rank traces the whole tree for its own pixels). */
+#define PT_REFLECT_DEFAULT_RAYS_IN_FLIGHT 8388608u /* 2^23 rays: 352 MB of ray slots and pixel words, or the frame's if that is less */
+typedef struct pt_reflect_desc {
+    const void*  hit;          /* w*h x pt_hit, required */
+    const float* position;     /* w*h x 4, required */
+    void*  hit2;               /* w*h x pt_hit or NULL, exclusive: what the mirror ray hits */
+    float* position2;          /* w*h x 4  or NULL, exclusive: where it hits, .w = 1; zeros where it does not */
+    float* ray;                /* w*h x 8  or NULL, exclusive: the mirror ray in pt_trace_device's layout */
+    float* sky;                /* w*h x 4  or NULL, exclusive: the probe's radiance where the ray escapes, .w = 1; zeros elsewhere.  Needs a probe */
+    void*  scratch;            /* pt_reflect_layout's bytes, 16-byte aligned, required, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    float bias;                /* finite, >= 0: the origin is lifted by bias * hit.t along the normal */
+    float max_distance;        /* finite, > 0: the ray's tmax, world units (1e16f is the G-buffer's) */
+    uint32_t max_rays_in_flight; /* 0 = PT_REFLECT_DEFAULT_RAYS_IN_FLIGHT: bounds the scratch */
+    uint32_t flags;            /* must be 0 */
+} pt_reflect_desc;
+typedef struct pt_reflect_stats { uint64_t pixels, traced, skipped, nonfinite, invalid, hits, escaped, batches; double kernel_ms, trace_ms; } pt_reflect_stats;
+int pt_reflect_layout(const pt_ctx* ctx, uint32_t max_rays_in_flight, size_t* bytes);
+int pt_reflect_planes(pt_ctx* ctx, const pt_reflect_desc* desc, pt_reflect_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

@@ -32,6 +32,7 @@ EXPORTS = [
     "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes", "pt_bloom_layout", "pt_bloom_planes",
     "pt_motion_blur_layout", "pt_motion_blur_planes",
     "pt_dof_layout", "pt_dof_planes", "pt_lens_warp_planes", "pt_warp_matrix", "pt_ao_layout", "pt_ao_planes",
+    "pt_reflect_layout", "pt_reflect_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -385,6 +386,28 @@ AO_PLANES = {"hit": 8, "position": 4, "ao": 1, "out": 4, "bent": 4}
 AO_OUTPUTS = ("ao", "out", "bent")
 
 
+PT_REFLECT_DEFAULT_RAYS_IN_FLIGHT = 1 << 23
+
+
+class ReflectDesc(C.Structure):  # pt_reflect_desc
+    _fields_ = [("hit", C.c_void_p), ("position", C.c_void_p), ("hit2", C.c_void_p), ("position2", C.c_void_p), ("ray", C.c_void_p),
+                ("sky", C.c_void_p), ("scratch", C.c_void_p), ("block_mask", C.c_void_p), ("bias", C.c_float), ("max_distance", C.c_float),
+                ("max_rays_in_flight", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ReflectStats(C.Structure):  # pt_reflect_stats
+    _fields_ = [("pixels", C.c_uint64), ("traced", C.c_uint64), ("skipped", C.c_uint64), ("nonfinite", C.c_uint64), ("invalid", C.c_uint64),
+                ("hits", C.c_uint64), ("escaped", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double), ("trace_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the frame-sized planes of pt_reflect_planes: 32-bit words per pixel (the scratch, one batch of rays, is pt_reflect_layout's)
+REFLECT_PLANES = {"hit": 8, "position": 4, "hit2": 8, "position2": 4, "ray": 8, "sky": 4}
+REFLECT_OUTPUTS = ("hit2", "position2", "ray", "sky")
+
+
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
 
 
@@ -694,6 +717,8 @@ def load_library() -> C.CDLL:
     L.pt_warp_matrix.argtypes = [vp, vp, u32, u32, vp]
     L.pt_ao_layout.argtypes = [vp, u32, u32, C.POINTER(C.c_size_t)]
     L.pt_ao_planes.argtypes = [vp, C.POINTER(AoDesc), C.POINTER(AoStats)]
+    L.pt_reflect_layout.argtypes = [vp, u32, C.POINTER(C.c_size_t)]
+    L.pt_reflect_planes.argtypes = [vp, C.POINTER(ReflectDesc), C.POINTER(ReflectStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

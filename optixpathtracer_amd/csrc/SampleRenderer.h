@@ -515,6 +515,22 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The size in bytes of reflectPlanes's scratch: one batch of rays (pt_reflect_layout); max_rays_in_flight 0 is the library's default.
+    size_t reflectLayout(uint32_t max_rays_in_flight = 0) {
+        size_t bytes = 0;
+        ck(pt_reflect_layout(ctx, max_rays_in_flight, &bytes));
+        return bytes;
+    }
+    // Mirror reflections from the G-buffer (pt_reflect_planes): every pixel of a hit in d.hit shoots its mirror ray through the current tree;
+    // what it sees is a second G-buffer — d.hit2 (pt_trace_device's pt_hit for that ray), d.position2, d.ray — and d.sky, the probe's radiance
+    // where the ray escapes.  d.scratch is reflectLayout's bytes, 16-byte aligned.  Returns the pixels, those traced, skipped (misses),
+    // non-finite and invalid, the rays that hit and escaped, the batches, and the device times of the pass and of its traversal launches.
+    pt_reflect_stats reflectPlanes(const pt_reflect_desc& d, pt_reflect_stats* stats = nullptr) {
+        pt_reflect_stats s{};
+        ck(pt_reflect_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

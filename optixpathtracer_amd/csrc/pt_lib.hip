@@ -42,3 +42,4 @@
 #include "pt_dof.hip"
 #include "pt_lens_warp.hip"
 #include "pt_ao.hip"
+#include "pt_reflect.hip"

@@ -1205,6 +1205,42 @@ class SampleRenderer:
         desc.seed, desc.flags = seed, _lib.PT_AO_JITTER if jitter else 0
         return self._run_pass("pt_ao_planes", desc, _lib.AoStats(), result)
 
+    def reflectLayout(self, max_rays_in_flight=0):
+        """The size in bytes of reflectPlanes's scratch (pt_reflect_layout): one batch of min(M, frame pixels) pixels, M = max_rays_in_flight
+        or the library's default (_lib.PT_REFLECT_DEFAULT_RAYS_IN_FLIGHT) when 0."""
+        nbytes = C.c_size_t()
+        self._ck(self._L.pt_reflect_layout(self._ctx, int(max_rays_in_flight), C.byref(nbytes)), "pt_reflect_layout")
+        return nbytes.value
+
+    def reflectPlanes(self, hit, position, hit2=None, position2=None, ray=None, sky=None, scratch=None, mask=None, bias=1e-3,
+                      max_distance=1e16, max_rays_in_flight=0) -> dict:
+        """Mirror reflections from the G-buffer (pt_reflect_planes, include/pt_amd.h: the rule, in full): every pixel of a hit shoots the
+        mirror image of its eye ray about the geometric normal through the context's current tree, from the hit position lifted by
+        bias * hit.t along the normal, and what the ray sees is written as a second G-buffer: hit2 (h, w, 8), the pt_hit that
+        traceDevice returns for that ray; position2 (h, w, 4), where it hits (.w 1; zeros where it does not); ray (h, w, 8), the ray in
+        traceDevice's layout; sky (h, w, 4), the probe's radiance where the ray escapes (.w 1; zeros elsewhere; needs setProbe).
+        surfacePlanes(hit=hit2), aoPlanes(hit2, position2) and every other pass that reads a hit plane work on the reflected surface.
+
+        hit (h, w, 8) and position (h, w, 4) are renderGBuffer's planes of this frame: CUDA float32 tensors on the context's device —
+        dense, any 4-byte-aligned storage offset — or raw device pointers.  The four outputs are optional; hit2 is allocated with torch,
+        zero-filled, when none is given.  scratch: a float32 (bytes / 4,) tensor of reflectLayout(max_rays_in_flight) bytes, 16-byte
+        aligned, or a raw pointer; allocated when None.  The rays are traced in batches of at most max_rays_in_flight (0: the library's
+        default); the result does not depend on it.  max_distance is the rays' tmax (the G-buffer's 1e16 by default).  mask: 8x8 blocks
+        as renderMask takes them, None = every block.  Ordering is on the device, as temporalMoments.
+        Returns {"hit2", "position2", "ray", "sky": the tensors (None for a raw pointer or an absent plane), "scratch", "stats": {pixels,
+        traced, skipped, nonfinite, invalid, hits, escaped, batches, kernel_ms, trace_ms}}."""
+        max_rays_in_flight = int(max_rays_in_flight)
+        if not 0 <= max_rays_in_flight < 2**32:
+            raise ValueError("reflectPlanes: max_rays_in_flight must be in [0,4294967295]")
+        given = dict(hit=hit, position=position, hit2=hit2, position2=position2, ray=ray, sky=sky)
+        desc = _lib.ReflectDesc()
+        result = self._bind_planes("reflectPlanes", desc, given, _lib.REFLECT_PLANES, ("hit", "position"), _lib.REFLECT_OUTPUTS,
+                                   alloc=("hit2",) if position2 is None and ray is None and sky is None else ())
+        self._bind_scratch("reflectPlanes", desc, result, scratch, lambda: (self.reflectLayout(max_rays_in_flight) // 4,))
+        m = self._bind_mask("reflectPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.bias, desc.max_distance, desc.max_rays_in_flight, desc.flags = float(bias), float(max_distance), max_rays_in_flight, 0
+        return self._run_pass("pt_reflect_planes", desc, _lib.ReflectStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
