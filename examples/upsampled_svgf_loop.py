@@ -44,10 +44,18 @@ Per frame, on `hi`:
      where the ray escaped and that albedo times the mean of step 10's irradiance elsewhere; it is blended with weight F into the pixels
      of mesh K — in torch: the composition is this example's, not a rule of the library.  The displayed frame then comes from the tone
      mapper, as with steps 14 to 16.
+ 19. with --sun [--sun-dir X Y Z --sun-spread S --sun-rays N --sun-radiance R G B], behind steps 11 and 12 and in front of step 18: a
+     distant disc light that the probe does not hold.  shadowPlanes shoots N any-hit rays a pixel towards it through `hi`'s tree, jittered
+     by the frame index, and writes the direct light (radiance * cosine * visibility); modulatePlanes multiplies it by step 9's albedo, and
+     the product is added to the composed frame: shadow edges at the display resolution.  With --reflect, reflectPlanes also writes
+     position2 and the mirror ray, a second shadowPlanes call lights the reflected surface (hit2, position2, view_ray = ray), and the
+     reflection's colour where the ray hit is that light times the reflected surface's albedo instead of the mean-irradiance stand-in.
+     The displayed frame then comes from the tone mapper.
 `hi` never renders a colour sample.
 
   python3 examples/upsampled_svgf_loop.py [--scene textured|two_box] [--scale 2|3|4] [--size 960 540] [--frames 16] [--lod] [--aniso N] [--edge-aa]
                                           [--ao] [--ao-rays N] [--ao-radius R] [--reflect] [--reflect-mesh K] [--reflectivity F]
+                                          [--sun] [--sun-dir X Y Z] [--sun-spread S] [--sun-rays N] [--sun-radiance R G B]
                                           [--auto-exposure] [--tonemap aces|reinhard|linear] [--bloom] [--bloom-threshold T]
                                           [--bloom-levels N] [--motion-blur] [--shutter F] [--blur-taps N]
                                           [--dof] [--focus F | --autofocus] [--aperture K] [--dof-taps N] [--out-dir .]
@@ -97,9 +105,12 @@ class UpsampledLoop:
     def __init__(self, model, size, scale, lod=False, aniso=0, spp=1, probe=None, plan=None, iterations=5, sigma_lum=4.0, min_length=4, max_history=32,
                  edge_aa=False, auto_exposure=False, tonemap="aces", bloom=False, bloom_threshold=1.0, bloom_levels=6,
                  motion_blur=False, shutter=0.5, blur_taps=12, dof=False, focus=4.0, autofocus=False, aperture=6.0, dof_taps=32,
-                 ao=False, ao_rays=4, ao_radius=0.5, reflect=False, reflect_mesh=0, reflectivity=0.5):
+                 ao=False, ao_rays=4, ao_radius=0.5, reflect=False, reflect_mesh=0, reflectivity=0.5,
+                 sun=False, sun_dir=(0.4, 1.0, -0.3), sun_spread=0.01, sun_rays=4, sun_radiance=(3.0, 2.9, 2.7)):
         import torch
 
+        self.sun = bool(sun)
+        self.sun_lights = [dict(dir=tuple(sun_dir), spread=float(sun_spread), radiance=tuple(sun_radiance), rays=int(sun_rays))]
         self.ao, self.ao_prm = bool(ao), dict(rays=int(ao_rays), radius=float(ao_radius))
         self.reflect, self.reflect_mesh, self.reflectivity = bool(reflect), int(reflect_mesh), float(reflectivity)
         lod = lod or aniso > 0  # the anisotropic pass uses the pyramid as well
@@ -163,6 +174,13 @@ class UpsampledLoop:
         if self.reflect:
             self.hit2, self.sky, self.albedo2, self.reflection = planes(h, w, 8), planes(h, w, 4), planes(h, w, 4), planes(h, w, 4)
             self.reflect_batch = torch.zeros((self.hi.reflectLayout() // 4,), device="cuda:0")
+        # step 19: the direct light, its product with the albedo, the rays' batch; with step 18 the same for the reflected surface, which
+        # also needs where the mirror ray hit and the ray itself
+        if self.sun:
+            self.sun_light, self.sun_lit = planes(h, w, 4), planes(h, w, 4)
+            self.sun_batch = torch.zeros((self.hi.shadowLayout(self.sun_lights) // 4,), device="cuda:0")
+            if self.reflect:
+                self.position2, self.ray2, self.sun_light2, self.sun_lit2 = planes(h, w, 4), planes(h, w, 8), planes(h, w, 4), planes(h, w, 4)
         self.accum = self.lo.deviceBuffer(R.PT_BUF_ACCUM)
         # per renderer: the scene's texcoords per primitive and, with --lod, the mip pyramid of its textures — once, before the loop
         self.table = {id(r): r.copyTexcoordsDevice() for r in (self.lo, self.hi)}
@@ -225,23 +243,39 @@ class UpsampledLoop:
         else:
             ao = dict(ao_ms=0.0, ao_trace_ms=0.0, ao_rays=0, ao_occluded=0, ao_batches=0, ao_chain_ms=0.0)
         # with auto exposure, depth of field, bloom or motion blur the tone mapper writes the displayed frame
-        shown = None if self.auto_exposure or self.dof or self.bloom or self.motion_blur or self.reflect else self.frame_rgba8
+        shown = None if self.auto_exposure or self.dof or self.bloom or self.motion_blur or self.reflect or self.sun else self.frame_rgba8
         if self.edge_aa:
             m = hi.modulatePlanes(irradiance, albedo=self.albedo, out=self.modulated)["stats"]
             e = hi.edgeAaPlanes(self.modulated, self.hi_gbuf["hit"], self.hi_gbuf["position"], out=self.final, frame=shown)["stats"]
         else:
             m = hi.modulatePlanes(irradiance, albedo=self.albedo, out=self.final, frame=shown)["stats"]
             e = dict(kernel_ms=0.0, boundary=0, blended=0)
+        sun = dict(sun_ms=0.0, sun_trace_ms=0.0, sun_rays=0, sun_occluded=0, sun_backfacing=0, sun_batches=0, sun_reflected_ms=0.0)
+        if self.sun:
+            hg = self.hi_gbuf
+            sh = hi.shadowPlanes(hg["hit"], hg["position"], lights=self.sun_lights, light=self.sun_light, scratch=self.sun_batch, jitter=True, seed=k)["stats"]
+            hi.modulatePlanes(self.sun_light, albedo=self.albedo, out=self.sun_lit)
+            self.final[..., 0:3] += self.sun_lit[..., 0:3]
+            sun.update(sun_ms=sh["kernel_ms"], sun_trace_ms=sh["trace_ms"], sun_rays=sh["rays"], sun_occluded=sh["occluded"], sun_backfacing=sh["backfacing"],
+                       sun_batches=sh["batches"])
         if self.reflect:
             import torch
 
             hg = self.hi_gbuf
-            rf = hi.reflectPlanes(hg["hit"], hg["position"], hit2=self.hit2, sky=self.sky, scratch=self.reflect_batch)["stats"]
+            more = dict(position2=self.position2, ray=self.ray2) if self.sun else {}
+            rf = hi.reflectPlanes(hg["hit"], hg["position"], hit2=self.hit2, sky=self.sky, scratch=self.reflect_batch, **more)["stats"]
             rs = self._albedo(hi, self.hit2, self.albedo2)  # every pass that reads a hit plane works on the second G-buffer
             escaped = self.sky[..., 3:4] == 1.0
             seen = escaped | (self.hit2.view(torch.int32)[..., 3:4] >= 0)  # the pixels whose mirror ray was traced
-            mean = irradiance[..., 0:3].mean(dim=(0, 1))
-            self.reflection[..., 0:3] = torch.where(escaped, self.sky[..., 0:3], self.albedo2[..., 0:3] * mean)
+            if self.sun:  # the reflected surface under the sun: facing is judged from the mirror ray's origin, not from the eye
+                s2 = hi.shadowPlanes(self.hit2, self.position2, lights=self.sun_lights, view_ray=self.ray2, light=self.sun_light2, scratch=self.sun_batch,
+                                     jitter=True, seed=k)["stats"]
+                hi.modulatePlanes(self.sun_light2, albedo=self.albedo2, out=self.sun_lit2)
+                reflected = self.sun_lit2[..., 0:3]
+                sun.update(sun_reflected_ms=s2["kernel_ms"])
+            else:
+                reflected = self.albedo2[..., 0:3] * irradiance[..., 0:3].mean(dim=(0, 1))
+            self.reflection[..., 0:3] = torch.where(escaped, self.sky[..., 0:3], reflected)
             self.reflection[..., 3] = seen[..., 0].to(torch.float32)
             words = hg["hit"].view(torch.int32)
             mirror = (words[..., 3:4] >= 0) & (words[..., 4:5] == self.reflect_mesh) & seen
@@ -278,7 +312,7 @@ class UpsampledLoop:
             self.cur = o
         else:
             x, tm = dict(kernel_ms=0.0, skipped=0, under=0, over=0), dict(kernel_ms=0.0, clipped=0)
-            if self.dof or self.bloom or self.motion_blur or self.reflect:
+            if self.dof or self.bloom or self.motion_blur or self.reflect or self.sun:
                 tm = hi.tonemapPlanes(lit, frame=self.frame_rgba8, op="linear", write_out=False)["stats"]
         t2 = time.perf_counter()
         ev = float(self.state[self.cur][0, 0]) if self.auto_exposure else 0.0  # read back for the caller's printing, outside the timed frame
@@ -290,7 +324,7 @@ class UpsampledLoop:
                     blended=e["blended"], exposure_ms=x["kernel_ms"], tonemap_ms=tm["kernel_ms"], ev=ev, skipped=x["skipped"], under=x["under"],
                     over=x["over"], clipped=tm["clipped"], bloom_ms=b["kernel_ms"], bright=b["bright"],
                     motion_blur_ms=mb["kernel_ms"], moving=mb["moving"], dof_ms=df["kernel_ms"], gathered=df["gathered"],
-                    focus=self.focus_now[0] if self.dof else 0.0, **ao, **rfl, mirrored=int(self.mirrored.sum()) if self.reflect else 0)
+                    focus=self.focus_now[0] if self.dof else 0.0, **ao, **rfl, **sun, mirrored=int(self.mirrored.sum()) if self.reflect else 0)
 
     def close(self):
         self.lo.close()
@@ -326,6 +360,11 @@ def main(argv=None):
     ap.add_argument("--reflect", action="store_true", help="mirror reflections (reflectPlanes) at the display resolution, blended into the pixels of one mesh")
     ap.add_argument("--reflect-mesh", type=int, default=0, metavar="K", help="with --reflect: the mesh that mirrors")
     ap.add_argument("--reflectivity", type=float, default=0.5, metavar="F", help="with --reflect: the reflection's weight in that mesh's pixels, in [0, 1]")
+    ap.add_argument("--sun", action="store_true", help="a distant disc light (shadowPlanes) at the display resolution, added to the composed frame; lights --reflect's surface too")
+    ap.add_argument("--sun-dir", type=float, nargs=3, default=[0.4, 1.0, -0.3], metavar=("X", "Y", "Z"), help="with --sun: the direction towards the light")
+    ap.add_argument("--sun-spread", type=float, default=0.01, metavar="S", help="with --sun: the tangent of the disc's angular radius, in [0, 1]")
+    ap.add_argument("--sun-rays", type=int, default=4, metavar="N", help="with --sun: rays per pixel and frame (1..32)")
+    ap.add_argument("--sun-radiance", type=float, nargs=3, default=[3.0, 2.9, 2.7], metavar=("R", "G", "B"), help="with --sun: the light's radiance")
     ap.add_argument("--out-dir", default=".")
     args = ap.parse_args(argv)
     w, h = args.size
@@ -335,7 +374,8 @@ def main(argv=None):
                          bloom_levels=args.bloom_levels, motion_blur=args.motion_blur, shutter=args.shutter, blur_taps=args.blur_taps,
                          dof=args.dof, focus=args.focus, autofocus=args.autofocus, aperture=args.aperture, dof_taps=args.dof_taps,
                          ao=args.ao, ao_rays=args.ao_rays, ao_radius=args.ao_radius, reflect=args.reflect, reflect_mesh=args.reflect_mesh,
-                         reflectivity=args.reflectivity)
+                         reflectivity=args.reflectivity, sun=args.sun, sun_dir=args.sun_dir, sun_spread=args.sun_spread, sun_rays=args.sun_rays,
+                         sun_radiance=args.sun_radiance)
     cam = R.make_camera(cam0, w / h)
     for k in range(args.frames):
         prev, cam = cam, R.make_camera(orbit(cam0, 0.01 * k), w / h)
@@ -348,6 +388,8 @@ def main(argv=None):
               + (f"occlusion {x['ao_ms']:.3f} ms (traversal {x['ao_trace_ms']:.3f} ms, {x['ao_occluded']} of {x['ao_rays']} rays occluded, {x['ao_batches']} batches), "
                  f"its accumulation, filter and product {x['ao_chain_ms']:.3f} ms; " if loop.ao else "")
               + (f"edge aa {x['edge_aa_ms']:.3f} ms, {x['blended']} of {x['boundary']} boundary pixels blended; " if loop.edge_aa else "")
+              + (f"sun {x['sun_ms']:.3f} ms (traversal {x['sun_trace_ms']:.3f} ms, {x['sun_occluded']} of {x['sun_rays']} rays shadowed, {x['sun_backfacing']} pairs "
+                 f"under the horizon, {x['sun_batches']} batches)" + (f", on the reflected surface {x['sun_reflected_ms']:.3f} ms; " if loop.reflect else "; ") if loop.sun else "")
               + (f"reflection {x['reflect_ms']:.3f} ms (traversal {x['reflect_trace_ms']:.3f} ms, {x['reflect_hits']} rays hit, {x['reflect_escaped']} escaped, "
                  f"{x['reflect_batches']} batches), its surface pass {x['reflect_surface_ms']:.3f} ms, {x['mirrored']} pixels mirror; " if loop.reflect else "")
               + (f"depth of field {x['dof_ms']:.3f} ms ({x['gathered']} pixels gather, focus {x['focus']:.3f}); " if loop.dof else "")
@@ -366,6 +408,8 @@ def main(argv=None):
         np.save(os.path.join(args.out_dir, "upsampled_svgf_ao.npy"), loop.ao_filtered.cpu().numpy())
     if loop.reflect:
         np.save(os.path.join(args.out_dir, "upsampled_svgf_reflection.npy"), loop.reflection.cpu().numpy())
+    if loop.sun:
+        np.save(os.path.join(args.out_dir, "upsampled_svgf_sun.npy"), loop.sun_light.cpu().numpy())
     print(f"wrote upsampled_svgf_final.npy and upsampled_svgf_frame.npy to {args.out_dir}")
     loop.close()
     return 0

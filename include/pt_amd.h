@@ -38,7 +38,8 @@
  * DEVICE pointers under the same contract (its ordering cases: tests/test_gpu_lens_warp.py); pt_warp_matrix is host arithmetic and touches
  * no device at all.  pt_ao_planes takes DEVICE pointers under the same contract (its ordering case: tests/test_gpu_ao.py); pt_ao_layout
  * touches no device memory.  pt_reflect_planes takes DEVICE pointers under the same contract (its ordering case:
- * tests/test_gpu_reflect.py); pt_reflect_layout touches no device memory.
+ * tests/test_gpu_reflect.py); pt_reflect_layout touches no device memory.  pt_shadow_planes takes DEVICE pointers under the same contract
+ * (its ordering case: tests/test_gpu_shadow.py); pt_shadow_layout touches no device memory.
  *
  * VERSIONING.  pt_version() = "ptamd <major>.<minor> ...".  Structs only ever grow at the end; a caller
  * that may meet a newer or older library uses pt_get_stats_n(ctx, &s, sizeof s) (copies the common
@@ -53,7 +54,7 @@
  * caller that may meet an older library looks the symbol up (dlsym) before it relies on one.  pt_bloom_layout and pt_bloom_planes were added
  * in the same way and keep "0.4" as well; so were pt_motion_blur_layout and pt_motion_blur_planes, and pt_dof_layout and pt_dof_planes,
  * and pt_lens_warp_planes and pt_warp_matrix, and pt_ao_layout and pt_ao_planes, and
- * pt_reflect_layout and pt_reflect_planes.
+ * pt_reflect_layout and pt_reflect_planes, and pt_shadow_layout and pt_shadow_planes.
  */
 #ifndef PT_AMD_H
 #define PT_AMD_H
@@ -2125,6 +2126,101 @@ typedef struct pt_reflect_desc {
 typedef struct pt_reflect_stats { uint64_t pixels, traced, skipped, nonfinite, invalid, hits, escaped, batches; double kernel_ms, trace_ms; } pt_reflect_stats;
 int pt_reflect_layout(const pt_ctx* ctx, uint32_t max_rays_in_flight, size_t* bytes);
 int pt_reflect_planes(pt_ctx* ctx, const pt_reflect_desc* desc, pt_reflect_stats* stats /* may be NULL */);
+
+/* SUN SHADOWS AND DIRECT LIGHT FROM THE G-BUFFER (no reference counterpart).  The third pass of the chain that asks the acceleration
+ * structure, and the most common question: does this surface point see the light?  The caller names up to PT_SHADOW_MAX_LIGHTS distant
+ * disc lights — a direction, an angular size, a radiance: a sun, a moon, a key light — and per pixel of a hit the pass shoots rays_i any-hit
+ * rays towards each light that stands above the pixel's horizon, through the context's CURRENT tree (it follows pt_update_meshes* and
+ * pt_transform_meshes), and writes the open fraction per light (visibility) and the lights' sum (light), which pt_modulate_planes multiplies
+ * by an albedo.  It works on any hit plane: renderGBuffer's, or pt_reflect_planes's hit2 / position2 with view_ray = its ray plane, which
+ * lights the mirrored surface (examples/upsampled_svgf_loop.py --sun, --sun --reflect).  The rule holds no random numbers, no CDF search
+ * and no transcendental: it is built from dot3, normalize3, pt_ao_planes's frame, pt_dof_planes's spiral and hash, and the any-hit query.
+ * Stateless like every pass here: the planes and the scratch are caller-owned DEVICE memory of the context's device (the planes 4-byte
+ * aligned, frame-sized, indexed Y * width + X; the scratch 16-byte aligned); block_mask and lights are HOST memory.
+ *
+ * The pixel set is pt_ao_planes's: the rank's owned pixels, view pixels only while views are set, whole blocks of block_mask.  A pixel
+ * outside the set is not written.  No address is formed from hit's prim, which is looked at for its sign only.
+ *
+ * Rule.  Float32 throughout, one rounding per operation, no fused multiply-add, sqrtf and / correctly rounded (pt_detmath.h's contract);
+ * dot3, normalize3, sel_max0 and "finite" are pt_ao_planes's.  R is the sum of the lights' rays.  (x, y) are the LOCAL coordinates of the
+ * pixel in its rectangle.
+ * Per light i, the same for every pixel: L_i = normalize3(dir_i); T_i, B_i = the frame of pt_ao_planes's step 4 with L_i in place of n:
+ *        sg = (L.z >= 0) ? 1.0f : -1.0f;  a = -1.0f / (sg + L.z);  b = (L.x * L.y) * a;
+ *        T = (1.0f + (sg * (L.x * L.x)) * a,  sg * b,  (-sg) * L.x);   B = (b,  sg + (L.y * L.y) * a,  -L.y).
+ * Per pixel p of the set:
+ *   1. h = hit[p].  If h.prim < 0 (the sign only; a miss): visibility = (1, 1, 1, 1), light = (0, 0, 0, 1); stats->skipped counts it; it
+ *      shoots no ray.
+ *   2. P = position[p].xyz, ng = h.ng, t = h.t.  If one of those seven words is not finite, or t > 0 is false, or, with view_ray, one of
+ *      view_ray[p]'s first three words is not finite: the same outputs as a miss; stats->nonfinite counts it; it shoots no ray.
+ *   3. Facing: E = view_ray[p].xyz when view_ray is given, else the eye of p's camera (the frame's, or with views the one of p's view).
+ *      n = dot3(ng, E - P) < 0 ? -ng : ng.  The origin: O = P + n * (bias * t) per component, the product first and then the sum.
+ *   4. Per light i, ascending: c = dot3(n, L_i).  If c > 0.0f is false the light is under the pixel's horizon: v_i = 0.0f, no ray is shot,
+ *      and stats->backfacing counts the pair.  Otherwise c_i = c > 1.0f ? 1.0f : c, and the rays of step 5 are shot.
+ *   5. The rays of light i, for k = 0 .. rays_i - 1:
+ *        rho = sqrtf(((float)k + 0.5f) / (float)rays_i);  Dk = D[(k + k0) & 127], D being pt_dof_planes's spiral; k0 = 0 without
+ *        PT_SHADOW_JITTER, with it k0 = pass_hash(x, y, seed + i) & 63, pt_dof_planes's hash, the addition in uint32_t (it wraps);
+ *        a = (rho * Dk.x) * spread_i;  b = (rho * Dk.y) * spread_i;
+ *        w = (L_i + T_i * a) + B_i * b per component;  d = normalize3(w).
+ *      The ray is (O, tmin = 0.0f, d, tmax = max_distance), in pt_trace_device's eight words, and is tested with pt_trace_device's validity
+ *      rule as in pt_ao_planes: an invalid ray is not traced, counts as unoccluded, and stats->invalid counts it.  occ is exactly what
+ *      pt_trace_device(PT_QUERY_ANY) returns for that ray over the current geometry.  A sample under the surface's horizon is not
+ *      special-cased: the tree decides.
+ *   6. v_i = (float)open_i / (float)rays_i, open_i the rays of light i with occ == 0 (the invalid ones included).  Absent lights
+ *      (i >= num_lights) have v_i = 1.0f.  visibility = (v_0, v_1, v_2, v_3).
+ *   7. light.xyz starts at +0 and adds radiance_i * (c_i * v_i) per component, over i ascending, over the lights of step 5 only;
+ *      light.w = 1.0f.  The clamp of step 4 and the finite, non-negative radiances keep light free of NaN for any finite input.
+ * stats->pixels is the size of the set; traced the pixels that passed steps 1 and 2 (pixels = skipped + nonfinite + traced); backfacing the
+ * (pixel, light) pairs under the horizon; rays the rays traced (the slots of step 5 minus invalid); occluded those with occ == 1.
+ *
+ * Batches and scratch.  The pixel list is cut into batches of floor(M / R) pixels, M = max_rays_in_flight or, when that is 0,
+ * PT_SHADOW_DEFAULT_RAYS_IN_FLIGHT.  For each batch, in stream order, the pass generates the rays, traces them (the traversal kernel and
+ * grid of pt_trace_device) and reduces them; stats->batches says how many ran.  The scratch holds ONE batch — a 256-byte head, as in
+ * pt_ao_planes, then 40 bytes a ray slot, then 32 bytes a batch pixel (a first slot and a stride per light) — and nothing per frame
+ * pixel.  pt_shadow_layout returns its size for min(floor(M / R), width * height) pixels a batch: 256 + pixels * (40 * R + 32), rounded up
+ * to 16.  It looks at the lights' rays only.  The result does not depend on M, bit for bit.
+ *
+ * Refused with PT_ERR_INVALID (text in pt_last_error, nothing enqueued, nothing written): pt_ao_planes's list (a null ctx or desc; no
+ * pt_resize yet; hit, position or scratch NULL; a plane that fails the pointer checks; a written plane or the scratch overlapping anything;
+ * a scratch that is not 16-byte aligned or smaller than the layout; bias negative or not finite), and: num_lights outside
+ * 1 .. PT_SHADOW_MAX_LIGHTS; lights NULL; a light with rays == 0, or R > PT_SHADOW_MAX_RAYS; a non-finite dir, or a dir for which normalize3
+ * does not give finite components with dot3(L, L) > 0.5f; spread not finite or outside [0, 1]; a radiance that is not finite or negative;
+ * max_distance not finite or not > 0; max_rays_in_flight non-zero and below R; visibility and light both NULL; an unknown flag bit.  The
+ * traversal's stack-overflow bit gives PT_ERR_UNSUPPORTED, as in pt_trace.
+ * Ordering and state, as pt_ao_planes: the call waits for the frames in flight and completes queued queries (their counts stay for
+ * pt_query_wait), runs on pt_stream(ctx) under the STREAM CONTRACT, is complete when it returns, and touches neither the context's query
+ * state, nor the frame buffers, nor pt_stats.  For zero pixels it launches nothing and returns PT_OK.
+ * Not part of this interface: lights sampled from the probe; point or area lights at a finite distance; a shading normal; coloured or
+ * partial occluders; an asynchronous variant; a pt_multi_* wrapper (per-rank calls work). */
+#define PT_SHADOW_MAX_LIGHTS 4
+#define PT_SHADOW_MAX_RAYS 32                 /* the SUM of the lights' rays */
+#define PT_SHADOW_DEFAULT_RAYS_IN_FLIGHT 8388608u
+typedef struct pt_shadow_light {              /* 32 bytes */
+    float dir[3];       /* towards the light, any length the checks above accept */
+    float spread;       /* tan of the disc's angular radius, 0 .. 1; 0 = a point at infinity */
+    float radiance[3];  /* finite, >= 0 */
+    uint32_t rays;      /* >= 1 */
+} pt_shadow_light;
+typedef enum pt_shadow_flags { PT_SHADOW_JITTER = 1 } pt_shadow_flags;
+typedef struct pt_shadow_desc {
+    const void*  hit;          /* w*h x pt_hit, required */
+    const float* position;     /* w*h x 4, required */
+    const float* view_ray;     /* w*h x 8 or NULL: pt_reflect_planes's `ray` plane; its origin replaces the eye in step 3 */
+    float* visibility;         /* w*h x 4 or NULL, exclusive: v_0 .. v_3 */
+    float* light;              /* w*h x 4 or NULL, exclusive: (sum_i radiance_i * (c_i * v_i), 1) */
+    void*  scratch;            /* pt_shadow_layout's bytes, 16-byte aligned, required, exclusive */
+    const uint8_t* block_mask; /* HOST, as pt_render_gbuffer, or NULL */
+    const pt_shadow_light* lights; /* HOST, num_lights entries */
+    uint32_t num_lights;       /* 1 .. PT_SHADOW_MAX_LIGHTS */
+    uint32_t max_rays_in_flight; /* 0 = PT_SHADOW_DEFAULT_RAYS_IN_FLIGHT; else >= R: bounds the scratch */
+    float max_distance;        /* finite, > 0: the rays' tmax, world units */
+    float bias;                /* finite, >= 0: the origin is lifted by bias * hit.t along the normal */
+    uint32_t seed;             /* PT_SHADOW_JITTER: e.g. the frame index */
+    uint32_t flags;            /* pt_shadow_flags */
+} pt_shadow_desc;
+typedef struct pt_shadow_stats { uint64_t pixels, traced, skipped, nonfinite, backfacing, rays, occluded, invalid, batches;
+                                 double kernel_ms, trace_ms; } pt_shadow_stats;
+int pt_shadow_layout(const pt_ctx* ctx, const pt_shadow_light* lights, uint32_t num_lights, uint32_t max_rays_in_flight, size_t* bytes);
+int pt_shadow_planes(pt_ctx* ctx, const pt_shadow_desc* desc, pt_shadow_stats* stats /* may be NULL */);
 
 /* The acceleration structure as the traversal kernels see it, copied to host memory — for inspection, for a host-side
  * traversal of the SAME tree (bench.py's CPU baseline, tests) or for serialisation.  Call with nodes == tris == NULL to get the

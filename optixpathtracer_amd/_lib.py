@@ -32,7 +32,7 @@ EXPORTS = [
     "pt_upsample_planes", "pt_edge_aa_planes", "pt_exposure_planes", "pt_tonemap_planes", "pt_bloom_layout", "pt_bloom_planes",
     "pt_motion_blur_layout", "pt_motion_blur_planes",
     "pt_dof_layout", "pt_dof_planes", "pt_lens_warp_planes", "pt_warp_matrix", "pt_ao_layout", "pt_ao_planes",
-    "pt_reflect_layout", "pt_reflect_planes",
+    "pt_reflect_layout", "pt_reflect_planes", "pt_shadow_layout", "pt_shadow_planes",
     "pt_set_views", "pt_get_views", "pt_set_view_cameras", "pt_set_view_cameras_device", "pt_multi_set_views", "pt_multi_set_view_cameras",
 ]
 
@@ -408,6 +408,36 @@ REFLECT_PLANES = {"hit": 8, "position": 4, "hit2": 8, "position2": 4, "ray": 8, 
 REFLECT_OUTPUTS = ("hit2", "position2", "ray", "sky")
 
 
+PT_SHADOW_MAX_LIGHTS = 4
+PT_SHADOW_MAX_RAYS = 32  # the sum of the lights' rays
+PT_SHADOW_DEFAULT_RAYS_IN_FLIGHT = 1 << 23
+PT_SHADOW_JITTER = 1  # pt_shadow_flags
+
+
+class ShadowLight(C.Structure):  # pt_shadow_light
+    _fields_ = [("dir", C.c_float * 3), ("spread", C.c_float), ("radiance", C.c_float * 3), ("rays", C.c_uint32)]
+
+
+class ShadowDesc(C.Structure):  # pt_shadow_desc
+    _fields_ = [("hit", C.c_void_p), ("position", C.c_void_p), ("view_ray", C.c_void_p), ("visibility", C.c_void_p), ("light", C.c_void_p),
+                ("scratch", C.c_void_p), ("block_mask", C.c_void_p), ("lights", C.c_void_p), ("num_lights", C.c_uint32),
+                ("max_rays_in_flight", C.c_uint32), ("max_distance", C.c_float), ("bias", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ShadowStats(C.Structure):  # pt_shadow_stats
+    _fields_ = [("pixels", C.c_uint64), ("traced", C.c_uint64), ("skipped", C.c_uint64), ("nonfinite", C.c_uint64), ("backfacing", C.c_uint64),
+                ("rays", C.c_uint64), ("occluded", C.c_uint64), ("invalid", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double),
+                ("trace_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the frame-sized planes of pt_shadow_planes: 32-bit words per pixel (the scratch, one batch of rays, is pt_shadow_layout's)
+SHADOW_PLANES = {"hit": 8, "position": 4, "view_ray": 8, "visibility": 4, "light": 4}
+SHADOW_OUTPUTS = ("visibility", "light")
+
+
 PT_TMOM_CLEAR_COLOR, PT_TMOM_CLAMP = 1, 2  # pt_tmom_flags
 
 
@@ -719,6 +749,8 @@ def load_library() -> C.CDLL:
     L.pt_ao_planes.argtypes = [vp, C.POINTER(AoDesc), C.POINTER(AoStats)]
     L.pt_reflect_layout.argtypes = [vp, u32, C.POINTER(C.c_size_t)]
     L.pt_reflect_planes.argtypes = [vp, C.POINTER(ReflectDesc), C.POINTER(ReflectStats)]
+    L.pt_shadow_layout.argtypes = [vp, C.POINTER(ShadowLight), u32, u32, C.POINTER(C.c_size_t)]
+    L.pt_shadow_planes.argtypes = [vp, C.POINTER(ShadowDesc), C.POINTER(ShadowStats)]
     L.pt_temporal_moments.argtypes = [vp, C.POINTER(TMomDesc), C.POINTER(TMomStats)]
     L.pt_modulate_planes.argtypes = [vp, C.POINTER(ModulateDesc), C.POINTER(ModulateStats)]
     L.pt_sample_plan.argtypes = [vp, C.POINTER(PlanDesc), C.POINTER(PlanStats)]

@@ -531,6 +531,24 @@ class SampleRenderer {
         if (stats) *stats = s;
         return s;
     }
+    // The size in bytes of shadowPlanes's scratch: one batch of rays (pt_shadow_layout) for these lights' ray counts; max_rays_in_flight 0
+    // is the library's default.
+    size_t shadowLayout(const pt_shadow_light* lights, uint32_t num_lights, uint32_t max_rays_in_flight = 0) {
+        size_t bytes = 0;
+        ck(pt_shadow_layout(ctx, lights, num_lights, max_rays_in_flight, &bytes));
+        return bytes;
+    }
+    // Shadows and direct light of d.num_lights distant disc lights from the G-buffer (pt_shadow_planes): every pixel of a hit in d.hit
+    // shoots each light's rays, for the lights above its horizon, through the current tree, into d.visibility (the open fraction per light)
+    // and / or d.light (the sum of radiance * cosine * visibility, 1 in .w); d.view_ray, pt_reflect_planes's ray plane, lights a reflected
+    // surface.  d.scratch is shadowLayout's bytes, 16-byte aligned.  Returns the pixels, those traced, skipped (misses) and non-finite, the
+    // (pixel, light) pairs under the horizon, the rays traced, occluded and invalid, the batches, and the device times.
+    pt_shadow_stats shadowPlanes(const pt_shadow_desc& d, pt_shadow_stats* stats = nullptr) {
+        pt_shadow_stats s{};
+        ck(pt_shadow_planes(ctx, &d, &s));
+        if (stats) *stats = s;
+        return s;
+    }
     // Which 8x8 blocks of the coming frame need new samples (pt_sample_plan): those where the reprojection loses a pixel, where enough
     // pixels have a short history or moments that are still noisy, and those the refresh names.  d.block_mask_out is HOST memory, one
     // byte per block: what renderMask and the passes take as their mask.  Returns the block and pixel counts and the device time.

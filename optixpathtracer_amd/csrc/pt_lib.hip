@@ -43,3 +43,4 @@
 #include "pt_lens_warp.hip"
 #include "pt_ao.hip"
 #include "pt_reflect.hip"
+#include "pt_shadow.hip"

@@ -1241,6 +1241,83 @@ class SampleRenderer:
         desc.bias, desc.max_distance, desc.max_rays_in_flight, desc.flags = float(bias), float(max_distance), max_rays_in_flight, 0
         return self._run_pass("pt_reflect_planes", desc, _lib.ReflectStats(), result)
 
+    @staticmethod
+    def _shadow_lights(fn, lights, max_rays_in_flight=0):
+        """The ctypes array of `lights`: _lib.ShadowLight records or dicts / sequences of (dir, spread, radiance, rays), or one of them
+        alone; checks the counts"""
+        # one (dir, spread, radiance, rays) tuple, not four lights: its second item is a number
+        lone_tuple = isinstance(lights, (tuple, list)) and len(lights) == 4 and isinstance(lights[1], (int, float, np.floating, np.integer))
+        if isinstance(lights, (_lib.ShadowLight, dict)) or lone_tuple:
+            lights = [lights]
+        lights = list(lights) if lights is not None else []
+        if not 1 <= len(lights) <= _lib.PT_SHADOW_MAX_LIGHTS:
+            raise ValueError(f"{fn}: 1..{_lib.PT_SHADOW_MAX_LIGHTS} lights are expected, not {len(lights)}")
+        arr = (_lib.ShadowLight * len(lights))()
+        for i, l in enumerate(lights):
+            if isinstance(l, _lib.ShadowLight):
+                d, spread, rad, rays = tuple(l.dir), l.spread, tuple(l.radiance), l.rays
+            elif isinstance(l, dict):
+                d, spread, rad, rays = l["dir"], l.get("spread", 0.0), l.get("radiance", (1.0, 1.0, 1.0)), l.get("rays", 1)
+            else:
+                d, spread, rad, rays = l
+            d, rad, rays = tuple(float(v) for v in d), tuple(float(v) for v in rad), int(rays)
+            if len(d) != 3 or len(rad) != 3:
+                raise ValueError(f"{fn}: light {i}: dir and radiance must be three floats")
+            if not 1 <= rays < 2**32:
+                raise ValueError(f"{fn}: light {i}: rays must be >= 1, not {rays}")
+            arr[i].dir[:], arr[i].spread, arr[i].radiance[:], arr[i].rays = d, float(spread), rad, rays
+        total = sum(l.rays for l in arr)
+        if total > _lib.PT_SHADOW_MAX_RAYS:
+            raise ValueError(f"{fn}: the lights' rays add up to {total}, above {_lib.PT_SHADOW_MAX_RAYS}")
+        max_rays_in_flight = int(max_rays_in_flight)
+        if not 0 <= max_rays_in_flight < 2**32 or 0 < max_rays_in_flight < total:
+            raise ValueError(f"{fn}: max_rays_in_flight must be 0 or in [the lights' rays,4294967295]")
+        return arr
+
+    def shadowLayout(self, lights, max_rays_in_flight=0):
+        """The size in bytes of shadowPlanes's scratch (pt_shadow_layout): one batch of min(floor(M / R), frame pixels) pixels, R the sum of
+        the lights' rays, M = max_rays_in_flight or the library's default (_lib.PT_SHADOW_DEFAULT_RAYS_IN_FLIGHT) when 0."""
+        arr = self._shadow_lights("shadowLayout", lights, max_rays_in_flight)
+        nbytes = C.c_size_t()
+        self._ck(self._L.pt_shadow_layout(self._ctx, arr, len(arr), int(max_rays_in_flight), C.byref(nbytes)), "pt_shadow_layout")
+        return nbytes.value
+
+    def shadowPlanes(self, hit, position, lights=None, view_ray=None, visibility=None, light=None, scratch=None, mask=None,
+                     max_distance=1e16, bias=1e-3, seed=0, jitter=False, max_rays_in_flight=0) -> dict:
+        """Shadows and direct light of up to four distant disc lights from the G-buffer (pt_shadow_planes, include/pt_amd.h: the rule, in
+        full).  lights: 1..4 of _lib.ShadowLight, dict(dir=, spread=, radiance=, rays=) or (dir, spread, radiance, rays): `dir` points
+        towards the light, `spread` is the tangent of the disc's angular radius (0: a point at infinity), `rays` the any-hit rays a pixel
+        shoots at it; the rays of all lights add up to at most 32.  Every pixel of a hit shoots them, for each light above its horizon,
+        through the context's current tree, from the hit position lifted by bias * hit.t along the normal.  visibility (h, w, 4) holds the
+        open fraction per light (1 for an absent light and for a miss), light (h, w, 4) the sum of radiance * cosine * visibility with 1
+        in .w: what modulatePlanes multiplies by an albedo.
+
+        hit (h, w, 8) and position (h, w, 4) are renderGBuffer's planes of this frame, or reflectPlanes's hit2 and position2 with
+        view_ray = its `ray` plane (h, w, 8), whose origin then stands in for the eye: CUDA float32 tensors on the context's device —
+        dense, any 4-byte-aligned storage offset — or raw device pointers.  light is allocated with torch, zero-filled, when neither
+        output is given.  scratch: a float32 (bytes / 4,) tensor of shadowLayout(lights, max_rays_in_flight) bytes, 16-byte aligned, or a
+        raw pointer; allocated when None.  The rays are traced in batches of at most max_rays_in_flight (0: the library's default); the
+        result does not depend on it.  jitter: each pixel's pattern is turned by a hash of its coordinates, `seed` and the light's index.
+        mask: 8x8 blocks as renderMask takes them, None = every block.  Ordering is on the device, as temporalMoments.
+        Returns {"visibility", "light": the tensors (None for a raw pointer or an absent plane), "scratch", "stats": {pixels, traced,
+        skipped, nonfinite, backfacing, rays, occluded, invalid, batches, kernel_ms, trace_ms}}."""
+        if lights is None:
+            raise ValueError("shadowPlanes: lights is required")
+        seed = int(seed)
+        if not 0 <= seed < 2**32:
+            raise ValueError("shadowPlanes: seed must be in [0,4294967295]")
+        arr = self._shadow_lights("shadowPlanes", lights, max_rays_in_flight)
+        given = dict(hit=hit, position=position, view_ray=view_ray, visibility=visibility, light=light)
+        desc = _lib.ShadowDesc()
+        result = self._bind_planes("shadowPlanes", desc, given, _lib.SHADOW_PLANES, ("hit", "position"), _lib.SHADOW_OUTPUTS,
+                                   alloc=("light",) if visibility is None else ())
+        self._bind_scratch("shadowPlanes", desc, result, scratch, lambda: (self.shadowLayout(arr, max_rays_in_flight) // 4,))
+        m = self._bind_mask("shadowPlanes", desc, mask)  # noqa: F841 (kept until the call has returned)
+        desc.lights, desc.num_lights = C.addressof(arr), len(arr)  # (arr is kept until the call has returned)
+        desc.max_rays_in_flight, desc.max_distance, desc.bias = int(max_rays_in_flight), float(max_distance), float(bias)
+        desc.seed, desc.flags = seed, _lib.PT_SHADOW_JITTER if jitter else 0
+        return self._run_pass("pt_shadow_planes", desc, _lib.ShadowStats(), result)
+
     def samplePlan(self, motion, hit, position, prev_hit, prev_position, history_in, moments_in, length_in, mask=None, normal_cos=0.9,
                    plane_eps=0.01, min_weight=0.25, threshold=0.05, dark_floor=0.01, min_length=4, min_pixels=4, refresh_period=0,
                    frame_index=0) -> dict:
