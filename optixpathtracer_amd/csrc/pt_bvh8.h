@@ -116,6 +116,15 @@ PT_DEV uint32_t leaf_count(uint32_t lbits, uint32_t s) { return (uint32_t)__popc
 // that finish before it, instead of one by one where they finish: 1/8 share 1.78 -> 1.90 ms, full frame 7.84 -> 8.16.)
 #define PT8_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
+// Lane masks (trace8_wave keeps its lane states as 64-bit masks in scalar registers).  PT8_VOTE takes a COMPARE of per-lane integers and nothing
+// else: the ballot of a compare is the compare's own result, the ballot of any other boolean is selected as 0/1 into a register and compared
+// again.  PT8_LANE_IN is the way back: this lane's bit of a wave-uniform mask as a predicate, which is the mask itself ANDed into exec.
+#define PT8_VOTE(cmp) __builtin_amdgcn_ballot_w64(cmp)
+#define PT8_LANE_IN(mask) __builtin_amdgcn_inverse_ballot_w64(mask)
+PT_DEV uint32_t pt8_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); } // a value every lane holds alike, into a scalar register
+// the phase of the traversal loop as a type: the step bodies are written once and compiled once per phase
+template <bool STEALING> struct Pt8Phase { static constexpr bool stealing = STEALING; };
+
 #define PT_WAVELOG_CAP (1u << 20)
 #ifdef PT_DEBUG_STATS
 #define PT_STAT(x) x
@@ -161,6 +170,17 @@ typedef uint32_t* Global32;
 // LOCAL = true (pt_fused.h): the wave traverses a private window of the queue arrays — entries [woff, woff + ln1) of `a.queue`'s arrays and, in
 // TR_UNIFIED, the shadow entries [woff, woff + ln2) of `a.queue2`'s — on its own: no sub-queue prefix, no chunk counter, every ray taken by
 // this wave (its spare lanes steal from the first iteration it has fewer rays than lanes).  Spill stack and fault word are the launch's.
+//
+// Two phases, two loops.  A wave's life is a BULK phase — write back what finished, refill idle lanes from the queue, traverse until fewer than
+// PT8_REFILL lanes hold a ray — followed by a STEALING phase: steal round, traverse, PT8_STEAL_PERIOD iterations at a time.  It crosses once,
+// after the refill that took the last of its rays (`exhausted`), at the `break` of the bulk phase's loop; what used to be the `if (!stealing)`
+// block (owner, s_leaf, s_cnt, s_key of the rays in flight) sits between the two loops.  A wave whose first refill exhausts its share (the
+// fused loop's waves always, and every wave of a launch of up to 64 rays per wave) never traverses in the bulk loop.  One loop served both
+// phases before, and every bulk iteration paid for the other phase: a wait for LDS and a branch round the s_key refresh at its top, the
+// steal-period test at its bottom, the atomics and result stores of the stealing finish() inlined in its pop path with a dozen scalar mask
+// merges behind them.  The step bodies are written once (`iterate`, a generic lambda over Pt8Phase) and compiled per phase: in the bulk loop a
+// finished lane only marks itself (pm = 0, sp = -1) and the only LDS accesses are the pop and the push.  Lane states are masks in scalar
+// registers (`act`), the refill's cursors scalar too.  Listing, hand walk and measurements: profiles/rwzztwo_summary.md.
 template <int MODE, bool LOCAL, bool CARRY = false>
 PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t nw, const uint32_t ln1, const uint32_t ln2, const uint32_t woff) {
     __shared__ uint32_t s_stack[PT8_LDS_DEPTH * 2 * 64];
@@ -176,8 +196,9 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     const uint32_t gstride = gridDim.x * 64u;
     const int lds_depth = PT8_LDS_DEPTH - a.lds_skip;
     // index space of the launch: TR_UNIFIED: [0,n2) = shadow rays of `queue2`, [n2, n) = rays of `queue`; else [0,n1) = rays of `queue`
-    const uint32_t n1 = LOCAL ? ln1 : qreader_init(a.queue, s_prefix);
-    const uint32_t n2 = (MODE == TR_UNIFIED) ? (LOCAL ? ln2 : qreader_init(a.queue2, s_prefix2)) : 0u;
+    // (wave-uniform, and read from LDS: through readfirstlane, so that the refill's cursors below are scalar registers and scalar compares)
+    const uint32_t n1 = pt8_uniform(LOCAL ? ln1 : qreader_init(a.queue, s_prefix));
+    const uint32_t n2 = (MODE == TR_UNIFIED) ? pt8_uniform(LOCAL ? ln2 : qreader_init(a.queue2, s_prefix2)) : 0u;
     const uint32_t n = n1 + n2;
     uint32_t chunk = (n / (nw * 2u)) & ~(uint32_t)(PT8_MIN_CHUNK < 64 ? PT8_MIN_CHUNK - 1 : 63);
     chunk = chunk < (uint32_t)PT8_MIN_CHUNK ? (uint32_t)PT8_MIN_CHUNK : (chunk > (uint32_t)PT8_CHUNK ? (uint32_t)PT8_CHUNK : chunk);
@@ -190,17 +211,19 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     bool shadow_lane = (MODE == TR_SHADOW_APPLY); // TR_UNIFIED: per lane, set at refill
 
-    bool active = false, exhausted = false;
+    // Lane states are 64-bit lane masks in scalar registers, changed at wave-uniform places only.  A lane holds a ray exactly while its `pm` is
+    // not 0 (start_ray sets at least four of its bits, finish() clears it): one compare at the bottom of an iteration gives `act`, and a
+    // predicate is a mask put into exec (PT8_LANE_IN), never a 0/1 register that is compared again.
+    unsigned long long act = 0ull; // lanes that hold a ray
     RaySetup r;
     r.o = r.d = r.idir = r.dn = mk3(0.f);
     float tmin = 0.f, tmax = 0.f, best = 0.f;
     int32_t bprim = -1;                        // closest-hit lanes: primitive of the best hit; shadow lanes: 1 = occluded
     int32_t bleaf = -1;                        // closest-hit lanes: leaf triangle of the best hit (before the stealing phase; then s_leaf)
-    uint32_t pm = 0;                           // near-side slot masks of the ray's octant: z half | y quarters << 8 | x slots << 16
+    uint32_t pm = 0;                           // near-side slot masks of the ray's octant: z half | y quarters << 8 | x slots << 16; 0 = the lane holds no ray
     uint32_t g_base = 0, g_imask = 0, g_hits = 0; // current node group: children still to visit (slot positions)
     uint32_t t_base = 0, t_mask = 0, t_bits = 0; // current triangle group: pending bits of the node's leafbits
-    int sp = 0;
-    bool stealing = false;   // wave-uniform: the queue is exhausted and the shared records are in use
+    int sp = 0;              // levels on the traversal stack; -1: the lane holds a finished ray whose result is not written yet (bulk phase only)
     // four small per-lane fields share one register (the kernel sits exactly at the 96 VGPRs of 5 waves per SIMD):
     //   owner (bits 0-7): the lane whose shared record this lane's ray belongs to | hint1, hint2 (8-15, 16-23): sub-queue of the lane's last
     //   queue lookups | sb (24-31): stack bottom — levels [sb, sp) are live, entries below sb were taken by co-workers
@@ -210,7 +233,6 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
 #define SET_OWNER(v) (misc = (misc & ~0xffu) | (uint32_t)(v))
 #define SET_SB(v) (misc = (misc & 0x00ffffffu) | ((uint32_t)(v) << 24))
     uint32_t slot = 0; // position of the lane's ray in its queue's arrays (PathState)
-    bool unwritten = false; // this lane holds a finished ray whose result is not written yet
     PT_STAT(uint32_t c_nodes = 0; uint32_t c_tris = 0; uint32_t c_maxsp = 0; uint32_t c_push = 0; uint32_t c_ray = 0; uint32_t c_raymax = 0; uint32_t c_iters = 0;
             uint32_t c_act = 0; uint32_t c_exec = 0; uint32_t c_nodeit = 0;)
     PT_WLOG(const unsigned long long w_t0 = wall_clock64(); unsigned long long w_tex = 0; uint32_t w_iters = 0;)
@@ -231,13 +253,17 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
     const Global32 ovf_stack = (Global32)a.ovf;
     auto push = [&](uint32_t v0, uint32_t v1) {
         PT_STAT(++c_push; if ((uint32_t)sp + 1 > c_maxsp) c_maxsp = sp + 1;)
-        if (sp < lds_depth) {
+        if (__builtin_expect(sp < lds_depth, 1)) { // the hot path, and the only one
             lds_stack[(sp * 2) * 64 + lane] = v0;
             lds_stack[(sp * 2 + 1) * 64 + lane] = v1;
             ++sp;
-        } else if (sp < lds_depth + a.ovf_depth) {
-            ovf_stack[(size_t)((sp - lds_depth) * 2) * gstride + gtid] = v0;
-            ovf_stack[(size_t)((sp - lds_depth) * 2 + 1) * gstride + gtid] = v1;
+            return;
+        }
+        // one cold block: a spill level, its address formed here, or the full stack
+        const int lv = sp - lds_depth;
+        if (lv < a.ovf_depth) {
+            ovf_stack[(size_t)(lv * 2) * gstride + gtid] = v0;
+            ovf_stack[(size_t)(lv * 2 + 1) * gstride + gtid] = v1;
             ++sp;
         } else {
             // Stack full: pt_create refuses trees deeper than the stack, so this is unreachable unless that check is
@@ -296,22 +322,21 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
         return ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)bprim;
     };
     // this lane is done with its (share of the) ray
-    auto finish = [&]() {
-        if (stealing) {
+    auto finish = [&](auto phase) {
+        pm = 0u; // the lane holds no ray any more: it leaves `act` at the bottom of the iteration
+        if (decltype(phase)::stealing) {
             atomicMin(&s_key[OWNER], local_key());
             if (atomicSub(&s_cnt[OWNER], 1u) == 1u) { // the last co-worker publishes the merged result
                 const unsigned long long k = s_key[OWNER];
                 if (is_shadow()) write_result(0.f, k == 0ull ? 1 : 0);
                 else write_result(__uint_as_float((uint32_t)(k >> 32)), (int32_t)(uint32_t)k < 0 ? -1 : s_leaf[OWNER]);
             }
-            active = false;
             return;
         }
         // Before the stealing phase the result is not written here: a finish reached by one or two lanes at a time would stall the whole
         // wave on the write-back's dependent loads (pending contribution -> accumulator).  The lane keeps (slot, best, bprim) — it is
-        // idle until the next refill — and all finished lanes write together at the top of the loop.
-        unwritten = true;
-        active = false;
+        // idle until the next refill — and all lanes that finished in the bulk loop write together at the top of the outer loop.
+        sp = -1;
         PT_STAT(if (c_ray > c_raymax) c_raymax = c_ray;
                 if (a.dbg) atomicAdd(&a.dbg[(is_shadow() ? 32 : 16) + (31 - __clz((int)(c_ray | 1u)))], 1ull);
                 c_ray = 0;)
@@ -333,16 +358,153 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
         t_mask = 0;
     };
 
+    // ---------------- traverse: one iteration of either phase's loop
+    auto iterate = [&](auto phase) {
+        constexpr bool STEALING = decltype(phase)::stealing;
+        if (STEALING) {
+            if (PT8_LANE_IN(act)) { // pick up what the ray's other workers found
+                const unsigned long long k = s_key[OWNER];
+                if (is_shadow()) {
+                    if (k == 0ull) finish(phase); // occluded elsewhere: nothing left to do for this ray
+                } else if (k < local_key()) {
+                    best = __uint_as_float((uint32_t)(k >> 32));
+                    bprim = (int32_t)(uint32_t)k;
+                }
+            }
+            act = PT8_VOTE(pm != 0u);
+        }
+        PT_WLOG(const unsigned long long w_a = clock64();)
+        // the vote: one compare, two scalar ANDs.  A lane of `act` with triangles pending wants a triangle step, any other lane of `act` a
+        // node step (which also covers "group empty → pop")
+        const unsigned long long m_pend = PT8_VOTE(t_mask != 0u);
+        const unsigned long long m_tri = act & m_pend, m_node = act & ~m_pend;
+        // One step type per iteration, the one more lanes wait for (biased 2:1 towards triangle steps), so that the two code paths never
+        // run with complementary half-empty masks.  (Running BOTH types per iteration in the tail phase, their loads in flight together,
+        // was measured: no gain — a lone wave of 64 rays takes 40 us either way.)
+        const bool node_turn = __popcll(m_node) >= PT8_TRI_BIAS * __popcll(m_tri);
+        // The step type is wave-uniform, so each type keeps its record's words in a scope of its own, from the loads to the arithmetic under
+        // one predicate.  (Shared registers r0..r4, loaded in a phase 1 and read in a phase 2 under a second predicate, had to hold a value
+        // on every path: 2 x 20 v_mov 0 per iteration, and a wait for all vector memory at the top of the loop — the finished rays' result
+        // stores included — to order those moves behind the previous iteration's loads.)
+        PT_WLOG(unsigned long long w_b = w_a; unsigned long long w_c = w_a;)
+        if (PT8_LANE_IN(node_turn ? m_node : 0ull)) {
+            if (g_hits == 0u) {
+                if (sp == SB) {
+                    finish(phase);
+                } else {
+                    uint32_t v0, v1;
+                    pop(v0, v1);
+                    g_base = v0;
+                    g_imask = v1 & 0xffu;
+                    g_hits = v1 >> 8;
+                }
+            }
+            if (pm != 0u) { // not finished just above
+                // next child of the group in (slot ^ octant) order
+                uint32_t h = g_hits, t = h & pm;
+                h = t ? t : h;
+                t = h & (pm >> 8);
+                h = t ? t : h;
+                t = h & (pm >> 16);
+                h = t ? t : h; // a single bit now
+                g_hits ^= h;
+                const uint32_t idx = g_base + (uint32_t)__popc(g_imask & (h - 1u));
+                if (g_hits != 0u) push(g_base, g_imask | (g_hits << 8));
+                PT_STAT(++c_nodes; ++c_ray;)
+                const Node8* nd = reinterpret_cast<const Node8*>(node_bytes + idx * (uint32_t)sizeof(Node8));
+                const float4 n0 = nd->n0, n1 = nd->n1, n2 = nd->n2, n3 = nd->n3, n4 = nd->n4;
+                PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
+                const NodeHdr nh = node_hdr(n0, n1);
+                const uint32_t imask = nh.imask;
+                const float ax = nh.sx * r.idir.x, ay = nh.sy * r.idir.y, az = nh.sz * r.idir.z;
+                const float bx = (nh.ox - r.o.x) * r.idir.x, by = (nh.oy - r.o.y) * r.idir.y, bz = (nh.oz - r.o.z) * r.idir.z;
+                // near/far planes per axis follow the direction sign
+                const bool nx = r.idir.x < 0.0f, ny = r.idir.y < 0.0f, nz = r.idir.z < 0.0f;
+                const uint32_t lox0 = __float_as_uint(n2.x), lox1 = __float_as_uint(n2.y), loy0 = __float_as_uint(n2.z), loy1 = __float_as_uint(n2.w);
+                const uint32_t loz0 = __float_as_uint(n3.x), loz1 = __float_as_uint(n3.y), hix0 = __float_as_uint(n3.z), hix1 = __float_as_uint(n3.w);
+                const uint32_t hiy0 = __float_as_uint(n4.x), hiy1 = __float_as_uint(n4.y), hiz0 = __float_as_uint(n4.z), hiz1 = __float_as_uint(n4.w);
+                const uint32_t nearx[2] = {nx ? hix0 : lox0, nx ? hix1 : lox1}, farx[2] = {nx ? lox0 : hix0, nx ? lox1 : hix1};
+                const uint32_t neary[2] = {ny ? hiy0 : loy0, ny ? hiy1 : loy1}, fary[2] = {ny ? loy0 : hiy0, ny ? loy1 : hiy1};
+                const uint32_t nearz[2] = {nz ? hiz0 : loz0, nz ? hiz1 : loz1}, farz[2] = {nz ? loz0 : hiz0, nz ? loz1 : hiz1};
+                // No extra widening of the far plane here: the 8-bit grid (rounded outward from boxes already padded
+                // by 2^-16 of the scene size) is orders of magnitude coarser than the rounding of these products.
+                // (Measured and rejected, twice: two children per v_pk_fma_f32 — 24 packed instead of 48 scalar FMAs, conversions landing in adjacent
+                // registers, no packing moves: traversal 5 % SLOWER in round 3 (0.847 vs 0.807 ms per launch).  The packed FP32 FMA does not issue
+                // at twice the scalar rate here, and the register pairs add 7 spills.)
+                uint32_t miss = 0u; // sign bits of tfar - tnear, slot 7 first (one subtract + one funnel shift per child)
+#pragma unroll
+                for (int s = 7; s >= 0; --s) {
+                    const int w = s >> 2, k = s & 3;
+                    const float tnx = __builtin_fmaf(u8f(nearx[w], k), ax, bx), tfx = __builtin_fmaf(u8f(farx[w], k), ax, bx);
+                    const float tny = __builtin_fmaf(u8f(neary[w], k), ay, by), tfy = __builtin_fmaf(u8f(fary[w], k), ay, by);
+                    const float tnz = __builtin_fmaf(u8f(nearz[w], k), az, bz), tfz = __builtin_fmaf(u8f(farz[w], k), az, bz);
+                    const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
+                    const float tf = fminf(fminf(tfx, tfy), fminf(tfz, best));
+                    miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(tf - tn), 31u);
+                }
+                const uint32_t hm = miss ^ 0xffu; // hit mask in slot positions
+                const uint32_t hits = hm & imask;
+                // triangles of the leaf children that were hit
+                g_base = nh.child_base;
+                g_imask = imask;
+                g_hits = hits;
+                t_base = nh.tri_base;
+                t_bits = nh.lbits;
+                t_mask = leaf_pending(hm, nh.lbits);
+            }
+        }
+        if (PT8_LANE_IN(node_turn ? 0ull : m_tri)) {
+            const uint32_t bit = (uint32_t)__ffs((int)t_mask) - 1u;
+            t_mask &= t_mask - 1u;
+            PT_STAT(++c_tris; ++c_ray;)
+            const uint32_t leaf = leaf_of(t_base, t_bits, bit);
+            const LeafTri* tp = reinterpret_cast<const LeafTri*>(tri_bytes + leaf * (uint32_t)sizeof(LeafTri));
+            const float4 ta = tp->t0, tb = tp->t1, tc = tp->t2;
+            PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
+            float t, det;
+            const v3 v0 = mk3(ta.x, ta.y, ta.z), v1 = mk3(ta.w, tb.x, tb.y), v2 = mk3(tb.z, tb.w, tc.x);
+            if (tri_test_det(r, v0, v1, v2, t, det)) {
+                const int32_t prim = __float_as_int(tc.y);
+                if (MODE == TR_SHADOW_APPLY || MODE == TR_ANY_QUERY || (MODE == TR_UNIFIED && shadow_lane)) {
+                    if (t > tmin && t < tmax && (!a.cull_back || det > 0.0f) && hit_in_box(r, v0, v1, v2, a.bvh.hit_pad, t)) {
+                        bprim = 1;
+                        best = t;
+                        finish(phase);
+                    }
+                } else if (t > tmin && (t < best || (t == best && bprim >= 0 && prim < bprim)) && hit_in_box(r, v0, v1, v2, a.bvh.hit_pad, t)) {
+                    best = t;
+                    bprim = prim;
+                    bleaf = (int32_t)leaf;
+                    if (STEALING) {
+                        const unsigned long long key = local_key();
+                        atomicMin(&s_key[OWNER], key);
+                        if (s_key[OWNER] == key) s_leaf[OWNER] = bleaf;
+                    }
+                }
+            }
+        }
+        PT_STAT(++c_iters; if (a.dbg && lane == 0) {
+            const bool node_step = __popcll(m_node) >= PT8_TRI_BIAS * __popcll(m_tri);
+            c_act += (uint32_t)__popcll(m_node | m_tri);
+            c_exec += (uint32_t)__popcll(node_step ? m_node : m_tri);
+            c_nodeit += node_step ? 1u : 0u;
+        })
+        PT_WLOG(++w_iters; w_c01 += w_b - w_a; w_c12 += w_c - w_b; w_c23 += clock64() - w_c;)
+        act = PT8_VOTE(pm != 0u);
+    };
+
+    // ---------------- the bulk phase: write back, refill from the queue, traverse until fewer than PT8_REFILL lanes hold a ray
     for (;;) {
+        bool exhausted = false; // the queue has nothing left for this wave
         PT_WLOG(const unsigned long long w_p0 = clock64(); ++w_np;)
-        if (unwritten) { // results of the rays that finished since the last pass: all finished lanes at once
+        if (sp < 0) { // results of the rays that finished since the last pass: all finished lanes at once
             write_result(best, is_shadow() ? bprim : bleaf);
-            unwritten = false;
+            sp = 0;
         }
         PT_WLOG(__builtin_amdgcn_s_waitcnt(0); const unsigned long long w_p1 = clock64(); w_cw += w_p1 - w_p0;)
         // ---------------- refill idle lanes
-        const unsigned long long idle = __ballot(!active);
-        if (idle != 0ull && !exhausted) {
+        const unsigned long long idle = ~act;
+        if (idle != 0ull) {
             const uint32_t cnt = (uint32_t)__popcll(idle);
             if (chunk_next == chunk_end) {
                 if (nchunks <= nw) { // every chunk belongs to a wave by its block index: nothing to fetch (and no same-address atomic: 10 ns each, serialised)
@@ -350,7 +512,7 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                 } else {
                     uint32_t c = 0;
                     if (lane == 0) c = atomicAdd(a.work, 1u);
-                    c = __shfl(c, 0) + nw;
+                    c = pt8_uniform(c) + nw;
                     const unsigned long long b0 = (unsigned long long)c * chunk;
                     chunk_next = b0 < n ? (uint32_t)b0 : n;
                     chunk_end = (b0 + chunk < n) ? (uint32_t)(b0 + chunk) : n;
@@ -362,7 +524,7 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
             const uint32_t first = chunk_next;
             chunk_next += take;
             if (chunk_next == chunk_end && nchunks <= nw) exhausted = true; // the wave's only chunk is taken: its spare lanes start stealing at once
-            if (!active && rank < take) {
+            if (PT8_LANE_IN(idle & PT8_VOTE(rank < take))) {
                 const uint32_t gi = first + rank;
                 if (LOCAL) {
                     shadow_lane = (MODE == TR_SHADOW_APPLY) || (MODE == TR_UNIFIED && gi < n2);
@@ -411,218 +573,93 @@ PT_DEV void trace8_wave(const Trace8Args& a, const uint32_t wid, const uint32_t 
                 g_base = 0;
                 g_imask = 1u;
                 g_hits = 1u;
-                active = true;
             }
+            act = PT8_VOTE(pm != 0u);
         }
         PT_WLOG(__builtin_amdgcn_s_waitcnt(0); const unsigned long long w_p2 = clock64(); w_cr += w_p2 - w_p1;)
-        if (exhausted) {
-            if (!stealing) { // the wave took its last chunk: from here on its rays are shared work
-                stealing = true;
-                PT_WLOG(w_tex = wall_clock64();)
-                SET_OWNER(lane);
-                if (active) {
-                    s_leaf[lane] = bleaf; // from here on the leaf index of a ray's best hit lives beside its shared key
-                    s_cnt[lane] = 1u;
-                    s_key[lane] = local_key();
-                }
-                PT8_WAVE_SYNC(); // one wave per workgroup: orders the LDS writes above before other lanes' reads
-            }
-            // ---------------- steal round: idle lane k takes the bottom stack entry of victim k
-            const unsigned long long idle2 = __ballot(!active);
-            const bool victim = active && sp > SB && SB < lds_depth;
-            const unsigned long long vmask = __ballot(victim);
-            if (idle2 != 0ull && vmask != 0ull) {
-                const uint32_t ni = (uint32_t)__popcll(idle2), nv = (uint32_t)__popcll(vmask);
-                const uint32_t m = ni < nv ? ni : nv;
-                const uint32_t vrank = (uint32_t)__popcll(vmask & lt_mask), irank = (uint32_t)__popcll(idle2 & lt_mask);
-                const bool give = victim && vrank < m, take = !active && irank < m;
-                if (give) s_vlane[vrank] = lane;
-                PT8_WAVE_SYNC();
-                const uint32_t v = take ? s_vlane[irank] : lane; // every lane runs the shuffles; only takers keep what they read
-                const float ox = __shfl(r.o.x, (int)v), oy = __shfl(r.o.y, (int)v), oz = __shfl(r.o.z, (int)v);
-                const float dx = __shfl(r.d.x, (int)v), dy = __shfl(r.d.y, (int)v), dz = __shfl(r.d.z, (int)v);
-                const float ix = __shfl(r.idir.x, (int)v), iy = __shfl(r.idir.y, (int)v), iz = __shfl(r.idir.z, (int)v);
-                const float nx_ = __shfl(r.dn.x, (int)v), ny_ = __shfl(r.dn.y, (int)v), nz_ = __shfl(r.dn.z, (int)v);
-                const float vtmin = __shfl(tmin, (int)v), vtmax = __shfl(tmax, (int)v);
-                const uint32_t vpm = __shfl(pm, (int)v), vslot = __shfl(slot, (int)v), vmisc = __shfl(misc, (int)v);
-                const uint32_t vowner = vmisc & 0xffu;
-                const int vsb = (int)(vmisc >> 24);
-                const int vshadow = __shfl((int)shadow_lane, (int)v);
-                if (take) {
-                    r.o = mk3(ox, oy, oz);
-                    r.d = mk3(dx, dy, dz);
-                    r.idir = mk3(ix, iy, iz);
-                    r.dn = mk3(nx_, ny_, nz_);
-                    tmin = vtmin;
-                    tmax = vtmax;
-                    pm = vpm;
-                    slot = vslot;
-                    SET_OWNER(vowner);
-                    shadow_lane = vshadow != 0;
-                    const uint32_t e0 = s_stack[(vsb * 2) * 64 + v], e1 = s_stack[(vsb * 2 + 1) * 64 + v];
-                    g_base = e0;
-                    g_imask = e1 & 0xffu;
-                    g_hits = e1 >> 8;
-                    t_mask = 0;
-                    sp = 0;
-                    SET_SB(0);
-                    // start from the ray's merged state (so that the tie-break "equal t, lower primitive" sees the current holder)
-                    const unsigned long long k = s_key[OWNER];
-                    if (is_shadow()) {
-                        best = tmax;
-                        bprim = 0; // k == 0 (already occluded) is caught by the refresh below
-                    } else {
-                        best = __uint_as_float((uint32_t)(k >> 32));
-                        bprim = (int32_t)(uint32_t)k;
-                    }
-                    atomicAdd(&s_cnt[OWNER], 1u);
-                    active = true;
-                }
-                PT8_WAVE_SYNC(); // takers have read the entries before their victims may overwrite those levels
-                if (give) {
-                    const int nsb = SB + 1;
-                    SET_SB(nsb == sp ? 0 : nsb);
-                    if (nsb == sp) sp = 0;
-                }
-            }
-        }
+        if (exhausted || act == 0ull) break; // the wave took its last chunk: it crosses to the stealing phase, here and nowhere else
         PT_WLOG(w_cs += clock64() - w_p2;)
-        unsigned long long act = __ballot(active);
-        if (act == 0ull) break;
-        const uint32_t thresh = exhausted ? 1u : (uint32_t)PT8_REFILL;
-        uint32_t it = 0;
-        // ---------------- traverse
-        do {
-            if (stealing && active) { // pick up what the ray's other workers found
+        do iterate(Pt8Phase<false>()); while ((uint32_t)__popcll(act) >= (uint32_t)PT8_REFILL);
+    }
+
+    // ---------------- the stealing phase: from here on the wave's rays are shared work
+    PT_WLOG(w_tex = wall_clock64();)
+    SET_OWNER(lane);
+    if (PT8_LANE_IN(act)) {
+        s_leaf[lane] = bleaf; // from here on the leaf index of a ray's best hit lives beside its shared key
+        s_cnt[lane] = 1u;
+        s_key[lane] = local_key();
+    }
+    PT8_WAVE_SYNC(); // one wave per workgroup: orders the LDS writes above before other lanes' reads
+    for (;;) {
+        PT_WLOG(const unsigned long long w_s0 = clock64(); ++w_np;)
+        // ---------------- steal round: idle lane k takes the bottom stack entry of victim k
+        const bool active = PT8_LANE_IN(act);
+        const unsigned long long idle2 = ~act;
+        const bool victim = active && sp > SB && SB < lds_depth;
+        const unsigned long long vmask = __ballot(victim);
+        if (idle2 != 0ull && vmask != 0ull) {
+            const uint32_t ni = (uint32_t)__popcll(idle2), nv = (uint32_t)__popcll(vmask);
+            const uint32_t m = ni < nv ? ni : nv;
+            const uint32_t vrank = (uint32_t)__popcll(vmask & lt_mask), irank = (uint32_t)__popcll(idle2 & lt_mask);
+            const bool give = victim && vrank < m, take = !active && irank < m;
+            if (give) s_vlane[vrank] = lane;
+            PT8_WAVE_SYNC();
+            const uint32_t v = take ? s_vlane[irank] : lane; // every lane runs the shuffles; only takers keep what they read
+            const float ox = __shfl(r.o.x, (int)v), oy = __shfl(r.o.y, (int)v), oz = __shfl(r.o.z, (int)v);
+            const float dx = __shfl(r.d.x, (int)v), dy = __shfl(r.d.y, (int)v), dz = __shfl(r.d.z, (int)v);
+            const float ix = __shfl(r.idir.x, (int)v), iy = __shfl(r.idir.y, (int)v), iz = __shfl(r.idir.z, (int)v);
+            const float nx_ = __shfl(r.dn.x, (int)v), ny_ = __shfl(r.dn.y, (int)v), nz_ = __shfl(r.dn.z, (int)v);
+            const float vtmin = __shfl(tmin, (int)v), vtmax = __shfl(tmax, (int)v);
+            const uint32_t vpm = __shfl(pm, (int)v), vslot = __shfl(slot, (int)v), vmisc = __shfl(misc, (int)v);
+            const uint32_t vowner = vmisc & 0xffu;
+            const int vsb = (int)(vmisc >> 24);
+            const int vshadow = __shfl((int)shadow_lane, (int)v);
+            if (take) {
+                r.o = mk3(ox, oy, oz);
+                r.d = mk3(dx, dy, dz);
+                r.idir = mk3(ix, iy, iz);
+                r.dn = mk3(nx_, ny_, nz_);
+                tmin = vtmin;
+                tmax = vtmax;
+                pm = vpm;
+                slot = vslot;
+                SET_OWNER(vowner);
+                shadow_lane = vshadow != 0;
+                const uint32_t e0 = s_stack[(vsb * 2) * 64 + v], e1 = s_stack[(vsb * 2 + 1) * 64 + v];
+                g_base = e0;
+                g_imask = e1 & 0xffu;
+                g_hits = e1 >> 8;
+                t_mask = 0;
+                sp = 0;
+                SET_SB(0);
+                // start from the ray's merged state (so that the tie-break "equal t, lower primitive" sees the current holder)
                 const unsigned long long k = s_key[OWNER];
                 if (is_shadow()) {
-                    if (k == 0ull) finish(); // occluded elsewhere: nothing left to do for this ray
-                } else if (k < local_key()) {
+                    best = tmax;
+                    bprim = 0; // k == 0 (already occluded) is caught by the refresh below
+                } else {
                     best = __uint_as_float((uint32_t)(k >> 32));
                     bprim = (int32_t)(uint32_t)k;
                 }
+                atomicAdd(&s_cnt[OWNER], 1u);
             }
-            PT_WLOG(const unsigned long long w_a = clock64();)
-            const bool want_tri = active && t_mask != 0u;
-            const bool want_node = active && t_mask == 0u; // node step also covers "group empty → pop"
-            const unsigned long long m_tri = __ballot(want_tri), m_node = __ballot(want_node);
-            // One step type per iteration, the one more lanes wait for (biased 2:1 towards triangle steps), so that the two code paths never
-            // run with complementary half-empty masks.  (Running BOTH types per iteration in the tail phase, their loads in flight together,
-            // was measured: no gain — a lone wave of 64 rays takes 40 us either way.)
-            const bool node_turn = __popcll(m_node) >= PT8_TRI_BIAS * __popcll(m_tri);
-            // The step type is wave-uniform, so each type keeps its record's words in a scope of its own, from the loads to the arithmetic under
-            // one predicate.  (Shared registers r0..r4, loaded in a phase 1 and read in a phase 2 under a second predicate, had to hold a value
-            // on every path: 2 x 20 v_mov 0 per iteration, and a wait for all vector memory at the top of the loop — the finished rays' result
-            // stores included — to order those moves behind the previous iteration's loads.)
-            PT_WLOG(unsigned long long w_b = w_a; unsigned long long w_c = w_a;)
-            if (want_node && node_turn) {
-                if (g_hits == 0u) {
-                    if (sp == SB) {
-                        finish();
-                    } else {
-                        uint32_t v0, v1;
-                        pop(v0, v1);
-                        g_base = v0;
-                        g_imask = v1 & 0xffu;
-                        g_hits = v1 >> 8;
-                    }
-                }
-                if (active) {
-                    // next child of the group in (slot ^ octant) order
-                    uint32_t h = g_hits, t = h & pm;
-                    h = t ? t : h;
-                    t = h & (pm >> 8);
-                    h = t ? t : h;
-                    t = h & (pm >> 16);
-                    h = t ? t : h; // a single bit now
-                    g_hits ^= h;
-                    const uint32_t idx = g_base + (uint32_t)__popc(g_imask & (h - 1u));
-                    if (g_hits != 0u) push(g_base, g_imask | (g_hits << 8));
-                    PT_STAT(++c_nodes; ++c_ray;)
-                    const Node8* nd = reinterpret_cast<const Node8*>(node_bytes + idx * (uint32_t)sizeof(Node8));
-                    const float4 n0 = nd->n0, n1 = nd->n1, n2 = nd->n2, n3 = nd->n3, n4 = nd->n4;
-                    PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
-                    const NodeHdr nh = node_hdr(n0, n1);
-                    const uint32_t imask = nh.imask;
-                    const float ax = nh.sx * r.idir.x, ay = nh.sy * r.idir.y, az = nh.sz * r.idir.z;
-                    const float bx = (nh.ox - r.o.x) * r.idir.x, by = (nh.oy - r.o.y) * r.idir.y, bz = (nh.oz - r.o.z) * r.idir.z;
-                    // near/far planes per axis follow the direction sign
-                    const bool nx = r.idir.x < 0.0f, ny = r.idir.y < 0.0f, nz = r.idir.z < 0.0f;
-                    const uint32_t lox0 = __float_as_uint(n2.x), lox1 = __float_as_uint(n2.y), loy0 = __float_as_uint(n2.z), loy1 = __float_as_uint(n2.w);
-                    const uint32_t loz0 = __float_as_uint(n3.x), loz1 = __float_as_uint(n3.y), hix0 = __float_as_uint(n3.z), hix1 = __float_as_uint(n3.w);
-                    const uint32_t hiy0 = __float_as_uint(n4.x), hiy1 = __float_as_uint(n4.y), hiz0 = __float_as_uint(n4.z), hiz1 = __float_as_uint(n4.w);
-                    const uint32_t nearx[2] = {nx ? hix0 : lox0, nx ? hix1 : lox1}, farx[2] = {nx ? lox0 : hix0, nx ? lox1 : hix1};
-                    const uint32_t neary[2] = {ny ? hiy0 : loy0, ny ? hiy1 : loy1}, fary[2] = {ny ? loy0 : hiy0, ny ? loy1 : hiy1};
-                    const uint32_t nearz[2] = {nz ? hiz0 : loz0, nz ? hiz1 : loz1}, farz[2] = {nz ? loz0 : hiz0, nz ? loz1 : hiz1};
-                    // No extra widening of the far plane here: the 8-bit grid (rounded outward from boxes already padded
-                    // by 2^-16 of the scene size) is orders of magnitude coarser than the rounding of these products.
-                    // (Measured and rejected, twice: two children per v_pk_fma_f32 — 24 packed instead of 48 scalar FMAs, conversions landing in adjacent
-                    // registers, no packing moves: traversal 5 % SLOWER in round 3 (0.847 vs 0.807 ms per launch).  The packed FP32 FMA does not issue
-                    // at twice the scalar rate here, and the register pairs add 7 spills.)
-                    uint32_t miss = 0u; // sign bits of tfar - tnear, slot 7 first (one subtract + one funnel shift per child)
-#pragma unroll
-                    for (int s = 7; s >= 0; --s) {
-                        const int w = s >> 2, k = s & 3;
-                        const float tnx = __builtin_fmaf(u8f(nearx[w], k), ax, bx), tfx = __builtin_fmaf(u8f(farx[w], k), ax, bx);
-                        const float tny = __builtin_fmaf(u8f(neary[w], k), ay, by), tfy = __builtin_fmaf(u8f(fary[w], k), ay, by);
-                        const float tnz = __builtin_fmaf(u8f(nearz[w], k), az, bz), tfz = __builtin_fmaf(u8f(farz[w], k), az, bz);
-                        const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
-                        const float tf = fminf(fminf(tfx, tfy), fminf(tfz, best));
-                        miss = __builtin_amdgcn_alignbit(miss, __float_as_uint(tf - tn), 31u);
-                    }
-                    const uint32_t hm = miss ^ 0xffu; // hit mask in slot positions
-                    const uint32_t hits = hm & imask;
-                    // triangles of the leaf children that were hit
-                    g_base = nh.child_base;
-                    g_imask = imask;
-                    g_hits = hits;
-                    t_base = nh.tri_base;
-                    t_bits = nh.lbits;
-                    t_mask = leaf_pending(hm, nh.lbits);
-                }
+            PT8_WAVE_SYNC(); // takers have read the entries before their victims may overwrite those levels
+            if (give) {
+                const int nsb = SB + 1;
+                SET_SB(nsb == sp ? 0 : nsb);
+                if (nsb == sp) sp = 0;
             }
-            if (want_tri && !node_turn) {
-                const uint32_t bit = (uint32_t)__ffs((int)t_mask) - 1u;
-                t_mask &= t_mask - 1u;
-                PT_STAT(++c_tris; ++c_ray;)
-                const uint32_t leaf = leaf_of(t_base, t_bits, bit);
-                const LeafTri* tp = reinterpret_cast<const LeafTri*>(tri_bytes + leaf * (uint32_t)sizeof(LeafTri));
-                const float4 ta = tp->t0, tb = tp->t1, tc = tp->t2;
-                PT_WLOG(w_b = clock64(); __builtin_amdgcn_s_waitcnt(0); w_c = clock64();)
-                float t, det;
-                const v3 v0 = mk3(ta.x, ta.y, ta.z), v1 = mk3(ta.w, tb.x, tb.y), v2 = mk3(tb.z, tb.w, tc.x);
-                if (tri_test_det(r, v0, v1, v2, t, det)) {
-                    const int32_t prim = __float_as_int(tc.y);
-                    if (MODE == TR_SHADOW_APPLY || MODE == TR_ANY_QUERY || (MODE == TR_UNIFIED && shadow_lane)) {
-                        if (t > tmin && t < tmax && (!a.cull_back || det > 0.0f) && hit_in_box(r, v0, v1, v2, a.bvh.hit_pad, t)) {
-                            bprim = 1;
-                            best = t;
-                            finish();
-                        }
-                    } else if (t > tmin && (t < best || (t == best && bprim >= 0 && prim < bprim)) && hit_in_box(r, v0, v1, v2, a.bvh.hit_pad, t)) {
-                        best = t;
-                        bprim = prim;
-                        bleaf = (int32_t)leaf;
-                        if (stealing) {
-                            const unsigned long long key = local_key();
-                            atomicMin(&s_key[OWNER], key);
-                            if (s_key[OWNER] == key) s_leaf[OWNER] = bleaf;
-                        }
-                    }
-                }
-            }
-            PT_STAT(++c_iters; if (a.dbg && lane == 0) {
-                const bool node_step = __popcll(m_node) >= PT8_TRI_BIAS * __popcll(m_tri);
-                c_act += (uint32_t)__popcll(m_node | m_tri);
-                c_exec += (uint32_t)__popcll(node_step ? m_node : m_tri);
-                c_nodeit += node_step ? 1u : 0u;
-            })
-            PT_WLOG(++w_iters; w_c01 += w_b - w_a; w_c12 += w_c - w_b; w_c23 += clock64() - w_c;)
-            act = __ballot(active);
-            ++it;
-            // with idle lanes around, return to the steal round every PT8_STEAL_PERIOD iterations
-            if (stealing && act != ~0ull && it >= (uint32_t)PT8_STEAL_PERIOD) break;
-        } while ((uint32_t)__popcll(act) >= thresh);
+        }
+        PT_WLOG(w_cs += clock64() - w_s0;)
+        act = PT8_VOTE(pm != 0u);
+        if (act == 0ull) break;
+        // the stealing loop: until no lane holds a ray, and with idle lanes around back to the steal round every PT8_STEAL_PERIOD iterations
+        uint32_t it = 0;
+        do {
+            iterate(Pt8Phase<true>());
+            if (++it >= (uint32_t)PT8_STEAL_PERIOD && act != ~0ull) break;
+        } while (act != 0ull);
     }
     PT_STAT(if (a.dbg) {
         atomicAdd(&a.dbg[0], (unsigned long long)c_nodes);
